@@ -401,6 +401,35 @@ def sample_clocks(run_steps):
             "samples": len(busy), "source": "rocm-smi polled during ~1.5 s of the same step replayed right after the timed region"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, peaks, fixes):
+    """--dump-outputs: what the timed region's last step handed its caller, one float32 / float64 array per field as
+    <out_dir>/<name>.npy -- the peak records (windows x pairs) and, on multi-rank jobs, the solve of every capture set.
+    The inputs are seeded, so two builds run with the same arguments can be compared array by array.  Past 64 MB the peak
+    records are cut to a fixed, seeded sample of windows (peak_window_index.npy names them).  Returns the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    if peaks is not None:
+        rows = np.arange(peaks.shape[0])
+        row_bytes = peaks[:1].size * 20                                       # lag (as f64), abs_corr (f32), corr (f64)
+        if peaks.shape[0] * row_bytes > DUMP_LIMIT_BYTES:
+            rows = np.sort(np.random.default_rng(SEED_BASE).choice(peaks.shape[0], DUMP_LIMIT_BYTES // (row_bytes + 8), replace=False))
+            arrays["peak_window_index"] = rows.astype(np.float64)
+        arrays["peak_lag"] = peaks["lag"][rows].astype(np.float64)
+        arrays["peak_abs_corr"] = peaks["abs_corr"][rows].astype(np.float32)
+        arrays["peak_corr"] = peaks["corr"][rows].astype(np.float64)
+    if fixes:
+        arrays["solve_status"] = np.array([float(f[0]) for f in fixes])
+        arrays["solve_lat_lon"] = np.array([[float(f[1][0]), float(f[1][1])] for f in fixes])
+        arrays["solve_median_target_lags"] = np.array([np.asarray(f[3], dtype=np.float64) for f in fixes])
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def run_job(args, env, cfg_name, scaling, sim, steps, warmup, full):
     """one job (configuration + sharding mode) on the process group `env`: captures, warm-up, timed region; `full`: also the
     per-kernel table, the roofline object, the graph-replay leg, clocks (the contract line's job).  Returns (result dict for
@@ -565,6 +594,10 @@ def run_job(args, env, cfg_name, scaling, sim, steps, warmup, full):
             raise BenchCheckFailed("profiling recorded nothing for %s" % dominant)
     timed_peaks = None if state["peaks"] is None else state["peaks"].copy()     # what the contract's timed region produced
     timed_fix = state["fix"]
+    timed_fixes = state.get("fixes") or ([timed_fix] if timed_fix is not None else [])
+    dumped = None
+    if full and rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, timed_peaks, timed_fixes)
     graph_leg = None
     if full and not args.no_graph_leg:
         step()                                                            # captures the graph
@@ -646,8 +679,10 @@ def run_job(args, env, cfg_name, scaling, sim, steps, warmup, full):
             out["dominant_chosen_by"] = dominant_by
             out.update(roofline_fields(args, env, cfg_name, scaling, sim, table, prof_timed, dominant, timed_mode, table_steps, steps,
                                        dt, samples_per_step, n_fft, n1, n2, n_windows, n_pairs, S, wl, max_lag, graph_leg))
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if timed_fix is not None:
-            fixes = state.get("fixes") or [timed_fix]
+            fixes = timed_fixes
             frc, flle, fit, flag, fref = timed_fix
             sol = {"status": int(frc), "lat": round(float(flle[0]), 6), "lon": round(float(flle[1]), 6), "iterations": int(fit),
                    "solver": "tdoa_solve_surface: weighted Gauss-Newton over all pairs, position held on the ellipsoid at the "
@@ -908,7 +943,7 @@ def launch_ranks(gpus, argv, environ=None, run=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: the config's); ms_per_step = their time / steps")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", choices=sorted(CONFIGS), default=None)
     ap.add_argument("--scaling", choices=("strong", "weak"), default=None)
@@ -929,7 +964,14 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="at --gpus 1: initialise torch.distributed (nccl = RCCL, world size 1) and run the multi-GPU step -- "
                          "tdoa_process(rank, world), all_gather_into_tensor of the peak records, owner merge, solve -- on one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (peak records; the solve on multi-rank jobs) as "
+                         "DIR/<name>.npy in float32 / float64, at most 64 MB, for comparing two builds output by output")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     rc = launch_ranks(args.gpus, sys.argv[1:])
     if rc is not None:

@@ -57,12 +57,57 @@ def test_a_given_master_port_is_kept():
 
 def test_end_to_end_without_a_gpu_the_ranks_start_and_refuse():
     """`python bench.py --gpus 2` here: two ranks come up under torch.distributed.run, each finds no HIP device and says so;
-    the parent hands the launcher's non-zero status on and prints no JSON line"""
+    the parent hands the launcher's non-zero status on and prints no JSON line.  The children see no device on a GPU machine
+    either (a negative ordinal ends the visible list), so there too nothing they start runs on the GPU."""
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
+    env.update(HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
                         "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode != 0
     assert "starting 2 ranks" in r.stderr and "needs an MI355X" in r.stderr
     assert r.stdout.strip() == ""
+
+
+def _peaks(n_windows, n_pairs):
+    import numpy as np
+    import tdoa_amd
+    rng = np.random.default_rng(5)
+    pk = np.zeros((n_windows, n_pairs), dtype=tdoa_amd.capi.PEAK_DTYPE)
+    pk["lag"] = rng.integers(-20000, 20001, pk.shape)
+    pk["abs_corr"] = rng.random(pk.shape)
+    pk["corr"] = rng.standard_normal(pk.shape)
+    return pk
+
+
+def test_dump_outputs_writes_the_peak_records_as_float_arrays(tmp_path):
+    import numpy as np
+    pk = _peaks(99, 3)
+    fixes = [(0, (41.2, -96.0, 400.0), 6, np.array([1.0, -2.0, 3.0]), None)]
+    names = bench.dump_outputs(str(tmp_path / "out"), pk, fixes)
+    assert names == ["peak_abs_corr", "peak_corr", "peak_lag", "solve_lat_lon", "solve_median_target_lags", "solve_status"]
+    got = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["peak_lag"], pk["lag"]) and np.array_equal(got["peak_abs_corr"], pk["abs_corr"])
+    assert np.array_equal(got["peak_corr"], pk["corr"])
+    assert got["solve_lat_lon"].tolist() == [[41.2, -96.0]] and got["solve_median_target_lags"].tolist() == [[1.0, -2.0, 3.0]]
+    assert bench.dump_outputs(str(tmp_path / "single"), pk, []) == ["peak_abs_corr", "peak_corr", "peak_lag"]
+
+
+def test_dump_outputs_past_the_limit_is_a_fixed_sample_of_windows(tmp_path, monkeypatch):
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20 * 3 * 100)
+    pk = _peaks(1000, 3)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), pk, [])
+    sizes = sum(np.load(p).nbytes for p in (tmp_path / "a").iterdir())
+    assert sizes <= bench.DUMP_LIMIT_BYTES
+    rows = np.load(tmp_path / "a" / "peak_window_index.npy").astype(int)
+    assert len(rows) > 50 and np.array_equal(rows, np.load(tmp_path / "b" / "peak_window_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "peak_corr.npy"), pk["corr"][rows])
+
+
+def test_steps_must_be_positive():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr and r.stdout == ""

@@ -58,7 +58,7 @@ def _worker(rank, world, port, q):
     buf = torch.from_numpy(sharding.peaks_as_bytes(local).copy())
     gathered = sharding.all_gather_peaks(buf, dist)
     merged = sharding.merge_sharded(gathered.numpy(), n_windows, 3)
-    dist.barrier()
+    dist.monitored_barrier()        # CPU-only ranks: dist.barrier() probes for an accelerator and so opens the GPU where one exists
     dist.destroy_process_group()
     q.put((rank, merged.tobytes()))
 
@@ -118,7 +118,7 @@ def _worker8(rank, world, port, n_windows, n_pairs, q):
     local = _fake_peaks(n_windows, n_pairs, units)
     gathered = sharding.all_gather_peaks(torch.from_numpy(sharding.peaks_as_bytes(local).copy()), dist)
     merged = sharding.merge_sharded(gathered.numpy(), n_windows, n_pairs)
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
     q.put((rank, len(units), merged.tobytes()))
 
