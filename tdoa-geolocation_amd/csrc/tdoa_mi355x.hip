@@ -47,6 +47,79 @@ struct ProfRec {
     double bytes;
 };
 
+// Path switches (A/B measurements, tests): read from the environment once, when the context is made -- a captured graph
+// must not depend on an environment that changes later --, partly rewritten by tdoa_debug_flags / tdoa_debug_force_generic.
+// kKnobVars says what each one does.  Every field is an element of the step graph's key.
+struct Knobs {
+    bool force_generic = false, use_graph = true, short_lag = true, segment_form = true, segment_quads = true, decimate = true,
+         k1_once = true, pow2_only = false, fused_k1 = true, dec_cols = true, dec_cols_always = false, dec_staged = true,
+         small_fused = true, small_fused_always = false, stg_folded = true, stg_folded_always = false, stg_blocks = true,
+         seg_pack3 = true, memset_nodes = false, xcd_rows = true;
+    int zpad = 256, stg_loaders = 0, stg_rows = 0, stg_cw = 0, stg_bufs = 0, seg_chunks_override = 0, xcd_pair_mb = 48;
+};
+
+// One row per Knobs field: its environment variable (nullptr: none) and how a value is read -- a switch takes `when_one`
+// where the value starts with '1' and the opposite otherwise, a number is clamp(atoi(value)) --, and the tdoa_debug_flags
+// bit that sets a switch (TDOA_DEBUG_*, 0: none) the same way: `when_one` where it is set, the opposite where it is not
+struct KnobVar {
+    const char *env;
+    unsigned int debug_bit;
+    bool Knobs::*flag;
+    bool when_one;
+    int Knobs::*num;
+    int (*clamp)(int);
+};
+constexpr KnobVar off_if(const char *env, bool Knobs::*f, unsigned int bit = 0) { return {env, bit, f, false, nullptr, nullptr}; }
+constexpr KnobVar on_if(const char *env, bool Knobs::*f, unsigned int bit = 0) { return {env, bit, f, true, nullptr, nullptr}; }
+constexpr KnobVar number(const char *env, int Knobs::*f, int (*clamp)(int)) { return {env, 0, nullptr, false, f, clamp}; }
+const KnobVar kKnobVars[] = {
+    on_if(nullptr, &Knobs::force_generic, TDOA_DEBUG_GENERIC_KERNELS),                 // tests: the any-size kernels even at the hot sizes
+    off_if("TDOA_NO_GRAPH", &Knobs::use_graph),            // no whole-step hipGraph
+    off_if("TDOA_NO_SHORT_LAG", &Knobs::short_lag, TDOA_DEBUG_NO_SHORT_LAG),        // the general inverse for short searches
+    off_if("TDOA_NO_SEGMENT_FORM", &Knobs::segment_form, TDOA_DEBUG_NO_SEGMENT_FORM),  // no LDS-resident overlap-save form for short searches
+    off_if("TDOA_NO_SEGMENT_QUADS", &Knobs::segment_quads, TDOA_DEBUG_NO_SEGMENT_QUADS),      // segment form one pair-window at a time (no shared station transforms)
+    off_if("TDOA_NO_DECIMATE", &Knobs::decimate, TDOA_DEBUG_NO_DECIMATE),          // the full inverse even where the decimated one applies
+    off_if("TDOA_NO_K1_ONCE", &Knobs::k1_once, TDOA_DEBUG_NO_K1_ONCE),            // the statistics pre-pass everywhere (no single-look K1, k1_single_look.hpp)
+    on_if("TDOA_POW2_ONLY", &Knobs::pow2_only, TDOA_DEBUG_POW2_ONLY),            // transform lengths are powers of two everywhere (no 5 x 2^22 plan for ten-second windows)
+    // padding (elements) after every 256 rows of a two-sweep plan's TZ: 2 KB; measured on cfg3: 0 -> 107 ms column pass, 128 -> 91,
+    // 256 -> 87, 512 -> 89.  Rows stay 128-byte aligned (the finish sweep reads 16-byte pairs).
+    number("TDOA_ZPAD", &Knobs::zpad, [](int v) { return v < 0 ? 0 : v > 4096 ? 4096 : v & ~15; }),
+    off_if("TDOA_NO_FUSED_K1", &Knobs::fused_k1, TDOA_DEBUG_NO_FUSED_K1),          // K1 always materialises its codes (no discriminator inside the column kernels)
+    off_if("TDOA_NO_DEC_COLS", &Knobs::dec_cols, TDOA_DEBUG_NO_DEC_COLS),          // the tile form of the decimated pair step (k_pair_decimate16; none on 4096 x 4096 plans)
+    on_if("TDOA_DEC_COLS_ALWAYS", &Knobs::dec_cols_always, TDOA_DEBUG_DEC_COLS_ALWAYS),      // the column walk wherever the decimated inverse applies (measurements)
+    off_if("TDOA_NO_DEC_STAGED", &Knobs::dec_staged, TDOA_DEBUG_NO_DEC_STAGED),      // the column walk one pair-window per wave from memory (k_pair_decimate_cols), no LDS staging
+    off_if("TDOA_NO_SMALL_FUSED", &Knobs::small_fused, TDOA_DEBUG_NO_SMALL_FUSED),    // the decimated inverse's small plan as two kernels with V' in memory between them
+    on_if("TDOA_SMALL_FUSED_ALWAYS", &Knobs::small_fused_always, TDOA_DEBUG_SMALL_FUSED_ALWAYS),      // ... fused for any number of pair-windows (tests)
+    off_if("TDOA_NO_STG_FOLDED", &Knobs::stg_folded),      // the staged walk always with a loader wave next to at most fifteen walks
+    on_if("TDOA_STG_FOLDED_ALWAYS", &Knobs::stg_folded_always),      // ... folded wherever the blocked layout applies (tests)
+    off_if("TDOA_NO_STG_BLOCKS", &Knobs::stg_blocks),      // the staged walk reads row-major spectra on every plan
+    // loader waves per workgroup of k_pair_decimate_staged, rows per phase, at most n walks (compute waves) per workgroup, phases
+    // in the LDS ring (0: the library's choice)
+    number("TDOA_DEC_STAGED_LOADERS", &Knobs::stg_loaders, [](int v) { return std::max(0, std::min(4, v)); }),
+    number("TDOA_DEC_STAGED_ROWS", &Knobs::stg_rows, [](int v) { return v == 8 || v == 4 || v == 2 ? v : 0; }),
+    number("TDOA_DEC_STAGED_CW", &Knobs::stg_cw, [](int v) { return std::max(0, std::min(15, v)); }),
+    number("TDOA_DEC_STAGED_BUFS", &Knobs::stg_bufs, [](int v) { return std::max(0, std::min(16, v)); }),
+    off_if("TDOA_NO_SEG_PACK3", &Knobs::seg_pack3, TDOA_DEBUG_NO_SEG_PACK3),        // the segment form reads int32 code rows (round 3's layout)
+    number("TDOA_SEG_CHUNKS", &Knobs::seg_chunks_override, [](int v) { return std::max(0, v); }),      // chunk count of the segment form
+    // probe only: zero the step's accumulators with hipMemsetAsync nodes instead of k_zero_u64 kernel nodes
+    on_if("TDOA_DEBUG_MEMSET_NODES", &Knobs::memset_nodes),
+    off_if("TDOA_NO_XCD_ROWS", &Knobs::xcd_rows, TDOA_DEBUG_NO_XCD_ROWS),          // plain 2-D grid of the pair kernels even with more pairs than stations
+    // k_pair_decimate16 groups a window's pair-windows on one XCD when the window's spectra exceed n MB (round 4, same-box A/B:
+    // cfg4, 8 x 8.4 MB, 11.05 ms grouped against 11.20 -- its pair step pulled 27 GB per step through the fabric for 5.6 GB of
+    // spectra; cfg2, 3 x 8.4 MB: 0.69 ms grouped against 0.66 plain)
+    number("TDOA_XCD_PAIR_MB", &Knobs::xcd_pair_mb, [](int v) { return std::max(0, v); }),
+};
+
+// The staged walk's share-out of a window's pairs for every station count 2 .. 16: the groups of all of them back to back
+// (what ensure_stg_groups uploads) and, per station count, where its groups start, how many there are, the most stations
+// (slots) and the most pairs (max_n) of one group -- tab: next to n_lw loader waves; tab16: the folded form's, up to
+// sixteen walks per workgroup
+struct StgTable { int off = 0, count = 0, slots = 0, max_n = 0; };
+struct StgTables {
+    StgTable tab[kStgMaxStations + 1], tab16[kStgMaxStations + 1];
+    std::vector<StgGroup> groups;
+};
+
 }  // namespace
 
 struct tdoa_ctx {
@@ -78,7 +151,6 @@ struct tdoa_ctx {
     bool capturing = false;
     struct GraphMark { int kernel; double bytes; hipGraphNode_t before, last; hipEvent_t e0, e1; };
     std::vector<GraphMark> graph_marks;
-    bool force_generic = false;   // tests: run the any-size kernels even at the hot sizes
     std::vector<ProfRec> recs;
     std::vector<hipEvent_t> prof_pool;      // events of the profiling path, reused from call to call
     size_t prof_used = 0;                   // handed out since the last prof_collect
@@ -94,36 +166,11 @@ struct tdoa_ctx {
     // whole-step hipGraph of tdoa_process (launch-bound when windows are processed in many groups)
     int n_cu = 256;                         // multiprocessors of this device
     double workspace_limit = 24.0 * 1073741824.0;      // bytes of FFT workspace one launch group may take: a third of the device's memory
-    bool use_graph = true;                  // TDOA_NO_GRAPH=1 at tdoa_create time turns the whole-step hipGraph off
-    bool short_lag = true;                  // TDOA_NO_SHORT_LAG=1 at tdoa_create time forces the general inverse for short searches
-    bool segment_form = true;               // TDOA_NO_SEGMENT_FORM=1: no LDS-resident overlap-save form for short searches
-    bool segment_quads = true;              // TDOA_NO_SEGMENT_QUADS=1: segment form one pair-window at a time (no shared station transforms)
-    bool memset_nodes = false;              // TDOA_DEBUG_MEMSET_NODES=1 (probe only): zero the step's accumulators with
-                                            // hipMemsetAsync nodes instead of k_zero_u64 kernel nodes
-    bool dec_cols = true;                   // TDOA_NO_DEC_COLS=1: the tile form of the decimated pair step (k_pair_decimate16; none on 4096 x 4096 plans)
-    bool dec_cols_always = false;           // TDOA_DEC_COLS_ALWAYS=1: the column walk wherever the decimated inverse applies (measurements)
-    bool dec_staged = true;                 // TDOA_NO_DEC_STAGED=1: the column walk one pair-window per wave from memory (k_pair_decimate_cols), no LDS staging
-    int stg_loaders = 0;                    // TDOA_DEC_STAGED_LOADERS=n: loader waves per workgroup of k_pair_decimate_staged (0: the library's choice)
-    // the staged walk's share-out of a window's pairs to workgroups, for every station count 2 .. 16 (build_stg_groups)
-    struct StgTable { int off = 0, count = 0, slots = 0, max_n = 0; } stg_tab[kStgMaxStations + 1], stg_tab16[kStgMaxStations + 1];      // (..16: the folded form's, sixteen walks per workgroup)
-    bool stg_folded_always = false;         // TDOA_STG_FOLDED_ALWAYS=1: ... wherever the blocked layout applies (tests)
-    bool stg_folded = true;                 // TDOA_NO_STG_FOLDED=1: always a loader wave next to at most fifteen walks
-    DevBuf stg_groups;
+    Knobs knobs;
+    StgTables stg;                          // the staged walk's share-out of a window's pairs (stg_tables)
+    DevBuf stg_groups;                      // ... its groups, uploaded once
     bool stg_ready = false;
-    bool small_fused_always = false;        // TDOA_SMALL_FUSED_ALWAYS=1 / tdoa_debug_flags: ... for any number of pair-windows (tests)
-    bool small_fused = true;                // TDOA_NO_SMALL_FUSED=1: the small plan of the decimated inverse as two kernels with V' in memory between them
-    bool stg_blocks = true;                 // TDOA_NO_STG_BLOCKS=1: the staged walk reads row-major spectra on every plan
-    int stg_cw = 0;                         // TDOA_DEC_STAGED_CW=n: at most n walks (compute waves) per workgroup (0: fifteen -- sixteen waves less the loader)
-    int stg_rows = 0, stg_bufs = 0;         // TDOA_DEC_STAGED_ROWS=2|4|8, TDOA_DEC_STAGED_BUFS=n: rows per phase, phases in the LDS ring (0: the library's choice)
-    bool seg_pack3 = true;                  // TDOA_NO_SEG_PACK3=1: the segment form reads int32 code rows (round 3's layout)
-    int seg_chunks_override = 0;            // TDOA_SEG_CHUNKS=n at tdoa_create time: chunk count of the segment form
     int graph_nodes = 0, graph_edges = 0, graph_roots = 0, graph_memsets = 0;      // structure of the captured step (tdoa_debug_graph_info)
-    bool fused_k1 = true;                   // TDOA_NO_FUSED_K1=1: K1 always materialises its codes (no discriminator inside the column kernels)
-    int zpad = 256;                         // TDOA_ZPAD=n at tdoa_create time: padding (elements) after every 256 rows of a two-sweep plan's TZ:
-                                            // 2 KB; measured on cfg3: 0 -> 107 ms column pass, 128 -> 91, 256 -> 87, 512 -> 89
-    bool decimate = true;                   // TDOA_NO_DECIMATE=1: general form with the full inverse even where the decimated one applies
-    bool pow2_only = false;                 // TDOA_POW2_ONLY=1: transform lengths are powers of two everywhere (no 5 x 2^22 plan for ten-second windows)
-    bool k1_once = true;                    // TDOA_NO_K1_ONCE=1: the statistics pre-pass everywhere (no single-look K1, k1_single_look.hpp)
     bool once_active = false;               // the last step (run_fm_batch, or the replayed graph) took the single-look path: decode multiplies by slot_gain
     bool graph_once = false;                // ... of the step the cached graph holds (a pair call on another path in between must not change what a replay reports)
     DevBuf once_edges, once_tiles, once_fin, slot_gain;
@@ -131,11 +178,6 @@ struct tdoa_ctx {
     DevBuf dec_taps, dec_gain;
     long long dec_nc = 0;
     int dec_reach = -1, dec_T = 0;
-    bool xcd_rows = true;                   // TDOA_NO_XCD_ROWS=1: plain 2-D grid of the pair kernel even with more pairs than stations
-    int xcd_pair_mb = 48;                   // TDOA_XCD_PAIR_MB=n: k_pair_decimate16 groups a window's pair-windows on one XCD when the
-                                            // window's spectra exceed n MB (round 4, same-box A/B: cfg4, 8 x 8.4 MB, 11.05 ms grouped
-                                            // against 11.20 -- its pair step pulled 27 GB per step through the fabric for 5.6 GB of
-                                            // spectra; cfg2, 3 x 8.4 MB: 0.69 ms grouped against 0.66 plain)
     uint64_t alloc_gen = 0;                 // bumped whenever a workspace buffer moves
     std::vector<uint64_t> graph_key;
     hipGraph_t graph = nullptr;
@@ -415,7 +457,7 @@ int *launch_k1(tdoa_ctx *ctx, hipStream_t st, const SWDesc *d_sw, int n_sw, int 
         hipLaunchKernelGGL(k_zero_u64, dim3((unsigned)(((size_t)n_sw + 255) / 256)), dim3(256), 0, st, power, (size_t)n_sw);
         hipLaunchKernelGGL(k_k1_power, per_chunk, dim3(256), 0, st, d_sw, power);
     }
-    zero_partials(st, partials, n_sw, ctx->memset_nodes);
+    zero_partials(st, partials, n_sw, ctx->knobs.memset_nodes);
     const long long items = (long long)((pieces + kDemodItem - 1) / kDemodItem) * n_sw;      // workgroup items
     const int blocks = (int)std::max<long long>(1, std::min<long long>(items, ctx->n_cu));        // one workgroup per CU (128 KB table)
     if (materialise && pack3)
@@ -468,19 +510,29 @@ DecDesign decimation_design(const FftPlan &pl, int reach)
 // (N2 = 2048 -- windows of 4 to 8 s at 2 Msps, N = 2^24 -- joined in round 5: until then that plan ran the full inverse)
 bool cols_only_plan(const FftPlan &pl) { return pl.N1 == 4096 && (pl.N2 == 4096 || pl.N2 == 3072 || pl.N2 == 2560 || pl.N2 == 2048); }
 
-bool decimation_applies(const tdoa_ctx *ctx, const FftPlan &pl, int lag_lo, int lag_hi)
+// largest |lag| an inverse looks at: the searched lags and their refinement neighbours
+int lag_reach(int lag_lo, int lag_hi) { return std::max(lag_hi + 1, -(lag_lo - 1)); }
+
+// column outputs of a pruned inverse that can hold a searched lag: np at the start of the column, nn at its end
+void pruned_outputs(const FftPlan &pl, int lag_lo, int lag_hi, int *np, int *nn)
 {
-    if (!ctx->decimate || ctx->force_generic || pl.N1 != 4096 || (pl.N2 != 256 && pl.N2 != 512 && !cols_only_plan(pl))) return false;
-    if (cols_only_plan(pl) && !(ctx->dec_cols && TDOA_HAVE_DEC_COLS)) return false;
+    const long long n_real = 2 * pl.Nc;
+    *np = lag_hi >= 0 ? (int)((lag_hi / 2) / pl.N1) + 1 : 0;
+    *nn = lag_lo < 0 ? pl.N2 - (int)(((n_real + lag_lo) / 2) / pl.N1) : 0;
+}
+
+bool decimation_applies(const Knobs &k, const FftPlan &pl, int lag_lo, int lag_hi)
+{
+    if (!k.decimate || k.force_generic || pl.N1 != 4096 || (pl.N2 != 256 && pl.N2 != 512 && !cols_only_plan(pl))) return false;
+    if (cols_only_plan(pl) && !(k.dec_cols && TDOA_HAVE_DEC_COLS)) return false;
     {   // the small plan's K5 kernel evaluates the column outputs that can hold a searched lag as direct sums: at most kPruneMax
-        // of them (run_fm_batch's `pruned`; 4096 packed lags per output: search ranges up to ~32 000 lags).  choose_fft_size
+        // of them (FmRoute::pruned; 4096 packed lags per output: search ranges up to ~32 000 lags).  choose_fft_size
         // relies on this function alone -- a 5 x 2^k plan has no other inverse to fall back to.
-        const long long n_real = 2 * pl.Nc;
-        const int np = lag_hi >= 0 ? (int)((lag_hi / 2) / pl.N1) + 1 : 0;
-        const int nn = lag_lo < 0 ? pl.N2 - (int)(((n_real + lag_lo) / 2) / pl.N1) : 0;
+        int np, nn;
+        pruned_outputs(pl, lag_lo, lag_hi, &np, &nn);
         if (np + nn > kPruneMax || lag_hi >= pl.Nc || lag_lo <= -pl.Nc) return false;
     }
-    const int reach = std::max(lag_hi + 1, -(lag_lo - 1));
+    const int reach = lag_reach(lag_lo, lag_hi);
     if (reach <= 4095) return false;                       // the short-lag forms take those
     return decimation_design(pl, reach).ok;
 }
@@ -505,50 +557,12 @@ size_t dec_spectra_offset(const FftPlan &pl, int n_pw)
 {
     return dec_edge_offset(pl, n_pw) + (size_t)n_pw * (size_t)std::max(pl.N2, 4096) * (2 * kDecEdge);
 }
-// stations per window of a UNIFORM batch -- every window carries all the P = S (S - 1) / 2 pairs of its S <= 16 stations,
-// station-windows laid out window by window (process_impl's window-major order), so that a workgroup can name a window's
-// stations sw_base .. sw_base + S - 1 -- else 0
-int uniform_batch_stations(int n_sw, int n_pw, int pairs_per_window)
-{
-    if (pairs_per_window <= 0 || n_pw % pairs_per_window != 0) return 0;
-    const int n_win = n_pw / pairs_per_window;
-    if (n_sw % n_win != 0) return 0;
-    const int st = n_sw / n_win;
-    return st >= 2 && st <= kStgMaxStations && st * (st - 1) / 2 == pairs_per_window ? st : 0;
-}
-// Which form the decimated pair step takes.  The column walk (dec_stream.hpp, dec_staged.hpp) is the only one on the 4096 x 2048
-// and larger plans.  On the others: with the stations' rows staged in LDS it is ahead from three stations on (cfg2, 3 pairs:
-// 0.57 ms against 0.60 for the tile form; cfg4: 3.0 against 5.05; cfg5: 72 against 118); one pair-window per wave from memory
-// (batches the staged walk does not take) where windows carry more pairs than stations; the tile form otherwise -- it asks
-// for a tile's 32 KB at once and a lone pair waits for nothing else.
-bool dec_walks_columns(const tdoa_ctx *ctx, const FftPlan &pl, int n_sw, int n_pw, int pairs_per_window)
-{
-    if (!ctx->dec_cols || !TDOA_HAVE_DEC_COLS) return false;      // (TDOA_DEC_STEPS other than 8 / 12: the walk is not built)
-    if (cols_only_plan(pl) || ctx->dec_cols_always) return true;
-    if (pairs_per_window <= 0 || n_pw % pairs_per_window != 0 || n_sw <= 0) return false;
-    if (ctx->dec_staged && uniform_batch_stations(n_sw, n_pw, pairs_per_window) >= 3) return true;
-    return pairs_per_window > n_sw / (n_pw / pairs_per_window);
-}
-
-// stations per window when the decimated pair step runs as the LDS-staged column walk (dec_staged.hpp), else 0
-int staged_walk_stations(const tdoa_ctx *ctx, const FftPlan &pl, int n_sw, int n_pw, int pairs_per_window)
-{
-    if (!TDOA_HAVE_DEC_COLS || !ctx->dec_staged || !dec_walks_columns(ctx, pl, n_sw, n_pw, pairs_per_window)) return 0;
-    return uniform_batch_stations(n_sw, n_pw, pairs_per_window);
-}
-// ... and whether its spectra are laid out in blocks of 64 columns (out of place, where the tile form keeps its tiles: the
-// plans that have that room; the 4096 x 2048 and larger plans keep their rows in place).  A loader's piece of a row is then
-// followed in memory by its piece of the next row -- 4 KB runs per station and phase instead of 512-byte pieces 32 KB apart.
-bool staged_walk_blocks(const tdoa_ctx *ctx, const FftPlan &pl, int n_sw, int n_pw, int pairs_per_window)
-{
-    return ctx->stg_blocks && !cols_only_plan(pl) && staged_walk_stations(ctx, pl, n_sw, n_pw, pairs_per_window) > 0;
-}
 
 // taps h[t] = sinc(t/16) * kaiser(t), |t| <= T, rounded to f32; gain[m] = 1 / w[m], w[m] = sum_t h[t] cos(2 pi t m / Nc) / 16
 // evaluated from the ROUNDED taps, so the correction is exact for the filter that runs.  No-op when already built.
 int ensure_decimation(tdoa_ctx *ctx, const FftPlan &pl, int lag_lo, int lag_hi)
 {
-    const int reach = std::max(lag_hi + 1, -(lag_lo - 1));
+    const int reach = lag_reach(lag_lo, lag_hi);
     if (ctx->dec_nc == pl.Nc && ctx->dec_reach == reach) return TDOA_OK;
     const long long M = reach / 2 + 2;
     const DecDesign dd = decimation_design(pl, reach);
@@ -592,31 +606,9 @@ int ensure_decimation(tdoa_ctx *ctx, const FftPlan &pl, int lag_lo, int lag_hi)
     return TDOA_OK;
 }
 
-// make every workspace buffer of run_fm_batch large enough (no allocation may happen while a
-// stream capture is open)
-// segment form (search ranges up to 1024 lags, hot row size): 256-lag quarter count of its frames, 0 = does not apply
-int segment_pq(const tdoa_ctx *ctx, const FftPlan &pl, int lag_lo, int lag_hi, int n_pw)
-{
-    // lags lag_lo - 1 .. lag_hi + 1 (refinement neighbours included) must lie in [-P, P], P = 256 seg_pq
-    const int reach = std::max(lag_hi + 1, -(lag_lo - 1));
-    const int pq = reach <= 256 ? 1 : reach <= 512 ? 2 : reach <= 1024 ? 4 : 0;
-    const bool row16 = pl.N1 == 4096 && !ctx->force_generic;
-    return pq && row16 && ctx->short_lag && ctx->segment_form && n_pw > 0 && pl.N2 >= 8 ? pq : 0;
-}
-
-// K1 evaluated inside the forward column kernels (no code array): the plans with a k_fwd_col*_k1 kernel, unless a
-// consumer needs the codes in memory (segment form, k1_smooth, k1_gate) or a window may be shorter than two samples
-bool fused_k1_applies(const tdoa_ctx *ctx, const FftPlan &pl, int lag_lo, int lag_hi, int n_pw, bool allow)
-{
-    if (!allow || !ctx->fused_k1 || ctx->force_generic || ctx->prm.k1_smooth > 1 || ctx->prm.k1_gate) return false;
-    if (pl.N1 != 4096 || !(pl.N2 == 256 || pl.N2 == 512 || pl.N2 == 2048 || pl.N2 == 2560 || pl.N2 == 3072 || pl.N2 == 4096)) return false;
-    return segment_pq(ctx, pl, lag_lo, lag_hi, n_pw) == 0;
-}
-
-// single-look K1 (k1_single_look.hpp): largest |lag| a K5 kernel or the refinement looks at, entries per edge array,
-// tile records per station-window of the fused column kernels
-int once_k_max(int lag_lo, int lag_hi) { return std::max(lag_hi + 1, -(lag_lo - 1)); }
-int once_k1(int lag_lo, int lag_hi) { return (once_k_max(lag_lo, lag_hi) + 1 + 3) & ~3; }
+// single-look K1 (k1_single_look.hpp): entries per edge array (the largest |lag| K = lag_reach, + 1, rounded up), tile
+// records per station-window of the fused column kernels
+int once_k1(int lag_lo, int lag_hi) { return (lag_reach(lag_lo, lag_hi) + 1 + 3) & ~3; }
 int once_tiles_per_sw(const FftPlan &pl)      // records per station-window: one per wave and tile (k1_single_look.hpp)
 {
     return kOnceWavesPerTile * (pl.N2 == 512 ? pl.N1 / 32 : (pl.N1 / 64) * std::max(1, pl.N2 / 256));
@@ -701,26 +693,32 @@ std::vector<StgGroup> build_stg_groups(int S, int cap, bool fill = false)
     return out;
 }
 
+// the staged walk's tables (StgTables) for the knobs that shape them -- ctx->stg, built once by tdoa_create
+StgTables stg_tables(const Knobs &k)
+{
+    StgTables t;
+    const int n_lw = std::max(1, std::min(k.stg_loaders ? k.stg_loaders : 1, 4));
+    const int cap = k.stg_cw > 0 ? std::min(k.stg_cw, kStgMaxWaves - n_lw) : kStgMaxWaves - n_lw;
+    for (int pass = 0; pass < 2; pass++)
+    for (int S = 2; S <= kStgMaxStations; S++) {
+        const std::vector<StgGroup> g = pass ? build_stg_groups(S, k.stg_cw > 0 ? std::min(k.stg_cw + 1, kStgMaxWaves) : kStgMaxWaves, true)
+                                             : build_stg_groups(S, cap);
+        StgTable &e = pass ? t.tab16[S] : t.tab[S];
+        e.off = (int)t.groups.size();
+        e.count = (int)g.size();
+        for (const StgGroup &x : g) {
+            e.slots = std::max(e.slots, __builtin_popcount(x.mask));
+            e.max_n = std::max(e.max_n, (int)x.n);
+        }
+        t.groups.insert(t.groups.end(), g.begin(), g.end());
+    }
+    return t;
+}
+
 int ensure_stg_groups(tdoa_ctx *ctx)
 {
     if (ctx->stg_ready) return TDOA_OK;
-    const int n_lw = std::max(1, std::min(ctx->stg_loaders ? ctx->stg_loaders : 1, 4));
-    const int cap = ctx->stg_cw > 0 ? std::min(ctx->stg_cw, kStgMaxWaves - n_lw) : kStgMaxWaves - n_lw;
-    std::vector<StgGroup> all;
-    for (int pass = 0; pass < 2; pass++)
-    for (int S = 2; S <= kStgMaxStations; S++) {
-        const std::vector<StgGroup> g = pass ? build_stg_groups(S, ctx->stg_cw > 0 ? std::min(ctx->stg_cw + 1, kStgMaxWaves) : kStgMaxWaves, true)
-                                             : build_stg_groups(S, cap);
-        auto &t = pass ? ctx->stg_tab16[S] : ctx->stg_tab[S];
-        t.off = (int)all.size();
-        t.count = (int)g.size();
-        t.slots = t.max_n = 0;
-        for (const StgGroup &x : g) {
-            t.slots = std::max(t.slots, __builtin_popcount(x.mask));
-            t.max_n = std::max(t.max_n, (int)x.n);
-        }
-        all.insert(all.end(), g.begin(), g.end());
-    }
+    const std::vector<StgGroup> &all = ctx->stg.groups;
     int rc;
     if ((rc = ensure(ctx, ctx->stg_groups, sizeof(StgGroup) * all.size()))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(ctx->stg_groups.p, all.data(), sizeof(StgGroup) * all.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -729,486 +727,613 @@ int ensure_stg_groups(tdoa_ctx *ctx)
     return TDOA_OK;
 }
 
-int reserve_fm_batch(tdoa_ctx *ctx, int n_sw, int maxlen, int n_pw, const FftPlan &pl, int lag_lo, int lag_hi,
-                     bool allow_fused_k1)
+// f(std::integral_constant<int, V>{}) for the V of Vs equal to v -- the last one when none is: a launcher's template ladder
+// (every V listed is instantiated)
+template <int V, int... More, typename F>
+void with_int(int v, F &&f)
 {
-    int rc;
-    const long long code_stride = ((long long)maxlen + 15) / 8 * 8;
-    if ((rc = ensure(ctx, ctx->partials, sizeof(StatsPartial) * (size_t)n_sw))) return rc;
-    if ((rc = ensure(ctx, ctx->stats, sizeof(FmStats) * (size_t)n_sw))) return rc;
-    if (!fused_k1_applies(ctx, pl, lag_lo, lag_hi, n_pw, allow_fused_k1)) {
-        if ((rc = ensure(ctx, ctx->codes, sizeof(int) * (size_t)code_stride * n_sw))) return rc;
-        if (ctx->prm.k1_smooth > 1 && (rc = ensure(ctx, ctx->codes_lp, sizeof(int) * (size_t)code_stride * n_sw))) return rc;
-    }
-    if (ctx->prm.k1_gate && (rc = ensure(ctx, ctx->k1_power, sizeof(unsigned long long) * (size_t)n_sw))) return rc;
-    if (ctx->k1_once && n_pw && fused_k1_applies(ctx, pl, lag_lo, lag_hi, n_pw, allow_fused_k1)) {      // single-look K1
-        if ((rc = ensure(ctx, ctx->once_edges, sizeof(float) * 2 * (size_t)once_k1(lag_lo, lag_hi) * n_sw))) return rc;
-        if ((rc = ensure(ctx, ctx->once_tiles, sizeof(OnceTile) * (size_t)once_tiles_per_sw(pl) * n_sw))) return rc;
-        if ((rc = ensure(ctx, ctx->once_fin, sizeof(OnceFin) * (size_t)n_sw))) return rc;
-    }
-    if ((rc = ensure(ctx, ctx->tz, sizeof(float2) * (size_t)pl.Zs * n_sw))) return rc;
-    if (n_pw && decimation_applies(ctx, pl, lag_lo, lag_hi) && (rc = ensure_decimation(ctx, pl, lag_lo, lag_hi))) return rc;
-    if (n_pw && decimation_applies(ctx, pl, lag_lo, lag_hi) && (rc = ensure_stg_groups(ctx))) return rc;
-    size_t v_elems = (size_t)pl.Nc * n_pw;
-    if (n_pw && decimation_applies(ctx, pl, lag_lo, lag_hi))      // G + V' of the pairs, then the tiled spectra of the stations
-        v_elems = std::max(v_elems, dec_spectra_offset(pl, n_pw) + (cols_only_plan(pl) ? 0 : (size_t)pl.Nc * n_sw));
-    if (n_pw && (rc = ensure(ctx, ctx->v, sizeof(float2) * v_elems))) return rc;
-    return TDOA_OK;
+    if constexpr (sizeof...(More) == 0) f(std::integral_constant<int, V>{});
+    else if (v == V) f(std::integral_constant<int, V>{});
+    else with_int<More...>(v, f);
+}
+// f(std::integral_constant<int, V>{}) for every V of Vs
+template <int... Vs, typename F>
+void for_ints(F &&f) { (f(std::integral_constant<int, Vs>{}), ...); }
+template <typename F>
+void with_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
 }
 
-// second sweep of the two-sweep column pass: the G = N2 / 256 rows kb + 256 a of every column, in place
-void launch_col_finish(hipStream_t st, float2 *tz, const FftPlan &pl, int n_sw)
+// ---- mode B: the forms a batch takes (plan_fm_batch), then the launches (run_fm_batch) --------------------------------
+// What the caller knows of a batch of station-windows (sw) and pair-windows (pw).
+struct FmBatchShape {
+    int n_sw = 0, n_pw = 0, maxlen = 0;      // maxlen: longest window
+    int pairs_per_window = 0;        // > 0: every window of the batch carries this many pair-windows (window-major sharding)
+    int stations_per_window = 0;     // > 0: ... and they are all the S (S - 1) / 2 pairs of its S stations, station-windows laid
+                                     // out window by window, pairs in the order (0,1), (0,2), ..., (S-2,S-1) -- process_impl's
+                                     // window-major layout, which the staged walk's groups are built for; 0 otherwise
+    int n_quads = 0;                 // segment form: quads of the batch (two station transforms serve up to four pair-windows)
+    bool allow_fused_k1 = true;      // false: a window may be shorter than two samples
+    bool separate_stats = false;     // K1 and its statistics run over other windows than the transforms (TDOA_LAGS_GO)
+    bool equal_len = false;          // every station-window of the batch has `maxlen` samples
+    bool fine = false;               // sub-sample refinement: the peaks' neighbours are read back
+    int k1_smooth = 0;               // tdoa_params' optional K1 steps (both work on codes in memory)
+    bool k1_gate = false;
+};
+// ... with the context's optional K1 steps filled in
+FmBatchShape batch_shape(const tdoa_ctx *ctx)
 {
-    const dim3 grid(pl.N1 / 512, 256, n_sw), blk(256);
-    if (pl.N2 == 4096) hipLaunchKernelGGL(k_fwd_col_finish<16>, grid, blk, 0, st, tz, pl);
-    else if (pl.N2 == 2560) hipLaunchKernelGGL(k_fwd_col_finish<10>, grid, blk, 0, st, tz, pl);
-    else if (pl.N2 == 3072) hipLaunchKernelGGL(k_fwd_col_finish<12>, grid, blk, 0, st, tz, pl);
-    else hipLaunchKernelGGL(k_fwd_col_finish<8>, grid, blk, 0, st, tz, pl);
+    FmBatchShape b;
+    b.k1_smooth = ctx->prm.k1_smooth;
+    b.k1_gate = ctx->prm.k1_gate != 0;
+    return b;
 }
 
-// ---- mode B core: run stats + forward + inverse + peak over prepared descriptors
-// sw/pw descriptors are already in device memory; maxlen = longest window.
-int run_fm_batch(tdoa_ctx *ctx, const SWDesc *d_sw, int n_sw, int maxlen, const PWDesc *d_pw, int n_pw,
-                 unsigned long long *d_keys, const FftPlan &pl, int lag_lo, int lag_hi, float *lag_dump,
-                 float dump_scale, double sum_len, float *fine_raw = nullptr, int pairs_per_window = 0,
-                 const QuadDesc *d_quads = nullptr, int n_quads = 0, bool allow_fused_k1 = true,
-                 const SWDesc *d_sw_stats = nullptr,      // d_sw_stats: the windows K1 and its statistics run over when the
-                                                          // transforms see truncated ones (TDOA_LAGS_GO); default: d_sw
-                 bool equal_len = false)                  // every station-window of the batch has `maxlen` samples
-{
-    int rc;
-    const int pieces = std::max(1, (maxlen + kDemodPiece - 1) / kDemodPiece);
-    const long long code_stride = ((long long)maxlen + 15) / 8 * 8;      // rows stay 16-byte aligned
-    if ((rc = ensure(ctx, ctx->partials, sizeof(StatsPartial) * (size_t)n_sw))) return rc;
-    if ((rc = ensure(ctx, ctx->stats, sizeof(FmStats) * (size_t)n_sw))) return rc;
-    if ((rc = ensure(ctx, ctx->tz, sizeof(float2) * (size_t)pl.Zs * n_sw))) return rc;
-    if ((rc = reserve_fm_batch(ctx, n_sw, maxlen, n_pw, pl, lag_lo, lag_hi, allow_fused_k1))) return rc;
-    auto *stats = static_cast<FmStats *>(ctx->stats.p);
-    const int *codes = nullptr;
-    auto *tz = static_cast<float2 *>(ctx->tz.p);
-    auto *v = static_cast<float2 *>(ctx->v.p);
-    hipStream_t st = ctx->stream;
-    const double nc8 = 8.0 * (double)pl.Nc;
+enum class ColPass { None, K1_256, K1_512, K1_TwoSweep, C256, TwoSweep, Short16x, Colx, Generic };
+enum class RowPass { None, UnpackBlocks, UnpackInPlace, UnpackTiles, Hot, Generic };
+enum class Inverse { None, Segments, Decimated, ShortLag, Full };
+enum class PairStep { Tiles, Columns, Staged };        // the decimated inverse's pair step
 
-    // hot-size kernels (fft_radix16.hpp) when the plan allows, else the any-size kernels of
-    // fft_stockham.hpp
-    const bool row16 = pl.N1 == 4096 && !ctx->force_generic;
-    const bool col16 = row16 && pl.N2 == 256;
-    const bool col2pass = row16 && (pl.N2 == 4096 || pl.N2 == 2048 || pl.N2 == 2560 || pl.N2 == 3072);   // 256-point sub-transforms + G-point finish (two sweeps)
-    const int col16x = row16 && pl.N2 >= 16 && pl.N2 <= 128 ? pl.N2 / 16 : 0;   // short columns: k_fwd_col16x_c16<F>
-    const int colx = row16 && (pl.N2 == 512 || pl.N2 == 1024) ? pl.N2 / 256 : 0;   // last radix of k_fwd_colx_c16
-    int np = 0, nn = 0;
-    {
-        const long long n_real = 2 * pl.Nc;
-        np = lag_hi >= 0 ? (int)((lag_hi / 2) / pl.N1) + 1 : 0;
-        nn = lag_lo < 0 ? pl.N2 - (int)(((n_real + lag_lo) / 2) / pl.N1) : 0;
-    }
+// the LDS-staged column walk's launch (dec_staged.hpp)
+struct StagedGeometry {
+    bool folded = false, blocked = false;
+    int n_lw = 0, n_cw = 0, slots = 0, groups = 0, off = 0, rows = 0, nb = 0, n_items = 0;
+    unsigned int blocks = 0;
+    size_t lds = 0;
+};
+
+// Bytes of every workspace buffer a batch uses (0: not used)
+struct FmBytes { size_t partials, stats, codes, codes_lp, k1_power, once_edges, once_tiles, once_fin, tz, v; };
+
+// Every choice of a batch's kernels, made once by plan_fm_batch
+struct FmRoute {
+    int status = TDOA_OK;            // != TDOA_OK: the batch cannot run, `error` says why
+    const char *error = nullptr;
+    FftPlan pl{}, ps2{};             // the plan; the small plan of the decimated inverse
+    int lag_lo = 0, lag_hi = 0;
+    FmBatchShape b;
+    long long code_stride = 0;
+    bool row16 = false;              // hot-size kernels (fft_radix16.hpp), else the any-size ones of fft_stockham.hpp
+    ColPass col = ColPass::None;
+    int col_f = 0;                   // Short16x: N2 / 16, Colx: N2 / 256 (template argument)
+    RowPass row = RowPass::None;
+    Inverse inv = Inverse::None;
+    PairStep step = PairStep::Tiles;
+    bool fused_k1 = false, once = false, pruned = false, seg_quads = false, seg_pack3 = false, small_fused = false;
+    bool dec_tables = false;         // the decimated inverse applies: its filter and the staged tables are set up
+    int fk = 0, np = 0, nn = 0, np2 = 0, nn2 = 0, seg_pq = 0, seg_chunks = 0;
+    int xcd_pairs = 0, dec_gp = 0;   // pair-windows of a window on one XCD: k_inv_row_pair4096's 1-D grid, k_pair_decimate16's (0: plain)
+    unsigned int xcd_grid = 0;
+    dim3 dec_grid;
+    StagedGeometry stg;
+    FmBytes bytes{};
+};
+
+FmRoute plan_fm_batch(const Knobs &k, const StgTables &t, int n_cu, const FftPlan &pl, int lag_lo, int lag_hi, const FmBatchShape &b)
+{
+    FmRoute r;
+    r.pl = pl;
+    r.lag_lo = lag_lo;
+    r.lag_hi = lag_hi;
+    r.b = b;
+    const int n_sw = b.n_sw, n_pw = b.n_pw, ppw = b.pairs_per_window, reach = lag_reach(lag_lo, lag_hi);
+    r.code_stride = ((long long)b.maxlen + 15) / 8 * 8;      // rows stay 16-byte aligned
+    r.row16 = pl.N1 == 4096 && !k.force_generic;
+    pruned_outputs(pl, lag_lo, lag_hi, &r.np, &r.nn);
     // short-lag form: the inverse row kernel emits its shares of the few column sums that can hold a lag and V is
     // never written (needs lag_lo - 1 .. lag_hi + 1 inside [-512 fk, 512 fk - 1] for the refinement neighbours)
-    int fk = 0;
-    if (row16 && ctx->short_lag) {
-        const int reach = std::max(lag_hi + 1, -(lag_lo - 1));
-        fk = reach <= 511 ? 1 : reach <= 1023 ? 2 : reach <= 2047 ? 4 : reach <= 4095 ? 8 : 0;
-    }
-    const bool pruned = !ctx->force_generic && pl.N1 >= 128 && pl.N2 <= 4096 && np + nn <= kPruneMax && np + nn <= pl.N2 &&
-                        lag_hi < pl.Nc && lag_lo > -pl.Nc;
-    // decimated inverse (general form on 4096 x 256 and 4096 x 512 plans)
-    const bool decim = pruned && fk == 0 && decimation_applies(ctx, pl, lag_lo, lag_hi) &&
-                       ctx->dec_nc == pl.Nc && ctx->dec_reach == std::max(lag_hi + 1, -(lag_lo - 1));
+    if (r.row16 && k.short_lag) r.fk = reach <= 511 ? 1 : reach <= 1023 ? 2 : reach <= 2047 ? 4 : reach <= 4095 ? 8 : 0;
+    r.pruned = !k.force_generic && pl.N1 >= 128 && pl.N2 <= 4096 && r.np + r.nn <= kPruneMax && r.np + r.nn <= pl.N2 &&
+               lag_hi < pl.Nc && lag_lo > -pl.Nc;
+    r.dec_tables = n_pw > 0 && decimation_applies(k, pl, lag_lo, lag_hi);
     // segment form (search ranges up to 1024 lags): overlap-save over 4096-point frames entirely in LDS; neither the
-    // column pass nor TZ nor V rows are touched.  Its chunk sums and lag array live where the short-lag form keeps its
-    // shares (inside this pair-window's V row), which bounds the chunk count by N2 / 2.
-    int seg_chunks = 0;
-    const int seg_pq = segment_pq(ctx, pl, lag_lo, lag_hi, n_pw);
+    // column pass nor TZ nor V rows are touched.  Lags lag_lo - 1 .. lag_hi + 1 must lie in [-P, P], P = 256 seg_pq.  Its
+    // chunk sums and lag array live where the short-lag form keeps its shares (inside this pair-window's V row), which
+    // bounds the chunk count by N2 / 2.
+    {
+        const int pq = reach <= 256 ? 1 : reach <= 512 ? 2 : reach <= 1024 ? 4 : 0;
+        r.seg_pq = pq && r.row16 && k.short_lag && k.segment_form && n_pw > 0 && pl.N2 >= 8 ? pq : 0;
+    }
     // quads (two station transforms per segment serve up to four pair-windows) when that is fewer transforms than one
     // per pair-window
-    const bool seg_quads = ctx->segment_quads && d_quads && n_quads > 0 && 2 * n_quads < n_pw;
-    if (seg_pq) {
-        const int hop = 4096 - 512 * seg_pq;
-        const int frames = (maxlen + hop - 1) / hop;
-        const int trips = seg_quads ? frames : (frames + 1) / 2;        // the pair kernel takes two frames per trip
-        const int units = seg_quads ? n_quads : n_pw;
+    r.seg_quads = k.segment_quads && b.n_quads > 0 && 2 * b.n_quads < n_pw;
+    if (r.seg_pq) {
+        const int hop = 4096 - 512 * r.seg_pq;
+        const int frames = (b.maxlen + hop - 1) / hop;
+        const int trips = r.seg_quads ? frames : (frames + 1) / 2;        // the pair kernel takes two frames per trip
+        const int units = r.seg_quads ? b.n_quads : n_pw;
         // chunks per unit: the grid runs in rounds of 2 workgroups per CU (64 KB LDS, 128 VGPRs x 512 threads); cost
         // model = rounds x (trips of the longest chunk + 1 for the prologue and the final inverse transform).  The model
         // is flat over a wide range (measured: 10 ... 36 chunks within 2 % on cfg2); among the near-ties take the most
         // chunks -- more, shorter workgroups balance better than one round of long ones (5 chunks: 4 % slower).
         const int c_max = std::max(1, std::min({trips / 8, pl.N2 / 2 - 1, (8192 + units - 1) / units}));
-        const long long slots = 2ll * ctx->n_cu;
+        const long long slots = 2ll * n_cu;
         auto cost = [&](int c) { return (double)(((long long)c * units + slots - 1) / slots) * ((trips + c - 1) / c + 1); };
         double best = cost(1);
         for (int c = 2; c <= c_max; c++) best = std::min(best, cost(c));
         for (int c = 1; c <= c_max; c++)
-            if (cost(c) <= 1.03 * best) seg_chunks = c;
-        if (ctx->seg_chunks_override > 0) seg_chunks = std::max(1, std::min({ctx->seg_chunks_override, trips, pl.N2 / 2 - 1}));
+            if (cost(c) <= 1.03 * best) r.seg_chunks = c;
+        if (k.seg_chunks_override > 0) r.seg_chunks = std::max(1, std::min({k.seg_chunks_override, trips, pl.N2 / 2 - 1}));
     }
     // its code rows at 3 bytes per code (round 4; the gate and the smoother work on int32 rows)
-    const bool seg_pack3 = seg_chunks > 0 && ctx->seg_pack3 && !ctx->prm.k1_gate && ctx->prm.k1_smooth <= 1;
-    const bool fused_k1 = fused_k1_applies(ctx, pl, lag_lo, lag_hi, n_pw, allow_fused_k1);
+    r.seg_pack3 = r.seg_chunks > 0 && k.seg_pack3 && !b.k1_gate && b.k1_smooth <= 1;
+    // K1 evaluated inside the forward column kernels (no code array): the plans with a k_fwd_col*_k1 kernel, unless a
+    // consumer needs the codes in memory (segment form, k1_smooth, k1_gate) or a window may be shorter than two samples
+    r.fused_k1 = b.allow_fused_k1 && k.fused_k1 && !k.force_generic && b.k1_smooth <= 1 && !b.k1_gate && pl.N1 == 4096 &&
+                 (pl.N2 == 256 || pl.N2 == 512 || pl.N2 == 2048 || pl.N2 == 2560 || pl.N2 == 3072 || pl.N2 == 4096) && r.seg_pq == 0;
     // single-look K1 (k1_single_look.hpp): no statistics pre-pass.  Needs windows of one length, the peak picked by
     // k_small_col_peak or a pruned column kernel, and head / tail runs of K samples that do not meet.
-    const int once_kmax = once_k_max(lag_lo, lag_hi), once_n1 = once_k1(lag_lo, lag_hi);
-    const bool once = ctx->k1_once && fused_k1 && equal_len && !d_sw_stats && n_pw > 0 && !seg_chunks && fk == 0 && pruned &&
-                      once_kmax < maxlen / 2 && once_kmax + 1 <= kOncePiece * kOnceMaxPieces;
-    ctx->once_active = once;
-    OnceCorr oc{};
-    auto *once_tiles = static_cast<OnceTile *>(ctx->once_tiles.p);
-    if (once) {
-        oc.edges = static_cast<const float *>(ctx->once_edges.p);
-        oc.fin = static_cast<const OnceFin *>(ctx->once_fin.p);
-        oc.slot_gain = static_cast<double *>(ctx->slot_gain.p);
-        oc.k1 = once_n1;
-        oc.raw_per_unit = (float)(8.0 * (double)pl.Nc);          // raw = 4 N sum w w, N = 2 Nc
-        oc.k_max = once_kmax;
-        // 4096 samples per window -> the estimates (m0, s0) the column kernels normalise with; then the running sums of the
-        // first and the last K samples of every window (streamed like k_fm_demod, 2 x (K + 1) samples per window)
-        const int pieces = (once_kmax + 1 + kOncePiece - 1) / kOncePiece;
-        ProfScope ps(ctx, TDOA_K_STATS, (2.0 * (2.0 * (once_kmax + 1) + (double)kOnceRuns * (kOnceRun + 1)) + 8.0 * (once_kmax + 1)) * n_sw);
-        hipLaunchKernelGGL(k_once_estimate, dim3(n_sw), dim3(kOnceRuns), 0, st, d_sw, static_cast<const int *>(ctx->k1_direct.p), stats);
-        const int blocks = std::max(1, std::min(2 * n_sw, ctx->n_cu));
-        hipLaunchKernelGGL(k_once_edges, dim3(blocks), dim3(kDemodThreads), kK1DirectBytes, st, d_sw, n_sw,
-                           static_cast<const int *>(ctx->k1_direct.p), stats, static_cast<float *>(ctx->once_edges.p), once_kmax,
-                           once_n1, pieces);
-    } else {
-        // K1: capture bytes -> exact window statistics (fused: nothing else; the column pass evaluates the discriminator
-        // itself) and, materialised, the 24-bit phase codes as int32
-        ProfScope ps(ctx, TDOA_K_STATS, (fused_k1 ? 2.0 : seg_pack3 ? 5.0 : 6.0) * sum_len);
-        codes = launch_k1(ctx, st, d_sw_stats ? d_sw_stats : d_sw, n_sw, maxlen, pieces, code_stride, !fused_k1, seg_pack3);
-    }
-    const size_t lds_col = sizeof(float2) * 2 * (size_t)pl.N2 * pl.C;
-    const size_t lds_row = sizeof(float2) * 2 * (size_t)pl.N1;
-    const size_t lds_row2 = sizeof(float2) * 4 * (size_t)pl.N1;
-    const size_t lds_col16 = sizeof(float2) * 256 * 32;
-    const size_t lds_pair16 = sizeof(float2) * 2 * kRowLds;
-    if (!seg_chunks) {
-        // two-sweep column pass (N2 = 2048, 4096): 8 Nc written, read and written again -- SURVEY's third pass
-        ProfScope ps(ctx, TDOA_K_FWD_COL, (fused_k1 ? 2.0 : 4.0) * sum_len + (col2pass ? 3.0 : 1.0) * nc8 * n_sw);
-        const auto *qtable = static_cast<const int *>(ctx->k1_quad.p);
-#define TDOA_COL256(SUB, ONCE_)                                                                                       \
-    hipLaunchKernelGGL((k_fwd_col256_k1<SUB, ONCE_>), dim3(ctx->n_cu), dim3(1024), kColK1Lds, st, d_sw, qtable, stats, tz, pl,    \
-                       n_sw, ONCE_ ? once_tiles : static_cast<OnceTile *>(nullptr))
-        if (fused_k1 && col16) {
-            if (once) TDOA_COL256(false, true);
-            else TDOA_COL256(false, false);
-        }
-        else if (fused_k1 && col2pass) {
-            if (once) TDOA_COL256(true, true);
-            else TDOA_COL256(true, false);
-#undef TDOA_COL256
-            launch_col_finish(st, tz, pl, n_sw);
-        }
-        else if (fused_k1 && colx == 2) {
-            if (once)
-                hipLaunchKernelGGL(k_fwd_col512_k1<true>, dim3(ctx->n_cu), dim3(1024), kCol512Lds, st, d_sw, qtable, stats, tz, pl,
-                                   n_sw, once_tiles);
-            else
-                hipLaunchKernelGGL(k_fwd_col512_k1<false>, dim3(ctx->n_cu), dim3(1024), kCol512Lds, st, d_sw, qtable, stats, tz, pl,
-                                   n_sw, static_cast<OnceTile *>(nullptr));
-        }
-        else if (col16)
-            hipLaunchKernelGGL(k_fwd_col256_c16<false>, dim3(pl.N1 / 32, n_sw), dim3(512), lds_col16, st, d_sw, codes,
-                               code_stride, stats, tz, pl);
-        else if (col2pass) {
-            hipLaunchKernelGGL(k_fwd_col256_c16<true>, dim3(pl.N1 / 32, n_sw, pl.N2 / 256), dim3(512), lds_col16, st,
-                               d_sw, codes, code_stride, stats, tz, pl);
-            launch_col_finish(st, tz, pl, n_sw);
-        }
-        else if (col16x == 1)
-            hipLaunchKernelGGL(k_fwd_col16x_c16<1>, dim3(pl.N1 / 256, n_sw), dim3(256), 0, st, d_sw, codes, code_stride,
-                               stats, tz, pl);
-        else if (col16x == 2)
-            hipLaunchKernelGGL(k_fwd_col16x_c16<2>, dim3(pl.N1 / 128, n_sw), dim3(256), 0, st, d_sw, codes, code_stride,
-                               stats, tz, pl);
-        else if (col16x == 4)
-            hipLaunchKernelGGL(k_fwd_col16x_c16<4>, dim3(pl.N1 / 64, n_sw), dim3(256), 0, st, d_sw, codes, code_stride,
-                               stats, tz, pl);
-        else if (col16x == 8)
-            hipLaunchKernelGGL(k_fwd_col16x_c16<8>, dim3(pl.N1 / 32, n_sw), dim3(256), 0, st, d_sw, codes, code_stride,
-                               stats, tz, pl);
-        else if (colx == 2)
-            hipLaunchKernelGGL(k_fwd_colx_c16<2>, dim3(pl.N1 / 16, n_sw), dim3(512), lds_col16, st, d_sw, codes,
-                               code_stride, stats, tz, pl);
-        else if (colx == 4)
-            hipLaunchKernelGGL(k_fwd_colx_c16<4>, dim3(pl.N1 / 8, n_sw), dim3(512), lds_col16, st, d_sw, codes,
-                               code_stride, stats, tz, pl);
-        else
-            hipLaunchKernelGGL(k_fwd_col_c16, dim3(pl.N1 / pl.C, n_sw), dim3(256), lds_col, st, d_sw, codes,
-                               code_stride, stats, tz, pl);
-    }
-    if (once) {
-        // the tiles' exact sums -> the window statistics (bit-identical to the pre-pass's), eps and g of every station-window
-        ProfScope ps(ctx, TDOA_K_STATS, sizeof(OnceTile) * (double)once_tiles_per_sw(pl) * n_sw);
-        hipLaunchKernelGGL(k_once_final, dim3(n_sw), dim3(256), 0, st, d_sw, once_tiles, once_tiles_per_sw(pl), stats,
-                           static_cast<OnceFin *>(ctx->once_fin.p), n_sw);
-    }
+    r.once = k.k1_once && r.fused_k1 && b.equal_len && !b.separate_stats && n_pw > 0 && !r.seg_chunks && r.fk == 0 && r.pruned &&
+             reach < b.maxlen / 2 && reach + 1 <= kOncePiece * kOnceMaxPieces;
+    // forward column pass (two sweeps -- 256-point sub-transforms + a G-point finish -- on the 4096 x 2048 and larger plans)
+    const bool two_sweep = pl.N2 == 4096 || pl.N2 == 2048 || pl.N2 == 2560 || pl.N2 == 3072;
+    if (r.seg_chunks) r.col = ColPass::None;
+    else if (r.fused_k1) r.col = pl.N2 == 256 ? ColPass::K1_256 : pl.N2 == 512 ? ColPass::K1_512 : ColPass::K1_TwoSweep;
+    else if (!r.row16) r.col = ColPass::Generic;
+    else if (pl.N2 == 256) r.col = ColPass::C256;
+    else if (two_sweep) r.col = ColPass::TwoSweep;
+    else if (pl.N2 >= 16 && pl.N2 <= 128) { r.col = ColPass::Short16x; r.col_f = pl.N2 / 16; }      // k_fwd_col16x_c16<F>
+    else if (pl.N2 == 512 || pl.N2 == 1024) { r.col = ColPass::Colx; r.col_f = pl.N2 / 256; }     // last radix of k_fwd_colx_c16
+    else r.col = ColPass::Generic;
     // XCD-aware 1-D grid of the pair kernel when every window of the group carries the same `pairs_per_window` > S pairs
     // (window-major sharding with more pairs than stations): see k_inv_row_pair4096
-    int xcd_pairs = 0;
-    unsigned int xcd_grid = 0;
     // ... or when a window's spectra are too large to wait in the Infinity Cache for their second reader (cfg3: 3 x 134 MB per
     // window, and the plain grid runs ALL rows of one pair-window before the next: 62 ms against 73-75 for its pair-row pass;
     // one workgroup running a group's pair-windows one after the other measured 67)
-    if (row16 && ctx->xcd_rows && pairs_per_window > 0 && n_pw % pairs_per_window == 0 && n_sw > 0 && pl.N2 > 2) {
-        const int stations = n_sw / (n_pw / pairs_per_window);
-        if (pairs_per_window > stations ||
-            (pairs_per_window > 1 && (size_t)stations * (size_t)pl.Nc * sizeof(float2) > ((size_t)64 << 20))) {
-            const long long groups = (long long)(n_pw / pairs_per_window) * (pl.N2 / 2 - 1);
-            const long long blocks = (groups + 7) / 8 * 8 * pairs_per_window;
-            if (blocks < (1ll << 31)) { xcd_pairs = pairs_per_window; xcd_grid = (unsigned int)blocks; }
+    const bool uniform = ppw > 0 && n_pw % ppw == 0 && n_sw > 0;
+    if (r.row16 && k.xcd_rows && uniform && pl.N2 > 2) {
+        const int stations = n_sw / (n_pw / ppw);
+        if (ppw > stations || (ppw > 1 && (size_t)stations * (size_t)pl.Nc * sizeof(float2) > ((size_t)64 << 20))) {
+            const long long groups = (long long)(n_pw / ppw) * (pl.N2 / 2 - 1);
+            const long long blocks = (groups + 7) / 8 * 8 * ppw;
+            if (blocks < (1ll << 31)) { r.xcd_pairs = ppw; r.xcd_grid = (unsigned int)blocks; }
         }
     }
-    if (!seg_chunks) {
-        ProfScope ps(ctx, TDOA_K_FWD_ROW, 2.0 * nc8 * n_sw);
-        if (row16 && decim && staged_walk_blocks(ctx, pl, n_sw, n_pw, pairs_per_window))     // unpacked spectra in blocks of 64 columns (k_pair_decimate_staged)
-            hipLaunchKernelGGL(k_fwd_row4096_unpack<false>, dim3(pl.N2 / 2, n_sw), dim3(512), sizeof(float2) * 2 * kRowLds, st, tz, pl,
-                               v + dec_spectra_offset(pl, n_pw), fused_k1 && (col16 || colx == 2), kStgBlockCols);
-        else if (row16 && decim && dec_walks_columns(ctx, pl, n_sw, n_pw, pairs_per_window))     // unpacked spectra back into their rows (k_pair_decimate_cols walks the columns)
-            hipLaunchKernelGGL(k_fwd_row4096_unpack<true>, dim3(pl.N2 / 2, n_sw), dim3(512), sizeof(float2) * 2 * kRowLds, st, tz, pl,
-                               tz, fused_k1 && (col16 || colx == 2), 0);
-        else if (row16 && decim)     // unpacked spectra in COLS-column tiles behind G and V' in the V workspace (k_pair_decimate16 streams them)
-            hipLaunchKernelGGL(k_fwd_row4096_unpack<false>, dim3(pl.N2 / 2, n_sw), dim3(512), sizeof(float2) * 2 * kRowLds, st, tz, pl,
-                               v + dec_spectra_offset(pl, n_pw), fused_k1 && (col16 || colx == 2), 0);
-        else if (row16)
-            hipLaunchKernelGGL(k_fwd_row4096, dim3(pl.N2, n_sw), dim3(256), 0, st, tz, pl, fused_k1 && (col16 || colx == 2));
-        else
-            hipLaunchKernelGGL(k_fwd_row, dim3(pl.N2, n_sw), dim3(256), lds_row, st, tz, pl);
-    }
-    if (n_pw && seg_chunks) {
-        const int hop = 4096 - 512 * seg_pq;
-        const double frames = (double)((maxlen + hop - 1) / hop);
-        const float mul = (float)(4.0 * 2.0 * (double)pl.Nc / 4096.0);          // 4 N / M
-        const size_t lds_seg = sizeof(float2) * 2 * kRow8Lds;
-        const double code_bytes = seg_pack3 ? 3.0 : 4.0;
-#define TDOA_SEGMENTS_AS(PQ, PACK)                                                                                   \
-    do {                                                                                                             \
-        if (seg_quads) {                                                                                             \
-            ProfScope ps(ctx, TDOA_K_INV_ROW, 4.0 * code_bytes * 4096.0 * frames * n_quads);  /* four frames of codes */ \
-            hipLaunchKernelGGL((k_xcorr_segments_quad<PQ, PACK>), dim3(seg_chunks, n_quads), dim3(512), lds_seg, st, d_sw, \
-                               d_quads, codes, code_stride, stats, v, pl, seg_chunks);                               \
-        } else {                                                                                                     \
-            ProfScope ps(ctx, TDOA_K_INV_ROW, 2.0 * code_bytes * 4096.0 * frames * n_pw);   /* two frames of codes */  \
-            hipLaunchKernelGGL((k_xcorr_segments<PQ, PACK>), dim3(seg_chunks, n_pw), dim3(512), lds_seg, st, d_sw, d_pw, codes, \
-                               code_stride, stats, v, pl, seg_chunks);                                               \
-        }                                                                                                            \
-    } while (0)
-#define TDOA_SEGMENTS(PQ)                                                                                            \
-    do {                                                                                                             \
-        if (seg_pack3) TDOA_SEGMENTS_AS(PQ, true);                                                                   \
-        else TDOA_SEGMENTS_AS(PQ, false);                                                                            \
-        {                                                                                                            \
-            ProfScope ps(ctx, TDOA_K_INV_COL, 4.0 * 512.0 * PQ * (seg_chunks + 1) * n_pw);                            \
-            hipLaunchKernelGGL(k_segments_reduce<PQ>, dim3(2 * PQ + 1, n_pw), dim3(256), 0, st, v, d_keys, d_pw, pl,  \
-                               seg_chunks, mul, lag_lo, lag_hi, lag_dump, dump_scale);                               \
-        }                                                                                                            \
-        if (fine_raw) ctx->prof_last = -1;          /* unscoped launch: the next scope records its own start */     \
-        if (fine_raw)                                                                                                \
-            hipLaunchKernelGGL(k_refine_segments<PQ>, dim3((n_pw + 63) / 64), dim3(64), 0, st, v, d_keys, d_pw, pl,   \
-                               n_pw, fine_raw);                                                                      \
-    } while (0)
-        if (seg_pq == 1) TDOA_SEGMENTS(1);
-        else if (seg_pq == 2) TDOA_SEGMENTS(2);
-        else TDOA_SEGMENTS(4);
-#undef TDOA_SEGMENTS
-#undef TDOA_SEGMENTS_AS
-    } else if (n_pw && decim) {
-        // decimated inverse: K3 + FIR decimation of the pair's spectrum (one read of the two station spectra), then the
-        // R = Nc/16-point inverse on the small plan (rows, pruned column pass with the window divided out, K5)
-        FftPlan ps2;
-        if ((rc = make_plan(2 * (pl.Nc / kDecD), true, &ps2))) return fail(ctx, rc, "decimated plan");
-        const size_t rc_pts = (size_t)(pl.Nc / kDecD);
-        float2 *g = v, *vs = v + rc_pts * (size_t)n_pw;                 // compact: [n_pw][R] each, inside the V workspace
-        int np2 = 0, nn2 = 0;
-        {
-            const long long n_real2 = 2 * ps2.Nc;
-            np2 = lag_hi >= 0 ? (int)((lag_hi / 2) / ps2.N1) + 1 : 0;
-            nn2 = lag_lo < 0 ? ps2.N2 - (int)(((n_real2 + lag_lo) / 2) / ps2.N1) : 0;
-        }
-        {
-            ProfScope ps(ctx, TDOA_K_INV_ROW, 2.0 * nc8 * n_pw + 8.0 * (double)rc_pts * n_pw);      // two spectra read, G written
-            float2 *edges = v + dec_edge_offset(pl, n_pw), *spectra = v + dec_spectra_offset(pl, n_pw);
-            // pair-windows of a window that share station tiles on one XCD (k_pair_decimate16): when the batch is uniform and
-            // a window's spectra are too many to come from on-die memory for their other readers (ctx->xcd_pair_mb: cfg5, 16
-            // stations x 16.8 MB: its step 258 -> 237 ms in round 3; cfg4, 8 x 8.4 MB: -1.3 % since round 4; cfg2: plain grid)
-            int gp = 0;
-            dim3 grid(pl.N2 / 2, n_pw);
-            if (ctx->xcd_rows && pairs_per_window > 1 && n_pw % pairs_per_window == 0 && n_sw > 0 &&
-                (size_t)(n_sw / (n_pw / pairs_per_window)) * (size_t)pl.Nc * sizeof(float2) > ((size_t)ctx->xcd_pair_mb << 20)) {
-                const long long groups = (long long)(n_pw / pairs_per_window) * (pl.N2 / 2);
-                const long long blocks = (groups + 7) / 8 * 8 * pairs_per_window;
-                if (blocks < (1ll << 31)) { gp = pairs_per_window; grid = dim3((unsigned int)blocks); }
+    if (n_pw == 0) r.inv = Inverse::None;
+    else if (r.seg_chunks) r.inv = Inverse::Segments;
+    else if (r.pruned && r.fk == 0 && r.dec_tables) r.inv = Inverse::Decimated;
+    else r.inv = r.fk ? Inverse::ShortLag : Inverse::Full;
+    if (r.inv == Inverse::Decimated) {
+        // Which form the pair step takes.  The column walk (dec_stream.hpp, dec_staged.hpp) is the only one on the 4096 x 2048
+        // and larger plans.  On the others: with the stations' rows staged in LDS it is ahead from three stations on (cfg2, 3
+        // pairs: 0.57 ms against 0.60 for the tile form; cfg4: 3.0 against 5.05; cfg5: 72 against 118); one pair-window per
+        // wave from memory (batches the staged walk does not take) where windows carry more pairs than stations; the tile form
+        // otherwise -- it asks for a tile's 32 KB at once and a lone pair waits for nothing else.
+        const int S = b.stations_per_window;
+        const int staged_s = uniform && S >= 2 && S <= kStgMaxStations && S * (S - 1) / 2 == ppw && n_sw == (n_pw / ppw) * S ? S : 0;
+        bool walks = false;
+        if (k.dec_cols && TDOA_HAVE_DEC_COLS)      // (TDOA_DEC_STEPS other than 8 / 12: the walk is not built)
+            walks = cols_only_plan(pl) || k.dec_cols_always || (uniform && ((k.dec_staged && staged_s >= 3) || ppw > n_sw / (n_pw / ppw)));
+        r.step = !walks ? PairStep::Tiles : k.dec_staged && staged_s ? PairStep::Staged : PairStep::Columns;
+        if (r.step == PairStep::Staged) {
+            // One loader wave, the other waves of at most sixteen walk one pair each; the share-out of the window's pairs comes
+            // from build_stg_groups.  What the geometry is chosen for is the BARRIER: one per phase stops all sixteen waves, and
+            // the pair step of BASELINE config 4 took 4.33 / 3.57 / 3.38 ms with 2 / 4 / 8 rows per phase (the ring's depth
+            // made no difference: 3, 6 or 8 phases of two rows all 4.3 ms) -- so the most rows per phase of which TWO phases
+            // fit the workgroup's share of the LDS: 8 rows up to eight station slots; small workgroups (three pairs: four
+            // waves) leave room for their neighbours on the CU.
+            StagedGeometry &g = r.stg;
+            // spectra in blocks of 64 columns (out of place, where the tile form keeps its tiles: the plans that have that room;
+            // the 4096 x 2048 and larger plans keep their rows in place).  A loader's piece of a row is then followed in memory
+            // by its piece of the next row -- 4 KB runs per station and phase instead of 512-byte pieces 32 KB apart.
+            g.blocked = k.stg_blocks && !cols_only_plan(pl);
+            // the FOLDED form (dec_staged.hpp: no loader wave, up to sixteen walks, the last waves bring one station each): blocked
+            // spectra, a two-phase ring -- where sixteen walks per workgroup make FEWER workgroups (16 stations: eight groups
+            // instead of nine, cfg5 pair step 73.5 -> 70.2 ms; 8 stations: 16 + 12 walks measured 3.21 ms against 3.12 for
+            // 14 + 14 next to a loader wave, and keep the loader).  Every group's stations need a wave to bring them: no more
+            // station slots than walks (TDOA_DEC_STAGED_CW=2..6 on eight stations, or two stations, would break that).
+            const StgTable &t16 = t.tab16[staged_s];
+            g.folded = g.blocked && k.stg_folded && !k.stg_loaders && k.stg_bufs <= 2 && t16.slots <= 8 && t16.slots <= t16.max_n &&
+                       (t16.count < t.tab[staged_s].count || k.stg_folded_always);
+            const StgTable &tab = g.folded ? t16 : t.tab[staged_s];
+            g.groups = tab.count;
+            g.off = tab.off;
+            g.n_cw = tab.max_n;
+            g.slots = tab.slots;
+            g.n_lw = g.folded ? 0 : std::max(1, std::min(k.stg_loaders ? k.stg_loaders : 1, std::min(4, g.slots)));
+            // (few-station batches wait for memory rather than for the barrier: eight rows per phase there as well, and on the
+            //  blocked plans a third phase in the ring where two workgroups still share a CU's LDS -- cfg2: 0.594 -> 0.571 ms;
+            //  a fourth, or a third on the in-place plans, lost: cfg2 0.63, cfg3 17.8 against 16.3)
+            const int wgs_by_waves = std::max(1, kStgMaxWaves / (g.n_cw + g.n_lw));
+            const int budget = wgs_by_waves >= 2 ? 80 * 1024 : kStgLdsBytes;
+            const int phase = g.slots * 1024;      // bytes of one row of every station
+            g.rows = k.stg_rows ? k.stg_rows : 2 * 8 * phase <= kStgLdsBytes ? 8 : 2 * 4 * phase <= kStgLdsBytes ? 4 : 2;
+            const int per_phase = g.n_lw ? g.rows * ((g.slots + g.n_lw - 1) / g.n_lw) : g.rows;
+            if (g.rows * phase * 2 > kStgLdsBytes) {
+                r.status = TDOA_ERR_INVALID;
+                r.error = "TDOA_DEC_STAGED_ROWS: two phases do not fit the LDS ring";
             }
-            // W_N^DK, DK = N2 / 8 bins between a thread's consecutive elements of a tile (N = 2 Nc)
-            const double ang = -2.0 * M_PI * (double)(pl.N2 / 8) / (2.0 * (double)pl.Nc);
-            const float2 rot = make_float2((float)std::cos(ang), (float)std::sin(ang));
-            const int stg_s = staged_walk_stations(ctx, pl, n_sw, n_pw, pairs_per_window);
-            const bool stg_blk = staged_walk_blocks(ctx, pl, n_sw, n_pw, pairs_per_window);
-            if (dec_walks_columns(ctx, pl, n_sw, n_pw, pairs_per_window) && stg_s) {
-#if TDOA_HAVE_DEC_COLS
-                // One loader wave, the other waves of at most sixteen walk one pair each; the share-out of the window's pairs comes
-                // from build_stg_groups.  What the geometry is chosen for is the BARRIER: one per phase stops all sixteen waves, and
-                // the pair step of BASELINE config 4 took 4.33 / 3.57 / 3.38 ms with 2 / 4 / 8 rows per phase (the ring's depth
-                // made no difference: 3, 6 or 8 phases of two rows all 4.3 ms) -- so the most rows per phase of which TWO phases
-                // fit the workgroup's share of the LDS: 8 rows up to eight station slots; small workgroups (three pairs: four
-                // waves) leave room for their neighbours on the CU.
-                const int P = pairs_per_window, n_win = n_pw / P;
-                // the FOLDED form (dec_staged.hpp: no loader wave, up to sixteen walks, the last waves bring one station each): blocked
-                // spectra, a two-phase ring -- where sixteen walks per workgroup make FEWER workgroups (16 stations: eight groups
-                // instead of nine, cfg5 pair step 73.5 -> 70.2 ms; 8 stations: 16 + 12 walks measured 3.21 ms against 3.12 for
-                // 14 + 14 next to a loader wave, and keep the loader)
-                const bool folded = stg_blk && ctx->stg_folded && !ctx->stg_loaders && ctx->stg_bufs <= 2 && ctx->stg_tab16[stg_s].slots <= 8 &&
-                                    (ctx->stg_tab16[stg_s].count < ctx->stg_tab[stg_s].count || ctx->stg_folded_always);
-                const auto &tab = folded ? ctx->stg_tab16[stg_s] : ctx->stg_tab[stg_s];
-                const int groups = tab.count, n_cw = tab.max_n, slots = tab.slots;
-                const int n_lw = folded ? 0 : std::max(1, std::min(ctx->stg_loaders ? ctx->stg_loaders : 1, std::min(4, slots)));
-                // (few-station batches wait for memory rather than for the barrier: eight rows per phase there as well, and on the
-                //  blocked plans a third phase in the ring where two workgroups still share a CU's LDS -- cfg2: 0.594 -> 0.571 ms;
-                //  a fourth, or a third on the in-place plans, lost: cfg2 0.63, cfg3 17.8 against 16.3)
-                const int wgs_by_waves = std::max(1, kStgMaxWaves / (n_cw + n_lw));
-                const int budget = wgs_by_waves >= 2 ? 80 * 1024 : kStgLdsBytes;
-                int rows = ctx->stg_rows;
-                if (!rows) rows = 2 * 8 * slots * 1024 <= kStgLdsBytes ? 8 : 2 * 4 * slots * 1024 <= kStgLdsBytes ? 4 : 2;
-                const int per_phase = n_lw ? rows * ((slots + n_lw - 1) / n_lw) : rows;
-                int nb = folded ? 2 : ctx->stg_bufs ? ctx->stg_bufs : stg_blk ? std::max(2, std::min(3, budget / (rows * slots * 1024))) : 2;
-                if (rows * slots * 1024 * 2 > kStgLdsBytes) return fail(ctx, TDOA_ERR_INVALID, "TDOA_DEC_STAGED_ROWS: two phases do not fit the LDS ring");
-                nb = std::min(nb, kStgLdsBytes / (rows * slots * 1024));
-                nb = std::max(2, std::min(nb, 2 + kStgMaxInFlight / per_phase));
-                const int n_items = n_win * 32;
-                const unsigned int blocks = (unsigned int)((n_items + 7) / 8 * 8) * (unsigned int)groups;
-                const size_t lds = (size_t)nb * rows * slots * 1024;
-                const float *tp = static_cast<const float *>(ctx->dec_taps.p);
-                const StgGroup *gt = static_cast<const StgGroup *>(ctx->stg_groups.p) + tab.off;
-                const dim3 sblock(64 * (n_cw + n_lw));
-#define TDOA_STAGED_R(N2V, RV)                                                                                       \
-    hipLaunchKernelGGL((k_pair_decimate_staged<N2V, RV>), dim3(blocks), sblock, lds, st, d_pw, stg_blk ? spectra : tz, g, edges, pl, tp, gt, \
-                       n_items, P, slots, n_cw, groups, nb, stg_blk ? (long long)pl.Nc : (long long)pl.Zs, (int)stg_blk)
-#define TDOA_STAGED(N2V)                                                                                              \
-    do {                                                                                                              \
-        if (rows == 8) TDOA_STAGED_R(N2V, 8);                                                                         \
-        else if (rows == 4) TDOA_STAGED_R(N2V, 4);                                                                    \
-        else TDOA_STAGED_R(N2V, 2);                                                                                   \
-    } while (0)
-                if (pl.N2 == 256) TDOA_STAGED(256);
-                else if (pl.N2 == 512) TDOA_STAGED(512);
-                else if (pl.N2 == 2048) TDOA_STAGED(2048);
-                else if (pl.N2 == 2560) TDOA_STAGED(2560);
-                else if (pl.N2 == 3072) TDOA_STAGED(3072);
-                else TDOA_STAGED(4096);
-#undef TDOA_STAGED_R
-#undef TDOA_STAGED
-#endif
-            } else if (dec_walks_columns(ctx, pl, n_sw, n_pw, pairs_per_window)) {
-#if TDOA_HAVE_DEC_COLS
-                const dim3 sgrid(32, (unsigned int)((n_pw + kDecWavesPerWg - 1) / kDecWavesPerWg)), sblock(64 * kDecWavesPerWg);
-                const float *tp = static_cast<const float *>(ctx->dec_taps.p);
-                if (pl.N2 == 256) hipLaunchKernelGGL(k_pair_decimate_cols<256>, sgrid, sblock, 0, st, d_pw, tz, g, edges, pl, tp, n_pw);
-                else if (pl.N2 == 512) hipLaunchKernelGGL(k_pair_decimate_cols<512>, sgrid, sblock, 0, st, d_pw, tz, g, edges, pl, tp, n_pw);
-                else if (pl.N2 == 2048) hipLaunchKernelGGL(k_pair_decimate_cols<2048>, sgrid, sblock, 0, st, d_pw, tz, g, edges, pl, tp, n_pw);
-                else if (pl.N2 == 2560) hipLaunchKernelGGL(k_pair_decimate_cols<2560>, sgrid, sblock, 0, st, d_pw, tz, g, edges, pl, tp, n_pw);
-                else if (pl.N2 == 3072) hipLaunchKernelGGL(k_pair_decimate_cols<3072>, sgrid, sblock, 0, st, d_pw, tz, g, edges, pl, tp, n_pw);
-                else hipLaunchKernelGGL(k_pair_decimate_cols<4096>, sgrid, sblock, 0, st, d_pw, tz, g, edges, pl, tp, n_pw);
-#endif
-            } else if (pl.N2 == 256)
-                hipLaunchKernelGGL(k_pair_decimate16<8>, grid, dim3(512), sizeof(float2) * 2 * 16 * kDecPitch, st,
-                                   d_pw, spectra, g, edges, pl, static_cast<const float *>(ctx->dec_taps.p), ps2.N2, gp, n_pw, rot);
-            else
-                hipLaunchKernelGGL(k_pair_decimate16<9>, grid, dim3(512), sizeof(float2) * 2 * 16 * kDecPitch, st,
-                                   d_pw, spectra, g, edges, pl, static_cast<const float *>(ctx->dec_taps.p), ps2.N2, gp, n_pw, rot);
+            g.nb = g.folded ? 2 : k.stg_bufs ? k.stg_bufs : g.blocked ? std::max(2, std::min(3, budget / (g.rows * phase))) : 2;
+            g.nb = std::min(g.nb, kStgLdsBytes / (g.rows * phase));
+            g.nb = std::max(2, std::min(g.nb, 2 + kStgMaxInFlight / per_phase));
+            g.n_items = (n_pw / ppw) * 32;
+            g.blocks = (unsigned int)((g.n_items + 7) / 8 * 8) * (unsigned int)g.groups;
+            g.lds = (size_t)g.nb * g.rows * phase;
         }
-        {
-            ProfScope ps(ctx, TDOA_K_INV_COL, 3.0 * 8.0 * (double)rc_pts * n_pw);
-            const int by_col = dec_walks_columns(ctx, pl, n_sw, n_pw, pairs_per_window) ? 1 : 0;
-            if (ctx->small_fused && np2 == 3 && nn2 == 3 && ps2.odd == 1 && ps2.N1 == 4096 && ps2.N2 >= 8 && (n_pw >= 1024 || ctx->small_fused_always)) {
-                // rows, column sums and K5 in one pass, V' never written (the reference's 20 000 lags on the 4096 x 16 / x 32 small
-                // plans).  One workgroup per pair-window and CU at a time: for batches of a thousand pair-windows and more -- cfg5
-                // (4500 per launch, 32 rows each) 25.2 -> 21.7 ms per step, cfg4 (2772, 16 rows) 1.26 -> 1.24; cfg2's 297 pair-windows
-                // are one round and a tail of such workgroups (0.165 -> 0.253 ms) and keep the two kernels.
-                hipLaunchKernelGGL(k_small_rows_col_peak, dim3(n_pw), dim3(512), sizeof(float2) * 2 * kRow8Lds, st, g,
-                                   v + dec_edge_offset(pl, n_pw), d_keys, d_pw, ps2, pl.N2, by_col, lag_lo, lag_hi, lag_dump, dump_scale,
-                                   static_cast<const float *>(ctx->dec_gain.p), oc);
+        // pair-windows of a window that share station tiles on one XCD (k_pair_decimate16): when the batch is uniform and
+        // a window's spectra are too many to come from on-die memory for their other readers (ctx->xcd_pair_mb: cfg5, 16
+        // stations x 16.8 MB: its step 258 -> 237 ms in round 3; cfg4, 8 x 8.4 MB: -1.3 % since round 4; cfg2: plain grid)
+        r.dec_grid = dim3(pl.N2 / 2, n_pw);
+        if (k.xcd_rows && ppw > 1 && uniform &&
+            (size_t)(n_sw / (n_pw / ppw)) * (size_t)pl.Nc * sizeof(float2) > ((size_t)k.xcd_pair_mb << 20)) {
+            const long long groups = (long long)(n_pw / ppw) * (pl.N2 / 2);
+            const long long blocks = (groups + 7) / 8 * 8 * ppw;
+            if (blocks < (1ll << 31)) { r.dec_gp = ppw; r.dec_grid = dim3((unsigned int)blocks); }
+        }
+        // the R = Nc/16-point inverse on the small plan (rows, pruned column pass with the window divided out, K5)
+        if (int rc = make_plan(2 * (pl.Nc / kDecD), true, &r.ps2)) {
+            r.status = rc;
+            r.error = "decimated plan";
+        } else {
+            pruned_outputs(r.ps2, lag_lo, lag_hi, &r.np2, &r.nn2);
+        }
+        // rows, column sums and K5 in one pass, V' never written (the reference's 20 000 lags on the 4096 x 16 / x 32 small
+        // plans).  One workgroup per pair-window and CU at a time: for batches of a thousand pair-windows and more -- cfg5
+        // (4500 per launch, 32 rows each) 25.2 -> 21.7 ms per step, cfg4 (2772, 16 rows) 1.26 -> 1.24; cfg2's 297 pair-windows
+        // are one round and a tail of such workgroups (0.165 -> 0.253 ms) and keep the two kernels.
+        r.small_fused = k.small_fused && r.np2 == 3 && r.nn2 == 3 && r.ps2.odd == 1 && r.ps2.N1 == 4096 && r.ps2.N2 >= 8 &&
+                        (n_pw >= 1024 || k.small_fused_always);
+    }
+    if (r.seg_chunks) r.row = RowPass::None;
+    else if (!r.row16) r.row = RowPass::Generic;
+    else if (r.inv != Inverse::Decimated) r.row = RowPass::Hot;
+    else if (r.step == PairStep::Staged && r.stg.blocked) r.row = RowPass::UnpackBlocks;     // unpacked spectra in blocks of 64 columns
+    else if (r.step != PairStep::Tiles) r.row = RowPass::UnpackInPlace;     // unpacked spectra back into their rows (the walk reads columns)
+    else r.row = RowPass::UnpackTiles;     // unpacked spectra in COLS-column tiles behind G and V' in the V workspace
+    FmBytes &by = r.bytes;
+    by.partials = sizeof(StatsPartial) * (size_t)n_sw;
+    by.stats = sizeof(FmStats) * (size_t)n_sw;
+    if (!r.fused_k1) {
+        by.codes = sizeof(int) * (size_t)r.code_stride * n_sw;
+        if (b.k1_smooth > 1) by.codes_lp = by.codes;
+    }
+    if (b.k1_gate) by.k1_power = sizeof(unsigned long long) * (size_t)n_sw;
+    if (r.once) {
+        by.once_edges = sizeof(float) * 2 * (size_t)once_k1(lag_lo, lag_hi) * n_sw;
+        by.once_tiles = sizeof(OnceTile) * (size_t)once_tiles_per_sw(pl) * n_sw;
+        by.once_fin = sizeof(OnceFin) * (size_t)n_sw;
+    }
+    by.tz = sizeof(float2) * (size_t)pl.Zs * n_sw;
+    if (n_pw) {
+        size_t v_elems = (size_t)pl.Nc * n_pw;
+        if (r.dec_tables)      // G + V' of the pairs, then the tiled spectra of the stations
+            v_elems = std::max(v_elems, dec_spectra_offset(pl, n_pw) + (cols_only_plan(pl) ? 0 : (size_t)pl.Nc * n_sw));
+        by.v = sizeof(float2) * v_elems;
+    }
+    return r;
+}
+
+// make every workspace buffer of a batch large enough (no allocation may happen while a stream capture is open)
+int reserve_fm_batch(tdoa_ctx *ctx, const FmRoute &r)
+{
+    const FmBytes &by = r.bytes;
+    const std::pair<DevBuf *, size_t> bufs[] = {{&ctx->partials, by.partials}, {&ctx->stats, by.stats}, {&ctx->codes, by.codes},
+                                                {&ctx->codes_lp, by.codes_lp}, {&ctx->k1_power, by.k1_power},
+                                                {&ctx->once_edges, by.once_edges}, {&ctx->once_tiles, by.once_tiles},
+                                                {&ctx->once_fin, by.once_fin}, {&ctx->tz, by.tz}};
+    int rc;
+    for (const auto &x : bufs)
+        if ((rc = ensure(ctx, *x.first, x.second))) return rc;
+    if (r.dec_tables && (rc = ensure_decimation(ctx, r.pl, r.lag_lo, r.lag_hi))) return rc;
+    if (r.dec_tables && (rc = ensure_stg_groups(ctx))) return rc;
+    return ensure(ctx, ctx->v, by.v);
+}
+
+// second sweep of the two-sweep column pass: the G = N2 / 256 rows kb + 256 a of every column, in place
+void launch_col_finish(hipStream_t st, float2 *tz, const FftPlan &pl, int n_sw)
+{
+    with_int<16, 10, 12, 8>(pl.N2 / 256, [&](auto g) {
+        hipLaunchKernelGGL(k_fwd_col_finish<decltype(g)::value>, dim3(pl.N1 / 512, 256, n_sw), dim3(256), 0, st, tz, pl);
+    });
+}
+
+// what the launchers of a batch read and write: the caller's descriptors and outputs, then (run_fm_batch) the workspace
+struct FmBufs {
+    const SWDesc *sw = nullptr;
+    const SWDesc *sw_stats = nullptr;        // FmBatchShape::separate_stats: the windows K1 and its statistics run over
+    const PWDesc *pw = nullptr;
+    const QuadDesc *quads = nullptr;
+    unsigned long long *keys = nullptr;
+    float *lag_dump = nullptr;
+    float dump_scale = 1.0f;
+    double sum_len = 0.0;                    // samples of all station-windows (the profiling scopes' bytes)
+    float *fine_raw = nullptr;               // FmBatchShape::fine: 3 raw neighbours per slot
+    hipStream_t st = nullptr;
+    FmStats *stats = nullptr;
+    float2 *tz = nullptr, *v = nullptr;
+    const int *codes = nullptr;              // K1's codes in memory (nullptr: fused into the column pass)
+    OnceCorr oc{};                           // single-look path: what a K5 kernel needs to correct its candidates
+};
+
+// K1 -- capture bytes -> exact window statistics (fused: nothing else; the column pass evaluates the discriminator itself)
+// and, materialised, the 24-bit phase codes -- or the single-look path's estimates and edge sums.  Returns the codes in
+// memory (nullptr: none).
+const int *launch_stats(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
+{
+    const int n_sw = r.b.n_sw;
+    if (r.once) {
+        // 4096 samples per window -> the estimates (m0, s0) the column kernels normalise with; then the running sums of the
+        // first and the last K samples of every window (streamed like k_fm_demod, 2 x (K + 1) samples per window)
+        const int k_max = lag_reach(r.lag_lo, r.lag_hi), pieces = (k_max + 1 + kOncePiece - 1) / kOncePiece;
+        const auto *table = static_cast<const int *>(ctx->k1_direct.p);
+        ProfScope ps(ctx, TDOA_K_STATS, (2.0 * (2.0 * (k_max + 1) + (double)kOnceRuns * (kOnceRun + 1)) + 8.0 * (k_max + 1)) * n_sw);
+        hipLaunchKernelGGL(k_once_estimate, dim3(n_sw), dim3(kOnceRuns), 0, bf.st, bf.sw, table, bf.stats);
+        hipLaunchKernelGGL(k_once_edges, dim3(std::max(1, std::min(2 * n_sw, ctx->n_cu))), dim3(kDemodThreads), kK1DirectBytes, bf.st, bf.sw,
+                           n_sw, table, bf.stats, static_cast<float *>(ctx->once_edges.p), k_max, bf.oc.k1, pieces);
+        return nullptr;
+    }
+    const int pieces = std::max(1, (r.b.maxlen + kDemodPiece - 1) / kDemodPiece);
+    ProfScope ps(ctx, TDOA_K_STATS, (r.fused_k1 ? 2.0 : r.seg_pack3 ? 5.0 : 6.0) * bf.sum_len);
+    return launch_k1(ctx, bf.st, bf.sw_stats ? bf.sw_stats : bf.sw, n_sw, r.b.maxlen, pieces, r.code_stride, !r.fused_k1, r.seg_pack3);
+}
+
+// forward column pass; on the single-look path then the tiles' exact sums -> the window statistics
+void launch_fwd_cols(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
+{
+    if (r.col == ColPass::None) return;
+    const FftPlan &pl = r.pl;
+    const int n_sw = r.b.n_sw;
+    auto *tiles = r.once ? static_cast<OnceTile *>(ctx->once_tiles.p) : nullptr;
+    const auto *qtable = static_cast<const int *>(ctx->k1_quad.p);
+    const bool two_sweep = r.col == ColPass::K1_TwoSweep || r.col == ColPass::TwoSweep;
+    const size_t lds16 = sizeof(float2) * 256 * 32;
+    {
+        // two-sweep column pass (N2 = 2048, 4096): 8 Nc written, read and written again -- SURVEY's third pass
+        ProfScope ps(ctx, TDOA_K_FWD_COL, (r.fused_k1 ? 2.0 : 4.0) * bf.sum_len + (two_sweep ? 3.0 : 1.0) * (8.0 * (double)pl.Nc) * n_sw);
+        switch (r.col) {
+        case ColPass::K1_256:
+        case ColPass::K1_TwoSweep:
+            with_bool(two_sweep, [&](auto sub) { with_bool(r.once, [&](auto once) {
+                hipLaunchKernelGGL((k_fwd_col256_k1<decltype(sub)::value, decltype(once)::value>), dim3(ctx->n_cu), dim3(1024), kColK1Lds,
+                                   bf.st, bf.sw, qtable, bf.stats, bf.tz, pl, n_sw, tiles);
+            }); });
+            break;
+        case ColPass::K1_512:
+            with_bool(r.once, [&](auto once) {
+                hipLaunchKernelGGL(k_fwd_col512_k1<decltype(once)::value>, dim3(ctx->n_cu), dim3(1024), kCol512Lds, bf.st, bf.sw, qtable,
+                                   bf.stats, bf.tz, pl, n_sw, tiles);
+            });
+            break;
+        case ColPass::C256:
+            hipLaunchKernelGGL(k_fwd_col256_c16<false>, dim3(pl.N1 / 32, n_sw), dim3(512), lds16, bf.st, bf.sw, bf.codes, r.code_stride,
+                               bf.stats, bf.tz, pl);
+            break;
+        case ColPass::TwoSweep:
+            hipLaunchKernelGGL(k_fwd_col256_c16<true>, dim3(pl.N1 / 32, n_sw, pl.N2 / 256), dim3(512), lds16, bf.st, bf.sw, bf.codes,
+                               r.code_stride, bf.stats, bf.tz, pl);
+            break;
+        case ColPass::Short16x:
+            with_int<1, 2, 4, 8>(r.col_f, [&](auto f) {
+                hipLaunchKernelGGL(k_fwd_col16x_c16<decltype(f)::value>, dim3(pl.N1 * decltype(f)::value / 256, n_sw), dim3(256), 0, bf.st,
+                                   bf.sw, bf.codes, r.code_stride, bf.stats, bf.tz, pl);
+            });
+            break;
+        case ColPass::Colx:
+            with_int<2, 4>(r.col_f, [&](auto x) {
+                hipLaunchKernelGGL(k_fwd_colx_c16<decltype(x)::value>, dim3(pl.N1 * decltype(x)::value / 32, n_sw), dim3(512), lds16, bf.st,
+                                   bf.sw, bf.codes, r.code_stride, bf.stats, bf.tz, pl);
+            });
+            break;
+        default:
+            hipLaunchKernelGGL(k_fwd_col_c16, dim3(pl.N1 / pl.C, n_sw), dim3(256), sizeof(float2) * 2 * (size_t)pl.N2 * pl.C, bf.st,
+                               bf.sw, bf.codes, r.code_stride, bf.stats, bf.tz, pl);
+        }
+        if (two_sweep) launch_col_finish(bf.st, bf.tz, pl, n_sw);
+    }
+    if (r.once) {
+        ProfScope ps(ctx, TDOA_K_STATS, sizeof(OnceTile) * (double)once_tiles_per_sw(pl) * n_sw);
+        hipLaunchKernelGGL(k_once_final, dim3(n_sw), dim3(256), 0, bf.st, bf.sw, tiles, once_tiles_per_sw(pl), bf.stats,
+                           static_cast<OnceFin *>(ctx->once_fin.p), n_sw);
+    }
+}
+
+// forward row pass: the spectra in TZ, or unpacked where the decimated pair step reads them
+void launch_fwd_rows(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
+{
+    if (r.row == RowPass::None) return;
+    const FftPlan &pl = r.pl;
+    const int n_sw = r.b.n_sw;
+    float2 *spectra = bf.v + dec_spectra_offset(pl, r.b.n_pw);
+    const bool k1_cols = r.col == ColPass::K1_256 || r.col == ColPass::K1_512;
+    const dim3 half(pl.N2 / 2, n_sw);
+    const size_t lds = sizeof(float2) * 2 * kRowLds;
+    ProfScope ps(ctx, TDOA_K_FWD_ROW, 2.0 * (8.0 * (double)pl.Nc) * n_sw);
+    if (r.row == RowPass::UnpackBlocks)
+        hipLaunchKernelGGL(k_fwd_row4096_unpack<false>, half, dim3(512), lds, bf.st, bf.tz, pl, spectra, k1_cols, kStgBlockCols);
+    else if (r.row == RowPass::UnpackInPlace)
+        hipLaunchKernelGGL(k_fwd_row4096_unpack<true>, half, dim3(512), lds, bf.st, bf.tz, pl, bf.tz, k1_cols, 0);
+    else if (r.row == RowPass::UnpackTiles)
+        hipLaunchKernelGGL(k_fwd_row4096_unpack<false>, half, dim3(512), lds, bf.st, bf.tz, pl, spectra, k1_cols, 0);
+    else if (r.row == RowPass::Hot)
+        hipLaunchKernelGGL(k_fwd_row4096, dim3(pl.N2, n_sw), dim3(256), 0, bf.st, bf.tz, pl, k1_cols);
+    else
+        hipLaunchKernelGGL(k_fwd_row, dim3(pl.N2, n_sw), dim3(256), sizeof(float2) * 2 * (size_t)pl.N1, bf.st, bf.tz, pl);
+}
+
+// segment form: the pair (or quad) kernel, the chunk reduction with the peak pick, the refinement's neighbours
+void launch_segments(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
+{
+    const FftPlan &pl = r.pl;
+    const int n_pw = r.b.n_pw, n_quads = r.b.n_quads, chunks = r.seg_chunks, hop = 4096 - 512 * r.seg_pq;
+    const double frames = (double)((r.b.maxlen + hop - 1) / hop), code_bytes = r.seg_pack3 ? 3.0 : 4.0;
+    const float mul = (float)(4.0 * 2.0 * (double)pl.Nc / 4096.0);          // 4 N / M
+    const size_t lds = sizeof(float2) * 2 * kRow8Lds;
+    with_int<1, 2, 4>(r.seg_pq, [&](auto pq) {
+        constexpr int PQ = decltype(pq)::value;
+        with_bool(r.seg_pack3, [&](auto pack) {
+            constexpr bool PACK = decltype(pack)::value;
+            if (r.seg_quads) {
+                ProfScope ps(ctx, TDOA_K_INV_ROW, 4.0 * code_bytes * 4096.0 * frames * n_quads);      // four frames of codes
+                hipLaunchKernelGGL((k_xcorr_segments_quad<PQ, PACK>), dim3(chunks, n_quads), dim3(512), lds, bf.st, bf.sw, bf.quads,
+                                   bf.codes, r.code_stride, bf.stats, bf.v, pl, chunks);
             } else {
-            hipLaunchKernelGGL(k_inv_rows_plain_r8, dim3(ps2.N2 / 2, n_pw), dim3(512), sizeof(float2) * 2 * kRow8Lds, st, g,
-                               v + dec_edge_offset(pl, n_pw), vs, ps2, pl.N2, by_col);
-            if (np2 == 3 && nn2 == 3)          // the reference's 20 000 lags on either small plan
-                hipLaunchKernelGGL((k_small_col_peak<3, 3>), dim3(ps2.N1 / 256, n_pw), dim3(256), 0, st, vs, d_keys, d_pw, ps2, lag_lo,
-                                   lag_hi, np2, nn2, lag_dump, dump_scale, static_cast<const float *>(ctx->dec_gain.p), oc);
-            else
-                hipLaunchKernelGGL((k_small_col_peak<0, 0>), dim3(ps2.N1 / 256, n_pw), dim3(256), 0, st, vs, d_keys, d_pw, ps2, lag_lo,
-                                   lag_hi, np2, nn2, lag_dump, dump_scale, static_cast<const float *>(ctx->dec_gain.p), oc);
+                ProfScope ps(ctx, TDOA_K_INV_ROW, 2.0 * code_bytes * 4096.0 * frames * n_pw);         // two frames of codes
+                hipLaunchKernelGGL((k_xcorr_segments<PQ, PACK>), dim3(chunks, n_pw), dim3(512), lds, bf.st, bf.sw, bf.pw, bf.codes,
+                                   r.code_stride, bf.stats, bf.v, pl, chunks);
             }
-        }
-    } else if (n_pw) {
+        });
         {
-            ProfScope ps(ctx, TDOA_K_INV_ROW, 3.0 * nc8 * n_pw);     // SURVEY's model: two spectra read, V written, per pair
-            if (fk) {
-#define TDOA_PAIR_ROWS(FK)                                                                                           \
-    do {                                                                                                             \
-        if (pl.N2 > 2)                                                                                               \
-            hipLaunchKernelGGL((k_inv_row_pair4096<false, FK>), xcd_pairs ? dim3(xcd_grid) : dim3(pl.N2 / 2 - 1, n_pw), \
-                               dim3(256), lds_pair16, st, d_pw, tz, v, pl, xcd_pairs, n_pw);                         \
-        hipLaunchKernelGGL((k_inv_row_pair4096<true, FK>), dim3(1, n_pw), dim3(256), lds_pair16, st, d_pw, tz, v, pl, \
-                           0, n_pw);                                                                                 \
-    } while (0)
-                if (fk == 1) TDOA_PAIR_ROWS(1);
-                else if (fk == 2) TDOA_PAIR_ROWS(2);
-                else if (fk == 4) TDOA_PAIR_ROWS(4);
-                else TDOA_PAIR_ROWS(8);
-            } else if (row16) {
-                TDOA_PAIR_ROWS(0);
-#undef TDOA_PAIR_ROWS
-            } else {
-                hipLaunchKernelGGL(k_inv_row_pair, dim3(pl.N2 / 2, n_pw), dim3(256), lds_row2, st, d_pw, tz, v, pl);
-            }
+            ProfScope ps(ctx, TDOA_K_INV_COL, 4.0 * 512.0 * PQ * (chunks + 1) * n_pw);
+            hipLaunchKernelGGL(k_segments_reduce<PQ>, dim3(2 * PQ + 1, n_pw), dim3(256), 0, bf.st, bf.v, bf.keys, bf.pw, pl, chunks, mul,
+                               r.lag_lo, r.lag_hi, bf.lag_dump, bf.dump_scale);
         }
-        {
-            ProfScope ps(ctx, TDOA_K_INV_COL, fk ? 8.0 * 256 * fk * pl.N2 * n_pw : nc8 * n_pw);
-            if (fk == 1)
-                hipLaunchKernelGGL(k_fused_reduce<1>, dim3(2, n_pw), dim3(256), 0, st, v, d_keys, d_pw, pl, lag_lo, lag_hi,
-                                   lag_dump, dump_scale);
-            else if (fk == 2)
-                hipLaunchKernelGGL(k_fused_reduce<2>, dim3(4, n_pw), dim3(256), 0, st, v, d_keys, d_pw, pl, lag_lo, lag_hi,
-                                   lag_dump, dump_scale);
-            else if (fk == 4)
-                hipLaunchKernelGGL(k_fused_reduce<4>, dim3(8, n_pw), dim3(256), 0, st, v, d_keys, d_pw, pl, lag_lo, lag_hi,
-                                   lag_dump, dump_scale);
-            else if (fk == 8)
-                hipLaunchKernelGGL(k_fused_reduce<8>, dim3(16, n_pw), dim3(256), 0, st, v, d_keys, d_pw, pl, lag_lo, lag_hi,
-                                   lag_dump, dump_scale);
-            else if (pruned) {
-                const dim3 grid(pl.N1 / 128, n_pw), blk(256);
-                const size_t lds_wtab = sizeof(float2) * (size_t)pl.N2;
-#define TDOA_PRUNED(NP, NN)                                                                                      \
-    hipLaunchKernelGGL((k_inv_col_pruned<NP, NN>), grid, blk, lds_wtab, st, v, d_keys, d_pw, pl, lag_lo, lag_hi, \
-                       lag_dump, dump_scale, oc)
-                const bool fixed = (pl.N2 & 31) == 0;     // the compile-time forms read 32 rows per trip unguarded
-                if (fixed && np == 3 && nn == 3) TDOA_PRUNED(3, 3);
-                else if (fixed && np == 1 && nn == 1) TDOA_PRUNED(1, 1);
-                else if (fixed && np == 2 && nn == 2) TDOA_PRUNED(2, 2);
-                else if (fixed && np == 4 && nn == 4) TDOA_PRUNED(4, 4);
-                else
-                    hipLaunchKernelGGL(k_inv_col_pruned_any, grid, blk, lds_wtab, st, v, d_keys, d_pw, pl, lag_lo, lag_hi, np,
-                                       nn, lag_dump, dump_scale, oc);
-#undef TDOA_PRUNED
-            }
-            else
-                hipLaunchKernelGGL(k_inv_col_peak, dim3(pl.N1 / pl.C, n_pw), dim3(256), lds_col, st, v, d_keys,
-                                   d_pw, pl, lag_lo, lag_hi, lag_dump, dump_scale);
+        if (r.b.fine) {
+            ctx->prof_last = -1;          // unscoped launch: the next scope records its own start
+            hipLaunchKernelGGL(k_refine_segments<PQ>, dim3((n_pw + 63) / 64), dim3(64), 0, bf.st, bf.v, bf.keys, bf.pw, pl, n_pw, bf.fine_raw);
+        }
+    });
+}
+
+// decimated inverse, pair step: K3 + FIR decimation of the pair's spectrum (one read of the two station spectra) into G
+void launch_pair_step(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
+{
+    const FftPlan &pl = r.pl;
+    const int n_pw = r.b.n_pw;
+    float2 *g = bf.v, *edges = bf.v + dec_edge_offset(pl, n_pw), *spectra = bf.v + dec_spectra_offset(pl, n_pw);
+    const auto *taps = static_cast<const float *>(ctx->dec_taps.p);
+    ProfScope ps(ctx, TDOA_K_INV_ROW, 2.0 * (8.0 * (double)pl.Nc) * n_pw + 8.0 * (double)(pl.Nc / kDecD) * n_pw);      // two spectra read, G written
+#if TDOA_HAVE_DEC_COLS
+    if (r.step == PairStep::Staged) {
+        const StagedGeometry &sg = r.stg;
+        const StgGroup *gt = static_cast<const StgGroup *>(ctx->stg_groups.p) + sg.off;
+        with_int<256, 512, 2048, 2560, 3072, 4096>(pl.N2, [&](auto n2) { with_int<8, 4, 2>(sg.rows, [&](auto rows) {
+            hipLaunchKernelGGL((k_pair_decimate_staged<decltype(n2)::value, decltype(rows)::value>), dim3(sg.blocks), dim3(64 * (sg.n_cw + sg.n_lw)),
+                               sg.lds, bf.st, bf.pw, sg.blocked ? spectra : bf.tz, g, edges, pl, taps, gt, sg.n_items, r.b.pairs_per_window,
+                               sg.slots, sg.n_cw, sg.groups, sg.nb, sg.blocked ? (long long)pl.Nc : (long long)pl.Zs, (int)sg.blocked);
+        }); });
+        return;
+    }
+    if (r.step == PairStep::Columns) {
+        const dim3 grid(32, (unsigned int)((n_pw + kDecWavesPerWg - 1) / kDecWavesPerWg)), block(64 * kDecWavesPerWg);
+        with_int<256, 512, 2048, 2560, 3072, 4096>(pl.N2, [&](auto n2) {
+            hipLaunchKernelGGL(k_pair_decimate_cols<decltype(n2)::value>, grid, block, 0, bf.st, bf.pw, bf.tz, g, edges, pl, taps, n_pw);
+        });
+        return;
+    }
+#endif
+    // W_N^DK, DK = N2 / 8 bins between a thread's consecutive elements of a tile (N = 2 Nc)
+    const double ang = -2.0 * M_PI * (double)(pl.N2 / 8) / (2.0 * (double)pl.Nc);
+    const float2 rot = make_float2((float)std::cos(ang), (float)std::sin(ang));
+    with_int<8, 9>(pl.N2 == 256 ? 8 : 9, [&](auto lg) {
+        hipLaunchKernelGGL(k_pair_decimate16<decltype(lg)::value>, r.dec_grid, dim3(512), sizeof(float2) * 2 * 16 * kDecPitch, bf.st, bf.pw,
+                           spectra, g, edges, pl, taps, r.ps2.N2, r.dec_gp, n_pw, rot);
+    });
+}
+
+// decimated inverse, small plan: the R = Nc/16-point inverse of G (rows, pruned column pass with the window divided out, K5)
+void launch_small_plan(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
+{
+    const FftPlan &pl = r.pl, &ps2 = r.ps2;
+    const int n_pw = r.b.n_pw, by_col = r.step != PairStep::Tiles ? 1 : 0;
+    const size_t rc_pts = (size_t)(pl.Nc / kDecD);
+    float2 *g = bf.v, *vs = bf.v + rc_pts * (size_t)n_pw, *edges = bf.v + dec_edge_offset(pl, n_pw);      // G, V': [n_pw][R] each
+    const auto *gain = static_cast<const float *>(ctx->dec_gain.p);
+    const size_t lds = sizeof(float2) * 2 * kRow8Lds;
+    ProfScope ps(ctx, TDOA_K_INV_COL, 3.0 * 8.0 * (double)rc_pts * n_pw);
+    if (r.small_fused) {
+        hipLaunchKernelGGL(k_small_rows_col_peak, dim3(n_pw), dim3(512), lds, bf.st, g, edges, bf.keys, bf.pw, ps2, pl.N2, by_col, r.lag_lo,
+                           r.lag_hi, bf.lag_dump, bf.dump_scale, gain, bf.oc);
+        return;
+    }
+    hipLaunchKernelGGL(k_inv_rows_plain_r8, dim3(ps2.N2 / 2, n_pw), dim3(512), lds, bf.st, g, edges, vs, ps2, pl.N2, by_col);
+    with_int<3, 0>(r.np2 == 3 && r.nn2 == 3 ? 3 : 0, [&](auto n) {      // 3: the reference's 20 000 lags on either small plan
+        hipLaunchKernelGGL((k_small_col_peak<decltype(n)::value, decltype(n)::value>), dim3(ps2.N1 / 256, n_pw), dim3(256), 0, bf.st, vs,
+                           bf.keys, bf.pw, ps2, r.lag_lo, r.lag_hi, r.np2, r.nn2, bf.lag_dump, bf.dump_scale, gain, bf.oc);
+    });
+}
+
+// full or short-lag inverse: pair rows (K3 + inverse rows), then the column pass with the peak pick
+void launch_inverse(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
+{
+    const FftPlan &pl = r.pl;
+    const int n_pw = r.b.n_pw;
+    const double nc8 = 8.0 * (double)pl.Nc;
+    {
+        ProfScope ps(ctx, TDOA_K_INV_ROW, 3.0 * nc8 * n_pw);     // SURVEY's model: two spectra read, V written, per pair
+        if (r.row16) {
+            const size_t lds = sizeof(float2) * 2 * kRowLds;
+            with_int<0, 1, 2, 4, 8>(r.fk, [&](auto fk) {
+                constexpr int FK = decltype(fk)::value;
+                if (pl.N2 > 2)
+                    hipLaunchKernelGGL((k_inv_row_pair4096<false, FK>), r.xcd_pairs ? dim3(r.xcd_grid) : dim3(pl.N2 / 2 - 1, n_pw), dim3(256),
+                                       lds, bf.st, bf.pw, bf.tz, bf.v, pl, r.xcd_pairs, n_pw);
+                hipLaunchKernelGGL((k_inv_row_pair4096<true, FK>), dim3(1, n_pw), dim3(256), lds, bf.st, bf.pw, bf.tz, bf.v, pl, 0, n_pw);
+            });
+        } else {
+            hipLaunchKernelGGL(k_inv_row_pair, dim3(pl.N2 / 2, n_pw), dim3(256), sizeof(float2) * 4 * (size_t)pl.N1, bf.st, bf.pw, bf.tz, bf.v, pl);
         }
     }
-    if (n_pw && fine_raw) {   // V (or the short-lag array) of this batch is still in place: peak neighbours for the parabola
-        const dim3 g1((n_pw + 63) / 64), b1(64);
-        ctx->prof_last = -1;      // unscoped launches: the next scope records its own start
-        if (seg_chunks) { /* done above: k_refine_segments */ }
-        else if (fk == 1) hipLaunchKernelGGL(k_refine_fused<1>, g1, b1, 0, st, v, d_keys, d_pw, pl, n_pw, fine_raw);
-        else if (fk == 2) hipLaunchKernelGGL(k_refine_fused<2>, g1, b1, 0, st, v, d_keys, d_pw, pl, n_pw, fine_raw);
-        else if (fk == 4) hipLaunchKernelGGL(k_refine_fused<4>, g1, b1, 0, st, v, d_keys, d_pw, pl, n_pw, fine_raw);
-        else if (fk == 8) hipLaunchKernelGGL(k_refine_fused<8>, g1, b1, 0, st, v, d_keys, d_pw, pl, n_pw, fine_raw);
-        else if (decim) {      // the row-pass output of the small plan is still in place behind G; window divided out per lag
-            FftPlan ps2;
-            if ((rc = make_plan(2 * (pl.Nc / kDecD), true, &ps2))) return fail(ctx, rc, "decimated plan");
-            hipLaunchKernelGGL(k_refine_peaks, dim3(n_pw), dim3(64), 0, st, v + (size_t)(pl.Nc / kDecD) * (size_t)n_pw, d_keys, d_pw,
-                               ps2, fine_raw, static_cast<const float *>(ctx->dec_gain.p), oc);
-        }
-        else hipLaunchKernelGGL(k_refine_peaks, dim3(n_pw), dim3(64), 0, st, v, d_keys, d_pw, pl, fine_raw, static_cast<const float *>(nullptr), oc);
+    ProfScope ps(ctx, TDOA_K_INV_COL, r.fk ? 8.0 * 256 * r.fk * pl.N2 * n_pw : nc8 * n_pw);
+    const dim3 grid(pl.N1 / 128, n_pw);
+    const size_t lds_wtab = sizeof(float2) * (size_t)pl.N2;
+    const bool fixed = (pl.N2 & 31) == 0;     // the compile-time forms of the pruned kernel read 32 rows per trip unguarded
+    if (r.fk)
+        with_int<1, 2, 4, 8>(r.fk, [&](auto fk) {
+            hipLaunchKernelGGL(k_fused_reduce<decltype(fk)::value>, dim3(2 * decltype(fk)::value, n_pw), dim3(256), 0, bf.st, bf.v, bf.keys,
+                               bf.pw, pl, r.lag_lo, r.lag_hi, bf.lag_dump, bf.dump_scale);
+        });
+    else if (r.pruned && fixed && r.np == r.nn && r.np >= 1 && r.np <= 4)
+        with_int<3, 1, 2, 4>(r.np, [&](auto n) {
+            hipLaunchKernelGGL((k_inv_col_pruned<decltype(n)::value, decltype(n)::value>), grid, dim3(256), lds_wtab, bf.st, bf.v, bf.keys,
+                               bf.pw, pl, r.lag_lo, r.lag_hi, bf.lag_dump, bf.dump_scale, bf.oc);
+        });
+    else if (r.pruned)
+        hipLaunchKernelGGL(k_inv_col_pruned_any, grid, dim3(256), lds_wtab, bf.st, bf.v, bf.keys, bf.pw, pl, r.lag_lo, r.lag_hi, r.np, r.nn,
+                           bf.lag_dump, bf.dump_scale, bf.oc);
+    else
+        hipLaunchKernelGGL(k_inv_col_peak, dim3(pl.N1 / pl.C, n_pw), dim3(256), sizeof(float2) * 2 * (size_t)pl.N2 * pl.C, bf.st, bf.v,
+                           bf.keys, bf.pw, pl, r.lag_lo, r.lag_hi, bf.lag_dump, bf.dump_scale);
+}
+
+// refinement: V (the short-lag array; the small plan's row-pass output behind G) of this batch is still in place -- the
+// peak's neighbours for the parabola (the segment form's: launch_segments)
+void launch_refine(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
+{
+    const int n_pw = r.b.n_pw;
+    ctx->prof_last = -1;      // unscoped launches: the next scope records its own start
+    if (r.inv == Inverse::ShortLag)
+        with_int<1, 2, 4, 8>(r.fk, [&](auto fk) {
+            hipLaunchKernelGGL(k_refine_fused<decltype(fk)::value>, dim3((n_pw + 63) / 64), dim3(64), 0, bf.st, bf.v, bf.keys, bf.pw, r.pl,
+                               n_pw, bf.fine_raw);
+        });
+    else if (r.inv == Inverse::Decimated)      // window divided out per lag
+        hipLaunchKernelGGL(k_refine_peaks, dim3(n_pw), dim3(64), 0, bf.st, bf.v + (size_t)(r.pl.Nc / kDecD) * (size_t)n_pw, bf.keys, bf.pw,
+                           r.ps2, bf.fine_raw, static_cast<const float *>(ctx->dec_gain.p), bf.oc);
+    else if (r.inv == Inverse::Full)
+        hipLaunchKernelGGL(k_refine_peaks, dim3(n_pw), dim3(64), 0, bf.st, bf.v, bf.keys, bf.pw, r.pl, bf.fine_raw,
+                           static_cast<const float *>(nullptr), bf.oc);
+}
+
+// ---- mode B core: K1 + forward transforms + inverse + peak pick over descriptors already in device memory
+int run_fm_batch(tdoa_ctx *ctx, const FmBatchShape &shape, const FftPlan &pl, int lag_lo, int lag_hi, FmBufs bf)
+{
+    const FmRoute r = plan_fm_batch(ctx->knobs, ctx->stg, ctx->n_cu, pl, lag_lo, lag_hi, shape);
+    if (r.error) return fail(ctx, r.status, r.error);
+    int rc;
+    if ((rc = reserve_fm_batch(ctx, r))) return rc;
+    ctx->once_active = r.once;
+    bf.st = ctx->stream;
+    bf.stats = static_cast<FmStats *>(ctx->stats.p);
+    bf.tz = static_cast<float2 *>(ctx->tz.p);
+    bf.v = static_cast<float2 *>(ctx->v.p);
+    if (r.once)
+        bf.oc = OnceCorr{static_cast<const float *>(ctx->once_edges.p), static_cast<const OnceFin *>(ctx->once_fin.p),
+                         static_cast<double *>(ctx->slot_gain.p), once_k1(lag_lo, lag_hi), lag_reach(lag_lo, lag_hi),
+                         (float)(8.0 * (double)pl.Nc)};          // raw = 4 N sum w w, N = 2 Nc
+    bf.codes = launch_stats(ctx, r, bf);
+    launch_fwd_cols(ctx, r, bf);
+    launch_fwd_rows(ctx, r, bf);
+    if (r.inv == Inverse::Segments) {
+        launch_segments(ctx, r, bf);
+    } else if (r.inv == Inverse::Decimated) {
+        launch_pair_step(ctx, r, bf);
+        launch_small_plan(ctx, r, bf);
+    } else if (r.inv != Inverse::None) {
+        launch_inverse(ctx, r, bf);
     }
+    if (r.inv != Inverse::None && r.b.fine) launch_refine(ctx, r, bf);
     HIPCHK(ctx, hipGetLastError());
     return TDOA_OK;
 }
@@ -1237,42 +1362,29 @@ int allow_big_lds(tdoa_ctx *ctx)
     if ((rc = set_lds(ctx, k_fwd_col256_c16<true>, all))) return rc;
     if ((rc = set_lds(ctx, k_fwd_colx_c16<2>, all))) return rc;
     if ((rc = set_lds(ctx, k_fwd_colx_c16<4>, all))) return rc;
-    if ((rc = set_lds(ctx, k_inv_row_pair4096<false, 0>, all))) return rc;
-    if ((rc = set_lds(ctx, k_inv_row_pair4096<true, 0>, all))) return rc;
-    if ((rc = set_lds(ctx, k_inv_row_pair4096<false, 1>, all))) return rc;
-    if ((rc = set_lds(ctx, k_inv_row_pair4096<true, 1>, all))) return rc;
-    if ((rc = set_lds(ctx, k_inv_row_pair4096<false, 2>, all))) return rc;
-    if ((rc = set_lds(ctx, k_inv_row_pair4096<true, 2>, all))) return rc;
-    if ((rc = set_lds(ctx, k_inv_row_pair4096<false, 4>, all))) return rc;
-    if ((rc = set_lds(ctx, k_inv_row_pair4096<true, 4>, all))) return rc;
-    if ((rc = set_lds(ctx, k_inv_row_pair4096<false, 8>, all))) return rc;
-    if ((rc = set_lds(ctx, k_inv_row_pair4096<true, 8>, all))) return rc;
     if ((rc = set_lds(ctx, (k_fm_demod<true, true>), all))) return rc;
-    if ((rc = set_lds(ctx, (k_xcorr_segments<1, false>), all))) return rc;
-    if ((rc = set_lds(ctx, (k_xcorr_segments<2, false>), all))) return rc;
-    if ((rc = set_lds(ctx, (k_xcorr_segments<4, false>), all))) return rc;
-    if ((rc = set_lds(ctx, (k_xcorr_segments_quad<1, false>), all))) return rc;
-    if ((rc = set_lds(ctx, (k_xcorr_segments_quad<2, false>), all))) return rc;
-    if ((rc = set_lds(ctx, (k_xcorr_segments_quad<4, false>), all))) return rc;
-    if ((rc = set_lds(ctx, (k_xcorr_segments<1, true>), all))) return rc;
-    if ((rc = set_lds(ctx, (k_xcorr_segments<2, true>), all))) return rc;
-    if ((rc = set_lds(ctx, (k_xcorr_segments<4, true>), all))) return rc;
-    if ((rc = set_lds(ctx, (k_xcorr_segments_quad<1, true>), all))) return rc;
-    if ((rc = set_lds(ctx, (k_xcorr_segments_quad<2, true>), all))) return rc;
-    if ((rc = set_lds(ctx, (k_xcorr_segments_quad<4, true>), all))) return rc;
     if ((rc = set_lds(ctx, k_pair_decimate16<8>, all))) return rc;
     if ((rc = set_lds(ctx, k_pair_decimate16<9>, all))) return rc;
     if ((rc = set_lds(ctx, k_inv_rows_plain_r8, all))) return rc;
     if ((rc = set_lds(ctx, k_small_rows_col_peak, all))) return rc;
+    for_ints<0, 1, 2, 4, 8>([&](auto fk) {
+        if (!rc) rc = set_lds(ctx, k_inv_row_pair4096<false, decltype(fk)::value>, all);
+        if (!rc) rc = set_lds(ctx, k_inv_row_pair4096<true, decltype(fk)::value>, all);
+    });
+    for_ints<1, 2, 4>([&](auto pq) {
+        for_ints<0, 1>([&](auto pack) {
+            if (!rc) rc = set_lds(ctx, k_xcorr_segments<decltype(pq)::value, (bool)decltype(pack)::value>, all);
+            if (!rc) rc = set_lds(ctx, k_xcorr_segments_quad<decltype(pq)::value, (bool)decltype(pack)::value>, all);
+        });
+    });
 #if TDOA_HAVE_DEC_COLS
-#define TDOA_STG_LDS(N2V, RV)                                                                    \
-    if ((rc = set_lds(ctx, (k_pair_decimate_staged<N2V, RV>), all))) return rc;
-#define TDOA_STG_LDS_N(N2V) TDOA_STG_LDS(N2V, 2) TDOA_STG_LDS(N2V, 4) TDOA_STG_LDS(N2V, 8)
-    TDOA_STG_LDS_N(256) TDOA_STG_LDS_N(512) TDOA_STG_LDS_N(2048) TDOA_STG_LDS_N(2560) TDOA_STG_LDS_N(3072) TDOA_STG_LDS_N(4096)
-#undef TDOA_STG_LDS_N
-#undef TDOA_STG_LDS
+    for_ints<256, 512, 2048, 2560, 3072, 4096>([&](auto n2) {
+        for_ints<2, 4, 8>([&](auto rv) {
+            if (!rc) rc = set_lds(ctx, k_pair_decimate_staged<decltype(n2)::value, decltype(rv)::value>, all);
+        });
+    });
 #endif
-    return TDOA_OK;
+    return rc;
 }
 
 int check_ctx(tdoa_ctx *ctx)
@@ -1293,11 +1405,11 @@ int check_ctx(tdoa_ctx *ctx)
 long long choose_fft_size(const tdoa_ctx *ctx, long long need, int lag_lo, int lag_hi, int zpad, FftPlan *pl, int *rc)
 {
     const long long p = std::max<long long>(next_pow2(need), 64);
-    if (!ctx->pow2_only && p == (1ll << 25)) {
+    if (!ctx->knobs.pow2_only && p == (1ll << 25)) {
         // 5 x 2^22 = 20 971 520 (4096 x 2560), then 3 x 2^23 = 25 165 824 (4096 x 3072: windows of 10.5 to 12.6 s at 2 Msps)
         for (const long long cand : {5ll << 22, 3ll << 23}) {
             FftPlan q;
-            if (need <= cand && make_plan(cand, true, &q, zpad) == TDOA_OK && decimation_applies(ctx, q, lag_lo, lag_hi)) {
+            if (need <= cand && make_plan(cand, true, &q, zpad) == TDOA_OK && decimation_applies(ctx->knobs, q, lag_lo, lag_hi)) {
                 *pl = q;
                 *rc = TDOA_OK;
                 return cand;
@@ -1371,7 +1483,7 @@ int fm_pair(tdoa_ctx *ctx, const uint8_t *iq1, size_t n1, const uint8_t *iq2, si
         lag_hi = (int)eff - 1;
     }
     FftPlan pl;
-    const long long n = choose_fft_size(ctx, (long long)std::max(n1, n2) + max_lag, lag_lo, lag_hi, ctx->zpad, &pl, &rc);
+    const long long n = choose_fft_size(ctx, (long long)std::max(n1, n2) + max_lag, lag_lo, lag_hi, ctx->knobs.zpad, &pl, &rc);
     if (rc) return fail(ctx, rc, "FFT size unsupported");
     ctx->plan = pl;            // tdoa_plan_info reports the plan of the last call, pair calls included
     ctx->plan_n = n;
@@ -1397,10 +1509,17 @@ int fm_pair(tdoa_ctx *ctx, const uint8_t *iq1, size_t n1, const uint8_t *iq2, si
     HIPCHK(ctx, hipMemsetAsync(ctx->keys.p, 0, sizeof(unsigned long long), ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(ctx->scales.p, &scale, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     ctx->prof_last = -1;
-    rc = run_fm_batch(ctx, d_sw, 2, (int)std::max(n1, n2), d_pw, 1, static_cast<unsigned long long *>(ctx->keys.p),
-                      pl, lag_lo, lag_hi, dump, 1.0f, (double)(n1 + n2),
-                      fine ? static_cast<float *>(ctx->fine_raw.p) : nullptr, 0, nullptr, 0, n1 >= 2 && n2 >= 2 && corr_len >= 2,
-                      corr_len != n1 ? d_sw + 2 : nullptr, n1 == n2 && corr_len == n1);
+    FmBatchShape shape = batch_shape(ctx);
+    shape.n_sw = 2;
+    shape.n_pw = 1;
+    shape.maxlen = (int)std::max(n1, n2);
+    shape.allow_fused_k1 = n1 >= 2 && n2 >= 2 && corr_len >= 2;
+    shape.separate_stats = corr_len != n1;
+    shape.equal_len = n1 == n2 && corr_len == n1;
+    shape.fine = fine != nullptr;
+    const FmBufs bf{d_sw, shape.separate_stats ? d_sw + 2 : nullptr, d_pw, nullptr, static_cast<unsigned long long *>(ctx->keys.p),
+                    dump, 1.0f, (double)(n1 + n2), fine ? static_cast<float *>(ctx->fine_raw.p) : nullptr};
+    rc = run_fm_batch(ctx, shape, pl, lag_lo, lag_hi, bf);
     if (rc) return rc;
     const double *slot_gain = ctx->once_active ? static_cast<const double *>(ctx->slot_gain.p) : nullptr;
     hipLaunchKernelGGL(k_decode_peaks, dim3(1), dim3(64), 0, ctx->stream,
@@ -1553,35 +1672,13 @@ int tdoa_create(const tdoa_params *p, tdoa_ctx **out)
         }
     }
     // run-time switches are read ONCE here (a captured graph must not depend on an environment that changes later)
-    if (const char *e = std::getenv("TDOA_NO_GRAPH")) ctx->use_graph = !(e[0] == '1');
-    if (const char *e = std::getenv("TDOA_NO_SHORT_LAG")) ctx->short_lag = !(e[0] == '1');
-    if (const char *e = std::getenv("TDOA_NO_SEGMENT_FORM")) ctx->segment_form = !(e[0] == '1');
-    if (const char *e = std::getenv("TDOA_NO_SEGMENT_QUADS")) ctx->segment_quads = !(e[0] == '1');
-    if (const char *e = std::getenv("TDOA_NO_DECIMATE")) ctx->decimate = !(e[0] == '1');
-    if (const char *e = std::getenv("TDOA_NO_K1_ONCE")) ctx->k1_once = !(e[0] == '1');
-    if (const char *e = std::getenv("TDOA_POW2_ONLY")) ctx->pow2_only = e[0] == '1';
-    if (const char *e = std::getenv("TDOA_ZPAD")) {
-        const int v = std::atoi(e);
-        ctx->zpad = v < 0 ? 0 : v > 4096 ? 4096 : v & ~15;      // rows stay 128-byte aligned (the finish sweep reads 16-byte pairs)
+    for (const KnobVar &kv : kKnobVars) {
+        const char *e = kv.env ? std::getenv(kv.env) : nullptr;
+        if (!e) continue;
+        if (kv.flag) ctx->knobs.*kv.flag = e[0] == '1' ? kv.when_one : !kv.when_one;
+        else ctx->knobs.*kv.num = kv.clamp(std::atoi(e));
     }
-    if (const char *e = std::getenv("TDOA_NO_FUSED_K1")) ctx->fused_k1 = !(e[0] == '1');
-    if (const char *e = std::getenv("TDOA_NO_DEC_COLS")) ctx->dec_cols = !(e[0] == '1');
-    if (const char *e = std::getenv("TDOA_DEC_COLS_ALWAYS")) ctx->dec_cols_always = e[0] == '1';
-    if (const char *e = std::getenv("TDOA_NO_DEC_STAGED")) ctx->dec_staged = !(e[0] == '1');
-    if (const char *e = std::getenv("TDOA_NO_SMALL_FUSED")) ctx->small_fused = !(e[0] == '1');
-    if (const char *e = std::getenv("TDOA_SMALL_FUSED_ALWAYS")) ctx->small_fused_always = e[0] == '1';
-    if (const char *e = std::getenv("TDOA_NO_STG_FOLDED")) ctx->stg_folded = !(e[0] == '1');
-    if (const char *e = std::getenv("TDOA_STG_FOLDED_ALWAYS")) ctx->stg_folded_always = e[0] == '1';
-    if (const char *e = std::getenv("TDOA_NO_STG_BLOCKS")) ctx->stg_blocks = !(e[0] == '1');
-    if (const char *e = std::getenv("TDOA_DEC_STAGED_LOADERS")) ctx->stg_loaders = std::max(0, std::min(4, std::atoi(e)));
-    if (const char *e = std::getenv("TDOA_DEC_STAGED_ROWS")) ctx->stg_rows = std::atoi(e) == 8 ? 8 : std::atoi(e) == 4 ? 4 : std::atoi(e) == 2 ? 2 : 0;
-    if (const char *e = std::getenv("TDOA_DEC_STAGED_CW")) ctx->stg_cw = std::max(0, std::min(15, std::atoi(e)));
-    if (const char *e = std::getenv("TDOA_DEC_STAGED_BUFS")) ctx->stg_bufs = std::max(0, std::min(16, std::atoi(e)));
-    if (const char *e = std::getenv("TDOA_NO_SEG_PACK3")) ctx->seg_pack3 = !(e[0] == '1');
-    if (const char *e = std::getenv("TDOA_SEG_CHUNKS")) ctx->seg_chunks_override = std::max(0, std::atoi(e));
-    if (const char *e = std::getenv("TDOA_DEBUG_MEMSET_NODES")) ctx->memset_nodes = e[0] == '1';
-    if (const char *e = std::getenv("TDOA_NO_XCD_ROWS")) ctx->xcd_rows = !(e[0] == '1');
-    if (const char *e = std::getenv("TDOA_XCD_PAIR_MB")) ctx->xcd_pair_mb = std::max(0, std::atoi(e));
+    ctx->stg = stg_tables(ctx->knobs);
     *out = ctx;
     return TDOA_OK;
 }
@@ -1883,7 +1980,7 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
     const bool go = ctx->prm.lag_mode == TDOA_LAGS_GO;
     const int lag_lo = go ? 0 : -(ctx->prm.max_lag - 1), lag_hi = go ? 0 : ctx->prm.max_lag - 1;
     FftPlan pl;
-    const long long n = choose_fft_size(ctx, wlen + ctx->prm.max_lag, lag_lo, lag_hi, ctx->zpad, &pl, &rc);
+    const long long n = choose_fft_size(ctx, wlen + ctx->prm.max_lag, lag_lo, lag_hi, ctx->knobs.zpad, &pl, &rc);
     if (rc) return fail(ctx, rc, "FFT size unsupported");
     ctx->plan = pl;
     ctx->plan_n = n;
@@ -1908,14 +2005,25 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
     // by a third of the device's memory for the workspace (96 GB of an MI355X's 288: cfg4's 99 windows x 36 spectra are one
     // group of 30 GB; round 3 stopped at 24 GiB and ran them as 85 + 14)
     int per_batch = ctx->prm.windows_per_batch > 0 ? ctx->prm.windows_per_batch : (int)std::max<size_t>(mine.size(), 1);
+    // a launch group of n_sw station-windows and n_pw pair-windows as run_fm_batch sees it
+    auto shape_of = [&](int n_sw, int n_pw, int n_quads) {
+        FmBatchShape b = batch_shape(ctx);
+        b.n_sw = n_sw;
+        b.n_pw = n_pw;
+        b.maxlen = (int)wlen;
+        b.pairs_per_window = pair_major ? 0 : P;
+        b.stations_per_window = pair_major ? 0 : S;
+        b.n_quads = n_quads;
+        b.allow_fused_k1 = corr_len >= 2;
+        b.separate_stats = go;
+        b.equal_len = !go;                   // every window has wlen samples
+        b.fine = fine_host != nullptr;
+        return b;
+    };
     // what reserve_fm_batch asks for per window (+ 1/8: ensure() rounds every buffer up): TZ, the V workspace in the form this
-    // plan's pair step uses (dec_spectra_offset + the tiled spectra behind the tile form), code rows where K1 is materialised
-    double bytes_per_window = 8.0 * (double)pl.Zs * S + 8.0 * (double)pl.Nc * P;
-    if (decimation_applies(ctx, pl, lag_lo, lag_hi))
-        bytes_per_window = 8.0 * (double)pl.Zs * S +
-                           8.0 * std::max((double)pl.Nc * P, (double)dec_spectra_offset(pl, P) + (cols_only_plan(pl) ? 0.0 : (double)pl.Nc * S));
-    if (!fused_k1_applies(ctx, pl, lag_lo, lag_hi, P, true)) bytes_per_window += 4.0 * (double)(wlen + 16) * S * (ctx->prm.k1_smooth > 1 ? 2 : 1);
-    bytes_per_window *= 1.125;
+    // plan's pair step uses, code rows where K1 is materialised
+    const FmBytes by = plan_fm_batch(ctx->knobs, ctx->stg, ctx->n_cu, pl, lag_lo, lag_hi, shape_of(S, P, 0)).bytes;
+    const double bytes_per_window = 1.125 * ((double)by.tz + (double)by.v + (double)by.codes + (double)by.codes_lp);
     // the bound: a third of the device (tdoa_create), and not more than is FREE now plus what this context already holds of it
     // (captures attached by the caller, other contexts, other ranks on the same card all count against the device)
     double limit = ctx->workspace_limit;
@@ -2002,7 +2110,7 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
         if ((rc = ensure(ctx, ctx->fine_raw, 3 * sizeof(float) * slots))) return rc;
         if ((rc = ensure(ctx, ctx->fine, sizeof(FineOut) * slots))) return rc;
     }
-    if (n_first && (rc = reserve_fm_batch(ctx, n_first * S, (int)wlen, n_first * P, pl, lag_lo, lag_hi, true)))
+    if (n_first && (rc = reserve_fm_batch(ctx, plan_fm_batch(ctx->knobs, ctx->stg, ctx->n_cu, pl, lag_lo, lag_hi, shape_of(n_first * S, n_first * P, 0)))))
         return rc;
     auto *d_sw = static_cast<SWDesc *>(ctx->g_sw_desc.p);
     auto *d_pw = static_cast<PWDesc *>(ctx->g_pw_desc.p);
@@ -2014,19 +2122,15 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
     std::vector<uint64_t> key = {(uint64_t)S, (uint64_t)rank, (uint64_t)world, (uint64_t)per_batch, (uint64_t)wlen,
                                  (uint64_t)ctx->prm.max_lag | ((uint64_t)ctx->prm.k1_smooth << 32) | ((uint64_t)(ctx->prm.k1_gate != 0) << 62) |
                                      ((uint64_t)go << 61), (uint64_t)block,
-                                 (uint64_t)ctx->force_generic | ((uint64_t)ctx->short_lag << 1) |
-                                     ((uint64_t)ctx->segment_form << 3) | ((uint64_t)ctx->xcd_rows << 4) |
-                                     ((uint64_t)ctx->segment_quads << 6) |
-                                     ((uint64_t)ctx->decimate << 8) | ((uint64_t)ctx->fused_k1 << 9) | ((uint64_t)ctx->k1_once << 11) | ((uint64_t)ctx->seg_pack3 << 12) | ((uint64_t)ctx->dec_cols << 13) | ((uint64_t)ctx->dec_cols_always << 14) | ((uint64_t)ctx->pow2_only << 15) | ((uint64_t)ctx->dec_staged << 7) | ((uint64_t)ctx->stg_cw << 58) | ((uint64_t)ctx->stg_loaders << 54) | ((uint64_t)ctx->stg_blocks << 53) | ((uint64_t)ctx->stg_folded << 50) | ((uint64_t)ctx->stg_folded_always << 49) | ((uint64_t)ctx->small_fused << 52) | ((uint64_t)ctx->small_fused_always << 51) | ((uint64_t)ctx->stg_rows << 28) | ((uint64_t)ctx->stg_bufs << 32) |
-                                     ((uint64_t)ctx->memset_nodes << 10) | ((uint64_t)ctx->seg_chunks_override << 16) | ((uint64_t)ctx->xcd_pair_mb << 40),
                                  ctx->alloc_gen, (uint64_t)(fine_host != nullptr), 0};
     std::memcpy(&key.back(), &gate, sizeof(double));
+    for (const KnobVar &kv : kKnobVars) key.push_back(kv.flag ? (uint64_t)(ctx->knobs.*kv.flag) : (uint64_t)(ctx->knobs.*kv.num));
     for (auto &c : ctx->caps) {
         key.push_back((uint64_t)(uintptr_t)c.dev);
         key.push_back((uint64_t)c.n);
     }
     key.push_back(ctx->graph_prof ? 0x100000000ull | ctx->prof_mask : 0ull);      // an instrumented step is a different graph
-    const bool graph_ok = ctx->use_graph && !ctx->profiling;
+    const bool graph_ok = ctx->knobs.use_graph && !ctx->profiling;
     const bool replay = graph_ok && ctx->graph_exec && key == ctx->graph_key;
 
     std::vector<SWDesc> sw_full;
@@ -2050,7 +2154,7 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
 
     auto enqueue = [&]() -> int {
         ctx->prof_last = -1;
-        if (ctx->memset_nodes)               // probe only (TDOA_DEBUG_MEMSET_NODES=1)
+        if (ctx->knobs.memset_nodes)         // probe only (TDOA_DEBUG_MEMSET_NODES=1)
             (void)hipMemsetAsync(d_keys, 0, sizeof(unsigned long long) * slots, st);
         else
             hipLaunchKernelGGL(k_zero_u64, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, d_keys, slots);
@@ -2058,11 +2162,9 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
         for (size_t w0 = 0; w0 < mine.size(); w0 += per_batch) {
             const int nw = (int)std::min<size_t>(per_batch, mine.size() - w0);
             const int n_sw = (int)(sw_off[w0 + nw] - sw_off[w0]), n_pw = (int)(pw_off[w0 + nw] - pw_off[w0]);
-            const int r = run_fm_batch(ctx, d_sw + sw_off[w0], n_sw, (int)wlen, d_pw + pw_off[w0], n_pw, d_keys, pl,
-                                       lag_lo, lag_hi, nullptr, 1.0f,
-                                       (double)wlen * n_sw, fine_raw, pair_major ? 0 : P, d_quads + q_off[w0],
-                                       (int)(q_off[w0 + nw] - q_off[w0]), corr_len >= 2,
-                                       go ? d_sw + sw.size() + sw_off[w0] : nullptr, !go);      // every window has wlen samples
+            const FmBufs bf{d_sw + sw_off[w0], go ? d_sw + sw.size() + sw_off[w0] : nullptr, d_pw + pw_off[w0], d_quads + q_off[w0],
+                            d_keys, nullptr, 1.0f, (double)wlen * n_sw, fine_raw};
+            const int r = run_fm_batch(ctx, shape_of(n_sw, n_pw, (int)(q_off[w0 + nw] - q_off[w0])), pl, lag_lo, lag_hi, bf);
             if (r) return r;
         }
         // (every batch of a step takes the same path: same plan, same lag range, same lengths)
@@ -2114,7 +2216,7 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
             ctx->graph_memsets = memsets;
             if (n_nodes && (n_roots != 1 || n_edges + 1 < n_nodes))
                 return fail(ctx, TDOA_ERR_STATE, "captured step is not one dependency chain");
-            if (memsets && !ctx->memset_nodes) return fail(ctx, TDOA_ERR_STATE, "captured step holds a memset node");
+            if (memsets && !ctx->knobs.memset_nodes) return fail(ctx, TDOA_ERR_STATE, "captured step holds a memset node");
         }
         // graph-mode profiling: an event-record node before the first and after the last kernel of every marked scope
         for (auto &m : ctx->graph_marks) {
@@ -2339,7 +2441,7 @@ int tdoa_fm_preprocess_u8(tdoa_ctx *ctx, const uint8_t *iq, size_t n, float *out
 int tdoa_debug_force_generic(tdoa_ctx *ctx, int on)
 {
     if (!ctx) return TDOA_ERR_INVALID;
-    ctx->force_generic = on != 0;
+    ctx->knobs.force_generic = on != 0;
     return TDOA_OK;
 }
 
@@ -2412,21 +2514,8 @@ int tdoa_debug_graph_info(tdoa_ctx *ctx, int32_t info[4], const char *dot_path)
 int tdoa_debug_flags(tdoa_ctx *ctx, unsigned flags)
 {
     if (!ctx) return TDOA_ERR_INVALID;
-    ctx->force_generic = (flags & TDOA_DEBUG_GENERIC_KERNELS) != 0;
-    ctx->short_lag = !(flags & TDOA_DEBUG_NO_SHORT_LAG);
-    ctx->segment_form = !(flags & TDOA_DEBUG_NO_SEGMENT_FORM);
-    ctx->xcd_rows = !(flags & TDOA_DEBUG_NO_XCD_ROWS);
-    ctx->segment_quads = !(flags & TDOA_DEBUG_NO_SEGMENT_QUADS);
-    ctx->decimate = !(flags & TDOA_DEBUG_NO_DECIMATE);
-    ctx->fused_k1 = !(flags & TDOA_DEBUG_NO_FUSED_K1);
-    ctx->k1_once = !(flags & TDOA_DEBUG_NO_K1_ONCE);
-    ctx->seg_pack3 = !(flags & TDOA_DEBUG_NO_SEG_PACK3);
-    ctx->dec_cols = !(flags & TDOA_DEBUG_NO_DEC_COLS);
-    ctx->dec_cols_always = (flags & TDOA_DEBUG_DEC_COLS_ALWAYS) != 0;
-    ctx->pow2_only = (flags & TDOA_DEBUG_POW2_ONLY) != 0;
-    ctx->dec_staged = !(flags & TDOA_DEBUG_NO_DEC_STAGED);
-    ctx->small_fused = !(flags & TDOA_DEBUG_NO_SMALL_FUSED);
-    ctx->small_fused_always = (flags & TDOA_DEBUG_SMALL_FUSED_ALWAYS) != 0;
+    for (const KnobVar &kv : kKnobVars)
+        if (kv.debug_bit) ctx->knobs.*kv.flag = (flags & kv.debug_bit) ? kv.when_one : !kv.when_one;
     return TDOA_OK;
 }
 

@@ -148,6 +148,27 @@ def test_staged_walk_with_and_without_a_loader_wave(oracle, n_stations, folded, 
     assert (peaks["lag"] == want[None, :]).all() and (peaks["abs_corr"] > 100.0).all()
 
 
+def test_staged_walk_with_fewer_walks_than_a_groups_stations(oracle, monkeypatch):
+    """TDOA_DEC_STAGED_CW=3 on eight stations and cfg4's window geometry (4096 x 256 plan): the folded form's share-out
+    would put five stations (pairs (0,1) .. (0,4)) on four walking waves, and in that form each wave brings one station --
+    the fifth would never reach the LDS.  The library must take the form with a loader wave there instead: the same bits
+    as the per-pair walk, and the geometry's lags"""
+    import tdoa_amd
+    monkeypatch.setenv("TDOA_DEC_STAGED_CW", "3")
+    n_stations, wl = 8, 2_000_000
+    rng = np.random.default_rng(500)
+    delays = [int(x) for x in rng.integers(0, 300, size=n_stations)]
+    caps = [np.concatenate([oracle.simulate_delayed_fm(wl, d, 850 + k, 100 * (s + 1) + k) for k in range(3)])
+            for s, d in enumerate(delays)]
+    with tdoa_amd.Context(max_lag=ML, window_len=wl) as c:
+        peaks = c.process_u8(caps)
+        c.debug_flags(dec_cols_always=True, no_dec_staged=True)
+        walk = c.process()
+    assert np.array_equal(walk, peaks)
+    want = np.array([delays[j] - delays[i] for i in range(n_stations) for j in range(i + 1, n_stations)])
+    assert (peaks["lag"] == want[None, :]).all() and (peaks["abs_corr"] > 100.0).all()
+
+
 def test_staged_walk_in_launch_groups_and_shards(oracle):
     """the staged walk behind tdoa_process's batching and sharding: two windows per launch group (three windows: a group of two
     and a group of one), and the windows dealt to two ranks (wid % 2: rank 0 two windows, rank 1 one) -- every variant must
