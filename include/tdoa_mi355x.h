@@ -323,6 +323,15 @@ int tdoa_debug_segment_quads(int n_stations, const int32_t *pairs, int n_pairs, 
  * (stations outside 2..16, max_pairs outside 1..16, more than max_groups). */
 int tdoa_debug_staged_groups(int n_stations, int max_pairs, uint32_t *masks_out, int32_t *counts_out, uint8_t *pairs_out, int max_groups);
 
+/* tests only (host, no GPU): what tdoa_process(rank, world) runs for n_stations captures cut into n_windows windows, with
+ * launch groups of at most max_per_batch windows before the grid limit.  pw_out gets 6 ints per owned pair-window, in launch
+ * order: unit wid * n_pairs + pair, launch group, the template's and the signal's station-window slot (relative to the
+ * group) and the stations of those two slots.  quads_out (room for max_pw) gets 9 ints per segment-form quad: launch group,
+ * slots a, b, c, d (-1 = empty) and the group-relative pair-window of (a,c), (a,d), (b,c), (b,d) (-1 = not wanted);
+ * *n_quads their number.  Returns the number of pair-windows, or a negative TDOA_ERR_* value. */
+int tdoa_debug_step_layout(int n_stations, int n_windows, int rank, int world, int max_per_batch, int32_t *pw_out, int max_pw,
+                           int32_t *quads_out, int32_t *n_quads);
+
 /* ---- downstream (processor.go:125-163, 932-1045), host side ---------------- */
 void tdoa_latlon_to_ecef(double lat, double lon, double elev, double xyz[3]);
 void tdoa_ecef_to_latlon(double x, double y, double z, double lle[3]);

@@ -11,7 +11,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <climits>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <new>
 #include <string>
@@ -120,6 +122,8 @@ struct StgTables {
     std::vector<StgGroup> groups;
 };
 
+using QuadCache = std::map<std::vector<int>, std::vector<StationQuad>>;    // owned pair ids of a window -> its quad cover
+
 }  // namespace
 
 struct tdoa_ctx {
@@ -183,7 +187,7 @@ struct tdoa_ctx {
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     DevBuf g_sw_desc, g_pw_desc, g_quad_desc, g_scales, g_keys;
-    std::map<std::vector<int>, std::vector<StationQuad>> quad_cache;   // owned pair ids of a window -> its quad cover
+    QuadCache quad_cache;                   // segment-form quad covers (build_step_layout)
     DevBuf qual;                            // QualAcc per (window, station)
     StagedUploader uploader;                // pinned staging buffers + copy streams, created on first use
     DevBuf fine_raw, fine;                  // (f)-4 refinement: 3 raw neighbours and tdoa_fine_peak per slot
@@ -1553,6 +1557,236 @@ int fm_pair(tdoa_ctx *ctx, const uint8_t *iq1, size_t n1, const uint8_t *iq2, si
     return TDOA_OK;
 }
 
+// IQ bytes of station s's window wid: block wid / wpb of that capture's OWN thirds, window wid % wpb of wlen samples in it
+const uint8_t *window_iq(const tdoa_ctx *ctx, int s, int wid, int wpb, long long wlen)
+{
+    const auto &c = ctx->caps[s];
+    return c.dev + 2 * ((long long)(wid / wpb) * (long long)(c.n / 3) + (long long)(wid % wpb) * wlen);
+}
+
+// Which (window, pair) units of a step one rank runs, in which launch groups, and the descriptors' indices -- plain
+// numbers, no device state.  Window wi of the rank (mine[wi]) owns station-windows [sw_off[wi], sw_off[wi+1]) and likewise
+// pw and quads; every slot and pair-window index is relative to the first window of its launch group.
+struct StepLayout {
+    std::vector<int> mine;                   // owned windows, ascending
+    int per_batch = 1;                       // windows per launch group
+    std::vector<int> sw_station;             // station of each station-window
+    std::vector<PWDesc> pw;                  // len_a is the caller's
+    std::vector<QuadDesc> quads;
+    std::vector<size_t> sw_off, pw_off, q_off;
+};
+
+// max_per_batch: the caller's bound (tdoa_params.windows_per_batch, workspace).  TDOA_ERR_UNSUPPORTED: a window's station
+// or pair count alone exceeds the grid limit.
+int build_step_layout(int S, int W, int rank, int world, int max_per_batch, QuadCache &quad_cache, StepLayout *out)
+{
+    const int P = S * (S - 1) / 2;
+    StepLayout &L = *out;
+    L = StepLayout{};
+    // Sharding (SURVEY section 8e): window-major -- rank r owns the windows wid = r (mod world), so a station-window
+    // is transformed once and reused by all its pairs.  With fewer windows than ranks that would leave ranks idle:
+    // then the (window, pair) units u = wid*P + p are dealt u = r (mod world) and a rank transforms only the
+    // stations its pairs need (station spectra are duplicated across ranks).  tdoa_amd/sharding.py unit_owner states the same rule.
+    const bool pair_major = W < world;
+    auto owns = [&](int wid, int p) { return pair_major ? ((wid * P + p) % world) == rank : (wid % world) == rank; };
+    for (int w = 0; w < W; w++) {
+        bool any = false;
+        for (int p = 0; p < P && !any; p++) any = owns(w, p);
+        if (any) L.mine.push_back(w);
+    }
+    // default: every window of this rank in one launch group (launch tails cost more than cache residency gains)
+    L.per_batch = std::min(max_per_batch, (int)std::max<size_t>(L.mine.size(), 1));
+    // per_batch * S and per_batch * P become gridDim.y of the FFT kernels (HIP limit 65535)
+    if (std::max(S, P) > 65535) return TDOA_ERR_UNSUPPORTED;
+    L.per_batch = std::max(1, std::min(L.per_batch, 65535 / std::max(S, P)));
+    if (!L.mine.empty()) {                   // groups of equal size (99 windows at most 85 at a time: 50 + 49, not 85 + 14)
+        const int groups = ((int)L.mine.size() + L.per_batch - 1) / L.per_batch;
+        L.per_batch = ((int)L.mine.size() + groups - 1) / groups;
+    }
+
+    const size_t nm = L.mine.size(), pb = (size_t)L.per_batch;
+    L.sw_off.assign(nm + 1, 0);
+    L.pw_off.assign(nm + 1, 0);
+    L.q_off.assign(nm + 1, 0);
+    for (size_t wi = 0; wi < nm; wi++) {
+        const int wid = L.mine[wi];
+        const size_t batch_base = L.sw_off[wi - wi % pb];
+        std::vector<int> slot(S, -1), owned;
+        std::vector<std::pair<int, int>> st_pairs;
+        int p = 0;
+        for (int i = 0; i < S; i++)
+            for (int j = i + 1; j < S; j++, p++) {
+                if (!owns(wid, p)) continue;
+                for (int s : {i, j})
+                    if (slot[s] < 0) {
+                        slot[s] = (int)(L.sw_station.size() - batch_base);
+                        L.sw_station.push_back(s);
+                    }
+                L.pw.push_back(PWDesc{slot[i], slot[j], wid * P + p, 0});
+                owned.push_back(p);
+                st_pairs.emplace_back(i, j);
+            }
+        L.sw_off[wi + 1] = L.sw_station.size();
+        L.pw_off[wi + 1] = L.pw.size();
+        // segment form: the quad cover of this window's pairs (the same for every window under window-major sharding).
+        // Every pair-window of the rank is in exactly one quad; run_fm_batch takes the quads of a batch or none of them.
+        // (the greedy cover costs O(P S^2) per quad: beyond kMaxQuadStations stations the segment form stays pair by pair)
+        if (!owned.empty() && S <= kMaxQuadStations) {
+            auto it = quad_cache.find(owned);
+            if (it == quad_cache.end()) it = quad_cache.emplace(owned, build_segment_quads(S, st_pairs)).first;
+            const int pw_base = (int)(L.pw_off[wi] - L.pw_off[wi - wi % pb]);
+            for (const StationQuad &q : it->second) {
+                QuadDesc d{slot[q.a], q.b >= 0 ? slot[q.b] : -1, slot[q.c], q.d >= 0 ? slot[q.d] : -1, {-1, -1, -1, -1}};
+                for (int o = 0; o < 4; o++)
+                    if (q.pair[o] >= 0) d.pw[o] = pw_base + q.pair[o];
+                L.quads.push_back(d);
+            }
+        }
+        L.q_off[wi + 1] = L.quads.size();
+    }
+    return TDOA_OK;
+}
+
+// Upper bound on windows per launch group: tdoa_params.windows_per_batch, and a third of the device's memory for the
+// workspace (96 GB of an MI355X's 288: cfg4's 99 windows x 36 spectra are one group of 30 GB; round 3 stopped at 24 GiB and
+// ran them as 85 + 14).  one_window: the launch group of one window as run_fm_batch sees it.
+// (ADVICE r05 asks to evaluate this once per shape and to count every buffer in `held`: a change of grouping, its own PR)
+int batch_bound(tdoa_ctx *ctx, const FftPlan &pl, int lag_lo, int lag_hi, const FmBatchShape &one_window)
+{
+    // what reserve_fm_batch asks for per window (+ 1/8: ensure() rounds every buffer up): TZ, the V workspace in the form this
+    // plan's pair step uses, code rows where K1 is materialised
+    const FmBytes by = plan_fm_batch(ctx->knobs, ctx->stg, ctx->n_cu, pl, lag_lo, lag_hi, one_window).bytes;
+    const double bytes_per_window = 1.125 * ((double)by.tz + (double)by.v + (double)by.codes + (double)by.codes_lp);
+    // the bound: a third of the device (tdoa_create), and not more than is FREE now plus what this context already holds of it
+    // (captures attached by the caller, other contexts, other ranks on the same card all count against the device)
+    double limit = ctx->workspace_limit;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+        const double held = (double)ctx->tz.cap + (double)ctx->v.cap + (double)ctx->codes.cap + (double)ctx->codes_lp.cap;
+        limit = std::min(limit, std::max(0.0, (double)free_b + held - 1073741824.0));      // 1 GiB stays free: descriptors, edges, the runtime
+    } else {
+        (void)hipGetLastError();
+    }
+    const int asked = ctx->prm.windows_per_batch > 0 ? ctx->prm.windows_per_batch : INT_MAX;
+    return (int)std::max(1.0, std::min<double>(asked, limit / bytes_per_window));
+}
+
+// Everything a step's launches depend on: same key => the captured graph can be replayed as is
+std::vector<uint64_t> step_graph_key(const tdoa_ctx *ctx, int rank, int world, int per_batch, long long wlen, long long block,
+                                     bool go, bool fine, double gate)
+{
+    std::vector<uint64_t> key = {(uint64_t)ctx->caps.size(), (uint64_t)rank, (uint64_t)world, (uint64_t)per_batch, (uint64_t)wlen,
+                                 (uint64_t)ctx->prm.max_lag | ((uint64_t)ctx->prm.k1_smooth << 32) | ((uint64_t)(ctx->prm.k1_gate != 0) << 62) |
+                                     ((uint64_t)go << 61), (uint64_t)block,
+                                 ctx->alloc_gen, (uint64_t)fine, 0};
+    std::memcpy(&key.back(), &gate, sizeof(double));
+    for (const KnobVar &kv : kKnobVars) key.push_back(kv.flag ? (uint64_t)(ctx->knobs.*kv.flag) : (uint64_t)(ctx->knobs.*kv.num));
+    for (auto &c : ctx->caps) {
+        key.push_back((uint64_t)(uintptr_t)c.dev);
+        key.push_back((uint64_t)c.n);
+    }
+    key.push_back(ctx->graph_prof ? 0x100000000ull | ctx->prof_mask : 0ull);      // an instrumented step is a different graph
+    return key;
+}
+
+bool step_graph_on(const tdoa_ctx *ctx) { return ctx->knobs.use_graph && !ctx->profiling; }
+
+// the step graph captured under `key` is there: run_step_graph will replay it (its descriptors are still on the device)
+bool step_graph_replays(const tdoa_ctx *ctx, const std::vector<uint64_t> &key)
+{
+    return step_graph_on(ctx) && ctx->graph_exec && key == ctx->graph_key;
+}
+
+// after -> [record ev] -> after's successors
+hipError_t splice_event_record(hipGraph_t g, hipGraphNode_t after, hipEvent_t ev)
+{
+    size_t nd = 0;
+    hipError_t r = hipGraphNodeGetDependentNodes(after, nullptr, &nd);
+    if (r != hipSuccess) return r;
+    std::vector<hipGraphNode_t> succ(nd);
+    if (nd && (r = hipGraphNodeGetDependentNodes(after, succ.data(), &nd)) != hipSuccess) return r;
+    hipGraphNode_t rec = nullptr;
+    for (hipGraphNode_t sn : succ)
+        if ((r = hipGraphRemoveDependencies(g, &after, &sn, 1)) != hipSuccess) return r;
+    if ((r = hipGraphAddEventRecordNode(&rec, g, &after, 1, ev)) != hipSuccess) return r;
+    for (hipGraphNode_t sn : succ)
+        if ((r = hipGraphAddDependencies(g, &rec, &sn, 1)) != hipSuccess) return r;
+    return hipSuccess;
+}
+
+// Enqueues one step on ctx->stream: replays the cached step graph when `key` is its key, else captures enqueue() into a
+// new one and launches that, or -- graphs off, or the profiling path -- runs enqueue() directly.
+int run_step_graph(tdoa_ctx *ctx, const std::vector<uint64_t> &key, const std::function<int()> &enqueue)
+{
+    hipStream_t st = ctx->stream;
+    if (step_graph_replays(ctx, key)) {
+        ctx->once_active = ctx->graph_once;
+        HIPCHK(ctx, hipGraphLaunch(ctx->graph_exec, st));
+        return TDOA_OK;
+    }
+    if (!step_graph_on(ctx)) return enqueue();
+    if (ctx->graph_exec) { (void)hipGraphExecDestroy(ctx->graph_exec); ctx->graph_exec = nullptr; }
+    if (ctx->graph) { (void)hipGraphDestroy(ctx->graph); ctx->graph = nullptr; }
+    ctx->graph_key.clear();
+    HIPCHK(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    clear_graph_marks(ctx);
+    ctx->capturing = true;
+    const int rc = enqueue();
+    ctx->capturing = false;
+    hipGraph_t g = nullptr;
+    hipError_t e = hipStreamEndCapture(st, &g);
+    if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
+    if (e != hipSuccess) return fail(ctx, TDOA_ERR_HIP, "hipStreamEndCapture", e);
+    ctx->graph = g;
+    // the step was captured from ONE stream: it must come out as one dependency chain -- every node but the first has
+    // a predecessor (a node without one would replay unordered against the kernels that feed or consume it)
+    size_t n_nodes = 0, n_edges = 0, n_roots = 0;
+    HIPCHK(ctx, hipGraphGetNodes(g, nullptr, &n_nodes));
+    HIPCHK(ctx, hipGraphGetEdges(g, nullptr, nullptr, &n_edges));
+    HIPCHK(ctx, hipGraphGetRootNodes(g, nullptr, &n_roots));
+    std::vector<hipGraphNode_t> nodes(n_nodes);
+    if (n_nodes) HIPCHK(ctx, hipGraphGetNodes(g, nodes.data(), &n_nodes));
+    int memsets = 0;
+    for (hipGraphNode_t nd : nodes) {
+        hipGraphNodeType ty;
+        if (hipGraphNodeGetType(nd, &ty) == hipSuccess && ty == hipGraphNodeTypeMemset) memsets++;
+    }
+    ctx->graph_nodes = (int)n_nodes;
+    ctx->graph_edges = (int)n_edges;
+    ctx->graph_roots = (int)n_roots;
+    ctx->graph_memsets = memsets;
+    if (n_nodes && (n_roots != 1 || n_edges + 1 < n_nodes))
+        return fail(ctx, TDOA_ERR_STATE, "captured step is not one dependency chain");
+    if (memsets && !ctx->knobs.memset_nodes) return fail(ctx, TDOA_ERR_STATE, "captured step holds a memset node");
+    // graph-mode profiling: an event-record node before the first and after the last kernel of every marked scope
+    for (auto &m : ctx->graph_marks) {
+        if (!m.before || !m.last || m.last == m.before) { m.e0 = m.e1 = nullptr; continue; }
+        HIPCHK(ctx, hipEventCreate(&m.e0));
+        HIPCHK(ctx, hipEventCreate(&m.e1));
+        HIPCHK(ctx, splice_event_record(g, m.last, m.e1));       // (the later place first: `before` keeps its successor until then)
+        HIPCHK(ctx, splice_event_record(g, m.before, m.e0));
+    }
+    HIPCHK(ctx, hipGraphInstantiate(&ctx->graph_exec, g, nullptr, nullptr, 0));
+    ctx->graph_key = key;
+    ctx->graph_once = ctx->once_active;
+    HIPCHK(ctx, hipGraphLaunch(ctx->graph_exec, st));
+    return TDOA_OK;
+}
+
+// after the step has synchronised: add the times of the event-record nodes the step graph holds
+void collect_step_graph_marks(tdoa_ctx *ctx)
+{
+    if (!step_graph_on(ctx) || !ctx->graph_prof) return;
+    for (auto &m : ctx->graph_marks) {
+        float ms = 0;
+        if (m.e0 && m.e1 && hipEventElapsedTime(&ms, m.e0, m.e1) == hipSuccess) {
+            ctx->prof_ms[m.kernel] += ms;
+            ctx->prof_launches[m.kernel] += 1;
+            ctx->prof_bytes[m.kernel] += m.bytes;
+        }
+    }
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -1989,23 +2223,8 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
     if (go && fine_host) return fail(ctx, TDOA_ERR_UNSUPPORTED, "sub-sample refinement with TDOA_LAGS_GO");
     const long long corr_len = go ? go_blocks(wlen, ctx->prm.corr_block) * ctx->prm.corr_block : wlen;
 
-    // Sharding (SURVEY section 8e): window-major -- rank r owns the windows wid = r (mod world), so a station-window
-    // is transformed once and reused by all its pairs.  With fewer windows than ranks that would leave ranks idle:
-    // then the (window, pair) units u = wid*P + p are dealt u = r (mod world) and a rank transforms only the
-    // stations its pairs need (station spectra are duplicated across ranks).
-    const bool pair_major = W < world;
-    auto owns = [&](int wid, int p) { return pair_major ? ((wid * P + p) % world) == rank : (wid % world) == rank; };
-    std::vector<int> mine;
-    for (int w = 0; w < W; w++) {
-        bool any = false;
-        for (int p = 0; p < P && !any; p++) any = owns(w, p);
-        if (any) mine.push_back(w);
-    }
-    // default: every window of this rank in one launch group (launch tails cost more than cache residency gains), bounded
-    // by a third of the device's memory for the workspace (96 GB of an MI355X's 288: cfg4's 99 windows x 36 spectra are one
-    // group of 30 GB; round 3 stopped at 24 GiB and ran them as 85 + 14)
-    int per_batch = ctx->prm.windows_per_batch > 0 ? ctx->prm.windows_per_batch : (int)std::max<size_t>(mine.size(), 1);
     // a launch group of n_sw station-windows and n_pw pair-windows as run_fm_batch sees it
+    const bool pair_major = W < world;       // (build_step_layout's sharding rule)
     auto shape_of = [&](int n_sw, int n_pw, int n_quads) {
         FmBatchShape b = batch_shape(ctx);
         b.n_sw = n_sw;
@@ -2020,76 +2239,21 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
         b.fine = fine_host != nullptr;
         return b;
     };
-    // what reserve_fm_batch asks for per window (+ 1/8: ensure() rounds every buffer up): TZ, the V workspace in the form this
-    // plan's pair step uses, code rows where K1 is materialised
-    const FmBytes by = plan_fm_batch(ctx->knobs, ctx->stg, ctx->n_cu, pl, lag_lo, lag_hi, shape_of(S, P, 0)).bytes;
-    const double bytes_per_window = 1.125 * ((double)by.tz + (double)by.v + (double)by.codes + (double)by.codes_lp);
-    // the bound: a third of the device (tdoa_create), and not more than is FREE now plus what this context already holds of it
-    // (captures attached by the caller, other contexts, other ranks on the same card all count against the device)
-    double limit = ctx->workspace_limit;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const double held = (double)ctx->tz.cap + (double)ctx->v.cap + (double)ctx->codes.cap + (double)ctx->codes_lp.cap;
-            limit = std::min(limit, std::max(0.0, (double)free_b + held - 1073741824.0));      // 1 GiB stays free: descriptors, edges, the runtime
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    per_batch = (int)std::max(1.0, std::min<double>(per_batch, limit / bytes_per_window));
-    // per_batch * S and per_batch * P become gridDim.y of the FFT kernels (HIP limit 65535)
-    if (std::max(S, P) > 65535) return fail(ctx, TDOA_ERR_UNSUPPORTED, "too many station pairs for one launch group");
-    per_batch = std::max(1, std::min(per_batch, 65535 / std::max(S, P)));
-    if (!mine.empty()) {                     // groups of equal size (99 windows at most 85 at a time: 50 + 49, not 85 + 14)
-        const int groups = ((int)mine.size() + per_batch - 1) / per_batch;
-        per_batch = ((int)mine.size() + groups - 1) / groups;
-    }
+    StepLayout lay;
+    if (build_step_layout(S, W, rank, world, batch_bound(ctx, pl, lag_lo, lag_hi, shape_of(S, P, 0)), ctx->quad_cache, &lay))
+        return fail(ctx, TDOA_ERR_UNSUPPORTED, "too many station pairs for one launch group");
+    const int per_batch = lay.per_batch;
+    const size_t n_mine = lay.mine.size();
 
-    // all descriptors, uploaded once; window wi of this rank owns sw[sw_off[wi] .. sw_off[wi+1]) and likewise pw
+    // all descriptors, uploaded once.  TDOA_LAGS_GO: a second copy of the station-window descriptors with the full window
+    // length follows the first
+    const size_t n_sw_all = lay.sw_station.size();
     std::vector<SWDesc> sw;
-    std::vector<PWDesc> pw;
-    std::vector<QuadDesc> quads;
-    std::vector<size_t> sw_off(mine.size() + 1, 0), pw_off(mine.size() + 1, 0), q_off(mine.size() + 1, 0);
-    for (size_t wi = 0; wi < mine.size(); wi++) {
-        const int wid = mine[wi];
-        const size_t batch_base = sw_off[wi - (wi % (size_t)per_batch)];   // PWDesc indices are relative to the batch
-        std::vector<int> slot(S, -1);
-        int p = 0;
-        for (int i = 0; i < S; i++)
-            for (int j = i + 1; j < S; j++, p++) {
-                if (!owns(wid, p)) continue;
-                for (int s : {i, j})
-                    if (slot[s] < 0) {
-                        const long long off = (long long)(wid / wpb) * (long long)(ctx->caps[s].n / 3) + (long long)(wid % wpb) * wlen;
-                        slot[s] = (int)(sw.size() - batch_base);
-                        sw.push_back(SWDesc{ctx->caps[s].dev + 2 * off, (int32_t)corr_len, 0});
-                    }
-                pw.push_back(PWDesc{slot[i], slot[j], wid * P + p, (int32_t)corr_len});
-            }
-        sw_off[wi + 1] = sw.size();
-        pw_off[wi + 1] = pw.size();
-        // segment form: the quad cover of this window's pairs (the same for every window under window-major sharding).
-        // Every pair-window of the rank is in exactly one quad; run_fm_batch takes the quads of a batch or none of them.
-        // (the greedy cover costs O(P S^2) per quad: beyond kMaxQuadStations stations the segment form stays pair by pair)
-        if (pw_off[wi + 1] > pw_off[wi] && S <= kMaxQuadStations) {
-            std::vector<int> owned;
-            std::vector<std::pair<int, int>> st_pairs;
-            p = 0;
-            for (int i = 0; i < S; i++)
-                for (int j = i + 1; j < S; j++, p++)
-                    if (owns(wid, p)) { owned.push_back(p); st_pairs.emplace_back(i, j); }
-            auto it = ctx->quad_cache.find(owned);
-            if (it == ctx->quad_cache.end()) it = ctx->quad_cache.emplace(owned, build_segment_quads(S, st_pairs)).first;
-            const int pw_base = (int)(pw_off[wi] - pw_off[wi - (wi % (size_t)per_batch)]);    // batch-relative pair-window index
-            for (const StationQuad &q : it->second) {
-                QuadDesc d{slot[q.a], q.b >= 0 ? slot[q.b] : -1, slot[q.c], q.d >= 0 ? slot[q.d] : -1, {-1, -1, -1, -1}};
-                for (int o = 0; o < 4; o++)
-                    if (q.pair[o] >= 0) d.pw[o] = pw_base + q.pair[o];
-                quads.push_back(d);
-            }
-        }
-        q_off[wi + 1] = quads.size();
-    }
+    for (size_t wi = 0; wi < n_mine; wi++)
+        for (size_t k = lay.sw_off[wi]; k < lay.sw_off[wi + 1]; k++)
+            sw.push_back(SWDesc{window_iq(ctx, lay.sw_station[k], lay.mine[wi], wpb, wlen), (int32_t)corr_len, 0});
+    for (size_t k = 0; go && k < n_sw_all; k++) sw.push_back(SWDesc{sw[k].base, (int32_t)wlen, 0});
+    for (PWDesc &d : lay.pw) d.len_a = (int32_t)corr_len;
     const size_t slots = (size_t)W * P;
     if (go && corr_len == 0) {                                 // windows of at most one block: (0, 0.0) everywhere (:708-717)
         if (out_host) std::memset(out_host, 0, sizeof(tdoa_peak) * slots);
@@ -2097,15 +2261,14 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
         return TDOA_OK;
     }
     hipStream_t st = ctx->stream;
-    const int n_first = (int)std::min<size_t>(per_batch, mine.size());
+    const int n_first = (int)std::min<size_t>(per_batch, n_mine);
     if ((rc = ensure(ctx, ctx->peaks, sizeof(PeakOut) * slots))) return rc;
     if ((rc = ensure(ctx, ctx->g_keys, sizeof(unsigned long long) * slots))) return rc;
     if ((rc = ensure(ctx, ctx->g_scales, sizeof(double) * slots))) return rc;
     if ((rc = ensure(ctx, ctx->slot_gain, sizeof(double) * slots))) return rc;
-    // TDOA_LAGS_GO: a second copy of the station-window descriptors with the full window length follows the first
-    if ((rc = ensure(ctx, ctx->g_sw_desc, sizeof(SWDesc) * std::max<size_t>(2 * sw.size(), 1)))) return rc;
-    if ((rc = ensure(ctx, ctx->g_pw_desc, sizeof(PWDesc) * std::max<size_t>(pw.size(), 1)))) return rc;
-    if ((rc = ensure(ctx, ctx->g_quad_desc, sizeof(QuadDesc) * std::max<size_t>(quads.size(), 1)))) return rc;
+    if ((rc = ensure(ctx, ctx->g_sw_desc, sizeof(SWDesc) * std::max<size_t>(2 * n_sw_all, 1)))) return rc;
+    if ((rc = ensure(ctx, ctx->g_pw_desc, sizeof(PWDesc) * std::max<size_t>(lay.pw.size(), 1)))) return rc;
+    if ((rc = ensure(ctx, ctx->g_quad_desc, sizeof(QuadDesc) * std::max<size_t>(lay.quads.size(), 1)))) return rc;
     if (fine_host) {
         if ((rc = ensure(ctx, ctx->fine_raw, 3 * sizeof(float) * slots))) return rc;
         if ((rc = ensure(ctx, ctx->fine, sizeof(FineOut) * slots))) return rc;
@@ -2118,36 +2281,16 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
     auto *d_keys = static_cast<unsigned long long *>(ctx->g_keys.p);
     auto *d_scales = static_cast<double *>(ctx->g_scales.p);
 
-    // everything the launches depend on: same key => the captured graph can be replayed as is
-    std::vector<uint64_t> key = {(uint64_t)S, (uint64_t)rank, (uint64_t)world, (uint64_t)per_batch, (uint64_t)wlen,
-                                 (uint64_t)ctx->prm.max_lag | ((uint64_t)ctx->prm.k1_smooth << 32) | ((uint64_t)(ctx->prm.k1_gate != 0) << 62) |
-                                     ((uint64_t)go << 61), (uint64_t)block,
-                                 ctx->alloc_gen, (uint64_t)(fine_host != nullptr), 0};
-    std::memcpy(&key.back(), &gate, sizeof(double));
-    for (const KnobVar &kv : kKnobVars) key.push_back(kv.flag ? (uint64_t)(ctx->knobs.*kv.flag) : (uint64_t)(ctx->knobs.*kv.num));
-    for (auto &c : ctx->caps) {
-        key.push_back((uint64_t)(uintptr_t)c.dev);
-        key.push_back((uint64_t)c.n);
-    }
-    key.push_back(ctx->graph_prof ? 0x100000000ull | ctx->prof_mask : 0ull);      // an instrumented step is a different graph
-    const bool graph_ok = ctx->knobs.use_graph && !ctx->profiling;
-    const bool replay = graph_ok && ctx->graph_exec && key == ctx->graph_key;
-
-    std::vector<SWDesc> sw_full;
-    if (!replay) {
+    const std::vector<uint64_t> key = step_graph_key(ctx, rank, world, per_batch, wlen, block, go, fine_host != nullptr, gate);
+    if (!step_graph_replays(ctx, key)) {
         std::vector<double> scales(slots, 1.0 / (4.0 * (double)n * std::sqrt((double)corr_len)));
         HIPCHK(ctx, hipMemcpyAsync(d_scales, scales.data(), sizeof(double) * slots, hipMemcpyHostToDevice, st));
         if (!sw.empty()) {
             HIPCHK(ctx, hipMemcpyAsync(d_sw, sw.data(), sizeof(SWDesc) * sw.size(), hipMemcpyHostToDevice, st));
-            if (go) {
-                sw_full = sw;
-                for (auto &d : sw_full) d.len = (int32_t)wlen;
-                HIPCHK(ctx, hipMemcpyAsync(d_sw + sw.size(), sw_full.data(), sizeof(SWDesc) * sw.size(), hipMemcpyHostToDevice, st));
-            }
-            HIPCHK(ctx, hipMemcpyAsync(d_pw, pw.data(), sizeof(PWDesc) * pw.size(), hipMemcpyHostToDevice, st));
+            HIPCHK(ctx, hipMemcpyAsync(d_pw, lay.pw.data(), sizeof(PWDesc) * lay.pw.size(), hipMemcpyHostToDevice, st));
         }
-        if (!quads.empty())
-            HIPCHK(ctx, hipMemcpyAsync(d_quads, quads.data(), sizeof(QuadDesc) * quads.size(), hipMemcpyHostToDevice, st));
+        if (!lay.quads.empty())
+            HIPCHK(ctx, hipMemcpyAsync(d_quads, lay.quads.data(), sizeof(QuadDesc) * lay.quads.size(), hipMemcpyHostToDevice, st));
 
         HIPCHK(ctx, hipStreamSynchronize(st));   // host vectors go out of scope below
     }
@@ -2159,12 +2302,12 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
         else
             hipLaunchKernelGGL(k_zero_u64, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, d_keys, slots);
         float *fine_raw = fine_host ? static_cast<float *>(ctx->fine_raw.p) : nullptr;
-        for (size_t w0 = 0; w0 < mine.size(); w0 += per_batch) {
-            const int nw = (int)std::min<size_t>(per_batch, mine.size() - w0);
-            const int n_sw = (int)(sw_off[w0 + nw] - sw_off[w0]), n_pw = (int)(pw_off[w0 + nw] - pw_off[w0]);
-            const FmBufs bf{d_sw + sw_off[w0], go ? d_sw + sw.size() + sw_off[w0] : nullptr, d_pw + pw_off[w0], d_quads + q_off[w0],
-                            d_keys, nullptr, 1.0f, (double)wlen * n_sw, fine_raw};
-            const int r = run_fm_batch(ctx, shape_of(n_sw, n_pw, (int)(q_off[w0 + nw] - q_off[w0])), pl, lag_lo, lag_hi, bf);
+        for (size_t w0 = 0; w0 < n_mine; w0 += per_batch) {
+            const int nw = (int)std::min<size_t>(per_batch, n_mine - w0);
+            const int n_sw = (int)(lay.sw_off[w0 + nw] - lay.sw_off[w0]), n_pw = (int)(lay.pw_off[w0 + nw] - lay.pw_off[w0]);
+            const FmBufs bf{d_sw + lay.sw_off[w0], go ? d_sw + n_sw_all + lay.sw_off[w0] : nullptr, d_pw + lay.pw_off[w0],
+                            d_quads + lay.q_off[w0], d_keys, nullptr, 1.0f, (double)wlen * n_sw, fine_raw};
+            const int r = run_fm_batch(ctx, shape_of(n_sw, n_pw, (int)(lay.q_off[w0 + nw] - lay.q_off[w0])), pl, lag_lo, lag_hi, bf);
             if (r) return r;
         }
         // (every batch of a step takes the same path: same plan, same lag range, same lengths)
@@ -2178,75 +2321,8 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
                            static_cast<PeakOut *>(ctx->peaks.p), (int)slots, slot_gain);
         return TDOA_OK;
     };
+    if ((rc = run_step_graph(ctx, key, enqueue))) return rc;
 
-    if (replay) {
-        ctx->once_active = ctx->graph_once;
-        HIPCHK(ctx, hipGraphLaunch(ctx->graph_exec, st));
-    } else if (graph_ok) {
-        if (ctx->graph_exec) { (void)hipGraphExecDestroy(ctx->graph_exec); ctx->graph_exec = nullptr; }
-        if (ctx->graph) { (void)hipGraphDestroy(ctx->graph); ctx->graph = nullptr; }
-        ctx->graph_key.clear();
-        HIPCHK(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        clear_graph_marks(ctx);
-        ctx->capturing = true;
-        rc = enqueue();
-        ctx->capturing = false;
-        hipGraph_t g = nullptr;
-        hipError_t e = hipStreamEndCapture(st, &g);
-        if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-        if (e != hipSuccess) return fail(ctx, TDOA_ERR_HIP, "hipStreamEndCapture", e);
-        ctx->graph = g;
-        // the step was captured from ONE stream: it must come out as one dependency chain -- every node but the first has
-        // a predecessor (a node without one would replay unordered against the kernels that feed or consume it)
-        {
-            size_t n_nodes = 0, n_edges = 0, n_roots = 0;
-            HIPCHK(ctx, hipGraphGetNodes(g, nullptr, &n_nodes));
-            HIPCHK(ctx, hipGraphGetEdges(g, nullptr, nullptr, &n_edges));
-            HIPCHK(ctx, hipGraphGetRootNodes(g, nullptr, &n_roots));
-            std::vector<hipGraphNode_t> nodes(n_nodes);
-            if (n_nodes) HIPCHK(ctx, hipGraphGetNodes(g, nodes.data(), &n_nodes));
-            int memsets = 0;
-            for (hipGraphNode_t nd : nodes) {
-                hipGraphNodeType ty;
-                if (hipGraphNodeGetType(nd, &ty) == hipSuccess && ty == hipGraphNodeTypeMemset) memsets++;
-            }
-            ctx->graph_nodes = (int)n_nodes;
-            ctx->graph_edges = (int)n_edges;
-            ctx->graph_roots = (int)n_roots;
-            ctx->graph_memsets = memsets;
-            if (n_nodes && (n_roots != 1 || n_edges + 1 < n_nodes))
-                return fail(ctx, TDOA_ERR_STATE, "captured step is not one dependency chain");
-            if (memsets && !ctx->knobs.memset_nodes) return fail(ctx, TDOA_ERR_STATE, "captured step holds a memset node");
-        }
-        // graph-mode profiling: an event-record node before the first and after the last kernel of every marked scope
-        for (auto &m : ctx->graph_marks) {
-            if (!m.before || !m.last || m.last == m.before) { m.e0 = m.e1 = nullptr; continue; }
-            HIPCHK(ctx, hipEventCreate(&m.e0));
-            HIPCHK(ctx, hipEventCreate(&m.e1));
-            auto splice = [&](hipGraphNode_t after, hipEvent_t ev) -> hipError_t {      // after -> [record ev] -> after's successors
-                size_t nd = 0;
-                hipError_t r = hipGraphNodeGetDependentNodes(after, nullptr, &nd);
-                if (r != hipSuccess) return r;
-                std::vector<hipGraphNode_t> succ(nd);
-                if (nd && (r = hipGraphNodeGetDependentNodes(after, succ.data(), &nd)) != hipSuccess) return r;
-                hipGraphNode_t rec = nullptr;
-                for (hipGraphNode_t sn : succ)
-                    if ((r = hipGraphRemoveDependencies(g, &after, &sn, 1)) != hipSuccess) return r;
-                if ((r = hipGraphAddEventRecordNode(&rec, g, &after, 1, ev)) != hipSuccess) return r;
-                for (hipGraphNode_t sn : succ)
-                    if ((r = hipGraphAddDependencies(g, &rec, &sn, 1)) != hipSuccess) return r;
-                return hipSuccess;
-            };
-            HIPCHK(ctx, splice(m.last, m.e1));       // (the later place first: `before` keeps its successor until then)
-            HIPCHK(ctx, splice(m.before, m.e0));
-        }
-        HIPCHK(ctx, hipGraphInstantiate(&ctx->graph_exec, g, nullptr, nullptr, 0));
-        ctx->graph_key = key;
-        ctx->graph_once = ctx->once_active;
-        HIPCHK(ctx, hipGraphLaunch(ctx->graph_exec, st));
-    } else {
-        if ((rc = enqueue())) return rc;
-    }
     if (out_dev)
         HIPCHK(ctx, hipMemcpyAsync(out_dev, ctx->peaks.p, sizeof(PeakOut) * slots, hipMemcpyDeviceToDevice, st));
     if (out_host)
@@ -2255,15 +2331,7 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
         HIPCHK(ctx, hipMemcpyAsync(fine_host, ctx->fine.p, sizeof(FineOut) * slots, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     prof_collect(ctx);
-    if (graph_ok && ctx->graph_prof)            // the replay just finished: read the event-record nodes of this step
-        for (auto &m : ctx->graph_marks) {
-            float ms = 0;
-            if (m.e0 && m.e1 && hipEventElapsedTime(&ms, m.e0, m.e1) == hipSuccess) {
-                ctx->prof_ms[m.kernel] += ms;
-                ctx->prof_launches[m.kernel] += 1;
-                ctx->prof_bytes[m.kernel] += m.bytes;
-            }
-        }
+    collect_step_graph_marks(ctx);
     return TDOA_OK;
 }
 
@@ -2341,8 +2409,7 @@ int tdoa_window_quality_all(tdoa_ctx *ctx, int rank, int world, tdoa_window_qual
     for (size_t wi = 0; wi < mine.size(); wi++) {
         const int wid = mine[wi];
         for (int s = 0; s < S; s++) {
-            const long long off = (long long)(wid / wpb) * (long long)(ctx->caps[s].n / 3) + (long long)(wid % wpb) * wlen;
-            sw[wi * S + s] = SWDesc{ctx->caps[s].dev + 2 * off, (int32_t)wlen, 0};
+            sw[wi * S + s] = SWDesc{window_iq(ctx, s, wid, wpb, wlen), (int32_t)wlen, 0};
         }
     }
     if ((rc = ensure(ctx, ctx->g_sw_desc, sizeof(SWDesc) * std::max<size_t>(sw.size(), 1)))) return rc;
@@ -2478,6 +2545,33 @@ int tdoa_debug_staged_groups(int n_stations, int max_pairs, uint32_t *masks_out,
         std::memcpy(pairs_out + 16 * i, g[i].pair, 16);
     }
     return (int)g.size();
+}
+
+int tdoa_debug_step_layout(int n_stations, int n_windows, int rank, int world, int max_per_batch, int32_t *pw_out, int max_pw,
+                           int32_t *quads_out, int32_t *n_quads)
+{
+    if (n_stations < 2 || n_windows < 1 || world < 1 || rank < 0 || rank >= world || max_per_batch < 1 || max_pw < 0 ||
+        (max_pw && (!pw_out || !quads_out)) || !n_quads)
+        return -TDOA_ERR_INVALID;
+    QuadCache cache;
+    StepLayout L;
+    if (int rc = build_step_layout(n_stations, n_windows, rank, world, max_per_batch, cache, &L)) return -rc;
+    if ((int)L.pw.size() > max_pw) return -TDOA_ERR_INVALID;
+    for (size_t wi = 0; wi < L.mine.size(); wi++) {
+        const size_t batch = wi / L.per_batch, sw_base = L.sw_off[batch * L.per_batch];
+        for (size_t k = L.pw_off[wi]; k < L.pw_off[wi + 1]; k++) {
+            const PWDesc &d = L.pw[k];
+            const int32_t rec[6] = {d.out_index, (int32_t)batch, d.sw_a, d.sw_b, L.sw_station[sw_base + d.sw_a], L.sw_station[sw_base + d.sw_b]};
+            std::memcpy(pw_out + 6 * k, rec, sizeof(rec));
+        }
+        for (size_t k = L.q_off[wi]; k < L.q_off[wi + 1]; k++) {      // at most one quad per pair-window
+            const QuadDesc &q = L.quads[k];
+            const int32_t rec[9] = {(int32_t)batch, q.sw_ta, q.sw_tb, q.sw_sc, q.sw_sd, q.pw[0], q.pw[1], q.pw[2], q.pw[3]};
+            std::memcpy(quads_out + 9 * k, rec, sizeof(rec));
+        }
+    }
+    *n_quads = (int32_t)L.quads.size();
+    return (int)L.pw.size();
 }
 
 int tdoa_debug_graph_info(tdoa_ctx *ctx, int32_t info[4], const char *dot_path)

@@ -72,7 +72,7 @@ SYMBOLS = [
     "tdoa_num_windows", "tdoa_num_pairs", "tdoa_process", "tdoa_process_u8",
     "tdoa_process_fine", "tdoa_fm_xcorr_fine_u8", "tdoa_window_quality_all", "tdoa_window_quality_u8",
     "tdoa_fm_xcorr_u8", "tdoa_fm_preprocess_u8", "tdoa_fm_xcorr_lags_u8", "tdoa_debug_force_generic",
-    "tdoa_debug_flags", "tdoa_debug_last_k1", "tdoa_debug_graph_info", "tdoa_debug_segment_quads", "tdoa_debug_staged_groups", "tdoa_cross_correlate_batch_c64",
+    "tdoa_debug_flags", "tdoa_debug_last_k1", "tdoa_debug_graph_info", "tdoa_debug_segment_quads", "tdoa_debug_staged_groups", "tdoa_debug_step_layout", "tdoa_cross_correlate_batch_c64",
     "tdoa_latlon_to_ecef", "tdoa_ecef_to_latlon", "tdoa_solve_3station", "tdoa_solve_nstation", "tdoa_solve_surface",
     "tdoa_profile_enable", "tdoa_profile_select", "tdoa_profile_reset", "tdoa_profile_get", "tdoa_kernel_name",
     "tdoa_plan_info",
@@ -146,6 +146,8 @@ def load(build_if_missing=True):
     L.tdoa_debug_graph_info.argtypes = [vp, C.POINTER(C.c_int32), C.c_char_p]
     L.tdoa_debug_segment_quads.argtypes = [C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int]
     L.tdoa_debug_staged_groups.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_int]
+    L.tdoa_debug_step_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.tdoa_latlon_to_ecef.argtypes = [C.c_double, C.c_double, C.c_double, dp]
     L.tdoa_latlon_to_ecef.restype = None
     L.tdoa_ecef_to_latlon.argtypes = [C.c_double, C.c_double, C.c_double, dp]
@@ -566,3 +568,20 @@ def solve_surface(stations_lle, range_diff, weights=None, height_m=0.0):
     rc = load().tdoa_solve_surface(_d(st.reshape(-1)), n, _d(rd), _d(wt) if wt is not None else None, float(height_m),
                                    _d(out), C.byref(it))
     return rc, out, it.value
+
+
+def step_layout(n_stations, n_windows, rank, world, max_per_batch=2**31 - 1):
+    """host only: what tdoa_process(rank, world) runs, as tdoa_debug_step_layout lays it out -- (pair-windows, quads):
+    rows [unit, group, slot a, slot b, station of slot a, station of slot b] in launch order, and
+    rows [group, slot a, slot b, slot c, slot d, pw(a,c), pw(a,d), pw(b,c), pw(b,d)] with group-relative indices"""
+    n_pairs = n_stations * (n_stations - 1) // 2
+    cap = max(n_windows * n_pairs, 1)
+    pw = np.zeros((cap, 6), dtype=np.int32)
+    quads = np.zeros((cap, 9), dtype=np.int32)
+    nq = C.c_int32(0)
+    n = load().tdoa_debug_step_layout(int(n_stations), int(n_windows), int(rank), int(world), int(max_per_batch),
+                                      pw.ctypes.data_as(C.POINTER(C.c_int32)), cap,
+                                      quads.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nq))
+    if n < 0:
+        raise ValueError("tdoa_debug_step_layout: error %d" % -n)
+    return pw[:n], quads[:nq.value]

@@ -161,6 +161,58 @@ def test_unit_ownership_window_major_and_pair_major():
     assert set(owners) == set(range(8))
 
 
+def test_step_layout_matches_sharding_and_the_launch_group_rule(capi):
+    """the library's step layout (build_step_layout, tdoa_mi355x.hip) against tdoa_amd/sharding.py: every (window, pair)
+    unit owned once, by unit_owner; n owned windows under a bound b run as g = ceil(n / b) launch groups of ceil(n / g)
+    windows, the last one short; group-relative station-window slots dense from 0, each holding one station's window, the
+    pair's two stations for every pair-window; every pair-window of a group in exactly one of that group's quads"""
+    from tdoa_amd import sharding
+    quad_slots = ((1, 3), (1, 4), (2, 3), (2, 4))          # (a,c), (a,d), (b,c), (b,d) as columns of a quad row
+    for S in range(2, 17):
+        P = S * (S - 1) // 2
+        pairs = np.array([(i, j) for i in range(S) for j in range(i + 1, S)])
+        for W in (3, 6, 21, 99):
+            for world in (1, 2, 3, 8):
+                for bound in (1, 4, 2**31 - 1):
+                    owner = np.full(W * P, -1)
+                    for rank in range(world):
+                        pw, quads = capi.step_layout(S, W, rank, world, bound)
+                        units, group = pw[:, 0], pw[:, 1]
+                        assert len(np.unique(units)) == len(units) and (owner[units] == -1).all()
+                        owner[units] = rank
+                        wid = units // P
+                        assert (np.diff(wid) >= 0).all()                        # launch order: window by window
+                        windows, wi = np.unique(wid, return_inverse=True)
+                        n = len(windows)
+                        if n == 0:
+                            assert len(quads) == 0
+                            continue
+                        b = min(bound, 65535 // max(S, P))
+                        g = -(-n // b)
+                        per_batch = -(-n // g)
+                        assert per_batch * max(S, P) <= 65535
+                        assert (group == wi // per_batch).all() and group.max() == g - 1
+                        assert (pairs[units % P] == pw[:, 4:6]).all()
+                        for k in range(g):
+                            rows = pw[group == k]
+                            held = {}
+                            for (sa, sb, ta, tb), w in zip(rows[:, 2:6].tolist(), wid[group == k].tolist()):
+                                assert held.setdefault(sa, (ta, w)) == (ta, w) and held.setdefault(sb, (tb, w)) == (tb, w)
+                            assert sorted(held) == list(range(len(held)))
+                            seen = []
+                            for q in quads[quads[:, 0] == k].tolist():
+                                for o, (t, s) in enumerate(quad_slots):
+                                    if q[5 + o] >= 0:
+                                        assert rows[q[5 + o], 2:4].tolist() == [q[t], q[s]]
+                                        seen.append(q[5 + o])
+                            assert sorted(seen) == list(range(len(rows)))
+                    assert (owner == [sharding.unit_owner(u // P, u % P, world, W, P) for u in range(W * P)]).all()
+    with pytest.raises(ValueError, match="error 5"):            # TDOA_ERR_UNSUPPORTED: a window's pairs exceed the grid limit
+        capi.step_layout(363, 3, 0, 1)
+    with pytest.raises(ValueError, match="error 1"):
+        capi.step_layout(4, 3, 2, 2)
+
+
 
 def test_nstation_solver_ignores_a_zero_weight_outlier(capi):
     """the plausibility gate hands a pair weight 0: a wildly wrong range difference on that pair must not move the fix"""
