@@ -296,7 +296,8 @@ enum {
                                         instead of one workgroup per pair-window that keeps the column sums in registers
                                         (k_small_rows_col_peak; environment: TDOA_NO_SMALL_FUSED=1)                            */
     TDOA_DEBUG_SMALL_FUSED_ALWAYS = 65536 /* (switches a form ON) ... for any number of pair-windows; the library takes it from
-                                        1024 pair-windows per launch on (environment: TDOA_SMALL_FUSED_ALWAYS=1)              */
+                                        1024 pair-windows per launch on (environment: TDOA_SMALL_FUSED_ALWAYS=1).  Never in a
+                                        batch that refines: the refinement reads V', which the one kernel does not write      */
 };
 int tdoa_debug_flags(tdoa_ctx *ctx, unsigned flags);
 /* inspection: the K1 statistics of station-window `sw_index` of the last batch (the order of the batch's descriptors:
@@ -307,6 +308,43 @@ int tdoa_debug_last_k1(tdoa_ctx *ctx, int sw_index, tdoa_fm_stats *stats, int32_
  * dot_path (may be NULL): also writes the graph in Graphviz form (hipGraphDebugDotPrint).  The library itself refuses a
  * captured step that is not ONE dependency chain of kernel nodes (TDOA_ERR_STATE), see DESIGN.md section 7. */
 int tdoa_debug_graph_info(tdoa_ctx *ctx, int32_t info[4], const char *dot_path);
+/* tests only: fill the context's float workspaces -- G, V, V', the edge sums, the staged spectra and the segment sums (one
+ * buffer), TZ, the refinement's raw neighbours and the single-look edge sums -- over their whole capacity with a quiet NaN
+ * (0x7FC00000), then synchronise.  A later call that reads a value it did not write shows NaN instead of an earlier call's
+ * bytes.  Buffers of integers, descriptors, peak keys, statistics or phase codes are left alone; unallocated ones are
+ * skipped.  TDOA_ERR_INVALID for a NULL context. */
+int tdoa_debug_poison_workspace(tdoa_ctx *ctx);
+/* tests only (host): the kernel forms of the last batch the library planned (for a replayed step graph: of the batch it
+ * captured).  info[TDOA_ROUTE_*] below; TDOA_ERR_STATE before any batch ran. */
+enum {
+    TDOA_ROUTE_INVERSE = 0,      /* TDOA_INV_*                                                                         */
+    TDOA_ROUTE_PAIR_STEP = 1,    /* TDOA_STEP_* (the decimated inverse's pair step; TDOA_STEP_TILES otherwise)          */
+    TDOA_ROUTE_COL_PASS = 2,     /* TDOA_COL_*                                                                         */
+    TDOA_ROUTE_ROW_PASS = 3,     /* TDOA_ROW_*                                                                         */
+    TDOA_ROUTE_FK = 4,           /* short-lag form: column blocks of 256 per side (0: not that form)                   */
+    TDOA_ROUTE_SEG_PQ = 5,       /* segment form: search reach in units of 256 lags (0: not that form)                 */
+    TDOA_ROUTE_SEG_QUADS = 6,    /* 0/1 below: station quads chosen (only the segment form uses them)                  */
+    TDOA_ROUTE_SEG_PACK3 = 7,    /* segment form reads 3-byte codes                                                    */
+    TDOA_ROUTE_FUSED_K1 = 8,     /* discriminator inside the forward column kernels                                    */
+    TDOA_ROUTE_ONCE = 9,         /* single-look K1                                                                      */
+    TDOA_ROUTE_SMALL_FUSED = 10, /* the decimated inverse's small plan in one kernel (k_small_rows_col_peak)             */
+    TDOA_ROUTE_PRUNED = 11,      /* pruned inverse column pass                                                          */
+    TDOA_ROUTE_XCD_PAIRS = 12,   /* k_inv_row_pair4096 on its XCD-grouped 1-D grid                                      */
+    TDOA_ROUTE_DEC_GP = 13,      /* k_pair_decimate16 on its XCD-grouped grid                                           */
+    TDOA_ROUTE_STG_FOLDED = 14,  /* staged column walk without a loader wave                                            */
+    TDOA_ROUTE_STG_BLOCKED = 15  /* staged column walk reads spectra in blocks of 64 columns                             */
+};
+enum { TDOA_INV_NONE = 0, TDOA_INV_SEGMENTS = 1, TDOA_INV_DECIMATED = 2, TDOA_INV_SHORT_LAG = 3, TDOA_INV_FULL = 4 };
+enum { TDOA_STEP_TILES = 0, TDOA_STEP_COLUMNS = 1, TDOA_STEP_STAGED = 2 };
+enum {
+    TDOA_COL_NONE = 0, TDOA_COL_K1_256 = 1, TDOA_COL_K1_512 = 2, TDOA_COL_K1_TWO_SWEEP = 3, TDOA_COL_C256 = 4,
+    TDOA_COL_TWO_SWEEP = 5, TDOA_COL_SHORT16X = 6, TDOA_COL_COLX = 7, TDOA_COL_GENERIC = 8
+};
+enum {
+    TDOA_ROW_NONE = 0, TDOA_ROW_UNPACK_BLOCKS = 1, TDOA_ROW_UNPACK_IN_PLACE = 2, TDOA_ROW_UNPACK_TILES = 3, TDOA_ROW_HOT = 4,
+    TDOA_ROW_GENERIC = 5
+};
+int tdoa_debug_last_route(const tdoa_ctx *ctx, int32_t info[16]);
 /* tests only (host, no GPU): the cover of a window's station pairs by "quads" -- two template stations x two signal
  * stations whose two packed transforms per segment serve up to four pairs in the segment form.
  * pairs[2 i], pairs[2 i + 1] = template, signal station of pair i; quads_out gets 8 ints per quad: stations a, b, c, d

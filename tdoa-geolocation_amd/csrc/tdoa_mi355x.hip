@@ -177,6 +177,9 @@ struct tdoa_ctx {
     int graph_nodes = 0, graph_edges = 0, graph_roots = 0, graph_memsets = 0;      // structure of the captured step (tdoa_debug_graph_info)
     bool once_active = false;               // the last step (run_fm_batch, or the replayed graph) took the single-look path: decode multiplies by slot_gain
     bool graph_once = false;                // ... of the step the cached graph holds (a pair call on another path in between must not change what a replay reports)
+    int32_t route[16] = {0};                // the last batch's FmRoute as tdoa_debug_last_route reports it (route_info)
+    int32_t graph_route[16] = {0};          // ... of the batch the cached graph captured last
+    bool route_set = false;
     DevBuf once_edges, once_tiles, once_fin, slot_gain;
     // decimated inverse (k_pair_decimate16): FIR taps and window correction for (Nc, reach); small plan of the R-point inverse
     DevBuf dec_taps, dec_gain;
@@ -977,7 +980,9 @@ FmRoute plan_fm_batch(const Knobs &k, const StgTables &t, int n_cu, const FftPla
         // plans).  One workgroup per pair-window and CU at a time: for batches of a thousand pair-windows and more -- cfg5
         // (4500 per launch, 32 rows each) 25.2 -> 21.7 ms per step, cfg4 (2772, 16 rows) 1.26 -> 1.24; cfg2's 297 pair-windows
         // are one round and a tail of such workgroups (0.165 -> 0.253 ms) and keep the two kernels.
-        r.small_fused = k.small_fused && r.np2 == 3 && r.nn2 == 3 && r.ps2.odd == 1 && r.ps2.N1 == 4096 && r.ps2.N2 >= 8 &&
+        // Not for a batch that refines: the refinement reads the peak's neighbours out of V' (launch_refine), which this
+        // kernel never writes -- such a batch runs the two kernels, whose integer peaks carry the same bits.
+        r.small_fused = k.small_fused && !b.fine && r.np2 == 3 && r.nn2 == 3 && r.ps2.odd == 1 && r.ps2.N1 == 4096 && r.ps2.N2 >= 8 &&
                         (n_pw >= 1024 || k.small_fused_always);
     }
     if (r.seg_chunks) r.row = RowPass::None;
@@ -1310,6 +1315,17 @@ void launch_refine(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
                            static_cast<const float *>(nullptr), bf.oc);
 }
 
+// a route as tdoa_debug_last_route reports it (include/tdoa_mi355x.h TDOA_ROUTE_*, numbered as the enums here)
+static_assert((int)Inverse::Full == TDOA_INV_FULL && (int)Inverse::Decimated == TDOA_INV_DECIMATED, "TDOA_INV_*");
+static_assert((int)PairStep::Staged == TDOA_STEP_STAGED && (int)ColPass::Generic == TDOA_COL_GENERIC &&
+              (int)RowPass::Generic == TDOA_ROW_GENERIC && (int)RowPass::UnpackTiles == TDOA_ROW_UNPACK_TILES, "TDOA_STEP/COL/ROW_*");
+void route_info(const FmRoute &r, int32_t out[16])
+{
+    const int32_t v[16] = {(int32_t)r.inv, (int32_t)r.step, (int32_t)r.col, (int32_t)r.row, r.fk, r.seg_pq, r.seg_quads, r.seg_pack3,
+                           r.fused_k1, r.once, r.small_fused, r.pruned, r.xcd_pairs > 0, r.dec_gp > 0, r.stg.folded, r.stg.blocked};
+    std::memcpy(out, v, sizeof(v));
+}
+
 // ---- mode B core: K1 + forward transforms + inverse + peak pick over descriptors already in device memory
 int run_fm_batch(tdoa_ctx *ctx, const FmBatchShape &shape, const FftPlan &pl, int lag_lo, int lag_hi, FmBufs bf)
 {
@@ -1318,6 +1334,8 @@ int run_fm_batch(tdoa_ctx *ctx, const FmBatchShape &shape, const FftPlan &pl, in
     int rc;
     if ((rc = reserve_fm_batch(ctx, r))) return rc;
     ctx->once_active = r.once;
+    route_info(r, ctx->route);
+    ctx->route_set = true;
     bf.st = ctx->stream;
     bf.stats = static_cast<FmStats *>(ctx->stats.p);
     bf.tz = static_cast<float2 *>(ctx->tz.p);
@@ -1721,6 +1739,7 @@ int run_step_graph(tdoa_ctx *ctx, const std::vector<uint64_t> &key, const std::f
     hipStream_t st = ctx->stream;
     if (step_graph_replays(ctx, key)) {
         ctx->once_active = ctx->graph_once;
+        std::memcpy(ctx->route, ctx->graph_route, sizeof(ctx->route));
         HIPCHK(ctx, hipGraphLaunch(ctx->graph_exec, st));
         return TDOA_OK;
     }
@@ -1769,6 +1788,7 @@ int run_step_graph(tdoa_ctx *ctx, const std::vector<uint64_t> &key, const std::f
     HIPCHK(ctx, hipGraphInstantiate(&ctx->graph_exec, g, nullptr, nullptr, 0));
     ctx->graph_key = key;
     ctx->graph_once = ctx->once_active;
+    std::memcpy(ctx->graph_route, ctx->route, sizeof(ctx->route));
     HIPCHK(ctx, hipGraphLaunch(ctx->graph_exec, st));
     return TDOA_OK;
 }
@@ -2602,6 +2622,25 @@ int tdoa_debug_graph_info(tdoa_ctx *ctx, int32_t info[4], const char *dot_path)
             std::fclose(f);
         }
     }
+    return TDOA_OK;
+}
+
+int tdoa_debug_poison_workspace(tdoa_ctx *ctx)
+{
+    if (!ctx) return TDOA_ERR_INVALID;
+    // floats only: no kernel derives an index from a value in these buffers (peak lags come from the keys, which are not
+    // poisoned), so a NaN can end up in a result but never in an address
+    for (DevBuf *b : {&ctx->v, &ctx->tz, &ctx->fine_raw, &ctx->once_edges})
+        if (b->p && b->cap >= 4) HIPCHK(ctx, hipMemsetD32Async(static_cast<hipDeviceptr_t>(b->p), 0x7FC00000, b->cap / 4, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return TDOA_OK;
+}
+
+int tdoa_debug_last_route(const tdoa_ctx *ctx, int32_t info[16])
+{
+    if (!ctx || !info) return TDOA_ERR_INVALID;
+    if (!ctx->route_set) return TDOA_ERR_STATE;
+    std::memcpy(info, ctx->route, sizeof(ctx->route));
     return TDOA_OK;
 }
 

@@ -49,6 +49,15 @@ FINE_DTYPE = np.dtype([("delay", np.float64), ("frac", np.float32), ("y", np.flo
                        ("reserved", np.int32)])
 
 
+# tdoa_debug_last_route: the names of include/tdoa_mi355x.h's TDOA_INV_*, TDOA_STEP_*, TDOA_COL_*, TDOA_ROW_* in number order
+ROUTE_INVERSE = ["none", "segments", "decimated", "short_lag", "full"]
+ROUTE_PAIR_STEP = ["tiles", "columns", "staged"]
+ROUTE_COL_PASS = ["none", "k1_256", "k1_512", "k1_two_sweep", "c256", "two_sweep", "short16x", "colx", "generic"]
+ROUTE_ROW_PASS = ["none", "unpack_blocks", "unpack_in_place", "unpack_tiles", "hot", "generic"]
+ROUTE_FLAGS = ["seg_quads", "seg_pack3", "fused_k1", "once", "small_fused", "pruned", "xcd_pairs", "dec_gp", "stg_folded",
+               "stg_blocked"]
+
+
 class FastAnalysis(C.Structure):
     _fields_ = [("total_samples", C.c_int32), ("has_clipping", C.c_int32), ("has_overload", C.c_int32),
                 ("reserved", C.c_int32), ("i_avg", C.c_double), ("q_avg", C.c_double), ("i_std", C.c_double),
@@ -72,7 +81,7 @@ SYMBOLS = [
     "tdoa_num_windows", "tdoa_num_pairs", "tdoa_process", "tdoa_process_u8",
     "tdoa_process_fine", "tdoa_fm_xcorr_fine_u8", "tdoa_window_quality_all", "tdoa_window_quality_u8",
     "tdoa_fm_xcorr_u8", "tdoa_fm_preprocess_u8", "tdoa_fm_xcorr_lags_u8", "tdoa_debug_force_generic",
-    "tdoa_debug_flags", "tdoa_debug_last_k1", "tdoa_debug_graph_info", "tdoa_debug_segment_quads", "tdoa_debug_staged_groups", "tdoa_debug_step_layout", "tdoa_cross_correlate_batch_c64",
+    "tdoa_debug_flags", "tdoa_debug_last_k1", "tdoa_debug_graph_info", "tdoa_debug_poison_workspace", "tdoa_debug_last_route", "tdoa_debug_segment_quads", "tdoa_debug_staged_groups", "tdoa_debug_step_layout", "tdoa_cross_correlate_batch_c64",
     "tdoa_latlon_to_ecef", "tdoa_ecef_to_latlon", "tdoa_solve_3station", "tdoa_solve_nstation", "tdoa_solve_surface",
     "tdoa_profile_enable", "tdoa_profile_select", "tdoa_profile_reset", "tdoa_profile_get", "tdoa_kernel_name",
     "tdoa_plan_info",
@@ -144,6 +153,8 @@ def load(build_if_missing=True):
     L.tdoa_debug_flags.argtypes = [vp, C.c_uint]
     L.tdoa_debug_last_k1.argtypes = [vp, C.c_int, C.POINTER(FmStats), C.POINTER(C.c_int32)]
     L.tdoa_debug_graph_info.argtypes = [vp, C.POINTER(C.c_int32), C.c_char_p]
+    L.tdoa_debug_poison_workspace.argtypes = [vp]
+    L.tdoa_debug_last_route.argtypes = [vp, C.POINTER(C.c_int32)]
     L.tdoa_debug_segment_quads.argtypes = [C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int]
     L.tdoa_debug_staged_groups.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_int]
     L.tdoa_debug_step_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
@@ -437,6 +448,22 @@ class Context:
         info = (C.c_int32 * 4)()
         self._chk(self._L.tdoa_debug_graph_info(self._h, info, dot_path.encode() if dot_path else None))
         return dict(nodes=info[0], edges=info[1], roots=info[2], memsets=info[3])
+
+    def poison_workspace(self):
+        """fill the float workspaces with NaN (tdoa_debug_poison_workspace): a later call that reads what it did not write
+        then shows NaN instead of an earlier call's values"""
+        self._chk(self._L.tdoa_debug_poison_workspace(self._h))
+
+    def last_route(self):
+        """the kernel forms of the last batch planned, or of the batch the replayed step graph captured
+        (tdoa_debug_last_route): {"inverse", "pair_step", "col_pass", "row_pass": names; "fk", "seg_pq": numbers; the
+        ROUTE_FLAGS: bools}"""
+        info = (C.c_int32 * 16)()
+        self._chk(self._L.tdoa_debug_last_route(self._h, info))
+        out = dict(inverse=ROUTE_INVERSE[info[0]], pair_step=ROUTE_PAIR_STEP[info[1]], col_pass=ROUTE_COL_PASS[info[2]],
+                   row_pass=ROUTE_ROW_PASS[info[3]], fk=info[4], seg_pq=info[5])
+        out.update((name, bool(info[6 + k])) for k, name in enumerate(ROUTE_FLAGS))
+        return out
 
     def fm_stats(self, iq):
         """window statistics from the reduce-only pass of the fused path (tdoa_fm_preprocess_u8 with out_f32 = NULL)"""

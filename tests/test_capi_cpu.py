@@ -70,6 +70,26 @@ def test_invalid_params_rejected(capi):
     L.tdoa_destroy(None)                    # must be a no-op
 
 
+def test_workspace_poison_and_route_hooks_refuse_a_null_context(capi):
+    """the test hooks behind tests/test_gpu_refine_routes.py: exported, bound, and host-side safe without a context"""
+    import ctypes as C
+    L = capi.load()
+    assert "tdoa_debug_poison_workspace" in capi.SYMBOLS and "tdoa_debug_last_route" in capi.SYMBOLS
+    info = (C.c_int32 * 16)(*([-7] * 16))
+    assert L.tdoa_debug_poison_workspace(None) == 1          # TDOA_ERR_INVALID
+    assert L.tdoa_debug_last_route(None, info) == 1
+    assert list(info) == [-7] * 16                         # nothing written
+    # the names the Context method reports follow the header's numbering
+    text = open(os.path.join(ROOT, "include", "tdoa_mi355x.h")).read()
+    for prefix, names in (("TDOA_INV_", capi.ROUTE_INVERSE), ("TDOA_STEP_", capi.ROUTE_PAIR_STEP),
+                          ("TDOA_COL_", capi.ROUTE_COL_PASS), ("TDOA_ROW_", capi.ROUTE_ROW_PASS)):
+        for k, name in enumerate(names):
+            assert re.search(r"\b%s%s\s*=\s*%d\b" % (prefix, name.upper(), k), text), (prefix, name)
+    fields = ["INVERSE", "PAIR_STEP", "COL_PASS", "ROW_PASS", "FK", "SEG_PQ"] + [f.upper() for f in capi.ROUTE_FLAGS]
+    for k, name in enumerate(fields):
+        assert re.search(r"\bTDOA_ROUTE_%s\s*=\s*%d\b" % (name, k), text), name
+
+
 def test_host_geodesy_and_solver_match_oracle(capi, oracle):
     for lle in oracle.STATIONS.values():
         assert np.allclose(capi.latlon_to_ecef(*lle), oracle.latlon_to_ecef(*lle), rtol=0, atol=1e-6)

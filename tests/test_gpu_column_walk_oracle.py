@@ -62,11 +62,16 @@ def test_column_walk_batch_4096x256_vs_oracle(oracle, n_stations, capsys):
         assert tuple(c.plan_info())[1:] == (4096, 256) and c.last_k1(0)[1]
         assert peaks.size % 4 == (0 if n_stations == 8 else 2)
         # (more pairs than stations: the library walks the columns by itself -- asserted through the tile form differing in
-        # the last bits, not being the same numbers)
+        # the last bits, not being the same numbers, and through the route)
+        assert c.last_route()["pair_step"] == "staged"
         c.debug_flags(no_dec_cols=True)
+        c.poison_workspace()
         tiles = c.process()
+        assert c.last_route()["pair_step"] == "tiles"
         c.debug_flags(no_dec_staged=True)                            # one pair-window per wave, rows straight from memory
+        c.poison_workspace()
         walk = c.process()
+        assert c.last_route()["pair_step"] == "columns"
         c.debug_flags()
         assert np.array_equal(tiles["lag"], peaks["lag"]) and not np.array_equal(tiles["corr"], peaks["corr"])
         # the staged walk and the per-pair walk run the same arithmetic in the same order: the same bits
@@ -89,9 +94,11 @@ def test_column_walk_batch_4096x512_vs_oracle(oracle, capsys):
     with tdoa_amd.Context(max_lag=ML, window_len=wl) as c:
         peaks = c.process_u8(caps)
         assert tuple(c.plan_info())[1:] == (4096, 512) and c.last_k1(0)[1]
-        assert peaks.size == 18
+        assert peaks.size == 18 and c.last_route()["pair_step"] == "staged"
         c.debug_flags(no_dec_staged=True)
+        c.poison_workspace()
         walk = c.process()
+        assert c.last_route()["pair_step"] == "columns"
         c.debug_flags()
         assert np.array_equal(walk, peaks)
         _check_batch(oracle, c, peaks, 4, wl, blk, {(0, 1), (1, 5)}, capsys, "k_pair_decimate_staged<512>, 4 stations")
@@ -117,9 +124,11 @@ def test_staged_walk_group_geometries_vs_the_per_pair_walk(oracle, n_stations, w
     with tdoa_amd.Context(max_lag=ML, window_len=wl) as c:
         c.debug_flags(dec_cols_always=True)                          # (two stations: the library's own choice is the tile form)
         peaks = c.process_u8(caps)
-        assert c.last_k1(0)[1]
+        assert c.last_k1(0)[1] and c.last_route()["pair_step"] == "staged"
         c.debug_flags(dec_cols_always=True, no_dec_staged=True)
+        c.poison_workspace()
         walk = c.process()
+        assert c.last_route()["pair_step"] == "columns"
     assert peaks.shape == (3, n_stations * (n_stations - 1) // 2)
     assert np.array_equal(walk, peaks)
     want = np.array([delays[j] - delays[i] for i in range(n_stations) for j in range(i + 1, n_stations)])
@@ -141,8 +150,11 @@ def test_staged_walk_with_and_without_a_loader_wave(oracle, n_stations, folded, 
             for s, d in enumerate(delays)]
     with tdoa_amd.Context(max_lag=ML, window_len=wl) as c:
         peaks = c.process_u8(caps)
+        assert (c.last_route()["pair_step"], c.last_route()["stg_folded"]) == ("staged", folded)
         c.debug_flags(dec_cols_always=True, no_dec_staged=True)
+        c.poison_workspace()
         walk = c.process()
+        assert c.last_route()["pair_step"] == "columns"
     assert np.array_equal(walk, peaks)
     want = np.array([delays[j] - delays[i] for i in range(n_stations) for j in range(i + 1, n_stations)])
     assert (peaks["lag"] == want[None, :]).all() and (peaks["abs_corr"] > 100.0).all()
@@ -162,8 +174,11 @@ def test_staged_walk_with_fewer_walks_than_a_groups_stations(oracle, monkeypatch
             for s, d in enumerate(delays)]
     with tdoa_amd.Context(max_lag=ML, window_len=wl) as c:
         peaks = c.process_u8(caps)
+        assert (c.last_route()["pair_step"], c.last_route()["stg_folded"]) == ("staged", False)
         c.debug_flags(dec_cols_always=True, no_dec_staged=True)
+        c.poison_workspace()
         walk = c.process()
+        assert c.last_route()["pair_step"] == "columns"
     assert np.array_equal(walk, peaks)
     want = np.array([delays[j] - delays[i] for i in range(n_stations) for j in range(i + 1, n_stations)])
     assert (peaks["lag"] == want[None, :]).all() and (peaks["abs_corr"] > 100.0).all()

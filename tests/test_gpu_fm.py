@@ -239,11 +239,16 @@ def test_two_sweep_plan_padded_rows_in_every_form(oracle):
     with tdoa_amd.Context() as c:
         lags = c.fm_xcorr_lags(a, b, 3000)                   # short-lag form (k_inv_row_pair4096<*, 8>)
         assert tuple(c.plan_info())[1:] == (4096, 2048)
+        assert (c.last_route()["inverse"], c.last_route()["fk"]) == ("short_lag", 8)
         _assert_lags_close(lags, want)
         c.debug_flags(no_short_lag=True)                      # general inverse + pruned column pass
+        c.poison_workspace()
         _assert_lags_close(c.fm_xcorr_lags(a, b, 3000), lags)
+        assert c.last_route()["inverse"] == "full"
         c.debug_flags(no_fused_k1=True)                       # k_fwd_col256_c16<true> writes the padded rows
+        c.poison_workspace()
         _assert_lags_close(c.fm_xcorr_lags(a, b, 3000), lags)
+        assert (c.last_route()["col_pass"], c.last_route()["fused_k1"]) == ("two_sweep", False)
 
 
 @pytest.mark.parametrize("n1,n2,max_lag,delay", [(2_000_000, 2_000_000, 20000, 57), (1_234_567, 1_999_999, 20000, -19876),
@@ -257,10 +262,15 @@ def test_decimated_pair_step_column_walk_vs_tiles(oracle, n1, n2, max_lag, delay
     b = oracle.simulate_delayed_fm(n2, max(0, delay), 71, 2)
     with tdoa_amd.Context(max_lag=max_lag, window_len=max(n1, n2)) as c:
         tiles, peak_t = c.fm_xcorr_lags(a, b, max_lag), c.fm_xcorr(a, b, max_lag)
+        assert (c.last_route()["inverse"], c.last_route()["pair_step"]) == ("decimated", "tiles")
         c.debug_flags(dec_cols_always=True)
+        c.poison_workspace()
         cols, peak_c = c.fm_xcorr_lags(a, b, max_lag), c.fm_xcorr(a, b, max_lag)
+        assert (c.last_route()["inverse"], c.last_route()["pair_step"]) == ("decimated", "columns")
         c.debug_flags(no_decimate=True)
+        c.poison_workspace()
         full = c.fm_xcorr_lags(a, b, max_lag)
+        assert c.last_route()["inverse"] == "full"
     assert peak_t[0] == peak_c[0] == delay
     scale = np.abs(full).max()
     assert np.abs(cols - tiles).max() <= 5e-7 * scale
@@ -281,15 +291,20 @@ def test_decimated_inverse_on_the_ten_second_plan(oracle, n1, n2, delay, max_lag
     with tdoa_amd.Context(max_lag=max_lag, window_len=max(n1, n2)) as c:
         dec_lags, dec_peak = c.fm_xcorr_lags(a, b, max_lag), c.fm_xcorr(a, b, max_lag)
         assert tuple(c.plan_info()) == (5 << 22, 4096, 2560)
+        assert (c.last_route()["inverse"], c.last_route()["pair_step"]) == ("decimated", "columns")
         c.debug_flags(no_k1_once=True)
+        c.poison_workspace()
         pre_lags = c.fm_xcorr_lags(a, b, max_lag)
-        assert tuple(c.plan_info()) == (5 << 22, 4096, 2560)
+        assert tuple(c.plan_info()) == (5 << 22, 4096, 2560) and not c.last_route()["once"]
         c.debug_flags(pow2_only=True)
+        c.poison_workspace()
         p2_lags, p2_peak = c.fm_xcorr_lags(a, b, max_lag), c.fm_xcorr(a, b, max_lag)
         assert tuple(c.plan_info()) == (1 << 25, 4096, 4096)
+        assert (c.last_route()["inverse"], c.last_route()["pair_step"]) == ("decimated", "columns")
         c.debug_flags(no_decimate=True)
+        c.poison_workspace()
         full_lags, full_peak = c.fm_xcorr_lags(a, b, max_lag), c.fm_xcorr(a, b, max_lag)
-        assert tuple(c.plan_info()) == (1 << 25, 4096, 4096)
+        assert tuple(c.plan_info()) == (1 << 25, 4096, 4096) and c.last_route()["inverse"] == "full"
     assert dec_peak[0] == p2_peak[0] == full_peak[0] == delay
     assert abs(dec_peak[1] - full_peak[1]) <= 2e-6 * abs(full_peak[1])
     assert abs(p2_peak[1] - full_peak[1]) <= 2e-6 * abs(full_peak[1])
@@ -311,8 +326,11 @@ def test_decimated_inverse_on_the_4096x2048_plan(oracle, n1, n2, delay):
     with tdoa_amd.Context(max_lag=20000, window_len=max(n1, n2)) as c:
         dec_lags, dec_peak = c.fm_xcorr_lags(a, b, 20000), c.fm_xcorr(a, b, 20000)
         assert tuple(c.plan_info()) == (1 << 24, 4096, 2048) and c.last_k1(0)[1] == (n1 == n2)
+        assert (c.last_route()["inverse"], c.last_route()["pair_step"]) == ("decimated", "columns")
         c.debug_flags(no_decimate=True)
+        c.poison_workspace()
         full_lags, full_peak = c.fm_xcorr_lags(a, b, 20000), c.fm_xcorr(a, b, 20000)
+        assert c.last_route()["inverse"] == "full"
     assert dec_peak[0] == full_peak[0] == delay
     assert not np.array_equal(dec_lags, full_lags)                       # (two different inverses ran)
     scale = np.abs(full_lags).max()
@@ -436,20 +454,27 @@ def test_short_lag_form_vs_oracle_and_general_form(oracle, max_lag, delay):
     assert olag == delay
     with tdoa_amd.Context(max_lag=max_lag, window_len=n) as c:
         lags = c.fm_xcorr_lags(a, b, max_lag)
+        assert c.last_route()["inverse"] == ("segments" if max_lag <= 1024 else "short_lag" if max_lag <= 4095 else "full")
         _assert_lags_close(lags, want)
+        c.poison_workspace()
         (lag, corr), fine = c.fm_xcorr_fine(a, b, max_lag, 1e9)
         assert lag == olag and abs(corr - ocorr) <= REL_TOL * abs(ocorr)
         ofine = oracle.b_refine_peak(ta, tb, lag, 1e9)
         assert np.abs(fine["y"] - ofine["y"]).max() <= REL_TOL * abs(ocorr)
         assert abs(fine["frac"] - ofine["frac"]) < 1e-4
         c.debug_flags(no_segment_form=True)                        # short-lag shares of the four-step form
+        c.poison_workspace()
         shares = c.fm_xcorr_lags(a, b, max_lag)
+        assert c.last_route()["inverse"] == ("short_lag" if max_lag <= 4095 else "full")
         _assert_lags_close(shares, want)
         _assert_lags_close(shares, lags)
+        c.poison_workspace()
         (lag_s, corr_s), fine_s = c.fm_xcorr_fine(a, b, max_lag, 1e9)
         assert lag_s == olag and abs(corr_s - ocorr) <= REL_TOL * abs(ocorr) and abs(fine_s["frac"] - ofine["frac"]) < 1e-4
         c.debug_flags(no_short_lag=True)
+        c.poison_workspace()
         general = c.fm_xcorr_lags(a, b, max_lag)
+        assert c.last_route()["inverse"] == "full"
         _assert_lags_close(general, lags)
         assert c.fm_xcorr(a, b, max_lag)[0] == lag
 
@@ -475,8 +500,8 @@ def test_short_column_kernels(oracle, n, label):
 
 @pytest.mark.parametrize("per_batch", [0, 2])
 def test_short_lag_form_in_the_batched_path(oracle, per_batch):
-    """tdoa_process with 4096-point rows and a 300-lag range: many pair-windows through the short-lag inverse,
-    against the oracle and against the general form."""
+    """tdoa_process with 4096-point rows and a 300-lag range: many pair-windows through the segment form (the library's
+    choice up to 1024 lags) and the short-lag inverse, against the oracle and against the general form."""
     import tdoa_amd
     block, wl, ml = 140_000, 70_000, 300
     delays = [0, 41, -17]
@@ -488,7 +513,7 @@ def test_short_lag_form_in_the_batched_path(oracle, per_batch):
         for s, cap in enumerate(caps):
             c.capture_upload(s, cap)
         peaks, fine = c.process_fine(120.0)
-        assert peaks.shape == (6, 3)
+        assert peaks.shape == (6, 3) and c.last_route()["inverse"] == "segments"
         for wid in range(6):
             off = (wid // 2) * block + (wid % 2) * wl
             pre = [oracle.b_preprocess(cp[2 * off:2 * (off + wl)])[0] for cp in caps]
@@ -499,11 +524,15 @@ def test_short_lag_form_in_the_batched_path(oracle, per_batch):
                 of = oracle.b_refine_peak(pre[i], pre[j], olag, 120.0)
                 assert abs(fine[wid, p]["frac"] - of["frac"]) < 1e-4
         c.debug_flags(no_segment_form=True)
+        c.poison_workspace()
         shares = c.process()
+        assert (c.last_route()["inverse"], c.last_route()["fk"]) == ("short_lag", 1)
         assert np.array_equal(shares["lag"], peaks["lag"])
         assert np.abs(shares["corr"] - peaks["corr"]).max() <= REL_TOL * np.abs(peaks["corr"]).max()
         c.debug_flags(no_short_lag=True)
+        c.poison_workspace()
         general = c.process()
+        assert c.last_route()["inverse"] == "full"
         assert np.array_equal(general["lag"], peaks["lag"])
         assert np.abs(general["corr"] - peaks["corr"]).max() <= REL_TOL * np.abs(peaks["corr"]).max()
 
@@ -525,9 +554,12 @@ def test_fused_k1_vs_materialised_codes(oracle, n1, n2, max_lag):
     with tdoa_amd.Context(max_lag=max_lag, window_len=max(n1, n2)) as c:
         c.debug_flags()
         fused = c.fm_xcorr_lags(a, b, max_lag)
+        assert c.last_route()["fused_k1"] == (c.plan_info()[2] >= 256)      # (the 4096 x 16 and x 64 plans have no fused kernel)
         lag, corr = c.fm_xcorr(a, b, max_lag)
         c.debug_flags(no_fused_k1=True)
+        c.poison_workspace()
         stored = c.fm_xcorr_lags(a, b, max_lag)
+        assert not c.last_route()["fused_k1"]
         lag2, corr2 = c.fm_xcorr(a, b, max_lag)
     _assert_lags_close(fused, want)
     _assert_lags_close(fused, stored, 1e-6)
@@ -545,7 +577,9 @@ def test_fused_k1_in_the_batched_path(oracle):
         c.debug_flags()
         fused = c.process_u8(caps)
         c.debug_flags(no_fused_k1=True)
+        c.poison_workspace()
         stored = c.process()
+        assert not c.last_route()["fused_k1"]
     assert fused.shape == (6, 3)
     assert np.array_equal(fused["lag"], stored["lag"])
     assert np.abs(fused["corr"] - stored["corr"]).max() <= 1e-6 * np.abs(stored["corr"]).max()
@@ -563,8 +597,11 @@ def test_fused_column_kernel_on_odd_window_starts_at_the_timed_plan(oracle, bloc
     with tdoa_amd.Context(max_lag=ml, window_len=wl) as c:
         fused = c.process_u8(caps)
         assert tuple(c.plan_info())[1:] == plan
+        assert (c.last_route()["inverse"], c.last_route()["fused_k1"]) == ("decimated", True)
         c.debug_flags(no_fused_k1=True)
+        c.poison_workspace()
         stored = c.process()
+        assert (c.last_route()["inverse"], c.last_route()["fused_k1"]) == ("decimated", False)
     assert fused.shape == (3, 1)
     assert np.array_equal(fused["lag"], stored["lag"])
     assert np.abs(fused["corr"] - stored["corr"]).max() <= 1e-6 * np.abs(stored["corr"]).max()
@@ -609,9 +646,14 @@ def test_segment_form_packed_code_rows_are_bit_identical(oracle, n1, n2, max_lag
     b[2 * 7:2 * (7 + k)] = a[:2 * k]                                # a common stretch: a real peak at lag 7
     with tdoa_amd.Context(max_lag=max_lag, window_len=max(n1, n2)) as c:
         packed, peak_p = c.fm_xcorr_lags(a, b, max_lag), c.fm_xcorr(a, b, max_lag)
+        seg = c.last_route()["inverse"] == "segments"
+        assert c.last_route()["seg_pack3"] == seg
         c.debug_flags(no_seg_pack3=True)
+        c.poison_workspace()
         plain, peak_i = c.fm_xcorr_lags(a, b, max_lag), c.fm_xcorr(a, b, max_lag)
+        assert (c.last_route()["inverse"] == "segments") == seg and not c.last_route()["seg_pack3"]
         c.debug_flags(no_segment_quads=True)
+        c.poison_workspace()
         pair_p = c.fm_xcorr_lags(a, b, max_lag)
     assert np.array_equal(packed, plain) and peak_p == peak_i
     assert np.array_equal(pair_p, packed)
@@ -635,10 +677,15 @@ def test_segment_quads_vs_one_pair_at_a_time(oracle, n_st, ml, per_batch):
             c.capture_upload(s, cap)
         quads, fine_q = c.process_fine(120.0)
         assert quads.shape == (6, len(pairs))
+        assert (c.last_route()["inverse"], c.last_route()["seg_quads"]) == ("segments", True)
         c.debug_flags(no_segment_quads=True)
+        c.poison_workspace()
         single, fine_s = c.process_fine(120.0)
+        assert (c.last_route()["inverse"], c.last_route()["seg_quads"]) == ("segments", False)
         c.debug_flags(no_segment_form=True, no_short_lag=True)
+        c.poison_workspace()
         general = c.process()
+        assert c.last_route()["inverse"] == "full"
         # sharded: window-major (2 ranks) and pair-major (more ranks than windows: odd pair subsets per rank)
         c.debug_flags()
         for world in (2, 7):
@@ -668,12 +715,13 @@ def test_segment_quads_vs_one_pair_at_a_time(oracle, n_st, ml, per_batch):
 @pytest.mark.parametrize("n1,n2,max_lag,delay", [(2_000_000, 2_000_000, 20000, 57), (1_234_567, 1_999_999, 20000, -19876),
                                                  (1_500_000, 1_100_000, 4096, 4001), (2_000_000, 2_000_000, 23000, 9),
                                                  (2_000_000, 2_000_000, 26000, -25001), (4_000_000, 3_999_000, 20000, 1234),
-                                                 (2_200_000, 3_100_000, 20000, -19999)])
+                                                 (2_200_000, 3_100_000, 20000, -19999), (2_000_000, 2_000_000, 22000, -21001)])
 def test_decimated_inverse_vs_full_inverse(oracle, n1, n2, max_lag, delay):
     """4096 x 256 and 4096 x 512 plans, search ranges above 4095 lags: K3 + FIR decimation of the pair's spectrum + an
     Nc/16-point inverse (k_pair_decimate16) against the full inverse (k_inv_row_pair4096 + k_inv_col_pruned), every lag,
-    and both against the f64 oracle.  26000 lags on the 4096 x 256 plan leave no room for the transition band: that
-    range must fall back by itself."""
+    and both against the f64 oracle.  23 000 and 26 000 lags on the 4096 x 256 plan leave too little room for the transition
+    band (the 95-tap filter reaches 118.6 and 110.8 dB of the 120 required): those ranges must fall back by themselves;
+    22 000 (121.2 dB) is the widest that decimates there."""
     import tdoa_amd
     a = oracle.simulate_delayed_fm(n1, max(0, -delay), 91, 1)
     b = oracle.simulate_delayed_fm(n2, max(0, delay), 91, 2)
@@ -684,11 +732,17 @@ def test_decimated_inverse_vs_full_inverse(oracle, n1, n2, max_lag, delay):
     with tdoa_amd.Context(max_lag=max_lag, window_len=max(n1, n2)) as c:
         dec = c.fm_xcorr_lags(a, b, max_lag)
         lag, corr = c.fm_xcorr(a, b, max_lag)
+        c.poison_workspace()
         _, fine = c.fm_xcorr_fine(a, b, max_lag, 1e9)
         assert c.plan_info()[1:] == ((4096, 256) if max(n1, n2) <= 2_000_000 else (4096, 512))
+        falls_back = max_lag >= 23000 and c.plan_info()[2] == 256                               # (see above)
+        assert c.last_route()["inverse"] == ("full" if falls_back else "decimated")
         c.debug_flags(no_decimate=True)
+        c.poison_workspace()
         full = c.fm_xcorr_lags(a, b, max_lag)
+        assert c.last_route()["inverse"] == "full"
         lag_f, corr_f = c.fm_xcorr(a, b, max_lag)
+        c.poison_workspace()
         _, fine_f = c.fm_xcorr_fine(a, b, max_lag, 1e9)
     _assert_lags_close(dec, want)
     _assert_lags_close(full, want)
@@ -699,5 +753,5 @@ def test_decimated_inverse_vs_full_inverse(oracle, n1, n2, max_lag, delay):
     ofine = oracle.b_refine_peak(ta, tb, olag, 1e9)
     assert np.abs(fine["y"] - ofine["y"]).max() <= REL_TOL * abs(ocorr) and np.abs(fine_f["y"] - ofine["y"]).max() <= REL_TOL * abs(ocorr)
     assert abs(fine["frac"] - ofine["frac"]) < 1e-4 and abs(fine_f["frac"] - ofine["frac"]) < 1e-4
-    if max_lag == 26000:
+    if falls_back:
         assert np.array_equal(dec, full)          # same kernels: the decimated form did not apply

@@ -28,9 +28,12 @@ def test_lag_arrays_identical_with_the_two_kernel_path(oracle, wl):
         c.debug_flags(small_fused_always=True)                       # (the library's own rule: from 1024 pair-windows per launch on)
         fused = c.fm_xcorr_lags(a, b, ML)
         peak = c.fm_xcorr(a, b, ML)
+        assert (c.last_route()["pair_step"], c.last_route()["small_fused"]) == ("tiles", True)
         c.debug_flags(no_small_fused=True)
+        c.poison_workspace()
         two = c.fm_xcorr_lags(a, b, ML)
         peak2 = c.fm_xcorr(a, b, ML)
+        assert (c.last_route()["pair_step"], c.last_route()["small_fused"]) == ("tiles", False)
     assert fused.shape == two.shape == (2 * ML - 1,)
     assert np.array_equal(fused, two) and np.abs(fused).max() > 100.0
     assert peak == peak2 and peak[0] == 173
@@ -52,11 +55,18 @@ def test_batch_peaks_identical_with_the_two_kernel_path(oracle, n_stations, wl, 
         c.debug_flags(no_dec_cols=not staged, small_fused_always=True)
         fused = c.process_u8(caps)
         assert c.last_k1(0)[1]
+        route = c.last_route()
+        assert (route["pair_step"], route["small_fused"]) == ("staged" if staged else "tiles", True)
         c.debug_flags(no_dec_cols=not staged, no_small_fused=True)
+        c.poison_workspace()
         two = c.process()
+        assert c.last_route() == dict(route, small_fused=False)
+        c.poison_workspace()
         fine_two = c.process_fine(4.0)
         c.debug_flags(no_dec_cols=not staged, small_fused_always=True)
-        fine_fused = c.process_fine(4.0)
+        c.poison_workspace()
+        fine_fused = c.process_fine(4.0)                         # (a batch that refines keeps the two kernels: V' is read)
+        assert c.last_route() == dict(route, small_fused=False)
     assert np.array_equal(fused, two)
     assert np.array_equal(fine_fused[0], fine_two[0]) and np.array_equal(fine_fused[1], fine_two[1])
     want = np.array([delays[j] - delays[i] for i in range(n_stations) for j in range(i + 1, n_stations)])

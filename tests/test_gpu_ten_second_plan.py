@@ -67,13 +67,18 @@ def test_every_lag_vs_f64_oracle_on_the_5x2p22_plan(oracle, n1, n2, delay, f64, 
         assert c.last_k1(0)[1] == (n1 == n2)
         e0 = _lags_close(lags, want, 1e-5)
         assert peak[0] == delay and abs(peak[1] - ocorr) <= 1e-5 * abs(ocorr)
+        assert (c.last_route()["inverse"], c.last_route()["pair_step"]) == ("decimated", "columns")
         c.debug_flags(no_k1_once=True)                              # statistics pre-pass + discriminator in the column pass
+        c.poison_workspace()
         e1 = _lags_close(c.fm_xcorr_lags(a, b, ML), want, 1e-5)
         assert tuple(c.plan_info()) == PLAN5 and not c.last_k1(0)[1]
+        assert (c.last_route()["once"], c.last_route()["col_pass"]) == (False, "k1_two_sweep")
         c.debug_flags(no_fused_k1=True)                             # materialised codes: k_fwd_col256_c16<true> + the 10-point finish
+        c.poison_workspace()
         e2 = _lags_close(c.fm_xcorr_lags(a, b, ML), want, 1e-5)
-        assert tuple(c.plan_info()) == PLAN5
+        assert tuple(c.plan_info()) == PLAN5 and c.last_route()["col_pass"] == "two_sweep"
         c.debug_flags(pow2_only=True)                               # the same window in N = 2^25
+        c.poison_workspace()
         p2 = c.fm_xcorr_lags(a, b, ML)
         assert tuple(c.plan_info()) == PLAN25
         e3 = _lags_close(p2, want, 1e-5)
@@ -96,9 +101,11 @@ def test_every_lag_on_the_3x2p23_plan(oracle, n1, n2, delay, f64, capsys):
         lags, peak = c.fm_xcorr_lags(a, b, ML), c.fm_xcorr(a, b, ML)
         assert tuple(c.plan_info()) == PLAN3 and c.last_k1(0)[1] == (n1 == n2)
         c.debug_flags(no_fused_k1=True)
+        c.poison_workspace()
         codes = c.fm_xcorr_lags(a, b, ML)
-        assert tuple(c.plan_info()) == PLAN3
+        assert tuple(c.plan_info()) == PLAN3 and not c.last_route()["fused_k1"]
         c.debug_flags(pow2_only=True)
+        c.poison_workspace()
         p2, p2_peak = c.fm_xcorr_lags(a, b, ML), c.fm_xcorr(a, b, ML)
         assert tuple(c.plan_info()) == PLAN25
     assert peak[0] == p2_peak[0] == delay
@@ -132,15 +139,21 @@ def test_where_the_5x2p22_plan_does_not_apply(oracle):
     b = oracle.simulate_delayed_fm(n, 300, 14, 2)
     with tdoa_amd.Context(max_lag=ML, window_len=n) as c:
         assert c.fm_xcorr(a, b, 600)[0] == 300                       # segment form
-        assert tuple(c.plan_info()) == PLAN25
+        assert tuple(c.plan_info()) == PLAN25 and c.last_route()["inverse"] == "segments"
+        c.poison_workspace()
         assert c.fm_xcorr(a, b, 3000)[0] == 300                      # short-lag rows
-        assert tuple(c.plan_info()) == PLAN25
+        assert tuple(c.plan_info()) == PLAN25 and c.last_route()["inverse"] == "short_lag"
+        c.poison_workspace()
         assert c.fm_xcorr(a, b, ML)[0] == 300
-        assert tuple(c.plan_info()) == PLAN5
+        assert tuple(c.plan_info()) == PLAN5 and c.last_route()["inverse"] == "decimated"
         c.debug_flags(no_decimate=True)
+        c.poison_workspace()
         assert c.fm_xcorr(a, b, ML)[0] == 300 and tuple(c.plan_info()) == PLAN25
+        assert c.last_route()["inverse"] == "full"
         c.debug_flags(no_dec_cols=True)
+        c.poison_workspace()
         assert c.fm_xcorr(a, b, ML)[0] == 300 and tuple(c.plan_info()) == PLAN25
+        assert c.last_route()["inverse"] == "full"
     with tdoa_amd.Context(max_lag=ML, window_len=n, lag_mode=1) as c:          # TDOA_LAGS_GO: equal lengths, lag 0 only
         assert c.fm_xcorr(a, b, ML)[0] == 0 and tuple(c.plan_info()) == PLAN25
 
@@ -159,6 +172,7 @@ def test_go_lag_set_and_wide_ranges_on_ten_second_windows(oracle):
         lags = c.fm_xcorr_lags(a, b, ML)
         assert tuple(c.plan_info()) == PLAN5
         c.debug_flags(pow2_only=True)
+        c.poison_workspace()
         lag2, corr2 = c.fm_xcorr(a, b, ML)
         lags2 = c.fm_xcorr_lags(a, b, ML)
         assert tuple(c.plan_info()) == PLAN25
@@ -186,9 +200,12 @@ def test_refinement_on_the_small_plan_4096x160(oracle):
     with tdoa_amd.Context(max_lag=ML, window_len=n) as c:
         (lag, corr), fine = c.fm_xcorr_fine(a, b, ML, 25000.0)
         assert tuple(c.plan_info()) == PLAN5
+        assert (c.last_route()["inverse"], c.last_route()["pair_step"], c.last_route()["small_fused"]) == ("decimated", "columns", False)
         c.debug_flags(pow2_only=True)
+        c.poison_workspace()
         (lag2, corr2), fine2 = c.fm_xcorr_fine(a, b, ML, 25000.0)
         assert tuple(c.plan_info()) == PLAN25
+        assert (c.last_route()["inverse"], c.last_route()["pair_step"]) == ("decimated", "columns")
     assert lag == lag2 == delay and abs(corr - ocorr) <= 1e-5 * abs(ocorr)
     assert np.abs(np.asarray(fine["y"], dtype=np.float64) - y).max() <= 1e-5 * abs(ocorr)
     assert abs(float(fine["frac"]) - oracle.b_parabola_vertex(*y)) < 1e-4
@@ -208,11 +225,17 @@ def test_cfg3_batch_on_both_plans(oracle, capsys):
             c.synth_weak_capture(s, L, oracle.STATIONS[nm], oracle.DEFAULT_TX, oracle.SEED_BASE + s, tgt_power=20000.0)
         peaks = c.process()
         assert tuple(c.plan_info()) == PLAN5 and c.last_k1(0)[1]
+        assert (c.last_route()["inverse"], c.last_route()["pair_step"]) == ("decimated", "staged")
+        c.poison_workspace()
         again = c.process()                                          # the replayed graph
+        c.poison_workspace()
         fpk, fine = c.process_fine(25000.0)                          # + the refinement on the 4096 x 160 small plan, batched
+        assert (c.last_route()["inverse"], c.last_route()["small_fused"]) == ("decimated", False)
         c.debug_flags(pow2_only=True)
+        c.poison_workspace()
         p2 = c.process()
         assert tuple(c.plan_info()) == PLAN25
+        c.poison_workspace()
         fpk2, fine2 = c.process_fine(25000.0)
         tgt = [c.capture_download(s, L, L) for s in range(3)]
     assert peaks.shape == (3, 3) and np.array_equal(peaks, again)
