@@ -17,11 +17,16 @@ Multi-GPU (one rank per GPU, torch.distributed over RCCL; no collective on the d
   --scaling strong (BASELINE config 4 as written: `--config cfg4 --scaling strong`): ONE capture set; rank r runs
       tdoa_process(ctx, r, world) on the windows it owns (wid % world == r), one all-gather, byte-wise owner merge and the
       N-station least-squares solve on rank 0 -- all inside the timed region.  value = the job's station-samples / time.
-  At N > 1 the default run (cfg2, weak) times BOTH: its contract line is the weak-scaled cfg2 job, and the sharded cfg4 job
-  is timed right after it in the same process group and attached as `sharded_cfg4`.
+  At N > 1 the default run (cfg2, weak) with --full times BOTH: its contract line is the weak-scaled cfg2 job, and the
+  sharded cfg4 job is timed right after it in the same process group and attached as `sharded_cfg4`.
   Multi-rank jobs correlate captures with TRUE delays (--sim fmdelay: one frequency-modulated carrier from TX, every
   station's copy delayed by its propagation time), so the solve inside the timed region has a position to find: the run
   FAILS unless every pair's median target-block lag equals the geometry's and the fix lies within 150 m of TX.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  --full also reports what the
+headline figure does not need: the roofline and per-kernel fields, the graph-replay leg, clocks and the sustained replay,
+the end-to-end leg from host buffers, the CPU baseline with the window-0 parity check against the oracle and, at N > 1, the
+sharded cfg4 job.  The --no-* switches below turn single legs of --full off.
 
 Prints ONE JSON line on rank 0 (see the contract in the task description).
 """
@@ -430,10 +435,12 @@ def dump_outputs(out_dir, peaks, fixes):
     return sorted(arrays)
 
 
-def run_job(args, env, cfg_name, scaling, sim, steps, warmup, full):
-    """one job (configuration + sharding mode) on the process group `env`: captures, warm-up, timed region; `full`: also the
-    per-kernel table, the roofline object, the graph-replay leg, clocks (the contract line's job).  Returns (result dict for
-    rank 0 | None, parity flag)."""
+def run_job(args, env, cfg_name, scaling, sim, steps, warmup, contract, full):
+    """one job (configuration + sharding mode) on the process group `env`: captures, warm-up, timed region.  `contract`: the
+    contract line's job, whose timed region is the step graph with event-record nodes around the dominant kernel (picked
+    from an untimed per-kernel table first) and whose outputs --dump-outputs writes; `full` (--full): also the roofline
+    object, the graph-replay leg, clocks, the end-to-end leg and the CPU baseline.  Returns (result dict for rank 0 | None,
+    parity flag)."""
     import numpy as np
     import torch
     import tdoa_amd
@@ -530,9 +537,10 @@ def run_job(args, env, cfg_name, scaling, sim, steps, warmup, full):
     for _ in range(warmup):
         step()
     table, dominant, timed_mode, table_steps, dominant_by = None, None, 0, steps, None
-    if full:
-        # (untimed) every kernel scope of a few steps with events: the per-kernel table of the JSON line and the name of the
-        # dominant kernel.  Kernels launched one by one, an event at every kernel boundary.
+    if contract:
+        # (untimed) every kernel scope of a few steps with events: the name of the dominant kernel, which the timed region
+        # instruments (plain runs too: it is part of what the timed steps are), and the per-kernel table of --full's fields.
+        # Kernels launched one by one, an event at every kernel boundary.
         ctx.profile_enable(True)
         ctx.profile_select(None)
         ctx.profile_reset()
@@ -586,7 +594,7 @@ def run_job(args, env, cfg_name, scaling, sim, steps, warmup, full):
         ctx.profile_reset()
     dt = timed(steps)
     prof_timed = None
-    if full:
+    if contract:
         ctx.profile_enable(False)
         ctx.profile_select(None)
         prof_timed = ctx.profile()
@@ -596,7 +604,7 @@ def run_job(args, env, cfg_name, scaling, sim, steps, warmup, full):
     timed_fix = state["fix"]
     timed_fixes = state.get("fixes") or ([timed_fix] if timed_fix is not None else [])
     dumped = None
-    if full and rank == 0 and args.dump_outputs:
+    if contract and rank == 0 and args.dump_outputs:
         dumped = dump_outputs(args.dump_outputs, timed_peaks, timed_fixes)
     graph_leg = None
     if full and not args.no_graph_leg:
@@ -675,7 +683,7 @@ def run_job(args, env, cfg_name, scaling, sim, steps, warmup, full):
                        else "statistics pre-pass + discriminator in the column pass (capture bytes read twice)",
             "clocks": clocks, "sustained": sustained, "path_switches": path_switches() or None,
         }
-        if full:
+        if contract and full:
             out["dominant_chosen_by"] = dominant_by
             out.update(roofline_fields(args, env, cfg_name, scaling, sim, table, prof_timed, dominant, timed_mode, table_steps, steps,
                                        dt, samples_per_step, n_fft, n1, n2, n_windows, n_pairs, S, wl, max_lag, graph_leg))
@@ -940,7 +948,7 @@ def launch_ranks(gpus, argv, environ=None, run=None):
     return (run or subprocess.call)(cmd, env=dict(environ))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: the config's); ms_per_step = their time / steps")
@@ -950,11 +958,16 @@ def main():
     ap.add_argument("--seconds", type=float, default=None, help="capture length per station (overrides the config)")
     ap.add_argument("--batch", type=int, default=0, help="windows per launch group (0 = library default)")
     ap.add_argument("--max-lag", type=int, default=20000, help="search range in samples (reference: 20000, processor.go:633)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-graph-leg", action="store_true")
-    ap.add_argument("--no-clocks", action="store_true", help="skip the ~1.5 s sustained replay that samples clock and power")
-    ap.add_argument("--no-h2d", action="store_true", help="skip the end-to-end leg from host buffers (SURVEY 8d secondary figure)")
-    ap.add_argument("--no-sharded-leg", action="store_true", help="at N > 1: only the contract line's job, no sharded cfg4 job")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: roofline and per-kernel fields, the "
+                         "graph-replay leg, clocks, the end-to-end leg from host buffers, the CPU baseline with the window-0 "
+                         "parity check and, at N > 1, the sharded cfg4 job")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity check")
+    ap.add_argument("--no-graph-leg", action="store_true", help="with --full: skip the graph replay without event-record nodes")
+    ap.add_argument("--no-clocks", action="store_true", help="with --full: skip the ~1.5 s sustained replay that samples clock and power")
+    ap.add_argument("--no-h2d", action="store_true",
+                    help="with --full: skip the end-to-end leg from host buffers (SURVEY 8d secondary figure)")
+    ap.add_argument("--no-sharded-leg", action="store_true", help="with --full at N > 1: only the contract line's job, no sharded cfg4 job")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--sim", choices=("config", "fm", "random", "fmdelay"), default=None,
                     help="capture bytes: 'config' = the config's simulator (+-1..3 LSB tones + noise; the default on one GPU), 'fm' = "
@@ -967,11 +980,16 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (peak records; the solve on multi-rank jobs) as "
                          "DIR/<name>.npy in float32 / float64, at most 64 MB, for comparing two builds output by output")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps is not None and args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.warmup < 0:
         ap.error("--warmup must not be negative")
+    return args
+
+
+def main():
+    args = parse_args()
 
     rc = launch_ranks(args.gpus, sys.argv[1:])
     if rc is not None:
@@ -1037,11 +1055,11 @@ def main():
             raise SystemExit(err)
         return res
 
-    out, parity = agreed(lambda: run_job(args, env, cfg_name, scaling, sim, steps, args.warmup, full=True))
-    # the sharded job BASELINE config 4 names, in the same run (default multi-rank invocation only)
-    if use_dist and args.config is None and args.scaling is None and not args.no_sharded_leg:
+    out, parity = agreed(lambda: run_job(args, env, cfg_name, scaling, sim, steps, args.warmup, contract=True, full=args.full))
+    # the sharded job BASELINE config 4 names, in the same run (default multi-rank invocation with --full only)
+    if args.full and use_dist and args.config is None and args.scaling is None and not args.no_sharded_leg:
         s_steps = min(steps, CONFIGS["cfg4"]["steps"])
-        sh, _ = agreed(lambda: run_job(args, env, "cfg4", "strong", sim, s_steps, 1, full=False))
+        sh, _ = agreed(lambda: run_job(args, env, "cfg4", "strong", sim, s_steps, 1, contract=False, full=False))
         if rank == 0:
             one = same_config_one_gpu("cfg4")
             out["sharded_cfg4"] = {
@@ -1064,7 +1082,7 @@ def main():
         else:
             print("TDOA_STG_PROF: the loaded library is not a -DTDOA_STG_TIMING build (TDOA_LIB_VARIANT)", file=sys.stderr)
     if rank == 0:
-        if world > 1:
+        if args.full and world > 1:
             out["same_config_one_gpu"] = same_config_one_gpu(cfg_name)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())

@@ -4,12 +4,13 @@
 # prints one line per variant: pair-step ms (the scope k_inv_row_pair) and the step
 # STG_VARIANTS="rows bufs loaders [walks per workgroup];..." : geometries of the staged walk to run (0 = the library's choice)
 TAG=${1:-r05}; CFG=${2:-cfg4}; STEPS=${3:-5}
-mkdir -p gpurun_out/$TAG
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"            # where the runs write (OUT=<dir> to choose)
+mkdir -p $OUT/$TAG
 run() {   # name, env...
   local name=$1; shift
-  env "$@" timeout -k 10 300 python3 bench.py --config $CFG --steps $STEPS --warmup 2 --no-cpu-baseline --no-h2d --no-clocks --no-graph-leg \
-      > gpurun_out/$TAG/stg_${CFG}_$name.json 2> gpurun_out/$TAG/stg_${CFG}_$name.err || { echo "$name FAILED"; tail -3 gpurun_out/$TAG/stg_${CFG}_$name.err; return 1; }
-  python3 - "$name" gpurun_out/$TAG/stg_${CFG}_$name.json <<'PY'
+  env "$@" timeout -k 10 300 python3 bench.py --full --config $CFG --steps $STEPS --warmup 2 --no-cpu-baseline --no-h2d --no-clocks --no-graph-leg \
+      > $OUT/$TAG/stg_${CFG}_$name.json 2> $OUT/$TAG/stg_${CFG}_$name.err || { echo "$name FAILED"; tail -3 $OUT/$TAG/stg_${CFG}_$name.err; return 1; }
+  python3 - "$name" $OUT/$TAG/stg_${CFG}_$name.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 k = d["roofline"]["kernels_ms_per_step"]

@@ -108,6 +108,37 @@ def test_dump_outputs_past_the_limit_is_a_fixed_sample_of_windows(tmp_path, monk
     assert np.array_equal(np.load(tmp_path / "a" / "peak_corr.npy"), pk["corr"][rows])
 
 
+def test_full_is_off_by_default():
+    """a plain run times the steps and prints the line; the extra legs only run with --full, which the --no-* switches thin"""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and plain.steps == 20 and plain.warmup == 5
+    full = bench.parse_args(["--full", "--no-cpu-baseline", "--no-h2d"])
+    assert full.full and full.no_cpu_baseline and full.no_h2d and not full.no_graph_leg and not full.no_clocks
+
+
+def test_scripts_that_read_the_full_fields_ask_for_them():
+    """fields a plain run no longer prints: a bench.py call of a script that reads one of them passes --full (a call piped
+    into a reader on its own line is judged by that line, any other by its whole script)"""
+    import glob
+    import re
+    full_only = ("roofline", "kernels_ms_per_step", "graph_replay", "parity_window0", "cpu_baseline", "end_to_end_h2d",
+                 "sharded_cfg4", "dominant_chosen_by")
+
+    def reads_full(text):
+        return any(re.search(r"\b%s\b" % k, text) for k in full_only)
+
+    checked = 0
+    for f in sorted(glob.glob(os.path.join(ROOT, "scripts", "*.sh"))):
+        text = open(f).read()
+        for ln in text.splitlines():
+            if not re.search(r"python3? bench\.py", ln) or ln.lstrip().startswith("#"):
+                continue
+            if reads_full(ln if "sys.stdin" in ln else text):
+                assert "--full" in ln, "%s: %s" % (os.path.basename(f), ln.strip())
+                checked += 1
+    assert checked > 0
+
+
 def test_steps_must_be_positive():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 2 and "--steps" in r.stderr and r.stdout == ""
