@@ -408,6 +408,31 @@ def b_preprocess_gate(iq_u8, window=0, gate=1):
     return out, st, cls.value
 
 
+def b_smooth_codes(code, window):
+    """ob_smooth_codes: the centred, edge-truncated moving average of half-window window // 2 on int32 codes, exact, rounded
+    half up"""
+    c = np.ascontiguousarray(code, dtype=np.int32)
+    out = np.empty_like(c)
+    i32p = C.POINTER(C.c_int32)
+    lib().ob_smooth_codes(c.ctypes.data_as(i32p), C.c_size_t(c.size), C.c_int(int(window)), out.ctypes.data_as(i32p))
+    return out
+
+
+def b_power_sum(iq_u8):
+    """ob_power_sum_u8: M = sum (2I-255)^2 + (2Q-255)^2 over the samples (exact)"""
+    s = np.ascontiguousarray(iq_u8, dtype=np.uint8)
+    f = lib().ob_power_sum_u8
+    f.restype = C.c_uint64
+    return int(f(_u8(s), C.c_size_t(s.size // 2)))
+
+
+def b_envelope_class(power_sum, n):
+    """ob_envelope_class: 1 when 100 M <= 65025 n (mean power <= 0.01: the gate's envelope branch)"""
+    f = lib().ob_envelope_class
+    f.argtypes = [C.c_uint64, C.c_size_t]
+    return int(f(int(power_sum), int(n)))
+
+
 def b_envelope_code(i, q):
     f = lib().ob_envelope_code
     f.restype = C.c_int32

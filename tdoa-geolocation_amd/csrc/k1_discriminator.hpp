@@ -583,12 +583,14 @@ __global__ void k_fm_stats_final(const SWDesc *sw, const StatsPartial *acc, FmSt
     stats[id] = out;
 }
 
-// inspection hook: the normalised discriminator output of window 0 (from materialised codes)
+// inspection hook: the normalised discriminator output of window 0 (from materialised codes).  k1_normalise negates the
+// stored code, so a code of 0 in a window of mean 0 (a one-sample window; any window whose codes sum to 0) comes out as
+// -0.0 where (code - mean) * scale is +0.0; + 0.0f gives the reference's sign.  (The transforms never see a difference.)
 __global__ void k_fm_dump(const SWDesc *sw, const int *codes, const FmStats *stats, float *out)
 {
     const FmStats st = stats[0];
     int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < sw[0].len) out[i] = k1_normalise(codes[i], st.mean, st.scale);
+    if (i < sw[0].len) out[i] = k1_normalise(codes[i], st.mean, st.scale) + 0.0f;
 }
 
 }  // namespace tdoa
