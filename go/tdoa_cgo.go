@@ -96,6 +96,23 @@ func (g *gpuCorrelator) processCapturesFine(gate float64) ([]C.tdoa_peak, []C.td
 	return peaks, fine, nil
 }
 
+// ProcessPeaks returns the k strongest separate peaks of every (window, pair) correlation, strongest first, and how many
+// each holds: peak 1 is processCaptures' peak; the others are local maxima more than minSeparation lags from every peak
+// already chosen (multipath, a second emitter, the main-to-sidelobe ratio).
+func (g *gpuCorrelator) ProcessPeaks(k, minSeparation int) ([]C.tdoa_peak, []C.int32_t, error) {
+	var perBlock, total C.int
+	C.tdoa_num_windows(g.ctx, &perBlock, &total)
+	n := int(total) * int(C.tdoa_num_pairs(g.ctx))
+	if n == 0 || k < 1 {
+		return nil, nil, fmt.Errorf("tdoa_process_peaks: no pair-windows or k < 1")
+	}
+	peaks, count := make([]C.tdoa_peak, n*k), make([]C.int32_t, n)
+	if rc := C.tdoa_process_peaks(g.ctx, 0, 1, C.int(k), C.int(minSeparation), &peaks[0], &count[0]); rc != C.TDOA_OK {
+		return nil, nil, fmt.Errorf("tdoa_process_peaks: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return peaks, count, nil
+}
+
 // windowQuality is fastAnalyzeSamples' statistics (fast_analyzer.go:117-155) for every (window, station).
 func (g *gpuCorrelator) windowQuality(stations int) ([]C.tdoa_window_quality, error) {
 	var perBlock, total C.int

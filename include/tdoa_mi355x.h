@@ -240,6 +240,26 @@ int tdoa_fm_xcorr_fine_u8(tdoa_ctx *ctx, const uint8_t *iq1, size_t n1, const ui
                           int max_lag, double gate_samples, tdoa_peak *peak /* may be NULL */,
                           tdoa_fine_peak *fine);
 
+/* The whole correlation of every pair-window, and its K strongest separate peaks (multipath, several emitters on the
+ * channel, peak-to-sidelobe confidence).  Same layouts as tdoa_process: windows of other ranks are zero-filled, pairs
+ * are i < j.  Both run inside the step graph; TDOA_LAGS_GO returns TDOA_ERR_UNSUPPORTED.
+ *
+ * tdoa_process_lags: [n_windows_total][n_pairs][2*max_lag-1] float, reference scale (lag d at d + max_lag - 1), the
+ * values the peak search compared.  Either pointer may be NULL, not both.
+ *
+ * tdoa_process_peaks: [n_windows_total][n_pairs][k] peaks, 1 <= k <= 16, min_separation >= 1.  Peak 1 is tdoa_process's
+ * peak.  Each next peak is the largest |c[l]| over the lags l that are a local maximum of |c| (|c[l]| >= |c[l-1]| and
+ * >= |c[l+1]|, a neighbour outside the searched range counting as smaller), lie more than min_separation lags from
+ * every peak already chosen, and hold neither NaN nor 0.  Ties go to the smaller |lag|, then the positive lag.  The
+ * selection stops after k peaks or when no lag qualifies; unused records are zero.  count_host
+ * [n_windows_total][n_pairs] (may be NULL): the records written. */
+int tdoa_process_lags(tdoa_ctx *ctx, int rank, int world, float *lags_host, void *lags_dev);
+int tdoa_process_peaks(tdoa_ctx *ctx, int rank, int world, int k, int min_separation, tdoa_peak *peaks_host,
+                       int32_t *count_host);
+/* the same selection for one pair of host windows (count may be NULL) */
+int tdoa_fm_xcorr_peaks_u8(tdoa_ctx *ctx, const uint8_t *iq1, size_t n1, const uint8_t *iq2, size_t n2, int max_lag,
+                           int k, int min_separation, tdoa_peak *peaks, int32_t *count);
+
 /* Capture-quality statistics of every (window, station) in one streaming pass over the bytes
  * in HBM: the byte statistics of fastAnalyzeSamples
  * (fast_analyzer.go:117-155) and the block power of validateDataFile (collector.go:219-224).
@@ -264,6 +284,10 @@ int tdoa_fm_preprocess_u8(tdoa_ctx *ctx, const uint8_t *iq, size_t n, float *out
 int tdoa_fm_xcorr_lags_u8(tdoa_ctx *ctx, const uint8_t *iq1, size_t n1, const uint8_t *iq2, size_t n2,
                           int max_lag, double *lags_out /* [2*max_lag-1] */);
 
+/* tests only: run the selection kernel of tdoa_process_peaks on a caller's raw surface (n_lags values for the lags
+ * lag_lo, lag_lo + 1, ...) with scale 1; peak 1 comes from the surface like the others */
+int tdoa_debug_select_peaks(tdoa_ctx *ctx, const float *surface, int n_lags, int lag_lo, int k, int min_separation,
+                            tdoa_peak *peaks, int32_t *count);
 /* tests only: run the any-size fallback kernels even where a hot-size kernel exists */
 int tdoa_debug_force_generic(tdoa_ctx *ctx, int on);
 /* tests / measurements only: pick kernel variants by hand.  flags == 0 is the library's default path; every bit

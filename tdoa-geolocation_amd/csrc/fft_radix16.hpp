@@ -1286,9 +1286,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SELF ? 1 : 
 // grid (2 FK, n_pw): blockIdx.x = side * FK + k; 256 threads.
 template <int FK>
 __global__ __launch_bounds__(256) void k_fused_reduce(float2 *V, unsigned long long *keys, const PWDesc *pw, FftPlan pl,
-                                                      int lag_lo, int lag_hi, float *lag_dump, float dump_scale)
+                                                      int lag_lo, int lag_hi, float *lag_dump, float dump_scale,
+                                                      size_t dump_stride)
 {
     __shared__ unsigned long long red[4];
+    if (lag_dump) lag_dump += (size_t)blockIdx.y * dump_stride;
     const int RP = pl.N2 / 2, j = threadIdx.x;
     const int side = blockIdx.x / FK, k = blockIdx.x % FK;
     float2 *part = V + (size_t)blockIdx.y * pl.Nc;
@@ -1313,9 +1315,11 @@ __global__ __launch_bounds__(256) void k_fused_reduce(float2 *V, unsigned long l
     for (int q = 0; q < 2; q++) {
         const int d = 2 * m + q;
         lags[d + 512 * FK] = vals[q];
-        if (d >= lag_lo && d <= lag_hi && vals[q] == vals[q]) {
-            const unsigned long long key = peak_key(vals[q], d);
-            best = key > best ? key : best;
+        if (d >= lag_lo && d <= lag_hi) {
+            if (vals[q] == vals[q]) {
+                const unsigned long long key = peak_key(vals[q], d);
+                best = key > best ? key : best;
+            }
             if (lag_dump) lag_dump[d - lag_lo] = vals[q] * dump_scale;
         }
     }
@@ -1366,9 +1370,10 @@ constexpr int kPruneMax = 8;
 // oc (single-look K1, k1_single_look.hpp): the residual-mean terms added to every candidate before the argmax
 __global__ __launch_bounds__(256) void k_inv_col_pruned_any(const float2 *V, unsigned long long *keys, const PWDesc *pw,
                                                        FftPlan pl, int lag_lo, int lag_hi, int np, int nn,
-                                                       float *lag_dump, float dump_scale, OnceCorr oc)
+                                                       float *lag_dump, float dump_scale, size_t dump_stride, OnceCorr oc)
 {
     extern __shared__ float2 wtab[];               // e^{+2 pi i k/N2}, N2 entries (dynamic LDS)
+    if (lag_dump) lag_dump += (size_t)blockIdx.y * dump_stride;
     __shared__ float4 part[4][kPruneMax][64];
     __shared__ unsigned long long red[4];
     const int N2 = pl.N2, N1 = pl.N1;
@@ -1430,9 +1435,11 @@ __global__ __launch_bounds__(256) void k_inv_col_pruned_any(const float2 *V, uns
         for (int q = 0; q < 4; q++) {
             const long long dq = d + q;
             if (oc.fin) vals[q] += once_correction(oc, op, dq);
-            if (dq >= lag_lo && dq <= lag_hi && vals[q] == vals[q]) {
-                const unsigned long long k = peak_key(vals[q], (int)dq);
-                best = k > best ? k : best;
+            if (dq >= lag_lo && dq <= lag_hi) {
+                if (vals[q] == vals[q]) {
+                    const unsigned long long k = peak_key(vals[q], (int)dq);
+                    best = k > best ? k : best;
+                }
                 if (lag_dump) lag_dump[dq - lag_lo] = vals[q] * dump_scale;
             }
         }
@@ -1454,9 +1461,10 @@ __global__ __launch_bounds__(256) void k_inv_col_pruned_any(const float2 *V, uns
 template <int NP, int NN>
 __global__ __launch_bounds__(256) void k_inv_col_pruned(const float2 *V, unsigned long long *keys, const PWDesc *pw,
                                                        FftPlan pl, int lag_lo, int lag_hi, float *lag_dump,
-                                                       float dump_scale, OnceCorr oc)
+                                                       float dump_scale, size_t dump_stride, OnceCorr oc)
 {
     constexpr int NOUT = NP + NN;
+    if (lag_dump) lag_dump += (size_t)blockIdx.y * dump_stride;
     constexpr int NPW = (NP - 1 > NN ? NP - 1 : NN) + 1;     // powers w^0 .. w^(NPW-1)
     extern __shared__ float2 wtab[];               // e^{+2 pi i k/N2}, N2 entries (dynamic LDS)
     __shared__ float4 part[4][NOUT][64];
@@ -1527,9 +1535,11 @@ __global__ __launch_bounds__(256) void k_inv_col_pruned(const float2 *V, unsigne
         for (int q = 0; q < 4; q++) {
             const long long dq = d + q;
             if (oc.fin) vals[q] += once_correction(oc, op, dq);
-            if (dq >= lag_lo && dq <= lag_hi && vals[q] == vals[q]) {
-                const unsigned long long k = peak_key(vals[q], (int)dq);
-                best = k > best ? k : best;
+            if (dq >= lag_lo && dq <= lag_hi) {
+                if (vals[q] == vals[q]) {
+                    const unsigned long long k = peak_key(vals[q], (int)dq);
+                    best = k > best ? k : best;
+                }
                 if (lag_dump) lag_dump[dq - lag_lo] = vals[q] * dump_scale;
             }
         }

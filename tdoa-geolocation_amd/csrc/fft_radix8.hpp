@@ -605,8 +605,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4) TDOA_
 template <int NP = 0, int NN = 0>
 __global__ __launch_bounds__(256) void k_small_col_peak(const float2 *V, unsigned long long *keys, const PWDesc *pw, FftPlan pl,
                                                         int lag_lo, int lag_hi, int np_rt, int nn_rt, float *lag_dump,
-                                                        float dump_scale, const float *gain, OnceCorr oc)
+                                                        float dump_scale, size_t dump_stride, const float *gain, OnceCorr oc)
 {
+    if (lag_dump) lag_dump += (size_t)blockIdx.y * dump_stride;
     constexpr bool FIXED = NP > 0 && NN > 0;
     const int np = FIXED ? NP : np_rt, nn = FIXED ? NN : nn_rt;
     __shared__ float2 wtab[256];                   // e^{+2 pi i k / N2'}  (N2' = 16, 32; 256 / 160 behind the column walk of the 4096 x 4096 / x 2560 plans)
@@ -691,9 +692,11 @@ __global__ __launch_bounds__(256) void k_small_col_peak(const float2 *V, unsigne
 #pragma unroll
                 for (int q = 0; q < 2; q++) {
                     const long long dq = d + q;
-                    if (dq >= lag_lo && dq <= lag_hi && vals[q] == vals[q]) {
-                        const unsigned long long k = peak_key(vals[q], (int)dq);
-                        best = k > best ? k : best;
+                    if (dq >= lag_lo && dq <= lag_hi) {
+                        if (vals[q] == vals[q]) {
+                            const unsigned long long k = peak_key(vals[q], (int)dq);
+                            best = k > best ? k : best;
+                        }
                         if (lag_dump) lag_dump[dq - lag_lo] = vals[q] * dump_scale;
                     }
                 }
@@ -721,9 +724,10 @@ __global__ __launch_bounds__(256) void k_small_col_peak(const float2 *V, unsigne
 // grid (n_pw), 512 threads at two waves per SIMD (~200 VGPRs), dynamic LDS 64 KB.
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2) TDOA_PLAIN_DS_OPS)) void k_small_rows_col_peak(
     const float2 *G, const float2 *E, unsigned long long *keys, const PWDesc *pw, FftPlan pl, int big_n2, int by_column, int lag_lo,
-    int lag_hi, float *lag_dump, float dump_scale, const float *gain, OnceCorr oc)
+    int lag_hi, float *lag_dump, float dump_scale, size_t dump_stride, const float *gain, OnceCorr oc)
 {
-    constexpr int NO = 6;                                           // outputs n2 = 0, 1, 2, N2 - 3, N2 - 2, N2 - 1
+    constexpr int NO = 6;
+    if (lag_dump) lag_dump += (size_t)blockIdx.x * dump_stride;                                           // outputs n2 = 0, 1, 2, N2 - 3, N2 - 2, N2 - 1
     extern __shared__ float2 lds[];   // 2 * kRow8Lds
     __shared__ unsigned long long red[8];
     float2 *la = lds, *lb = lds + kRow8Lds;
@@ -841,9 +845,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2) TDOA_
 #pragma unroll
                 for (int q = 0; q < 2; q++) {
                     const long long dq = d + q;
-                    if (dq >= lag_lo && dq <= lag_hi && vals[q] == vals[q]) {
-                        const unsigned long long key = peak_key(vals[q], (int)dq);
-                        best = key > best ? key : best;
+                    if (dq >= lag_lo && dq <= lag_hi) {
+                        if (vals[q] == vals[q]) {
+                            const unsigned long long key = peak_key(vals[q], (int)dq);
+                            best = key > best ? key : best;
+                        }
                         if (lag_dump) lag_dump[dq - lag_lo] = vals[q] * dump_scale;
                     }
                 }
@@ -1110,8 +1116,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4) TDOA_
 template <int PQ>
 __global__ __launch_bounds__(256) void k_segments_reduce(float2 *V, unsigned long long *keys, const PWDesc *pw, FftPlan pl,
                                                         int n_chunks, float mul, int lag_lo, int lag_hi, float *lag_dump,
-                                                        float dump_scale)
+                                                        float dump_scale, size_t dump_stride)
 {
+    if (lag_dump) lag_dump += (size_t)blockIdx.y * dump_stride;
     constexpr int P = 256 * PQ;
     __shared__ unsigned long long red[4];
     float *base = reinterpret_cast<float *>(V + (size_t)blockIdx.y * pl.Nc);
@@ -1125,8 +1132,8 @@ __global__ __launch_bounds__(256) void k_segments_reduce(float2 *V, unsigned lon
     const int dlag = li - P;
     if (live) lags[li] = v;
     unsigned long long best = 0;
-    if (live && dlag >= lag_lo && dlag <= lag_hi && v == v) {
-        best = peak_key(v, dlag);
+    if (live && dlag >= lag_lo && dlag <= lag_hi) {
+        if (v == v) best = peak_key(v, dlag);
         if (lag_dump) lag_dump[dlag - lag_lo] = v * dump_scale;
     }
     best = wave_max_u64(best);

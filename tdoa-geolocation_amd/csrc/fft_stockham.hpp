@@ -324,9 +324,10 @@ __global__ __launch_bounds__(256) void k_inv_row_pair(const PWDesc *pw, const fl
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_inv_col_peak(const float2 *V, unsigned long long *keys, const PWDesc *pw,
                                                       FftPlan pl, int lag_lo, int lag_hi, float *lag_dump,
-                                                      float dump_scale)
+                                                      float dump_scale, size_t dump_stride)
 {
     extern __shared__ float2 lds[];
+    if (lag_dump) lag_dump += (size_t)blockIdx.y * dump_stride;
     const int tile = pl.N2 << pl.logC;
     const float2 *in = V + (size_t)blockIdx.y * pl.Nc;
     const int c0 = blockIdx.x << pl.logC;
@@ -345,14 +346,18 @@ __global__ __launch_bounds__(256) void k_inv_col_peak(const float2 *V, unsigned 
         long long d0 = 2 * m;
         if (d0 >= Nc) d0 -= 2 * Nc;
         long long d1 = d0 + 1;
-        if (d0 >= lag_lo && d0 <= lag_hi && v.x == v.x) {
-            unsigned long long k = peak_key(v.x, (int)d0);
-            best = k > best ? k : best;
+        if (d0 >= lag_lo && d0 <= lag_hi) {
+            if (v.x == v.x) {
+                unsigned long long k = peak_key(v.x, (int)d0);
+                best = k > best ? k : best;
+            }
             if (lag_dump) lag_dump[d0 - lag_lo] = v.x * dump_scale;
         }
-        if (d1 >= lag_lo && d1 <= lag_hi && v.y == v.y) {
-            unsigned long long k = peak_key(v.y, (int)d1);
-            best = k > best ? k : best;
+        if (d1 >= lag_lo && d1 <= lag_hi) {
+            if (v.y == v.y) {
+                unsigned long long k = peak_key(v.y, (int)d1);
+                best = k > best ? k : best;
+            }
             if (lag_dump) lag_dump[d1 - lag_lo] = v.y * dump_scale;
         }
     }

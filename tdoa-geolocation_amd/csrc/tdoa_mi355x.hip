@@ -33,6 +33,7 @@
 #include "host_geodesy.hpp"
 #include "host_upload.hpp"
 #include "segment_quads.hpp"
+#include "peak_select.hpp"
 
 using namespace tdoa;
 
@@ -194,6 +195,9 @@ struct tdoa_ctx {
     DevBuf qual;                            // QualAcc per (window, station)
     StagedUploader uploader;                // pinned staging buffers + copy streams, created on first use
     DevBuf fine_raw, fine;                  // (f)-4 refinement: 3 raw neighbours and tdoa_fine_peak per slot
+    // tdoa_process_lags / _peaks: the K5 kernels' lag arrays [owned pair-window][2 max_lag - 1], the surfaces in the caller's
+    // layout [slot][2 max_lag - 1], the selected peaks [slot][k] and their counts [slot]
+    DevBuf surf, surf_out, sel_peaks, sel_count;
 };
 
 namespace {
@@ -1049,6 +1053,7 @@ struct FmBufs {
     float dump_scale = 1.0f;
     double sum_len = 0.0;                    // samples of all station-windows (the profiling scopes' bytes)
     float *fine_raw = nullptr;               // FmBatchShape::fine: 3 raw neighbours per slot
+    size_t dump_stride = 0;                  // lag_dump: floats between the lag arrays of consecutive pair-windows of the batch
     hipStream_t st = nullptr;
     FmStats *stats = nullptr;
     float2 *tz = nullptr, *v = nullptr;
@@ -1186,7 +1191,7 @@ void launch_segments(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
         {
             ProfScope ps(ctx, TDOA_K_INV_COL, 4.0 * 512.0 * PQ * (chunks + 1) * n_pw);
             hipLaunchKernelGGL(k_segments_reduce<PQ>, dim3(2 * PQ + 1, n_pw), dim3(256), 0, bf.st, bf.v, bf.keys, bf.pw, pl, chunks, mul,
-                               r.lag_lo, r.lag_hi, bf.lag_dump, bf.dump_scale);
+                               r.lag_lo, r.lag_hi, bf.lag_dump, bf.dump_scale, bf.dump_stride);
         }
         if (r.b.fine) {
             ctx->prof_last = -1;          // unscoped launch: the next scope records its own start
@@ -1243,13 +1248,13 @@ void launch_small_plan(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
     ProfScope ps(ctx, TDOA_K_INV_COL, 3.0 * 8.0 * (double)rc_pts * n_pw);
     if (r.small_fused) {
         hipLaunchKernelGGL(k_small_rows_col_peak, dim3(n_pw), dim3(512), lds, bf.st, g, edges, bf.keys, bf.pw, ps2, pl.N2, by_col, r.lag_lo,
-                           r.lag_hi, bf.lag_dump, bf.dump_scale, gain, bf.oc);
+                           r.lag_hi, bf.lag_dump, bf.dump_scale, bf.dump_stride, gain, bf.oc);
         return;
     }
     hipLaunchKernelGGL(k_inv_rows_plain_r8, dim3(ps2.N2 / 2, n_pw), dim3(512), lds, bf.st, g, edges, vs, ps2, pl.N2, by_col);
     with_int<3, 0>(r.np2 == 3 && r.nn2 == 3 ? 3 : 0, [&](auto n) {      // 3: the reference's 20 000 lags on either small plan
         hipLaunchKernelGGL((k_small_col_peak<decltype(n)::value, decltype(n)::value>), dim3(ps2.N1 / 256, n_pw), dim3(256), 0, bf.st, vs,
-                           bf.keys, bf.pw, ps2, r.lag_lo, r.lag_hi, r.np2, r.nn2, bf.lag_dump, bf.dump_scale, gain, bf.oc);
+                           bf.keys, bf.pw, ps2, r.lag_lo, r.lag_hi, r.np2, r.nn2, bf.lag_dump, bf.dump_scale, bf.dump_stride, gain, bf.oc);
     });
 }
 
@@ -1281,19 +1286,19 @@ void launch_inverse(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
     if (r.fk)
         with_int<1, 2, 4, 8>(r.fk, [&](auto fk) {
             hipLaunchKernelGGL(k_fused_reduce<decltype(fk)::value>, dim3(2 * decltype(fk)::value, n_pw), dim3(256), 0, bf.st, bf.v, bf.keys,
-                               bf.pw, pl, r.lag_lo, r.lag_hi, bf.lag_dump, bf.dump_scale);
+                               bf.pw, pl, r.lag_lo, r.lag_hi, bf.lag_dump, bf.dump_scale, bf.dump_stride);
         });
     else if (r.pruned && fixed && r.np == r.nn && r.np >= 1 && r.np <= 4)
         with_int<3, 1, 2, 4>(r.np, [&](auto n) {
             hipLaunchKernelGGL((k_inv_col_pruned<decltype(n)::value, decltype(n)::value>), grid, dim3(256), lds_wtab, bf.st, bf.v, bf.keys,
-                               bf.pw, pl, r.lag_lo, r.lag_hi, bf.lag_dump, bf.dump_scale, bf.oc);
+                               bf.pw, pl, r.lag_lo, r.lag_hi, bf.lag_dump, bf.dump_scale, bf.dump_stride, bf.oc);
         });
     else if (r.pruned)
         hipLaunchKernelGGL(k_inv_col_pruned_any, grid, dim3(256), lds_wtab, bf.st, bf.v, bf.keys, bf.pw, pl, r.lag_lo, r.lag_hi, r.np, r.nn,
-                           bf.lag_dump, bf.dump_scale, bf.oc);
+                           bf.lag_dump, bf.dump_scale, bf.dump_stride, bf.oc);
     else
         hipLaunchKernelGGL(k_inv_col_peak, dim3(pl.N1 / pl.C, n_pw), dim3(256), sizeof(float2) * 2 * (size_t)pl.N2 * pl.C, bf.st, bf.v,
-                           bf.keys, bf.pw, pl, r.lag_lo, r.lag_hi, bf.lag_dump, bf.dump_scale);
+                           bf.keys, bf.pw, pl, r.lag_lo, r.lag_hi, bf.lag_dump, bf.dump_scale, bf.dump_stride);
 }
 
 // refinement: V (the short-lag array; the small plan's row-pass output behind G) of this batch is still in place -- the
@@ -1469,13 +1474,17 @@ int stage_pair_u8(tdoa_ctx *ctx, const uint8_t *iq1, size_t n1, const uint8_t *i
     return TDOA_OK;
 }
 
+// sel_k > 0 (tdoa_fm_xcorr_peaks_u8): also the sel_k strongest separate peaks of the lag array (peak_select.hpp)
 int fm_pair(tdoa_ctx *ctx, const uint8_t *iq1, size_t n1, const uint8_t *iq2, size_t n2, int max_lag,
-            tdoa_peak *peak, double *lags_out, tdoa_fine_peak *fine = nullptr, double gate = 0.0)
+            tdoa_peak *peak, double *lags_out, tdoa_fine_peak *fine = nullptr, double gate = 0.0, int sel_k = 0,
+            int sel_sep = 0, tdoa_peak *sel_peaks = nullptr, int32_t *sel_count = nullptr)
 {
     int rc;
     if ((rc = check_ctx(ctx))) return rc;
-    if (max_lag < 1 || (!peak && !lags_out && !fine)) return fail(ctx, TDOA_ERR_INVALID, "bad argument");
+    if (max_lag < 1 || (!peak && !lags_out && !fine && !sel_k)) return fail(ctx, TDOA_ERR_INVALID, "bad argument");
     if (n1 == 0 || n2 == 0) {   // processor.go:622-625 behaviour: (0, 0.0)
+        if (sel_k) std::fill(sel_peaks, sel_peaks + sel_k, tdoa_peak{0, 0.0f, 0.0});
+        if (sel_k && sel_count) *sel_count = 0;
         if (peak) *peak = tdoa_peak{0, 0.0f, 0.0};
         if (fine) *fine = tdoa_fine_peak{0.0, 0.0f, {0.0f, 0.0f, 0.0f}, gate >= 0.0 ? 1 : 0, 0};
         if (lags_out) std::fill(lags_out, lags_out + (2 * max_lag - 1), 0.0);
@@ -1522,7 +1531,11 @@ int fm_pair(tdoa_ctx *ctx, const uint8_t *iq1, size_t n1, const uint8_t *iq2, si
     }
     const int n_dump = lag_hi - lag_lo + 1;                   // the kernels write lag d at dump[d - lag_lo]
     float *dump = nullptr;
-    if (lags_out) {
+    if (sel_k) {
+        if ((rc = ensure(ctx, ctx->sel_peaks, sizeof(PeakOut) * sel_k))) return rc;
+        if ((rc = ensure(ctx, ctx->sel_count, sizeof(int32_t)))) return rc;
+    }
+    if (lags_out || sel_k) {
         if ((rc = ensure(ctx, ctx->lagdump, sizeof(float) * (size_t)n_dump))) return rc;
         dump = static_cast<float *>(ctx->lagdump.p);
         HIPCHK(ctx, hipMemsetAsync(dump, 0, sizeof(float) * (size_t)n_dump, ctx->stream));
@@ -1555,6 +1568,15 @@ int fm_pair(tdoa_ctx *ctx, const uint8_t *iq1, size_t n1, const uint8_t *iq2, si
                            static_cast<unsigned long long *>(ctx->keys.p), static_cast<double *>(ctx->scales.p),
                            static_cast<float *>(ctx->fine_raw.p), static_cast<FineOut *>(ctx->fine.p), gate, 1, slot_gain);
         HIPCHK(ctx, hipMemcpyAsync(&fk, ctx->fine.p, sizeof(fk), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (sel_k) {
+        hipLaunchKernelGGL(k_select_peaks, dim3(1), dim3(kSelThreads), 0, ctx->stream, dump, (size_t)0, n_dump, lag_lo,
+                           static_cast<const PWDesc *>(nullptr), static_cast<const unsigned long long *>(ctx->keys.p),
+                           static_cast<const double *>(ctx->scales.p), slot_gain, sel_k, sel_sep,
+                           static_cast<PeakOut *>(ctx->sel_peaks.p), static_cast<int32_t *>(ctx->sel_count.p));
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(sel_peaks, ctx->sel_peaks.p, sizeof(PeakOut) * sel_k, hipMemcpyDeviceToHost, ctx->stream));
+        if (sel_count) HIPCHK(ctx, hipMemcpyAsync(sel_count, ctx->sel_count.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     }
     double pair_gain = 1.0;                                   // single-look K1: the lag array lacks g_t g_s like the key does
     if (lags_out && slot_gain)
@@ -1680,7 +1702,9 @@ int batch_bound(tdoa_ctx *ctx, const FftPlan &pl, int lag_lo, int lag_hi, const 
     double limit = ctx->workspace_limit;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const double held = (double)ctx->tz.cap + (double)ctx->v.cap + (double)ctx->codes.cap + (double)ctx->codes_lp.cap;
+        // (the surface outputs' buffers too: whether an earlier call allocated them must not change the grouping)
+        const double held = (double)ctx->tz.cap + (double)ctx->v.cap + (double)ctx->codes.cap + (double)ctx->codes_lp.cap +
+                            (double)ctx->surf.cap + (double)ctx->surf_out.cap;
         limit = std::min(limit, std::max(0.0, (double)free_b + held - 1073741824.0));      // 1 GiB stays free: descriptors, edges, the runtime
     } else {
         (void)hipGetLastError();
@@ -1691,7 +1715,7 @@ int batch_bound(tdoa_ctx *ctx, const FftPlan &pl, int lag_lo, int lag_hi, const 
 
 // Everything a step's launches depend on: same key => the captured graph can be replayed as is
 std::vector<uint64_t> step_graph_key(const tdoa_ctx *ctx, int rank, int world, int per_batch, long long wlen, long long block,
-                                     bool go, bool fine, double gate)
+                                     bool go, bool fine, double gate, int surf_mode = 0, int sel_k = 0, int sel_sep = 0)
 {
     std::vector<uint64_t> key = {(uint64_t)ctx->caps.size(), (uint64_t)rank, (uint64_t)world, (uint64_t)per_batch, (uint64_t)wlen,
                                  (uint64_t)ctx->prm.max_lag | ((uint64_t)ctx->prm.k1_smooth << 32) | ((uint64_t)(ctx->prm.k1_gate != 0) << 62) |
@@ -1704,6 +1728,9 @@ std::vector<uint64_t> step_graph_key(const tdoa_ctx *ctx, int rank, int world, i
         key.push_back((uint64_t)c.n);
     }
     key.push_back(ctx->graph_prof ? 0x100000000ull | ctx->prof_mask : 0ull);      // an instrumented step is a different graph
+    key.push_back((uint64_t)surf_mode);
+    key.push_back((uint64_t)sel_k);
+    key.push_back((uint64_t)sel_sep);
     return key;
 }
 
@@ -1952,7 +1979,8 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->scales, &ctx->peaks, &ctx->scratch_a, &ctx->scratch_b, &ctx->lagdump,
                       &ctx->ex_a, &ctx->ex_b, &ctx->ex_c, &ctx->ex_d, &ctx->ex_part,
                       &ctx->g_sw_desc, &ctx->g_pw_desc, &ctx->g_quad_desc, &ctx->g_scales, &ctx->g_keys, &ctx->fine_raw, &ctx->fine, &ctx->qual,
-                      &ctx->once_edges, &ctx->once_tiles, &ctx->once_fin, &ctx->slot_gain};
+                      &ctx->once_edges, &ctx->once_tiles, &ctx->once_fin, &ctx->slot_gain, &ctx->surf, &ctx->surf_out,
+                      &ctx->sel_peaks, &ctx->sel_count};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -2218,8 +2246,19 @@ int tdoa_plan_info(const tdoa_ctx *ctx, int64_t *fft_n, int32_t *n1, int32_t *n2
     return TDOA_OK;
 }
 
+// tdoa_process_lags / tdoa_process_peaks: what a step writes besides its peaks
+struct SurfaceOut {
+    int mode = 0;                            // 0: nothing, kSurfLags: the surfaces, kSurfPeaks: k peaks per pair-window
+    int k = 0, min_sep = 0;
+    float *lags_host = nullptr;
+    void *lags_dev = nullptr;
+    tdoa_peak *peaks_host = nullptr;
+    int32_t *count_host = nullptr;
+};
+constexpr int kSurfLags = 1, kSurfPeaks = 2;
+
 static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host, void *out_dev,
-                        tdoa_fine_peak *fine_host, double gate)
+                        tdoa_fine_peak *fine_host, double gate, const SurfaceOut &so = SurfaceOut{})
 {
     int rc;
     if ((rc = check_ctx(ctx))) return rc;
@@ -2295,13 +2334,32 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
     }
     if (n_first && (rc = reserve_fm_batch(ctx, plan_fm_batch(ctx->knobs, ctx->stg, ctx->n_cu, pl, lag_lo, lag_hi, shape_of(n_first * S, n_first * P, 0)))))
         return rc;
+    // surface outputs: allocated after the grouping is fixed (batch_bound counts these buffers as held, so a later call
+    // groups as this one did)
+    const int n_lags = lag_hi - lag_lo + 1;
+    const size_t n_owned = lay.pw.size(), surf_n = (size_t)n_lags * slots;
+    if (so.mode) {
+        auto nomem = [&](const char *what) {
+            char buf[256];
+            snprintf(buf, sizeof(buf), "%s (%.1f MB) does not fit in device memory: %s", what,
+                     (so.mode == kSurfLags ? 2.0 : 1.0) * 4.0 * (double)n_lags * (double)std::max(n_owned, slots) / 1e6,
+                     ctx->last_error.c_str());
+            return fail(ctx, TDOA_ERR_NOMEM, buf);
+        };
+        if (ensure(ctx, ctx->surf, sizeof(float) * std::max<size_t>(n_owned * n_lags, 1))) return nomem("correlation surfaces");
+        if (so.mode == kSurfLags && ensure(ctx, ctx->surf_out, sizeof(float) * (surf_n + 1))) return nomem("correlation surfaces, caller's layout");
+        if (so.mode == kSurfPeaks && (ensure(ctx, ctx->sel_peaks, sizeof(PeakOut) * slots * so.k) ||
+                                      ensure(ctx, ctx->sel_count, sizeof(int32_t) * (slots + 1))))
+            return nomem("selected peaks");
+    }
     auto *d_sw = static_cast<SWDesc *>(ctx->g_sw_desc.p);
     auto *d_pw = static_cast<PWDesc *>(ctx->g_pw_desc.p);
     auto *d_quads = static_cast<QuadDesc *>(ctx->g_quad_desc.p);
     auto *d_keys = static_cast<unsigned long long *>(ctx->g_keys.p);
     auto *d_scales = static_cast<double *>(ctx->g_scales.p);
 
-    const std::vector<uint64_t> key = step_graph_key(ctx, rank, world, per_batch, wlen, block, go, fine_host != nullptr, gate);
+    const std::vector<uint64_t> key = step_graph_key(ctx, rank, world, per_batch, wlen, block, go, fine_host != nullptr, gate,
+                                                     so.mode, so.k, so.min_sep);
     if (!step_graph_replays(ctx, key)) {
         std::vector<double> scales(slots, 1.0 / (4.0 * (double)n * std::sqrt((double)corr_len)));
         HIPCHK(ctx, hipMemcpyAsync(d_scales, scales.data(), sizeof(double) * slots, hipMemcpyHostToDevice, st));
@@ -2325,8 +2383,12 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
         for (size_t w0 = 0; w0 < n_mine; w0 += per_batch) {
             const int nw = (int)std::min<size_t>(per_batch, n_mine - w0);
             const int n_sw = (int)(lay.sw_off[w0 + nw] - lay.sw_off[w0]), n_pw = (int)(lay.pw_off[w0 + nw] - lay.pw_off[w0]);
-            const FmBufs bf{d_sw + lay.sw_off[w0], go ? d_sw + n_sw_all + lay.sw_off[w0] : nullptr, d_pw + lay.pw_off[w0],
-                            d_quads + lay.q_off[w0], d_keys, nullptr, 1.0f, (double)wlen * n_sw, fine_raw};
+            FmBufs bf{d_sw + lay.sw_off[w0], go ? d_sw + n_sw_all + lay.sw_off[w0] : nullptr, d_pw + lay.pw_off[w0],
+                      d_quads + lay.q_off[w0], d_keys, nullptr, 1.0f, (double)wlen * n_sw, fine_raw};
+            if (so.mode) {                   // the K5 kernels' lag arrays, pair-window i of the batch at i * n_lags
+                bf.lag_dump = static_cast<float *>(ctx->surf.p) + lay.pw_off[w0] * (size_t)n_lags;
+                bf.dump_stride = (size_t)n_lags;
+            }
             const int r = run_fm_batch(ctx, shape_of(n_sw, n_pw, (int)(lay.q_off[w0 + nw] - lay.q_off[w0])), pl, lag_lo, lag_hi, bf);
             if (r) return r;
         }
@@ -2339,6 +2401,25 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
         ProfScope ps(ctx, TDOA_K_PEAK, 32.0 * (double)slots);
         hipLaunchKernelGGL(k_decode_peaks, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, d_keys, d_scales,
                            static_cast<PeakOut *>(ctx->peaks.p), (int)slots, slot_gain);
+        if (so.mode) ctx->prof_last = -1;    // unscoped launches: kernel nodes, the step stays one chain
+        const float *surf = static_cast<const float *>(ctx->surf.p);
+        if (so.mode == kSurfLags) {
+            hipLaunchKernelGGL(k_zero_u64, dim3((unsigned)((surf_n / 2 + 256) / 256)), dim3(256), 0, st,
+                               static_cast<unsigned long long *>(ctx->surf_out.p), (surf_n + 1) / 2);
+            if (n_owned)
+                hipLaunchKernelGGL(k_surface_out, dim3((unsigned)n_owned, (unsigned)((n_lags + 1023) / 1024)), dim3(256), 0, st, surf,
+                                   (size_t)n_lags, n_lags, d_pw, d_scales, slot_gain, static_cast<float *>(ctx->surf_out.p));
+        } else if (so.mode == kSurfPeaks) {
+            const size_t rec_words = slots * (size_t)so.k * (sizeof(PeakOut) / 8);
+            hipLaunchKernelGGL(k_zero_u64, dim3((unsigned)((rec_words + 255) / 256)), dim3(256), 0, st,
+                               static_cast<unsigned long long *>(ctx->sel_peaks.p), rec_words);
+            hipLaunchKernelGGL(k_zero_u64, dim3((unsigned)((slots / 2 + 256) / 256)), dim3(256), 0, st,
+                               static_cast<unsigned long long *>(ctx->sel_count.p), (slots + 1) / 2);
+            if (n_owned)
+                hipLaunchKernelGGL(k_select_peaks, dim3((unsigned)n_owned), dim3(kSelThreads), 0, st, surf, (size_t)n_lags, n_lags,
+                                   lag_lo, d_pw, d_keys, d_scales, slot_gain, so.k, so.min_sep,
+                                   static_cast<PeakOut *>(ctx->sel_peaks.p), static_cast<int32_t *>(ctx->sel_count.p));
+        }
         return TDOA_OK;
     };
     if ((rc = run_step_graph(ctx, key, enqueue))) return rc;
@@ -2349,6 +2430,14 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
         HIPCHK(ctx, hipMemcpyAsync(out_host, ctx->peaks.p, sizeof(PeakOut) * slots, hipMemcpyDeviceToHost, st));
     if (fine_host)
         HIPCHK(ctx, hipMemcpyAsync(fine_host, ctx->fine.p, sizeof(FineOut) * slots, hipMemcpyDeviceToHost, st));
+    if (so.lags_dev)
+        HIPCHK(ctx, hipMemcpyAsync(so.lags_dev, ctx->surf_out.p, sizeof(float) * surf_n, hipMemcpyDeviceToDevice, st));
+    if (so.lags_host)
+        HIPCHK(ctx, hipMemcpyAsync(so.lags_host, ctx->surf_out.p, sizeof(float) * surf_n, hipMemcpyDeviceToHost, st));
+    if (so.peaks_host)
+        HIPCHK(ctx, hipMemcpyAsync(so.peaks_host, ctx->sel_peaks.p, sizeof(PeakOut) * slots * so.k, hipMemcpyDeviceToHost, st));
+    if (so.count_host)
+        HIPCHK(ctx, hipMemcpyAsync(so.count_host, ctx->sel_count.p, sizeof(int32_t) * slots, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     prof_collect(ctx);
     collect_step_graph_marks(ctx);
@@ -2372,6 +2461,78 @@ int tdoa_fm_xcorr_fine_u8(tdoa_ctx *ctx, const uint8_t *iq1, size_t n1, const ui
 {
     if (!fine || !(gate_samples >= 0.0)) return fail(ctx, TDOA_ERR_INVALID, "fine is NULL or gate < 0");
     return fm_pair(ctx, iq1, n1, iq2, n2, max_lag, peak, nullptr, fine, gate_samples);
+}
+
+// the arguments of the peak selection (k in 1 .. kSelMaxK, min_separation >= 1, an output) and the lag mode it needs
+static int check_selection(tdoa_ctx *ctx, int k, int min_separation, const void *out)
+{
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (k < 1 || k > kSelMaxK || min_separation < 1 || !out)
+        return fail(ctx, TDOA_ERR_INVALID, "k outside 1..16, min_separation < 1 or output NULL");
+    if (ctx->prm.lag_mode == TDOA_LAGS_GO) return fail(ctx, TDOA_ERR_UNSUPPORTED, "peak selection with TDOA_LAGS_GO");
+    return TDOA_OK;
+}
+
+int tdoa_process_lags(tdoa_ctx *ctx, int rank, int world, float *lags_host, void *lags_dev)
+{
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (!lags_host && !lags_dev) return fail(ctx, TDOA_ERR_INVALID, "lags_host and lags_dev are NULL");
+    if (ctx->prm.lag_mode == TDOA_LAGS_GO) return fail(ctx, TDOA_ERR_UNSUPPORTED, "correlation surfaces with TDOA_LAGS_GO");
+    SurfaceOut so;
+    so.mode = kSurfLags;
+    so.lags_host = lags_host;
+    so.lags_dev = lags_dev;
+    return process_impl(ctx, rank, world, nullptr, nullptr, nullptr, 0.0, so);
+}
+
+int tdoa_process_peaks(tdoa_ctx *ctx, int rank, int world, int k, int min_separation, tdoa_peak *peaks_host,
+                       int32_t *count_host)
+{
+    int rc;
+    if ((rc = check_selection(ctx, k, min_separation, peaks_host))) return rc;
+    SurfaceOut so;
+    so.mode = kSurfPeaks;
+    so.k = k;
+    so.min_sep = min_separation;
+    so.peaks_host = peaks_host;
+    so.count_host = count_host;
+    return process_impl(ctx, rank, world, nullptr, nullptr, nullptr, 0.0, so);
+}
+
+int tdoa_fm_xcorr_peaks_u8(tdoa_ctx *ctx, const uint8_t *iq1, size_t n1, const uint8_t *iq2, size_t n2, int max_lag, int k,
+                           int min_separation, tdoa_peak *peaks, int32_t *count)
+{
+    int rc;
+    if ((rc = check_selection(ctx, k, min_separation, peaks))) return rc;
+    return fm_pair(ctx, iq1, n1, iq2, n2, max_lag, nullptr, nullptr, nullptr, 0.0, k, min_separation, peaks, count);
+}
+
+int tdoa_debug_select_peaks(tdoa_ctx *ctx, const float *surface, int n_lags, int lag_lo, int k, int min_separation,
+                            tdoa_peak *peaks, int32_t *count)
+{
+    int rc;
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (k < 1 || k > kSelMaxK || min_separation < 1 || !peaks || !surface || n_lags < 1 ||
+        (long long)lag_lo + n_lags - 1 > INT_MAX / 2 || lag_lo < -(INT_MAX / 2))
+        return fail(ctx, TDOA_ERR_INVALID, "bad argument");
+    if ((rc = check_ctx(ctx))) return rc;
+    if ((rc = ensure(ctx, ctx->lagdump, sizeof(float) * (size_t)n_lags))) return rc;
+    if ((rc = ensure(ctx, ctx->scales, sizeof(double)))) return rc;
+    if ((rc = ensure(ctx, ctx->sel_peaks, sizeof(PeakOut) * k))) return rc;
+    if ((rc = ensure(ctx, ctx->sel_count, sizeof(int32_t)))) return rc;
+    const double one = 1.0;
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->lagdump.p, surface, sizeof(float) * (size_t)n_lags, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->scales.p, &one, sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_select_peaks, dim3(1), dim3(kSelThreads), 0, st, static_cast<const float *>(ctx->lagdump.p), (size_t)0,
+                       n_lags, lag_lo, static_cast<const PWDesc *>(nullptr), static_cast<const unsigned long long *>(nullptr),
+                       static_cast<const double *>(ctx->scales.p), static_cast<const double *>(nullptr), k, min_separation,
+                       static_cast<PeakOut *>(ctx->sel_peaks.p), static_cast<int32_t *>(ctx->sel_count.p));
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(peaks, ctx->sel_peaks.p, sizeof(PeakOut) * k, hipMemcpyDeviceToHost, st));
+    if (count) HIPCHK(ctx, hipMemcpyAsync(count, ctx->sel_count.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));       // `one` is a stack object
+    return TDOA_OK;
 }
 
 // fast_analyzer.go:139-155 and collector.go:224 from the exact integer sums, in the reference's expression order
@@ -2630,7 +2791,7 @@ int tdoa_debug_poison_workspace(tdoa_ctx *ctx)
     if (!ctx) return TDOA_ERR_INVALID;
     // floats only: no kernel derives an index from a value in these buffers (peak lags come from the keys, which are not
     // poisoned), so a NaN can end up in a result but never in an address
-    for (DevBuf *b : {&ctx->v, &ctx->tz, &ctx->fine_raw, &ctx->once_edges})
+    for (DevBuf *b : {&ctx->v, &ctx->tz, &ctx->fine_raw, &ctx->once_edges, &ctx->surf, &ctx->surf_out})
         if (b->p && b->cap >= 4) HIPCHK(ctx, hipMemsetD32Async(static_cast<hipDeviceptr_t>(b->p), 0x7FC00000, b->cap / 4, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return TDOA_OK;

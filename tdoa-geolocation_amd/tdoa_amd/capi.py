@@ -84,7 +84,7 @@ SYMBOLS = [
     "tdoa_debug_flags", "tdoa_debug_last_k1", "tdoa_debug_graph_info", "tdoa_debug_poison_workspace", "tdoa_debug_last_route", "tdoa_debug_segment_quads", "tdoa_debug_staged_groups", "tdoa_debug_step_layout", "tdoa_cross_correlate_batch_c64",
     "tdoa_latlon_to_ecef", "tdoa_ecef_to_latlon", "tdoa_solve_3station", "tdoa_solve_nstation", "tdoa_solve_surface",
     "tdoa_profile_enable", "tdoa_profile_select", "tdoa_profile_reset", "tdoa_profile_get", "tdoa_kernel_name",
-    "tdoa_plan_info",
+    "tdoa_plan_info", "tdoa_process_lags", "tdoa_process_peaks", "tdoa_fm_xcorr_peaks_u8", "tdoa_debug_select_peaks",
 ]
 
 _lib = None
@@ -171,6 +171,10 @@ def load(build_if_missing=True):
     L.tdoa_profile_reset.argtypes = [vp]
     L.tdoa_profile_get.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_int64), dp]
     L.tdoa_plan_info.argtypes = [vp, C.POINTER(C.c_int64), i32p, i32p]
+    L.tdoa_process_lags.argtypes = [vp, C.c_int, C.c_int, fp, vp]
+    L.tdoa_process_peaks.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p]
+    L.tdoa_fm_xcorr_peaks_u8.argtypes = [vp, u8p, sz, u8p, sz, C.c_int, C.c_int, C.c_int, vp, i32p]
+    L.tdoa_debug_select_peaks.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p]
     _lib = L
     return L
 
@@ -435,6 +439,46 @@ class Context:
         out = np.zeros(2 * max_lag - 1, dtype=np.float64)
         self._chk(self._L.tdoa_fm_xcorr_lags_u8(self._h, _u8(a), a.size // 2, _u8(b), b.size // 2, int(max_lag), _d(out)))
         return out
+
+    def process_lags(self, rank=0, world=1, out_dev_ptr=None, want_host=True):
+        """tdoa_process_lags -> [W][P][2 max_lag - 1] float32 correlation surfaces, reference scale (lag d at d + max_lag - 1);
+        windows of other ranks are zero"""
+        wpb, w = self.num_windows()
+        out = np.zeros((w, self.num_pairs(), 2 * self.params.max_lag - 1), dtype=np.float32) if want_host else None
+        self._chk(self._L.tdoa_process_lags(self._h, int(rank), int(world), _f(out) if want_host else None,
+                                            C.c_void_p(int(out_dev_ptr)) if out_dev_ptr else None))
+        return out
+
+    def process_peaks(self, k, min_separation, rank=0, world=1):
+        """tdoa_process_peaks -> (peaks [W][P][k] PEAK_DTYPE, count [W][P] int32): the k strongest separate peaks of every
+        pair-window (include/tdoa_mi355x.h states the rule); peak 1 is process()'s"""
+        wpb, w = self.num_windows()
+        p = self.num_pairs()
+        out = np.zeros((w, p, max(int(k), 1)), dtype=PEAK_DTYPE)
+        count = np.zeros((w, p), dtype=np.int32)
+        self._chk(self._L.tdoa_process_peaks(self._h, int(rank), int(world), int(k), int(min_separation),
+                                             out.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out, count
+
+    def fm_xcorr_peaks(self, iq1, iq2, max_lag, k, min_separation):
+        """tdoa_fm_xcorr_peaks_u8 -> (peaks [k] PEAK_DTYPE, count) of one pair of windows"""
+        a = np.ascontiguousarray(iq1, dtype=np.uint8)
+        b = np.ascontiguousarray(iq2, dtype=np.uint8)
+        out = np.zeros(max(int(k), 1), dtype=PEAK_DTYPE)
+        count = C.c_int32()
+        self._chk(self._L.tdoa_fm_xcorr_peaks_u8(self._h, _u8(a), a.size // 2, _u8(b), b.size // 2, int(max_lag), int(k),
+                                                 int(min_separation), out.ctypes.data_as(C.c_void_p), C.byref(count)))
+        return out, count.value
+
+    def debug_select_peaks(self, surface, lag_lo, k, min_separation):
+        """tdoa_debug_select_peaks: the selection kernel on a raw surface (lags lag_lo, lag_lo + 1, ...) at scale 1 ->
+        (peaks [k] PEAK_DTYPE, count)"""
+        c = np.ascontiguousarray(surface, dtype=np.float32)
+        out = np.zeros(max(int(k), 1), dtype=PEAK_DTYPE)
+        count = C.c_int32()
+        self._chk(self._L.tdoa_debug_select_peaks(self._h, _f(c), c.size, int(lag_lo), int(k), int(min_separation),
+                                                  out.ctypes.data_as(C.c_void_p), C.byref(count)))
+        return out, count.value
 
     def fm_preprocess(self, iq):
         a = np.ascontiguousarray(iq, dtype=np.uint8)
