@@ -123,3 +123,67 @@ func (g *gpuCorrelator) windowQuality(stations int) ([]C.tdoa_window_quality, er
 	}
 	return out, nil
 }
+
+// Group shards the batched path over several GPUs in one call: one tdoa_ctx per member, member k = rank k of
+// len(devices). Devices may repeat (several members on one GPU). Not safe for concurrent use; the library runs the
+// members on threads of its own inside each call and merges their peaks on the host.
+type Group struct{ g *C.tdoa_group }
+
+// NewGroup opens one context per entry of devices (e.g. 0..tdoa_device_count()-1 for the whole node).
+func NewGroup(devices []int32, goLagSet bool) (*Group, error) {
+	if len(devices) == 0 {
+		return nil, fmt.Errorf("tdoa_group_create: no devices")
+	}
+	var p C.tdoa_params
+	C.tdoa_default_params(&p)
+	if goLagSet {
+		p.lag_mode = C.TDOA_LAGS_GO
+	}
+	var g *C.tdoa_group
+	rc := C.tdoa_group_create(&p, (*C.int32_t)(unsafe.Pointer(&devices[0])), C.int(len(devices)), &g)
+	if rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_group_create: %s (%s)", C.GoString(C.tdoa_strerror(rc)),
+			C.GoString(C.tdoa_group_last_error(nil)))
+	}
+	return &Group{g: g}, nil
+}
+
+func (g *Group) Close() { C.tdoa_group_destroy(g.g) }
+
+// UploadFiles hands the group one .dat file per station (paths[s] = station s); every member reads only the sample
+// runs of the windows it owns. Returns size/2 per file, like loadIQData (processor.go:182).
+func (g *Group) UploadFiles(paths []string) ([]int, error) {
+	if len(paths) == 0 {
+		return nil, fmt.Errorf("tdoa_group_capture_upload_files: no files")
+	}
+	cpaths := make([]*C.char, len(paths)) // C strings: the slice holds no Go pointers (cgo rule)
+	for i, p := range paths {
+		cpaths[i] = C.CString(p)
+		defer C.free(unsafe.Pointer(cpaths[i]))
+	}
+	ns := make([]C.size_t, len(paths))
+	if rc := C.tdoa_group_capture_upload_files(g.g, C.int(len(paths)), &cpaths[0], &ns[0]); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_group_capture_upload_files: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	out := make([]int, len(ns))
+	for i, n := range ns {
+		out[i] = int(n)
+	}
+	return out, nil
+}
+
+// Process is processCaptures over the group: one peak per (window, pair), pairs ordered i<j, the same bytes one context
+// returns.
+func (g *Group) Process() ([]C.tdoa_peak, int, error) {
+	m := C.tdoa_group_member(g.g, 0)
+	var perBlock, total C.int
+	if rc := C.tdoa_num_windows(m, &perBlock, &total); rc != C.TDOA_OK {
+		return nil, 0, fmt.Errorf("tdoa_num_windows: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs := int(C.tdoa_num_pairs(m))
+	out := make([]C.tdoa_peak, int(total)*pairs)
+	if rc := C.tdoa_group_process(g.g, &out[0]); rc != C.TDOA_OK {
+		return nil, 0, fmt.Errorf("tdoa_group_process: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return out, pairs, nil
+}

@@ -394,6 +394,50 @@ int tdoa_debug_staged_groups(int n_stations, int max_pairs, uint32_t *masks_out,
 int tdoa_debug_step_layout(int n_stations, int n_windows, int rank, int world, int max_per_batch, int32_t *pw_out, int max_pw,
                            int32_t *quads_out, int32_t *n_quads);
 
+/* ---- multi-device group ----------------------------------------------------
+ * One call that shards tdoa_process over several GPUs (processor.go:816-850 over a node's devices).  A group holds one
+ * tdoa_ctx per member; member k is rank k of n_members in the sense of tdoa_process(ctx, rank, world, ...), so the
+ * (window, pair) units are dealt exactly as there.  Devices may repeat: several members on one GPU share it.
+ *
+ * Ownership: the group owns its member contexts; tdoa_group_destroy destroys them.  The library copies what it needs
+ * during a call and keeps no host pointer afterwards.
+ * Threading: a group is single-caller, like a context.  Inside tdoa_group_capture_upload_files and tdoa_group_process
+ * member 0 runs on the caller's thread and every other member on a host thread of its own, started for the call and
+ * joined before it returns; each thread calls into its own member only.  No collective library is used: the peak records
+ * come back to the host and are merged there. */
+typedef struct tdoa_group tdoa_group;
+
+/* one tdoa_ctx per member, member k = rank k of n_members; devices may repeat (several members on one GPU).  p may be NULL
+ * (tdoa_default_params); p->device is ignored.  TDOA_ERR_INVALID for n_members < 1, NULL devices / out or a negative
+ * ordinal, TDOA_ERR_NO_DEVICE for an ordinal >= tdoa_device_count(), both before any member is created; if a member's
+ * tdoa_create fails, the members already made are destroyed and its status returned.  *out is NULL on every failure, and
+ * tdoa_group_last_error(NULL) then names the member (the calling thread's last failed tdoa_group_create). */
+int         tdoa_group_create(const tdoa_params *p, const int32_t *devices, int n_members, tdoa_group **out);
+void        tdoa_group_destroy(tdoa_group *g);   /* NULL: no-op */
+const char *tdoa_group_last_error(const tdoa_group *g);  /* "member k (device d): <that ctx's tdoa_last_error>" */
+tdoa_ctx   *tdoa_group_member(tdoa_group *g, int k);     /* borrowed; for synth/download/debug calls on one member;
+                                                            NULL for k outside 0 .. n_members - 1 */
+
+/* .dat files (raw u8 I,Q, any size): each member preads and uploads only the sample runs its windows need
+ * (tdoa_debug_owned_runs; the window grid comes from the shortest file), after dropping its previous captures.  Station s
+ * is paths[s]; *n_samples (may be NULL) receives size/2 per file, like tdoa_capture_upload_file. */
+int tdoa_group_capture_upload_files(tdoa_group *g, int n_stations, const char *const *paths, size_t *n_samples);
+
+/* every pair on every window, sharded over the members; out_host = [n_windows_total][n_pairs], byte-identical to
+ * tdoa_process(single ctx, 0, 1, out_host, NULL) on the same captures.  TDOA_ERR_STATE if the members do not hold the same
+ * station count and capture lengths (captures made on single members through tdoa_group_member must agree).  out_host is
+ * written only if every member succeeded; otherwise the first failing member's status is returned and
+ * tdoa_group_last_error names it.  With one member, its tdoa_process writes out_host directly. */
+int tdoa_group_process(tdoa_group *g, tdoa_peak *out_host);
+
+/* the sample runs member `rank` of `world` uploads for a capture of total_samples (window grid from n_min, the shortest
+ * capture of the job; block offsets from the capture's own thirds): adjacent owned windows form one run, and with fewer
+ * windows than members (the pair-major fallback) the whole capture is one run.  *n_runs receives the number of runs; at
+ * most max_runs of them are written to first[] / count[] (max_runs = 0 with NULL arrays asks for the count).
+ * host-only, no device needed */
+int tdoa_debug_owned_runs(size_t total_samples, size_t n_min, int64_t window_len, int rank, int world,
+                          size_t *first, size_t *count, int max_runs, int *n_runs);
+
 /* ---- downstream (processor.go:125-163, 932-1045), host side ---------------- */
 void tdoa_latlon_to_ecef(double lat, double lon, double elev, double xyz[3]);
 void tdoa_ecef_to_latlon(double x, double y, double z, double lle[3]);

@@ -61,9 +61,9 @@ public:
         streams_.clear();
     }
 
-    // copy `bytes` from src (host memory) or, when src is NULL, from file descriptor fd at offset 0, to dst (device).
-    // Returns 0 ok, 1 HIP failure, 2 short read.
-    int run(uint8_t *dst, const uint8_t *src, int fd, size_t bytes)
+    // copy `bytes` from src (host memory) or, when src is NULL, from file descriptor fd at byte offset file_off, to dst
+    // (device).  Returns 0 ok, 1 HIP failure, 2 short read.
+    int run(uint8_t *dst, const uint8_t *src, int fd, size_t bytes, size_t file_off = 0)
     {
         const int T = threads();
         const size_t n_chunks = (bytes + kChunk - 1) / kChunk;
@@ -82,7 +82,7 @@ public:
                 } else {
                     size_t got = 0;
                     while (got < len) {
-                        const ssize_t r = pread(fd, static_cast<uint8_t *>(buf) + got, len - got, (off_t)(off + got));
+                        const ssize_t r = pread(fd, static_cast<uint8_t *>(buf) + got, len - got, (off_t)(file_off + off + got));
                         if (r <= 0) { status = 2; return; }
                         got += (size_t)r;
                     }

@@ -1616,6 +1616,17 @@ struct StepLayout {
     std::vector<size_t> sw_off, pw_off, q_off;
 };
 
+// The rank of `world` that runs pair p of window wid in a job of W windows and P pairs -- the one statement of the sharding
+// rule that the step layout, the multi-device group's merge and its file ingest all use.  Window-major:
+// rank r owns the windows wid = r (mod world), so a station-window is transformed once and reused by all its pairs.  With
+// fewer windows than ranks that would leave ranks idle: then the (window, pair) units u = wid*P + p are dealt
+// u = r (mod world) and a rank transforms only the stations its pairs need (station spectra are duplicated across ranks).
+// tdoa_amd/sharding.py unit_owner states the same rule.
+int unit_owner(int wid, int p, int W, int P, int world)
+{
+    return W < world ? (int)(((long long)wid * P + p) % world) : wid % world;
+}
+
 // max_per_batch: the caller's bound (tdoa_params.windows_per_batch, workspace).  TDOA_ERR_UNSUPPORTED: a window's station
 // or pair count alone exceeds the grid limit.
 int build_step_layout(int S, int W, int rank, int world, int max_per_batch, QuadCache &quad_cache, StepLayout *out)
@@ -1623,12 +1634,7 @@ int build_step_layout(int S, int W, int rank, int world, int max_per_batch, Quad
     const int P = S * (S - 1) / 2;
     StepLayout &L = *out;
     L = StepLayout{};
-    // Sharding: window-major -- rank r owns the windows wid = r (mod world), so a station-window
-    // is transformed once and reused by all its pairs.  With fewer windows than ranks that would leave ranks idle:
-    // then the (window, pair) units u = wid*P + p are dealt u = r (mod world) and a rank transforms only the
-    // stations its pairs need (station spectra are duplicated across ranks).  tdoa_amd/sharding.py unit_owner states the same rule.
-    const bool pair_major = W < world;
-    auto owns = [&](int wid, int p) { return pair_major ? ((wid * P + p) % world) == rank : (wid % world) == rank; };
+    auto owns = [&](int wid, int p) { return unit_owner(wid, p, W, P, world) == rank; };
     for (int w = 0; w < W; w++) {
         bool any = false;
         for (int p = 0; p < P && !any; p++) any = owns(w, p);
@@ -2013,8 +2019,8 @@ static int capture_buffer(tdoa_ctx *ctx, int station, size_t bytes, uint8_t **ou
     return TDOA_OK;
 }
 
-// host memory (src) or file (fd, from offset 0) -> device, through the context's staged uploader
-static int staged_upload(tdoa_ctx *ctx, uint8_t *dst, const uint8_t *src, int fd, size_t bytes)
+// host memory (src) or file (fd, from byte file_off) -> device, through the context's staged uploader
+static int staged_upload(tdoa_ctx *ctx, uint8_t *dst, const uint8_t *src, int fd, size_t bytes, size_t file_off = 0)
 {
     if (bytes == 0) return TDOA_OK;
     if (bytes < (1u << 20) && src) {   // small: one plain copy beats waking threads
@@ -2027,7 +2033,7 @@ static int staged_upload(tdoa_ctx *ctx, uint8_t *dst, const uint8_t *src, int fd
         (void)hipGetLastError();
         return fail(ctx, TDOA_ERR_HIP, "staging buffers for the uploader");
     }
-    const int st = ctx->uploader.run(dst, src, fd, bytes);
+    const int st = ctx->uploader.run(dst, src, fd, bytes, file_off);
     if (st == 2) return fail(ctx, TDOA_ERR_INVALID, "failed to read data");
     if (st) {
         (void)hipGetLastError();
@@ -2066,6 +2072,26 @@ int tdoa_capture_upload_range(tdoa_ctx *ctx, int station, size_t total_samples, 
     ctx->caps[station].n = 0;                                  // not valid until the copy has finished
     if ((rc = staged_upload(ctx, d + 2 * first_sample, iq, -1, 2 * n_samples))) return rc;
     (void)had;
+    ctx->caps[station].n = total_samples;
+    return TDOA_OK;
+}
+
+// The file form of tdoa_capture_upload_range, for the multi-device group's ingest (group_api.inc): every run
+// [first, first + count) of a capture of total_samples is pread from fd at byte 2 first straight into a station buffer of
+// the capture's full size, through the same staged uploader.
+static int capture_upload_file_runs(tdoa_ctx *ctx, int station, int fd, size_t total_samples,
+                                    const std::vector<std::pair<size_t, size_t>> &runs)
+{
+    int rc;
+    if ((rc = check_ctx(ctx))) return rc;
+    if (station < 0 || station > 1023 || fd < 0) return fail(ctx, TDOA_ERR_INVALID, "bad station/file");
+    for (const auto &r : runs)
+        if (r.first > total_samples || r.second > total_samples - r.first) return fail(ctx, TDOA_ERR_INVALID, "run outside capture");
+    uint8_t *d = nullptr;
+    if ((rc = capture_buffer(ctx, station, 2 * total_samples, &d))) return rc;
+    ctx->caps[station].n = 0;                                  // not valid until every copy has finished
+    for (const auto &r : runs)
+        if ((rc = staged_upload(ctx, d + 2 * r.first, nullptr, fd, 2 * r.second, 2 * r.first))) return rc;
     ctx->caps[station].n = total_samples;
     return TDOA_OK;
 }
@@ -2193,6 +2219,7 @@ int tdoa_capture_download(tdoa_ctx *ctx, int station, size_t first_sample, size_
 int tdoa_capture_clear(tdoa_ctx *ctx)
 {
     if (!ctx) return TDOA_ERR_INVALID;
+    (void)hipSetDevice(ctx->device);         // the caller's thread may last have used another context's device
     for (auto &c : ctx->caps)
         if (c.owned && c.dev) (void)hipFree(const_cast<uint8_t *>(c.dev));
     ctx->caps.clear();
@@ -2899,3 +2926,4 @@ int tdoa_debug_stg_prof(unsigned long long *out8)
 }  // extern "C"
 
 #include "exact_reference_api.inc"
+#include "group_api.inc"

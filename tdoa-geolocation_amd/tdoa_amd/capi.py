@@ -85,6 +85,8 @@ SYMBOLS = [
     "tdoa_latlon_to_ecef", "tdoa_ecef_to_latlon", "tdoa_solve_3station", "tdoa_solve_nstation", "tdoa_solve_surface",
     "tdoa_profile_enable", "tdoa_profile_select", "tdoa_profile_reset", "tdoa_profile_get", "tdoa_kernel_name",
     "tdoa_plan_info", "tdoa_process_lags", "tdoa_process_peaks", "tdoa_fm_xcorr_peaks_u8", "tdoa_debug_select_peaks",
+    "tdoa_group_create", "tdoa_group_destroy", "tdoa_group_last_error", "tdoa_group_member",
+    "tdoa_group_capture_upload_files", "tdoa_group_process", "tdoa_debug_owned_runs",
 ]
 
 _lib = None
@@ -175,6 +177,17 @@ def load(build_if_missing=True):
     L.tdoa_process_peaks.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p]
     L.tdoa_fm_xcorr_peaks_u8.argtypes = [vp, u8p, sz, u8p, sz, C.c_int, C.c_int, C.c_int, vp, i32p]
     L.tdoa_debug_select_peaks.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p]
+    L.tdoa_group_create.argtypes = [C.POINTER(Params), i32p, C.c_int, C.POINTER(vp)]
+    L.tdoa_group_destroy.argtypes = [vp]
+    L.tdoa_group_destroy.restype = None
+    L.tdoa_group_last_error.argtypes = [vp]
+    L.tdoa_group_last_error.restype = C.c_char_p
+    L.tdoa_group_member.argtypes = [vp, C.c_int]
+    L.tdoa_group_member.restype = vp
+    L.tdoa_group_capture_upload_files.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(sz)]
+    L.tdoa_group_process.argtypes = [vp, vp]
+    L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
+                                        C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -202,16 +215,21 @@ def _c64(x):
     return a, a.view(np.float32)
 
 
+def _params(kw):
+    p = default_params()
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError("unknown parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 class Context:
     """One tdoa_ctx (one GPU, single caller)."""
 
     def __init__(self, **kw):
         self._L = load()
-        p = default_params()
-        for k, v in kw.items():
-            if not hasattr(p, k):
-                raise TypeError("unknown parameter %r" % k)
-            setattr(p, k, v)
+        p = _params(kw)
         self.params = p
         h = C.c_void_p()
         rc = self._L.tdoa_create(C.byref(p), C.byref(h))
@@ -571,6 +589,87 @@ class Context:
         return n.value, n1.value, n2.value
 
 
+class _Member(Context):
+    """A group member's tdoa_ctx, borrowed (tdoa_group_member): every Context call; close() leaves it to the group."""
+
+    def __init__(self, group, handle):
+        self._L = group._L
+        self.params = group.params
+        self._group = group                  # the group outlives its views
+        self._h = C.c_void_p(handle)
+
+    def close(self):
+        self._h = None
+
+
+class Group:
+    """A multi-device group (tdoa_group): one tdoa_ctx per member, member k = rank k of len(devices) in tdoa_process's
+    sharding; devices may repeat (several members on one GPU).  Keyword arguments are tdoa_params fields, as for Context."""
+
+    def __init__(self, devices, **kw):
+        self._L = load()
+        self.params = _params(kw)
+        self.devices = [int(d) for d in devices]
+        n = len(self.devices)
+        devs = (C.c_int32 * n)(*self.devices)
+        h = C.c_void_p()
+        rc = self._L.tdoa_group_create(C.byref(self.params), devs if n else None, n, C.byref(h))
+        if rc != OK:
+            raise TdoaError(rc, "%s (%s)" % (self._L.tdoa_strerror(rc).decode(), self._L.tdoa_group_last_error(None).decode()))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.tdoa_group_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _chk(self, rc):
+        if rc != OK:
+            detail = self._L.tdoa_group_last_error(self._h).decode()
+            raise TdoaError(rc, "%s (%s)" % (self._L.tdoa_strerror(rc).decode(), detail))
+
+    def member(self, k):
+        """member k's context, borrowed: synth / download / debug calls on that member alone"""
+        h = self._L.tdoa_group_member(self._h, int(k))
+        if not h:
+            raise IndexError("no member %r in a group of %d" % (k, len(self.devices)))
+        return _Member(self, h)
+
+    def capture_upload_files(self, paths):
+        """station s = paths[s] (.dat, raw u8 I,Q); every member reads only the sample runs its windows need.
+        Returns size/2 per file."""
+        n = len(paths)
+        arr = (C.c_char_p * n)(*[os.fsencode(p) for p in paths])
+        ns = (C.c_size_t * n)()
+        self._chk(self._L.tdoa_group_capture_upload_files(self._h, n, arr, ns))
+        return list(ns)
+
+    def process(self, out=None):
+        """tdoa_group_process -> [W][P] PEAK_DTYPE, byte-identical to a single context's process(); `out` (optional): a
+        C-contiguous [W][P] PEAK_DTYPE array to write into (left as it was if the call fails)"""
+        m = self.member(0)
+        _, w = m.num_windows()
+        p = m.num_pairs()
+        if out is None:
+            out = np.zeros((w, p), dtype=PEAK_DTYPE)
+        elif out.dtype != PEAK_DTYPE or out.shape != (w, p) or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous (%d, %d) PEAK_DTYPE array" % (w, p))
+        self._chk(self._L.tdoa_group_process(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+
 def latlon_to_ecef(lat, lon, elev):
     out = np.zeros(3)
     load().tdoa_latlon_to_ecef(lat, lon, elev, _d(out))
@@ -639,6 +738,21 @@ def solve_surface(stations_lle, range_diff, weights=None, height_m=0.0):
     rc = load().tdoa_solve_surface(_d(st.reshape(-1)), n, _d(rd), _d(wt) if wt is not None else None, float(height_m),
                                    _d(out), C.byref(it))
     return rc, out, it.value
+
+
+def owned_runs(total_samples, n_min, window_len, rank, world):
+    """host only: [(first_sample, n_samples)] a group member `rank` of `world` uploads of a capture of total_samples
+    (tdoa_debug_owned_runs; the C++ form of sharding.owned_sample_runs)"""
+    L = load()
+    args = (int(total_samples), int(n_min), int(window_len), int(rank), int(world))
+    n = C.c_int(0)
+    rc = L.tdoa_debug_owned_runs(*args, None, None, 0, C.byref(n))          # the count first
+    first, count = (C.c_size_t * max(n.value, 1))(), (C.c_size_t * max(n.value, 1))()
+    if rc == OK:
+        rc = L.tdoa_debug_owned_runs(*args, first, count, n.value, C.byref(n))
+    if rc != OK:
+        raise ValueError("tdoa_debug_owned_runs: error %d" % rc)
+    return [(first[i], count[i]) for i in range(n.value)]
 
 
 def step_layout(n_stations, n_windows, rank, world, max_per_batch=2**31 - 1):
