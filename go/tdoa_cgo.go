@@ -113,6 +113,26 @@ func (g *gpuCorrelator) ProcessPeaks(k, minSeparation int) ([]C.tdoa_peak, []C.i
 	return peaks, count, nil
 }
 
+// ProcessStacked adds the correlation surfaces of windowsPerStack consecutive windows of a block (0: the whole block) lag by
+// lag and returns, per stack and pair, up to k peaks, their count and peak 1 refined to a fraction of a sample: one delay
+// per station pair and frequency block where single windows are too noisy for their own argmax (processor.go:770-782).
+func (g *gpuCorrelator) ProcessStacked(windowsPerStack, k, minSeparation int, gate float64) ([]C.tdoa_peak, []C.int32_t, []C.tdoa_fine_peak, error) {
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, nil, nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	n := int(total) * int(C.tdoa_num_pairs(g.ctx))
+	if n == 0 || k < 1 {
+		return nil, nil, nil, fmt.Errorf("tdoa_process_stacked: no stack-pairs or k < 1")
+	}
+	peaks, count, fine := make([]C.tdoa_peak, n*k), make([]C.int32_t, n), make([]C.tdoa_fine_peak, n)
+	if rc := C.tdoa_process_stacked(g.ctx, 0, 1, C.int(windowsPerStack), C.int(k), C.int(minSeparation), C.double(gate),
+		&peaks[0], &count[0], &fine[0], nil, nil); rc != C.TDOA_OK {
+		return nil, nil, nil, fmt.Errorf("tdoa_process_stacked: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return peaks, count, fine, nil
+}
+
 // windowQuality is fastAnalyzeSamples' statistics (fast_analyzer.go:117-155) for every (window, station).
 func (g *gpuCorrelator) windowQuality(stations int) ([]C.tdoa_window_quality, error) {
 	var perBlock, total C.int
@@ -186,4 +206,24 @@ func (g *Group) Process() ([]C.tdoa_peak, int, error) {
 		return nil, 0, fmt.Errorf("tdoa_group_process: %s", C.GoString(C.tdoa_group_last_error(g.g)))
 	}
 	return out, pairs, nil
+}
+
+// ProcessStacked is gpuCorrelator.ProcessStacked over the group: the members' fixed-point partial sums are added on the
+// host and finished on member 0, the same bytes one context returns.
+func (g *Group) ProcessStacked(windowsPerStack, k, minSeparation int, gate float64) ([]C.tdoa_peak, []C.int32_t, []C.tdoa_fine_peak, error) {
+	m := C.tdoa_group_member(g.g, 0)
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(m, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, nil, nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	n := int(total) * int(C.tdoa_num_pairs(m))
+	if n == 0 || k < 1 {
+		return nil, nil, nil, fmt.Errorf("tdoa_group_process_stacked: no stack-pairs or k < 1")
+	}
+	peaks, count, fine := make([]C.tdoa_peak, n*k), make([]C.int32_t, n), make([]C.tdoa_fine_peak, n)
+	if rc := C.tdoa_group_process_stacked(g.g, C.int(windowsPerStack), C.int(k), C.int(minSeparation), C.double(gate),
+		&peaks[0], &count[0], &fine[0], nil); rc != C.TDOA_OK {
+		return nil, nil, nil, fmt.Errorf("tdoa_group_process_stacked: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return peaks, count, fine, nil
 }

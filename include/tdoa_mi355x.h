@@ -260,6 +260,42 @@ int tdoa_process_peaks(tdoa_ctx *ctx, int rank, int world, int k, int min_separa
 int tdoa_fm_xcorr_peaks_u8(tdoa_ctx *ctx, const uint8_t *iq1, size_t n1, const uint8_t *iq2, size_t n2, int max_lag,
                            int k, int min_separation, tdoa_peak *peaks, int32_t *count);
 
+/* Stacked correlation: the surfaces of a run of windows of one block added lag by lag -- one peak set per (stack, pair)
+ * instead of one per pair-window.  The stations' clocks do not move within a block, so the windows' lags line up and the
+ * sum keeps its maximum at the true delay where a single window's argmax is already lost in noise (coherent processing
+ * gain, processor.go:770-782), on the plan of the short window.
+ *
+ * A stack is a run of windows_per_stack consecutive windows of ONE block (0: the whole block; the last stack of a block
+ * may be shorter; stacks never cross a block boundary, block 1 being another frequency).  With m = windows_per_stack,
+ * stacks_per_block = ceil(windows_per_block / m), and stack j of block b has the id sid = b * stacks_per_block + j.
+ * For stack sid, pair p, lag l, with c_w[l] the value tdoa_process_lags returns for window w as a double before its
+ * rounding to float:
+ *     q_w[l] = llrint(c_w[l] * 2^32)                     (int64, round to nearest even)
+ *     Q[l]   = sum of q_w[l] over the stack's windows     (int64, exact, any order)
+ *     C[l]   = (double)Q[l] * 2^-32 / sqrt(n_w)           n_w = windows in the stack
+ * C is on the reference's scale for a template of n_w * window_len samples, so stacks and single windows compare.  The
+ * fixed-point sum is associative: the result does not depend on the launch grouping or on which rank owned which window,
+ * and a group's result is byte-identical to one context's.  |c| <= sqrt(window_len) <= 2^13 and a few thousand windows
+ * stay far inside int64; the quantum is 2.3e-10.  Captures are bytes, so every c_w is finite; a non-finite term is not
+ * defined behaviour of this call.
+ *
+ * peaks_host [n_stacks_total][n_pairs][k]: the selection rule of tdoa_process_peaks applied to (float)C (1 <= k <= 16,
+ * min_separation >= 1; peak 1 = the argmax of |C|, ties to the smaller |lag|, then the positive lag).  corr of a record is
+ * the double C[l], abs_corr its float magnitude.  count_host [n_stacks_total][n_pairs]: the records written.
+ * fine_host [n_stacks_total][n_pairs]: peak 1 refined by the parabola and gate of tdoa_process_fine on C[d-1], C[d],
+ * C[d+1] in double (a neighbour outside the searched range is reported as 0 and leaves frac at 0).
+ * surface_host [n_stacks_total][n_pairs][2*max_lag-1]: (float)C.  partial_host, same shape: Q as the rank summed it.
+ * Any of the five may be NULL, not all.
+ * world > 1: a rank sums the windows (pair-major deal: the pair-windows) it owns; partial_host is then its share of Q --
+ * zero where it owns nothing -- and the only output that means anything alone: the sum of the ranks' partials is the Q of
+ * world = 1, word for word.  The other outputs of a rank are computed from its own partial, with n_w of the whole stack.
+ * Runs inside the step graph.  TDOA_LAGS_GO: TDOA_ERR_UNSUPPORTED.  k, min_separation, a negative windows_per_stack or
+ * gate_samples < 0: TDOA_ERR_INVALID. */
+int tdoa_num_stacks(const tdoa_ctx *ctx, int windows_per_stack, int *stacks_per_block, int *n_stacks_total);
+int tdoa_process_stacked(tdoa_ctx *ctx, int rank, int world, int windows_per_stack, int k, int min_separation,
+                         double gate_samples, tdoa_peak *peaks_host, int32_t *count_host, tdoa_fine_peak *fine_host,
+                         float *surface_host, int64_t *partial_host);
+
 /* Capture-quality statistics of every (window, station) in one streaming pass over the bytes
  * in HBM: the byte statistics of fastAnalyzeSamples
  * (fast_analyzer.go:117-155) and the block power of validateDataFile (collector.go:219-224).
@@ -429,6 +465,13 @@ int tdoa_group_capture_upload_files(tdoa_group *g, int n_stations, const char *c
  * written only if every member succeeded; otherwise the first failing member's status is returned and
  * tdoa_group_last_error names it.  With one member, its tdoa_process writes out_host directly. */
 int tdoa_group_process(tdoa_group *g, tdoa_peak *out_host);
+
+/* tdoa_process_stacked over the members (layouts as there; any output may be NULL, not all): every member sums the windows
+ * of its rank, the host adds the members' int64 partial sums, and member 0 finishes the sum with the kernels a single
+ * context's call ends with -- the outputs are byte-identical to tdoa_process_stacked(single ctx, 0, 1, ...).  Errors as
+ * tdoa_group_process.  With one member, its call writes the outputs directly. */
+int tdoa_group_process_stacked(tdoa_group *g, int windows_per_stack, int k, int min_separation, double gate_samples,
+                               tdoa_peak *peaks_host, int32_t *count_host, tdoa_fine_peak *fine_host, float *surface_host);
 
 /* the sample runs member `rank` of `world` uploads for a capture of total_samples (window grid from n_min, the shortest
  * capture of the job; block offsets from the capture's own thirds): adjacent owned windows form one run, and with fewer

@@ -1,0 +1,64 @@
+#!/usr/bin/env python3
+"""ms per call of tdoa_process, tdoa_process_peaks(k = 1, min_separation = 1) and tdoa_process_stacked(0, 1, 1) on the window
+geometry of BASELINE config 2 (synthetic captures on the device, one GPU), in one run.  The three are timed in alternation,
+`--rounds` rounds of `--steps` calls each, so that the spread between rounds of the same call stands next to the
+differences between the calls: median, and the lowest and highest round.  The graphs replay; host copies are included,
+as a caller sees them.   usage: scripts/time_stacked.py [--steps N] [--rounds R]"""
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tdoa-geolocation_amd"))
+try:
+    import torch          # noqa: F401  before the library: the process keeps torch's HIP runtime (bench.py does the same)
+except Exception:         # pragma: no cover
+    torch = None
+import numpy as np
+import tdoa_amd
+
+ST = [(41.18660274289527, -95.96064116595667, 355.69), (41.24669616513154, -96.08366304481238, 329.0),
+      (41.32916620016985, -96.03513381562004, 373.18)]
+TX = (41.20, -96.00, 400.0)
+
+
+def timed(fn, steps):
+    fn()                  # the call's own graph is captured again after another call's: not part of the timed window
+    fn()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    return (time.perf_counter() - t0) / steps * 1e3
+
+
+def main(steps, rounds):
+    c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=20000)
+    for s in range(3):
+        c.synth_capture(s, 66_666_666, ST[s], TX, 0x5D0A0000 + s)
+    _, W = c.num_windows()
+    P = c.num_pairs()
+    _, n_stacks = c.num_stacks(0)
+    legs = {"process_ms": lambda: c.process(), "process_peaks_k1_ms": lambda: c.process_peaks(1, 1),
+            "process_stacked_ms": lambda: c.process_stacked(0, 1, 1)}
+    times = {name: [] for name in legs}
+    for _ in range(rounds):
+        for name, fn in legs.items():
+            times[name].append(timed(fn, steps))
+    out = {"config": "cfg2", "stations": 3, "pairs": P, "windows": W, "stacks": n_stacks, "steps": steps, "rounds": rounds,
+           "surface_MB": round(W * P * (2 * 20000 - 1) * 4 / 1e6, 1)}
+    for name, t in times.items():
+        out[name] = {"median": round(float(np.median(t)), 3), "min": round(min(t), 3), "max": round(max(t), 3)}
+    print(json.dumps(out), flush=True)
+    c.close()
+
+
+if __name__ == "__main__":
+    args = sys.argv[1:]
+    opt = {"--steps": 20, "--rounds": 5}
+    for name in opt:
+        if name in args:
+            i = args.index(name)
+            opt[name] = int(args[i + 1])
+            del args[i:i + 2]
+    main(opt["--steps"], opt["--rounds"])

@@ -1,5 +1,6 @@
 // group_api.inc -- the multi-device group (include/tdoa_mi355x.h, "multi-device group"): one tdoa_ctx per member, member k
-// is rank k of n_members, and one call shards tdoa_process over them and merges their peak records on the host.
+// is rank k of n_members, and one call shards tdoa_process over them and merges their peak records on the host
+// (tdoa_process_stacked: adds their fixed-point partial sums and finishes the sum on member 0).
 // Included at the end of tdoa_mi355x.hip; uses its helpers (fail, check_ctx, unit_owner, capture_upload_file_runs).
 //
 // Threads.  tdoa_group_capture_upload_files and tdoa_group_process run member 0 on the caller's thread and members 1..n-1
@@ -25,6 +26,7 @@
 struct tdoa_group {
     std::vector<tdoa_ctx *> members;
     std::vector<std::vector<tdoa_peak>> out;  // member k's tdoa_process(k, n) records, kept from call to call
+    std::vector<std::vector<int64_t>> partial;   // member k's tdoa_process_stacked(k, n) sums, likewise
     std::string last_error;
 };
 
@@ -240,6 +242,55 @@ int tdoa_group_process(tdoa_group *g, tdoa_peak *out_host)
             out_host[u] = g->out[unit_owner(wid, p, W, P, world)][u];
         }
     return TDOA_OK;
+}
+
+// tdoa_process_stacked over the members: each returns only its share of the fixed-point sums; the host adds them (integer
+// addition: any order gives the same words) and member 0 finishes the sum with the kernels a single context's call ends with.
+int tdoa_group_process_stacked(tdoa_group *g, int windows_per_stack, int k, int min_separation, double gate_samples,
+                               tdoa_peak *peaks_host, int32_t *count_host, tdoa_fine_peak *fine_host, float *surface_host)
+{
+    if (!g) return TDOA_ERR_INVALID;
+    if (const char *bad = check_stacked_args(windows_per_stack, k, min_separation, gate_samples,
+                                             peaks_host || count_host || fine_host || surface_host))
+        return group_fail(g, TDOA_ERR_INVALID, bad);
+    const int world = (int)g->members.size();
+    tdoa_ctx *c0 = g->members[0];
+    if (world == 1) {                        // no merge: the member's call writes the outputs
+        const int rc = tdoa_process_stacked(c0, 0, 1, windows_per_stack, k, min_separation, gate_samples, peaks_host, count_host,
+                                            fine_host, surface_host, nullptr);
+        return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
+    }
+    if (c0->prm.lag_mode == TDOA_LAGS_GO) return group_fail(g, TDOA_ERR_UNSUPPORTED, "stacked correlation with TDOA_LAGS_GO");
+    for (int m = 1; m < world; m++) {        // (as tdoa_group_process: every member must cut the same windows)
+        const auto &a = c0->caps, &b = g->members[m]->caps;
+        bool same = a.size() == b.size();
+        for (size_t s = 0; same && s < a.size(); s++) same = a[s].n == b[s].n;
+        if (!same)
+            return group_fail(g, TDOA_ERR_STATE, member_name(m, g->members[m]->device) +
+                                                     "station count or capture lengths differ from member 0's");
+    }
+    int n_stacks = 0;
+    if (tdoa_num_stacks(c0, windows_per_stack, nullptr, &n_stacks) != TDOA_OK)
+        return group_fail(g, TDOA_ERR_STATE, member_name(0, c0->device) + "captures missing or too small");
+    const size_t n_q = (size_t)n_stacks * tdoa_num_pairs(c0) * (size_t)(2 * c0->prm.max_lag - 1);
+    g->partial.resize(world);
+    for (auto &q : g->partial) q.resize(n_q);
+    std::vector<int> status(world, TDOA_OK);
+    const bool ran = run_members(world, [&](int m) {
+        status[m] = tdoa_process_stacked(g->members[m], m, world, windows_per_stack, k, min_separation, gate_samples, nullptr,
+                                         nullptr, nullptr, nullptr, g->partial[m].data());
+    });
+    if (!ran) return group_fail(g, TDOA_ERR_NOMEM, "could not start a member thread");
+    for (int m = 0; m < world; m++)
+        if (status[m] != TDOA_OK) return member_fail(g, m, status[m]);
+    std::vector<int64_t> &sum = g->partial[0];
+    for (int m = 1; m < world; m++) {
+        const int64_t *q = g->partial[m].data();
+        for (size_t i = 0; i < n_q; i++) sum[i] += q[i];
+    }
+    const int rc = stack_finish_from_host(c0, sum.data(), windows_per_stack, k, min_separation, gate_samples, peaks_host,
+                                          count_host, fine_host, surface_host);
+    return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
 }
 
 int tdoa_debug_owned_runs(size_t total_samples, size_t n_min, int64_t window_len, int rank, int world, size_t *first,

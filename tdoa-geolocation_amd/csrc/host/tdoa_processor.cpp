@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -108,7 +108,8 @@ double median(std::vector<double> v)
 
 int main(int argc, char **argv)
 {
-    bool fm = false, fine = false;
+    bool fm = false, fine = false, stack = false;
+    int stack_m = 0;         // --stack=WINDOWS: windows per stack (0, or plain --stack: a whole block)
     double gate = 120.0;     // samples; PROJECT_NOTES.md:29-32 (max |TDOA| about 57 us = 114 samples at 2 Msps)
     tdoa_params prm;
     tdoa_default_params(&prm);
@@ -117,6 +118,8 @@ int main(int argc, char **argv)
         std::string a = argv[i];
         if (a == "--fm") fm = true;
         else if (a == "--fine") fm = fine = true;              // sub-sample refinement + plausibility gate (implies --fm)
+        else if (a == "--stack") fm = stack = true;            // one delay per block and pair from the summed surfaces (implies --fm)
+        else if (a.rfind("--stack=", 0) == 0) { fm = stack = true; stack_m = std::atoi(a.c_str() + 8); }
         else if (a == "--gate" && i + 1 < argc) gate = std::atof(argv[++i]);
         else if (a == "--device" && i + 1 < argc) prm.device = std::atoi(argv[++i]);
         else if (a == "--window" && i + 1 < argc) prm.window_len = std::atoll(argv[++i]);
@@ -277,6 +280,19 @@ int main(int argc, char **argv)
             fines.resize((size_t)W * P);
             if ((rc = tdoa_process_fine(ctx, 0, 1, gate, peaks.data(), fines.data()))) return die("tdoa_process_fine", rc);
         } else if ((rc = tdoa_process(ctx, 0, 1, peaks.data(), nullptr))) return die("tdoa_process", rc);
+        // --stack: the windows' surfaces of a block added lag by lag (tdoa_process_stacked), two peaks per stack-pair
+        int spb = 0, n_stacks = 0;
+        std::vector<tdoa_peak> spk;
+        std::vector<int32_t> scnt;
+        std::vector<tdoa_fine_peak> sfine;
+        if (stack) {
+            if ((rc = tdoa_num_stacks(ctx, stack_m, &spb, &n_stacks))) return die("tdoa_num_stacks", rc);
+            spk.resize((size_t)n_stacks * P * 2);
+            scnt.resize((size_t)n_stacks * P);
+            sfine.resize((size_t)n_stacks * P);
+            if ((rc = tdoa_process_stacked(ctx, 0, 1, stack_m, 2, 1, gate, spk.data(), scnt.data(), sfine.data(), nullptr, nullptr)))
+                return die("tdoa_process_stacked", rc);
+        }
         std::printf("\n=== FM-DISCRIMINATOR CROSS-CORRELATION: %d windows x %d pairs ===\n", W, P);
         int p = 0;
         for (int i = 0; i < S; i++)
@@ -306,6 +322,23 @@ int main(int argc, char **argv)
                     if (ok.empty()) ct.clear();                    // no plausible window: the pair gets weight 0 in the N-station solve
                     std::printf("TGT %s - %s: refined delay=%.3f samples, %zu of %zu windows within +-%.1f samples\n",
                                 caps[i].st.name.c_str(), caps[j].st.name.c_str(), lag_used, ok.size(), all.size(), gate);
+                }
+                if (stack) {
+                    // one line per stack; the target block's refined stacked delays replace the per-window choice
+                    const int m = stack_m > 0 && stack_m < wpb ? stack_m : wpb;
+                    std::vector<double> sd, sc;
+                    for (int sid = 0; sid < n_stacks; sid++) {
+                        const size_t u = (size_t)sid * P + p;
+                        const tdoa_peak &p1 = spk[2 * u], &p2 = spk[2 * u + 1];
+                        const int sj = sid % spb, n_w = std::min(m, wpb - sj * m);
+                        std::printf("STACK block %d stack %d %s - %s: windows=%d delay=%d samples refined=%.3f |C|=%.6f ratio=%.3f\n",
+                                    sid / spb + 1, sj, caps[i].st.name.c_str(), caps[j].st.name.c_str(), n_w, p1.lag,
+                                    sfine[u].delay, (double)p1.abs_corr,
+                                    scnt[u] > 1 ? (double)p1.abs_corr / (double)p2.abs_corr : INFINITY);
+                        if (sid / spb == 1) { sd.push_back(sfine[u].delay); sc.push_back(p1.abs_corr); }
+                    }
+                    lag_used = median(sd);
+                    ct = sc;
                 }
                 tgt_dt.push_back(lag_used / prm.sample_rate);
                 tgt_w.push_back(median(ct));

@@ -34,6 +34,7 @@
 #include "host_upload.hpp"
 #include "segment_quads.hpp"
 #include "peak_select.hpp"
+#include "stack_surfaces.hpp"
 
 using namespace tdoa;
 
@@ -198,6 +199,9 @@ struct tdoa_ctx {
     // tdoa_process_lags / _peaks: the K5 kernels' lag arrays [owned pair-window][2 max_lag - 1], the surfaces in the caller's
     // layout [slot][2 max_lag - 1], the selected peaks [slot][k] and their counts [slot]
     DevBuf surf, surf_out, sel_peaks, sel_count;
+    // tdoa_process_stacked: the fixed-point sums Q [stack][pair][2 max_lag - 1], the float stack surfaces of the same shape,
+    // the stack-pairs' keys, their refined peak 1, and the descriptors (sqrt(n_w) per stack, unit scales, runs, list)
+    DevBuf stack_q, stack_surf, stack_keys, stack_fine, stack_desc;
 };
 
 namespace {
@@ -1710,7 +1714,7 @@ int batch_bound(tdoa_ctx *ctx, const FftPlan &pl, int lag_lo, int lag_hi, const 
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
         // (the surface outputs' buffers too: whether an earlier call allocated them must not change the grouping)
         const double held = (double)ctx->tz.cap + (double)ctx->v.cap + (double)ctx->codes.cap + (double)ctx->codes_lp.cap +
-                            (double)ctx->surf.cap + (double)ctx->surf_out.cap;
+                            (double)ctx->surf.cap + (double)ctx->surf_out.cap + (double)ctx->stack_q.cap + (double)ctx->stack_surf.cap;
         limit = std::min(limit, std::max(0.0, (double)free_b + held - 1073741824.0));      // 1 GiB stays free: descriptors, edges, the runtime
     } else {
         (void)hipGetLastError();
@@ -1721,7 +1725,8 @@ int batch_bound(tdoa_ctx *ctx, const FftPlan &pl, int lag_lo, int lag_hi, const 
 
 // Everything a step's launches depend on: same key => the captured graph can be replayed as is
 std::vector<uint64_t> step_graph_key(const tdoa_ctx *ctx, int rank, int world, int per_batch, long long wlen, long long block,
-                                     bool go, bool fine, double gate, int surf_mode = 0, int sel_k = 0, int sel_sep = 0)
+                                     bool go, bool fine, double gate, int surf_mode = 0, int sel_k = 0, int sel_sep = 0, int stack_m = 0,
+                                     bool stack_finish = false)
 {
     std::vector<uint64_t> key = {(uint64_t)ctx->caps.size(), (uint64_t)rank, (uint64_t)world, (uint64_t)per_batch, (uint64_t)wlen,
                                  (uint64_t)ctx->prm.max_lag | ((uint64_t)ctx->prm.k1_smooth << 32) | ((uint64_t)(ctx->prm.k1_gate != 0) << 62) |
@@ -1737,6 +1742,7 @@ std::vector<uint64_t> step_graph_key(const tdoa_ctx *ctx, int rank, int world, i
     key.push_back((uint64_t)surf_mode);
     key.push_back((uint64_t)sel_k);
     key.push_back((uint64_t)sel_sep);
+    key.push_back((uint64_t)stack_m | ((uint64_t)stack_finish << 32));
     return key;
 }
 
@@ -1986,7 +1992,8 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->ex_a, &ctx->ex_b, &ctx->ex_c, &ctx->ex_d, &ctx->ex_part,
                       &ctx->g_sw_desc, &ctx->g_pw_desc, &ctx->g_quad_desc, &ctx->g_scales, &ctx->g_keys, &ctx->fine_raw, &ctx->fine, &ctx->qual,
                       &ctx->once_edges, &ctx->once_tiles, &ctx->once_fin, &ctx->slot_gain, &ctx->surf, &ctx->surf_out,
-                      &ctx->sel_peaks, &ctx->sel_count};
+                      &ctx->sel_peaks, &ctx->sel_count, &ctx->stack_q, &ctx->stack_surf, &ctx->stack_keys, &ctx->stack_fine,
+                      &ctx->stack_desc};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -2281,8 +2288,141 @@ struct SurfaceOut {
     void *lags_dev = nullptr;
     tdoa_peak *peaks_host = nullptr;
     int32_t *count_host = nullptr;
+    // kSurfStack (tdoa_process_stacked): peaks_host / count_host are per stack-pair
+    int stack_m = 0;                         // windows per stack, 0: the whole block
+    tdoa_fine_peak *stack_fine_host = nullptr;
+    float *stack_surface_host = nullptr;
+    int64_t *partial_host = nullptr;
+    bool stack_finish() const { return peaks_host || count_host || stack_fine_host || stack_surface_host; }
 };
-constexpr int kSurfLags = 1, kSurfPeaks = 2;
+constexpr int kSurfLags = 1, kSurfPeaks = 2, kSurfStack = 3;
+
+// The stacks of a job (include/tdoa_mi355x.h, "stacked correlation") and which of a rank's pair-windows each (stack, pair)
+// sums -- plain numbers, like StepLayout.  The device copy (ctx->stack_desc) is roots, ones, desc, list in this order.
+struct StackLayout {
+    int spb = 0, n_stacks = 0;               // stacks per block, stacks of the three blocks
+    std::vector<double> roots;               // [n_stacks]: sqrt(n_w)
+    std::vector<StackDesc> desc;             // [n_stacks * P]
+    std::vector<int32_t> list;               // the rank's pair-window numbers (indices into StepLayout::pw), by stack-pair
+};
+
+static void stack_geometry(int wpb, int m, int *spb, int *n_stacks)
+{
+    const int mm = m > 0 ? std::min(m, wpb) : wpb;
+    *spb = (wpb + mm - 1) / mm;
+    *n_stacks = 3 * *spb;
+}
+
+static StackLayout build_stack_layout(const std::vector<PWDesc> &pw, int wpb, int P, int m)
+{
+    StackLayout L;
+    stack_geometry(wpb, m, &L.spb, &L.n_stacks);
+    const int mm = m > 0 ? std::min(m, wpb) : wpb;
+    for (int sid = 0; sid < L.n_stacks; sid++)
+        L.roots.push_back(std::sqrt((double)std::min(mm, wpb - (sid % L.spb) * mm)));
+    auto stack_pair = [&](const PWDesc &d) {
+        const int wid = d.out_index / P, p = d.out_index % P;
+        return ((wid / wpb) * L.spb + (wid % wpb) / mm) * P + p;
+    };
+    L.desc.assign((size_t)L.n_stacks * P, StackDesc{0, 0});
+    for (const PWDesc &d : pw) L.desc[stack_pair(d)].count++;
+    int32_t at = 0;
+    for (StackDesc &d : L.desc) {
+        d.first = at;
+        at += d.count;
+        d.count = 0;
+    }
+    L.list.resize(pw.size());
+    for (size_t i = 0; i < pw.size(); i++) {
+        StackDesc &d = L.desc[stack_pair(pw[i])];
+        L.list[d.first + d.count++] = (int32_t)i;
+    }
+    return L;
+}
+
+// the device views of ctx->stack_desc for n_stacks stacks of P pairs
+struct StackDev {
+    const double *roots, *ones;
+    const StackDesc *desc;
+    const int32_t *list;
+};
+static size_t stack_desc_bytes(size_t n_stacks, size_t P, size_t n_owned)
+{
+    return sizeof(double) * (n_stacks + n_stacks * P) + sizeof(StackDesc) * n_stacks * P + sizeof(int32_t) * std::max<size_t>(n_owned, 1);
+}
+static StackDev stack_dev(const tdoa_ctx *ctx, size_t n_stacks, size_t P)
+{
+    StackDev d;
+    d.roots = static_cast<const double *>(ctx->stack_desc.p);
+    d.ones = d.roots + n_stacks;
+    d.desc = reinterpret_cast<const StackDesc *>(d.ones + n_stacks * P);
+    d.list = reinterpret_cast<const int32_t *>(d.desc + n_stacks * P);
+    return d;
+}
+
+// roots and unit scales, and with `runs` the stack-pairs' runs and the list, to ctx->stack_desc; the caller synchronises
+// before the host vectors go.  (without `runs` the part a cached step graph's k_stack_accumulate reads stays as it is)
+static int upload_stack_desc(tdoa_ctx *ctx, const StackLayout &sl, int P, std::vector<double> *ones, bool runs)
+{
+    const size_t n_sp = (size_t)sl.n_stacks * P;
+    const StackDev d = stack_dev(ctx, sl.n_stacks, P);
+    ones->assign(n_sp, 1.0);
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(const_cast<double *>(d.roots), sl.roots.data(), sizeof(double) * sl.n_stacks, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(const_cast<double *>(d.ones), ones->data(), sizeof(double) * n_sp, hipMemcpyHostToDevice, st));
+    if (runs && !sl.desc.empty())
+        HIPCHK(ctx, hipMemcpyAsync(const_cast<StackDesc *>(d.desc), sl.desc.data(), sizeof(StackDesc) * n_sp, hipMemcpyHostToDevice, st));
+    if (runs && !sl.list.empty())
+        HIPCHK(ctx, hipMemcpyAsync(const_cast<int32_t *>(d.list), sl.list.data(), sizeof(int32_t) * sl.list.size(), hipMemcpyHostToDevice, st));
+    return TDOA_OK;
+}
+
+// the buffers of the finishing kernels for n_sp stack-pairs of n_lags lags
+static int ensure_stack_finish(tdoa_ctx *ctx, size_t n_sp, int n_lags, int k)
+{
+    int rc;
+    if ((rc = ensure(ctx, ctx->stack_surf, sizeof(float) * n_sp * n_lags))) return rc;
+    if ((rc = ensure(ctx, ctx->stack_keys, sizeof(unsigned long long) * n_sp))) return rc;
+    if ((rc = ensure(ctx, ctx->stack_fine, sizeof(FineOut) * n_sp))) return rc;
+    if ((rc = ensure(ctx, ctx->sel_peaks, sizeof(PeakOut) * n_sp * k))) return rc;
+    return ensure(ctx, ctx->sel_count, sizeof(int32_t) * (n_sp + 1));
+}
+
+// Q (ctx->stack_q) -> float surfaces, k peaks and the refined peak 1 of every stack-pair: the one place the scale, the
+// selection and the refinement of a stack are computed, for a context's own sum and for a group's merged one alike.
+// Kernel launches only (the step graph captures them).
+static void launch_stack_finish(tdoa_ctx *ctx, int n_stacks, int P, int n_lags, int lag_lo, int k, int min_sep, double gate)
+{
+    hipStream_t st = ctx->stream;
+    const unsigned n_sp = (unsigned)(n_stacks * P);
+    const StackDev d = stack_dev(ctx, n_stacks, P);
+    auto *Q = static_cast<const long long *>(ctx->stack_q.p);
+    auto *keys = static_cast<unsigned long long *>(ctx->stack_keys.p);
+    auto *surf = static_cast<float *>(ctx->stack_surf.p);
+    auto *peaks = static_cast<PeakOut *>(ctx->sel_peaks.p);
+    auto *count = static_cast<int32_t *>(ctx->sel_count.p);
+    const dim3 grid(n_sp, (unsigned)((n_lags + kStackTile - 1) / kStackTile));
+    hipLaunchKernelGGL(k_zero_u64, dim3((n_sp + 255) / 256), dim3(256), 0, st, keys, (size_t)n_sp);
+    hipLaunchKernelGGL(k_stack_finish, grid, dim3(kStackThreads), 0, st, Q, n_lags, lag_lo, P, d.roots, surf, keys);
+    hipLaunchKernelGGL(k_select_peaks, dim3(n_sp), dim3(kSelThreads), 0, st, static_cast<const float *>(surf), (size_t)n_lags, n_lags,
+                       lag_lo, static_cast<const PWDesc *>(nullptr), static_cast<const unsigned long long *>(keys), d.ones,
+                       static_cast<const double *>(nullptr), k, min_sep, peaks, count);
+    hipLaunchKernelGGL(k_stack_fine, dim3((n_sp + 63) / 64), dim3(64), 0, st, Q, n_lags, lag_lo, P, (int)n_sp, d.roots,
+                       static_cast<const unsigned long long *>(keys), k, peaks, static_cast<const int32_t *>(count),
+                       static_cast<FineOut *>(ctx->stack_fine.p), gate);
+}
+
+// the outputs of a finished stack to the host (any pointer may be NULL); asynchronous on ctx->stream
+static int download_stack(tdoa_ctx *ctx, size_t n_sp, int n_lags, int k, tdoa_peak *peaks, int32_t *count, tdoa_fine_peak *fine,
+                          float *surface)
+{
+    hipStream_t st = ctx->stream;
+    if (peaks) HIPCHK(ctx, hipMemcpyAsync(peaks, ctx->sel_peaks.p, sizeof(PeakOut) * n_sp * k, hipMemcpyDeviceToHost, st));
+    if (count) HIPCHK(ctx, hipMemcpyAsync(count, ctx->sel_count.p, sizeof(int32_t) * n_sp, hipMemcpyDeviceToHost, st));
+    if (fine) HIPCHK(ctx, hipMemcpyAsync(fine, ctx->stack_fine.p, sizeof(FineOut) * n_sp, hipMemcpyDeviceToHost, st));
+    if (surface) HIPCHK(ctx, hipMemcpyAsync(surface, ctx->stack_surf.p, sizeof(float) * n_sp * n_lags, hipMemcpyDeviceToHost, st));
+    return TDOA_OK;
+}
 
 static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host, void *out_dev,
                         tdoa_fine_peak *fine_host, double gate, const SurfaceOut &so = SurfaceOut{})
@@ -2365,6 +2505,7 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
     // groups as this one did)
     const int n_lags = lag_hi - lag_lo + 1;
     const size_t n_owned = lay.pw.size(), surf_n = (size_t)n_lags * slots;
+    StackLayout stk;
     if (so.mode) {
         auto nomem = [&](const char *what) {
             char buf[256];
@@ -2378,6 +2519,14 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
         if (so.mode == kSurfPeaks && (ensure(ctx, ctx->sel_peaks, sizeof(PeakOut) * slots * so.k) ||
                                       ensure(ctx, ctx->sel_count, sizeof(int32_t) * (slots + 1))))
             return nomem("selected peaks");
+        if (so.mode == kSurfStack) {
+            stk = build_stack_layout(lay.pw, wpb, P, so.stack_m);
+            const size_t n_sp = (size_t)stk.n_stacks * P;
+            if (ensure(ctx, ctx->stack_q, sizeof(long long) * n_sp * n_lags) ||
+                ensure(ctx, ctx->stack_desc, stack_desc_bytes(stk.n_stacks, P, n_owned)) ||
+                (so.stack_finish() && ensure_stack_finish(ctx, n_sp, n_lags, so.k)))
+                return nomem("correlation surfaces and their stacked sums");
+        }
     }
     auto *d_sw = static_cast<SWDesc *>(ctx->g_sw_desc.p);
     auto *d_pw = static_cast<PWDesc *>(ctx->g_pw_desc.p);
@@ -2386,8 +2535,10 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
     auto *d_scales = static_cast<double *>(ctx->g_scales.p);
 
     const std::vector<uint64_t> key = step_graph_key(ctx, rank, world, per_batch, wlen, block, go, fine_host != nullptr, gate,
-                                                     so.mode, so.k, so.min_sep);
+                                                     so.mode, so.k, so.min_sep, so.stack_m, so.mode == kSurfStack && so.stack_finish());
     if (!step_graph_replays(ctx, key)) {
+        std::vector<double> ones;
+        if (so.mode == kSurfStack && (rc = upload_stack_desc(ctx, stk, P, &ones, true))) return rc;
         std::vector<double> scales(slots, 1.0 / (4.0 * (double)n * std::sqrt((double)corr_len)));
         HIPCHK(ctx, hipMemcpyAsync(d_scales, scales.data(), sizeof(double) * slots, hipMemcpyHostToDevice, st));
         if (!sw.empty()) {
@@ -2446,6 +2597,12 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
                 hipLaunchKernelGGL(k_select_peaks, dim3((unsigned)n_owned), dim3(kSelThreads), 0, st, surf, (size_t)n_lags, n_lags,
                                    lag_lo, d_pw, d_keys, d_scales, slot_gain, so.k, so.min_sep,
                                    static_cast<PeakOut *>(ctx->sel_peaks.p), static_cast<int32_t *>(ctx->sel_count.p));
+        } else if (so.mode == kSurfStack) {
+            const StackDev sd = stack_dev(ctx, stk.n_stacks, P);
+            hipLaunchKernelGGL(k_stack_accumulate, dim3((unsigned)(stk.n_stacks * P), (unsigned)((n_lags + kStackTile - 1) / kStackTile)),
+                               dim3(kStackThreads), 0, st, surf, (size_t)n_lags, n_lags, d_pw, sd.desc, sd.list, d_scales, slot_gain,
+                               static_cast<long long *>(ctx->stack_q.p));
+            if (so.stack_finish()) launch_stack_finish(ctx, stk.n_stacks, P, n_lags, lag_lo, so.k, so.min_sep, gate);
         }
         return TDOA_OK;
     };
@@ -2461,10 +2618,18 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
         HIPCHK(ctx, hipMemcpyAsync(so.lags_dev, ctx->surf_out.p, sizeof(float) * surf_n, hipMemcpyDeviceToDevice, st));
     if (so.lags_host)
         HIPCHK(ctx, hipMemcpyAsync(so.lags_host, ctx->surf_out.p, sizeof(float) * surf_n, hipMemcpyDeviceToHost, st));
-    if (so.peaks_host)
-        HIPCHK(ctx, hipMemcpyAsync(so.peaks_host, ctx->sel_peaks.p, sizeof(PeakOut) * slots * so.k, hipMemcpyDeviceToHost, st));
-    if (so.count_host)
-        HIPCHK(ctx, hipMemcpyAsync(so.count_host, ctx->sel_count.p, sizeof(int32_t) * slots, hipMemcpyDeviceToHost, st));
+    if (so.mode == kSurfStack) {
+        const size_t n_sp = (size_t)stk.n_stacks * P;
+        if ((rc = download_stack(ctx, n_sp, n_lags, so.k, so.peaks_host, so.count_host, so.stack_fine_host, so.stack_surface_host)))
+            return rc;
+        if (so.partial_host)
+            HIPCHK(ctx, hipMemcpyAsync(so.partial_host, ctx->stack_q.p, sizeof(int64_t) * n_sp * n_lags, hipMemcpyDeviceToHost, st));
+    } else {
+        if (so.peaks_host)
+            HIPCHK(ctx, hipMemcpyAsync(so.peaks_host, ctx->sel_peaks.p, sizeof(PeakOut) * slots * so.k, hipMemcpyDeviceToHost, st));
+        if (so.count_host)
+            HIPCHK(ctx, hipMemcpyAsync(so.count_host, ctx->sel_count.p, sizeof(int32_t) * slots, hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(ctx, hipStreamSynchronize(st));
     prof_collect(ctx);
     collect_step_graph_marks(ctx);
@@ -2524,6 +2689,75 @@ int tdoa_process_peaks(tdoa_ctx *ctx, int rank, int world, int k, int min_separa
     so.peaks_host = peaks_host;
     so.count_host = count_host;
     return process_impl(ctx, rank, world, nullptr, nullptr, nullptr, 0.0, so);
+}
+
+int tdoa_num_stacks(const tdoa_ctx *ctx, int windows_per_stack, int *stacks_per_block, int *n_stacks_total)
+{
+    if (!ctx || windows_per_stack < 0) return TDOA_ERR_INVALID;
+    int wpb = 0;
+    const int rc = tdoa_num_windows(ctx, &wpb, nullptr);
+    if (rc) return rc;
+    int spb, n;
+    stack_geometry(wpb, windows_per_stack, &spb, &n);
+    if (stacks_per_block) *stacks_per_block = spb;
+    if (n_stacks_total) *n_stacks_total = n;
+    return TDOA_OK;
+}
+
+// the arguments of tdoa_process_stacked / tdoa_group_process_stacked that need no device
+static const char *check_stacked_args(int windows_per_stack, int k, int min_separation, double gate_samples, bool any_output)
+{
+    if (windows_per_stack < 0) return "windows_per_stack < 0";
+    if (k < 1 || k > kSelMaxK || min_separation < 1) return "k outside 1..16 or min_separation < 1";
+    if (!(gate_samples >= 0.0)) return "gate < 0";
+    if (!any_output) return "every output is NULL";
+    return nullptr;
+}
+
+int tdoa_process_stacked(tdoa_ctx *ctx, int rank, int world, int windows_per_stack, int k, int min_separation,
+                         double gate_samples, tdoa_peak *peaks_host, int32_t *count_host, tdoa_fine_peak *fine_host,
+                         float *surface_host, int64_t *partial_host)
+{
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (const char *bad = check_stacked_args(windows_per_stack, k, min_separation, gate_samples,
+                                             peaks_host || count_host || fine_host || surface_host || partial_host))
+        return fail(ctx, TDOA_ERR_INVALID, bad);
+    if (ctx->prm.lag_mode == TDOA_LAGS_GO) return fail(ctx, TDOA_ERR_UNSUPPORTED, "stacked correlation with TDOA_LAGS_GO");
+    SurfaceOut so;
+    so.mode = kSurfStack;
+    so.k = k;
+    so.min_sep = min_separation;
+    so.stack_m = windows_per_stack;
+    so.peaks_host = peaks_host;
+    so.count_host = count_host;
+    so.stack_fine_host = fine_host;
+    so.stack_surface_host = surface_host;
+    so.partial_host = partial_host;
+    return process_impl(ctx, rank, world, nullptr, nullptr, nullptr, gate_samples, so);
+}
+
+// The group's finish on one context: the members' summed Q uploaded, then the kernels a context's own call ends with.
+// Not part of a step graph (the context's cached step stays valid unless a buffer had to grow).
+static int stack_finish_from_host(tdoa_ctx *ctx, const int64_t *q_sum, int windows_per_stack, int k, int min_separation,
+                                  double gate, tdoa_peak *peaks, int32_t *count, tdoa_fine_peak *fine, float *surface)
+{
+    int rc, wpb = 0;
+    if ((rc = check_ctx(ctx))) return rc;
+    if ((rc = tdoa_num_windows(ctx, &wpb, nullptr))) return fail(ctx, rc, "captures missing or too small");
+    const int P = tdoa_num_pairs(ctx), n_lags = 2 * ctx->prm.max_lag - 1, lag_lo = -(ctx->prm.max_lag - 1);
+    const StackLayout sl = build_stack_layout({}, wpb, P, windows_per_stack);
+    const size_t n_sp = (size_t)sl.n_stacks * P;
+    if ((rc = ensure(ctx, ctx->stack_q, sizeof(long long) * n_sp * n_lags))) return rc;
+    if ((rc = ensure(ctx, ctx->stack_desc, stack_desc_bytes(sl.n_stacks, P, 0)))) return rc;   // (a member's step made it larger)
+    if ((rc = ensure_stack_finish(ctx, n_sp, n_lags, k))) return rc;
+    std::vector<double> ones;
+    if ((rc = upload_stack_desc(ctx, sl, P, &ones, false))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->stack_q.p, q_sum, sizeof(int64_t) * n_sp * n_lags, hipMemcpyHostToDevice, ctx->stream));
+    launch_stack_finish(ctx, sl.n_stacks, P, n_lags, lag_lo, k, min_separation, gate);
+    HIPCHK(ctx, hipGetLastError());
+    if ((rc = download_stack(ctx, n_sp, n_lags, k, peaks, count, fine, surface))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return TDOA_OK;
 }
 
 int tdoa_fm_xcorr_peaks_u8(tdoa_ctx *ctx, const uint8_t *iq1, size_t n1, const uint8_t *iq2, size_t n2, int max_lag, int k,
@@ -2817,8 +3051,9 @@ int tdoa_debug_poison_workspace(tdoa_ctx *ctx)
 {
     if (!ctx) return TDOA_ERR_INVALID;
     // floats only: no kernel derives an index from a value in these buffers (peak lags come from the keys, which are not
-    // poisoned), so a NaN can end up in a result but never in an address
-    for (DevBuf *b : {&ctx->v, &ctx->tz, &ctx->fine_raw, &ctx->once_edges, &ctx->surf, &ctx->surf_out})
+    // poisoned), so a NaN can end up in a result but never in an address.  (stack_q holds integers: the pattern is a large
+    // number there, and every element is written before it is read like the floats)
+    for (DevBuf *b : {&ctx->v, &ctx->tz, &ctx->fine_raw, &ctx->once_edges, &ctx->surf, &ctx->surf_out, &ctx->stack_q, &ctx->stack_surf})
         if (b->p && b->cap >= 4) HIPCHK(ctx, hipMemsetD32Async(static_cast<hipDeviceptr_t>(b->p), 0x7FC00000, b->cap / 4, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return TDOA_OK;

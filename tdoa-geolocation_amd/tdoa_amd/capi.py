@@ -87,6 +87,7 @@ SYMBOLS = [
     "tdoa_plan_info", "tdoa_process_lags", "tdoa_process_peaks", "tdoa_fm_xcorr_peaks_u8", "tdoa_debug_select_peaks",
     "tdoa_group_create", "tdoa_group_destroy", "tdoa_group_last_error", "tdoa_group_member",
     "tdoa_group_capture_upload_files", "tdoa_group_process", "tdoa_debug_owned_runs",
+    "tdoa_num_stacks", "tdoa_process_stacked", "tdoa_group_process_stacked",
 ]
 
 _lib = None
@@ -186,6 +187,10 @@ def load(build_if_missing=True):
     L.tdoa_group_member.restype = vp
     L.tdoa_group_capture_upload_files.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(sz)]
     L.tdoa_group_process.argtypes = [vp, vp]
+    L.tdoa_num_stacks.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.tdoa_process_stacked.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, i32p, vp, fp,
+                                       C.POINTER(C.c_int64)]
+    L.tdoa_group_process_stacked.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, i32p, vp, fp]
     L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
                                         C.POINTER(C.c_int)]
     _lib = L
@@ -478,6 +483,27 @@ class Context:
                                              out.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.POINTER(C.c_int32))))
         return out, count
 
+    def num_stacks(self, windows_per_stack=0):
+        """tdoa_num_stacks -> (stacks_per_block, n_stacks_total)"""
+        a, b = C.c_int(), C.c_int()
+        self._chk(self._L.tdoa_num_stacks(self._h, int(windows_per_stack), C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def process_stacked(self, windows_per_stack=0, k=1, min_separation=1, gate=None, rank=0, world=1, want_surface=False,
+                        want_partial=False):
+        """tdoa_process_stacked -> dict: peaks [n_stacks][P][k] PEAK_DTYPE, count [n_stacks][P] int32, fine [n_stacks][P]
+        FINE_DTYPE (peak 1 refined; gate None: max_lag), and on request surface [n_stacks][P][2 max_lag - 1] float32 and
+        partial (same shape, int64: the rank's fixed-point sums Q).  With world > 1 only `partial` means anything alone."""
+        _, n = self.num_stacks(windows_per_stack)
+        out = _stacked_outputs(n, self.num_pairs(), 2 * self.params.max_lag - 1, k, want_surface, want_partial)
+        self._chk(self._L.tdoa_process_stacked(
+            self._h, int(rank), int(world), int(windows_per_stack), int(k), int(min_separation),
+            float(self.params.max_lag if gate is None else gate), out["peaks"].ctypes.data_as(C.c_void_p),
+            out["count"].ctypes.data_as(C.POINTER(C.c_int32)), out["fine"].ctypes.data_as(C.c_void_p),
+            _f(out["surface"]) if want_surface else None,
+            out["partial"].ctypes.data_as(C.POINTER(C.c_int64)) if want_partial else None))
+        return out
+
     def fm_xcorr_peaks(self, iq1, iq2, max_lag, k, min_separation):
         """tdoa_fm_xcorr_peaks_u8 -> (peaks [k] PEAK_DTYPE, count) of one pair of windows"""
         a = np.ascontiguousarray(iq1, dtype=np.uint8)
@@ -589,6 +615,16 @@ class Context:
         return n.value, n1.value, n2.value
 
 
+def _stacked_outputs(n_stacks, p, n_lags, k, want_surface, want_partial):
+    out = {"peaks": np.zeros((n_stacks, p, max(int(k), 1)), dtype=PEAK_DTYPE), "count": np.zeros((n_stacks, p), dtype=np.int32),
+           "fine": np.zeros((n_stacks, p), dtype=FINE_DTYPE)}
+    if want_surface:
+        out["surface"] = np.zeros((n_stacks, p, n_lags), dtype=np.float32)
+    if want_partial:
+        out["partial"] = np.zeros((n_stacks, p, n_lags), dtype=np.int64)
+    return out
+
+
 class _Member(Context):
     """A group member's tdoa_ctx, borrowed (tdoa_group_member): every Context call; close() leaves it to the group."""
 
@@ -667,6 +703,19 @@ class Group:
         elif out.dtype != PEAK_DTYPE or out.shape != (w, p) or not out.flags.c_contiguous:
             raise ValueError("out must be a C-contiguous (%d, %d) PEAK_DTYPE array" % (w, p))
         self._chk(self._L.tdoa_group_process(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def process_stacked(self, windows_per_stack=0, k=1, min_separation=1, gate=None, want_surface=False):
+        """tdoa_group_process_stacked -> the dict of Context.process_stacked (no partial), byte-identical to a single
+        context's"""
+        m = self.member(0)
+        _, n = m.num_stacks(windows_per_stack)
+        out = _stacked_outputs(n, m.num_pairs(), 2 * self.params.max_lag - 1, k, want_surface, False)
+        self._chk(self._L.tdoa_group_process_stacked(
+            self._h, int(windows_per_stack), int(k), int(min_separation),
+            float(self.params.max_lag if gate is None else gate), out["peaks"].ctypes.data_as(C.c_void_p),
+            out["count"].ctypes.data_as(C.POINTER(C.c_int32)), out["fine"].ctypes.data_as(C.c_void_p),
+            _f(out["surface"]) if want_surface else None))
         return out
 
 
