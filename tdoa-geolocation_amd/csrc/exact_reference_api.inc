@@ -88,11 +88,11 @@ int ex_prepare(tdoa_ctx *ctx, size_t n, ExWork *w)
     if ((rc = ensure(ctx, ctx->ex_d, bytes))) return rc;
     const size_t chunks = (n + kPowChunk - 1) / kPowChunk + 1;
     if ((rc = ensure(ctx, ctx->ex_part, sizeof(double) * (chunks + 8)))) return rc;
-    w->a = static_cast<float2 *>(ctx->ex_a.p);
-    w->b = static_cast<float2 *>(ctx->ex_b.p);
-    w->c = static_cast<float2 *>(ctx->ex_c.p);
-    w->d = static_cast<float2 *>(ctx->ex_d.p);
-    w->power = static_cast<double *>(ctx->ex_part.p);
+    w->a = ctx->ex_a.as<float2>();
+    w->b = ctx->ex_b.as<float2>();
+    w->c = ctx->ex_c.as<float2>();
+    w->d = ctx->ex_d.as<float2>();
+    w->power = ctx->ex_part.as<double>();
     w->mean = reinterpret_cast<float2 *>(w->power + 2);
     w->partials = w->power + 8;
     return TDOA_OK;
@@ -164,8 +164,8 @@ int ex_tdc(tdoa_ctx *ctx, const float2 *d1, size_t n1, const float2 *d2, size_t 
         return fail(ctx, TDOA_ERR_UNSUPPORTED, "correlation geometry unsupported");
     if ((rc = ensure(ctx, ctx->scratch_b, sizeof(double) * (size_t)nb * (size_t)ml))) return rc;
     if ((rc = ensure(ctx, ctx->lagdump, sizeof(double) * (size_t)ml + sizeof(ExPeak)))) return rc;
-    auto *bc = static_cast<double *>(ctx->scratch_b.p);
-    auto *cv = static_cast<double *>(ctx->lagdump.p);
+    auto *bc = ctx->scratch_b.as<double>();
+    auto *cv = ctx->lagdump.as<double>();
     auto *pk = reinterpret_cast<ExPeak *>(cv + ml);
     hipStream_t st = ctx->stream;
     if (ml >= 64) {
@@ -212,8 +212,8 @@ int tdoa_load_iq_u8(tdoa_ctx *ctx, const uint8_t *raw, size_t n, float *out_c64)
     if ((rc = ensure(ctx, ctx->tz, n * sizeof(float2)))) return rc;
     hipStream_t st = ctx->stream;
     HIPCHK(ctx, hipMemcpyAsync(ctx->scratch_a.p, raw, 2 * n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_ex_u8_to_c64, dim3(ex_grid(n)), dim3(256), 0, st, static_cast<uint8_t *>(ctx->scratch_a.p), n,
-                       static_cast<float2 *>(ctx->tz.p));
+    hipLaunchKernelGGL(k_ex_u8_to_c64, dim3(ex_grid(n)), dim3(256), 0, st, ctx->scratch_a.as<uint8_t>(), n,
+                       ctx->tz.as<float2>());
     HIPCHK(ctx, hipMemcpyAsync(out_c64, ctx->tz.p, n * sizeof(float2), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     return TDOA_OK;
@@ -227,7 +227,7 @@ int tdoa_preprocess_c64(tdoa_ctx *ctx, const float *sig, size_t n, float *out_c6
     float2 *src, *dst;
     if ((rc = ex_upload_c64(ctx, ctx->scratch_a, sig, n, &src))) return rc;
     if ((rc = ensure(ctx, ctx->tz, std::max<size_t>(n, 1) * sizeof(float2)))) return rc;
-    dst = static_cast<float2 *>(ctx->tz.p);
+    dst = ctx->tz.as<float2>();
     if ((rc = ex_preprocess(ctx, src, dst, n, weak_chain))) return rc;
     if (n) HIPCHK(ctx, hipMemcpyAsync(out_c64, dst, n * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -258,8 +258,8 @@ int tdoa_cross_correlate_c64(tdoa_ctx *ctx, const float *s1, size_t n1, const fl
     float2 *src, *p1, *p2;
     if ((rc = ensure(ctx, ctx->tz, n1 * sizeof(float2)))) return rc;
     if ((rc = ensure(ctx, ctx->v, n2 * sizeof(float2)))) return rc;
-    p1 = static_cast<float2 *>(ctx->tz.p);
-    p2 = static_cast<float2 *>(ctx->v.p);
+    p1 = ctx->tz.as<float2>();
+    p2 = ctx->v.as<float2>();
     float2 *src2;
     if ((rc = ex_upload_c64(ctx, ctx->scratch_a, s1, n1, &src))) return rc;
     if ((rc = ex_upload_c64(ctx, ctx->scratch_b, s2, n2, &src2))) return rc;
@@ -298,7 +298,7 @@ int tdoa_cross_correlate_batch_c64(tdoa_ctx *ctx, const float *const *signals, c
     // raw signals in tz, preprocessed ones in v, one DC-mean slot per signal behind them
     if ((rc = ensure(ctx, ctx->tz, total * sizeof(float2)))) return rc;
     if ((rc = ensure(ctx, ctx->v, (total + (size_t)n_signals + 2) * sizeof(float2)))) return rc;
-    float2 *raw = static_cast<float2 *>(ctx->tz.p), *pre = static_cast<float2 *>(ctx->v.p);
+    float2 *raw = ctx->tz.as<float2>(), *pre = ctx->v.as<float2>();
     float2 *means = pre + total;
     for (int s = 0; s < n_signals; s++)
         if (n[s])
@@ -341,7 +341,7 @@ int tdoa_simple_correlate_c64(tdoa_ctx *ctx, const float *s1, size_t n1, const f
     if (ml > sl - tl) ml = sl - tl;
     if (ml < 1) ml = 1;
     if ((rc = ensure(ctx, ctx->lagdump, sizeof(SimpleLag) * (size_t)ml + 16))) return rc;
-    auto *lags = static_cast<SimpleLag *>(ctx->lagdump.p);
+    auto *lags = ctx->lagdump.as<SimpleLag>();
     auto *tp = reinterpret_cast<float *>(lags + ml);
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL(k_ex_seq_power_f32, dim3(1), dim3(64), 0, st, tpl, (size_t)tl, tp);
@@ -406,8 +406,8 @@ int tdoa_fast_snr_u8(tdoa_ctx *ctx, const uint8_t *samples, int total, double *s
     hipStream_t st = ctx->stream;
     HIPCHK(ctx, hipMemcpyAsync(ctx->ex_a.p, x.data(), bytes, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(ctx->ex_b.p, tw.data(), bytes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_ex_fast_dft, dim3((asz + 255) / 256), dim3(256), 0, st, static_cast<double2 *>(ctx->ex_a.p),
-                       static_cast<double2 *>(ctx->ex_b.p), asz, static_cast<double2 *>(ctx->ex_c.p));
+    hipLaunchKernelGGL(k_ex_fast_dft, dim3((asz + 255) / 256), dim3(256), 0, st, ctx->ex_a.as<double2>(),
+                       ctx->ex_b.as<double2>(), asz, ctx->ex_c.as<double2>());
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(ft.data(), ctx->ex_c.p, bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));

@@ -98,6 +98,23 @@ bool run_members(int n, const std::function<void(int)> &work)
     return started;
 }
 
+// The merges take (window, pair) records and sums from different members: they must all cut the same windows of the same
+// stations.  false: *who is the first member whose station count or capture lengths differ from member 0's.
+bool group_same_captures(const tdoa_group *g, int *who)
+{
+    const auto &a = g->members[0]->caps;
+    for (int k = 1; k < (int)g->members.size(); k++) {
+        const auto &b = g->members[k]->caps;
+        bool same = a.size() == b.size();
+        for (size_t s = 0; same && s < a.size(); s++) same = a[s].n == b[s].n;
+        if (!same) {
+            *who = k;
+            return false;
+        }
+    }
+    return true;
+}
+
 // one member's share of the group's file ingest: its previous captures dropped, then every file's owned runs
 int group_member_upload(tdoa_ctx *ctx, int rank, int world, const std::vector<int> &fds, const std::vector<size_t> &n_samples,
                         size_t n_min)
@@ -211,15 +228,9 @@ int tdoa_group_process(tdoa_group *g, tdoa_peak *out_host)
     if (!out_host) return group_fail(g, TDOA_ERR_INVALID, "out_host is NULL");
     const int world = (int)g->members.size();
     tdoa_ctx *c0 = g->members[0];
-    // the merge takes (window, pair) records from different members: they must all cut the same windows of the same stations
-    for (int k = 1; k < world; k++) {
-        const auto &a = c0->caps, &b = g->members[k]->caps;
-        bool same = a.size() == b.size();
-        for (size_t s = 0; same && s < a.size(); s++) same = a[s].n == b[s].n;
-        if (!same)
-            return group_fail(g, TDOA_ERR_STATE, member_name(k, g->members[k]->device) +
-                                                     "station count or capture lengths differ from member 0's");
-    }
+    if (int who = 0; !group_same_captures(g, &who))
+        return group_fail(g, TDOA_ERR_STATE, member_name(who, g->members[who]->device) +
+                                                 "station count or capture lengths differ from member 0's");
     int wpb = 0, W = 0;
     if (tdoa_num_windows(c0, &wpb, &W) != TDOA_OK)
         return group_fail(g, TDOA_ERR_STATE, member_name(0, c0->device) + "captures missing or too small");
@@ -261,14 +272,9 @@ int tdoa_group_process_stacked(tdoa_group *g, int windows_per_stack, int k, int 
         return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
     }
     if (c0->prm.lag_mode == TDOA_LAGS_GO) return group_fail(g, TDOA_ERR_UNSUPPORTED, "stacked correlation with TDOA_LAGS_GO");
-    for (int m = 1; m < world; m++) {        // (as tdoa_group_process: every member must cut the same windows)
-        const auto &a = c0->caps, &b = g->members[m]->caps;
-        bool same = a.size() == b.size();
-        for (size_t s = 0; same && s < a.size(); s++) same = a[s].n == b[s].n;
-        if (!same)
-            return group_fail(g, TDOA_ERR_STATE, member_name(m, g->members[m]->device) +
-                                                     "station count or capture lengths differ from member 0's");
-    }
+    if (int who = 0; !group_same_captures(g, &who))
+        return group_fail(g, TDOA_ERR_STATE, member_name(who, g->members[who]->device) +
+                                                 "station count or capture lengths differ from member 0's");
     int n_stacks = 0;
     if (tdoa_num_stacks(c0, windows_per_stack, nullptr, &n_stacks) != TDOA_OK)
         return group_fail(g, TDOA_ERR_STATE, member_name(0, c0->device) + "captures missing or too small");

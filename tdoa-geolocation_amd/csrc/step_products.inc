@@ -1,0 +1,219 @@
+// step_products.inc -- what a step (process_impl) can write besides its peak records: the correlation surfaces
+// (tdoa_process_lags), the K strongest peaks per pair-window (tdoa_process_peaks), the stacked surfaces of a block's windows
+// (tdoa_process_stacked).  Every product is four functions next to each other, called by process_impl in this order:
+//   reserve_*   its buffers, after the step's grouping is fixed (batch_bound counts them as held, so a later call groups as
+//               this one did); no allocation may happen once the step is being captured
+//   key_*       the words it appends to the step graph's key: everything its launches depend on
+//   (upload_stack: the one product with descriptors of its own sends them with the step's, when the step is not replayed)
+//   enqueue_*   its kernels, after the step's decode -- unscoped launches, kernel nodes only: the step stays one chain
+//   download_*  its asynchronous copies out on ctx->stream
+// All of them read the K5 kernels' lag arrays in ctx->surf, pair-window i of the rank at i * n_lags.
+// Included by tdoa_mi355x.hip after step_graph.inc and stacked_api.inc.
+
+namespace {
+
+// What the stages see of the step (read-only)
+struct StepView {
+    tdoa_ctx *ctx;
+    const StepLayout *lay;
+    size_t slots;                            // W x P records of the job
+    int n_lags, lag_lo, P, wpb;
+    const PWDesc *d_pw;                      // the rank's pair-windows, the slots' keys and scales on the device
+    const unsigned long long *d_keys;
+    const double *d_scales;
+    const double *slot_gain;                 // enqueue_* only: the single-look path's gains, nullptr on every other path
+
+    size_t n_owned() const { return lay->pw.size(); }
+    size_t surf_n() const { return (size_t)n_lags * slots; }
+};
+
+struct LagsProduct {
+    float *lags_host = nullptr;
+    void *lags_dev = nullptr;
+};
+struct PeaksProduct {
+    int k = 0, min_sep = 0;
+    tdoa_peak *peaks_host = nullptr;         // [slot][k]
+    int32_t *count_host = nullptr;           // [slot]
+};
+struct StackProduct {
+    int m = 0;                               // windows per stack, 0: the whole block
+    int k = 0, min_sep = 0;
+    double gate = 0.0;
+    tdoa_peak *peaks_host = nullptr;         // [stack][pair][k]
+    int32_t *count_host = nullptr;           // [stack][pair]
+    tdoa_fine_peak *fine_host = nullptr;
+    float *surface_host = nullptr;
+    int64_t *partial_host = nullptr;         // the rank's fixed-point sums Q
+    StackLayout layout;                      // filled by reserve_stack
+    std::vector<double> ones;                // upload_stack's host copy of the unit scales (lives until the step's upload has synchronised)
+    // the finishing kernels run when one of their outputs is asked for (a group member returns its partial sums only)
+    bool finish() const { return peaks_host || count_host || fine_host || surface_host; }
+};
+
+// the product of one step; the numbers are the first word a product appends to the graph key
+struct StepProduct {
+    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3 } kind = None;
+    LagsProduct lags;
+    PeaksProduct peaks;
+    StackProduct stack;
+};
+
+// ctx->surf for the rank's pair-windows; `copies`: float surfaces of the step the product holds in all (the message's size)
+int surfaces_nomem(const StepView &v, const char *what, double copies)
+{
+    char buf[256];
+    snprintf(buf, sizeof(buf), "%s (%.1f MB) does not fit in device memory: %s", what,
+             copies * 4.0 * (double)v.n_lags * (double)std::max(v.n_owned(), v.slots) / 1e6, v.ctx->last_error.c_str());
+    return fail(v.ctx, TDOA_ERR_NOMEM, buf);
+}
+int reserve_surf(const StepView &v, double copies)
+{
+    if (ensure(v.ctx, v.ctx->surf, sizeof(float) * std::max<size_t>(v.n_owned() * v.n_lags, 1)))
+        return surfaces_nomem(v, "correlation surfaces", copies);
+    return TDOA_OK;
+}
+
+// ---- the surfaces in the caller's layout [slot][n_lags] (ctx->surf_out) ----------------------------------------------
+int reserve_lags(const StepView &v, const LagsProduct &)
+{
+    if (int rc = reserve_surf(v, 2.0)) return rc;
+    if (ensure(v.ctx, v.ctx->surf_out, sizeof(float) * (v.surf_n() + 1))) return surfaces_nomem(v, "correlation surfaces, caller's layout", 2.0);
+    return TDOA_OK;
+}
+void key_lags(const LagsProduct &, std::vector<uint64_t> *key) { key->insert(key->end(), {StepProduct::Lags, 0, 0, 0}); }
+void enqueue_lags(const StepView &v, const LagsProduct &)
+{
+    hipStream_t st = v.ctx->stream;
+    hipLaunchKernelGGL(k_zero_u64, dim3((unsigned)((v.surf_n() / 2 + 256) / 256)), dim3(256), 0, st,
+                       v.ctx->surf_out.as<unsigned long long>(), (v.surf_n() + 1) / 2);
+    if (v.n_owned())
+        hipLaunchKernelGGL(k_surface_out, dim3((unsigned)v.n_owned(), (unsigned)((v.n_lags + 1023) / 1024)), dim3(256), 0, st,
+                           v.ctx->surf.as<const float>(), (size_t)v.n_lags, v.n_lags, v.d_pw, v.d_scales, v.slot_gain,
+                           v.ctx->surf_out.as<float>());
+}
+int download_lags(const StepView &v, const LagsProduct &p)
+{
+    tdoa_ctx *ctx = v.ctx;
+    if (p.lags_dev)
+        HIPCHK(ctx, hipMemcpyAsync(p.lags_dev, ctx->surf_out.p, sizeof(float) * v.surf_n(), hipMemcpyDeviceToDevice, ctx->stream));
+    if (p.lags_host)
+        HIPCHK(ctx, hipMemcpyAsync(p.lags_host, ctx->surf_out.p, sizeof(float) * v.surf_n(), hipMemcpyDeviceToHost, ctx->stream));
+    return TDOA_OK;
+}
+
+// ---- k peaks [slot][k] and their counts [slot] (ctx->sel_peaks, ctx->sel_count) ----------------------------------------
+int reserve_peaks(const StepView &v, const PeaksProduct &p)
+{
+    if (int rc = reserve_surf(v, 1.0)) return rc;
+    if (ensure(v.ctx, v.ctx->sel_peaks, sizeof(PeakOut) * v.slots * p.k) || ensure(v.ctx, v.ctx->sel_count, sizeof(int32_t) * (v.slots + 1)))
+        return surfaces_nomem(v, "selected peaks", 1.0);
+    return TDOA_OK;
+}
+void key_peaks(const PeaksProduct &p, std::vector<uint64_t> *key)
+{
+    key->insert(key->end(), {StepProduct::Peaks, (uint64_t)p.k, (uint64_t)p.min_sep, 0});
+}
+void enqueue_peaks(const StepView &v, const PeaksProduct &p)
+{
+    tdoa_ctx *ctx = v.ctx;
+    hipStream_t st = ctx->stream;
+    const size_t rec_words = v.slots * (size_t)p.k * (sizeof(PeakOut) / 8);
+    hipLaunchKernelGGL(k_zero_u64, dim3((unsigned)((rec_words + 255) / 256)), dim3(256), 0, st, ctx->sel_peaks.as<unsigned long long>(),
+                       rec_words);
+    hipLaunchKernelGGL(k_zero_u64, dim3((unsigned)((v.slots / 2 + 256) / 256)), dim3(256), 0, st,
+                       ctx->sel_count.as<unsigned long long>(), (v.slots + 1) / 2);
+    if (v.n_owned())
+        hipLaunchKernelGGL(k_select_peaks, dim3((unsigned)v.n_owned()), dim3(kSelThreads), 0, st, ctx->surf.as<const float>(),
+                           (size_t)v.n_lags, v.n_lags, v.lag_lo, v.d_pw, v.d_keys, v.d_scales, v.slot_gain, p.k, p.min_sep,
+                           ctx->sel_peaks.as<PeakOut>(), ctx->sel_count.as<int32_t>());
+}
+int download_peaks(const StepView &v, const PeaksProduct &p)
+{
+    tdoa_ctx *ctx = v.ctx;
+    if (p.peaks_host)
+        HIPCHK(ctx, hipMemcpyAsync(p.peaks_host, ctx->sel_peaks.p, sizeof(PeakOut) * v.slots * p.k, hipMemcpyDeviceToHost, ctx->stream));
+    if (p.count_host)
+        HIPCHK(ctx, hipMemcpyAsync(p.count_host, ctx->sel_count.p, sizeof(int32_t) * v.slots, hipMemcpyDeviceToHost, ctx->stream));
+    return TDOA_OK;
+}
+
+// ---- the stacks' fixed-point sums (ctx->stack_q) and, finished, their surfaces and peaks (stacked_api.inc) ------------
+int reserve_stack(const StepView &v, StackProduct &p)
+{
+    tdoa_ctx *ctx = v.ctx;
+    if (int rc = reserve_surf(v, 1.0)) return rc;
+    p.layout = build_stack_layout(v.lay->pw, v.wpb, v.P, p.m);
+    const size_t n_sp = (size_t)p.layout.n_stacks * v.P;
+    if (ensure(ctx, ctx->stack_q, sizeof(long long) * n_sp * v.n_lags) ||
+        ensure(ctx, ctx->stack_desc, stack_desc_bytes(p.layout.n_stacks, v.P, v.n_owned())) ||
+        (p.finish() && ensure_stack_finish(ctx, n_sp, v.n_lags, p.k)))
+        return surfaces_nomem(v, "correlation surfaces and their stacked sums", 1.0);
+    return TDOA_OK;
+}
+void key_stack(const StackProduct &p, std::vector<uint64_t> *key)
+{
+    key->insert(key->end(), {StepProduct::Stack, (uint64_t)p.k, (uint64_t)p.min_sep, (uint64_t)p.m | ((uint64_t)p.finish() << 32)});
+}
+int upload_stack(const StepView &v, StackProduct &p) { return upload_stack_desc(v.ctx, p.layout, v.P, &p.ones, true); }
+void enqueue_stack(const StepView &v, const StackProduct &p)
+{
+    tdoa_ctx *ctx = v.ctx;
+    const int n_stacks = p.layout.n_stacks;
+    const StackDev sd = stack_dev(ctx, n_stacks, v.P);
+    hipLaunchKernelGGL(k_stack_accumulate, dim3((unsigned)(n_stacks * v.P), (unsigned)((v.n_lags + kStackTile - 1) / kStackTile)),
+                       dim3(kStackThreads), 0, ctx->stream, ctx->surf.as<const float>(), (size_t)v.n_lags, v.n_lags, v.d_pw, sd.desc, sd.list,
+                       v.d_scales, v.slot_gain, ctx->stack_q.as<long long>());
+    if (p.finish()) launch_stack_finish(ctx, n_stacks, v.P, v.n_lags, v.lag_lo, p.k, p.min_sep, p.gate);
+}
+int download_stack_product(const StepView &v, const StackProduct &p)
+{
+    tdoa_ctx *ctx = v.ctx;
+    const size_t n_sp = (size_t)p.layout.n_stacks * v.P;
+    if (int rc = download_stack(ctx, n_sp, v.n_lags, p.k, p.peaks_host, p.count_host, p.fine_host, p.surface_host)) return rc;
+    if (p.partial_host)
+        HIPCHK(ctx, hipMemcpyAsync(p.partial_host, ctx->stack_q.p, sizeof(int64_t) * n_sp * v.n_lags, hipMemcpyDeviceToHost, ctx->stream));
+    return TDOA_OK;
+}
+
+// ---- process_impl's one dispatch per stage ---------------------------------------------------------------------------
+int reserve_product(const StepView &v, StepProduct &p)
+{
+    switch (p.kind) {
+    case StepProduct::Lags: return reserve_lags(v, p.lags);
+    case StepProduct::Peaks: return reserve_peaks(v, p.peaks);
+    case StepProduct::Stack: return reserve_stack(v, p.stack);
+    default: return TDOA_OK;
+    }
+}
+void key_product(const StepProduct &p, std::vector<uint64_t> *key)
+{
+    switch (p.kind) {
+    case StepProduct::Lags: return key_lags(p.lags, key);
+    case StepProduct::Peaks: return key_peaks(p.peaks, key);
+    case StepProduct::Stack: return key_stack(p.stack, key);
+    default: key->insert(key->end(), {StepProduct::None, 0, 0, 0});
+    }
+}
+int upload_product(const StepView &v, StepProduct &p) { return p.kind == StepProduct::Stack ? upload_stack(v, p.stack) : TDOA_OK; }
+void enqueue_product(const StepView &v, const StepProduct &p)
+{
+    if (p.kind != StepProduct::None) v.ctx->prof_last = -1;    // unscoped launches
+    switch (p.kind) {
+    case StepProduct::Lags: return enqueue_lags(v, p.lags);
+    case StepProduct::Peaks: return enqueue_peaks(v, p.peaks);
+    case StepProduct::Stack: return enqueue_stack(v, p.stack);
+    default: return;
+    }
+}
+int download_product(const StepView &v, const StepProduct &p)
+{
+    switch (p.kind) {
+    case StepProduct::Lags: return download_lags(v, p.lags);
+    case StepProduct::Peaks: return download_peaks(v, p.peaks);
+    case StepProduct::Stack: return download_stack_product(v, p.stack);
+    default: return TDOA_OK;
+    }
+}
+
+}  // namespace
