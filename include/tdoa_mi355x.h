@@ -392,7 +392,8 @@ enum {
     TDOA_ROUTE_XCD_PAIRS = 12,   /* k_inv_row_pair4096 on its XCD-grouped 1-D grid                                      */
     TDOA_ROUTE_DEC_GP = 13,      /* k_pair_decimate16 on its XCD-grouped grid                                           */
     TDOA_ROUTE_STG_FOLDED = 14,  /* staged column walk without a loader wave                                            */
-    TDOA_ROUTE_STG_BLOCKED = 15  /* staged column walk reads spectra in blocks of 64 columns                             */
+    TDOA_ROUTE_STG_BLOCKED = 15  /* staged column walk, a BIT FIELD (test the bits below, not == 1):                     */
+                                 /* TDOA_ROUTE_STG_BLOCKED_BIT | TDOA_ROUTE_STG_MERGED_BIT                              */
 };
 enum { TDOA_INV_NONE = 0, TDOA_INV_SEGMENTS = 1, TDOA_INV_DECIMATED = 2, TDOA_INV_SHORT_LAG = 3, TDOA_INV_FULL = 4 };
 enum { TDOA_STEP_TILES = 0, TDOA_STEP_COLUMNS = 1, TDOA_STEP_STAGED = 2 };
@@ -404,6 +405,10 @@ enum {
     TDOA_ROW_NONE = 0, TDOA_ROW_UNPACK_BLOCKS = 1, TDOA_ROW_UNPACK_IN_PLACE = 2, TDOA_ROW_UNPACK_TILES = 3, TDOA_ROW_HOT = 4,
     TDOA_ROW_GENERIC = 5
 };
+/* info[TDOA_ROUTE_STG_BLOCKED]: */
+#define TDOA_ROUTE_STG_BLOCKED_BIT 1 /* the walk reads spectra in blocks of 64 columns                                      */
+#define TDOA_ROUTE_STG_MERGED_BIT 2  /* ... and adds the neighbour shares inside a block itself: only the block-edge        */
+                                     /* columns' shares go through memory                                                   */
 int tdoa_debug_last_route(const tdoa_ctx *ctx, int32_t info[16]);
 /* tests only (host, no GPU): the cover of a window's station pairs by "quads" -- two template stations x two signal
  * stations whose two packed transforms per segment serve up to four pairs in the segment form.

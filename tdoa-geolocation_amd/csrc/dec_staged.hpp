@@ -22,7 +22,9 @@
 // of one XCD and start together, so later groups find rows in that XCD's L2.
 // Where the plan leaves room (N2 = 256, 512) the row pass writes the spectra in BLOCKS of 64 columns, [column / 64][k2][column % 64]:
 // a loader's pieces of consecutive rows are then consecutive in memory and a station's R rows go out back to back.
-// Outputs: exactly k_pair_decimate_cols's -- G[pw][N2/16][4096] and the neighbour shares X[pw][12][4096].
+// Outputs: exactly k_pair_decimate_cols's -- G[pw][N2/16][4096] and the neighbour shares X[pw][12][4096] -- or, with MERGE_, G
+// with the shares of a block's inner columns already added (the same bits the row pass would produce) and X at the block-edge
+// columns only.
 //
 // What bounds it (round 5, measurement build -DTDOA_STG_TIMING + scripts/microbench/lds_dma_probe.hip, profiles/r05_staged_walk_*):
 // the walks' vector issue.  The counters first read otherwise -- the walks 28 - 37 % of their cycles at the barrier, the loader
@@ -45,6 +47,13 @@ constexpr int kStgMaxStations = 16;          // station slots in LDS (1 KB per r
 constexpr int kStgMaxWaves = 16;
 constexpr int kStgLdsBytes = 128 * 1024;     // the ring: phases x rows per phase x stations x 1 KB
 constexpr int kStgMaxInFlight = 60;          // LDS-DMA instructions a loader wave leaves outstanding (the counter holds 63)
+// merged shares: a walk holds 4 C - 2 more values (44 VGPRs) for its whole run and the kernel grows from 99 / 101 / 113 VGPRs
+// at four waves per SIMD (R = 2 / 4 / 8) to 177 / 179 / 191 at two, no scratch -- the waves of a CU that may run it.  (At
+// three waves per SIMD, 168 registers, the compiler spills nine of them: -DTDOA_STG_MERGE_WAVES=12.)
+#ifndef TDOA_STG_MERGE_WAVES
+#define TDOA_STG_MERGE_WAVES 8
+#endif
+constexpr int kStgMergeWaves = TDOA_STG_MERGE_WAVES;
 constexpr int kStgBlockCols = 64;            // the blocked layout of the unpacked spectra: [column / 64][row k2][column % 64]
 // one workgroup's share of a window's pairs: `n` of them, by their index in the window's pair list, and the stations they touch
 // (bit s = the window's station s); a station's place in the LDS ring is its rank among the set bits
@@ -87,7 +96,9 @@ __device__ __forceinline__ void stg_wait_vm(int n)
 // phase and wave costs more than the barrier it replaces.  Commit 73f2769 holds it.)
 // R_: rows (and partner rows) per phase = per barrier; nb: phases in the ring (nb - 1 of them are in flight or being read:
 // what hides the memory latency is (nb - 2) R S KB per workgroup)
-template <int N2_, int R_>
+// MERGE_ (blocked plans, workgroups of at most kStgMergeWaves waves): the neighbour shares of the 126 inner columns never
+// reach memory -- see "merged shares" below; X then holds the block-edge columns' shares only.
+template <int N2_, int R_, bool MERGE_ = false>
 // (plain ds_read_b64 with immediate row offsets: left to itself the backend pairs the reads of two rows into ds_read2st64_b64,
 //  which the LDS serves at half the rate of two plain reads -- MI355X_MICROARCH.md, LDS table; -DTDOA_STG_PAIRED_READS for the A/B)
 #ifdef TDOA_STG_PAIRED_READS
@@ -95,7 +106,8 @@ template <int N2_, int R_>
 #else
 #define TDOA_STG_DS_OPS TDOA_PLAIN_DS_OPS
 #endif
-__global__ __launch_bounds__(64 * kStgMaxWaves) __attribute__((amdgpu_waves_per_eu(4, 4) TDOA_STG_DS_OPS)) void k_pair_decimate_staged(const PWDesc *pw, const float2 *U, float2 *G, float2 *X, FftPlan pl,
+__global__ __launch_bounds__(64 * (MERGE_ ? kStgMergeWaves : kStgMaxWaves))
+__attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kStgMergeWaves / 4 : 4) TDOA_STG_DS_OPS)) void k_pair_decimate_staged(const PWDesc *pw, const float2 *U, float2 *G, float2 *X, FftPlan pl,
                                                                              const float *__restrict__ taps, const StgGroup *__restrict__ groups,
                                                                              int n_items, int P, int S, int n_cw, int n_groups, int nb,
                                                                              long long u_stride, int blocked)
@@ -367,23 +379,68 @@ __global__ __launch_bounds__(64 * kStgMaxWaves) __attribute__((amdgpu_waves_per_
         pair_u_pk(*row0_at(Ua, k1), *row0_at(Ua, kp), *row0_at(Ub, k1), *row0_at(Ub, kp), w_n((float)k1 * (float)N2), k1 == 0, q, qm);
         mac_all(at, tr, q);
     }
-    x_top[0] = make_float2(0.0f, 0.0f);
-    x_bot[0] = make_float2(0.0f, 0.0f);
-    auto bottom_leaves = [&](int i) {
-        if (i >= NG) x_bot[(size_t)(kDecEdge + i - NG) * N1] = ab[SS - 1];
-        else if (i >= 0) g_bot[(size_t)i * N1] = ab[SS - 1];
-        else x_bot[(size_t)(kDecEdge + i) * N1] = ab[SS - 1];
+    // ---- merged shares (MERGE_) ----------------------------------------------------------------------------------------------
+    // A share and the output it belongs to leave their walks a whole column apart in time: the downward walk of column k1 is through
+    // with its first C - 1 shares (slots 1 .. C - 1, for the LAST outputs of column k1 - 1) and with its own outputs 0 .. C - 1 after
+    // 2 C - 1 groups of rows, while the shares those outputs wait for (slots C .. 2 C - 1 of column k1 - 1) are that walk's last
+    // values; the upward walk mirrors it.  So a walk HOLDS the first 2 C - 1 values that leave each of its two stencils (held_t,
+    // held_b: 4 C - 2 float2, pushed in front so that every index is a constant) and settles everything after its last row:
+    //   * lane l takes from lane l + 1 the shares that lane held (ds_bpermute) and adds each to its own late output;
+    //   * lane l takes from lane l - 1 that lane's late shares and adds each to the output it held.
+    // An output receives exactly ONE share (k_inv_rows_plain_r8's merge adds one slot row of one neighbouring column to a row
+    // of G: rows 0 .. C - 1 slot C + row of the column to the left, rows N2' - C + 1 .. N2' - 1 slot row - (N2' - C) of the
+    // column to the right; slot 0 is never read), and the sum here is that kernel's: the f32 addition G + share of the same two
+    // values, so the bits are the same.  Lanes 0 and 63 have one neighbour in another workgroup: columns = 0 (mod 64) still
+    // write slots 1 .. C - 1 to X and columns = 63 (mod 64) slots C .. 2 C - 1, and the row pass adds those alone.
+    constexpr int H = MERGE_ ? 2 * C - 1 : 1;
+    [[maybe_unused]] float2 held_t[H], held_b[H];
+    [[maybe_unused]] auto hold = [&](float2 (&h)[H], float2 v) {
+#pragma unroll
+        for (int u = H - 1; u > 0; u--) h[u] = h[u - 1];
+        h[0] = v;
+    };
+    [[maybe_unused]] auto lane_from = [&](float2 v, int src) {
+        return make_float2(__int_as_float(__builtin_amdgcn_ds_bpermute(4 * src, __float_as_int(v.x))),
+                           __int_as_float(__builtin_amdgcn_ds_bpermute(4 * src, __float_as_int(v.y))));
+    };
+    [[maybe_unused]] const int lane_up = (lane + 1) & 63, lane_dn = (lane + 63) & 63;
+    if constexpr (!MERGE_) {
+        x_top[0] = make_float2(0.0f, 0.0f);
+        x_bot[0] = make_float2(0.0f, 0.0f);
+    }
+    auto shift_b = [&]() {
 #pragma unroll
         for (int u = SS - 1; u > 0; u--) ab[u] = ab[u - 1];
         ab[0] = make_float2(0.0f, 0.0f);
     };
-    auto top_leaves = [&](int i) {
-        if (i < 0) x_top[(size_t)(kDecEdge + i) * N1] = at[SS - 1];
-        else if (i < NG) g_top[(size_t)i * N1] = at[SS - 1];
-        else x_top[(size_t)(kDecEdge + i - NG) * N1] = at[SS - 1];
+    auto shift_t = [&]() {
 #pragma unroll
         for (int s = SS - 1; s > 0; s--) at[s] = at[s - 1];
         at[0] = make_float2(0.0f, 0.0f);
+    };
+    auto bottom_leaves = [&](int i) {
+        if constexpr (MERGE_) {                                    // (inside the loop: i = NG + C - 1 down to C + 1)
+            if (i > NG - C) hold(held_b, ab[SS - 1]);              // held_b[j]: the value of i = NG - (C - 1) + j
+            else g_bot[(size_t)i * N1] = ab[SS - 1];
+            shift_b();
+            return;
+        }
+        if (i >= NG) x_bot[(size_t)(kDecEdge + i - NG) * N1] = ab[SS - 1];
+        else if (i >= 0) g_bot[(size_t)i * N1] = ab[SS - 1];
+        else x_bot[(size_t)(kDecEdge + i) * N1] = ab[SS - 1];
+        shift_b();
+    };
+    auto top_leaves = [&](int i) {
+        if constexpr (MERGE_) {                                    // (inside the loop: i = -(C - 1) .. NG - C)
+            if (i < C) hold(held_t, at[SS - 1]);                   // held_t[j]: the value of i = C - 1 - j
+            else g_top[(size_t)i * N1] = at[SS - 1];
+            shift_t();
+            return;
+        }
+        if (i < 0) x_top[(size_t)(kDecEdge + i) * N1] = at[SS - 1];
+        else if (i < NG) g_top[(size_t)i * N1] = at[SS - 1];
+        else x_top[(size_t)(kDecEdge + i - NG) * N1] = at[SS - 1];
+        shift_t();
     };
     // LDS byte offsets of this lane's four operands inside a (phase, row) block of S KB: column k1 of the forward piece,
     // column km = 4095 - k1 of the partner piece (its block is stored ascending: lane 63 - l)
@@ -443,16 +500,62 @@ __global__ __launch_bounds__(64 * kStgMaxWaves) __attribute__((amdgpu_waves_per_
         }
         if (((k2 + R - 1) & 15) == 15) top_leaves((k2 >> 4) - (SS - 1 - C));
     }
+    if constexpr (MERGE_) {
+        static_assert(!MERGE_ || SS == 2 * C, "the held values: C - 1 shares and C outputs per stencil");
 #pragma unroll
-    for (int n = 0; n < SS - 1; n++) top_leaves(NG - (SS - 1 - C) + n);
+        for (int n = 0; n < SS - 1; n++) {                         // the values of i = NG - (C - 1) + n
+            const float2 v = at[SS - 1];
+            if (n < C - 1) {                                       // output i: + slot n + 1 of column k1 + 1 (that walk's i = n + 1 - C)
+                const float2 s = lane_from(held_t[2 * C - 2 - n], lane_up);
+                g_top[(size_t)(NG - (C - 1) + n) * N1] = lane < 63 ? make_float2(v.x + s.x, v.y + s.y) : v;
+            } else {                                               // slot C + r: the share of output r of column k1 + 1
+                const int r = n - (C - 1);
+                const float2 s = lane_from(v, lane_dn), g = held_t[C - 1 - r];
+                g_top[(size_t)r * N1] = lane > 0 ? make_float2(g.x + s.x, g.y + s.y) : g;
+                if (lane == 63) x_top[(size_t)(C + r) * N1] = v;
+            }
+            shift_t();
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int s = 1; s < C; s++) x_top[(size_t)s * N1] = held_t[2 * C - 1 - s];
+        }
+    } else {
+#pragma unroll
+        for (int n = 0; n < SS - 1; n++) top_leaves(NG - (SS - 1 - C) + n);
+    }
     {
         const TapRow tr = tap_row(16);
         float2 q, qm;
         pair_u_pk(*row0_at(Ua, km), *row0_at(Ua, k1 + 1), *row0_at(Ub, km), *row0_at(Ub, k1 + 1), w_n((float)km * (float)N2), false, q, qm);
         mac_all(ab, tr, q);
     }
+    if constexpr (MERGE_) {
 #pragma unroll
-    for (int n = 0; n < SS; n++) bottom_leaves(C - n);
+        for (int n = 0; n < SS; n++) {                             // the values of i = C - n
+            const float2 v = ab[SS - 1];
+            if (n == 0) {
+                g_bot[(size_t)C * N1] = v;
+            } else if (n <= C) {                                   // output r: + slot C + r of column km - 1 (lane + 1; that walk's i = NG + r)
+                const int r = C - n;
+                const float2 s = lane_from(held_b[C - 1 + r], lane_up);
+                g_bot[(size_t)r * N1] = lane < 63 ? make_float2(v.x + s.x, v.y + s.y) : v;
+            } else {                                               // slot s: the share of output NG - C + s of column km - 1 (lane + 1)
+                const int sl = 2 * C - n;
+                const float2 s = lane_from(v, lane_dn), g = held_b[sl - 1];
+                g_bot[(size_t)(NG - C + sl) * N1] = lane > 0 ? make_float2(g.x + s.x, g.y + s.y) : g;
+                if (lane == 63) x_bot[(size_t)sl * N1] = v;
+            }
+            shift_b();
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int s = C; s < 2 * C; s++) x_bot[(size_t)s * N1] = held_b[s - 1];
+        }
+    } else {
+#pragma unroll
+        for (int n = 0; n < SS; n++) bottom_leaves(C - n);
+    }
     TDOA_STG_T(if (lane == 0) { atomicAdd(&g_stg_prof[0], __builtin_readcyclecounter() - t_in); atomicAdd(&g_stg_prof[1], t_bar);
                                 atomicAdd(&g_stg_prof[5], 1ull); })
 }

@@ -302,6 +302,9 @@ constexpr int kDecSteps = TDOA_DEC_STEPS;                   // a tap t = 16 (s -
 constexpr int kDecCentre = kDecSteps / 2;                   // C
 constexpr int kDecTmax = 16 * kDecCentre - 1;               // |t| <= T <= kDecTmax
 constexpr int kDecEdge = kDecCentre;                        // outputs on either side of a tile boundary that the other tile's bins reach
+// how the small plan's row pass finds the neighbours' shares (its by_column argument): E per tile, X for every column, X for
+// the two columns at the edges of a 64-column block only
+constexpr int kSharesTiles = 0, kSharesColumns = 1, kSharesBlockEdges = 2;
 static_assert(kDecSteps % 2 == 0 && kDecSteps >= 4 && kDecSteps <= 14, "FIR geometry: 8 zero slots per side, 16 taps per phase in LDS");
 // LDS image of a tile (4096 consecutive bins, no halo): bin o lives at [o & 15][dec_slot((o >> 4) + 8)],
 // dec_slot(i) = i + ((i + 8) >> 4).  8 zero slots on either side stand for the neighbouring tiles (their share of an
@@ -543,6 +546,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4) TDOA_
 // by_column (k_pair_decimate_cols, dec_stream.hpp): the shares arrive as X[pw][12][4096] -- row i < kDecEdge of G gets slot
 // row kDecEdge + i of the column to its left, row i >= N2' - kDecEdge slot row i - (N2' - kDecEdge) of the column to its
 // right (slot row 0 is all zeros and is skipped): one more coalesced row read for 11 of the N2' rows.
+// by_column = kSharesBlockEdges (k_pair_decimate_staged<.., MERGE_ = true>): the walks of a block of 64 columns have added the
+// shares among themselves; X holds, and this kernel reads, only what crosses a block edge -- a column = 0 (mod 64) takes its
+// left neighbour's slots, a column = 63 (mod 64) its right neighbour's, nothing else of X is read (or was written).
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4) TDOA_PLAIN_DS_OPS)) void k_inv_rows_plain_r8(const float2 *G, const float2 *E, float2 *V, FftPlan pl, int big_n2, int by_column)
 {
     extern __shared__ float2 lds[];   // 2 * kRow8Lds
@@ -563,6 +569,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4) TDOA_
         if (by_column) {
             const bool left = row < kDecEdge;
             if ((!left && row < pl.N2 - kDecEdge) || row == pl.N2 - kDecEdge) return;
+            if (by_column == kSharesBlockEdges && (t & 63) != (left ? 0 : 63)) return;      // (t + 512 r = t mod 64)
             const float2 *x = E + ((size_t)blockIdx.y * (2 * kDecEdge) + (size_t)(left ? kDecEdge + row : row - (pl.N2 - kDecEdge))) * 4096;
 #pragma unroll
             for (int r = 0; r < 8; r++) {
@@ -746,6 +753,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2) TDOA_
         if (by_column) {
             const bool left = row < kDecEdge;
             if ((!left && row < N2 - kDecEdge) || row == N2 - kDecEdge) return;
+            if (by_column == kSharesBlockEdges && (t & 63) != (left ? 0 : 63)) return;
             const float2 *x = E + ((size_t)blockIdx.x * (2 * kDecEdge) + (size_t)(left ? kDecEdge + row : row - (N2 - kDecEdge))) * 4096;
 #pragma unroll
             for (int r = 0; r < 8; r++) {

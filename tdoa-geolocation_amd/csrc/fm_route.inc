@@ -115,6 +115,7 @@ enum class PairStep { Tiles, Columns, Staged };        // the decimated inverse'
 // the LDS-staged column walk's launch (dec_staged.hpp)
 struct StagedGeometry {
     bool folded = false, blocked = false;
+    bool merged = false;             // the walks of a 64-column block add the neighbour shares among themselves; X: block edges only
     int n_lw = 0, n_cw = 0, slots = 0, groups = 0, off = 0, rows = 0, nb = 0, n_items = 0;
     unsigned int blocks = 0;
     size_t lds = 0;
@@ -140,6 +141,7 @@ struct FmRoute {
     bool fused_k1 = false, once = false, pruned = false, seg_quads = false, seg_pack3 = false, small_fused = false;
     bool dec_tables = false;         // the decimated inverse applies: its filter and the staged tables are set up
     int fk = 0, np = 0, nn = 0, np2 = 0, nn2 = 0, seg_pq = 0, seg_chunks = 0;
+    int shares = kSharesTiles;       // where the small plan's row pass finds the neighbours' shares (kShares*, fft_radix8.hpp)
     int xcd_pairs = 0, dec_gp = 0;   // pair-windows of a window on one XCD: k_inv_row_pair4096's 1-D grid, k_pair_decimate16's (0: plain)
     unsigned int xcd_grid = 0;
     dim3 dec_grid;
@@ -269,10 +271,16 @@ FmRoute plan_fm_batch(const Knobs &k, const StgTables &t, int n_cu, const FftPla
             g.n_cw = tab.max_n;
             g.slots = tab.slots;
             g.n_lw = g.folded ? 0 : std::max(1, std::min(k.stg_loaders ? k.stg_loaders : 1, std::min(4, g.slots)));
+            // neighbour shares merged inside the walk (dec_staged.hpp, "merged shares"): the blocked plans.  The merging kernel
+            // needs 177 - 191 VGPRs: two waves per SIMD, kStgMergeWaves = 8 per CU.  Merged only where TWO workgroups still share
+            // the CU as they do unmerged -- at most four waves each: three walks and a loader, cfg2's three stations (measured:
+            // DESIGN.md section 9).  A seven-wave workgroup (four stations) would fall from two per CU to one, twelve walks in
+            // flight to six, on a kernel that waits for memory: not measured, not merged; larger groups do not fit at all.
+            g.merged = k.stg_merge && g.blocked && (pl.N2 == 256 || pl.N2 == 512) && 2 * (g.n_cw + g.n_lw) <= kStgMergeWaves;
             // (few-station batches wait for memory rather than for the barrier: eight rows per phase there as well, and on the
             //  blocked plans a third phase in the ring where two workgroups still share a CU's LDS -- cfg2: 0.594 -> 0.571 ms;
             //  a fourth, or a third on the in-place plans, lost: cfg2 0.63, cfg3 17.8 against 16.3)
-            const int wgs_by_waves = std::max(1, kStgMaxWaves / (g.n_cw + g.n_lw));
+            const int wgs_by_waves = std::max(1, (g.merged ? kStgMergeWaves : kStgMaxWaves) / (g.n_cw + g.n_lw));      // workgroups a CU's wave slots hold
             const int budget = wgs_by_waves >= 2 ? 80 * 1024 : kStgLdsBytes;
             const int phase = g.slots * 1024;      // bytes of one row of every station
             g.rows = k.stg_rows ? k.stg_rows : 2 * 8 * phase <= kStgLdsBytes ? 8 : 2 * 4 * phase <= kStgLdsBytes ? 4 : 2;
@@ -288,6 +296,7 @@ FmRoute plan_fm_batch(const Knobs &k, const StgTables &t, int n_cu, const FftPla
             g.blocks = (unsigned int)((g.n_items + 7) / 8 * 8) * (unsigned int)g.groups;
             g.lds = (size_t)g.nb * g.rows * phase;
         }
+        r.shares = r.step == PairStep::Tiles ? kSharesTiles : r.stg.merged ? kSharesBlockEdges : kSharesColumns;
         // pair-windows of a window that share station tiles on one XCD (k_pair_decimate16): when the batch is uniform and
         // a window's spectra are too many to come from on-die memory for their other readers (ctx->xcd_pair_mb: cfg5, 16
         // stations x 16.8 MB: its step 258 -> 237 ms in round 3; cfg4, 8 x 8.4 MB: -1.3 % since round 4; cfg2: plain grid)
@@ -525,6 +534,15 @@ void launch_segments(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
     });
 }
 
+// the neighbour shares between the pair step and the small plan, one way: E [N2][2 C] per pair-window (tiles), X [2 C][4096]
+// (column walks), or X's slots of the two edge columns of every 64-column block (merged staged walk: 2 C - 1 values per edge)
+double dec_share_bytes(const FmRoute &r)
+{
+    const double per_pw = r.shares == kSharesTiles ? (double)r.pl.N2 * (2 * kDecEdge) : r.shares == kSharesColumns ? 4096.0 * (2 * kDecEdge)
+                                                                                       : (4096.0 / kStgBlockCols) * (2 * kDecEdge - 1);
+    return 8.0 * per_pw * r.b.n_pw;
+}
+
 // decimated inverse, pair step: K3 + FIR decimation of the pair's spectrum (one read of the two station spectra) into G
 void launch_pair_step(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
 {
@@ -532,15 +550,22 @@ void launch_pair_step(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
     const int n_pw = r.b.n_pw;
     float2 *g = bf.v, *edges = bf.v + dec_edge_offset(pl, n_pw), *spectra = bf.v + dec_spectra_offset(pl, n_pw);
     const auto *taps = ctx->dec_taps.as<const float>();
-    ProfScope ps(ctx, TDOA_K_INV_ROW, 2.0 * (8.0 * (double)pl.Nc) * n_pw + 8.0 * (double)(pl.Nc / kDecD) * n_pw);      // two spectra read, G written
+    ProfScope ps(ctx, TDOA_K_INV_ROW, 2.0 * (8.0 * (double)pl.Nc) * n_pw + 8.0 * (double)(pl.Nc / kDecD) * n_pw + dec_share_bytes(r));      // two spectra read, G and the shares written
 #if TDOA_HAVE_DEC_COLS
     if (r.step == PairStep::Staged) {
         const StagedGeometry &sg = r.stg;
         const StgGroup *gt = ctx->stg_groups.as<const StgGroup>() + sg.off;
         with_int<256, 512, 2048, 2560, 3072, 4096>(pl.N2, [&](auto n2) { with_int<8, 4, 2>(sg.rows, [&](auto rows) {
-            hipLaunchKernelGGL((k_pair_decimate_staged<decltype(n2)::value, decltype(rows)::value>), dim3(sg.blocks), dim3(64 * (sg.n_cw + sg.n_lw)),
-                               sg.lds, bf.st, bf.pw, sg.blocked ? spectra : bf.tz, g, edges, pl, taps, gt, sg.n_items, r.b.pairs_per_window,
-                               sg.slots, sg.n_cw, sg.groups, sg.nb, sg.blocked ? (long long)pl.Nc : (long long)pl.Zs, (int)sg.blocked);
+            auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3(sg.blocks), dim3(64 * (sg.n_cw + sg.n_lw)), sg.lds, bf.st, bf.pw, sg.blocked ? spectra : bf.tz, g,
+                                   edges, pl, taps, gt, sg.n_items, r.b.pairs_per_window, sg.slots, sg.n_cw, sg.groups, sg.nb,
+                                   sg.blocked ? (long long)pl.Nc : (long long)pl.Zs, (int)sg.blocked);
+            };
+            constexpr int N2 = decltype(n2)::value, R = decltype(rows)::value;
+            if constexpr (N2 == 256 || N2 == 512) {
+                if (sg.merged) return launch(k_pair_decimate_staged<N2, R, true>);
+            }
+            launch(k_pair_decimate_staged<N2, R>);
         }); });
         return;
     }
@@ -565,12 +590,12 @@ void launch_pair_step(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
 void launch_small_plan(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
 {
     const FftPlan &pl = r.pl, &ps2 = r.ps2;
-    const int n_pw = r.b.n_pw, by_col = r.step != PairStep::Tiles ? 1 : 0;
+    const int n_pw = r.b.n_pw, by_col = r.shares;
     const size_t rc_pts = (size_t)(pl.Nc / kDecD);
     float2 *g = bf.v, *vs = bf.v + rc_pts * (size_t)n_pw, *edges = bf.v + dec_edge_offset(pl, n_pw);      // G, V': [n_pw][R] each
     const auto *gain = ctx->dec_gain.as<const float>();
     const size_t lds = sizeof(float2) * 2 * kRow8Lds;
-    ProfScope ps(ctx, TDOA_K_INV_COL, 3.0 * 8.0 * (double)rc_pts * n_pw);
+    ProfScope ps(ctx, TDOA_K_INV_COL, 3.0 * 8.0 * (double)rc_pts * n_pw + dec_share_bytes(r));
     if (r.small_fused) {
         hipLaunchKernelGGL(k_small_rows_col_peak, dim3(n_pw), dim3(512), lds, bf.st, g, edges, bf.keys, bf.pw, ps2, pl.N2, by_col, r.lag_lo,
                            r.lag_hi, bf.lag_dump, bf.dump_scale, bf.dump_stride, gain, bf.oc);
@@ -652,7 +677,8 @@ static_assert((int)PairStep::Staged == TDOA_STEP_STAGED && (int)ColPass::Generic
 void route_info(const FmRoute &r, int32_t out[16])
 {
     const int32_t v[16] = {(int32_t)r.inv, (int32_t)r.step, (int32_t)r.col, (int32_t)r.row, r.fk, r.seg_pq, r.seg_quads, r.seg_pack3,
-                           r.fused_k1, r.once, r.small_fused, r.pruned, r.xcd_pairs > 0, r.dec_gp > 0, r.stg.folded, r.stg.blocked};
+                           r.fused_k1, r.once, r.small_fused, r.pruned, r.xcd_pairs > 0, r.dec_gp > 0, r.stg.folded,
+                           (r.stg.blocked ? TDOA_ROUTE_STG_BLOCKED_BIT : 0) | (r.stg.merged ? TDOA_ROUTE_STG_MERGED_BIT : 0)};
     std::memcpy(out, v, sizeof(v));
 }
 
@@ -748,6 +774,8 @@ int allow_big_lds(tdoa_ctx *ctx)
     for_ints<256, 512, 2048, 2560, 3072, 4096>([&](auto n2) {
         for_ints<2, 4, 8>([&](auto rv) {
             if (!rc) rc = set_lds(ctx, k_pair_decimate_staged<decltype(n2)::value, decltype(rv)::value>, all);
+            if constexpr (decltype(n2)::value == 256 || decltype(n2)::value == 512)
+                if (!rc) rc = set_lds(ctx, (k_pair_decimate_staged<decltype(n2)::value, decltype(rv)::value, true>), all);
         });
     });
 #endif

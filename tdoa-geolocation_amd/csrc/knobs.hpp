@@ -15,7 +15,7 @@ struct Knobs {
     bool force_generic = false, use_graph = true, short_lag = true, segment_form = true, segment_quads = true, decimate = true,
          k1_once = true, pow2_only = false, fused_k1 = true, dec_cols = true, dec_cols_always = false, dec_staged = true,
          small_fused = true, small_fused_always = false, stg_folded = true, stg_folded_always = false, stg_blocks = true,
-         seg_pack3 = true, memset_nodes = false, xcd_rows = true;
+         seg_pack3 = true, memset_nodes = false, xcd_rows = true, stg_merge = true;
     int zpad = 256, stg_loaders = 0, stg_rows = 0, stg_cw = 0, stg_bufs = 0, seg_chunks_override = 0, xcd_pair_mb = 48;
 };
 
@@ -54,6 +54,7 @@ const KnobVar kKnobVars[] = {
     off_if("TDOA_NO_STG_FOLDED", &Knobs::stg_folded),      // the staged walk always with a loader wave next to at most fifteen walks
     on_if("TDOA_STG_FOLDED_ALWAYS", &Knobs::stg_folded_always),      // ... folded wherever the blocked layout applies (tests)
     off_if("TDOA_NO_STG_BLOCKS", &Knobs::stg_blocks),      // the staged walk reads row-major spectra on every plan
+    off_if("TDOA_NO_STG_MERGE", &Knobs::stg_merge),        // the staged walk leaves every column's neighbour shares in X for the small plan's row pass
     // loader waves per workgroup of k_pair_decimate_staged, rows per phase, at most n walks (compute waves) per workgroup, phases
     // in the LDS ring (0: the library's choice)
     number("TDOA_DEC_STAGED_LOADERS", &Knobs::stg_loaders, [](int v) { return std::max(0, std::min(4, v)); }),

@@ -56,6 +56,8 @@ ROUTE_COL_PASS = ["none", "k1_256", "k1_512", "k1_two_sweep", "c256", "two_sweep
 ROUTE_ROW_PASS = ["none", "unpack_blocks", "unpack_in_place", "unpack_tiles", "hot", "generic"]
 ROUTE_FLAGS = ["seg_quads", "seg_pack3", "fused_k1", "once", "small_fused", "pruned", "xcd_pairs", "dec_gp", "stg_folded",
                "stg_blocked"]
+# the last slot is a bit field (TDOA_ROUTE_STG_BLOCKED_BIT, TDOA_ROUTE_STG_MERGED_BIT): last_route() reports each bit as a bool
+ROUTE_STG_BLOCKED_BIT, ROUTE_STG_MERGED_BIT = 1, 2
 
 
 class FastAnalysis(C.Structure):
@@ -545,12 +547,13 @@ class Context:
     def last_route(self):
         """the kernel forms of the last batch planned, or of the batch the replayed step graph captured
         (tdoa_debug_last_route): {"inverse", "pair_step", "col_pass", "row_pass": names; "fk", "seg_pq": numbers; the
-        ROUTE_FLAGS: bools}"""
+        ROUTE_FLAGS and "stg_merged" (the staged walk settles the neighbour shares inside a 64-column block): bools}"""
         info = (C.c_int32 * 16)()
         self._chk(self._L.tdoa_debug_last_route(self._h, info))
         out = dict(inverse=ROUTE_INVERSE[info[0]], pair_step=ROUTE_PAIR_STEP[info[1]], col_pass=ROUTE_COL_PASS[info[2]],
                    row_pass=ROUTE_ROW_PASS[info[3]], fk=info[4], seg_pq=info[5])
         out.update((name, bool(info[6 + k])) for k, name in enumerate(ROUTE_FLAGS))
+        out["stg_blocked"], out["stg_merged"] = bool(info[15] & ROUTE_STG_BLOCKED_BIT), bool(info[15] & ROUTE_STG_MERGED_BIT)
         return out
 
     def fm_stats(self, iq):
