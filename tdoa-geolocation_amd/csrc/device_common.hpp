@@ -116,18 +116,6 @@ __device__ __forceinline__ float2 unit_root_any(float num, float quarter_den, fl
     return unit_root_quarter(r * inv_quarter_den, (int)q, positive);
 }
 
-// 64-bit peak key: [ |v| bits : 32 ][ (0x7fffffff - rank) : 31 ][ sign : 1 ]
-// rank orders lags 0, +1, -1, +2, -2, ... so the larger key is the larger |v|,
-// then the smaller |lag|, then the positive lag (processor.go:596-611 order).
-__device__ __forceinline__ unsigned long long peak_key(float v, int lag)
-{
-    unsigned int mag = __float_as_uint(fabsf(v));
-    unsigned int a = lag < 0 ? (unsigned int)(-lag) : (unsigned int)lag;
-    unsigned int rank = 2u * a - (lag > 0 ? 1u : 0u);
-    unsigned int low = ((0x7fffffffu - rank) << 1) | (v < 0.0f ? 1u : 0u);
-    return ((unsigned long long)mag << 32) | low;
-}
-
 // Zero `n` 64-bit words.  Used instead of hipMemsetAsync inside the captured step: a kernel node like every other node
 // of the graph.
 __global__ void k_zero_u64(unsigned long long *p, size_t n)

@@ -14,6 +14,7 @@
 
 #include "device_common.hpp"
 #include "fft_stockham.hpp"
+#include "peak_key.hpp"
 #include "k1_single_look.hpp"
 #include "k1_discriminator.hpp"
 
@@ -1280,7 +1281,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SELF ? 1 : 
 }
 
 // short-lag form, second half: element sums over the N2/2 row-pair shares in a fixed order (four interleaved
-// partial sums, then ((s0 + s1) + (s2 + s3))), lag filter and K5.
+// partial sums, then ((s0 + s1) + (s2 + s3))), lag filter and K5 (peak_key.hpp).
 // part = V + pw_index * Nc: [RP][2][256 FK] float2, followed by the lag array lags[1024 FK] (float),
 // lags[li] = c[li - 512 FK] unscaled, kept for the sub-sample refinement.
 // grid (2 FK, n_pw): blockIdx.x = side * FK + k; 256 threads.
@@ -1315,22 +1316,9 @@ __global__ __launch_bounds__(256) void k_fused_reduce(float2 *V, unsigned long l
     for (int q = 0; q < 2; q++) {
         const int d = 2 * m + q;
         lags[d + 512 * FK] = vals[q];
-        if (d >= lag_lo && d <= lag_hi) {
-            if (vals[q] == vals[q]) {
-                const unsigned long long key = peak_key(vals[q], d);
-                best = key > best ? key : best;
-            }
-            if (lag_dump) lag_dump[d - lag_lo] = vals[q] * dump_scale;
-        }
+        k5_offer(best, vals[q], d, lag_lo, lag_hi, lag_dump, dump_scale);
     }
-    best = wave_max_u64(best);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long bb = red[0];
-        for (int w = 1; w < 4; w++) bb = red[w] > bb ? red[w] : bb;
-        if (bb) atomicMax(&keys[pw[blockIdx.y].out_index], bb);
-    }
+    k5_commit<4>(best, red, &pw[blockIdx.y].out_index, keys);
 }
 
 // refinement neighbours c[lag-1], c[lag], c[lag+1] from the lag array k_fused_reduce left behind
@@ -1342,20 +1330,8 @@ __global__ void k_refine_fused(const float2 *V, const unsigned long long *keys, 
     const int id = blockIdx.x * blockDim.x + threadIdx.x;   // one thread per pair-window
     if (id >= n_pw) return;
     const int slot = pw[id].out_index;
-    const unsigned long long k = keys[slot];
-    float r[3] = {0.0f, 0.0f, 0.0f};
-    if (k != 0 && (unsigned int)(k >> 32) != 0) {
-        const unsigned int rank = 0x7fffffffu - ((unsigned int)k >> 1);
-        const int lag = rank == 0 ? 0 : ((rank & 1u) ? (int)((rank + 1u) >> 1) : -(int)(rank >> 1));
-        const float *lags = reinterpret_cast<const float *>(V + (size_t)id * pl.Nc + (size_t)(pl.N2 / 2) * 2 * 256 * FK);
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-            const int li = lag - 1 + q + 512 * FK;
-            r[q] = li >= 0 && li < 1024 * FK ? lags[li] : 0.0f;
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 3; q++) raw[3 * (size_t)slot + q] = r[q];
+    const float *lags = reinterpret_cast<const float *>(V + (size_t)id * pl.Nc + (size_t)(pl.N2 / 2) * 2 * 256 * FK);
+    refine_from_lag_array(lags, 1024 * FK, 512 * FK, keys[slot], raw + 3 * (size_t)slot);
 }
 
 // ---------------------------------------------------------------------------
@@ -1364,6 +1340,38 @@ __global__ void k_refine_fused(const float2 *V, const unsigned long long *keys, 
 //   n2 in [0, NP)  (non-negative lags)  and  n2 in [N2 - NN, N2)  (negative lags), NP + NN <= 8.
 // ---------------------------------------------------------------------------
 constexpr int kPruneMax = 8;
+
+// The tail of the two pruned column kernels (256 threads, grid (N1/128, n_pw)): the four row groups' partial sums out of
+// LDS in a fixed order, output (o, column pair c) -> lags d .. d + 3, the single-look correction, K5 (peak_key.hpp).
+template <int NO>
+__device__ __forceinline__ void pruned_col_finish(const float4 (&part)[4][NO][64], int np, int nn, const FftPlan &pl,
+                                                  int lag_lo, int lag_hi, float *lag_dump, float dump_scale,
+                                                  const OnceCorr &oc, const OncePair &op, unsigned long long *red,
+                                                  const PWDesc &pwd, unsigned long long *keys)
+{
+    const int N2 = pl.N2, N1 = pl.N1;
+    unsigned long long best = 0;
+    for (int e = threadIdx.x; e < 64 * (np + nn); e += 256) {
+        const int o = e >> 6, c = e & 63;
+        float4 s = part[0][o][c];
+#pragma unroll
+        for (int gg = 1; gg < 4; gg++) {
+            const float4 q = part[gg][o][c];
+            s.x += q.x; s.y += q.y; s.z += q.z; s.w += q.w;
+        }
+        const int n2 = o < np ? o : N2 - nn + (o - np);
+        float vals[4] = {s.x, s.y, s.z, s.w};   // lags 2m .. 2m+3 with m = n2*N1 + n1
+        long long d = 2 * ((long long)n2 * N1 + (blockIdx.x << 7) + 2 * c);
+        if (d >= pl.Nc) d -= 2 * pl.Nc;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const long long dq = d + q;
+            if (oc.fin) vals[q] += once_correction(oc, op, dq);
+            k5_offer(best, vals[q], dq, lag_lo, lag_hi, lag_dump, dump_scale);
+        }
+    }
+    k5_commit<4>(best, red, &pwd.out_index, keys);
+}
 
 // grid (N1/128, n_pw), 256 threads: cp = t & 63 (column PAIR: n1 = 128*bx + 2cp, +1), g = t >> 6
 // (row group: rows g, g+4, ...); 16-byte loads -> 1 KB contiguous per row, 8 rows in flight per thread
@@ -1418,40 +1426,7 @@ __global__ __launch_bounds__(256) void k_inv_col_pruned_any(const float2 *V, uns
 #pragma unroll
     for (int o = 0; o < kPruneMax; o++) part[g][o][cp] = acc[o];
     __syncthreads();
-    unsigned long long best = 0;
-    for (int e = threadIdx.x; e < 64 * nout; e += 256) {
-        const int o = e >> 6, c = e & 63;
-        float4 s = part[0][o][c];
-#pragma unroll
-        for (int gg = 1; gg < 4; gg++) {
-            const float4 q = part[gg][o][c];
-            s.x += q.x; s.y += q.y; s.z += q.z; s.w += q.w;
-        }
-        const int n2 = o < np ? o : N2 - nn + (o - np);
-        float vals[4] = {s.x, s.y, s.z, s.w};   // lags 2m .. 2m+3 with m = n2*N1 + n1
-        long long d = 2 * ((long long)n2 * N1 + (blockIdx.x << 7) + 2 * c);
-        if (d >= pl.Nc) d -= 2 * pl.Nc;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const long long dq = d + q;
-            if (oc.fin) vals[q] += once_correction(oc, op, dq);
-            if (dq >= lag_lo && dq <= lag_hi) {
-                if (vals[q] == vals[q]) {
-                    const unsigned long long k = peak_key(vals[q], (int)dq);
-                    best = k > best ? k : best;
-                }
-                if (lag_dump) lag_dump[dq - lag_lo] = vals[q] * dump_scale;
-            }
-        }
-    }
-    best = wave_max_u64(best);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long bb = red[0];
-        for (int w = 1; w < 4; w++) bb = red[w] > bb ? red[w] : bb;
-        if (bb) atomicMax(&keys[pwd.out_index], bb);
-    }
+    pruned_col_finish(part, np, nn, pl, lag_lo, lag_hi, lag_dump, dump_scale, oc, op, red, pwd, keys);
 }
 
 // The same kernel for a compile-time output set (NP outputs 0..NP-1, NN outputs N2-NN..N2-1): the
@@ -1518,40 +1493,7 @@ __global__ __launch_bounds__(256) void k_inv_col_pruned(const float2 *V, unsigne
 #pragma unroll
     for (int o = 0; o < NOUT; o++) part[g][o][cp] = acc[o];
     __syncthreads();
-    unsigned long long best = 0;
-    for (int e = threadIdx.x; e < 64 * NOUT; e += 256) {
-        const int o = e >> 6, c = e & 63;
-        float4 s = part[0][o][c];
-#pragma unroll
-        for (int gg = 1; gg < 4; gg++) {
-            const float4 q = part[gg][o][c];
-            s.x += q.x; s.y += q.y; s.z += q.z; s.w += q.w;
-        }
-        const int n2 = o < NP ? o : N2 - NN + (o - NP);
-        float vals[4] = {s.x, s.y, s.z, s.w};   // lags 2m .. 2m+3 with m = n2*N1 + n1
-        long long d = 2 * ((long long)n2 * N1 + (blockIdx.x << 7) + 2 * c);
-        if (d >= pl.Nc) d -= 2 * pl.Nc;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const long long dq = d + q;
-            if (oc.fin) vals[q] += once_correction(oc, op, dq);
-            if (dq >= lag_lo && dq <= lag_hi) {
-                if (vals[q] == vals[q]) {
-                    const unsigned long long k = peak_key(vals[q], (int)dq);
-                    best = k > best ? k : best;
-                }
-                if (lag_dump) lag_dump[dq - lag_lo] = vals[q] * dump_scale;
-            }
-        }
-    }
-    best = wave_max_u64(best);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long bb = red[0];
-        for (int w = 1; w < 4; w++) bb = red[w] > bb ? red[w] : bb;
-        if (bb) atomicMax(&keys[pwd.out_index], bb);
-    }
+    pruned_col_finish(part, NP, NN, pl, lag_lo, lag_hi, lag_dump, dump_scale, oc, op, red, pwd, keys);
 }
 
 }  // namespace tdoa

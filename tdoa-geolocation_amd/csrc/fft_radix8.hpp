@@ -16,6 +16,7 @@
 #include "device_common.hpp"
 #include "fft_stockham.hpp"
 #include "fft_radix16.hpp"
+#include "peak_key.hpp"
 
 namespace tdoa {
 
@@ -598,6 +599,30 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4) TDOA_
     inv_rows_twiddle_store(va, vb, t, a, b, V + (size_t)blockIdx.y * pl.Nc, pl);
 }
 
+// single-look K1 in the small-plan K5 kernels: the additive terms of the lags d and d + 1 of an output row (positive: the row
+// holds the non-negative lags; rows of one sign: uniform)
+__device__ __forceinline__ void small_once_terms(const OnceCorr &oc, const OncePair &op, bool positive, long long d, float &term0,
+                                                 float &term1)
+{
+    const int di = (int)(d < -oc.k_max ? -oc.k_max : d > oc.k_max ? oc.k_max - 1 : d);      // (d + 1 stays on d's side)
+    const OnceSide &sd = positive ? op.pos : op.neg;
+    term0 = once_term(oc.edges, sd, op.a, di, oc.k_max);
+    term1 = once_term(oc.edges, sd, op.a, di + 1, oc.k_max);
+}
+
+// the two values of a small-plan column output (lags d: real part, d + 1: imaginary part) as K5 candidates: the window
+// divided out (gain[|m|] = 1 / w[m], m = packed lag index), the single-look terms added
+__device__ __forceinline__ void small_offer(unsigned long long &best, float2 acc, float term0, float term1, long long d,
+                                            const float *gain, int lag_lo, int lag_hi, float *lag_dump, float dump_scale)
+{
+    if (d + 1 >= lag_lo && d <= lag_hi) {
+        const long long m = d >> 1;
+        const float gg = gain[m < 0 ? -m : m];
+        k5_offer(best, acc.x * gg + term0, d, lag_lo, lag_hi, lag_dump, dump_scale);
+        k5_offer(best, acc.y * gg + term1, d + 1, lag_lo, lag_hi, lag_dump, dump_scale);
+    }
+}
+
 // column pass + K5 of the small plan (N2' = 16 or 32 rows of 4096): one thread per column n1 reads its N2' values
 // (coalesced 2 KB runs per row), evaluates the np + nn outputs n2 that can hold a searched lag as direct sums, divides the
 // window out (gain[|m|] = 1 / w[m], m = packed lag index) and keeps the best peak key.  Same lag bookkeeping as
@@ -644,10 +669,7 @@ __global__ __launch_bounds__(256) void k_small_col_peak(const float2 *V, unsigne
             const int n2 = o < np ? o : N2 - nn + (o - np);
             long long d = 2 * ((long long)n2 * N1 + n1);
             if (d >= pl.Nc) d -= 2 * pl.Nc;
-            const int di = (int)(d < -oc.k_max ? -oc.k_max : d > oc.k_max ? oc.k_max - 1 : d);      // (d + 1 stays on d's side)
-            const OnceSide &sd = o < np ? op.pos : op.neg;                                          // rows of one sign: uniform
-            term[o][0] = once_term(oc.edges, sd, op.a, di, oc.k_max);
-            term[o][1] = once_term(oc.edges, sd, op.a, di + 1, oc.k_max);
+            small_once_terms(oc, op, o < np, d, term[o][0], term[o][1]);
         }
     }
     for (int k0 = 0; k0 < N2; k0 += 8) {
@@ -692,32 +714,10 @@ __global__ __launch_bounds__(256) void k_small_col_peak(const float2 *V, unsigne
             const int n2 = o < np ? o : N2 - nn + (o - np);
             long long d = 2 * ((long long)n2 * N1 + n1);           // lags d (real part) and d + 1 (imaginary part)
             if (d >= pl.Nc) d -= 2 * pl.Nc;
-            if (d + 1 >= lag_lo && d <= lag_hi) {
-                const long long m = d >> 1;
-                const float gg = gain[m < 0 ? -m : m];
-                const float vals[2] = {acc[o].x * gg + term[o][0], acc[o].y * gg + term[o][1]};
-#pragma unroll
-                for (int q = 0; q < 2; q++) {
-                    const long long dq = d + q;
-                    if (dq >= lag_lo && dq <= lag_hi) {
-                        if (vals[q] == vals[q]) {
-                            const unsigned long long k = peak_key(vals[q], (int)dq);
-                            best = k > best ? k : best;
-                        }
-                        if (lag_dump) lag_dump[dq - lag_lo] = vals[q] * dump_scale;
-                    }
-                }
-            }
+            small_offer(best, acc[o], term[o][0], term[o][1], d, gain, lag_lo, lag_hi, lag_dump, dump_scale);
         }
     }
-    best = wave_max_u64(best);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long bb = red[0];
-        for (int w = 1; w < 4; w++) bb = red[w] > bb ? red[w] : bb;
-        if (bb) atomicMax(&keys[pwd.out_index], bb);
-    }
+    k5_commit<4>(best, red, &pwd.out_index, keys);
 }
 
 // k_inv_rows_plain_r8 + k_small_col_peak<3, 3> in ONE pass (round 5): V' -- 8 Nc/16 bytes written and read back per
@@ -840,38 +840,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2) TDOA_
             long long d = 2 * ((long long)n2 * N1 + n1);           // lags d (real part) and d + 1 (imaginary part)
             if (d >= pl.Nc) d -= 2 * pl.Nc;
             float term0 = 0.0f, term1 = 0.0f;
-            if (oc.fin) {
-                const int di = (int)(d < -oc.k_max ? -oc.k_max : d > oc.k_max ? oc.k_max - 1 : d);      // (d + 1 stays on d's side)
-                const OnceSide &sd = o < 3 ? op.pos : op.neg;
-                term0 = once_term(oc.edges, sd, op.a, di, oc.k_max);
-                term1 = once_term(oc.edges, sd, op.a, di + 1, oc.k_max);
-            }
-            if (d + 1 >= lag_lo && d <= lag_hi) {
-                const long long m = d >> 1;
-                const float gg = gain[m < 0 ? -m : m];
-                const float vals[2] = {acc[o][k].x * gg + term0, acc[o][k].y * gg + term1};
-#pragma unroll
-                for (int q = 0; q < 2; q++) {
-                    const long long dq = d + q;
-                    if (dq >= lag_lo && dq <= lag_hi) {
-                        if (vals[q] == vals[q]) {
-                            const unsigned long long key = peak_key(vals[q], (int)dq);
-                            best = key > best ? key : best;
-                        }
-                        if (lag_dump) lag_dump[dq - lag_lo] = vals[q] * dump_scale;
-                    }
-                }
-            }
+            if (oc.fin) small_once_terms(oc, op, o < 3, d, term0, term1);
+            small_offer(best, acc[o][k], term0, term1, d, gain, lag_lo, lag_hi, lag_dump, dump_scale);
         }
     }
-    best = wave_max_u64(best);
-    if ((t & 63) == 0) red[t >> 6] = best;
-    __syncthreads();
-    if (t == 0) {
-        unsigned long long bb = red[0];
-        for (int w = 1; w < 8; w++) bb = red[w] > bb ? red[w] : bb;
-        if (bb) atomicMax(&keys[pwd.out_index], bb);
-    }
+    k5_commit<8>(best, red, &pwd.out_index, keys);
 }
 
 // ---------------------------------------------------------------------------
@@ -1118,7 +1091,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4) TDOA_
 }
 
 // chunk sums in a fixed order -> lag array (kept for the sub-sample refinement: lags[li] = c[li - P], unscaled like the
-// keys, at float offset N2 * P of the pair-window's V row -- behind every chunk sum), lag filter, K5.
+// keys, at float offset N2 * P of the pair-window's V row -- behind every chunk sum), lag filter, K5 (peak_key.hpp).
 // mul = 4 N / 4096 brings the sums to the scale of the four-step form (decode multiplies by 1 / (4 N sqrt(len))).
 // grid (2 PQ + 1, n_pw), 256 threads.
 template <int PQ>
@@ -1140,18 +1113,8 @@ __global__ __launch_bounds__(256) void k_segments_reduce(float2 *V, unsigned lon
     const int dlag = li - P;
     if (live) lags[li] = v;
     unsigned long long best = 0;
-    if (live && dlag >= lag_lo && dlag <= lag_hi) {
-        if (v == v) best = peak_key(v, dlag);
-        if (lag_dump) lag_dump[dlag - lag_lo] = v * dump_scale;
-    }
-    best = wave_max_u64(best);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long bb = red[0];
-        for (int w = 1; w < 4; w++) bb = red[w] > bb ? red[w] : bb;
-        if (bb) atomicMax(&keys[pw[blockIdx.y].out_index], bb);
-    }
+    if (live) k5_offer(best, v, dlag, lag_lo, lag_hi, lag_dump, dump_scale);
+    k5_commit<4>(best, red, &pw[blockIdx.y].out_index, keys);
 }
 
 // refinement neighbours c[lag-1], c[lag], c[lag+1] from the lag array k_segments_reduce left behind (2P + 1 entries)
@@ -1163,20 +1126,8 @@ __global__ void k_refine_segments(const float2 *V, const unsigned long long *key
     const int id = blockIdx.x * blockDim.x + threadIdx.x;   // one thread per pair-window
     if (id >= n_pw) return;
     const int slot = pw[id].out_index;
-    const unsigned long long k = keys[slot];
-    float r[3] = {0.0f, 0.0f, 0.0f};
-    if (k != 0 && (unsigned int)(k >> 32) != 0) {
-        const unsigned int rank = 0x7fffffffu - ((unsigned int)k >> 1);
-        const int lag = rank == 0 ? 0 : ((rank & 1u) ? (int)((rank + 1u) >> 1) : -(int)(rank >> 1));
-        const float *lags = reinterpret_cast<const float *>(V + (size_t)id * pl.Nc) + (size_t)pl.N2 * P;
-#pragma unroll
-        for (int q = 0; q < 3; q++) {
-            const int li = lag - 1 + q + P;
-            r[q] = li >= 0 && li <= 2 * P ? lags[li] : 0.0f;
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 3; q++) raw[3 * (size_t)slot + q] = r[q];
+    const float *lags = reinterpret_cast<const float *>(V + (size_t)id * pl.Nc) + (size_t)pl.N2 * P;
+    refine_from_lag_array(lags, 2 * P + 1, P, keys[slot], raw + 3 * (size_t)slot);
 }
 
 }  // namespace tdoa

@@ -20,6 +20,7 @@
 #include "device_common.hpp"
 #include "k1_discriminator.hpp"
 #include "k1_single_look.hpp"
+#include "peak_key.hpp"
 
 namespace tdoa {
 
@@ -319,7 +320,7 @@ __global__ __launch_bounds__(256) void k_inv_row_pair(const PWDesc *pw, const fl
 // inverse column pass + K5 argmax.  After the length-N2 IFFT down a column,
 // element (n2, n1) is q[m], m = n2*N1 + n1.
 // lags 2m (real part) and 2m+1 (imag part), minus N when >= N/2.
-// Candidates with lag_lo <= lag <= lag_hi enter a 64-bit atomicMax key.
+// Candidates with lag_lo <= lag <= lag_hi enter a 64-bit atomicMax key (K5: peak_key.hpp).
 // grid: (N1 / C, n_pair_windows), dynamic LDS: 2 * N2 * C * 8 bytes
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_inv_col_peak(const float2 *V, unsigned long long *keys, const PWDesc *pw,
@@ -346,38 +347,12 @@ __global__ __launch_bounds__(256) void k_inv_col_peak(const float2 *V, unsigned 
         long long d0 = 2 * m;
         if (d0 >= Nc) d0 -= 2 * Nc;
         long long d1 = d0 + 1;
-        if (d0 >= lag_lo && d0 <= lag_hi) {
-            if (v.x == v.x) {
-                unsigned long long k = peak_key(v.x, (int)d0);
-                best = k > best ? k : best;
-            }
-            if (lag_dump) lag_dump[d0 - lag_lo] = v.x * dump_scale;
-        }
-        if (d1 >= lag_lo && d1 <= lag_hi) {
-            if (v.y == v.y) {
-                unsigned long long k = peak_key(v.y, (int)d1);
-                best = k > best ? k : best;
-            }
-            if (lag_dump) lag_dump[d1 - lag_lo] = v.y * dump_scale;
-        }
+        k5_offer(best, v.x, d0, lag_lo, lag_hi, lag_dump, dump_scale);
+        k5_offer(best, v.y, d1, lag_lo, lag_hi, lag_dump, dump_scale);
     }
-    best = wave_max_u64(best);
     __shared__ unsigned long long red[4];
-    int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-    if (lane == 0) red[wid] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long b = red[0];
-        for (int w = 1; w < (int)(blockDim.x / kWave); w++) b = red[w] > b ? red[w] : b;
-        if (b) atomicMax(&keys[pw[blockIdx.y].out_index], b);
-    }
+    k5_commit<4>(best, red, &pw[blockIdx.y].out_index, keys);
 }
-
-struct PeakOut {      // mirrors tdoa_peak
-    int32_t lag;
-    float abs_corr;
-    double corr;
-};
 
 // decode keys -> peaks; scale = 1 / (4 N sqrt(len_a)); slot_gain (single-look K1, k1_single_look.hpp): the pair-window's
 // g_t g_s, published by the K5 kernel that built the key (nullptr: the values were normalised before the transforms)
@@ -386,24 +361,7 @@ __global__ void k_decode_peaks(const unsigned long long *keys, const double *sca
 {
     int id = blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= n) return;
-    unsigned long long k = keys[id];
-    unsigned int mag = (unsigned int)(k >> 32), low = (unsigned int)k;
-    PeakOut p;
-    if (k == 0 || mag == 0) {
-        p.lag = 0;
-        p.abs_corr = 0.0f;
-        p.corr = 0.0;
-    } else {
-        unsigned int rank = 0x7fffffffu - (low >> 1);
-        int lag = rank == 0 ? 0 : ((rank & 1u) ? (int)((rank + 1u) >> 1) : -(int)(rank >> 1));
-        double v = (double)__uint_as_float(mag) * scales[id];
-        if (slot_gain) v *= slot_gain[id];
-        if (low & 1u) v = -v;
-        p.lag = lag;
-        p.corr = v;
-        p.abs_corr = (float)fabs(v);
-    }
-    out[id] = p;
+    out[id] = decode_peak(keys[id], scales[id], slot_gain ? slot_gain + id : nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -423,12 +381,11 @@ __global__ __launch_bounds__(64) void k_refine_peaks(const float2 *V, const unsi
 {
     const int slot = pw[blockIdx.x].out_index;
     const unsigned long long k = keys[slot];
-    if (k == 0 || (unsigned int)(k >> 32) == 0) {
+    if (!key_live(k)) {
         if (threadIdx.x < 3) raw[3 * (size_t)slot + threadIdx.x] = 0.0f;
         return;
     }
-    const unsigned int rank = 0x7fffffffu - ((unsigned int)k >> 1);
-    const int lag = rank == 0 ? 0 : ((rank & 1u) ? (int)((rank + 1u) >> 1) : -(int)(rank >> 1));
+    const int lag = key_lag(k);
     const float2 *in = V + (size_t)blockIdx.x * pl.Nc;
     const float inv2 = 2.0f / (float)pl.N2;
     for (int q = 0; q < 3; q++) {
@@ -475,12 +432,10 @@ __global__ void k_decode_fine(const unsigned long long *keys, const double *scal
     f.y[0] = f.y[1] = f.y[2] = 0.0f;
     f.reserved = 0;
     int lag = 0;
-    if (k != 0 && (unsigned int)(k >> 32) != 0) {
-        const unsigned int low = (unsigned int)k;
-        const unsigned int rank = 0x7fffffffu - (low >> 1);
-        lag = rank == 0 ? 0 : ((rank & 1u) ? (int)((rank + 1u) >> 1) : -(int)(rank >> 1));
+    if (key_live(k)) {
+        lag = key_lag(k);
         const double sc0 = slot_gain ? scales[id] * slot_gain[id] : scales[id];
-        const double sc = (low & 1u) ? -sc0 : sc0;
+        const double sc = key_negative(k) ? -sc0 : sc0;
         const double ym = (double)raw[3 * (size_t)id] * sc, y0 = (double)raw[3 * (size_t)id + 1] * sc,
                      yp = (double)raw[3 * (size_t)id + 2] * sc;
         const double den = ym - 2.0 * y0 + yp;

@@ -2,7 +2,8 @@
 // tdoa_process_lags): the K strongest separate peaks, and the surfaces themselves in the caller's layout.
 //
 // The surfaces are the lag arrays the K5 kernels dump while they search (lag d of the batch's pair-window i at
-// dump[i * stride + d - lag_lo]): raw, unscaled values, bit for bit the floats the peak keys were built from.
+// dump[i * stride + d - lag_lo]): raw, unscaled values, bit for bit the floats the peak keys were built from (one step
+// offers a value to the key and writes it to the surface: k5_offer, peak_key.hpp).
 //
 // Selection rule (include/tdoa_mi355x.h, tdoa_process_peaks):
 //   peak 1 is tdoa_process's peak, decoded from the same key;
@@ -19,18 +20,12 @@
 
 #include "device_common.hpp"
 #include "fft_stockham.hpp"
+#include "peak_key.hpp"
 
 namespace tdoa {
 
 constexpr int kSelThreads = 512;
 constexpr int kSelMaxK = 16;             // tdoa_process_peaks: k in 1 .. kSelMaxK
-
-// the lag of a peak_key
-__device__ __forceinline__ int key_lag(unsigned long long k)
-{
-    const unsigned int rank = 0x7fffffffu - ((unsigned int)k >> 1);
-    return rank == 0 ? 0 : ((rank & 1u) ? (int)((rank + 1u) >> 1) : -(int)(rank >> 1));
-}
 
 // key of index l of an n-lag surface when l is a candidate, else 0 (NaN and 0 never are; a NaN neighbour fails the
 // comparison, so its neighbours are not local maxima either)
@@ -75,17 +70,10 @@ __global__ __launch_bounds__(kSelThreads) void k_select_peaks(const float *surf,
             for (int j = 1; j < kSelThreads / kWave; j++) b = red[j] > b ? red[j] : b;
             __syncthreads();                 // red is written again next round
         }
-        if ((unsigned int)(b >> 32) == 0u) break;            // no key, or |c| = 0 everywhere: nothing qualifies
+        if (!key_live(b)) break;                             // no key, or |c| = 0 everywhere: nothing qualifies
         const int lag = key_lag(b);
         if (t == 0) {
-            double v = (double)__uint_as_float((unsigned int)(b >> 32)) * scales[slot];
-            if (slot_gain) v *= slot_gain[slot];
-            if ((unsigned int)b & 1u) v = -v;
-            PeakOut p;
-            p.lag = lag;
-            p.corr = v;
-            p.abs_corr = (float)fabs(v);
-            out[(size_t)slot * k + r] = p;
+            out[(size_t)slot * k + r] = decode_peak(b, scales[slot], slot_gain ? slot_gain + slot : nullptr);
             chosen[r] = lag;
         }
         got = r + 1;

@@ -15,6 +15,7 @@
 
 #include "device_common.hpp"
 #include "fft_stockham.hpp"
+#include "peak_key.hpp"
 #include "peak_select.hpp"
 
 namespace tdoa {
@@ -93,20 +94,11 @@ __global__ __launch_bounds__(kStackThreads) void k_stack_finish(const long long 
         if (l < n) {
             const float v = (float)stack_value(q[l], root);
             o[l] = v;
-            if (v == v) {
-                const unsigned long long k = peak_key(v, l + lag_lo);
-                best = k > best ? k : best;
-            }
+            k5_max(best, v, l + lag_lo);
         }
     }
-    best = wave_max_u64(best);
-    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int j = 1; j < kStackThreads / kWave; j++) best = red[j] > best ? red[j] : best;
-        if (best) atomicMax(keys + blockIdx.x, best);
-    }
+    const int32_t slot = blockIdx.x;
+    k5_commit<kStackThreads / kWave>(best, red, &slot, keys);
 }
 
 // One thread per stack-pair.  The records k_select_peaks wrote carry (float)C as corr: corr becomes the double C[lag]
@@ -137,7 +129,7 @@ __global__ void k_stack_fine(const long long *Q, int n, int lag_lo, int n_pairs,
     f.y[0] = f.y[1] = f.y[2] = 0.0f;
     f.reserved = 0;
     const unsigned long long key = keys[id];
-    if (key != 0 && (unsigned int)(key >> 32) != 0) {
+    if (key_live(key)) {
         const int lag = key_lag(key), l = lag - lag_lo;
         const double y0r = stack_value(q[l], root);
         const double sg = y0r < 0.0 ? -1.0 : 1.0;
