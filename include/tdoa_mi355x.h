@@ -321,7 +321,8 @@ int tdoa_fm_xcorr_lags_u8(tdoa_ctx *ctx, const uint8_t *iq1, size_t n1, const ui
                           int max_lag, double *lags_out /* [2*max_lag-1] */);
 
 /* tests only: run the selection kernel of tdoa_process_peaks on a caller's raw surface (n_lags values for the lags
- * lag_lo, lag_lo + 1, ...) with scale 1; peak 1 comes from the surface like the others */
+ * lag_lo, lag_lo + 1, ...) with scale 1; peak 1 comes from the surface like the others.  A peak key orders lags by
+ * 2 |lag| in 31 bits: every lag of the surface must lie in -(2^30 - 1) .. 2^30 - 1, TDOA_ERR_INVALID otherwise */
 int tdoa_debug_select_peaks(tdoa_ctx *ctx, const float *surface, int n_lags, int lag_lo, int k, int min_separation,
                             tdoa_peak *peaks, int32_t *count);
 /* tests only: run the any-size fallback kernels even where a hot-size kernel exists */

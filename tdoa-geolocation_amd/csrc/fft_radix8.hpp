@@ -1093,15 +1093,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4) TDOA_
 // chunk sums in a fixed order -> lag array (kept for the sub-sample refinement: lags[li] = c[li - P], unscaled like the
 // keys, at float offset N2 * P of the pair-window's V row -- behind every chunk sum), lag filter, K5 (peak_key.hpp).
 // mul = 4 N / 4096 brings the sums to the scale of the four-step form (decode multiplies by 1 / (4 N sqrt(len))).
+// A pair-window with a station-window of equal codes (fm_stats_flat) is 0 at every lag: both segment kernels transform
+// it next to another station-window, whose rounding error (1e-7 of ITS peak) would otherwise be the surface.
+// sw: the windows the statistics were taken over (FmBufs::sw_stats where K1 runs over other windows than the transforms).
 // grid (2 PQ + 1, n_pw), 256 threads.
 template <int PQ>
-__global__ __launch_bounds__(256) void k_segments_reduce(float2 *V, unsigned long long *keys, const PWDesc *pw, FftPlan pl,
-                                                        int n_chunks, float mul, int lag_lo, int lag_hi, float *lag_dump,
-                                                        float dump_scale, size_t dump_stride)
+__global__ __launch_bounds__(256) void k_segments_reduce(float2 *V, unsigned long long *keys, const PWDesc *pw, const SWDesc *sw,
+                                                        const FmStats *stats, FftPlan pl, int n_chunks, float mul, int lag_lo,
+                                                        int lag_hi, float *lag_dump, float dump_scale, size_t dump_stride)
 {
     if (lag_dump) lag_dump += (size_t)blockIdx.y * dump_stride;
     constexpr int P = 256 * PQ;
     __shared__ unsigned long long red[4];
+    const PWDesc d = pw[blockIdx.y];
+    const bool flat = fm_stats_flat(stats[d.sw_a], sw[d.sw_a].len) || fm_stats_flat(stats[d.sw_b], sw[d.sw_b].len);
     float *base = reinterpret_cast<float *>(V + (size_t)blockIdx.y * pl.Nc);
     float *lags = reinterpret_cast<float *>(V + (size_t)blockIdx.y * pl.Nc) + (size_t)pl.N2 * P;
     const int li = blockIdx.x * 256 + threadIdx.x;            // lag index d + P, valid up to 2 P
@@ -1109,7 +1114,7 @@ __global__ __launch_bounds__(256) void k_segments_reduce(float2 *V, unsigned lon
     float s = 0.0f;
     if (live)
         for (int ch = 0; ch < n_chunks; ch++) s += base[(size_t)ch * (2 * P + 8) + li];
-    const float v = s * mul;
+    const float v = flat ? 0.0f : s * mul;
     const int dlag = li - P;
     if (live) lags[li] = v;
     unsigned long long best = 0;

@@ -524,8 +524,9 @@ void launch_segments(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
         });
         {
             ProfScope ps(ctx, TDOA_K_INV_COL, 4.0 * 512.0 * PQ * (chunks + 1) * n_pw);
-            hipLaunchKernelGGL(k_segments_reduce<PQ>, dim3(2 * PQ + 1, n_pw), dim3(256), 0, bf.st, bf.v, bf.keys, bf.pw, pl, chunks, mul,
-                               r.lag_lo, r.lag_hi, bf.lag_dump, bf.dump_scale, bf.dump_stride);
+            hipLaunchKernelGGL(k_segments_reduce<PQ>, dim3(2 * PQ + 1, n_pw), dim3(256), 0, bf.st, bf.v, bf.keys, bf.pw,
+                               bf.sw_stats ? bf.sw_stats : bf.sw, bf.stats, pl,
+                               chunks, mul, r.lag_lo, r.lag_hi, bf.lag_dump, bf.dump_scale, bf.dump_stride);
         }
         if (r.b.fine) {
             ctx->prof_last = -1;          // unscoped launch: the next scope records its own start

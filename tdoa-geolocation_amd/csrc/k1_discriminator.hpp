@@ -552,6 +552,19 @@ __global__ __launch_bounds__(256) void k_k1_smooth(const SWDesc *sw, const int *
     k1_block_stats_256(s1, s2, &acc[blockIdx.y]);
 }
 
+// A station-window whose codes are all equal (a constant capture) or that has no samples: each of its samples normalises
+// to 0, so its correlation with anything is 0 at every lag.  A kernel that transforms two station-windows as one complex
+// frame gets that 0 only up to the other one's rounding error and has to put it there itself.  Exact, from the integer
+// sums: len S2 = S1^2 holds for equal codes only (Cauchy-Schwarz); len < 2^31, S2 < 2^96, |S1| < 2^63.  `len` is the
+// length the sums were taken over -- the K1 window, which under TDOA_LAGS_GO is longer than the transformed one.
+// Uniform arguments keep the whole test on the scalar unit.
+__device__ __forceinline__ bool fm_stats_flat(const FmStats &st, int len)
+{
+    const unsigned long long a = st.s1 < 0 ? 0ull - (unsigned long long)st.s1 : (unsigned long long)st.s1;
+    const unsigned __int128 s2 = ((unsigned __int128)st.s2_hi << 64) | st.s2_lo;
+    return len <= 0 || s2 * (unsigned __int128)(unsigned int)len == (unsigned __int128)a * a;
+}
+
 // mean and scale of every station-window from its exact sums, in f64:
 // S2 as (double)(S2 >> 32) * 2^32 + (double)(S2 & 0xffffffff), var = (S2 - S1^2/L) / L
 __global__ void k_fm_stats_final(const SWDesc *sw, const StatsPartial *acc, FmStats *stats, int n_sw)

@@ -18,7 +18,8 @@ struct PeakOut {      // mirrors tdoa_peak
 
 // 64-bit peak key: [ |v| bits : 32 ][ (0x7fffffff - rank) : 31 ][ sign : 1 ]
 // rank orders lags 0, +1, -1, +2, -2, ... so the larger key is the larger |v|,
-// then the smaller |lag|, then the positive lag (processor.go:596-611 order).
+// then the smaller |lag|, then the positive lag (processor.go:596-611 order).  rank <= 2 |lag| has 31 bits:
+// |lag| <= 2^30 - 1 (every search range is far inside; tdoa_debug_select_peaks refuses a surface that is not).
 __device__ __forceinline__ unsigned long long peak_key(float v, int lag)
 {
     unsigned int mag = __float_as_uint(fabsf(v));

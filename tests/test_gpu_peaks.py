@@ -31,6 +31,13 @@ def _same_bytes(a, b):
     return a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
+def _record_is_surface_max(rec, s, ml):
+    """no tolerance: float32(rec.corr) is s[rec.lag + ml - 1], sign included, rec.abs_corr its magnitude, that magnitude is
+    max |s|, rec.lag the first lag in the key's order that holds it; max |s| = 0: the zero record (tdoa_amd.peaks)"""
+    from tdoa_amd.peaks import record_is_surface_max
+    return record_is_surface_max(rec, s, ml)
+
+
 def _check_rule(got, cnt, want_surface, ml):
     """the kernel's records against the rule on the oracle's float64 surface: lags equal while the oracle's order is
     unambiguous (consecutive candidates more than 1e-5 apart, relative), magnitudes within 2e-6 of the peak"""
@@ -76,6 +83,11 @@ def _route_case(oracle, c, caps, wl, wpb, ml, check_units=2, **flags):
     idx = base["lag"].astype(np.int64) + ml - 1
     at = np.take_along_axis(lags, idx[..., None], axis=2)[..., 0]
     assert np.allclose(at, base["corr"], rtol=1e-6, atol=0)
+    # ... and, with no tolerance, every record is its own surface's maximum (the key's order decides ties)
+    for wid in range(w):
+        for q in range(p):
+            _record_is_surface_max(base[wid, q], lags[wid, q], ml)
+            _record_is_surface_max(pk[wid, q, 0], lags[wid, q], ml)
     n = len(caps)
     pairs = [(i, j) for i in range(n) for j in range(i + 1, n)]
     rng = np.random.default_rng(len(caps) * 1000 + wl)
@@ -198,7 +210,9 @@ def test_two_paths(oracle):
 
 def test_selection_rule_edges():
     """tdoa_debug_select_peaks against the float64 rule: a plateau, peaks at either end, NaN, all zero, fewer candidates
-    than k, and random surfaces with every k and a few separations"""
+    than k, and random surfaces with every k and a few separations; then the key at its limits: the rank of a lag is 2 |lag|
+    in 31 bits, so the entry point takes lags up to +-(2^30 - 1) (TDOA_ERR_INVALID beyond), ties between +L and -L there,
+    -0.0 next to 0.0, a lone negative value at the last index, and +d against -d with opposite signs"""
     import tdoa_amd
     from tdoa_amd.peaks import select_peaks
 
@@ -223,6 +237,46 @@ def test_selection_rule_edges():
         assert cnt == 0 and not got["lag"].any() and not got["abs_corr"].any()
         got, cnt = run(c, [0.0, 1.0, 0.0, -2.0, 0.0], 0, 8, 1)
         assert cnt == 2 and got[0]["corr"] == -2.0
+        far = 2 ** 30 - 1                                               # the largest |lag| a key holds
+        s = np.zeros(far - (far - 6) + 1)
+        s[[0, 3, 6]] = [2.0, -5.0, 1.0]                                 # lags far - 6 .. far, the last one a candidate
+        got, cnt = run(c, s, far - 6, 8, 1)
+        assert [int(x) for x in got["lag"][:cnt]] == [far - 3, far - 6, far]
+        got, cnt = run(c, s[::-1], -far, 8, 1)
+        assert [int(x) for x in got["lag"][:cnt]] == [-far + 3, -far + 6, -far]
+        got, cnt = run(c, [4.0, 1.0, 4.0], far - 2, 2, 1)               # a tie inside one sign: the smaller |lag|
+        assert int(got[0]["lag"]) == far - 2
+        got, cnt = run(c, [4.0, 1.0, 4.0], -far, 2, 1)
+        assert int(got[0]["lag"]) == -far + 2
+        n = 2 ** 30
+        for lag_lo in (-far, n - 5):                                    # lag_lo = -(2^30 - 1) and lag_lo = 2^30 - n
+            got, cnt = run(c, np.linspace(1.0, 2.0, 5), lag_lo, 4, 1)
+            assert cnt == 1 and int(got[0]["lag"]) == lag_lo + 4
+        # +L against -L: a surface that held both far ends would be 2^31 - 1 floats; the tie on one of 2^21 + 1 floats instead
+        # (the far ends themselves: each sign on its own, above)
+        L = 1 << 20
+        s = np.zeros(2 * L + 1, dtype=np.float32)
+        s[0], s[-1] = -3.0, 3.0
+        got, cnt = run(c, s, -L, 2, 1)
+        assert [(int(g["lag"]), float(g["corr"])) for g in got[:cnt]] == [(L, 3.0), (-L, -3.0)]
+        s[0], s[-1] = 3.0, -3.0
+        got, cnt = run(c, s, -L, 2, 1)
+        assert [(int(g["lag"]), float(g["corr"])) for g in got[:cnt]] == [(L, -3.0), (-L, 3.0)]
+        got, cnt = run(c, np.array([-0.0, 0.0, -0.0, 0.0], dtype=np.float32), -2, 8, 1)
+        assert cnt == 0 and not got["lag"].any() and not got["corr"].any()
+        got, cnt = run(c, [0.0, 0.0, 0.0, 0.0, -1.5], -2, 8, 1)          # the only value: negative, at the last index
+        assert cnt == 1 and (int(got[0]["lag"]), float(got[0]["corr"]), float(got[0]["abs_corr"])) == (2, -1.5, 1.5)
+        for neg_first in (True, False):                                  # equal magnitude at -d and +d, opposite signs
+            v = 2.5 if neg_first else -2.5
+            got, cnt = run(c, [0.0, -v, 0.0, 0.0, 0.0, 0.0, 0.0, v, 0.0], -4, 2, 1)
+            assert cnt == 2 and (int(got[0]["lag"]), float(got[0]["corr"])) == (3, v)
+            assert (int(got[1]["lag"]), float(got[1]["corr"])) == (-3, -v)
+        for bad_lo, n_bad in [(-far - 1, 3), (far - 1, 3), (far + 1, 1), (-2 ** 31, 3), (2 ** 31 - 1, 1)]:
+            with pytest.raises(tdoa_amd.TdoaError) as e:                # a lag the key cannot hold
+                c.debug_select_peaks(np.ones(n_bad), bad_lo, 4, 1)
+            assert e.value.status == 1
+        got, cnt = run(c, [1.0, 2.0, 3.0], far - 2, 4, 1)               # ... and the last one it can
+        assert cnt == 1 and int(got[0]["lag"]) == far
         rng = np.random.default_rng(9)
         for trial in range(24):
             n = int(rng.integers(1, 50000))

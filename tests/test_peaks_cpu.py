@@ -80,3 +80,44 @@ def test_rule_separation_and_greedy_order():
     for lag, v in got:                                                 # each is a local maximum holding its own value
         i = lag + 2000
         assert c[i] == v and abs(v) >= abs(c[i - 1]) and abs(v) >= abs(c[i + 1])
+
+
+def _rec(lag, corr):
+    r = np.zeros((), dtype=np.dtype([("lag", np.int32), ("abs_corr", np.float32), ("corr", np.float64)]))
+    r["lag"], r["corr"], r["abs_corr"] = lag, corr, np.float32(abs(corr))
+    return r
+
+
+def test_surface_max_and_the_record_check_on_hand_made_surfaces():
+    """surface_max / record_is_surface_max (what the GPU tests hold every pair-window's record to): ties in the key's order, a
+    negative winner, all zero, NaN, and every way a record can be wrong"""
+    from tdoa_amd.peaks import record_is_surface_max, surface_max
+    s = np.array([0.5, -3.0, 1.0, 0.0, 2.0, 3.0, -0.25], dtype=np.float32)         # lags -3 .. 3, ml = 4
+    T, v = surface_max(s, -3)
+    assert T == [2, -2] and v == np.float32(3.0)                                   # equal |lag|: the positive lag first
+    assert record_is_surface_max(_rec(2, 3.0), s, 4) == [2, -2]
+    for bad in [_rec(-2, -3.0), _rec(2, -3.0), _rec(1, 2.0), _rec(2, 3.0000002), _rec(0, 0.0), _rec(4, 3.0)]:
+        with pytest.raises(AssertionError):
+            record_is_surface_max(bad, s, 4)
+    wrong_abs = _rec(2, 3.0)
+    wrong_abs["abs_corr"] = 2.5
+    with pytest.raises(AssertionError):
+        record_is_surface_max(wrong_abs, s, 4)
+    T, v = surface_max([1.0, 0.0, 0.0, 0.0, -1.0, 0.0, 1.0], 0)                    # smaller |lag| before the sign of the lag
+    assert T == [0, 4, 6] and v == np.float32(1.0)
+    n = np.array([0.5, 1.0, -7.0], dtype=np.float32)                               # a negative winner at the last lag
+    assert surface_max(n, -1) == ([1], np.float32(-7.0))
+    assert record_is_surface_max(_rec(1, -7.0), n, 2) == [1]
+    with pytest.raises(AssertionError):
+        record_is_surface_max(_rec(1, 7.0), n, 2)                                  # the sign belongs to the record
+    # the double behind the record rounds to the surface's float: equal after rounding, not before
+    third = np.array([0.0, np.float32(1.0 / 3.0), 0.0], dtype=np.float32)
+    assert record_is_surface_max(_rec(0, float(third[1]) * (1 + 2.0 ** -30)), third, 2) == [0]
+    z = np.array([0.0, -0.0, 0.0], dtype=np.float32)                               # all zero: only the zero record
+    assert surface_max(z, -1)[0] == [0, 1, -1] and surface_max(z, -1)[1] == 0
+    record_is_surface_max(_rec(0, 0.0), z, 2)
+    for bad in [_rec(1, 0.0), _rec(0, 1e-30)]:
+        with pytest.raises(AssertionError):
+            record_is_surface_max(bad, z, 2)
+    assert surface_max([np.nan, 2.0, np.nan], 5) == ([6], np.float32(2.0))         # NaN never counts
+    assert surface_max([np.nan, np.nan], 0) == ([], np.float32(0.0)) and surface_max([], 0)[0] == []
