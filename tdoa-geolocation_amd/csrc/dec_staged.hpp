@@ -1,7 +1,7 @@
 // dec_staged.hpp -- the column walk of the decimated pair step with the stations' rows STAGED IN LDS (round 5).
 //
-// k_pair_decimate_cols (dec_stream.hpp) gives every pair-window its own walk: each walk loads the rows of its two stations
-// itself, so a window of S stations and P pairs asks for 2 P / S = S - 1 times its spectra and leaves it to the caches to
+// The walk itself is dec_walk.hpp.  k_pair_decimate_cols (dec_stream.hpp) gives every pair-window its own: each loads the rows
+// of its two stations itself, so a window of S stations and P pairs asks for 2 P / S = S - 1 times its spectra and leaves it to the caches to
 // serve the repeats.  They do so poorly: the walks that share a station drift apart by more than the L2 holds, and the
 // memory-side counters showed 2.1 x (8 stations, BASELINE config 4) and 3.2 x (16 stations, config 5) the compulsory bytes
 // coming through the fabric.  Here one workgroup owns 64 columns (and their 64 partner columns) of ONE window
@@ -10,7 +10,7 @@
 //     (global_load_lds_dwordx4: one wave-instruction = the 512 bytes of a station's row piece + the 512 bytes of its partner
 //     row piece, no VGPR in between), R rows per phase into a ring of two (or more) phases -- a phase's bytes are asked for while
 //     the phase before it is read;
-//   * every COMPUTE wave walks one pair: the same register stencil as k_pair_decimate_cols (twelve accumulators per walk, K3 on
+//   * every COMPUTE wave walks one pair: the register stencil of dec_walk.hpp (twelve accumulators per walk, K3 on
 //     packed pairs), its four operands per row four ds_read_b64, the row's taps through the scalar cache into SGPR pairs;
 //   * one raw s_barrier per phase; the loader waits with a counted vmcnt (later phases stay in flight across the barrier).
 // (Or no loader wave at all -- the FOLDED form below: sixteen walks, the last waves each bring one station -- where that makes
@@ -39,7 +39,7 @@
 // grid: 8 x ceil(windows 32 / 8) x groups workgroups (1-D), 64 (compute waves + 1) threads; dynamic LDS nb x R x slots KB.
 #pragma once
 
-#include "dec_stream.hpp"
+#include "dec_walk.hpp"
 
 namespace tdoa {
 
@@ -112,10 +112,8 @@ __attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kSt
                                                                              int n_items, int P, int S, int n_cw, int n_groups, int nb,
                                                                              long long u_stride, int blocked)
 {
-    constexpr int N2 = N2_, N1 = 4096, C = kDecCentre, SS = kDecSteps, R = R_;
-    constexpr int NG = N2 / 16;
-    constexpr bool POW2 = (N2 & (N2 - 1)) == 0;
-    static_assert(NG >= 2 * C + 2 && 16 % R == 0 && N2 % R == 0 && R % 2 == 0, "ring and loop geometry");
+    constexpr int N2 = N2_, N1 = 4096, SS = kDecSteps, R = R_;
+    static_assert(16 % R == 0 && N2 % R == 0 && R % 2 == 0, "ring and loop geometry");
     // the ring: [phase slot][station][row of the phase][fwd | partner][64] float2 -- the row index innermost, so that a walk's
     // four operand addresses change once per PHASE (one v_add each) and the row inside the phase is an immediate offset
     extern __shared__ __attribute__((aligned(16))) unsigned char stage_raw[];
@@ -307,7 +305,7 @@ __attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kSt
         return;
     }
 
-    // ---- compute: the walk of k_pair_decimate_cols for pair-window pwu, operands from LDS -----------------------------------
+    // ---- compute: the walk of dec_walk.hpp for pair-window pwu, operands from LDS ----------------------------------------------
     const int pidx = gd->pair[wave];
     const unsigned int pwu = (unsigned int)(w * P + pidx);
     const PWDesc d = wpw[pidx];
@@ -315,69 +313,22 @@ __attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kSt
     const int k1 = cb * 64 + lane, km = N1 - 1 - k1;
     const float2 *Ua = U + (size_t)d.sw_a * (size_t)u_stride, *Ub = U + (size_t)d.sw_b * (size_t)u_stride;
     const float invNc = 1.0f / (float)pl.Nc;
-    auto w_n = [&](float num) {
-        if constexpr (POW2) return unit_root(num, invNc, false);
-        else return unit_root_any(num, 0.5f * (float)pl.Nc, 2.0f * invNc, false);
-    };
-    const size_t rc = (size_t)(pl.Nc / kDecD);
-    float2 *g_top = G + (size_t)pwu * rc + k1, *g_bot = G + (size_t)pwu * rc + km;
-    float2 *x_top = X + (size_t)pwu * kDecShareRows * N1 + k1, *x_bot = X + (size_t)pwu * kDecShareRows * N1 + km;
-
-    float2 at[SS], ab[SS];
-#pragma unroll
-    for (int s = 0; s < SS; s++) at[s] = ab[s] = make_float2(0.0f, 0.0f);
-    typedef float v2f __attribute__((ext_vector_type(2)));
+    typedef WalkStencil<N2, true> Walk;
+    constexpr int C = Walk::C, NG = Walk::NG;
+    Walk st;
+    st.start(G, X, pl, pwu, k1);
     // The taps of a row's phase are the same twelve numbers for every lane AND every wave: they are read through the scalar
     // cache into SGPR pairs (s_load_dwordx8 + x4 at a wave-uniform address, issued next to the rows' LDS reads) and enter the
     // multiply-adds as the scalar operand (v_pk_fma_f32 v, v, s[lo:hi] with op_sel picking the half).  From LDS they were three
     // ds_read_b128 per row and wave -- 3 KB of LDS traffic beside the 2 KB of operands, the LDS pipe at ~95 % of the walks'
     // issue time (cfg4 pair step 3.45 -> 3.08 ms, cfg5 83.7 -> 79.2).  Table: [16 phases][16 steps] floats, rot16 at 256, phase 0
     // with its steps reversed at 288 (ensure_decimation).
-    struct TapRow { v2f h2[SS / 2]; };
     const float2 *rot16 = reinterpret_cast<const float2 *>(taps + 256);
-    auto tap_row = [&](int p) {
-        static_assert(SS % 4 == 0, "whole float4 of taps per phase");
-        TapRow r;
-        const float4 *tp = reinterpret_cast<const float4 *>(taps + (p < 16 ? 16 * p : 288));
-#pragma unroll
-        for (int s = 0; s < SS / 4; s++) {
-            const float4 v = tp[s];
-            r.h2[2 * s] = v2f{v.x, v.y};
-            r.h2[2 * s + 1] = v2f{v.z, v.w};
-        }
-        return r;
-    };
-    auto mac = [](float2 &acc, const TapRow &tr, auto s_c, float2 q_) {       // acc += tap[s] q
-        constexpr int s = decltype(s_c)::value;
-        v2f a = {acc.x, acc.y};
-        const v2f q = {q_.x, q_.y};
-        if (s & 1) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(a) : "v"(q), "s"(tr.h2[s / 2]));
-        else asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "+v"(a) : "v"(q), "s"(tr.h2[s / 2]));
-        acc = make_float2(a.x, a.y);
-    };
-    auto mac_all = [&](float2 (&acc)[SS], const TapRow &tr, float2 q) {
-        mac(acc[0], tr, std::integral_constant<int, 0>{}, q);
-        mac(acc[1], tr, std::integral_constant<int, 1>{}, q);
-        mac(acc[2], tr, std::integral_constant<int, 2>{}, q);
-        mac(acc[3], tr, std::integral_constant<int, 3>{}, q);
-        mac(acc[4], tr, std::integral_constant<int, 4>{}, q);
-        mac(acc[5], tr, std::integral_constant<int, 5>{}, q);
-        mac(acc[6], tr, std::integral_constant<int, 6>{}, q);
-        mac(acc[7], tr, std::integral_constant<int, 7>{}, q);
-        if constexpr (SS > 8) {
-            mac(acc[8], tr, std::integral_constant<int, 8>{}, q);
-            mac(acc[9], tr, std::integral_constant<int, 9>{}, q);
-            mac(acc[10], tr, std::integral_constant<int, 10>{}, q);
-            mac(acc[11], tr, std::integral_constant<int, 11>{}, q);
-        }
-    };
-    // row 0 of column k1 pairs inside row 0 (dec_stream.hpp): straight from memory, once per walk
+    auto tap_row = [&](int p) { return walk_tap_row<SS>(taps + (p < 16 ? 16 * p : 288)); };
+    // row 0 of column k1 (dec_walk.hpp, row0_top): straight from memory, once per walk
     {
         const int kp = (N1 - k1) & (N1 - 1);
-        const TapRow tr = tap_row(0);
-        float2 q, qm;
-        pair_u_pk(*row0_at(Ua, k1), *row0_at(Ua, kp), *row0_at(Ub, k1), *row0_at(Ub, kp), w_n((float)k1 * (float)N2), k1 == 0, q, qm);
-        mac_all(at, tr, q);
+        st.row0_top(*row0_at(Ua, k1), *row0_at(Ua, kp), *row0_at(Ub, k1), *row0_at(Ub, kp), walk_root<N2>(pl, invNc, (float)k1 * (float)N2), k1 == 0, tap_row(0));
     }
     // ---- merged shares (MERGE_) ----------------------------------------------------------------------------------------------
     // A share and the output it belongs to leave their walks a whole column apart in time: the downward walk of column k1 is through
@@ -404,43 +355,24 @@ __attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kSt
                            __int_as_float(__builtin_amdgcn_ds_bpermute(4 * src, __float_as_int(v.y))));
     };
     [[maybe_unused]] const int lane_up = (lane + 1) & 63, lane_dn = (lane + 63) & 63;
-    if constexpr (!MERGE_) {
-        x_top[0] = make_float2(0.0f, 0.0f);
-        x_bot[0] = make_float2(0.0f, 0.0f);
-    }
-    auto shift_b = [&]() {
-#pragma unroll
-        for (int u = SS - 1; u > 0; u--) ab[u] = ab[u - 1];
-        ab[0] = make_float2(0.0f, 0.0f);
-    };
-    auto shift_t = [&]() {
-#pragma unroll
-        for (int s = SS - 1; s > 0; s--) at[s] = at[s - 1];
-        at[0] = make_float2(0.0f, 0.0f);
-    };
+    if constexpr (!MERGE_) st.slot0_is_zero();
     auto bottom_leaves = [&](int i) {
         if constexpr (MERGE_) {                                    // (inside the loop: i = NG + C - 1 down to C + 1)
-            if (i > NG - C) hold(held_b, ab[SS - 1]);              // held_b[j]: the value of i = NG - (C - 1) + j
-            else g_bot[(size_t)i * N1] = ab[SS - 1];
-            shift_b();
-            return;
+            if (i > NG - C) hold(held_b, st.ab[SS - 1]);           // held_b[j]: the value of i = NG - (C - 1) + j
+            else st.g_bot[(size_t)i * N1] = st.ab[SS - 1];
+            st.shift_b();
+        } else {
+            st.bottom_leaves(i);
         }
-        if (i >= NG) x_bot[(size_t)(kDecEdge + i - NG) * N1] = ab[SS - 1];
-        else if (i >= 0) g_bot[(size_t)i * N1] = ab[SS - 1];
-        else x_bot[(size_t)(kDecEdge + i) * N1] = ab[SS - 1];
-        shift_b();
     };
     auto top_leaves = [&](int i) {
         if constexpr (MERGE_) {                                    // (inside the loop: i = -(C - 1) .. NG - C)
-            if (i < C) hold(held_t, at[SS - 1]);                   // held_t[j]: the value of i = C - 1 - j
-            else g_top[(size_t)i * N1] = at[SS - 1];
-            shift_t();
-            return;
+            if (i < C) hold(held_t, st.at[SS - 1]);                // held_t[j]: the value of i = C - 1 - j
+            else st.g_top[(size_t)i * N1] = st.at[SS - 1];
+            st.shift_t();
+        } else {
+            st.top_leaves(i);
         }
-        if (i < 0) x_top[(size_t)(kDecEdge + i) * N1] = at[SS - 1];
-        else if (i < NG) g_top[(size_t)i * N1] = at[SS - 1];
-        else x_top[(size_t)(kDecEdge + i - NG) * N1] = at[SS - 1];
-        shift_t();
     };
     // LDS byte offsets of this lane's four operands inside a (phase, row) block of S KB: column k1 of the forward piece,
     // column km = 4095 - k1 of the partner piece (its block is stored ascending: lane 63 - l)
@@ -448,20 +380,11 @@ __attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kSt
     const unsigned int o_bf = (unsigned int)(sb * R) * 1024u + 8u * (unsigned int)lane, o_bm = (unsigned int)(sb * R) * 1024u + 512u + 8u * (unsigned int)(63 - lane);
     auto lds_at = [&](unsigned int off) { return *reinterpret_cast<const float2 *>(stage_raw + off); };
     float2 wg = make_float2(1.0f, 0.0f);
-    // tr: the taps of the row's phase; tb (FIRST rows only): the upward walk's taps -- phase 0: the reversed row
-    auto row = [&](float2 ua, float2 uam, float2 ub, float2 ubm, int k2, auto first_c, const TapRow &tr, const TapRow &tb) {
+    auto row = [&](const float2 (&v)[4], int k2, auto first_c, const TapRow<SS> &tr, const TapRow<SS> &tb) {
         constexpr bool FIRST = decltype(first_c)::value;            // the only row of a phase whose FIR phase can be 0
         const int p = k2 & 15, g = k2 >> 4;
-        float2 q, qm;
-        pair_u_pk(ua, uam, ub, ubm, cmul(wg, rot16[p]), false, q, qm);
-        if (FIRST && k2 == 0) q = qm = make_float2(0.0f, 0.0f);     // row 0: done above
-        mac_all(at, tr, q);
-        if (!FIRST) {
-            mac_all(ab, tr, qm);
-        } else {
-            mac_all(ab, tb, qm);
-            if (p == 0 && g > 0) bottom_leaves(NG - g + C);
-        }
+        st.template row<FIRST>(v[0], v[1], v[2], v[3], k2, cmul(wg, rot16[p]), tr, tb);
+        if (FIRST && p == 0 && g > 0) bottom_leaves(NG - g + C);
     };
     int buf = 0;
     TDOA_STG_T(const unsigned long long t_in = __builtin_readcyclecounter(); unsigned long long t_bar = 0;)
@@ -476,7 +399,7 @@ __attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kSt
         const unsigned int a_af = base + o_af, a_am = base + o_am, a_bf = base + o_bf, a_bm = base + o_bm;      // this phase's operands
         if (++buf == nb) buf = 0;
         const int k2 = ph * R;
-        if ((k2 & 15) == 0) wg = w_n((float)k2 + (float)k1 * (float)N2);
+        if ((k2 & 15) == 0) wg = walk_root<N2>(pl, invNc, (float)k2 + (float)k1 * (float)N2);
         // two rows at a time (their eight reads in flight together; four rows' worth of operands did not fit 128 registers)
 #pragma unroll
         for (int r0 = 0; r0 < R; r0 += 2) {
@@ -489,14 +412,11 @@ __attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kSt
                 v[r][3] = lds_at(a_bm + 1024u * (unsigned int)(r0 + r));
             }
             const int p0 = (k2 + r0) & 15;
-            const TapRow t0 = tap_row(p0), t1 = tap_row(p0 + 1);
-            if (r0 == 0) {
-                const TapRow tb = tap_row(p0 ? p0 : 16);
-                row(v[0][0], v[0][1], v[0][2], v[0][3], k2, std::true_type{}, t0, tb);
-            } else {
-                row(v[0][0], v[0][1], v[0][2], v[0][3], k2 + r0, std::false_type{}, t0, t0);
-            }
-            row(v[1][0], v[1][1], v[1][2], v[1][3], k2 + r0 + 1, std::false_type{}, t1, t1);
+            const TapRow<SS> t0 = tap_row(p0), t1 = tap_row(p0 + 1);
+            // t0, t1: the taps of the two rows' phases; tb (the phase's first row only): the upward walk's -- phase 0: the reversed row
+            if (r0 == 0) row(v[0], k2, std::true_type{}, t0, tap_row(p0 ? p0 : 16));
+            else row(v[0], k2 + r0, std::false_type{}, t0, t0);
+            row(v[1], k2 + r0 + 1, std::false_type{}, t1, t1);
         }
         if (((k2 + R - 1) & 15) == 15) top_leaves((k2 >> 4) - (SS - 1 - C));
     }
@@ -504,53 +424,48 @@ __attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kSt
         static_assert(!MERGE_ || SS == 2 * C, "the held values: C - 1 shares and C outputs per stencil");
 #pragma unroll
         for (int n = 0; n < SS - 1; n++) {                         // the values of i = NG - (C - 1) + n
-            const float2 v = at[SS - 1];
+            const float2 v = st.at[SS - 1];
             if (n < C - 1) {                                       // output i: + slot n + 1 of column k1 + 1 (that walk's i = n + 1 - C)
                 const float2 s = lane_from(held_t[2 * C - 2 - n], lane_up);
-                g_top[(size_t)(NG - (C - 1) + n) * N1] = lane < 63 ? make_float2(v.x + s.x, v.y + s.y) : v;
+                st.g_top[(size_t)(NG - (C - 1) + n) * N1] = lane < 63 ? make_float2(v.x + s.x, v.y + s.y) : v;
             } else {                                               // slot C + r: the share of output r of column k1 + 1
                 const int r = n - (C - 1);
                 const float2 s = lane_from(v, lane_dn), g = held_t[C - 1 - r];
-                g_top[(size_t)r * N1] = lane > 0 ? make_float2(g.x + s.x, g.y + s.y) : g;
-                if (lane == 63) x_top[(size_t)(C + r) * N1] = v;
+                st.g_top[(size_t)r * N1] = lane > 0 ? make_float2(g.x + s.x, g.y + s.y) : g;
+                if (lane == 63) st.x_top[(size_t)(C + r) * N1] = v;
             }
-            shift_t();
+            st.shift_t();
         }
         if (lane == 0) {
 #pragma unroll
-            for (int s = 1; s < C; s++) x_top[(size_t)s * N1] = held_t[2 * C - 1 - s];
+            for (int s = 1; s < C; s++) st.x_top[(size_t)s * N1] = held_t[2 * C - 1 - s];
         }
     } else {
 #pragma unroll
         for (int n = 0; n < SS - 1; n++) top_leaves(NG - (SS - 1 - C) + n);
     }
-    {
-        const TapRow tr = tap_row(16);
-        float2 q, qm;
-        pair_u_pk(*row0_at(Ua, km), *row0_at(Ua, k1 + 1), *row0_at(Ub, km), *row0_at(Ub, k1 + 1), w_n((float)km * (float)N2), false, q, qm);
-        mac_all(ab, tr, q);
-    }
+    st.row0_bottom(*row0_at(Ua, km), *row0_at(Ua, k1 + 1), *row0_at(Ub, km), *row0_at(Ub, k1 + 1), walk_root<N2>(pl, invNc, (float)km * (float)N2), tap_row(16));
     if constexpr (MERGE_) {
 #pragma unroll
         for (int n = 0; n < SS; n++) {                             // the values of i = C - n
-            const float2 v = ab[SS - 1];
+            const float2 v = st.ab[SS - 1];
             if (n == 0) {
-                g_bot[(size_t)C * N1] = v;
+                st.g_bot[(size_t)C * N1] = v;
             } else if (n <= C) {                                   // output r: + slot C + r of column km - 1 (lane + 1; that walk's i = NG + r)
                 const int r = C - n;
                 const float2 s = lane_from(held_b[C - 1 + r], lane_up);
-                g_bot[(size_t)r * N1] = lane < 63 ? make_float2(v.x + s.x, v.y + s.y) : v;
+                st.g_bot[(size_t)r * N1] = lane < 63 ? make_float2(v.x + s.x, v.y + s.y) : v;
             } else {                                               // slot s: the share of output NG - C + s of column km - 1 (lane + 1)
                 const int sl = 2 * C - n;
                 const float2 s = lane_from(v, lane_dn), g = held_b[sl - 1];
-                g_bot[(size_t)(NG - C + sl) * N1] = lane > 0 ? make_float2(g.x + s.x, g.y + s.y) : g;
-                if (lane == 63) x_bot[(size_t)sl * N1] = v;
+                st.g_bot[(size_t)(NG - C + sl) * N1] = lane > 0 ? make_float2(g.x + s.x, g.y + s.y) : g;
+                if (lane == 63) st.x_bot[(size_t)sl * N1] = v;
             }
-            shift_b();
+            st.shift_b();
         }
         if (lane == 0) {
 #pragma unroll
-            for (int s = C; s < 2 * C; s++) x_bot[(size_t)s * N1] = held_b[s - 1];
+            for (int s = C; s < 2 * C; s++) st.x_bot[(size_t)s * N1] = held_b[s - 1];
         }
     } else {
 #pragma unroll

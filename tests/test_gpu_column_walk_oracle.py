@@ -3,7 +3,7 @@ against the oracle (until round 5 it was only compared with 
 geometry's lags).  Since round 5 the library runs it with the stations' rows staged in LDS (k_pair_decimate_staged,
 csrc/dec_staged.hpp: one workgroup per window and 64-column block, a loader wave and one walk per compute wave);
 k_pair_decimate_cols<256> / <512> (one pair-window per wave straight from memory, four per workgroup) is what
-TDOA_DEBUG_NO_DEC_STAGED leaves.  BOTH are held against the oracle here.
+TDOA_DEBUG_NO_DEC_STAGED leaves.  BOTH (and with them the walk they share, csrc/dec_walk.hpp) are held against the oracle here.
 
 Every (window, pair) of a tdoa_process batch, in the reference's pair order i < j (processor.go:816-850), is held against
 oracle.b_xcorr_peak_fft (ob_* codes, float64 FFT correlation) on the bytes downloaded from the device: lag identical, corr
