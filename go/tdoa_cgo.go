@@ -133,6 +133,28 @@ func (g *gpuCorrelator) ProcessStacked(windowsPerStack, k, minSeparation int, ga
 	return peaks, count, fine, nil
 }
 
+// ProcessStackedDrift is ProcessStacked along the best of the 2*maxDrift+1 lag slopes h/driftDen lags per window, searched
+// per stack and pair: shift(h, j) = sgn(h)*((2|h|j + D) div (2D)) lags for window j of a stack, terms outside the searched
+// range contributing 0.  drift holds h* per stack-pair (the pair's relative clock rate is h*/(driftDen*window_len)), the
+// other results are those of the stack taken along that slope; the reported lag is the lag at the stack's first window.
+// One context sums all its windows: there is no group form of this call.
+func (g *gpuCorrelator) ProcessStackedDrift(windowsPerStack, k, minSeparation int, gate float64, maxDrift, driftDen int) ([]C.tdoa_peak, []C.int32_t, []C.tdoa_fine_peak, []C.int32_t, error) {
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, nil, nil, nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	n := int(total) * int(C.tdoa_num_pairs(g.ctx))
+	if n == 0 || k < 1 {
+		return nil, nil, nil, nil, fmt.Errorf("tdoa_process_stacked_drift: no stack-pairs or k < 1")
+	}
+	peaks, count, fine, drift := make([]C.tdoa_peak, n*k), make([]C.int32_t, n), make([]C.tdoa_fine_peak, n), make([]C.int32_t, n)
+	if rc := C.tdoa_process_stacked_drift(g.ctx, C.int(windowsPerStack), C.int(k), C.int(minSeparation), C.double(gate),
+		C.int(maxDrift), C.int(driftDen), &peaks[0], &count[0], &fine[0], nil, nil, &drift[0], nil); rc != C.TDOA_OK {
+		return nil, nil, nil, nil, fmt.Errorf("tdoa_process_stacked_drift: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return peaks, count, fine, drift, nil
+}
+
 // windowQuality is fastAnalyzeSamples' statistics (fast_analyzer.go:117-155) for every (window, station).
 func (g *gpuCorrelator) windowQuality(stations int) ([]C.tdoa_window_quality, error) {
 	var perBlock, total C.int

@@ -263,7 +263,9 @@ int tdoa_fm_xcorr_peaks_u8(tdoa_ctx *ctx, const uint8_t *iq1, size_t n1, const u
 /* Stacked correlation: the surfaces of a run of windows of one block added lag by lag -- one peak set per (stack, pair)
  * instead of one per pair-window.  The stations' clocks do not move within a block, so the windows' lags line up and the
  * sum keeps its maximum at the true delay where a single window's argmax is already lost in noise (coherent processing
- * gain, processor.go:770-782), on the plan of the short window.
+ * gain, processor.go:770-782), on the plan of the short window.  (That holds for receivers on one clock and for the
+ * synthetic captures.  Two free-running receivers differ in sample rate, the lag slides from window to window and this
+ * sum smears: tdoa_process_stacked_drift below searches the slope and stacks along it.)
  *
  * A stack is a run of windows_per_stack consecutive windows of ONE block (0: the whole block; the last stack of a block
  * may be shorter; stacks never cross a block boundary, block 1 being another frequency).  With m = windows_per_stack,
@@ -295,6 +297,41 @@ int tdoa_num_stacks(const tdoa_ctx *ctx, int windows_per_stack, int *stacks_per_
 int tdoa_process_stacked(tdoa_ctx *ctx, int rank, int world, int windows_per_stack, int k, int min_separation,
                          double gate_samples, tdoa_peak *peaks_host, int32_t *count_host, tdoa_fine_peak *fine_host,
                          float *surface_host, int64_t *partial_host);
+
+/* Drift-compensated stacking: the stacks of tdoa_process_stacked taken along a lag slope, the slope searched per
+ * (stack, pair).  Two receivers whose sample rates differ by r (1 ppm: 1e-6) see their relative delay slide by
+ * r * window_len lags per window; the plain stack then adds windows that do not line up.  Stacks, pairs, q_w[l], n_w and
+ * C = Q * 2^-32 / sqrt(n_w) are exactly those of tdoa_process_stacked; window w of a stack has the position j = 0, 1, ...
+ * in it, counted by window id.
+ * Hypothesis h in -H .. H (H = max_drift) stands for a slope of h / D lags per window (D = drift_den).  Its shift is
+ *     shift(h, j) = sgn(h) * ((2 |h| j + D) div (2 D))      the nearest integer to h j / D, halves away from zero;
+ *                                                            integers only, shift(-h, j) = -shift(h, j)
+ *     Q_h[L]      = sum over j of q_j[L + shift(h, j)]       a term whose lag falls outside -max_lag < lag < max_lag
+ *                                                            contributes 0
+ * and C_h is derived from Q_h as C from Q.  A pair whose lag is d0 + rho j in window j peaks at L = d0 under the hypothesis
+ * nearest rho: the reported lag is the lag at the stack's first window.
+ * profile_host [n_stacks_total][n_pairs][2H+1]: entry h + H is the peak of hypothesis h, the largest peak key of
+ * (float)C_h[L] over L (the floats and the tie rule of tdoa_process_stacked's peak 1): lag, abs_corr the float magnitude,
+ * corr the signed float as a double; no peak (every value 0): the zero record.
+ * drift_host [n_stacks_total][n_pairs]: h*, the hypothesis with the largest abs_corr; ties go to the smaller |h|, then to
+ * the positive h (the lag takes no part); no peak at all: 0.  The pair's relative clock rate is
+ * h* / (D * window_len), times 1e6 in ppm.
+ * peaks_host, count_host, fine_host, surface_host: those of tdoa_process_stacked computed on Q_{h*} in place of Q;
+ * partial_host: Q_{h*}.  So profile[h* + H].lag == peaks[0].lag with the same abs_corr, and with H = 0 every output is
+ * byte-identical to tdoa_process_stacked(ctx, 0, 1, ...) and drift_host all zero.  Any of the seven may be NULL, not all.
+ * No rank / world and no group entry: the ranks' per-hypothesis maxima cannot be merged, and their per-hypothesis sums
+ * would be 2H+1 surfaces each; one context sums all its windows.
+ * Limit: a slope also smears the peak inside one window.  The search repairs the alignment between windows only; it is
+ * meant for slopes up to about the peak's width per window.
+ * Runs inside the step graph.  TDOA_ERR_INVALID: what tdoa_process_stacked refuses, drift_den < 1, max_drift < 0 or > 512,
+ * a search whose largest shift, shift(H, m_eff - 1) with m_eff the stack length in use, exceeds max_lag - 1, all seven
+ * outputs NULL.  TDOA_LAGS_GO: TDOA_ERR_UNSUPPORTED.  Before captures exist: TDOA_ERR_STATE. */
+int tdoa_process_stacked_drift(tdoa_ctx *ctx, int windows_per_stack, int k, int min_separation, double gate_samples,
+                               int max_drift /* H */, int drift_den /* D */,
+                               tdoa_peak *peaks_host, int32_t *count_host, tdoa_fine_peak *fine_host,
+                               float *surface_host, int64_t *partial_host,
+                               int32_t *drift_host   /* [n_stacks_total][n_pairs]          */,
+                               tdoa_peak *profile_host /* [n_stacks_total][n_pairs][2H+1]  */);
 
 /* Capture-quality statistics of every (window, station) in one streaming pass over the bytes
  * in HBM: the byte statistics of fastAnalyzeSamples

@@ -3,7 +3,9 @@
 geometry of BASELINE config 2 (synthetic captures on the device, one GPU), in one run.  The three are timed in alternation,
 `--rounds` rounds of `--steps` calls each, so that the spread between rounds of the same call stands next to the
 differences between the calls: median, and the lowest and highest round.  The graphs replay; host copies are included,
-as a caller sees them.   usage: scripts/time_stacked.py [--steps N] [--rounds R]"""
+as a caller sees them.  Every `--drift H/D` adds a leg: tdoa_process_stacked_drift(0, H, D, 1, 1) with the profile downloaded
+(0/1 is the plain stack with the search's fixed cost; the difference between two legs is the search kernel's time for the
+hypotheses between them).   usage: scripts/time_stacked.py [--steps N] [--rounds R] [--drift H/D]..."""
 import json
 import os
 import sys
@@ -32,7 +34,7 @@ def timed(fn, steps):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
-def main(steps, rounds):
+def main(steps, rounds, drifts=()):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=20000)
     for s in range(3):
         c.synth_capture(s, 66_666_666, ST[s], TX, 0x5D0A0000 + s)
@@ -41,6 +43,8 @@ def main(steps, rounds):
     _, n_stacks = c.num_stacks(0)
     legs = {"process_ms": lambda: c.process(), "process_peaks_k1_ms": lambda: c.process_peaks(1, 1),
             "process_stacked_ms": lambda: c.process_stacked(0, 1, 1)}
+    for H, D in drifts:
+        legs["process_stacked_drift_%d_%d_ms" % (H, D)] = lambda H=H, D=D: c.process_stacked_drift(0, H, D, 1, 1)
     times = {name: [] for name in legs}
     for _ in range(rounds):
         for name, fn in legs.items():
@@ -61,4 +65,10 @@ if __name__ == "__main__":
             i = args.index(name)
             opt[name] = int(args[i + 1])
             del args[i:i + 2]
-    main(opt["--steps"], opt["--rounds"])
+    drifts = []
+    while "--drift" in args:
+        i = args.index("--drift")
+        h, _, d = args[i + 1].partition("/")
+        drifts.append((int(h), int(d or 1)))
+        del args[i:i + 2]
+    main(opt["--steps"], opt["--rounds"], drifts)

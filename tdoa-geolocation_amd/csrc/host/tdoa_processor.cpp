@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -110,6 +110,8 @@ int main(int argc, char **argv)
 {
     bool fm = false, fine = false, stack = false;
     int stack_m = 0;         // --stack=WINDOWS: windows per stack (0, or plain --stack: a whole block)
+    bool drift = false;      // --drift=H[/D] (with --stack): stack along the best of the slopes -H/D .. H/D lags per window
+    int drift_h = 0, drift_d = 1;
     double gate = 120.0;     // samples; PROJECT_NOTES.md:29-32 (max |TDOA| about 57 us = 114 samples at 2 Msps)
     tdoa_params prm;
     tdoa_default_params(&prm);
@@ -120,6 +122,12 @@ int main(int argc, char **argv)
         else if (a == "--fine") fm = fine = true;              // sub-sample refinement + plausibility gate (implies --fm)
         else if (a == "--stack") fm = stack = true;            // one delay per block and pair from the summed surfaces (implies --fm)
         else if (a.rfind("--stack=", 0) == 0) { fm = stack = true; stack_m = std::atoi(a.c_str() + 8); }
+        else if (a.rfind("--drift=", 0) == 0) {
+            drift = true;
+            drift_h = std::atoi(a.c_str() + 8);
+            const size_t slash = a.find('/');
+            drift_d = slash == std::string::npos ? 1 : std::atoi(a.c_str() + slash + 1);
+        }
         else if (a == "--gate" && i + 1 < argc) gate = std::atof(argv[++i]);
         else if (a == "--device" && i + 1 < argc) prm.device = std::atoi(argv[++i]);
         else if (a == "--window" && i + 1 < argc) prm.window_len = std::atoll(argv[++i]);
@@ -128,6 +136,7 @@ int main(int argc, char **argv)
         else if (a == "--k1-gate") prm.k1_gate = 1;                                          // its power gate (envelope branch)
         else pos.push_back(a);
     }
+    if (drift && !stack) { std::fprintf(stderr, "--drift needs --stack\n"); return 1; }
     if (pos.size() < 4) {                                     // processor.go:1048-1052
         usage(argv[0]);
         return 1;
@@ -244,8 +253,13 @@ int main(int argc, char **argv)
         }
     } else {
         // ---- north-star path: raw bytes in, one peak per (window, pair) out
-        for (int s = 0; s < S; s++)   // file -> pinned staging -> HBM
-            if ((rc = tdoa_capture_upload_file(ctx, s, caps[s].path.c_str(), nullptr))) return die("tdoa_capture_upload_file", rc);
+        size_t shortest = (size_t)-1;            // samples of the shortest capture: a window is window_len of them, or a whole block
+        for (int s = 0; s < S; s++) { // file -> pinned staging -> HBM
+            size_t n_samples = 0;
+            if ((rc = tdoa_capture_upload_file(ctx, s, caps[s].path.c_str(), &n_samples))) return die("tdoa_capture_upload_file", rc);
+            shortest = std::min(shortest, n_samples);
+        }
+        const long long wlen = std::min<long long>(prm.window_len, (long long)(shortest / 3));
         int wpb = 0, W = 0;
         if ((rc = tdoa_num_windows(ctx, &wpb, &W))) return die("tdoa_num_windows", rc);
         const int P = tdoa_num_pairs(ctx);
@@ -285,12 +299,18 @@ int main(int argc, char **argv)
         std::vector<tdoa_peak> spk;
         std::vector<int32_t> scnt;
         std::vector<tdoa_fine_peak> sfine;
+        std::vector<int32_t> sdrift;             // --drift: h* per stack-pair (tdoa_process_stacked_drift)
         if (stack) {
             if ((rc = tdoa_num_stacks(ctx, stack_m, &spb, &n_stacks))) return die("tdoa_num_stacks", rc);
             spk.resize((size_t)n_stacks * P * 2);
             scnt.resize((size_t)n_stacks * P);
             sfine.resize((size_t)n_stacks * P);
-            if ((rc = tdoa_process_stacked(ctx, 0, 1, stack_m, 2, 1, gate, spk.data(), scnt.data(), sfine.data(), nullptr, nullptr)))
+            if (drift) {
+                sdrift.resize((size_t)n_stacks * P);
+                if ((rc = tdoa_process_stacked_drift(ctx, stack_m, 2, 1, gate, drift_h, drift_d, spk.data(), scnt.data(), sfine.data(),
+                                                     nullptr, nullptr, sdrift.data(), nullptr)))
+                    return die("tdoa_process_stacked_drift", rc);
+            } else if ((rc = tdoa_process_stacked(ctx, 0, 1, stack_m, 2, 1, gate, spk.data(), scnt.data(), sfine.data(), nullptr, nullptr)))
                 return die("tdoa_process_stacked", rc);
         }
         std::printf("\n=== FM-DISCRIMINATOR CROSS-CORRELATION: %d windows x %d pairs ===\n", W, P);
@@ -331,10 +351,14 @@ int main(int argc, char **argv)
                         const size_t u = (size_t)sid * P + p;
                         const tdoa_peak &p1 = spk[2 * u], &p2 = spk[2 * u + 1];
                         const int sj = sid % spb, n_w = std::min(m, wpb - sj * m);
-                        std::printf("STACK block %d stack %d %s - %s: windows=%d delay=%d samples refined=%.3f |C|=%.6f ratio=%.3f\n",
+                        std::printf("STACK block %d stack %d %s - %s: windows=%d delay=%d samples refined=%.3f |C|=%.6f ratio=%.3f",
                                     sid / spb + 1, sj, caps[i].st.name.c_str(), caps[j].st.name.c_str(), n_w, p1.lag,
                                     sfine[u].delay, (double)p1.abs_corr,
                                     scnt[u] > 1 ? (double)p1.abs_corr / (double)p2.abs_corr : INFINITY);
+                        if (drift)               // the slope h* / D and the relative clock rate it stands for
+                            std::printf(" drift=%+d/%d lags/window (%+.3f ppm)", (int)sdrift[u], drift_d,
+                                        1e6 * (double)sdrift[u] / ((double)drift_d * (double)wlen));
+                        std::printf("\n");
                         if (sid / spb == 1) { sd.push_back(sfine[u].delay); sc.push_back(p1.abs_corr); }
                     }
                     lag_used = median(sd);

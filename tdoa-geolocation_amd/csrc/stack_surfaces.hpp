@@ -38,21 +38,22 @@ __device__ __forceinline__ long long stack_term(float raw, double s, double g, b
 // C[l] of a stack of n_w windows; root = sqrt(n_w), rounded on the host
 __device__ __forceinline__ double stack_value(long long q, double root) { return (double)q * (1.0 / 4294967296.0) / root; }
 
-// grid (n_stacks * P, ceil(n / kStackTile)), kStackThreads threads.  surf + i * stride: the n raw values of the rank's
-// pair-window i (the K5 kernels' dump); list: pair-window numbers grouped by stack-pair, desc[stack-pair] its run.
-// Thread t of tile y owns the lags 4 (y * 256 + t) .. + 3 in registers for every row.  n is odd, so only every fourth row
-// starts on a 16-byte boundary (surf itself does): such a row is read as float4, the others and the last lags of a row
-// as single floats of the same 16 bytes.  Q[stack-pair][l] is written for every l, zero where the rank owns no window.
-__global__ __launch_bounds__(kStackThreads) void k_stack_accumulate(const float *surf, size_t stride, int n, const PWDesc *pw,
-                                                                   const StackDesc *desc, const int32_t *list,
-                                                                   const double *scales, const double *slot_gain,
-                                                                   long long *Q)
+// every row of a stack read at its own lags: the plain stack
+struct NoShear {
+    static constexpr bool shear = false;
+    __device__ __forceinline__ int operator()(int) const { return 0; }
+};
+
+// The body of k_stack_accumulate and of k_stack_accumulate_sheared (stack_drift.hpp): the rows of stack-pair d added into
+// the four lags l0 .. l0 + 3 of a thread, acc[u] += q of row r at lag l0 + u + shift(slot of r).  Without a shear (NoShear)
+// a row whose four lags start on a 16-byte boundary is read as float4, the others and the last lags of a row as single
+// floats of the same 16 bytes; with one (Shift::shear) every lag is read alone and a lag outside the row adds 0.
+template <class Shift>
+__device__ __forceinline__ void stack_accumulate_rows(const float *surf, size_t stride, int n, const PWDesc *pw, const StackDesc d,
+                                                      const int32_t *list, const double *scales, const double *slot_gain,
+                                                      int l0, const Shift shift, long long acc[4])
 {
-    const StackDesc d = desc[blockIdx.x];
-    const int l0 = 4 * ((int)blockIdx.y * kStackThreads + (int)threadIdx.x);
-    if (l0 >= n) return;
     const bool whole = l0 + 3 < n;
-    long long acc[4] = {0, 0, 0, 0};
 #pragma unroll 2
     for (int r = 0; r < d.count; r++) {
         const int i = list[d.first + r];
@@ -60,7 +61,12 @@ __global__ __launch_bounds__(kStackThreads) void k_stack_accumulate(const float 
         const double s = scales[slot], g = slot_gain ? slot_gain[slot] : 1.0;
         const size_t off = (size_t)i * stride + (size_t)l0;
         float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (whole && (off & 3) == 0) {
+        if (Shift::shear) {
+            const int sh = shift(slot);
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if (l0 + u < n && l0 + u + sh >= 0 && l0 + u + sh < n) v[u] = surf[(size_t)i * stride + (size_t)(l0 + u + sh)];
+        } else if (whole && (off & 3) == 0) {
             const float4 x = *reinterpret_cast<const float4 *>(surf + off);
             v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
         } else {
@@ -71,6 +77,22 @@ __global__ __launch_bounds__(kStackThreads) void k_stack_accumulate(const float 
 #pragma unroll
         for (int u = 0; u < 4; u++) acc[u] += stack_term(v[u], s, g, slot_gain != nullptr);
     }
+}
+
+// grid (n_stacks * P, ceil(n / kStackTile)), kStackThreads threads.  surf + i * stride: the n raw values of the rank's
+// pair-window i (the K5 kernels' dump); list: pair-window numbers grouped by stack-pair, desc[stack-pair] its run.
+// Thread t of tile y owns the lags 4 (y * 256 + t) .. + 3 in registers for every row.  n is odd, so only every fourth row
+// starts on a 16-byte boundary (surf itself does).  Q[stack-pair][l] is written for every l, zero where the rank owns no
+// window.
+__global__ __launch_bounds__(kStackThreads) void k_stack_accumulate(const float *surf, size_t stride, int n, const PWDesc *pw,
+                                                                   const StackDesc *desc, const int32_t *list,
+                                                                   const double *scales, const double *slot_gain,
+                                                                   long long *Q)
+{
+    const int l0 = 4 * ((int)blockIdx.y * kStackThreads + (int)threadIdx.x);
+    if (l0 >= n) return;
+    long long acc[4] = {0, 0, 0, 0};
+    stack_accumulate_rows(surf, stride, n, pw, desc[blockIdx.x], list, scales, slot_gain, l0, NoShear{}, acc);
     long long *q = Q + (size_t)blockIdx.x * n + l0;
 #pragma unroll
     for (int u = 0; u < 4; u++)

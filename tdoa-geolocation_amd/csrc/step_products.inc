@@ -1,10 +1,12 @@
 // step_products.inc -- what a step (process_impl) can write besides its peak records: the correlation surfaces
 // (tdoa_process_lags), the K strongest peaks per pair-window (tdoa_process_peaks), the stacked surfaces of a block's windows
-// (tdoa_process_stacked).  Every product is four functions next to each other, called by process_impl in this order:
+// (tdoa_process_stacked), the same stacks taken along the best of 2H+1 lag slopes (tdoa_process_stacked_drift).  Every
+// product is four functions next to each other, called by process_impl in this order:
 //   reserve_*   its buffers, after the step's grouping is fixed (batch_bound counts them as held, so a later call groups as
 //               this one did); no allocation may happen once the step is being captured
 //   key_*       the words it appends to the step graph's key: everything its launches depend on
-//   (upload_stack: the one product with descriptors of its own sends them with the step's, when the step is not replayed)
+//   (upload_stack, upload_stack_drift: the products with descriptors of their own send them with the step's, when the step
+//   is not replayed)
 //   enqueue_*   its kernels, after the step's decode -- unscoped launches, kernel nodes only: the step stays one chain
 //   download_*  its asynchronous copies out on ctx->stream
 // All of them read the K5 kernels' lag arrays in ctx->surf, pair-window i of the rank at i * n_lags.
@@ -51,12 +53,22 @@ struct StackProduct {
     bool finish() const { return peaks_host || count_host || fine_host || surface_host; }
 };
 
+struct StackDriftProduct {
+    StackProduct stack;                      // the stack's own arguments and outputs, computed on Q_{h*}
+    int H = 0, D = 1;                        // hypotheses -H .. H, slope h / D lags per window
+    int32_t *drift_host = nullptr;           // [stack][pair]: h*
+    tdoa_peak *profile_host = nullptr;       // [stack][pair][2H+1]
+    int mm = 0, hb = 1;                      // filled by reserve_stack_drift: the stack length, hypotheses per workgroup
+    std::vector<int32_t> tab;                // ... and shift(h, j) at [(h + H) * mm + j]
+};
+
 // the product of one step; the numbers are the first word a product appends to the graph key
 struct StepProduct {
-    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3 } kind = None;
+    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4 } kind = None;
     LagsProduct lags;
     PeaksProduct peaks;
     StackProduct stack;
+    StackDriftProduct drift;
 };
 
 // ctx->surf for the rank's pair-windows; `copies`: float surfaces of the step the product holds in all (the message's size)
@@ -176,6 +188,101 @@ int download_stack_product(const StepView &v, const StackProduct &p)
     return TDOA_OK;
 }
 
+// ---- the stacks along the best lag slope (stack_drift.hpp): the per-slope keys, h* and the profile, then the stack's own --
+// shift(h, j) = sgn(h) ((2 |h| j + D) div (2 D)): the nearest integer to h j / D, halves away from zero
+long long drift_shift(int h, long long j, long long D)
+{
+    const long long a = (2 * (long long)std::abs(h) * j + D) / (2 * D);
+    return h < 0 ? -a : a;
+}
+// the stack length a call with windows_per_stack = m uses
+int stack_length(int wpb, int m) { return m > 0 ? std::min(m, wpb) : wpb; }
+
+int reserve_stack_drift(const StepView &v, StackDriftProduct &p)
+{
+    tdoa_ctx *ctx = v.ctx;
+    if (int rc = reserve_stack(v, p.stack)) return rc;
+    p.mm = stack_length(v.wpb, p.stack.m);
+    const int n_hyp = 2 * p.H + 1;
+    p.tab.resize((size_t)n_hyp * p.mm);
+    for (int h = -p.H; h <= p.H; h++)
+        for (int j = 0; j < p.mm; j++) p.tab[(size_t)(h + p.H) * p.mm + j] = (int32_t)drift_shift(h, j, p.D);
+    // hypotheses per workgroup: the most whose shifts spread over no more than the staged span holds beyond its tile, for
+    // every window position (one hypothesis has no spread); not more than twice the hypotheses there are
+    for (p.hb = kShearHyp; p.hb > 1; p.hb /= 2) {
+        bool fits = p.hb / 2 < n_hyp;
+        for (int z0 = 0; fits && z0 < n_hyp; z0 += p.hb)
+            for (int j = 0; fits && j < p.mm; j++)
+                fits = p.tab[(size_t)std::min(z0 + p.hb - 1, n_hyp - 1) * p.mm + j] - p.tab[(size_t)z0 * p.mm + j] <= kShearSpread;
+        if (fits) break;
+    }
+    const size_t n_sp = (size_t)p.stack.layout.n_stacks * v.P;
+    if (ensure(ctx, ctx->drift_tab, sizeof(int32_t) * p.tab.size()) ||
+        ensure(ctx, ctx->drift_keys, sizeof(unsigned long long) * n_sp * n_hyp) ||
+        ensure(ctx, ctx->drift_h, sizeof(int32_t) * std::max<size_t>(n_sp, 1)) ||
+        ensure(ctx, ctx->drift_prof, sizeof(PeakOut) * n_sp * n_hyp))
+        return surfaces_nomem(v, "the slope search's keys and profile", 1.0);
+    return TDOA_OK;
+}
+void key_stack_drift(const StackDriftProduct &p, std::vector<uint64_t> *key)
+{
+    const StackProduct &s = p.stack;
+    key->insert(key->end(), {StepProduct::StackDrift, (uint64_t)s.k, (uint64_t)s.min_sep, (uint64_t)s.m | ((uint64_t)s.finish() << 32),
+                             (uint64_t)p.H, (uint64_t)p.D});
+}
+int upload_stack_drift(const StepView &v, StackDriftProduct &p)
+{
+    tdoa_ctx *ctx = v.ctx;
+    if (int rc = upload_stack(v, p.stack)) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->drift_tab.p, p.tab.data(), sizeof(int32_t) * p.tab.size(), hipMemcpyHostToDevice, ctx->stream));
+    return TDOA_OK;
+}
+template <int HB>
+void launch_shear_search(const StepView &v, const StackDriftProduct &p, const StackDev &sd, const ShearGeom &g)
+{
+    tdoa_ctx *ctx = v.ctx;
+    const int n_stacks = p.stack.layout.n_stacks, n_hyp = 2 * p.H + 1;
+    hipLaunchKernelGGL(k_stack_shear_search<HB>,
+                       dim3((unsigned)(n_stacks * v.P), (unsigned)((v.n_lags + kShearTile - 1) / kShearTile), (unsigned)((n_hyp + HB - 1) / HB)),
+                       dim3(kStackThreads), 0, ctx->stream, ctx->surf.as<const float>(), (size_t)v.n_lags, v.n_lags, v.lag_lo, v.d_pw,
+                       sd.desc, sd.list, v.d_scales, v.slot_gain, sd.roots, ctx->drift_tab.as<const int32_t>(), g,
+                       ctx->drift_keys.as<unsigned long long>());
+}
+void enqueue_stack_drift(const StepView &v, const StackDriftProduct &p)
+{
+    tdoa_ctx *ctx = v.ctx;
+    hipStream_t st = ctx->stream;
+    const StackProduct &s = p.stack;
+    const int n_stacks = s.layout.n_stacks, n_hyp = 2 * p.H + 1;
+    const unsigned n_sp = (unsigned)(n_stacks * v.P);
+    const StackDev sd = stack_dev(ctx, n_stacks, v.P);
+    const ShearGeom g{p.H, p.mm, v.wpb, v.P};
+    const size_t n_keys = (size_t)n_sp * n_hyp;
+    hipLaunchKernelGGL(k_zero_u64, dim3((unsigned)((n_keys + 255) / 256)), dim3(256), 0, st, ctx->drift_keys.as<unsigned long long>(), n_keys);
+    switch (p.hb) {
+    case 8: launch_shear_search<8>(v, p, sd, g); break;
+    case 4: launch_shear_search<4>(v, p, sd, g); break;
+    case 2: launch_shear_search<2>(v, p, sd, g); break;
+    default: launch_shear_search<1>(v, p, sd, g);
+    }
+    hipLaunchKernelGGL(k_stack_pick_drift, dim3(n_sp), dim3(kWave), 0, st, ctx->drift_keys.as<const unsigned long long>(), p.H,
+                       ctx->drift_h.as<int32_t>(), ctx->drift_prof.as<PeakOut>());
+    hipLaunchKernelGGL(k_stack_accumulate_sheared, dim3(n_sp, (unsigned)((v.n_lags + kStackTile - 1) / kStackTile)), dim3(kStackThreads), 0,
+                       st, ctx->surf.as<const float>(), (size_t)v.n_lags, v.n_lags, v.d_pw, sd.desc, sd.list, v.d_scales, v.slot_gain,
+                       ctx->drift_tab.as<const int32_t>(), ctx->drift_h.as<const int32_t>(), g, ctx->stack_q.as<long long>());
+    if (s.finish()) launch_stack_finish(ctx, n_stacks, v.P, v.n_lags, v.lag_lo, s.k, s.min_sep, s.gate);
+}
+int download_stack_drift(const StepView &v, const StackDriftProduct &p)
+{
+    tdoa_ctx *ctx = v.ctx;
+    const size_t n_sp = (size_t)p.stack.layout.n_stacks * v.P;
+    if (int rc = download_stack_product(v, p.stack)) return rc;
+    if (p.drift_host) HIPCHK(ctx, hipMemcpyAsync(p.drift_host, ctx->drift_h.p, sizeof(int32_t) * n_sp, hipMemcpyDeviceToHost, ctx->stream));
+    if (p.profile_host)
+        HIPCHK(ctx, hipMemcpyAsync(p.profile_host, ctx->drift_prof.p, sizeof(PeakOut) * n_sp * (2 * p.H + 1), hipMemcpyDeviceToHost, ctx->stream));
+    return TDOA_OK;
+}
+
 // ---- process_impl's one dispatch per stage ---------------------------------------------------------------------------
 int reserve_product(const StepView &v, StepProduct &p)
 {
@@ -183,6 +290,7 @@ int reserve_product(const StepView &v, StepProduct &p)
     case StepProduct::Lags: return reserve_lags(v, p.lags);
     case StepProduct::Peaks: return reserve_peaks(v, p.peaks);
     case StepProduct::Stack: return reserve_stack(v, p.stack);
+    case StepProduct::StackDrift: return reserve_stack_drift(v, p.drift);
     default: return TDOA_OK;
     }
 }
@@ -192,10 +300,18 @@ void key_product(const StepProduct &p, std::vector<uint64_t> *key)
     case StepProduct::Lags: return key_lags(p.lags, key);
     case StepProduct::Peaks: return key_peaks(p.peaks, key);
     case StepProduct::Stack: return key_stack(p.stack, key);
+    case StepProduct::StackDrift: return key_stack_drift(p.drift, key);
     default: key->insert(key->end(), {StepProduct::None, 0, 0, 0});
     }
 }
-int upload_product(const StepView &v, StepProduct &p) { return p.kind == StepProduct::Stack ? upload_stack(v, p.stack) : TDOA_OK; }
+int upload_product(const StepView &v, StepProduct &p)
+{
+    switch (p.kind) {
+    case StepProduct::Stack: return upload_stack(v, p.stack);
+    case StepProduct::StackDrift: return upload_stack_drift(v, p.drift);
+    default: return TDOA_OK;
+    }
+}
 void enqueue_product(const StepView &v, const StepProduct &p)
 {
     if (p.kind != StepProduct::None) v.ctx->prof_last = -1;    // unscoped launches
@@ -203,6 +319,7 @@ void enqueue_product(const StepView &v, const StepProduct &p)
     case StepProduct::Lags: return enqueue_lags(v, p.lags);
     case StepProduct::Peaks: return enqueue_peaks(v, p.peaks);
     case StepProduct::Stack: return enqueue_stack(v, p.stack);
+    case StepProduct::StackDrift: return enqueue_stack_drift(v, p.drift);
     default: return;
     }
 }
@@ -212,6 +329,7 @@ int download_product(const StepView &v, const StepProduct &p)
     case StepProduct::Lags: return download_lags(v, p.lags);
     case StepProduct::Peaks: return download_peaks(v, p.peaks);
     case StepProduct::Stack: return download_stack_product(v, p.stack);
+    case StepProduct::StackDrift: return download_stack_drift(v, p.drift);
     default: return TDOA_OK;
     }
 }

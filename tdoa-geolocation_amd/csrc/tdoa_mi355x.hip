@@ -36,6 +36,7 @@
 #include "segment_quads.hpp"
 #include "peak_select.hpp"
 #include "stack_surfaces.hpp"
+#include "stack_drift.hpp"
 
 using namespace tdoa;
 
@@ -147,6 +148,9 @@ struct tdoa_ctx {
     // tdoa_process_stacked: the fixed-point sums Q [stack][pair][2 max_lag - 1], the float stack surfaces of the same shape,
     // the stack-pairs' keys, their refined peak 1, and the descriptors (sqrt(n_w) per stack, unit scales, runs, list)
     DevBuf stack_q, stack_surf, stack_keys, stack_fine, stack_desc;
+    // tdoa_process_stacked_drift: the shift table [2H+1][stack length], the keys [stack][pair][2H+1] of the slopes' maxima,
+    // h* [stack][pair] and the decoded profile [stack][pair][2H+1]
+    DevBuf drift_tab, drift_keys, drift_h, drift_prof;
 };
 
 namespace {
@@ -475,7 +479,7 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->g_sw_desc, &ctx->g_pw_desc, &ctx->g_quad_desc, &ctx->g_scales, &ctx->g_keys, &ctx->fine_raw, &ctx->fine, &ctx->qual,
                       &ctx->once_edges, &ctx->once_tiles, &ctx->once_fin, &ctx->slot_gain, &ctx->surf, &ctx->surf_out,
                       &ctx->sel_peaks, &ctx->sel_count, &ctx->stack_q, &ctx->stack_surf, &ctx->stack_keys, &ctx->stack_fine,
-                      &ctx->stack_desc};
+                      &ctx->stack_desc, &ctx->drift_tab, &ctx->drift_keys, &ctx->drift_h, &ctx->drift_prof};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -968,6 +972,42 @@ int tdoa_process_stacked(tdoa_ctx *ctx, int rank, int world, int windows_per_sta
     sp.partial_host = partial_host;
     // (the gate stays a word of the step graph's key through the step's own gate argument)
     return process_impl(ctx, rank, world, nullptr, nullptr, nullptr, gate_samples, std::move(prod));
+}
+
+int tdoa_process_stacked_drift(tdoa_ctx *ctx, int windows_per_stack, int k, int min_separation, double gate_samples,
+                               int max_drift, int drift_den, tdoa_peak *peaks_host, int32_t *count_host, tdoa_fine_peak *fine_host,
+                               float *surface_host, int64_t *partial_host, int32_t *drift_host, tdoa_peak *profile_host)
+{
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (const char *bad = check_stacked_args(windows_per_stack, k, min_separation, gate_samples,
+                                             peaks_host || count_host || fine_host || surface_host || partial_host || drift_host ||
+                                                 profile_host))
+        return fail(ctx, TDOA_ERR_INVALID, bad);
+    if (drift_den < 1) return fail(ctx, TDOA_ERR_INVALID, "drift_den < 1");
+    if (max_drift < 0 || max_drift > 512) return fail(ctx, TDOA_ERR_INVALID, "max_drift outside 0 .. 512");
+    if (ctx->prm.lag_mode == TDOA_LAGS_GO) return fail(ctx, TDOA_ERR_UNSUPPORTED, "stacked correlation with TDOA_LAGS_GO");
+    int wpb = 0;
+    if (int rc = tdoa_num_windows(ctx, &wpb, nullptr)) return fail(ctx, rc, "captures missing or too small");
+    if (drift_shift(max_drift, stack_length(wpb, windows_per_stack) - 1, drift_den) > ctx->prm.max_lag - 1)
+        return fail(ctx, TDOA_ERR_INVALID, "the search's largest shift exceeds max_lag - 1");
+    StepProduct prod;
+    prod.kind = StepProduct::StackDrift;
+    StackDriftProduct &dp = prod.drift;
+    dp.H = max_drift;
+    dp.D = drift_den;
+    dp.drift_host = drift_host;
+    dp.profile_host = profile_host;
+    StackProduct &sp = dp.stack;
+    sp.m = windows_per_stack;
+    sp.k = k;
+    sp.min_sep = min_separation;
+    sp.gate = gate_samples;
+    sp.peaks_host = peaks_host;
+    sp.count_host = count_host;
+    sp.fine_host = fine_host;
+    sp.surface_host = surface_host;
+    sp.partial_host = partial_host;
+    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, gate_samples, std::move(prod));
 }
 
 // fast_analyzer.go:139-155 and collector.go:224 from the exact integer sums, in the reference's expression order

@@ -89,7 +89,7 @@ SYMBOLS = [
     "tdoa_plan_info", "tdoa_process_lags", "tdoa_process_peaks", "tdoa_fm_xcorr_peaks_u8", "tdoa_debug_select_peaks",
     "tdoa_group_create", "tdoa_group_destroy", "tdoa_group_last_error", "tdoa_group_member",
     "tdoa_group_capture_upload_files", "tdoa_group_process", "tdoa_debug_owned_runs",
-    "tdoa_num_stacks", "tdoa_process_stacked", "tdoa_group_process_stacked",
+    "tdoa_num_stacks", "tdoa_process_stacked", "tdoa_group_process_stacked", "tdoa_process_stacked_drift",
 ]
 
 _lib = None
@@ -193,6 +193,8 @@ def load(build_if_missing=True):
     L.tdoa_process_stacked.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, i32p, vp, fp,
                                        C.POINTER(C.c_int64)]
     L.tdoa_group_process_stacked.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, i32p, vp, fp]
+    L.tdoa_process_stacked_drift.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, i32p, vp, fp,
+                                             C.POINTER(C.c_int64), i32p, vp]
     L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
                                         C.POINTER(C.c_int)]
     _lib = L
@@ -504,6 +506,27 @@ class Context:
             out["count"].ctypes.data_as(C.POINTER(C.c_int32)), out["fine"].ctypes.data_as(C.c_void_p),
             _f(out["surface"]) if want_surface else None,
             out["partial"].ctypes.data_as(C.POINTER(C.c_int64)) if want_partial else None))
+        return out
+
+    def process_stacked_drift(self, windows_per_stack=0, max_drift=0, drift_den=1, k=1, min_separation=1, gate=None,
+                              want_surface=False, want_partial=False, want_profile=True):
+        """tdoa_process_stacked_drift -> the dict of process_stacked computed along the best of the 2 max_drift + 1 lag
+        slopes h / drift_den lags per window, plus drift [n_stacks][P] int32 (h*) and, unless want_profile is False,
+        profile [n_stacks][P][2 max_drift + 1] PEAK_DTYPE (the peak of every slope); partial is Q of h*"""
+        _, n = self.num_stacks(windows_per_stack)
+        p = self.num_pairs()
+        out = _stacked_outputs(n, p, 2 * self.params.max_lag - 1, k, want_surface, want_partial)
+        out["drift"] = np.zeros((n, p), dtype=np.int32)
+        if want_profile:
+            out["profile"] = np.zeros((n, p, 2 * max(int(max_drift), 0) + 1), dtype=PEAK_DTYPE)
+        self._chk(self._L.tdoa_process_stacked_drift(
+            self._h, int(windows_per_stack), int(k), int(min_separation),
+            float(self.params.max_lag if gate is None else gate), int(max_drift), int(drift_den),
+            out["peaks"].ctypes.data_as(C.c_void_p), out["count"].ctypes.data_as(C.POINTER(C.c_int32)),
+            out["fine"].ctypes.data_as(C.c_void_p), _f(out["surface"]) if want_surface else None,
+            out["partial"].ctypes.data_as(C.POINTER(C.c_int64)) if want_partial else None,
+            out["drift"].ctypes.data_as(C.POINTER(C.c_int32)),
+            out["profile"].ctypes.data_as(C.c_void_p) if want_profile else None))
         return out
 
     def fm_xcorr_peaks(self, iq1, iq2, max_lag, k, min_separation):

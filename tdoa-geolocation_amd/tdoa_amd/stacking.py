@@ -1,8 +1,11 @@
-"""The stacked correlation of tdoa_process_stacked (include/tdoa_mi355x.h, "stacked correlation") in float64 / int64 numpy:
-what the GPU kernels (csrc/stack_surfaces.hpp) are held to.  Tests use it; the library does not."""
+"""The stacked correlation of tdoa_process_stacked (include/tdoa_mi355x.h, "stacked correlation") and the slope search of
+tdoa_process_stacked_drift ("drift-compensated stacking") in float64 / int64 numpy: what the GPU kernels
+(csrc/stack_surfaces.hpp, csrc/stack_drift.hpp) are held to.  Tests use it; the library does not."""
 import numpy as np
 
-from .peaks import select_peaks
+from .peaks import select_peaks, surface_max
+
+PEAK_DTYPE = np.dtype([("lag", np.int32), ("abs_corr", np.float32), ("corr", np.float64)])      # tdoa_peak
 
 Q_ONE = 2.0 ** 32          # fixed-point units per unit of correlation
 
@@ -65,3 +68,55 @@ def refine(c, max_lag, lag):
     den = ym - 2.0 * y0 + yp
     fr = 0.5 * (ym - yp) / den if den < 0 else 0.0
     return float(lag) + float(np.clip(fr, -0.5, 0.5))
+
+
+def shift(h, j, den):
+    """shift(h, j) = sgn(h) ((2 |h| j + D) div (2 D)): the nearest integer to h j / D, halves away from zero"""
+    h, j, den = int(h), int(j), int(den)
+    if den < 1 or j < 0:
+        raise ValueError("den must be >= 1 and j >= 0")
+    a = (2 * abs(h) * j + den) // (2 * den)
+    return -a if h < 0 else a
+
+
+def sheared_sum(q_windows, h, den):
+    """q_windows [m][L] int64, window j of a stack at row j -> Q_h[L] = sum_j q_j[L + shift(h, j)], a term outside the
+    searched range contributing 0"""
+    q = np.asarray(q_windows, dtype=np.int64)
+    n = q.shape[-1]
+    out = np.zeros(n, dtype=np.int64)
+    for j in range(q.shape[0]):
+        s = shift(h, j, den)
+        lo, hi = max(0, -s), min(n, n - s)              # L with 0 <= L + s < n
+        if lo < hi:
+            out[lo:hi] += q[j, lo + s:hi + s]
+    return out
+
+
+def drift_search(q_windows, max_drift, den, max_lag):
+    """the slope search on one stack-pair's windows q_windows [m][2 max_lag - 1] int64 -> (h*, profile [2 max_drift + 1]
+    PEAK_DTYPE, Q_h*): per hypothesis the maximum of |float32(C_h)| (ties: smaller |lag|, then the positive lag), h* the
+    hypothesis with the largest abs_corr (ties: smaller |h|, then the positive h; nothing but zeros: 0)"""
+    q = np.asarray(q_windows, dtype=np.int64)
+    H, ml = int(max_drift), int(max_lag)
+    if q.ndim != 2 or q.shape[1] != 2 * ml - 1:
+        raise ValueError("q_windows must be [m][2 max_lag - 1]")
+    if shift(H, max(q.shape[0] - 1, 0), den) > ml - 1:
+        raise ValueError("the largest shift exceeds max_lag - 1")
+    profile = np.zeros(2 * H + 1, dtype=PEAK_DTYPE)
+    sums = {}
+    best = None
+    for h in sorted(range(-H, H + 1), key=lambda x: (abs(x), x < 0)):       # 0, +1, -1, +2, -2, ...
+        sums[h] = sheared_sum(q, h, den)
+        T, top = surface_max(from_fixed(sums[h], q.shape[0]).astype(np.float32), -(ml - 1))
+        if T and top != 0:
+            profile[h + H] = (T[0], np.abs(top), np.float64(top))
+            if best is None or profile[h + H]["abs_corr"] > profile[best + H]["abs_corr"]:
+                best = h
+    best = 0 if best is None else best
+    return best, profile, sums[best]
+
+
+def drift_ppm(h, den, window_len):
+    """the relative clock rate a slope of h / den lags per window of window_len samples stands for, in parts per million"""
+    return 1e6 * float(h) / (float(den) * float(window_len))

@@ -1,0 +1,312 @@
+"""GPU: drift-compensated stacking (tdoa_process_stacked_drift; include/tdoa_mi355x.h, "drift-compensated stacking").
+
+Every comparison with the numpy model (tdoa_amd.stacking) is exact: process_stacked(1, ..., want_partial=True) returns each
+window's fixed-point q word for word, the model turns those into Q_h, the profile, h* and the float surface.
+
+1. the definition: drift, profile, partial and surface are the model's bytes, peaks / count / fine the plain stack's exact
+   relations on Q_{h*};
+2. H = 0 returns process_stacked's bytes;
+3. planted slopes are found, one of them at the edge of the lag range;
+4. the noisy case of tests/test_stack_drift_cpu.py: the plain stack misses, the search finds slope and delay;
+5. the single-look path and many lag tiles, on poisoned workspace;
+   and stacks so long that a workgroup takes four, two or one slope instead of eight;
+6. the step graph stays one chain, replays, and leaves process() and process_stacked() as they were;
+7. argument errors on a live context;
+8. tdoa_processor --stack --drift prints what Context.process_stacked_drift returns."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden")
+ST = [(41.18660274289527, -95.96064116595667, 355.69), (41.24669616513154, -96.08366304481238, 329.0),
+      (41.32916620016985, -96.03513381562004, 373.18)]
+TX = (41.20, -96.00, 400.0)
+K, SEP = 8, 8
+OUTPUTS = ("peaks", "count", "fine", "surface", "partial", "drift", "profile")
+
+
+def _synth(c, n_stations, block):
+    for s in range(n_stations):
+        c.synth_capture(s, block, ST[s % 3], TX, 0x57AC0000 + s)
+
+
+def _same_bytes(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def _drift(c, m, H, D, k=K, sep=SEP, gate=None):
+    return c.process_stacked_drift(m, H, D, k, sep, gate=gate, want_surface=True, want_partial=True)
+
+
+def _check_against_model(c, out, m, H, D, k=K, sep=SEP, gate=None, q=None):
+    """`out` of process_stacked_drift(m, H, D, k, sep, gate) on context c against the model on c's own one-window
+    partials (q, when the caller has them already): no tolerance.  Returns the model's h* [n_stacks][P]."""
+    from tdoa_amd import stacking
+    ml = c.params.max_lag
+    gate = float(ml if gate is None else gate)
+    wpb, _ = c.num_windows()
+    if q is None:
+        q = c.process_stacked(1, 1, 1, want_partial=True)["partial"]       # [W][P][L]: q of every pair-window
+    _, ids = stacking.stack_ids(wpb, m)
+    n_pairs = q.shape[1]
+    assert out["drift"].shape == (len(ids), n_pairs) and out["drift"].dtype == np.int32
+    assert out["profile"].shape == (len(ids), n_pairs, 2 * H + 1)
+    want_h = np.zeros((len(ids), n_pairs), dtype=np.int32)
+    for sid, wins in ids:
+        for p in range(n_pairs):
+            h, profile, qh = stacking.drift_search(q[wins, p], H, D, ml)
+            want_h[sid, p] = h
+            assert int(out["drift"][sid, p]) == h, (sid, p, int(out["drift"][sid, p]), h)
+            assert out["profile"][sid, p].tobytes() == profile.tobytes(), (sid, p)
+            assert np.array_equal(out["partial"][sid, p], qh), (sid, p)
+            c64 = stacking.from_fixed(qh, len(wins))
+            assert out["surface"][sid, p].tobytes() == c64.astype(np.float32).tobytes(), (sid, p)
+            # the plain stack's exact relations (tests/test_gpu_stacked.py), on Q_{h*}
+            cnt = int(out["count"][sid, p])
+            rec = out["peaks"][sid, p]
+            want_sel = stacking.stacked_peaks(c64, ml, k, sep)
+            assert cnt == len(want_sel) and [(int(r["lag"]), float(r["corr"])) for r in rec[:cnt]] == want_sel, (sid, p)
+            at = c64[rec["lag"][:cnt].astype(np.int64) + ml - 1]
+            assert at.tobytes() == rec["corr"][:cnt].tobytes(), (sid, p)
+            assert np.array_equal(rec["abs_corr"][:cnt], np.abs(at).astype(np.float32))
+            assert not rec["lag"][cnt:].any() and not rec["corr"][cnt:].any()
+            f = out["fine"][sid, p]
+            if cnt:
+                assert abs(float(f["delay"]) - stacking.refine(c64, ml, int(rec[0]["lag"]))) <= 1e-9
+                assert int(out["profile"][sid, p, h + H]["lag"]) == int(rec[0]["lag"])
+                assert out["profile"][sid, p, h + H]["abs_corr"] == rec[0]["abs_corr"]
+            assert int(f["plausible"]) == int(abs(float(f["delay"])) <= gate)
+    return want_h
+
+
+def test_definition_against_the_model():
+    """3 stations, 5 windows per block, 1399 lags (two lag tiles, the second partial), stacks of 2 (2 + 2 + 1) and whole
+    blocks, 11 and 7 hypotheses (no multiple of a hypothesis block)"""
+    import tdoa_amd
+    wl, wpb, ml = 10_000, 5, 700
+    with tdoa_amd.Context(max_lag=ml, window_len=wl) as c:
+        _synth(c, 3, wpb * wl)
+        for m in (2, 0):
+            for H, D in ((5, 2), (3, 1)):
+                out = _drift(c, m, H, D, gate=50.0)
+                assert (out["count"] >= 1).all()
+                h = _check_against_model(c, out, m, H, D, gate=50.0)
+                print("m %d H %d D %d: h* %s" % (m, H, D, h.ravel()))
+
+
+def test_no_slopes_is_the_plain_stack():
+    import tdoa_amd
+    wl, wpb, ml = 10_000, 5, 700
+    with tdoa_amd.Context(max_lag=ml, window_len=wl) as c:
+        _synth(c, 3, wpb * wl)
+        for m in (2, 0):
+            want = c.process_stacked(m, K, SEP, gate=50.0, want_surface=True, want_partial=True)
+            got = _drift(c, m, 0, 1, gate=50.0)
+            for key in want:
+                assert _same_bytes(got[key], want[key]), (m, key)
+            assert not got["drift"].any() and got["profile"].shape == (want["count"].shape + (1,))
+            assert np.array_equal(got["profile"][..., 0]["lag"], want["peaks"][..., 0]["lag"])
+            assert np.array_equal(got["profile"][..., 0]["abs_corr"], want["peaks"][..., 0]["abs_corr"])
+
+
+@pytest.mark.parametrize("h0, den, d0", [(3, 2, 7), (-5, 4, 30), (4, 1, -62)])
+def test_planted_slopes(oracle, h0, den, d0):
+    """windows of simulate_delayed_fm at noise 0.02 delayed by d0 + shift(h0, j): the search returns the slope and the
+    delay of the stack's first window.  (4, 1, -62) starts one lag from the edge of the range: terms outside it contribute
+    0, the model decides what is expected."""
+    import tdoa_amd
+    from tdoa_amd import stacking
+    wl, wpb, ml, H = 8192, 6, 64, 8
+    a = [oracle.simulate_delayed_fm(wl, 0, 300 + w, 3000 + w, 1.0, 0.02) for w in range(wpb)]
+    b = [oracle.simulate_delayed_fm(wl, d0 + stacking.shift(h0, w, den), 300 + w, 4000 + w, 1.0, 0.02) for w in range(wpb)]
+    with tdoa_amd.Context(max_lag=ml, window_len=wl) as c:
+        for s, x in enumerate((a, b)):
+            c.capture_upload(s, np.concatenate(x * 3))          # the three blocks repeat the windows
+        assert c.num_windows() == (wpb, 3 * wpb)
+        out = _drift(c, 0, H, den, 2, 2)
+        print("planted %+d/%d at %d: drift %s lag %s" % (h0, den, d0, out["drift"].ravel(), out["peaks"][:, 0, 0]["lag"]))
+        _check_against_model(c, out, 0, H, den, 2, 2)
+        if (h0, den, d0) != (4, 1, -62):
+            assert (out["drift"] == h0).all() and (out["peaks"][:, 0, 0]["lag"] == d0).all()
+
+
+def test_search_finds_the_delay_the_plain_stack_misses(oracle):
+    """the inputs of tests/test_stack_drift_cpu.py (12 windows of 8192 samples at noise 0.7, a slope of 3/2 lag per window
+    from delay 7): process() reproduces the oracle's per-window lags, process_stacked misses 7, the search over H = 8, D = 2
+    returns slope 3 and lag 7 in all three blocks with the float64 model's ratio of peak 1 to peak 2 (1.95) within 1 %"""
+    import tdoa_amd
+    from tdoa_amd import stacking
+    wl, wpb, ml, d0, H, D = 8192, 12, 64, 7, 8, 2
+    delays = [d0 + stacking.shift(3, w, D) for w in range(wpb)]
+    a = [oracle.simulate_delayed_fm(wl, 0, 100 + w, 1000 + w, 1.0, 0.7) for w in range(wpb)]
+    b = [oracle.simulate_delayed_fm(wl, delays[w], 100 + w, 2000 + w, 1.0, 0.7) for w in range(wpb)]
+    q, lags = [], []
+    for w in range(wpb):
+        cw = oracle.b_xcorr_all_lags(oracle.b_preprocess(a[w])[0], oracle.b_preprocess(b[w])[0], ml)
+        lags.append(oracle.b_pick_peak(cw, ml)[0])
+        q.append(stacking.to_fixed(cw))
+    h, _, qh = stacking.drift_search(np.array(q), H, D, ml)
+    want_pk = stacking.stacked_peaks(stacking.from_fixed(qh, wpb), ml, 2, 2)
+    want_ratio = abs(want_pk[0][1]) / abs(want_pk[1][1])
+    assert h == 3 and want_pk[0][0] == d0 and want_ratio >= 1.5
+    with tdoa_amd.Context(max_lag=ml, window_len=wl) as c:
+        for s, x in enumerate((a, b)):
+            c.capture_upload(s, np.concatenate(x * 3))
+        assert [int(x) for x in c.process()["lag"][:, 0]] == lags * 3
+        plain = c.process_stacked(0, 2, 2)
+        out = c.process_stacked_drift(0, H, D, 2, 2)
+        ratio = out["peaks"][:, 0, 0]["abs_corr"].astype(np.float64) / out["peaks"][:, 0, 1]["abs_corr"]
+        print("plain stack lags %s; drift %s lags %s ratios %s (model %.4f)"
+              % (plain["peaks"][:, 0, 0]["lag"], out["drift"].ravel(), out["peaks"][:, 0, 0]["lag"], ratio, want_ratio))
+        assert (plain["peaks"][:, 0, 0]["lag"] != d0).all()
+        assert (out["drift"] == 3).all() and (out["peaks"][:, 0, 0]["lag"] == d0).all() and (out["count"] == 2).all()
+        assert (np.abs(ratio - want_ratio) <= 0.01 * want_ratio).all()
+
+
+def test_single_look_path_and_many_tiles_on_poisoned_workspace():
+    """2 stations, windows of 1 100 000, 2 per block, 39 999 lags: the single-look path (its slot gains enter q) and 40 lag
+    tiles"""
+    import tdoa_amd
+    wl, wpb, ml, H, D = 1_100_000, 2, 20000, 3, 1
+    with tdoa_amd.Context(max_lag=ml, window_len=wl) as c:
+        _synth(c, 2, wpb * wl)
+        c.poison_workspace()
+        out = _drift(c, 0, H, D)
+        assert c.last_route()["once"]
+        for key in ("peaks", "fine", "profile"):
+            for field in out[key].dtype.names:
+                assert np.isfinite(out[key][field]).all(), (key, field)
+        assert np.isfinite(out["surface"]).all()
+        c.poison_workspace()
+        again = _drift(c, 0, H, D)                               # replayed on poisoned workspace
+        assert all(_same_bytes(again[k], out[k]) for k in OUTPUTS)
+        _check_against_model(c, out, 0, H, D)
+
+
+def test_long_stacks_take_fewer_slopes_per_workgroup():
+    """The search stages 4 096 words per window: a tile of 1 024 lags and up to 3 072 of spread between the first and the
+    last slope of a workgroup's block.  With slopes of -1, 0, +1 lag per window the spread at the last window of a stack of
+    m is (b - 1)(m - 1) for a block of b slopes: stacks of 1 100 fit four slopes (3 x 1 099), stacks of 1 600 two (1 599),
+    the whole block of 3 100 windows one.  2 stations, windows of 4 096, 6 199 lags (seven tiles)."""
+    import tdoa_amd
+    wl, wpb, ml = 4096, 3100, 3100
+    with tdoa_amd.Context(max_lag=ml, window_len=wl) as c:
+        _synth(c, 2, wpb * wl)
+        assert c.num_windows() == (wpb, 3 * wpb)
+        q = c.process_stacked(1, 1, 1, want_partial=True)["partial"]
+        for m in (1100, 1600, 0):
+            out = _drift(c, m, 1, 1, 2, 2)
+            h = _check_against_model(c, out, m, 1, 1, 2, 2, q=q)
+            print("m %d: h* %s" % (m, h.ravel()))
+
+
+def test_graph_replays_and_leaves_its_neighbours_alone():
+    import tdoa_amd
+    wl, wpb, ml = 10_000, 5, 700
+    with tdoa_amd.Context(max_lag=ml, window_len=wl) as c:
+        _synth(c, 3, wpb * wl)
+        base = c.process()
+        stack = c.process_stacked(2, K, SEP, want_surface=True, want_partial=True)
+        a = _drift(c, 2, 5, 2)
+        first = c.graph_info()
+        assert first["memsets"] == 0 and first["roots"] == 1
+        b = _drift(c, 2, 5, 2)                                   # the same key: replayed
+        assert c.graph_info() == first
+        assert all(_same_bytes(a[k], b[k]) for k in OUTPUTS)
+        assert _same_bytes(c.process(), base)
+        mid = c.process_stacked(2, K, SEP, want_surface=True, want_partial=True)
+        assert all(_same_bytes(mid[k], stack[k]) for k in stack)
+        other = _drift(c, 2, 3, 1)                               # another (H, D): another graph, another profile shape
+        info = c.graph_info()
+        assert info["memsets"] == 0 and info["roots"] == 1 and other["profile"].shape[-1] == 7
+        again = _drift(c, 2, 5, 2)
+        assert all(_same_bytes(a[k], again[k]) for k in OUTPUTS)
+        assert _same_bytes(c.process(), base)
+        after = c.process_stacked(2, K, SEP, want_surface=True, want_partial=True)
+        assert all(_same_bytes(after[k], stack[k]) for k in stack)
+    with tdoa_amd.Context(max_lag=ml, window_len=wl, windows_per_batch=1) as c:     # a stack spans several launch groups
+        _synth(c, 3, wpb * wl)
+        for (H, D), want in (((5, 2), a), ((3, 1), other)):
+            got = _drift(c, 2, H, D)
+            assert all(_same_bytes(got[k], want[k]) for k in OUTPUTS), (H, D)
+
+
+def test_argument_errors():
+    import tdoa_amd
+    wl, ml = 8192, 64
+    with tdoa_amd.Context(max_lag=ml, window_len=wl) as c:
+        with pytest.raises(tdoa_amd.TdoaError) as e:             # before captures exist
+            c.process_stacked_drift(0, 1, 1)
+        assert e.value.status == 6
+        drift = np.zeros(8, dtype=np.int32)
+        assert c._L.tdoa_process_stacked_drift(c._h, 0, 1, 1, 0.0, 1, 1, None, None, None, None, None,
+                                               drift.ctypes.data_as(c._L.tdoa_process_stacked_drift.argtypes[12]), None) == 6
+        _synth(c, 2, 5 * wl)
+        for kw in ({"drift_den": 0}, {"max_drift": -1}, {"max_drift": 513, "drift_den": 4096}, {"k": 0}, {"k": 17},
+                   {"min_separation": 0}, {"windows_per_stack": -1}, {"gate": -1.0},
+                   {"max_drift": 64, "drift_den": 1}, {"max_drift": 16, "drift_den": 1}):     # shifts 256 and 64 > 63
+            with pytest.raises(tdoa_amd.TdoaError) as e:
+                c.process_stacked_drift(**kw)
+            assert e.value.status == 1, kw
+        assert c._L.tdoa_process_stacked_drift(c._h, 0, 1, 1, 0.0, 1, 1, None, None, None, None, None, None, None) == 1
+        # the limit itself: shift(63, 4) = 63 with whole blocks, and stacks of 2 leave room for 63 lags per window
+        assert c.process_stacked_drift(0, 63, 4)["drift"].shape == (3, 1)
+        assert c.process_stacked_drift(2, 63, 1, want_profile=False)["drift"].shape == (9, 1)
+    with tdoa_amd.Context(max_lag=ml, window_len=wl, lag_mode=tdoa_amd.capi.LAGS_GO) as c:
+        _synth(c, 2, 5 * wl)
+        with pytest.raises(tdoa_amd.TdoaError) as e:
+            c.process_stacked_drift(0, 1, 1)
+        assert e.value.status == 5
+
+
+def test_cli_drift_prints_the_library_result(tmp_path):
+    """tdoa_processor --stack --drift=2 on the golden three-station captures: every STACK line carries the slope and the
+    lag process_stacked_drift returns; without --drift no line changes"""
+    import tdoa_amd
+    from tdoa_amd import stacking
+    tdoa_amd.build.build()
+    cli = tdoa_amd.build.build_cli()
+    csv = tmp_path / "lat-lon-table.csv"
+    csv.write_text("Name,Latitude,Longitude,Elevation\nKEVO,41.30888549464701,-96.02619229605524,356.0\n"
+                   "162400000,41.25703803095629,-95.95512763589404,349.07\nkx0u,41.18660274289527,-95.96064116595667,355.69\n"
+                   "n3pay,41.24669616513154,-96.08366304481238,329.0\nkf0mtl,41.32916620016985,-96.03513381562004,373.18\n")
+    dats = [os.path.join(GOLD, "sim-%s-1754900000.dat" % n) for n in ("kx0u", "n3pay", "kf0mtl")]
+    opts = ["--window", "2000", "--max-lag", "150"]
+    tail = ["162400000", "101700000", str(csv)] + dats
+    r = subprocess.run([cli, "--stack", "--drift=2"] + opts + tail, capture_output=True, text=True, timeout=300)
+    assert r.returncode in (0, 3), r.stderr            # (the 3-station solve may fail on these captures: tests/test_processor_cli.py)
+    rows = re.findall(r"^STACK block (\d) stack (\d+) (\w+) - (\w+): windows=(\d+) delay=(-?\d+) samples refined=(-?[\d.]+) "
+                      r"\|C\|=([\d.]+) ratio=([\d.]+|inf) drift=([+-]\d+)/(\d+) lags/window \(([+-][\d.]+) ppm\)$", r.stdout, flags=re.M)
+    assert len(rows) == 9, r.stdout
+    with tdoa_amd.Context(max_lag=150, window_len=2000) as c:
+        for s, p in enumerate(dats):
+            c.capture_upload_file(s, p)
+        wpb, _ = c.num_windows()
+        assert wpb == 2 and c.num_stacks(0) == (1, 3)
+        out = c.process_stacked_drift(0, 2, 1, 2, 1, gate=120.0)
+    names = ["kx0u", "n3pay", "kf0mtl"]
+    pairs = [(0, 1), (0, 2), (1, 2)]
+    seen = set()
+    for row in rows:
+        block, p = int(row[0]) - 1, pairs.index((names.index(row[2]), names.index(row[3])))
+        seen.add((block, p))
+        rec = out["peaks"][block, p]
+        h = int(out["drift"][block, p])
+        assert int(row[1]) == 0 and int(row[4]) == wpb and int(row[5]) == int(rec[0]["lag"])
+        assert abs(float(row[6]) - float(out["fine"][block, p]["delay"])) <= 5.1e-4
+        assert abs(float(row[7]) - float(rec[0]["abs_corr"])) <= 5.1e-7 + 1e-6 * float(rec[0]["abs_corr"])
+        assert int(row[9]) == h and int(row[10]) == 1
+        assert abs(float(row[11]) - stacking.drift_ppm(h, 1, 2000)) <= 5.1e-4
+    assert len(seen) == 9
+    # the target block's refined delays along the chosen slopes are what the solver is given
+    dt = re.search(r"^Time differences \(μs\): (.*)$", r.stdout, flags=re.M).group(1).split()
+    assert [float(x) for x in dt] == [round(float(out["fine"][1, p]["delay"]) / 2e6 * 1e6, 3) for p in range(3)]
+    plain = subprocess.run([cli, "--stack"] + opts + tail, capture_output=True, text=True, timeout=300)
+    assert plain.returncode in (0, 3) and "drift=" not in plain.stdout
+    assert len(re.findall(r"^STACK block \d stack 0 .* ratio=([\d.]+|inf)$", plain.stdout, flags=re.M)) == 9
