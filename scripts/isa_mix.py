@@ -5,7 +5,7 @@ import collections
 import re
 import sys
 
-HOT = ("k_fwd_col256_k1ILb0ELb1", "k_pair_decimate16", "k_fwd_row4096_unpack", "k_inv_rows_plain_r8", "k_small_col_peak", "k_once_edges")
+HOT = ("k_fwd_col256_k1ILb0ELb1ELb1", "k_pair_decimate16", "k_fwd_row4096_unpack", "k_inv_rows_plain_r8", "k_small_col_peak", "k_once_edges")
 
 
 def main():

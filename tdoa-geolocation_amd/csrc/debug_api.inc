@@ -45,6 +45,17 @@ int tdoa_debug_staged_groups(int n_stations, int max_pairs, uint32_t *masks_out,
     return (int)g.size();
 }
 
+int tdoa_debug_k1_split_table(uint16_t *hi, uint8_t *lo)
+{
+    if (!hi || !lo) return TDOA_ERR_INVALID;
+    std::vector<int32_t> tab, direct, quad;
+    std::vector<uint8_t> split;
+    k1_build_table_host(tab, direct, quad, &split);
+    std::memcpy(lo, split.data(), kK1DirectEntries);
+    std::memcpy(hi, split.data() + kK1DirectEntries, 2 * (size_t)kK1DirectEntries);
+    return TDOA_OK;
+}
+
 int tdoa_debug_step_layout(int n_stations, int n_windows, int rank, int world, int max_per_batch, int32_t *pw_out, int max_pw,
                            int32_t *quads_out, int32_t *n_quads)
 {

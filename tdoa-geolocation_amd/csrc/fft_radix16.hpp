@@ -368,7 +368,7 @@ __device__ __forceinline__ float2 k1_element_from(int a0, int a1, int ap, int i0
 // The memory counter of a wave retires in order: with the stores at the end of a trip and the loads at the top of the next,
 // the first lookup waited for every store before it to be acknowledged (and 256 store instructions left the CU at once).
 // grid (n_cu), 1024 threads, dynamic LDS 64 KB (table) + 64 KB (plane [256][64]).
-constexpr size_t kColK1Lds = kK1QuadrantBytes + sizeof(float) * 256 * 64;
+constexpr size_t kColK1Lds = kK1QuadrantBytes + sizeof(float) * 256 * 64;      // (the split form of either kernel: kK1SplitLds)
 
 // Which tile a workgroup takes as its seq-th: workgroups go to the XCDs round-robin (seq % 8, the grid is a multiple of 8).
 // A window may start on any 2-byte boundary, in which case the 256-byte row pieces of adjacent column blocks share a cache
@@ -416,7 +416,9 @@ __device__ __forceinline__ void col_k1_fetch(const ColK1Tile &t, int G, int N1, 
     sb = t.p[ib >= 0 && ib < t.len ? ib : 0];                                        // if the window has one
 }
 
-// rows of a tile whose table reads are in flight together (2 reads per row): 4 -> 8 reads; TDOA_COL_BATCH=8 for an A/B
+// rows of a tile whose table reads are in flight together -- quadrant table: 2 reads per row, 4 rows -> 8 reads; split
+// table: 4 sub-dword reads per row, 4 rows -> 16 reads; TDOA_COL_BATCH=2 / 8 for an A/B
+// (split table, 4 reads per row, cfg2 step: 2 rows 2.468 ms, 4 rows 2.4625, 8 rows 2.480 -- profiles/r07_k1_split_ab.json)
 #ifndef TDOA_COL_BATCH
 #define TDOA_COL_BATCH 4
 #endif
@@ -450,16 +452,24 @@ __device__ __forceinline__ void batch_general(F &f, int g, std::integer_sequence
 // (Round 4 also built this kernel with the whole 128 KB half-plane table in LDS -- 5.5 instructions per look-up instead of
 // 13 -- next to an exchange plane of half the tile: bit-identical results, 2 % SLOWER on cfg2 / cfg4 / cfg3, because the
 // half plane doubles the exchange's barriers (8 per tile) and LDS instructions.  Commit f53a7d8)
-template <bool SUB, bool ONCE = false>
+// SPLIT (round 7): the look-up is k1_split_angle2 on the 96 KB split half-plane table -- 11 vector instructions per dword
+// instead of 22 -- and the LDS holds the WHOLE plane at address 0, then the table (k1_discriminator.hpp: 160 KB, the four
+// barriers of the exchange stay); `table` is then the 96 KB lo | hi array.  Same angles modulo a turn: same results.
+template <bool SUB, bool ONCE = false, bool SPLIT = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_fwd_col256_k1(const SWDesc *__restrict__ sw, const int *__restrict__ table, const FmStats *__restrict__ stats, float2 *__restrict__ T,
                                                        FftPlan pl, int n_sw, OnceTile *__restrict__ once_tiles)
 {
     constexpr int LOGW = 6, W = 1 << LOGW;                      // 64 columns per tile
-    constexpr int kTableEntries = kK1QuadrantEntries;
-    extern __shared__ int lds_k1[];                             // the table at offset 0 (the offset IS the address), then the plane
-    int *lut = lds_k1;
-    float *plane = reinterpret_cast<float *>(lds_k1 + kTableEntries);           // [256][W]
-    k1_assert_lds0(lut);
+    constexpr int kTableEntries = kK1QuadrantEntries;           // (quadrant form)
+    // the kernel's only LDS, from address 0.  Quadrant form: the table (an entry's offset IS its address), then the plane.
+    // SPLIT: the plane, then at kK1SplitLoAddr the table's lo | hi arrays (k1_split_read builds their addresses).
+    extern __shared__ int lds_k1[];
+    int *lut = lds_k1;                                          // quadrant table (unused in the split form)
+    int *split_table = lds_k1 + kK1SplitLoAddr / 4;
+    float *plane = reinterpret_cast<float *>(SPLIT ? lds_k1 : lds_k1 + kTableEntries);           // [256][W]
+    static_assert(sizeof(float) * 256 * W == kK1SplitLoAddr, "the split table follows the plane");
+    if (SPLIT) k1_assert_split_lds(lds_k1, split_table);
+    else k1_assert_lds0(lut);
     const int G = SUB ? pl.N2 >> 8 : 1;
     const int N1 = pl.N1, nbx = N1 >> LOGW;
     const int n_tiles = n_sw * G * nbx;
@@ -470,8 +480,12 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
         col_k1_fetch<LOGW>(col_k1_tile<SUB>(sw, col_k1_order(blockIdx.x, nbx), nbx, G), G, N1, j, tid & (W - 1),
                            j, lane & 15, raw_next, sb_next);
     }
-    for (int k = threadIdx.x; k < kTableEntries / 4; k += blockDim.x)
-        reinterpret_cast<int4 *>(lut)[k] = reinterpret_cast<const int4 *>(table)[k];
+    if (SPLIT)
+        for (int k = threadIdx.x; k < (int)(kK1SplitBytes / 16); k += blockDim.x)
+            reinterpret_cast<int4 *>(split_table)[k] = reinterpret_cast<const int4 *>(table)[k];
+    else
+        for (int k = threadIdx.x; k < kTableEntries / 4; k += blockDim.x)
+            reinterpret_cast<int4 *>(lut)[k] = reinterpret_cast<const int4 *>(table)[k];
     __syncthreads();
     const float2 wj = unit_root((float)(threadIdx.x >> LOGW), 2.0f / 256.0f, false);      // W_256^j: the thread's item never changes
     float2 v[16];                                                // the previous tile's outputs until they are stored (below)
@@ -498,7 +512,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
 #pragma unroll
             for (int r = 0; r < 16; r++) raw[r] = raw_next[r];
             // boundary samples: lane L took row r = L & 15 of the wave's item
-            const int ab = k1_angle_quadrant<false, true>(k1_index_bytes(sb_next), ~sb_next, lut);
+            const int ab = SPLIT ? k1_split_angle(sb_next) : k1_angle_quadrant<false, true>(k1_index_bytes(sb_next), ~sb_next, lut);
             // rows are classified per wave (it holds item j of every r): entirely inside the window -- no bounds selects,
             // the common case --, entirely beyond it -- zero padding, nothing to look up (40 % of the rows of a 10 s window
             // in N = 2^25) --, or general
@@ -514,7 +528,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
                     return;
                 }
                 int a0, a1;
-                k1_angle2_quadrant<true>(raw[r], lut, a0, a1);
+                if (SPLIT) k1_split_angle2(raw[r], a0, a1);
+                else k1_angle2_quadrant<true>(raw[r], lut, a0, a1);
                 // the angle of sample 2m - 1 is the left lane's second angle; lane 0 keeps `old` = the boundary sample's
                 const int bnd = __builtin_amdgcn_readlane(ab, r);
                 const int ap = __builtin_amdgcn_update_dpp(bnd, a1, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
@@ -536,6 +551,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
             // workgroup's first trip v[] is zero and goes to the place of THIS tile, which the same thread overwrites with the
             // real values one trip later (one wave's stores to an address stay in order).
             // When the four rows lie inside the window (all but the window's first row and its tail) their EIGHT table reads
+            // (split table: sixteen sub-dword reads)
             // are issued back to back and only then placed: one read followed by its placement (the form above) waits out the
             // LDS latency for every sample while the CU's sixteen waves all queue at the LDS at the same time.
 #pragma unroll
@@ -545,20 +561,30 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
                 const int i_first0 = 2 * ((a + G * (jw + 16 * (kColBatch * g))) * N1 + (t.bx << LOGW));
                 const int i_end3 = 2 * ((a + G * (jw + 16 * (kColBatch * g + kColBatch - 1))) * N1 + (t.bx << LOGW)) + 2 * W;
                 if (__builtin_expect(i_first0 > 0 && i_end3 <= len, 1)) {
-                    unsigned int neg[kColBatch];
-                    int c0[kColBatch], c1[kColBatch];
+                    unsigned int neg[kColBatch];                        // (SPLIT: the reflection masks)
+                    int c0[kColBatch], c1[kColBatch], d0[kColBatch], d1[kColBatch];      // (SPLIT: hi parts, lo parts)
 #pragma unroll
                     for (int q = 0; q < kColBatch; q++) {
-                        const unsigned int x = k1_index_bytes(raw[kColBatch * g + q]);
-                        neg[q] = ~raw[kColBatch * g + q];
-                        c0[q] = k1_table_read<true>(lut, k1_quadrant_offset<false>(x));
-                        c1[q] = k1_table_read<true>(lut, k1_quadrant_offset<true>(x));
+                        if constexpr (SPLIT) {
+                            unsigned int h0, l0, h1, l1;
+                            neg[q] = k1_split_mask(raw[kColBatch * g + q]);
+                            const unsigned int fw = raw[kColBatch * g + q] ^ neg[q];
+                            k1_split_read<false>(fw, h0, l0);
+                            k1_split_read<true>(fw, h1, l1);
+                            c0[q] = (int)h0; d0[q] = (int)l0; c1[q] = (int)h1; d1[q] = (int)l1;
+                        } else {
+                            const unsigned int x = k1_index_bytes(raw[kColBatch * g + q]);
+                            neg[q] = ~raw[kColBatch * g + q];
+                            c0[q] = k1_table_read<true>(lut, k1_quadrant_offset<false>(x));
+                            c1[q] = k1_table_read<true>(lut, k1_quadrant_offset<true>(x));
+                        }
                     }
-                    __builtin_amdgcn_sched_barrier(0);                  // (the eight reads stay ahead of their placements)
+                    __builtin_amdgcn_sched_barrier(0);                  // (the batch's 8 / 16 reads stay ahead of their placements)
 #pragma unroll
                     for (int q = 0; q < kColBatch; q++) {
                         const int r = kColBatch * g + q;
-                        const int a0 = k1_quadrant_place<false>(c0[q], neg[q]), a1 = k1_quadrant_place<true>(c1[q], neg[q]);
+                        const int a0 = SPLIT ? k1_split_place<false>((unsigned int)c0[q], (unsigned int)d0[q], neg[q]) : k1_quadrant_place<false>(c0[q], neg[q]);
+                        const int a1 = SPLIT ? k1_split_place<true>((unsigned int)c1[q], (unsigned int)d1[q], neg[q]) : k1_quadrant_place<true>(c1[q], neg[q]);
                         const int bnd = __builtin_amdgcn_readlane(ab, r);
                         const int ap = __builtin_amdgcn_update_dpp(bnd, a1, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
                         const int st0 = k1_stored_code_scaled(a0, ap), st1 = k1_stored_code_scaled(a1, a0);
@@ -848,7 +874,7 @@ __global__ __launch_bounds__(512) void k_fwd_colx_c16(const SWDesc *sw, const in
 // par = t >> 9) transforms the rows n2 = 2 (j + 16 r) + par; a wave holds two consecutive items j of one parity (one per
 // half-wave), so the left-lane angle sharing runs inside a half-wave and the 32 boundary samples of a wave (16 rows x 2
 // items) are looked up by its lanes 0..31 and handed out by a lane permute.
-// grid (n_cu), 1024 threads, dynamic LDS 64 KB (table) + 64 KB (planes [2][256][32]).
+// grid (n_cu), 1024 threads, dynamic LDS 64 KB (table) + 64 KB (planes [2][256][32]); SPLIT: planes, then 96 KB of table.
 // ---------------------------------------------------------------------------
 constexpr size_t kCol512Lds = kK1QuadrantBytes + sizeof(float) * 2 * 256 * 32;
 
@@ -883,20 +909,27 @@ __device__ __forceinline__ void col512_fetch(const Col512Tile &t, int N1, int ti
     sb = t.p[ib >= 0 && ib < t.len ? ib : 0];
 }
 
-template <bool ONCE = false>
+// SPLIT: as in k_fwd_col256_k1 -- the planes at address 0, then the 96 KB split half-plane table; `qtable` is that table
+template <bool ONCE = false, bool SPLIT = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_fwd_col512_k1(const SWDesc *__restrict__ sw, const int *__restrict__ qtable, const FmStats *__restrict__ stats,
                                                        float2 *__restrict__ T, FftPlan pl, int n_sw, OnceTile *__restrict__ once_tiles)
 {
     constexpr int F = 2, C = 32, LOGC = 5;
-    extern __shared__ int lds_k1[];                             // the table at offset 0 (the offset IS the address), then the planes
-    int *lut = lds_k1;
-    float *plane = reinterpret_cast<float *>(lds_k1 + kK1QuadrantEntries);      // [F][256][C]
-    k1_assert_lds0(lut);
+    // the kernel's only LDS, from address 0: the quadrant table, then the planes; SPLIT: the planes, then the table's lo | hi
+    // arrays at kK1SplitLoAddr (see k_fwd_col256_k1)
+    extern __shared__ int lds_k1[];
+    int *lut = lds_k1;                                          // quadrant table (unused in the split form)
+    int *split_table = lds_k1 + kK1SplitLoAddr / 4;
+    float *plane = reinterpret_cast<float *>(SPLIT ? lds_k1 : lds_k1 + kK1QuadrantEntries);      // [F][256][C]
+    static_assert(sizeof(float) * F * 256 * C == kK1SplitLoAddr, "the split table follows the planes");
+    if (SPLIT) k1_assert_split_lds(lds_k1, split_table);
+    else k1_assert_lds0(lut);
     const int N1 = pl.N1, nbx = N1 / C;
     const int n_tiles = n_sw * nbx;
     unsigned int raw_next[16], sb_next = 0;
     if ((int)blockIdx.x < n_tiles) col512_fetch(col512_tile(sw, col_k1_order(blockIdx.x, nbx), nbx), N1, threadIdx.x, raw_next, sb_next);
-    for (int k = threadIdx.x; k < kK1QuadrantEntries; k += blockDim.x) lut[k] = qtable[k];
+    for (int k = threadIdx.x; k < (int)(SPLIT ? kK1SplitBytes / 4 : kK1QuadrantEntries); k += blockDim.x)
+        (SPLIT ? split_table : lut)[k] = qtable[k];
     __builtin_amdgcn_s_waitcnt(0x0f70);                          // vmcnt(0): the loop is entered with nothing pending
     __syncthreads();
     // thread constants: the item's stage twiddle W_256^j and the parity twiddle W_512^j (odd rows only)
@@ -924,7 +957,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
             unsigned int raw[16];
 #pragma unroll
             for (int r = 0; r < 16; r++) raw[r] = raw_next[r];
-            const int ab = k1_angle_quadrant<false, true>(k1_index_bytes(sb_next), ~sb_next, lut);
+            const int ab = SPLIT ? k1_split_angle(sb_next) : k1_angle_quadrant<false, true>(k1_index_bytes(sb_next), ~sb_next, lut);
             const int jw = __builtin_amdgcn_readfirstlane(j & ~1), pw = __builtin_amdgcn_readfirstlane(par);
             double t1 = 0.0, t2 = 0.0;                            // ONCE: exact sums of this thread's stored codes
             auto row_general = [&](auto r_c) {
@@ -936,7 +969,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
                     return;
                 }
                 int a0, a1;
-                k1_angle2_quadrant<true>(raw[r], lut, a0, a1);
+                if (SPLIT) k1_split_angle2(raw[r], a0, a1);
+                else k1_angle2_quadrant<true>(raw[r], lut, a0, a1);
                 const int left = wave_shift_right1(a1);
                 const int bnd = __shfl(ab, 2 * r + (lane >> LOGC), kWave);
                 const int ap = c ? left : bnd;
@@ -953,7 +987,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
                                                        &t1, &t2);
                 }
             };
-            // rows four at a time, their eight table reads in flight together (see k_fwd_col256_k1)
+            // rows four at a time, their eight (split table: sixteen) table reads in flight together (see k_fwd_col256_k1)
 #pragma unroll
             for (int g = 0; g < 16 / kColBatch; g++) {
 #pragma unroll
@@ -961,20 +995,30 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4))) vo
                 const int i_first0 = 2 * ((F * (jw + 16 * (kColBatch * g)) + pw) * N1 + t.bx * C);
                 const int i_end3 = 2 * ((F * (jw + 1 + 16 * (kColBatch * g + kColBatch - 1)) + pw) * N1 + t.bx * C + C);
                 if (__builtin_expect(i_first0 > 0 && i_end3 <= len, 1)) {
-                    unsigned int neg[kColBatch];
-                    int c0[kColBatch], c1[kColBatch];
+                    unsigned int neg[kColBatch];                        // (SPLIT: the reflection masks)
+                    int c0[kColBatch], c1[kColBatch], d0[kColBatch], d1[kColBatch];      // (SPLIT: hi parts, lo parts)
 #pragma unroll
                     for (int q = 0; q < kColBatch; q++) {
-                        const unsigned int x = k1_index_bytes(raw[kColBatch * g + q]);
-                        neg[q] = ~raw[kColBatch * g + q];
-                        c0[q] = k1_table_read<true>(lut, k1_quadrant_offset<false>(x));
-                        c1[q] = k1_table_read<true>(lut, k1_quadrant_offset<true>(x));
+                        if constexpr (SPLIT) {
+                            unsigned int h0, l0, h1, l1;
+                            neg[q] = k1_split_mask(raw[kColBatch * g + q]);
+                            const unsigned int fw = raw[kColBatch * g + q] ^ neg[q];
+                            k1_split_read<false>(fw, h0, l0);
+                            k1_split_read<true>(fw, h1, l1);
+                            c0[q] = (int)h0; d0[q] = (int)l0; c1[q] = (int)h1; d1[q] = (int)l1;
+                        } else {
+                            const unsigned int x = k1_index_bytes(raw[kColBatch * g + q]);
+                            neg[q] = ~raw[kColBatch * g + q];
+                            c0[q] = k1_table_read<true>(lut, k1_quadrant_offset<false>(x));
+                            c1[q] = k1_table_read<true>(lut, k1_quadrant_offset<true>(x));
+                        }
                     }
-                    __builtin_amdgcn_sched_barrier(0);                  // (the eight reads stay ahead of their placements)
+                    __builtin_amdgcn_sched_barrier(0);                  // (the batch's 8 / 16 reads stay ahead of their placements)
 #pragma unroll
                     for (int q = 0; q < kColBatch; q++) {
                         const int r = kColBatch * g + q;
-                        const int a0 = k1_quadrant_place<false>(c0[q], neg[q]), a1 = k1_quadrant_place<true>(c1[q], neg[q]);
+                        const int a0 = SPLIT ? k1_split_place<false>((unsigned int)c0[q], (unsigned int)d0[q], neg[q]) : k1_quadrant_place<false>(c0[q], neg[q]);
+                        const int a1 = SPLIT ? k1_split_place<true>((unsigned int)c1[q], (unsigned int)d1[q], neg[q]) : k1_quadrant_place<true>(c1[q], neg[q]);
                         const int left = wave_shift_right1(a1);
                         const int bnd = __shfl(ab, 2 * r + (lane >> LOGC), kWave);
                         const int ap = c ? left : bnd;

@@ -139,6 +139,7 @@ struct FmRoute {
     Inverse inv = Inverse::None;
     PairStep step = PairStep::Tiles;
     bool fused_k1 = false, once = false, pruned = false, seg_quads = false, seg_pack3 = false, small_fused = false;
+    bool k1_split = false;           // the fused column kernel looks angles up in the split half-plane table (160 KB of LDS)
     bool dec_tables = false;         // the decimated inverse applies: its filter and the staged tables are set up
     int fk = 0, np = 0, nn = 0, np2 = 0, nn2 = 0, seg_pq = 0, seg_chunks = 0;
     int shares = kSharesTiles;       // where the small plan's row pass finds the neighbours' shares (kShares*, fft_radix8.hpp)
@@ -215,6 +216,8 @@ FmRoute plan_fm_batch(const Knobs &k, const StgTables &t, int n_cu, const FftPla
     else if (pl.N2 >= 16 && pl.N2 <= 128) { r.col = ColPass::Short16x; r.col_f = pl.N2 / 16; }      // k_fwd_col16x_c16<F>
     else if (pl.N2 == 512 || pl.N2 == 1024) { r.col = ColPass::Colx; r.col_f = pl.N2 / 256; }     // last radix of k_fwd_colx_c16
     else r.col = ColPass::Generic;
+    // (the 4096 x 512 plan's kernel keeps the quadrant table unless asked: measured slower with the split one, knobs.hpp)
+    r.k1_split = k.k1_split && (r.col == ColPass::K1_256 || r.col == ColPass::K1_TwoSweep || (r.col == ColPass::K1_512 && k.k1_split_512));
     // XCD-aware 1-D grid of the pair kernel when every window of the group carries the same `pairs_per_window` > S pairs
     // (window-major sharding with more pairs than stations): see k_inv_row_pair4096
     // ... or when a window's spectra are too large to wait in the Infinity Cache for their second reader (cfg3: 3 x 134 MB per
@@ -424,7 +427,7 @@ void launch_fwd_cols(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
     const FftPlan &pl = r.pl;
     const int n_sw = r.b.n_sw;
     auto *tiles = r.once ? ctx->once_tiles.as<OnceTile>() : nullptr;
-    const auto *qtable = ctx->k1_quad.as<const int>();
+    const auto *qtable = r.k1_split ? ctx->k1_split.as<const int>() : ctx->k1_quad.as<const int>();
     const bool two_sweep = r.col == ColPass::K1_TwoSweep || r.col == ColPass::TwoSweep;
     const size_t lds16 = sizeof(float2) * 256 * 32;
     {
@@ -433,16 +436,17 @@ void launch_fwd_cols(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
         switch (r.col) {
         case ColPass::K1_256:
         case ColPass::K1_TwoSweep:
-            with_bool(two_sweep, [&](auto sub) { with_bool(r.once, [&](auto once) {
-                hipLaunchKernelGGL((k_fwd_col256_k1<decltype(sub)::value, decltype(once)::value>), dim3(ctx->n_cu), dim3(1024), kColK1Lds,
-                                   bf.st, bf.sw, qtable, bf.stats, bf.tz, pl, n_sw, tiles);
-            }); });
+            with_bool(two_sweep, [&](auto sub) { with_bool(r.once, [&](auto once) { with_bool(r.k1_split, [&](auto split) {
+                hipLaunchKernelGGL((k_fwd_col256_k1<decltype(sub)::value, decltype(once)::value, decltype(split)::value>), dim3(ctx->n_cu),
+                                   dim3(1024), decltype(split)::value ? kK1SplitLds : kColK1Lds, bf.st, bf.sw, qtable, bf.stats, bf.tz, pl,
+                                   n_sw, tiles);
+            }); }); });
             break;
         case ColPass::K1_512:
-            with_bool(r.once, [&](auto once) {
-                hipLaunchKernelGGL(k_fwd_col512_k1<decltype(once)::value>, dim3(ctx->n_cu), dim3(1024), kCol512Lds, bf.st, bf.sw, qtable,
-                                   bf.stats, bf.tz, pl, n_sw, tiles);
-            });
+            with_bool(r.once, [&](auto once) { with_bool(r.k1_split, [&](auto split) {
+                hipLaunchKernelGGL((k_fwd_col512_k1<decltype(once)::value, decltype(split)::value>), dim3(ctx->n_cu), dim3(1024),
+                                   decltype(split)::value ? kK1SplitLds : kCol512Lds, bf.st, bf.sw, qtable, bf.stats, bf.tz, pl, n_sw, tiles);
+            }); });
             break;
         case ColPass::C256:
             hipLaunchKernelGGL(k_fwd_col256_c16<false>, dim3(pl.N1 / 32, n_sw), dim3(512), lds16, bf.st, bf.sw, bf.codes, r.code_stride,
@@ -679,7 +683,8 @@ void route_info(const FmRoute &r, int32_t out[16])
 {
     const int32_t v[16] = {(int32_t)r.inv, (int32_t)r.step, (int32_t)r.col, (int32_t)r.row, r.fk, r.seg_pq, r.seg_quads, r.seg_pack3,
                            r.fused_k1, r.once, r.small_fused, r.pruned, r.xcd_pairs > 0, r.dec_gp > 0, r.stg.folded,
-                           (r.stg.blocked ? TDOA_ROUTE_STG_BLOCKED_BIT : 0) | (r.stg.merged ? TDOA_ROUTE_STG_MERGED_BIT : 0)};
+                           (r.stg.blocked ? TDOA_ROUTE_STG_BLOCKED_BIT : 0) | (r.stg.merged ? TDOA_ROUTE_STG_MERGED_BIT : 0) |
+                               (r.k1_split ? TDOA_ROUTE_K1_SPLIT_BIT : 0)};
     std::memcpy(out, v, sizeof(v));
 }
 
@@ -749,6 +754,21 @@ int allow_big_lds(tdoa_ctx *ctx)
     if ((rc = set_lds(ctx, (k_fwd_col256_k1<false, true>), all))) return rc;
     if ((rc = set_lds(ctx, (k_fwd_col256_k1<true, true>), all))) return rc;
     if ((rc = set_lds(ctx, k_fwd_col_c16, all))) return rc;
+    {   // the split-table forms of the fused column kernels take the CU's whole LDS.  A device that refuses the size runs the
+        // quadrant forms above instead (tdoa_create clears Knobs::k1_split): not an error.
+        hipError_t e = hipSuccess;
+        auto ask = [&](auto kernel) {
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kK1SplitLds);
+        };
+        for_ints<0, 1>([&](auto once) {
+            ask(k_fwd_col512_k1<(bool)decltype(once)::value, true>);
+            ask(k_fwd_col256_k1<false, (bool)decltype(once)::value, true>);
+            ask(k_fwd_col256_k1<true, (bool)decltype(once)::value, true>);
+        });
+        if (e != hipSuccess) (void)hipGetLastError();
+        ctx->k1_split_lds = e == hipSuccess;
+    }
     if ((rc = set_lds(ctx, k_fwd_row, all))) return rc;
     if ((rc = set_lds(ctx, k_inv_row_pair, all))) return rc;
     if ((rc = set_lds(ctx, k_inv_col_peak, all))) return rc;

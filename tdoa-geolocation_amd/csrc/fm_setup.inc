@@ -7,7 +7,10 @@ namespace {
 // The K1 angle table (k1_discriminator.hpp): first-octant directions (mn, mx), index mx (mx + 1) / 2 + mn over the
 // indices of the odd magnitudes 2 idx + 1; entry = llround(atan2(mn', mx') 2^23 / pi) of the gcd-reduced pair, float64.
 // (oracle/tdoa_oracle.c: ob_octant_code states the same expression; tests compare the device's codes with it bit for bit)
-void k1_build_table_host(std::vector<int32_t> &tab, std::vector<int32_t> &direct, std::vector<int32_t> &quad)
+// `split` (optional): the direct table in three bytes per angle, as the fused column kernels keep it in LDS -- lo[i] =
+// direct[i] & 0xff (32768 uint8), then hi[i] = direct[i] >> 8 (32768 uint16, < 2^15), same index: kK1SplitBytes
+void k1_build_table_host(std::vector<int32_t> &tab, std::vector<int32_t> &direct, std::vector<int32_t> &quad,
+                         std::vector<uint8_t> *split = nullptr)
 {
     tab.resize(kK1TableEntries);
     for (int mx = 0; mx < 128; mx++)
@@ -39,6 +42,15 @@ void k1_build_table_host(std::vector<int32_t> &tab, std::vector<int32_t> &direct
             const int c = tab[(size_t)mx * (mx + 1) / 2 + mn];
             quad[(size_t)iq * 128 + ia] = (iq > ia ? (kK1Half >> 1) - c : c) * 256;      // scaled: a full turn = 2^32
         }
+    if (split) {
+        split->resize(kK1SplitBytes);
+        uint8_t *lo = split->data();
+        uint16_t *hi = reinterpret_cast<uint16_t *>(split->data() + kK1DirectEntries);
+        for (int i = 0; i < kK1DirectEntries; i++) {
+            lo[i] = (uint8_t)(direct[i] & 0xff);
+            hi[i] = (uint16_t)(direct[i] >> 8);
+        }
+    }
 }
 
 // ---- decimated inverse (fft_radix8.hpp, k_pair_decimate16) ----------------------------------------------------------

@@ -19,8 +19,9 @@
 // 0 <= mn <= mx <= 127 (index of the odd magnitudes |2b - 255| = 2 idx + 1): 8256 int32, built by the HOST in float64
 // (tdoa_mi355x.hip, k1_build_table_host).  The kernels keep tables DERIVED from it by the host with the integer placement
 // rules (|Q| > |I|: 2^22 - c; I < 0: 2^23 - c; Q < 0: -c) in LDS: the first-quadrant table of the column kernels (128 x 128
-// entries, scaled by 256, k1_angle_quadrant) and the half-plane table of the streaming pass (32768 entries,
-// k1_direct_angle2).  (Round 3 started with the 33 KB first-octant table itself in LDS and a 17-instruction lookup pinned
+// entries, scaled by 256, k1_angle_quadrant; since round 7 behind TDOA_K1_QUAD_TABLE=1), the half-plane table of the
+// streaming pass (32768 entries, k1_direct_angle2) and the same half plane in three bytes per angle, k_fwd_col256_k1's
+// default and k_fwd_col512_k1's under TDOA_K1_SPLIT_512=1 (k1_split_angle2).  (Round 3 started with the 33 KB first-octant table itself in LDS and a 17-instruction lookup pinned
 // in inline assembly; the 11-instruction quadrant lookup replaced it once the column kernels became one workgroup per CU.)
 //
 // Two ways the codes reach the transforms:
@@ -146,6 +147,82 @@ __device__ __forceinline__ int k1_direct_angle(unsigned int s, const int *dlut)
     int a0, a1;
     k1_direct_angle2(s | 0x80000000u, dlut, a0, a1);                           // (high half: any sample with Q > 0)
     return a0;
+}
+
+// The column kernels' SPLIT half-plane table (round 7): the same 32768 half-plane angles a, 0 < a < 2^23, in three bytes
+// each -- hi[i] = a >> 8 as uint16 (64 KB) and lo[i] = a & 0xff as uint8 (32 KB), same index i = b_I | (b_Q & 0x7f) << 8 --,
+// 96 KB that fit next to the WHOLE 64 KB exchange plane of a column kernel in the 160 KB of a CU (the 128 KB int32 table
+// left room for half a plane only: twice the exchange's barriers, round 4).  LDS layout of such a kernel, which has no
+// static LDS (k1_assert_lds0): the plane at address 0, lo at 0x10000, hi at 0x18000.  A reflected sample's 16-bit word
+// lies in 0x8000 .. 0xffff (b_Q >= 128), so  word + 0x8000  and  2 word + 0x8000  ARE the two addresses, and the constant
+// goes into the LDS instructions' offset field.  The two parts combine to hi << 16 | lo << 8 = 256 a, the scaled angle
+// of the quadrant form (a full turn = 2^32); the half turn of a reflected sample is bit 31.
+// Per dword (two samples): 3 instructions for the reflection, 4 for the addresses, 4 LDS reads, 4 to combine and place --
+// 11 vector instructions against 22 of the quadrant form (k1_index_bytes, ~w, 2 x (3 + 6)).
+// In halves like the quadrant form, so that a batch's reads are issued before their placements: k1_split_mask (per dword),
+// k1_split_read<HI> (addresses + the two reads, plain C++ loads: the compiler places the s_waitcnt), k1_split_place<HI>.
+constexpr unsigned int kK1SplitLoAddr = 0x10000u, kK1SplitHiAddr = 0x18000u;
+constexpr size_t kK1SplitBytes = 3 * (size_t)kK1DirectEntries;          // 98 304: lo[32768] uint8, then hi[32768] uint16
+constexpr size_t kK1SplitLds = kK1SplitLoAddr + kK1SplitBytes;          // 163 840: plane + table = the CU's LDS
+static_assert(kK1SplitHiAddr == kK1SplitLoAddr + kK1DirectEntries && kK1SplitLds == 160 * 1024, "split table layout");
+
+// the split layout's form of k1_assert_lds0: the dynamic segment `seg` (the plane first) starts at LDS address 0 and the
+// table the kernel copied to `table` sits at the addresses k1_split_read builds
+__device__ __forceinline__ void k1_assert_split_lds(const int *seg, const int *table)
+{
+    k1_assert_lds0(seg);
+    if ((unsigned int)(uintptr_t)(const __attribute__((address_space(3))) int *)table != kK1SplitLoAddr) __builtin_trap();
+}
+
+// per 16-bit half of w: 0xffff if Q < 0 (the sample is looked up reflected), else 0
+__device__ __forceinline__ unsigned int k1_split_mask(unsigned int w)
+{
+    typedef short short2v __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(unsigned int, __builtin_bit_cast(short2v, ~w) >> (short)15);      // v_not, v_pk_ashrrev_i16
+}
+
+// the two table parts of one sample of the REFLECTED dword fw = w ^ k1_split_mask(w)
+template <bool HI>
+__device__ __forceinline__ void k1_split_read(unsigned int fw, unsigned int &hi, unsigned int &lo)
+{
+    const unsigned int word = HI ? fw >> 16 : fw & 0xffffu;                   // 0x8000 .. 0xffff
+#if defined(__HIP_DEVICE_COMPILE__)      // (an LDS pointer is 32 bits wide in the device pass only)
+    hi = *__builtin_bit_cast(const __attribute__((address_space(3))) unsigned short *, 2u * word + (kK1SplitHiAddr - 0x10000u));
+    lo = *__builtin_bit_cast(const __attribute__((address_space(3))) unsigned char *, word + (kK1SplitLoAddr - 0x8000u));
+#else
+    hi = lo = word;
+#endif
+}
+
+// scaled angle of that sample from its parts; pm = k1_split_mask(w)
+template <bool HI>
+__device__ __forceinline__ int k1_split_place(unsigned int hi, unsigned int lo, unsigned int pm)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const unsigned int a = __builtin_amdgcn_perm(hi, lo, 0x0504000cu);      // hi << 16 | lo << 8 (v_perm_b32: bytes 0, lo.0, hi.0, hi.1)
+#else
+    const unsigned int a = hi << 16 | lo << 8;
+#endif
+    return (int)(a | (HI ? pm & 0x80000000u : pm << 31));                      // + half a turn if reflected
+}
+
+// the two samples of a dword / one sample s = b_I | b_Q << 8: scaled angles, modulo 2^32
+__device__ __forceinline__ void k1_split_angle2(unsigned int w, int &a0, int &a1)
+{
+    const unsigned int pm = k1_split_mask(w), fw = w ^ pm;
+    unsigned int h0, l0, h1, l1;
+    k1_split_read<false>(fw, h0, l0);
+    k1_split_read<true>(fw, h1, l1);
+    a0 = k1_split_place<false>(h0, l0, pm);
+    a1 = k1_split_place<true>(h1, l1, pm);
+}
+
+__device__ __forceinline__ int k1_split_angle(unsigned int s)
+{
+    const unsigned int pm = k1_split_mask(s), fw = s ^ pm;
+    unsigned int h, l;
+    k1_split_read<false>(fw, h, l);
+    return k1_split_place<false>(h, l, pm);
 }
 
 // lane i takes the value of lane i - 1 (lane 0 keeps its own): one DPP move

@@ -15,7 +15,7 @@ struct Knobs {
     bool force_generic = false, use_graph = true, short_lag = true, segment_form = true, segment_quads = true, decimate = true,
          k1_once = true, pow2_only = false, fused_k1 = true, dec_cols = true, dec_cols_always = false, dec_staged = true,
          small_fused = true, small_fused_always = false, stg_folded = true, stg_folded_always = false, stg_blocks = true,
-         seg_pack3 = true, memset_nodes = false, xcd_rows = true, stg_merge = true;
+         seg_pack3 = true, memset_nodes = false, xcd_rows = true, stg_merge = true, k1_split = true, k1_split_512 = false;
     int zpad = 256, stg_loaders = 0, stg_rows = 0, stg_cw = 0, stg_bufs = 0, seg_chunks_override = 0, xcd_pair_mb = 48;
 };
 
@@ -70,6 +70,12 @@ const KnobVar kKnobVars[] = {
     // cfg4, 8 x 8.4 MB, 11.05 ms grouped against 11.20 -- its pair step pulled 27 GB per step through the fabric for 5.6 GB of
     // spectra; cfg2, 3 x 8.4 MB: 0.69 ms grouped against 0.66 plain)
     number("TDOA_XCD_PAIR_MB", &Knobs::xcd_pair_mb, [](int v) { return std::max(0, v); }),
+    // the fused column kernels look angles up in the 64 KB quadrant table (22 vector instructions per dword) instead of the 96 KB
+    // split half-plane table (11; k1_discriminator.hpp) -- also what a device without 160 KB of LDS per workgroup runs
+    off_if("TDOA_K1_QUAD_TABLE", &Knobs::k1_split),
+    // ... the split table in k_fwd_col512_k1 too.  Off by default: that kernel exchanges through LDS twice per tile and the
+    // extra gathers cost more than the instructions save (cfg5 step 151.9 -> 154.3 ms, profiles/r07_k1_split_ab.json)
+    on_if("TDOA_K1_SPLIT_512", &Knobs::k1_split_512),
 };
 
 // run-time switches are read ONCE, when the context is made (a captured graph must not depend on an environment that changes later)

@@ -90,6 +90,7 @@ struct tdoa_ctx {
 
     DevBuf k1_direct;                       // kK1DirectEntries half-plane angle codes of the streaming K1 kernel
     DevBuf k1_quad;                         // kK1QuadrantEntries first-quadrant angle codes (k_fwd_col256_k1)
+    DevBuf k1_split;                        // kK1SplitBytes: the half-plane angles as lo | hi, the fused column kernels' default table
     DevBuf sw_desc, pw_desc, partials, stats, codes, codes_lp, k1_power, tz, v, keys, scales, peaks, scratch_a, scratch_b, lagdump;
     DevBuf ex_a, ex_b, ex_c, ex_d, ex_part;
 
@@ -122,6 +123,7 @@ struct tdoa_ctx {
     StgTables stg;                          // the staged walk's share-out of a window's pairs (stg_tables)
     DevBuf stg_groups;                      // ... its groups, uploaded once
     bool stg_ready = false;
+    bool k1_split_lds = false;              // the split-table column kernels may ask for kK1SplitLds of dynamic LDS (allow_big_lds)
     int graph_nodes = 0, graph_edges = 0, graph_roots = 0, graph_memsets = 0;      // structure of the captured step (tdoa_debug_graph_info)
     bool once_active = false;               // the last step (run_fm_batch, or the replayed graph) took the single-look path: decode multiplies by slot_gain
     bool graph_once = false;                // ... of the step the cached graph holds (a pair call on another path in between must not change what a replay reports)
@@ -435,7 +437,8 @@ int tdoa_create(const tdoa_params *p, tdoa_ctx **out)
     }
     {   // K1 angle tables, once per context (the first-octant table is the host's source for the two the kernels use)
         std::vector<int32_t> tab, direct, quad;
-        k1_build_table_host(tab, direct, quad);
+        std::vector<uint8_t> split;
+        k1_build_table_host(tab, direct, quad, &split);
         void *dt = nullptr, *dq = nullptr;
         if (hipMalloc(&dt, kK1DirectBytes) != hipSuccess) {
             (void)hipStreamDestroy(ctx->stream);
@@ -455,8 +458,20 @@ int tdoa_create(const tdoa_params *p, tdoa_ctx **out)
             tdoa_destroy(ctx);
             return TDOA_ERR_HIP;
         }
+        void *ds = nullptr;
+        if (hipMalloc(&ds, kK1SplitBytes) != hipSuccess) {
+            tdoa_destroy(ctx);
+            return TDOA_ERR_NOMEM;
+        }
+        ctx->k1_split.p = ds;
+        ctx->k1_split.cap = kK1SplitBytes;
+        if (hipMemcpy(ds, split.data(), kK1SplitBytes, hipMemcpyHostToDevice) != hipSuccess) {
+            tdoa_destroy(ctx);
+            return TDOA_ERR_HIP;
+        }
     }
     knobs_from_env(ctx->knobs);
+    if (!ctx->k1_split_lds) ctx->knobs.k1_split = false;      // the device gives no workgroup 160 KB of LDS: the quadrant route
     ctx->stg = stg_tables(ctx->knobs);
     *out = ctx;
     return TDOA_OK;
@@ -473,7 +488,7 @@ void tdoa_destroy(tdoa_ctx *ctx)
     clear_graph_marks(ctx);
     if (ctx->graph) (void)hipGraphDestroy(ctx->graph);
     tdoa_capture_clear(ctx);
-    DevBuf *bufs[] = {&ctx->k1_direct, &ctx->k1_quad, &ctx->sw_desc, &ctx->pw_desc, &ctx->partials, &ctx->stats, &ctx->codes, &ctx->codes_lp, &ctx->k1_power, &ctx->dec_taps, &ctx->dec_gain, &ctx->stg_groups, &ctx->tz, &ctx->v, &ctx->keys,
+    DevBuf *bufs[] = {&ctx->k1_direct, &ctx->k1_quad, &ctx->k1_split, &ctx->sw_desc, &ctx->pw_desc, &ctx->partials, &ctx->stats, &ctx->codes, &ctx->codes_lp, &ctx->k1_power, &ctx->dec_taps, &ctx->dec_gain, &ctx->stg_groups, &ctx->tz, &ctx->v, &ctx->keys,
                       &ctx->scales, &ctx->peaks, &ctx->scratch_a, &ctx->scratch_b, &ctx->lagdump,
                       &ctx->ex_a, &ctx->ex_b, &ctx->ex_c, &ctx->ex_d, &ctx->ex_part,
                       &ctx->g_sw_desc, &ctx->g_pw_desc, &ctx->g_quad_desc, &ctx->g_scales, &ctx->g_keys, &ctx->fine_raw, &ctx->fine, &ctx->qual,
