@@ -155,6 +155,34 @@ func (g *gpuCorrelator) ProcessStackedDrift(windowsPerStack, k, minSeparation in
 	return peaks, count, fine, drift, nil
 }
 
+// ProcessTrack is the best delay track through every stack's windows: one lag per window, consecutive lags at most maxStep
+// apart, the sum of the windows' fixed-point correlation values along the track the largest (the header's "delay tracks").
+// score holds one record per stack-pair (lag: the track's lag at the stack's first window, corr: the signed sum along the
+// track on C's scale), lags and values stackLen entries per stack-pair (positions past a shorter stack's end are 0).
+// A track crosses every window of its stack: there is no group form of this call.
+func (g *gpuCorrelator) ProcessTrack(windowsPerStack, maxStep int) (score []C.tdoa_peak, lags []C.int32_t, values []C.double, stackLen int, err error) {
+	var perBlock, total, wpb C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, nil, nil, 0, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	if rc := C.tdoa_num_windows(g.ctx, &wpb, nil); rc != C.TDOA_OK {
+		return nil, nil, nil, 0, fmt.Errorf("tdoa_num_windows: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	stackLen = int(wpb)
+	if windowsPerStack > 0 && windowsPerStack < stackLen {
+		stackLen = windowsPerStack
+	}
+	n := int(total) * int(C.tdoa_num_pairs(g.ctx))
+	if n == 0 || stackLen == 0 {
+		return nil, nil, nil, 0, fmt.Errorf("tdoa_process_track: no stack-pairs")
+	}
+	score, lags, values = make([]C.tdoa_peak, n), make([]C.int32_t, n*stackLen), make([]C.double, n*stackLen)
+	if rc := C.tdoa_process_track(g.ctx, C.int(windowsPerStack), C.int(maxStep), &score[0], &lags[0], &values[0], nil, nil); rc != C.TDOA_OK {
+		return nil, nil, nil, 0, fmt.Errorf("tdoa_process_track: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return score, lags, values, stackLen, nil
+}
+
 // windowQuality is fastAnalyzeSamples' statistics (fast_analyzer.go:117-155) for every (window, station).
 func (g *gpuCorrelator) windowQuality(stations int) ([]C.tdoa_window_quality, error) {
 	var perBlock, total C.int

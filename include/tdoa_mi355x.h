@@ -322,7 +322,8 @@ int tdoa_process_stacked(tdoa_ctx *ctx, int rank, int world, int windows_per_sta
  * No rank / world and no group entry: the ranks' per-hypothesis maxima cannot be merged, and their per-hypothesis sums
  * would be 2H+1 surfaces each; one context sums all its windows.
  * Limit: a slope also smears the peak inside one window.  The search repairs the alignment between windows only; it is
- * meant for slopes up to about the peak's width per window.
+ * meant for slopes up to about the peak's width per window.  One slope per stack: a delay that moves between windows
+ * but not along a line is tdoa_process_track's, below.
  * Runs inside the step graph.  TDOA_ERR_INVALID: what tdoa_process_stacked refuses, drift_den < 1, max_drift < 0 or > 512,
  * a search whose largest shift, shift(H, m_eff - 1) with m_eff the stack length in use, exceeds max_lag - 1, all seven
  * outputs NULL.  TDOA_LAGS_GO: TDOA_ERR_UNSUPPORTED.  Before captures exist: TDOA_ERR_STATE. */
@@ -332,6 +333,47 @@ int tdoa_process_stacked_drift(tdoa_ctx *ctx, int windows_per_stack, int k, int 
                                float *surface_host, int64_t *partial_host,
                                int32_t *drift_host   /* [n_stacks_total][n_pairs]          */,
                                tdoa_peak *profile_host /* [n_stacks_total][n_pairs][2H+1]  */);
+
+/* Delay tracks: one lag per window of a stack, for a delay that moves between windows but not along a line (a crystal
+ * that is still warming up, a slope that changes sign inside a block, windows that carry no peak at all).  Consecutive
+ * lags differ by at most J = max_step, and the track is the one along which the sum of the windows' correlation values is
+ * largest: dynamic programming (Viterbi) over the surfaces of the step.
+ * Stacks, pairs, q_w[l] = llrint(c_w[l] * 2^32), n_w and C = Q * 2^-32 / sqrt(n_w) are exactly those of
+ * tdoa_process_stacked.  Window w of a stack has position j = 0 ... n_w-1 by window id.  Lags run over
+ * -max_lag < l < max_lag.  J = max_step >= 0.
+ * For a polarity σ in {+1, -1}, computed from the stack's last window back to its first:
+ *     T_{n_w-1}[l] = σ q_{n_w-1}[l]
+ *     T_j[l]       = σ q_j[l] + max over |δ| <= J, l+δ inside the range, of T_{j+1}[l+δ]
+ *     D_j[l]       = the δ of that maximum; equal maxima: the smaller |δ|, then the positive δ
+ *     L_0          = the l with the largest T_0[l]; equal maxima: the smaller |l|, then the positive l
+ *     L_{j+1}      = L_j + D_j[L_j]
+ * Polarity: the polarity with the larger max T_0 is taken, +1 on a tie: the track with the largest |sum over j of
+ * q_j[L_j]|.  Every lag: T_0[l] is the best sum over all tracks that start at lag l in the stack's first window, so the
+ * results are indexed by the lag at the first window, as the slope search reports its lag.  No track: if max T_0 = 0
+ * (nothing but zeros) the score is the zero record and all lags and values are 0.  J = 0: σ T_0 = Q, and the score and
+ * the surface are tdoa_process_stacked's peak 1 and surface, byte for byte.
+ * mm is the stack length: windows_per_block when windows_per_stack is 0 or larger than it, otherwise windows_per_stack;
+ * positions j >= n_w of a shorter last stack hold 0.
+ * score_host:   lag = L_0; corr the double (σ max T_0) * 2^-32 / sqrt(n_w), the signed sum along the track on C's scale;
+ *               abs_corr its float magnitude.
+ * lags_host:    lags[j] = L_j.
+ * values_host:  values[j] = (double)q_j[L_j] * 2^-32, the window's own correlation on the track: where the signal fades.
+ * total_host:   σ T_0 of the chosen polarity, exact.
+ * surface_host: (float)(total * 2^-32 / sqrt(n_w)).  More paths raise the score of noise alone (it grows with J): judge a
+ *               score against the rest of this surface, not against a plain stack's.
+ * Any of the five may be NULL, not all.
+ * There is no rank / world and no group entry: a track crosses every window of its stack, so one context holds them all
+ * (as for the slope search above, whose per-hypothesis maxima cannot be merged either).
+ * Runs inside the step graph, one kernel per window position of a stack.  TDOA_ERR_INVALID: a NULL context (checked
+ * before anything needs a device), windows_per_stack < 0, max_step < 0 or > 64, a stack length in use above 4096, all
+ * five outputs NULL.  TDOA_LAGS_GO: TDOA_ERR_UNSUPPORTED.  Before captures exist: TDOA_ERR_STATE.  Too little device memory
+ * (the steps D take 2 bytes per lag, window and pair): TDOA_ERR_NOMEM. */
+int tdoa_process_track(tdoa_ctx *ctx, int windows_per_stack, int max_step /* J */,
+                       tdoa_peak *score_host   /* [n_stacks_total][n_pairs]      */,
+                       int32_t   *lags_host    /* [n_stacks_total][n_pairs][mm]  */,
+                       double    *values_host  /* [n_stacks_total][n_pairs][mm]  */,
+                       float     *surface_host /* [n_stacks_total][n_pairs][2*max_lag-1] */,
+                       int64_t   *total_host   /* same shape                      */);
 
 /* Capture-quality statistics of every (window, station) in one streaming pass over the bytes
  * in HBM: the byte statistics of fastAnalyzeSamples
@@ -553,7 +595,9 @@ int  tdoa_solve_surface(const double *stations_lle, int n_stations, const double
 /* ---- measurement ----------------------------------------------------------- */
 enum {
     TDOA_K_STATS = 0, TDOA_K_FWD_COL, TDOA_K_FWD_ROW, TDOA_K_INV_ROW, TDOA_K_INV_COL,
-    TDOA_K_PEAK, TDOA_K_COUNT
+    TDOA_K_PEAK,
+    TDOA_K_TRACK_STEP, TDOA_K_TRACK_FINISH,      /* tdoa_process_track's two kernels (appended: the scopes above keep their numbers) */
+    TDOA_K_COUNT
 };
 /* on = 1: tdoa_process launches its kernels one by one with HIP events at the boundaries of the selected scopes.
  * on = 2: tdoa_process keeps replaying the whole step as one hipGraph (the default path); the selected scopes are timed by

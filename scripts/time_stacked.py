@@ -5,7 +5,9 @@ geometry of BASELINE config 2 (synthetic captures on the device, one GPU), in on
 differences between the calls: median, and the lowest and highest round.  The graphs replay; host copies are included,
 as a caller sees them.  Every `--drift H/D` adds a leg: tdoa_process_stacked_drift(0, H, D, 1, 1) with the profile downloaded
 (0/1 is the plain stack with the search's fixed cost; the difference between two legs is the search kernel's time for the
-hypotheses between them).   usage: scripts/time_stacked.py [--steps N] [--rounds R] [--drift H/D]..."""
+hypotheses between them).  Every `--track J` adds a leg: tdoa_process_track(0, J) with score, lags and values downloaded (one
+kernel per window of a block after the surfaces; the difference between two legs is what the wider scan costs).
+usage: scripts/time_stacked.py [--steps N] [--rounds R] [--drift H/D]... [--track J]..."""
 import json
 import os
 import sys
@@ -34,7 +36,7 @@ def timed(fn, steps):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
-def main(steps, rounds, drifts=()):
+def main(steps, rounds, drifts=(), tracks=()):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=20000)
     for s in range(3):
         c.synth_capture(s, 66_666_666, ST[s], TX, 0x5D0A0000 + s)
@@ -45,6 +47,8 @@ def main(steps, rounds, drifts=()):
             "process_stacked_ms": lambda: c.process_stacked(0, 1, 1)}
     for H, D in drifts:
         legs["process_stacked_drift_%d_%d_ms" % (H, D)] = lambda H=H, D=D: c.process_stacked_drift(0, H, D, 1, 1)
+    for J in tracks:
+        legs["process_track_%d_ms" % J] = lambda J=J: c.process_track(0, J)
     times = {name: [] for name in legs}
     for _ in range(rounds):
         for name, fn in legs.items():
@@ -71,4 +75,9 @@ if __name__ == "__main__":
         h, _, d = args[i + 1].partition("/")
         drifts.append((int(h), int(d or 1)))
         del args[i:i + 2]
-    main(opt["--steps"], opt["--rounds"], drifts)
+    tracks = []
+    while "--track" in args:
+        i = args.index("--track")
+        tracks.append(int(args[i + 1]))
+        del args[i:i + 2]
+    main(opt["--steps"], opt["--rounds"], drifts, tracks)

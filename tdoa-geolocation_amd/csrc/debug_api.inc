@@ -119,8 +119,10 @@ int tdoa_debug_poison_workspace(tdoa_ctx *ctx)
     if (!ctx) return TDOA_ERR_INVALID;
     // floats only: no kernel derives an index from a value in these buffers (peak lags come from the keys, which are not
     // poisoned), so a NaN can end up in a result but never in an address.  (stack_q holds integers: the pattern is a large
-    // number there, and every element is written before it is read like the floats)
-    for (DevBuf *b : {&ctx->v, &ctx->tz, &ctx->fine_raw, &ctx->once_edges, &ctx->surf, &ctx->surf_out, &ctx->stack_q, &ctx->stack_surf})
+    // number there, and every element is written before it is read like the floats; so does track_t, the sums of
+    // tdoa_process_track -- its steps, track_d, are added to lag indices and stay as they are)
+    for (DevBuf *b : {&ctx->v, &ctx->tz, &ctx->fine_raw, &ctx->once_edges, &ctx->surf, &ctx->surf_out, &ctx->stack_q, &ctx->stack_surf,
+                      &ctx->track_t})
         if (b->p && b->cap >= 4) HIPCHK(ctx, hipMemsetD32Async(static_cast<hipDeviceptr_t>(b->p), 0x7FC00000, b->cap / 4, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return TDOA_OK;

@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -112,6 +112,8 @@ int main(int argc, char **argv)
     int stack_m = 0;         // --stack=WINDOWS: windows per stack (0, or plain --stack: a whole block)
     bool drift = false;      // --drift=H[/D] (with --stack): stack along the best of the slopes -H/D .. H/D lags per window
     int drift_h = 0, drift_d = 1;
+    bool track = false;      // --track=J (with --stack): one lag per window of every stack, at most J lags apart (tdoa_process_track)
+    int track_j = 0;
     double gate = 120.0;     // samples; PROJECT_NOTES.md:29-32 (max |TDOA| about 57 us = 114 samples at 2 Msps)
     tdoa_params prm;
     tdoa_default_params(&prm);
@@ -128,6 +130,7 @@ int main(int argc, char **argv)
             const size_t slash = a.find('/');
             drift_d = slash == std::string::npos ? 1 : std::atoi(a.c_str() + slash + 1);
         }
+        else if (a.rfind("--track=", 0) == 0) { track = true; track_j = std::atoi(a.c_str() + 8); }
         else if (a == "--gate" && i + 1 < argc) gate = std::atof(argv[++i]);
         else if (a == "--device" && i + 1 < argc) prm.device = std::atoi(argv[++i]);
         else if (a == "--window" && i + 1 < argc) prm.window_len = std::atoll(argv[++i]);
@@ -137,6 +140,7 @@ int main(int argc, char **argv)
         else pos.push_back(a);
     }
     if (drift && !stack) { std::fprintf(stderr, "--drift needs --stack\n"); return 1; }
+    if (track && !stack) { std::fprintf(stderr, "--track needs --stack\n"); return 1; }
     if (pos.size() < 4) {                                     // processor.go:1048-1052
         usage(argv[0]);
         return 1;
@@ -300,6 +304,8 @@ int main(int argc, char **argv)
         std::vector<int32_t> scnt;
         std::vector<tdoa_fine_peak> sfine;
         std::vector<int32_t> sdrift;             // --drift: h* per stack-pair (tdoa_process_stacked_drift)
+        std::vector<tdoa_peak> tscore;           // --track: the score and the lags of every stack-pair's track (tdoa_process_track)
+        std::vector<int32_t> tlags;
         if (stack) {
             if ((rc = tdoa_num_stacks(ctx, stack_m, &spb, &n_stacks))) return die("tdoa_num_stacks", rc);
             spk.resize((size_t)n_stacks * P * 2);
@@ -312,6 +318,13 @@ int main(int argc, char **argv)
                     return die("tdoa_process_stacked_drift", rc);
             } else if ((rc = tdoa_process_stacked(ctx, 0, 1, stack_m, 2, 1, gate, spk.data(), scnt.data(), sfine.data(), nullptr, nullptr)))
                 return die("tdoa_process_stacked", rc);
+            if (track) {
+                const int mm = stack_m > 0 && stack_m < wpb ? stack_m : wpb;
+                tscore.resize((size_t)n_stacks * P);
+                tlags.resize((size_t)n_stacks * P * mm);
+                if ((rc = tdoa_process_track(ctx, stack_m, track_j, tscore.data(), tlags.data(), nullptr, nullptr, nullptr)))
+                    return die("tdoa_process_track", rc);
+            }
         }
         std::printf("\n=== FM-DISCRIMINATOR CROSS-CORRELATION: %d windows x %d pairs ===\n", W, P);
         int p = 0;
@@ -360,6 +373,16 @@ int main(int argc, char **argv)
                                         1e6 * (double)sdrift[u] / ((double)drift_d * (double)wlen));
                         std::printf("\n");
                         if (sid / spb == 1) { sd.push_back(sfine[u].delay); sc.push_back(p1.abs_corr); }
+                    }
+                    for (int sid = 0; track && sid < n_stacks; sid++) {   // the track of every stack: a line of its own
+                        const size_t u = (size_t)sid * P + p;
+                        const int sj = sid % spb, n_w = std::min(m, wpb - sj * m);
+                        const int32_t *lg = tlags.data() + u * m;
+                        std::printf("TRACK block %d stack %d %s - %s: windows=%d step=%d first=%d last=%d score=%.6f lags=",
+                                    sid / spb + 1, sj, caps[i].st.name.c_str(), caps[j].st.name.c_str(), n_w, track_j, (int)lg[0],
+                                    (int)lg[n_w - 1], tscore[u].corr);
+                        for (int w = 0; w < n_w; w++) std::printf(w ? ",%d" : "%d", (int)lg[w]);
+                        std::printf("\n");
                     }
                     lag_used = median(sd);
                     ct = sc;

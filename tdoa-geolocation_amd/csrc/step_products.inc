@@ -1,12 +1,13 @@
 // step_products.inc -- what a step (process_impl) can write besides its peak records: the correlation surfaces
 // (tdoa_process_lags), the K strongest peaks per pair-window (tdoa_process_peaks), the stacked surfaces of a block's windows
-// (tdoa_process_stacked), the same stacks taken along the best of 2H+1 lag slopes (tdoa_process_stacked_drift).  Every
-// product is four functions next to each other, called by process_impl in this order:
+// (tdoa_process_stacked), the same stacks taken along the best of 2H+1 lag slopes (tdoa_process_stacked_drift), the best
+// delay track through a stack's windows (tdoa_process_track).  Every product is four functions next to each other, called
+// by process_impl in this order:
 //   reserve_*   its buffers, after the step's grouping is fixed (batch_bound counts them as held, so a later call groups as
 //               this one did); no allocation may happen once the step is being captured
 //   key_*       the words it appends to the step graph's key: everything its launches depend on
-//   (upload_stack, upload_stack_drift: the products with descriptors of their own send them with the step's, when the step
-//   is not replayed)
+//   (upload_stack, upload_stack_drift, upload_stack_track: the products with descriptors of their own send them with the
+//   step's, when the step is not replayed)
 //   enqueue_*   its kernels, after the step's decode -- unscoped launches, kernel nodes only: the step stays one chain
 //   download_*  its asynchronous copies out on ctx->stream
 // All of them read the K5 kernels' lag arrays in ctx->surf, pair-window i of the rank at i * n_lags.
@@ -62,13 +63,27 @@ struct StackDriftProduct {
     std::vector<int32_t> tab;                // ... and shift(h, j) at [(h + H) * mm + j]
 };
 
+struct StackTrackProduct {
+    int m = 0, J = 0;                        // windows per stack (0: the whole block), the largest step between two windows
+    tdoa_peak *score_host = nullptr;         // [stack][pair]
+    int32_t *lags_host = nullptr;            // [stack][pair][mm]
+    double *values_host = nullptr;           // [stack][pair][mm]
+    float *surface_host = nullptr;           // [stack][pair][n_lags]
+    int64_t *total_host = nullptr;           // [stack][pair][n_lags]
+    int mm = 0;                              // filled by reserve_stack_track: the stack length,
+    StackLayout layout;                      // the stacks (their roots are what the finish reads),
+    std::vector<int32_t> table;              // pos [stack-pair][mm], then n_w [stack-pair] (stack_track.hpp, TrackTable)
+    std::vector<double> ones;                // upload_stack_desc's host copy of the unit scales
+};
+
 // the product of one step; the numbers are the first word a product appends to the graph key
 struct StepProduct {
-    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4 } kind = None;
+    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5 } kind = None;
     LagsProduct lags;
     PeaksProduct peaks;
     StackProduct stack;
     StackDriftProduct drift;
+    StackTrackProduct track;
 };
 
 // ctx->surf for the rank's pair-windows; `copies`: float surfaces of the step the product holds in all (the message's size)
@@ -283,6 +298,87 @@ int download_stack_drift(const StepView &v, const StackDriftProduct &p)
     return TDOA_OK;
 }
 
+// ---- the best delay track through every stack-pair's windows (stack_track.hpp) ------------------------------------------
+// T (ctx->track_t): two halves [stack-pair][n_lags] TrackPair, position j writes half j & 1 and reads the other, so T_0 ends
+// in the first; D (ctx->track_d): [stack-pair][mm][n_lags][2] int8; total and the float surface go where the plain stack
+// keeps Q and its surface (ctx->stack_q, ctx->stack_surf)
+int reserve_stack_track(const StepView &v, StackTrackProduct &p)
+{
+    tdoa_ctx *ctx = v.ctx;
+    if (int rc = reserve_surf(v, 1.0)) return rc;
+    p.layout = build_stack_layout(v.lay->pw, v.wpb, v.P, p.m);
+    p.mm = stack_length(v.wpb, p.m);
+    const size_t n_sp = (size_t)p.layout.n_stacks * v.P;
+    p.table.assign(n_sp * p.mm + n_sp, -1);
+    std::fill(p.table.begin() + n_sp * p.mm, p.table.end(), 0);
+    for (size_t i = 0; i < v.lay->pw.size(); i++) {
+        const int wid = v.lay->pw[i].out_index / v.P, pair = v.lay->pw[i].out_index % v.P;
+        const size_t sp = (size_t)((wid / v.wpb) * p.layout.spb + (wid % v.wpb) / p.mm) * v.P + pair;
+        p.table[sp * p.mm + (wid % v.wpb) % p.mm] = (int32_t)i;
+        p.table[n_sp * p.mm + sp]++;
+    }
+    if (ensure(ctx, ctx->stack_desc, stack_desc_bytes(p.layout.n_stacks, v.P, v.n_owned())) ||
+        ensure(ctx, ctx->track_tab, sizeof(int32_t) * p.table.size()) ||
+        ensure(ctx, ctx->track_t, 2 * sizeof(TrackPair) * n_sp * v.n_lags) ||
+        ensure(ctx, ctx->track_d, 2 * n_sp * p.mm * v.n_lags) ||
+        ensure(ctx, ctx->stack_q, sizeof(long long) * n_sp * v.n_lags) ||
+        ensure(ctx, ctx->stack_surf, sizeof(float) * n_sp * v.n_lags) ||
+        ensure(ctx, ctx->track_score, sizeof(PeakOut) * n_sp) ||
+        ensure(ctx, ctx->track_lags, sizeof(int32_t) * n_sp * p.mm) ||
+        ensure(ctx, ctx->track_values, sizeof(double) * n_sp * p.mm))
+        return surfaces_nomem(v, "correlation surfaces and the track's sums and steps", 1.0 + 0.5 * p.mm);
+    return TDOA_OK;
+}
+void key_stack_track(const StackTrackProduct &p, std::vector<uint64_t> *key)
+{
+    key->insert(key->end(), {StepProduct::StackTrack, (uint64_t)p.m, (uint64_t)p.J, 0});
+}
+int upload_stack_track(const StepView &v, StackTrackProduct &p)
+{
+    tdoa_ctx *ctx = v.ctx;
+    if (int rc = upload_stack_desc(ctx, p.layout, v.P, &p.ones, true)) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->track_tab.p, p.table.data(), sizeof(int32_t) * p.table.size(), hipMemcpyHostToDevice, ctx->stream));
+    return TDOA_OK;
+}
+void enqueue_stack_track(const StepView &v, const StackTrackProduct &p)
+{
+    tdoa_ctx *ctx = v.ctx;
+    hipStream_t st = ctx->stream;
+    const int n_stacks = p.layout.n_stacks;
+    const unsigned n_sp = (unsigned)(n_stacks * v.P);
+    const StackDev sd = stack_dev(ctx, n_stacks, v.P);
+    const int32_t *tab = ctx->track_tab.as<const int32_t>();
+    const TrackTable tt{tab, tab + (size_t)n_sp * p.mm, p.mm};
+    TrackPair *half[2] = {ctx->track_t.as<TrackPair>(), ctx->track_t.as<TrackPair>() + (size_t)n_sp * v.n_lags};
+    const dim3 grid(n_sp, (unsigned)((v.n_lags + kTrackTile - 1) / kTrackTile));
+    {
+        ProfScope ps(ctx, TDOA_K_TRACK_STEP, (4.0 + 2.0 * sizeof(TrackPair) + 2.0) * (double)v.n_lags * (double)v.n_owned());
+        for (int j = p.mm - 1; j >= 0; j--)
+            hipLaunchKernelGGL(k_track_step, grid, dim3(kTrackThreads), 0, st, ctx->surf.as<const float>(), (size_t)v.n_lags, v.n_lags,
+                               v.d_pw, v.d_scales, v.slot_gain, tt, j, p.J, static_cast<const TrackPair *>(half[(j + 1) & 1]),
+                               half[j & 1], ctx->track_d.as<signed char>());
+    }
+    ProfScope ps(ctx, TDOA_K_TRACK_FINISH, (2.0 * sizeof(TrackPair) + 12.0) * (double)v.n_lags * n_sp);
+    hipLaunchKernelGGL(k_track_finish, dim3(n_sp), dim3(kTrackThreads), 0, st, static_cast<const TrackPair *>(half[0]),
+                       ctx->track_d.as<const signed char>(), ctx->surf.as<const float>(), (size_t)v.n_lags, v.n_lags, v.lag_lo, v.P,
+                       v.d_pw, v.d_scales, v.slot_gain, sd.roots, tt, ctx->track_score.as<PeakOut>(), ctx->track_lags.as<int32_t>(),
+                       ctx->track_values.as<double>(), ctx->stack_q.as<long long>(), ctx->stack_surf.as<float>());
+}
+int download_stack_track(const StepView &v, const StackTrackProduct &p)
+{
+    tdoa_ctx *ctx = v.ctx;
+    hipStream_t st = ctx->stream;
+    const size_t n_sp = (size_t)p.layout.n_stacks * v.P;
+    if (p.score_host) HIPCHK(ctx, hipMemcpyAsync(p.score_host, ctx->track_score.p, sizeof(PeakOut) * n_sp, hipMemcpyDeviceToHost, st));
+    if (p.lags_host) HIPCHK(ctx, hipMemcpyAsync(p.lags_host, ctx->track_lags.p, sizeof(int32_t) * n_sp * p.mm, hipMemcpyDeviceToHost, st));
+    if (p.values_host) HIPCHK(ctx, hipMemcpyAsync(p.values_host, ctx->track_values.p, sizeof(double) * n_sp * p.mm, hipMemcpyDeviceToHost, st));
+    if (p.surface_host)
+        HIPCHK(ctx, hipMemcpyAsync(p.surface_host, ctx->stack_surf.p, sizeof(float) * n_sp * v.n_lags, hipMemcpyDeviceToHost, st));
+    if (p.total_host)
+        HIPCHK(ctx, hipMemcpyAsync(p.total_host, ctx->stack_q.p, sizeof(int64_t) * n_sp * v.n_lags, hipMemcpyDeviceToHost, st));
+    return TDOA_OK;
+}
+
 // ---- process_impl's one dispatch per stage ---------------------------------------------------------------------------
 int reserve_product(const StepView &v, StepProduct &p)
 {
@@ -291,6 +387,7 @@ int reserve_product(const StepView &v, StepProduct &p)
     case StepProduct::Peaks: return reserve_peaks(v, p.peaks);
     case StepProduct::Stack: return reserve_stack(v, p.stack);
     case StepProduct::StackDrift: return reserve_stack_drift(v, p.drift);
+    case StepProduct::StackTrack: return reserve_stack_track(v, p.track);
     default: return TDOA_OK;
     }
 }
@@ -301,6 +398,7 @@ void key_product(const StepProduct &p, std::vector<uint64_t> *key)
     case StepProduct::Peaks: return key_peaks(p.peaks, key);
     case StepProduct::Stack: return key_stack(p.stack, key);
     case StepProduct::StackDrift: return key_stack_drift(p.drift, key);
+    case StepProduct::StackTrack: return key_stack_track(p.track, key);
     default: key->insert(key->end(), {StepProduct::None, 0, 0, 0});
     }
 }
@@ -309,6 +407,7 @@ int upload_product(const StepView &v, StepProduct &p)
     switch (p.kind) {
     case StepProduct::Stack: return upload_stack(v, p.stack);
     case StepProduct::StackDrift: return upload_stack_drift(v, p.drift);
+    case StepProduct::StackTrack: return upload_stack_track(v, p.track);
     default: return TDOA_OK;
     }
 }
@@ -320,6 +419,7 @@ void enqueue_product(const StepView &v, const StepProduct &p)
     case StepProduct::Peaks: return enqueue_peaks(v, p.peaks);
     case StepProduct::Stack: return enqueue_stack(v, p.stack);
     case StepProduct::StackDrift: return enqueue_stack_drift(v, p.drift);
+    case StepProduct::StackTrack: return enqueue_stack_track(v, p.track);
     default: return;
     }
 }
@@ -330,6 +430,7 @@ int download_product(const StepView &v, const StepProduct &p)
     case StepProduct::Peaks: return download_peaks(v, p.peaks);
     case StepProduct::Stack: return download_stack_product(v, p.stack);
     case StepProduct::StackDrift: return download_stack_drift(v, p.drift);
+    case StepProduct::StackTrack: return download_stack_track(v, p.track);
     default: return TDOA_OK;
     }
 }

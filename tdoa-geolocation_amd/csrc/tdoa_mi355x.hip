@@ -37,6 +37,7 @@
 #include "peak_select.hpp"
 #include "stack_surfaces.hpp"
 #include "stack_drift.hpp"
+#include "stack_track.hpp"
 
 using namespace tdoa;
 
@@ -153,6 +154,10 @@ struct tdoa_ctx {
     // tdoa_process_stacked_drift: the shift table [2H+1][stack length], the keys [stack][pair][2H+1] of the slopes' maxima,
     // h* [stack][pair] and the decoded profile [stack][pair][2H+1]
     DevBuf drift_tab, drift_keys, drift_h, drift_prof;
+    // tdoa_process_track: where the stack-pairs' windows are (pos [stack][pair][stack length], n_w [stack][pair]), the two
+    // halves of T [stack][pair][2 max_lag - 1][2 polarities], the steps D [stack][pair][stack length][2 max_lag - 1][2], and
+    // the score, lags and values of every stack-pair's track
+    DevBuf track_tab, track_t, track_d, track_score, track_lags, track_values;
 };
 
 namespace {
@@ -395,7 +400,7 @@ const char *tdoa_last_error(const tdoa_ctx *ctx) { return ctx ? ctx->last_error.
 const char *tdoa_kernel_name(int k)
 {
     static const char *names[TDOA_K_COUNT] = {"k_fm_demod", "k_fwd_col", "k_fwd_row", "k_inv_row_pair",
-                                              "k_inv_col_peak", "k_decode_peaks"};
+                                              "k_inv_col_peak", "k_decode_peaks", "k_track_step", "k_track_finish"};
     return (k >= 0 && k < TDOA_K_COUNT) ? names[k] : "";
 }
 
@@ -494,7 +499,8 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->g_sw_desc, &ctx->g_pw_desc, &ctx->g_quad_desc, &ctx->g_scales, &ctx->g_keys, &ctx->fine_raw, &ctx->fine, &ctx->qual,
                       &ctx->once_edges, &ctx->once_tiles, &ctx->once_fin, &ctx->slot_gain, &ctx->surf, &ctx->surf_out,
                       &ctx->sel_peaks, &ctx->sel_count, &ctx->stack_q, &ctx->stack_surf, &ctx->stack_keys, &ctx->stack_fine,
-                      &ctx->stack_desc, &ctx->drift_tab, &ctx->drift_keys, &ctx->drift_h, &ctx->drift_prof};
+                      &ctx->stack_desc, &ctx->drift_tab, &ctx->drift_keys, &ctx->drift_h, &ctx->drift_prof, &ctx->track_tab,
+                      &ctx->track_t, &ctx->track_d, &ctx->track_score, &ctx->track_lags, &ctx->track_values};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1023,6 +1029,31 @@ int tdoa_process_stacked_drift(tdoa_ctx *ctx, int windows_per_stack, int k, int 
     sp.surface_host = surface_host;
     sp.partial_host = partial_host;
     return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, gate_samples, std::move(prod));
+}
+
+int tdoa_process_track(tdoa_ctx *ctx, int windows_per_stack, int max_step, tdoa_peak *score_host, int32_t *lags_host,
+                       double *values_host, float *surface_host, int64_t *total_host)
+{
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (windows_per_stack < 0) return fail(ctx, TDOA_ERR_INVALID, "windows_per_stack < 0");
+    if (max_step < 0 || max_step > kTrackMaxStep) return fail(ctx, TDOA_ERR_INVALID, "max_step outside 0 .. 64");
+    if (!score_host && !lags_host && !values_host && !surface_host && !total_host)
+        return fail(ctx, TDOA_ERR_INVALID, "every output is NULL");
+    if (ctx->prm.lag_mode == TDOA_LAGS_GO) return fail(ctx, TDOA_ERR_UNSUPPORTED, "delay tracks with TDOA_LAGS_GO");
+    int wpb = 0;
+    if (int rc = tdoa_num_windows(ctx, &wpb, nullptr)) return fail(ctx, rc, "captures missing or too small");
+    if (stack_length(wpb, windows_per_stack) > 4096) return fail(ctx, TDOA_ERR_INVALID, "a stack of more than 4096 windows");
+    StepProduct prod;
+    prod.kind = StepProduct::StackTrack;
+    StackTrackProduct &tp = prod.track;
+    tp.m = windows_per_stack;
+    tp.J = max_step;
+    tp.score_host = score_host;
+    tp.lags_host = lags_host;
+    tp.values_host = values_host;
+    tp.surface_host = surface_host;
+    tp.total_host = total_host;
+    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, std::move(prod));
 }
 
 // fast_analyzer.go:139-155 and collector.go:224 from the exact integer sums, in the reference's expression order

@@ -8,7 +8,7 @@ import numpy as np
 from . import build as _build
 
 OK = 0
-KERNELS = ["STATS", "FWD_COL", "FWD_ROW", "INV_ROW", "INV_COL", "PEAK"]
+KERNELS = ["STATS", "FWD_COL", "FWD_ROW", "INV_ROW", "INV_COL", "PEAK", "TRACK_STEP", "TRACK_FINISH"]
 
 
 class TdoaError(RuntimeError):
@@ -92,6 +92,7 @@ SYMBOLS = [
     "tdoa_group_create", "tdoa_group_destroy", "tdoa_group_last_error", "tdoa_group_member",
     "tdoa_group_capture_upload_files", "tdoa_group_process", "tdoa_debug_owned_runs",
     "tdoa_num_stacks", "tdoa_process_stacked", "tdoa_group_process_stacked", "tdoa_process_stacked_drift",
+    "tdoa_process_track",
 ]
 
 _lib = None
@@ -198,6 +199,7 @@ def load(build_if_missing=True):
     L.tdoa_group_process_stacked.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, i32p, vp, fp]
     L.tdoa_process_stacked_drift.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, i32p, vp, fp,
                                              C.POINTER(C.c_int64), i32p, vp]
+    L.tdoa_process_track.argtypes = [vp, C.c_int, C.c_int, vp, i32p, dp, fp, C.POINTER(C.c_int64)]
     L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
                                         C.POINTER(C.c_int)]
     _lib = L
@@ -530,6 +532,30 @@ class Context:
             out["partial"].ctypes.data_as(C.POINTER(C.c_int64)) if want_partial else None,
             out["drift"].ctypes.data_as(C.POINTER(C.c_int32)),
             out["profile"].ctypes.data_as(C.c_void_p) if want_profile else None))
+        return out
+
+    def process_track(self, windows_per_stack=0, max_step=1, want_surface=False, want_total=False):
+        """tdoa_process_track -> dict: score [n_stacks][P] PEAK_DTYPE (lag: the track's lag at the stack's first window,
+        corr: the signed sum along the track on C's scale), lags [n_stacks][P][mm] int32 and values [n_stacks][P][mm]
+        float64 (each window's lag and its own correlation there; mm the stack length, positions past a shorter stack's
+        end 0), and on request surface [n_stacks][P][2 max_lag - 1] float32 and total (same shape, int64): the best sum
+        over the tracks that start at every lag"""
+        _, n = self.num_stacks(windows_per_stack)
+        p = self.num_pairs()
+        wpb, _ = self.num_windows()
+        mm = wpb if int(windows_per_stack) <= 0 else min(int(windows_per_stack), wpb)
+        n_lags = 2 * self.params.max_lag - 1
+        out = {"score": np.zeros((n, p), dtype=PEAK_DTYPE), "lags": np.zeros((n, p, mm), dtype=np.int32),
+               "values": np.zeros((n, p, mm), dtype=np.float64)}
+        if want_surface:
+            out["surface"] = np.zeros((n, p, n_lags), dtype=np.float32)
+        if want_total:
+            out["total"] = np.zeros((n, p, n_lags), dtype=np.int64)
+        self._chk(self._L.tdoa_process_track(
+            self._h, int(windows_per_stack), int(max_step), out["score"].ctypes.data_as(C.c_void_p),
+            out["lags"].ctypes.data_as(C.POINTER(C.c_int32)), _d(out["values"]),
+            _f(out["surface"]) if want_surface else None,
+            out["total"].ctypes.data_as(C.POINTER(C.c_int64)) if want_total else None))
         return out
 
     def fm_xcorr_peaks(self, iq1, iq2, max_lag, k, min_separation):
