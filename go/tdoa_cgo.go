@@ -183,6 +183,34 @@ func (g *gpuCorrelator) ProcessTrack(windowsPerStack, maxStep int) (score []C.td
 	return score, lags, values, stackLen, nil
 }
 
+// centrePtr is the centres as the C ABI takes them: nil (all 0), or one int32 per station.
+func centrePtr(centre []int32) *C.int32_t {
+	if len(centre) == 0 {
+		return nil
+	}
+	return (*C.int32_t)(unsafe.Pointer(&centre[0]))
+}
+
+// ProcessClosure is the closure search: per stack and station triple i < j < k the three lags that close
+// (lag_ij + lag_jk = lag_ik) with the largest summed magnitude within gate lags of the pairs' centres (the header's
+// "closure search"), next to what the three independent argmaxes give (own_q, residual) and the runner-up.  centre: one
+// lag per station (nil: all 0).  The records are [stack][triple], triples the second return value.
+func (g *gpuCorrelator) ProcessClosure(windowsPerStack, gate, minSeparation int, centre []int32) ([]C.tdoa_closure, int, error) {
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, 0, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	triples := int(C.tdoa_num_triples(g.ctx))
+	if int(total)*triples == 0 {
+		return nil, 0, fmt.Errorf("tdoa_process_closure: no stacks or fewer than three stations")
+	}
+	out := make([]C.tdoa_closure, int(total)*triples)
+	if rc := C.tdoa_process_closure(g.ctx, C.int(windowsPerStack), C.int(gate), C.int(minSeparation), centrePtr(centre), &out[0]); rc != C.TDOA_OK {
+		return nil, 0, fmt.Errorf("tdoa_process_closure: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return out, triples, nil
+}
+
 // windowQuality is fastAnalyzeSamples' statistics (fast_analyzer.go:117-155) for every (window, station).
 func (g *gpuCorrelator) windowQuality(stations int) ([]C.tdoa_window_quality, error) {
 	var perBlock, total C.int
@@ -276,4 +304,23 @@ func (g *Group) ProcessStacked(windowsPerStack, k, minSeparation int, gate float
 		return nil, nil, nil, fmt.Errorf("tdoa_group_process_stacked: %s", C.GoString(C.tdoa_group_last_error(g.g)))
 	}
 	return peaks, count, fine, nil
+}
+
+// ProcessClosure is gpuCorrelator.ProcessClosure over the group: the members' fixed-point partial sums are added on the
+// host and searched on member 0, the same bytes one context returns.
+func (g *Group) ProcessClosure(windowsPerStack, gate, minSeparation int, centre []int32) ([]C.tdoa_closure, int, error) {
+	m := C.tdoa_group_member(g.g, 0)
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(m, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, 0, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	triples := int(C.tdoa_num_triples(m))
+	if int(total)*triples == 0 {
+		return nil, 0, fmt.Errorf("tdoa_group_process_closure: no stacks or fewer than three stations")
+	}
+	out := make([]C.tdoa_closure, int(total)*triples)
+	if rc := C.tdoa_group_process_closure(g.g, C.int(windowsPerStack), C.int(gate), C.int(minSeparation), centrePtr(centre), &out[0]); rc != C.TDOA_OK {
+		return nil, 0, fmt.Errorf("tdoa_group_process_closure: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return out, triples, nil
 }

@@ -375,6 +375,62 @@ int tdoa_process_track(tdoa_ctx *ctx, int windows_per_stack, int max_step /* J *
                        float     *surface_host /* [n_stacks_total][n_pairs][2*max_lag-1] */,
                        int64_t   *total_host   /* same shape                      */);
 
+/* Closure search: one consistent lag set per station triple of a stack.  Everything above works on one station pair at a
+ * time, but the delays of three stations i < j < k close: lag(i,j) + lag(j,k) = lag(i,k).  When noise, multipath or a second
+ * emitter moves one pair's argmax the three lags contradict each other; the third surface usually holds what repairs them.
+ * The search is exact integer work on Q: no station coordinates, no geometry, no floating point.
+ * S stations with S >= 3.
+ * Pairs are i < j in the library's order, p(i,j) = i*S - i(i+1)/2 + (j-i-1).
+ * Triples are i < j < k in lexicographic order.  There are T = S(S-1)(S-2)/6 of them, returned by tdoa_num_triples.
+ * Stacks, n_w and the int64 Q_p[l] over -max_lag < l < max_lag are exactly those of tdoa_process_stacked.
+ * windows_per_stack has the same meaning, and stacks never cross a block.
+ *   M_p[l] = |Q_p[l]|, an int64.
+ *   centre[s] is an int32 per station.  NULL means all 0.  The centre of a pair is c_p(i,j) = centre[j] - centre[i], so
+ *     centres close by construction.
+ *   G = gate, 0 <= G <= 1023.  A pair's gated window is the lags c_p + x with |x| <= G that lie inside the searched range.
+ *   A cell (u, v) of triple (i,j,k) has |u| <= G, |v| <= G and |v-u| <= G.  Its lags are a = c_ij + u, b = c_ik + v and
+ *     e = b - a = c_jk + (v-u).  All three must lie inside -max_lag < . < max_lag; a cell with a lag outside does not exist.
+ *   score_q(u,v) = M_ij[a] + M_ik[b] + M_jk[e].  This is an int64, and at most 3 * 2^57 here.
+ *   The joint cell (u*, v*) is the largest score_q.  Among equal maxima the smaller |u| wins, then the positive u, then the
+ *     smaller |v|, then the positive v.
+ *   The zero record (all bytes 0) is returned when no cell exists or the maximum is 0.
+ *   Independent peaks: for each of the three pairs, x*_p is the argmax of M_p over its gated window.  Equal maxima go to the
+ *     smaller |x|, then the positive x.  Then own_q is the sum of the three maxima, and
+ *     residual = (c_ij+x*_ij) + (c_jk+x*_jk) - (c_ik+x*_ik).
+ *     So score_q <= own_q, and residual == 0 implies score_q == own_q.
+ *   Runner-up: runner_q is the largest score_q over the cells with max(|u-u*|, |v-v*|) > min_separation
+ *     (min_separation >= 1).  It is 0 when there is none.  A score is judged against it.
+ * The record, 80 bytes, no padding: */
+typedef struct {
+    int32_t lag_ij, lag_ik, lag_jk, residual;      /* a, b, e of the joint cell; the independent peaks' closure residual */
+    int64_t score_q, own_q, runner_q;
+    double corr_ij, corr_ik, corr_jk;              /* the signed C = Q * 2^-32 / sqrt(n_w) at the three joint lags */
+    double score, runner_up;                       /* (double)score_q * 2^-32 / sqrt(n_w) and the same of runner_q */
+} tdoa_closure;
+
+/* S(S-1)(S-2)/6 for the context's stations; 0 for a NULL context, fewer than 3 or more than 64 stations */
+int tdoa_num_triples(const tdoa_ctx *ctx);
+
+/* closure_host: [n_stacks_total][n_triples] (tdoa_num_stacks, tdoa_num_triples).  A centre that puts a whole window outside
+ * the range is legal: it gives zero records.  One context sums all its windows; tdoa_group_process_closure is the group
+ * form (the search is a function of the complete stacked Q only, so the members' partial sums merge).
+ * Runs inside the step graph, behind the stack's accumulation: two launches of the search kernel (the joint cell, the
+ * runner-up) and two of the finishing kernel.  (windows_per_stack, gate, min_separation) are part of the graph's key;
+ * the centres are data in a device buffer, so a call that changes only the centres replays the same graph.
+ * TDOA_ERR_INVALID: a NULL context (checked before anything needs a device), windows_per_stack < 0, gate < 0 or > 1023,
+ * min_separation < 1, a NULL output.  TDOA_ERR_UNSUPPORTED: fewer than three stations (or more than 64), TDOA_LAGS_GO.
+ * Before captures exist: TDOA_ERR_STATE. */
+int tdoa_process_closure(tdoa_ctx *ctx, int windows_per_stack, int gate /* G */, int min_separation,
+                         const int32_t *centre /* [n_stations] or NULL */,
+                         tdoa_closure *closure_host /* [n_stacks_total][n_triples] */);
+
+/* tests only: the same kernels on the caller's words q [n_sets][P][2*max_lag-1], P = n_stations (n_stations-1) / 2 rows in
+ * the library's pair order, every set a stack of n_w windows; out [n_sets][T].  Needs a context for max_lag and the device,
+ * and no captures.  TDOA_ERR_INVALID: what tdoa_process_closure refuses, q NULL, n_sets < 1, n_w < 1, n_stations outside
+ * 3 .. 64. */
+int tdoa_debug_closure_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int gate,
+                              int min_separation, const int32_t *centre, tdoa_closure *out);
+
 /* Capture-quality statistics of every (window, station) in one streaming pass over the bytes
  * in HBM: the byte statistics of fastAnalyzeSamples
  * (fast_analyzer.go:117-155) and the block power of validateDataFile (collector.go:219-224).
@@ -565,6 +621,13 @@ int tdoa_group_process(tdoa_group *g, tdoa_peak *out_host);
  * tdoa_group_process.  With one member, its call writes the outputs directly. */
 int tdoa_group_process_stacked(tdoa_group *g, int windows_per_stack, int k, int min_separation, double gate_samples,
                                tdoa_peak *peaks_host, int32_t *count_host, tdoa_fine_peak *fine_host, float *surface_host);
+
+/* tdoa_process_closure over the members: they sum their windows as in tdoa_group_process_stacked, the host adds the
+ * partials, and member 0 runs the search on the merged Q -- the records are byte-identical to
+ * tdoa_process_closure(single ctx, ...).  Errors as there and as tdoa_group_process.  With one member, its call writes the
+ * records directly. */
+int tdoa_group_process_closure(tdoa_group *g, int windows_per_stack, int gate, int min_separation,
+                               const int32_t *centre, tdoa_closure *closure_host);
 
 /* the sample runs member `rank` of `world` uploads for a capture of total_samples (window grid from n_min, the shortest
  * capture of the job; block offsets from the capture's own thirds): adjacent owned windows form one run, and with fewer

@@ -6,8 +6,10 @@ differences between the calls: median, and the lowest and highest round.  The gr
 as a caller sees them.  Every `--drift H/D` adds a leg: tdoa_process_stacked_drift(0, H, D, 1, 1) with the profile downloaded
 (0/1 is the plain stack with the search's fixed cost; the difference between two legs is the search kernel's time for the
 hypotheses between them).  Every `--track J` adds a leg: tdoa_process_track(0, J) with score, lags and values downloaded (one
-kernel per window of a block after the surfaces; the difference between two legs is what the wider scan costs).
-usage: scripts/time_stacked.py [--steps N] [--rounds R] [--drift H/D]... [--track J]..."""
+kernel per window of a block after the surfaces; the difference between two legs is what the wider scan costs).  Every
+`--closure G` adds a leg: tdoa_process_closure(0, G, 1) with the records downloaded (the stack's accumulation, then two
+launches of the search and two of its finish).  `--stations S` runs all legs on S stations (default 3; 8 gives 56 triples).
+usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--drift H/D]... [--track J]... [--closure G]..."""
 import json
 import os
 import sys
@@ -36,10 +38,10 @@ def timed(fn, steps):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
-def main(steps, rounds, drifts=(), tracks=()):
+def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=20000)
-    for s in range(3):
-        c.synth_capture(s, 66_666_666, ST[s], TX, 0x5D0A0000 + s)
+    for s in range(stations):
+        c.synth_capture(s, 66_666_666, ST[s % 3], TX, 0x5D0A0000 + s)
     _, W = c.num_windows()
     P = c.num_pairs()
     _, n_stacks = c.num_stacks(0)
@@ -49,11 +51,13 @@ def main(steps, rounds, drifts=(), tracks=()):
         legs["process_stacked_drift_%d_%d_ms" % (H, D)] = lambda H=H, D=D: c.process_stacked_drift(0, H, D, 1, 1)
     for J in tracks:
         legs["process_track_%d_ms" % J] = lambda J=J: c.process_track(0, J)
+    for G in closures:
+        legs["process_closure_%d_ms" % G] = lambda G=G: c.process_closure(0, G, 1)
     times = {name: [] for name in legs}
     for _ in range(rounds):
         for name, fn in legs.items():
             times[name].append(timed(fn, steps))
-    out = {"config": "cfg2", "stations": 3, "pairs": P, "windows": W, "stacks": n_stacks, "steps": steps, "rounds": rounds,
+    out = {"config": "cfg2" if stations == 3 else "cfg2 windows, %d stations" % stations, "stations": stations, "pairs": P, "windows": W, "stacks": n_stacks, "steps": steps, "rounds": rounds,
            "surface_MB": round(W * P * (2 * 20000 - 1) * 4 / 1e6, 1)}
     for name, t in times.items():
         out[name] = {"median": round(float(np.median(t)), 3), "min": round(min(t), 3), "max": round(max(t), 3)}
@@ -63,7 +67,7 @@ def main(steps, rounds, drifts=(), tracks=()):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
-    opt = {"--steps": 20, "--rounds": 5}
+    opt = {"--steps": 20, "--rounds": 5, "--stations": 3}
     for name in opt:
         if name in args:
             i = args.index(name)
@@ -80,4 +84,9 @@ if __name__ == "__main__":
         i = args.index("--track")
         tracks.append(int(args[i + 1]))
         del args[i:i + 2]
-    main(opt["--steps"], opt["--rounds"], drifts, tracks)
+    closures = []
+    while "--closure" in args:
+        i = args.index("--closure")
+        closures.append(int(args[i + 1]))
+        del args[i:i + 2]
+    main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"])

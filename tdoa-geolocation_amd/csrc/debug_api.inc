@@ -120,9 +120,10 @@ int tdoa_debug_poison_workspace(tdoa_ctx *ctx)
     // floats only: no kernel derives an index from a value in these buffers (peak lags come from the keys, which are not
     // poisoned), so a NaN can end up in a result but never in an address.  (stack_q holds integers: the pattern is a large
     // number there, and every element is written before it is read like the floats; so does track_t, the sums of
-    // tdoa_process_track -- its steps, track_d, are added to lag indices and stay as they are)
+    // tdoa_process_track -- its steps, track_d, are added to lag indices and stay as they are; the closure search's
+    // candidates, cells and records are compared and copied, never added to an address)
     for (DevBuf *b : {&ctx->v, &ctx->tz, &ctx->fine_raw, &ctx->once_edges, &ctx->surf, &ctx->surf_out, &ctx->stack_q, &ctx->stack_surf,
-                      &ctx->track_t})
+                      &ctx->track_t, &ctx->closure_part, &ctx->closure_best, &ctx->closure_out})
         if (b->p && b->cap >= 4) HIPCHK(ctx, hipMemsetD32Async(static_cast<hipDeviceptr_t>(b->p), 0x7FC00000, b->cap / 4, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return TDOA_OK;
@@ -214,6 +215,37 @@ int tdoa_debug_select_peaks(tdoa_ctx *ctx, const float *surface, int n_lags, int
     HIPCHK(ctx, hipMemcpyAsync(peaks, ctx->sel_peaks.p, sizeof(PeakOut) * k, hipMemcpyDeviceToHost, st));
     if (count) HIPCHK(ctx, hipMemcpyAsync(count, ctx->sel_count.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));       // `one` is a stack object
+    return TDOA_OK;
+}
+
+// the closure search's kernels (closure_api.inc) on the caller's words: n_sets sets of P = S (S-1) / 2 rows of 2 max_lag - 1
+// int64, every set a stack of n_w windows.  Needs the context for max_lag and the device only; its buffers are its own, so a
+// cached step graph and the stack's sums stay as they are.
+int tdoa_debug_closure_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int gate, int min_separation,
+                              const int32_t *centre, tdoa_closure *out)
+{
+    int rc;
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (const char *bad = check_closure_args(gate, min_separation, out)) return fail(ctx, TDOA_ERR_INVALID, bad);
+    if (!q || n_sets < 1 || n_w < 1 || n_stations < 3 || n_stations > kClosureMaxStations)
+        return fail(ctx, TDOA_ERR_INVALID, "q is NULL, n_sets < 1, n_w < 1 or n_stations outside 3 .. 64");
+    const ClosureGeom g = closure_geom(n_stations, ctx->prm.max_lag, gate, min_separation);
+    if ((long long)n_sets * g.T > INT_MAX / 4) return fail(ctx, TDOA_ERR_INVALID, "too many sets");
+    if ((rc = check_ctx(ctx))) return rc;
+    const size_t n_q = (size_t)n_sets * g.P * g.n;
+    if ((rc = ensure(ctx, ctx->closure_q, sizeof(long long) * n_q))) return rc;
+    if ((rc = ensure(ctx, ctx->closure_roots, sizeof(double) * n_sets))) return rc;
+    if ((rc = ensure_closure(ctx, n_sets, g))) return rc;
+    const std::vector<double> roots((size_t)n_sets, std::sqrt((double)n_w));
+    const std::vector<int32_t> c = closure_centres(centre, n_stations);
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->closure_q.p, q, sizeof(long long) * n_q, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->closure_roots.p, roots.data(), sizeof(double) * n_sets, hipMemcpyHostToDevice, st));
+    if ((rc = upload_closure_centre(ctx, c))) return rc;
+    launch_closure(ctx, ctx->closure_q.as<const long long>(), ctx->closure_roots.as<const double>(), n_sets, g);
+    HIPCHK(ctx, hipGetLastError());
+    if ((rc = download_closure(ctx, n_sets, g, out))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(st));       // the host vectors go out of scope
     return TDOA_OK;
 }
 

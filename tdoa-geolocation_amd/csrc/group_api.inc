@@ -299,6 +299,50 @@ int tdoa_group_process_stacked(tdoa_group *g, int windows_per_stack, int k, int 
     return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
 }
 
+// tdoa_process_closure over the members: their shares of the fixed-point sums as in tdoa_group_process_stacked, added on the
+// host; member 0 searches the merged Q with the kernels a single context's call ends with.
+int tdoa_group_process_closure(tdoa_group *g, int windows_per_stack, int gate, int min_separation, const int32_t *centre,
+                               tdoa_closure *closure_host)
+{
+    if (!g) return TDOA_ERR_INVALID;
+    if (windows_per_stack < 0) return group_fail(g, TDOA_ERR_INVALID, "windows_per_stack < 0");
+    if (const char *bad = check_closure_args(gate, min_separation, closure_host)) return group_fail(g, TDOA_ERR_INVALID, bad);
+    const int world = (int)g->members.size();
+    tdoa_ctx *c0 = g->members[0];
+    if (world == 1) {                        // no merge: the member's call writes the records
+        const int rc = tdoa_process_closure(c0, windows_per_stack, gate, min_separation, centre, closure_host);
+        return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
+    }
+    if (c0->prm.lag_mode == TDOA_LAGS_GO) return group_fail(g, TDOA_ERR_UNSUPPORTED, "the closure search with TDOA_LAGS_GO");
+    if (c0->caps.empty()) return group_fail(g, TDOA_ERR_STATE, member_name(0, c0->device) + "captures missing");
+    if (c0->caps.size() < 3 || c0->caps.size() > (size_t)kClosureMaxStations)
+        return group_fail(g, TDOA_ERR_UNSUPPORTED, "the closure search needs 3 .. 64 stations");
+    if (int who = 0; !group_same_captures(g, &who))
+        return group_fail(g, TDOA_ERR_STATE, member_name(who, g->members[who]->device) +
+                                                 "station count or capture lengths differ from member 0's");
+    int n_stacks = 0;
+    if (tdoa_num_stacks(c0, windows_per_stack, nullptr, &n_stacks) != TDOA_OK)
+        return group_fail(g, TDOA_ERR_STATE, member_name(0, c0->device) + "captures missing or too small");
+    const size_t n_q = (size_t)n_stacks * tdoa_num_pairs(c0) * (size_t)(2 * c0->prm.max_lag - 1);
+    g->partial.resize(world);
+    for (auto &q : g->partial) q.resize(n_q);
+    std::vector<int> status(world, TDOA_OK);
+    const bool ran = run_members(world, [&](int m) {
+        status[m] = tdoa_process_stacked(g->members[m], m, world, windows_per_stack, 1, 1, 0.0, nullptr, nullptr, nullptr, nullptr,
+                                         g->partial[m].data());
+    });
+    if (!ran) return group_fail(g, TDOA_ERR_NOMEM, "could not start a member thread");
+    for (int m = 0; m < world; m++)
+        if (status[m] != TDOA_OK) return member_fail(g, m, status[m]);
+    std::vector<int64_t> &sum = g->partial[0];
+    for (int m = 1; m < world; m++) {
+        const int64_t *q = g->partial[m].data();
+        for (size_t i = 0; i < n_q; i++) sum[i] += q[i];
+    }
+    const int rc = closure_from_host(c0, sum.data(), windows_per_stack, gate, min_separation, centre, closure_host);
+    return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
+}
+
 int tdoa_debug_owned_runs(size_t total_samples, size_t n_min, int64_t window_len, int rank, int world, size_t *first,
                           size_t *count, int max_runs, int *n_runs)
 {

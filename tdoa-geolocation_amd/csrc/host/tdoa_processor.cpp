@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -114,6 +114,8 @@ int main(int argc, char **argv)
     int drift_h = 0, drift_d = 1;
     bool track = false;      // --track=J (with --stack): one lag per window of every stack, at most J lags apart (tdoa_process_track)
     int track_j = 0;
+    bool closure = false;    // --closure=G[/SEP] (with --stack): per stack and station triple the three lags that close (tdoa_process_closure)
+    int closure_g = 0, closure_sep = 1;
     double gate = 120.0;     // samples; PROJECT_NOTES.md:29-32 (max |TDOA| about 57 us = 114 samples at 2 Msps)
     tdoa_params prm;
     tdoa_default_params(&prm);
@@ -131,6 +133,12 @@ int main(int argc, char **argv)
             drift_d = slash == std::string::npos ? 1 : std::atoi(a.c_str() + slash + 1);
         }
         else if (a.rfind("--track=", 0) == 0) { track = true; track_j = std::atoi(a.c_str() + 8); }
+        else if (a.rfind("--closure=", 0) == 0) {
+            closure = true;
+            closure_g = std::atoi(a.c_str() + 10);
+            const size_t slash = a.find('/');
+            closure_sep = slash == std::string::npos ? 1 : std::atoi(a.c_str() + slash + 1);
+        }
         else if (a == "--gate" && i + 1 < argc) gate = std::atof(argv[++i]);
         else if (a == "--device" && i + 1 < argc) prm.device = std::atoi(argv[++i]);
         else if (a == "--window" && i + 1 < argc) prm.window_len = std::atoll(argv[++i]);
@@ -141,6 +149,7 @@ int main(int argc, char **argv)
     }
     if (drift && !stack) { std::fprintf(stderr, "--drift needs --stack\n"); return 1; }
     if (track && !stack) { std::fprintf(stderr, "--track needs --stack\n"); return 1; }
+    if (closure && !stack) { std::fprintf(stderr, "--closure needs --stack\n"); return 1; }
     if (pos.size() < 4) {                                     // processor.go:1048-1052
         usage(argv[0]);
         return 1;
@@ -306,6 +315,7 @@ int main(int argc, char **argv)
         std::vector<int32_t> sdrift;             // --drift: h* per stack-pair (tdoa_process_stacked_drift)
         std::vector<tdoa_peak> tscore;           // --track: the score and the lags of every stack-pair's track (tdoa_process_track)
         std::vector<int32_t> tlags;
+        std::vector<tdoa_closure> clos;          // --closure: one record per stack and station triple (tdoa_process_closure)
         if (stack) {
             if ((rc = tdoa_num_stacks(ctx, stack_m, &spb, &n_stacks))) return die("tdoa_num_stacks", rc);
             spk.resize((size_t)n_stacks * P * 2);
@@ -324,6 +334,11 @@ int main(int argc, char **argv)
                 tlags.resize((size_t)n_stacks * P * mm);
                 if ((rc = tdoa_process_track(ctx, stack_m, track_j, tscore.data(), tlags.data(), nullptr, nullptr, nullptr)))
                     return die("tdoa_process_track", rc);
+            }
+            if (closure) {
+                clos.resize((size_t)n_stacks * std::max(tdoa_num_triples(ctx), 1));
+                if ((rc = tdoa_process_closure(ctx, stack_m, closure_g, closure_sep, nullptr, clos.data())))
+                    return die("tdoa_process_closure", rc);
             }
         }
         std::printf("\n=== FM-DISCRIMINATOR CROSS-CORRELATION: %d windows x %d pairs ===\n", W, P);
@@ -390,6 +405,21 @@ int main(int argc, char **argv)
                 tgt_dt.push_back(lag_used / prm.sample_rate);
                 tgt_w.push_back(median(ct));
             }
+        // --closure: the three lags of every station triple that close, a line per stack and triple
+        const int T = closure ? tdoa_num_triples(ctx) : 0, cm = stack_m > 0 && stack_m < wpb ? stack_m : wpb;
+        for (int sid = 0; sid < (T ? n_stacks : 0); sid++) {
+            const double root = std::sqrt((double)std::min(cm, wpb - (sid % spb) * cm));
+            int t = 0;
+            for (int i = 0; i < S; i++)
+                for (int j = i + 1; j < S; j++)
+                    for (int k = j + 1; k < S; k++, t++) {
+                        const tdoa_closure &c = clos[(size_t)sid * T + t];
+                        std::printf("CLOSURE block %d stack %d %s - %s - %s: lags=%d,%d,%d residual=%d score=%.6f own=%.6f runner=%.6f\n",
+                                    sid / spb + 1, sid % spb, caps[i].st.name.c_str(), caps[j].st.name.c_str(), caps[k].st.name.c_str(),
+                                    (int)c.lag_ij, (int)c.lag_ik, (int)c.lag_jk, (int)c.residual, c.score,
+                                    (double)c.own_q / 4294967296.0 / root, c.runner_up);
+                    }
+        }
     }
 
     // ---- downstream: range differences and the position solve (processor.go:892-926)

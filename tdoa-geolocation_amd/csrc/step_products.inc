@@ -1,13 +1,13 @@
 // step_products.inc -- what a step (process_impl) can write besides its peak records: the correlation surfaces
 // (tdoa_process_lags), the K strongest peaks per pair-window (tdoa_process_peaks), the stacked surfaces of a block's windows
 // (tdoa_process_stacked), the same stacks taken along the best of 2H+1 lag slopes (tdoa_process_stacked_drift), the best
-// delay track through a stack's windows (tdoa_process_track).  Every product is four functions next to each other, called
-// by process_impl in this order:
+// delay track through a stack's windows (tdoa_process_track), one consistent lag set per station triple of a stack
+// (tdoa_process_closure).  Every product is four functions next to each other, called by process_impl in this order:
 //   reserve_*   its buffers, after the step's grouping is fixed (batch_bound counts them as held, so a later call groups as
 //               this one did); no allocation may happen once the step is being captured
 //   key_*       the words it appends to the step graph's key: everything its launches depend on
 //   (upload_stack, upload_stack_drift, upload_stack_track: the products with descriptors of their own send them with the
-//   step's, when the step is not replayed)
+//   step's, when the step is not replayed; refresh_closure: data a call may change under the same key, sent every time)
 //   enqueue_*   its kernels, after the step's decode -- unscoped launches, kernel nodes only: the step stays one chain
 //   download_*  its asynchronous copies out on ctx->stream
 // All of them read the K5 kernels' lag arrays in ctx->surf, pair-window i of the rank at i * n_lags.
@@ -76,14 +76,22 @@ struct StackTrackProduct {
     std::vector<double> ones;                // upload_stack_desc's host copy of the unit scales
 };
 
+struct ClosureProduct {
+    StackProduct stack;                      // the stack whose sums Q are searched: no output of its own, so no finishing kernels
+    int G = 0, sep = 1;                      // gate, min_separation
+    std::vector<int32_t> centre;             // [stations]: data, not part of the key
+    tdoa_closure *out_host = nullptr;        // [stack][triple]
+};
+
 // the product of one step; the numbers are the first word a product appends to the graph key
 struct StepProduct {
-    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5 } kind = None;
+    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6 } kind = None;
     LagsProduct lags;
     PeaksProduct peaks;
     StackProduct stack;
     StackDriftProduct drift;
     StackTrackProduct track;
+    ClosureProduct closure;
 };
 
 // ctx->surf for the rank's pair-windows; `copies`: float surfaces of the step the product holds in all (the message's size)
@@ -379,6 +387,32 @@ int download_stack_track(const StepView &v, const StackTrackProduct &p)
     return TDOA_OK;
 }
 
+// ---- the closure search on the stacks' sums (stack_closure.hpp, closure_api.inc) ---------------------------------------
+int reserve_closure(const StepView &v, ClosureProduct &p)
+{
+    if (int rc = reserve_stack(v, p.stack)) return rc;
+    const ClosureGeom g = closure_geom((int)p.centre.size(), v.ctx->prm.max_lag, p.G, p.sep);
+    if (ensure_closure(v.ctx, p.stack.layout.n_stacks, g)) return surfaces_nomem(v, "the closure search's candidates and records", 1.0);
+    return TDOA_OK;
+}
+void key_closure(const ClosureProduct &p, std::vector<uint64_t> *key)
+{
+    key->insert(key->end(), {StepProduct::Closure, (uint64_t)p.stack.m, (uint64_t)p.G, (uint64_t)p.sep});
+}
+int refresh_closure(const StepView &v, const ClosureProduct &p) { return upload_closure_centre(v.ctx, p.centre); }
+void enqueue_closure(const StepView &v, const ClosureProduct &p)
+{
+    tdoa_ctx *ctx = v.ctx;
+    enqueue_stack(v, p.stack);
+    const int n_stacks = p.stack.layout.n_stacks;
+    launch_closure(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, n_stacks, v.P).roots, n_stacks,
+                   closure_geom((int)p.centre.size(), ctx->prm.max_lag, p.G, p.sep));
+}
+int download_closure_product(const StepView &v, const ClosureProduct &p)
+{
+    return download_closure(v.ctx, p.stack.layout.n_stacks, closure_geom((int)p.centre.size(), v.ctx->prm.max_lag, p.G, p.sep), p.out_host);
+}
+
 // ---- process_impl's one dispatch per stage ---------------------------------------------------------------------------
 int reserve_product(const StepView &v, StepProduct &p)
 {
@@ -388,6 +422,7 @@ int reserve_product(const StepView &v, StepProduct &p)
     case StepProduct::Stack: return reserve_stack(v, p.stack);
     case StepProduct::StackDrift: return reserve_stack_drift(v, p.drift);
     case StepProduct::StackTrack: return reserve_stack_track(v, p.track);
+    case StepProduct::Closure: return reserve_closure(v, p.closure);
     default: return TDOA_OK;
     }
 }
@@ -399,6 +434,7 @@ void key_product(const StepProduct &p, std::vector<uint64_t> *key)
     case StepProduct::Stack: return key_stack(p.stack, key);
     case StepProduct::StackDrift: return key_stack_drift(p.drift, key);
     case StepProduct::StackTrack: return key_stack_track(p.track, key);
+    case StepProduct::Closure: return key_closure(p.closure, key);
     default: key->insert(key->end(), {StepProduct::None, 0, 0, 0});
     }
 }
@@ -408,8 +444,14 @@ int upload_product(const StepView &v, StepProduct &p)
     case StepProduct::Stack: return upload_stack(v, p.stack);
     case StepProduct::StackDrift: return upload_stack_drift(v, p.drift);
     case StepProduct::StackTrack: return upload_stack_track(v, p.track);
+    case StepProduct::Closure: return upload_stack(v, p.closure.stack);
     default: return TDOA_OK;
     }
+}
+// every call, replayed or not, before the step is launched
+int refresh_product(const StepView &v, const StepProduct &p)
+{
+    return p.kind == StepProduct::Closure ? refresh_closure(v, p.closure) : TDOA_OK;
 }
 void enqueue_product(const StepView &v, const StepProduct &p)
 {
@@ -420,6 +462,7 @@ void enqueue_product(const StepView &v, const StepProduct &p)
     case StepProduct::Stack: return enqueue_stack(v, p.stack);
     case StepProduct::StackDrift: return enqueue_stack_drift(v, p.drift);
     case StepProduct::StackTrack: return enqueue_stack_track(v, p.track);
+    case StepProduct::Closure: return enqueue_closure(v, p.closure);
     default: return;
     }
 }
@@ -431,6 +474,7 @@ int download_product(const StepView &v, const StepProduct &p)
     case StepProduct::Stack: return download_stack_product(v, p.stack);
     case StepProduct::StackDrift: return download_stack_drift(v, p.drift);
     case StepProduct::StackTrack: return download_stack_track(v, p.track);
+    case StepProduct::Closure: return download_closure_product(v, p.closure);
     default: return TDOA_OK;
     }
 }

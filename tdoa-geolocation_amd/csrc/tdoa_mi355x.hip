@@ -38,6 +38,7 @@
 #include "stack_surfaces.hpp"
 #include "stack_drift.hpp"
 #include "stack_track.hpp"
+#include "stack_closure.hpp"
 
 using namespace tdoa;
 
@@ -158,12 +159,16 @@ struct tdoa_ctx {
     // halves of T [stack][pair][2 max_lag - 1][2 polarities], the steps D [stack][pair][stack length][2 max_lag - 1][2], and
     // the score, lags and values of every stack-pair's track
     DevBuf track_tab, track_t, track_d, track_score, track_lags, track_values;
+    // the closure search: the stations' centres, the tiles' candidates [stack][triple][tile], (u*, v*) and the records
+    // [stack][triple]; tdoa_debug_closure_from_q's own words and sqrt(n_w)
+    DevBuf closure_centre, closure_part, closure_best, closure_out, closure_q, closure_roots;
 };
 
 namespace {
 
 static_assert(sizeof(PeakOut) == sizeof(tdoa_peak), "tdoa_peak layout");
 static_assert(sizeof(FmStats) == sizeof(tdoa_fm_stats), "tdoa_fm_stats layout");
+static_assert(sizeof(ClosureOut) == sizeof(tdoa_closure) && sizeof(tdoa_closure) == 80, "tdoa_closure layout");
 
 int fail(tdoa_ctx *ctx, int status, const char *what, hipError_t e = hipSuccess)
 {
@@ -345,6 +350,7 @@ int check_selection(tdoa_ctx *ctx, int k, int min_separation, const void *out)
 #include "fm_pair.inc"
 #include "step_graph.inc"
 #include "stacked_api.inc"
+#include "closure_api.inc"
 #include "step_products.inc"
 
 // ===========================================================================
@@ -500,7 +506,8 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->once_edges, &ctx->once_tiles, &ctx->once_fin, &ctx->slot_gain, &ctx->surf, &ctx->surf_out,
                       &ctx->sel_peaks, &ctx->sel_count, &ctx->stack_q, &ctx->stack_surf, &ctx->stack_keys, &ctx->stack_fine,
                       &ctx->stack_desc, &ctx->drift_tab, &ctx->drift_keys, &ctx->drift_h, &ctx->drift_prof, &ctx->track_tab,
-                      &ctx->track_t, &ctx->track_d, &ctx->track_score, &ctx->track_lags, &ctx->track_values};
+                      &ctx->track_t, &ctx->track_d, &ctx->track_score, &ctx->track_lags, &ctx->track_values, &ctx->closure_centre,
+                      &ctx->closure_part, &ctx->closure_best, &ctx->closure_out, &ctx->closure_q, &ctx->closure_roots};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -890,6 +897,7 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
 
         HIPCHK(ctx, hipStreamSynchronize(st));   // host vectors go out of scope below
     }
+    if ((rc = refresh_product(view, prod))) return rc;
 
     auto enqueue = [&]() -> int {
         ctx->prof_last = -1;
@@ -1053,6 +1061,29 @@ int tdoa_process_track(tdoa_ctx *ctx, int windows_per_stack, int max_step, tdoa_
     tp.values_host = values_host;
     tp.surface_host = surface_host;
     tp.total_host = total_host;
+    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, std::move(prod));
+}
+
+int tdoa_process_closure(tdoa_ctx *ctx, int windows_per_stack, int gate, int min_separation, const int32_t *centre,
+                         tdoa_closure *closure_host)
+{
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (windows_per_stack < 0) return fail(ctx, TDOA_ERR_INVALID, "windows_per_stack < 0");
+    if (const char *bad = check_closure_args(gate, min_separation, closure_host)) return fail(ctx, TDOA_ERR_INVALID, bad);
+    if (ctx->prm.lag_mode == TDOA_LAGS_GO) return fail(ctx, TDOA_ERR_UNSUPPORTED, "the closure search with TDOA_LAGS_GO");
+    if (ctx->caps.empty()) return fail(ctx, TDOA_ERR_STATE, "captures missing");
+    const int S = (int)ctx->caps.size();
+    if (S < 3 || S > kClosureMaxStations) return fail(ctx, TDOA_ERR_UNSUPPORTED, "the closure search needs 3 .. 64 stations");
+    StepProduct prod;
+    prod.kind = StepProduct::Closure;
+    ClosureProduct &cp = prod.closure;
+    cp.stack.m = windows_per_stack;
+    cp.stack.k = 1;
+    cp.stack.min_sep = 1;
+    cp.G = gate;
+    cp.sep = min_separation;
+    cp.centre = closure_centres(centre, S);
+    cp.out_host = closure_host;
     return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, std::move(prod));
 }
 

@@ -45,6 +45,10 @@ class FinePeak(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+CLOSURE_DTYPE = np.dtype([("lag_ij", np.int32), ("lag_ik", np.int32), ("lag_jk", np.int32), ("residual", np.int32),
+                          ("score_q", np.int64), ("own_q", np.int64), ("runner_q", np.int64),
+                          ("corr_ij", np.float64), ("corr_ik", np.float64), ("corr_jk", np.float64),
+                          ("score", np.float64), ("runner_up", np.float64)])      # tdoa_closure
 FINE_DTYPE = np.dtype([("delay", np.float64), ("frac", np.float32), ("y", np.float32, (3,)), ("plausible", np.int32),
                        ("reserved", np.int32)])
 
@@ -93,6 +97,7 @@ SYMBOLS = [
     "tdoa_group_capture_upload_files", "tdoa_group_process", "tdoa_debug_owned_runs",
     "tdoa_num_stacks", "tdoa_process_stacked", "tdoa_group_process_stacked", "tdoa_process_stacked_drift",
     "tdoa_process_track",
+    "tdoa_num_triples", "tdoa_process_closure", "tdoa_group_process_closure", "tdoa_debug_closure_from_q",
 ]
 
 _lib = None
@@ -200,6 +205,10 @@ def load(build_if_missing=True):
     L.tdoa_process_stacked_drift.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, i32p, vp, fp,
                                              C.POINTER(C.c_int64), i32p, vp]
     L.tdoa_process_track.argtypes = [vp, C.c_int, C.c_int, vp, i32p, dp, fp, C.POINTER(C.c_int64)]
+    L.tdoa_num_triples.argtypes = [vp]
+    L.tdoa_process_closure.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, vp]
+    L.tdoa_group_process_closure.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, vp]
+    L.tdoa_debug_closure_from_q.argtypes = [vp, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, vp]
     L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
                                         C.POINTER(C.c_int)]
     _lib = L
@@ -558,6 +567,36 @@ class Context:
             out["total"].ctypes.data_as(C.POINTER(C.c_int64)) if want_total else None))
         return out
 
+    def num_triples(self):
+        """tdoa_num_triples: S (S-1) (S-2) / 6 station triples (0 with fewer than three stations)"""
+        return self._L.tdoa_num_triples(self._h)
+
+    def process_closure(self, windows_per_stack=0, gate=0, min_separation=1, centre=None):
+        """tdoa_process_closure -> [n_stacks][T] CLOSURE_DTYPE: per stack and station triple i < j < k the three lags that
+        close (lag_ij + lag_jk = lag_ik) with the largest summed magnitude within `gate` lags of the pairs' centres
+        (centre: one int per station, None: all 0), next to what the three independent argmaxes give (own_q, residual)
+        and the runner-up"""
+        _, n = self.num_stacks(windows_per_stack)
+        out = np.zeros((n, self.num_triples()), dtype=CLOSURE_DTYPE)
+        self._chk(self._L.tdoa_process_closure(self._h, int(windows_per_stack), int(gate), int(min_separation),
+                                               _centre(centre, self.num_stations()), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def closure_from_q(self, q, n_stations, n_w=1, gate=0, min_separation=1, centre=None):
+        """tdoa_debug_closure_from_q: the closure kernels on the caller's words q [n_sets][P][2 max_lag - 1] int64 (or one
+        set [P][2 max_lag - 1]) -> [n_sets][T] CLOSURE_DTYPE"""
+        q = np.ascontiguousarray(q, dtype=np.int64)
+        if q.ndim == 2:
+            q = q[None]
+        S = int(n_stations)
+        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
+            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
+        out = np.zeros((q.shape[0], max(S * (S - 1) * (S - 2) // 6, 1)), dtype=CLOSURE_DTYPE)
+        self._chk(self._L.tdoa_debug_closure_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], S, int(n_w),
+                                                    int(gate), int(min_separation), _centre(centre, S),
+                                                    out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def fm_xcorr_peaks(self, iq1, iq2, max_lag, k, min_separation):
         """tdoa_fm_xcorr_peaks_u8 -> (peaks [k] PEAK_DTYPE, count) of one pair of windows"""
         a = np.ascontiguousarray(iq1, dtype=np.uint8)
@@ -671,6 +710,16 @@ class Context:
         return n.value, n1.value, n2.value
 
 
+def _centre(centre, n_stations):
+    """the centres as the C ABI takes them: None, or n_stations int32"""
+    if centre is None:
+        return None
+    c = np.ascontiguousarray(centre, dtype=np.int32)
+    if c.shape != (int(n_stations),):
+        raise ValueError("centre must hold one integer per station")
+    return c.ctypes.data_as(C.POINTER(C.c_int32))
+
+
 def _stacked_outputs(n_stacks, p, n_lags, k, want_surface, want_partial):
     out = {"peaks": np.zeros((n_stacks, p, max(int(k), 1)), dtype=PEAK_DTYPE), "count": np.zeros((n_stacks, p), dtype=np.int32),
            "fine": np.zeros((n_stacks, p), dtype=FINE_DTYPE)}
@@ -772,6 +821,16 @@ class Group:
             float(self.params.max_lag if gate is None else gate), out["peaks"].ctypes.data_as(C.c_void_p),
             out["count"].ctypes.data_as(C.POINTER(C.c_int32)), out["fine"].ctypes.data_as(C.c_void_p),
             _f(out["surface"]) if want_surface else None))
+        return out
+
+
+    def process_closure(self, windows_per_stack=0, gate=0, min_separation=1, centre=None):
+        """tdoa_group_process_closure -> [n_stacks][T] CLOSURE_DTYPE, byte-identical to a single context's"""
+        m = self.member(0)
+        _, n = m.num_stacks(windows_per_stack)
+        out = np.zeros((n, m.num_triples()), dtype=CLOSURE_DTYPE)
+        self._chk(self._L.tdoa_group_process_closure(self._h, int(windows_per_stack), int(gate), int(min_separation),
+                                                     _centre(centre, m.num_stations()), out.ctypes.data_as(C.c_void_p)))
         return out
 
 
