@@ -529,7 +529,8 @@ enum {
     TDOA_ROUTE_DEC_GP = 13,      /* k_pair_decimate16 on its XCD-grouped grid                                           */
     TDOA_ROUTE_STG_FOLDED = 14,  /* staged column walk without a loader wave                                            */
     TDOA_ROUTE_STG_BLOCKED = 15  /* staged column walk, a BIT FIELD (test the bits below, not == 1):                     */
-                                 /* TDOA_ROUTE_STG_BLOCKED_BIT | TDOA_ROUTE_STG_MERGED_BIT | TDOA_ROUTE_K1_SPLIT_BIT    */
+                                 /* TDOA_ROUTE_STG_BLOCKED_BIT | TDOA_ROUTE_STG_MERGED_BIT | TDOA_ROUTE_K1_SPLIT_BIT |  */
+                                 /* TDOA_ROUTE_STG_PAIRED_BIT | TDOA_ROUTE_STG_NT_BIT                                   */
 };
 enum { TDOA_INV_NONE = 0, TDOA_INV_SEGMENTS = 1, TDOA_INV_DECIMATED = 2, TDOA_INV_SHORT_LAG = 3, TDOA_INV_FULL = 4 };
 enum { TDOA_STEP_TILES = 0, TDOA_STEP_COLUMNS = 1, TDOA_STEP_STAGED = 2 };
@@ -548,6 +549,10 @@ enum {
 #define TDOA_ROUTE_K1_SPLIT_BIT 4    /* (same slot) the fused column kernel looks angles up in the 96 KB split half-plane     */
                                      /* table -- 160 KB of LDS -- instead of the quadrant table (TDOA_K1_QUAD_TABLE=1)        */
                                      /* (the 4096 x 512 plan's kernel: only under TDOA_K1_SPLIT_512=1)                        */
+#define TDOA_ROUTE_STG_PAIRED_BIT 8  /* ... the blocks are paired lines: a row's 64 columns of block cb, then the partner    */
+                                     /* row's 64 columns of block 63 - cb -- one KB per LDS-DMA (TDOA_NO_STG_PAIRED=1: off)  */
+#define TDOA_ROUTE_STG_NT_BIT 16     /* ... and the loader wave's LDS-DMA is non-temporal: one pair group per window, every  */
+                                     /* staged byte read once (TDOA_NO_STG_NT=1: off)                                        */
 int tdoa_debug_last_route(const tdoa_ctx *ctx, int32_t info[16]);
 /* tests only (host, no GPU): the cover of a window's station pairs by "quads" -- two template stations x two signal
  * stations whose two packed transforms per segment serve up to four pairs in the segment form.
@@ -564,6 +569,11 @@ int tdoa_debug_segment_quads(int n_stations, const int32_t *pairs, int n_pairs, 
  * More than eight stations: every group stays within eight.  Returns the number of groups, or a negative TDOA_ERR_* value
  * (stations outside 2..16, max_pairs outside 1..16, more than max_groups). */
 int tdoa_debug_staged_groups(int n_stations, int max_pairs, uint32_t *masks_out, int32_t *counts_out, uint8_t *pairs_out, int max_groups);
+
+/* tests only (host, no GPU): where the paired block layout of the staged column walk (csrc/dec_staged.hpp, stg_paired_at) puts
+ * element (row, col) of a 4096-column x n2-row spectrum: the element index in [0, 4096 n2), = (cb n2 + k2) 128 + e for line
+ * [cb][k2], element e.  n2 = 256 or 512, row in [0, n2), col in [0, 4096); anything else returns -1. */
+int64_t tdoa_debug_stg_paired_index(int n2, int row, int col);
 
 /* tests only (host, no GPU): the split half-plane angle table of the fused column kernels as the library builds it --
  * for index i = b_I | (b_Q & 0x7f) << 8 of a sample with b_Q >= 128 and angle code a in (0, 2^23): hi[i] = a >> 8,

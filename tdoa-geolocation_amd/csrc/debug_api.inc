@@ -45,6 +45,12 @@ int tdoa_debug_staged_groups(int n_stations, int max_pairs, uint32_t *masks_out,
     return (int)g.size();
 }
 
+int64_t tdoa_debug_stg_paired_index(int n2, int row, int col)
+{
+    if ((n2 != 256 && n2 != 512) || row < 0 || row >= n2 || col < 0 || col >= 4096) return -1;
+    return (int64_t)tdoa::stg_paired_at(n2, row, col);
+}
+
 int tdoa_debug_k1_split_table(uint16_t *hi, uint8_t *lo)
 {
     if (!hi || !lo) return TDOA_ERR_INVALID;

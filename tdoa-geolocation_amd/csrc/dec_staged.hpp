@@ -8,8 +8,8 @@
 // for a GROUP of its pairs:
 //   * a LOADER wave brings the rows (k2, N2 - k2) of every station the group's pairs touch into LDS by LDS-DMA
 //     (global_load_lds_dwordx4: one wave-instruction = the 512 bytes of a station's row piece + the 512 bytes of its partner
-//     row piece, no VGPR in between), R rows per phase into a ring of two (or more) phases -- a phase's bytes are asked for while
-//     the phase before it is read;
+//     row piece -- one KB line of the paired layout below --, no VGPR in between), R rows per phase into a ring of two (or
+//     more) phases -- a phase's bytes are asked for while the phase before it is read;
 //   * every COMPUTE wave walks one pair: the register stencil of dec_walk.hpp (twelve accumulators per walk, K3 on
 //     packed pairs), its four operands per row four ds_read_b64, the row's taps through the scalar cache into SGPR pairs;
 //   * one raw s_barrier per phase; the loader waits with a counted vmcnt (later phases stay in flight across the barrier).
@@ -20,8 +20,17 @@
 // eight stations -- a station sits in the ring at its RANK among the group's stations, so eight rows per phase fit for any S.
 // A station's row piece comes from memory once per GROUP; the groups of one (window, column block) take consecutive slots
 // of one XCD and start together, so later groups find rows in that XCD's L2.
-// Where the plan leaves room (N2 = 256, 512) the row pass writes the spectra in BLOCKS of 64 columns, [column / 64][k2][column % 64]:
-// a loader's pieces of consecutive rows are then consecutive in memory and a station's R rows go out back to back.
+// Where the plan leaves room (N2 = 256, 512) the row pass writes the spectra in BLOCKS of 64 columns, as PAIRED LINES (round 9,
+// stg_paired_at below): U[cb (32)][k2][128], line [cb][k2] = the 64 columns of block cb of row k2, then the 64 columns of block
+// 63 - cb of the partner row N2 - k2 -- exactly the KB the ring holds for a station and row.  One LDS-DMA instruction then
+// reads one contiguous KB (lane l its bytes 16 l ..), a station's rows follow each other in memory through the whole walk
+// (one ascending stream per station: R KB per phase), row 0's partner lies in its own line and phase 0 goes out like every
+// other phase.  Where a window's pairs are ONE group every staged byte has one reader in the launch, and the loader wave asks
+// for it non-temporally (kStgLayoutNt; several groups keep the default policy: the later ones find the rows in their XCD's L2).
+// Before round 9 the blocks were [column / 64][k2][column % 64] -- the forward piece and the partner piece of a ring line in
+// different blocks, lanes 0..31 ascending through one and lanes 32..63 descending through the other: two 512-byte pieces per
+// instruction, two 4 KB runs per station and phase, phase 0 (row 0 pairs with row 0) row by row through the hand-laid block.
+// That form stays behind TDOA_NO_STG_PAIRED=1, non-temporal loads behind TDOA_NO_STG_NT=1; measured: DESIGN.md section 9.
 // Outputs: exactly k_pair_decimate_cols's -- G[pw][N2/16][4096] and the neighbour shares X[pw][12][4096] -- or, with MERGE_, G
 // with the shares of a block's inner columns already added (the same bits the row pass would produce) and X at the block-edge
 // columns only.
@@ -54,7 +63,7 @@ constexpr int kStgMaxInFlight = 60;          // LDS-DMA instructions a loader wa
 #define TDOA_STG_MERGE_WAVES 8
 #endif
 constexpr int kStgMergeWaves = TDOA_STG_MERGE_WAVES;
-constexpr int kStgBlockCols = 64;            // the blocked layout of the unpacked spectra: [column / 64][row k2][column % 64]
+constexpr int kStgBlockCols = 64;            // columns per block of the unpacked spectra (paired lines, or [column / 64][row k2][column % 64])
 // one workgroup's share of a window's pairs: `n` of them, by their index in the window's pair list, and the stations they touch
 // (bit s = the window's station s); a station's place in the LDS ring is its rank among the set bits
 struct StgGroup {
@@ -63,7 +72,75 @@ struct StgGroup {
     uint8_t pair[16];
 };
 
+// what the launch tells the kernel about the unpacked spectra and the loader's loads (k_pair_decimate_staged's `layout`)
+enum : int {
+    kStgLayoutBlocked = 1,      // blocks of 64 columns (either form below); 0: row-major rows, in place
+    kStgLayoutPaired = 2,       // ... the PAIRED blocks of stg_paired_at
+    kStgLayoutNt = 4            // the loader wave's LDS-DMA non-temporal: every staged byte has one reader in this launch
+};
+
+// The PAIRED block layout of a station-window's unpacked spectrum (4096 columns x N2 rows, N2 = 256 / 512 a power of two):
+// U[cb (32)][k2 (N2)][128].  Line [cb][k2] is the 1 KB the LDS ring holds for that station and row -- columns 64 cb .. 64 cb + 63
+// of row k2, then columns 4032 - 64 cb .. 4095 - 64 cb of the partner row (N2 - k2) mod N2 (rows 0 and N2 / 2 pair with
+// themselves), both ascending -- so one LDS-DMA instruction reads ONE contiguous KB, a station's rows follow each other in memory
+// through the whole walk (8 KB per phase of eight rows, one ascending stream), and phase 0 is a phase like any other.
+// The element index of (row, column); used by the row pass that writes the layout (k_fwd_row4096_unpack), by both loaders and
+// by the walk's row-0 reads below, and exported to the tests (tdoa_debug_stg_paired_index).
+__host__ __device__ inline size_t stg_paired_at(int n2, int row, int col)
+{
+    const int b = col >> 6;
+    return b < 32 ? ((size_t)b * (size_t)n2 + (size_t)row) * 128 + (size_t)(col & 63)
+                  : ((size_t)(63 - b) * (size_t)n2 + (size_t)((n2 - row) & (n2 - 1))) * 128 + 64 + (size_t)(col & 63);
+}
+
 #if TDOA_HAVE_DEC_COLS
+
+// One station's R_ rows of a phase by LDS-DMA, as ONE asm statement: M0 (the LDS destination) is written and read inside the
+// same statement, the compiler can put nothing between its parts, and the wait state an M0 write needs before the next LDS-DMA
+// is in the text: the s_nop after the first write, the v_add between every later write and the next load.  M0 is the
+// compiler's own register: the statement leaves it as it found it.  (Naming it as clobbered instead is refused -- "clobber list
+// contains reserved registers: m0 ... may lead to undefined behaviour", once per instantiation.)
+// A row is 1 KB further on in LDS; in memory `step` further per lane.
+// (hipcc counts none of these loads: the caller waits with stg_wait_vm.)
+#define TDOA_STG_ROW(mod_, step_) "global_load_lds_dwordx4 %[v], %[b]" mod_ "\n\ts_add_u32 m0, m0, 0x400\n\tv_add_u32 %[v], " step_ ", %[v]\n\t"
+#define TDOA_STG_ROWS2(mod_, step_) TDOA_STG_ROW(mod_, step_) TDOA_STG_ROW(mod_, step_)
+#define TDOA_STG_ROWS4(mod_, step_) TDOA_STG_ROWS2(mod_, step_) TDOA_STG_ROWS2(mod_, step_)
+#define TDOA_STG_ROWS8(mod_, step_) TDOA_STG_ROWS4(mod_, step_) TDOA_STG_ROWS4(mod_, step_)
+#define TDOA_STG_STATION(rows_, ...)                                                                                           \
+    asm volatile("s_mov_b32 %[keep], m0\n\ts_mov_b32 m0, %[dst]\n\ts_nop 0\n\t" rows_ "s_mov_b32 m0, %[keep]"                    \
+                 : [keep] "=&s"(keep), [v] "+v"(v) : [b] "s"(base), [dst] "s"(dst), ##__VA_ARGS__ : "memory", "scc")
+// paired layout: lane l reads bytes 16 l .. 16 l + 15 of a line, the next row's line is the next KB.  NT_: non-temporal.
+template <int R_, bool NT_>
+__device__ __forceinline__ void stg_dma_lines(unsigned int v, unsigned long long base, unsigned int dst)
+{
+    static_assert(R_ == 2 || R_ == 4 || R_ == 8, "rows per phase");
+    unsigned int keep;
+    if constexpr (NT_) {
+        if constexpr (R_ == 8) TDOA_STG_STATION(TDOA_STG_ROWS8(" nt", "0x400"));
+        else if constexpr (R_ == 4) TDOA_STG_STATION(TDOA_STG_ROWS4(" nt", "0x400"));
+        else TDOA_STG_STATION(TDOA_STG_ROWS2(" nt", "0x400"));
+    } else {
+        if constexpr (R_ == 8) TDOA_STG_STATION(TDOA_STG_ROWS8("", "0x400"));
+        else if constexpr (R_ == 4) TDOA_STG_STATION(TDOA_STG_ROWS4("", "0x400"));
+        else TDOA_STG_STATION(TDOA_STG_ROWS2("", "0x400"));
+    }
+}
+// [column / 64][k2][column % 64] blocks: lanes 0..31 the forward piece (the next row 512 bytes up), lanes 32..63 the partner
+// piece of block 63 - cb (512 bytes down): dv = +-512 per lane
+template <int R_>
+__device__ __forceinline__ void stg_dma_halves(unsigned int v, int dv, unsigned long long base, unsigned int dst)
+{
+    static_assert(R_ == 2 || R_ == 4 || R_ == 8, "rows per phase");
+    unsigned int keep;
+    if constexpr (R_ == 8) TDOA_STG_STATION(TDOA_STG_ROWS8("", "%[dv]"), [dv] "v"(dv));
+    else if constexpr (R_ == 4) TDOA_STG_STATION(TDOA_STG_ROWS4("", "%[dv]"), [dv] "v"(dv));
+    else TDOA_STG_STATION(TDOA_STG_ROWS2("", "%[dv]"), [dv] "v"(dv));
+}
+#undef TDOA_STG_STATION
+#undef TDOA_STG_ROWS8
+#undef TDOA_STG_ROWS4
+#undef TDOA_STG_ROWS2
+#undef TDOA_STG_ROW
 
 #ifdef TDOA_STG_TIMING
 // measurement build: wave-cycles [0] walks in total, [1] walks at the barrier, [2] loaders in total, [3] loaders waiting for
@@ -110,7 +187,7 @@ __global__ __launch_bounds__(64 * (MERGE_ ? kStgMergeWaves : kStgMaxWaves))
 __attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kStgMergeWaves / 4 : 4) TDOA_STG_DS_OPS)) void k_pair_decimate_staged(const PWDesc *pw, const float2 *U, float2 *G, float2 *X, FftPlan pl,
                                                                              const float *__restrict__ taps, const StgGroup *__restrict__ groups,
                                                                              int n_items, int P, int S, int n_cw, int n_groups, int nb,
-                                                                             long long u_stride, int blocked)
+                                                                             long long u_stride, int layout)
 {
     constexpr int N2 = N2_, N1 = 4096, SS = kDecSteps, R = R_;
     static_assert(16 % R == 0 && N2 % R == 0 && R % 2 == 0, "ring and loop geometry");
@@ -118,6 +195,7 @@ __attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kSt
     // four operand addresses change once per PHASE (one v_add each) and the row inside the phase is an immediate offset
     extern __shared__ __attribute__((aligned(16))) unsigned char stage_raw[];
     const int t = threadIdx.x;
+    const bool blocked = (layout & kStgLayoutBlocked) != 0, paired = (layout & kStgLayoutPaired) != 0, nt = (layout & kStgLayoutNt) != 0;
     // workgroup -> (window, column block, group of pairs): the groups of an item are consecutive slots of one XCD
     const unsigned int b = blockIdx.x, xcd = b & 7u, slot = b >> 3;
     const int item = (int)(xcd + 8u * (slot / (unsigned int)n_groups)), grp = (int)(slot % (unsigned int)n_groups);
@@ -131,8 +209,10 @@ __attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kSt
     const unsigned int mask = gd->mask;                            // stations this group's pairs touch: S or fewer
     const int zpad = pl.zpad;
     // where element (row 0, column c) of a station's spectrum lives: row-major rows (in place, the 4096 x 2048 and larger plans)
-    // or blocks of 64 columns, [c / 64][k2][c % 64] (kStgBlockCols; see the loader)
-    auto row0_at = [&](const float2 *base, int c) { return blocked ? base + (size_t)(c >> 6) * ((size_t)N2 * 64) + (c & 63) : base + c; };
+    // or blocks of 64 columns: paired (stg_paired_at) or [c / 64][k2][c % 64] (kStgBlockCols; see the loader)
+    auto row0_at = [&](const float2 *base, int c) {
+        return paired ? base + stg_paired_at(N2, 0, c) : blocked ? base + (size_t)(c >> 6) * ((size_t)N2 * 64) + (c & 63) : base + c;
+    };
     constexpr int NP = N2 / R;                                     // phases
 
     // FOLDED form (no loader wave: blockDim = 64 n_cw; blocked layout, two phases in the ring): the LAST popcount(mask) waves of the
@@ -152,20 +232,17 @@ __attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kSt
     typedef __attribute__((address_space(3))) unsigned char *lds_ptr_f;
     const unsigned int lds0_f = (unsigned int)(uintptr_t)((lds_ptr_f)stage_raw);
     auto issue_one = [&](int ph, int buf_) {                           // rows ph R .. ph R + R - 1 of the duty station -> ring slot buf_
-        unsigned int keep;
         const unsigned int dst = lds0_f + (unsigned int)(buf_ * S * R + duty * R) * 1024u;
-        asm volatile("s_mov_b32 %[keep], m0\n\ts_mov_b32 m0, %[dst]" : [keep] "=&s"(keep) : [dst] "s"(dst) : "memory");
-        if (ph > 0) {                                                  // a station's pieces of consecutive rows: 512 bytes apart
+        if (paired) {                                                  // lines [cb][ph R ..]: R KB in a row, every phase alike
+            stg_dma_lines<R, false>(16u * (unsigned int)lane + 1024u * (unsigned int)(cb * N2 + ph * R), duty_base, dst);
+        } else if (ph > 0) {                                           // a station's pieces of consecutive rows: 512 bytes apart
             const int k2 = ph * R, km2 = N2 - k2;
             const unsigned int of = 8u * ((unsigned int)cb * (N2 * 64u) + (unsigned int)k2 * 64u);
             const unsigned int om = 8u * ((unsigned int)(63 - cb) * (N2 * 64u) + (unsigned int)km2 * 64u);
-            unsigned int v = 16u * (unsigned int)(lane & 31) + (lane < 32 ? of : om);
-            const int dv = lane < 32 ? 512 : -512;
-#pragma unroll
-            for (int r = 0; r < R; r++)
-                asm volatile("global_load_lds_dwordx4 %[v], %[b]\n\tv_add_u32 %[v], %[v], %[dv]\n\ts_add_u32 m0, m0, 0x400"
-                             : [v] "+v"(v) : [b] "s"(duty_base), [dv] "v"(dv) : "memory", "scc");
+            stg_dma_halves<R>(16u * (unsigned int)(lane & 31) + (lane < 32 ? of : om), lane < 32 ? 512 : -512, duty_base, dst);
         } else {                                                       // (row 0 pairs with row 0, not with row N2)
+            unsigned int keep;
+            asm volatile("s_mov_b32 %[keep], m0\n\ts_mov_b32 m0, %[dst]" : [keep] "=&s"(keep) : [dst] "s"(dst) : "memory");
 #pragma unroll
             for (int r = 0; r < R; r++) {
                 const int k2 = r, km2 = k2 ? N2 - k2 : 0;
@@ -174,8 +251,8 @@ __attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kSt
                 const unsigned int v = 16u * (unsigned int)(lane & 31) + (lane < 32 ? of : om);
                 asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %[v], %[b]\n\ts_add_u32 m0, m0, 0x400" : : [v] "v"(v), [b] "s"(duty_base) : "memory", "scc");
             }
+            asm volatile("s_mov_b32 m0, %[keep]" : : [keep] "s"(keep) : "memory");
         }
-        asm volatile("s_mov_b32 m0, %[keep]" : : [keep] "s"(keep) : "memory");
     };
     if (has_duty) issue_one(0, 0);                                     // phase 0; phase ph + 1 goes out at the top of phase ph
 
@@ -203,9 +280,25 @@ __attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kSt
         typedef __attribute__((address_space(3))) unsigned char *lds_ptr;
         const unsigned int lds0 = (unsigned int)(uintptr_t)((lds_ptr)stage_raw);      // the ring's LDS byte address
         auto issue = [&](int ph, int buf) {
-            // blocked layout, every phase but the first (whose row 0 pairs with row 0, not with row N2): station by station, a station's R
-            // rows back to back -- its 512-byte pieces are consecutive in memory (forward: ascending, partner: descending), 4 KB runs;
-            // row by row across the stations the same loads took 6 % longer on sixteen stations (cfg5 78.8 -> 73.8 ms, 8 stations: equal)
+            // blocked layouts: station by station, a station's R rows back to back (row by row across the stations the same loads
+            // took 6 % longer on sixteen stations: cfg5 78.8 -> 73.8 ms, 8 stations: equal).
+            // PAIRED: the lines [cb][ph R .. ph R + R - 1] of every station -- R KB in a row, one lane offset for all stations and
+            // phases, phase 0 included; non-temporal where the launch says that nobody reads a line twice.
+            if (paired) {
+                const unsigned int voff0 = 16u * (unsigned int)lane + 1024u * (unsigned int)(cb * N2 + ph * R);
+                unsigned int dst = lds0 + (unsigned int)(buf * S * R + lw * R) * 1024u;
+#pragma unroll
+                for (int s_ = 0; s_ < kStgMaxStations; s_++) {
+                    if ((mine >> s_) & 1u) {
+                        if (nt) stg_dma_lines<R, true>(voff0, sbase[s_], dst);
+                        else stg_dma_lines<R, false>(voff0, sbase[s_], dst);
+                        dst += (unsigned int)(n_lw * R) * 1024u;
+                    }
+                }
+                return;
+            }
+            // [column / 64][k2][column % 64] blocks, every phase but the first (whose row 0 pairs with row 0, not with row N2): a
+            // station's 512-byte pieces are consecutive in memory (forward: ascending, partner: descending), 4 KB runs
             if (blocked && ph > 0) {
                 const int k2 = ph * R, km2 = N2 - k2;
                 const unsigned int of = 8u * ((unsigned int)cb * (N2 * 64u) + (unsigned int)k2 * 64u);
@@ -216,13 +309,7 @@ __attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kSt
 #pragma unroll
                 for (int s_ = 0; s_ < kStgMaxStations; s_++) {
                     if ((mine >> s_) & 1u) {
-                        unsigned int keep, v = voff0;
-                        asm volatile("s_mov_b32 %[keep], m0\n\ts_mov_b32 m0, %[dst]\n\ts_nop 0" : [keep] "=&s"(keep) : [dst] "s"(dst) : "memory");
-#pragma unroll
-                        for (int r = 0; r < R; r++)
-                            asm volatile("global_load_lds_dwordx4 %[v], %[b]\n\tv_add_u32 %[v], %[v], %[dv]\n\ts_add_u32 m0, m0, 0x400"
-                                         : [v] "+v"(v) : [b] "s"(sbase[s_]), [dv] "v"(dv) : "memory", "scc");
-                        asm volatile("s_mov_b32 m0, %[keep]" : : [keep] "s"(keep) : "memory");
+                        stg_dma_halves<R>(voff0, dv, sbase[s_], dst);
                         dst += (unsigned int)(n_lw * R) * 1024u;
                     }
                 }
@@ -393,6 +480,7 @@ __attribute__((amdgpu_waves_per_eu(MERGE_ ? kStgMergeWaves / 4 : 4, MERGE_ ? kSt
         TDOA_STG_T(const unsigned long long t0 = __builtin_readcyclecounter();)
         if (has_duty) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's share of phase ph has landed
         __builtin_amdgcn_s_barrier();                              // phase ph is in LDS
+        asm volatile("" ::: "memory");                             // ... and no read of the ring is moved above the barrier
         TDOA_STG_T(t_bar += __builtin_readcyclecounter() - t0;)
         if (has_duty && ph + 1 < NP) issue_one(ph + 1, (ph + 1) & 1);      // (folded form: nb = 2)
         const unsigned int base = (unsigned int)(buf * R) * (unsigned int)S * 1024u;

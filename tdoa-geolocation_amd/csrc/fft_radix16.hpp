@@ -206,8 +206,13 @@ __global__ __launch_bounds__(256) void k_fwd_row4096(float2 *TZ, FftPlan pl, boo
 #else
 #define TDOA_ROW_STORE(p, val) (*(p) = (val))
 #endif
+// `paired` (with tile_cols = 64): the staged walk's PAIRED blocks (stg_paired_at, dec_staged.hpp) -- line [cb][k2] holds the 64
+// columns of block cb of row k2 and, behind them, the 64 columns of block 63 - cb of row N2 - k2.  This workgroup has both rows
+// of such a line, so it writes whole lines: [cb][a] and [cb][N2 - a] (a = 0: rows 0 and N2 / 2, each with itself).
+__host__ __device__ inline size_t stg_paired_at(int n2, int row, int col);      // dec_staged.hpp
 template <bool ROWMAJOR = false>
-__global__ __launch_bounds__(512) void k_fwd_row4096_unpack(const float2 *TZ, FftPlan pl, float2 *tiled, bool pre_tw, int tile_cols)
+__global__ __launch_bounds__(512) void k_fwd_row4096_unpack(const float2 *TZ, FftPlan pl, float2 *tiled, bool pre_tw, int tile_cols,
+                                                            bool paired = false)
 {
     extern __shared__ float2 lds2[];                             // [2][kRowLds]
     const int a = blockIdx.x, g = threadIdx.x >> 8, j = threadIdx.x & 255;
@@ -247,6 +252,16 @@ __global__ __launch_bounds__(512) void k_fwd_row4096_unpack(const float2 *TZ, Ff
         float2 *out = tiled + (size_t)blockIdx.y * pl.Zs + (size_t)k2 * 4096 + (size_t)(k2 >> 8) * pl.zpad + j;
 #pragma unroll
         for (int k = 0; k < 16; k++) TDOA_ROW_STORE(out + 256 * k, v[oreg(k)]);
+    } else if (paired) {
+        // a thread's columns j + 256 k lie in blocks (j >> 6) + 4 k: k < 8 the forward halves of lines [(j >> 6) + 4 k][k2],
+        // k >= 8 the partner halves of lines [31 - (j >> 6) - 4 (k - 8)][N2 - k2] -- two bases, four blocks = 512 N2 elements apart
+        float2 *fwd = tiled + (size_t)blockIdx.y * pl.Nc + stg_paired_at(pl.N2, k2, j);
+        float2 *par = tiled + (size_t)blockIdx.y * pl.Nc + stg_paired_at(pl.N2, k2, j + 2048);
+        const ptrdiff_t step = (ptrdiff_t)512 * pl.N2;
+#pragma unroll
+        for (int k = 0; k < 8; k++) TDOA_ROW_STORE(fwd + step * k, v[oreg(k)]);
+#pragma unroll
+        for (int k = 8; k < 16; k++) TDOA_ROW_STORE(par - step * (k - 8), v[oreg(k)]);
     } else {
         // tiles of COLS columns x N2 rows: column k1 = j + 256 k -> tile k1 / COLS.  COLS = 4096 / N2 (4096 elements per tile:
         // k_pair_decimate16) or tile_cols = 64 (the staged column walk's blocks, dec_staged.hpp) -- a divisor of 256 either way,

@@ -115,6 +115,8 @@ enum class PairStep { Tiles, Columns, Staged };        // the decimated inverse'
 // the LDS-staged column walk's launch (dec_staged.hpp)
 struct StagedGeometry {
     bool folded = false, blocked = false;
+    bool paired = false;             // blocked, as the paired lines of stg_paired_at: one contiguous KB per LDS-DMA
+    bool nt = false;                 // the loader wave's LDS-DMA non-temporal (one pair group: a staged byte has one reader)
     bool merged = false;             // the walks of a 64-column block add the neighbour shares among themselves; X: block edges only
     int n_lw = 0, n_cw = 0, slots = 0, groups = 0, off = 0, rows = 0, nb = 0, n_items = 0;
     unsigned int blocks = 0;
@@ -260,6 +262,9 @@ FmRoute plan_fm_batch(const Knobs &k, const StgTables &t, int n_cu, const FftPla
             // the 4096 x 2048 and larger plans keep their rows in place).  A loader's piece of a row is then followed in memory
             // by its piece of the next row -- 4 KB runs per station and phase instead of 512-byte pieces 32 KB apart.
             g.blocked = k.stg_blocks && !cols_only_plan(pl);
+            // ... as paired lines [cb][k2][fwd 64 | partner 64] (stg_paired_at): what the ring holds for a station and row is then
+            // ONE KB of memory, a station's rows one ascending stream -- three 8 KB runs per phase of cfg2 instead of six of 4 KB
+            g.paired = g.blocked && k.stg_paired && (pl.N2 == 256 || pl.N2 == 512);
             // the FOLDED form (dec_staged.hpp: no loader wave, up to sixteen walks, the last waves bring one station each): blocked
             // spectra, a two-phase ring -- where sixteen walks per workgroup make FEWER workgroups (16 stations: eight groups
             // instead of nine, cfg5 pair step 73.5 -> 70.2 ms; 8 stations: 16 + 12 walks measured 3.21 ms against 3.12 for
@@ -273,6 +278,10 @@ FmRoute plan_fm_batch(const Knobs &k, const StgTables &t, int n_cu, const FftPla
             g.off = tab.off;
             g.n_cw = tab.max_n;
             g.slots = tab.slots;
+            // One pair group per (window, column block): every staged byte is read once in the launch, and the loader wave asks
+            // for it non-temporally.  Several groups keep the default policy -- the later ones find the rows in their XCD's L2,
+            // which is what holds cfg4's traffic at its compulsory bytes.
+            g.nt = g.paired && k.stg_nt && !g.folded && g.groups == 1;
             g.n_lw = g.folded ? 0 : std::max(1, std::min(k.stg_loaders ? k.stg_loaders : 1, std::min(4, g.slots)));
             // neighbour shares merged inside the walk (dec_staged.hpp, "merged shares"): the blocked plans.  The merging kernel
             // needs 177 - 191 VGPRs: two waves per SIMD, kStgMergeWaves = 8 per CU.  Merged only where TWO workgroups still share
@@ -493,11 +502,11 @@ void launch_fwd_rows(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
     const size_t lds = sizeof(float2) * 2 * kRowLds;
     ProfScope ps(ctx, TDOA_K_FWD_ROW, 2.0 * (8.0 * (double)pl.Nc) * n_sw);
     if (r.row == RowPass::UnpackBlocks)
-        hipLaunchKernelGGL(k_fwd_row4096_unpack<false>, half, dim3(512), lds, bf.st, bf.tz, pl, spectra, k1_cols, kStgBlockCols);
+        hipLaunchKernelGGL(k_fwd_row4096_unpack<false>, half, dim3(512), lds, bf.st, bf.tz, pl, spectra, k1_cols, kStgBlockCols, r.stg.paired);
     else if (r.row == RowPass::UnpackInPlace)
-        hipLaunchKernelGGL(k_fwd_row4096_unpack<true>, half, dim3(512), lds, bf.st, bf.tz, pl, bf.tz, k1_cols, 0);
+        hipLaunchKernelGGL(k_fwd_row4096_unpack<true>, half, dim3(512), lds, bf.st, bf.tz, pl, bf.tz, k1_cols, 0, false);
     else if (r.row == RowPass::UnpackTiles)
-        hipLaunchKernelGGL(k_fwd_row4096_unpack<false>, half, dim3(512), lds, bf.st, bf.tz, pl, spectra, k1_cols, 0);
+        hipLaunchKernelGGL(k_fwd_row4096_unpack<false>, half, dim3(512), lds, bf.st, bf.tz, pl, spectra, k1_cols, 0, false);
     else if (r.row == RowPass::Hot)
         hipLaunchKernelGGL(k_fwd_row4096, dim3(pl.N2, n_sw), dim3(256), 0, bf.st, bf.tz, pl, k1_cols);
     else
@@ -564,7 +573,8 @@ void launch_pair_step(tdoa_ctx *ctx, const FmRoute &r, const FmBufs &bf)
             auto launch = [&](auto kernel) {
                 hipLaunchKernelGGL(kernel, dim3(sg.blocks), dim3(64 * (sg.n_cw + sg.n_lw)), sg.lds, bf.st, bf.pw, sg.blocked ? spectra : bf.tz, g,
                                    edges, pl, taps, gt, sg.n_items, r.b.pairs_per_window, sg.slots, sg.n_cw, sg.groups, sg.nb,
-                                   sg.blocked ? (long long)pl.Nc : (long long)pl.Zs, (int)sg.blocked);
+                                   sg.blocked ? (long long)pl.Nc : (long long)pl.Zs,
+                                   (sg.blocked ? kStgLayoutBlocked : 0) | (sg.paired ? kStgLayoutPaired : 0) | (sg.nt ? kStgLayoutNt : 0));
             };
             constexpr int N2 = decltype(n2)::value, R = decltype(rows)::value;
             if constexpr (N2 == 256 || N2 == 512) {
@@ -684,7 +694,8 @@ void route_info(const FmRoute &r, int32_t out[16])
     const int32_t v[16] = {(int32_t)r.inv, (int32_t)r.step, (int32_t)r.col, (int32_t)r.row, r.fk, r.seg_pq, r.seg_quads, r.seg_pack3,
                            r.fused_k1, r.once, r.small_fused, r.pruned, r.xcd_pairs > 0, r.dec_gp > 0, r.stg.folded,
                            (r.stg.blocked ? TDOA_ROUTE_STG_BLOCKED_BIT : 0) | (r.stg.merged ? TDOA_ROUTE_STG_MERGED_BIT : 0) |
-                               (r.k1_split ? TDOA_ROUTE_K1_SPLIT_BIT : 0)};
+                               (r.k1_split ? TDOA_ROUTE_K1_SPLIT_BIT : 0) | (r.stg.paired ? TDOA_ROUTE_STG_PAIRED_BIT : 0) |
+                               (r.stg.nt ? TDOA_ROUTE_STG_NT_BIT : 0)};
     std::memcpy(out, v, sizeof(v));
 }
 

@@ -15,7 +15,8 @@ struct Knobs {
     bool force_generic = false, use_graph = true, short_lag = true, segment_form = true, segment_quads = true, decimate = true,
          k1_once = true, pow2_only = false, fused_k1 = true, dec_cols = true, dec_cols_always = false, dec_staged = true,
          small_fused = true, small_fused_always = false, stg_folded = true, stg_folded_always = false, stg_blocks = true,
-         seg_pack3 = true, memset_nodes = false, xcd_rows = true, stg_merge = true, k1_split = true, k1_split_512 = false;
+         seg_pack3 = true, memset_nodes = false, xcd_rows = true, stg_merge = true, k1_split = true, k1_split_512 = false,
+         stg_paired = true, stg_nt = true;
     int zpad = 256, stg_loaders = 0, stg_rows = 0, stg_cw = 0, stg_bufs = 0, seg_chunks_override = 0, xcd_pair_mb = 48;
 };
 
@@ -54,6 +55,11 @@ const KnobVar kKnobVars[] = {
     off_if("TDOA_NO_STG_FOLDED", &Knobs::stg_folded),      // the staged walk always with a loader wave next to at most fifteen walks
     on_if("TDOA_STG_FOLDED_ALWAYS", &Knobs::stg_folded_always),      // ... folded wherever the blocked layout applies (tests)
     off_if("TDOA_NO_STG_BLOCKS", &Knobs::stg_blocks),      // the staged walk reads row-major spectra on every plan
+    // the blocked plans' spectra as [column / 64][k2][column % 64] (two 512-byte pieces per LDS-DMA) instead of the paired lines of
+    // stg_paired_at (dec_staged.hpp)
+    off_if("TDOA_NO_STG_PAIRED", &Knobs::stg_paired),
+    // the loader wave's LDS-DMA with the default cache policy even where a launch reads every staged byte once (one pair group)
+    off_if("TDOA_NO_STG_NT", &Knobs::stg_nt),
     off_if("TDOA_NO_STG_MERGE", &Knobs::stg_merge),        // the staged walk leaves every column's neighbour shares in X for the small plan's row pass
     // loader waves per workgroup of k_pair_decimate_staged, rows per phase, at most n walks (compute waves) per workgroup, phases
     // in the LDS ring (0: the library's choice)

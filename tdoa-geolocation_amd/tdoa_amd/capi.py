@@ -60,10 +60,12 @@ ROUTE_COL_PASS = ["none", "k1_256", "k1_512", "k1_two_sweep", "c256", "two_sweep
 ROUTE_ROW_PASS = ["none", "unpack_blocks", "unpack_in_place", "unpack_tiles", "hot", "generic"]
 ROUTE_FLAGS = ["seg_quads", "seg_pack3", "fused_k1", "once", "small_fused", "pruned", "xcd_pairs", "dec_gp", "stg_folded",
                "stg_blocked"]
-# the last slot is a bit field (TDOA_ROUTE_STG_BLOCKED_BIT, TDOA_ROUTE_STG_MERGED_BIT, TDOA_ROUTE_K1_SPLIT_BIT): last_route()
-# reports each bit as a bool -- ROUTE_FLAGS' last name, then ROUTE_BIT_FLAGS
-ROUTE_STG_BLOCKED_BIT, ROUTE_STG_MERGED_BIT, ROUTE_K1_SPLIT_BIT = 1, 2, 4
-ROUTE_BIT_FLAGS = {"stg_blocked": ROUTE_STG_BLOCKED_BIT, "stg_merged": ROUTE_STG_MERGED_BIT, "k1_split": ROUTE_K1_SPLIT_BIT}
+# the last slot is a bit field (TDOA_ROUTE_STG_BLOCKED_BIT, TDOA_ROUTE_STG_MERGED_BIT, TDOA_ROUTE_K1_SPLIT_BIT,
+# TDOA_ROUTE_STG_PAIRED_BIT, TDOA_ROUTE_STG_NT_BIT): last_route() reports each bit as a bool -- ROUTE_FLAGS' last name, then
+# ROUTE_BIT_FLAGS
+ROUTE_STG_BLOCKED_BIT, ROUTE_STG_MERGED_BIT, ROUTE_K1_SPLIT_BIT, ROUTE_STG_PAIRED_BIT, ROUTE_STG_NT_BIT = 1, 2, 4, 8, 16
+ROUTE_BIT_FLAGS = {"stg_blocked": ROUTE_STG_BLOCKED_BIT, "stg_merged": ROUTE_STG_MERGED_BIT, "k1_split": ROUTE_K1_SPLIT_BIT,
+                   "stg_paired": ROUTE_STG_PAIRED_BIT, "stg_nt": ROUTE_STG_NT_BIT}
 
 
 class FastAnalysis(C.Structure):
@@ -89,7 +91,7 @@ SYMBOLS = [
     "tdoa_num_windows", "tdoa_num_pairs", "tdoa_process", "tdoa_process_u8",
     "tdoa_process_fine", "tdoa_fm_xcorr_fine_u8", "tdoa_window_quality_all", "tdoa_window_quality_u8",
     "tdoa_fm_xcorr_u8", "tdoa_fm_preprocess_u8", "tdoa_fm_xcorr_lags_u8", "tdoa_debug_force_generic",
-    "tdoa_debug_flags", "tdoa_debug_last_k1", "tdoa_debug_graph_info", "tdoa_debug_poison_workspace", "tdoa_debug_last_route", "tdoa_debug_segment_quads", "tdoa_debug_staged_groups", "tdoa_debug_step_layout", "tdoa_debug_k1_split_table", "tdoa_cross_correlate_batch_c64",
+    "tdoa_debug_flags", "tdoa_debug_last_k1", "tdoa_debug_graph_info", "tdoa_debug_poison_workspace", "tdoa_debug_last_route", "tdoa_debug_segment_quads", "tdoa_debug_staged_groups", "tdoa_debug_step_layout", "tdoa_debug_k1_split_table", "tdoa_debug_stg_paired_index", "tdoa_cross_correlate_batch_c64",
     "tdoa_latlon_to_ecef", "tdoa_ecef_to_latlon", "tdoa_solve_3station", "tdoa_solve_nstation", "tdoa_solve_surface",
     "tdoa_profile_enable", "tdoa_profile_select", "tdoa_profile_reset", "tdoa_profile_get", "tdoa_kernel_name",
     "tdoa_plan_info", "tdoa_process_lags", "tdoa_process_peaks", "tdoa_fm_xcorr_peaks_u8", "tdoa_debug_select_peaks",
@@ -171,6 +173,8 @@ def load(build_if_missing=True):
     L.tdoa_debug_segment_quads.argtypes = [C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int]
     L.tdoa_debug_staged_groups.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_int]
     L.tdoa_debug_k1_split_table.argtypes = [C.POINTER(C.c_uint16), u8p]
+    L.tdoa_debug_stg_paired_index.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.tdoa_debug_stg_paired_index.restype = C.c_int64
     L.tdoa_debug_step_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.tdoa_latlon_to_ecef.argtypes = [C.c_double, C.c_double, C.c_double, dp]
@@ -638,8 +642,9 @@ class Context:
     def last_route(self):
         """the kernel forms of the last batch planned, or of the batch the replayed step graph captured
         (tdoa_debug_last_route): {"inverse", "pair_step", "col_pass", "row_pass": names; "fk", "seg_pq": numbers; the
-        ROUTE_FLAGS, "stg_merged" (the staged walk settles the neighbour shares inside a 64-column block) and "k1_split" (the
-        fused column kernel reads the split half-plane angle table): bools}"""
+        ROUTE_FLAGS, "stg_merged" (the staged walk settles the neighbour shares inside a 64-column block), "k1_split" (the
+        fused column kernel reads the split half-plane angle table), "stg_paired" (the staged walk's spectra lie in paired
+        lines, one KB per LDS-DMA) and "stg_nt" (its loader wave's loads are non-temporal): bools}"""
         info = (C.c_int32 * 16)()
         self._chk(self._L.tdoa_debug_last_route(self._h, info))
         out = dict(inverse=ROUTE_INVERSE[info[0]], pair_step=ROUTE_PAIR_STEP[info[1]], col_pass=ROUTE_COL_PASS[info[2]],
@@ -877,6 +882,14 @@ def staged_groups(n_stations, max_pairs=15):
     if n < 0:
         raise ValueError("tdoa_debug_staged_groups: error %d" % -n)
     return [(int(masks[g]), [int(x) for x in pairs[g, :counts[g]]]) for g in range(n)]
+
+
+def stg_paired_index(n2, row, col):
+    """host only: the element index of (row, col) in the staged walk's paired block layout of a 4096 x n2 spectrum"""
+    i = load().tdoa_debug_stg_paired_index(int(n2), int(row), int(col))
+    if i < 0:
+        raise ValueError("tdoa_debug_stg_paired_index: n2 is 256 or 512, row in [0, n2), col in [0, 4096)")
+    return int(i)
 
 
 def k1_split_table():
