@@ -211,6 +211,62 @@ func (g *gpuCorrelator) ProcessClosure(windowsPerStack, gate, minSeparation int,
 	return out, triples, nil
 }
 
+// tablePtr is a delay table as the C ABI takes it: nil (forget the table), or nCells * nStations int32.
+func tablePtr(delay []int32) *C.int32_t {
+	if len(delay) == 0 {
+		return nil
+	}
+	return (*C.int32_t)(unsafe.Pointer(&delay[0]))
+}
+
+// LocateGridTable is the host-only table of a latitude / longitude grid (the header's "delay-table search"): cell
+// r*cols + c at (lat0 + r*dlat, lon0 + c*dlon, heightM), one delay per station in units of 1/16 sample.  stationsLLE holds
+// latitude, longitude and elevation per station.
+func LocateGridTable(stationsLLE []float64, lat0, lon0, dlat, dlon float64, rows, cols int, heightM, sampleRate float64) ([]int32, error) {
+	n := len(stationsLLE) / 3
+	if n < 1 || rows < 1 || cols < 1 || rows*cols > 1<<22 {
+		return nil, fmt.Errorf("tdoa_locate_grid_table: no stations, or rows*cols outside 1 .. 2^22")
+	}
+	delay := make([]int32, rows*cols*n)
+	if rc := C.tdoa_locate_grid_table((*C.double)(unsafe.Pointer(&stationsLLE[0])), C.int(n), C.double(lat0), C.double(lon0),
+		C.double(dlat), C.double(dlon), C.int(rows), C.int(cols), C.double(heightM), C.double(sampleRate),
+		(*C.int32_t)(unsafe.Pointer(&delay[0]))); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_locate_grid_table: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	return delay, nil
+}
+
+// LocateSetTable hands the context its delay table [nCells][nStations] (nil: forget it); nCols gives cells their rows and
+// columns.  The table stays on the device until it is replaced.
+func (g *gpuCorrelator) LocateSetTable(delay []int32, nCells, nCols, nStations int) error {
+	if rc := C.tdoa_locate_set_table(g.ctx, tablePtr(delay), C.int(nCells), C.int(nCols), C.int(nStations)); rc != C.TDOA_OK {
+		return fmt.Errorf("tdoa_locate_set_table: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return nil
+}
+
+// ProcessLocate is the delay-table search: per stack the table's cell with the largest summed magnitude of all pairs' stacks
+// at the cell's lags, the runner-up, and per pair the lag and the signed correlation at the best cell ([stack][pair]; what
+// tdoa_solve_surface takes as range differences and weights).
+func (g *gpuCorrelator) ProcessLocate(windowsPerStack, minSeparation int) (loc []C.tdoa_location, lags []int32, corr []float64, err error) {
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, nil, nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs := int(C.tdoa_num_pairs(g.ctx))
+	if int(total)*pairs == 0 {
+		return nil, nil, nil, fmt.Errorf("tdoa_process_locate: no stacks or fewer than two stations")
+	}
+	loc = make([]C.tdoa_location, int(total))
+	lags = make([]int32, int(total)*pairs)
+	corr = make([]float64, int(total)*pairs)
+	if rc := C.tdoa_process_locate(g.ctx, C.int(windowsPerStack), C.int(minSeparation), &loc[0], (*C.int32_t)(unsafe.Pointer(&lags[0])),
+		(*C.double)(unsafe.Pointer(&corr[0])), nil); rc != C.TDOA_OK {
+		return nil, nil, nil, fmt.Errorf("tdoa_process_locate: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return loc, lags, corr, nil
+}
+
 // windowQuality is fastAnalyzeSamples' statistics (fast_analyzer.go:117-155) for every (window, station).
 func (g *gpuCorrelator) windowQuality(stations int) ([]C.tdoa_window_quality, error) {
 	var perBlock, total C.int
@@ -323,4 +379,34 @@ func (g *Group) ProcessClosure(windowsPerStack, gate, minSeparation int, centre 
 		return nil, 0, fmt.Errorf("tdoa_group_process_closure: %s", C.GoString(C.tdoa_group_last_error(g.g)))
 	}
 	return out, triples, nil
+}
+
+// LocateSetTable hands every member the delay table (gpuCorrelator.LocateSetTable).
+func (g *Group) LocateSetTable(delay []int32, nCells, nCols, nStations int) error {
+	if rc := C.tdoa_group_locate_set_table(g.g, tablePtr(delay), C.int(nCells), C.int(nCols), C.int(nStations)); rc != C.TDOA_OK {
+		return fmt.Errorf("tdoa_group_locate_set_table: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return nil
+}
+
+// ProcessLocate is gpuCorrelator.ProcessLocate over the group: the members' fixed-point partial sums are added on the host
+// and searched on member 0, the same bytes one context returns.
+func (g *Group) ProcessLocate(windowsPerStack, minSeparation int) (loc []C.tdoa_location, lags []int32, corr []float64, err error) {
+	m := C.tdoa_group_member(g.g, 0)
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(m, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, nil, nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs := int(C.tdoa_num_pairs(m))
+	if int(total)*pairs == 0 {
+		return nil, nil, nil, fmt.Errorf("tdoa_group_process_locate: no stacks or fewer than two stations")
+	}
+	loc = make([]C.tdoa_location, int(total))
+	lags = make([]int32, int(total)*pairs)
+	corr = make([]float64, int(total)*pairs)
+	if rc := C.tdoa_group_process_locate(g.g, C.int(windowsPerStack), C.int(minSeparation), &loc[0], (*C.int32_t)(unsafe.Pointer(&lags[0])),
+		(*C.double)(unsafe.Pointer(&corr[0])), nil); rc != C.TDOA_OK {
+		return nil, nil, nil, fmt.Errorf("tdoa_group_process_locate: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return loc, lags, corr, nil
 }

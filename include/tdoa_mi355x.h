@@ -431,6 +431,78 @@ int tdoa_process_closure(tdoa_ctx *ctx, int windows_per_stack, int gate /* G */,
 int tdoa_debug_closure_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int gate,
                               int min_separation, const int32_t *centre, tdoa_closure *out);
 
+/* Delay-table search: a grid of candidate positions scored on all pairs' stacks.  Peaks, drift and tracks look at one
+ * station pair, the closure search at one station triple, and a position is found afterwards from one picked lag per pair
+ * (tdoa_solve_nstation, tdoa_solve_surface) -- a single wrong argmax pulls the fix kilometres off.  S stations have S - 1 free
+ * delays; a transmitter position is the two-parameter family that makes a joint search of all of them tractable.  Every
+ * candidate position ("cell") fixes one delay per station, hence one lag per pair, and its score is the sum of all pairs'
+ * stacked magnitudes at those lags.  The best cell uses every pair at once and needs no peak to be picked.
+ * The search is exact integer work on Q: the library knows nothing about the earth here, the delays are data.
+ * Stacks, windows_per_stack, n_w, pairs i < j in the library's order and the int64 Q_p[l] over -max_lag < l < max_lag are
+ * exactly those of tdoa_process_stacked.  M_p[l] = |Q_p[l]|.
+ *   The table: delay[n_cells][n_stations] is int32, in units of 1/16 sample (TDOA_DELAY_UNIT).  1 <= n_cells <= 2^22.
+ *     Entry t[c][s] is the propagation delay from candidate c to station s.  Only differences matter.
+ *     n_cols >= 1 gives cells their coordinates, row = c div n_cols and col = c mod n_cols.  The last row may be short.
+ *     n_cols = n_cells is a plain list.
+ *   A cell's lags: for pair (i, j), d = t[c][j] - t[c][i], taken in 64 bits.  Then
+ *     lag_p(c) = sgn(d) * ((2|d| + 16) div 32).
+ *     This is the nearest integer to d/16, halves away from zero, integers only (the rule of shift(h, j) in the slope search).
+ *     The sign is tdoa_peak's: lag > 0 means the second station lags the first.  It is also the sign of the closure search's
+ *     centre[j] - centre[i].
+ *   A cell's score: score_q(c) is the sum over all P pairs of M_p[lag_p(c)].  A pair whose lag falls outside the searched
+ *     range contributes 0 and is not counted in pairs_in(c).
+ *   The location is the cell with the largest score_q.  Among equal maxima the smaller cell index wins.
+ *     If the largest score is 0, the zero record and zero lags and correlations are returned.
+ *   The runner-up is the largest score_q over cells with max(|row - row*|, |col - col*|) > min_separation (>= 1).  Ties are
+ *     broken the same way.  runner_q and runner_cell are 0 when there is none (a cell that exists and scores 0 gives
+ *     runner_q 0 and its own index).  A score is judged against the runner-up.
+ *   Overflow: |Q| <= n_w * 2^45.  The call returns TDOA_ERR_UNSUPPORTED when P * (stack length in use) > 2^17, so every sum
+ *     stays below 2^62.
+ * The record, 48 bytes, no padding: */
+#define TDOA_DELAY_UNIT 16
+typedef struct {
+    int32_t cell, runner_cell, pairs_in, reserved;   /* pairs_in of the best cell */
+    int64_t score_q, runner_q;
+    double  score, runner_up;                        /* (double)x_q * 2^-32 / sqrt(n_w) */
+} tdoa_location;
+
+/* The table is context state: it needs no captures, is uploaded once and kept on the device (station-major).  It is data,
+ * not part of a step graph's key -- only n_cells and n_cols are, so a call after a new table of the same shape replays the
+ * same graph.  delay == NULL or n_cells == 0: forget the table.
+ * TDOA_ERR_INVALID: a NULL context, n_cells outside 1 .. 2^22, n_cols < 1, n_stations outside 2 .. 64. */
+int tdoa_locate_set_table(tdoa_ctx *ctx, const int32_t *delay /* [n_cells][n_stations] */, int n_cells, int n_cols, int n_stations);
+
+/* lags_host and corr_host are what a caller hands to tdoa_solve_surface (range difference lag / sample_rate * c, weight
+ * |C|) for a fix finer than the grid.  Runs inside the step graph, behind the stack's accumulation: the scores, the
+ * runner-up's pass over the map and two launches of the finishing kernel.  (windows_per_stack, min_separation, n_cells,
+ * n_cols) are part of the graph's key.  tdoa_group_process_locate is the group form (the search is a function of the
+ * complete stacked Q only, so the members' partial sums merge).
+ * TDOA_ERR_INVALID: a NULL context (checked before anything needs a device), a NULL loc_host, windows_per_stack < 0,
+ * min_separation < 1.  TDOA_ERR_STATE: no captures, no table, or a table whose n_stations differs from the captures'.
+ * TDOA_ERR_UNSUPPORTED: fewer than 2 or more than 64 stations, TDOA_LAGS_GO, the overflow bound (and more than 65535
+ * stacks).  TDOA_ERR_NOMEM: the map [n_stacks_total][n_cells] does not fit; tdoa_last_error says so. */
+int tdoa_process_locate(tdoa_ctx *ctx, int windows_per_stack, int min_separation,
+                        tdoa_location *loc_host /* [n_stacks_total], required */,
+                        int32_t *lags_host      /* [n_stacks_total][n_pairs]: lag_p(cell*), 0 where outside / no location; may be NULL */,
+                        double  *corr_host      /* same shape: signed C = Q * 2^-32 / sqrt(n_w) there; may be NULL */,
+                        int64_t *map_host       /* [n_stacks_total][n_cells]: score_q of every cell; may be NULL */);
+
+/* tests only: the same kernels on the caller's words q [n_sets][P][2*max_lag-1], P = n_stations (n_stations-1) / 2 rows in
+ * the library's pair order, every set a stack of n_w windows, with the context's table; outputs as tdoa_process_locate's
+ * with n_sets for n_stacks_total.  Needs no captures.  Precondition: |q| <= 2^62 div P.  TDOA_ERR_INVALID: what
+ * tdoa_process_locate refuses, q NULL, n_sets outside 1 .. 65535, n_w < 1, n_stations outside 2 .. 64.  TDOA_ERR_STATE: no
+ * table, or one of another n_stations.  TDOA_ERR_UNSUPPORTED: P * n_w > 2^17. */
+int tdoa_debug_locate_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int min_separation,
+                             tdoa_location *loc, int32_t *lags, double *corr, int64_t *map);
+
+/* Host only, no device: the table of a latitude / longitude grid at one height.  Cell r*cols + c lies at
+ * (lat0 + r*dlat, lon0 + c*dlon, height_m), degrees and metres; stations_lle is [n_stations][3] like tdoa_solve_nstation's.
+ * delay = llrint(16 * sample_rate * |ecef(cell) - ecef(station)| / c), through tdoa_latlon_to_ecef, c = 299 792 458 m/s.
+ * TDOA_ERR_INVALID: NULL pointers, n_stations < 1, rows*cols outside 1 .. 2^22, non-finite input, sample_rate <= 0, a delay
+ * that does not fit int32. */
+int tdoa_locate_grid_table(const double *stations_lle, int n_stations, double lat0, double lon0, double dlat, double dlon,
+                           int rows, int cols, double height_m, double sample_rate, int32_t *delay /* [rows*cols][n_stations] */);
+
 /* Capture-quality statistics of every (window, station) in one streaming pass over the bytes
  * in HBM: the byte statistics of fastAnalyzeSamples
  * (fast_analyzer.go:117-155) and the block power of validateDataFile (collector.go:219-224).
@@ -638,6 +710,13 @@ int tdoa_group_process_stacked(tdoa_group *g, int windows_per_stack, int k, int 
  * records directly. */
 int tdoa_group_process_closure(tdoa_group *g, int windows_per_stack, int gate, int min_separation,
                                const int32_t *centre, tdoa_closure *closure_host);
+
+/* tdoa_locate_set_table on every member, and tdoa_process_locate over them: they sum their windows as in
+ * tdoa_group_process_stacked, the host adds the partials, and member 0 runs the search on the merged Q with its table -- the
+ * outputs are byte-identical to tdoa_process_locate(single ctx, ...).  Errors as there and as tdoa_group_process. */
+int tdoa_group_locate_set_table(tdoa_group *g, const int32_t *delay, int n_cells, int n_cols, int n_stations);
+int tdoa_group_process_locate(tdoa_group *g, int windows_per_stack, int min_separation, tdoa_location *loc_host,
+                              int32_t *lags_host, double *corr_host, int64_t *map_host);
 
 /* the sample runs member `rank` of `world` uploads for a capture of total_samples (window grid from n_min, the shortest
  * capture of the job; block offsets from the capture's own thirds): adjacent owned windows form one run, and with fewer

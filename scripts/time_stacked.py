@@ -8,8 +8,11 @@ as a caller sees them.  Every `--drift H/D` adds a leg: tdoa_process_stacked_dri
 hypotheses between them).  Every `--track J` adds a leg: tdoa_process_track(0, J) with score, lags and values downloaded (one
 kernel per window of a block after the surfaces; the difference between two legs is what the wider scan costs).  Every
 `--closure G` adds a leg: tdoa_process_closure(0, G, 1) with the records downloaded (the stack's accumulation, then two
-launches of the search and two of its finish).  `--stations S` runs all legs on S stations (default 3; 8 gives 56 triples).
-usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--drift H/D]... [--track J]... [--closure G]..."""
+launches of the search and two of its finish).  Every `--locate ROWSxCOLS` adds a leg: tdoa_process_locate(0, 1) on a grid of
+that many cells over 0.3 x 0.4 degrees around the stations, with the records, lags and correlations downloaded and the map
+left on the device (the table is set once per round, outside the timed window).  `--stations S` runs all legs on S stations (default 3; 8 gives 56 triples).
+usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--drift H/D]... [--track J]... [--closure G]...
+[--locate ROWSxCOLS]..."""
 import json
 import os
 import sys
@@ -38,7 +41,7 @@ def timed(fn, steps):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
-def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3):
+def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=()):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=20000)
     for s in range(stations):
         c.synth_capture(s, 66_666_666, ST[s % 3], TX, 0x5D0A0000 + s)
@@ -53,9 +56,18 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3):
         legs["process_track_%d_ms" % J] = lambda J=J: c.process_track(0, J)
     for G in closures:
         legs["process_closure_%d_ms" % G] = lambda G=G: c.process_closure(0, G, 1)
+    setup = {}
+    for rows, cols in locates:
+        table = tdoa_amd.capi.locate_grid_table([ST[s % 3] for s in range(stations)], 41.10, -96.20, 0.3 / max(rows - 1, 1),
+                                                0.4 / max(cols - 1, 1), rows, cols, 350.0, 2e6)
+        name = "process_locate_%dx%d_ms" % (rows, cols)
+        setup[name] = lambda table=table, cols=cols: c.locate_set_table(table, cols)
+        legs[name] = lambda: c.process_locate(0, 1)
     times = {name: [] for name in legs}
     for _ in range(rounds):
         for name, fn in legs.items():
+            if name in setup:
+                setup[name]()
             times[name].append(timed(fn, steps))
     out = {"config": "cfg2" if stations == 3 else "cfg2 windows, %d stations" % stations, "stations": stations, "pairs": P, "windows": W, "stacks": n_stacks, "steps": steps, "rounds": rounds,
            "surface_MB": round(W * P * (2 * 20000 - 1) * 4 / 1e6, 1)}
@@ -89,4 +101,10 @@ if __name__ == "__main__":
         i = args.index("--closure")
         closures.append(int(args[i + 1]))
         del args[i:i + 2]
-    main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"])
+    locates = []
+    while "--locate" in args:
+        i = args.index("--locate")
+        rows, _, cols = args[i + 1].partition("x")
+        locates.append((int(rows), int(cols)))
+        del args[i:i + 2]
+    main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates)

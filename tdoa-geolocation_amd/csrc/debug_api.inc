@@ -127,9 +127,12 @@ int tdoa_debug_poison_workspace(tdoa_ctx *ctx)
     // poisoned), so a NaN can end up in a result but never in an address.  (stack_q holds integers: the pattern is a large
     // number there, and every element is written before it is read like the floats; so does track_t, the sums of
     // tdoa_process_track -- its steps, track_d, are added to lag indices and stay as they are; the closure search's
-    // candidates, cells and records are compared and copied, never added to an address)
+    // candidates, cells and records are compared and copied, never added to an address; the delay-table search's map,
+    // candidates and records likewise -- a cell taken from a candidate is checked against the table's size -- and its table,
+    // which is state, is left alone)
     for (DevBuf *b : {&ctx->v, &ctx->tz, &ctx->fine_raw, &ctx->once_edges, &ctx->surf, &ctx->surf_out, &ctx->stack_q, &ctx->stack_surf,
-                      &ctx->track_t, &ctx->closure_part, &ctx->closure_best, &ctx->closure_out})
+                      &ctx->track_t, &ctx->closure_part, &ctx->closure_best, &ctx->closure_out, &ctx->locate_map, &ctx->locate_part,
+                      &ctx->locate_best, &ctx->locate_out, &ctx->locate_lags, &ctx->locate_corr})
         if (b->p && b->cap >= 4) HIPCHK(ctx, hipMemsetD32Async(static_cast<hipDeviceptr_t>(b->p), 0x7FC00000, b->cap / 4, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return TDOA_OK;
@@ -252,6 +255,38 @@ int tdoa_debug_closure_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n
     HIPCHK(ctx, hipGetLastError());
     if ((rc = download_closure(ctx, n_sets, g, out))) return rc;
     HIPCHK(ctx, hipStreamSynchronize(st));       // the host vectors go out of scope
+    return TDOA_OK;
+}
+
+// the delay-table search's kernels (locate_api.inc) on the caller's words: n_sets sets of P = S (S-1) / 2 rows of 2 max_lag - 1
+// int64, every set a stack of n_w windows, against the context's table.  Needs the context for max_lag, the table and the
+// device only; its words are its own, so the stack's sums stay as they are.  (A call that has to allocate or grow one of its
+// buffers moves alloc_gen like every ensure(): the next step captures its graph again, with the same results -- the closure
+// entry above behaves the same way.)
+int tdoa_debug_locate_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int min_separation,
+                             tdoa_location *loc, int32_t *lags, double *corr, int64_t *map)
+{
+    int rc;
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (const char *bad = check_locate_args(min_separation, loc)) return fail(ctx, TDOA_ERR_INVALID, bad);
+    if (!q || n_sets < 1 || n_sets > kLocateMaxSets || n_w < 1 || n_stations < 2 || n_stations > kLocateMaxStations)
+        return fail(ctx, TDOA_ERR_INVALID, "q is NULL, n_sets outside 1 .. 65535, n_w < 1 or n_stations outside 2 .. 64");
+    if (const char *bad = check_locate_table(ctx, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
+    const LocateGeom g = locate_geom(ctx, min_separation);
+    if (locate_overflows(g.P, n_w)) return fail(ctx, TDOA_ERR_UNSUPPORTED, "pairs x n_w > 2^17: a cell's score could overflow");
+    if ((rc = check_ctx(ctx))) return rc;
+    const size_t n_q = (size_t)n_sets * g.P * g.n;
+    if ((rc = ensure(ctx, ctx->locate_q, sizeof(long long) * n_q))) return rc;
+    if ((rc = ensure(ctx, ctx->locate_roots, sizeof(double) * n_sets))) return rc;
+    if ((rc = ensure_locate(ctx, n_sets, g))) return rc;
+    const std::vector<double> roots((size_t)n_sets, std::sqrt((double)n_w));
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->locate_q.p, q, sizeof(long long) * n_q, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->locate_roots.p, roots.data(), sizeof(double) * n_sets, hipMemcpyHostToDevice, st));
+    launch_locate(ctx, ctx->locate_q.as<const long long>(), ctx->locate_roots.as<const double>(), n_sets, g);
+    HIPCHK(ctx, hipGetLastError());
+    if ((rc = download_locate(ctx, n_sets, g, loc, lags, corr, map))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(st));       // the host vector goes out of scope
     return TDOA_OK;
 }
 

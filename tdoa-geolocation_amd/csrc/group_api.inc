@@ -343,6 +343,57 @@ int tdoa_group_process_closure(tdoa_group *g, int windows_per_stack, int gate, i
     return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
 }
 
+// the table to every member: each keeps its own copy, member 0's is the one a group of several searches with
+int tdoa_group_locate_set_table(tdoa_group *g, const int32_t *delay, int n_cells, int n_cols, int n_stations)
+{
+    if (!g) return TDOA_ERR_INVALID;
+    for (size_t m = 0; m < g->members.size(); m++)
+        if (const int rc = tdoa_locate_set_table(g->members[m], delay, n_cells, n_cols, n_stations)) return member_fail(g, (int)m, rc);
+    return TDOA_OK;
+}
+
+// tdoa_process_locate over the members: their shares of the fixed-point sums as in tdoa_group_process_stacked, added on the
+// host; member 0 searches the merged Q with the kernels a single context's call ends with.
+int tdoa_group_process_locate(tdoa_group *g, int windows_per_stack, int min_separation, tdoa_location *loc_host, int32_t *lags_host,
+                              double *corr_host, int64_t *map_host)
+{
+    if (!g) return TDOA_ERR_INVALID;
+    if (windows_per_stack < 0) return group_fail(g, TDOA_ERR_INVALID, "windows_per_stack < 0");
+    if (const char *bad = check_locate_args(min_separation, loc_host)) return group_fail(g, TDOA_ERR_INVALID, bad);
+    const int world = (int)g->members.size();
+    tdoa_ctx *c0 = g->members[0];
+    if (world == 1) {                        // no merge: the member's call writes the outputs
+        const int rc = tdoa_process_locate(c0, windows_per_stack, min_separation, loc_host, lags_host, corr_host, map_host);
+        return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
+    }
+    const char *what = nullptr;
+    if (const int rc = check_locate_state(c0, windows_per_stack, &what)) return group_fail(g, rc, member_name(0, c0->device) + what);
+    if (int who = 0; !group_same_captures(g, &who))
+        return group_fail(g, TDOA_ERR_STATE, member_name(who, g->members[who]->device) +
+                                                 "station count or capture lengths differ from member 0's");
+    int n_stacks = 0;
+    if (tdoa_num_stacks(c0, windows_per_stack, nullptr, &n_stacks) != TDOA_OK)
+        return group_fail(g, TDOA_ERR_STATE, member_name(0, c0->device) + "captures missing or too small");
+    const size_t n_q = (size_t)n_stacks * tdoa_num_pairs(c0) * (size_t)(2 * c0->prm.max_lag - 1);
+    g->partial.resize(world);
+    for (auto &q : g->partial) q.resize(n_q);
+    std::vector<int> status(world, TDOA_OK);
+    const bool ran = run_members(world, [&](int m) {
+        status[m] = tdoa_process_stacked(g->members[m], m, world, windows_per_stack, 1, 1, 0.0, nullptr, nullptr, nullptr, nullptr,
+                                         g->partial[m].data());
+    });
+    if (!ran) return group_fail(g, TDOA_ERR_NOMEM, "could not start a member thread");
+    for (int m = 0; m < world; m++)
+        if (status[m] != TDOA_OK) return member_fail(g, m, status[m]);
+    std::vector<int64_t> &sum = g->partial[0];
+    for (int m = 1; m < world; m++) {
+        const int64_t *q = g->partial[m].data();
+        for (size_t i = 0; i < n_q; i++) sum[i] += q[i];
+    }
+    const int rc = locate_from_host(c0, sum.data(), windows_per_stack, min_separation, loc_host, lags_host, corr_host, map_host);
+    return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
+}
+
 int tdoa_debug_owned_runs(size_t total_samples, size_t n_min, int64_t window_len, int rank, int world, size_t *first,
                           size_t *count, int max_runs, int *n_runs)
 {

@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -116,6 +116,11 @@ int main(int argc, char **argv)
     int track_j = 0;
     bool closure = false;    // --closure=G[/SEP] (with --stack): per stack and station triple the three lags that close (tdoa_process_closure)
     int closure_g = 0, closure_sep = 1;
+    // --locate=ROWSxCOLS/SPAN_KM (with --stack): per stack the best cell of a square grid of that span centred on the stations'
+    // centroid, at their mean height (tdoa_process_locate)
+    bool locate = false;
+    int locate_rows = 0, locate_cols = 0;
+    double locate_km = 0.0;
     double gate = 120.0;     // samples; PROJECT_NOTES.md:29-32 (max |TDOA| about 57 us = 114 samples at 2 Msps)
     tdoa_params prm;
     tdoa_default_params(&prm);
@@ -139,6 +144,14 @@ int main(int argc, char **argv)
             const size_t slash = a.find('/');
             closure_sep = slash == std::string::npos ? 1 : std::atoi(a.c_str() + slash + 1);
         }
+        else if (a.rfind("--locate=", 0) == 0) {
+            locate = true;
+            if (std::sscanf(a.c_str() + 9, "%dx%d/%lf", &locate_rows, &locate_cols, &locate_km) != 3 || locate_rows < 1 || locate_cols < 1 ||
+                (long long)locate_rows * locate_cols > (1ll << 22) || !(locate_km > 0.0)) {
+                std::fprintf(stderr, "--locate=ROWSxCOLS/SPAN_KM with ROWS x COLS in 1 .. 2^22 and SPAN_KM > 0, e.g. --locate=64x64/40\n");
+                return 1;
+            }
+        }
         else if (a == "--gate" && i + 1 < argc) gate = std::atof(argv[++i]);
         else if (a == "--device" && i + 1 < argc) prm.device = std::atoi(argv[++i]);
         else if (a == "--window" && i + 1 < argc) prm.window_len = std::atoll(argv[++i]);
@@ -150,6 +163,7 @@ int main(int argc, char **argv)
     if (drift && !stack) { std::fprintf(stderr, "--drift needs --stack\n"); return 1; }
     if (track && !stack) { std::fprintf(stderr, "--track needs --stack\n"); return 1; }
     if (closure && !stack) { std::fprintf(stderr, "--closure needs --stack\n"); return 1; }
+    if (locate && !stack) { std::fprintf(stderr, "--locate needs --stack\n"); return 1; }
     if (pos.size() < 4) {                                     // processor.go:1048-1052
         usage(argv[0]);
         return 1;
@@ -316,6 +330,8 @@ int main(int argc, char **argv)
         std::vector<tdoa_peak> tscore;           // --track: the score and the lags of every stack-pair's track (tdoa_process_track)
         std::vector<int32_t> tlags;
         std::vector<tdoa_closure> clos;          // --closure: one record per stack and station triple (tdoa_process_closure)
+        std::vector<tdoa_location> locs;         // --locate: one record per stack (tdoa_process_locate)
+        double grid_lat0 = 0, grid_lon0 = 0, grid_dlat = 0, grid_dlon = 0;
         if (stack) {
             if ((rc = tdoa_num_stacks(ctx, stack_m, &spb, &n_stacks))) return die("tdoa_num_stacks", rc);
             spk.resize((size_t)n_stacks * P * 2);
@@ -339,6 +355,30 @@ int main(int argc, char **argv)
                 clos.resize((size_t)n_stacks * std::max(tdoa_num_triples(ctx), 1));
                 if ((rc = tdoa_process_closure(ctx, stack_m, closure_g, closure_sep, nullptr, clos.data())))
                     return die("tdoa_process_closure", rc);
+            }
+            if (locate) {
+                // the grid: SPAN_KM on a side around the stations' centroid, a degree of latitude taken as 111.32 km and a
+                // degree of longitude as 111.32 km cos(latitude of the centroid)
+                std::vector<double> lle(3 * (size_t)S);
+                double lat_c = 0, lon_c = 0, h_c = 0;
+                for (int s = 0; s < S; s++) {
+                    lat_c += (lle[3 * s] = caps[s].st.lat) / S;
+                    lon_c += (lle[3 * s + 1] = caps[s].st.lon) / S;
+                    h_c += (lle[3 * s + 2] = caps[s].st.elev) / S;
+                }
+                const double pi = 3.14159265358979323846, span_lat = locate_km / 111.32, span_lon = locate_km / (111.32 * std::cos(lat_c * pi / 180));
+                grid_dlat = locate_rows > 1 ? span_lat / (locate_rows - 1) : 0.0;
+                grid_dlon = locate_cols > 1 ? span_lon / (locate_cols - 1) : 0.0;
+                grid_lat0 = lat_c - grid_dlat * (locate_rows - 1) / 2;
+                grid_lon0 = lon_c - grid_dlon * (locate_cols - 1) / 2;
+                std::vector<int32_t> table((size_t)locate_rows * locate_cols * S);
+                if ((rc = tdoa_locate_grid_table(lle.data(), S, grid_lat0, grid_lon0, grid_dlat, grid_dlon, locate_rows, locate_cols, h_c,
+                                                 prm.sample_rate, table.data())))
+                    return die("tdoa_locate_grid_table", rc);
+                if ((rc = tdoa_locate_set_table(ctx, table.data(), locate_rows * locate_cols, locate_cols, S)))
+                    return die("tdoa_locate_set_table", rc);
+                locs.resize((size_t)n_stacks);
+                if ((rc = tdoa_process_locate(ctx, stack_m, 1, locs.data(), nullptr, nullptr, nullptr))) return die("tdoa_process_locate", rc);
             }
         }
         std::printf("\n=== FM-DISCRIMINATOR CROSS-CORRELATION: %d windows x %d pairs ===\n", W, P);
@@ -419,6 +459,13 @@ int main(int argc, char **argv)
                                     (int)c.lag_ij, (int)c.lag_ik, (int)c.lag_jk, (int)c.residual, c.score,
                                     (double)c.own_q / 4294967296.0 / root, c.runner_up);
                     }
+        }
+        // --locate: the best cell of the grid, a line per stack
+        for (size_t sid = 0; sid < locs.size(); sid++) {
+            const tdoa_location &l = locs[sid];
+            std::printf("LOCATE block %d stack %d: cell=%d lat=%.6f lon=%.6f pairs=%d score=%.6f runner=%.6f\n", (int)sid / spb + 1,
+                        (int)sid % spb, (int)l.cell, grid_lat0 + (l.cell / locate_cols) * grid_dlat, grid_lon0 + (l.cell % locate_cols) * grid_dlon,
+                        (int)l.pairs_in, l.score, l.runner_up);
         }
     }
 

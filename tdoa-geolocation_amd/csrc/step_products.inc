@@ -2,7 +2,7 @@
 // (tdoa_process_lags), the K strongest peaks per pair-window (tdoa_process_peaks), the stacked surfaces of a block's windows
 // (tdoa_process_stacked), the same stacks taken along the best of 2H+1 lag slopes (tdoa_process_stacked_drift), the best
 // delay track through a stack's windows (tdoa_process_track), one consistent lag set per station triple of a stack
-// (tdoa_process_closure).  Every product is four functions next to each other, called by process_impl in this order:
+// (tdoa_process_closure), a table of candidate positions scored on all pairs' stacks (tdoa_process_locate).  Every product is four functions next to each other, called by process_impl in this order:
 //   reserve_*   its buffers, after the step's grouping is fixed (batch_bound counts them as held, so a later call groups as
 //               this one did); no allocation may happen once the step is being captured
 //   key_*       the words it appends to the step graph's key: everything its launches depend on
@@ -83,15 +83,26 @@ struct ClosureProduct {
     tdoa_closure *out_host = nullptr;        // [stack][triple]
 };
 
+struct LocateProduct {
+    StackProduct stack;                      // the stack whose sums Q are searched: no output of its own, so no finishing kernels
+    int sep = 1;                             // min_separation
+    int n_cells = 0, n_cols = 0;             // the shape of the context's table: in the key (the table itself is data)
+    tdoa_location *loc_host = nullptr;       // [stack]
+    int32_t *lags_host = nullptr;            // [stack][pair]
+    double *corr_host = nullptr;             // [stack][pair]
+    int64_t *map_host = nullptr;             // [stack][cell]
+};
+
 // the product of one step; the numbers are the first word a product appends to the graph key
 struct StepProduct {
-    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6 } kind = None;
+    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6, Locate = 7 } kind = None;
     LagsProduct lags;
     PeaksProduct peaks;
     StackProduct stack;
     StackDriftProduct drift;
     StackTrackProduct track;
     ClosureProduct closure;
+    LocateProduct locate;
 };
 
 // ctx->surf for the rank's pair-windows; `copies`: float surfaces of the step the product holds in all (the message's size)
@@ -413,6 +424,28 @@ int download_closure_product(const StepView &v, const ClosureProduct &p)
     return download_closure(v.ctx, p.stack.layout.n_stacks, closure_geom((int)p.centre.size(), v.ctx->prm.max_lag, p.G, p.sep), p.out_host);
 }
 
+// ---- the delay-table search on the stacks' sums (stack_locate.hpp, locate_api.inc) -------------------------------------
+int reserve_locate(const StepView &v, LocateProduct &p)
+{
+    if (int rc = reserve_stack(v, p.stack)) return rc;
+    return ensure_locate(v.ctx, p.stack.layout.n_stacks, locate_geom(v.ctx, p.sep));
+}
+void key_locate(const LocateProduct &p, std::vector<uint64_t> *key)
+{
+    key->insert(key->end(), {StepProduct::Locate, (uint64_t)p.stack.m, (uint64_t)p.sep, (uint64_t)p.n_cells | ((uint64_t)p.n_cols << 32)});
+}
+void enqueue_locate(const StepView &v, const LocateProduct &p)
+{
+    tdoa_ctx *ctx = v.ctx;
+    enqueue_stack(v, p.stack);
+    const int n_stacks = p.stack.layout.n_stacks;
+    launch_locate(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, n_stacks, v.P).roots, n_stacks, locate_geom(ctx, p.sep));
+}
+int download_locate_product(const StepView &v, const LocateProduct &p)
+{
+    return download_locate(v.ctx, p.stack.layout.n_stacks, locate_geom(v.ctx, p.sep), p.loc_host, p.lags_host, p.corr_host, p.map_host);
+}
+
 // ---- process_impl's one dispatch per stage ---------------------------------------------------------------------------
 int reserve_product(const StepView &v, StepProduct &p)
 {
@@ -423,6 +456,7 @@ int reserve_product(const StepView &v, StepProduct &p)
     case StepProduct::StackDrift: return reserve_stack_drift(v, p.drift);
     case StepProduct::StackTrack: return reserve_stack_track(v, p.track);
     case StepProduct::Closure: return reserve_closure(v, p.closure);
+    case StepProduct::Locate: return reserve_locate(v, p.locate);
     default: return TDOA_OK;
     }
 }
@@ -435,6 +469,7 @@ void key_product(const StepProduct &p, std::vector<uint64_t> *key)
     case StepProduct::StackDrift: return key_stack_drift(p.drift, key);
     case StepProduct::StackTrack: return key_stack_track(p.track, key);
     case StepProduct::Closure: return key_closure(p.closure, key);
+    case StepProduct::Locate: return key_locate(p.locate, key);
     default: key->insert(key->end(), {StepProduct::None, 0, 0, 0});
     }
 }
@@ -445,6 +480,7 @@ int upload_product(const StepView &v, StepProduct &p)
     case StepProduct::StackDrift: return upload_stack_drift(v, p.drift);
     case StepProduct::StackTrack: return upload_stack_track(v, p.track);
     case StepProduct::Closure: return upload_stack(v, p.closure.stack);
+    case StepProduct::Locate: return upload_stack(v, p.locate.stack);
     default: return TDOA_OK;
     }
 }
@@ -463,6 +499,7 @@ void enqueue_product(const StepView &v, const StepProduct &p)
     case StepProduct::StackDrift: return enqueue_stack_drift(v, p.drift);
     case StepProduct::StackTrack: return enqueue_stack_track(v, p.track);
     case StepProduct::Closure: return enqueue_closure(v, p.closure);
+    case StepProduct::Locate: return enqueue_locate(v, p.locate);
     default: return;
     }
 }
@@ -475,6 +512,7 @@ int download_product(const StepView &v, const StepProduct &p)
     case StepProduct::StackDrift: return download_stack_drift(v, p.drift);
     case StepProduct::StackTrack: return download_stack_track(v, p.track);
     case StepProduct::Closure: return download_closure_product(v, p.closure);
+    case StepProduct::Locate: return download_locate_product(v, p.locate);
     default: return TDOA_OK;
     }
 }

@@ -39,6 +39,7 @@
 #include "stack_drift.hpp"
 #include "stack_track.hpp"
 #include "stack_closure.hpp"
+#include "stack_locate.hpp"
 
 using namespace tdoa;
 
@@ -162,6 +163,11 @@ struct tdoa_ctx {
     // the closure search: the stations' centres, the tiles' candidates [stack][triple][tile], (u*, v*) and the records
     // [stack][triple]; tdoa_debug_closure_from_q's own words and sqrt(n_w)
     DevBuf closure_centre, closure_part, closure_best, closure_out, closure_q, closure_roots;
+    // the delay-table search: the table [station][cell] (state: tdoa_locate_set_table; 0 cells: none), the map [stack][cell],
+    // the tiles' candidates [stack][tile], the locations' cells and records [stack], the best cells' lags and correlations
+    // [stack][pair]; tdoa_debug_locate_from_q's own words and sqrt(n_w)
+    DevBuf locate_table, locate_map, locate_part, locate_best, locate_out, locate_lags, locate_corr, locate_q, locate_roots;
+    int locate_cells = 0, locate_cols = 0, locate_stations = 0;
 };
 
 namespace {
@@ -169,6 +175,8 @@ namespace {
 static_assert(sizeof(PeakOut) == sizeof(tdoa_peak), "tdoa_peak layout");
 static_assert(sizeof(FmStats) == sizeof(tdoa_fm_stats), "tdoa_fm_stats layout");
 static_assert(sizeof(ClosureOut) == sizeof(tdoa_closure) && sizeof(tdoa_closure) == 80, "tdoa_closure layout");
+static_assert(sizeof(LocateOut) == sizeof(tdoa_location) && sizeof(tdoa_location) == 48, "tdoa_location layout");
+static_assert(kLocateDelayUnit == TDOA_DELAY_UNIT, "the table's unit");
 
 int fail(tdoa_ctx *ctx, int status, const char *what, hipError_t e = hipSuccess)
 {
@@ -351,6 +359,7 @@ int check_selection(tdoa_ctx *ctx, int k, int min_separation, const void *out)
 #include "step_graph.inc"
 #include "stacked_api.inc"
 #include "closure_api.inc"
+#include "locate_api.inc"
 #include "step_products.inc"
 
 // ===========================================================================
@@ -507,7 +516,9 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->sel_peaks, &ctx->sel_count, &ctx->stack_q, &ctx->stack_surf, &ctx->stack_keys, &ctx->stack_fine,
                       &ctx->stack_desc, &ctx->drift_tab, &ctx->drift_keys, &ctx->drift_h, &ctx->drift_prof, &ctx->track_tab,
                       &ctx->track_t, &ctx->track_d, &ctx->track_score, &ctx->track_lags, &ctx->track_values, &ctx->closure_centre,
-                      &ctx->closure_part, &ctx->closure_best, &ctx->closure_out, &ctx->closure_q, &ctx->closure_roots};
+                      &ctx->closure_part, &ctx->closure_best, &ctx->closure_out, &ctx->closure_q, &ctx->closure_roots, &ctx->locate_table,
+                      &ctx->locate_map, &ctx->locate_part, &ctx->locate_best, &ctx->locate_out, &ctx->locate_lags, &ctx->locate_corr,
+                      &ctx->locate_q, &ctx->locate_roots};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1084,6 +1095,30 @@ int tdoa_process_closure(tdoa_ctx *ctx, int windows_per_stack, int gate, int min
     cp.sep = min_separation;
     cp.centre = closure_centres(centre, S);
     cp.out_host = closure_host;
+    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, std::move(prod));
+}
+
+int tdoa_process_locate(tdoa_ctx *ctx, int windows_per_stack, int min_separation, tdoa_location *loc_host, int32_t *lags_host,
+                        double *corr_host, int64_t *map_host)
+{
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (windows_per_stack < 0) return fail(ctx, TDOA_ERR_INVALID, "windows_per_stack < 0");
+    if (const char *bad = check_locate_args(min_separation, loc_host)) return fail(ctx, TDOA_ERR_INVALID, bad);
+    const char *what = nullptr;
+    if (const int rc = check_locate_state(ctx, windows_per_stack, &what)) return fail(ctx, rc, what);
+    StepProduct prod;
+    prod.kind = StepProduct::Locate;
+    LocateProduct &lp = prod.locate;
+    lp.stack.m = windows_per_stack;
+    lp.stack.k = 1;
+    lp.stack.min_sep = 1;
+    lp.sep = min_separation;
+    lp.n_cells = ctx->locate_cells;
+    lp.n_cols = ctx->locate_cols;
+    lp.loc_host = loc_host;
+    lp.lags_host = lags_host;
+    lp.corr_host = corr_host;
+    lp.map_host = map_host;
     return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, std::move(prod));
 }
 

@@ -49,6 +49,9 @@ CLOSURE_DTYPE = np.dtype([("lag_ij", np.int32), ("lag_ik", np.int32), ("lag_jk",
                           ("score_q", np.int64), ("own_q", np.int64), ("runner_q", np.int64),
                           ("corr_ij", np.float64), ("corr_ik", np.float64), ("corr_jk", np.float64),
                           ("score", np.float64), ("runner_up", np.float64)])      # tdoa_closure
+LOCATION_DTYPE = np.dtype([("cell", np.int32), ("runner_cell", np.int32), ("pairs_in", np.int32), ("reserved", np.int32),
+                           ("score_q", np.int64), ("runner_q", np.int64),
+                           ("score", np.float64), ("runner_up", np.float64)])      # tdoa_location
 FINE_DTYPE = np.dtype([("delay", np.float64), ("frac", np.float32), ("y", np.float32, (3,)), ("plausible", np.int32),
                        ("reserved", np.int32)])
 
@@ -100,6 +103,8 @@ SYMBOLS = [
     "tdoa_num_stacks", "tdoa_process_stacked", "tdoa_group_process_stacked", "tdoa_process_stacked_drift",
     "tdoa_process_track",
     "tdoa_num_triples", "tdoa_process_closure", "tdoa_group_process_closure", "tdoa_debug_closure_from_q",
+    "tdoa_locate_set_table", "tdoa_process_locate", "tdoa_debug_locate_from_q", "tdoa_locate_grid_table",
+    "tdoa_group_locate_set_table", "tdoa_group_process_locate",
 ]
 
 _lib = None
@@ -213,6 +218,14 @@ def load(build_if_missing=True):
     L.tdoa_process_closure.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, vp]
     L.tdoa_group_process_closure.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, vp]
     L.tdoa_debug_closure_from_q.argtypes = [vp, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, vp]
+    i64p = C.POINTER(C.c_int64)
+    L.tdoa_locate_set_table.argtypes = [vp, i32p, C.c_int, C.c_int, C.c_int]
+    L.tdoa_group_locate_set_table.argtypes = [vp, i32p, C.c_int, C.c_int, C.c_int]
+    L.tdoa_process_locate.argtypes = [vp, C.c_int, C.c_int, vp, i32p, dp, i64p]
+    L.tdoa_group_process_locate.argtypes = [vp, C.c_int, C.c_int, vp, i32p, dp, i64p]
+    L.tdoa_debug_locate_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p, dp, i64p]
+    L.tdoa_locate_grid_table.argtypes = [dp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
+                                         C.c_double, C.c_double, i32p]
     L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
                                         C.POINTER(C.c_int)]
     _lib = L
@@ -601,6 +614,36 @@ class Context:
                                                     out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def locate_set_table(self, table, n_cols=None):
+        """tdoa_locate_set_table: table [n_cells][n_stations] int32 delays in units of 1/16 sample; n_cols gives cells their
+        rows and columns (None: a plain list).  table None: forget it.  Kept on the device until replaced"""
+        ptr, n_cells, n_cols, S = _table(table, n_cols)
+        self._chk(self._L.tdoa_locate_set_table(self._h, ptr, n_cells, n_cols, S))
+        self._locate_cells = n_cells
+
+    def process_locate(self, windows_per_stack=0, min_separation=1, want_map=False):
+        """tdoa_process_locate -> {"loc": [n_stacks] LOCATION_DTYPE, "lags": [n_stacks][P] int32, "corr": [n_stacks][P]
+        float64, and with want_map "map": [n_stacks][n_cells] int64}: per stack the table's cell with the largest summed
+        magnitude of all pairs' stacks at the cell's lags, the runner-up, and the lags and signed correlations there"""
+        _, n = self.num_stacks(windows_per_stack)
+        out = _locate_outputs(n, self.num_pairs(), getattr(self, "_locate_cells", 0), want_map)
+        self._chk(self._L.tdoa_process_locate(self._h, int(windows_per_stack), int(min_separation), *_locate_ptrs(out)))
+        return out
+
+    def locate_from_q(self, q, n_stations, n_w=1, min_separation=1, want_map=True):
+        """tdoa_debug_locate_from_q: the search's kernels on the caller's words q [n_sets][P][2 max_lag - 1] int64 (or one
+        set [P][2 max_lag - 1]) with the context's table -> what process_locate returns, n_sets for n_stacks"""
+        q = np.ascontiguousarray(q, dtype=np.int64)
+        if q.ndim == 2:
+            q = q[None]
+        S = int(n_stations)
+        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
+            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
+        out = _locate_outputs(q.shape[0], q.shape[1], getattr(self, "_locate_cells", 0), want_map)
+        self._chk(self._L.tdoa_debug_locate_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], S, int(n_w),
+                                                   int(min_separation), *_locate_ptrs(out)))
+        return out
+
     def fm_xcorr_peaks(self, iq1, iq2, max_lag, k, min_separation):
         """tdoa_fm_xcorr_peaks_u8 -> (peaks [k] PEAK_DTYPE, count) of one pair of windows"""
         a = np.ascontiguousarray(iq1, dtype=np.uint8)
@@ -725,6 +768,29 @@ def _centre(centre, n_stations):
     return c.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def _table(table, n_cols):
+    """(pointer, n_cells, n_cols, n_stations) of a delay table as the C ABI takes it; None: (NULL, 0, 1, 0)"""
+    if table is None:
+        return None, 0, 1, 0
+    t = np.ascontiguousarray(table, dtype=np.int32)
+    if t.ndim != 2:
+        raise ValueError("table must be [n_cells][n_stations]")
+    return t.ctypes.data_as(C.POINTER(C.c_int32)), t.shape[0], int(t.shape[0] if n_cols is None else n_cols), t.shape[1]
+
+
+def _locate_outputs(n_sets, p, n_cells, want_map):
+    out = {"loc": np.zeros(n_sets, dtype=LOCATION_DTYPE), "lags": np.zeros((n_sets, p), dtype=np.int32),
+           "corr": np.zeros((n_sets, p), dtype=np.float64)}
+    if want_map:
+        out["map"] = np.zeros((n_sets, n_cells), dtype=np.int64)
+    return out
+
+
+def _locate_ptrs(out):
+    return (out["loc"].ctypes.data_as(C.c_void_p), out["lags"].ctypes.data_as(C.POINTER(C.c_int32)), _d(out["corr"]),
+            out["map"].ctypes.data_as(C.POINTER(C.c_int64)) if "map" in out else None)
+
+
 def _stacked_outputs(n_stacks, p, n_lags, k, want_surface, want_partial):
     out = {"peaks": np.zeros((n_stacks, p, max(int(k), 1)), dtype=PEAK_DTYPE), "count": np.zeros((n_stacks, p), dtype=np.int32),
            "fine": np.zeros((n_stacks, p), dtype=FINE_DTYPE)}
@@ -837,6 +903,34 @@ class Group:
         self._chk(self._L.tdoa_group_process_closure(self._h, int(windows_per_stack), int(gate), int(min_separation),
                                                      _centre(centre, m.num_stations()), out.ctypes.data_as(C.c_void_p)))
         return out
+
+
+    def locate_set_table(self, table, n_cols=None):
+        """tdoa_group_locate_set_table: the table to every member"""
+        ptr, n_cells, n_cols, S = _table(table, n_cols)
+        self._chk(self._L.tdoa_group_locate_set_table(self._h, ptr, n_cells, n_cols, S))
+        self._locate_cells = n_cells
+
+    def process_locate(self, windows_per_stack=0, min_separation=1, want_map=False):
+        """tdoa_group_process_locate -> Context.process_locate's outputs, byte-identical to a single context's"""
+        m = self.member(0)
+        _, n = m.num_stacks(windows_per_stack)
+        out = _locate_outputs(n, m.num_pairs(), getattr(self, "_locate_cells", 0), want_map)
+        self._chk(self._L.tdoa_group_process_locate(self._h, int(windows_per_stack), int(min_separation), *_locate_ptrs(out)))
+        return out
+
+
+def locate_grid_table(stations_lle, lat0, lon0, dlat, dlon, rows, cols, height_m, sample_rate):
+    """tdoa_locate_grid_table (host only): the delay table [rows cols][n_stations] int32 of a latitude / longitude grid"""
+    st = np.ascontiguousarray(stations_lle, dtype=np.float64).reshape(-1, 3)
+    rows, cols = int(rows), int(cols)
+    n_cells = rows * cols if rows >= 1 and cols >= 1 and rows * cols <= 2 ** 22 else 1      # (the library refuses the rest)
+    out = np.zeros((n_cells, st.shape[0]), dtype=np.int32)
+    rc = load().tdoa_locate_grid_table(_d(st.reshape(-1)), st.shape[0], float(lat0), float(lon0), float(dlat), float(dlon), rows,
+                                       cols, float(height_m), float(sample_rate), out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != OK:
+        raise TdoaError(rc, "tdoa_locate_grid_table")
+    return out
 
 
 def latlon_to_ecef(lat, lon, elev):
