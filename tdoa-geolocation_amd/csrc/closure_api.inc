@@ -85,31 +85,23 @@ int tdoa_num_triples(const tdoa_ctx *ctx)
     return S >= 3 && S <= kClosureMaxStations ? closure_triples(S) : 0;
 }
 
-// The group's search on one context: the members' summed Q uploaded, then the kernels a context's own call ends with.
-// Not part of a step graph (the context's cached step stays valid unless a buffer had to grow).
+// the closure search on a group's merged sum (finish_from_host, stacked_api.inc)
 static int closure_from_host(tdoa_ctx *ctx, const int64_t *q_sum, int windows_per_stack, int gate, int min_separation,
                              const int32_t *centre, tdoa_closure *out)
 {
-    int rc, wpb = 0;
-    if ((rc = check_ctx(ctx))) return rc;
-    if ((rc = tdoa_num_windows(ctx, &wpb, nullptr))) return fail(ctx, rc, "captures missing or too small");
-    const int S = (int)ctx->caps.size(), P = tdoa_num_pairs(ctx);
+    const int S = (int)ctx->caps.size();
     const ClosureGeom g = closure_geom(S, ctx->prm.max_lag, gate, min_separation);
-    const StackLayout sl = build_stack_layout({}, wpb, P, windows_per_stack);
-    const size_t n_sp = (size_t)sl.n_stacks * P;
-    if ((rc = ensure(ctx, ctx->stack_q, sizeof(long long) * n_sp * g.n))) return rc;
-    if ((rc = ensure(ctx, ctx->stack_desc, stack_desc_bytes(sl.n_stacks, P, 0)))) return rc;   // (a member's step made it larger)
-    if ((rc = ensure_closure(ctx, sl.n_stacks, g))) return rc;
-    std::vector<double> ones;
     const std::vector<int32_t> c = closure_centres(centre, S);
-    if ((rc = upload_stack_desc(ctx, sl, P, &ones, false))) return rc;
-    if ((rc = upload_closure_centre(ctx, c))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->stack_q.p, q_sum, sizeof(int64_t) * n_sp * g.n, hipMemcpyHostToDevice, ctx->stream));
-    launch_closure(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, sl.n_stacks, P).roots, sl.n_stacks, g);
-    HIPCHK(ctx, hipGetLastError());
-    if ((rc = download_closure(ctx, sl.n_stacks, g, out))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDOA_OK;
+    return finish_from_host(
+        ctx, q_sum, windows_per_stack,
+        [&](int n_stacks, const double *roots) -> int {
+            int rc;
+            if ((rc = ensure_closure(ctx, n_stacks, g))) return rc;
+            if ((rc = upload_closure_centre(ctx, c))) return rc;
+            launch_closure(ctx, ctx->stack_q.as<const long long>(), roots, n_stacks, g);
+            return TDOA_OK;
+        },
+        [&](int n_stacks) { return download_closure(ctx, n_stacks, g, out); });
 }
 
 }  // extern "C"

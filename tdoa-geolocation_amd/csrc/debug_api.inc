@@ -227,9 +227,24 @@ int tdoa_debug_select_peaks(tdoa_ctx *ctx, const float *surface, int n_lags, int
     return TDOA_OK;
 }
 
+// The caller's words and sqrt(n_w) for each of n_sets sets, for the two entries below, in buffers that are theirs alone
+// (ctx->debug_q, ctx->debug_roots): the stack's sums and a cached step graph's buffers stay as they are.  (A call that has to
+// allocate or grow one of its buffers moves alloc_gen like every ensure(): the next step captures its graph again, with the
+// same results.)  *roots lives until the caller has synchronised.
+static int upload_debug_q(tdoa_ctx *ctx, const int64_t *q, size_t n_q, int n_sets, int n_w, std::vector<double> *roots)
+{
+    int rc;
+    if ((rc = check_ctx(ctx))) return rc;
+    if ((rc = ensure(ctx, ctx->debug_q, sizeof(long long) * n_q))) return rc;
+    if ((rc = ensure(ctx, ctx->debug_roots, sizeof(double) * n_sets))) return rc;
+    roots->assign((size_t)n_sets, std::sqrt((double)n_w));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->debug_q.p, q, sizeof(long long) * n_q, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->debug_roots.p, roots->data(), sizeof(double) * n_sets, hipMemcpyHostToDevice, ctx->stream));
+    return TDOA_OK;
+}
+
 // the closure search's kernels (closure_api.inc) on the caller's words: n_sets sets of P = S (S-1) / 2 rows of 2 max_lag - 1
-// int64, every set a stack of n_w windows.  Needs the context for max_lag and the device only; its buffers are its own, so a
-// cached step graph and the stack's sums stay as they are.
+// int64, every set a stack of n_w windows.  Needs the context for max_lag and the device only.
 int tdoa_debug_closure_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int gate, int min_separation,
                               const int32_t *centre, tdoa_closure *out)
 {
@@ -240,29 +255,18 @@ int tdoa_debug_closure_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n
         return fail(ctx, TDOA_ERR_INVALID, "q is NULL, n_sets < 1, n_w < 1 or n_stations outside 3 .. 64");
     const ClosureGeom g = closure_geom(n_stations, ctx->prm.max_lag, gate, min_separation);
     if ((long long)n_sets * g.T > INT_MAX / 4) return fail(ctx, TDOA_ERR_INVALID, "too many sets");
-    if ((rc = check_ctx(ctx))) return rc;
-    const size_t n_q = (size_t)n_sets * g.P * g.n;
-    if ((rc = ensure(ctx, ctx->closure_q, sizeof(long long) * n_q))) return rc;
-    if ((rc = ensure(ctx, ctx->closure_roots, sizeof(double) * n_sets))) return rc;
-    if ((rc = ensure_closure(ctx, n_sets, g))) return rc;
-    const std::vector<double> roots((size_t)n_sets, std::sqrt((double)n_w));
+    std::vector<double> roots;
     const std::vector<int32_t> c = closure_centres(centre, n_stations);
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->closure_q.p, q, sizeof(long long) * n_q, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->closure_roots.p, roots.data(), sizeof(double) * n_sets, hipMemcpyHostToDevice, st));
+    if ((rc = upload_debug_q(ctx, q, (size_t)n_sets * g.P * g.n, n_sets, n_w, &roots))) return rc;
+    if ((rc = ensure_closure(ctx, n_sets, g))) return rc;
     if ((rc = upload_closure_centre(ctx, c))) return rc;
-    launch_closure(ctx, ctx->closure_q.as<const long long>(), ctx->closure_roots.as<const double>(), n_sets, g);
-    HIPCHK(ctx, hipGetLastError());
-    if ((rc = download_closure(ctx, n_sets, g, out))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(st));       // the host vectors go out of scope
-    return TDOA_OK;
+    launch_closure(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), n_sets, g);
+    return download_and_wait(ctx, [&] { return download_closure(ctx, n_sets, g, out); });
 }
 
 // the delay-table search's kernels (locate_api.inc) on the caller's words: n_sets sets of P = S (S-1) / 2 rows of 2 max_lag - 1
 // int64, every set a stack of n_w windows, against the context's table.  Needs the context for max_lag, the table and the
-// device only; its words are its own, so the stack's sums stay as they are.  (A call that has to allocate or grow one of its
-// buffers moves alloc_gen like every ensure(): the next step captures its graph again, with the same results -- the closure
-// entry above behaves the same way.)
+// device only.
 int tdoa_debug_locate_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int min_separation,
                              tdoa_location *loc, int32_t *lags, double *corr, int64_t *map)
 {
@@ -274,20 +278,11 @@ int tdoa_debug_locate_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_
     if (const char *bad = check_locate_table(ctx, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
     const LocateGeom g = locate_geom(ctx, min_separation);
     if (locate_overflows(g.P, n_w)) return fail(ctx, TDOA_ERR_UNSUPPORTED, "pairs x n_w > 2^17: a cell's score could overflow");
-    if ((rc = check_ctx(ctx))) return rc;
-    const size_t n_q = (size_t)n_sets * g.P * g.n;
-    if ((rc = ensure(ctx, ctx->locate_q, sizeof(long long) * n_q))) return rc;
-    if ((rc = ensure(ctx, ctx->locate_roots, sizeof(double) * n_sets))) return rc;
+    std::vector<double> roots;
+    if ((rc = upload_debug_q(ctx, q, (size_t)n_sets * g.P * g.n, n_sets, n_w, &roots))) return rc;
     if ((rc = ensure_locate(ctx, n_sets, g))) return rc;
-    const std::vector<double> roots((size_t)n_sets, std::sqrt((double)n_w));
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->locate_q.p, q, sizeof(long long) * n_q, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->locate_roots.p, roots.data(), sizeof(double) * n_sets, hipMemcpyHostToDevice, st));
-    launch_locate(ctx, ctx->locate_q.as<const long long>(), ctx->locate_roots.as<const double>(), n_sets, g);
-    HIPCHK(ctx, hipGetLastError());
-    if ((rc = download_locate(ctx, n_sets, g, loc, lags, corr, map))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(st));       // the host vector goes out of scope
-    return TDOA_OK;
+    launch_locate(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), n_sets, g);
+    return download_and_wait(ctx, [&] { return download_locate(ctx, n_sets, g, loc, lags, corr, map); });
 }
 
 #ifdef TDOA_STG_TIMING

@@ -115,6 +115,40 @@ bool group_same_captures(const tdoa_group *g, int *who)
     return true;
 }
 
+// What the stacked group calls share once their own checks are through: the members' shares of the stacks' fixed-point sums
+// (each member's tdoa_process_stacked returns only its partial Q; k = min_separation = 1 and gate 0 reach nothing but its
+// step graph's key, so the three calls replay one graph per windows_per_stack), added on the host into member 0's (integer
+// addition: any order gives the same words).  *merged stays valid until the group's next call.
+int group_merged_q(tdoa_group *g, int windows_per_stack, const int64_t **merged)
+{
+    const int world = (int)g->members.size();
+    tdoa_ctx *c0 = g->members[0];
+    if (int who = 0; !group_same_captures(g, &who))
+        return group_fail(g, TDOA_ERR_STATE, member_name(who, g->members[who]->device) +
+                                                 "station count or capture lengths differ from member 0's");
+    int n_stacks = 0;
+    if (tdoa_num_stacks(c0, windows_per_stack, nullptr, &n_stacks) != TDOA_OK)
+        return group_fail(g, TDOA_ERR_STATE, member_name(0, c0->device) + "captures missing or too small");
+    const size_t n_q = (size_t)n_stacks * tdoa_num_pairs(c0) * (size_t)(2 * c0->prm.max_lag - 1);
+    g->partial.resize(world);
+    for (auto &q : g->partial) q.resize(n_q);
+    std::vector<int> status(world, TDOA_OK);
+    const bool ran = run_members(world, [&](int m) {
+        status[m] = tdoa_process_stacked(g->members[m], m, world, windows_per_stack, 1, 1, 0.0, nullptr, nullptr, nullptr, nullptr,
+                                         g->partial[m].data());
+    });
+    if (!ran) return group_fail(g, TDOA_ERR_NOMEM, "could not start a member thread");
+    for (int m = 0; m < world; m++)
+        if (status[m] != TDOA_OK) return member_fail(g, m, status[m]);
+    std::vector<int64_t> &sum = g->partial[0];
+    for (int m = 1; m < world; m++) {
+        const int64_t *q = g->partial[m].data();
+        for (size_t i = 0; i < n_q; i++) sum[i] += q[i];
+    }
+    *merged = sum.data();
+    return TDOA_OK;
+}
+
 // one member's share of the group's file ingest: its previous captures dropped, then every file's owned runs
 int group_member_upload(tdoa_ctx *ctx, int rank, int world, const std::vector<int> &fds, const std::vector<size_t> &n_samples,
                         size_t n_min)
@@ -255,8 +289,8 @@ int tdoa_group_process(tdoa_group *g, tdoa_peak *out_host)
     return TDOA_OK;
 }
 
-// tdoa_process_stacked over the members: each returns only its share of the fixed-point sums; the host adds them (integer
-// addition: any order gives the same words) and member 0 finishes the sum with the kernels a single context's call ends with.
+// tdoa_process_stacked over the members: the host adds their shares of the fixed-point sums (group_merged_q) and member 0
+// finishes the sum with the kernels a single context's call ends with.
 int tdoa_group_process_stacked(tdoa_group *g, int windows_per_stack, int k, int min_separation, double gate_samples,
                                tdoa_peak *peaks_host, int32_t *count_host, tdoa_fine_peak *fine_host, float *surface_host)
 {
@@ -272,29 +306,9 @@ int tdoa_group_process_stacked(tdoa_group *g, int windows_per_stack, int k, int 
         return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
     }
     if (c0->prm.lag_mode == TDOA_LAGS_GO) return group_fail(g, TDOA_ERR_UNSUPPORTED, "stacked correlation with TDOA_LAGS_GO");
-    if (int who = 0; !group_same_captures(g, &who))
-        return group_fail(g, TDOA_ERR_STATE, member_name(who, g->members[who]->device) +
-                                                 "station count or capture lengths differ from member 0's");
-    int n_stacks = 0;
-    if (tdoa_num_stacks(c0, windows_per_stack, nullptr, &n_stacks) != TDOA_OK)
-        return group_fail(g, TDOA_ERR_STATE, member_name(0, c0->device) + "captures missing or too small");
-    const size_t n_q = (size_t)n_stacks * tdoa_num_pairs(c0) * (size_t)(2 * c0->prm.max_lag - 1);
-    g->partial.resize(world);
-    for (auto &q : g->partial) q.resize(n_q);
-    std::vector<int> status(world, TDOA_OK);
-    const bool ran = run_members(world, [&](int m) {
-        status[m] = tdoa_process_stacked(g->members[m], m, world, windows_per_stack, k, min_separation, gate_samples, nullptr,
-                                         nullptr, nullptr, nullptr, g->partial[m].data());
-    });
-    if (!ran) return group_fail(g, TDOA_ERR_NOMEM, "could not start a member thread");
-    for (int m = 0; m < world; m++)
-        if (status[m] != TDOA_OK) return member_fail(g, m, status[m]);
-    std::vector<int64_t> &sum = g->partial[0];
-    for (int m = 1; m < world; m++) {
-        const int64_t *q = g->partial[m].data();
-        for (size_t i = 0; i < n_q; i++) sum[i] += q[i];
-    }
-    const int rc = stack_finish_from_host(c0, sum.data(), windows_per_stack, k, min_separation, gate_samples, peaks_host,
+    const int64_t *sum = nullptr;
+    if (const int rc = group_merged_q(g, windows_per_stack, &sum)) return rc;
+    const int rc = stack_finish_from_host(c0, sum, windows_per_stack, k, min_separation, gate_samples, peaks_host,
                                           count_host, fine_host, surface_host);
     return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
 }
@@ -317,29 +331,9 @@ int tdoa_group_process_closure(tdoa_group *g, int windows_per_stack, int gate, i
     if (c0->caps.empty()) return group_fail(g, TDOA_ERR_STATE, member_name(0, c0->device) + "captures missing");
     if (c0->caps.size() < 3 || c0->caps.size() > (size_t)kClosureMaxStations)
         return group_fail(g, TDOA_ERR_UNSUPPORTED, "the closure search needs 3 .. 64 stations");
-    if (int who = 0; !group_same_captures(g, &who))
-        return group_fail(g, TDOA_ERR_STATE, member_name(who, g->members[who]->device) +
-                                                 "station count or capture lengths differ from member 0's");
-    int n_stacks = 0;
-    if (tdoa_num_stacks(c0, windows_per_stack, nullptr, &n_stacks) != TDOA_OK)
-        return group_fail(g, TDOA_ERR_STATE, member_name(0, c0->device) + "captures missing or too small");
-    const size_t n_q = (size_t)n_stacks * tdoa_num_pairs(c0) * (size_t)(2 * c0->prm.max_lag - 1);
-    g->partial.resize(world);
-    for (auto &q : g->partial) q.resize(n_q);
-    std::vector<int> status(world, TDOA_OK);
-    const bool ran = run_members(world, [&](int m) {
-        status[m] = tdoa_process_stacked(g->members[m], m, world, windows_per_stack, 1, 1, 0.0, nullptr, nullptr, nullptr, nullptr,
-                                         g->partial[m].data());
-    });
-    if (!ran) return group_fail(g, TDOA_ERR_NOMEM, "could not start a member thread");
-    for (int m = 0; m < world; m++)
-        if (status[m] != TDOA_OK) return member_fail(g, m, status[m]);
-    std::vector<int64_t> &sum = g->partial[0];
-    for (int m = 1; m < world; m++) {
-        const int64_t *q = g->partial[m].data();
-        for (size_t i = 0; i < n_q; i++) sum[i] += q[i];
-    }
-    const int rc = closure_from_host(c0, sum.data(), windows_per_stack, gate, min_separation, centre, closure_host);
+    const int64_t *sum = nullptr;
+    if (const int rc = group_merged_q(g, windows_per_stack, &sum)) return rc;
+    const int rc = closure_from_host(c0, sum, windows_per_stack, gate, min_separation, centre, closure_host);
     return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
 }
 
@@ -368,29 +362,9 @@ int tdoa_group_process_locate(tdoa_group *g, int windows_per_stack, int min_sepa
     }
     const char *what = nullptr;
     if (const int rc = check_locate_state(c0, windows_per_stack, &what)) return group_fail(g, rc, member_name(0, c0->device) + what);
-    if (int who = 0; !group_same_captures(g, &who))
-        return group_fail(g, TDOA_ERR_STATE, member_name(who, g->members[who]->device) +
-                                                 "station count or capture lengths differ from member 0's");
-    int n_stacks = 0;
-    if (tdoa_num_stacks(c0, windows_per_stack, nullptr, &n_stacks) != TDOA_OK)
-        return group_fail(g, TDOA_ERR_STATE, member_name(0, c0->device) + "captures missing or too small");
-    const size_t n_q = (size_t)n_stacks * tdoa_num_pairs(c0) * (size_t)(2 * c0->prm.max_lag - 1);
-    g->partial.resize(world);
-    for (auto &q : g->partial) q.resize(n_q);
-    std::vector<int> status(world, TDOA_OK);
-    const bool ran = run_members(world, [&](int m) {
-        status[m] = tdoa_process_stacked(g->members[m], m, world, windows_per_stack, 1, 1, 0.0, nullptr, nullptr, nullptr, nullptr,
-                                         g->partial[m].data());
-    });
-    if (!ran) return group_fail(g, TDOA_ERR_NOMEM, "could not start a member thread");
-    for (int m = 0; m < world; m++)
-        if (status[m] != TDOA_OK) return member_fail(g, m, status[m]);
-    std::vector<int64_t> &sum = g->partial[0];
-    for (int m = 1; m < world; m++) {
-        const int64_t *q = g->partial[m].data();
-        for (size_t i = 0; i < n_q; i++) sum[i] += q[i];
-    }
-    const int rc = locate_from_host(c0, sum.data(), windows_per_stack, min_separation, loc_host, lags_host, corr_host, map_host);
+    const int64_t *sum = nullptr;
+    if (const int rc = group_merged_q(g, windows_per_stack, &sum)) return rc;
+    const int rc = locate_from_host(c0, sum, windows_per_stack, min_separation, loc_host, lags_host, corr_host, map_host);
     return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
 }
 

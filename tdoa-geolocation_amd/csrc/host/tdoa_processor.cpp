@@ -97,6 +97,15 @@ void usage(const char *argv0)
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
 
+// the stacks tdoa_num_stacks counted for --stack=WINDOWS on blocks of wpb windows: the windows of a full stack and of stack
+// sid (the last stack of a block may be short)
+struct Stacks {
+    int wpb = 0, m = 0, spb = 0, n = 0;
+    Stacks() {}
+    Stacks(int wpb_, int stack_m, int spb_, int n_) : wpb(wpb_), m(stack_m > 0 && stack_m < wpb_ ? stack_m : wpb_), spb(spb_), n(n_) {}
+    int n_w(int sid) const { return std::min(m, wpb - (sid % spb) * m); }
+};
+
 double median(std::vector<double> v)
 {
     if (v.empty()) return 0;
@@ -323,6 +332,7 @@ int main(int argc, char **argv)
         } else if ((rc = tdoa_process(ctx, 0, 1, peaks.data(), nullptr))) return die("tdoa_process", rc);
         // --stack: the windows' surfaces of a block added lag by lag (tdoa_process_stacked), two peaks per stack-pair
         int spb = 0, n_stacks = 0;
+        Stacks stacks;
         std::vector<tdoa_peak> spk;
         std::vector<int32_t> scnt;
         std::vector<tdoa_fine_peak> sfine;
@@ -334,6 +344,7 @@ int main(int argc, char **argv)
         double grid_lat0 = 0, grid_lon0 = 0, grid_dlat = 0, grid_dlon = 0;
         if (stack) {
             if ((rc = tdoa_num_stacks(ctx, stack_m, &spb, &n_stacks))) return die("tdoa_num_stacks", rc);
+            stacks = Stacks(wpb, stack_m, spb, n_stacks);
             spk.resize((size_t)n_stacks * P * 2);
             scnt.resize((size_t)n_stacks * P);
             sfine.resize((size_t)n_stacks * P);
@@ -345,9 +356,8 @@ int main(int argc, char **argv)
             } else if ((rc = tdoa_process_stacked(ctx, 0, 1, stack_m, 2, 1, gate, spk.data(), scnt.data(), sfine.data(), nullptr, nullptr)))
                 return die("tdoa_process_stacked", rc);
             if (track) {
-                const int mm = stack_m > 0 && stack_m < wpb ? stack_m : wpb;
                 tscore.resize((size_t)n_stacks * P);
-                tlags.resize((size_t)n_stacks * P * mm);
+                tlags.resize((size_t)n_stacks * P * stacks.m);
                 if ((rc = tdoa_process_track(ctx, stack_m, track_j, tscore.data(), tlags.data(), nullptr, nullptr, nullptr)))
                     return die("tdoa_process_track", rc);
             }
@@ -413,12 +423,11 @@ int main(int argc, char **argv)
                 }
                 if (stack) {
                     // one line per stack; the target block's refined stacked delays replace the per-window choice
-                    const int m = stack_m > 0 && stack_m < wpb ? stack_m : wpb;
                     std::vector<double> sd, sc;
                     for (int sid = 0; sid < n_stacks; sid++) {
                         const size_t u = (size_t)sid * P + p;
                         const tdoa_peak &p1 = spk[2 * u], &p2 = spk[2 * u + 1];
-                        const int sj = sid % spb, n_w = std::min(m, wpb - sj * m);
+                        const int sj = sid % spb, n_w = stacks.n_w(sid);
                         std::printf("STACK block %d stack %d %s - %s: windows=%d delay=%d samples refined=%.3f |C|=%.6f ratio=%.3f",
                                     sid / spb + 1, sj, caps[i].st.name.c_str(), caps[j].st.name.c_str(), n_w, p1.lag,
                                     sfine[u].delay, (double)p1.abs_corr,
@@ -431,8 +440,8 @@ int main(int argc, char **argv)
                     }
                     for (int sid = 0; track && sid < n_stacks; sid++) {   // the track of every stack: a line of its own
                         const size_t u = (size_t)sid * P + p;
-                        const int sj = sid % spb, n_w = std::min(m, wpb - sj * m);
-                        const int32_t *lg = tlags.data() + u * m;
+                        const int sj = sid % spb, n_w = stacks.n_w(sid);
+                        const int32_t *lg = tlags.data() + u * stacks.m;
                         std::printf("TRACK block %d stack %d %s - %s: windows=%d step=%d first=%d last=%d score=%.6f lags=",
                                     sid / spb + 1, sj, caps[i].st.name.c_str(), caps[j].st.name.c_str(), n_w, track_j, (int)lg[0],
                                     (int)lg[n_w - 1], tscore[u].corr);
@@ -446,9 +455,9 @@ int main(int argc, char **argv)
                 tgt_w.push_back(median(ct));
             }
         // --closure: the three lags of every station triple that close, a line per stack and triple
-        const int T = closure ? tdoa_num_triples(ctx) : 0, cm = stack_m > 0 && stack_m < wpb ? stack_m : wpb;
+        const int T = closure ? tdoa_num_triples(ctx) : 0;
         for (int sid = 0; sid < (T ? n_stacks : 0); sid++) {
-            const double root = std::sqrt((double)std::min(cm, wpb - (sid % spb) * cm));
+            const double root = std::sqrt((double)stacks.n_w(sid));
             int t = 0;
             for (int i = 0; i < S; i++)
                 for (int j = i + 1; j < S; j++)

@@ -122,29 +122,19 @@ static int download_locate(tdoa_ctx *ctx, size_t n_sets, const LocateGeom &g, td
     return TDOA_OK;
 }
 
-// The group's search on one context: the members' summed Q uploaded, then the kernels a context's own call ends with.
-// Not part of a step graph (the context's cached step stays valid unless a buffer had to grow).
+// the delay-table search on a group's merged sum (finish_from_host, stacked_api.inc)
 static int locate_from_host(tdoa_ctx *ctx, const int64_t *q_sum, int windows_per_stack, int min_separation, tdoa_location *loc,
                             int32_t *lags, double *corr, int64_t *map)
 {
-    int rc, wpb = 0;
-    if ((rc = check_ctx(ctx))) return rc;
-    if ((rc = tdoa_num_windows(ctx, &wpb, nullptr))) return fail(ctx, rc, "captures missing or too small");
-    const int P = tdoa_num_pairs(ctx);
     const LocateGeom g = locate_geom(ctx, min_separation);
-    const StackLayout sl = build_stack_layout({}, wpb, P, windows_per_stack);
-    const size_t n_sp = (size_t)sl.n_stacks * P;
-    if ((rc = ensure(ctx, ctx->stack_q, sizeof(long long) * n_sp * g.n))) return rc;
-    if ((rc = ensure(ctx, ctx->stack_desc, stack_desc_bytes(sl.n_stacks, P, 0)))) return rc;   // (a member's step made it larger)
-    if ((rc = ensure_locate(ctx, sl.n_stacks, g))) return rc;
-    std::vector<double> ones;
-    if ((rc = upload_stack_desc(ctx, sl, P, &ones, false))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->stack_q.p, q_sum, sizeof(int64_t) * n_sp * g.n, hipMemcpyHostToDevice, ctx->stream));
-    launch_locate(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, sl.n_stacks, P).roots, sl.n_stacks, g);
-    HIPCHK(ctx, hipGetLastError());
-    if ((rc = download_locate(ctx, sl.n_stacks, g, loc, lags, corr, map))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDOA_OK;
+    return finish_from_host(
+        ctx, q_sum, windows_per_stack,
+        [&](int n_stacks, const double *roots) -> int {
+            if (int rc = ensure_locate(ctx, n_stacks, g)) return rc;
+            launch_locate(ctx, ctx->stack_q.as<const long long>(), roots, n_stacks, g);
+            return TDOA_OK;
+        },
+        [&](int n_stacks) { return download_locate(ctx, n_stacks, g, loc, lags, corr, map); });
 }
 
 // what tdoa_process_locate and the group's call refuse once the arguments are in range: the lag mode, the captures, the
@@ -162,7 +152,7 @@ static int check_locate_state(const tdoa_ctx *ctx, int windows_per_stack, const 
     if (const char *bad = check_locate_table(ctx, S)) return refuse(TDOA_ERR_STATE, bad);
     int wpb = 0;
     if (tdoa_num_windows(ctx, &wpb, nullptr)) return refuse(TDOA_ERR_STATE, "captures missing or too small");
-    if (locate_overflows(S * (S - 1) / 2, windows_per_stack > 0 ? std::min(windows_per_stack, wpb) : wpb))
+    if (locate_overflows(S * (S - 1) / 2, stack_geom(wpb, windows_per_stack).mm))
         return refuse(TDOA_ERR_UNSUPPORTED, "pairs x stack length > 2^17: a cell's score could overflow");
     if (3ll * wpb > kLocateMaxSets) return refuse(TDOA_ERR_UNSUPPORTED, "more than 65535 stacks");
     return TDOA_OK;

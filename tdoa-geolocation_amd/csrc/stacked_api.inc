@@ -1,36 +1,43 @@
-// stacked_api.inc -- stacked correlation, host side: the stacks of a job, the finishing kernels' launches and downloads
-// (shared by a context's own step, step_products.inc, and the group's merged sum), tdoa_num_stacks.
-// Included by tdoa_mi355x.hip before step_products.inc.
+// stacked_api.inc -- stacked correlation, host side: the stacks' geometry (StackGeom: the one place their lengths and counts
+// are worked out), the stacks of a job, the finishing kernels' launches and downloads (shared by a context's own step,
+// step_products.inc, and the group's merged sum), tdoa_num_stacks, and finish_from_host: a merged sum uploaded and handed to
+// the stack's finish, the closure search or the delay-table search.
+// Included by tdoa_mi355x.hip before closure_api.inc, locate_api.inc and step_products.inc.
 
 extern "C" {
 
+// The stacks of a block of wpb windows, windows_per_stack at a time (0 or more than wpb: the whole block): every length,
+// count and index the host code needs of them comes from here.
+struct StackGeom {
+    int wpb = 0, mm = 0, spb = 0, n_stacks = 0;            // windows per block, windows of a full stack, stacks per block, stacks of the three blocks
+    int n_w(int sid) const { return std::min(mm, wpb - (sid % spb) * mm); }        // the last stack of a block may be short
+    int stack_of(int wid) const { return (wid / wpb) * spb + (wid % wpb) / mm; }
+    int pos_of(int wid) const { return (wid % wpb) % mm; }                          // window wid's place in its stack
+};
+static StackGeom stack_geom(int wpb, int windows_per_stack)
+{
+    StackGeom g;
+    g.wpb = wpb;
+    g.mm = windows_per_stack > 0 ? std::min(windows_per_stack, wpb) : wpb;
+    g.spb = (wpb + g.mm - 1) / g.mm;
+    g.n_stacks = 3 * g.spb;
+    return g;
+}
+
 // The stacks of a job (include/tdoa_mi355x.h, "stacked correlation") and which of a rank's pair-windows each (stack, pair)
 // sums -- plain numbers, like StepLayout.  The device copy (ctx->stack_desc) is roots, ones, desc, list in this order.
-struct StackLayout {
-    int spb = 0, n_stacks = 0;               // stacks per block, stacks of the three blocks
+struct StackLayout : StackGeom {
     std::vector<double> roots;               // [n_stacks]: sqrt(n_w)
     std::vector<StackDesc> desc;             // [n_stacks * P]
     std::vector<int32_t> list;               // the rank's pair-window numbers (indices into StepLayout::pw), by stack-pair
 };
 
-static void stack_geometry(int wpb, int m, int *spb, int *n_stacks)
-{
-    const int mm = m > 0 ? std::min(m, wpb) : wpb;
-    *spb = (wpb + mm - 1) / mm;
-    *n_stacks = 3 * *spb;
-}
-
-static StackLayout build_stack_layout(const std::vector<PWDesc> &pw, int wpb, int P, int m)
+static StackLayout build_stack_layout(const std::vector<PWDesc> &pw, const StackGeom &geom, int P)
 {
     StackLayout L;
-    stack_geometry(wpb, m, &L.spb, &L.n_stacks);
-    const int mm = m > 0 ? std::min(m, wpb) : wpb;
-    for (int sid = 0; sid < L.n_stacks; sid++)
-        L.roots.push_back(std::sqrt((double)std::min(mm, wpb - (sid % L.spb) * mm)));
-    auto stack_pair = [&](const PWDesc &d) {
-        const int wid = d.out_index / P, p = d.out_index % P;
-        return ((wid / wpb) * L.spb + (wid % wpb) / mm) * P + p;
-    };
+    static_cast<StackGeom &>(L) = geom;
+    for (int sid = 0; sid < L.n_stacks; sid++) L.roots.push_back(std::sqrt((double)L.n_w(sid)));
+    auto stack_pair = [&](const PWDesc &d) { return L.stack_of(d.out_index / P) * P + d.out_index % P; };
     L.desc.assign((size_t)L.n_stacks * P, StackDesc{0, 0});
     for (const PWDesc &d : pw) L.desc[stack_pair(d)].count++;
     int32_t at = 0;
@@ -137,10 +144,9 @@ int tdoa_num_stacks(const tdoa_ctx *ctx, int windows_per_stack, int *stacks_per_
     int wpb = 0;
     const int rc = tdoa_num_windows(ctx, &wpb, nullptr);
     if (rc) return rc;
-    int spb, n;
-    stack_geometry(wpb, windows_per_stack, &spb, &n);
-    if (stacks_per_block) *stacks_per_block = spb;
-    if (n_stacks_total) *n_stacks_total = n;
+    const StackGeom g = stack_geom(wpb, windows_per_stack);
+    if (stacks_per_block) *stacks_per_block = g.spb;
+    if (n_stacks_total) *n_stacks_total = g.n_stacks;
     return TDOA_OK;
 }
 
@@ -154,28 +160,52 @@ static const char *check_stacked_args(int windows_per_stack, int k, int min_sepa
     return nullptr;
 }
 
-// The group's finish on one context: the members' summed Q uploaded, then the kernels a context's own call ends with.
-// Not part of a step graph (the context's cached step stays valid unless a buffer had to grow).
-static int stack_finish_from_host(tdoa_ctx *ctx, const int64_t *q_sum, int windows_per_stack, int k, int min_separation,
-                                  double gate, tdoa_peak *peaks, int32_t *count, tdoa_fine_peak *fine, float *surface)
+// The end of every call that launches outside a step graph: the launches' error, the call's own copies out, the wait (the
+// host vectors its uploads read go after it).
+static int download_and_wait(tdoa_ctx *ctx, const std::function<int()> &download)
+{
+    HIPCHK(ctx, hipGetLastError());
+    if (int rc = download()) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return TDOA_OK;
+}
+
+// A group's merged sum on one context: q_sum into ctx->stack_q with the stacks' roots and unit scales beside it, then
+// launch(n_stacks, roots) -- the caller's own buffers and the kernels a context's own call ends with -- and its download.
+// Not part of a step graph (the context's cached step stays valid unless a buffer had to grow: the runs and the list its
+// k_stack_accumulate reads stay as they are).
+static int finish_from_host(tdoa_ctx *ctx, const int64_t *q_sum, int windows_per_stack,
+                            const std::function<int(int n_stacks, const double *roots)> &launch,
+                            const std::function<int(int n_stacks)> &download)
 {
     int rc, wpb = 0;
     if ((rc = check_ctx(ctx))) return rc;
     if ((rc = tdoa_num_windows(ctx, &wpb, nullptr))) return fail(ctx, rc, "captures missing or too small");
-    const int P = tdoa_num_pairs(ctx), n_lags = 2 * ctx->prm.max_lag - 1, lag_lo = -(ctx->prm.max_lag - 1);
-    const StackLayout sl = build_stack_layout({}, wpb, P, windows_per_stack);
+    const int P = tdoa_num_pairs(ctx), n_lags = 2 * ctx->prm.max_lag - 1;
+    const StackLayout sl = build_stack_layout({}, stack_geom(wpb, windows_per_stack), P);
     const size_t n_sp = (size_t)sl.n_stacks * P;
     if ((rc = ensure(ctx, ctx->stack_q, sizeof(long long) * n_sp * n_lags))) return rc;
     if ((rc = ensure(ctx, ctx->stack_desc, stack_desc_bytes(sl.n_stacks, P, 0)))) return rc;   // (a member's step made it larger)
-    if ((rc = ensure_stack_finish(ctx, n_sp, n_lags, k))) return rc;
     std::vector<double> ones;
     if ((rc = upload_stack_desc(ctx, sl, P, &ones, false))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(ctx->stack_q.p, q_sum, sizeof(int64_t) * n_sp * n_lags, hipMemcpyHostToDevice, ctx->stream));
-    launch_stack_finish(ctx, sl.n_stacks, P, n_lags, lag_lo, k, min_separation, gate);
-    HIPCHK(ctx, hipGetLastError());
-    if ((rc = download_stack(ctx, n_sp, n_lags, k, peaks, count, fine, surface))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDOA_OK;
+    if ((rc = launch(sl.n_stacks, stack_dev(ctx, sl.n_stacks, P).roots))) return rc;
+    return download_and_wait(ctx, [&] { return download(sl.n_stacks); });
+}
+
+// the merged stacks finished: surfaces, k peaks and the refined peak 1
+static int stack_finish_from_host(tdoa_ctx *ctx, const int64_t *q_sum, int windows_per_stack, int k, int min_separation,
+                                  double gate, tdoa_peak *peaks, int32_t *count, tdoa_fine_peak *fine, float *surface)
+{
+    const int P = tdoa_num_pairs(ctx), n_lags = 2 * ctx->prm.max_lag - 1, lag_lo = -(ctx->prm.max_lag - 1);
+    return finish_from_host(
+        ctx, q_sum, windows_per_stack,
+        [&](int n_stacks, const double *) -> int {
+            if (int rc = ensure_stack_finish(ctx, (size_t)n_stacks * P, n_lags, k)) return rc;
+            launch_stack_finish(ctx, n_stacks, P, n_lags, lag_lo, k, min_separation, gate);
+            return TDOA_OK;
+        },
+        [&](int n_stacks) { return download_stack(ctx, (size_t)n_stacks * P, n_lags, k, peaks, count, fine, surface); });
 }
 
 }  // extern "C"

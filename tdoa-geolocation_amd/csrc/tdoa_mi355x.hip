@@ -161,12 +161,14 @@ struct tdoa_ctx {
     // the score, lags and values of every stack-pair's track
     DevBuf track_tab, track_t, track_d, track_score, track_lags, track_values;
     // the closure search: the stations' centres, the tiles' candidates [stack][triple][tile], (u*, v*) and the records
-    // [stack][triple]; tdoa_debug_closure_from_q's own words and sqrt(n_w)
-    DevBuf closure_centre, closure_part, closure_best, closure_out, closure_q, closure_roots;
+    // [stack][triple]
+    DevBuf closure_centre, closure_part, closure_best, closure_out;
     // the delay-table search: the table [station][cell] (state: tdoa_locate_set_table; 0 cells: none), the map [stack][cell],
     // the tiles' candidates [stack][tile], the locations' cells and records [stack], the best cells' lags and correlations
-    // [stack][pair]; tdoa_debug_locate_from_q's own words and sqrt(n_w)
-    DevBuf locate_table, locate_map, locate_part, locate_best, locate_out, locate_lags, locate_corr, locate_q, locate_roots;
+    // [stack][pair]
+    DevBuf locate_table, locate_map, locate_part, locate_best, locate_out, locate_lags, locate_corr;
+    // tdoa_debug_closure_from_q and tdoa_debug_locate_from_q: the caller's words and sqrt(n_w) per set
+    DevBuf debug_q, debug_roots;
     int locate_cells = 0, locate_cols = 0, locate_stations = 0;
 };
 
@@ -516,9 +518,9 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->sel_peaks, &ctx->sel_count, &ctx->stack_q, &ctx->stack_surf, &ctx->stack_keys, &ctx->stack_fine,
                       &ctx->stack_desc, &ctx->drift_tab, &ctx->drift_keys, &ctx->drift_h, &ctx->drift_prof, &ctx->track_tab,
                       &ctx->track_t, &ctx->track_d, &ctx->track_score, &ctx->track_lags, &ctx->track_values, &ctx->closure_centre,
-                      &ctx->closure_part, &ctx->closure_best, &ctx->closure_out, &ctx->closure_q, &ctx->closure_roots, &ctx->locate_table,
+                      &ctx->closure_part, &ctx->closure_best, &ctx->closure_out, &ctx->locate_table,
                       &ctx->locate_map, &ctx->locate_part, &ctx->locate_best, &ctx->locate_out, &ctx->locate_lags, &ctx->locate_corr,
-                      &ctx->locate_q, &ctx->locate_roots};
+                      &ctx->debug_q, &ctx->debug_roots};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -806,7 +808,7 @@ int tdoa_plan_info(const tdoa_ctx *ctx, int64_t *fft_n, int32_t *n1, int32_t *n2
 }
 
 static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host, void *out_dev,
-                        tdoa_fine_peak *fine_host, double gate, StepProduct prod = StepProduct{})
+                        tdoa_fine_peak *fine_host, double gate, StepProduct *prod = nullptr)
 {
     int rc;
     if ((rc = check_ctx(ctx))) return rc;
@@ -891,12 +893,15 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
     // call groups as this one did)
     const int n_lags = lag_hi - lag_lo + 1;
     const StepView view{ctx, &lay, slots, n_lags, lag_lo, P, wpb, d_pw, d_keys, d_scales, nullptr};
-    if ((rc = reserve_product(view, prod))) return rc;
+    if (prod && (rc = prod->reserve(view))) return rc;
 
     std::vector<uint64_t> key = step_graph_key(ctx, rank, world, per_batch, wlen, block, go, fine_host != nullptr, gate);
-    key_product(prod, &key);
+    if (prod)
+        prod->key(&key);
+    else
+        key.insert(key.end(), {StepProduct::None, 0, 0, 0});
     if (!step_graph_replays(ctx, key)) {
-        if ((rc = upload_product(view, prod))) return rc;
+        if (prod && (rc = prod->upload(view))) return rc;
         std::vector<double> scales(slots, 1.0 / (4.0 * (double)n * std::sqrt((double)corr_len)));
         HIPCHK(ctx, hipMemcpyAsync(d_scales, scales.data(), sizeof(double) * slots, hipMemcpyHostToDevice, st));
         if (!sw.empty()) {
@@ -908,7 +913,7 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
 
         HIPCHK(ctx, hipStreamSynchronize(st));   // host vectors go out of scope below
     }
-    if ((rc = refresh_product(view, prod))) return rc;
+    if (prod && (rc = prod->refresh(view))) return rc;      // every call, replayed or not, before the step is launched
 
     auto enqueue = [&]() -> int {
         ctx->prof_last = -1;
@@ -922,7 +927,7 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
             const int n_sw = (int)(lay.sw_off[w0 + nw] - lay.sw_off[w0]), n_pw = (int)(lay.pw_off[w0 + nw] - lay.pw_off[w0]);
             FmBufs bf{d_sw + lay.sw_off[w0], go ? d_sw + n_sw_all + lay.sw_off[w0] : nullptr, d_pw + lay.pw_off[w0],
                       d_quads + lay.q_off[w0], d_keys, nullptr, 1.0f, (double)wlen * n_sw, fine_raw};
-            if (prod.kind != StepProduct::None) {      // the K5 kernels' lag arrays, pair-window i of the batch at i * n_lags
+            if (prod) {                                // the K5 kernels' lag arrays, pair-window i of the batch at i * n_lags
                 bf.lag_dump = ctx->surf.as<float>() + lay.pw_off[w0] * (size_t)n_lags;
                 bf.dump_stride = (size_t)n_lags;
             }
@@ -933,7 +938,10 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
         launch_decode(ctx, d_keys, d_scales, slots, fine_raw, gate);
         StepView v = view;
         v.slot_gain = ctx->once_active ? ctx->slot_gain.as<const double>() : nullptr;
-        enqueue_product(v, prod);
+        if (prod) {
+            ctx->prof_last = -1;             // unscoped launches
+            prod->enqueue(v);
+        }
         return TDOA_OK;
     };
     if ((rc = run_step_graph(ctx, key, enqueue))) return rc;
@@ -944,7 +952,7 @@ static int process_impl(tdoa_ctx *ctx, int rank, int world, tdoa_peak *out_host,
         HIPCHK(ctx, hipMemcpyAsync(out_host, ctx->peaks.p, sizeof(PeakOut) * slots, hipMemcpyDeviceToHost, st));
     if (fine_host)
         HIPCHK(ctx, hipMemcpyAsync(fine_host, ctx->fine.p, sizeof(FineOut) * slots, hipMemcpyDeviceToHost, st));
-    if ((rc = download_product(view, prod))) return rc;
+    if (prod && (rc = prod->download(view))) return rc;
     HIPCHK(ctx, hipStreamSynchronize(st));
     prof_collect(ctx);
     collect_step_graph_marks(ctx);
@@ -968,11 +976,10 @@ int tdoa_process_lags(tdoa_ctx *ctx, int rank, int world, float *lags_host, void
     if (!ctx) return TDOA_ERR_INVALID;
     if (!lags_host && !lags_dev) return fail(ctx, TDOA_ERR_INVALID, "lags_host and lags_dev are NULL");
     if (ctx->prm.lag_mode == TDOA_LAGS_GO) return fail(ctx, TDOA_ERR_UNSUPPORTED, "correlation surfaces with TDOA_LAGS_GO");
-    StepProduct prod;
-    prod.kind = StepProduct::Lags;
-    prod.lags.lags_host = lags_host;
-    prod.lags.lags_dev = lags_dev;
-    return process_impl(ctx, rank, world, nullptr, nullptr, nullptr, 0.0, prod);
+    LagsProduct prod;
+    prod.lags_host = lags_host;
+    prod.lags_dev = lags_dev;
+    return process_impl(ctx, rank, world, nullptr, nullptr, nullptr, 0.0, &prod);
 }
 
 int tdoa_process_peaks(tdoa_ctx *ctx, int rank, int world, int k, int min_separation, tdoa_peak *peaks_host,
@@ -980,146 +987,137 @@ int tdoa_process_peaks(tdoa_ctx *ctx, int rank, int world, int k, int min_separa
 {
     int rc;
     if ((rc = check_selection(ctx, k, min_separation, peaks_host))) return rc;
-    StepProduct prod;
-    prod.kind = StepProduct::Peaks;
-    prod.peaks.k = k;
-    prod.peaks.min_sep = min_separation;
-    prod.peaks.peaks_host = peaks_host;
-    prod.peaks.count_host = count_host;
-    return process_impl(ctx, rank, world, nullptr, nullptr, nullptr, 0.0, prod);
+    PeaksProduct prod;
+    prod.k = k;
+    prod.min_sep = min_separation;
+    prod.peaks_host = peaks_host;
+    prod.count_host = count_host;
+    return process_impl(ctx, rank, world, nullptr, nullptr, nullptr, 0.0, &prod);
+}
+
+// What every entry on stacks refuses before it builds its product, in this order: a null context, a negative
+// windows_per_stack, the entry's own arguments (bad_args: its check's message, which needs no context), TDOA_LAGS_GO under
+// the entry's own name, and for the searches the captures.
+static int refuse_stacked(tdoa_ctx *ctx, int windows_per_stack, const char *bad_args, const char *go_what, bool need_captures = false)
+{
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (windows_per_stack < 0) return fail(ctx, TDOA_ERR_INVALID, "windows_per_stack < 0");
+    if (bad_args) return fail(ctx, TDOA_ERR_INVALID, bad_args);
+    if (ctx->prm.lag_mode == TDOA_LAGS_GO) return fail(ctx, TDOA_ERR_UNSUPPORTED, go_what);
+    if (need_captures && ctx->caps.empty()) return fail(ctx, TDOA_ERR_STATE, "captures missing");
+    return TDOA_OK;
+}
+
+// the stack of a product: its length, its selection and its outputs (the searches on Q ask for none: k = min_separation = 1)
+static void fill_stack(StackProduct *sp, int windows_per_stack, int k = 1, int min_separation = 1, double gate = 0.0,
+                       tdoa_peak *peaks_host = nullptr, int32_t *count_host = nullptr, tdoa_fine_peak *fine_host = nullptr,
+                       float *surface_host = nullptr, int64_t *partial_host = nullptr)
+{
+    sp->m = windows_per_stack;
+    sp->k = k;
+    sp->min_sep = min_separation;
+    sp->gate = gate;
+    sp->peaks_host = peaks_host;
+    sp->count_host = count_host;
+    sp->fine_host = fine_host;
+    sp->surface_host = surface_host;
+    sp->partial_host = partial_host;
 }
 
 int tdoa_process_stacked(tdoa_ctx *ctx, int rank, int world, int windows_per_stack, int k, int min_separation,
                          double gate_samples, tdoa_peak *peaks_host, int32_t *count_host, tdoa_fine_peak *fine_host,
                          float *surface_host, int64_t *partial_host)
 {
-    if (!ctx) return TDOA_ERR_INVALID;
-    if (const char *bad = check_stacked_args(windows_per_stack, k, min_separation, gate_samples,
-                                             peaks_host || count_host || fine_host || surface_host || partial_host))
-        return fail(ctx, TDOA_ERR_INVALID, bad);
-    if (ctx->prm.lag_mode == TDOA_LAGS_GO) return fail(ctx, TDOA_ERR_UNSUPPORTED, "stacked correlation with TDOA_LAGS_GO");
-    StepProduct prod;
-    prod.kind = StepProduct::Stack;
-    StackProduct &sp = prod.stack;
-    sp.m = windows_per_stack;
-    sp.k = k;
-    sp.min_sep = min_separation;
-    sp.gate = gate_samples;
-    sp.peaks_host = peaks_host;
-    sp.count_host = count_host;
-    sp.fine_host = fine_host;
-    sp.surface_host = surface_host;
-    sp.partial_host = partial_host;
+    const char *bad = check_stacked_args(windows_per_stack, k, min_separation, gate_samples,
+                                         peaks_host || count_host || fine_host || surface_host || partial_host);
+    if (int rc = refuse_stacked(ctx, windows_per_stack, bad, "stacked correlation with TDOA_LAGS_GO")) return rc;
+    StackProduct prod;
+    fill_stack(&prod, windows_per_stack, k, min_separation, gate_samples, peaks_host, count_host, fine_host, surface_host, partial_host);
     // (the gate stays a word of the step graph's key through the step's own gate argument)
-    return process_impl(ctx, rank, world, nullptr, nullptr, nullptr, gate_samples, std::move(prod));
+    return process_impl(ctx, rank, world, nullptr, nullptr, nullptr, gate_samples, &prod);
 }
 
 int tdoa_process_stacked_drift(tdoa_ctx *ctx, int windows_per_stack, int k, int min_separation, double gate_samples,
                                int max_drift, int drift_den, tdoa_peak *peaks_host, int32_t *count_host, tdoa_fine_peak *fine_host,
                                float *surface_host, int64_t *partial_host, int32_t *drift_host, tdoa_peak *profile_host)
 {
-    if (!ctx) return TDOA_ERR_INVALID;
-    if (const char *bad = check_stacked_args(windows_per_stack, k, min_separation, gate_samples,
-                                             peaks_host || count_host || fine_host || surface_host || partial_host || drift_host ||
-                                                 profile_host))
-        return fail(ctx, TDOA_ERR_INVALID, bad);
-    if (drift_den < 1) return fail(ctx, TDOA_ERR_INVALID, "drift_den < 1");
-    if (max_drift < 0 || max_drift > 512) return fail(ctx, TDOA_ERR_INVALID, "max_drift outside 0 .. 512");
-    if (ctx->prm.lag_mode == TDOA_LAGS_GO) return fail(ctx, TDOA_ERR_UNSUPPORTED, "stacked correlation with TDOA_LAGS_GO");
+    const char *bad = check_stacked_args(windows_per_stack, k, min_separation, gate_samples,
+                                         peaks_host || count_host || fine_host || surface_host || partial_host || drift_host ||
+                                             profile_host);
+    if (!bad && drift_den < 1) bad = "drift_den < 1";
+    if (!bad && (max_drift < 0 || max_drift > 512)) bad = "max_drift outside 0 .. 512";
+    if (int rc = refuse_stacked(ctx, windows_per_stack, bad, "stacked correlation with TDOA_LAGS_GO")) return rc;
     int wpb = 0;
     if (int rc = tdoa_num_windows(ctx, &wpb, nullptr)) return fail(ctx, rc, "captures missing or too small");
-    if (drift_shift(max_drift, stack_length(wpb, windows_per_stack) - 1, drift_den) > ctx->prm.max_lag - 1)
+    if (drift_shift(max_drift, stack_geom(wpb, windows_per_stack).mm - 1, drift_den) > ctx->prm.max_lag - 1)
         return fail(ctx, TDOA_ERR_INVALID, "the search's largest shift exceeds max_lag - 1");
-    StepProduct prod;
-    prod.kind = StepProduct::StackDrift;
-    StackDriftProduct &dp = prod.drift;
-    dp.H = max_drift;
-    dp.D = drift_den;
-    dp.drift_host = drift_host;
-    dp.profile_host = profile_host;
-    StackProduct &sp = dp.stack;
-    sp.m = windows_per_stack;
-    sp.k = k;
-    sp.min_sep = min_separation;
-    sp.gate = gate_samples;
-    sp.peaks_host = peaks_host;
-    sp.count_host = count_host;
-    sp.fine_host = fine_host;
-    sp.surface_host = surface_host;
-    sp.partial_host = partial_host;
-    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, gate_samples, std::move(prod));
+    StackDriftProduct prod;
+    fill_stack(&prod, windows_per_stack, k, min_separation, gate_samples, peaks_host, count_host, fine_host, surface_host, partial_host);
+    prod.H = max_drift;
+    prod.D = drift_den;
+    prod.drift_host = drift_host;
+    prod.profile_host = profile_host;
+    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, gate_samples, &prod);
 }
 
 int tdoa_process_track(tdoa_ctx *ctx, int windows_per_stack, int max_step, tdoa_peak *score_host, int32_t *lags_host,
                        double *values_host, float *surface_host, int64_t *total_host)
 {
-    if (!ctx) return TDOA_ERR_INVALID;
-    if (windows_per_stack < 0) return fail(ctx, TDOA_ERR_INVALID, "windows_per_stack < 0");
-    if (max_step < 0 || max_step > kTrackMaxStep) return fail(ctx, TDOA_ERR_INVALID, "max_step outside 0 .. 64");
-    if (!score_host && !lags_host && !values_host && !surface_host && !total_host)
-        return fail(ctx, TDOA_ERR_INVALID, "every output is NULL");
-    if (ctx->prm.lag_mode == TDOA_LAGS_GO) return fail(ctx, TDOA_ERR_UNSUPPORTED, "delay tracks with TDOA_LAGS_GO");
+    const char *bad = nullptr;
+    if (max_step < 0 || max_step > kTrackMaxStep)
+        bad = "max_step outside 0 .. 64";
+    else if (!score_host && !lags_host && !values_host && !surface_host && !total_host)
+        bad = "every output is NULL";
+    if (int rc = refuse_stacked(ctx, windows_per_stack, bad, "delay tracks with TDOA_LAGS_GO")) return rc;
     int wpb = 0;
     if (int rc = tdoa_num_windows(ctx, &wpb, nullptr)) return fail(ctx, rc, "captures missing or too small");
-    if (stack_length(wpb, windows_per_stack) > 4096) return fail(ctx, TDOA_ERR_INVALID, "a stack of more than 4096 windows");
-    StepProduct prod;
-    prod.kind = StepProduct::StackTrack;
-    StackTrackProduct &tp = prod.track;
-    tp.m = windows_per_stack;
-    tp.J = max_step;
-    tp.score_host = score_host;
-    tp.lags_host = lags_host;
-    tp.values_host = values_host;
-    tp.surface_host = surface_host;
-    tp.total_host = total_host;
-    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, std::move(prod));
+    if (stack_geom(wpb, windows_per_stack).mm > 4096) return fail(ctx, TDOA_ERR_INVALID, "a stack of more than 4096 windows");
+    StackTrackProduct prod;
+    prod.m = windows_per_stack;
+    prod.J = max_step;
+    prod.score_host = score_host;
+    prod.lags_host = lags_host;
+    prod.values_host = values_host;
+    prod.surface_host = surface_host;
+    prod.total_host = total_host;
+    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
 }
 
 int tdoa_process_closure(tdoa_ctx *ctx, int windows_per_stack, int gate, int min_separation, const int32_t *centre,
                          tdoa_closure *closure_host)
 {
-    if (!ctx) return TDOA_ERR_INVALID;
-    if (windows_per_stack < 0) return fail(ctx, TDOA_ERR_INVALID, "windows_per_stack < 0");
-    if (const char *bad = check_closure_args(gate, min_separation, closure_host)) return fail(ctx, TDOA_ERR_INVALID, bad);
-    if (ctx->prm.lag_mode == TDOA_LAGS_GO) return fail(ctx, TDOA_ERR_UNSUPPORTED, "the closure search with TDOA_LAGS_GO");
-    if (ctx->caps.empty()) return fail(ctx, TDOA_ERR_STATE, "captures missing");
+    if (int rc = refuse_stacked(ctx, windows_per_stack, check_closure_args(gate, min_separation, closure_host),
+                                "the closure search with TDOA_LAGS_GO", true))
+        return rc;
     const int S = (int)ctx->caps.size();
     if (S < 3 || S > kClosureMaxStations) return fail(ctx, TDOA_ERR_UNSUPPORTED, "the closure search needs 3 .. 64 stations");
-    StepProduct prod;
-    prod.kind = StepProduct::Closure;
-    ClosureProduct &cp = prod.closure;
-    cp.stack.m = windows_per_stack;
-    cp.stack.k = 1;
-    cp.stack.min_sep = 1;
-    cp.G = gate;
-    cp.sep = min_separation;
-    cp.centre = closure_centres(centre, S);
-    cp.out_host = closure_host;
-    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, std::move(prod));
+    ClosureProduct prod;
+    fill_stack(&prod, windows_per_stack);
+    prod.G = gate;
+    prod.sep = min_separation;
+    prod.centre = closure_centres(centre, S);
+    prod.out_host = closure_host;
+    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
 }
 
 int tdoa_process_locate(tdoa_ctx *ctx, int windows_per_stack, int min_separation, tdoa_location *loc_host, int32_t *lags_host,
                         double *corr_host, int64_t *map_host)
 {
-    if (!ctx) return TDOA_ERR_INVALID;
-    if (windows_per_stack < 0) return fail(ctx, TDOA_ERR_INVALID, "windows_per_stack < 0");
-    if (const char *bad = check_locate_args(min_separation, loc_host)) return fail(ctx, TDOA_ERR_INVALID, bad);
-    const char *what = nullptr;
+    if (int rc = refuse_stacked(ctx, windows_per_stack, check_locate_args(min_separation, loc_host),
+                                "the delay-table search with TDOA_LAGS_GO", true))
+        return rc;
+    const char *what = nullptr;              // (the station count, the table, the overflow bound: shared with the group's call)
     if (const int rc = check_locate_state(ctx, windows_per_stack, &what)) return fail(ctx, rc, what);
-    StepProduct prod;
-    prod.kind = StepProduct::Locate;
-    LocateProduct &lp = prod.locate;
-    lp.stack.m = windows_per_stack;
-    lp.stack.k = 1;
-    lp.stack.min_sep = 1;
-    lp.sep = min_separation;
-    lp.n_cells = ctx->locate_cells;
-    lp.n_cols = ctx->locate_cols;
-    lp.loc_host = loc_host;
-    lp.lags_host = lags_host;
-    lp.corr_host = corr_host;
-    lp.map_host = map_host;
-    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, std::move(prod));
+    LocateProduct prod;
+    fill_stack(&prod, windows_per_stack);
+    prod.sep = min_separation;
+    prod.n_cells = ctx->locate_cells;
+    prod.n_cols = ctx->locate_cols;
+    prod.loc_host = loc_host;
+    prod.lags_host = lags_host;
+    prod.corr_host = corr_host;
+    prod.map_host = map_host;
+    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
 }
 
 // fast_analyzer.go:139-155 and collector.go:224 from the exact integer sums, in the reference's expression order

@@ -20,6 +20,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from stack_helpers import same_bytes as _same_bytes, stacks_q as _stacks_q, windows_q as _windows_q
 from test_closure_cpu import _check_hand_case, hand_cases, noisy_windows
 
 pytestmark = pytest.mark.gpu
@@ -35,23 +36,6 @@ CENTRES = [None, (0, 13, -650, 300), (0, 0, 0, 5000)]        # the last: every t
 def _synth(c, n_stations, block):
     for s in range(n_stations):
         c.synth_capture(s, block, ST[s % 3], TX, 0xC105E000 + s)
-
-
-def _same_bytes(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def _windows_q(c):
-    """q of every pair-window [W][P][L], word for word"""
-    return c.process_stacked(1, 1, 1, want_partial=True)["partial"]
-
-
-def _stacks_q(c, q, m):
-    """(Q [n_stacks][P][L], n_w [n_stacks]) of stacks of m windows from the windows' q"""
-    from tdoa_amd import stacking
-    wpb, _ = c.num_windows()
-    _, ids = stacking.stack_ids(wpb, m)
-    return np.stack([q[wins].sum(axis=0) for _, wins in ids]), [len(wins) for _, wins in ids]
 
 
 def _model(c, q, m, G, sep, centre):

@@ -87,6 +87,33 @@ def test_group_over_captures_synthesised_on_each_member():
     assert want.shape == (9, 3) and (want["abs_corr"] > 0).all()
 
 
+def test_stacked_calls_of_different_sizes_share_the_merged_sum():
+    """tdoa_group_process_stacked, _closure and _locate gather the members' fixed-point sums through one function and keep
+    them in the group from call to call: stacks of 2, whole blocks, single windows and whole blocks again (9, 3, 15 and 3
+    stacks of 6 pairs and 1399 lags) on one group of two members, each the single context's bytes.  Four stations, windows
+    of 10 000, 5 per block: the geometry of the searches' four_stations fixtures."""
+    import tdoa_amd
+    wl, wpb, ml = 10_000, 5, 700
+    table = np.random.default_rng(29).integers(-16 * 900, 16 * 900 + 1, size=(300, 4), dtype=np.int32)
+    with tdoa_amd.Group([0, 0], max_lag=ml, window_len=wl) as g, tdoa_amd.Context(max_lag=ml, window_len=wl) as c:
+        for target in [g.member(0), g.member(1), c]:
+            for s in range(4):
+                target.synth_capture(s, wpb * wl, ST[s % 3], TX, 0x5D0A0000 + s)
+        g.locate_set_table(table, 20)        # (the group's binding sizes the map it returns from this call)
+        c.locate_set_table(table, 20)
+        calls = [("stacks of 2", lambda x: x.process_stacked(2, 3, 4, want_surface=True)),
+                 ("closure, whole blocks", lambda x: {"closure": x.process_closure(0, 37, 2, (0, 13, -250, 100))}),
+                 ("locate, single windows", lambda x: x.process_locate(1, 2, want_map=True)),
+                 ("whole blocks", lambda x: x.process_stacked(0, 3, 4, want_surface=True))]
+        for name, call in calls:
+            got, want = call(g), call(c)
+            assert sorted(got) == sorted(want), name
+            for key in want:
+                assert got[key].shape == want[key].shape and got[key].dtype == want[key].dtype, (name, key)
+                assert got[key].tobytes() == want[key].tobytes(), (name, key)
+        assert want["peaks"].shape == (3, 6, 3) and (want["peaks"]["abs_corr"][:, :, 0] > 0).all()
+
+
 def test_members_with_different_stations_are_refused(tmp_path, oracle):
     import tdoa_amd
     paths = _write(tmp_path, oracle)

@@ -22,6 +22,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from stack_helpers import same_bytes as _same_bytes, stacks_q as _stacks_q, windows_q as _windows_q
 from test_locate_cpu import FS, GRID, ST4, _check_hand_case, hand_cases, noisy_case, noisy_windows, own_lags
 
 pytestmark = pytest.mark.gpu
@@ -37,27 +38,16 @@ def _synth(c, n_stations, block):
         c.synth_capture(s, block, ST[s % 3], TX, 0x10CA7E00 + s)
 
 
-def _same_bytes(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
 def _same_outputs(got, want):
     """got: process_locate's dict; want: the model's (records, lags, corr, map)"""
     names = ("loc", "lags", "corr", "map")
     return all(_same_bytes(got[k], w) for k, w in zip(names, want) if k in got)
 
 
-def _windows_q(c):
-    """q of every pair-window [W][P][L], word for word"""
-    return c.process_stacked(1, 1, 1, want_partial=True)["partial"]
-
-
 def _model(c, q, m, table, n_cols, sep):
-    from tdoa_amd import locate, stacking
-    wpb, _ = c.num_windows()
-    _, ids = stacking.stack_ids(wpb, m)
-    Q = np.stack([q[wins].sum(axis=0) for _, wins in ids])
-    return locate.locate_stacks(Q, table, n_cols, c.params.max_lag, sep, [len(wins) for _, wins in ids])
+    from tdoa_amd import locate
+    Q, n_w = _stacks_q(c, q, m)
+    return locate.locate_stacks(Q, table, n_cols, c.params.max_lag, sep, n_w)
 
 
 def _grid_table(stations, **kw):

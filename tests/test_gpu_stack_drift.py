@@ -20,6 +20,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from stack_helpers import same_bytes as _same_bytes, windows_q as _windows_q
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,10 +38,6 @@ def _synth(c, n_stations, block):
         c.synth_capture(s, block, ST[s % 3], TX, 0x57AC0000 + s)
 
 
-def _same_bytes(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
 def _drift(c, m, H, D, k=K, sep=SEP, gate=None):
     return c.process_stacked_drift(m, H, D, k, sep, gate=gate, want_surface=True, want_partial=True)
 
@@ -52,7 +50,7 @@ def _check_against_model(c, out, m, H, D, k=K, sep=SEP, gate=None, q=None):
     gate = float(ml if gate is None else gate)
     wpb, _ = c.num_windows()
     if q is None:
-        q = c.process_stacked(1, 1, 1, want_partial=True)["partial"]       # [W][P][L]: q of every pair-window
+        q = _windows_q(c)
     _, ids = stacking.stack_ids(wpb, m)
     n_pairs = q.shape[1]
     assert out["drift"].shape == (len(ids), n_pairs) and out["drift"].dtype == np.int32

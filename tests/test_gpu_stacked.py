@@ -14,6 +14,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from stack_helpers import same_bytes as _same_bytes
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,10 +30,6 @@ def _synth(c, n_stations, block):
     for s in range(n_stations):
         lle = ST[s % 3]
         c.synth_capture(s, block, (lle[0] + 0.01 * (s // 3), lle[1], lle[2]), TX, 0x57AC0000 + s)
-
-
-def _same_bytes(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def _finite(out):

@@ -22,6 +22,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from stack_helpers import same_bytes as _same_bytes, windows_q as _windows_q
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,17 +39,8 @@ def _synth(c, n_stations, block):
         c.synth_capture(s, block, ST[s % 3], TX, 0x57AC0000 + s)
 
 
-def _same_bytes(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
 def _track(c, m, J):
     return c.process_track(m, J, want_surface=True, want_total=True)
-
-
-def _windows_q(c):
-    """q of every pair-window [W][P][L], word for word"""
-    return c.process_stacked(1, 1, 1, want_partial=True)["partial"]
 
 
 def _check_against_model(c, out, m, J, q=None):
