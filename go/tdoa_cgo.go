@@ -267,6 +267,42 @@ func (g *gpuCorrelator) ProcessLocate(windowsPerStack, minSeparation int) (loc [
 	return loc, lags, corr, nil
 }
 
+// LocateSetClock hands the context the stations' clocks for the delay-table search, [nStacks][nStations] in units of 1/16
+// sample (nil: forget them): stack sid's lags are taken from (t[c][j] - t[c][i]) + (clock[sid][j] - clock[sid][i]).  One row per
+// stack of the searches that follow; ProcessSync's clocks times 16, or 8*(before + after) for the block between two
+// reference blocks.
+func (g *gpuCorrelator) LocateSetClock(clock []int32, nStacks, nStations int) error {
+	if rc := C.tdoa_locate_set_clock(g.ctx, tablePtr(clock), C.int(nStacks), C.int(nStations)); rc != C.TDOA_OK {
+		return fmt.Errorf("tdoa_locate_set_clock: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return nil
+}
+
+// ProcessSync is the clock search (the header's "clock search"): per stack the stations' clocks k_s = centre[s] + x_s,
+// |x_s| <= gate, station 0 the gauge, that make all pairs' stacks largest at the lags the known emitter's delays refDelay
+// (one per station, units of 1/16 sample) predict -- a joint start, the placing and `rounds` sweeps.  clock is
+// [stack][station] in samples, lags and corr [stack][pair].  The caller reads the stacks of the block whose emitter it
+// described.
+func (g *gpuCorrelator) ProcessSync(windowsPerStack, gate, rounds int, refDelay, centre []int32) (sync []C.tdoa_sync, clock, lags []int32, corr []float64, err error) {
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, nil, nil, nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs, stations := int(C.tdoa_num_pairs(g.ctx)), len(refDelay)
+	if int(total)*pairs == 0 || stations*(stations-1)/2 != pairs {
+		return nil, nil, nil, nil, fmt.Errorf("tdoa_process_sync: no stacks, fewer than two stations, or not one delay per station")
+	}
+	sync = make([]C.tdoa_sync, int(total))
+	clock = make([]int32, int(total)*stations)
+	lags = make([]int32, int(total)*pairs)
+	corr = make([]float64, int(total)*pairs)
+	if rc := C.tdoa_process_sync(g.ctx, C.int(windowsPerStack), C.int(gate), C.int(rounds), tablePtr(refDelay), centrePtr(centre), &sync[0],
+		(*C.int32_t)(unsafe.Pointer(&clock[0])), (*C.int32_t)(unsafe.Pointer(&lags[0])), (*C.double)(unsafe.Pointer(&corr[0]))); rc != C.TDOA_OK {
+		return nil, nil, nil, nil, fmt.Errorf("tdoa_process_sync: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return sync, clock, lags, corr, nil
+}
+
 // windowQuality is fastAnalyzeSamples' statistics (fast_analyzer.go:117-155) for every (window, station).
 func (g *gpuCorrelator) windowQuality(stations int) ([]C.tdoa_window_quality, error) {
 	var perBlock, total C.int
@@ -409,4 +445,35 @@ func (g *Group) ProcessLocate(windowsPerStack, minSeparation int) (loc []C.tdoa_
 		return nil, nil, nil, fmt.Errorf("tdoa_group_process_locate: %s", C.GoString(C.tdoa_group_last_error(g.g)))
 	}
 	return loc, lags, corr, nil
+}
+
+// LocateSetClock hands every member the stations' clocks (gpuCorrelator.LocateSetClock).
+func (g *Group) LocateSetClock(clock []int32, nStacks, nStations int) error {
+	if rc := C.tdoa_group_locate_set_clock(g.g, tablePtr(clock), C.int(nStacks), C.int(nStations)); rc != C.TDOA_OK {
+		return fmt.Errorf("tdoa_group_locate_set_clock: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return nil
+}
+
+// ProcessSync is gpuCorrelator.ProcessSync over the group: the members' fixed-point partial sums are added on the host and
+// searched on member 0, the same bytes one context returns.
+func (g *Group) ProcessSync(windowsPerStack, gate, rounds int, refDelay, centre []int32) (sync []C.tdoa_sync, clock, lags []int32, corr []float64, err error) {
+	m := C.tdoa_group_member(g.g, 0)
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(m, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, nil, nil, nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs, stations := int(C.tdoa_num_pairs(m)), len(refDelay)
+	if int(total)*pairs == 0 || stations*(stations-1)/2 != pairs {
+		return nil, nil, nil, nil, fmt.Errorf("tdoa_group_process_sync: no stacks, fewer than two stations, or not one delay per station")
+	}
+	sync = make([]C.tdoa_sync, int(total))
+	clock = make([]int32, int(total)*stations)
+	lags = make([]int32, int(total)*pairs)
+	corr = make([]float64, int(total)*pairs)
+	if rc := C.tdoa_group_process_sync(g.g, C.int(windowsPerStack), C.int(gate), C.int(rounds), tablePtr(refDelay), centrePtr(centre), &sync[0],
+		(*C.int32_t)(unsafe.Pointer(&clock[0])), (*C.int32_t)(unsafe.Pointer(&lags[0])), (*C.double)(unsafe.Pointer(&corr[0]))); rc != C.TDOA_OK {
+		return nil, nil, nil, nil, fmt.Errorf("tdoa_group_process_sync: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return sync, clock, lags, corr, nil
 }

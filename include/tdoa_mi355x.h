@@ -480,12 +480,31 @@ int tdoa_locate_set_table(tdoa_ctx *ctx, const int32_t *delay /* [n_cells][n_sta
  * TDOA_ERR_INVALID: a NULL context (checked before anything needs a device), a NULL loc_host, windows_per_stack < 0,
  * min_separation < 1.  TDOA_ERR_STATE: no captures, no table, or a table whose n_stations differs from the captures'.
  * TDOA_ERR_UNSUPPORTED: fewer than 2 or more than 64 stations, TDOA_LAGS_GO, the overflow bound (and more than 65535
- * stacks).  TDOA_ERR_NOMEM: the map [n_stacks_total][n_cells] does not fit; tdoa_last_error says so. */
+ * stacks).  TDOA_ERR_NOMEM: the map [n_stacks_total][n_cells] does not fit; tdoa_last_error says so.
+ * With station clocks (tdoa_locate_set_clock, below): whether a clock table is present is one more word of the graph's key,
+ * and a clock table of another n_stacks or n_stations is TDOA_ERR_STATE. */
 int tdoa_process_locate(tdoa_ctx *ctx, int windows_per_stack, int min_separation,
                         tdoa_location *loc_host /* [n_stacks_total], required */,
                         int32_t *lags_host      /* [n_stacks_total][n_pairs]: lag_p(cell*), 0 where outside / no location; may be NULL */,
                         double  *corr_host      /* same shape: signed C = Q * 2^-32 / sqrt(n_w) there; may be NULL */,
                         int64_t *map_host       /* [n_stacks_total][n_cells]: score_q of every cell; may be NULL */);
+
+/* Station clocks for the delay-table search.  A table entry is pure propagation delay: the search above assumes that all
+ * stations share one clock.  Stations that start their captures samples apart add clock[j] - clock[i] to every lag of pair
+ * (i, j).  The clock table gives every stack its own station clocks (from tdoa_process_sync, below).
+ *   clock[n_stacks][n_stations] is int32, in units of 1/16 sample (TDOA_DELAY_UNIT), like the delay table.  Only differences
+ *     matter.  A caller can therefore give the block between two reference blocks the exact midpoint 8 * (k_before + k_after)
+ *     of their clocks in samples.
+ *   With a clock table set, tdoa_process_locate, tdoa_debug_locate_from_q and the group form use, for stack sid,
+ *     d = (t[c][j] - t[c][i]) + (clock[sid][j] - clock[sid][i]), taken in 64 bits, and then the rule of lag_p(c) above.
+ *     Everything else is unchanged.
+ *   Without a clock table, and with an all-zero one, every output is byte-identical.
+ * The clock table is context state, like the delay table: it needs no captures and is kept on the device.  Its contents are
+ * data; whether one is present is part of a step graph's key, so new clocks of the same shape replay the same graph.
+ * clock == NULL or n_stacks == 0: forget the clocks.  A search whose stacks (n_stacks_total; n_sets for the debug call) or
+ * stations differ from the clock table's n_stacks or n_stations returns TDOA_ERR_STATE.
+ * TDOA_ERR_INVALID: a NULL context, n_stacks outside 1 .. 65535, n_stations outside 2 .. 64. */
+int tdoa_locate_set_clock(tdoa_ctx *ctx, const int32_t *clock /* [n_stacks][n_stations] */, int n_stacks, int n_stations);
 
 /* tests only: the same kernels on the caller's words q [n_sets][P][2*max_lag-1], P = n_stations (n_stations-1) / 2 rows in
  * the library's pair order, every set a stack of n_w windows, with the context's table; outputs as tdoa_process_locate's
@@ -502,6 +521,65 @@ int tdoa_debug_locate_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_
  * that does not fit int32. */
 int tdoa_locate_grid_table(const double *stations_lle, int n_stations, double lat0, double lon0, double dlat, double dlon,
                            int rows, int cols, double height_m, double sample_rate, int32_t *delay /* [rows*cols][n_stations] */);
+
+/* Clock search: the stations' clock offsets from a block whose emitter is known.  Collector stations are synchronised by
+ * reference signals, not by disciplined oscillators: every capture is [reference | target | reference] blocks for that
+ * reason.  A reference block's emitter position is known, so the lag each pair would have from propagation alone is known;
+ * what is left of the pair's peak is the difference of the two stations' clocks.  S stations have S - 1 free clocks, and all
+ * P pairs' stacks are searched for them together: no peak is picked.
+ * The search is exact integer work on Q.  Stacks, windows_per_stack, n_w, pairs i < j in the library's order and the int64
+ * Q_p[l] over -max_lag < l < max_lag are exactly those of tdoa_process_locate.  M_p[l] = |Q_p[l]|.
+ *   ref_delay[n_stations] is int32, in units of 1/16 sample (TDOA_DELAY_UNIT): the propagation delays from the known emitter,
+ *     one row of a delay table (tdoa_locate_grid_table with rows = cols = 1, for example).
+ *     e_ij = sgn(d) * ((2|d| + 16) div 32) with d = ref_delay[j] - ref_delay[i], taken in 64 bits: the rule of lag_p(c).
+ *   centre[n_stations] is int32, in samples.  NULL means all 0.
+ *   G = gate, 0 <= G <= 1023.  R = rounds, 0 <= R <= 16.
+ *   The unknowns are k_s = centre[s] + x_s with |x_s| <= G, in samples.  x_0 = 0: station 0 is the gauge.
+ *   The objective is F(k) = sum over i < j of M_ij[e_ij + k_j - k_i].  A lag outside the searched range adds 0 to F and is
+ *     not counted in pairs_in.
+ *   Order of candidates everywhere: rank(x) = 2|x| - (x > 0), so the smaller |x| comes first, then the positive x.  "Largest"
+ *     always means the first of equal maxima in rank order.
+ *   Start.  S = 2: x_1 is the largest M_01[e_01 + centre[1] - centre[0] + x].  S >= 3: (x_1, x_2) jointly over the whole
+ *     square [-G, G]^2, the largest M_01[e_01 + k_1 - k_0] + M_02[e_02 + k_2 - k_0] + M_12[e_12 + k_2 - k_1].  Among equal
+ *     maxima the smaller rank(x_1) wins, then the smaller rank(x_2).  There is no |x_2 - x_1| constraint, unlike the closure
+ *     search; a lag outside the range just adds 0.
+ *   Placing, for s = 3 .. S-1 in order: x_s is the largest sum over i < s of M_is[e_is + (centre[s] + x) - k_i].
+ *   Sweeps, R times: for s = 1 .. S-1 in order (Gauss-Seidel, k_0 fixed) x_s is the largest sum over all S - 1 partners
+ *     i != s of M at the pair's lag: e_is + (centre[s] + x) - k_i for a partner i < s, e_si + k_i - (centre[s] + x) for a
+ *     partner i > s.  F never decreases over a sweep, and a sweep that moves nothing makes all later sweeps no-ops.
+ *   If F at the final k is 0, the record, the clocks, the lags and the correlations are all zero.
+ *   Overflow: the call returns TDOA_ERR_UNSUPPORTED when P * (stack length in use) > 2^17, as tdoa_process_locate does.
+ * The record, 32 bytes, no padding: */
+typedef struct {
+    int32_t moved, pairs_in;   /* stations the last sweep changed (0: converged; 0 when R = 0); pairs inside the range at the final k */
+    int64_t score_q, start_q;  /* F at the final k; F after placing, so score_q >= start_q */
+    double  score;             /* (double)score_q * 2^-32 / sqrt(n_w) */
+} tdoa_sync;
+
+/* Runs on every stack of all three blocks, as the other stack products do; the caller reads the stacks of the block whose
+ * emitter it described.  clock_host times TDOA_DELAY_UNIT is what tdoa_locate_set_clock takes.  Runs inside the step graph,
+ * behind the stack's accumulation: the joint start over (2G+1)^2 cells (three or more stations) and one workgroup per stack
+ * for the placing, the sweeps and the outputs.  (windows_per_stack, gate, rounds) are part of the graph's key; ref_delay and
+ * centre are data in a device buffer, so a call that changes only them replays the same graph.  tdoa_group_process_sync is
+ * the group form (the search is a function of the complete stacked Q only, so the members' partial sums merge).
+ * TDOA_ERR_INVALID: a NULL context (checked before anything needs a device), windows_per_stack < 0, gate < 0 or > 1023,
+ * rounds < 0 or > 16, a NULL ref_delay, a NULL sync_host.  TDOA_ERR_UNSUPPORTED: fewer than 2 or more than 64 stations,
+ * TDOA_LAGS_GO, the overflow bound (and more than 65535 stacks).  Before captures exist: TDOA_ERR_STATE. */
+int tdoa_process_sync(tdoa_ctx *ctx, int windows_per_stack, int gate /* G */, int rounds /* R */,
+                      const int32_t *ref_delay /* [n_stations] */, const int32_t *centre /* [n_stations] or NULL */,
+                      tdoa_sync *sync_host    /* [n_stacks_total], required */,
+                      int32_t   *clock_host   /* [n_stacks_total][n_stations]: k_s in samples; may be NULL */,
+                      int32_t   *lags_host    /* [n_stacks_total][n_pairs]: e_ij + k_j - k_i, 0 where outside; may be NULL */,
+                      double    *corr_host    /* same shape: signed C = Q * 2^-32 / sqrt(n_w) there; may be NULL */);
+
+/* tests only: the same kernels on the caller's words q [n_sets][P][2*max_lag-1], P = n_stations (n_stations-1) / 2 rows in
+ * the library's pair order, every set a stack of n_w windows; outputs as tdoa_process_sync's with n_sets for
+ * n_stacks_total.  Needs a context for max_lag and the device, and no captures.  Precondition: |q| <= 2^62 div P.
+ * TDOA_ERR_INVALID: what tdoa_process_sync refuses, q NULL, n_sets outside 1 .. 65535, n_w < 1, n_stations outside 2 .. 64.
+ * TDOA_ERR_UNSUPPORTED: P * n_w > 2^17. */
+int tdoa_debug_sync_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int gate, int rounds,
+                           const int32_t *ref_delay, const int32_t *centre, tdoa_sync *sync, int32_t *clock, int32_t *lags,
+                           double *corr);
 
 /* Capture-quality statistics of every (window, station) in one streaming pass over the bytes
  * in HBM: the byte statistics of fastAnalyzeSamples
@@ -717,6 +795,15 @@ int tdoa_group_process_closure(tdoa_group *g, int windows_per_stack, int gate, i
 int tdoa_group_locate_set_table(tdoa_group *g, const int32_t *delay, int n_cells, int n_cols, int n_stations);
 int tdoa_group_process_locate(tdoa_group *g, int windows_per_stack, int min_separation, tdoa_location *loc_host,
                               int32_t *lags_host, double *corr_host, int64_t *map_host);
+
+/* tdoa_locate_set_clock on every member (tdoa_group_process_locate then searches with member 0's clocks), and
+ * tdoa_process_sync over the members: they sum their windows as in tdoa_group_process_stacked, the host adds the partials,
+ * and member 0 runs the search on the merged Q -- the outputs are byte-identical to tdoa_process_sync(single ctx, ...).
+ * Errors as there and as tdoa_group_process.  With one member, its call writes the outputs directly. */
+int tdoa_group_locate_set_clock(tdoa_group *g, const int32_t *clock, int n_stacks, int n_stations);
+int tdoa_group_process_sync(tdoa_group *g, int windows_per_stack, int gate, int rounds, const int32_t *ref_delay,
+                            const int32_t *centre, tdoa_sync *sync_host, int32_t *clock_host, int32_t *lags_host,
+                            double *corr_host);
 
 /* the sample runs member `rank` of `world` uploads for a capture of total_samples (window grid from n_min, the shortest
  * capture of the job; block offsets from the capture's own thirds): adjacent owned windows form one run, and with fewer

@@ -10,9 +10,12 @@ kernel per window of a block after the surfaces; the difference between two legs
 `--closure G` adds a leg: tdoa_process_closure(0, G, 1) with the records downloaded (the stack's accumulation, then two
 launches of the search and two of its finish).  Every `--locate ROWSxCOLS` adds a leg: tdoa_process_locate(0, 1) on a grid of
 that many cells over 0.3 x 0.4 degrees around the stations, with the records, lags and correlations downloaded and the map
-left on the device (the table is set once per round, outside the timed window).  `--stations S` runs all legs on S stations (default 3; 8 gives 56 triples).
+left on the device (the table is set once per round, outside the timed window).  Every `--sync G[/R]` adds a leg:
+tdoa_process_sync(0, G, R) (R defaults to 2) against the delays of a known emitter at TX, with the records, clocks, lags and
+correlations downloaded (the stack's accumulation, then the joint start over (2G+1)^2 cells and one workgroup per stack for
+the placing and the sweeps).  `--stations S` runs all legs on S stations (default 3; 8 gives 56 triples).
 usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--drift H/D]... [--track J]... [--closure G]...
-[--locate ROWSxCOLS]..."""
+[--locate ROWSxCOLS]... [--sync G[/R]]..."""
 import json
 import os
 import sys
@@ -41,7 +44,7 @@ def timed(fn, steps):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
-def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=()):
+def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=()):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=20000)
     for s in range(stations):
         c.synth_capture(s, 66_666_666, ST[s % 3], TX, 0x5D0A0000 + s)
@@ -63,6 +66,9 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
         name = "process_locate_%dx%d_ms" % (rows, cols)
         setup[name] = lambda table=table, cols=cols: c.locate_set_table(table, cols)
         legs[name] = lambda: c.process_locate(0, 1)
+    ref = tdoa_amd.capi.locate_grid_table([ST[s % 3] for s in range(stations)], TX[0], TX[1], 0.0, 0.0, 1, 1, TX[2], 2e6)[0]
+    for G, R in syncs:
+        legs["process_sync_%d_%d_ms" % (G, R)] = lambda G=G, R=R: c.process_sync(ref, 0, G, R)
     times = {name: [] for name in legs}
     for _ in range(rounds):
         for name, fn in legs.items():
@@ -107,4 +113,10 @@ if __name__ == "__main__":
         rows, _, cols = args[i + 1].partition("x")
         locates.append((int(rows), int(cols)))
         del args[i:i + 2]
-    main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates)
+    syncs = []
+    while "--sync" in args:
+        i = args.index("--sync")
+        g, _, r = args[i + 1].partition("/")
+        syncs.append((int(g), int(r or 2)))
+        del args[i:i + 2]
+    main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs)

@@ -227,7 +227,7 @@ int tdoa_debug_select_peaks(tdoa_ctx *ctx, const float *surface, int n_lags, int
     return TDOA_OK;
 }
 
-// The caller's words and sqrt(n_w) for each of n_sets sets, for the two entries below, in buffers that are theirs alone
+// The caller's words and sqrt(n_w) for each of n_sets sets, for the three entries below, in buffers that are theirs alone
 // (ctx->debug_q, ctx->debug_roots): the stack's sums and a cached step graph's buffers stay as they are.  (A call that has to
 // allocate or grow one of its buffers moves alloc_gen like every ensure(): the next step captures its graph again, with the
 // same results.)  *roots lives until the caller has synchronised.
@@ -276,6 +276,7 @@ int tdoa_debug_locate_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_
     if (!q || n_sets < 1 || n_sets > kLocateMaxSets || n_w < 1 || n_stations < 2 || n_stations > kLocateMaxStations)
         return fail(ctx, TDOA_ERR_INVALID, "q is NULL, n_sets outside 1 .. 65535, n_w < 1 or n_stations outside 2 .. 64");
     if (const char *bad = check_locate_table(ctx, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
+    if (const char *bad = check_locate_clock(ctx, n_sets, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
     const LocateGeom g = locate_geom(ctx, min_separation);
     if (locate_overflows(g.P, n_w)) return fail(ctx, TDOA_ERR_UNSUPPORTED, "pairs x n_w > 2^17: a cell's score could overflow");
     std::vector<double> roots;
@@ -283,6 +284,28 @@ int tdoa_debug_locate_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_
     if ((rc = ensure_locate(ctx, n_sets, g))) return rc;
     launch_locate(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), n_sets, g);
     return download_and_wait(ctx, [&] { return download_locate(ctx, n_sets, g, loc, lags, corr, map); });
+}
+
+// the clock search's kernels (sync_api.inc) on the caller's words: n_sets sets of P = S (S-1) / 2 rows of 2 max_lag - 1 int64,
+// every set a stack of n_w windows.  Needs the context for max_lag and the device only.
+int tdoa_debug_sync_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int gate, int rounds,
+                           const int32_t *ref_delay, const int32_t *centre, tdoa_sync *sync, int32_t *clock, int32_t *lags,
+                           double *corr)
+{
+    int rc;
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (const char *bad = check_sync_args(gate, rounds, ref_delay, sync)) return fail(ctx, TDOA_ERR_INVALID, bad);
+    if (!q || n_sets < 1 || n_sets > kLocateMaxSets || n_w < 1 || n_stations < 2 || n_stations > kSyncMaxStations)
+        return fail(ctx, TDOA_ERR_INVALID, "q is NULL, n_sets outside 1 .. 65535, n_w < 1 or n_stations outside 2 .. 64");
+    const SyncGeom g = sync_geom(n_stations, ctx->prm.max_lag, gate, rounds);
+    if (locate_overflows(g.P, n_w)) return fail(ctx, TDOA_ERR_UNSUPPORTED, "pairs x n_w > 2^17: the objective could overflow");
+    std::vector<double> roots;
+    const std::vector<int32_t> in = sync_inputs(ref_delay, centre, n_stations);
+    if ((rc = upload_debug_q(ctx, q, (size_t)n_sets * g.P * g.n, n_sets, n_w, &roots))) return rc;
+    if ((rc = ensure_sync(ctx, n_sets, g))) return rc;
+    if ((rc = upload_sync_in(ctx, in))) return rc;
+    launch_sync(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), n_sets, g);
+    return download_and_wait(ctx, [&] { return download_sync(ctx, n_sets, g, sync, clock, lags, corr); });
 }
 
 #ifdef TDOA_STG_TIMING

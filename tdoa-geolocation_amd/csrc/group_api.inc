@@ -368,6 +368,37 @@ int tdoa_group_process_locate(tdoa_group *g, int windows_per_stack, int min_sepa
     return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
 }
 
+// the clocks to every member: each keeps its own copy, member 0's is the one a group of several searches with
+int tdoa_group_locate_set_clock(tdoa_group *g, const int32_t *clock, int n_stacks, int n_stations)
+{
+    if (!g) return TDOA_ERR_INVALID;
+    for (size_t m = 0; m < g->members.size(); m++)
+        if (const int rc = tdoa_locate_set_clock(g->members[m], clock, n_stacks, n_stations)) return member_fail(g, (int)m, rc);
+    return TDOA_OK;
+}
+
+// tdoa_process_sync over the members: their shares of the fixed-point sums as in tdoa_group_process_stacked, added on the
+// host; member 0 searches the merged Q with the kernels a single context's call ends with.
+int tdoa_group_process_sync(tdoa_group *g, int windows_per_stack, int gate, int rounds, const int32_t *ref_delay, const int32_t *centre,
+                            tdoa_sync *sync_host, int32_t *clock_host, int32_t *lags_host, double *corr_host)
+{
+    if (!g) return TDOA_ERR_INVALID;
+    if (windows_per_stack < 0) return group_fail(g, TDOA_ERR_INVALID, "windows_per_stack < 0");
+    if (const char *bad = check_sync_args(gate, rounds, ref_delay, sync_host)) return group_fail(g, TDOA_ERR_INVALID, bad);
+    const int world = (int)g->members.size();
+    tdoa_ctx *c0 = g->members[0];
+    if (world == 1) {                        // no merge: the member's call writes the outputs
+        const int rc = tdoa_process_sync(c0, windows_per_stack, gate, rounds, ref_delay, centre, sync_host, clock_host, lags_host, corr_host);
+        return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
+    }
+    const char *what = nullptr;
+    if (const int rc = check_sync_state(c0, windows_per_stack, &what)) return group_fail(g, rc, member_name(0, c0->device) + what);
+    const int64_t *sum = nullptr;
+    if (const int rc = group_merged_q(g, windows_per_stack, &sum)) return rc;
+    const int rc = sync_from_host(c0, sum, windows_per_stack, gate, rounds, ref_delay, centre, sync_host, clock_host, lags_host, corr_host);
+    return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
+}
+
 int tdoa_debug_owned_runs(size_t total_samples, size_t n_min, int64_t window_len, int rank, int world, size_t *first,
                           size_t *count, int max_runs, int *n_runs)
 {

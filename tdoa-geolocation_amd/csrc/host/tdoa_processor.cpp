@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -130,6 +130,12 @@ int main(int argc, char **argv)
     bool locate = false;
     int locate_rows = 0, locate_cols = 0;
     double locate_km = 0.0;
+    // --sync=LAT,LON,HEIGHT[/G[/R]] (with --stack --locate, whole-block stacks): the reference emitter's position; the stations'
+    // clocks are searched on the two reference blocks within G samples, R sweeps (tdoa_process_sync), and the locate runs with
+    // them -- blocks 1 and 3 with their own clocks, block 2 with their midpoint (tdoa_locate_set_clock)
+    bool sync = false;
+    double sync_lat = 0, sync_lon = 0, sync_h = 0;
+    int sync_g = 128, sync_r = 2;
     double gate = 120.0;     // samples; PROJECT_NOTES.md:29-32 (max |TDOA| about 57 us = 114 samples at 2 Msps)
     tdoa_params prm;
     tdoa_default_params(&prm);
@@ -161,6 +167,14 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
+        else if (a.rfind("--sync=", 0) == 0) {
+            sync = true;
+            const int got = std::sscanf(a.c_str() + 7, "%lf,%lf,%lf/%d/%d", &sync_lat, &sync_lon, &sync_h, &sync_g, &sync_r);
+            if (got < 3 || sync_g < 0 || sync_g > 1023 || sync_r < 0 || sync_r > 16) {
+                std::fprintf(stderr, "--sync=LAT,LON,HEIGHT[/G[/R]] with G in 0 .. 1023 and R in 0 .. 16, e.g. --sync=41.257,-95.955,349/128/2\n");
+                return 1;
+            }
+        }
         else if (a == "--gate" && i + 1 < argc) gate = std::atof(argv[++i]);
         else if (a == "--device" && i + 1 < argc) prm.device = std::atoi(argv[++i]);
         else if (a == "--window" && i + 1 < argc) prm.window_len = std::atoll(argv[++i]);
@@ -173,6 +187,8 @@ int main(int argc, char **argv)
     if (track && !stack) { std::fprintf(stderr, "--track needs --stack\n"); return 1; }
     if (closure && !stack) { std::fprintf(stderr, "--closure needs --stack\n"); return 1; }
     if (locate && !stack) { std::fprintf(stderr, "--locate needs --stack\n"); return 1; }
+    if (sync && !locate) { std::fprintf(stderr, "--sync needs --stack --locate\n"); return 1; }
+    if (sync && stack_m != 0) { std::fprintf(stderr, "--sync needs whole-block stacks: --stack without =WINDOWS\n"); return 1; }
     if (pos.size() < 4) {                                     // processor.go:1048-1052
         usage(argv[0]);
         return 1;
@@ -341,6 +357,8 @@ int main(int argc, char **argv)
         std::vector<int32_t> tlags;
         std::vector<tdoa_closure> clos;          // --closure: one record per stack and station triple (tdoa_process_closure)
         std::vector<tdoa_location> locs;         // --locate: one record per stack (tdoa_process_locate)
+        std::vector<tdoa_sync> syncs;            // --sync: one record and S clocks per block (tdoa_process_sync)
+        std::vector<int32_t> clocks;
         double grid_lat0 = 0, grid_lon0 = 0, grid_dlat = 0, grid_dlon = 0;
         if (stack) {
             if ((rc = tdoa_num_stacks(ctx, stack_m, &spb, &n_stacks))) return die("tdoa_num_stacks", rc);
@@ -387,6 +405,24 @@ int main(int argc, char **argv)
                     return die("tdoa_locate_grid_table", rc);
                 if ((rc = tdoa_locate_set_table(ctx, table.data(), locate_rows * locate_cols, locate_cols, S)))
                     return die("tdoa_locate_set_table", rc);
+                if (sync) {
+                    // the known emitter's delays: the table of its one cell; then the clocks of every block (the blocks are
+                    // the stacks here), and the locate's clock table from those of the two reference blocks
+                    std::vector<int32_t> ref((size_t)S), table16((size_t)n_stacks * S);
+                    if ((rc = tdoa_locate_grid_table(lle.data(), S, sync_lat, sync_lon, 0.0, 0.0, 1, 1, sync_h, prm.sample_rate, ref.data())))
+                        return die("tdoa_locate_grid_table", rc);
+                    syncs.resize((size_t)n_stacks);
+                    clocks.resize((size_t)n_stacks * S);
+                    if ((rc = tdoa_process_sync(ctx, stack_m, sync_g, sync_r, ref.data(), nullptr, syncs.data(), clocks.data(), nullptr, nullptr)))
+                        return die("tdoa_process_sync", rc);
+                    for (int s = 0; s < S; s++) {
+                        const int32_t before = clocks[s], after = clocks[2 * (size_t)S + s];
+                        table16[s] = TDOA_DELAY_UNIT * before;
+                        table16[(size_t)S + s] = TDOA_DELAY_UNIT / 2 * (before + after);
+                        table16[2 * (size_t)S + s] = TDOA_DELAY_UNIT * after;
+                    }
+                    if ((rc = tdoa_locate_set_clock(ctx, table16.data(), n_stacks, S))) return die("tdoa_locate_set_clock", rc);
+                }
                 locs.resize((size_t)n_stacks);
                 if ((rc = tdoa_process_locate(ctx, stack_m, 1, locs.data(), nullptr, nullptr, nullptr))) return die("tdoa_process_locate", rc);
             }
@@ -468,6 +504,12 @@ int main(int argc, char **argv)
                                     (int)c.lag_ij, (int)c.lag_ik, (int)c.lag_jk, (int)c.residual, c.score,
                                     (double)c.own_q / 4294967296.0 / root, c.runner_up);
                     }
+        }
+        // --sync: the clocks of the two reference blocks, a line each
+        for (size_t sid = 0; sid < syncs.size(); sid += 2) {
+            std::printf("SYNC block %d: clock=", (int)sid + 1);
+            for (int s = 0; s < S; s++) std::printf("%s%d", s ? "," : "", (int)clocks[sid * S + s]);
+            std::printf(" moved=%d score=%.6f\n", (int)syncs[sid].moved, syncs[sid].score);
         }
         // --locate: the best cell of the grid, a line per stack
         for (size_t sid = 0; sid < locs.size(); sid++) {

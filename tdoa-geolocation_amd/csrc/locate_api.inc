@@ -1,4 +1,4 @@
-// locate_api.inc -- the delay-table search, host side: the table a context keeps, the search's buffers, the kernels' launches
+// locate_api.inc -- the delay-table search, host side: the table and the station clocks a context keeps, the search's buffers, the kernels' launches
 // (shared by a context's own step, step_products.inc, the group's merged sum and tdoa_debug_locate_from_q), the host-only
 // grid table.  Included by tdoa_mi355x.hip after closure_api.inc and before step_products.inc.
 
@@ -34,6 +34,15 @@ static const char *check_locate_table(const tdoa_ctx *ctx, int S)
     return nullptr;
 }
 
+// what a search on n_sets stacks of S stations needs of the context's clock table, when there is one
+static const char *check_locate_clock(const tdoa_ctx *ctx, int n_sets, int S)
+{
+    if (ctx->clock_stacks == 0) return nullptr;
+    if (ctx->clock_stacks != n_sets) return "the clock table's n_stacks differs from the stacks searched";
+    if (ctx->clock_stations != S) return "the clock table's n_stations differs from the stations searched";
+    return nullptr;
+}
+
 // every sum of P magnitudes of at most n_w 2^45 stays below 2^62
 static bool locate_overflows(int P, long long n_w) { return (long long)P * n_w > (1ll << 17); }
 
@@ -63,6 +72,36 @@ int tdoa_locate_set_table(tdoa_ctx *ctx, const int32_t *delay, int n_cells, int 
     return TDOA_OK;
 }
 
+int tdoa_locate_set_clock(tdoa_ctx *ctx, const int32_t *clock, int n_stacks, int n_stations)
+{
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (!clock || n_stacks == 0) {           // forget the clocks (the buffer stays: a cached step graph may still name it)
+        ctx->clock_stacks = ctx->clock_stations = 0;
+        return TDOA_OK;
+    }
+    if (n_stacks < 1 || n_stacks > kLocateMaxSets || n_stations < 2 || n_stations > kLocateMaxStations)
+        return fail(ctx, TDOA_ERR_INVALID, "n_stacks outside 1 .. 65535 or n_stations outside 2 .. 64");
+    int rc;
+    if ((rc = check_ctx(ctx))) return rc;
+    const int S = n_stations, P = S * (S - 1) / 2;
+    std::vector<long long> cd((size_t)n_stacks * P);           // per (stack, pair) clock[j] - clock[i]: what the kernels add to d
+    for (int sid = 0; sid < n_stacks; sid++) {
+        const int32_t *k = clock + (size_t)sid * S;
+        long long *row = cd.data() + (size_t)sid * P;
+        for (int i = 0; i < S; i++)
+            for (int j = i + 1; j < S; j++) *row++ = (long long)k[j] - (long long)k[i];
+    }
+    if ((rc = ensure(ctx, ctx->locate_clock, sizeof(long long) * cd.size()))) {
+        ctx->clock_stacks = ctx->clock_stations = 0;
+        return rc;
+    }
+    ctx->clock_stacks = n_stacks;
+    ctx->clock_stations = n_stations;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->locate_clock.p, cd.data(), sizeof(long long) * cd.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // cd goes out of scope
+    return TDOA_OK;
+}
+
 // the buffers of the search for n_sets stacks: the map, the tiles' candidates, the locations' cells, the records and the
 // best cells' lags and correlations
 static int ensure_locate(tdoa_ctx *ctx, size_t n_sets, const LocateGeom &g)
@@ -82,12 +121,14 @@ static int ensure_locate(tdoa_ctx *ctx, size_t n_sets, const LocateGeom &g)
 }
 
 // Q [n_sets][P][n] -> the records in ctx->locate_out, the map, lags and correlations: the one place the search is launched.
-// Kernel launches only (the step graph captures them).
+// With a clock table (its shape checked by the caller: n_sets stacks of g.S stations) the scores' clock instantiation runs
+// and the finish adds the same differences.  Kernel launches only (the step graph captures them).
 static void launch_locate(tdoa_ctx *ctx, const long long *Q, const double *roots, int n_sets, const LocateGeom &g)
 {
     hipStream_t st = ctx->stream;
     const dim3 grid((unsigned)g.tiles, (unsigned)n_sets), one((unsigned)n_sets);
     auto *table = ctx->locate_table.as<const int32_t>();
+    const long long *cdiff = ctx->clock_stacks ? ctx->locate_clock.as<const long long>() : nullptr;
     auto *map = ctx->locate_map.as<long long>();
     auto *part = ctx->locate_part.as<ClosureCand>();
     auto *best = ctx->locate_best.as<int32_t>();
@@ -95,18 +136,25 @@ static void launch_locate(tdoa_ctx *ctx, const long long *Q, const double *roots
     auto *lags = ctx->locate_lags.as<int32_t>();
     auto *corr = ctx->locate_corr.as<double>();
     switch (g.S <= kLocateRegStations ? g.S : 0) {
-#define TDOA_LOCATE_CASE(s) case s: hipLaunchKernelGGL(k_locate_scores<s>, grid, dim3(kLocateThreads), 0, st, Q, g, table, map, part); break;
+#define TDOA_LOCATE_CASE(s)                                                                                                      \
+    case s:                                                                                                                      \
+        if (cdiff)                                                                                                               \
+            hipLaunchKernelGGL((k_locate_scores<s, true>), grid, dim3(kLocateThreads), 0, st, Q, g, table, cdiff, map, part);    \
+        else                                                                                                                     \
+            hipLaunchKernelGGL((k_locate_scores<s, false>), grid, dim3(kLocateThreads), 0, st, Q, g, table, cdiff, map, part);   \
+        break;
     TDOA_LOCATE_CASE(2) TDOA_LOCATE_CASE(3) TDOA_LOCATE_CASE(4) TDOA_LOCATE_CASE(5) TDOA_LOCATE_CASE(6) TDOA_LOCATE_CASE(7)
     TDOA_LOCATE_CASE(8) TDOA_LOCATE_CASE(9) TDOA_LOCATE_CASE(10) TDOA_LOCATE_CASE(11) TDOA_LOCATE_CASE(12) TDOA_LOCATE_CASE(13)
     TDOA_LOCATE_CASE(14) TDOA_LOCATE_CASE(15) TDOA_LOCATE_CASE(16)
-    default: TDOA_LOCATE_CASE(0)
+    default:
+        TDOA_LOCATE_CASE(0)
     }
 #undef TDOA_LOCATE_CASE
-    hipLaunchKernelGGL(k_locate_finish, one, dim3(kLocateThreads), 0, st, Q, g, table, roots, static_cast<const ClosureCand *>(part), 0,
+    hipLaunchKernelGGL(k_locate_finish, one, dim3(kLocateThreads), 0, st, Q, g, table, cdiff, roots, static_cast<const ClosureCand *>(part), 0,
                        best, out, lags, corr);
     hipLaunchKernelGGL(k_locate_runner, grid, dim3(kLocateThreads), 0, st, static_cast<const long long *>(map), g,
                        static_cast<const int32_t *>(best), part);
-    hipLaunchKernelGGL(k_locate_finish, one, dim3(kLocateThreads), 0, st, Q, g, table, roots, static_cast<const ClosureCand *>(part), 1,
+    hipLaunchKernelGGL(k_locate_finish, one, dim3(kLocateThreads), 0, st, Q, g, table, cdiff, roots, static_cast<const ClosureCand *>(part), 1,
                        best, out, lags, corr);
 }
 
@@ -138,7 +186,7 @@ static int locate_from_host(tdoa_ctx *ctx, const int64_t *q_sum, int windows_per
 }
 
 // what tdoa_process_locate and the group's call refuse once the arguments are in range: the lag mode, the captures, the
-// station count, the table, the overflow bound.  *what receives the message.
+// station count, the table, the overflow bound, the clock table's shape.  *what receives the message.
 static int check_locate_state(const tdoa_ctx *ctx, int windows_per_stack, const char **what)
 {
     const auto refuse = [&](int status, const char *why) {
@@ -155,6 +203,7 @@ static int check_locate_state(const tdoa_ctx *ctx, int windows_per_stack, const 
     if (locate_overflows(S * (S - 1) / 2, stack_geom(wpb, windows_per_stack).mm))
         return refuse(TDOA_ERR_UNSUPPORTED, "pairs x stack length > 2^17: a cell's score could overflow");
     if (3ll * wpb > kLocateMaxSets) return refuse(TDOA_ERR_UNSUPPORTED, "more than 65535 stacks");
+    if (const char *bad = check_locate_clock(ctx, stack_geom(wpb, windows_per_stack).n_stacks, S)) return refuse(TDOA_ERR_STATE, bad);
     return TDOA_OK;
 }
 

@@ -7,6 +7,7 @@
 //
 // k_locate_scores   one cell per lane: its station delays from the station-major table, one lag and one 8-byte gather of Q per
 //                   pair; the scores go to the map [set][cell], the tile's best out as a two-word candidate (key = ~cell)
+//                   (a second instantiation adds the stack's clock difference of each pair: tdoa_locate_set_clock)
 // k_locate_runner   the same grid over the map: the best cell more than min_separation rows or columns from the location
 // k_locate_finish   the tiles' candidates -> the record, and the lags and signed correlations of the best cell; after the
 //                   runner-up's pass: runner_q, runner_up, runner_cell
@@ -43,18 +44,19 @@ struct LocateGeom {
 };
 
 // lag_p(c) = sgn(d) ((2 |d| + 16) div 32), d = t[c][j] - t[c][i] in 64 bits: the nearest integer to d / 16, halves away from
-// zero
-__device__ __forceinline__ long long locate_lag(int32_t ti, int32_t tj)
+// zero.  With station clocks (tdoa_locate_set_clock) the stack's clock difference of the pair, cd = clock[j] - clock[i], is
+// added to d first: it is the same for every cell of a (stack, pair), so the kernels take it as one word per (set, pair).
+__device__ __forceinline__ long long locate_lag(int32_t ti, int32_t tj, long long cd = 0)
 {
-    const long long d = (long long)tj - (long long)ti;
+    const long long d = (long long)tj - (long long)ti + cd;
     const long long a = (2 * (d < 0 ? -d : d) + kLocateDelayUnit) / (2 * kLocateDelayUnit);
     return d < 0 ? -a : a;
 }
 
 // M_p at a cell's lag, 0 outside the searched range
-__device__ __forceinline__ long long locate_m(const long long *q, int32_t ti, int32_t tj, const LocateGeom &g)
+__device__ __forceinline__ long long locate_m(const long long *q, int32_t ti, int32_t tj, const LocateGeom &g, long long cd = 0)
 {
-    const long long idx = locate_lag(ti, tj) - g.lag_lo;
+    const long long idx = locate_lag(ti, tj, cd) - g.lag_lo;
     if (idx < 0 || idx >= g.n) return 0;
     const long long v = q[idx];
     return v < 0 ? -v : v;
@@ -62,10 +64,13 @@ __device__ __forceinline__ long long locate_m(const long long *q, int32_t ti, in
 
 // grid (tiles, n_sets), kLocateThreads threads.  Q: [set][pair][n]; table: [station][n_cells].  S_T: the station count when
 // it is at most kLocateRegStations (the delays stay in registers, both loops unrolled), 0: any count, the delays re-read.
+// CLK: cdiff [set][pair] holds the pairs' clock differences -- the same word for the whole workgroup, so it is read through
+// the scalar cache and costs no vector register; without CLK cdiff is not read and the kernel is the clock-less one.
 // map[set][cell] = score_q(cell); partial[set * tiles + tile] = the tile's best candidate (equal scores: the smaller cell).
-template <int S_T>
+template <int S_T, bool CLK>
 __global__ __launch_bounds__(kLocateThreads) void k_locate_scores(const long long *Q, LocateGeom g, const int32_t *table,
-                                                                  long long *map, ClosureCand *partial)
+                                                                  const long long *__restrict__ cdiff, long long *map,
+                                                                  ClosureCand *partial)
 {
     __shared__ long long red_s[kLocateThreads / kWave];
     __shared__ uint32_t red_k[kLocateThreads / kWave];
@@ -77,7 +82,23 @@ __global__ __launch_bounds__(kLocateThreads) void k_locate_scores(const long lon
         const long long *q = Q + (size_t)set * g.P * g.n;
         const int32_t *tc = table + cell;
         long long s = 0;
-        if constexpr (S_T > 0) {
+        if constexpr (CLK) {
+            const long long *cd = cdiff + (size_t)set * g.P;
+            if constexpr (S_T > 0) {
+                int32_t d[S_T];
+#pragma unroll
+                for (int i = 0; i < S_T; i++) d[i] = tc[(size_t)i * g.n_cells];
+#pragma unroll
+                for (int i = 0; i < S_T; i++)
+#pragma unroll
+                    for (int j = i + 1; j < S_T; j++, q += g.n, cd++) s += locate_m(q, d[i], d[j], g, *cd);
+            } else {
+                for (int i = 0; i < g.S; i++) {
+                    const int32_t di = tc[(size_t)i * g.n_cells];
+                    for (int j = i + 1; j < g.S; j++, q += g.n, cd++) s += locate_m(q, di, tc[(size_t)j * g.n_cells], g, *cd);
+                }
+            }
+        } else if constexpr (S_T > 0) {
             int32_t d[S_T];
 #pragma unroll
             for (int i = 0; i < S_T; i++) d[i] = tc[(size_t)i * g.n_cells];
@@ -140,8 +161,10 @@ __device__ __forceinline__ void locate_pair(int p, int S, int *i, int *j)
 // pass 1 (partial now holds the runner-up's pass): runner_q, runner_up and runner_cell of a record that is not the zero
 // record, where a cell outside the location's neighbourhood exists.
 // roots[set] = sqrt(n_w).
+// cdiff: the pairs' clock differences [set][pair], nullptr: none.
 __global__ __launch_bounds__(kLocateThreads) void k_locate_finish(const long long *Q, LocateGeom g, const int32_t *table,
-                                                                  const double *roots, const ClosureCand *partial, int pass,
+                                                                  const long long *cdiff, const double *roots,
+                                                                  const ClosureCand *partial, int pass,
                                                                   int32_t *best, LocateOut *out, int32_t *lags, double *corr)
 {
     __shared__ long long red_s[kLocateThreads / kWave];
@@ -177,7 +200,9 @@ __global__ __launch_bounds__(kLocateThreads) void k_locate_finish(const long lon
         if (found) {
             int i, j;
             locate_pair(p, g.S, &i, &j);
-            const long long l = locate_lag(table[(size_t)i * g.n_cells + cell], table[(size_t)j * g.n_cells + cell]), idx = l - g.lag_lo;
+            const long long l = locate_lag(table[(size_t)i * g.n_cells + cell], table[(size_t)j * g.n_cells + cell],
+                                           cdiff ? cdiff[(size_t)set * g.P + p] : 0),
+                            idx = l - g.lag_lo;
             if (idx >= 0 && idx < g.n) {
                 lag = (int32_t)l;
                 c = stack_value(q[(size_t)p * g.n + idx], root);

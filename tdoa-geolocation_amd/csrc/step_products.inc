@@ -2,7 +2,8 @@
 // (tdoa_process_lags), the K strongest peaks per pair-window (tdoa_process_peaks), the stacked surfaces of a block's windows
 // (tdoa_process_stacked), the same stacks taken along the best of 2H+1 lag slopes (tdoa_process_stacked_drift), the best
 // delay track through a stack's windows (tdoa_process_track), one consistent lag set per station triple of a stack
-// (tdoa_process_closure), a table of candidate positions scored on all pairs' stacks (tdoa_process_locate).  Every product
+// (tdoa_process_closure), a table of candidate positions scored on all pairs' stacks (tdoa_process_locate), the stations'
+// clock offsets from a block whose emitter is known (tdoa_process_sync).  Every product
 // is a struct derived from StepProduct: the entry point fills it, process_impl calls its six hooks in this order (a product
 // overrides the ones it needs; process_impl without a product writes the peak records only):
 //   reserve   its buffers, after the step's grouping is fixed (batch_bound counts them as held, so a later call groups as
@@ -12,7 +13,7 @@
 //   refresh   data a call may change under the same key, sent every time
 //   enqueue   its kernels, after the step's decode -- unscoped launches, kernel nodes only: the step stays one chain
 //   download  its asynchronous copies out on ctx->stream
-// The products that search a stack's sums (drift, closure, locate) derive from StackProduct and call its hooks from theirs.
+// The products that search a stack's sums (drift, closure, locate, sync) derive from StackProduct and call its hooks from theirs.
 // All of them read the K5 kernels' lag arrays in ctx->surf, pair-window i of the rank at i * n_lags.
 // Included by tdoa_mi355x.hip after step_graph.inc and stacked_api.inc.
 
@@ -35,7 +36,7 @@ struct StepView {
 
 // the product of one step; the numbers are the first word a product appends to the graph key
 struct StepProduct {
-    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6, Locate = 7 };
+    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6, Locate = 7, Sync = 8 };
     virtual int reserve(const StepView &v) = 0;
     virtual void key(std::vector<uint64_t> *key) const = 0;
     virtual int upload(const StepView &) { return TDOA_OK; }
@@ -398,6 +399,7 @@ struct ClosureProduct : StackProduct {
 struct LocateProduct : StackProduct {
     int sep = 1;                             // min_separation
     int n_cells = 0, n_cols = 0;             // the shape of the context's table: in the key (the table itself is data)
+    bool clocked = false;                    // the context holds station clocks: in the key (another kernel; the clocks are data)
     tdoa_location *loc_host = nullptr;       // [stack]
     int32_t *lags_host = nullptr;            // [stack][pair]
     double *corr_host = nullptr;             // [stack][pair]
@@ -410,7 +412,7 @@ struct LocateProduct : StackProduct {
     }
     void key(std::vector<uint64_t> *key) const override
     {
-        key->insert(key->end(), {Locate, (uint64_t)m, (uint64_t)sep, (uint64_t)n_cells | ((uint64_t)n_cols << 32)});
+        key->insert(key->end(), {Locate, (uint64_t)m, (uint64_t)sep, (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked});
     }
     void enqueue(const StepView &v) const override
     {
@@ -421,6 +423,37 @@ struct LocateProduct : StackProduct {
     int download(const StepView &v) const override
     {
         return download_locate(v.ctx, layout.n_stacks, locate_geom(v.ctx, sep), loc_host, lags_host, corr_host, map_host);
+    }
+};
+
+// ---- the clock search on the stacks' sums (stack_sync.hpp, sync_api.inc) ------------------------------------------------
+// Its stack has no output of its own either.
+struct SyncProduct : StackProduct {
+    int S = 0, G = 0, R = 0;                 // stations, gate, rounds
+    std::vector<int32_t> in;                 // ref_delay and centre (sync_inputs): data, not part of the key
+    tdoa_sync *sync_host = nullptr;          // [stack]
+    int32_t *clock_host = nullptr;           // [stack][station]
+    int32_t *lags_host = nullptr;            // [stack][pair]
+    double *corr_host = nullptr;             // [stack][pair]
+
+    SyncGeom geom(const tdoa_ctx *ctx) const { return sync_geom(S, ctx->prm.max_lag, G, R); }
+    int reserve(const StepView &v) override
+    {
+        if (int rc = StackProduct::reserve(v)) return rc;
+        if (ensure_sync(v.ctx, layout.n_stacks, geom(v.ctx))) return surfaces_nomem(v, "the clock search's candidates and records", 1.0);
+        return TDOA_OK;
+    }
+    void key(std::vector<uint64_t> *key) const override { key->insert(key->end(), {Sync, (uint64_t)m, (uint64_t)G, (uint64_t)R}); }
+    int refresh(const StepView &v) override { return upload_sync_in(v.ctx, in); }
+    void enqueue(const StepView &v) const override
+    {
+        tdoa_ctx *ctx = v.ctx;
+        StackProduct::enqueue(v);
+        launch_sync(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, layout.n_stacks, v.P).roots, layout.n_stacks, geom(ctx));
+    }
+    int download(const StepView &v) const override
+    {
+        return download_sync(v.ctx, layout.n_stacks, geom(v.ctx), sync_host, clock_host, lags_host, corr_host);
     }
 };
 

@@ -40,6 +40,7 @@
 #include "stack_track.hpp"
 #include "stack_closure.hpp"
 #include "stack_locate.hpp"
+#include "stack_sync.hpp"
 
 using namespace tdoa;
 
@@ -167,9 +168,16 @@ struct tdoa_ctx {
     // the tiles' candidates [stack][tile], the locations' cells and records [stack], the best cells' lags and correlations
     // [stack][pair]
     DevBuf locate_table, locate_map, locate_part, locate_best, locate_out, locate_lags, locate_corr;
-    // tdoa_debug_closure_from_q and tdoa_debug_locate_from_q: the caller's words and sqrt(n_w) per set
+    // ... and the stacks' station clocks as the kernels take them, clock[j] - clock[i] per [stack][pair] (state:
+    // tdoa_locate_set_clock; 0 stacks: none)
+    DevBuf locate_clock;
+    // the clock search: ref_delay and centre (kSyncMaxStations words each), the start's tiles' candidates [stack][tile], the
+    // records [stack], the clocks [stack][station], the lags and correlations [stack][pair]
+    DevBuf sync_in, sync_part, sync_out, sync_clock, sync_lags, sync_corr;
+    // tdoa_debug_closure_from_q, tdoa_debug_locate_from_q and tdoa_debug_sync_from_q: the caller's words and sqrt(n_w) per set
     DevBuf debug_q, debug_roots;
     int locate_cells = 0, locate_cols = 0, locate_stations = 0;
+    int clock_stacks = 0, clock_stations = 0;
 };
 
 namespace {
@@ -179,6 +187,7 @@ static_assert(sizeof(FmStats) == sizeof(tdoa_fm_stats), "tdoa_fm_stats layout");
 static_assert(sizeof(ClosureOut) == sizeof(tdoa_closure) && sizeof(tdoa_closure) == 80, "tdoa_closure layout");
 static_assert(sizeof(LocateOut) == sizeof(tdoa_location) && sizeof(tdoa_location) == 48, "tdoa_location layout");
 static_assert(kLocateDelayUnit == TDOA_DELAY_UNIT, "the table's unit");
+static_assert(sizeof(SyncOut) == sizeof(tdoa_sync) && sizeof(tdoa_sync) == 32, "tdoa_sync layout");
 
 int fail(tdoa_ctx *ctx, int status, const char *what, hipError_t e = hipSuccess)
 {
@@ -362,6 +371,7 @@ int check_selection(tdoa_ctx *ctx, int k, int min_separation, const void *out)
 #include "stacked_api.inc"
 #include "closure_api.inc"
 #include "locate_api.inc"
+#include "sync_api.inc"
 #include "step_products.inc"
 
 // ===========================================================================
@@ -520,7 +530,8 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->track_t, &ctx->track_d, &ctx->track_score, &ctx->track_lags, &ctx->track_values, &ctx->closure_centre,
                       &ctx->closure_part, &ctx->closure_best, &ctx->closure_out, &ctx->locate_table,
                       &ctx->locate_map, &ctx->locate_part, &ctx->locate_best, &ctx->locate_out, &ctx->locate_lags, &ctx->locate_corr,
-                      &ctx->debug_q, &ctx->debug_roots};
+                      &ctx->locate_clock, &ctx->sync_in, &ctx->sync_part, &ctx->sync_out, &ctx->sync_clock, &ctx->sync_lags,
+                      &ctx->sync_corr, &ctx->debug_q, &ctx->debug_roots};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1117,6 +1128,28 @@ int tdoa_process_locate(tdoa_ctx *ctx, int windows_per_stack, int min_separation
     prod.lags_host = lags_host;
     prod.corr_host = corr_host;
     prod.map_host = map_host;
+    prod.clocked = ctx->clock_stacks != 0;
+    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
+}
+
+int tdoa_process_sync(tdoa_ctx *ctx, int windows_per_stack, int gate, int rounds, const int32_t *ref_delay, const int32_t *centre,
+                      tdoa_sync *sync_host, int32_t *clock_host, int32_t *lags_host, double *corr_host)
+{
+    if (int rc = refuse_stacked(ctx, windows_per_stack, check_sync_args(gate, rounds, ref_delay, sync_host),
+                                "the clock search with TDOA_LAGS_GO", true))
+        return rc;
+    const char *what = nullptr;              // (the station count, the overflow bound: shared with the group's call)
+    if (const int rc = check_sync_state(ctx, windows_per_stack, &what)) return fail(ctx, rc, what);
+    SyncProduct prod;
+    fill_stack(&prod, windows_per_stack);
+    prod.S = (int)ctx->caps.size();
+    prod.G = gate;
+    prod.R = rounds;
+    prod.in = sync_inputs(ref_delay, centre, prod.S);
+    prod.sync_host = sync_host;
+    prod.clock_host = clock_host;
+    prod.lags_host = lags_host;
+    prod.corr_host = corr_host;
     return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
 }
 

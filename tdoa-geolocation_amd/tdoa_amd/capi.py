@@ -52,6 +52,8 @@ CLOSURE_DTYPE = np.dtype([("lag_ij", np.int32), ("lag_ik", np.int32), ("lag_jk",
 LOCATION_DTYPE = np.dtype([("cell", np.int32), ("runner_cell", np.int32), ("pairs_in", np.int32), ("reserved", np.int32),
                            ("score_q", np.int64), ("runner_q", np.int64),
                            ("score", np.float64), ("runner_up", np.float64)])      # tdoa_location
+SYNC_DTYPE = np.dtype([("moved", np.int32), ("pairs_in", np.int32), ("score_q", np.int64), ("start_q", np.int64),
+                       ("score", np.float64)])      # tdoa_sync
 FINE_DTYPE = np.dtype([("delay", np.float64), ("frac", np.float32), ("y", np.float32, (3,)), ("plausible", np.int32),
                        ("reserved", np.int32)])
 
@@ -105,6 +107,8 @@ SYMBOLS = [
     "tdoa_num_triples", "tdoa_process_closure", "tdoa_group_process_closure", "tdoa_debug_closure_from_q",
     "tdoa_locate_set_table", "tdoa_process_locate", "tdoa_debug_locate_from_q", "tdoa_locate_grid_table",
     "tdoa_group_locate_set_table", "tdoa_group_process_locate",
+    "tdoa_locate_set_clock", "tdoa_group_locate_set_clock", "tdoa_process_sync", "tdoa_debug_sync_from_q",
+    "tdoa_group_process_sync",
 ]
 
 _lib = None
@@ -226,6 +230,11 @@ def load(build_if_missing=True):
     L.tdoa_debug_locate_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p, dp, i64p]
     L.tdoa_locate_grid_table.argtypes = [dp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
                                          C.c_double, C.c_double, i32p]
+    L.tdoa_locate_set_clock.argtypes = [vp, i32p, C.c_int, C.c_int]
+    L.tdoa_group_locate_set_clock.argtypes = [vp, i32p, C.c_int, C.c_int]
+    L.tdoa_process_sync.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, vp, i32p, i32p, dp]
+    L.tdoa_group_process_sync.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, vp, i32p, i32p, dp]
+    L.tdoa_debug_sync_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, vp, i32p, i32p, dp]
     L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
                                         C.POINTER(C.c_int)]
     _lib = L
@@ -644,6 +653,38 @@ class Context:
                                                    int(min_separation), *_locate_ptrs(out)))
         return out
 
+    def locate_set_clock(self, clock):
+        """tdoa_locate_set_clock: clock [n_stacks][n_stations] int32 station clocks in units of 1/16 sample, one row per stack
+        of the searches that follow.  clock None: forget them.  Kept on the device until replaced"""
+        self._chk(self._L.tdoa_locate_set_clock(self._h, *_clock(clock)))
+
+    def process_sync(self, ref_delay, windows_per_stack=0, gate=0, rounds=0, centre=None):
+        """tdoa_process_sync -> {"sync": [n_stacks] SYNC_DTYPE, "clock": [n_stacks][S] int32 (samples), "lags": [n_stacks][P]
+        int32, "corr": [n_stacks][P] float64}: per stack the station clocks k_s = centre[s] + x_s, |x_s| <= gate, k_0 =
+        centre[0], that make all pairs' stacks largest at the lags the known emitter's delays ref_delay [S] (units of 1/16
+        sample) predict; a joint start, the placing and `rounds` sweeps"""
+        _, n = self.num_stacks(windows_per_stack)
+        S = self.num_stations()
+        out = _sync_outputs(n, S)
+        self._chk(self._L.tdoa_process_sync(self._h, int(windows_per_stack), int(gate), int(rounds), _ref_delay(ref_delay, S),
+                                            _centre(centre, S), *_sync_ptrs(out)))
+        return out
+
+    def sync_from_q(self, q, ref_delay, n_w=1, gate=0, rounds=0, centre=None):
+        """tdoa_debug_sync_from_q: the clock search's kernels on the caller's words q [n_sets][P][2 max_lag - 1] int64 (or
+        one set [P][2 max_lag - 1]) -> what process_sync returns, n_sets for n_stacks"""
+        q = np.ascontiguousarray(q, dtype=np.int64)
+        if q.ndim == 2:
+            q = q[None]
+        S = int(np.size(ref_delay))
+        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
+            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
+        out = _sync_outputs(q.shape[0], S)
+        self._chk(self._L.tdoa_debug_sync_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], S, int(n_w),
+                                                 int(gate), int(rounds), _ref_delay(ref_delay, S), _centre(centre, S),
+                                                 *_sync_ptrs(out)))
+        return out
+
     def fm_xcorr_peaks(self, iq1, iq2, max_lag, k, min_separation):
         """tdoa_fm_xcorr_peaks_u8 -> (peaks [k] PEAK_DTYPE, count) of one pair of windows"""
         a = np.ascontiguousarray(iq1, dtype=np.uint8)
@@ -776,6 +817,36 @@ def _table(table, n_cols):
     if t.ndim != 2:
         raise ValueError("table must be [n_cells][n_stations]")
     return t.ctypes.data_as(C.POINTER(C.c_int32)), t.shape[0], int(t.shape[0] if n_cols is None else n_cols), t.shape[1]
+
+
+def _clock(clock):
+    """(pointer, n_stacks, n_stations) of a clock table as the C ABI takes it; None: (NULL, 0, 0)"""
+    if clock is None:
+        return None, 0, 0
+    k = np.ascontiguousarray(clock, dtype=np.int32)
+    if k.ndim != 2:
+        raise ValueError("clock must be [n_stacks][n_stations]")
+    return k.ctypes.data_as(C.POINTER(C.c_int32)), k.shape[0], k.shape[1]
+
+
+def _ref_delay(ref_delay, n_stations):
+    """the known emitter's delays as the C ABI takes them: n_stations int32"""
+    r = np.ascontiguousarray(ref_delay, dtype=np.int32).reshape(-1)
+    if r.shape != (int(n_stations),):
+        raise ValueError("ref_delay must hold one delay per station")
+    return r.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _sync_outputs(n_sets, n_stations):
+    p = n_stations * (n_stations - 1) // 2
+    return {"sync": np.zeros(n_sets, dtype=SYNC_DTYPE), "clock": np.zeros((n_sets, n_stations), dtype=np.int32),
+            "lags": np.zeros((n_sets, p), dtype=np.int32), "corr": np.zeros((n_sets, p), dtype=np.float64)}
+
+
+def _sync_ptrs(out):
+    i32p = C.POINTER(C.c_int32)
+    return (out["sync"].ctypes.data_as(C.c_void_p), out["clock"].ctypes.data_as(i32p), out["lags"].ctypes.data_as(i32p),
+            _d(out["corr"]))
 
 
 def _locate_outputs(n_sets, p, n_cells, want_map):
@@ -917,6 +988,21 @@ class Group:
         _, n = m.num_stacks(windows_per_stack)
         out = _locate_outputs(n, m.num_pairs(), getattr(self, "_locate_cells", 0), want_map)
         self._chk(self._L.tdoa_group_process_locate(self._h, int(windows_per_stack), int(min_separation), *_locate_ptrs(out)))
+        return out
+
+
+    def locate_set_clock(self, clock):
+        """tdoa_group_locate_set_clock: the station clocks to every member"""
+        self._chk(self._L.tdoa_group_locate_set_clock(self._h, *_clock(clock)))
+
+    def process_sync(self, ref_delay, windows_per_stack=0, gate=0, rounds=0, centre=None):
+        """tdoa_group_process_sync -> Context.process_sync's outputs, byte-identical to a single context's"""
+        m = self.member(0)
+        _, n = m.num_stacks(windows_per_stack)
+        S = m.num_stations()
+        out = _sync_outputs(n, S)
+        self._chk(self._L.tdoa_group_process_sync(self._h, int(windows_per_stack), int(gate), int(rounds), _ref_delay(ref_delay, S),
+                                                  _centre(centre, S), *_sync_ptrs(out)))
         return out
 
 

@@ -8,7 +8,10 @@ pair (i, j), i < j in the library's order:
     score_q(c) = sum over the pairs of M_p[lag_p(c)],  M_p[l] = |Q_p[l]|, a lag outside -max_lag < l < max_lag counting 0
 
 The location is the cell with the largest score_q (equal maxima: the smaller cell); the runner-up is the largest score_q
-over the cells more than min_separation rows or columns away, row = c div n_cols, col = c mod n_cols."""
+over the cells more than min_separation rows or columns away, row = c div n_cols, col = c mod n_cols.
+
+With station clocks (tdoa_locate_set_clock: one int32 per station of the stack, in the table's unit) the difference a lag is
+made of is d = (t[c][j] - t[c][i]) + (clock[j] - clock[i]); everything else is unchanged."""
 import numpy as np
 
 from .stacking import from_fixed
@@ -24,27 +27,31 @@ WGS84_A = 6378137.0
 WGS84_F = 1.0 / 298.257223563
 
 
-def pair_lags(table):
-    """table [n_cells][S] integers -> lag_p(c) [n_cells][P] int64, pairs i < j in the library's order"""
+def pair_lags(table, clock=None):
+    """table [n_cells][S] integers, clock None or [S] integers in the table's unit -> lag_p(c) [n_cells][P] int64, pairs i < j
+    in the library's order"""
     t = np.asarray(table, dtype=np.int64)
     if t.ndim != 2 or t.shape[1] < 2:
         raise ValueError("table must be [n_cells][n_stations], n_stations >= 2")
     S = t.shape[1]
+    k = np.zeros(S, dtype=np.int64) if clock is None else np.asarray(clock, dtype=np.int64)
+    if k.shape != (S,):
+        raise ValueError("clock must hold one integer per station")
     out = np.zeros((t.shape[0], S * (S - 1) // 2), dtype=np.int64)
     p = 0
     for i in range(S):
         for j in range(i + 1, S):
-            d = t[:, j] - t[:, i]
+            d = (t[:, j] - t[:, i]) + (k[j] - k[i])
             out[:, p] = np.sign(d) * ((2 * np.abs(d) + DELAY_UNIT) // (2 * DELAY_UNIT))
             p += 1
     return out
 
 
-def locate(q_pairs, table, n_cols, max_lag, min_separation=1, n_w=1):
-    """One stack: q_pairs [P][2 max_lag - 1] int64 in the library's pair order, table [n_cells][S] ->
-    (record LOCATION_DTYPE, lags [P] int32, corr [P] float64, map [n_cells] int64)"""
+def locate(q_pairs, table, n_cols, max_lag, min_separation=1, n_w=1, clock=None):
+    """One stack: q_pairs [P][2 max_lag - 1] int64 in the library's pair order, table [n_cells][S], clock None or the stack's
+    [S] station clocks in the table's unit -> (record LOCATION_DTYPE, lags [P] int32, corr [P] float64, map [n_cells] int64)"""
     ml, sep, n_cols = int(max_lag), int(min_separation), int(n_cols)
-    lag = pair_lags(table)
+    lag = pair_lags(table, clock)
     n_cells, P = lag.shape
     q = np.asarray(q_pairs, dtype=np.int64)
     if q.shape != (P, 2 * ml - 1):
@@ -74,12 +81,15 @@ def locate(q_pairs, table, n_cols, max_lag, min_separation=1, n_w=1):
     return rec, lags, corr, score
 
 
-def locate_stacks(q, table, n_cols, max_lag, min_separation=1, n_w=1):
+def locate_stacks(q, table, n_cols, max_lag, min_separation=1, n_w=1, clock=None):
     """q [n_sets][P][2 max_lag - 1] -> (records [n_sets], lags [n_sets][P], corr [n_sets][P], map [n_sets][n_cells]);
-    n_w a number or one per set"""
+    n_w a number or one per set; clock None or [n_sets][S]"""
     q = np.asarray(q, dtype=np.int64)
     n = np.broadcast_to(np.asarray(n_w), (q.shape[0],))
-    out = [locate(q[s], table, n_cols, max_lag, min_separation, int(n[s])) for s in range(q.shape[0])]
+    if clock is not None and np.shape(clock)[0] != q.shape[0]:
+        raise ValueError("clock must hold one row per set")
+    out = [locate(q[s], table, n_cols, max_lag, min_separation, int(n[s]), None if clock is None else clock[s])
+           for s in range(q.shape[0])]
     return tuple(np.stack([o[k] for o in out]) for k in range(4))
 
 
