@@ -267,6 +267,32 @@ func (g *gpuCorrelator) ProcessLocate(windowsPerStack, minSeparation int) (loc [
 	return loc, lags, corr, nil
 }
 
+// ProcessLocateTrack follows an emitter through the stacks of every block on the delay-table search's maps (the header's
+// "cell tracks"): per block one cell per stack, consecutive cells at most maxStep rows and columns apart, with the largest
+// summed score, and the runner-up.  cells and own are [block][stacks per block] (the track's cell in every stack and that
+// stack's own score there), lags and corr [stack][pair] at the track's cell, each row what tdoa_solve_surface takes.
+func (g *gpuCorrelator) ProcessLocateTrack(windowsPerStack, maxStep, minSeparation int) (track []C.tdoa_cell_track, cells []int32, own []int64, lags []int32, corr []float64, err error) {
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, nil, nil, nil, nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs := int(C.tdoa_num_pairs(g.ctx))
+	if int(total)*pairs == 0 {
+		return nil, nil, nil, nil, nil, fmt.Errorf("tdoa_process_locate_track: no stacks or fewer than two stations")
+	}
+	track = make([]C.tdoa_cell_track, int(total)/int(perBlock))
+	cells = make([]int32, int(total))
+	own = make([]int64, int(total))
+	lags = make([]int32, int(total)*pairs)
+	corr = make([]float64, int(total)*pairs)
+	if rc := C.tdoa_process_locate_track(g.ctx, C.int(windowsPerStack), C.int(maxStep), C.int(minSeparation), &track[0],
+		(*C.int32_t)(unsafe.Pointer(&cells[0])), (*C.int64_t)(unsafe.Pointer(&own[0])), (*C.int32_t)(unsafe.Pointer(&lags[0])),
+		(*C.double)(unsafe.Pointer(&corr[0])), nil); rc != C.TDOA_OK {
+		return nil, nil, nil, nil, nil, fmt.Errorf("tdoa_process_locate_track: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return track, cells, own, lags, corr, nil
+}
+
 // LocateSetClock hands the context the stations' clocks for the delay-table search, [nStacks][nStations] in units of 1/16
 // sample (nil: forget them): stack sid's lags are taken from (t[c][j] - t[c][i]) + (clock[sid][j] - clock[sid][i]).  One row per
 // stack of the searches that follow; ProcessSync's clocks times 16, or 8*(before + after) for the block between two
@@ -445,6 +471,31 @@ func (g *Group) ProcessLocate(windowsPerStack, minSeparation int) (loc []C.tdoa_
 		return nil, nil, nil, fmt.Errorf("tdoa_group_process_locate: %s", C.GoString(C.tdoa_group_last_error(g.g)))
 	}
 	return loc, lags, corr, nil
+}
+
+// ProcessLocateTrack is gpuCorrelator.ProcessLocateTrack over the group: the members' fixed-point partial sums are added on
+// the host and searched on member 0, the same bytes one context returns.
+func (g *Group) ProcessLocateTrack(windowsPerStack, maxStep, minSeparation int) (track []C.tdoa_cell_track, cells []int32, own []int64, lags []int32, corr []float64, err error) {
+	m := C.tdoa_group_member(g.g, 0)
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(m, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, nil, nil, nil, nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs := int(C.tdoa_num_pairs(m))
+	if int(total)*pairs == 0 {
+		return nil, nil, nil, nil, nil, fmt.Errorf("tdoa_group_process_locate_track: no stacks or fewer than two stations")
+	}
+	track = make([]C.tdoa_cell_track, int(total)/int(perBlock))
+	cells = make([]int32, int(total))
+	own = make([]int64, int(total))
+	lags = make([]int32, int(total)*pairs)
+	corr = make([]float64, int(total)*pairs)
+	if rc := C.tdoa_group_process_locate_track(g.g, C.int(windowsPerStack), C.int(maxStep), C.int(minSeparation), &track[0],
+		(*C.int32_t)(unsafe.Pointer(&cells[0])), (*C.int64_t)(unsafe.Pointer(&own[0])), (*C.int32_t)(unsafe.Pointer(&lags[0])),
+		(*C.double)(unsafe.Pointer(&corr[0])), nil); rc != C.TDOA_OK {
+		return nil, nil, nil, nil, nil, fmt.Errorf("tdoa_group_process_locate_track: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return track, cells, own, lags, corr, nil
 }
 
 // LocateSetClock hands every member the stations' clocks (gpuCorrelator.LocateSetClock).

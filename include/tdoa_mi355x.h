@@ -581,6 +581,72 @@ int tdoa_debug_sync_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_st
                            const int32_t *ref_delay, const int32_t *centre, tdoa_sync *sync, int32_t *clock, int32_t *lags,
                            double *corr);
 
+/* Cell tracks: follow an emitter from stack to stack through the delay-table search's maps.  tdoa_process_locate locates
+ * every stack alone.  Stations with free-running clocks give every stack of a target block its own clock row, so the block's
+ * windows cannot be summed lag by lag; their maps can be added cell by cell, because every map is in the emitter's
+ * coordinates with that stack's clocks applied.  A position that moves between stacks (a vehicle, residual clock error) is
+ * the 2-D analogue of tdoa_process_track's lag, and the same recurrence answers it.
+ * Stacks, windows_per_stack, n_w, the table, the clocks and score_q(sid, c) are exactly tdoa_process_locate's.
+ *   A track spans the stacks of one block: block b has positions j = 0 .. L-1, L = stacks_per_block (tdoa_num_stacks),
+ *     stack sid = b L + j.  n_tracks = n_stacks_total / L.  s_j[c] = score_q(b L + j, c), with clocks when a clock table is set.
+ *   Cells have row = c div n_cols and col = c mod n_cols.  A neighbour (row + dr, col + dc) exists when row + dr >= 0,
+ *     0 <= col + dc < n_cols and its index is < n_cells (the last row may be short; n_cols = n_cells is a list, where tracks
+ *     move along the index).
+ *   J = max_step, 0 <= J <= 16.  The recurrence runs from the last position back to the first:
+ *     T_{L-1}[c] = s_{L-1}[c]
+ *     T_j[c]     = s_j[c] + max over |dr| <= J, |dc| <= J, neighbour exists, of T_{j+1}[neighbour]
+ *     D_j[c]     = the (dr, dc) of that maximum
+ *   Ties in D_j: the smaller rank(dr), then the smaller rank(dc), rank(x) = 2|x| - (x > 0) as in the clock search.  This is
+ *     what a row maximum followed by a column maximum produces.  (0, 0) always exists.
+ *   L_0 is the cell with the largest T_0; among equal maxima the smaller cell wins, which is the location's rule.
+ *     L_{j+1} = L_j + D_j[L_j].
+ *   If max T_0 = 0, the zero record is returned and every per-position output is 0.
+ *   The runner-up is the largest T_0 over cells with max(|row - row_0|, |col - col_0|) > min_separation from L_0; ties and
+ *     the case that there is none are as in tdoa_process_locate.
+ *   There is no polarity: scores are sums of magnitudes.
+ *   Overflow: the call returns TDOA_ERR_UNSUPPORTED when P * windows_per_block > 2^17; a track's sum is then below 2^62 by
+ *     the argument tdoa_process_locate uses per stack.
+ * Identities (held by the tests):
+ *   L = 1 (windows_per_stack = 0): cell, runner_cell, score_q, runner_q, score, runner_up, lags, corr and total are
+ *     tdoa_process_locate's bytes; total is its map.
+ *   J = 0: total = the sum over j of the stacks' maps, word for word.
+ *   score_q = total[cell] = the sum over j of own[j].
+ *   Consecutive cells are at most J rows and columns apart.
+ * The record, 48 bytes, no padding: */
+typedef struct {
+    int32_t cell, runner_cell;   /* L_0; the runner-up's cell */
+    int32_t positions, steps;    /* L; the number of positions after which the track moves to another cell */
+    int64_t score_q, runner_q;   /* max T_0; the runner-up's T_0 */
+    double  score, runner_up;    /* (double)x_q * 2^-32 / sqrt(N_w), N_w = the windows of the track (L = 1: the location's scale) */
+} tdoa_cell_track;
+
+/* Runs inside the step graph, behind the stack's accumulation and the delay-table search: one launch per position
+ * j = L-2 .. 0 of the recurrence's kernel, then the best cell, the walk and the runner-up's pass over T_0.
+ * (windows_per_stack, max_step, min_separation, n_cells, n_cols, whether a clock table is present) are part of the graph's
+ * key; the table and the clocks are data.  Every position's row of lags_host / corr_host can go to tdoa_solve_surface.
+ * tdoa_group_process_locate_track is the group form.
+ * TDOA_ERR_INVALID: a NULL context (checked before anything needs a device), a NULL track_host, windows_per_stack < 0,
+ * max_step outside 0 .. 16, min_separation < 1.  TDOA_ERR_STATE: no captures, no table, or a table or clock table whose
+ * shape does not match.  TDOA_ERR_UNSUPPORTED: TDOA_LAGS_GO, fewer than 2 or more than 64 stations, the overflow bound
+ * above, more than 65535 stacks, L > 4096.  TDOA_ERR_NOMEM: besides the map the call needs 2 bytes per (stack, cell) for D
+ * and 16 per (track, cell) for the two halves of T; tdoa_last_error says which did not fit. */
+int tdoa_process_locate_track(tdoa_ctx *ctx, int windows_per_stack, int max_step /* J */, int min_separation,
+                              tdoa_cell_track *track_host /* [n_tracks], required */,
+                              int32_t *cells_host /* [n_tracks][L]: L_j; may be NULL */,
+                              int64_t *own_host   /* [n_tracks][L]: s_j[L_j] (where the signal fades); may be NULL */,
+                              int32_t *lags_host  /* [n_stacks_total][n_pairs]: lag_p(L_j) of stack b L + j, clocks included, 0 where outside; may be NULL */,
+                              double  *corr_host  /* same shape: the signed C there on that stack's own scale; may be NULL */,
+                              int64_t *total_host /* [n_tracks][n_cells]: T_0; may be NULL */);
+
+/* tests only: the same kernels on the caller's words q [n_sets][P][2*max_lag-1] as tdoa_debug_locate_from_q takes them, with
+ * the context's table and clocks.  n_sets is a multiple of track_len; set t * track_len + j is position j of track t, every
+ * set a stack of n_w windows, N_w = track_len * n_w.  Needs no captures.  Precondition: |q| <= 2^62 div (P * track_len).
+ * TDOA_ERR_INVALID: what tdoa_process_locate_track and tdoa_debug_locate_from_q refuse, track_len < 1 or not a divisor of
+ * n_sets.  TDOA_ERR_STATE: as tdoa_debug_locate_from_q.  TDOA_ERR_UNSUPPORTED: P * track_len * n_w > 2^17, track_len > 4096. */
+int tdoa_debug_locate_track_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w,
+                                   int max_step, int min_separation, tdoa_cell_track *track, int32_t *cells, int64_t *own,
+                                   int32_t *lags, double *corr, int64_t *total);
+
 /* Capture-quality statistics of every (window, station) in one streaming pass over the bytes
  * in HBM: the byte statistics of fastAnalyzeSamples
  * (fast_analyzer.go:117-155) and the block power of validateDataFile (collector.go:219-224).
@@ -804,6 +870,15 @@ int tdoa_group_locate_set_clock(tdoa_group *g, const int32_t *clock, int n_stack
 int tdoa_group_process_sync(tdoa_group *g, int windows_per_stack, int gate, int rounds, const int32_t *ref_delay,
                             const int32_t *centre, tdoa_sync *sync_host, int32_t *clock_host, int32_t *lags_host,
                             double *corr_host);
+
+/* tdoa_process_locate_track over the members (the table and the clocks as set by tdoa_group_locate_set_table and
+ * tdoa_group_locate_set_clock): they sum their windows as in tdoa_group_process_stacked, the host adds the partials, and
+ * member 0 runs the search and the recurrence on the merged Q -- the outputs are byte-identical to
+ * tdoa_process_locate_track(single ctx, ...).  Errors as there and as tdoa_group_process.  With one member, its call writes
+ * the outputs directly. */
+int tdoa_group_process_locate_track(tdoa_group *g, int windows_per_stack, int max_step, int min_separation,
+                                    tdoa_cell_track *track_host, int32_t *cells_host, int64_t *own_host, int32_t *lags_host,
+                                    double *corr_host, int64_t *total_host);
 
 /* the sample runs member `rank` of `world` uploads for a capture of total_samples (window grid from n_min, the shortest
  * capture of the job; block offsets from the capture's own thirds): adjacent owned windows form one run, and with fewer

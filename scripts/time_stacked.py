@@ -13,9 +13,13 @@ that many cells over 0.3 x 0.4 degrees around the stations, with the records, la
 left on the device (the table is set once per round, outside the timed window).  Every `--sync G[/R]` adds a leg:
 tdoa_process_sync(0, G, R) (R defaults to 2) against the delays of a known emitter at TX, with the records, clocks, lags and
 correlations downloaded (the stack's accumulation, then the joint start over (2G+1)^2 cells and one workgroup per stack for
-the placing and the sweeps).  `--stations S` runs all legs on S stations (default 3; 8 gives 56 triples).
-usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--drift H/D]... [--track J]... [--closure G]...
-[--locate ROWSxCOLS]... [--sync G[/R]]..."""
+the placing and the sweeps).  Every `--locate-track J` adds a leg per `--locate` grid: tdoa_process_locate_track(0, J, 1) on
+that grid with the records, cells, own scores, lags and correlations downloaded and T_0 left on the device (the search's
+launches, then one launch per stack of a block but the last and four to finish).  `--stack M` gives the locate and
+locate-track legs stacks of M windows (default 0: whole blocks, one position per track).  `--stations S` runs all legs on S
+stations (default 3; 8 gives 56 triples).
+usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--stack M] [--drift H/D]... [--track J]...
+[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--sync G[/R]]..."""
 import json
 import os
 import sys
@@ -44,7 +48,7 @@ def timed(fn, steps):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
-def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=()):
+def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=(), locate_tracks=(), stack=0):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=20000)
     for s in range(stations):
         c.synth_capture(s, 66_666_666, ST[s % 3], TX, 0x5D0A0000 + s)
@@ -65,7 +69,11 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
                                                 0.4 / max(cols - 1, 1), rows, cols, 350.0, 2e6)
         name = "process_locate_%dx%d_ms" % (rows, cols)
         setup[name] = lambda table=table, cols=cols: c.locate_set_table(table, cols)
-        legs[name] = lambda: c.process_locate(0, 1)
+        legs[name] = lambda: c.process_locate(stack, 1)
+        for J in locate_tracks:
+            name = "process_locate_track_%dx%d_J%d_ms" % (rows, cols, J)
+            setup[name] = lambda table=table, cols=cols: c.locate_set_table(table, cols)
+            legs[name] = lambda J=J: c.process_locate_track(stack, J, 1)
     ref = tdoa_amd.capi.locate_grid_table([ST[s % 3] for s in range(stations)], TX[0], TX[1], 0.0, 0.0, 1, 1, TX[2], 2e6)[0]
     for G, R in syncs:
         legs["process_sync_%d_%d_ms" % (G, R)] = lambda G=G, R=R: c.process_sync(ref, 0, G, R)
@@ -75,7 +83,7 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
             if name in setup:
                 setup[name]()
             times[name].append(timed(fn, steps))
-    out = {"config": "cfg2" if stations == 3 else "cfg2 windows, %d stations" % stations, "stations": stations, "pairs": P, "windows": W, "stacks": n_stacks, "steps": steps, "rounds": rounds,
+    out = {"config": "cfg2" if stations == 3 else "cfg2 windows, %d stations" % stations, "stations": stations, "pairs": P, "windows": W, "stacks": n_stacks, "locate_stacks": c.num_stacks(stack)[1], "steps": steps, "rounds": rounds,
            "surface_MB": round(W * P * (2 * 20000 - 1) * 4 / 1e6, 1)}
     for name, t in times.items():
         out[name] = {"median": round(float(np.median(t)), 3), "min": round(min(t), 3), "max": round(max(t), 3)}
@@ -85,7 +93,7 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
 
 if __name__ == "__main__":
     args = sys.argv[1:]
-    opt = {"--steps": 20, "--rounds": 5, "--stations": 3}
+    opt = {"--steps": 20, "--rounds": 5, "--stations": 3, "--stack": 0}
     for name in opt:
         if name in args:
             i = args.index(name)
@@ -107,6 +115,11 @@ if __name__ == "__main__":
         i = args.index("--closure")
         closures.append(int(args[i + 1]))
         del args[i:i + 2]
+    locate_tracks = []
+    while "--locate-track" in args:
+        i = args.index("--locate-track")
+        locate_tracks.append(int(args[i + 1]))
+        del args[i:i + 2]
     locates = []
     while "--locate" in args:
         i = args.index("--locate")
@@ -119,4 +132,4 @@ if __name__ == "__main__":
         g, _, r = args[i + 1].partition("/")
         syncs.append((int(g), int(r or 2)))
         del args[i:i + 2]
-    main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs)
+    main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs, locate_tracks, opt["--stack"])

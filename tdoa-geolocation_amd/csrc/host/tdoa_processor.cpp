@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -133,6 +133,10 @@ int main(int argc, char **argv)
     // --sync=LAT,LON,HEIGHT[/G[/R]] (with --stack --locate, whole-block stacks): the reference emitter's position; the stations'
     // clocks are searched on the two reference blocks within G samples, R sweeps (tdoa_process_sync), and the locate runs with
     // them -- blocks 1 and 3 with their own clocks, block 2 with their midpoint (tdoa_locate_set_clock)
+    // --locate-track=J[/SEP] (with --stack --locate): per block the best track of cells through its stacks' maps, consecutive
+    // cells at most J rows and columns apart (tdoa_process_locate_track)
+    bool locate_track = false;
+    int ltrack_j = 0, ltrack_sep = 1;
     bool sync = false;
     double sync_lat = 0, sync_lon = 0, sync_h = 0;
     int sync_g = 128, sync_r = 2;
@@ -167,6 +171,14 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
+        else if (a.rfind("--locate-track=", 0) == 0) {
+            locate_track = true;
+            const int got = std::sscanf(a.c_str() + 15, "%d/%d", &ltrack_j, &ltrack_sep);
+            if (got < 1 || ltrack_j < 0 || ltrack_j > 16 || ltrack_sep < 1) {
+                std::fprintf(stderr, "--locate-track=J[/SEP] with J in 0 .. 16 and SEP >= 1, e.g. --locate-track=1\n");
+                return 1;
+            }
+        }
         else if (a.rfind("--sync=", 0) == 0) {
             sync = true;
             const int got = std::sscanf(a.c_str() + 7, "%lf,%lf,%lf/%d/%d", &sync_lat, &sync_lon, &sync_h, &sync_g, &sync_r);
@@ -187,6 +199,7 @@ int main(int argc, char **argv)
     if (track && !stack) { std::fprintf(stderr, "--track needs --stack\n"); return 1; }
     if (closure && !stack) { std::fprintf(stderr, "--closure needs --stack\n"); return 1; }
     if (locate && !stack) { std::fprintf(stderr, "--locate needs --stack\n"); return 1; }
+    if (locate_track && !locate) { std::fprintf(stderr, "--locate-track needs --stack --locate\n"); return 1; }
     if (sync && !locate) { std::fprintf(stderr, "--sync needs --stack --locate\n"); return 1; }
     if (sync && stack_m != 0) { std::fprintf(stderr, "--sync needs whole-block stacks: --stack without =WINDOWS\n"); return 1; }
     if (pos.size() < 4) {                                     // processor.go:1048-1052
@@ -357,6 +370,9 @@ int main(int argc, char **argv)
         std::vector<int32_t> tlags;
         std::vector<tdoa_closure> clos;          // --closure: one record per stack and station triple (tdoa_process_closure)
         std::vector<tdoa_location> locs;         // --locate: one record per stack (tdoa_process_locate)
+        std::vector<tdoa_cell_track> ltracks;    // --locate-track: one record per block, a cell and its own score per stack
+        std::vector<int32_t> lt_cells;           // (tdoa_process_locate_track)
+        std::vector<int64_t> lt_own;
         std::vector<tdoa_sync> syncs;            // --sync: one record and S clocks per block (tdoa_process_sync)
         std::vector<int32_t> clocks;
         double grid_lat0 = 0, grid_lon0 = 0, grid_dlat = 0, grid_dlon = 0;
@@ -425,6 +441,14 @@ int main(int argc, char **argv)
                 }
                 locs.resize((size_t)n_stacks);
                 if ((rc = tdoa_process_locate(ctx, stack_m, 1, locs.data(), nullptr, nullptr, nullptr))) return die("tdoa_process_locate", rc);
+                if (locate_track) {
+                    ltracks.resize((size_t)(n_stacks / spb));
+                    lt_cells.resize((size_t)n_stacks);
+                    lt_own.resize((size_t)n_stacks);
+                    if ((rc = tdoa_process_locate_track(ctx, stack_m, ltrack_j, ltrack_sep, ltracks.data(), lt_cells.data(), lt_own.data(), nullptr,
+                                                        nullptr, nullptr)))
+                        return die("tdoa_process_locate_track", rc);
+                }
             }
         }
         std::printf("\n=== FM-DISCRIMINATOR CROSS-CORRELATION: %d windows x %d pairs ===\n", W, P);
@@ -517,6 +541,19 @@ int main(int argc, char **argv)
             std::printf("LOCATE block %d stack %d: cell=%d lat=%.6f lon=%.6f pairs=%d score=%.6f runner=%.6f\n", (int)sid / spb + 1,
                         (int)sid % spb, (int)l.cell, grid_lat0 + (l.cell / locate_cols) * grid_dlat, grid_lon0 + (l.cell % locate_cols) * grid_dlon,
                         (int)l.pairs_in, l.score, l.runner_up);
+        }
+        // --locate-track: the block's track, then its cell in every stack with the stack's own score there (on the stack's scale)
+        for (size_t b = 0; b < ltracks.size(); b++) {
+            const tdoa_cell_track &t = ltracks[b];
+            std::printf("LOCATE-TRACK block %d: cell=%d positions=%d steps=%d score=%.6f runner=%.6f runner_cell=%d\n", (int)b + 1, (int)t.cell,
+                        (int)t.positions, (int)t.steps, t.score, t.runner_up, (int)t.runner_cell);
+            for (int j = 0; j < spb; j++) {
+                const size_t sid = b * spb + j;
+                const int cell = lt_cells[sid];
+                std::printf("LOCATE-TRACK block %d stack %d: cell=%d lat=%.6f lon=%.6f own=%.6f\n", (int)b + 1, j, cell,
+                            grid_lat0 + (cell / locate_cols) * grid_dlat, grid_lon0 + (cell % locate_cols) * grid_dlon,
+                            (double)lt_own[sid] / 4294967296.0 / std::sqrt((double)stacks.n_w((int)sid)));
+            }
         }
     }
 

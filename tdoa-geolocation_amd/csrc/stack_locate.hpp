@@ -9,8 +9,9 @@
 //                   pair; the scores go to the map [set][cell], the tile's best out as a two-word candidate (key = ~cell)
 //                   (a second instantiation adds the stack's clock difference of each pair: tdoa_locate_set_clock)
 // k_locate_runner   the same grid over the map: the best cell more than min_separation rows or columns from the location
-// k_locate_finish   the tiles' candidates -> the record, and the lags and signed correlations of the best cell; after the
-//                   runner-up's pass: runner_q, runner_up, runner_cell
+// k_locate_finish   the tiles' candidates -> the record, and the lags and signed correlations of the best cell
+//                   (locate_pair_value, shared with the cell tracks of stack_cell_track.hpp); after the runner-up's pass:
+//                   runner_q, runner_up, runner_cell
 //
 // Everything is integer arithmetic on the Q words of stack_surfaces.hpp; the only floating point is stack_value on the way
 // out.  The candidate, its order and the workgroup reduction are the closure search's (stack_closure.hpp).
@@ -154,6 +155,24 @@ __device__ __forceinline__ void locate_pair(int p, int S, int *i, int *j)
     *j = a + 1 + p;
 }
 
+// What the finishing kernels report of one cell for pair p of a set: lag_p(cell) and the signed C of the set's row there;
+// false, lag 0 and 0.0 for a pair outside the range.  q: the set's rows [P][n]; cd: the set's clock differences [P], nullptr:
+// none.
+__device__ __forceinline__ bool locate_pair_value(const long long *q, const LocateGeom &g, const int32_t *table, const long long *cd,
+                                                  int cell, int p, double root, int32_t *lag, double *c)
+{
+    int i, j;
+    locate_pair(p, g.S, &i, &j);
+    const long long l = locate_lag(table[(size_t)i * g.n_cells + cell], table[(size_t)j * g.n_cells + cell], cd ? cd[p] : 0),
+                    idx = l - g.lag_lo;
+    *lag = 0;
+    *c = 0.0;
+    if (idx < 0 || idx >= g.n) return false;
+    *lag = (int32_t)l;
+    *c = stack_value(q[(size_t)p * g.n + idx], root);
+    return true;
+}
+
 // One workgroup per set.
 // pass 0: the tiles' candidates -> the location into best and the record (cell, pairs_in, score_q, score; the runner-up's
 // fields 0), and per pair lag_p(cell*) and the signed C there (0 and 0.0 for a pair outside the range).  A largest score of 0:
@@ -197,18 +216,7 @@ __global__ __launch_bounds__(kLocateThreads) void k_locate_finish(const long lon
     for (int p = t; p < g.P; p += kLocateThreads) {
         int32_t lag = 0;
         double c = 0.0;
-        if (found) {
-            int i, j;
-            locate_pair(p, g.S, &i, &j);
-            const long long l = locate_lag(table[(size_t)i * g.n_cells + cell], table[(size_t)j * g.n_cells + cell],
-                                           cdiff ? cdiff[(size_t)set * g.P + p] : 0),
-                            idx = l - g.lag_lo;
-            if (idx >= 0 && idx < g.n) {
-                lag = (int32_t)l;
-                c = stack_value(q[(size_t)p * g.n + idx], root);
-                inside++;
-            }
-        }
+        if (found && locate_pair_value(q, g, table, cdiff ? cdiff + (size_t)set * g.P : nullptr, cell, p, root, &lag, &c)) inside++;
         lags[(size_t)set * g.P + p] = lag;
         corr[(size_t)set * g.P + p] = c;
     }

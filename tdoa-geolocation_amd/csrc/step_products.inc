@@ -3,7 +3,8 @@
 // (tdoa_process_stacked), the same stacks taken along the best of 2H+1 lag slopes (tdoa_process_stacked_drift), the best
 // delay track through a stack's windows (tdoa_process_track), one consistent lag set per station triple of a stack
 // (tdoa_process_closure), a table of candidate positions scored on all pairs' stacks (tdoa_process_locate), the stations'
-// clock offsets from a block whose emitter is known (tdoa_process_sync).  Every product
+// clock offsets from a block whose emitter is known (tdoa_process_sync), the best track of cells through the stacks of a
+// block on the delay-table search's maps (tdoa_process_locate_track).  Every product
 // is a struct derived from StepProduct: the entry point fills it, process_impl calls its six hooks in this order (a product
 // overrides the ones it needs; process_impl without a product writes the peak records only):
 //   reserve   its buffers, after the step's grouping is fixed (batch_bound counts them as held, so a later call groups as
@@ -36,7 +37,7 @@ struct StepView {
 
 // the product of one step; the numbers are the first word a product appends to the graph key
 struct StepProduct {
-    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6, Locate = 7, Sync = 8 };
+    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6, Locate = 7, Sync = 8, CellTrack = 9 };
     virtual int reserve(const StepView &v) = 0;
     virtual void key(std::vector<uint64_t> *key) const = 0;
     virtual int upload(const StepView &) { return TDOA_OK; }
@@ -423,6 +424,45 @@ struct LocateProduct : StackProduct {
     int download(const StepView &v) const override
     {
         return download_locate(v.ctx, layout.n_stacks, locate_geom(v.ctx, sep), loc_host, lags_host, corr_host, map_host);
+    }
+};
+
+// ---- cell tracks through the maps of a block's stacks (stack_cell_track.hpp, locate_track_api.inc) ---------------------
+// The search's own records stay on the device; lags_host and corr_host receive the track's positions' instead of the best
+// cells'.  A track spans a block: L = the stacks per block, and the three blocks' tracks hold all their windows.
+struct CellTrackProduct : LocateProduct {
+    int J = 0;                               // max_step
+    tdoa_cell_track *track_host = nullptr;   // [track]
+    int32_t *cells_host = nullptr;           // [track][L]
+    int64_t *own_host = nullptr;             // [track][L]
+    int64_t *total_host = nullptr;           // [track][cell]
+    std::vector<double> track_roots;         // refresh's host copy of sqrt(N_w) (lives until the call has synchronised)
+
+    int reserve(const StepView &v) override
+    {
+        if (int rc = LocateProduct::reserve(v)) return rc;
+        return ensure_locate_track(v.ctx, layout.n_stacks, layout.spb, locate_geom(v.ctx, sep));
+    }
+    void key(std::vector<uint64_t> *key) const override
+    {
+        key->insert(key->end(), {CellTrack, (uint64_t)m, (uint64_t)J, (uint64_t)sep, (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked});
+    }
+    int refresh(const StepView &v) override  // (every call: the debug and the group's calls write their own roots there)
+    {
+        track_roots = block_track_roots(v.wpb);
+        return upload_locate_track_roots(v.ctx, track_roots);
+    }
+    void enqueue(const StepView &v) const override
+    {
+        tdoa_ctx *ctx = v.ctx;
+        LocateProduct::enqueue(v);
+        launch_locate_track(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, layout.n_stacks, v.P).roots, layout.n_stacks, layout.spb, J,
+                            locate_geom(ctx, sep));
+    }
+    int download(const StepView &v) const override
+    {
+        return download_locate_track(v.ctx, layout.n_stacks, layout.spb, locate_geom(v.ctx, sep), track_host, cells_host, own_host, lags_host,
+                                     corr_host, total_host);
     }
 };
 

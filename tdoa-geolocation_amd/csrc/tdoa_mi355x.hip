@@ -41,6 +41,7 @@
 #include "stack_closure.hpp"
 #include "stack_locate.hpp"
 #include "stack_sync.hpp"
+#include "stack_cell_track.hpp"
 
 using namespace tdoa;
 
@@ -171,6 +172,9 @@ struct tdoa_ctx {
     // ... and the stacks' station clocks as the kernels take them, clock[j] - clock[i] per [stack][pair] (state:
     // tdoa_locate_set_clock; 0 stacks: none)
     DevBuf locate_clock;
+    // cell tracks (tdoa_process_locate_track): the steps D [stack][cell][2], the two halves of T [track][cell], sqrt(N_w) per
+    // track, the records [track], the tracks' cells and own scores [stack]
+    DevBuf ctrack_d, ctrack_t, ctrack_roots, ctrack_out, ctrack_cells, ctrack_own;
     // the clock search: ref_delay and centre (kSyncMaxStations words each), the start's tiles' candidates [stack][tile], the
     // records [stack], the clocks [stack][station], the lags and correlations [stack][pair]
     DevBuf sync_in, sync_part, sync_out, sync_clock, sync_lags, sync_corr;
@@ -188,6 +192,7 @@ static_assert(sizeof(ClosureOut) == sizeof(tdoa_closure) && sizeof(tdoa_closure)
 static_assert(sizeof(LocateOut) == sizeof(tdoa_location) && sizeof(tdoa_location) == 48, "tdoa_location layout");
 static_assert(kLocateDelayUnit == TDOA_DELAY_UNIT, "the table's unit");
 static_assert(sizeof(SyncOut) == sizeof(tdoa_sync) && sizeof(tdoa_sync) == 32, "tdoa_sync layout");
+static_assert(sizeof(CellTrackOut) == sizeof(tdoa_cell_track) && sizeof(tdoa_cell_track) == 48, "tdoa_cell_track layout");
 
 int fail(tdoa_ctx *ctx, int status, const char *what, hipError_t e = hipSuccess)
 {
@@ -371,6 +376,7 @@ int check_selection(tdoa_ctx *ctx, int k, int min_separation, const void *out)
 #include "stacked_api.inc"
 #include "closure_api.inc"
 #include "locate_api.inc"
+#include "locate_track_api.inc"
 #include "sync_api.inc"
 #include "step_products.inc"
 
@@ -531,7 +537,8 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->closure_part, &ctx->closure_best, &ctx->closure_out, &ctx->locate_table,
                       &ctx->locate_map, &ctx->locate_part, &ctx->locate_best, &ctx->locate_out, &ctx->locate_lags, &ctx->locate_corr,
                       &ctx->locate_clock, &ctx->sync_in, &ctx->sync_part, &ctx->sync_out, &ctx->sync_clock, &ctx->sync_lags,
-                      &ctx->sync_corr, &ctx->debug_q, &ctx->debug_roots};
+                      &ctx->sync_corr, &ctx->debug_q, &ctx->debug_roots, &ctx->ctrack_d, &ctx->ctrack_t, &ctx->ctrack_roots,
+                      &ctx->ctrack_out, &ctx->ctrack_cells, &ctx->ctrack_own};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1129,6 +1136,30 @@ int tdoa_process_locate(tdoa_ctx *ctx, int windows_per_stack, int min_separation
     prod.corr_host = corr_host;
     prod.map_host = map_host;
     prod.clocked = ctx->clock_stacks != 0;
+    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
+}
+
+int tdoa_process_locate_track(tdoa_ctx *ctx, int windows_per_stack, int max_step, int min_separation, tdoa_cell_track *track_host,
+                              int32_t *cells_host, int64_t *own_host, int32_t *lags_host, double *corr_host, int64_t *total_host)
+{
+    if (int rc = refuse_stacked(ctx, windows_per_stack, check_locate_track_args(max_step, min_separation, track_host),
+                                "the delay-table search with TDOA_LAGS_GO", true))
+        return rc;
+    const char *what = nullptr;              // (what the search refuses, the track's overflow bound and length: shared with the group's call)
+    if (const int rc = check_locate_track_state(ctx, windows_per_stack, &what)) return fail(ctx, rc, what);
+    CellTrackProduct prod;
+    fill_stack(&prod, windows_per_stack);
+    prod.sep = min_separation;
+    prod.n_cells = ctx->locate_cells;
+    prod.n_cols = ctx->locate_cols;
+    prod.clocked = ctx->clock_stacks != 0;
+    prod.J = max_step;
+    prod.track_host = track_host;
+    prod.cells_host = cells_host;
+    prod.own_host = own_host;
+    prod.lags_host = lags_host;
+    prod.corr_host = corr_host;
+    prod.total_host = total_host;
     return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
 }
 

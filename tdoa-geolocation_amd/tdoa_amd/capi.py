@@ -54,6 +54,9 @@ LOCATION_DTYPE = np.dtype([("cell", np.int32), ("runner_cell", np.int32), ("pair
                            ("score", np.float64), ("runner_up", np.float64)])      # tdoa_location
 SYNC_DTYPE = np.dtype([("moved", np.int32), ("pairs_in", np.int32), ("score_q", np.int64), ("start_q", np.int64),
                        ("score", np.float64)])      # tdoa_sync
+CELL_TRACK_DTYPE = np.dtype([("cell", np.int32), ("runner_cell", np.int32), ("positions", np.int32), ("steps", np.int32),
+                             ("score_q", np.int64), ("runner_q", np.int64),
+                             ("score", np.float64), ("runner_up", np.float64)])      # tdoa_cell_track
 FINE_DTYPE = np.dtype([("delay", np.float64), ("frac", np.float32), ("y", np.float32, (3,)), ("plausible", np.int32),
                        ("reserved", np.int32)])
 
@@ -108,6 +111,7 @@ SYMBOLS = [
     "tdoa_locate_set_table", "tdoa_process_locate", "tdoa_debug_locate_from_q", "tdoa_locate_grid_table",
     "tdoa_group_locate_set_table", "tdoa_group_process_locate",
     "tdoa_locate_set_clock", "tdoa_group_locate_set_clock", "tdoa_process_sync", "tdoa_debug_sync_from_q",
+    "tdoa_process_locate_track", "tdoa_debug_locate_track_from_q", "tdoa_group_process_locate_track",
     "tdoa_group_process_sync",
 ]
 
@@ -234,6 +238,10 @@ def load(build_if_missing=True):
     L.tdoa_group_locate_set_clock.argtypes = [vp, i32p, C.c_int, C.c_int]
     L.tdoa_process_sync.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, vp, i32p, i32p, dp]
     L.tdoa_group_process_sync.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, vp, i32p, i32p, dp]
+    L.tdoa_process_locate_track.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, i32p, i64p, i32p, dp, i64p]
+    L.tdoa_group_process_locate_track.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, i32p, i64p, i32p, dp, i64p]
+    L.tdoa_debug_locate_track_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p, i64p, i32p,
+                                                 dp, i64p]
     L.tdoa_debug_sync_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, vp, i32p, i32p, dp]
     L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
                                         C.POINTER(C.c_int)]
@@ -685,6 +693,33 @@ class Context:
                                                  *_sync_ptrs(out)))
         return out
 
+    def process_locate_track(self, windows_per_stack=0, max_step=0, min_separation=1, want_total=False):
+        """tdoa_process_locate_track -> {"track": [n_tracks] CELL_TRACK_DTYPE, "cells": [n_tracks][L] int32, "own":
+        [n_tracks][L] int64, "lags": [n_stacks][P] int32, "corr": [n_stacks][P] float64, and with want_total "total":
+        [n_tracks][n_cells] int64}: per block the track of cells through its stacks' maps, consecutive cells at most max_step
+        rows and columns apart, with the largest summed score; the runner-up; per stack the lags and signed correlations at
+        the track's cell"""
+        per_block, n = self.num_stacks(windows_per_stack)
+        out = _locate_track_outputs(n, per_block, self.num_pairs(), getattr(self, "_locate_cells", 0), want_total)
+        self._chk(self._L.tdoa_process_locate_track(self._h, int(windows_per_stack), int(max_step), int(min_separation),
+                                                    *_locate_track_ptrs(out)))
+        return out
+
+    def locate_track_from_q(self, q, n_stations, track_len, n_w=1, max_step=0, min_separation=1, want_total=True):
+        """tdoa_debug_locate_track_from_q: the search's and the recurrence's kernels on the caller's words q
+        [n_sets][P][2 max_lag - 1] int64, set t track_len + j position j of track t, with the context's table and clocks ->
+        what process_locate_track returns, n_sets for n_stacks"""
+        q = np.ascontiguousarray(q, dtype=np.int64)
+        if q.ndim == 2:
+            q = q[None]
+        S = int(n_stations)
+        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
+            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
+        out = _locate_track_outputs(q.shape[0], max(int(track_len), 1), q.shape[1], getattr(self, "_locate_cells", 0), want_total)
+        self._chk(self._L.tdoa_debug_locate_track_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], int(track_len), S,
+                                                         int(n_w), int(max_step), int(min_separation), *_locate_track_ptrs(out)))
+        return out
+
     def fm_xcorr_peaks(self, iq1, iq2, max_lag, k, min_separation):
         """tdoa_fm_xcorr_peaks_u8 -> (peaks [k] PEAK_DTYPE, count) of one pair of windows"""
         a = np.ascontiguousarray(iq1, dtype=np.uint8)
@@ -862,6 +897,22 @@ def _locate_ptrs(out):
             out["map"].ctypes.data_as(C.POINTER(C.c_int64)) if "map" in out else None)
 
 
+def _locate_track_outputs(n_sets, track_len, p, n_cells, want_total):
+    n_tracks = max(n_sets // track_len, 1)
+    out = {"track": np.zeros(n_tracks, dtype=CELL_TRACK_DTYPE), "cells": np.zeros((n_tracks, track_len), dtype=np.int32),
+           "own": np.zeros((n_tracks, track_len), dtype=np.int64), "lags": np.zeros((n_sets, p), dtype=np.int32),
+           "corr": np.zeros((n_sets, p), dtype=np.float64)}
+    if want_total:
+        out["total"] = np.zeros((n_tracks, n_cells), dtype=np.int64)
+    return out
+
+
+def _locate_track_ptrs(out):
+    i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    return (out["track"].ctypes.data_as(C.c_void_p), out["cells"].ctypes.data_as(i32p), out["own"].ctypes.data_as(i64p),
+            out["lags"].ctypes.data_as(i32p), _d(out["corr"]), out["total"].ctypes.data_as(i64p) if "total" in out else None)
+
+
 def _stacked_outputs(n_stacks, p, n_lags, k, want_surface, want_partial):
     out = {"peaks": np.zeros((n_stacks, p, max(int(k), 1)), dtype=PEAK_DTYPE), "count": np.zeros((n_stacks, p), dtype=np.int32),
            "fine": np.zeros((n_stacks, p), dtype=FINE_DTYPE)}
@@ -994,6 +1045,15 @@ class Group:
     def locate_set_clock(self, clock):
         """tdoa_group_locate_set_clock: the station clocks to every member"""
         self._chk(self._L.tdoa_group_locate_set_clock(self._h, *_clock(clock)))
+
+    def process_locate_track(self, windows_per_stack=0, max_step=0, min_separation=1, want_total=False):
+        """tdoa_group_process_locate_track -> Context.process_locate_track's outputs, byte-identical to a single context's"""
+        m = self.member(0)
+        per_block, n = m.num_stacks(windows_per_stack)
+        out = _locate_track_outputs(n, per_block, m.num_pairs(), getattr(self, "_locate_cells", 0), want_total)
+        self._chk(self._L.tdoa_group_process_locate_track(self._h, int(windows_per_stack), int(max_step), int(min_separation),
+                                                          *_locate_track_ptrs(out)))
+        return out
 
     def process_sync(self, ref_delay, windows_per_stack=0, gate=0, rounds=0, centre=None):
         """tdoa_group_process_sync -> Context.process_sync's outputs, byte-identical to a single context's"""

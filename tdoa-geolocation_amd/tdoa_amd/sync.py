@@ -126,3 +126,20 @@ def midpoint_clock(clock_before, clock_after):
     if a.shape != b.shape:
         raise ValueError("the two clock tables must have the same shape")
     return ((DELAY_UNIT // 2) * (a + b)).astype(np.int32)
+
+
+def ramp_clock(k_before, k_after, n):
+    """the clocks of the n positions of the block between two reference blocks, in units of 1/16 sample, linear between the
+    centres of the two reference blocks (blocks of equal length, position j's centre (n + 2 j + 1) / (4 n) of the way):
+
+        clock_j = 16 k_before + r(16 (k_after - k_before) (n + 2 j + 1), 4 n)
+
+    r(a, b) the nearest integer to a / b, halves away from zero, in integers only.  k_before, k_after [S] in samples ->
+    [n][S] int32; its mean over j is midpoint_clock's value up to the rounding"""
+    a, b, n = np.asarray(k_before, dtype=np.int64), np.asarray(k_after, dtype=np.int64), int(n)
+    if a.shape != b.shape or a.ndim != 1:
+        raise ValueError("the two clocks must hold one integer per station")
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    num = DELAY_UNIT * (b - a)[None, :] * (n + 2 * np.arange(n, dtype=np.int64) + 1)[:, None]
+    return (DELAY_UNIT * a[None, :] + np.sign(num) * ((2 * np.abs(num) + 4 * n) // (8 * n))).astype(np.int32)
