@@ -267,6 +267,29 @@ func (g *gpuCorrelator) ProcessLocate(windowsPerStack, minSeparation int) (loc [
 	return loc, lags, corr, nil
 }
 
+// ProcessLocateMulti finds up to nEmitters emitters per stack (the header's "several emitters per stack"): round 0 is
+// ProcessLocate's search, every later round searches again with the lags within guard of the earlier rounds' cells' lags
+// counting 0 in every pair.  loc is [round][stack], lags and corr [round][stack][pair]; an excluded pair reports its lag and
+// 0.0, so tdoa_solve_surface gives it no weight.
+func (g *gpuCorrelator) ProcessLocateMulti(windowsPerStack, nEmitters, guard, minSeparation int) (loc []C.tdoa_location, lags []int32, corr []float64, err error) {
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, nil, nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs := int(C.tdoa_num_pairs(g.ctx))
+	if int(total)*pairs == 0 || nEmitters < 1 {
+		return nil, nil, nil, fmt.Errorf("tdoa_process_locate_multi: no stacks, fewer than two stations or no rounds")
+	}
+	loc = make([]C.tdoa_location, nEmitters*int(total))
+	lags = make([]int32, nEmitters*int(total)*pairs)
+	corr = make([]float64, nEmitters*int(total)*pairs)
+	if rc := C.tdoa_process_locate_multi(g.ctx, C.int(windowsPerStack), C.int(nEmitters), C.int(guard), C.int(minSeparation), &loc[0],
+		(*C.int32_t)(unsafe.Pointer(&lags[0])), (*C.double)(unsafe.Pointer(&corr[0])), nil); rc != C.TDOA_OK {
+		return nil, nil, nil, fmt.Errorf("tdoa_process_locate_multi: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return loc, lags, corr, nil
+}
+
 // ProcessLocateTrack follows an emitter through the stacks of every block on the delay-table search's maps (the header's
 // "cell tracks"): per block one cell per stack, consecutive cells at most maxStep rows and columns apart, with the largest
 // summed score, and the runner-up.  cells and own are [block][stacks per block] (the track's cell in every stack and that
@@ -469,6 +492,28 @@ func (g *Group) ProcessLocate(windowsPerStack, minSeparation int) (loc []C.tdoa_
 	if rc := C.tdoa_group_process_locate(g.g, C.int(windowsPerStack), C.int(minSeparation), &loc[0], (*C.int32_t)(unsafe.Pointer(&lags[0])),
 		(*C.double)(unsafe.Pointer(&corr[0])), nil); rc != C.TDOA_OK {
 		return nil, nil, nil, fmt.Errorf("tdoa_group_process_locate: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return loc, lags, corr, nil
+}
+
+// ProcessLocateMulti is gpuCorrelator.ProcessLocateMulti over the group: the members' fixed-point partial sums are added on
+// the host and searched on member 0, the same bytes one context returns.
+func (g *Group) ProcessLocateMulti(windowsPerStack, nEmitters, guard, minSeparation int) (loc []C.tdoa_location, lags []int32, corr []float64, err error) {
+	m := C.tdoa_group_member(g.g, 0)
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(m, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, nil, nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs := int(C.tdoa_num_pairs(m))
+	if int(total)*pairs == 0 || nEmitters < 1 {
+		return nil, nil, nil, fmt.Errorf("tdoa_group_process_locate_multi: no stacks, fewer than two stations or no rounds")
+	}
+	loc = make([]C.tdoa_location, nEmitters*int(total))
+	lags = make([]int32, nEmitters*int(total)*pairs)
+	corr = make([]float64, nEmitters*int(total)*pairs)
+	if rc := C.tdoa_group_process_locate_multi(g.g, C.int(windowsPerStack), C.int(nEmitters), C.int(guard), C.int(minSeparation), &loc[0],
+		(*C.int32_t)(unsafe.Pointer(&lags[0])), (*C.double)(unsafe.Pointer(&corr[0])), nil); rc != C.TDOA_OK {
+		return nil, nil, nil, fmt.Errorf("tdoa_group_process_locate_multi: %s", C.GoString(C.tdoa_group_last_error(g.g)))
 	}
 	return loc, lags, corr, nil
 }

@@ -647,6 +647,50 @@ int tdoa_debug_locate_track_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, 
                                    int max_step, int min_separation, tdoa_cell_track *track, int32_t *cells, int64_t *own,
                                    int32_t *lags, double *corr, int64_t *total);
 
+/* Several emitters per stack: mask the found lags and search again.  The peak of an emitter A in pair p's stack raises every
+ * cell whose lag_p equals A's -- a whole hyperbola on the map -- and where three of A's pairs coincide a ridge, far more than
+ * min_separation from A.  A weaker emitter B on the same channel lies under those ridges, so tdoa_process_locate's runner-up
+ * is not a second emitter.  Taking A's lags out of every pair's stack and searching again finds B.
+ * Stacks, windows_per_stack, n_w, the table, the clocks, lag_p(c), Q and the record are exactly tdoa_process_locate's.
+ * K = n_emitters, 1 <= K <= TDOA_LOCATE_MAX_EMITTERS.  Per stack, rounds r = 0 .. K-1:
+ *   E_p(r) is the set of excluded lags of pair p.  E_p(0) is empty.
+ *     E_p(r+1) = E_p(r) united with { l : |l - lag_p(cell*_r)| <= guard } if round r found a cell and lag_p(cell*_r) lies
+ *     inside the searched range; otherwise E_p(r+1) = E_p(r).  Intervals are clipped at the range edges.  They may overlap.
+ *   M_p^r[l] = 0 for l in E_p(r) or outside the range, else |Q_p[l]|.
+ *   score_q^r(c) = the sum over all P pairs of M_p^r[lag_p(c)].
+ *   Round r's record: the largest score_q^r, equal maxima going to the smaller cell; the runner-up of that round's map beyond
+ *     min_separation of that round's cell; pairs_in counts the pairs inside the range and not excluded at the cell; reserved
+ *     carries the number of pairs inside the range but excluded at the cell.
+ *   Per pair: a pair outside the range reports lag 0 and 0.0.  An excluded pair reports its lag and 0.0, so
+ *     tdoa_solve_surface gives it no weight.
+ *   If the largest score of a round is 0, the result is the zero record, zero lags and zero correlations, and nothing is
+ *     added to E.  Every later round is then the zero record too.
+ *   Q is never written.
+ * Identity (held by the tests): round 0, and therefore the whole call with K = 1, returns tdoa_process_locate's bytes --
+ *   record, lags, correlations, map.  reserved is 0 there.
+ * The outputs are laid out [round][stack][...].  It joins nothing across stacks: combining it with tdoa_process_locate_track
+ * is out of scope.
+ * Runs inside the step graph, behind the stack's accumulation: round 0 as tdoa_process_locate launches it, then per further
+ * round the masked scores, the runner-up's pass and two finishing launches.  (windows_per_stack, K, guard, min_separation,
+ * n_cells, n_cols, whether a clock table is present) are part of the graph's key; the table, the clocks and the excluded
+ * intervals are data.  tdoa_group_process_locate_multi is the group form.
+ * TDOA_ERR_INVALID (no device needed): what tdoa_process_locate refuses, n_emitters outside 1 .. 8, guard < 0.  Every other
+ * refusal is tdoa_process_locate's.  TDOA_ERR_NOMEM: the map [K][n_stacks_total][n_cells] does not fit; tdoa_last_error says
+ * so. */
+#define TDOA_LOCATE_MAX_EMITTERS 8
+int tdoa_process_locate_multi(tdoa_ctx *ctx, int windows_per_stack, int n_emitters /* K */, int guard /* >= 0 lags */,
+                              int min_separation,
+                              tdoa_location *loc_host /* [K][n_stacks_total], required */,
+                              int32_t *lags_host      /* [K][n_stacks_total][n_pairs]; may be NULL */,
+                              double  *corr_host      /* same shape; may be NULL */,
+                              int64_t *map_host       /* [K][n_stacks_total][n_cells]: score_q^r of every cell; may be NULL */);
+
+/* tests only: the same kernels on the caller's words q [n_sets][P][2*max_lag-1] as tdoa_debug_locate_from_q takes them, with
+ * the context's table and clocks; outputs [K][n_sets][...].  Needs no captures.  Errors as tdoa_debug_locate_from_q's, plus
+ * n_emitters outside 1 .. 8 and guard < 0 (TDOA_ERR_INVALID). */
+int tdoa_debug_locate_multi_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int n_emitters,
+                                   int guard, int min_separation, tdoa_location *loc, int32_t *lags, double *corr, int64_t *map);
+
 /* Capture-quality statistics of every (window, station) in one streaming pass over the bytes
  * in HBM: the byte statistics of fastAnalyzeSamples
  * (fast_analyzer.go:117-155) and the block power of validateDataFile (collector.go:219-224).
@@ -879,6 +923,13 @@ int tdoa_group_process_sync(tdoa_group *g, int windows_per_stack, int gate, int 
 int tdoa_group_process_locate_track(tdoa_group *g, int windows_per_stack, int max_step, int min_separation,
                                     tdoa_cell_track *track_host, int32_t *cells_host, int64_t *own_host, int32_t *lags_host,
                                     double *corr_host, int64_t *total_host);
+
+/* tdoa_process_locate_multi over the members (the table and the clocks as set by tdoa_group_locate_set_table and
+ * tdoa_group_locate_set_clock): they sum their windows as in tdoa_group_process_stacked, the host adds the partials, and
+ * member 0 runs the rounds on the merged Q -- the outputs are byte-identical to tdoa_process_locate_multi(single ctx, ...).
+ * Errors as there and as tdoa_group_process.  With one member, its call writes the outputs directly. */
+int tdoa_group_process_locate_multi(tdoa_group *g, int windows_per_stack, int n_emitters, int guard, int min_separation,
+                                    tdoa_location *loc_host, int32_t *lags_host, double *corr_host, int64_t *map_host);
 
 /* the sample runs member `rank` of `world` uploads for a capture of total_samples (window grid from n_min, the shortest
  * capture of the job; block offsets from the capture's own thirds): adjacent owned windows form one run, and with fewer

@@ -15,11 +15,14 @@ tdoa_process_sync(0, G, R) (R defaults to 2) against the delays of a known emitt
 correlations downloaded (the stack's accumulation, then the joint start over (2G+1)^2 cells and one workgroup per stack for
 the placing and the sweeps).  Every `--locate-track J` adds a leg per `--locate` grid: tdoa_process_locate_track(0, J, 1) on
 that grid with the records, cells, own scores, lags and correlations downloaded and T_0 left on the device (the search's
-launches, then one launch per stack of a block but the last and four to finish).  `--stack M` gives the locate and
-locate-track legs stacks of M windows (default 0: whole blocks, one position per track).  `--stations S` runs all legs on S
+launches, then one launch per stack of a block but the last and four to finish).  Every `--emitters K[/GUARD]` adds a leg
+per `--locate` grid: tdoa_process_locate_multi(0, K, GUARD, 1) (GUARD defaults to 2) on that grid with the K planes of records,
+lags and correlations downloaded and the maps left on the device (the search's launches, then four per further round;
+K = 1 is the locate leg's work through the other entry).  `--stack M` gives the locate, locate-track and emitters legs stacks
+of M windows (default 0: whole blocks, one position per track).  `--stations S` runs all legs on S
 stations (default 3; 8 gives 56 triples).
 usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--stack M] [--drift H/D]... [--track J]...
-[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--sync G[/R]]..."""
+[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--sync G[/R]]..."""
 import json
 import os
 import sys
@@ -48,7 +51,7 @@ def timed(fn, steps):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
-def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=(), locate_tracks=(), stack=0):
+def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=(), locate_tracks=(), stack=0, emitters=()):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=20000)
     for s in range(stations):
         c.synth_capture(s, 66_666_666, ST[s % 3], TX, 0x5D0A0000 + s)
@@ -74,6 +77,10 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
             name = "process_locate_track_%dx%d_J%d_ms" % (rows, cols, J)
             setup[name] = lambda table=table, cols=cols: c.locate_set_table(table, cols)
             legs[name] = lambda J=J: c.process_locate_track(stack, J, 1)
+        for K, guard in emitters:
+            name = "process_locate_multi_%dx%d_K%d_G%d_ms" % (rows, cols, K, guard)
+            setup[name] = lambda table=table, cols=cols: c.locate_set_table(table, cols)
+            legs[name] = lambda K=K, guard=guard: c.process_locate_multi(stack, K, guard, 1)
     ref = tdoa_amd.capi.locate_grid_table([ST[s % 3] for s in range(stations)], TX[0], TX[1], 0.0, 0.0, 1, 1, TX[2], 2e6)[0]
     for G, R in syncs:
         legs["process_sync_%d_%d_ms" % (G, R)] = lambda G=G, R=R: c.process_sync(ref, 0, G, R)
@@ -120,6 +127,12 @@ if __name__ == "__main__":
         i = args.index("--locate-track")
         locate_tracks.append(int(args[i + 1]))
         del args[i:i + 2]
+    emitters = []
+    while "--emitters" in args:
+        i = args.index("--emitters")
+        k, _, g = args[i + 1].partition("/")
+        emitters.append((int(k), int(g or 2)))
+        del args[i:i + 2]
     locates = []
     while "--locate" in args:
         i = args.index("--locate")
@@ -132,4 +145,4 @@ if __name__ == "__main__":
         g, _, r = args[i + 1].partition("/")
         syncs.append((int(g), int(r or 2)))
         del args[i:i + 2]
-    main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs, locate_tracks, opt["--stack"])
+    main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs, locate_tracks, opt["--stack"], emitters)

@@ -286,6 +286,27 @@ int tdoa_debug_locate_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_
     return download_and_wait(ctx, [&] { return download_locate(ctx, n_sets, g, loc, lags, corr, map); });
 }
 
+// the rounds of several emitters per stack (locate_multi_api.inc) on the caller's words, as tdoa_debug_locate_from_q takes them;
+// the outputs are [round][set] planes.  Needs the context for max_lag, the table, the clocks and the device only.
+int tdoa_debug_locate_multi_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int n_emitters, int guard,
+                                   int min_separation, tdoa_location *loc, int32_t *lags, double *corr, int64_t *map)
+{
+    int rc;
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (const char *bad = check_locate_multi_args(n_emitters, guard, min_separation, loc)) return fail(ctx, TDOA_ERR_INVALID, bad);
+    if (!q || n_sets < 1 || n_sets > kLocateMaxSets || n_w < 1 || n_stations < 2 || n_stations > kLocateMaxStations)
+        return fail(ctx, TDOA_ERR_INVALID, "q is NULL, n_sets outside 1 .. 65535, n_w < 1 or n_stations outside 2 .. 64");
+    if (const char *bad = check_locate_table(ctx, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
+    if (const char *bad = check_locate_clock(ctx, n_sets, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
+    const LocateGeom g = locate_geom(ctx, min_separation);
+    if (locate_overflows(g.P, n_w)) return fail(ctx, TDOA_ERR_UNSUPPORTED, "pairs x n_w > 2^17: a cell's score could overflow");
+    std::vector<double> roots;
+    if ((rc = upload_debug_q(ctx, q, (size_t)n_sets * g.P * g.n, n_sets, n_w, &roots))) return rc;
+    if ((rc = ensure_locate_multi(ctx, n_sets, n_emitters, g))) return rc;
+    launch_locate_multi(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), n_sets, n_emitters, guard, g);
+    return download_and_wait(ctx, [&] { return download_locate_multi(ctx, n_sets, n_emitters, g, loc, lags, corr, map); });
+}
+
 // the delay-table search's and the cell tracks' kernels (locate_track_api.inc) on the caller's words: n_sets sets as
 // tdoa_debug_locate_from_q takes them, set t * track_len + j position j of track t.  Needs the context for max_lag, the table,
 // the clocks and the device only.

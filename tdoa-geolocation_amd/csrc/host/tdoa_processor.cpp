@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -137,6 +137,10 @@ int main(int argc, char **argv)
     // cells at most J rows and columns apart (tdoa_process_locate_track)
     bool locate_track = false;
     int ltrack_j = 0, ltrack_sep = 1;
+    // --emitters=K[/GUARD] (with --stack --locate): per stack K fixes, each searched with the lags within GUARD of the earlier
+    // fixes' lags counting 0 in every pair (tdoa_process_locate_multi)
+    bool emitters = false;
+    int emitters_k = 1, emitters_guard = 2;
     bool sync = false;
     double sync_lat = 0, sync_lon = 0, sync_h = 0;
     int sync_g = 128, sync_r = 2;
@@ -179,6 +183,14 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
+        else if (a.rfind("--emitters=", 0) == 0) {
+            emitters = true;
+            const int got = std::sscanf(a.c_str() + 11, "%d/%d", &emitters_k, &emitters_guard);
+            if (got < 1 || emitters_k < 1 || emitters_k > TDOA_LOCATE_MAX_EMITTERS || emitters_guard < 0) {
+                std::fprintf(stderr, "--emitters=K[/GUARD] with K in 1 .. 8 and GUARD >= 0, e.g. --emitters=2/2\n");
+                return 1;
+            }
+        }
         else if (a.rfind("--sync=", 0) == 0) {
             sync = true;
             const int got = std::sscanf(a.c_str() + 7, "%lf,%lf,%lf/%d/%d", &sync_lat, &sync_lon, &sync_h, &sync_g, &sync_r);
@@ -200,6 +212,7 @@ int main(int argc, char **argv)
     if (closure && !stack) { std::fprintf(stderr, "--closure needs --stack\n"); return 1; }
     if (locate && !stack) { std::fprintf(stderr, "--locate needs --stack\n"); return 1; }
     if (locate_track && !locate) { std::fprintf(stderr, "--locate-track needs --stack --locate\n"); return 1; }
+    if (emitters && !locate) { std::fprintf(stderr, "--emitters needs --stack --locate\n"); return 1; }
     if (sync && !locate) { std::fprintf(stderr, "--sync needs --stack --locate\n"); return 1; }
     if (sync && stack_m != 0) { std::fprintf(stderr, "--sync needs whole-block stacks: --stack without =WINDOWS\n"); return 1; }
     if (pos.size() < 4) {                                     // processor.go:1048-1052
@@ -373,6 +386,7 @@ int main(int argc, char **argv)
         std::vector<tdoa_cell_track> ltracks;    // --locate-track: one record per block, a cell and its own score per stack
         std::vector<int32_t> lt_cells;           // (tdoa_process_locate_track)
         std::vector<int64_t> lt_own;
+        std::vector<tdoa_location> mlocs;        // --emitters: one record per round and stack (tdoa_process_locate_multi)
         std::vector<tdoa_sync> syncs;            // --sync: one record and S clocks per block (tdoa_process_sync)
         std::vector<int32_t> clocks;
         double grid_lat0 = 0, grid_lon0 = 0, grid_dlat = 0, grid_dlon = 0;
@@ -441,6 +455,11 @@ int main(int argc, char **argv)
                 }
                 locs.resize((size_t)n_stacks);
                 if ((rc = tdoa_process_locate(ctx, stack_m, 1, locs.data(), nullptr, nullptr, nullptr))) return die("tdoa_process_locate", rc);
+                if (emitters) {
+                    mlocs.resize((size_t)emitters_k * n_stacks);
+                    if ((rc = tdoa_process_locate_multi(ctx, stack_m, emitters_k, emitters_guard, 1, mlocs.data(), nullptr, nullptr, nullptr)))
+                        return die("tdoa_process_locate_multi", rc);
+                }
                 if (locate_track) {
                     ltracks.resize((size_t)(n_stacks / spb));
                     lt_cells.resize((size_t)n_stacks);
@@ -542,6 +561,15 @@ int main(int argc, char **argv)
                         (int)sid % spb, (int)l.cell, grid_lat0 + (l.cell / locate_cols) * grid_dlat, grid_lon0 + (l.cell % locate_cols) * grid_dlon,
                         (int)l.pairs_in, l.score, l.runner_up);
         }
+        // --emitters: a fix per round, the stack's rounds together; a round that found nothing prints cell=-1
+        for (size_t sid = 0; sid < mlocs.size() / (size_t)emitters_k; sid++)
+            for (int r = 0; r < emitters_k; r++) {
+                const tdoa_location &l = mlocs[(size_t)r * n_stacks + sid];
+                const int cell = l.score_q > 0 ? (int)l.cell : -1;
+                std::printf("LOCATE-MULTI block %d stack %d round %d: cell=%d lat=%.6f lon=%.6f pairs=%d excluded=%d score=%.6f runner=%.6f\n",
+                            (int)sid / spb + 1, (int)sid % spb, r, cell, grid_lat0 + (l.cell / locate_cols) * grid_dlat,
+                            grid_lon0 + (l.cell % locate_cols) * grid_dlon, (int)l.pairs_in, (int)l.reserved, l.score, l.runner_up);
+            }
         // --locate-track: the block's track, then its cell in every stack with the stack's own score there (on the stack's scale)
         for (size_t b = 0; b < ltracks.size(); b++) {
             const tdoa_cell_track &t = ltracks[b];

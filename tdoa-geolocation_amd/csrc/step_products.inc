@@ -4,7 +4,8 @@
 // delay track through a stack's windows (tdoa_process_track), one consistent lag set per station triple of a stack
 // (tdoa_process_closure), a table of candidate positions scored on all pairs' stacks (tdoa_process_locate), the stations'
 // clock offsets from a block whose emitter is known (tdoa_process_sync), the best track of cells through the stacks of a
-// block on the delay-table search's maps (tdoa_process_locate_track).  Every product
+// block on the delay-table search's maps (tdoa_process_locate_track), several emitters per stack found one after the other on
+// masked lags (tdoa_process_locate_multi).  Every product
 // is a struct derived from StepProduct: the entry point fills it, process_impl calls its six hooks in this order (a product
 // overrides the ones it needs; process_impl without a product writes the peak records only):
 //   reserve   its buffers, after the step's grouping is fixed (batch_bound counts them as held, so a later call groups as
@@ -37,7 +38,7 @@ struct StepView {
 
 // the product of one step; the numbers are the first word a product appends to the graph key
 struct StepProduct {
-    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6, Locate = 7, Sync = 8, CellTrack = 9 };
+    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6, Locate = 7, Sync = 8, CellTrack = 9, LocateMulti = 10 };
     virtual int reserve(const StepView &v) = 0;
     virtual void key(std::vector<uint64_t> *key) const = 0;
     virtual int upload(const StepView &) { return TDOA_OK; }
@@ -424,6 +425,34 @@ struct LocateProduct : StackProduct {
     int download(const StepView &v) const override
     {
         return download_locate(v.ctx, layout.n_stacks, locate_geom(v.ctx, sep), loc_host, lags_host, corr_host, map_host);
+    }
+};
+
+// ---- several emitters per stack: the search's rounds on masked lags (stack_locate_multi.hpp, locate_multi_api.inc) --------
+// The outputs are [round][stack] planes; the excluded intervals' centres stay on the device.
+struct LocateMultiProduct : LocateProduct {
+    int K = 1, guard = 0;                    // n_emitters, guard: in the key (the launches and the mask; the centres are data)
+
+    int reserve(const StepView &v) override
+    {
+        if (int rc = StackProduct::reserve(v)) return rc;
+        return ensure_locate_multi(v.ctx, layout.n_stacks, K, locate_geom(v.ctx, sep));
+    }
+    void key(std::vector<uint64_t> *key) const override
+    {
+        key->insert(key->end(), {LocateMulti, (uint64_t)m, (uint64_t)K, (uint64_t)guard, (uint64_t)sep,
+                                 (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked});
+    }
+    void enqueue(const StepView &v) const override
+    {
+        tdoa_ctx *ctx = v.ctx;
+        StackProduct::enqueue(v);
+        launch_locate_multi(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, layout.n_stacks, v.P).roots, layout.n_stacks, K, guard,
+                            locate_geom(ctx, sep));
+    }
+    int download(const StepView &v) const override
+    {
+        return download_locate_multi(v.ctx, layout.n_stacks, K, locate_geom(v.ctx, sep), loc_host, lags_host, corr_host, map_host);
     }
 };
 

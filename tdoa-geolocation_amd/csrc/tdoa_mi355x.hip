@@ -40,6 +40,7 @@
 #include "stack_track.hpp"
 #include "stack_closure.hpp"
 #include "stack_locate.hpp"
+#include "stack_locate_multi.hpp"
 #include "stack_sync.hpp"
 #include "stack_cell_track.hpp"
 
@@ -172,6 +173,9 @@ struct tdoa_ctx {
     // ... and the stacks' station clocks as the kernels take them, clock[j] - clock[i] per [stack][pair] (state:
     // tdoa_locate_set_clock; 0 stacks: none)
     DevBuf locate_clock;
+    // several emitters per stack (tdoa_process_locate_multi): the buffers above hold one plane per round, and the excluded
+    // intervals' centres [stack][pair][round]
+    DevBuf locate_centres;
     // cell tracks (tdoa_process_locate_track): the steps D [stack][cell][2], the two halves of T [track][cell], sqrt(N_w) per
     // track, the records [track], the tracks' cells and own scores [stack]
     DevBuf ctrack_d, ctrack_t, ctrack_roots, ctrack_out, ctrack_cells, ctrack_own;
@@ -191,6 +195,7 @@ static_assert(sizeof(FmStats) == sizeof(tdoa_fm_stats), "tdoa_fm_stats layout");
 static_assert(sizeof(ClosureOut) == sizeof(tdoa_closure) && sizeof(tdoa_closure) == 80, "tdoa_closure layout");
 static_assert(sizeof(LocateOut) == sizeof(tdoa_location) && sizeof(tdoa_location) == 48, "tdoa_location layout");
 static_assert(kLocateDelayUnit == TDOA_DELAY_UNIT, "the table's unit");
+static_assert(kLocateMaxEmitters == TDOA_LOCATE_MAX_EMITTERS, "the rounds of tdoa_process_locate_multi");
 static_assert(sizeof(SyncOut) == sizeof(tdoa_sync) && sizeof(tdoa_sync) == 32, "tdoa_sync layout");
 static_assert(sizeof(CellTrackOut) == sizeof(tdoa_cell_track) && sizeof(tdoa_cell_track) == 48, "tdoa_cell_track layout");
 
@@ -377,6 +382,7 @@ int check_selection(tdoa_ctx *ctx, int k, int min_separation, const void *out)
 #include "closure_api.inc"
 #include "locate_api.inc"
 #include "locate_track_api.inc"
+#include "locate_multi_api.inc"
 #include "sync_api.inc"
 #include "step_products.inc"
 
@@ -538,7 +544,7 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->locate_map, &ctx->locate_part, &ctx->locate_best, &ctx->locate_out, &ctx->locate_lags, &ctx->locate_corr,
                       &ctx->locate_clock, &ctx->sync_in, &ctx->sync_part, &ctx->sync_out, &ctx->sync_clock, &ctx->sync_lags,
                       &ctx->sync_corr, &ctx->debug_q, &ctx->debug_roots, &ctx->ctrack_d, &ctx->ctrack_t, &ctx->ctrack_roots,
-                      &ctx->ctrack_out, &ctx->ctrack_cells, &ctx->ctrack_own};
+                      &ctx->ctrack_out, &ctx->ctrack_cells, &ctx->ctrack_own, &ctx->locate_centres};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1160,6 +1166,29 @@ int tdoa_process_locate_track(tdoa_ctx *ctx, int windows_per_stack, int max_step
     prod.lags_host = lags_host;
     prod.corr_host = corr_host;
     prod.total_host = total_host;
+    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
+}
+
+int tdoa_process_locate_multi(tdoa_ctx *ctx, int windows_per_stack, int n_emitters, int guard, int min_separation, tdoa_location *loc_host,
+                              int32_t *lags_host, double *corr_host, int64_t *map_host)
+{
+    if (int rc = refuse_stacked(ctx, windows_per_stack, check_locate_multi_args(n_emitters, guard, min_separation, loc_host),
+                                "the delay-table search with TDOA_LAGS_GO", true))
+        return rc;
+    const char *what = nullptr;              // (what the search refuses: shared with the group's call)
+    if (const int rc = check_locate_state(ctx, windows_per_stack, &what)) return fail(ctx, rc, what);
+    LocateMultiProduct prod;
+    fill_stack(&prod, windows_per_stack);
+    prod.sep = min_separation;
+    prod.n_cells = ctx->locate_cells;
+    prod.n_cols = ctx->locate_cols;
+    prod.clocked = ctx->clock_stacks != 0;
+    prod.K = n_emitters;
+    prod.guard = guard;
+    prod.loc_host = loc_host;
+    prod.lags_host = lags_host;
+    prod.corr_host = corr_host;
+    prod.map_host = map_host;
     return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
 }
 

@@ -113,6 +113,7 @@ SYMBOLS = [
     "tdoa_locate_set_clock", "tdoa_group_locate_set_clock", "tdoa_process_sync", "tdoa_debug_sync_from_q",
     "tdoa_process_locate_track", "tdoa_debug_locate_track_from_q", "tdoa_group_process_locate_track",
     "tdoa_group_process_sync",
+    "tdoa_process_locate_multi", "tdoa_debug_locate_multi_from_q", "tdoa_group_process_locate_multi",
 ]
 
 _lib = None
@@ -240,6 +241,9 @@ def load(build_if_missing=True):
     L.tdoa_group_process_sync.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, vp, i32p, i32p, dp]
     L.tdoa_process_locate_track.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, i32p, i64p, i32p, dp, i64p]
     L.tdoa_group_process_locate_track.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, i32p, i64p, i32p, dp, i64p]
+    L.tdoa_process_locate_multi.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p, dp, i64p]
+    L.tdoa_group_process_locate_multi.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p, dp, i64p]
+    L.tdoa_debug_locate_multi_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p, dp, i64p]
     L.tdoa_debug_locate_track_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p, i64p, i32p,
                                                  dp, i64p]
     L.tdoa_debug_sync_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, vp, i32p, i32p, dp]
@@ -720,6 +724,30 @@ class Context:
                                                          int(n_w), int(max_step), int(min_separation), *_locate_track_ptrs(out)))
         return out
 
+    def process_locate_multi(self, windows_per_stack=0, n_emitters=1, guard=0, min_separation=1, want_map=False):
+        """tdoa_process_locate_multi -> process_locate's dict with a leading axis of n_emitters rounds: "loc" [K][n_stacks],
+        "lags" and "corr" [K][n_stacks][P], with want_map "map" [K][n_stacks][n_cells].  Round r searches with the lags within
+        `guard` of the earlier rounds' cells' lags counting 0 in every pair"""
+        _, n = self.num_stacks(windows_per_stack)
+        out = _locate_multi_outputs(n_emitters, n, self.num_pairs(), getattr(self, "_locate_cells", 0), want_map)
+        self._chk(self._L.tdoa_process_locate_multi(self._h, int(windows_per_stack), int(n_emitters), int(guard), int(min_separation),
+                                                    *_locate_ptrs(out)))
+        return out
+
+    def locate_multi_from_q(self, q, n_stations, n_w=1, n_emitters=1, guard=0, min_separation=1, want_map=True):
+        """tdoa_debug_locate_multi_from_q: the rounds' kernels on the caller's words q [n_sets][P][2 max_lag - 1] int64 (or one
+        set [P][2 max_lag - 1]) with the context's table and clocks -> what process_locate_multi returns, n_sets for n_stacks"""
+        q = np.ascontiguousarray(q, dtype=np.int64)
+        if q.ndim == 2:
+            q = q[None]
+        S = int(n_stations)
+        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
+            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
+        out = _locate_multi_outputs(n_emitters, q.shape[0], q.shape[1], getattr(self, "_locate_cells", 0), want_map)
+        self._chk(self._L.tdoa_debug_locate_multi_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], S, int(n_w),
+                                                         int(n_emitters), int(guard), int(min_separation), *_locate_ptrs(out)))
+        return out
+
     def fm_xcorr_peaks(self, iq1, iq2, max_lag, k, min_separation):
         """tdoa_fm_xcorr_peaks_u8 -> (peaks [k] PEAK_DTYPE, count) of one pair of windows"""
         a = np.ascontiguousarray(iq1, dtype=np.uint8)
@@ -897,6 +925,15 @@ def _locate_ptrs(out):
             out["map"].ctypes.data_as(C.POINTER(C.c_int64)) if "map" in out else None)
 
 
+def _locate_multi_outputs(n_emitters, n_sets, p, n_cells, want_map):
+    k = min(max(int(n_emitters), 1), 8)      # (a count out of range is refused by the library; the arrays only have to exist)
+    out = {"loc": np.zeros((k, n_sets), dtype=LOCATION_DTYPE), "lags": np.zeros((k, n_sets, p), dtype=np.int32),
+           "corr": np.zeros((k, n_sets, p), dtype=np.float64)}
+    if want_map:
+        out["map"] = np.zeros((k, n_sets, n_cells), dtype=np.int64)
+    return out
+
+
 def _locate_track_outputs(n_sets, track_len, p, n_cells, want_total):
     n_tracks = max(n_sets // track_len, 1)
     out = {"track": np.zeros(n_tracks, dtype=CELL_TRACK_DTYPE), "cells": np.zeros((n_tracks, track_len), dtype=np.int32),
@@ -1053,6 +1090,15 @@ class Group:
         out = _locate_track_outputs(n, per_block, m.num_pairs(), getattr(self, "_locate_cells", 0), want_total)
         self._chk(self._L.tdoa_group_process_locate_track(self._h, int(windows_per_stack), int(max_step), int(min_separation),
                                                           *_locate_track_ptrs(out)))
+        return out
+
+    def process_locate_multi(self, windows_per_stack=0, n_emitters=1, guard=0, min_separation=1, want_map=False):
+        """tdoa_group_process_locate_multi -> Context.process_locate_multi's outputs, byte-identical to a single context's"""
+        m = self.member(0)
+        _, n = m.num_stacks(windows_per_stack)
+        out = _locate_multi_outputs(n_emitters, n, m.num_pairs(), getattr(self, "_locate_cells", 0), want_map)
+        self._chk(self._L.tdoa_group_process_locate_multi(self._h, int(windows_per_stack), int(n_emitters), int(guard),
+                                                          int(min_separation), *_locate_ptrs(out)))
         return out
 
     def process_sync(self, ref_delay, windows_per_stack=0, gate=0, rounds=0, centre=None):
