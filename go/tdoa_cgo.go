@@ -316,6 +316,52 @@ func (g *gpuCorrelator) ProcessLocateTrack(windowsPerStack, maxStep, minSeparati
 	return track, cells, own, lags, corr, nil
 }
 
+// TrackRounds holds what ProcessLocateTrackMulti returns, every slice with the round as its first index: Track
+// [round][block], Cells and Own [round][block][stacks per block], Pairs [round][stack][2] (pairs_in, reserved), Lags and Corr
+// [round][stack][pair].
+type TrackRounds struct {
+	Track []C.tdoa_cell_track
+	Cells []int32
+	Own   []int64
+	Pairs []int32
+	Lags  []int32
+	Corr  []float64
+}
+
+func newTrackRounds(nEmitters, total, perBlock, pairs int) *TrackRounds {
+	return &TrackRounds{
+		Track: make([]C.tdoa_cell_track, nEmitters*(total/perBlock)),
+		Cells: make([]int32, nEmitters*total),
+		Own:   make([]int64, nEmitters*total),
+		Pairs: make([]int32, nEmitters*total*2),
+		Lags:  make([]int32, nEmitters*total*pairs),
+		Corr:  make([]float64, nEmitters*total*pairs),
+	}
+}
+
+// ProcessLocateTrackMulti finds up to nEmitters emitters per block as cell tracks (the header's "several emitters per
+// block"): round 0 is ProcessLocateTrack's track, every later round tracks again with the lags within guard of the earlier
+// rounds' tracks' lags counting 0 in every stack's pairs.  An excluded pair reports its lag and 0.0, so tdoa_solve_surface
+// gives it no weight.
+func (g *gpuCorrelator) ProcessLocateTrackMulti(windowsPerStack, maxStep, nEmitters, guard, minSeparation int) (*TrackRounds, error) {
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs := int(C.tdoa_num_pairs(g.ctx))
+	if int(total)*pairs == 0 || nEmitters < 1 {
+		return nil, fmt.Errorf("tdoa_process_locate_track_multi: no stacks, fewer than two stations or no rounds")
+	}
+	r := newTrackRounds(nEmitters, int(total), int(perBlock), pairs)
+	if rc := C.tdoa_process_locate_track_multi(g.ctx, C.int(windowsPerStack), C.int(maxStep), C.int(nEmitters), C.int(guard),
+		C.int(minSeparation), &r.Track[0], (*C.int32_t)(unsafe.Pointer(&r.Cells[0])), (*C.int64_t)(unsafe.Pointer(&r.Own[0])),
+		(*C.int32_t)(unsafe.Pointer(&r.Pairs[0])), (*C.int32_t)(unsafe.Pointer(&r.Lags[0])), (*C.double)(unsafe.Pointer(&r.Corr[0])),
+		nil); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_process_locate_track_multi: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return r, nil
+}
+
 // LocateSetClock hands the context the stations' clocks for the delay-table search, [nStacks][nStations] in units of 1/16
 // sample (nil: forget them): stack sid's lags are taken from (t[c][j] - t[c][i]) + (clock[sid][j] - clock[sid][i]).  One row per
 // stack of the searches that follow; ProcessSync's clocks times 16, or 8*(before + after) for the block between two
@@ -541,6 +587,28 @@ func (g *Group) ProcessLocateTrack(windowsPerStack, maxStep, minSeparation int) 
 		return nil, nil, nil, nil, nil, fmt.Errorf("tdoa_group_process_locate_track: %s", C.GoString(C.tdoa_group_last_error(g.g)))
 	}
 	return track, cells, own, lags, corr, nil
+}
+
+// ProcessLocateTrackMulti is gpuCorrelator.ProcessLocateTrackMulti over the group: the members' fixed-point partial sums are
+// added on the host and tracked on member 0, the same bytes one context returns.
+func (g *Group) ProcessLocateTrackMulti(windowsPerStack, maxStep, nEmitters, guard, minSeparation int) (*TrackRounds, error) {
+	m := C.tdoa_group_member(g.g, 0)
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(m, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs := int(C.tdoa_num_pairs(m))
+	if int(total)*pairs == 0 || nEmitters < 1 {
+		return nil, fmt.Errorf("tdoa_group_process_locate_track_multi: no stacks, fewer than two stations or no rounds")
+	}
+	r := newTrackRounds(nEmitters, int(total), int(perBlock), pairs)
+	if rc := C.tdoa_group_process_locate_track_multi(g.g, C.int(windowsPerStack), C.int(maxStep), C.int(nEmitters), C.int(guard),
+		C.int(minSeparation), &r.Track[0], (*C.int32_t)(unsafe.Pointer(&r.Cells[0])), (*C.int64_t)(unsafe.Pointer(&r.Own[0])),
+		(*C.int32_t)(unsafe.Pointer(&r.Pairs[0])), (*C.int32_t)(unsafe.Pointer(&r.Lags[0])), (*C.double)(unsafe.Pointer(&r.Corr[0])),
+		nil); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_group_process_locate_track_multi: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return r, nil
 }
 
 // LocateSetClock hands every member the stations' clocks (gpuCorrelator.LocateSetClock).

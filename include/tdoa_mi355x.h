@@ -669,7 +669,7 @@ int tdoa_debug_locate_track_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, 
  * Identity (held by the tests): round 0, and therefore the whole call with K = 1, returns tdoa_process_locate's bytes --
  *   record, lags, correlations, map.  reserved is 0 there.
  * The outputs are laid out [round][stack][...].  It joins nothing across stacks: combining it with tdoa_process_locate_track
- * is out of scope.
+ * is out of scope.  tdoa_process_locate_track_multi below is the call that runs the rounds on a block's tracks.
  * Runs inside the step graph, behind the stack's accumulation: round 0 as tdoa_process_locate launches it, then per further
  * round the masked scores, the runner-up's pass and two finishing launches.  (windows_per_stack, K, guard, min_separation,
  * n_cells, n_cols, whether a clock table is present) are part of the graph's key; the table, the clocks and the excluded
@@ -690,6 +690,60 @@ int tdoa_process_locate_multi(tdoa_ctx *ctx, int windows_per_stack, int n_emitte
  * n_emitters outside 1 .. 8 and guard < 0 (TDOA_ERR_INVALID). */
 int tdoa_debug_locate_multi_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int n_emitters,
                                    int guard, int min_separation, tdoa_location *loc, int32_t *lags, double *corr, int64_t *map);
+
+/* Several emitters per block: mask a found track's lags and track again.  tdoa_process_locate_multi finds a second emitter
+ * only where a single stack shows it, and the runner-up of tdoa_process_locate_track is no second emitter, because emitter
+ * A's ridges survive the sum over stacks.  Taking the lags of A's track out of every stack's pairs and tracking again finds
+ * a weaker emitter B that no single stack shows, and lets both move.
+ * Stacks, windows_per_stack, n_w, tracks (one per block, L = stacks per block), the table, the clocks, lag_p(c) with the
+ * stack's clocks, Q, the recurrence T_j[c] = s_j[c] + max T_{j+1}[neighbour] with its tie order, and the record
+ * tdoa_cell_track are exactly tdoa_process_locate_track's.
+ * K = n_emitters, 1 <= K <= TDOA_LOCATE_MAX_EMITTERS.  Per track, rounds r = 0 .. K-1:
+ *   E_p^j(r) is the set of excluded lags of pair p in stack j of the track.  E_p^j(0) is empty.
+ *   M_p^{j,r}[l] = 0 for l in E_p^j(r) or outside the range, else |Q_p^j[l]|.
+ *   s_j^r(c) = the sum over all P pairs of M_p^{j,r}[lag_p^j(c)].
+ *   Round r's track is the cell track on the maps s_0^r .. s_{L-1}^r: T^r, D^r, L_0^r the cell of the largest T_0^r, equal
+ *     maxima going to the smaller cell.  The walk is L_{j+1}^r = L_j^r + D_j^r[L_j^r].  The runner-up is the largest T_0^r
+ *     beyond min_separation of L_0^r.  own_j^r = s_j^r[L_j^r].
+ *   If max T_0^r > 0: E_p^j(r+1) = E_p^j(r) united with { l : |l - lag_p^j(L_j^r)| <= guard } for every stack j and every
+ *     pair whose lag there lies inside the range.  Intervals are clipped at the range edges and may overlap.  Otherwise
+ *     E(r+1) = E(r): the round returns the zero record and zero per-position outputs, and so does every later round.
+ *   Per (round, stack): pairs_in counts the pairs inside the range and not excluded at L_j^r, reserved the pairs inside but
+ *     excluded there.  An excluded pair reports its lag and 0.0; a pair outside reports 0 and 0.0.
+ *   Q is never written.
+ * Identities (held by the tests):
+ *   Round 0 is tdoa_process_locate_track's bytes: record, cells, own, lags, corr, total.  So is the whole call with K = 1.
+ *     There pairs_in is the count of pairs inside and reserved is 0.
+ *   With one stack per track (L = 1), every round equals tdoa_process_locate_multi's round in cell, runner_cell, score_q,
+ *     runner_q, score, runner_up, the lags and correlations byte for byte, pairs_in and reserved, and the map as total;
+ *     positions = 1 and steps = 0.
+ * Outputs are laid out [round][...].  A round is judged by its own runner-up; there is no stop rule.
+ * Runs inside the step graph, behind the stack's accumulation: round 0 as tdoa_process_locate_track launches it and one
+ * launch for the centres its track gives, then per further round the masked scores, the recurrence's L-1 launches, the best
+ * cell, the runner-up's pass and two finishing launches.  (windows_per_stack, max_step, K, guard, min_separation, n_cells,
+ * n_cols, whether a clock table is present) are part of the graph's key; the table, the clocks and the excluded intervals
+ * are data.  tdoa_group_process_locate_track_multi is the group form.
+ * TDOA_ERR_INVALID (no device needed): what tdoa_process_locate_track refuses, n_emitters outside 1 .. 8, guard < 0.  Every
+ * other refusal is tdoa_process_locate_track's.  TDOA_ERR_NOMEM: besides what tdoa_process_locate_track needs, the call holds
+ * 8 bytes per (track, cell) for every round's T_0 (L = 1: the map of every round); tdoa_last_error names what did not fit,
+ * the rounds included. */
+int tdoa_process_locate_track_multi(tdoa_ctx *ctx, int windows_per_stack, int max_step /* J */, int n_emitters /* K */,
+                                    int guard /* >= 0 lags */, int min_separation,
+                                    tdoa_cell_track *track_host /* [K][n_tracks], required */,
+                                    int32_t *cells_host /* [K][n_tracks][L]; may be NULL */,
+                                    int64_t *own_host   /* [K][n_tracks][L]; may be NULL */,
+                                    int32_t *pairs_host /* [K][n_stacks_total][2]: pairs_in, reserved; may be NULL */,
+                                    int32_t *lags_host  /* [K][n_stacks_total][n_pairs]; may be NULL */,
+                                    double  *corr_host  /* same shape; may be NULL */,
+                                    int64_t *total_host /* [K][n_tracks][n_cells]: T_0^r; may be NULL */);
+
+/* tests only: the same kernels on the caller's words q [n_sets][P][2*max_lag-1] as tdoa_debug_locate_track_from_q takes them,
+ * with its preconditions and the context's table and clocks; outputs [K][...] with n_sets for n_stacks_total.  Needs no
+ * captures.  Errors as tdoa_debug_locate_track_from_q's, plus n_emitters outside 1 .. 8 and guard < 0 (TDOA_ERR_INVALID). */
+int tdoa_debug_locate_track_multi_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w,
+                                         int max_step, int n_emitters, int guard, int min_separation, tdoa_cell_track *track,
+                                         int32_t *cells, int64_t *own, int32_t *pairs, int32_t *lags, double *corr,
+                                         int64_t *total);
 
 /* Capture-quality statistics of every (window, station) in one streaming pass over the bytes
  * in HBM: the byte statistics of fastAnalyzeSamples
@@ -930,6 +984,15 @@ int tdoa_group_process_locate_track(tdoa_group *g, int windows_per_stack, int ma
  * Errors as there and as tdoa_group_process.  With one member, its call writes the outputs directly. */
 int tdoa_group_process_locate_multi(tdoa_group *g, int windows_per_stack, int n_emitters, int guard, int min_separation,
                                     tdoa_location *loc_host, int32_t *lags_host, double *corr_host, int64_t *map_host);
+
+/* tdoa_process_locate_track_multi over the members (the table and the clocks as set by tdoa_group_locate_set_table and
+ * tdoa_group_locate_set_clock): they sum their windows as in tdoa_group_process_stacked, the host adds the partials, and
+ * member 0 runs the rounds on the merged Q -- the outputs are byte-identical to tdoa_process_locate_track_multi(single ctx,
+ * ...).  Errors as there and as tdoa_group_process.  With one member, its call writes the outputs directly. */
+int tdoa_group_process_locate_track_multi(tdoa_group *g, int windows_per_stack, int max_step, int n_emitters, int guard,
+                                          int min_separation, tdoa_cell_track *track_host, int32_t *cells_host,
+                                          int64_t *own_host, int32_t *pairs_host, int32_t *lags_host, double *corr_host,
+                                          int64_t *total_host);
 
 /* the sample runs member `rank` of `world` uploads for a capture of total_samples (window grid from n_min, the shortest
  * capture of the job; block offsets from the capture's own thirds): adjacent owned windows form one run, and with fewer

@@ -18,11 +18,15 @@ that grid with the records, cells, own scores, lags and correlations downloaded 
 launches, then one launch per stack of a block but the last and four to finish).  Every `--emitters K[/GUARD]` adds a leg
 per `--locate` grid: tdoa_process_locate_multi(0, K, GUARD, 1) (GUARD defaults to 2) on that grid with the K planes of records,
 lags and correlations downloaded and the maps left on the device (the search's launches, then four per further round;
-K = 1 is the locate leg's work through the other entry).  `--stack M` gives the locate, locate-track and emitters legs stacks
+K = 1 is the locate leg's work through the other entry).  Every `--track-emitters K[/GUARD]` adds a leg per `--locate` grid and
+`--locate-track J`: tdoa_process_locate_track_multi(0, J, K, GUARD, 1) (GUARD defaults to 2) with the K planes of records, cells,
+own scores, counts, lags and correlations downloaded and every T_0 left on the device (the track's launches and one for the
+centres, then per further round the masked scores, the recurrence and four to finish; K = 1 is the locate-track leg's work
+through the other entry).  `--stack M` gives the locate, locate-track, emitters and track-emitters legs stacks
 of M windows (default 0: whole blocks, one position per track).  `--stations S` runs all legs on S
 stations (default 3; 8 gives 56 triples).
 usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--stack M] [--drift H/D]... [--track J]...
-[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--sync G[/R]]..."""
+[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--sync G[/R]]..."""
 import json
 import os
 import sys
@@ -51,7 +55,8 @@ def timed(fn, steps):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
-def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=(), locate_tracks=(), stack=0, emitters=()):
+def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=(), locate_tracks=(), stack=0, emitters=(),
+         track_emitters=()):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=20000)
     for s in range(stations):
         c.synth_capture(s, 66_666_666, ST[s % 3], TX, 0x5D0A0000 + s)
@@ -77,6 +82,10 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
             name = "process_locate_track_%dx%d_J%d_ms" % (rows, cols, J)
             setup[name] = lambda table=table, cols=cols: c.locate_set_table(table, cols)
             legs[name] = lambda J=J: c.process_locate_track(stack, J, 1)
+            for K, guard in track_emitters:
+                name = "process_locate_track_multi_%dx%d_J%d_K%d_G%d_ms" % (rows, cols, J, K, guard)
+                setup[name] = lambda table=table, cols=cols: c.locate_set_table(table, cols)
+                legs[name] = lambda J=J, K=K, guard=guard: c.process_locate_track_multi(stack, J, K, guard, 1)
         for K, guard in emitters:
             name = "process_locate_multi_%dx%d_K%d_G%d_ms" % (rows, cols, K, guard)
             setup[name] = lambda table=table, cols=cols: c.locate_set_table(table, cols)
@@ -127,6 +136,12 @@ if __name__ == "__main__":
         i = args.index("--locate-track")
         locate_tracks.append(int(args[i + 1]))
         del args[i:i + 2]
+    track_emitters = []
+    while "--track-emitters" in args:
+        i = args.index("--track-emitters")
+        k, _, g = args[i + 1].partition("/")
+        track_emitters.append((int(k), int(g or 2)))
+        del args[i:i + 2]
     emitters = []
     while "--emitters" in args:
         i = args.index("--emitters")
@@ -145,4 +160,5 @@ if __name__ == "__main__":
         g, _, r = args[i + 1].partition("/")
         syncs.append((int(g), int(r or 2)))
         del args[i:i + 2]
-    main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs, locate_tracks, opt["--stack"], emitters)
+    main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs, locate_tracks, opt["--stack"], emitters,
+         track_emitters)

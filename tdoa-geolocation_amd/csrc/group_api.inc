@@ -416,6 +416,32 @@ int tdoa_group_process_locate_multi(tdoa_group *g, int windows_per_stack, int n_
     return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
 }
 
+// tdoa_process_locate_track_multi over the members: their shares of the fixed-point sums as in tdoa_group_process_stacked,
+// added on the host; member 0 runs the rounds on the merged Q with the kernels a single context's call ends with.
+int tdoa_group_process_locate_track_multi(tdoa_group *g, int windows_per_stack, int max_step, int n_emitters, int guard, int min_separation,
+                                          tdoa_cell_track *track_host, int32_t *cells_host, int64_t *own_host, int32_t *pairs_host,
+                                          int32_t *lags_host, double *corr_host, int64_t *total_host)
+{
+    if (!g) return TDOA_ERR_INVALID;
+    if (windows_per_stack < 0) return group_fail(g, TDOA_ERR_INVALID, "windows_per_stack < 0");
+    if (const char *bad = check_locate_track_multi_args(max_step, n_emitters, guard, min_separation, track_host))
+        return group_fail(g, TDOA_ERR_INVALID, bad);
+    const int world = (int)g->members.size();
+    tdoa_ctx *c0 = g->members[0];
+    if (world == 1) {                        // no merge: the member's call writes the outputs
+        const int rc = tdoa_process_locate_track_multi(c0, windows_per_stack, max_step, n_emitters, guard, min_separation, track_host,
+                                                       cells_host, own_host, pairs_host, lags_host, corr_host, total_host);
+        return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
+    }
+    const char *what = nullptr;
+    if (const int rc = check_locate_track_state(c0, windows_per_stack, &what)) return group_fail(g, rc, member_name(0, c0->device) + what);
+    const int64_t *sum = nullptr;
+    if (const int rc = group_merged_q(g, windows_per_stack, &sum)) return rc;
+    const int rc = locate_track_multi_from_host(c0, sum, windows_per_stack, max_step, n_emitters, guard, min_separation, track_host,
+                                                cells_host, own_host, pairs_host, lags_host, corr_host, total_host);
+    return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
+}
+
 // the clocks to every member: each keeps its own copy, member 0's is the one a group of several searches with
 int tdoa_group_locate_set_clock(tdoa_group *g, const int32_t *clock, int n_stacks, int n_stations)
 {

@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -141,6 +141,10 @@ int main(int argc, char **argv)
     // fixes' lags counting 0 in every pair (tdoa_process_locate_multi)
     bool emitters = false;
     int emitters_k = 1, emitters_guard = 2;
+    // --track-emitters=K[/GUARD] (with --stack --locate --locate-track): per block K tracks, each tracked with the lags within
+    // GUARD of the earlier tracks' lags counting 0 in every stack's pairs (tdoa_process_locate_track_multi)
+    bool track_emitters = false;
+    int temitters_k = 1, temitters_guard = 2;
     bool sync = false;
     double sync_lat = 0, sync_lon = 0, sync_h = 0;
     int sync_g = 128, sync_r = 2;
@@ -191,6 +195,14 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
+        else if (a.rfind("--track-emitters=", 0) == 0) {
+            track_emitters = true;
+            const int got = std::sscanf(a.c_str() + 17, "%d/%d", &temitters_k, &temitters_guard);
+            if (got < 1 || temitters_k < 1 || temitters_k > TDOA_LOCATE_MAX_EMITTERS || temitters_guard < 0) {
+                std::fprintf(stderr, "--track-emitters=K[/GUARD] with K in 1 .. 8 and GUARD >= 0, e.g. --track-emitters=2/2\n");
+                return 1;
+            }
+        }
         else if (a.rfind("--sync=", 0) == 0) {
             sync = true;
             const int got = std::sscanf(a.c_str() + 7, "%lf,%lf,%lf/%d/%d", &sync_lat, &sync_lon, &sync_h, &sync_g, &sync_r);
@@ -213,6 +225,7 @@ int main(int argc, char **argv)
     if (locate && !stack) { std::fprintf(stderr, "--locate needs --stack\n"); return 1; }
     if (locate_track && !locate) { std::fprintf(stderr, "--locate-track needs --stack --locate\n"); return 1; }
     if (emitters && !locate) { std::fprintf(stderr, "--emitters needs --stack --locate\n"); return 1; }
+    if (track_emitters && !locate_track) { std::fprintf(stderr, "--track-emitters needs --stack --locate --locate-track\n"); return 1; }
     if (sync && !locate) { std::fprintf(stderr, "--sync needs --stack --locate\n"); return 1; }
     if (sync && stack_m != 0) { std::fprintf(stderr, "--sync needs whole-block stacks: --stack without =WINDOWS\n"); return 1; }
     if (pos.size() < 4) {                                     // processor.go:1048-1052
@@ -387,6 +400,9 @@ int main(int argc, char **argv)
         std::vector<int32_t> lt_cells;           // (tdoa_process_locate_track)
         std::vector<int64_t> lt_own;
         std::vector<tdoa_location> mlocs;        // --emitters: one record per round and stack (tdoa_process_locate_multi)
+        std::vector<tdoa_cell_track> mtracks;    // --track-emitters: one record per round and block, a cell, its own score and the
+        std::vector<int32_t> mt_cells, mt_pairs; // pairs' counts per round and stack (tdoa_process_locate_track_multi)
+        std::vector<int64_t> mt_own;
         std::vector<tdoa_sync> syncs;            // --sync: one record and S clocks per block (tdoa_process_sync)
         std::vector<int32_t> clocks;
         double grid_lat0 = 0, grid_lon0 = 0, grid_dlat = 0, grid_dlon = 0;
@@ -467,6 +483,15 @@ int main(int argc, char **argv)
                     if ((rc = tdoa_process_locate_track(ctx, stack_m, ltrack_j, ltrack_sep, ltracks.data(), lt_cells.data(), lt_own.data(), nullptr,
                                                         nullptr, nullptr)))
                         return die("tdoa_process_locate_track", rc);
+                }
+                if (track_emitters) {
+                    mtracks.resize((size_t)temitters_k * (n_stacks / spb));
+                    mt_cells.resize((size_t)temitters_k * n_stacks);
+                    mt_own.resize((size_t)temitters_k * n_stacks);
+                    mt_pairs.resize((size_t)temitters_k * n_stacks * 2);
+                    if ((rc = tdoa_process_locate_track_multi(ctx, stack_m, ltrack_j, temitters_k, temitters_guard, ltrack_sep, mtracks.data(),
+                                                              mt_cells.data(), mt_own.data(), mt_pairs.data(), nullptr, nullptr, nullptr)))
+                        return die("tdoa_process_locate_track_multi", rc);
                 }
             }
         }
@@ -583,6 +608,25 @@ int main(int argc, char **argv)
                             (double)lt_own[sid] / 4294967296.0 / std::sqrt((double)stacks.n_w((int)sid)));
             }
         }
+        // --track-emitters: a track per block and round, the block's rounds together, each followed by its positions; a round
+        // that found nothing prints cell=-1
+        const size_t n_blocks = mtracks.empty() ? 0 : (size_t)(n_stacks / spb);
+        for (size_t b = 0; b < n_blocks; b++)
+            for (int r = 0; r < temitters_k; r++) {
+                const tdoa_cell_track &t = mtracks[(size_t)r * n_blocks + b];
+                const bool found = t.score_q > 0;
+                std::printf("LOCATE-TRACK-MULTI block %d round %d: cell=%d positions=%d steps=%d score=%.6f runner=%.6f runner_cell=%d\n",
+                            (int)b + 1, r, found ? (int)t.cell : -1, (int)t.positions, (int)t.steps, t.score, t.runner_up, (int)t.runner_cell);
+                for (int j = 0; j < spb; j++) {
+                    const size_t sid = b * spb + j, at = (size_t)r * n_stacks + sid;
+                    const int cell = mt_cells[at];
+                    std::printf("LOCATE-TRACK-MULTI block %d round %d stack %d: cell=%d lat=%.6f lon=%.6f own=%.6f pairs=%d excluded=%d\n",
+                                (int)b + 1, r, j, found ? cell : -1, grid_lat0 + (cell / locate_cols) * grid_dlat,
+                                grid_lon0 + (cell % locate_cols) * grid_dlon,
+                                (double)mt_own[at] / 4294967296.0 / std::sqrt((double)stacks.n_w((int)sid)), (int)mt_pairs[2 * at],
+                                (int)mt_pairs[2 * at + 1]);
+                }
+            }
     }
 
     // ---- downstream: range differences and the position solve (processor.go:892-926)

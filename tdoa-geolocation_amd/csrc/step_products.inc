@@ -5,7 +5,8 @@
 // (tdoa_process_closure), a table of candidate positions scored on all pairs' stacks (tdoa_process_locate), the stations'
 // clock offsets from a block whose emitter is known (tdoa_process_sync), the best track of cells through the stacks of a
 // block on the delay-table search's maps (tdoa_process_locate_track), several emitters per stack found one after the other on
-// masked lags (tdoa_process_locate_multi).  Every product
+// masked lags (tdoa_process_locate_multi), several emitters per block found as cell tracks on masked lags
+// (tdoa_process_locate_track_multi).  Every product
 // is a struct derived from StepProduct: the entry point fills it, process_impl calls its six hooks in this order (a product
 // overrides the ones it needs; process_impl without a product writes the peak records only):
 //   reserve   its buffers, after the step's grouping is fixed (batch_bound counts them as held, so a later call groups as
@@ -38,7 +39,7 @@ struct StepView {
 
 // the product of one step; the numbers are the first word a product appends to the graph key
 struct StepProduct {
-    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6, Locate = 7, Sync = 8, CellTrack = 9, LocateMulti = 10 };
+    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6, Locate = 7, Sync = 8, CellTrack = 9, LocateMulti = 10, CellTrackMulti = 11 };
     virtual int reserve(const StepView &v) = 0;
     virtual void key(std::vector<uint64_t> *key) const = 0;
     virtual int upload(const StepView &) { return TDOA_OK; }
@@ -492,6 +493,36 @@ struct CellTrackProduct : LocateProduct {
     {
         return download_locate_track(v.ctx, layout.n_stacks, layout.spb, locate_geom(v.ctx, sep), track_host, cells_host, own_host, lags_host,
                                      corr_host, total_host);
+    }
+};
+
+// ---- several emitters per block: the cell tracks' rounds on masked lags (stack_locate_track_multi.hpp, -------------------
+// locate_track_multi_api.inc).  The outputs are [round] planes; the excluded intervals' centres stay on the device.
+struct CellTrackMultiProduct : CellTrackProduct {
+    int K = 1, guard = 0;                    // n_emitters, guard: in the key (the launches and the mask; the centres are data)
+    int32_t *pairs_host = nullptr;           // [round][stack][2]: pairs_in, reserved
+
+    int reserve(const StepView &v) override
+    {
+        if (int rc = StackProduct::reserve(v)) return rc;
+        return ensure_locate_track_multi(v.ctx, layout.n_stacks, layout.spb, K, locate_geom(v.ctx, sep));
+    }
+    void key(std::vector<uint64_t> *key) const override
+    {
+        key->insert(key->end(), {CellTrackMulti, (uint64_t)m, (uint64_t)J, (uint64_t)K, (uint64_t)guard, (uint64_t)sep,
+                                 (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked});
+    }
+    void enqueue(const StepView &v) const override
+    {
+        tdoa_ctx *ctx = v.ctx;
+        StackProduct::enqueue(v);
+        launch_locate_track_multi(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, layout.n_stacks, v.P).roots, layout.n_stacks,
+                                  layout.spb, J, K, guard, locate_geom(ctx, sep));
+    }
+    int download(const StepView &v) const override
+    {
+        return download_locate_track_multi(v.ctx, layout.n_stacks, layout.spb, K, locate_geom(v.ctx, sep), track_host, cells_host, own_host,
+                                           pairs_host, lags_host, corr_host, total_host);
     }
 };
 

@@ -43,6 +43,7 @@
 #include "stack_locate_multi.hpp"
 #include "stack_sync.hpp"
 #include "stack_cell_track.hpp"
+#include "stack_locate_track_multi.hpp"
 
 using namespace tdoa;
 
@@ -179,6 +180,9 @@ struct tdoa_ctx {
     // cell tracks (tdoa_process_locate_track): the steps D [stack][cell][2], the two halves of T [track][cell], sqrt(N_w) per
     // track, the records [track], the tracks' cells and own scores [stack]
     DevBuf ctrack_d, ctrack_t, ctrack_roots, ctrack_out, ctrack_cells, ctrack_own;
+    // several emitters per block (tdoa_process_locate_track_multi): the tracks' buffers above hold one plane per round (T as
+    // locate_track_multi_api.inc lays it out), and pairs_in and reserved [round][stack][2]
+    DevBuf ctrack_pairs;
     // the clock search: ref_delay and centre (kSyncMaxStations words each), the start's tiles' candidates [stack][tile], the
     // records [stack], the clocks [stack][station], the lags and correlations [stack][pair]
     DevBuf sync_in, sync_part, sync_out, sync_clock, sync_lags, sync_corr;
@@ -383,6 +387,7 @@ int check_selection(tdoa_ctx *ctx, int k, int min_separation, const void *out)
 #include "locate_api.inc"
 #include "locate_track_api.inc"
 #include "locate_multi_api.inc"
+#include "locate_track_multi_api.inc"
 #include "sync_api.inc"
 #include "step_products.inc"
 
@@ -544,7 +549,7 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->locate_map, &ctx->locate_part, &ctx->locate_best, &ctx->locate_out, &ctx->locate_lags, &ctx->locate_corr,
                       &ctx->locate_clock, &ctx->sync_in, &ctx->sync_part, &ctx->sync_out, &ctx->sync_clock, &ctx->sync_lags,
                       &ctx->sync_corr, &ctx->debug_q, &ctx->debug_roots, &ctx->ctrack_d, &ctx->ctrack_t, &ctx->ctrack_roots,
-                      &ctx->ctrack_out, &ctx->ctrack_cells, &ctx->ctrack_own, &ctx->locate_centres};
+                      &ctx->ctrack_out, &ctx->ctrack_cells, &ctx->ctrack_own, &ctx->locate_centres, &ctx->ctrack_pairs};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1189,6 +1194,34 @@ int tdoa_process_locate_multi(tdoa_ctx *ctx, int windows_per_stack, int n_emitte
     prod.lags_host = lags_host;
     prod.corr_host = corr_host;
     prod.map_host = map_host;
+    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
+}
+
+int tdoa_process_locate_track_multi(tdoa_ctx *ctx, int windows_per_stack, int max_step, int n_emitters, int guard, int min_separation,
+                                    tdoa_cell_track *track_host, int32_t *cells_host, int64_t *own_host, int32_t *pairs_host,
+                                    int32_t *lags_host, double *corr_host, int64_t *total_host)
+{
+    if (int rc = refuse_stacked(ctx, windows_per_stack, check_locate_track_multi_args(max_step, n_emitters, guard, min_separation, track_host),
+                                "the delay-table search with TDOA_LAGS_GO", true))
+        return rc;
+    const char *what = nullptr;              // (what the cell tracks refuse: shared with the group's call)
+    if (const int rc = check_locate_track_state(ctx, windows_per_stack, &what)) return fail(ctx, rc, what);
+    CellTrackMultiProduct prod;
+    fill_stack(&prod, windows_per_stack);
+    prod.sep = min_separation;
+    prod.n_cells = ctx->locate_cells;
+    prod.n_cols = ctx->locate_cols;
+    prod.clocked = ctx->clock_stacks != 0;
+    prod.J = max_step;
+    prod.K = n_emitters;
+    prod.guard = guard;
+    prod.track_host = track_host;
+    prod.cells_host = cells_host;
+    prod.own_host = own_host;
+    prod.pairs_host = pairs_host;
+    prod.lags_host = lags_host;
+    prod.corr_host = corr_host;
+    prod.total_host = total_host;
     return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
 }
 

@@ -114,6 +114,7 @@ SYMBOLS = [
     "tdoa_process_locate_track", "tdoa_debug_locate_track_from_q", "tdoa_group_process_locate_track",
     "tdoa_group_process_sync",
     "tdoa_process_locate_multi", "tdoa_debug_locate_multi_from_q", "tdoa_group_process_locate_multi",
+    "tdoa_process_locate_track_multi", "tdoa_debug_locate_track_multi_from_q", "tdoa_group_process_locate_track_multi",
 ]
 
 _lib = None
@@ -246,6 +247,9 @@ def load(build_if_missing=True):
     L.tdoa_debug_locate_multi_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p, dp, i64p]
     L.tdoa_debug_locate_track_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p, i64p, i32p,
                                                  dp, i64p]
+    L.tdoa_process_locate_track_multi.argtypes = [vp] + [C.c_int] * 5 + [vp, i32p, i64p, i32p, i32p, dp, i64p]
+    L.tdoa_group_process_locate_track_multi.argtypes = [vp] + [C.c_int] * 5 + [vp, i32p, i64p, i32p, i32p, dp, i64p]
+    L.tdoa_debug_locate_track_multi_from_q.argtypes = [vp, i64p] + [C.c_int] * 8 + [vp, i32p, i64p, i32p, i32p, dp, i64p]
     L.tdoa_debug_sync_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, vp, i32p, i32p, dp]
     L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
                                         C.POINTER(C.c_int)]
@@ -748,6 +752,35 @@ class Context:
                                                          int(n_emitters), int(guard), int(min_separation), *_locate_ptrs(out)))
         return out
 
+    def process_locate_track_multi(self, windows_per_stack=0, max_step=0, n_emitters=1, guard=0, min_separation=1, want_total=False):
+        """tdoa_process_locate_track_multi -> process_locate_track's dict with a leading axis of n_emitters rounds: "track"
+        [K][n_tracks], "cells" and "own" [K][n_tracks][L], "lags" and "corr" [K][n_stacks][P], "pairs" [K][n_stacks][2] int32
+        (pairs_in, reserved), with want_total "total" [K][n_tracks][n_cells].  Round r tracks with the lags within `guard` of
+        the earlier rounds' tracks' lags counting 0 in every stack's pairs"""
+        per_block, n = self.num_stacks(windows_per_stack)
+        out = _locate_track_multi_outputs(n_emitters, n, per_block, self.num_pairs(), getattr(self, "_locate_cells", 0), want_total)
+        self._chk(self._L.tdoa_process_locate_track_multi(self._h, int(windows_per_stack), int(max_step), int(n_emitters), int(guard),
+                                                          int(min_separation), *_locate_track_multi_ptrs(out)))
+        return out
+
+    def locate_track_multi_from_q(self, q, n_stations, track_len, n_w=1, max_step=0, n_emitters=1, guard=0, min_separation=1,
+                                  want_total=True):
+        """tdoa_debug_locate_track_multi_from_q: the rounds' kernels on the caller's words q [n_sets][P][2 max_lag - 1] int64, set
+        t track_len + j position j of track t, with the context's table and clocks -> what process_locate_track_multi returns,
+        n_sets for n_stacks"""
+        q = np.ascontiguousarray(q, dtype=np.int64)
+        if q.ndim == 2:
+            q = q[None]
+        S = int(n_stations)
+        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
+            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
+        out = _locate_track_multi_outputs(n_emitters, q.shape[0], max(int(track_len), 1), q.shape[1], getattr(self, "_locate_cells", 0),
+                                          want_total)
+        self._chk(self._L.tdoa_debug_locate_track_multi_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], int(track_len),
+                                                               S, int(n_w), int(max_step), int(n_emitters), int(guard),
+                                                               int(min_separation), *_locate_track_multi_ptrs(out)))
+        return out
+
     def fm_xcorr_peaks(self, iq1, iq2, max_lag, k, min_separation):
         """tdoa_fm_xcorr_peaks_u8 -> (peaks [k] PEAK_DTYPE, count) of one pair of windows"""
         a = np.ascontiguousarray(iq1, dtype=np.uint8)
@@ -944,6 +977,24 @@ def _locate_track_outputs(n_sets, track_len, p, n_cells, want_total):
     return out
 
 
+def _locate_track_multi_outputs(n_emitters, n_sets, track_len, p, n_cells, want_total):
+    k = min(max(int(n_emitters), 1), 8)      # (a count out of range is refused by the library; the arrays only have to exist)
+    n_tracks = max(n_sets // track_len, 1)
+    out = {"track": np.zeros((k, n_tracks), dtype=CELL_TRACK_DTYPE), "cells": np.zeros((k, n_tracks, track_len), dtype=np.int32),
+           "own": np.zeros((k, n_tracks, track_len), dtype=np.int64), "pairs": np.zeros((k, n_sets, 2), dtype=np.int32),
+           "lags": np.zeros((k, n_sets, p), dtype=np.int32), "corr": np.zeros((k, n_sets, p), dtype=np.float64)}
+    if want_total:
+        out["total"] = np.zeros((k, n_tracks, n_cells), dtype=np.int64)
+    return out
+
+
+def _locate_track_multi_ptrs(out):
+    i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    return (out["track"].ctypes.data_as(C.c_void_p), out["cells"].ctypes.data_as(i32p), out["own"].ctypes.data_as(i64p),
+            out["pairs"].ctypes.data_as(i32p), out["lags"].ctypes.data_as(i32p), _d(out["corr"]),
+            out["total"].ctypes.data_as(i64p) if "total" in out else None)
+
+
 def _locate_track_ptrs(out):
     i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
     return (out["track"].ctypes.data_as(C.c_void_p), out["cells"].ctypes.data_as(i32p), out["own"].ctypes.data_as(i64p),
@@ -1099,6 +1150,16 @@ class Group:
         out = _locate_multi_outputs(n_emitters, n, m.num_pairs(), getattr(self, "_locate_cells", 0), want_map)
         self._chk(self._L.tdoa_group_process_locate_multi(self._h, int(windows_per_stack), int(n_emitters), int(guard),
                                                           int(min_separation), *_locate_ptrs(out)))
+        return out
+
+    def process_locate_track_multi(self, windows_per_stack=0, max_step=0, n_emitters=1, guard=0, min_separation=1, want_total=False):
+        """tdoa_group_process_locate_track_multi -> Context.process_locate_track_multi's outputs, byte-identical to a single
+        context's"""
+        m = self.member(0)
+        per_block, n = m.num_stacks(windows_per_stack)
+        out = _locate_track_multi_outputs(n_emitters, n, per_block, m.num_pairs(), getattr(self, "_locate_cells", 0), want_total)
+        self._chk(self._L.tdoa_group_process_locate_track_multi(self._h, int(windows_per_stack), int(max_step), int(n_emitters),
+                                                                int(guard), int(min_separation), *_locate_track_multi_ptrs(out)))
         return out
 
     def process_sync(self, ref_delay, windows_per_stack=0, gate=0, rounds=0, centre=None):
