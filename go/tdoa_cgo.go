@@ -373,6 +373,33 @@ func (g *gpuCorrelator) LocateSetClock(clock []int32, nStacks, nStations int) er
 	return nil
 }
 
+// LocateSetStats switches the map statistics on (the header's "map statistics"): while set, ProcessLocate, ProcessLocateMulti,
+// ProcessLocateTrack and ProcessLocateTrackMulti also compute one tdoa_map_stats per judged plane -- the live cells' exact
+// words at ranks[i] / 65535 of them (32768: the median) and, with foot > 0, the cells that reach foot / 65536 of the way from
+// the first of those words to the best.  Up to eight ranks; nil or none: off.  LocateLastStats returns the last call's.
+func (g *gpuCorrelator) LocateSetStats(ranks []uint16, foot int) error {
+	var p *C.uint16_t
+	if len(ranks) > 0 {
+		p = (*C.uint16_t)(unsafe.Pointer(&ranks[0]))
+	}
+	if rc := C.tdoa_locate_set_stats(g.ctx, p, C.int(len(ranks)), C.int(foot)); rc != C.TDOA_OK {
+		return fmt.Errorf("tdoa_locate_set_stats: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return nil
+}
+
+// LocateLastStats returns the statistics of the last call of the delay-table family, one per judged plane in the records'
+// order ([round][stack] for the searches, [round][track] for the tracks); an error when that call computed none.
+func (g *gpuCorrelator) LocateLastStats() ([]C.tdoa_map_stats, error) {
+	var n C.int
+	C.tdoa_locate_last_stats(g.ctx, nil, 0, &n)
+	out := make([]C.tdoa_map_stats, int(n)+1)
+	if rc := C.tdoa_locate_last_stats(g.ctx, &out[0], n, &n); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_locate_last_stats: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return out[:int(n)], nil
+}
+
 // ProcessSync is the clock search (the header's "clock search"): per stack the stations' clocks k_s = centre[s] + x_s,
 // |x_s| <= gate, station 0 the gauge, that make all pairs' stacks largest at the lags the known emitter's delays refDelay
 // (one per station, units of 1/16 sample) predict -- a joint start, the placing and `rounds` sweeps.  clock is
@@ -617,6 +644,29 @@ func (g *Group) LocateSetClock(clock []int32, nStacks, nStations int) error {
 		return fmt.Errorf("tdoa_group_locate_set_clock: %s", C.GoString(C.tdoa_group_last_error(g.g)))
 	}
 	return nil
+}
+
+// LocateSetStats switches every member's map statistics on or off (gpuCorrelator.LocateSetStats).
+func (g *Group) LocateSetStats(ranks []uint16, foot int) error {
+	var p *C.uint16_t
+	if len(ranks) > 0 {
+		p = (*C.uint16_t)(unsafe.Pointer(&ranks[0]))
+	}
+	if rc := C.tdoa_group_locate_set_stats(g.g, p, C.int(len(ranks)), C.int(foot)); rc != C.TDOA_OK {
+		return fmt.Errorf("tdoa_group_locate_set_stats: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return nil
+}
+
+// LocateLastStats is gpuCorrelator.LocateLastStats for the group's last call: the same bytes one context returns.
+func (g *Group) LocateLastStats() ([]C.tdoa_map_stats, error) {
+	var n C.int
+	C.tdoa_group_locate_last_stats(g.g, nil, 0, &n)
+	out := make([]C.tdoa_map_stats, int(n)+1)
+	if rc := C.tdoa_group_locate_last_stats(g.g, &out[0], n, &n); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_group_locate_last_stats: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return out[:int(n)], nil
 }
 
 // ProcessSync is gpuCorrelator.ProcessSync over the group: the members' fixed-point partial sums are added on the host and

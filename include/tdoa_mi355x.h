@@ -745,6 +745,48 @@ int tdoa_debug_locate_track_multi_from_q(tdoa_ctx *ctx, const int64_t *q, int n_
                                          int32_t *cells, int64_t *own, int32_t *pairs, int32_t *lags, double *corr,
                                          int64_t *total);
 
+/* Map statistics: exact quantiles and the peak's footprint of every judged plane, computed where the plane lives.  The four
+ * calls of the delay-table family return a best cell and a runner-up on noise alone too, and the runner-up is one far cell
+ * on the first emitter's hyperbolae: it does not measure the noise.  The plane's own distribution does, and downloading the
+ * plane to get it costs an order of magnitude more than the call.
+ * The setting is context state, like the clock table.  While it is on, tdoa_process_locate, tdoa_process_locate_multi,
+ * tdoa_process_locate_track and tdoa_process_locate_track_multi, their tdoa_debug_*_from_q and tdoa_group_* forms also
+ * compute one tdoa_map_stats per judged plane -- the int64 plane whose largest word the record reports as score_q: the map
+ * [round][stack] of the two searches (and of tracks of one stack), T_0 [round][track] of the two track calls -- in the
+ * records' order.  The call's own outputs keep their bytes.  Off is the default, and with the setting off every call returns
+ * its bytes and captures its graph as before.
+ *   Per plane of n_cells words v[c] >= 0, best = the record's score_q, b = the record's cell, sep = the call's min_separation:
+ *   n_live = #{c : v[c] > 0}.  A cell with no pair inside the range scores 0 and is not noise.
+ *   quantile_q[i], i < n_ranks, is the word at index (ranks[i] * (n_live - 1)) div 65535 of the live words sorted ascending:
+ *     rank 0 is the smallest live word, rank 65535 is best, equal ranks give equal words.  quantile[i] is that word as the
+ *     call converts score_q to score: (double)q * 2^-32 / sqrt(n_w), n_w of the plane's stack or track.
+ *   foot > 0: with q0 = quantile_q[0] and d = best - q0, level_q = q0 + (d >> 16) * foot + (((d & 0xffff) * foot) >> 16), which
+ *     is q0 + (d * foot) div 65536 without overflow.  foot_cells = #{c : v[c] > 0 and v[c] >= level_q}; foot_near of those lie
+ *     within sep rows and columns of b; row_lo .. row_hi and col_lo .. col_hi is their bounding box (row = c div n_cols).
+ *     foot == 0 leaves level_q and the footprint's fields 0.
+ *   A zero record (score_q == 0) gives the all-zero statistics.  Unused words of the two arrays are 0.
+ * The selection is exact and the same in every run (integer histograms; a radix selection over six 11-bit digits).
+ * The record, 168 bytes, no padding: */
+#define TDOA_MAP_STATS_MAX_RANKS 8
+typedef struct {
+    int64_t quantile_q[TDOA_MAP_STATS_MAX_RANKS];
+    double  quantile[TDOA_MAP_STATS_MAX_RANKS];
+    int64_t level_q;
+    int32_t n_live, foot_cells, foot_near;
+    int32_t row_lo, row_hi, col_lo, col_hi, reserved;
+} tdoa_map_stats;
+
+/* ranks [n_ranks], each 0 .. 65535 (32768: the median); n_ranks == 0 or ranks == NULL switches the setting off.  The ranks'
+ * count and foot are one more word of a step graph's key; the ranks themselves are data, so new ranks of the same count
+ * replay the captured step.  TDOA_ERR_INVALID: a NULL context, n_ranks outside 0 .. 8, foot outside 0 .. 65535. */
+int tdoa_locate_set_stats(tdoa_ctx *ctx, const uint16_t *ranks /* [n_ranks] */, int n_ranks /* 0 .. 8 */, int foot /* 0 .. 65535 */);
+
+/* The statistics of the last call of the family on this context, which downloaded them with its other outputs: out
+ * [*n_planes] in the records' order.  n_planes (may be NULL) receives the count whenever there are statistics.
+ * TDOA_ERR_STATE: that call computed none (the setting was off).  TDOA_ERR_INVALID: a NULL context, a NULL out, max_planes
+ * less than the count. */
+int tdoa_locate_last_stats(tdoa_ctx *ctx, tdoa_map_stats *out, int max_planes, int *n_planes);
+
 /* Capture-quality statistics of every (window, station) in one streaming pass over the bytes
  * in HBM: the byte statistics of fastAnalyzeSamples
  * (fast_analyzer.go:117-155) and the block power of validateDataFile (collector.go:219-224).
@@ -993,6 +1035,11 @@ int tdoa_group_process_locate_track_multi(tdoa_group *g, int windows_per_stack, 
                                           int min_separation, tdoa_cell_track *track_host, int32_t *cells_host,
                                           int64_t *own_host, int32_t *pairs_host, int32_t *lags_host, double *corr_host,
                                           int64_t *total_host);
+
+/* tdoa_locate_set_stats on every member (member 0 judges the merged sum), and the last group call's statistics: the bytes a
+ * single context returns.  Errors as there. */
+int tdoa_group_locate_set_stats(tdoa_group *g, const uint16_t *ranks, int n_ranks, int foot);
+int tdoa_group_locate_last_stats(tdoa_group *g, tdoa_map_stats *out, int max_planes, int *n_planes);
 
 /* the sample runs member `rank` of `world` uploads for a capture of total_samples (window grid from n_min, the shortest
  * capture of the job; block offsets from the capture's own thirds): adjacent owned windows form one run, and with fewer

@@ -23,10 +23,12 @@ K = 1 is the locate leg's work through the other entry).  Every `--track-emitter
 own scores, counts, lags and correlations downloaded and every T_0 left on the device (the track's launches and one for the
 centres, then per further round the masked scores, the recurrence and four to finish; K = 1 is the locate-track leg's work
 through the other entry).  `--stack M` gives the locate, locate-track, emitters and track-emitters legs stacks
-of M windows (default 0: whole blocks, one position per track).  `--stations S` runs all legs on S
-stations (default 3; 8 gives 56 triples).
+of M windows (default 0: whole blocks, one position per track).  `--map-stats R1,R2[/FOOT]` adds, next to each of those four
+kinds of leg, the same leg with the map statistics on (tdoa_locate_set_stats with those ranks and FOOT, default 0; name
+..._stats_ms): the statistics' kernels and their download come on top, the planes stay on the device.  `--stations S` runs all
+legs on S stations (default 3; 8 gives 56 triples).
 usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--stack M] [--drift H/D]... [--track J]...
-[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--sync G[/R]]..."""
+[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]..."""
 import json
 import os
 import sys
@@ -56,7 +58,7 @@ def timed(fn, steps):
 
 
 def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=(), locate_tracks=(), stack=0, emitters=(),
-         track_emitters=()):
+         track_emitters=(), map_stats=None):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=20000)
     for s in range(stations):
         c.synth_capture(s, 66_666_666, ST[s % 3], TX, 0x5D0A0000 + s)
@@ -72,24 +74,28 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
     for G in closures:
         legs["process_closure_%d_ms" % G] = lambda G=G: c.process_closure(0, G, 1)
     setup = {}
+
+    def family(name, table, cols, fn):
+        """a leg of the delay-table family with the statistics off and, with --map-stats, the same leg with them on"""
+        setup[name] = lambda: (c.locate_set_table(table, cols), c.locate_set_stats(None)) if map_stats else c.locate_set_table(table, cols)
+        legs[name] = fn
+        if map_stats:
+            on = name[:-3] + "_stats_ms"
+            setup[on] = lambda: (c.locate_set_table(table, cols), c.locate_set_stats(*map_stats))
+            legs[on] = fn
+
     for rows, cols in locates:
         table = tdoa_amd.capi.locate_grid_table([ST[s % 3] for s in range(stations)], 41.10, -96.20, 0.3 / max(rows - 1, 1),
                                                 0.4 / max(cols - 1, 1), rows, cols, 350.0, 2e6)
-        name = "process_locate_%dx%d_ms" % (rows, cols)
-        setup[name] = lambda table=table, cols=cols: c.locate_set_table(table, cols)
-        legs[name] = lambda: c.process_locate(stack, 1)
+        family("process_locate_%dx%d_ms" % (rows, cols), table, cols, lambda: c.process_locate(stack, 1))
         for J in locate_tracks:
-            name = "process_locate_track_%dx%d_J%d_ms" % (rows, cols, J)
-            setup[name] = lambda table=table, cols=cols: c.locate_set_table(table, cols)
-            legs[name] = lambda J=J: c.process_locate_track(stack, J, 1)
+            family("process_locate_track_%dx%d_J%d_ms" % (rows, cols, J), table, cols, lambda J=J: c.process_locate_track(stack, J, 1))
             for K, guard in track_emitters:
-                name = "process_locate_track_multi_%dx%d_J%d_K%d_G%d_ms" % (rows, cols, J, K, guard)
-                setup[name] = lambda table=table, cols=cols: c.locate_set_table(table, cols)
-                legs[name] = lambda J=J, K=K, guard=guard: c.process_locate_track_multi(stack, J, K, guard, 1)
+                family("process_locate_track_multi_%dx%d_J%d_K%d_G%d_ms" % (rows, cols, J, K, guard), table, cols,
+                       lambda J=J, K=K, guard=guard: c.process_locate_track_multi(stack, J, K, guard, 1))
         for K, guard in emitters:
-            name = "process_locate_multi_%dx%d_K%d_G%d_ms" % (rows, cols, K, guard)
-            setup[name] = lambda table=table, cols=cols: c.locate_set_table(table, cols)
-            legs[name] = lambda K=K, guard=guard: c.process_locate_multi(stack, K, guard, 1)
+            family("process_locate_multi_%dx%d_K%d_G%d_ms" % (rows, cols, K, guard), table, cols,
+                   lambda K=K, guard=guard: c.process_locate_multi(stack, K, guard, 1))
     ref = tdoa_amd.capi.locate_grid_table([ST[s % 3] for s in range(stations)], TX[0], TX[1], 0.0, 0.0, 1, 1, TX[2], 2e6)[0]
     for G, R in syncs:
         legs["process_sync_%d_%d_ms" % (G, R)] = lambda G=G, R=R: c.process_sync(ref, 0, G, R)
@@ -101,6 +107,8 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
             times[name].append(timed(fn, steps))
     out = {"config": "cfg2" if stations == 3 else "cfg2 windows, %d stations" % stations, "stations": stations, "pairs": P, "windows": W, "stacks": n_stacks, "locate_stacks": c.num_stacks(stack)[1], "steps": steps, "rounds": rounds,
            "surface_MB": round(W * P * (2 * 20000 - 1) * 4 / 1e6, 1)}
+    if map_stats:
+        out["map_stats"] = {"ranks": list(map_stats[0]), "foot": map_stats[1]}
     for name, t in times.items():
         out[name] = {"median": round(float(np.median(t)), 3), "min": round(min(t), 3), "max": round(max(t), 3)}
     print(json.dumps(out), flush=True)
@@ -148,6 +156,12 @@ if __name__ == "__main__":
         k, _, g = args[i + 1].partition("/")
         emitters.append((int(k), int(g or 2)))
         del args[i:i + 2]
+    map_stats = None
+    if "--map-stats" in args:
+        i = args.index("--map-stats")
+        r, _, f = args[i + 1].partition("/")
+        map_stats = (tuple(int(x) for x in r.split(",")), int(f or 0))
+        del args[i:i + 2]
     locates = []
     while "--locate" in args:
         i = args.index("--locate")
@@ -161,4 +175,4 @@ if __name__ == "__main__":
         syncs.append((int(g), int(r or 2)))
         del args[i:i + 2]
     main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs, locate_tracks, opt["--stack"], emitters,
-         track_emitters)
+         track_emitters, map_stats)

@@ -332,7 +332,7 @@ int tdoa_debug_locate_track_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, 
     if ((rc = ensure_locate(ctx, n_sets, g))) return rc;
     if ((rc = ensure_locate_track(ctx, n_sets, track_len, g))) return rc;
     if ((rc = upload_locate_track_roots(ctx, track_roots))) return rc;
-    launch_locate(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), n_sets, g);
+    launch_locate(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), n_sets, g, false);
     launch_locate_track(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), n_sets, track_len, max_step, g);
     return download_and_wait(ctx, [&] { return download_locate_track(ctx, n_sets, track_len, g, track, cells, own, lags, corr, total); });
 }

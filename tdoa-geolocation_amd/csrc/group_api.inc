@@ -451,6 +451,22 @@ int tdoa_group_locate_set_clock(tdoa_group *g, const int32_t *clock, int n_stack
     return TDOA_OK;
 }
 
+int tdoa_group_locate_set_stats(tdoa_group *g, const uint16_t *ranks, int n_ranks, int foot)
+{
+    if (!g) return TDOA_ERR_INVALID;
+    for (size_t m = 0; m < g->members.size(); m++)
+        if (const int rc = tdoa_locate_set_stats(g->members[m], ranks, n_ranks, foot)) return member_fail(g, (int)m, rc);
+    return TDOA_OK;
+}
+
+// the statistics of the group's last call of the family: member 0 ran its search, on its own captures or on the merged sum
+int tdoa_group_locate_last_stats(tdoa_group *g, tdoa_map_stats *out, int max_planes, int *n_planes)
+{
+    if (!g) return TDOA_ERR_INVALID;
+    const int rc = tdoa_locate_last_stats(g->members[0], out, max_planes, n_planes);
+    return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
+}
+
 // tdoa_process_sync over the members: their shares of the fixed-point sums as in tdoa_group_process_stacked, added on the
 // host; member 0 searches the merged Q with the kernels a single context's call ends with.
 int tdoa_group_process_sync(tdoa_group *g, int windows_per_stack, int gate, int rounds, const int32_t *ref_delay, const int32_t *centre,

@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -145,6 +145,12 @@ int main(int argc, char **argv)
     // GUARD of the earlier tracks' lags counting 0 in every stack's pairs (tdoa_process_locate_track_multi)
     bool track_emitters = false;
     int temitters_k = 1, temitters_guard = 2;
+    // --map-stats=R1[,R2...][/FOOT] (with --stack --locate): a STATS line after every LOCATE, LOCATE-MULTI and track line -- the
+    // judged plane's live cells, its words at ranks R / 65535 of them (32768: the median) and the cells that reach FOOT / 65536
+    // of the way from the first of those words to the best (tdoa_locate_set_stats)
+    bool map_stats = false;
+    std::vector<uint16_t> stats_ranks;
+    int stats_foot = 0;
     bool sync = false;
     double sync_lat = 0, sync_lon = 0, sync_h = 0;
     int sync_g = 128, sync_r = 2;
@@ -195,6 +201,30 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
+        else if (a.rfind("--map-stats=", 0) == 0) {
+            map_stats = true;
+            const std::string arg = a.substr(12), list = arg.substr(0, arg.find('/'));
+            bool ok = !list.empty();
+            for (size_t at = 0; ok && at <= list.size();) {
+                const size_t end = std::min(list.find(',', at), list.size());
+                char *stop = nullptr;
+                const long r = std::strtol(list.c_str() + at, &stop, 10);
+                ok = end > at && stop == list.c_str() + end && r >= 0 && r <= 65535;
+                stats_ranks.push_back((uint16_t)r);
+                at = end + 1;
+            }
+            if (ok && arg.find('/') != std::string::npos) {
+                char *stop = nullptr;
+                const char *f = arg.c_str() + arg.find('/') + 1;
+                const long v = std::strtol(f, &stop, 10);
+                ok = *f && !*stop && v >= 0 && v <= 65535;
+                stats_foot = (int)v;
+            }
+            if (!ok || stats_ranks.size() > TDOA_MAP_STATS_MAX_RANKS) {
+                std::fprintf(stderr, "--map-stats=R1[,R2...][/FOOT] with 1 .. 8 ranks and FOOT in 0 .. 65535, e.g. --map-stats=32768,64880/49152\n");
+                return 1;
+            }
+        }
         else if (a.rfind("--track-emitters=", 0) == 0) {
             track_emitters = true;
             const int got = std::sscanf(a.c_str() + 17, "%d/%d", &temitters_k, &temitters_guard);
@@ -226,6 +256,7 @@ int main(int argc, char **argv)
     if (locate_track && !locate) { std::fprintf(stderr, "--locate-track needs --stack --locate\n"); return 1; }
     if (emitters && !locate) { std::fprintf(stderr, "--emitters needs --stack --locate\n"); return 1; }
     if (track_emitters && !locate_track) { std::fprintf(stderr, "--track-emitters needs --stack --locate --locate-track\n"); return 1; }
+    if (map_stats && !locate) { std::fprintf(stderr, "--map-stats needs --stack --locate\n"); return 1; }
     if (sync && !locate) { std::fprintf(stderr, "--sync needs --stack --locate\n"); return 1; }
     if (sync && stack_m != 0) { std::fprintf(stderr, "--sync needs whole-block stacks: --stack without =WINDOWS\n"); return 1; }
     if (pos.size() < 4) {                                     // processor.go:1048-1052
@@ -403,6 +434,7 @@ int main(int argc, char **argv)
         std::vector<tdoa_cell_track> mtracks;    // --track-emitters: one record per round and block, a cell, its own score and the
         std::vector<int32_t> mt_cells, mt_pairs; // pairs' counts per round and stack (tdoa_process_locate_track_multi)
         std::vector<int64_t> mt_own;
+        std::vector<tdoa_map_stats> lstats, mstats, ltstats, mtstats;      // --map-stats: one record per record of the four above
         std::vector<tdoa_sync> syncs;            // --sync: one record and S clocks per block (tdoa_process_sync)
         std::vector<int32_t> clocks;
         double grid_lat0 = 0, grid_lon0 = 0, grid_dlat = 0, grid_dlon = 0;
@@ -469,12 +501,20 @@ int main(int argc, char **argv)
                     }
                     if ((rc = tdoa_locate_set_clock(ctx, table16.data(), n_stacks, S))) return die("tdoa_locate_set_clock", rc);
                 }
+                if (map_stats && (rc = tdoa_locate_set_stats(ctx, stats_ranks.data(), (int)stats_ranks.size(), stats_foot)))
+                    return die("tdoa_locate_set_stats", rc);
+                const auto last_stats = [&](std::vector<tdoa_map_stats> *out, size_t n) {
+                    out->resize(map_stats ? n : 0);
+                    return map_stats ? tdoa_locate_last_stats(ctx, out->data(), (int)n, nullptr) : TDOA_OK;
+                };
                 locs.resize((size_t)n_stacks);
                 if ((rc = tdoa_process_locate(ctx, stack_m, 1, locs.data(), nullptr, nullptr, nullptr))) return die("tdoa_process_locate", rc);
+                if ((rc = last_stats(&lstats, locs.size()))) return die("tdoa_locate_last_stats", rc);
                 if (emitters) {
                     mlocs.resize((size_t)emitters_k * n_stacks);
                     if ((rc = tdoa_process_locate_multi(ctx, stack_m, emitters_k, emitters_guard, 1, mlocs.data(), nullptr, nullptr, nullptr)))
                         return die("tdoa_process_locate_multi", rc);
+                    if ((rc = last_stats(&mstats, mlocs.size()))) return die("tdoa_locate_last_stats", rc);
                 }
                 if (locate_track) {
                     ltracks.resize((size_t)(n_stacks / spb));
@@ -483,6 +523,7 @@ int main(int argc, char **argv)
                     if ((rc = tdoa_process_locate_track(ctx, stack_m, ltrack_j, ltrack_sep, ltracks.data(), lt_cells.data(), lt_own.data(), nullptr,
                                                         nullptr, nullptr)))
                         return die("tdoa_process_locate_track", rc);
+                    if ((rc = last_stats(&ltstats, ltracks.size()))) return die("tdoa_locate_last_stats", rc);
                 }
                 if (track_emitters) {
                     mtracks.resize((size_t)temitters_k * (n_stacks / spb));
@@ -492,6 +533,7 @@ int main(int argc, char **argv)
                     if ((rc = tdoa_process_locate_track_multi(ctx, stack_m, ltrack_j, temitters_k, temitters_guard, ltrack_sep, mtracks.data(),
                                                               mt_cells.data(), mt_own.data(), mt_pairs.data(), nullptr, nullptr, nullptr)))
                         return die("tdoa_process_locate_track_multi", rc);
+                    if ((rc = last_stats(&mtstats, mtracks.size()))) return die("tdoa_locate_last_stats", rc);
                 }
             }
         }
@@ -579,12 +621,23 @@ int main(int argc, char **argv)
             for (int s = 0; s < S; s++) std::printf("%s%d", s ? "," : "", (int)clocks[sid * S + s]);
             std::printf(" moved=%d score=%.6f\n", (int)syncs[sid].moved, syncs[sid].score);
         }
+        // --map-stats: the statistics of the plane the line before it judged, the words on the line's own scale
+        const auto print_stats = [&](const std::vector<tdoa_map_stats> &all, size_t at) {
+            if (at >= all.size()) return;
+            const tdoa_map_stats &m = all[at];
+            const double scale = m.quantile_q[0] ? m.quantile[0] / (double)m.quantile_q[0] : 0.0;
+            std::printf("STATS live=%d q=", (int)m.n_live);
+            for (size_t r = 0; r < stats_ranks.size(); r++) std::printf("%s%.6f", r ? "," : "", m.quantile[r]);
+            std::printf(" level=%.6f foot=%d near=%d rows=%d..%d cols=%d..%d\n", (double)m.level_q * scale, (int)m.foot_cells, (int)m.foot_near,
+                        (int)m.row_lo, (int)m.row_hi, (int)m.col_lo, (int)m.col_hi);
+        };
         // --locate: the best cell of the grid, a line per stack
         for (size_t sid = 0; sid < locs.size(); sid++) {
             const tdoa_location &l = locs[sid];
             std::printf("LOCATE block %d stack %d: cell=%d lat=%.6f lon=%.6f pairs=%d score=%.6f runner=%.6f\n", (int)sid / spb + 1,
                         (int)sid % spb, (int)l.cell, grid_lat0 + (l.cell / locate_cols) * grid_dlat, grid_lon0 + (l.cell % locate_cols) * grid_dlon,
                         (int)l.pairs_in, l.score, l.runner_up);
+            print_stats(lstats, sid);
         }
         // --emitters: a fix per round, the stack's rounds together; a round that found nothing prints cell=-1
         for (size_t sid = 0; sid < mlocs.size() / (size_t)emitters_k; sid++)
@@ -594,12 +647,14 @@ int main(int argc, char **argv)
                 std::printf("LOCATE-MULTI block %d stack %d round %d: cell=%d lat=%.6f lon=%.6f pairs=%d excluded=%d score=%.6f runner=%.6f\n",
                             (int)sid / spb + 1, (int)sid % spb, r, cell, grid_lat0 + (l.cell / locate_cols) * grid_dlat,
                             grid_lon0 + (l.cell % locate_cols) * grid_dlon, (int)l.pairs_in, (int)l.reserved, l.score, l.runner_up);
+                print_stats(mstats, (size_t)r * n_stacks + sid);
             }
         // --locate-track: the block's track, then its cell in every stack with the stack's own score there (on the stack's scale)
         for (size_t b = 0; b < ltracks.size(); b++) {
             const tdoa_cell_track &t = ltracks[b];
             std::printf("LOCATE-TRACK block %d: cell=%d positions=%d steps=%d score=%.6f runner=%.6f runner_cell=%d\n", (int)b + 1, (int)t.cell,
                         (int)t.positions, (int)t.steps, t.score, t.runner_up, (int)t.runner_cell);
+            print_stats(ltstats, b);
             for (int j = 0; j < spb; j++) {
                 const size_t sid = b * spb + j;
                 const int cell = lt_cells[sid];
@@ -617,6 +672,7 @@ int main(int argc, char **argv)
                 const bool found = t.score_q > 0;
                 std::printf("LOCATE-TRACK-MULTI block %d round %d: cell=%d positions=%d steps=%d score=%.6f runner=%.6f runner_cell=%d\n",
                             (int)b + 1, r, found ? (int)t.cell : -1, (int)t.positions, (int)t.steps, t.score, t.runner_up, (int)t.runner_cell);
+                print_stats(mtstats, (size_t)r * n_blocks + b);
                 for (int j = 0; j < spb; j++) {
                     const size_t sid = b * spb + j, at = (size_t)r * n_stacks + sid;
                     const int cell = mt_cells[at];

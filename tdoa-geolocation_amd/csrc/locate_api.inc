@@ -117,13 +117,16 @@ static int ensure_locate(tdoa_ctx *ctx, size_t n_sets, const LocateGeom &g)
     if ((rc = ensure(ctx, ctx->locate_best, sizeof(int32_t) * n_sets))) return rc;
     if ((rc = ensure(ctx, ctx->locate_out, sizeof(LocateOut) * n_sets))) return rc;
     if ((rc = ensure(ctx, ctx->locate_lags, sizeof(int32_t) * n_sets * g.P))) return rc;
-    return ensure(ctx, ctx->locate_corr, sizeof(double) * n_sets * g.P);
+    if ((rc = ensure(ctx, ctx->locate_corr, sizeof(double) * n_sets * g.P))) return rc;
+    return ensure_map_stats(ctx, n_sets);
 }
 
 // Q [n_sets][P][n] -> the records in ctx->locate_out, the map, lags and correlations: the one place the search is launched.
 // With a clock table (its shape checked by the caller: n_sets stacks of g.S stations) the scores' clock instantiation runs
-// and the finish adds the same differences.  Kernel launches only (the step graph captures them).
-static void launch_locate(tdoa_ctx *ctx, const long long *Q, const double *roots, int n_sets, const LocateGeom &g)
+// and the finish adds the same differences.  judged: the maps are what the call judges (the rounds and the cell tracks go on
+// from here and judge their own planes), so their statistics follow when the setting is on.  Kernel launches only (the step
+// graph captures them).
+static void launch_locate(tdoa_ctx *ctx, const long long *Q, const double *roots, int n_sets, const LocateGeom &g, bool judged = true)
 {
     hipStream_t st = ctx->stream;
     const dim3 grid((unsigned)g.tiles, (unsigned)n_sets), one((unsigned)n_sets);
@@ -156,6 +159,7 @@ static void launch_locate(tdoa_ctx *ctx, const long long *Q, const double *roots
                        static_cast<const int32_t *>(best), part);
     hipLaunchKernelGGL(k_locate_finish, one, dim3(kLocateThreads), 0, st, Q, g, table, cdiff, roots, static_cast<const ClosureCand *>(part), 1,
                        best, out, lags, corr);
+    if (judged) launch_map_stats(ctx, map, (size_t)g.n_cells, n_sets, g, out, roots, n_sets);
 }
 
 // the outputs to the host (all but loc may be NULL); asynchronous on ctx->stream
@@ -167,7 +171,7 @@ static int download_locate(tdoa_ctx *ctx, size_t n_sets, const LocateGeom &g, td
     if (lags) HIPCHK(ctx, hipMemcpyAsync(lags, ctx->locate_lags.p, sizeof(int32_t) * n_sets * g.P, hipMemcpyDeviceToHost, st));
     if (corr) HIPCHK(ctx, hipMemcpyAsync(corr, ctx->locate_corr.p, sizeof(double) * n_sets * g.P, hipMemcpyDeviceToHost, st));
     if (map) HIPCHK(ctx, hipMemcpyAsync(map, ctx->locate_map.p, sizeof(int64_t) * n_sets * g.n_cells, hipMemcpyDeviceToHost, st));
-    return TDOA_OK;
+    return download_map_stats(ctx, n_sets);
 }
 
 // the delay-table search on a group's merged sum (finish_from_host, stacked_api.inc)

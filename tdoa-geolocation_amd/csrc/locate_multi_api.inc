@@ -33,15 +33,17 @@ static int ensure_locate_multi(tdoa_ctx *ctx, size_t n_sets, int K, const Locate
     if ((rc = ensure(ctx, ctx->locate_out, sizeof(LocateOut) * K * n_sets))) return rc;
     if ((rc = ensure(ctx, ctx->locate_lags, sizeof(int32_t) * K * n_sets * g.P))) return rc;
     if ((rc = ensure(ctx, ctx->locate_corr, sizeof(double) * K * n_sets * g.P))) return rc;
-    return ensure(ctx, ctx->locate_centres, sizeof(LocateCentres) * n_sets * g.P);
+    if ((rc = ensure(ctx, ctx->locate_centres, sizeof(LocateCentres) * n_sets * g.P))) return rc;
+    return ensure_map_stats(ctx, K * n_sets);
 }
 
 // Q [n_sets][P][n] -> K planes of records, maps, lags and correlations: the one place the rounds are launched.  Round 0 is
 // launch_locate; every later round is the masked scores, the masked finish, and the runner-up's pass as the search runs it,
-// on the round's planes.  Kernel launches only (the step graph captures them).
+// on the round's planes.  The statistics of all K planes of maps follow the last round.  Kernel launches only (the step graph
+// captures them).
 static void launch_locate_multi(tdoa_ctx *ctx, const long long *Q, const double *roots, int n_sets, int K, int guard, const LocateGeom &g)
 {
-    launch_locate(ctx, Q, roots, n_sets, g);
+    launch_locate(ctx, Q, roots, n_sets, g, K == 1);
     if (K == 1) return;
     hipStream_t st = ctx->stream;
     const dim3 grid((unsigned)g.tiles, (unsigned)n_sets), one((unsigned)n_sets);
@@ -81,6 +83,7 @@ static void launch_locate_multi(tdoa_ctx *ctx, const long long *Q, const double 
         hipLaunchKernelGGL(k_locate_finish, one, dim3(kLocateThreads), 0, st, Q, g, table, cdiff, roots, static_cast<const ClosureCand *>(part), 1,
                            best, out, lags, corr);
     }
+    launch_map_stats(ctx, ctx->locate_map.as<const long long>(), (size_t)g.n_cells, K * n_sets, g, ctx->locate_out.p, roots, n_sets);
 }
 
 // the outputs to the host (all but loc may be NULL): the K planes lie one behind the other; asynchronous on ctx->stream

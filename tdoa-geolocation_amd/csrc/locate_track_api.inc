@@ -61,7 +61,8 @@ static int ensure_locate_track(tdoa_ctx *ctx, size_t n_sets, int L, const Locate
     if ((rc = ensure(ctx, ctx->ctrack_roots, sizeof(double) * n_tracks))) return rc;
     if ((rc = ensure(ctx, ctx->ctrack_out, sizeof(CellTrackOut) * n_tracks))) return rc;
     if ((rc = ensure(ctx, ctx->ctrack_cells, sizeof(int32_t) * n_sets))) return rc;
-    return ensure(ctx, ctx->ctrack_own, sizeof(long long) * n_sets);
+    if ((rc = ensure(ctx, ctx->ctrack_own, sizeof(long long) * n_sets))) return rc;
+    return ensure_map_stats(ctx, n_tracks);
 }
 
 // sqrt(N_w) of every track to ctx->ctrack_roots; the caller synchronises before `roots` goes
@@ -80,8 +81,11 @@ static const long long *locate_track_total(const tdoa_ctx *ctx, int L)
 // The maps launch_locate left for n_sets stacks -> the tracks' records in ctx->ctrack_out, cells, own scores, T_0, and the
 // positions' lags and correlations where the search keeps its best cells' (ctx->locate_lags, ctx->locate_corr): the one
 // place the recurrence is launched.  The search's candidates and best cells (ctx->locate_part, ctx->locate_best) are free by
-// now and serve the tracks, which are never more than the stacks.  Kernel launches only (the step graph captures them).
-static void launch_locate_track(tdoa_ctx *ctx, const long long *Q, const double *roots, int n_sets, int L, int J, const LocateGeom &lg)
+// now and serve the tracks, which are never more than the stacks.  judged: T_0 is what the call judges (the rounds go on from
+// here), so its statistics follow when the setting is on, on the tracks' own scale.  Kernel launches only (the step graph
+// captures them).
+static void launch_locate_track(tdoa_ctx *ctx, const long long *Q, const double *roots, int n_sets, int L, int J, const LocateGeom &lg,
+                                bool judged = true)
 {
     hipStream_t st = ctx->stream;
     const CellTrackGeom g = cell_track_geom(lg, L, J);
@@ -113,6 +117,7 @@ static void launch_locate_track(tdoa_ctx *ctx, const long long *Q, const double 
                            ctx->ctrack_cells.as<int32_t>(), ctx->ctrack_own.as<long long>(), ctx->locate_lags.as<int32_t>(),
                            ctx->locate_corr.as<double>());
     }
+    if (judged) launch_map_stats(ctx, t0, (size_t)g.n_cells, (int)n_tracks, lg, ctx->ctrack_out.p, ctx->ctrack_roots.as<const double>(), (int)n_tracks);
 }
 
 // the outputs to the host (all but track may be NULL); asynchronous on ctx->stream
@@ -128,7 +133,7 @@ static int download_locate_track(tdoa_ctx *ctx, size_t n_sets, int L, const Loca
     if (corr) HIPCHK(ctx, hipMemcpyAsync(corr, ctx->locate_corr.p, sizeof(double) * n_sets * g.P, hipMemcpyDeviceToHost, st));
     if (total)
         HIPCHK(ctx, hipMemcpyAsync(total, locate_track_total(ctx, L), sizeof(int64_t) * n_tracks * g.n_cells, hipMemcpyDeviceToHost, st));
-    return TDOA_OK;
+    return download_map_stats(ctx, n_tracks);
 }
 
 // sqrt(N_w) of the three blocks' tracks: a track holds all the windows of its block
@@ -150,7 +155,7 @@ static int locate_track_from_host(tdoa_ctx *ctx, const int64_t *q_sum, int windo
             if ((rc = ensure_locate(ctx, n_stacks, g))) return rc;
             if ((rc = ensure_locate_track(ctx, n_stacks, L, g))) return rc;
             if ((rc = upload_locate_track_roots(ctx, track_roots))) return rc;
-            launch_locate(ctx, ctx->stack_q.as<const long long>(), roots, n_stacks, g);
+            launch_locate(ctx, ctx->stack_q.as<const long long>(), roots, n_stacks, g, false);
             launch_locate_track(ctx, ctx->stack_q.as<const long long>(), roots, n_stacks, L, max_step, g);
             return TDOA_OK;
         },

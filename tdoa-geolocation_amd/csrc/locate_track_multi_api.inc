@@ -46,7 +46,8 @@ static int ensure_locate_track_multi(tdoa_ctx *ctx, size_t n_sets, int L, int K,
     if ((rc = ensure(ctx, ctx->ctrack_pairs, 2 * sizeof(int32_t) * K * n_sets))) return rc;
     if ((rc = ensure(ctx, ctx->locate_centres, sizeof(LocateCentres) * n_sets * g.P))) return rc;
     if ((rc = ensure_locate(ctx, n_sets, g))) return rc;
-    return ensure_locate_track(ctx, n_sets, L, g);
+    if ((rc = ensure_locate_track(ctx, n_sets, L, g))) return rc;
+    return ensure_map_stats(ctx, K * n_tracks);
 }
 
 // T_0 of round r's tracks (above)
@@ -64,8 +65,8 @@ static const long long *locate_track_multi_total(const tdoa_ctx *ctx, size_t n_s
 static void launch_locate_track_multi(tdoa_ctx *ctx, const long long *Q, const double *roots, int n_sets, int L, int J, int K, int guard,
                                       const LocateGeom &lg)
 {
-    launch_locate(ctx, Q, roots, n_sets, lg);
-    launch_locate_track(ctx, Q, roots, n_sets, L, J, lg);
+    launch_locate(ctx, Q, roots, n_sets, lg, false);
+    launch_locate_track(ctx, Q, roots, n_sets, L, J, lg, false);
     hipStream_t st = ctx->stream;
     const CellTrackGeom g = cell_track_geom(lg, L, J);
     const unsigned n_tracks = (unsigned)(n_sets / L);
@@ -127,6 +128,16 @@ static void launch_locate_track_multi(tdoa_ctx *ctx, const long long *Q, const d
                            static_cast<const long long *>(map), static_cast<const signed char *>(D), static_cast<const ClosureCand *>(part), 1,
                            best, out, cells, own, lags, corr);
     }
+    // the statistics of every round's T_0, in the records' order: K planes one behind the other for L = 1; otherwise round 0's
+    // and then the K - 1 others' (none with K = 1), which lie behind the ping-pong's other half
+    const size_t plane = (size_t)g.n_cells;
+    if (L == 1) {
+        launch_map_stats(ctx, locate_track_multi_total(ctx, n_sets, L, 0, lg), plane, K * (int)n_tracks, lg, ctx->ctrack_out.p, track_roots, (int)n_tracks);
+    } else {
+        launch_map_stats(ctx, locate_track_multi_total(ctx, n_sets, L, 0, lg), plane, (int)n_tracks, lg, ctx->ctrack_out.p, track_roots, (int)n_tracks);
+        launch_map_stats(ctx, locate_track_multi_total(ctx, n_sets, L, 1, lg), plane, (K - 1) * (int)n_tracks, lg,
+                         ctx->ctrack_out.as<CellTrackOut>() + n_tracks, track_roots, (int)n_tracks, (int)n_tracks);
+    }
 }
 
 // the outputs to the host (all but track may be NULL): the K planes lie one behind the other, but for T_0 of L > 1, which
@@ -146,7 +157,7 @@ static int download_locate_track_multi(tdoa_ctx *ctx, size_t n_sets, int L, int 
         for (int r = 0; r < K; r++)
             HIPCHK(ctx, hipMemcpyAsync(total + (size_t)r * plane, locate_track_multi_total(ctx, n_sets, L, r, g), sizeof(int64_t) * plane,
                                        hipMemcpyDeviceToHost, st));
-    return TDOA_OK;
+    return download_map_stats(ctx, K * n_tracks);
 }
 
 // the rounds on a group's merged sum (finish_from_host, stacked_api.inc)

@@ -112,7 +112,8 @@ int batch_bound(tdoa_ctx *ctx, const FftPlan &pl, int lag_lo, int lag_hi, const 
         const double held = (double)ctx->tz.cap + (double)ctx->v.cap + (double)ctx->codes.cap + (double)ctx->codes_lp.cap +
                             (double)ctx->surf.cap + (double)ctx->surf_out.cap + (double)ctx->stack_q.cap + (double)ctx->stack_surf.cap +
                             (double)ctx->drift_keys.cap + (double)ctx->drift_prof.cap + (double)ctx->track_t.cap + (double)ctx->track_d.cap +
-                            (double)ctx->locate_table.cap + (double)ctx->locate_map.cap + (double)ctx->ctrack_d.cap + (double)ctx->ctrack_t.cap;
+                            (double)ctx->locate_table.cap + (double)ctx->locate_map.cap + (double)ctx->ctrack_d.cap + (double)ctx->ctrack_t.cap +
+                            (double)ctx->mstat_hist.cap;
         limit = std::min(limit, std::max(0.0, (double)free_b + held - 1073741824.0));      // 1 GiB stays free: descriptors, edges, the runtime
     } else {
         (void)hipGetLastError();

@@ -403,6 +403,7 @@ struct LocateProduct : StackProduct {
     int sep = 1;                             // min_separation
     int n_cells = 0, n_cols = 0;             // the shape of the context's table: in the key (the table itself is data)
     bool clocked = false;                    // the context holds station clocks: in the key (another kernel; the clocks are data)
+    uint64_t stats = 0;                      // map statistics (map_stats_key): in the key (more kernels; the ranks are data), 0: off
     tdoa_location *loc_host = nullptr;       // [stack]
     int32_t *lags_host = nullptr;            // [stack][pair]
     double *corr_host = nullptr;             // [stack][pair]
@@ -415,7 +416,7 @@ struct LocateProduct : StackProduct {
     }
     void key(std::vector<uint64_t> *key) const override
     {
-        key->insert(key->end(), {Locate, (uint64_t)m, (uint64_t)sep, (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked});
+        key->insert(key->end(), {Locate, (uint64_t)m, (uint64_t)sep, (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked, stats});
     }
     void enqueue(const StepView &v) const override
     {
@@ -442,7 +443,7 @@ struct LocateMultiProduct : LocateProduct {
     void key(std::vector<uint64_t> *key) const override
     {
         key->insert(key->end(), {LocateMulti, (uint64_t)m, (uint64_t)K, (uint64_t)guard, (uint64_t)sep,
-                                 (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked});
+                                 (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked, stats});
     }
     void enqueue(const StepView &v) const override
     {
@@ -475,7 +476,7 @@ struct CellTrackProduct : LocateProduct {
     }
     void key(std::vector<uint64_t> *key) const override
     {
-        key->insert(key->end(), {CellTrack, (uint64_t)m, (uint64_t)J, (uint64_t)sep, (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked});
+        key->insert(key->end(), {CellTrack, (uint64_t)m, (uint64_t)J, (uint64_t)sep, (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked, stats});
     }
     int refresh(const StepView &v) override  // (every call: the debug and the group's calls write their own roots there)
     {
@@ -485,7 +486,9 @@ struct CellTrackProduct : LocateProduct {
     void enqueue(const StepView &v) const override
     {
         tdoa_ctx *ctx = v.ctx;
-        LocateProduct::enqueue(v);
+        StackProduct::enqueue(v);
+        launch_locate(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, layout.n_stacks, v.P).roots, layout.n_stacks, locate_geom(ctx, sep),
+                      false);                // (the track judges T_0, not the maps)
         launch_locate_track(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, layout.n_stacks, v.P).roots, layout.n_stacks, layout.spb, J,
                             locate_geom(ctx, sep));
     }
@@ -510,7 +513,7 @@ struct CellTrackMultiProduct : CellTrackProduct {
     void key(std::vector<uint64_t> *key) const override
     {
         key->insert(key->end(), {CellTrackMulti, (uint64_t)m, (uint64_t)J, (uint64_t)K, (uint64_t)guard, (uint64_t)sep,
-                                 (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked});
+                                 (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked, stats});
     }
     void enqueue(const StepView &v) const override
     {

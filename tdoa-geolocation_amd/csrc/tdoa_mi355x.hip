@@ -44,6 +44,7 @@
 #include "stack_sync.hpp"
 #include "stack_cell_track.hpp"
 #include "stack_locate_track_multi.hpp"
+#include "stack_map_stats.hpp"
 
 using namespace tdoa;
 
@@ -183,6 +184,11 @@ struct tdoa_ctx {
     // several emitters per block (tdoa_process_locate_track_multi): the tracks' buffers above hold one plane per round (T as
     // locate_track_multi_api.inc lays it out), and pairs_in and reserved [round][stack][2]
     DevBuf ctrack_pairs;
+    // map statistics (state: tdoa_locate_set_stats; 0 ranks: off): the ranks (eight words), the bins [plane][rank][2048] and
+    // the selection's state [plane] of one group of planes, the statistics [plane], and the last call's on the host
+    DevBuf mstat_ranks, mstat_hist, mstat_state, mstat_out;
+    int mstat_n_ranks = 0, mstat_foot = 0;
+    std::vector<MapStatsOut> mstat_host;
     // the clock search: ref_delay and centre (kSyncMaxStations words each), the start's tiles' candidates [stack][tile], the
     // records [stack], the clocks [stack][station], the lags and correlations [stack][pair]
     DevBuf sync_in, sync_part, sync_out, sync_clock, sync_lags, sync_corr;
@@ -202,6 +208,10 @@ static_assert(kLocateDelayUnit == TDOA_DELAY_UNIT, "the table's unit");
 static_assert(kLocateMaxEmitters == TDOA_LOCATE_MAX_EMITTERS, "the rounds of tdoa_process_locate_multi");
 static_assert(sizeof(SyncOut) == sizeof(tdoa_sync) && sizeof(tdoa_sync) == 32, "tdoa_sync layout");
 static_assert(sizeof(CellTrackOut) == sizeof(tdoa_cell_track) && sizeof(tdoa_cell_track) == 48, "tdoa_cell_track layout");
+static_assert(offsetof(CellTrackOut, cell) == offsetof(LocateOut, cell) && offsetof(CellTrackOut, score_q) == offsetof(LocateOut, score_q),
+              "the statistics' kernels read a track's record as a location's");
+static_assert(sizeof(MapStatsOut) == sizeof(tdoa_map_stats) && sizeof(tdoa_map_stats) == 168, "tdoa_map_stats layout");
+static_assert(kMapStatsMaxRanks == TDOA_MAP_STATS_MAX_RANKS, "the ranks of tdoa_locate_set_stats");
 
 int fail(tdoa_ctx *ctx, int status, const char *what, hipError_t e = hipSuccess)
 {
@@ -384,6 +394,7 @@ int check_selection(tdoa_ctx *ctx, int k, int min_separation, const void *out)
 #include "step_graph.inc"
 #include "stacked_api.inc"
 #include "closure_api.inc"
+#include "map_stats_api.inc"
 #include "locate_api.inc"
 #include "locate_track_api.inc"
 #include "locate_multi_api.inc"
@@ -549,7 +560,8 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->locate_map, &ctx->locate_part, &ctx->locate_best, &ctx->locate_out, &ctx->locate_lags, &ctx->locate_corr,
                       &ctx->locate_clock, &ctx->sync_in, &ctx->sync_part, &ctx->sync_out, &ctx->sync_clock, &ctx->sync_lags,
                       &ctx->sync_corr, &ctx->debug_q, &ctx->debug_roots, &ctx->ctrack_d, &ctx->ctrack_t, &ctx->ctrack_roots,
-                      &ctx->ctrack_out, &ctx->ctrack_cells, &ctx->ctrack_own, &ctx->locate_centres, &ctx->ctrack_pairs};
+                      &ctx->ctrack_out, &ctx->ctrack_cells, &ctx->ctrack_own, &ctx->locate_centres, &ctx->ctrack_pairs,
+                      &ctx->mstat_ranks, &ctx->mstat_hist, &ctx->mstat_state, &ctx->mstat_out};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1147,6 +1159,7 @@ int tdoa_process_locate(tdoa_ctx *ctx, int windows_per_stack, int min_separation
     prod.corr_host = corr_host;
     prod.map_host = map_host;
     prod.clocked = ctx->clock_stacks != 0;
+    prod.stats = map_stats_key(ctx);
     return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
 }
 
@@ -1164,6 +1177,7 @@ int tdoa_process_locate_track(tdoa_ctx *ctx, int windows_per_stack, int max_step
     prod.n_cells = ctx->locate_cells;
     prod.n_cols = ctx->locate_cols;
     prod.clocked = ctx->clock_stacks != 0;
+    prod.stats = map_stats_key(ctx);
     prod.J = max_step;
     prod.track_host = track_host;
     prod.cells_host = cells_host;
@@ -1188,6 +1202,7 @@ int tdoa_process_locate_multi(tdoa_ctx *ctx, int windows_per_stack, int n_emitte
     prod.n_cells = ctx->locate_cells;
     prod.n_cols = ctx->locate_cols;
     prod.clocked = ctx->clock_stacks != 0;
+    prod.stats = map_stats_key(ctx);
     prod.K = n_emitters;
     prod.guard = guard;
     prod.loc_host = loc_host;
@@ -1212,6 +1227,7 @@ int tdoa_process_locate_track_multi(tdoa_ctx *ctx, int windows_per_stack, int ma
     prod.n_cells = ctx->locate_cells;
     prod.n_cols = ctx->locate_cols;
     prod.clocked = ctx->clock_stacks != 0;
+    prod.stats = map_stats_key(ctx);
     prod.J = max_step;
     prod.K = n_emitters;
     prod.guard = guard;

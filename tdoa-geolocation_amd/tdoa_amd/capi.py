@@ -57,6 +57,11 @@ SYNC_DTYPE = np.dtype([("moved", np.int32), ("pairs_in", np.int32), ("score_q", 
 CELL_TRACK_DTYPE = np.dtype([("cell", np.int32), ("runner_cell", np.int32), ("positions", np.int32), ("steps", np.int32),
                              ("score_q", np.int64), ("runner_q", np.int64),
                              ("score", np.float64), ("runner_up", np.float64)])      # tdoa_cell_track
+MAP_STATS_MAX_RANKS = 8
+MAP_STATS_DTYPE = np.dtype([("quantile_q", np.int64, (MAP_STATS_MAX_RANKS,)), ("quantile", np.float64, (MAP_STATS_MAX_RANKS,)),
+                            ("level_q", np.int64), ("n_live", np.int32), ("foot_cells", np.int32), ("foot_near", np.int32),
+                            ("row_lo", np.int32), ("row_hi", np.int32), ("col_lo", np.int32), ("col_hi", np.int32),
+                            ("reserved", np.int32)])      # tdoa_map_stats
 FINE_DTYPE = np.dtype([("delay", np.float64), ("frac", np.float32), ("y", np.float32, (3,)), ("plausible", np.int32),
                        ("reserved", np.int32)])
 
@@ -115,6 +120,7 @@ SYMBOLS = [
     "tdoa_group_process_sync",
     "tdoa_process_locate_multi", "tdoa_debug_locate_multi_from_q", "tdoa_group_process_locate_multi",
     "tdoa_process_locate_track_multi", "tdoa_debug_locate_track_multi_from_q", "tdoa_group_process_locate_track_multi",
+    "tdoa_locate_set_stats", "tdoa_locate_last_stats", "tdoa_group_locate_set_stats", "tdoa_group_locate_last_stats",
 ]
 
 _lib = None
@@ -251,6 +257,10 @@ def load(build_if_missing=True):
     L.tdoa_group_process_locate_track_multi.argtypes = [vp] + [C.c_int] * 5 + [vp, i32p, i64p, i32p, i32p, dp, i64p]
     L.tdoa_debug_locate_track_multi_from_q.argtypes = [vp, i64p] + [C.c_int] * 8 + [vp, i32p, i64p, i32p, i32p, dp, i64p]
     L.tdoa_debug_sync_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, vp, i32p, i32p, dp]
+    L.tdoa_locate_set_stats.argtypes = [vp, C.POINTER(C.c_uint16), C.c_int, C.c_int]
+    L.tdoa_group_locate_set_stats.argtypes = [vp, C.POINTER(C.c_uint16), C.c_int, C.c_int]
+    L.tdoa_locate_last_stats.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
+    L.tdoa_group_locate_last_stats.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
                                         C.POINTER(C.c_int)]
     _lib = L
@@ -653,7 +663,7 @@ class Context:
         _, n = self.num_stacks(windows_per_stack)
         out = _locate_outputs(n, self.num_pairs(), getattr(self, "_locate_cells", 0), want_map)
         self._chk(self._L.tdoa_process_locate(self._h, int(windows_per_stack), int(min_separation), *_locate_ptrs(out)))
-        return out
+        return self._with_stats(out, "loc")
 
     def locate_from_q(self, q, n_stations, n_w=1, min_separation=1, want_map=True):
         """tdoa_debug_locate_from_q: the search's kernels on the caller's words q [n_sets][P][2 max_lag - 1] int64 (or one
@@ -667,12 +677,31 @@ class Context:
         out = _locate_outputs(q.shape[0], q.shape[1], getattr(self, "_locate_cells", 0), want_map)
         self._chk(self._L.tdoa_debug_locate_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], S, int(n_w),
                                                    int(min_separation), *_locate_ptrs(out)))
-        return out
+        return self._with_stats(out, "loc")
 
     def locate_set_clock(self, clock):
         """tdoa_locate_set_clock: clock [n_stacks][n_stations] int32 station clocks in units of 1/16 sample, one row per stack
         of the searches that follow.  clock None: forget them.  Kept on the device until replaced"""
         self._chk(self._L.tdoa_locate_set_clock(self._h, *_clock(clock)))
+
+    def locate_set_stats(self, ranks, foot=0):
+        """tdoa_locate_set_stats: while set, every process_locate*, locate*_from_q call also computes MAP_STATS_DTYPE
+        statistics of every judged plane (its dict gains "stats", shaped like "loc" or "track"): the live words' exact order
+        statistics at `ranks` (up to 8 values 0 .. 65535; 32768: the median) and, with foot > 0, the cells that reach
+        foot / 65536 of the way from the first rank's word to the best.  ranks None: off"""
+        self._chk(self._L.tdoa_locate_set_stats(self._h, *_ranks(ranks), int(foot)))
+        self._stats_on = ranks is not None and np.size(ranks) > 0
+
+    def locate_last_stats(self):
+        """tdoa_locate_last_stats -> [n_planes] MAP_STATS_DTYPE of the last call of the delay-table family, in its records'
+        order"""
+        return _last_stats(self, self._L.tdoa_locate_last_stats)
+
+    def _with_stats(self, out, like):
+        """out with "stats" shaped like out[like] while the setting is on"""
+        if getattr(self, "_stats_on", False):
+            out["stats"] = self.locate_last_stats().reshape(out[like].shape)
+        return out
 
     def process_sync(self, ref_delay, windows_per_stack=0, gate=0, rounds=0, centre=None):
         """tdoa_process_sync -> {"sync": [n_stacks] SYNC_DTYPE, "clock": [n_stacks][S] int32 (samples), "lags": [n_stacks][P]
@@ -711,7 +740,7 @@ class Context:
         out = _locate_track_outputs(n, per_block, self.num_pairs(), getattr(self, "_locate_cells", 0), want_total)
         self._chk(self._L.tdoa_process_locate_track(self._h, int(windows_per_stack), int(max_step), int(min_separation),
                                                     *_locate_track_ptrs(out)))
-        return out
+        return self._with_stats(out, "track")
 
     def locate_track_from_q(self, q, n_stations, track_len, n_w=1, max_step=0, min_separation=1, want_total=True):
         """tdoa_debug_locate_track_from_q: the search's and the recurrence's kernels on the caller's words q
@@ -726,7 +755,7 @@ class Context:
         out = _locate_track_outputs(q.shape[0], max(int(track_len), 1), q.shape[1], getattr(self, "_locate_cells", 0), want_total)
         self._chk(self._L.tdoa_debug_locate_track_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], int(track_len), S,
                                                          int(n_w), int(max_step), int(min_separation), *_locate_track_ptrs(out)))
-        return out
+        return self._with_stats(out, "track")
 
     def process_locate_multi(self, windows_per_stack=0, n_emitters=1, guard=0, min_separation=1, want_map=False):
         """tdoa_process_locate_multi -> process_locate's dict with a leading axis of n_emitters rounds: "loc" [K][n_stacks],
@@ -736,7 +765,7 @@ class Context:
         out = _locate_multi_outputs(n_emitters, n, self.num_pairs(), getattr(self, "_locate_cells", 0), want_map)
         self._chk(self._L.tdoa_process_locate_multi(self._h, int(windows_per_stack), int(n_emitters), int(guard), int(min_separation),
                                                     *_locate_ptrs(out)))
-        return out
+        return self._with_stats(out, "loc")
 
     def locate_multi_from_q(self, q, n_stations, n_w=1, n_emitters=1, guard=0, min_separation=1, want_map=True):
         """tdoa_debug_locate_multi_from_q: the rounds' kernels on the caller's words q [n_sets][P][2 max_lag - 1] int64 (or one
@@ -750,7 +779,7 @@ class Context:
         out = _locate_multi_outputs(n_emitters, q.shape[0], q.shape[1], getattr(self, "_locate_cells", 0), want_map)
         self._chk(self._L.tdoa_debug_locate_multi_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], S, int(n_w),
                                                          int(n_emitters), int(guard), int(min_separation), *_locate_ptrs(out)))
-        return out
+        return self._with_stats(out, "loc")
 
     def process_locate_track_multi(self, windows_per_stack=0, max_step=0, n_emitters=1, guard=0, min_separation=1, want_total=False):
         """tdoa_process_locate_track_multi -> process_locate_track's dict with a leading axis of n_emitters rounds: "track"
@@ -761,7 +790,7 @@ class Context:
         out = _locate_track_multi_outputs(n_emitters, n, per_block, self.num_pairs(), getattr(self, "_locate_cells", 0), want_total)
         self._chk(self._L.tdoa_process_locate_track_multi(self._h, int(windows_per_stack), int(max_step), int(n_emitters), int(guard),
                                                           int(min_separation), *_locate_track_multi_ptrs(out)))
-        return out
+        return self._with_stats(out, "track")
 
     def locate_track_multi_from_q(self, q, n_stations, track_len, n_w=1, max_step=0, n_emitters=1, guard=0, min_separation=1,
                                   want_total=True):
@@ -779,7 +808,7 @@ class Context:
         self._chk(self._L.tdoa_debug_locate_track_multi_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], int(track_len),
                                                                S, int(n_w), int(max_step), int(n_emitters), int(guard),
                                                                int(min_separation), *_locate_track_multi_ptrs(out)))
-        return out
+        return self._with_stats(out, "track")
 
     def fm_xcorr_peaks(self, iq1, iq2, max_lag, k, min_separation):
         """tdoa_fm_xcorr_peaks_u8 -> (peaks [k] PEAK_DTYPE, count) of one pair of windows"""
@@ -1011,6 +1040,27 @@ def _stacked_outputs(n_stacks, p, n_lags, k, want_surface, want_partial):
     return out
 
 
+def _ranks(ranks):
+    """(pointer, n_ranks) of the statistics' ranks as the C ABI takes them; None: (NULL, 0)"""
+    if ranks is None:
+        return None, 0
+    r = np.ascontiguousarray(ranks).reshape(-1)
+    if r.size and (r.min() < 0 or r.max() > 65535):
+        raise ValueError("ranks are 0 .. 65535")
+    r = r.astype(np.uint16)
+    return r.ctypes.data_as(C.POINTER(C.c_uint16)), r.size
+
+
+def _last_stats(owner, call):
+    n = C.c_int(0)
+    rc = call(owner._h, None, 0, C.byref(n))             # the count first (a state error when there are none)
+    if n.value == 0:
+        owner._chk(rc)
+    out = np.zeros(max(n.value, 1), dtype=MAP_STATS_DTYPE)
+    owner._chk(call(owner._h, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+    return out[:n.value]
+
+
 class _Member(Context):
     """A group member's tdoa_ctx, borrowed (tdoa_group_member): every Context call; close() leaves it to the group."""
 
@@ -1127,12 +1177,23 @@ class Group:
         _, n = m.num_stacks(windows_per_stack)
         out = _locate_outputs(n, m.num_pairs(), getattr(self, "_locate_cells", 0), want_map)
         self._chk(self._L.tdoa_group_process_locate(self._h, int(windows_per_stack), int(min_separation), *_locate_ptrs(out)))
-        return out
+        return self._with_stats(out, "loc")
 
 
     def locate_set_clock(self, clock):
         """tdoa_group_locate_set_clock: the station clocks to every member"""
         self._chk(self._L.tdoa_group_locate_set_clock(self._h, *_clock(clock)))
+
+    def locate_set_stats(self, ranks, foot=0):
+        """tdoa_group_locate_set_stats: Context.locate_set_stats on every member"""
+        self._chk(self._L.tdoa_group_locate_set_stats(self._h, *_ranks(ranks), int(foot)))
+        self._stats_on = ranks is not None and np.size(ranks) > 0
+
+    def locate_last_stats(self):
+        """tdoa_group_locate_last_stats -> Context.locate_last_stats' array, byte-identical to a single context's"""
+        return _last_stats(self, self._L.tdoa_group_locate_last_stats)
+
+    _with_stats = Context._with_stats
 
     def process_locate_track(self, windows_per_stack=0, max_step=0, min_separation=1, want_total=False):
         """tdoa_group_process_locate_track -> Context.process_locate_track's outputs, byte-identical to a single context's"""
@@ -1141,7 +1202,7 @@ class Group:
         out = _locate_track_outputs(n, per_block, m.num_pairs(), getattr(self, "_locate_cells", 0), want_total)
         self._chk(self._L.tdoa_group_process_locate_track(self._h, int(windows_per_stack), int(max_step), int(min_separation),
                                                           *_locate_track_ptrs(out)))
-        return out
+        return self._with_stats(out, "track")
 
     def process_locate_multi(self, windows_per_stack=0, n_emitters=1, guard=0, min_separation=1, want_map=False):
         """tdoa_group_process_locate_multi -> Context.process_locate_multi's outputs, byte-identical to a single context's"""
@@ -1150,7 +1211,7 @@ class Group:
         out = _locate_multi_outputs(n_emitters, n, m.num_pairs(), getattr(self, "_locate_cells", 0), want_map)
         self._chk(self._L.tdoa_group_process_locate_multi(self._h, int(windows_per_stack), int(n_emitters), int(guard),
                                                           int(min_separation), *_locate_ptrs(out)))
-        return out
+        return self._with_stats(out, "loc")
 
     def process_locate_track_multi(self, windows_per_stack=0, max_step=0, n_emitters=1, guard=0, min_separation=1, want_total=False):
         """tdoa_group_process_locate_track_multi -> Context.process_locate_track_multi's outputs, byte-identical to a single
@@ -1160,7 +1221,7 @@ class Group:
         out = _locate_track_multi_outputs(n_emitters, n, per_block, m.num_pairs(), getattr(self, "_locate_cells", 0), want_total)
         self._chk(self._L.tdoa_group_process_locate_track_multi(self._h, int(windows_per_stack), int(max_step), int(n_emitters),
                                                                 int(guard), int(min_separation), *_locate_track_multi_ptrs(out)))
-        return out
+        return self._with_stats(out, "track")
 
     def process_sync(self, ref_delay, windows_per_stack=0, gate=0, rounds=0, centre=None):
         """tdoa_group_process_sync -> Context.process_sync's outputs, byte-identical to a single context's"""
