@@ -264,107 +264,59 @@ int tdoa_debug_closure_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n
     return download_and_wait(ctx, [&] { return download_closure(ctx, n_sets, g, out); });
 }
 
-// the delay-table search's kernels (locate_api.inc) on the caller's words: n_sets sets of P = S (S-1) / 2 rows of 2 max_lag - 1
-// int64, every set a stack of n_w windows, against the context's table.  Needs the context for max_lag, the table and the
-// device only.
+// A call of the delay-table family (locate_run.inc) on the caller's words: n_sets sets of P = S (S-1) / 2 rows of 2 max_lag - 1
+// int64, every set a stack of n_w windows, against the context's table; with tracks set t * track_len + j is position j of
+// track t.  The outputs are [round] planes.  Needs the context for max_lag, the table, the clocks and the device only.
+static int debug_locate_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, const LocateCall &call)
+{
+    int rc;
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (const char *bad = check_locate_call(call)) return fail(ctx, TDOA_ERR_INVALID, bad);
+    if (!q || n_sets < 1 || n_sets > kLocateMaxSets || n_w < 1 || n_stations < 2 || n_stations > kLocateMaxStations)
+        return fail(ctx, TDOA_ERR_INVALID, "q is NULL, n_sets outside 1 .. 65535, n_w < 1 or n_stations outside 2 .. 64");
+    if (call.tracks && (track_len < 1 || n_sets % track_len != 0)) return fail(ctx, TDOA_ERR_INVALID, "track_len < 1 or not a divisor of n_sets");
+    if (const char *bad = check_locate_table(ctx, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
+    if (const char *bad = check_locate_clock(ctx, n_sets, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
+    const LocateRun run = locate_run(ctx, call, n_sets, track_len);
+    if (!call.tracks && locate_overflows(run.g.P, n_w)) return fail(ctx, TDOA_ERR_UNSUPPORTED, "pairs x n_w > 2^17: a cell's score could overflow");
+    if (call.tracks && locate_overflows(run.g.P, (long long)track_len * n_w))
+        return fail(ctx, TDOA_ERR_UNSUPPORTED, "pairs x track_len x n_w > 2^17: a track's sum could overflow");
+    if (call.tracks && track_len > kCellTrackMaxLen) return fail(ctx, TDOA_ERR_UNSUPPORTED, "a track of more than 4096 stacks");
+    std::vector<double> roots;
+    const std::vector<double> track_roots(run.n_tracks(), std::sqrt((double)track_len * (double)n_w));
+    if ((rc = upload_debug_q(ctx, q, (size_t)n_sets * run.g.P * run.g.n, n_sets, n_w, &roots))) return rc;
+    if ((rc = ensure_locate_run(ctx, run))) return rc;
+    if (call.tracks && (rc = upload_locate_track_roots(ctx, track_roots))) return rc;
+    launch_locate_run(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), run);
+    return download_and_wait(ctx, [&] { return download_locate_run(ctx, run, call); });
+}
+
 int tdoa_debug_locate_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int min_separation,
                              tdoa_location *loc, int32_t *lags, double *corr, int64_t *map)
 {
-    int rc;
-    if (!ctx) return TDOA_ERR_INVALID;
-    if (const char *bad = check_locate_args(min_separation, loc)) return fail(ctx, TDOA_ERR_INVALID, bad);
-    if (!q || n_sets < 1 || n_sets > kLocateMaxSets || n_w < 1 || n_stations < 2 || n_stations > kLocateMaxStations)
-        return fail(ctx, TDOA_ERR_INVALID, "q is NULL, n_sets outside 1 .. 65535, n_w < 1 or n_stations outside 2 .. 64");
-    if (const char *bad = check_locate_table(ctx, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
-    if (const char *bad = check_locate_clock(ctx, n_sets, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
-    const LocateGeom g = locate_geom(ctx, min_separation);
-    if (locate_overflows(g.P, n_w)) return fail(ctx, TDOA_ERR_UNSUPPORTED, "pairs x n_w > 2^17: a cell's score could overflow");
-    std::vector<double> roots;
-    if ((rc = upload_debug_q(ctx, q, (size_t)n_sets * g.P * g.n, n_sets, n_w, &roots))) return rc;
-    if ((rc = ensure_locate(ctx, n_sets, g))) return rc;
-    launch_locate(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), n_sets, g);
-    return download_and_wait(ctx, [&] { return download_locate(ctx, n_sets, g, loc, lags, corr, map); });
+    return debug_locate_from_q(ctx, q, n_sets, 0, n_stations, n_w, locate_search_call(false, 1, 0, min_separation, loc, lags, corr, map));
 }
 
-// the rounds of several emitters per stack (locate_multi_api.inc) on the caller's words, as tdoa_debug_locate_from_q takes them;
-// the outputs are [round][set] planes.  Needs the context for max_lag, the table, the clocks and the device only.
 int tdoa_debug_locate_multi_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int n_emitters, int guard,
                                    int min_separation, tdoa_location *loc, int32_t *lags, double *corr, int64_t *map)
 {
-    int rc;
-    if (!ctx) return TDOA_ERR_INVALID;
-    if (const char *bad = check_locate_multi_args(n_emitters, guard, min_separation, loc)) return fail(ctx, TDOA_ERR_INVALID, bad);
-    if (!q || n_sets < 1 || n_sets > kLocateMaxSets || n_w < 1 || n_stations < 2 || n_stations > kLocateMaxStations)
-        return fail(ctx, TDOA_ERR_INVALID, "q is NULL, n_sets outside 1 .. 65535, n_w < 1 or n_stations outside 2 .. 64");
-    if (const char *bad = check_locate_table(ctx, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
-    if (const char *bad = check_locate_clock(ctx, n_sets, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
-    const LocateGeom g = locate_geom(ctx, min_separation);
-    if (locate_overflows(g.P, n_w)) return fail(ctx, TDOA_ERR_UNSUPPORTED, "pairs x n_w > 2^17: a cell's score could overflow");
-    std::vector<double> roots;
-    if ((rc = upload_debug_q(ctx, q, (size_t)n_sets * g.P * g.n, n_sets, n_w, &roots))) return rc;
-    if ((rc = ensure_locate_multi(ctx, n_sets, n_emitters, g))) return rc;
-    launch_locate_multi(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), n_sets, n_emitters, guard, g);
-    return download_and_wait(ctx, [&] { return download_locate_multi(ctx, n_sets, n_emitters, g, loc, lags, corr, map); });
+    return debug_locate_from_q(ctx, q, n_sets, 0, n_stations, n_w, locate_search_call(true, n_emitters, guard, min_separation, loc, lags, corr, map));
 }
 
-// the delay-table search's and the cell tracks' kernels (locate_track_api.inc) on the caller's words: n_sets sets as
-// tdoa_debug_locate_from_q takes them, set t * track_len + j position j of track t.  Needs the context for max_lag, the table,
-// the clocks and the device only.
 int tdoa_debug_locate_track_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, int max_step,
                                    int min_separation, tdoa_cell_track *track, int32_t *cells, int64_t *own, int32_t *lags,
                                    double *corr, int64_t *total)
 {
-    int rc;
-    if (!ctx) return TDOA_ERR_INVALID;
-    if (const char *bad = check_locate_track_args(max_step, min_separation, track)) return fail(ctx, TDOA_ERR_INVALID, bad);
-    if (!q || n_sets < 1 || n_sets > kLocateMaxSets || n_w < 1 || n_stations < 2 || n_stations > kLocateMaxStations)
-        return fail(ctx, TDOA_ERR_INVALID, "q is NULL, n_sets outside 1 .. 65535, n_w < 1 or n_stations outside 2 .. 64");
-    if (track_len < 1 || n_sets % track_len != 0) return fail(ctx, TDOA_ERR_INVALID, "track_len < 1 or not a divisor of n_sets");
-    if (const char *bad = check_locate_table(ctx, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
-    if (const char *bad = check_locate_clock(ctx, n_sets, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
-    const LocateGeom g = locate_geom(ctx, min_separation);
-    if (locate_overflows(g.P, (long long)track_len * n_w))
-        return fail(ctx, TDOA_ERR_UNSUPPORTED, "pairs x track_len x n_w > 2^17: a track's sum could overflow");
-    if (track_len > kCellTrackMaxLen) return fail(ctx, TDOA_ERR_UNSUPPORTED, "a track of more than 4096 stacks");
-    std::vector<double> roots;
-    const std::vector<double> track_roots((size_t)(n_sets / track_len), std::sqrt((double)track_len * (double)n_w));
-    if ((rc = upload_debug_q(ctx, q, (size_t)n_sets * g.P * g.n, n_sets, n_w, &roots))) return rc;
-    if ((rc = ensure_locate(ctx, n_sets, g))) return rc;
-    if ((rc = ensure_locate_track(ctx, n_sets, track_len, g))) return rc;
-    if ((rc = upload_locate_track_roots(ctx, track_roots))) return rc;
-    launch_locate(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), n_sets, g, false);
-    launch_locate_track(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), n_sets, track_len, max_step, g);
-    return download_and_wait(ctx, [&] { return download_locate_track(ctx, n_sets, track_len, g, track, cells, own, lags, corr, total); });
+    return debug_locate_from_q(ctx, q, n_sets, track_len, n_stations, n_w,
+                               locate_track_call(false, max_step, 1, 0, min_separation, track, cells, own, nullptr, lags, corr, total));
 }
 
-// the rounds of several emitters per block (locate_track_multi_api.inc) on the caller's words, as
-// tdoa_debug_locate_track_from_q takes them; the outputs are [round] planes.  Needs the context for max_lag, the table, the
-// clocks and the device only.
 int tdoa_debug_locate_track_multi_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, int max_step,
                                          int n_emitters, int guard, int min_separation, tdoa_cell_track *track, int32_t *cells,
                                          int64_t *own, int32_t *pairs, int32_t *lags, double *corr, int64_t *total)
 {
-    int rc;
-    if (!ctx) return TDOA_ERR_INVALID;
-    if (const char *bad = check_locate_track_multi_args(max_step, n_emitters, guard, min_separation, track)) return fail(ctx, TDOA_ERR_INVALID, bad);
-    if (!q || n_sets < 1 || n_sets > kLocateMaxSets || n_w < 1 || n_stations < 2 || n_stations > kLocateMaxStations)
-        return fail(ctx, TDOA_ERR_INVALID, "q is NULL, n_sets outside 1 .. 65535, n_w < 1 or n_stations outside 2 .. 64");
-    if (track_len < 1 || n_sets % track_len != 0) return fail(ctx, TDOA_ERR_INVALID, "track_len < 1 or not a divisor of n_sets");
-    if (const char *bad = check_locate_table(ctx, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
-    if (const char *bad = check_locate_clock(ctx, n_sets, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
-    const LocateGeom g = locate_geom(ctx, min_separation);
-    if (locate_overflows(g.P, (long long)track_len * n_w))
-        return fail(ctx, TDOA_ERR_UNSUPPORTED, "pairs x track_len x n_w > 2^17: a track's sum could overflow");
-    if (track_len > kCellTrackMaxLen) return fail(ctx, TDOA_ERR_UNSUPPORTED, "a track of more than 4096 stacks");
-    std::vector<double> roots;
-    const std::vector<double> track_roots((size_t)(n_sets / track_len), std::sqrt((double)track_len * (double)n_w));
-    if ((rc = upload_debug_q(ctx, q, (size_t)n_sets * g.P * g.n, n_sets, n_w, &roots))) return rc;
-    if ((rc = ensure_locate_track_multi(ctx, n_sets, track_len, n_emitters, g))) return rc;
-    if ((rc = upload_locate_track_roots(ctx, track_roots))) return rc;
-    launch_locate_track_multi(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), n_sets, track_len, max_step,
-                              n_emitters, guard, g);
-    return download_and_wait(
-        ctx, [&] { return download_locate_track_multi(ctx, n_sets, track_len, n_emitters, g, track, cells, own, pairs, lags, corr, total); });
+    return debug_locate_from_q(ctx, q, n_sets, track_len, n_stations, n_w,
+                               locate_track_call(true, max_step, n_emitters, guard, min_separation, track, cells, own, pairs, lags, corr, total));
 }
 
 // the clock search's kernels (sync_api.inc) on the caller's words: n_sets sets of P = S (S-1) / 2 rows of 2 max_lag - 1 int64,

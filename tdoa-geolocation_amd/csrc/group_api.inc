@@ -346,100 +346,53 @@ int tdoa_group_locate_set_table(tdoa_group *g, const int32_t *delay, int n_cells
     return TDOA_OK;
 }
 
-// tdoa_process_locate over the members: their shares of the fixed-point sums as in tdoa_group_process_stacked, added on the
-// host; member 0 searches the merged Q with the kernels a single context's call ends with.
+// The four entries of the delay-table family over the members: their shares of the fixed-point sums as in
+// tdoa_group_process_stacked, added on the host; member 0 runs the call on the merged Q with the kernels a single context's
+// call ends with.
+static int group_locate_call(tdoa_group *g, int windows_per_stack, const LocateCall &call)
+{
+    if (!g) return TDOA_ERR_INVALID;
+    if (windows_per_stack < 0) return group_fail(g, TDOA_ERR_INVALID, "windows_per_stack < 0");
+    if (const char *bad = check_locate_call(call)) return group_fail(g, TDOA_ERR_INVALID, bad);
+    const int world = (int)g->members.size();
+    tdoa_ctx *c0 = g->members[0];
+    if (world == 1) {                        // no merge: the member's call writes the outputs
+        const int rc = process_locate_call(c0, windows_per_stack, call);
+        return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
+    }
+    const char *what = nullptr;
+    if (const int rc = check_locate_state(c0, windows_per_stack, call.tracks, &what)) return group_fail(g, rc, member_name(0, c0->device) + what);
+    const int64_t *sum = nullptr;
+    if (const int rc = group_merged_q(g, windows_per_stack, &sum)) return rc;
+    const int rc = locate_run_from_host(c0, sum, windows_per_stack, call);
+    return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
+}
+
 int tdoa_group_process_locate(tdoa_group *g, int windows_per_stack, int min_separation, tdoa_location *loc_host, int32_t *lags_host,
                               double *corr_host, int64_t *map_host)
 {
-    if (!g) return TDOA_ERR_INVALID;
-    if (windows_per_stack < 0) return group_fail(g, TDOA_ERR_INVALID, "windows_per_stack < 0");
-    if (const char *bad = check_locate_args(min_separation, loc_host)) return group_fail(g, TDOA_ERR_INVALID, bad);
-    const int world = (int)g->members.size();
-    tdoa_ctx *c0 = g->members[0];
-    if (world == 1) {                        // no merge: the member's call writes the outputs
-        const int rc = tdoa_process_locate(c0, windows_per_stack, min_separation, loc_host, lags_host, corr_host, map_host);
-        return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
-    }
-    const char *what = nullptr;
-    if (const int rc = check_locate_state(c0, windows_per_stack, &what)) return group_fail(g, rc, member_name(0, c0->device) + what);
-    const int64_t *sum = nullptr;
-    if (const int rc = group_merged_q(g, windows_per_stack, &sum)) return rc;
-    const int rc = locate_from_host(c0, sum, windows_per_stack, min_separation, loc_host, lags_host, corr_host, map_host);
-    return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
+    return group_locate_call(g, windows_per_stack, locate_search_call(false, 1, 0, min_separation, loc_host, lags_host, corr_host, map_host));
 }
 
-// tdoa_process_locate_track over the members: their shares of the fixed-point sums as in tdoa_group_process_stacked, added on
-// the host; member 0 runs the search and the recurrence on the merged Q with the kernels a single context's call ends with.
 int tdoa_group_process_locate_track(tdoa_group *g, int windows_per_stack, int max_step, int min_separation, tdoa_cell_track *track_host,
                                     int32_t *cells_host, int64_t *own_host, int32_t *lags_host, double *corr_host, int64_t *total_host)
 {
-    if (!g) return TDOA_ERR_INVALID;
-    if (windows_per_stack < 0) return group_fail(g, TDOA_ERR_INVALID, "windows_per_stack < 0");
-    if (const char *bad = check_locate_track_args(max_step, min_separation, track_host)) return group_fail(g, TDOA_ERR_INVALID, bad);
-    const int world = (int)g->members.size();
-    tdoa_ctx *c0 = g->members[0];
-    if (world == 1) {                        // no merge: the member's call writes the outputs
-        const int rc = tdoa_process_locate_track(c0, windows_per_stack, max_step, min_separation, track_host, cells_host, own_host,
-                                                 lags_host, corr_host, total_host);
-        return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
-    }
-    const char *what = nullptr;
-    if (const int rc = check_locate_track_state(c0, windows_per_stack, &what)) return group_fail(g, rc, member_name(0, c0->device) + what);
-    const int64_t *sum = nullptr;
-    if (const int rc = group_merged_q(g, windows_per_stack, &sum)) return rc;
-    const int rc = locate_track_from_host(c0, sum, windows_per_stack, max_step, min_separation, track_host, cells_host, own_host,
-                                          lags_host, corr_host, total_host);
-    return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
+    return group_locate_call(g, windows_per_stack, locate_track_call(false, max_step, 1, 0, min_separation, track_host, cells_host, own_host,
+                                                                     nullptr, lags_host, corr_host, total_host));
 }
 
-// tdoa_process_locate_multi over the members: their shares of the fixed-point sums as in tdoa_group_process_stacked, added on
-// the host; member 0 runs the rounds on the merged Q with the kernels a single context's call ends with.
 int tdoa_group_process_locate_multi(tdoa_group *g, int windows_per_stack, int n_emitters, int guard, int min_separation,
                                     tdoa_location *loc_host, int32_t *lags_host, double *corr_host, int64_t *map_host)
 {
-    if (!g) return TDOA_ERR_INVALID;
-    if (windows_per_stack < 0) return group_fail(g, TDOA_ERR_INVALID, "windows_per_stack < 0");
-    if (const char *bad = check_locate_multi_args(n_emitters, guard, min_separation, loc_host)) return group_fail(g, TDOA_ERR_INVALID, bad);
-    const int world = (int)g->members.size();
-    tdoa_ctx *c0 = g->members[0];
-    if (world == 1) {                        // no merge: the member's call writes the outputs
-        const int rc = tdoa_process_locate_multi(c0, windows_per_stack, n_emitters, guard, min_separation, loc_host, lags_host, corr_host,
-                                                 map_host);
-        return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
-    }
-    const char *what = nullptr;
-    if (const int rc = check_locate_state(c0, windows_per_stack, &what)) return group_fail(g, rc, member_name(0, c0->device) + what);
-    const int64_t *sum = nullptr;
-    if (const int rc = group_merged_q(g, windows_per_stack, &sum)) return rc;
-    const int rc = locate_multi_from_host(c0, sum, windows_per_stack, n_emitters, guard, min_separation, loc_host, lags_host, corr_host,
-                                          map_host);
-    return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
+    return group_locate_call(g, windows_per_stack, locate_search_call(true, n_emitters, guard, min_separation, loc_host, lags_host, corr_host, map_host));
 }
 
-// tdoa_process_locate_track_multi over the members: their shares of the fixed-point sums as in tdoa_group_process_stacked,
-// added on the host; member 0 runs the rounds on the merged Q with the kernels a single context's call ends with.
 int tdoa_group_process_locate_track_multi(tdoa_group *g, int windows_per_stack, int max_step, int n_emitters, int guard, int min_separation,
                                           tdoa_cell_track *track_host, int32_t *cells_host, int64_t *own_host, int32_t *pairs_host,
                                           int32_t *lags_host, double *corr_host, int64_t *total_host)
 {
-    if (!g) return TDOA_ERR_INVALID;
-    if (windows_per_stack < 0) return group_fail(g, TDOA_ERR_INVALID, "windows_per_stack < 0");
-    if (const char *bad = check_locate_track_multi_args(max_step, n_emitters, guard, min_separation, track_host))
-        return group_fail(g, TDOA_ERR_INVALID, bad);
-    const int world = (int)g->members.size();
-    tdoa_ctx *c0 = g->members[0];
-    if (world == 1) {                        // no merge: the member's call writes the outputs
-        const int rc = tdoa_process_locate_track_multi(c0, windows_per_stack, max_step, n_emitters, guard, min_separation, track_host,
-                                                       cells_host, own_host, pairs_host, lags_host, corr_host, total_host);
-        return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
-    }
-    const char *what = nullptr;
-    if (const int rc = check_locate_track_state(c0, windows_per_stack, &what)) return group_fail(g, rc, member_name(0, c0->device) + what);
-    const int64_t *sum = nullptr;
-    if (const int rc = group_merged_q(g, windows_per_stack, &sum)) return rc;
-    const int rc = locate_track_multi_from_host(c0, sum, windows_per_stack, max_step, n_emitters, guard, min_separation, track_host,
-                                                cells_host, own_host, pairs_host, lags_host, corr_host, total_host);
-    return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
+    return group_locate_call(g, windows_per_stack, locate_track_call(true, max_step, n_emitters, guard, min_separation, track_host, cells_host,
+                                                                     own_host, pairs_host, lags_host, corr_host, total_host));
 }
 
 // the clocks to every member: each keeps its own copy, member 0's is the one a group of several searches with

@@ -1,0 +1,453 @@
+// locate_run.inc -- the delay-table family, host side: tdoa_process_locate, tdoa_process_locate_multi, tdoa_process_locate_track
+// and tdoa_process_locate_track_multi are one computation with two switches (K rounds on masked lags; the recurrence over the L
+// stacks of a track).  A LocateCall is what a caller of one of the four asks for, a LocateRun is the call on n_sets stacks; the
+// checks the entries share and the run's buffers, launches, download and merged-sum call exist once, here, for a context's own
+// step (step_products.inc), the group's merged sum (group_api.inc) and the tdoa_debug_locate*_from_q entries (debug_api.inc).
+// Included by tdoa_mi355x.hip after locate_api.inc and before step_products.inc.
+
+namespace {
+
+// what one of the four entries is asked for.  tracks and rounds say which entry it is: without rounds K = 1 and guard = 0, and
+// only the entry with both reports the per-stack counts (pairs).  Of the outputs a search takes loc (required), lags, corr and
+// map, the tracks take track (required), cells, own, pairs (with rounds), lags, corr and total.
+struct LocateCall {
+    bool tracks = false, rounds = false;
+    int J = 0;                               // max_step
+    int K = 1, guard = 0;                    // n_emitters, guard
+    int sep = 1;                             // min_separation
+    tdoa_location *loc = nullptr;            // [round][stack]
+    tdoa_cell_track *track = nullptr;        // [round][track]
+    int32_t *cells = nullptr;                // [round][track][L]
+    int64_t *own = nullptr;                  // [round][track][L]
+    int32_t *pairs = nullptr;                // [round][stack][2]: pairs_in, reserved
+    int32_t *lags = nullptr;                 // [round][stack][pair]
+    double *corr = nullptr;                  // [round][stack][pair]
+    int64_t *map = nullptr;                  // [round][stack][cell]
+    int64_t *total = nullptr;                // [round][track][cell]
+};
+
+// the two searches' and the two tracks' calls (n_emitters and guard are read with rounds only)
+LocateCall locate_search_call(bool rounds, int n_emitters, int guard, int min_separation, tdoa_location *loc, int32_t *lags, double *corr,
+                              int64_t *map)
+{
+    LocateCall c;
+    c.rounds = rounds;
+    c.K = rounds ? n_emitters : 1;
+    c.guard = rounds ? guard : 0;
+    c.sep = min_separation;
+    c.loc = loc;
+    c.lags = lags;
+    c.corr = corr;
+    c.map = map;
+    return c;
+}
+LocateCall locate_track_call(bool rounds, int max_step, int n_emitters, int guard, int min_separation, tdoa_cell_track *track, int32_t *cells,
+                             int64_t *own, int32_t *pairs, int32_t *lags, double *corr, int64_t *total)
+{
+    LocateCall c = locate_search_call(rounds, n_emitters, guard, min_separation, nullptr, lags, corr, nullptr);
+    c.tracks = true;
+    c.J = max_step;
+    c.track = track;
+    c.cells = cells;
+    c.own = own;
+    c.pairs = pairs;
+    c.total = total;
+    return c;
+}
+
+// a call on n_sets stacks
+struct LocateRun {
+    LocateGeom g;
+    int n_sets;
+    int L;                                   // the stacks of a track, 0: no recurrence (the search alone)
+    int J, K, guard;
+    bool pairs;                              // the per-stack counts are produced (and with them the centres, even for K = 1)
+
+    size_t n_tracks() const { return L ? (size_t)n_sets / L : 0; }
+    size_t plane() const { return (size_t)n_sets * g.n_cells; }      // one round's maps, in words
+};
+
+LocateRun locate_run(const tdoa_ctx *ctx, const LocateCall &c, int n_sets, int L)
+{
+    return LocateRun{locate_geom(ctx, c.sep), n_sets, c.tracks ? L : 0, c.J, c.K, c.guard, c.tracks && c.rounds};
+}
+
+// the arguments of a call; they need no device
+const char *check_locate_call(const LocateCall &c)
+{
+    if (c.rounds && (c.K < 1 || c.K > kLocateMaxEmitters)) return "n_emitters outside 1 .. 8";
+    if (c.rounds && c.guard < 0) return "guard < 0";
+    if (c.tracks && (c.J < 0 || c.J > kCellTrackMaxStep)) return "max_step outside 0 .. 16";
+    if (c.sep < 1) return "min_separation < 1";
+    if (c.tracks ? !c.track : !c.loc) return c.tracks ? "track_host is NULL" : "loc_host is NULL";
+    return nullptr;
+}
+
+// what a search on S stations needs of the context's table; nullptr when it is there
+const char *check_locate_table(const tdoa_ctx *ctx, int S)
+{
+    if (ctx->locate_cells == 0) return "no delay table (tdoa_locate_set_table)";
+    if (ctx->locate_stations != S) return "the delay table's n_stations differs from the stations searched";
+    return nullptr;
+}
+
+// what a search on n_sets stacks of S stations needs of the context's clock table, when there is one
+const char *check_locate_clock(const tdoa_ctx *ctx, int n_sets, int S)
+{
+    if (ctx->clock_stacks == 0) return nullptr;
+    if (ctx->clock_stacks != n_sets) return "the clock table's n_stacks differs from the stacks searched";
+    if (ctx->clock_stations != S) return "the clock table's n_stations differs from the stations searched";
+    return nullptr;
+}
+
+// what a context's own call and the group's call refuse once the arguments are in range: the lag mode, the captures, the
+// station count, the table, the overflow bound, the clock table's shape; with tracks also a track's sum that could overflow
+// and too many positions.  *what receives the message.
+int check_locate_state(const tdoa_ctx *ctx, int windows_per_stack, bool tracks, const char **what)
+{
+    const auto refuse = [&](int status, const char *why) {
+        *what = why;
+        return status;
+    };
+    if (ctx->prm.lag_mode == TDOA_LAGS_GO) return refuse(TDOA_ERR_UNSUPPORTED, "the delay-table search with TDOA_LAGS_GO");
+    if (ctx->caps.empty()) return refuse(TDOA_ERR_STATE, "captures missing");
+    const int S = (int)ctx->caps.size(), P = S * (S - 1) / 2;
+    if (S < 2 || S > kLocateMaxStations) return refuse(TDOA_ERR_UNSUPPORTED, "the delay-table search needs 2 .. 64 stations");
+    if (const char *bad = check_locate_table(ctx, S)) return refuse(TDOA_ERR_STATE, bad);
+    int wpb = 0;
+    if (tdoa_num_windows(ctx, &wpb, nullptr)) return refuse(TDOA_ERR_STATE, "captures missing or too small");
+    const StackGeom sg = stack_geom(wpb, windows_per_stack);
+    if (locate_overflows(P, sg.mm)) return refuse(TDOA_ERR_UNSUPPORTED, "pairs x stack length > 2^17: a cell's score could overflow");
+    if (3ll * wpb > kLocateMaxSets) return refuse(TDOA_ERR_UNSUPPORTED, "more than 65535 stacks");
+    if (const char *bad = check_locate_clock(ctx, sg.n_stacks, S)) return refuse(TDOA_ERR_STATE, bad);
+    if (!tracks) return TDOA_OK;
+    if (locate_overflows(P, wpb)) return refuse(TDOA_ERR_UNSUPPORTED, "pairs x windows per block > 2^17: a track's sum could overflow");
+    if (sg.spb > kCellTrackMaxLen) return refuse(TDOA_ERR_UNSUPPORTED, "a track of more than 4096 stacks");
+    return TDOA_OK;
+}
+
+// sqrt(N_w) of the three blocks' tracks: a track holds all the windows of its block
+std::vector<double> block_track_roots(int wpb) { return std::vector<double>(3, std::sqrt((double)wpb)); }
+
+// sqrt(N_w) of every track to ctx->ctrack_roots; the caller synchronises before `roots` goes
+int upload_locate_track_roots(tdoa_ctx *ctx, const std::vector<double> &roots)
+{
+    HIPCHK(ctx, hipMemcpyAsync(ctx->ctrack_roots.p, roots.data(), sizeof(double) * roots.size(), hipMemcpyHostToDevice, ctx->stream));
+    return TDOA_OK;
+}
+
+// ---- where a round's planes lie -----------------------------------------------------------------------------------------------
+// The buffers of a run, in units of one round's plane ([stack] or [track] records, [stack][pair] words, [stack][cell] or
+// [track][cell] sums); "-" is not requested.  Round r's plane is plane r of its buffer, with two exceptions: locate_map with
+// tracks of L > 1, and ctrack_t.
+//
+//   buffer          search (L = 0)   tracks, L = 1     tracks, L > 1   what a round keeps there
+//   locate_map      K                K                 1               its scores.  L > 1: every round's scores overwrite the one
+//                                                                      plane (the round's finish has read it by then); L = 1: a
+//                                                                      track never leaves its map, which is T_0 and goes to the caller
+//   locate_part     1                1                 1               the tiles' candidates, one round at a time: the search's, then
+//   locate_best     1                1                 1               the tracks' (never more than the stacks), and the best cells
+//   locate_out      K                1                 1               the search's records; with tracks only round 0 runs the
+//                                                                      search's finish, and its records stay on the device
+//   locate_lags     K                K                 K               the best cells' lags and correlations, or the positions' of
+//   locate_corr     K                K                 K               the round's tracks (round 0's overwrite the search's)
+//   locate_centres  1 (K > 1 only)   1 (K > 1 or the counts)           the excluded intervals' centres [stack][pair], all rounds' words
+//   ctrack_d        -                -                 1               the steps D: a round's finish walks them before the next
+//                                                                      round's steps write them
+//   ctrack_t        -                -                 K + 1           [T_0 of round 0][the other half][T_0 of round 1] ... [T_0 of
+//                                                                      round K - 1]: a round steps between its own T_0 and the shared
+//                                                                      other half, so every round's T_0 is there for the download
+//   ctrack_roots    -                1                 1               sqrt(N_w) per track (data: uploaded by every call)
+//   ctrack_out      -                K                 K               the tracks' records
+//   ctrack_cells    -                K                 K               the tracks' cells and own scores [stack]
+//   ctrack_own      -                K                 K
+//   ctrack_pairs    -                K (the counts)    K (the counts)  pairs_in and reserved [stack][2]
+//   map statistics  K n_sets         the larger of n_sets and K n_tracks   one record per judged plane: the search judges its maps,
+//                                                                      the tracks judge T_0
+
+// round r's scores [stack][cell]
+long long *locate_run_map(const tdoa_ctx *ctx, const LocateRun &run, int r)
+{
+    return ctx->locate_map.as<long long>() + (run.L > 1 ? 0 : (size_t)r * run.plane());
+}
+
+// the planes round r's call judges and the caller of the tracks receives as `total`: T_0 of its tracks [track][cell], which for
+// tracks of one stack -- and for the search, whose stacks are judged one by one -- are the round's maps
+long long *locate_run_total(const tdoa_ctx *ctx, const LocateRun &run, int r)
+{
+    if (run.L <= 1) return locate_run_map(ctx, run, r);
+    return ctx->ctrack_t.as<long long>() + (size_t)(r == 0 ? 0 : r + 1) * run.n_tracks() * run.g.n_cells;
+}
+
+// the ping-pong's other half (L > 1)
+long long *locate_run_other(const tdoa_ctx *ctx, const LocateRun &run) { return ctx->ctrack_t.as<long long>() + run.n_tracks() * run.g.n_cells; }
+
+// round r's planes of the per-stack and per-track buffers
+struct LocateRound {
+    LocateOut *out;            // the search's records
+    int32_t *lags;
+    double *corr;
+    CellTrackOut *track;       // the tracks' records, cells, own scores and counts
+    int32_t *cells;
+    long long *own;
+    int32_t *pairs;
+};
+LocateRound locate_run_round(const tdoa_ctx *ctx, const LocateRun &run, int r)
+{
+    const size_t set0 = (size_t)r * run.n_sets;
+    return LocateRound{ctx->locate_out.as<LocateOut>() + set0,
+                       ctx->locate_lags.as<int32_t>() + set0 * run.g.P,
+                       ctx->locate_corr.as<double>() + set0 * run.g.P,
+                       ctx->ctrack_out.as<CellTrackOut>() + (size_t)r * run.n_tracks(),
+                       ctx->ctrack_cells.as<int32_t>() + set0,
+                       ctx->ctrack_own.as<long long>() + set0,
+                       ctx->ctrack_pairs.as<int32_t>() + 2 * set0};
+}
+
+// the planes the run's statistics judge
+size_t locate_run_judged(const LocateRun &run) { return (size_t)run.K * (run.L ? run.n_tracks() : (size_t)run.n_sets); }
+
+// the run's buffers (the table above)
+int ensure_locate_run(tdoa_ctx *ctx, const LocateRun &run)
+{
+    int rc;
+    const LocateGeom &g = run.g;
+    const size_t n_sets = run.n_sets, n_tracks = run.n_tracks(), K = run.K, sp = n_sets * g.P;
+    const size_t map_planes = run.L > 1 ? 1 : K, t_planes = run.L > 1 ? K + 1 : 0;
+    if (ensure(ctx, ctx->locate_map, sizeof(long long) * map_planes * run.plane()) ||
+        (run.L > 1 && (ensure(ctx, ctx->ctrack_d, 2 * run.plane()) || ensure(ctx, ctx->ctrack_t, sizeof(long long) * t_planes * n_tracks * g.n_cells)))) {
+        char buf[320];
+        snprintf(buf, sizeof(buf),
+                 "the delay-table search's maps [%d rounds][%zu stacks][%d cells] (%.1f MB as %zu planes) and the cell tracks' steps (%.1f MB) "
+                 "and sums [%zu][%zu tracks] (%.1f MB) do not fit in device memory: %s",
+                 run.K, n_sets, (int)g.n_cells, 8.0 * (double)map_planes * (double)run.plane() / 1e6, map_planes,
+                 run.L > 1 ? 2.0 * (double)run.plane() / 1e6 : 0.0, t_planes, n_tracks, 8.0 * (double)t_planes * (double)n_tracks * g.n_cells / 1e6,
+                 ctx->last_error.c_str());
+        return fail(ctx, TDOA_ERR_NOMEM, buf);
+    }
+    if ((rc = ensure(ctx, ctx->locate_part, sizeof(ClosureCand) * n_sets * g.tiles))) return rc;
+    if ((rc = ensure(ctx, ctx->locate_best, sizeof(int32_t) * n_sets))) return rc;
+    if ((rc = ensure(ctx, ctx->locate_out, sizeof(LocateOut) * (run.L ? 1 : K) * n_sets))) return rc;
+    if ((rc = ensure(ctx, ctx->locate_lags, sizeof(int32_t) * K * sp))) return rc;
+    if ((rc = ensure(ctx, ctx->locate_corr, sizeof(double) * K * sp))) return rc;
+    if ((run.K > 1 || run.pairs) && (rc = ensure(ctx, ctx->locate_centres, sizeof(LocateCentres) * sp))) return rc;
+    if (!run.L) return ensure_map_stats(ctx, locate_run_judged(run));
+    if ((rc = ensure(ctx, ctx->ctrack_roots, sizeof(double) * n_tracks))) return rc;
+    if ((rc = ensure(ctx, ctx->ctrack_out, sizeof(CellTrackOut) * K * n_tracks))) return rc;
+    if ((rc = ensure(ctx, ctx->ctrack_cells, sizeof(int32_t) * K * n_sets))) return rc;
+    if ((rc = ensure(ctx, ctx->ctrack_own, sizeof(long long) * K * n_sets))) return rc;
+    if (run.pairs && (rc = ensure(ctx, ctx->ctrack_pairs, 2 * sizeof(int32_t) * K * n_sets))) return rc;
+    return ensure_map_stats(ctx, std::max(n_sets, locate_run_judged(run)));
+}
+
+// ---- the launches' pieces -----------------------------------------------------------------------------------------------------
+// what every launch of a run takes
+struct LocateDev {
+    hipStream_t st;
+    const long long *Q;                      // [n_sets][P][n]
+    const double *roots, *track_roots;       // sqrt(N_w) per stack and per track
+    const int32_t *table;
+    const long long *cdiff;                  // the clock table's differences, nullptr without one
+    ClosureCand *part;
+    int32_t *best;
+    LocateCentres *centres;
+    signed char *D;
+};
+
+// The scores' kernel for a station count and the clock flag: the family's one station-count table.  `launch` is called with
+// std::integral_constant<int, S_T> -- the stations kept in registers up to reg_stations, 0: the re-reading form -- and
+// std::bool_constant<CLK>.
+template <class Launch> void locate_scores_dispatch(int S, int reg_stations, bool clocked, Launch &&launch)
+{
+    switch (S <= reg_stations ? S : 0) {
+#define TDOA_LOCATE_CASE(s)                                                                                                      \
+    case s:                                                                                                                      \
+        if (clocked)                                                                                                             \
+            launch(std::integral_constant<int, s>{}, std::true_type{});                                                          \
+        else                                                                                                                     \
+            launch(std::integral_constant<int, s>{}, std::false_type{});                                                         \
+        break;
+    TDOA_LOCATE_CASE(2) TDOA_LOCATE_CASE(3) TDOA_LOCATE_CASE(4) TDOA_LOCATE_CASE(5) TDOA_LOCATE_CASE(6) TDOA_LOCATE_CASE(7)
+    TDOA_LOCATE_CASE(8) TDOA_LOCATE_CASE(9) TDOA_LOCATE_CASE(10) TDOA_LOCATE_CASE(11) TDOA_LOCATE_CASE(12) TDOA_LOCATE_CASE(13)
+    TDOA_LOCATE_CASE(14) TDOA_LOCATE_CASE(15) TDOA_LOCATE_CASE(16)
+    default:
+        TDOA_LOCATE_CASE(0)
+    }
+#undef TDOA_LOCATE_CASE
+}
+
+// the rounds' mask as the kernels take it: a guard of the range's length already excludes every lag of the range
+LocateMask locate_mask(int round, int guard, const LocateGeom &g) { return LocateMask{round, std::min(guard, g.n)}; }
+
+// round r's scores into its map and the tiles' candidates: unmasked in round 0, on the lags the earlier rounds left otherwise
+void launch_locate_scores(const LocateDev &d, const LocateRun &run, int r, long long *map)
+{
+    const LocateGeom &g = run.g;
+    const dim3 grid((unsigned)g.tiles, (unsigned)run.n_sets), block(kLocateThreads);
+    if (r == 0) {
+        locate_scores_dispatch(g.S, kLocateRegStations, d.cdiff != nullptr, [&](auto s, auto clk) {
+            hipLaunchKernelGGL((k_locate_scores<decltype(s)::value, decltype(clk)::value>), grid, block, 0, d.st, d.Q, g, d.table, d.cdiff, map, d.part);
+        });
+        return;
+    }
+    const LocateMask mk = locate_mask(r, run.guard, g);
+    locate_scores_dispatch(g.S, kLocateMaskedRegStations, d.cdiff != nullptr, [&](auto s, auto clk) {
+        if constexpr (decltype(s)::value <= kLocateMaskedRegStations)      // (the table's last case is the unmasked kernel's alone)
+            hipLaunchKernelGGL((k_locate_scores_masked<decltype(s)::value, decltype(clk)::value>), grid, block, 0, d.st, d.Q, g, d.table, d.cdiff,
+                               static_cast<const LocateCentres *>(d.centres), mk, map, d.part);
+    });
+}
+
+// the search's end of round r on its map: the best cell and its record (pass 0, in a later round with the mask's test and the
+// round's centres), the runner-up's candidates, the record's runner-up (pass 1)
+void launch_locate_finish(const LocateDev &d, const LocateRun &run, int r, const long long *map, const LocateRound &p)
+{
+    const LocateGeom &g = run.g;
+    const dim3 grid((unsigned)g.tiles, (unsigned)run.n_sets), one((unsigned)run.n_sets), block(kLocateThreads);
+    const ClosureCand *part = d.part;
+    if (r == 0)
+        hipLaunchKernelGGL(k_locate_finish, one, block, 0, d.st, d.Q, g, d.table, d.cdiff, d.roots, part, 0, d.best, p.out, p.lags, p.corr);
+    else
+        hipLaunchKernelGGL(k_locate_finish_masked, one, block, 0, d.st, d.Q, g, d.table, d.cdiff, d.roots, part, locate_mask(r, run.guard, g),
+                           d.centres, d.best, p.out, p.lags, p.corr);
+    hipLaunchKernelGGL(k_locate_runner, grid, block, 0, d.st, map, g, static_cast<const int32_t *>(d.best), d.part);
+    hipLaunchKernelGGL(k_locate_finish, one, block, 0, d.st, d.Q, g, d.table, d.cdiff, d.roots, part, 1, d.best, p.out, p.lags, p.corr);
+}
+
+// the recurrence over the L stacks of every track, from the round's maps down to T_0 in t0: position L - 1 is the last stack's
+// map as it stands; an even position writes t0, an odd one `other`, and each reads what the position above wrote.  (A track
+// of one stack has no steps: its T_0 is its map.)
+void launch_cell_track_steps(const LocateDev &d, const CellTrackGeom &g, unsigned n_tracks, const long long *map, long long *t0, long long *other)
+{
+    const int rows = (int)(((long long)g.n_cells + g.n_cols - 1) / g.n_cols);
+    const dim3 tiles((unsigned)g.tiles_x * (unsigned)((rows + kCellTrackH - 1) / kCellTrackH), n_tracks);
+    for (int j = g.L - 2; j >= 0; j--) {
+        const long long *t_in = j == g.L - 2 ? map + (size_t)(g.L - 1) * g.n_cells : ((j + 1) & 1) ? other : t0;
+        const size_t in_stride = j == g.L - 2 ? (size_t)g.L * g.n_cells : (size_t)g.n_cells;
+        hipLaunchKernelGGL(k_cell_track_step, tiles, dim3(kCellTrackThreads), cell_track_lds_bytes(g.J), d.st, t_in, in_stride, map, g, j,
+                           (j & 1) ? other : t0, d.D);
+    }
+}
+
+// the tracks' end of round r on T_0: the tiles' candidates, the best track walked back through D and its record (pass 0, in a
+// later round with the mask's test, the counts and the round's centres), the runner-up's candidates, the record's runner-up
+void launch_cell_track_finish(const LocateDev &d, const LocateRun &run, const CellTrackGeom &g, int r, const long long *map, const long long *t0,
+                              const LocateRound &p)
+{
+    const unsigned n_tracks = (unsigned)run.n_tracks();
+    const dim3 grid((unsigned)run.g.tiles, n_tracks), one(n_tracks), block(kCellTrackThreads);
+    const signed char *D = d.D;
+    const ClosureCand *part = d.part;
+    hipLaunchKernelGGL(k_cell_track_best, grid, block, 0, d.st, t0, g.n_cells, d.part);
+    if (r == 0)
+        hipLaunchKernelGGL(k_cell_track_finish, one, block, 0, d.st, d.Q, run.g, g, d.table, d.cdiff, d.roots, d.track_roots, map, D, part, 0, d.best,
+                           p.track, p.cells, p.own, p.lags, p.corr);
+    else
+        hipLaunchKernelGGL(k_cell_track_finish_masked, one, block, 0, d.st, d.Q, run.g, g, d.table, d.cdiff, d.roots, d.track_roots, map, D, part,
+                           locate_mask(r, run.guard, run.g), d.centres, d.best, p.track, p.cells, p.own, p.pairs, p.lags, p.corr);
+    hipLaunchKernelGGL(k_locate_runner, grid, dim3(kLocateThreads), 0, d.st, t0, run.g, static_cast<const int32_t *>(d.best), d.part);
+    hipLaunchKernelGGL(k_cell_track_finish, one, block, 0, d.st, d.Q, run.g, g, d.table, d.cdiff, d.roots, d.track_roots, map, D, part, 1, d.best,
+                       p.track, p.cells, p.own, p.lags, p.corr);
+}
+
+CellTrackGeom cell_track_geom(const LocateGeom &lg, int L, int J)
+{
+    CellTrackGeom g;
+    g.n_cells = lg.n_cells;
+    g.n_cols = lg.n_cols;
+    g.tiles_x = (std::min(lg.n_cols, lg.n_cells) + kCellTrackW - 1) / kCellTrackW;     // (a row holds at most n_cells cells)
+    g.L = L;
+    g.J = J;
+    return g;
+}
+
+// Q [n_sets][P][n] -> the run's records, maps or T_0, cells, own scores, counts, lags and correlations, and the statistics of
+// the planes it judges: the one place the family is launched.  Round 0 unmasked, the centres its cells give where a later round
+// or the counts need them, rounds 1 .. K - 1 on masked lags, the statistics.  A round is the scores, then the search's end
+// (every round of a search; with tracks round 0 only, whose best cells the search's records keep on the device), then with
+// tracks the recurrence and the tracks' end.  With a clock table (its shape checked by the caller: n_sets stacks of g.S
+// stations) the scores' clock instantiation runs and the finishes add the same differences.  With tracks their roots are in
+// ctx->ctrack_roots (upload_locate_track_roots).  Kernel launches only (the step graph captures them).
+void launch_locate_run(tdoa_ctx *ctx, const long long *Q, const double *roots, const LocateRun &run)
+{
+    const LocateGeom &g = run.g;
+    const LocateDev d{ctx->stream, Q, roots, ctx->ctrack_roots.as<const double>(), ctx->locate_table.as<const int32_t>(),
+                      ctx->clock_stacks ? ctx->locate_clock.as<const long long>() : nullptr, ctx->locate_part.as<ClosureCand>(),
+                      ctx->locate_best.as<int32_t>(), ctx->locate_centres.as<LocateCentres>(), ctx->ctrack_d.as<signed char>()};
+    const CellTrackGeom tg = cell_track_geom(g, run.L, run.J);
+    const unsigned n_tracks = (unsigned)run.n_tracks();
+    for (int r = 0; r < run.K; r++) {
+        const LocateRound p = locate_run_round(ctx, run, r);
+        long long *map = locate_run_map(ctx, run, r), *t0 = locate_run_total(ctx, run, r);
+        launch_locate_scores(d, run, r, map);
+        if (!run.L || r == 0) launch_locate_finish(d, run, r, map, p);
+        if (run.L) {
+            launch_cell_track_steps(d, tg, n_tracks, map, t0, locate_run_other(ctx, run));
+            launch_cell_track_finish(d, run, tg, r, map, t0, p);
+        }
+        if (r > 0) continue;
+        const dim3 sets((unsigned)run.n_sets), block(kLocateThreads);
+        if (run.pairs)
+            hipLaunchKernelGGL(k_track_centres, sets, block, 0, d.st, g, run.L, d.table, d.cdiff, static_cast<const int32_t *>(d.best),
+                               static_cast<const int32_t *>(p.cells), d.centres, p.pairs);
+        else if (run.K > 1 && !run.L)
+            hipLaunchKernelGGL(k_locate_centres, sets, block, 0, d.st, g, d.table, d.cdiff, static_cast<const int32_t *>(d.best), d.centres);
+    }
+    // the statistics of the judged planes, in the records' order.  They lie one behind the other, but for T_0 of L > 1: round 0's
+    // and then the K - 1 others' (none with K = 1), which lie behind the ping-pong's other half
+    const size_t cells = (size_t)g.n_cells;
+    const int n = run.L ? (int)n_tracks : run.n_sets;
+    const void *rec = run.L ? ctx->ctrack_out.p : ctx->locate_out.p;
+    const double *scale = run.L ? d.track_roots : roots;
+    if (run.L <= 1) {
+        launch_map_stats(ctx, locate_run_total(ctx, run, 0), cells, run.K * n, g, rec, scale, n);
+    } else {
+        launch_map_stats(ctx, locate_run_total(ctx, run, 0), cells, n, g, rec, scale, n);
+        launch_map_stats(ctx, locate_run_total(ctx, run, 1), cells, (run.K - 1) * n, g, ctx->ctrack_out.as<CellTrackOut>() + n, scale, n, n);
+    }
+}
+
+// the outputs to the host (all but the records may be NULL): the K planes lie one behind the other, but for T_0 of L > 1,
+// which comes round by round; asynchronous on ctx->stream
+int download_locate_run(tdoa_ctx *ctx, const LocateRun &run, const LocateCall &o)
+{
+    hipStream_t st = ctx->stream;
+    const size_t K = run.K, n_sets = run.n_sets, n_tracks = run.n_tracks(), sp = n_sets * run.g.P, t_plane = n_tracks * run.g.n_cells;
+    if (!run.L) {
+        HIPCHK(ctx, hipMemcpyAsync(o.loc, ctx->locate_out.p, sizeof(LocateOut) * K * n_sets, hipMemcpyDeviceToHost, st));
+    } else {
+        HIPCHK(ctx, hipMemcpyAsync(o.track, ctx->ctrack_out.p, sizeof(CellTrackOut) * K * n_tracks, hipMemcpyDeviceToHost, st));
+        if (o.cells) HIPCHK(ctx, hipMemcpyAsync(o.cells, ctx->ctrack_cells.p, sizeof(int32_t) * K * n_sets, hipMemcpyDeviceToHost, st));
+        if (o.own) HIPCHK(ctx, hipMemcpyAsync(o.own, ctx->ctrack_own.p, sizeof(int64_t) * K * n_sets, hipMemcpyDeviceToHost, st));
+        if (o.pairs && run.pairs)
+            HIPCHK(ctx, hipMemcpyAsync(o.pairs, ctx->ctrack_pairs.p, 2 * sizeof(int32_t) * K * n_sets, hipMemcpyDeviceToHost, st));
+    }
+    if (o.lags) HIPCHK(ctx, hipMemcpyAsync(o.lags, ctx->locate_lags.p, sizeof(int32_t) * K * sp, hipMemcpyDeviceToHost, st));
+    if (o.corr) HIPCHK(ctx, hipMemcpyAsync(o.corr, ctx->locate_corr.p, sizeof(double) * K * sp, hipMemcpyDeviceToHost, st));
+    if (!run.L && o.map) HIPCHK(ctx, hipMemcpyAsync(o.map, ctx->locate_map.p, sizeof(int64_t) * K * run.plane(), hipMemcpyDeviceToHost, st));
+    for (int r = 0; run.L && o.total && r < run.K; r++)
+        HIPCHK(ctx, hipMemcpyAsync(o.total + (size_t)r * t_plane, locate_run_total(ctx, run, r), sizeof(int64_t) * t_plane, hipMemcpyDeviceToHost, st));
+    return download_map_stats(ctx, locate_run_judged(run));
+}
+
+// a call of the family on a group's merged sum (finish_from_host, stacked_api.inc); a track spans a block
+int locate_run_from_host(tdoa_ctx *ctx, const int64_t *q_sum, int windows_per_stack, const LocateCall &call)
+{
+    int wpb = 0;
+    if (int rc = tdoa_num_windows(ctx, &wpb, nullptr)) return fail(ctx, rc, "captures missing or too small");
+    const int L = stack_geom(wpb, windows_per_stack).spb;
+    const std::vector<double> track_roots = block_track_roots(wpb);          // (lives until finish_from_host has synchronised)
+    const auto run = [&](int n_stacks) { return locate_run(ctx, call, n_stacks, L); };
+    return finish_from_host(
+        ctx, q_sum, windows_per_stack,
+        [&](int n_stacks, const double *roots) -> int {
+            int rc;
+            if ((rc = ensure_locate_run(ctx, run(n_stacks)))) return rc;
+            if (call.tracks && (rc = upload_locate_track_roots(ctx, track_roots))) return rc;
+            launch_locate_run(ctx, ctx->stack_q.as<const long long>(), roots, run(n_stacks));
+            return TDOA_OK;
+        },
+        [&](int n_stacks) { return download_locate_run(ctx, run(n_stacks), call); });
+}
+
+}  // namespace

@@ -1,6 +1,6 @@
 // map_stats_api.inc -- map statistics, host side: the setting a context keeps (tdoa_locate_set_stats), the statistics' buffers,
-// the one place the kernels of stack_map_stats.hpp are launched (called at the end of the four launches of the delay-table
-// family, so a context's own step, the group's merged sum and the debug entries all get it), the download into the context
+// the one place the kernels of stack_map_stats.hpp are launched (called at the end of the delay-table family's launch,
+// launch_locate_run, so a context's own step, the group's merged sum and the debug entries all get it), the download into the context
 // and tdoa_locate_last_stats.  With the setting off nothing here allocates, launches or copies.
 // Included by tdoa_mi355x.hip after stacked_api.inc and before locate_api.inc.
 
@@ -8,7 +8,7 @@ extern "C" {
 
 static bool map_stats_on(const tdoa_ctx *ctx) { return ctx->mstat_n_ranks > 0; }
 
-// the word the four products append to the step graph's key: the ranks' count and foot (the ranks themselves are data)
+// the word the family's product appends to the step graph's key: the ranks' count and foot (the ranks themselves are data)
 static uint64_t map_stats_key(const tdoa_ctx *ctx) { return (uint64_t)ctx->mstat_n_ranks | ((uint64_t)ctx->mstat_foot << 8); }
 
 int tdoa_locate_set_stats(tdoa_ctx *ctx, const uint16_t *ranks, int n_ranks, int foot)

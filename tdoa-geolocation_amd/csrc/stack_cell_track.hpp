@@ -135,50 +135,13 @@ __global__ __launch_bounds__(kCellTrackThreads) void k_cell_track_best(const lon
     if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = ClosureCand{bs, bk, 0};
 }
 
-// One workgroup per track.  lg: the search's geometry (its sets are the stacks, its tiles the candidates' per track); map
-// and D as above; roots[stack] = sqrt(n_w), track_roots[track] = sqrt(N_w); cdiff: the pairs' clock differences
-// [stack][pair], nullptr: none.
-// pass 0 (partial holds k_cell_track_best's candidates): max T_0 and L_0 (equal maxima: the smaller cell); thread 0 walks
-// L_{j+1} = L_j + D_j[L_j] and writes cells[j], own[j] = s_j[L_j] and the number of steps; then, per position and pair,
-// lag_p(L_j) and the signed C there on the stack's own scale, as k_locate_finish writes them for its best cell; the record
-// (the runner-up's fields 0) and best[track] = L_0.
-// max T_0 = 0: the zero record, every per-position output 0, best = -1.
-// pass 1 (partial holds k_locate_runner's pass over T_0): runner_q, runner_up and runner_cell of a record that is not the
-// zero record, where a cell outside L_0's neighbourhood exists.
-__global__ __launch_bounds__(kCellTrackThreads) void k_cell_track_finish(const long long *Q, LocateGeom lg, CellTrackGeom g,
-                                                                         const int32_t *table, const long long *cdiff,
-                                                                         const double *roots, const double *track_roots,
-                                                                         const long long *map, const signed char *D,
-                                                                         const ClosureCand *partial, int pass,
-                                                                         int32_t *best, CellTrackOut *out, int32_t *cells,
-                                                                         long long *own, int32_t *lags, double *corr)
+// The walk of both finishes' pass 0, for the track whose stacks are set0 .. set0 + L - 1.  Found, with L_0 = cell: thread 0
+// walks L_{j+1} = L_j + D_j[L_j] and writes path[j] (LDS, for the per-position outputs), cells[j] and own[j] = s_j[L_j]; not
+// found: cells and own 0.  Ends with a barrier; returns the number of steps in thread 0.
+__device__ __forceinline__ int cell_track_walk(const CellTrackGeom &g, const long long *map, const signed char *D, size_t set0, bool found,
+                                               int cell, int32_t *path, int32_t *cells, long long *own)
 {
-    __shared__ long long red_s[kCellTrackThreads / kWave];
-    __shared__ uint32_t red_k[kCellTrackThreads / kWave];
-    __shared__ int32_t path[kCellTrackMaxLen];
-    const int track = blockIdx.x, t = threadIdx.x;
-    long long bs = kClosureAbsent;
-    uint32_t bk = 0;
-    for (int y = t; y < lg.tiles; y += kCellTrackThreads) {
-        const ClosureCand c = partial[(size_t)track * lg.tiles + y];
-        if (closure_better(c.score, c.key, bs, bk)) {
-            bs = c.score;
-            bk = c.key;
-        }
-    }
-    closure_block_best(bs, bk, red_s, red_k);
-    const double root = track_roots[track];
-    const int cell = (int)~bk;
-    if (pass == 1) {
-        if (t == 0 && out[track].score_q != 0 && bs >= 0 && cell >= 0 && cell < g.n_cells) {
-            out[track].runner_q = bs;
-            out[track].runner_up = stack_value(bs, root);
-            out[track].runner_cell = cell;
-        }
-        return;
-    }
-    const bool found = bs > 0 && cell >= 0 && cell < g.n_cells;
-    const size_t set0 = (size_t)track * g.L;
+    const int t = threadIdx.x;
     int steps = 0;
     if (!found) {
         for (int j = t; j < g.L; j += kCellTrackThreads) {
@@ -201,6 +164,47 @@ __global__ __launch_bounds__(kCellTrackThreads) void k_cell_track_finish(const l
         }
     }
     __syncthreads();
+    return steps;
+}
+
+// One workgroup per track.  lg: the search's geometry (its sets are the stacks, its tiles the candidates' per track); map
+// and D as above; roots[stack] = sqrt(n_w), track_roots[track] = sqrt(N_w); cdiff: the pairs' clock differences
+// [stack][pair], nullptr: none.
+// pass 0 (partial holds k_cell_track_best's candidates): max T_0 and L_0 (equal maxima: the smaller cell); thread 0 walks
+// L_{j+1} = L_j + D_j[L_j] and writes cells[j], own[j] = s_j[L_j] and the number of steps; then, per position and pair,
+// lag_p(L_j) and the signed C there on the stack's own scale, as k_locate_finish writes them for its best cell; the record
+// (the runner-up's fields 0) and best[track] = L_0.
+// max T_0 = 0: the zero record, every per-position output 0, best = -1.
+// pass 1 (partial holds k_locate_runner's pass over T_0): runner_q, runner_up and runner_cell of a record that is not the
+// zero record, where a cell outside L_0's neighbourhood exists.
+__global__ __launch_bounds__(kCellTrackThreads) void k_cell_track_finish(const long long *Q, LocateGeom lg, CellTrackGeom g,
+                                                                         const int32_t *table, const long long *cdiff,
+                                                                         const double *roots, const double *track_roots,
+                                                                         const long long *map, const signed char *D,
+                                                                         const ClosureCand *partial, int pass,
+                                                                         int32_t *best, CellTrackOut *out, int32_t *cells,
+                                                                         long long *own, int32_t *lags, double *corr)
+{
+    __shared__ long long red_s[kCellTrackThreads / kWave];
+    __shared__ uint32_t red_k[kCellTrackThreads / kWave];
+    __shared__ int32_t path[kCellTrackMaxLen];
+    const int track = blockIdx.x, t = threadIdx.x;
+    long long bs;
+    uint32_t bk;
+    locate_best_candidate(partial + (size_t)track * lg.tiles, lg.tiles, red_s, red_k, bs, bk);
+    const double root = track_roots[track];
+    const int cell = (int)~bk;
+    if (pass == 1) {
+        if (t == 0 && out[track].score_q != 0 && bs >= 0 && cell >= 0 && cell < g.n_cells) {
+            out[track].runner_q = bs;
+            out[track].runner_up = stack_value(bs, root);
+            out[track].runner_cell = cell;
+        }
+        return;
+    }
+    const bool found = bs > 0 && cell >= 0 && cell < g.n_cells;
+    const size_t set0 = (size_t)track * g.L;
+    const int steps = cell_track_walk(g, map, D, set0, found, cell, path, cells, own);
     for (int e = t; e < g.L * lg.P; e += kCellTrackThreads) {
         const int j = e / lg.P, p = e % lg.P;
         const size_t set = set0 + j;

@@ -82,35 +82,28 @@ __global__ __launch_bounds__(kLocateThreads) void k_locate_scores(const long lon
     if (cell < g.n_cells) {
         const long long *q = Q + (size_t)set * g.P * g.n;
         const int32_t *tc = table + cell;
+        const long long *cd = CLK ? cdiff + (size_t)set * g.P : nullptr;
         long long s = 0;
-        if constexpr (CLK) {
-            const long long *cd = cdiff + (size_t)set * g.P;
-            if constexpr (S_T > 0) {
-                int32_t d[S_T];
-#pragma unroll
-                for (int i = 0; i < S_T; i++) d[i] = tc[(size_t)i * g.n_cells];
-#pragma unroll
-                for (int i = 0; i < S_T; i++)
-#pragma unroll
-                    for (int j = i + 1; j < S_T; j++, q += g.n, cd++) s += locate_m(q, d[i], d[j], g, *cd);
-            } else {
-                for (int i = 0; i < g.S; i++) {
-                    const int32_t di = tc[(size_t)i * g.n_cells];
-                    for (int j = i + 1; j < g.S; j++, q += g.n, cd++) s += locate_m(q, di, tc[(size_t)j * g.n_cells], g, *cd);
-                }
-            }
-        } else if constexpr (S_T > 0) {
+        if constexpr (S_T > 0) {
             int32_t d[S_T];
 #pragma unroll
             for (int i = 0; i < S_T; i++) d[i] = tc[(size_t)i * g.n_cells];
 #pragma unroll
             for (int i = 0; i < S_T; i++)
 #pragma unroll
-                for (int j = i + 1; j < S_T; j++, q += g.n) s += locate_m(q, d[i], d[j], g);
+                for (int j = i + 1; j < S_T; j++, q += g.n) {
+                    long long c = 0;
+                    if constexpr (CLK) c = *cd++;
+                    s += locate_m(q, d[i], d[j], g, c);
+                }
         } else {
             for (int i = 0; i < g.S; i++) {
                 const int32_t di = tc[(size_t)i * g.n_cells];
-                for (int j = i + 1; j < g.S; j++, q += g.n) s += locate_m(q, di, tc[(size_t)j * g.n_cells], g);
+                for (int j = i + 1; j < g.S; j++, q += g.n) {
+                    long long c = 0;
+                    if constexpr (CLK) c = *cd++;
+                    s += locate_m(q, di, tc[(size_t)j * g.n_cells], g, c);
+                }
             }
         }
         map[(size_t)set * g.n_cells + cell] = s;
@@ -173,6 +166,31 @@ __device__ __forceinline__ bool locate_pair_value(const long long *q, const Loca
     return true;
 }
 
+// The start of every finishing kernel of the family: the tiles' candidates of the workgroup's set or track, cand[tiles], -> the
+// best of them in every thread (equal scores: the smaller cell).  kLocateThreads threads; ends with closure_block_best's barrier.
+__device__ __forceinline__ void locate_best_candidate(const ClosureCand *cand, int tiles, long long *red_s, uint32_t *red_k, long long &bs,
+                                                      uint32_t &bk)
+{
+    bs = kClosureAbsent;
+    bk = 0;
+    for (int y = threadIdx.x; y < tiles; y += kLocateThreads) {
+        const ClosureCand c = cand[y];
+        if (closure_better(c.score, c.key, bs, bk)) {
+            bs = c.score;
+            bk = c.key;
+        }
+    }
+    closure_block_best(bs, bk, red_s, red_k);
+}
+
+// the sum of a wave's counts, in every lane
+__device__ __forceinline__ int locate_wave_sum(int v)
+{
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+    return v;
+}
+
 // One workgroup per set.
 // pass 0: the tiles' candidates -> the location into best and the record (cell, pairs_in, score_q, score; the runner-up's
 // fields 0), and per pair lag_p(cell*) and the signed C there (0 and 0.0 for a pair outside the range).  A largest score of 0:
@@ -190,16 +208,9 @@ __global__ __launch_bounds__(kLocateThreads) void k_locate_finish(const long lon
     __shared__ uint32_t red_k[kLocateThreads / kWave];
     __shared__ int red_n[kLocateThreads / kWave];
     const int set = blockIdx.x, t = threadIdx.x;
-    long long bs = kClosureAbsent;
-    uint32_t bk = 0;
-    for (int y = t; y < g.tiles; y += kLocateThreads) {
-        const ClosureCand c = partial[(size_t)set * g.tiles + y];
-        if (closure_better(c.score, c.key, bs, bk)) {
-            bs = c.score;
-            bk = c.key;
-        }
-    }
-    closure_block_best(bs, bk, red_s, red_k);
+    long long bs;
+    uint32_t bk;
+    locate_best_candidate(partial + (size_t)set * g.tiles, g.tiles, red_s, red_k, bs, bk);
     const double root = roots[set];
     const int cell = (int)~bk;
     if (pass == 1) {
@@ -220,8 +231,7 @@ __global__ __launch_bounds__(kLocateThreads) void k_locate_finish(const long lon
         lags[(size_t)set * g.P + p] = lag;
         corr[(size_t)set * g.P + p] = c;
     }
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) inside += __shfl_xor(inside, off, kWave);
+    inside = locate_wave_sum(inside);
     if ((t & (kWave - 1)) == 0) red_n[t / kWave] = inside;
     __syncthreads();
     if (t != 0) return;

@@ -61,6 +61,17 @@ __device__ __forceinline__ long long locate_m_masked(const long long *q, int32_t
     return v < 0 ? -v : v;
 }
 
+// lag_p(cell) of pair p of a set where it lies inside the searched range, kLocateNoCentre otherwise: the centre round 0 leaves
+__device__ __forceinline__ int32_t locate_centre(const LocateGeom &g, const int32_t *table, const long long *cdiff, int set, int cell, int p)
+{
+    int i, j;
+    locate_pair(p, g.S, &i, &j);
+    const long long l = locate_lag(table[(size_t)i * g.n_cells + cell], table[(size_t)j * g.n_cells + cell],
+                                   cdiff ? cdiff[(size_t)set * g.P + p] : 0),
+                    idx = l - g.lag_lo;
+    return idx >= 0 && idx < g.n ? (int32_t)l : kLocateNoCentre;
+}
+
 // One workgroup per set, after round 0's finish has left the location's cell in best (-1: none):
 // centres[set][pair].c[0] = lag_p(cell*) where the round found a cell and the lag lies inside the range; c[1 ..] = none yet.
 __global__ __launch_bounds__(kLocateThreads) void k_locate_centres(LocateGeom g, const int32_t *table, const long long *cdiff,
@@ -69,15 +80,7 @@ __global__ __launch_bounds__(kLocateThreads) void k_locate_centres(LocateGeom g,
     const int set = blockIdx.x, cell = best[set];
     const bool found = cell >= 0 && cell < g.n_cells;
     for (int p = threadIdx.x; p < g.P; p += kLocateThreads) {
-        int32_t c = kLocateNoCentre;
-        if (found) {
-            int i, j;
-            locate_pair(p, g.S, &i, &j);
-            const long long l = locate_lag(table[(size_t)i * g.n_cells + cell], table[(size_t)j * g.n_cells + cell],
-                                           cdiff ? cdiff[(size_t)set * g.P + p] : 0),
-                            idx = l - g.lag_lo;
-            if (idx >= 0 && idx < g.n) c = (int32_t)l;
-        }
+        const int32_t c = found ? locate_centre(g, table, cdiff, set, cell, p) : kLocateNoCentre;
         LocateCentres cc;
         cc.c[0] = c;
         for (int r = 1; r < kLocateMaxEmitters; r++) cc.c[r] = kLocateNoCentre;
@@ -147,16 +150,9 @@ __global__ __launch_bounds__(kLocateThreads) void k_locate_finish_masked(const l
     __shared__ uint32_t red_k[kLocateThreads / kWave];
     __shared__ int red_n[kLocateThreads / kWave];
     const int set = blockIdx.x, t = threadIdx.x;
-    long long bs = kClosureAbsent;
-    uint32_t bk = 0;
-    for (int y = t; y < g.tiles; y += kLocateThreads) {
-        const ClosureCand c = partial[(size_t)set * g.tiles + y];
-        if (closure_better(c.score, c.key, bs, bk)) {
-            bs = c.score;
-            bk = c.key;
-        }
-    }
-    closure_block_best(bs, bk, red_s, red_k);
+    long long bs;
+    uint32_t bk;
+    locate_best_candidate(partial + (size_t)set * g.tiles, g.tiles, red_s, red_k, bs, bk);
     const double root = roots[set];
     const int cell = (int)~bk;
     const bool found = bs > 0 && cell >= 0 && cell < g.n_cells;
@@ -179,8 +175,7 @@ __global__ __launch_bounds__(kLocateThreads) void k_locate_finish_masked(const l
         corr[(size_t)set * g.P + p] = c;
         cen[p].c[mk.round] = centre;
     }
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) counts += __shfl_xor(counts, off, kWave);
+    counts = locate_wave_sum(counts);
     if ((t & (kWave - 1)) == 0) red_n[t / kWave] = counts;
     __syncthreads();
     if (t != 0) return;

@@ -20,14 +20,6 @@
 
 namespace tdoa {
 
-// the sum of a wave's counts, in every lane
-__device__ __forceinline__ int track_multi_wave_sum(int v)
-{
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
-
 // One workgroup per stack (set = track * L + position), after round 0's k_cell_track_finish has left the tracks' cells in
 // `cells` [set] and L_0 in best [track] (-1: the zero record):
 // centres[set][pair].c[0] = lag_p^j(L_j) where the track was found and the lag lies inside the range; c[1 ..] = none yet;
@@ -42,24 +34,14 @@ __global__ __launch_bounds__(kLocateThreads) void k_track_centres(LocateGeom g, 
     const bool found = best[set / L] >= 0 && cell >= 0 && cell < g.n_cells;
     int inside = 0;
     for (int p = t; p < g.P; p += kLocateThreads) {
-        int32_t c = kLocateNoCentre;
-        if (found) {
-            int i, j;
-            locate_pair(p, g.S, &i, &j);
-            const long long l = locate_lag(table[(size_t)i * g.n_cells + cell], table[(size_t)j * g.n_cells + cell],
-                                           cdiff ? cdiff[(size_t)set * g.P + p] : 0),
-                            idx = l - g.lag_lo;
-            if (idx >= 0 && idx < g.n) {
-                c = (int32_t)l;
-                inside++;
-            }
-        }
+        const int32_t c = found ? locate_centre(g, table, cdiff, set, cell, p) : kLocateNoCentre;
+        inside += c != kLocateNoCentre;
         LocateCentres cc;
         cc.c[0] = c;
         for (int r = 1; r < kLocateMaxEmitters; r++) cc.c[r] = kLocateNoCentre;
         centres[(size_t)set * g.P + p] = cc;
     }
-    inside = track_multi_wave_sum(inside);
+    inside = locate_wave_sum(inside);
     if ((t & (kWave - 1)) == 0) red_n[t / kWave] = inside;
     __syncthreads();
     if (t != 0) return;
@@ -87,41 +69,13 @@ __global__ __launch_bounds__(kCellTrackThreads) void k_cell_track_finish_masked(
     __shared__ uint32_t red_k[kCellTrackThreads / kWave];
     __shared__ int32_t path[kCellTrackMaxLen];
     const int track = blockIdx.x, t = threadIdx.x;
-    long long bs = kClosureAbsent;
-    uint32_t bk = 0;
-    for (int y = t; y < lg.tiles; y += kCellTrackThreads) {
-        const ClosureCand c = partial[(size_t)track * lg.tiles + y];
-        if (closure_better(c.score, c.key, bs, bk)) {
-            bs = c.score;
-            bk = c.key;
-        }
-    }
-    closure_block_best(bs, bk, red_s, red_k);
+    long long bs;
+    uint32_t bk;
+    locate_best_candidate(partial + (size_t)track * lg.tiles, lg.tiles, red_s, red_k, bs, bk);
     const int cell = (int)~bk;
     const bool found = bs > 0 && cell >= 0 && cell < g.n_cells;
     const size_t set0 = (size_t)track * g.L;
-    int steps = 0;
-    if (!found) {
-        for (int j = t; j < g.L; j += kCellTrackThreads) {
-            cells[set0 + j] = 0;
-            own[set0 + j] = 0;
-        }
-    } else if (t == 0) {
-        int c = cell;
-        for (int j = 0; j < g.L; j++) {
-            path[j] = c;
-            cells[set0 + j] = c;
-            own[set0 + j] = map[(set0 + j) * g.n_cells + c];
-            if (j + 1 == g.L) break;
-            const signed char *d = D + ((set0 + j) * g.n_cells + c) * 2;
-            const long long next = (long long)c + (long long)d[0] * g.n_cols + d[1];
-            if (next != c && next >= 0 && next < g.n_cells) {        // (D_j of a cell that exists names a cell that exists)
-                c = (int)next;
-                steps++;
-            }
-        }
-    }
-    __syncthreads();
+    const int steps = cell_track_walk(g, map, D, set0, found, cell, path, cells, own);
     const int lane = t & (kWave - 1);
     for (int j = t / kWave; j < g.L; j += kCellTrackThreads / kWave) {
         const size_t set = set0 + j;
@@ -143,7 +97,7 @@ __global__ __launch_bounds__(kCellTrackThreads) void k_cell_track_finish_masked(
             corr[set * lg.P + p] = c;
             cen[p].c[mk.round] = centre;
         }
-        counts = track_multi_wave_sum(counts);
+        counts = locate_wave_sum(counts);
         if (lane == 0) {
             pairs[2 * set] = counts & 0xffff;
             pairs[2 * set + 1] = counts >> 16;

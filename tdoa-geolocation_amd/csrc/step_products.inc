@@ -39,7 +39,7 @@ struct StepView {
 
 // the product of one step; the numbers are the first word a product appends to the graph key
 struct StepProduct {
-    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6, Locate = 7, Sync = 8, CellTrack = 9, LocateMulti = 10, CellTrackMulti = 11 };
+    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6, Locate = 7, Sync = 8 };
     virtual int reserve(const StepView &v) = 0;
     virtual void key(std::vector<uint64_t> *key) const = 0;
     virtual int upload(const StepView &) { return TDOA_OK; }
@@ -397,89 +397,33 @@ struct ClosureProduct : StackProduct {
     int download(const StepView &v) const override { return download_closure(v.ctx, layout.n_stacks, geom(v.ctx), out_host); }
 };
 
-// ---- the delay-table search on the stacks' sums (stack_locate.hpp, locate_api.inc) -------------------------------------
-// Its stack has no output of its own either.
+// ---- the delay-table family on the stacks' sums (locate_run.inc): tdoa_process_locate, tdoa_process_locate_multi, ---------
+// tdoa_process_locate_track and tdoa_process_locate_track_multi.  Its stack has no output of its own either.  A track spans a
+// block: L = the stacks per block, and the three blocks' tracks hold all their windows.
 struct LocateProduct : StackProduct {
-    int sep = 1;                             // min_separation
+    LocateCall call;                         // the entry's arguments and outputs
     int n_cells = 0, n_cols = 0;             // the shape of the context's table: in the key (the table itself is data)
     bool clocked = false;                    // the context holds station clocks: in the key (another kernel; the clocks are data)
     uint64_t stats = 0;                      // map statistics (map_stats_key): in the key (more kernels; the ranks are data), 0: off
-    tdoa_location *loc_host = nullptr;       // [stack]
-    int32_t *lags_host = nullptr;            // [stack][pair]
-    double *corr_host = nullptr;             // [stack][pair]
-    int64_t *map_host = nullptr;             // [stack][cell]
-
-    int reserve(const StepView &v) override
-    {
-        if (int rc = StackProduct::reserve(v)) return rc;
-        return ensure_locate(v.ctx, layout.n_stacks, locate_geom(v.ctx, sep));
-    }
-    void key(std::vector<uint64_t> *key) const override
-    {
-        key->insert(key->end(), {Locate, (uint64_t)m, (uint64_t)sep, (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked, stats});
-    }
-    void enqueue(const StepView &v) const override
-    {
-        tdoa_ctx *ctx = v.ctx;
-        StackProduct::enqueue(v);
-        launch_locate(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, layout.n_stacks, v.P).roots, layout.n_stacks, locate_geom(ctx, sep));
-    }
-    int download(const StepView &v) const override
-    {
-        return download_locate(v.ctx, layout.n_stacks, locate_geom(v.ctx, sep), loc_host, lags_host, corr_host, map_host);
-    }
-};
-
-// ---- several emitters per stack: the search's rounds on masked lags (stack_locate_multi.hpp, locate_multi_api.inc) --------
-// The outputs are [round][stack] planes; the excluded intervals' centres stay on the device.
-struct LocateMultiProduct : LocateProduct {
-    int K = 1, guard = 0;                    // n_emitters, guard: in the key (the launches and the mask; the centres are data)
-
-    int reserve(const StepView &v) override
-    {
-        if (int rc = StackProduct::reserve(v)) return rc;
-        return ensure_locate_multi(v.ctx, layout.n_stacks, K, locate_geom(v.ctx, sep));
-    }
-    void key(std::vector<uint64_t> *key) const override
-    {
-        key->insert(key->end(), {LocateMulti, (uint64_t)m, (uint64_t)K, (uint64_t)guard, (uint64_t)sep,
-                                 (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked, stats});
-    }
-    void enqueue(const StepView &v) const override
-    {
-        tdoa_ctx *ctx = v.ctx;
-        StackProduct::enqueue(v);
-        launch_locate_multi(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, layout.n_stacks, v.P).roots, layout.n_stacks, K, guard,
-                            locate_geom(ctx, sep));
-    }
-    int download(const StepView &v) const override
-    {
-        return download_locate_multi(v.ctx, layout.n_stacks, K, locate_geom(v.ctx, sep), loc_host, lags_host, corr_host, map_host);
-    }
-};
-
-// ---- cell tracks through the maps of a block's stacks (stack_cell_track.hpp, locate_track_api.inc) ---------------------
-// The search's own records stay on the device; lags_host and corr_host receive the track's positions' instead of the best
-// cells'.  A track spans a block: L = the stacks per block, and the three blocks' tracks hold all their windows.
-struct CellTrackProduct : LocateProduct {
-    int J = 0;                               // max_step
-    tdoa_cell_track *track_host = nullptr;   // [track]
-    int32_t *cells_host = nullptr;           // [track][L]
-    int64_t *own_host = nullptr;             // [track][L]
-    int64_t *total_host = nullptr;           // [track][cell]
     std::vector<double> track_roots;         // refresh's host copy of sqrt(N_w) (lives until the call has synchronised)
 
+    LocateRun run(const tdoa_ctx *ctx) const { return locate_run(ctx, call, layout.n_stacks, layout.spb); }
     int reserve(const StepView &v) override
     {
-        if (int rc = LocateProduct::reserve(v)) return rc;
-        return ensure_locate_track(v.ctx, layout.n_stacks, layout.spb, locate_geom(v.ctx, sep));
+        if (int rc = StackProduct::reserve(v)) return rc;
+        return ensure_locate_run(v.ctx, run(v.ctx));
     }
+    // everything the launches depend on: the rounds and the mask, the tracks' length (0: none) and step, whether the counts are
+    // produced (the centres are data)
     void key(std::vector<uint64_t> *key) const override
     {
-        key->insert(key->end(), {CellTrack, (uint64_t)m, (uint64_t)J, (uint64_t)sep, (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked, stats});
+        const uint64_t L = call.tracks ? (uint64_t)layout.spb : 0, pairs = call.tracks && call.rounds;
+        key->insert(key->end(), {Locate, (uint64_t)m, L | (pairs << 32), (uint64_t)call.J, (uint64_t)call.K, (uint64_t)call.guard,
+                                 (uint64_t)call.sep, (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked, stats});
     }
     int refresh(const StepView &v) override  // (every call: the debug and the group's calls write their own roots there)
     {
+        if (!call.tracks) return TDOA_OK;
         track_roots = block_track_roots(v.wpb);
         return upload_locate_track_roots(v.ctx, track_roots);
     }
@@ -487,46 +431,9 @@ struct CellTrackProduct : LocateProduct {
     {
         tdoa_ctx *ctx = v.ctx;
         StackProduct::enqueue(v);
-        launch_locate(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, layout.n_stacks, v.P).roots, layout.n_stacks, locate_geom(ctx, sep),
-                      false);                // (the track judges T_0, not the maps)
-        launch_locate_track(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, layout.n_stacks, v.P).roots, layout.n_stacks, layout.spb, J,
-                            locate_geom(ctx, sep));
+        launch_locate_run(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, layout.n_stacks, v.P).roots, run(ctx));
     }
-    int download(const StepView &v) const override
-    {
-        return download_locate_track(v.ctx, layout.n_stacks, layout.spb, locate_geom(v.ctx, sep), track_host, cells_host, own_host, lags_host,
-                                     corr_host, total_host);
-    }
-};
-
-// ---- several emitters per block: the cell tracks' rounds on masked lags (stack_locate_track_multi.hpp, -------------------
-// locate_track_multi_api.inc).  The outputs are [round] planes; the excluded intervals' centres stay on the device.
-struct CellTrackMultiProduct : CellTrackProduct {
-    int K = 1, guard = 0;                    // n_emitters, guard: in the key (the launches and the mask; the centres are data)
-    int32_t *pairs_host = nullptr;           // [round][stack][2]: pairs_in, reserved
-
-    int reserve(const StepView &v) override
-    {
-        if (int rc = StackProduct::reserve(v)) return rc;
-        return ensure_locate_track_multi(v.ctx, layout.n_stacks, layout.spb, K, locate_geom(v.ctx, sep));
-    }
-    void key(std::vector<uint64_t> *key) const override
-    {
-        key->insert(key->end(), {CellTrackMulti, (uint64_t)m, (uint64_t)J, (uint64_t)K, (uint64_t)guard, (uint64_t)sep,
-                                 (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked, stats});
-    }
-    void enqueue(const StepView &v) const override
-    {
-        tdoa_ctx *ctx = v.ctx;
-        StackProduct::enqueue(v);
-        launch_locate_track_multi(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, layout.n_stacks, v.P).roots, layout.n_stacks,
-                                  layout.spb, J, K, guard, locate_geom(ctx, sep));
-    }
-    int download(const StepView &v) const override
-    {
-        return download_locate_track_multi(v.ctx, layout.n_stacks, layout.spb, K, locate_geom(v.ctx, sep), track_host, cells_host, own_host,
-                                           pairs_host, lags_host, corr_host, total_host);
-    }
+    int download(const StepView &v) const override { return download_locate_run(v.ctx, run(v.ctx), call); }
 };
 
 // ---- the clock search on the stacks' sums (stack_sync.hpp, sync_api.inc) ------------------------------------------------

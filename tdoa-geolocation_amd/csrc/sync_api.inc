@@ -1,6 +1,6 @@
 // sync_api.inc -- the clock search, host side: its buffers, the kernels' launches (shared by a context's own step,
 // step_products.inc, the group's merged sum and tdoa_debug_sync_from_q).
-// Included by tdoa_mi355x.hip after locate_api.inc and before step_products.inc.
+// Included by tdoa_mi355x.hip after locate_api.inc and locate_run.inc and before step_products.inc.
 
 extern "C" {
 

@@ -182,7 +182,7 @@ struct tdoa_ctx {
     // track, the records [track], the tracks' cells and own scores [stack]
     DevBuf ctrack_d, ctrack_t, ctrack_roots, ctrack_out, ctrack_cells, ctrack_own;
     // several emitters per block (tdoa_process_locate_track_multi): the tracks' buffers above hold one plane per round (T as
-    // locate_track_multi_api.inc lays it out), and pairs_in and reserved [round][stack][2]
+    // locate_run.inc lays it out), and pairs_in and reserved [round][stack][2]
     DevBuf ctrack_pairs;
     // map statistics (state: tdoa_locate_set_stats; 0 ranks: off): the ranks (eight words), the bins [plane][rank][2048] and
     // the selection's state [plane] of one group of planes, the statistics [plane], and the last call's on the host
@@ -396,9 +396,7 @@ int check_selection(tdoa_ctx *ctx, int k, int min_separation, const void *out)
 #include "closure_api.inc"
 #include "map_stats_api.inc"
 #include "locate_api.inc"
-#include "locate_track_api.inc"
-#include "locate_multi_api.inc"
-#include "locate_track_multi_api.inc"
+#include "locate_run.inc"
 #include "sync_api.inc"
 #include "step_products.inc"
 
@@ -1141,104 +1139,49 @@ int tdoa_process_closure(tdoa_ctx *ctx, int windows_per_stack, int gate, int min
     return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
 }
 
-int tdoa_process_locate(tdoa_ctx *ctx, int windows_per_stack, int min_separation, tdoa_location *loc_host, int32_t *lags_host,
-                        double *corr_host, int64_t *map_host)
+// The four entries of the delay-table family (locate_run.inc): what they refuse -- the arguments, then the station count, the
+// table, the overflow bounds and the track's length, which the group's call shares -- and the product.
+static int process_locate_call(tdoa_ctx *ctx, int windows_per_stack, const LocateCall &call)
 {
-    if (int rc = refuse_stacked(ctx, windows_per_stack, check_locate_args(min_separation, loc_host),
-                                "the delay-table search with TDOA_LAGS_GO", true))
-        return rc;
-    const char *what = nullptr;              // (the station count, the table, the overflow bound: shared with the group's call)
-    if (const int rc = check_locate_state(ctx, windows_per_stack, &what)) return fail(ctx, rc, what);
+    if (int rc = refuse_stacked(ctx, windows_per_stack, check_locate_call(call), "the delay-table search with TDOA_LAGS_GO", true)) return rc;
+    const char *what = nullptr;
+    if (const int rc = check_locate_state(ctx, windows_per_stack, call.tracks, &what)) return fail(ctx, rc, what);
     LocateProduct prod;
     fill_stack(&prod, windows_per_stack);
-    prod.sep = min_separation;
+    prod.call = call;
     prod.n_cells = ctx->locate_cells;
     prod.n_cols = ctx->locate_cols;
-    prod.loc_host = loc_host;
-    prod.lags_host = lags_host;
-    prod.corr_host = corr_host;
-    prod.map_host = map_host;
     prod.clocked = ctx->clock_stacks != 0;
     prod.stats = map_stats_key(ctx);
     return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
+}
+
+int tdoa_process_locate(tdoa_ctx *ctx, int windows_per_stack, int min_separation, tdoa_location *loc_host, int32_t *lags_host,
+                        double *corr_host, int64_t *map_host)
+{
+    return process_locate_call(ctx, windows_per_stack, locate_search_call(false, 1, 0, min_separation, loc_host, lags_host, corr_host, map_host));
 }
 
 int tdoa_process_locate_track(tdoa_ctx *ctx, int windows_per_stack, int max_step, int min_separation, tdoa_cell_track *track_host,
                               int32_t *cells_host, int64_t *own_host, int32_t *lags_host, double *corr_host, int64_t *total_host)
 {
-    if (int rc = refuse_stacked(ctx, windows_per_stack, check_locate_track_args(max_step, min_separation, track_host),
-                                "the delay-table search with TDOA_LAGS_GO", true))
-        return rc;
-    const char *what = nullptr;              // (what the search refuses, the track's overflow bound and length: shared with the group's call)
-    if (const int rc = check_locate_track_state(ctx, windows_per_stack, &what)) return fail(ctx, rc, what);
-    CellTrackProduct prod;
-    fill_stack(&prod, windows_per_stack);
-    prod.sep = min_separation;
-    prod.n_cells = ctx->locate_cells;
-    prod.n_cols = ctx->locate_cols;
-    prod.clocked = ctx->clock_stacks != 0;
-    prod.stats = map_stats_key(ctx);
-    prod.J = max_step;
-    prod.track_host = track_host;
-    prod.cells_host = cells_host;
-    prod.own_host = own_host;
-    prod.lags_host = lags_host;
-    prod.corr_host = corr_host;
-    prod.total_host = total_host;
-    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
+    return process_locate_call(ctx, windows_per_stack, locate_track_call(false, max_step, 1, 0, min_separation, track_host, cells_host, own_host,
+                                                                         nullptr, lags_host, corr_host, total_host));
 }
 
 int tdoa_process_locate_multi(tdoa_ctx *ctx, int windows_per_stack, int n_emitters, int guard, int min_separation, tdoa_location *loc_host,
                               int32_t *lags_host, double *corr_host, int64_t *map_host)
 {
-    if (int rc = refuse_stacked(ctx, windows_per_stack, check_locate_multi_args(n_emitters, guard, min_separation, loc_host),
-                                "the delay-table search with TDOA_LAGS_GO", true))
-        return rc;
-    const char *what = nullptr;              // (what the search refuses: shared with the group's call)
-    if (const int rc = check_locate_state(ctx, windows_per_stack, &what)) return fail(ctx, rc, what);
-    LocateMultiProduct prod;
-    fill_stack(&prod, windows_per_stack);
-    prod.sep = min_separation;
-    prod.n_cells = ctx->locate_cells;
-    prod.n_cols = ctx->locate_cols;
-    prod.clocked = ctx->clock_stacks != 0;
-    prod.stats = map_stats_key(ctx);
-    prod.K = n_emitters;
-    prod.guard = guard;
-    prod.loc_host = loc_host;
-    prod.lags_host = lags_host;
-    prod.corr_host = corr_host;
-    prod.map_host = map_host;
-    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
+    return process_locate_call(ctx, windows_per_stack,
+                               locate_search_call(true, n_emitters, guard, min_separation, loc_host, lags_host, corr_host, map_host));
 }
 
 int tdoa_process_locate_track_multi(tdoa_ctx *ctx, int windows_per_stack, int max_step, int n_emitters, int guard, int min_separation,
                                     tdoa_cell_track *track_host, int32_t *cells_host, int64_t *own_host, int32_t *pairs_host,
                                     int32_t *lags_host, double *corr_host, int64_t *total_host)
 {
-    if (int rc = refuse_stacked(ctx, windows_per_stack, check_locate_track_multi_args(max_step, n_emitters, guard, min_separation, track_host),
-                                "the delay-table search with TDOA_LAGS_GO", true))
-        return rc;
-    const char *what = nullptr;              // (what the cell tracks refuse: shared with the group's call)
-    if (const int rc = check_locate_track_state(ctx, windows_per_stack, &what)) return fail(ctx, rc, what);
-    CellTrackMultiProduct prod;
-    fill_stack(&prod, windows_per_stack);
-    prod.sep = min_separation;
-    prod.n_cells = ctx->locate_cells;
-    prod.n_cols = ctx->locate_cols;
-    prod.clocked = ctx->clock_stacks != 0;
-    prod.stats = map_stats_key(ctx);
-    prod.J = max_step;
-    prod.K = n_emitters;
-    prod.guard = guard;
-    prod.track_host = track_host;
-    prod.cells_host = cells_host;
-    prod.own_host = own_host;
-    prod.pairs_host = pairs_host;
-    prod.lags_host = lags_host;
-    prod.corr_host = corr_host;
-    prod.total_host = total_host;
-    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
+    return process_locate_call(ctx, windows_per_stack, locate_track_call(true, max_step, n_emitters, guard, min_separation, track_host, cells_host,
+                                                                         own_host, pairs_host, lags_host, corr_host, total_host));
 }
 
 int tdoa_process_sync(tdoa_ctx *ctx, int windows_per_stack, int gate, int rounds, const int32_t *ref_delay, const int32_t *centre,

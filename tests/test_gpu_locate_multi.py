@@ -293,6 +293,10 @@ def test_graph_replays_and_leaves_its_neighbours_alone(pipeline):
     assert all(_same_bytes(after[k], stack[k]) for k in stack)
     after = c.process_locate(2, 2, want_map=True)
     assert all(_same_bytes(after[k], plain[k]) for k in plain)
+    one = c.process_locate_multi(2, 1, 0, 2, want_map=True)              # K = 1, guard 0: the search's launches -- the search's
+    assert all(_same_bytes(one[k][0], plain[k]) for k in NAMES)          # bytes, whichever entry's call captured the step
+    after = c.process_locate(2, 2, want_map=True)
+    assert all(_same_bytes(after[k], plain[k]) for k in plain)
     assert _same_bytes(_windows_q(c), q)                                 # Q is never written
 
 
