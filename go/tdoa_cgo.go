@@ -425,6 +425,58 @@ func (g *gpuCorrelator) ProcessSync(windowsPerStack, gate, rounds int, refDelay,
 	return sync, clock, lags, corr, nil
 }
 
+// SyncLines is what ProcessSyncDrift returns: one record, the clocks (samples) and the rates per block ([3][station]); per
+// stack the clock rows in units of 1/16 sample ([stack][station], what LocateSetClock takes for that block) and per stack and
+// pair the lag along the line and the signed correlation of that stack there.
+type SyncLines struct {
+	Line        []C.tdoa_sync_line
+	Clock, Rate []int32
+	Rows, Lags  []int32
+	Corr        []float64
+}
+
+func newSyncLines(total, stations, pairs int) *SyncLines {
+	return &SyncLines{Line: make([]C.tdoa_sync_line, 3), Clock: make([]int32, 3*stations), Rate: make([]int32, 3*stations),
+		Rows: make([]int32, total*stations), Lags: make([]int32, total*pairs), Corr: make([]float64, total*pairs)}
+}
+
+func i32Ptr(a []int32) *C.int32_t { return (*C.int32_t)(unsafe.Pointer(&a[0])) }
+
+// ProcessSyncDrift is the clock-line search (the header's "clock lines"): per block the stations' clocks k_s(j) = k_s +
+// shift(h_s, j) along the block's stacks, |k_s - centre[s]| <= gate, |h_s| <= maxDrift in units of 1/driftDen lag per stack,
+// station 0 the gauge, that make all pairs' signed sums along the block largest at the lags the known emitter's delays
+// refDelay predict -- the placing and `rounds` sweeps.  SyncLineClock continues a line past its block.
+func (g *gpuCorrelator) ProcessSyncDrift(windowsPerStack, gate, maxDrift, driftDen, rounds int, refDelay, centre []int32) (*SyncLines, error) {
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs, stations := int(C.tdoa_num_pairs(g.ctx)), len(refDelay)
+	if int(total)*pairs == 0 || stations*(stations-1)/2 != pairs {
+		return nil, fmt.Errorf("tdoa_process_sync_drift: no stacks, fewer than two stations, or not one delay per station")
+	}
+	o := newSyncLines(int(total), stations, pairs)
+	if rc := C.tdoa_process_sync_drift(g.ctx, C.int(windowsPerStack), C.int(gate), C.int(maxDrift), C.int(driftDen), C.int(rounds),
+		tablePtr(refDelay), centrePtr(centre), &o.Line[0], i32Ptr(o.Clock), i32Ptr(o.Rate), i32Ptr(o.Rows), i32Ptr(o.Lags),
+		(*C.double)(unsafe.Pointer(&o.Corr[0]))); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_process_sync_drift: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return o, nil
+}
+
+// SyncLineClock continues one line (clock in samples and rate, one per station) over positions first .. first + n - 1 in
+// units of 1/16 sample: [position][station], what LocateSetClock takes.  Host only.
+func SyncLineClock(clock, rate []int32, driftDen, first, n int) ([]int32, error) {
+	if len(clock) == 0 || len(clock) != len(rate) || n < 1 {
+		return nil, fmt.Errorf("tdoa_sync_line_clock: one clock and one rate per station, n >= 1")
+	}
+	out := make([]int32, n*len(clock))
+	if rc := C.tdoa_sync_line_clock(i32Ptr(clock), i32Ptr(rate), C.int(len(clock)), C.int(driftDen), C.int(first), C.int(n), i32Ptr(out)); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_sync_line_clock: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	return out, nil
+}
+
 // windowQuality is fastAnalyzeSamples' statistics (fast_analyzer.go:117-155) for every (window, station).
 func (g *gpuCorrelator) windowQuality(stations int) ([]C.tdoa_window_quality, error) {
 	var perBlock, total C.int
@@ -690,4 +742,25 @@ func (g *Group) ProcessSync(windowsPerStack, gate, rounds int, refDelay, centre 
 		return nil, nil, nil, nil, fmt.Errorf("tdoa_group_process_sync: %s", C.GoString(C.tdoa_group_last_error(g.g)))
 	}
 	return sync, clock, lags, corr, nil
+}
+
+// ProcessSyncDrift is gpuCorrelator.ProcessSyncDrift over the group: the members' fixed-point partial sums are added on the
+// host and searched on member 0, the same bytes one context returns.
+func (g *Group) ProcessSyncDrift(windowsPerStack, gate, maxDrift, driftDen, rounds int, refDelay, centre []int32) (*SyncLines, error) {
+	m := C.tdoa_group_member(g.g, 0)
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(m, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs, stations := int(C.tdoa_num_pairs(m)), len(refDelay)
+	if int(total)*pairs == 0 || stations*(stations-1)/2 != pairs {
+		return nil, fmt.Errorf("tdoa_group_process_sync_drift: no stacks, fewer than two stations, or not one delay per station")
+	}
+	o := newSyncLines(int(total), stations, pairs)
+	if rc := C.tdoa_group_process_sync_drift(g.g, C.int(windowsPerStack), C.int(gate), C.int(maxDrift), C.int(driftDen), C.int(rounds),
+		tablePtr(refDelay), centrePtr(centre), &o.Line[0], i32Ptr(o.Clock), i32Ptr(o.Rate), i32Ptr(o.Rows), i32Ptr(o.Lags),
+		(*C.double)(unsafe.Pointer(&o.Corr[0]))); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_group_process_sync_drift: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return o, nil
 }

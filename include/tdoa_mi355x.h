@@ -581,6 +581,85 @@ int tdoa_debug_sync_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_st
                            const int32_t *ref_delay, const int32_t *centre, tdoa_sync *sync, int32_t *clock, int32_t *lags,
                            double *corr);
 
+/* Clock lines: the stations' clock offsets and rates from a reference block.  tdoa_process_sync finds one offset per station
+ * per stack and assumes the clocks stand still inside that stack; free-running receivers drift by lags per second, so the
+ * whole-block stack smears along the drift and a one-window stack is where the noise wins.  This search takes the S - 1 clock
+ * rates together with the S - 1 clock offsets, over all pairs and all stacks of a block at once: the station-consistent form
+ * of tdoa_process_stacked_drift's slope search, as the clock search is of the per-pair argmax.
+ * Lines and positions.
+ *   Stacks, windows_per_stack, pairs i < j in the library's order, the int64 words Q_{sid,p}[l], e_ij from ref_delay, and
+ *     rank(x) = 2|x| - (x > 0) are those of tdoa_process_sync.
+ *   A line is one block.  Its positions are j = 0 .. L-1, the block's stacks in order (L = stacks_per_block).
+ *   The debug entry takes n_sets and track_len as tdoa_debug_locate_track_from_q does.
+ *   N_w is the number of windows of the whole line.
+ * Unknowns.
+ *   Per station s: k_s = centre[s] + x_s, |x_s| <= G (0 <= G <= 1023).
+ *   Per station s: a slope h_s, |h_s| <= H (0 <= H <= 512), of h_s / D lags per position (D >= 1).
+ *   Station 0 is the gauge: x_0 = 0, h_0 = 0.
+ *   Clock of s at position j: k_s(j) = k_s + shift(h_s, j), with shift(h, j) = sgn(h) * ((2|h|j + D) div (2D)), the slope
+ *     search's rule.
+ * Objective.
+ *   A_ij = sum over j of Q_{j,ij}[e_ij + k_j(j) - k_i(j)], the signed words summed along the line.
+ *   A term outside -max_lag < lag < max_lag adds 0 and is not counted in terms_in.
+ *   F = sum over i < j of |A_ij|.
+ * Candidates.
+ *   The candidates of a station are the (h, x) pairs in the order r = rank(h) * (2G+1) + rank(x).
+ *   "Largest" means the first of equal maxima in that order: smaller |h|, then the positive h, then smaller |x|, then the
+ *     positive x.
+ * Search.
+ *   Placing, for s = 1 .. S-1 in order: (x_s, h_s) is the largest sum over i < s of |A_is|, with the earlier stations where
+ *     they were put.
+ *   Sweeps, R times (0 <= R <= 16), for s = 1 .. S-1: (x_s, h_s) is the largest sum over i != s of |A_pair(i,s)|, with the sign
+ *     convention of the clock search's sweeps.
+ *   start_q is F after placing, and score_q is F at the end, so score_q >= start_q.
+ *   moved counts the stations whose (k, h) the last sweep changed.
+ *   If F = 0 at the end, every output of the line is zero.
+ * Overflow.  P * N_w > 2^17 returns TDOA_ERR_UNSUPPORTED.  The debug entry's precondition is |q| <= 2^62 div (P * L).
+ * The record, 40 bytes, no padding: */
+typedef struct {
+    int32_t moved, terms_in, positions, reserved;  /* stations the last sweep changed (0 when R = 0); terms inside the range at the end; L; 0 */
+    int64_t score_q, start_q;  /* F at the end; F after placing */
+    double  score;             /* (double)score_q * 2^-32 / sqrt(N_w) */
+} tdoa_sync_line;
+
+/* Outputs.  Per line (the three blocks in order): the record, clock[S] (k_s, in samples) and rate[S] (h_s).  Per stack:
+ * rows[n_stacks_total][S] = 16 * k_s(j), what tdoa_locate_set_clock takes for that block.  Per stack and pair: the lag along
+ * the line and the signed C of that stack there (0 and 0.0 outside the range).
+ * Runs on all three blocks, as the other stack products do; the caller reads the line of the block whose emitter it
+ * described.  Runs inside the step graph, behind the stack's accumulation: per step of a station one launch over tiles of 256
+ * candidates and one that commits the tiles' best, then the outputs.  (windows_per_stack, gate, max_drift, drift_den, rounds)
+ * are part of the graph's key; ref_delay, centre and the shift table are data in device buffers, so a call that changes only
+ * the delays and centres replays the same graph.
+ * TDOA_ERR_INVALID: what tdoa_process_sync refuses (line_host in the place of sync_host), max_drift < 0 or > 512, drift_den
+ * < 1.  TDOA_ERR_STATE and TDOA_ERR_UNSUPPORTED: as its sibling, the overflow bound taken on the block's windows. */
+int tdoa_process_sync_drift(tdoa_ctx *ctx, int windows_per_stack, int gate /* G */, int max_drift /* H */, int drift_den /* D */,
+                            int rounds /* R */, const int32_t *ref_delay /* [n_stations] */,
+                            const int32_t *centre /* [n_stations] or NULL */,
+                            tdoa_sync_line *line_host /* [3], required */,
+                            int32_t   *clock_host /* [3][n_stations]: k_s in samples; may be NULL */,
+                            int32_t   *rate_host  /* [3][n_stations]: h_s; may be NULL */,
+                            int32_t   *rows_host  /* [n_stacks_total][n_stations]: 16 k_s(j); may be NULL */,
+                            int32_t   *lags_host  /* [n_stacks_total][n_pairs]; may be NULL */,
+                            double    *corr_host  /* same shape; may be NULL */);
+
+/* tests only: the same kernels on the caller's words q [n_sets][P][2*max_lag-1], every set a stack of n_w windows, set
+ * t * track_len + j position j of line t, so N_w = track_len * n_w; outputs as tdoa_process_sync_drift's with n_sets /
+ * track_len lines and n_sets stacks.  Needs a context for max_lag and the device, and no captures.
+ * TDOA_ERR_INVALID: what tdoa_process_sync_drift refuses, q NULL, n_sets outside 1 .. 65535, n_w < 1, n_stations outside
+ * 2 .. 64, track_len < 1 or not a divisor of n_sets.  TDOA_ERR_UNSUPPORTED: P * track_len * n_w > 2^17. */
+int tdoa_debug_sync_drift_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, int gate,
+                                 int max_drift, int drift_den, int rounds, const int32_t *ref_delay, const int32_t *centre,
+                                 tdoa_sync_line *line, int32_t *clock, int32_t *rate, int32_t *rows, int32_t *lags,
+                                 double *corr);
+
+/* Host helper, no device: writes out[j - first_position][s] = 16 * k_s + r(16 * h_s * j, D) for j = first_position ..
+ * first_position + n_positions - 1.  Here r is the nearest integer, halves away from zero, in integers only.  This is the
+ * line continued past its block at the table's 1/16 sample.  It assumes, as the ramp between two reference blocks does, that
+ * the blocks follow one another without a gap.  TDOA_ERR_INVALID: a NULL pointer, n_stations < 1, drift_den < 1,
+ * first_position < 0, n_positions < 1. */
+int tdoa_sync_line_clock(const int32_t *clock, const int32_t *rate, int n_stations, int drift_den, int first_position,
+                         int n_positions, int32_t *out /* [n_positions][n_stations] */);
+
 /* Cell tracks: follow an emitter from stack to stack through the delay-table search's maps.  tdoa_process_locate locates
  * every stack alone.  Stations with free-running clocks give every stack of a target block its own clock row, so the block's
  * windows cannot be summed lag by lag; their maps can be added cell by cell, because every map is in the emitter's
@@ -1010,6 +1089,15 @@ int tdoa_group_locate_set_clock(tdoa_group *g, const int32_t *clock, int n_stack
 int tdoa_group_process_sync(tdoa_group *g, int windows_per_stack, int gate, int rounds, const int32_t *ref_delay,
                             const int32_t *centre, tdoa_sync *sync_host, int32_t *clock_host, int32_t *lags_host,
                             double *corr_host);
+
+/* tdoa_process_sync_drift over the members: they sum their windows as in tdoa_group_process_stacked, the host adds the
+ * partials, and member 0 runs the search on the merged Q.  F is a function of the complete stacked Q only, so the members'
+ * partial sums merge as they do for tdoa_group_process_sync.  The group returns a single context's bytes.  Errors as there and
+ * as tdoa_group_process.  With one member, its call writes the outputs directly. */
+int tdoa_group_process_sync_drift(tdoa_group *g, int windows_per_stack, int gate, int max_drift, int drift_den, int rounds,
+                                  const int32_t *ref_delay, const int32_t *centre, tdoa_sync_line *line_host,
+                                  int32_t *clock_host, int32_t *rate_host, int32_t *rows_host, int32_t *lags_host,
+                                  double *corr_host);
 
 /* tdoa_process_locate_track over the members (the table and the clocks as set by tdoa_group_locate_set_table and
  * tdoa_group_locate_set_clock): they sum their windows as in tdoa_group_process_stacked, the host adds the partials, and

@@ -25,10 +25,13 @@ centres, then per further round the masked scores, the recurrence and four to fi
 through the other entry).  `--stack M` gives the locate, locate-track, emitters and track-emitters legs stacks
 of M windows (default 0: whole blocks, one position per track).  `--map-stats R1,R2[/FOOT]` adds, next to each of those four
 kinds of leg, the same leg with the map statistics on (tdoa_locate_set_stats with those ranks and FOOT, default 0; name
-..._stats_ms): the statistics' kernels and their download come on top, the planes stay on the device.  `--stations S` runs all
+..._stats_ms): the statistics' kernels and their download come on top, the planes stay on the device.  Every `--sync-drift G/H[/D[/R]]` adds a leg:
+tdoa_process_sync_drift(M, G, H, D, R) (D defaults to 1, R to 2; M from `--stack`) against the same delays, with the records,
+clocks, rates, rows, lags and correlations downloaded (the stack's accumulation, then two launches per station's step: (2G+1)
+(2H+1) candidates in tiles of 256, and the commit; H = 0 is the search's fixed cost).  `--stations S` runs all
 legs on S stations (default 3; 8 gives 56 triples).
 usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--stack M] [--drift H/D]... [--track J]...
-[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]..."""
+[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]..."""
 import json
 import os
 import sys
@@ -58,7 +61,7 @@ def timed(fn, steps):
 
 
 def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=(), locate_tracks=(), stack=0, emitters=(),
-         track_emitters=(), map_stats=None):
+         track_emitters=(), map_stats=None, sync_drifts=()):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=20000)
     for s in range(stations):
         c.synth_capture(s, 66_666_666, ST[s % 3], TX, 0x5D0A0000 + s)
@@ -99,6 +102,8 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
     ref = tdoa_amd.capi.locate_grid_table([ST[s % 3] for s in range(stations)], TX[0], TX[1], 0.0, 0.0, 1, 1, TX[2], 2e6)[0]
     for G, R in syncs:
         legs["process_sync_%d_%d_ms" % (G, R)] = lambda G=G, R=R: c.process_sync(ref, 0, G, R)
+    for G, H, D, R in sync_drifts:
+        legs["process_sync_drift_%d_%d_%d_%d_ms" % (G, H, D, R)] = lambda G=G, H=H, D=D, R=R: c.process_sync_drift(ref, stack, G, H, D, R)
     times = {name: [] for name in legs}
     for _ in range(rounds):
         for name, fn in legs.items():
@@ -168,6 +173,12 @@ if __name__ == "__main__":
         rows, _, cols = args[i + 1].partition("x")
         locates.append((int(rows), int(cols)))
         del args[i:i + 2]
+    sync_drifts = []
+    while "--sync-drift" in args:
+        i = args.index("--sync-drift")
+        parts = args[i + 1].split("/")
+        sync_drifts.append((int(parts[0]), int(parts[1]), int(parts[2]) if len(parts) > 2 else 1, int(parts[3]) if len(parts) > 3 else 2))
+        del args[i:i + 2]
     syncs = []
     while "--sync" in args:
         i = args.index("--sync")
@@ -175,4 +186,4 @@ if __name__ == "__main__":
         syncs.append((int(g), int(r or 2)))
         del args[i:i + 2]
     main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs, locate_tracks, opt["--stack"], emitters,
-         track_emitters, map_stats)
+         track_emitters, map_stats, sync_drifts)

@@ -129,10 +129,12 @@ int tdoa_debug_poison_workspace(tdoa_ctx *ctx)
     // tdoa_process_track -- its steps, track_d, are added to lag indices and stay as they are; the closure search's
     // candidates, cells and records are compared and copied, never added to an address; the delay-table search's map,
     // candidates and records likewise -- a cell taken from a candidate is checked against the table's size -- and its table,
-    // which is state, is left alone)
+    // which is state, is left alone; the clock-line search's clocks only enter lags that are checked against the range, and a
+    // candidate's number taken from its tiles is clamped to the candidates there are)
     for (DevBuf *b : {&ctx->v, &ctx->tz, &ctx->fine_raw, &ctx->once_edges, &ctx->surf, &ctx->surf_out, &ctx->stack_q, &ctx->stack_surf,
                       &ctx->track_t, &ctx->closure_part, &ctx->closure_best, &ctx->closure_out, &ctx->locate_map, &ctx->locate_part,
-                      &ctx->locate_best, &ctx->locate_out, &ctx->locate_lags, &ctx->locate_corr})
+                      &ctx->locate_best, &ctx->locate_out, &ctx->locate_lags, &ctx->locate_corr, &ctx->sline_cur, &ctx->sline_part,
+                      &ctx->sline_out, &ctx->sline_rows, &ctx->sline_lags, &ctx->sline_corr})
         if (b->p && b->cap >= 4) HIPCHK(ctx, hipMemsetD32Async(static_cast<hipDeviceptr_t>(b->p), 0x7FC00000, b->cap / 4, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return TDOA_OK;

@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--sync-drift=H[/D]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -154,6 +154,11 @@ int main(int argc, char **argv)
     bool sync = false;
     double sync_lat = 0, sync_lon = 0, sync_h = 0;
     int sync_g = 128, sync_r = 2;
+    // --sync-drift=H[/D] (with --sync; any --stack=M): the stations' clock offsets and rates, slopes up to H / D lags per stack, are
+    // searched along each reference block's stacks (tdoa_process_sync_drift); blocks 1 and 3 are located under their own lines'
+    // clocks, block 2 under block 1's line continued over its positions (tdoa_sync_line_clock)
+    bool sync_drift = false;
+    int sdrift_h = 0, sdrift_d = 1;
     double gate = 120.0;     // samples; PROJECT_NOTES.md:29-32 (max |TDOA| about 57 us = 114 samples at 2 Msps)
     tdoa_params prm;
     tdoa_default_params(&prm);
@@ -241,6 +246,14 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
+        else if (a.rfind("--sync-drift=", 0) == 0) {
+            sync_drift = true;
+            const int got = std::sscanf(a.c_str() + 13, "%d/%d", &sdrift_h, &sdrift_d);
+            if (got < 1 || sdrift_h < 0 || sdrift_h > 512 || sdrift_d < 1) {
+                std::fprintf(stderr, "--sync-drift=H[/D] with H in 0 .. 512 and D >= 1, e.g. --sync-drift=16/4\n");
+                return 1;
+            }
+        }
         else if (a == "--gate" && i + 1 < argc) gate = std::atof(argv[++i]);
         else if (a == "--device" && i + 1 < argc) prm.device = std::atoi(argv[++i]);
         else if (a == "--window" && i + 1 < argc) prm.window_len = std::atoll(argv[++i]);
@@ -258,7 +271,8 @@ int main(int argc, char **argv)
     if (track_emitters && !locate_track) { std::fprintf(stderr, "--track-emitters needs --stack --locate --locate-track\n"); return 1; }
     if (map_stats && !locate) { std::fprintf(stderr, "--map-stats needs --stack --locate\n"); return 1; }
     if (sync && !locate) { std::fprintf(stderr, "--sync needs --stack --locate\n"); return 1; }
-    if (sync && stack_m != 0) { std::fprintf(stderr, "--sync needs whole-block stacks: --stack without =WINDOWS\n"); return 1; }
+    if (sync_drift && !sync) { std::fprintf(stderr, "--sync-drift needs --stack --locate --sync\n"); return 1; }
+    if (sync && !sync_drift && stack_m != 0) { std::fprintf(stderr, "--sync needs whole-block stacks: --stack without =WINDOWS\n"); return 1; }
     if (pos.size() < 4) {                                     // processor.go:1048-1052
         usage(argv[0]);
         return 1;
@@ -437,6 +451,8 @@ int main(int argc, char **argv)
         std::vector<tdoa_map_stats> lstats, mstats, ltstats, mtstats;      // --map-stats: one record per record of the four above
         std::vector<tdoa_sync> syncs;            // --sync: one record and S clocks per block (tdoa_process_sync)
         std::vector<int32_t> clocks;
+        std::vector<tdoa_sync_line> lines;       // --sync-drift: one record, S clocks and S rates per block (tdoa_process_sync_drift)
+        std::vector<int32_t> rates;
         double grid_lat0 = 0, grid_lon0 = 0, grid_dlat = 0, grid_dlon = 0;
         if (stack) {
             if ((rc = tdoa_num_stacks(ctx, stack_m, &spb, &n_stacks))) return die("tdoa_num_stacks", rc);
@@ -489,15 +505,27 @@ int main(int argc, char **argv)
                     std::vector<int32_t> ref((size_t)S), table16((size_t)n_stacks * S);
                     if ((rc = tdoa_locate_grid_table(lle.data(), S, sync_lat, sync_lon, 0.0, 0.0, 1, 1, sync_h, prm.sample_rate, ref.data())))
                         return die("tdoa_locate_grid_table", rc);
-                    syncs.resize((size_t)n_stacks);
-                    clocks.resize((size_t)n_stacks * S);
-                    if ((rc = tdoa_process_sync(ctx, stack_m, sync_g, sync_r, ref.data(), nullptr, syncs.data(), clocks.data(), nullptr, nullptr)))
-                        return die("tdoa_process_sync", rc);
-                    for (int s = 0; s < S; s++) {
-                        const int32_t before = clocks[s], after = clocks[2 * (size_t)S + s];
-                        table16[s] = TDOA_DELAY_UNIT * before;
-                        table16[(size_t)S + s] = TDOA_DELAY_UNIT / 2 * (before + after);
-                        table16[2 * (size_t)S + s] = TDOA_DELAY_UNIT * after;
+                    if (sync_drift) {
+                        // the lines of the three blocks and their rows; the target block's rows are block 1's line continued
+                        lines.resize(3);
+                        clocks.resize(3 * (size_t)S);
+                        rates.resize(3 * (size_t)S);
+                        if ((rc = tdoa_process_sync_drift(ctx, stack_m, sync_g, sdrift_h, sdrift_d, sync_r, ref.data(), nullptr, lines.data(),
+                                                          clocks.data(), rates.data(), table16.data(), nullptr, nullptr)))
+                            return die("tdoa_process_sync_drift", rc);
+                        if ((rc = tdoa_sync_line_clock(clocks.data(), rates.data(), S, sdrift_d, spb, spb, table16.data() + (size_t)spb * S)))
+                            return die("tdoa_sync_line_clock", rc);
+                    } else {
+                        syncs.resize((size_t)n_stacks);
+                        clocks.resize((size_t)n_stacks * S);
+                        if ((rc = tdoa_process_sync(ctx, stack_m, sync_g, sync_r, ref.data(), nullptr, syncs.data(), clocks.data(), nullptr, nullptr)))
+                            return die("tdoa_process_sync", rc);
+                        for (int s = 0; s < S; s++) {
+                            const int32_t before = clocks[s], after = clocks[2 * (size_t)S + s];
+                            table16[s] = TDOA_DELAY_UNIT * before;
+                            table16[(size_t)S + s] = TDOA_DELAY_UNIT / 2 * (before + after);
+                            table16[2 * (size_t)S + s] = TDOA_DELAY_UNIT * after;
+                        }
                     }
                     if ((rc = tdoa_locate_set_clock(ctx, table16.data(), n_stacks, S))) return die("tdoa_locate_set_clock", rc);
                 }
@@ -620,6 +648,14 @@ int main(int argc, char **argv)
             std::printf("SYNC block %d: clock=", (int)sid + 1);
             for (int s = 0; s < S; s++) std::printf("%s%d", s ? "," : "", (int)clocks[sid * S + s]);
             std::printf(" moved=%d score=%.6f\n", (int)syncs[sid].moved, syncs[sid].score);
+        }
+        // --sync-drift: the lines of the two reference blocks, a line each
+        for (size_t b = 0; b < lines.size(); b += 2) {
+            std::printf("SYNCLINE block %d: clock=", (int)b + 1);
+            for (int s = 0; s < S; s++) std::printf("%s%d", s ? "," : "", (int)clocks[b * S + s]);
+            std::printf(" rate=");
+            for (int s = 0; s < S; s++) std::printf("%s%d", s ? "," : "", (int)rates[b * S + s]);
+            std::printf("/%d moved=%d score=%.6f\n", sdrift_d, (int)lines[b].moved, lines[b].score);
         }
         // --map-stats: the statistics of the plane the line before it judged, the words on the line's own scale
         const auto print_stats = [&](const std::vector<tdoa_map_stats> &all, size_t at) {

@@ -42,6 +42,7 @@
 #include "stack_locate.hpp"
 #include "stack_locate_multi.hpp"
 #include "stack_sync.hpp"
+#include "stack_sync_drift.hpp"
 #include "stack_cell_track.hpp"
 #include "stack_locate_track_multi.hpp"
 #include "stack_map_stats.hpp"
@@ -192,6 +193,12 @@ struct tdoa_ctx {
     // the clock search: ref_delay and centre (kSyncMaxStations words each), the start's tiles' candidates [stack][tile], the
     // records [stack], the clocks [stack][station], the lags and correlations [stack][pair]
     DevBuf sync_in, sync_part, sync_out, sync_clock, sync_lags, sync_corr;
+    // the clock-line search: ref_delay and centre, the shift table [rank(h)][position], sqrt(N_w) [line], the stations' clocks
+    // [line][station][position], their k and h [line][station], the tiles' candidates [line][tile], `moved` and F after placing
+    // [line], the records [line], the clocks and rates [line][station], the rows [stack][station], the lags and correlations
+    // [stack][pair]
+    DevBuf sline_in, sline_tab, sline_roots, sline_cur, sline_k, sline_h, sline_part, sline_moved, sline_start, sline_out, sline_clock,
+        sline_rate, sline_rows, sline_lags, sline_corr;
     // tdoa_debug_closure_from_q, tdoa_debug_locate_from_q and tdoa_debug_sync_from_q: the caller's words and sqrt(n_w) per set
     DevBuf debug_q, debug_roots;
     int locate_cells = 0, locate_cols = 0, locate_stations = 0;
@@ -559,7 +566,10 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->locate_clock, &ctx->sync_in, &ctx->sync_part, &ctx->sync_out, &ctx->sync_clock, &ctx->sync_lags,
                       &ctx->sync_corr, &ctx->debug_q, &ctx->debug_roots, &ctx->ctrack_d, &ctx->ctrack_t, &ctx->ctrack_roots,
                       &ctx->ctrack_out, &ctx->ctrack_cells, &ctx->ctrack_own, &ctx->locate_centres, &ctx->ctrack_pairs,
-                      &ctx->mstat_ranks, &ctx->mstat_hist, &ctx->mstat_state, &ctx->mstat_out};
+                      &ctx->mstat_ranks, &ctx->mstat_hist, &ctx->mstat_state, &ctx->mstat_out,
+                      &ctx->sline_in, &ctx->sline_tab, &ctx->sline_roots, &ctx->sline_cur, &ctx->sline_k, &ctx->sline_h, &ctx->sline_part,
+                      &ctx->sline_moved, &ctx->sline_start, &ctx->sline_out, &ctx->sline_clock, &ctx->sline_rate, &ctx->sline_rows,
+                      &ctx->sline_lags, &ctx->sline_corr};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1372,3 +1382,4 @@ int tdoa_solve_surface(const double *stations_lle, int n_stations, const double 
 #include "debug_api.inc"
 #include "exact_reference_api.inc"
 #include "group_api.inc"
+#include "sync_drift_api.inc"

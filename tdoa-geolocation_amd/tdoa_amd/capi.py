@@ -54,6 +54,8 @@ LOCATION_DTYPE = np.dtype([("cell", np.int32), ("runner_cell", np.int32), ("pair
                            ("score", np.float64), ("runner_up", np.float64)])      # tdoa_location
 SYNC_DTYPE = np.dtype([("moved", np.int32), ("pairs_in", np.int32), ("score_q", np.int64), ("start_q", np.int64),
                        ("score", np.float64)])      # tdoa_sync
+SYNC_LINE_DTYPE = np.dtype([("moved", np.int32), ("terms_in", np.int32), ("positions", np.int32), ("reserved", np.int32),
+                            ("score_q", np.int64), ("start_q", np.int64), ("score", np.float64)])      # tdoa_sync_line
 CELL_TRACK_DTYPE = np.dtype([("cell", np.int32), ("runner_cell", np.int32), ("positions", np.int32), ("steps", np.int32),
                              ("score_q", np.int64), ("runner_q", np.int64),
                              ("score", np.float64), ("runner_up", np.float64)])      # tdoa_cell_track
@@ -121,6 +123,7 @@ SYMBOLS = [
     "tdoa_process_locate_multi", "tdoa_debug_locate_multi_from_q", "tdoa_group_process_locate_multi",
     "tdoa_process_locate_track_multi", "tdoa_debug_locate_track_multi_from_q", "tdoa_group_process_locate_track_multi",
     "tdoa_locate_set_stats", "tdoa_locate_last_stats", "tdoa_group_locate_set_stats", "tdoa_group_locate_last_stats",
+    "tdoa_process_sync_drift", "tdoa_debug_sync_drift_from_q", "tdoa_group_process_sync_drift", "tdoa_sync_line_clock",
 ]
 
 _lib = None
@@ -257,6 +260,10 @@ def load(build_if_missing=True):
     L.tdoa_group_process_locate_track_multi.argtypes = [vp] + [C.c_int] * 5 + [vp, i32p, i64p, i32p, i32p, dp, i64p]
     L.tdoa_debug_locate_track_multi_from_q.argtypes = [vp, i64p] + [C.c_int] * 8 + [vp, i32p, i64p, i32p, i32p, dp, i64p]
     L.tdoa_debug_sync_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, vp, i32p, i32p, dp]
+    L.tdoa_process_sync_drift.argtypes = [vp] + [C.c_int] * 5 + [i32p, i32p, vp, i32p, i32p, i32p, i32p, dp]
+    L.tdoa_group_process_sync_drift.argtypes = [vp] + [C.c_int] * 5 + [i32p, i32p, vp, i32p, i32p, i32p, i32p, dp]
+    L.tdoa_debug_sync_drift_from_q.argtypes = [vp, i64p] + [C.c_int] * 8 + [i32p, i32p, vp, i32p, i32p, i32p, i32p, dp]
+    L.tdoa_sync_line_clock.argtypes = [i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, i32p]
     L.tdoa_locate_set_stats.argtypes = [vp, C.POINTER(C.c_uint16), C.c_int, C.c_int]
     L.tdoa_group_locate_set_stats.argtypes = [vp, C.POINTER(C.c_uint16), C.c_int, C.c_int]
     L.tdoa_locate_last_stats.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
@@ -730,6 +737,35 @@ class Context:
                                                  *_sync_ptrs(out)))
         return out
 
+    def process_sync_drift(self, ref_delay, windows_per_stack=0, gate=0, max_drift=0, drift_den=1, rounds=0, centre=None):
+        """tdoa_process_sync_drift -> {"line": [3] SYNC_LINE_DTYPE, "clock": [3][S] int32 (samples), "rate": [3][S] int32,
+        "rows": [n_stacks][S] int32 (1/16 sample: tdoa_locate_set_clock's unit), "lags": [n_stacks][P] int32, "corr":
+        [n_stacks][P] float64}: per block the station clocks k_s(j) = k_s + shift(h_s, j), |k_s - centre[s]| <= gate, |h_s| <=
+        max_drift in units of 1 / drift_den lag per stack, that make all pairs' signed sums along the block's stacks largest
+        at the lags the known emitter's delays ref_delay [S] predict; the placing and `rounds` sweeps"""
+        _, n = self.num_stacks(windows_per_stack)
+        S = self.num_stations()
+        out = _sync_line_outputs(3, n, S)
+        self._chk(self._L.tdoa_process_sync_drift(self._h, int(windows_per_stack), int(gate), int(max_drift), int(drift_den), int(rounds),
+                                                  _ref_delay(ref_delay, S), _centre(centre, S), *_sync_line_ptrs(out)))
+        return out
+
+    def sync_drift_from_q(self, q, ref_delay, track_len, n_w=1, gate=0, max_drift=0, drift_den=1, rounds=0, centre=None):
+        """tdoa_debug_sync_drift_from_q: the clock-line search's kernels on the caller's words q [n_sets][P][2 max_lag - 1]
+        int64, set t track_len + j position j of line t -> what process_sync_drift returns, n_sets / track_len lines and
+        n_sets stacks"""
+        q = np.ascontiguousarray(q, dtype=np.int64)
+        if q.ndim == 2:
+            q = q[None]
+        S = int(np.size(ref_delay))
+        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
+            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
+        out = _sync_line_outputs(q.shape[0] // max(int(track_len), 1), q.shape[0], S)
+        self._chk(self._L.tdoa_debug_sync_drift_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], int(track_len), S,
+                                                       int(n_w), int(gate), int(max_drift), int(drift_den), int(rounds),
+                                                       _ref_delay(ref_delay, S), _centre(centre, S), *_sync_line_ptrs(out)))
+        return out
+
     def process_locate_track(self, windows_per_stack=0, max_step=0, min_separation=1, want_total=False):
         """tdoa_process_locate_track -> {"track": [n_tracks] CELL_TRACK_DTYPE, "cells": [n_tracks][L] int32, "own":
         [n_tracks][L] int64, "lags": [n_stacks][P] int32, "corr": [n_stacks][P] float64, and with want_total "total":
@@ -972,6 +1008,20 @@ def _sync_ptrs(out):
     i32p = C.POINTER(C.c_int32)
     return (out["sync"].ctypes.data_as(C.c_void_p), out["clock"].ctypes.data_as(i32p), out["lags"].ctypes.data_as(i32p),
             _d(out["corr"]))
+
+
+def _sync_line_outputs(n_lines, n_sets, n_stations):
+    p = n_stations * (n_stations - 1) // 2
+    n_lines = max(int(n_lines), 1)           # (the library refuses a call without a whole line)
+    return {"line": np.zeros(n_lines, dtype=SYNC_LINE_DTYPE), "clock": np.zeros((n_lines, n_stations), dtype=np.int32),
+            "rate": np.zeros((n_lines, n_stations), dtype=np.int32), "rows": np.zeros((n_sets, n_stations), dtype=np.int32),
+            "lags": np.zeros((n_sets, p), dtype=np.int32), "corr": np.zeros((n_sets, p), dtype=np.float64)}
+
+
+def _sync_line_ptrs(out):
+    i32p = C.POINTER(C.c_int32)
+    return (out["line"].ctypes.data_as(C.c_void_p), out["clock"].ctypes.data_as(i32p), out["rate"].ctypes.data_as(i32p),
+            out["rows"].ctypes.data_as(i32p), out["lags"].ctypes.data_as(i32p), _d(out["corr"]))
 
 
 def _locate_outputs(n_sets, p, n_cells, want_map):
@@ -1232,6 +1282,32 @@ class Group:
         self._chk(self._L.tdoa_group_process_sync(self._h, int(windows_per_stack), int(gate), int(rounds), _ref_delay(ref_delay, S),
                                                   _centre(centre, S), *_sync_ptrs(out)))
         return out
+
+    def process_sync_drift(self, ref_delay, windows_per_stack=0, gate=0, max_drift=0, drift_den=1, rounds=0, centre=None):
+        """tdoa_group_process_sync_drift -> Context.process_sync_drift's outputs, byte-identical to a single context's"""
+        m = self.member(0)
+        _, n = m.num_stacks(windows_per_stack)
+        S = m.num_stations()
+        out = _sync_line_outputs(3, n, S)
+        self._chk(self._L.tdoa_group_process_sync_drift(self._h, int(windows_per_stack), int(gate), int(max_drift), int(drift_den),
+                                                        int(rounds), _ref_delay(ref_delay, S), _centre(centre, S), *_sync_line_ptrs(out)))
+        return out
+
+
+def sync_line_clock(clock, rate, drift_den, first_position, n_positions):
+    """tdoa_sync_line_clock (host only): a line's clocks [S] (samples) and rates [S] continued over positions first_position
+    .. first_position + n_positions - 1 -> [n_positions][S] int32 in units of 1/16 sample, what locate_set_clock takes"""
+    k = np.ascontiguousarray(clock, dtype=np.int32).reshape(-1)
+    h = np.ascontiguousarray(rate, dtype=np.int32).reshape(-1)
+    if k.shape != h.shape:
+        raise ValueError("clock and rate must hold one integer per station")
+    out = np.zeros((max(int(n_positions), 1), k.shape[0]), dtype=np.int32)
+    i32p = C.POINTER(C.c_int32)
+    rc = load().tdoa_sync_line_clock(k.ctypes.data_as(i32p), h.ctypes.data_as(i32p), k.shape[0], int(drift_den), int(first_position),
+                                     int(n_positions), out.ctypes.data_as(i32p))
+    if rc != 0:
+        raise TdoaError(rc, "tdoa_sync_line_clock")
+    return out
 
 
 def locate_grid_table(stations_lle, lat0, lon0, dlat, dlon, rows, cols, height_m, sample_rate):
