@@ -400,6 +400,29 @@ func (g *gpuCorrelator) LocateLastStats() ([]C.tdoa_map_stats, error) {
 	return out[:int(n)], nil
 }
 
+// LocateSetUpsample sets the lag grid of the delay-table family (the header's "sub-sample locate"): while u in {2, 4, 8, 16} is
+// set, ProcessLocate, ProcessLocateMulti, ProcessLocateTrack and ProcessLocateTrackMulti score their cells on the surfaces
+// upsampled to 1/u sample, and the lags they return are in units of 1/u sample: a range difference is
+// lag / (u * sampleRate) * c.  1: off, the default.
+func (g *gpuCorrelator) LocateSetUpsample(u int) error {
+	if rc := C.tdoa_locate_set_upsample(g.ctx, C.int(u)); rc != C.TDOA_OK {
+		return fmt.Errorf("tdoa_locate_set_upsample: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return nil
+}
+
+// LocateUpsampleTaps returns the u phases' 16 taps at scale 2^15 (host only): the committed table the upsampler uses.
+func LocateUpsampleTaps(u int) ([]int32, error) {
+	if u < 1 || u > 16 {
+		return nil, fmt.Errorf("tdoa_locate_upsample_taps: u must be one of 1, 2, 4, 8, 16")
+	}
+	taps := make([]int32, u*16)
+	if rc := C.tdoa_locate_upsample_taps(C.int(u), (*C.int32_t)(unsafe.Pointer(&taps[0]))); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_locate_upsample_taps: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	return taps, nil
+}
+
 // ProcessSync is the clock search (the header's "clock search"): per stack the stations' clocks k_s = centre[s] + x_s,
 // |x_s| <= gate, station 0 the gauge, that make all pairs' stacks largest at the lags the known emitter's delays refDelay
 // (one per station, units of 1/16 sample) predict -- a joint start, the placing and `rounds` sweeps.  clock is
@@ -719,6 +742,15 @@ func (g *Group) LocateLastStats() ([]C.tdoa_map_stats, error) {
 		return nil, fmt.Errorf("tdoa_group_locate_last_stats: %s", C.GoString(C.tdoa_group_last_error(g.g)))
 	}
 	return out[:int(n)], nil
+}
+
+// LocateSetUpsample sets every member's lag grid (gpuCorrelator.LocateSetUpsample); a group of several upsamples the merged
+// sum on member 0.
+func (g *Group) LocateSetUpsample(u int) error {
+	if rc := C.tdoa_group_locate_set_upsample(g.g, C.int(u)); rc != C.TDOA_OK {
+		return fmt.Errorf("tdoa_group_locate_set_upsample: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return nil
 }
 
 // ProcessSync is gpuCorrelator.ProcessSync over the group: the members' fixed-point partial sums are added on the host and

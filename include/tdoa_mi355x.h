@@ -473,7 +473,10 @@ typedef struct {
 int tdoa_locate_set_table(tdoa_ctx *ctx, const int32_t *delay /* [n_cells][n_stations] */, int n_cells, int n_cols, int n_stations);
 
 /* lags_host and corr_host are what a caller hands to tdoa_solve_surface (range difference lag / sample_rate * c, weight
- * |C|) for a fix finer than the grid.  Runs inside the step graph, behind the stack's accumulation: the scores, the
+ * |C|).  They are the best cell's own table differences, rounded to the lag grid: they hold no measurement below one lag, so
+ * the solver's fix is the cell's position again, and a table finer than one lag of range difference only produces plateaus
+ * of equal scores (the smaller cell wins).  A fix finer than one lag needs the finer lag grid of tdoa_locate_set_upsample
+ * ("sub-sample locate", below).  Runs inside the step graph, behind the stack's accumulation: the scores, the
  * runner-up's pass over the map and two launches of the finishing kernel.  (windows_per_stack, min_separation, n_cells,
  * n_cols) are part of the graph's key.  tdoa_group_process_locate is the group form (the search is a function of the
  * complete stacked Q only, so the members' partial sums merge).
@@ -866,6 +869,45 @@ int tdoa_locate_set_stats(tdoa_ctx *ctx, const uint16_t *ranks /* [n_ranks] */, 
  * less than the count. */
 int tdoa_locate_last_stats(tdoa_ctx *ctx, tdoa_map_stats *out, int max_planes, int *n_planes);
 
+/* Sub-sample locate: band-limited upsampling of the stacked surfaces.  The delay table and the clock rows carry 1/16 sample,
+ * the surfaces Q exist at whole lags only: lag_p(c) rounds d / 16 to a whole lag, so no cell is told from its neighbour below
+ * one lag (150 m of range difference at 2 Msps).  With the setting U in {2, 4, 8, 16}, the four calls of the delay-table
+ * family, their tdoa_debug_*_from_q and tdoa_group_* forms score the cells on Q upsampled to 1/U sample.  U = 1 is the default
+ * and off: every call returns its bytes and captures its graph as before.
+ *   The upsampled row: for a row Q[l], -max_lag < l < max_lag, of n = 2 max_lag - 1 lags, n_U = (n - 1) U + 1 words; index u
+ *     stands for lag u / U - (max_lag - 1).
+ *       Q_U[U l + r] = floor((sum over k = 0 .. 15 of h_r[k] Q[l + k - 7] + 2^14) / 2^15),  r = 0 .. U - 1, Q outside the range = 0
+ *     h_r = h16[r 16 / U] of a committed table h16[16][16] of int32 at scale 2^15,
+ *       h16[rho][k] = rint(2^15 sinc(x) kaiser_6(x / 8)),  x = k - 7 - rho / 16    (a 16-tap Kaiser-windowed sinc, beta = 6).
+ *     The table is normative: the same 256 literals in csrc/stack_upsample.hpp and tdoa_amd/upsample.py
+ *     (tdoa_locate_upsample_taps returns them); nothing computes a tap at run time.  Phase 0 is the delta: Q_U[U l] = Q[l].
+ *     The sum is exact integer arithmetic, rounded half up by the floor; defined for |Q| <= 2^60.
+ *   The search: the family's calls as documented, on Q_U, U * table, U * clock, U * guard, with n_U lags from -(max_lag - 1) U.
+ *     The lag rule on d' = U d is sgn(d) * ((2|d| U + 16) div 32): the nearest 1/U lag, halves away from zero.
+ *     min_separation, max_step and the map statistics are in cells and do not change.
+ *   The outputs keep their layouts.  lags are in units of 1/U sample: a range difference is lag / (U * sample_rate) * c.
+ *     corr is the signed C of Q_U there.  The excluded intervals of the _multi calls are guard * U fine lags around the fine
+ *     centres.  A pair counts in pairs_in when its fine lag is inside the fine range.
+ *   Overflow: |Q_U| <= 2.04 |Q| + 1.  With U > 1 the calls return TDOA_ERR_UNSUPPORTED when 4 * P * (stack length in use)
+ *     > 2^17 (the tracks' bound on the windows of a track is tightened by the same factor 4), and when a table or clock entry
+ *     has |t| * U >= 2^31.  TDOA_ERR_NOMEM when the upsampled surfaces [n_stacks_total][n_pairs][n_U] do not fit;
+ *     tdoa_last_error says so.  Surfaces larger than the device's whole memory are refused by arithmetic, before anything is
+ *     allocated; a size between the free and the whole memory is refused when its allocation fails, with the same message.
+ *   The group's searches run on the merged sum: upsampling comes after the merge (the rounding is not linear).
+ * U is one more word of a step graph's key; table, clocks and taps are data.  U * table and U * clock differences are kept
+ * on the device beside the originals and remade when the table, the clocks or U change (here, in tdoa_locate_set_table and
+ * in tdoa_locate_set_clock), so this call needs the device when U > 1 and a table or clocks are set.
+ * TDOA_ERR_INVALID: a NULL context, U not one of 1, 2, 4, 8, 16. */
+int tdoa_locate_set_upsample(tdoa_ctx *ctx, int U);
+
+/* Host only, no device: the U phases' taps, taps[r][k] = h16[r 16 / U][k].  TDOA_ERR_INVALID: NULL taps, a bad U. */
+int tdoa_locate_upsample_taps(int U, int32_t *taps /* [U][16] */);
+
+/* tests only: the upsampler on the caller's rows q [n_rows][2*max_lag-1] -> out [n_rows][(2*max_lag-2)*U+1].  Needs a context
+ * for max_lag and the device, and no captures; the context's own setting is not read.  Precondition: |q| <= 2^60.
+ * TDOA_ERR_INVALID: a NULL context, q or out NULL, n_rows < 1, a bad U. */
+int tdoa_debug_upsample_q(tdoa_ctx *ctx, const int64_t *q, int n_rows, int U, int64_t *out);
+
 /* Capture-quality statistics of every (window, station) in one streaming pass over the bytes
  * in HBM: the byte statistics of fastAnalyzeSamples
  * (fast_analyzer.go:117-155) and the block power of validateDataFile (collector.go:219-224).
@@ -1128,6 +1170,10 @@ int tdoa_group_process_locate_track_multi(tdoa_group *g, int windows_per_stack, 
  * single context returns.  Errors as there. */
 int tdoa_group_locate_set_stats(tdoa_group *g, const uint16_t *ranks, int n_ranks, int foot);
 int tdoa_group_locate_last_stats(tdoa_group *g, tdoa_map_stats *out, int max_planes, int *n_planes);
+
+/* tdoa_locate_set_upsample on every member.  A group of several upsamples the merged sum on member 0; the outputs are the
+ * bytes a single context returns.  Errors as there. */
+int tdoa_group_locate_set_upsample(tdoa_group *g, int U);
 
 /* the sample runs member `rank` of `world` uploads for a capture of total_samples (window grid from n_min, the shortest
  * capture of the job; block offsets from the capture's own thirds): adjacent owned windows form one run, and with fewer

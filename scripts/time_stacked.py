@@ -29,9 +29,12 @@ kinds of leg, the same leg with the map statistics on (tdoa_locate_set_stats wit
 tdoa_process_sync_drift(M, G, H, D, R) (D defaults to 1, R to 2; M from `--stack`) against the same delays, with the records,
 clocks, rates, rows, lags and correlations downloaded (the stack's accumulation, then two launches per station's step: (2G+1)
 (2H+1) candidates in tiles of 256, and the commit; H = 0 is the search's fixed cost).  `--stations S` runs all
-legs on S stations (default 3; 8 gives 56 triples).
+legs on S stations (default 3; 8 gives 56 triples).  Every `--locate-upsample U` adds a leg per `--locate` grid:
+tdoa_process_locate(M, 1) with tdoa_locate_set_upsample(U) (name ..._upU_ms): the two scalings and the upsampler come in front
+of the search's launches, which then gather from surfaces U times as long; every other leg runs with U = 1.  `--max-lag N`
+(default 20000) sets the context's search range: one-window stacks (`--stack 1`) at U = 16 want 512.
 usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--stack M] [--drift H/D]... [--track J]...
-[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]..."""
+[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]... [--locate-upsample U]... [--max-lag N]"""
 import json
 import os
 import sys
@@ -61,8 +64,8 @@ def timed(fn, steps):
 
 
 def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=(), locate_tracks=(), stack=0, emitters=(),
-         track_emitters=(), map_stats=None, sync_drifts=()):
-    c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=20000)
+         track_emitters=(), map_stats=None, sync_drifts=(), upsamples=(), max_lag=20000):
+    c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=max_lag)
     for s in range(stations):
         c.synth_capture(s, 66_666_666, ST[s % 3], TX, 0x5D0A0000 + s)
     _, W = c.num_windows()
@@ -78,19 +81,25 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
         legs["process_closure_%d_ms" % G] = lambda G=G: c.process_closure(0, G, 1)
     setup = {}
 
-    def family(name, table, cols, fn):
+    def family(name, table, cols, fn, U=1):
         """a leg of the delay-table family with the statistics off and, with --map-stats, the same leg with them on"""
-        setup[name] = lambda: (c.locate_set_table(table, cols), c.locate_set_stats(None)) if map_stats else c.locate_set_table(table, cols)
+        def base():
+            c.locate_set_table(table, cols)
+            if upsamples:
+                c.locate_set_upsample(U)
+        setup[name] = lambda: (base(), c.locate_set_stats(None)) if map_stats else base()
         legs[name] = fn
         if map_stats:
             on = name[:-3] + "_stats_ms"
-            setup[on] = lambda: (c.locate_set_table(table, cols), c.locate_set_stats(*map_stats))
+            setup[on] = lambda: (base(), c.locate_set_stats(*map_stats))
             legs[on] = fn
 
     for rows, cols in locates:
         table = tdoa_amd.capi.locate_grid_table([ST[s % 3] for s in range(stations)], 41.10, -96.20, 0.3 / max(rows - 1, 1),
                                                 0.4 / max(cols - 1, 1), rows, cols, 350.0, 2e6)
         family("process_locate_%dx%d_ms" % (rows, cols), table, cols, lambda: c.process_locate(stack, 1))
+        for U in upsamples:
+            family("process_locate_%dx%d_up%d_ms" % (rows, cols, U), table, cols, lambda: c.process_locate(stack, 1), U)
         for J in locate_tracks:
             family("process_locate_track_%dx%d_J%d_ms" % (rows, cols, J), table, cols, lambda J=J: c.process_locate_track(stack, J, 1))
             for K, guard in track_emitters:
@@ -111,7 +120,9 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
                 setup[name]()
             times[name].append(timed(fn, steps))
     out = {"config": "cfg2" if stations == 3 else "cfg2 windows, %d stations" % stations, "stations": stations, "pairs": P, "windows": W, "stacks": n_stacks, "locate_stacks": c.num_stacks(stack)[1], "steps": steps, "rounds": rounds,
-           "surface_MB": round(W * P * (2 * 20000 - 1) * 4 / 1e6, 1)}
+           "surface_MB": round(W * P * (2 * max_lag - 1) * 4 / 1e6, 1)}
+    if max_lag != 20000:
+        out["max_lag"] = max_lag
     if map_stats:
         out["map_stats"] = {"ranks": list(map_stats[0]), "foot": map_stats[1]}
     for name, t in times.items():
@@ -122,7 +133,7 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
 
 if __name__ == "__main__":
     args = sys.argv[1:]
-    opt = {"--steps": 20, "--rounds": 5, "--stations": 3, "--stack": 0}
+    opt = {"--steps": 20, "--rounds": 5, "--stations": 3, "--stack": 0, "--max-lag": 20000}
     for name in opt:
         if name in args:
             i = args.index(name)
@@ -167,6 +178,11 @@ if __name__ == "__main__":
         r, _, f = args[i + 1].partition("/")
         map_stats = (tuple(int(x) for x in r.split(",")), int(f or 0))
         del args[i:i + 2]
+    upsamples = []
+    while "--locate-upsample" in args:
+        i = args.index("--locate-upsample")
+        upsamples.append(int(args[i + 1]))
+        del args[i:i + 2]
     locates = []
     while "--locate" in args:
         i = args.index("--locate")
@@ -186,4 +202,4 @@ if __name__ == "__main__":
         syncs.append((int(g), int(r or 2)))
         del args[i:i + 2]
     main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs, locate_tracks, opt["--stack"], emitters,
-         track_emitters, map_stats, sync_drifts)
+         track_emitters, map_stats, sync_drifts, upsamples, opt["--max-lag"])

@@ -130,11 +130,12 @@ int tdoa_debug_poison_workspace(tdoa_ctx *ctx)
     // candidates, cells and records are compared and copied, never added to an address; the delay-table search's map,
     // candidates and records likewise -- a cell taken from a candidate is checked against the table's size -- and its table,
     // which is state, is left alone; the clock-line search's clocks only enter lags that are checked against the range, and a
-    // candidate's number taken from its tiles is clamped to the candidates there are)
+    // candidate's number taken from its tiles is clamped to the candidates there are; the upsampled surfaces are integers like
+    // stack_q, every word written by the upsampler before a search reads it)
     for (DevBuf *b : {&ctx->v, &ctx->tz, &ctx->fine_raw, &ctx->once_edges, &ctx->surf, &ctx->surf_out, &ctx->stack_q, &ctx->stack_surf,
                       &ctx->track_t, &ctx->closure_part, &ctx->closure_best, &ctx->closure_out, &ctx->locate_map, &ctx->locate_part,
                       &ctx->locate_best, &ctx->locate_out, &ctx->locate_lags, &ctx->locate_corr, &ctx->sline_cur, &ctx->sline_part,
-                      &ctx->sline_out, &ctx->sline_rows, &ctx->sline_lags, &ctx->sline_corr})
+                      &ctx->sline_out, &ctx->sline_rows, &ctx->sline_lags, &ctx->sline_corr, &ctx->locate_qu})
         if (b->p && b->cap >= 4) HIPCHK(ctx, hipMemsetD32Async(static_cast<hipDeviceptr_t>(b->p), 0x7FC00000, b->cap / 4, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return TDOA_OK;
@@ -280,13 +281,18 @@ static int debug_locate_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int 
     if (const char *bad = check_locate_table(ctx, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
     if (const char *bad = check_locate_clock(ctx, n_sets, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
     const LocateRun run = locate_run(ctx, call, n_sets, track_len);
-    if (!call.tracks && locate_overflows(run.g.P, n_w)) return fail(ctx, TDOA_ERR_UNSUPPORTED, "pairs x n_w > 2^17: a cell's score could overflow");
-    if (call.tracks && locate_overflows(run.g.P, (long long)track_len * n_w))
-        return fail(ctx, TDOA_ERR_UNSUPPORTED, "pairs x track_len x n_w > 2^17: a track's sum could overflow");
+    if (!call.tracks && locate_overflows(run.g.P, n_w, run.U))
+        return fail(ctx, TDOA_ERR_UNSUPPORTED, run.U > 1 ? "4 x pairs x n_w > 2^17 on upsampled surfaces: a cell's score could overflow"
+                                                         : "pairs x n_w > 2^17: a cell's score could overflow");
+    if (call.tracks && locate_overflows(run.g.P, (long long)track_len * n_w, run.U))
+        return fail(ctx, TDOA_ERR_UNSUPPORTED, run.U > 1 ? "4 x pairs x track_len x n_w > 2^17 on upsampled surfaces: a track's sum could overflow"
+                                                         : "pairs x track_len x n_w > 2^17: a track's sum could overflow");
+    int status = TDOA_OK;
+    if (const char *bad = check_locate_upsample(ctx, (size_t)n_sets, run.g.P, &status)) return fail(ctx, status, bad);
     if (call.tracks && track_len > kCellTrackMaxLen) return fail(ctx, TDOA_ERR_UNSUPPORTED, "a track of more than 4096 stacks");
     std::vector<double> roots;
     const std::vector<double> track_roots(run.n_tracks(), std::sqrt((double)track_len * (double)n_w));
-    if ((rc = upload_debug_q(ctx, q, (size_t)n_sets * run.g.P * run.g.n, n_sets, n_w, &roots))) return rc;
+    if ((rc = upload_debug_q(ctx, q, (size_t)n_sets * run.g.P * run.n_in, n_sets, n_w, &roots))) return rc;
     if ((rc = ensure_locate_run(ctx, run))) return rc;
     if (call.tracks && (rc = upload_locate_track_roots(ctx, track_roots))) return rc;
     launch_locate_run(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), run);
@@ -319,6 +325,30 @@ int tdoa_debug_locate_track_multi_from_q(tdoa_ctx *ctx, const int64_t *q, int n_
 {
     return debug_locate_from_q(ctx, q, n_sets, track_len, n_stations, n_w,
                                locate_track_call(true, max_step, n_emitters, guard, min_separation, track, cells, own, pairs, lags, corr, total));
+}
+
+// The upsampler (stack_upsample.hpp) on the caller's words: n_rows rows of 2 max_lag - 1 int64 -> n_rows rows of
+// (2 max_lag - 2) U + 1.  Needs the context for max_lag and the device only; the setting of the context is not read.
+int tdoa_debug_upsample_q(tdoa_ctx *ctx, const int64_t *q, int n_rows, int U, int64_t *out)
+{
+    int rc;
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (!q || !out || n_rows < 1 || !upsample_factor_ok(U)) return fail(ctx, TDOA_ERR_INVALID, "q or out is NULL, n_rows < 1 or U is not one of 1, 2, 4, 8, 16");
+    const long long n = 2ll * ctx->prm.max_lag - 1, n_u = upsample_len(n, U), tiles = (n + kUpsampleThreads - 1) / kUpsampleThreads;
+    if (n_u > INT_MAX || (double)n_rows * (double)tiles > (double)INT_MAX) return fail(ctx, TDOA_ERR_UNSUPPORTED, "the upsampled rows do not fit the grid");
+    if (U == 1) {
+        std::memcpy(out, q, sizeof(int64_t) * (size_t)n_rows * (size_t)n);
+        return TDOA_OK;
+    }
+    if ((rc = check_ctx(ctx))) return rc;
+    if ((rc = ensure(ctx, ctx->debug_q, sizeof(long long) * (size_t)n_rows * (size_t)n))) return rc;
+    if ((rc = ensure(ctx, ctx->locate_qu, sizeof(long long) * (size_t)n_rows * (size_t)n_u))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->debug_q.p, q, sizeof(long long) * (size_t)n_rows * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    launch_stack_upsample(ctx->stream, ctx->debug_q.as<const long long>(), (size_t)n_rows, (int)n, U, ctx->locate_qu.as<long long>());
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->locate_qu.p, sizeof(long long) * (size_t)n_rows * (size_t)n_u, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return TDOA_OK;
 }
 
 // the clock search's kernels (sync_api.inc) on the caller's words: n_sets sets of P = S (S-1) / 2 rows of 2 max_lag - 1 int64,

@@ -412,6 +412,16 @@ int tdoa_group_locate_set_stats(tdoa_group *g, const uint16_t *ranks, int n_rank
     return TDOA_OK;
 }
 
+// the factor to every member: member 0's is the one a group of several searches with, on the merged sum (the upsampler's
+// rounding is not linear: upsampling comes after the merge)
+int tdoa_group_locate_set_upsample(tdoa_group *g, int U)
+{
+    if (!g) return TDOA_ERR_INVALID;
+    for (size_t m = 0; m < g->members.size(); m++)
+        if (const int rc = tdoa_locate_set_upsample(g->members[m], U)) return member_fail(g, (int)m, rc);
+    return TDOA_OK;
+}
+
 // the statistics of the group's last call of the family: member 0 ran its search, on its own captures or on the merged sum
 int tdoa_group_locate_last_stats(tdoa_group *g, tdoa_map_stats *out, int max_planes, int *n_planes)
 {

@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--sync-drift=H[/D]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--locate-upsample=U] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--sync-drift=H[/D]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -151,6 +151,9 @@ int main(int argc, char **argv)
     bool map_stats = false;
     std::vector<uint16_t> stats_ranks;
     int stats_foot = 0;
+    // --locate-upsample=U (with --stack --locate), U in 2, 4, 8, 16: the searches score their cells on the surfaces upsampled to
+    // 1/U sample (tdoa_locate_set_upsample); a grid finer than one lag of range difference needs it
+    int locate_up = 1;
     bool sync = false;
     double sync_lat = 0, sync_lon = 0, sync_h = 0;
     int sync_g = 128, sync_r = 2;
@@ -230,6 +233,13 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
+        else if (a.rfind("--locate-upsample=", 0) == 0) {
+            locate_up = std::atoi(a.c_str() + 18);
+            if (locate_up != 1 && locate_up != 2 && locate_up != 4 && locate_up != 8 && locate_up != 16) {
+                std::fprintf(stderr, "--locate-upsample=U with U one of 1, 2, 4, 8, 16, e.g. --locate-upsample=4\n");
+                return 1;
+            }
+        }
         else if (a.rfind("--track-emitters=", 0) == 0) {
             track_emitters = true;
             const int got = std::sscanf(a.c_str() + 17, "%d/%d", &temitters_k, &temitters_guard);
@@ -270,6 +280,7 @@ int main(int argc, char **argv)
     if (emitters && !locate) { std::fprintf(stderr, "--emitters needs --stack --locate\n"); return 1; }
     if (track_emitters && !locate_track) { std::fprintf(stderr, "--track-emitters needs --stack --locate --locate-track\n"); return 1; }
     if (map_stats && !locate) { std::fprintf(stderr, "--map-stats needs --stack --locate\n"); return 1; }
+    if (locate_up != 1 && !locate) { std::fprintf(stderr, "--locate-upsample needs --stack --locate\n"); return 1; }
     if (sync && !locate) { std::fprintf(stderr, "--sync needs --stack --locate\n"); return 1; }
     if (sync_drift && !sync) { std::fprintf(stderr, "--sync-drift needs --stack --locate --sync\n"); return 1; }
     if (sync && !sync_drift && stack_m != 0) { std::fprintf(stderr, "--sync needs whole-block stacks: --stack without =WINDOWS\n"); return 1; }
@@ -529,6 +540,7 @@ int main(int argc, char **argv)
                     }
                     if ((rc = tdoa_locate_set_clock(ctx, table16.data(), n_stacks, S))) return die("tdoa_locate_set_clock", rc);
                 }
+                if ((rc = tdoa_locate_set_upsample(ctx, locate_up))) return die("tdoa_locate_set_upsample", rc);
                 if (map_stats && (rc = tdoa_locate_set_stats(ctx, stats_ranks.data(), (int)stats_ranks.size(), stats_foot)))
                     return die("tdoa_locate_set_stats", rc);
                 const auto last_stats = [&](std::vector<tdoa_map_stats> *out, size_t n) {

@@ -18,8 +18,35 @@ static LocateGeom locate_geom(const tdoa_ctx *ctx, int min_separation)
     return g;
 }
 
-// every sum of P magnitudes of at most n_w 2^45 stays below 2^62
-static bool locate_overflows(int P, long long n_w) { return (long long)P * n_w > (1ll << 17); }
+// every sum of P magnitudes of at most n_w 2^45 stays below 2^62; on upsampled surfaces (U > 1) a magnitude is at most
+// 2.04 n_w 2^45 + 1, and the bound is tightened by the factor 4
+static bool locate_overflows(int P, long long n_w, int U = 1) { return (U > 1 ? 4ll : 1ll) * P * n_w > (1ll << 17); }
+
+// U x the table and U x the clock differences beside the originals, for the searches on upsampled surfaces (stack_upsample.hpp):
+// remade whenever the table, the clocks or U change, so that they are data of a replayed graph like the originals.  Nothing to
+// do with U = 1.  (An entry with |t| U >= 2^31 wraps here; the calls refuse such a table: check_locate_upsample.)
+static int remake_locate_scaled(tdoa_ctx *ctx)
+{
+    const int U = ctx->locate_up;
+    if (U == 1 || (ctx->locate_cells == 0 && ctx->clock_stacks == 0)) return TDOA_OK;
+    int rc;
+    if ((rc = check_ctx(ctx))) return rc;
+    if (ctx->locate_cells) {
+        const size_t n = (size_t)ctx->locate_stations * ctx->locate_cells;
+        if ((rc = ensure(ctx, ctx->locate_table_up, sizeof(int32_t) * n))) return rc;
+        hipLaunchKernelGGL(k_locate_scale_i32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->locate_table.as<const int32_t>(), U, n,
+                           ctx->locate_table_up.as<int32_t>());
+    }
+    if (ctx->clock_stacks) {
+        const size_t n = (size_t)ctx->clock_stacks * (ctx->clock_stations * (ctx->clock_stations - 1) / 2);
+        if ((rc = ensure(ctx, ctx->locate_clock_up, sizeof(long long) * n))) return rc;
+        hipLaunchKernelGGL(k_locate_scale_i64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->locate_clock.as<const long long>(), U, n,
+                           ctx->locate_clock_up.as<long long>());
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return TDOA_OK;
+}
 
 int tdoa_locate_set_table(tdoa_ctx *ctx, const int32_t *delay, int n_cells, int n_cols, int n_stations)
 {
@@ -33,8 +60,13 @@ int tdoa_locate_set_table(tdoa_ctx *ctx, const int32_t *delay, int n_cells, int 
     int rc;
     if ((rc = check_ctx(ctx))) return rc;
     std::vector<int32_t> t((size_t)n_cells * n_stations);      // station-major: a wave's cells read consecutive words
+    long long t_max = 0;
     for (int c = 0; c < n_cells; c++)
-        for (int s = 0; s < n_stations; s++) t[(size_t)s * n_cells + c] = delay[(size_t)c * n_stations + s];
+        for (int s = 0; s < n_stations; s++) {
+            const int32_t d = delay[(size_t)c * n_stations + s];
+            t[(size_t)s * n_cells + c] = d;
+            t_max = std::max(t_max, std::llabs((long long)d));
+        }
     if ((rc = ensure(ctx, ctx->locate_table, sizeof(int32_t) * t.size()))) {
         ctx->locate_cells = ctx->locate_cols = ctx->locate_stations = 0;
         return rc;
@@ -42,9 +74,10 @@ int tdoa_locate_set_table(tdoa_ctx *ctx, const int32_t *delay, int n_cells, int 
     ctx->locate_cells = n_cells;
     ctx->locate_cols = n_cols;
     ctx->locate_stations = n_stations;
+    ctx->locate_table_max = t_max;
     HIPCHK(ctx, hipMemcpyAsync(ctx->locate_table.p, t.data(), sizeof(int32_t) * t.size(), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // t goes out of scope
-    return TDOA_OK;
+    return remake_locate_scaled(ctx);
 }
 
 int tdoa_locate_set_clock(tdoa_ctx *ctx, const int32_t *clock, int n_stacks, int n_stations)
@@ -60,6 +93,8 @@ int tdoa_locate_set_clock(tdoa_ctx *ctx, const int32_t *clock, int n_stacks, int
     if ((rc = check_ctx(ctx))) return rc;
     const int S = n_stations, P = S * (S - 1) / 2;
     std::vector<long long> cd((size_t)n_stacks * P);           // per (stack, pair) clock[j] - clock[i]: what the kernels add to d
+    long long k_max = 0;
+    for (size_t i = 0; i < (size_t)n_stacks * S; i++) k_max = std::max(k_max, std::llabs((long long)clock[i]));
     for (int sid = 0; sid < n_stacks; sid++) {
         const int32_t *k = clock + (size_t)sid * S;
         long long *row = cd.data() + (size_t)sid * P;
@@ -72,8 +107,33 @@ int tdoa_locate_set_clock(tdoa_ctx *ctx, const int32_t *clock, int n_stacks, int
     }
     ctx->clock_stacks = n_stacks;
     ctx->clock_stations = n_stations;
+    ctx->locate_clock_max = k_max;
     HIPCHK(ctx, hipMemcpyAsync(ctx->locate_clock.p, cd.data(), sizeof(long long) * cd.size(), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // cd goes out of scope
+    return remake_locate_scaled(ctx);
+}
+
+// the lag grid of the family's surfaces: 1 / U sample (stack_upsample.hpp); a setting: with U > 1 and a table or clocks set,
+// their scaled copies are made here
+int tdoa_locate_set_upsample(tdoa_ctx *ctx, int U)
+{
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (!upsample_factor_ok(U)) return fail(ctx, TDOA_ERR_INVALID, "U is not one of 1, 2, 4, 8, 16");
+    if (U == ctx->locate_up) return TDOA_OK;
+    const int before = ctx->locate_up;
+    ctx->locate_up = U;
+    if (const int rc = remake_locate_scaled(ctx)) {
+        ctx->locate_up = before;
+        return rc;
+    }
+    return TDOA_OK;
+}
+
+// Host only: the U phases' taps, taps[r][k] = h16[r 16 / U][k]
+int tdoa_locate_upsample_taps(int U, int32_t *taps)
+{
+    if (!taps || !upsample_factor_ok(U)) return TDOA_ERR_INVALID;
+    for (int r = 0; r < U; r++) std::memcpy(taps + (size_t)r * kUpsampleTapCount, kUpsampleTaps[r * (kUpsamplePhases / U)], sizeof(kUpsampleTaps[0]));
     return TDOA_OK;
 }
 

@@ -55,9 +55,11 @@ LocateCall locate_track_call(bool rounds, int max_step, int n_emitters, int guar
     return c;
 }
 
-// a call on n_sets stacks
+// a call on n_sets stacks.  With the setting U > 1 (tdoa_locate_set_upsample) the kernels run on the upsampled surfaces: g
+// describes those -- n = (n_in - 1) U + 1 fine lags from lag_lo U -- and guard counts fine lags
 struct LocateRun {
     LocateGeom g;
+    int U, n_in;                             // the factor; the lags of a row of the Q the call is given
     int n_sets;
     int L;                                   // the stacks of a track, 0: no recurrence (the search alone)
     int J, K, guard;
@@ -69,7 +71,37 @@ struct LocateRun {
 
 LocateRun locate_run(const tdoa_ctx *ctx, const LocateCall &c, int n_sets, int L)
 {
-    return LocateRun{locate_geom(ctx, c.sep), n_sets, c.tracks ? L : 0, c.J, c.K, c.guard, c.tracks && c.rounds};
+    LocateGeom g = locate_geom(ctx, c.sep);
+    const int U = ctx->locate_up, n_in = g.n;
+    g.n = (int32_t)upsample_len(n_in, U);                                    // (check_locate_upsample: it fits)
+    g.lag_lo *= U;
+    const int guard = (int)std::min<long long>((long long)c.guard * U, g.n);      // (a guard of the range's length excludes every lag)
+    return LocateRun{g, U, n_in, n_sets, c.tracks ? L : 0, c.J, c.K, guard, c.tracks && c.rounds};
+}
+
+// What the setting U > 1 adds to the refusals of a call on n_sets stacks of P pairs, once the table and the clocks are known:
+// nullptr, or the message and *status.  The fine lags of a row must fit 32 bits and U times every table and clock entry too
+// (TDOA_ERR_UNSUPPORTED); the upsampled surfaces must not be larger than the device's memory (TDOA_ERR_NOMEM, by arithmetic:
+// nothing is allocated here).
+const char *check_locate_upsample(const tdoa_ctx *ctx, size_t n_sets, int P, int *status)
+{
+    thread_local char buf[320];
+    const int U = ctx->locate_up;
+    if (U == 1) return nullptr;
+    *status = TDOA_ERR_UNSUPPORTED;
+    const long long n_u = upsample_len(2ll * ctx->prm.max_lag - 1, U);
+    if (n_u > INT_MAX) return "the upsampled lag range does not fit 32 bits";
+    if (ctx->locate_table_max * U >= (1ll << 31)) return "a delay table entry times the upsampling factor does not fit 32 bits";
+    if (ctx->clock_stacks && ctx->locate_clock_max * U >= (1ll << 31)) return "a clock table entry times the upsampling factor does not fit 32 bits";
+    const double bytes = 8.0 * (double)n_sets * (double)P * (double)n_u;
+    const size_t tiles = ((size_t)(2ll * ctx->prm.max_lag - 1) + kUpsampleThreads - 1) / kUpsampleThreads;
+    if ((ctx->total_mem && bytes > (double)ctx->total_mem) || (double)n_sets * P * (double)tiles > (double)INT_MAX) {
+        *status = TDOA_ERR_NOMEM;
+        snprintf(buf, sizeof(buf), "the delay-table search's upsampled surfaces [%zu stacks][%d pairs][%lld lags of 1/%d sample] (%.1f MB) do not fit in device memory",
+                 n_sets, P, n_u, U, bytes / 1e6);
+        return buf;
+    }
+    return nullptr;
 }
 
 // the arguments of a call; they need no device
@@ -117,11 +149,18 @@ int check_locate_state(const tdoa_ctx *ctx, int windows_per_stack, bool tracks, 
     int wpb = 0;
     if (tdoa_num_windows(ctx, &wpb, nullptr)) return refuse(TDOA_ERR_STATE, "captures missing or too small");
     const StackGeom sg = stack_geom(wpb, windows_per_stack);
-    if (locate_overflows(P, sg.mm)) return refuse(TDOA_ERR_UNSUPPORTED, "pairs x stack length > 2^17: a cell's score could overflow");
+    const int U = ctx->locate_up;
+    if (locate_overflows(P, sg.mm, U))
+        return refuse(TDOA_ERR_UNSUPPORTED, U > 1 ? "4 x pairs x stack length > 2^17 on upsampled surfaces: a cell's score could overflow"
+                                                  : "pairs x stack length > 2^17: a cell's score could overflow");
     if (3ll * wpb > kLocateMaxSets) return refuse(TDOA_ERR_UNSUPPORTED, "more than 65535 stacks");
     if (const char *bad = check_locate_clock(ctx, sg.n_stacks, S)) return refuse(TDOA_ERR_STATE, bad);
+    int status = TDOA_OK;
+    if (const char *bad = check_locate_upsample(ctx, (size_t)sg.n_stacks, P, &status)) return refuse(status, bad);
     if (!tracks) return TDOA_OK;
-    if (locate_overflows(P, wpb)) return refuse(TDOA_ERR_UNSUPPORTED, "pairs x windows per block > 2^17: a track's sum could overflow");
+    if (locate_overflows(P, wpb, U))
+        return refuse(TDOA_ERR_UNSUPPORTED, U > 1 ? "4 x pairs x windows per block > 2^17 on upsampled surfaces: a track's sum could overflow"
+                                                  : "pairs x windows per block > 2^17: a track's sum could overflow");
     if (sg.spb > kCellTrackMaxLen) return refuse(TDOA_ERR_UNSUPPORTED, "a track of more than 4096 stacks");
     return TDOA_OK;
 }
@@ -164,6 +203,9 @@ int upload_locate_track_roots(tdoa_ctx *ctx, const std::vector<double> &roots)
 //   ctrack_pairs    -                K (the counts)    K (the counts)  pairs_in and reserved [stack][2]
 //   map statistics  K n_sets         the larger of n_sets and K n_tracks   one record per judged plane: the search judges its maps,
 //                                                                      the tracks judge T_0
+//   locate_qu       with U > 1: the upsampled surfaces [stack][pair][n], which every kernel above then reads as Q,
+//   locate_table_up             U x the table [station][cell] and U x the clock differences [stack][pair]: state beside the table and
+//   locate_clock_up             the clocks, remade when either or U changes (remake_locate_scaled), data of a replayed graph
 
 // round r's scores [stack][cell]
 long long *locate_run_map(const tdoa_ctx *ctx, const LocateRun &run, int r)
@@ -214,6 +256,14 @@ int ensure_locate_run(tdoa_ctx *ctx, const LocateRun &run)
     const LocateGeom &g = run.g;
     const size_t n_sets = run.n_sets, n_tracks = run.n_tracks(), K = run.K, sp = n_sets * g.P;
     const size_t map_planes = run.L > 1 ? 1 : K, t_planes = run.L > 1 ? K + 1 : 0;
+    if (run.U > 1) {
+        if (ensure(ctx, ctx->locate_qu, sizeof(long long) * sp * (size_t)g.n)) {
+            char buf[320];
+            snprintf(buf, sizeof(buf), "the delay-table search's upsampled surfaces [%zu stacks][%d pairs][%d lags of 1/%d sample] (%.1f MB) do not fit in device memory: %s",
+                     n_sets, (int)g.P, (int)g.n, run.U, 8.0 * (double)sp * (double)g.n / 1e6, ctx->last_error.c_str());
+            return fail(ctx, TDOA_ERR_NOMEM, buf);
+        }
+    }
     if (ensure(ctx, ctx->locate_map, sizeof(long long) * map_planes * run.plane()) ||
         (run.L > 1 && (ensure(ctx, ctx->ctrack_d, 2 * run.plane()) || ensure(ctx, ctx->ctrack_t, sizeof(long long) * t_planes * n_tracks * g.n_cells)))) {
         char buf[320];
@@ -244,7 +294,7 @@ int ensure_locate_run(tdoa_ctx *ctx, const LocateRun &run)
 // what every launch of a run takes
 struct LocateDev {
     hipStream_t st;
-    const long long *Q;                      // [n_sets][P][n]
+    const long long *Q;                      // [n_sets][P][n]: the call's words, with U > 1 the upsampled ones
     const double *roots, *track_roots;       // sqrt(N_w) per stack and per track
     const int32_t *table;
     const long long *cdiff;                  // the clock table's differences, nullptr without one
@@ -274,6 +324,20 @@ template <class Launch> void locate_scores_dispatch(int S, int reg_stations, boo
         TDOA_LOCATE_CASE(0)
     }
 #undef TDOA_LOCATE_CASE
+}
+
+// rows [n_rows][n] -> [n_rows][(n - 1) U + 1], U in {2, 4, 8, 16}: the one place the upsampler is launched (n_rows x tiles fits
+// the grid: check_locate_upsample, tdoa_debug_upsample_q)
+void launch_stack_upsample(hipStream_t st, const long long *Q, size_t n_rows, int n, int U, long long *out)
+{
+    const int tiles = (n + kUpsampleThreads - 1) / kUpsampleThreads;
+    const dim3 grid((unsigned)(n_rows * (size_t)tiles)), block(kUpsampleThreads);
+    switch (U) {
+    case 2: hipLaunchKernelGGL(k_stack_upsample<2>, grid, block, 0, st, Q, n, tiles, out); break;
+    case 4: hipLaunchKernelGGL(k_stack_upsample<4>, grid, block, 0, st, Q, n, tiles, out); break;
+    case 8: hipLaunchKernelGGL(k_stack_upsample<8>, grid, block, 0, st, Q, n, tiles, out); break;
+    case 16: hipLaunchKernelGGL(k_stack_upsample<16>, grid, block, 0, st, Q, n, tiles, out); break;
+    }
 }
 
 // the rounds' mask as the kernels take it: a guard of the range's length already excludes every lag of the range
@@ -367,12 +431,20 @@ CellTrackGeom cell_track_geom(const LocateGeom &lg, int L, int J)
 // (every round of a search; with tracks round 0 only, whose best cells the search's records keep on the device), then with
 // tracks the recurrence and the tracks' end.  With a clock table (its shape checked by the caller: n_sets stacks of g.S
 // stations) the scores' clock instantiation runs and the finishes add the same differences.  With tracks their roots are in
-// ctx->ctrack_roots (upload_locate_track_roots).  Kernel launches only (the step graph captures them).
+// ctx->ctrack_roots (upload_locate_track_roots).  With U > 1 the run starts with the upsampler, and every launch behind it takes
+// its output, the scaled table and the scaled clock differences: Q is [n_sets][P][n_in] then.  Kernel launches only (the step graph captures them).
 void launch_locate_run(tdoa_ctx *ctx, const long long *Q, const double *roots, const LocateRun &run)
 {
     const LocateGeom &g = run.g;
-    const LocateDev d{ctx->stream, Q, roots, ctx->ctrack_roots.as<const double>(), ctx->locate_table.as<const int32_t>(),
-                      ctx->clock_stacks ? ctx->locate_clock.as<const long long>() : nullptr, ctx->locate_part.as<ClosureCand>(),
+    const int32_t *table = ctx->locate_table.as<const int32_t>();
+    const long long *cdiff = ctx->clock_stacks ? ctx->locate_clock.as<const long long>() : nullptr;
+    if (run.U > 1) {
+        table = ctx->locate_table_up.as<const int32_t>();
+        if (cdiff) cdiff = ctx->locate_clock_up.as<const long long>();
+        launch_stack_upsample(ctx->stream, Q, (size_t)run.n_sets * g.P, run.n_in, run.U, ctx->locate_qu.as<long long>());
+        Q = ctx->locate_qu.as<const long long>();
+    }
+    const LocateDev d{ctx->stream, Q, roots, ctx->ctrack_roots.as<const double>(), table, cdiff, ctx->locate_part.as<ClosureCand>(),
                       ctx->locate_best.as<int32_t>(), ctx->locate_centres.as<LocateCentres>(), ctx->ctrack_d.as<signed char>()};
     const CellTrackGeom tg = cell_track_geom(g, run.L, run.J);
     const unsigned n_tracks = (unsigned)run.n_tracks();

@@ -406,6 +406,7 @@ struct LocateProduct : StackProduct {
     int n_cells = 0, n_cols = 0;             // the shape of the context's table: in the key (the table itself is data)
     bool clocked = false;                    // the context holds station clocks: in the key (another kernel; the clocks are data)
     uint64_t stats = 0;                      // map statistics (map_stats_key): in the key (more kernels; the ranks are data), 0: off
+    int up = 1;                              // the upsampling factor (tdoa_locate_set_upsample): in the key (more kernels, another geometry)
     std::vector<double> track_roots;         // refresh's host copy of sqrt(N_w) (lives until the call has synchronised)
 
     LocateRun run(const tdoa_ctx *ctx) const { return locate_run(ctx, call, layout.n_stacks, layout.spb); }
@@ -420,7 +421,7 @@ struct LocateProduct : StackProduct {
     {
         const uint64_t L = call.tracks ? (uint64_t)layout.spb : 0, pairs = call.tracks && call.rounds;
         key->insert(key->end(), {Locate, (uint64_t)m, L | (pairs << 32), (uint64_t)call.J, (uint64_t)call.K, (uint64_t)call.guard,
-                                 (uint64_t)call.sep, (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked, stats});
+                                 (uint64_t)call.sep, (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked | ((uint64_t)(up - 1) << 8), stats});
     }
     int refresh(const StepView &v) override  // (every call: the debug and the group's calls write their own roots there)
     {

@@ -46,6 +46,7 @@
 #include "stack_cell_track.hpp"
 #include "stack_locate_track_multi.hpp"
 #include "stack_map_stats.hpp"
+#include "stack_upsample.hpp"
 
 using namespace tdoa;
 
@@ -203,6 +204,13 @@ struct tdoa_ctx {
     DevBuf debug_q, debug_roots;
     int locate_cells = 0, locate_cols = 0, locate_stations = 0;
     int clock_stacks = 0, clock_stations = 0;
+    // sub-sample locate (state: tdoa_locate_set_upsample; 1: off): the factor U, the largest magnitudes of the table's and the
+    // clocks' entries (U times either must fit 32 bits), and a run's buffers: the upsampled surfaces [stack][pair][(n - 1) U + 1],
+    // U x the table and U x the clock differences.  Also the output of tdoa_debug_upsample_q.
+    int locate_up = 1;
+    long long locate_table_max = 0, locate_clock_max = 0;
+    DevBuf locate_qu, locate_table_up, locate_clock_up;
+    size_t total_mem = 0;                   // of the device, 0: unknown
 };
 
 namespace {
@@ -488,7 +496,8 @@ int tdoa_create(const tdoa_params *p, tdoa_ctx **out)
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, prm.device) == hipSuccess && cus > 0)
             ctx->n_cu = cus;
         size_t total_mem = 0;
-        if (hipDeviceTotalMem(&total_mem, prm.device) == hipSuccess && total_mem > 0)
+        if (hipDeviceTotalMem(&total_mem, prm.device) == hipSuccess && total_mem > 0) ctx->total_mem = total_mem;
+        if (total_mem > 0)
             ctx->workspace_limit = std::max(8.0 * 1073741824.0, (double)total_mem / 3.0);
     }
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -569,7 +578,7 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->mstat_ranks, &ctx->mstat_hist, &ctx->mstat_state, &ctx->mstat_out,
                       &ctx->sline_in, &ctx->sline_tab, &ctx->sline_roots, &ctx->sline_cur, &ctx->sline_k, &ctx->sline_h, &ctx->sline_part,
                       &ctx->sline_moved, &ctx->sline_start, &ctx->sline_out, &ctx->sline_clock, &ctx->sline_rate, &ctx->sline_rows,
-                      &ctx->sline_lags, &ctx->sline_corr};
+                      &ctx->sline_lags, &ctx->sline_corr, &ctx->locate_qu, &ctx->locate_table_up, &ctx->locate_clock_up};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1163,6 +1172,7 @@ static int process_locate_call(tdoa_ctx *ctx, int windows_per_stack, const Locat
     prod.n_cols = ctx->locate_cols;
     prod.clocked = ctx->clock_stacks != 0;
     prod.stats = map_stats_key(ctx);
+    prod.up = ctx->locate_up;
     return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
 }
 

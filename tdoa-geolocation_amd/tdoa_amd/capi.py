@@ -124,6 +124,7 @@ SYMBOLS = [
     "tdoa_process_locate_track_multi", "tdoa_debug_locate_track_multi_from_q", "tdoa_group_process_locate_track_multi",
     "tdoa_locate_set_stats", "tdoa_locate_last_stats", "tdoa_group_locate_set_stats", "tdoa_group_locate_last_stats",
     "tdoa_process_sync_drift", "tdoa_debug_sync_drift_from_q", "tdoa_group_process_sync_drift", "tdoa_sync_line_clock",
+    "tdoa_locate_set_upsample", "tdoa_group_locate_set_upsample", "tdoa_locate_upsample_taps", "tdoa_debug_upsample_q",
 ]
 
 _lib = None
@@ -268,6 +269,10 @@ def load(build_if_missing=True):
     L.tdoa_group_locate_set_stats.argtypes = [vp, C.POINTER(C.c_uint16), C.c_int, C.c_int]
     L.tdoa_locate_last_stats.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.tdoa_group_locate_last_stats.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
+    L.tdoa_locate_set_upsample.argtypes = [vp, C.c_int]
+    L.tdoa_group_locate_set_upsample.argtypes = [vp, C.c_int]
+    L.tdoa_locate_upsample_taps.argtypes = [C.c_int, i32p]
+    L.tdoa_debug_upsample_q.argtypes = [vp, i64p, C.c_int, C.c_int, i64p]
     L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
                                         C.POINTER(C.c_int)]
     _lib = L
@@ -703,6 +708,27 @@ class Context:
         """tdoa_locate_last_stats -> [n_planes] MAP_STATS_DTYPE of the last call of the delay-table family, in its records'
         order"""
         return _last_stats(self, self._L.tdoa_locate_last_stats)
+
+    def locate_set_upsample(self, U):
+        """tdoa_locate_set_upsample: while U in {2, 4, 8, 16} is set, every process_locate*, locate*_from_q call scores its
+        cells on the surfaces upsampled to 1/U sample (tdoa_amd.upsample states it); "lags" are then in units of 1/U sample.
+        U = 1: off"""
+        self._chk(self._L.tdoa_locate_set_upsample(self._h, int(U)))
+
+    def upsample_q(self, q, U):
+        """tdoa_debug_upsample_q: the upsampler on the caller's rows q [n_rows][2 max_lag - 1] int64 (or one row) ->
+        [n_rows][(2 max_lag - 2) U + 1] int64, written over a poisoned array"""
+        q = np.ascontiguousarray(q, dtype=np.int64)
+        one = q.ndim == 1
+        if one:
+            q = q[None]
+        n = 2 * self.params.max_lag - 1
+        if q.ndim != 2 or q.shape[1] != n:
+            raise ValueError("q must be [n_rows][2 max_lag - 1]")
+        out = np.full((q.shape[0], (n - 1) * int(U) + 1 if int(U) > 0 else 1), -0x0123456789ABCDEF, dtype=np.int64)
+        self._chk(self._L.tdoa_debug_upsample_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], int(U),
+                                                out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out[0] if one else out
 
     def _with_stats(self, out, like):
         """out with "stats" shaped like out[like] while the setting is on"""
@@ -1243,6 +1269,10 @@ class Group:
         """tdoa_group_locate_last_stats -> Context.locate_last_stats' array, byte-identical to a single context's"""
         return _last_stats(self, self._L.tdoa_group_locate_last_stats)
 
+    def locate_set_upsample(self, U):
+        """tdoa_group_locate_set_upsample: Context.locate_set_upsample on every member"""
+        self._chk(self._L.tdoa_group_locate_set_upsample(self._h, int(U)))
+
     _with_stats = Context._with_stats
 
     def process_locate_track(self, windows_per_stack=0, max_step=0, min_separation=1, want_total=False):
@@ -1308,6 +1338,15 @@ def sync_line_clock(clock, rate, drift_den, first_position, n_positions):
     if rc != 0:
         raise TdoaError(rc, "tdoa_sync_line_clock")
     return out
+
+
+def locate_upsample_taps(U):
+    """tdoa_locate_upsample_taps (host only) -> [U][16] int32: the taps of the U phases at scale 2^15"""
+    taps = np.zeros((max(int(U), 1), 16), dtype=np.int32)
+    rc = load().tdoa_locate_upsample_taps(int(U), taps.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc:
+        raise TdoaError(rc, "tdoa_locate_upsample_taps")
+    return taps
 
 
 def locate_grid_table(stations_lle, lat0, lon0, dlat, dlon, rows, cols, height_m, sample_rate):
