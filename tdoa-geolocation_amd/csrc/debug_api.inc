@@ -1,5 +1,6 @@
 // debug_api.inc -- the tdoa_debug_* and tdoa_profile_* entry points (tests and measurements).
-// Included at the end of tdoa_mi355x.hip.
+// Included by tdoa_mi355x.hip after its entries.  The searches' tdoa_debug_*_from_q entries are in the searches' own files
+// (debug_search_from_q, stack_search.inc).
 
 extern "C" {
 
@@ -228,149 +229,6 @@ int tdoa_debug_select_peaks(tdoa_ctx *ctx, const float *surface, int n_lags, int
     if (count) HIPCHK(ctx, hipMemcpyAsync(count, ctx->sel_count.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));       // `one` is a stack object
     return TDOA_OK;
-}
-
-// The caller's words and sqrt(n_w) for each of n_sets sets, for the three entries below, in buffers that are theirs alone
-// (ctx->debug_q, ctx->debug_roots): the stack's sums and a cached step graph's buffers stay as they are.  (A call that has to
-// allocate or grow one of its buffers moves alloc_gen like every ensure(): the next step captures its graph again, with the
-// same results.)  *roots lives until the caller has synchronised.
-static int upload_debug_q(tdoa_ctx *ctx, const int64_t *q, size_t n_q, int n_sets, int n_w, std::vector<double> *roots)
-{
-    int rc;
-    if ((rc = check_ctx(ctx))) return rc;
-    if ((rc = ensure(ctx, ctx->debug_q, sizeof(long long) * n_q))) return rc;
-    if ((rc = ensure(ctx, ctx->debug_roots, sizeof(double) * n_sets))) return rc;
-    roots->assign((size_t)n_sets, std::sqrt((double)n_w));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->debug_q.p, q, sizeof(long long) * n_q, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->debug_roots.p, roots->data(), sizeof(double) * n_sets, hipMemcpyHostToDevice, ctx->stream));
-    return TDOA_OK;
-}
-
-// the closure search's kernels (closure_api.inc) on the caller's words: n_sets sets of P = S (S-1) / 2 rows of 2 max_lag - 1
-// int64, every set a stack of n_w windows.  Needs the context for max_lag and the device only.
-int tdoa_debug_closure_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int gate, int min_separation,
-                              const int32_t *centre, tdoa_closure *out)
-{
-    int rc;
-    if (!ctx) return TDOA_ERR_INVALID;
-    if (const char *bad = check_closure_args(gate, min_separation, out)) return fail(ctx, TDOA_ERR_INVALID, bad);
-    if (!q || n_sets < 1 || n_w < 1 || n_stations < 3 || n_stations > kClosureMaxStations)
-        return fail(ctx, TDOA_ERR_INVALID, "q is NULL, n_sets < 1, n_w < 1 or n_stations outside 3 .. 64");
-    const ClosureGeom g = closure_geom(n_stations, ctx->prm.max_lag, gate, min_separation);
-    if ((long long)n_sets * g.T > INT_MAX / 4) return fail(ctx, TDOA_ERR_INVALID, "too many sets");
-    std::vector<double> roots;
-    const std::vector<int32_t> c = closure_centres(centre, n_stations);
-    if ((rc = upload_debug_q(ctx, q, (size_t)n_sets * g.P * g.n, n_sets, n_w, &roots))) return rc;
-    if ((rc = ensure_closure(ctx, n_sets, g))) return rc;
-    if ((rc = upload_closure_centre(ctx, c))) return rc;
-    launch_closure(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), n_sets, g);
-    return download_and_wait(ctx, [&] { return download_closure(ctx, n_sets, g, out); });
-}
-
-// A call of the delay-table family (locate_run.inc) on the caller's words: n_sets sets of P = S (S-1) / 2 rows of 2 max_lag - 1
-// int64, every set a stack of n_w windows, against the context's table; with tracks set t * track_len + j is position j of
-// track t.  The outputs are [round] planes.  Needs the context for max_lag, the table, the clocks and the device only.
-static int debug_locate_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, const LocateCall &call)
-{
-    int rc;
-    if (!ctx) return TDOA_ERR_INVALID;
-    if (const char *bad = check_locate_call(call)) return fail(ctx, TDOA_ERR_INVALID, bad);
-    if (!q || n_sets < 1 || n_sets > kLocateMaxSets || n_w < 1 || n_stations < 2 || n_stations > kLocateMaxStations)
-        return fail(ctx, TDOA_ERR_INVALID, "q is NULL, n_sets outside 1 .. 65535, n_w < 1 or n_stations outside 2 .. 64");
-    if (call.tracks && (track_len < 1 || n_sets % track_len != 0)) return fail(ctx, TDOA_ERR_INVALID, "track_len < 1 or not a divisor of n_sets");
-    if (const char *bad = check_locate_table(ctx, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
-    if (const char *bad = check_locate_clock(ctx, n_sets, n_stations)) return fail(ctx, TDOA_ERR_STATE, bad);
-    const LocateRun run = locate_run(ctx, call, n_sets, track_len);
-    if (!call.tracks && locate_overflows(run.g.P, n_w, run.U))
-        return fail(ctx, TDOA_ERR_UNSUPPORTED, run.U > 1 ? "4 x pairs x n_w > 2^17 on upsampled surfaces: a cell's score could overflow"
-                                                         : "pairs x n_w > 2^17: a cell's score could overflow");
-    if (call.tracks && locate_overflows(run.g.P, (long long)track_len * n_w, run.U))
-        return fail(ctx, TDOA_ERR_UNSUPPORTED, run.U > 1 ? "4 x pairs x track_len x n_w > 2^17 on upsampled surfaces: a track's sum could overflow"
-                                                         : "pairs x track_len x n_w > 2^17: a track's sum could overflow");
-    int status = TDOA_OK;
-    if (const char *bad = check_locate_upsample(ctx, (size_t)n_sets, run.g.P, &status)) return fail(ctx, status, bad);
-    if (call.tracks && track_len > kCellTrackMaxLen) return fail(ctx, TDOA_ERR_UNSUPPORTED, "a track of more than 4096 stacks");
-    std::vector<double> roots;
-    const std::vector<double> track_roots(run.n_tracks(), std::sqrt((double)track_len * (double)n_w));
-    if ((rc = upload_debug_q(ctx, q, (size_t)n_sets * run.g.P * run.n_in, n_sets, n_w, &roots))) return rc;
-    if ((rc = ensure_locate_run(ctx, run))) return rc;
-    if (call.tracks && (rc = upload_locate_track_roots(ctx, track_roots))) return rc;
-    launch_locate_run(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), run);
-    return download_and_wait(ctx, [&] { return download_locate_run(ctx, run, call); });
-}
-
-int tdoa_debug_locate_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int min_separation,
-                             tdoa_location *loc, int32_t *lags, double *corr, int64_t *map)
-{
-    return debug_locate_from_q(ctx, q, n_sets, 0, n_stations, n_w, locate_search_call(false, 1, 0, min_separation, loc, lags, corr, map));
-}
-
-int tdoa_debug_locate_multi_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int n_emitters, int guard,
-                                   int min_separation, tdoa_location *loc, int32_t *lags, double *corr, int64_t *map)
-{
-    return debug_locate_from_q(ctx, q, n_sets, 0, n_stations, n_w, locate_search_call(true, n_emitters, guard, min_separation, loc, lags, corr, map));
-}
-
-int tdoa_debug_locate_track_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, int max_step,
-                                   int min_separation, tdoa_cell_track *track, int32_t *cells, int64_t *own, int32_t *lags,
-                                   double *corr, int64_t *total)
-{
-    return debug_locate_from_q(ctx, q, n_sets, track_len, n_stations, n_w,
-                               locate_track_call(false, max_step, 1, 0, min_separation, track, cells, own, nullptr, lags, corr, total));
-}
-
-int tdoa_debug_locate_track_multi_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, int max_step,
-                                         int n_emitters, int guard, int min_separation, tdoa_cell_track *track, int32_t *cells,
-                                         int64_t *own, int32_t *pairs, int32_t *lags, double *corr, int64_t *total)
-{
-    return debug_locate_from_q(ctx, q, n_sets, track_len, n_stations, n_w,
-                               locate_track_call(true, max_step, n_emitters, guard, min_separation, track, cells, own, pairs, lags, corr, total));
-}
-
-// The upsampler (stack_upsample.hpp) on the caller's words: n_rows rows of 2 max_lag - 1 int64 -> n_rows rows of
-// (2 max_lag - 2) U + 1.  Needs the context for max_lag and the device only; the setting of the context is not read.
-int tdoa_debug_upsample_q(tdoa_ctx *ctx, const int64_t *q, int n_rows, int U, int64_t *out)
-{
-    int rc;
-    if (!ctx) return TDOA_ERR_INVALID;
-    if (!q || !out || n_rows < 1 || !upsample_factor_ok(U)) return fail(ctx, TDOA_ERR_INVALID, "q or out is NULL, n_rows < 1 or U is not one of 1, 2, 4, 8, 16");
-    const long long n = 2ll * ctx->prm.max_lag - 1, n_u = upsample_len(n, U), tiles = (n + kUpsampleThreads - 1) / kUpsampleThreads;
-    if (n_u > INT_MAX || (double)n_rows * (double)tiles > (double)INT_MAX) return fail(ctx, TDOA_ERR_UNSUPPORTED, "the upsampled rows do not fit the grid");
-    if (U == 1) {
-        std::memcpy(out, q, sizeof(int64_t) * (size_t)n_rows * (size_t)n);
-        return TDOA_OK;
-    }
-    if ((rc = check_ctx(ctx))) return rc;
-    if ((rc = ensure(ctx, ctx->debug_q, sizeof(long long) * (size_t)n_rows * (size_t)n))) return rc;
-    if ((rc = ensure(ctx, ctx->locate_qu, sizeof(long long) * (size_t)n_rows * (size_t)n_u))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->debug_q.p, q, sizeof(long long) * (size_t)n_rows * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    launch_stack_upsample(ctx->stream, ctx->debug_q.as<const long long>(), (size_t)n_rows, (int)n, U, ctx->locate_qu.as<long long>());
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, ctx->locate_qu.p, sizeof(long long) * (size_t)n_rows * (size_t)n_u, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return TDOA_OK;
-}
-
-// the clock search's kernels (sync_api.inc) on the caller's words: n_sets sets of P = S (S-1) / 2 rows of 2 max_lag - 1 int64,
-// every set a stack of n_w windows.  Needs the context for max_lag and the device only.
-int tdoa_debug_sync_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int gate, int rounds,
-                           const int32_t *ref_delay, const int32_t *centre, tdoa_sync *sync, int32_t *clock, int32_t *lags,
-                           double *corr)
-{
-    int rc;
-    if (!ctx) return TDOA_ERR_INVALID;
-    if (const char *bad = check_sync_args(gate, rounds, ref_delay, sync)) return fail(ctx, TDOA_ERR_INVALID, bad);
-    if (!q || n_sets < 1 || n_sets > kLocateMaxSets || n_w < 1 || n_stations < 2 || n_stations > kSyncMaxStations)
-        return fail(ctx, TDOA_ERR_INVALID, "q is NULL, n_sets outside 1 .. 65535, n_w < 1 or n_stations outside 2 .. 64");
-    const SyncGeom g = sync_geom(n_stations, ctx->prm.max_lag, gate, rounds);
-    if (locate_overflows(g.P, n_w)) return fail(ctx, TDOA_ERR_UNSUPPORTED, "pairs x n_w > 2^17: the objective could overflow");
-    std::vector<double> roots;
-    const std::vector<int32_t> in = sync_inputs(ref_delay, centre, n_stations);
-    if ((rc = upload_debug_q(ctx, q, (size_t)n_sets * g.P * g.n, n_sets, n_w, &roots))) return rc;
-    if ((rc = ensure_sync(ctx, n_sets, g))) return rc;
-    if ((rc = upload_sync_in(ctx, in))) return rc;
-    launch_sync(ctx, ctx->debug_q.as<const long long>(), ctx->debug_roots.as<const double>(), n_sets, g);
-    return download_and_wait(ctx, [&] { return download_sync(ctx, n_sets, g, sync, clock, lags, corr); });
 }
 
 #ifdef TDOA_STG_TIMING

@@ -1,7 +1,9 @@
 // group_api.inc -- the multi-device group (include/tdoa_mi355x.h, "multi-device group"): one tdoa_ctx per member, member k
 // is rank k of n_members, and one call shards tdoa_process over them and merges their peak records on the host
 // (tdoa_process_stacked: adds their fixed-point partial sums and finishes the sum on member 0).
-// Included at the end of tdoa_mi355x.hip; uses its helpers (fail, check_ctx, unit_owner, capture_upload_file_runs).
+// Included by tdoa_mi355x.hip after its entries and before stack_search.inc; uses its helpers (fail, check_ctx, unit_owner,
+// capture_upload_file_runs).  The group's calls of the searches on the stacks' sums are in the searches' own files
+// (group_process_search, stack_search.inc).
 //
 // Threads.  tdoa_group_capture_upload_files and tdoa_group_process run member 0 on the caller's thread and members 1..n-1
 // on std::threads started for the call; each thread calls into its own context only.  Two conditions make that safe, and a
@@ -313,30 +315,6 @@ int tdoa_group_process_stacked(tdoa_group *g, int windows_per_stack, int k, int 
     return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
 }
 
-// tdoa_process_closure over the members: their shares of the fixed-point sums as in tdoa_group_process_stacked, added on the
-// host; member 0 searches the merged Q with the kernels a single context's call ends with.
-int tdoa_group_process_closure(tdoa_group *g, int windows_per_stack, int gate, int min_separation, const int32_t *centre,
-                               tdoa_closure *closure_host)
-{
-    if (!g) return TDOA_ERR_INVALID;
-    if (windows_per_stack < 0) return group_fail(g, TDOA_ERR_INVALID, "windows_per_stack < 0");
-    if (const char *bad = check_closure_args(gate, min_separation, closure_host)) return group_fail(g, TDOA_ERR_INVALID, bad);
-    const int world = (int)g->members.size();
-    tdoa_ctx *c0 = g->members[0];
-    if (world == 1) {                        // no merge: the member's call writes the records
-        const int rc = tdoa_process_closure(c0, windows_per_stack, gate, min_separation, centre, closure_host);
-        return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
-    }
-    if (c0->prm.lag_mode == TDOA_LAGS_GO) return group_fail(g, TDOA_ERR_UNSUPPORTED, "the closure search with TDOA_LAGS_GO");
-    if (c0->caps.empty()) return group_fail(g, TDOA_ERR_STATE, member_name(0, c0->device) + "captures missing");
-    if (c0->caps.size() < 3 || c0->caps.size() > (size_t)kClosureMaxStations)
-        return group_fail(g, TDOA_ERR_UNSUPPORTED, "the closure search needs 3 .. 64 stations");
-    const int64_t *sum = nullptr;
-    if (const int rc = group_merged_q(g, windows_per_stack, &sum)) return rc;
-    const int rc = closure_from_host(c0, sum, windows_per_stack, gate, min_separation, centre, closure_host);
-    return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
-}
-
 // the table to every member: each keeps its own copy, member 0's is the one a group of several searches with
 int tdoa_group_locate_set_table(tdoa_group *g, const int32_t *delay, int n_cells, int n_cols, int n_stations)
 {
@@ -344,55 +322,6 @@ int tdoa_group_locate_set_table(tdoa_group *g, const int32_t *delay, int n_cells
     for (size_t m = 0; m < g->members.size(); m++)
         if (const int rc = tdoa_locate_set_table(g->members[m], delay, n_cells, n_cols, n_stations)) return member_fail(g, (int)m, rc);
     return TDOA_OK;
-}
-
-// The four entries of the delay-table family over the members: their shares of the fixed-point sums as in
-// tdoa_group_process_stacked, added on the host; member 0 runs the call on the merged Q with the kernels a single context's
-// call ends with.
-static int group_locate_call(tdoa_group *g, int windows_per_stack, const LocateCall &call)
-{
-    if (!g) return TDOA_ERR_INVALID;
-    if (windows_per_stack < 0) return group_fail(g, TDOA_ERR_INVALID, "windows_per_stack < 0");
-    if (const char *bad = check_locate_call(call)) return group_fail(g, TDOA_ERR_INVALID, bad);
-    const int world = (int)g->members.size();
-    tdoa_ctx *c0 = g->members[0];
-    if (world == 1) {                        // no merge: the member's call writes the outputs
-        const int rc = process_locate_call(c0, windows_per_stack, call);
-        return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
-    }
-    const char *what = nullptr;
-    if (const int rc = check_locate_state(c0, windows_per_stack, call.tracks, &what)) return group_fail(g, rc, member_name(0, c0->device) + what);
-    const int64_t *sum = nullptr;
-    if (const int rc = group_merged_q(g, windows_per_stack, &sum)) return rc;
-    const int rc = locate_run_from_host(c0, sum, windows_per_stack, call);
-    return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
-}
-
-int tdoa_group_process_locate(tdoa_group *g, int windows_per_stack, int min_separation, tdoa_location *loc_host, int32_t *lags_host,
-                              double *corr_host, int64_t *map_host)
-{
-    return group_locate_call(g, windows_per_stack, locate_search_call(false, 1, 0, min_separation, loc_host, lags_host, corr_host, map_host));
-}
-
-int tdoa_group_process_locate_track(tdoa_group *g, int windows_per_stack, int max_step, int min_separation, tdoa_cell_track *track_host,
-                                    int32_t *cells_host, int64_t *own_host, int32_t *lags_host, double *corr_host, int64_t *total_host)
-{
-    return group_locate_call(g, windows_per_stack, locate_track_call(false, max_step, 1, 0, min_separation, track_host, cells_host, own_host,
-                                                                     nullptr, lags_host, corr_host, total_host));
-}
-
-int tdoa_group_process_locate_multi(tdoa_group *g, int windows_per_stack, int n_emitters, int guard, int min_separation,
-                                    tdoa_location *loc_host, int32_t *lags_host, double *corr_host, int64_t *map_host)
-{
-    return group_locate_call(g, windows_per_stack, locate_search_call(true, n_emitters, guard, min_separation, loc_host, lags_host, corr_host, map_host));
-}
-
-int tdoa_group_process_locate_track_multi(tdoa_group *g, int windows_per_stack, int max_step, int n_emitters, int guard, int min_separation,
-                                          tdoa_cell_track *track_host, int32_t *cells_host, int64_t *own_host, int32_t *pairs_host,
-                                          int32_t *lags_host, double *corr_host, int64_t *total_host)
-{
-    return group_locate_call(g, windows_per_stack, locate_track_call(true, max_step, n_emitters, guard, min_separation, track_host, cells_host,
-                                                                     own_host, pairs_host, lags_host, corr_host, total_host));
 }
 
 // the clocks to every member: each keeps its own copy, member 0's is the one a group of several searches with
@@ -427,28 +356,6 @@ int tdoa_group_locate_last_stats(tdoa_group *g, tdoa_map_stats *out, int max_pla
 {
     if (!g) return TDOA_ERR_INVALID;
     const int rc = tdoa_locate_last_stats(g->members[0], out, max_planes, n_planes);
-    return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
-}
-
-// tdoa_process_sync over the members: their shares of the fixed-point sums as in tdoa_group_process_stacked, added on the
-// host; member 0 searches the merged Q with the kernels a single context's call ends with.
-int tdoa_group_process_sync(tdoa_group *g, int windows_per_stack, int gate, int rounds, const int32_t *ref_delay, const int32_t *centre,
-                            tdoa_sync *sync_host, int32_t *clock_host, int32_t *lags_host, double *corr_host)
-{
-    if (!g) return TDOA_ERR_INVALID;
-    if (windows_per_stack < 0) return group_fail(g, TDOA_ERR_INVALID, "windows_per_stack < 0");
-    if (const char *bad = check_sync_args(gate, rounds, ref_delay, sync_host)) return group_fail(g, TDOA_ERR_INVALID, bad);
-    const int world = (int)g->members.size();
-    tdoa_ctx *c0 = g->members[0];
-    if (world == 1) {                        // no merge: the member's call writes the outputs
-        const int rc = tdoa_process_sync(c0, windows_per_stack, gate, rounds, ref_delay, centre, sync_host, clock_host, lags_host, corr_host);
-        return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
-    }
-    const char *what = nullptr;
-    if (const int rc = check_sync_state(c0, windows_per_stack, &what)) return group_fail(g, rc, member_name(0, c0->device) + what);
-    const int64_t *sum = nullptr;
-    if (const int rc = group_merged_q(g, windows_per_stack, &sum)) return rc;
-    const int rc = sync_from_host(c0, sum, windows_per_stack, gate, rounds, ref_delay, centre, sync_host, clock_host, lags_host, corr_host);
     return rc == TDOA_OK ? rc : member_fail(g, 0, rc);
 }
 

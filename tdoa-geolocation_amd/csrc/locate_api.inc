@@ -1,6 +1,6 @@
 // locate_api.inc -- the delay-table family, host side: the table and the station clocks a context keeps and the host-only grid
 // table.  The family's runs on them are in locate_run.inc.  Included by tdoa_mi355x.hip after map_stats_api.inc and before
-// locate_run.inc.
+// locate_run.inc, sync_api.inc and sync_drift_api.inc (locate_overflows).
 
 extern "C" {
 

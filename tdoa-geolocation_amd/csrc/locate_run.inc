@@ -1,9 +1,9 @@
 // locate_run.inc -- the delay-table family, host side: tdoa_process_locate, tdoa_process_locate_multi, tdoa_process_locate_track
 // and tdoa_process_locate_track_multi are one computation with two switches (K rounds on masked lags; the recurrence over the L
 // stacks of a track).  A LocateCall is what a caller of one of the four asks for, a LocateRun is the call on n_sets stacks; the
-// checks the entries share and the run's buffers, launches, download and merged-sum call exist once, here, for a context's own
-// step (step_products.inc), the group's merged sum (group_api.inc) and the tdoa_debug_locate*_from_q entries (debug_api.inc).
-// Included by tdoa_mi355x.hip after locate_api.inc and before step_products.inc.
+// checks the entries share and the run's buffers, launches and download exist once, here; LocateSearch hands them to the three
+// routes of stack_search.inc, and the family's twelve entries and tdoa_debug_upsample_q are at the end.
+// Included by tdoa_mi355x.hip after stack_search.inc, map_stats_api.inc and locate_api.inc.
 
 namespace {
 
@@ -165,13 +165,24 @@ int check_locate_state(const tdoa_ctx *ctx, int windows_per_stack, bool tracks, 
     return TDOA_OK;
 }
 
-// sqrt(N_w) of the three blocks' tracks: a track holds all the windows of its block
-std::vector<double> block_track_roots(int wpb) { return std::vector<double>(3, std::sqrt((double)wpb)); }
-
-// sqrt(N_w) of every track to ctx->ctrack_roots; the caller synchronises before `roots` goes
-int upload_locate_track_roots(tdoa_ctx *ctx, const std::vector<double> &roots)
+// what the debug entries refuse of the caller's sets: the table, the clock table's shape, the overflow bounds, the track's length
+int check_locate_sets(const tdoa_ctx *ctx, bool tracks, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, const char **what)
 {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->ctrack_roots.p, roots.data(), sizeof(double) * roots.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (!q || n_sets < 1 || n_sets > kLocateMaxSets || n_w < 1 || n_stations < 2 || n_stations > kLocateMaxStations)
+        return refuse_with(what, TDOA_ERR_INVALID, "q is NULL, n_sets outside 1 .. 65535, n_w < 1 or n_stations outside 2 .. 64");
+    if (tracks && (track_len < 1 || n_sets % track_len != 0)) return refuse_with(what, TDOA_ERR_INVALID, "track_len < 1 or not a divisor of n_sets");
+    if (const char *bad = check_locate_table(ctx, n_stations)) return refuse_with(what, TDOA_ERR_STATE, bad);
+    if (const char *bad = check_locate_clock(ctx, n_sets, n_stations)) return refuse_with(what, TDOA_ERR_STATE, bad);
+    const int P = n_stations * (n_stations - 1) / 2, U = ctx->locate_up;
+    if (!tracks && locate_overflows(P, n_w, U))
+        return refuse_with(what, TDOA_ERR_UNSUPPORTED, U > 1 ? "4 x pairs x n_w > 2^17 on upsampled surfaces: a cell's score could overflow"
+                                                              : "pairs x n_w > 2^17: a cell's score could overflow");
+    if (tracks && locate_overflows(P, (long long)track_len * n_w, U))
+        return refuse_with(what, TDOA_ERR_UNSUPPORTED, U > 1 ? "4 x pairs x track_len x n_w > 2^17 on upsampled surfaces: a track's sum could overflow"
+                                                              : "pairs x track_len x n_w > 2^17: a track's sum could overflow");
+    int status = TDOA_OK;
+    if (const char *bad = check_locate_upsample(ctx, (size_t)n_sets, P, &status)) return refuse_with(what, status, bad);
+    if (tracks && track_len > kCellTrackMaxLen) return refuse_with(what, TDOA_ERR_UNSUPPORTED, "a track of more than 4096 stacks");
     return TDOA_OK;
 }
 
@@ -431,7 +442,7 @@ CellTrackGeom cell_track_geom(const LocateGeom &lg, int L, int J)
 // (every round of a search; with tracks round 0 only, whose best cells the search's records keep on the device), then with
 // tracks the recurrence and the tracks' end.  With a clock table (its shape checked by the caller: n_sets stacks of g.S
 // stations) the scores' clock instantiation runs and the finishes add the same differences.  With tracks their roots are in
-// ctx->ctrack_roots (upload_locate_track_roots).  With U > 1 the run starts with the upsampler, and every launch behind it takes
+// ctx->ctrack_roots (LocateSearch::refresh).  With U > 1 the run starts with the upsampler, and every launch behind it takes
 // its output, the scaled table and the scaled clock differences: Q is [n_sets][P][n_in] then.  Kernel launches only (the step graph captures them).
 void launch_locate_run(tdoa_ctx *ctx, const long long *Q, const double *roots, const LocateRun &run)
 {
@@ -502,24 +513,170 @@ int download_locate_run(tdoa_ctx *ctx, const LocateRun &run, const LocateCall &o
     return download_map_stats(ctx, locate_run_judged(run));
 }
 
-// a call of the family on a group's merged sum (finish_from_host, stacked_api.inc); a track spans a block
-int locate_run_from_host(tdoa_ctx *ctx, const int64_t *q_sum, int windows_per_stack, const LocateCall &call)
-{
-    int wpb = 0;
-    if (int rc = tdoa_num_windows(ctx, &wpb, nullptr)) return fail(ctx, rc, "captures missing or too small");
-    const int L = stack_geom(wpb, windows_per_stack).spb;
-    const std::vector<double> track_roots = block_track_roots(wpb);          // (lives until finish_from_host has synchronised)
-    const auto run = [&](int n_stacks) { return locate_run(ctx, call, n_stacks, L); };
-    return finish_from_host(
-        ctx, q_sum, windows_per_stack,
-        [&](int n_stacks, const double *roots) -> int {
-            int rc;
-            if ((rc = ensure_locate_run(ctx, run(n_stacks)))) return rc;
-            if (call.tracks && (rc = upload_locate_track_roots(ctx, track_roots))) return rc;
-            launch_locate_run(ctx, ctx->stack_q.as<const long long>(), roots, run(n_stacks));
-            return TDOA_OK;
-        },
-        [&](int n_stacks) { return download_locate_run(ctx, run(n_stacks), call); });
-}
+// ---- the family as a search on the stacks' sums (stack_search.inc) ----------------------------------------------------------------
+struct LocateSearch : StackSearch {
+    LocateCall call;                         // the entry's arguments and outputs
+    LocateRun run{};                         // bind: the call on the shape's sets; a context's own tracks span a block
+    bool clocked = false;                    // ... whether the context holds station clocks (another kernel; the clocks are data)
+    uint64_t stats = 0;                      // ... and the map statistics' word (map_stats_key: more kernels; the ranks are data), 0: off
+    std::vector<double> track_roots;         // sqrt(N_w) per track
+
+    explicit LocateSearch(const LocateCall &c) : StackSearch("the delay-table search with TDOA_LAGS_GO", nullptr), call(c) {}
+    const char *check_args() const override { return check_locate_call(call); }
+    int check_state(const tdoa_ctx *ctx, int windows_per_stack, const char **what) const override
+    {
+        return check_locate_state(ctx, windows_per_stack, call.tracks, what);
+    }
+    int check_sets(const tdoa_ctx *ctx, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, const char **what) const override
+    {
+        return check_locate_sets(ctx, call.tracks, q, n_sets, track_len, n_stations, n_w, what);
+    }
+    void bind(const tdoa_ctx *ctx, const SearchShape &sh) override
+    {
+        run = locate_run(ctx, call, sh.n_sets, sh.L);
+        clocked = ctx->clock_stacks != 0;
+        stats = map_stats_key(ctx);
+        track_roots.assign(run.n_tracks(), std::sqrt(sh.track_w));
+    }
+    // the rounds and the mask, the tracks' length (0: none) and step, whether the counts are produced (the centres are data), the
+    // table's shape (the table itself is data), the clock flag, the upsampling factor (more kernels, another geometry), the statistics
+    void key(std::vector<uint64_t> *key, int m) const override
+    {
+        key->insert(key->end(), {StepProduct::Locate, (uint64_t)m, (uint64_t)run.L | ((uint64_t)run.pairs << 32), (uint64_t)call.J, (uint64_t)call.K,
+                                 (uint64_t)call.guard, (uint64_t)call.sep, (uint64_t)run.g.n_cells | ((uint64_t)run.g.n_cols << 32),
+                                 (uint64_t)clocked | ((uint64_t)(run.U - 1) << 8), stats});
+    }
+    int reserve(tdoa_ctx *ctx) const override { return ensure_locate_run(ctx, run); }
+    // the tracks' roots (every call: the three routes write their own there)
+    int refresh(tdoa_ctx *ctx) const override
+    {
+        if (call.tracks)
+            HIPCHK(ctx, hipMemcpyAsync(ctx->ctrack_roots.p, track_roots.data(), sizeof(double) * track_roots.size(), hipMemcpyHostToDevice, ctx->stream));
+        return TDOA_OK;
+    }
+    void launch(tdoa_ctx *ctx, const long long *Q, const double *roots) const override { launch_locate_run(ctx, Q, roots, run); }
+    int download(tdoa_ctx *ctx) const override { return download_locate_run(ctx, run, call); }
+};
 
 }  // namespace
+
+extern "C" {
+
+// ---- a context's own call ---------------------------------------------------------------------------------------------------------
+int tdoa_process_locate(tdoa_ctx *ctx, int windows_per_stack, int min_separation, tdoa_location *loc_host, int32_t *lags_host,
+                        double *corr_host, int64_t *map_host)
+{
+    LocateSearch s(locate_search_call(false, 1, 0, min_separation, loc_host, lags_host, corr_host, map_host));
+    return process_search(ctx, windows_per_stack, s);
+}
+
+int tdoa_process_locate_track(tdoa_ctx *ctx, int windows_per_stack, int max_step, int min_separation, tdoa_cell_track *track_host,
+                              int32_t *cells_host, int64_t *own_host, int32_t *lags_host, double *corr_host, int64_t *total_host)
+{
+    LocateSearch s(locate_track_call(false, max_step, 1, 0, min_separation, track_host, cells_host, own_host, nullptr, lags_host, corr_host, total_host));
+    return process_search(ctx, windows_per_stack, s);
+}
+
+int tdoa_process_locate_multi(tdoa_ctx *ctx, int windows_per_stack, int n_emitters, int guard, int min_separation, tdoa_location *loc_host,
+                              int32_t *lags_host, double *corr_host, int64_t *map_host)
+{
+    LocateSearch s(locate_search_call(true, n_emitters, guard, min_separation, loc_host, lags_host, corr_host, map_host));
+    return process_search(ctx, windows_per_stack, s);
+}
+
+int tdoa_process_locate_track_multi(tdoa_ctx *ctx, int windows_per_stack, int max_step, int n_emitters, int guard, int min_separation,
+                                    tdoa_cell_track *track_host, int32_t *cells_host, int64_t *own_host, int32_t *pairs_host,
+                                    int32_t *lags_host, double *corr_host, int64_t *total_host)
+{
+    LocateSearch s(locate_track_call(true, max_step, n_emitters, guard, min_separation, track_host, cells_host, own_host, pairs_host, lags_host,
+                                     corr_host, total_host));
+    return process_search(ctx, windows_per_stack, s);
+}
+
+// ---- over a group's members: member 0's table, clocks and settings are the ones a group of several searches with -------------------
+int tdoa_group_process_locate(tdoa_group *g, int windows_per_stack, int min_separation, tdoa_location *loc_host, int32_t *lags_host,
+                              double *corr_host, int64_t *map_host)
+{
+    LocateSearch s(locate_search_call(false, 1, 0, min_separation, loc_host, lags_host, corr_host, map_host));
+    return group_process_search(g, windows_per_stack, s);
+}
+
+int tdoa_group_process_locate_track(tdoa_group *g, int windows_per_stack, int max_step, int min_separation, tdoa_cell_track *track_host,
+                                    int32_t *cells_host, int64_t *own_host, int32_t *lags_host, double *corr_host, int64_t *total_host)
+{
+    LocateSearch s(locate_track_call(false, max_step, 1, 0, min_separation, track_host, cells_host, own_host, nullptr, lags_host, corr_host, total_host));
+    return group_process_search(g, windows_per_stack, s);
+}
+
+int tdoa_group_process_locate_multi(tdoa_group *g, int windows_per_stack, int n_emitters, int guard, int min_separation,
+                                    tdoa_location *loc_host, int32_t *lags_host, double *corr_host, int64_t *map_host)
+{
+    LocateSearch s(locate_search_call(true, n_emitters, guard, min_separation, loc_host, lags_host, corr_host, map_host));
+    return group_process_search(g, windows_per_stack, s);
+}
+
+int tdoa_group_process_locate_track_multi(tdoa_group *g, int windows_per_stack, int max_step, int n_emitters, int guard, int min_separation,
+                                          tdoa_cell_track *track_host, int32_t *cells_host, int64_t *own_host, int32_t *pairs_host,
+                                          int32_t *lags_host, double *corr_host, int64_t *total_host)
+{
+    LocateSearch s(locate_track_call(true, max_step, n_emitters, guard, min_separation, track_host, cells_host, own_host, pairs_host, lags_host,
+                                     corr_host, total_host));
+    return group_process_search(g, windows_per_stack, s);
+}
+
+// ---- on the caller's words, against the context's table and clocks; the outputs are [round] planes -----------------------------------
+int tdoa_debug_locate_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int min_separation,
+                             tdoa_location *loc, int32_t *lags, double *corr, int64_t *map)
+{
+    LocateSearch s(locate_search_call(false, 1, 0, min_separation, loc, lags, corr, map));
+    return debug_search_from_q(ctx, q, n_sets, 0, n_stations, n_w, s);
+}
+
+int tdoa_debug_locate_multi_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int n_emitters, int guard,
+                                   int min_separation, tdoa_location *loc, int32_t *lags, double *corr, int64_t *map)
+{
+    LocateSearch s(locate_search_call(true, n_emitters, guard, min_separation, loc, lags, corr, map));
+    return debug_search_from_q(ctx, q, n_sets, 0, n_stations, n_w, s);
+}
+
+int tdoa_debug_locate_track_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, int max_step,
+                                   int min_separation, tdoa_cell_track *track, int32_t *cells, int64_t *own, int32_t *lags,
+                                   double *corr, int64_t *total)
+{
+    LocateSearch s(locate_track_call(false, max_step, 1, 0, min_separation, track, cells, own, nullptr, lags, corr, total));
+    return debug_search_from_q(ctx, q, n_sets, track_len, n_stations, n_w, s);
+}
+
+int tdoa_debug_locate_track_multi_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, int max_step,
+                                         int n_emitters, int guard, int min_separation, tdoa_cell_track *track, int32_t *cells,
+                                         int64_t *own, int32_t *pairs, int32_t *lags, double *corr, int64_t *total)
+{
+    LocateSearch s(locate_track_call(true, max_step, n_emitters, guard, min_separation, track, cells, own, pairs, lags, corr, total));
+    return debug_search_from_q(ctx, q, n_sets, track_len, n_stations, n_w, s);
+}
+
+// The upsampler (stack_upsample.hpp) on the caller's words: n_rows rows of 2 max_lag - 1 int64 -> n_rows rows of
+// (2 max_lag - 2) U + 1.  Needs the context for max_lag and the device only; the setting of the context is not read.
+int tdoa_debug_upsample_q(tdoa_ctx *ctx, const int64_t *q, int n_rows, int U, int64_t *out)
+{
+    int rc;
+    if (!ctx) return TDOA_ERR_INVALID;
+    if (!q || !out || n_rows < 1 || !upsample_factor_ok(U)) return fail(ctx, TDOA_ERR_INVALID, "q or out is NULL, n_rows < 1 or U is not one of 1, 2, 4, 8, 16");
+    const long long n = 2ll * ctx->prm.max_lag - 1, n_u = upsample_len(n, U), tiles = (n + kUpsampleThreads - 1) / kUpsampleThreads;
+    if (n_u > INT_MAX || (double)n_rows * (double)tiles > (double)INT_MAX) return fail(ctx, TDOA_ERR_UNSUPPORTED, "the upsampled rows do not fit the grid");
+    if (U == 1) {
+        std::memcpy(out, q, sizeof(int64_t) * (size_t)n_rows * (size_t)n);
+        return TDOA_OK;
+    }
+    if ((rc = check_ctx(ctx))) return rc;
+    if ((rc = ensure(ctx, ctx->debug_q, sizeof(long long) * (size_t)n_rows * (size_t)n))) return rc;
+    if ((rc = ensure(ctx, ctx->locate_qu, sizeof(long long) * (size_t)n_rows * (size_t)n_u))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->debug_q.p, q, sizeof(long long) * (size_t)n_rows * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    launch_stack_upsample(ctx->stream, ctx->debug_q.as<const long long>(), (size_t)n_rows, (int)n, U, ctx->locate_qu.as<long long>());
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out, ctx->locate_qu.p, sizeof(long long) * (size_t)n_rows * (size_t)n_u, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return TDOA_OK;
+}
+
+}  // extern "C"

@@ -2,7 +2,7 @@
 // the one place the kernels of stack_map_stats.hpp are launched (called at the end of the delay-table family's launch,
 // launch_locate_run, so a context's own step, the group's merged sum and the debug entries all get it), the download into the context
 // and tdoa_locate_last_stats.  With the setting off nothing here allocates, launches or copies.
-// Included by tdoa_mi355x.hip after stacked_api.inc and before locate_api.inc.
+// Included by tdoa_mi355x.hip before locate_api.inc and locate_run.inc.
 
 extern "C" {
 

@@ -1,8 +1,8 @@
 // stacked_api.inc -- stacked correlation, host side: the stacks' geometry (StackGeom: the one place their lengths and counts
 // are worked out), the stacks of a job, the finishing kernels' launches and downloads (shared by a context's own step,
 // step_products.inc, and the group's merged sum), tdoa_num_stacks, and finish_from_host: a merged sum uploaded and handed to
-// the stack's finish, the closure search or the delay-table search.
-// Included by tdoa_mi355x.hip before closure_api.inc, locate_api.inc and step_products.inc.
+// the stack's finish or to a search on the sums (search_from_host, stack_search.inc).
+// Included by tdoa_mi355x.hip after step_graph.inc and before step_products.inc.
 
 extern "C" {
 

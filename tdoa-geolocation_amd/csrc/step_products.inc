@@ -1,12 +1,8 @@
 // step_products.inc -- what a step (process_impl) can write besides its peak records: the correlation surfaces
 // (tdoa_process_lags), the K strongest peaks per pair-window (tdoa_process_peaks), the stacked surfaces of a block's windows
 // (tdoa_process_stacked), the same stacks taken along the best of 2H+1 lag slopes (tdoa_process_stacked_drift), the best
-// delay track through a stack's windows (tdoa_process_track), one consistent lag set per station triple of a stack
-// (tdoa_process_closure), a table of candidate positions scored on all pairs' stacks (tdoa_process_locate), the stations'
-// clock offsets from a block whose emitter is known (tdoa_process_sync), the best track of cells through the stacks of a
-// block on the delay-table search's maps (tdoa_process_locate_track), several emitters per stack found one after the other on
-// masked lags (tdoa_process_locate_multi), several emitters per block found as cell tracks on masked lags
-// (tdoa_process_locate_track_multi).  Every product
+// delay track through a stack's windows (tdoa_process_track), and a search on the stacks' sums (SearchProduct,
+// stack_search.inc: the closure, clock, clock-line and delay-table searches).  Every product
 // is a struct derived from StepProduct: the entry point fills it, process_impl calls its six hooks in this order (a product
 // overrides the ones it needs; process_impl without a product writes the peak records only):
 //   reserve   its buffers, after the step's grouping is fixed (batch_bound counts them as held, so a later call groups as
@@ -16,9 +12,10 @@
 //   refresh   data a call may change under the same key, sent every time
 //   enqueue   its kernels, after the step's decode -- unscoped launches, kernel nodes only: the step stays one chain
 //   download  its asynchronous copies out on ctx->stream
-// The products that search a stack's sums (drift, closure, locate, sync) derive from StackProduct and call its hooks from theirs.
+// StackDriftProduct and SearchProduct derive from StackProduct and call its hooks from theirs.
 // All of them read the K5 kernels' lag arrays in ctx->surf, pair-window i of the rank at i * n_lags.
-// Included by tdoa_mi355x.hip after step_graph.inc and stacked_api.inc.
+// Here: StepProduct, LagsProduct, PeaksProduct, StackProduct, StackDriftProduct, StackTrackProduct.
+// Included by tdoa_mi355x.hip after step_graph.inc and stacked_api.inc, before process_impl.
 
 namespace {
 
@@ -39,8 +36,7 @@ struct StepView {
 
 // the product of one step; the numbers are the first word a product appends to the graph key
 struct StepProduct {
-    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6, Locate = 7, Sync = 8,
-                SyncDrift = 9 /* sync_drift_api.inc */ };
+    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6, Locate = 7, Sync = 8, SyncDrift = 9 };
     virtual int reserve(const StepView &v) = 0;
     virtual void key(std::vector<uint64_t> *key) const = 0;
     virtual int upload(const StepView &) { return TDOA_OK; }
@@ -370,102 +366,6 @@ struct StackTrackProduct : StepProduct {
         if (total_host)
             HIPCHK(ctx, hipMemcpyAsync(total_host, ctx->stack_q.p, sizeof(int64_t) * n_sp * v.n_lags, hipMemcpyDeviceToHost, st));
         return TDOA_OK;
-    }
-};
-
-// ---- the closure search on the stacks' sums (stack_closure.hpp, closure_api.inc) ---------------------------------------
-// The stack whose sums Q are searched has no output of its own, so no finishing kernels (k = min_sep = 1 are never read).
-struct ClosureProduct : StackProduct {
-    int G = 0, sep = 1;                      // gate, min_separation
-    std::vector<int32_t> centre;             // [stations]: data, not part of the key
-    tdoa_closure *out_host = nullptr;        // [stack][triple]
-
-    ClosureGeom geom(const tdoa_ctx *ctx) const { return closure_geom((int)centre.size(), ctx->prm.max_lag, G, sep); }
-    int reserve(const StepView &v) override
-    {
-        if (int rc = StackProduct::reserve(v)) return rc;
-        if (ensure_closure(v.ctx, layout.n_stacks, geom(v.ctx))) return surfaces_nomem(v, "the closure search's candidates and records", 1.0);
-        return TDOA_OK;
-    }
-    void key(std::vector<uint64_t> *key) const override { key->insert(key->end(), {Closure, (uint64_t)m, (uint64_t)G, (uint64_t)sep}); }
-    int refresh(const StepView &v) override { return upload_closure_centre(v.ctx, centre); }
-    void enqueue(const StepView &v) const override
-    {
-        tdoa_ctx *ctx = v.ctx;
-        StackProduct::enqueue(v);
-        launch_closure(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, layout.n_stacks, v.P).roots, layout.n_stacks, geom(ctx));
-    }
-    int download(const StepView &v) const override { return download_closure(v.ctx, layout.n_stacks, geom(v.ctx), out_host); }
-};
-
-// ---- the delay-table family on the stacks' sums (locate_run.inc): tdoa_process_locate, tdoa_process_locate_multi, ---------
-// tdoa_process_locate_track and tdoa_process_locate_track_multi.  Its stack has no output of its own either.  A track spans a
-// block: L = the stacks per block, and the three blocks' tracks hold all their windows.
-struct LocateProduct : StackProduct {
-    LocateCall call;                         // the entry's arguments and outputs
-    int n_cells = 0, n_cols = 0;             // the shape of the context's table: in the key (the table itself is data)
-    bool clocked = false;                    // the context holds station clocks: in the key (another kernel; the clocks are data)
-    uint64_t stats = 0;                      // map statistics (map_stats_key): in the key (more kernels; the ranks are data), 0: off
-    int up = 1;                              // the upsampling factor (tdoa_locate_set_upsample): in the key (more kernels, another geometry)
-    std::vector<double> track_roots;         // refresh's host copy of sqrt(N_w) (lives until the call has synchronised)
-
-    LocateRun run(const tdoa_ctx *ctx) const { return locate_run(ctx, call, layout.n_stacks, layout.spb); }
-    int reserve(const StepView &v) override
-    {
-        if (int rc = StackProduct::reserve(v)) return rc;
-        return ensure_locate_run(v.ctx, run(v.ctx));
-    }
-    // everything the launches depend on: the rounds and the mask, the tracks' length (0: none) and step, whether the counts are
-    // produced (the centres are data)
-    void key(std::vector<uint64_t> *key) const override
-    {
-        const uint64_t L = call.tracks ? (uint64_t)layout.spb : 0, pairs = call.tracks && call.rounds;
-        key->insert(key->end(), {Locate, (uint64_t)m, L | (pairs << 32), (uint64_t)call.J, (uint64_t)call.K, (uint64_t)call.guard,
-                                 (uint64_t)call.sep, (uint64_t)n_cells | ((uint64_t)n_cols << 32), (uint64_t)clocked | ((uint64_t)(up - 1) << 8), stats});
-    }
-    int refresh(const StepView &v) override  // (every call: the debug and the group's calls write their own roots there)
-    {
-        if (!call.tracks) return TDOA_OK;
-        track_roots = block_track_roots(v.wpb);
-        return upload_locate_track_roots(v.ctx, track_roots);
-    }
-    void enqueue(const StepView &v) const override
-    {
-        tdoa_ctx *ctx = v.ctx;
-        StackProduct::enqueue(v);
-        launch_locate_run(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, layout.n_stacks, v.P).roots, run(ctx));
-    }
-    int download(const StepView &v) const override { return download_locate_run(v.ctx, run(v.ctx), call); }
-};
-
-// ---- the clock search on the stacks' sums (stack_sync.hpp, sync_api.inc) ------------------------------------------------
-// Its stack has no output of its own either.
-struct SyncProduct : StackProduct {
-    int S = 0, G = 0, R = 0;                 // stations, gate, rounds
-    std::vector<int32_t> in;                 // ref_delay and centre (sync_inputs): data, not part of the key
-    tdoa_sync *sync_host = nullptr;          // [stack]
-    int32_t *clock_host = nullptr;           // [stack][station]
-    int32_t *lags_host = nullptr;            // [stack][pair]
-    double *corr_host = nullptr;             // [stack][pair]
-
-    SyncGeom geom(const tdoa_ctx *ctx) const { return sync_geom(S, ctx->prm.max_lag, G, R); }
-    int reserve(const StepView &v) override
-    {
-        if (int rc = StackProduct::reserve(v)) return rc;
-        if (ensure_sync(v.ctx, layout.n_stacks, geom(v.ctx))) return surfaces_nomem(v, "the clock search's candidates and records", 1.0);
-        return TDOA_OK;
-    }
-    void key(std::vector<uint64_t> *key) const override { key->insert(key->end(), {Sync, (uint64_t)m, (uint64_t)G, (uint64_t)R}); }
-    int refresh(const StepView &v) override { return upload_sync_in(v.ctx, in); }
-    void enqueue(const StepView &v) const override
-    {
-        tdoa_ctx *ctx = v.ctx;
-        StackProduct::enqueue(v);
-        launch_sync(ctx, ctx->stack_q.as<const long long>(), stack_dev(ctx, layout.n_stacks, v.P).roots, layout.n_stacks, geom(ctx));
-    }
-    int download(const StepView &v) const override
-    {
-        return download_sync(v.ctx, layout.n_stacks, geom(v.ctx), sync_host, clock_host, lags_host, corr_host);
     }
 };
 

@@ -1,10 +1,11 @@
-// sync_api.inc -- the clock search, host side: its buffers, the kernels' launches (shared by a context's own step,
-// step_products.inc, the group's merged sum and tdoa_debug_sync_from_q).
-// Included by tdoa_mi355x.hip after locate_api.inc and locate_run.inc and before step_products.inc.
+// sync_api.inc -- the clock search (stack_sync.hpp), host side: the search as a StackSearch (stack_search.inc) -- its checks,
+// geometry, buffers, the one place its kernels are launched, its download -- and the search's three entries.
+// Included by tdoa_mi355x.hip after stack_search.inc and locate_api.inc (locate_overflows) and before sync_drift_api.inc,
+// which takes sync_inputs from here (declared in stack_search.inc).
 
-extern "C" {
+namespace {
 
-static SyncGeom sync_geom(int S, int max_lag, int gate, int rounds)
+SyncGeom sync_geom(int S, int max_lag, int gate, int rounds)
 {
     SyncGeom g;
     g.S = S;
@@ -18,18 +19,8 @@ static SyncGeom sync_geom(int S, int max_lag, int gate, int rounds)
     return g;
 }
 
-// the arguments the three sync entries share; they need no device
-static const char *check_sync_args(int gate, int rounds, const void *ref_delay, const void *sync)
-{
-    if (gate < 0 || gate > kSyncMaxGate) return "gate outside 0 .. 1023";
-    if (rounds < 0 || rounds > kSyncMaxRounds) return "rounds outside 0 .. 16";
-    if (!ref_delay) return "ref_delay is NULL";
-    if (!sync) return "sync_host is NULL";
-    return nullptr;
-}
-
-// ref_delay, then centre (NULL: all 0), kSyncMaxStations words each: what upload_sync_in sends
-static std::vector<int32_t> sync_inputs(const int32_t *ref_delay, const int32_t *centre, int S)
+// ref_delay, then centre (NULL: all 0), kSyncMaxStations words each: what the clock and the clock-line search upload
+std::vector<int32_t> sync_inputs(const int32_t *ref_delay, const int32_t *centre, int S)
 {
     std::vector<int32_t> in(2 * (size_t)kSyncMaxStations, 0);
     std::copy(ref_delay, ref_delay + S, in.begin());
@@ -37,89 +28,131 @@ static std::vector<int32_t> sync_inputs(const int32_t *ref_delay, const int32_t 
     return in;
 }
 
-// the buffers of the search for n_sets stacks: the inputs, the start's tiles' candidates, the records, clocks, lags and
-// correlations
-static int ensure_sync(tdoa_ctx *ctx, size_t n_sets, const SyncGeom &g)
+// the outputs of the three entries (all but sync may be NULL)
+struct SyncHost {
+    tdoa_sync *sync = nullptr;               // [set]
+    int32_t *clock = nullptr;                // [set][station]
+    int32_t *lags = nullptr;                 // [set][pair]
+    double *corr = nullptr;                  // [set][pair]
+};
+
+struct SyncSearch : StackSearch {
+    int G, R;                                // gate, rounds
+    const int32_t *ref_delay, *centre;       // [stations]; centre NULL: all 0
+    SyncHost o;
+    SyncGeom g;                              // bind: the geometry, the sets and the inputs as they are uploaded
+    size_t n_sets = 0;
+    std::vector<int32_t> in;
+
+    SyncSearch(int gate, int rounds, const int32_t *ref_delay, const int32_t *centre, const SyncHost &host)
+        : StackSearch("the clock search with TDOA_LAGS_GO", "the clock search's candidates and records"), G(gate), R(rounds),
+          ref_delay(ref_delay), centre(centre), o(host)
+    {
+    }
+    const char *check_args() const override
+    {
+        if (G < 0 || G > kSyncMaxGate) return "gate outside 0 .. 1023";
+        if (R < 0 || R > kSyncMaxRounds) return "rounds outside 0 .. 16";
+        if (!ref_delay) return "ref_delay is NULL";
+        if (!o.sync) return "sync_host is NULL";
+        return nullptr;
+    }
+    // the lag mode, the captures, the station count, the overflow bound
+    int check_state(const tdoa_ctx *ctx, int windows_per_stack, const char **what) const override
+    {
+        if (ctx->prm.lag_mode == TDOA_LAGS_GO) return refuse_with(what, TDOA_ERR_UNSUPPORTED, go_what);
+        if (ctx->caps.empty()) return refuse_with(what, TDOA_ERR_STATE, "captures missing");
+        const int S = (int)ctx->caps.size();
+        if (S < 2 || S > kSyncMaxStations) return refuse_with(what, TDOA_ERR_UNSUPPORTED, "the clock search needs 2 .. 64 stations");
+        int wpb = 0;
+        if (tdoa_num_windows(ctx, &wpb, nullptr)) return refuse_with(what, TDOA_ERR_STATE, "captures missing or too small");
+        if (locate_overflows(S * (S - 1) / 2, stack_geom(wpb, windows_per_stack).mm))
+            return refuse_with(what, TDOA_ERR_UNSUPPORTED, "pairs x stack length > 2^17: the objective could overflow");
+        if (3ll * wpb > kLocateMaxSets) return refuse_with(what, TDOA_ERR_UNSUPPORTED, "more than 65535 stacks");
+        return TDOA_OK;
+    }
+    int check_sets(const tdoa_ctx *, const int64_t *q, int n_sets, int, int n_stations, int n_w, const char **what) const override
+    {
+        if (!q || n_sets < 1 || n_sets > kLocateMaxSets || n_w < 1 || n_stations < 2 || n_stations > kSyncMaxStations)
+            return refuse_with(what, TDOA_ERR_INVALID, "q is NULL, n_sets outside 1 .. 65535, n_w < 1 or n_stations outside 2 .. 64");
+        if (locate_overflows(n_stations * (n_stations - 1) / 2, n_w))
+            return refuse_with(what, TDOA_ERR_UNSUPPORTED, "pairs x n_w > 2^17: the objective could overflow");
+        return TDOA_OK;
+    }
+    void bind(const tdoa_ctx *ctx, const SearchShape &sh) override
+    {
+        g = sync_geom(sh.S, ctx->prm.max_lag, G, R);
+        n_sets = (size_t)sh.n_sets;
+        in = sync_inputs(ref_delay, centre, sh.S);
+    }
+    void key(std::vector<uint64_t> *key, int m) const override
+    {
+        key->insert(key->end(), {StepProduct::Sync, (uint64_t)m, (uint64_t)G, (uint64_t)R});
+    }
+    // the inputs, the start's tiles' candidates, the records, clocks, lags and correlations
+    int reserve(tdoa_ctx *ctx) const override
+    {
+        int rc;
+        if ((rc = ensure(ctx, ctx->sync_in, sizeof(int32_t) * 2 * kSyncMaxStations))) return rc;
+        if ((rc = ensure(ctx, ctx->sync_part, sizeof(ClosureCand) * std::max<size_t>(n_sets * g.tiles, 1)))) return rc;
+        if ((rc = ensure(ctx, ctx->sync_out, sizeof(SyncOut) * n_sets))) return rc;
+        if ((rc = ensure(ctx, ctx->sync_clock, sizeof(int32_t) * n_sets * g.S))) return rc;
+        if ((rc = ensure(ctx, ctx->sync_lags, sizeof(int32_t) * n_sets * g.P))) return rc;
+        return ensure(ctx, ctx->sync_corr, sizeof(double) * n_sets * g.P);
+    }
+    // the delays and the centres: a call that changes only them replays the same graph
+    int refresh(tdoa_ctx *ctx) const override
+    {
+        HIPCHK(ctx, hipMemcpyAsync(ctx->sync_in.p, in.data(), sizeof(int32_t) * in.size(), hipMemcpyHostToDevice, ctx->stream));
+        return TDOA_OK;
+    }
+    // Q [n_sets][P][n] -> the records in ctx->sync_out, the clocks, lags and correlations: the one place the search is launched
+    void launch(tdoa_ctx *ctx, const long long *Q, const double *roots) const override
+    {
+        hipStream_t st = ctx->stream;
+        auto *d_in = ctx->sync_in.as<const int32_t>();
+        auto *part = ctx->sync_part.as<ClosureCand>();
+        if (g.tiles > 0)
+            hipLaunchKernelGGL(k_sync_start, dim3((unsigned)g.tiles, (unsigned)n_sets), dim3(kSyncThreads), 0, st, Q, g, d_in, part);
+        hipLaunchKernelGGL(k_sync_steps, dim3((unsigned)n_sets), dim3(kSyncThreads), 0, st, Q, g, d_in, roots,
+                           static_cast<const ClosureCand *>(part), ctx->sync_out.as<SyncOut>(), ctx->sync_clock.as<int32_t>(),
+                           ctx->sync_lags.as<int32_t>(), ctx->sync_corr.as<double>());
+    }
+    int download(tdoa_ctx *ctx) const override
+    {
+        hipStream_t st = ctx->stream;
+        HIPCHK(ctx, hipMemcpyAsync(o.sync, ctx->sync_out.p, sizeof(SyncOut) * n_sets, hipMemcpyDeviceToHost, st));
+        if (o.clock) HIPCHK(ctx, hipMemcpyAsync(o.clock, ctx->sync_clock.p, sizeof(int32_t) * n_sets * g.S, hipMemcpyDeviceToHost, st));
+        if (o.lags) HIPCHK(ctx, hipMemcpyAsync(o.lags, ctx->sync_lags.p, sizeof(int32_t) * n_sets * g.P, hipMemcpyDeviceToHost, st));
+        if (o.corr) HIPCHK(ctx, hipMemcpyAsync(o.corr, ctx->sync_corr.p, sizeof(double) * n_sets * g.P, hipMemcpyDeviceToHost, st));
+        return TDOA_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int tdoa_process_sync(tdoa_ctx *ctx, int windows_per_stack, int gate, int rounds, const int32_t *ref_delay, const int32_t *centre,
+                      tdoa_sync *sync_host, int32_t *clock_host, int32_t *lags_host, double *corr_host)
 {
-    int rc;
-    if ((rc = ensure(ctx, ctx->sync_in, sizeof(int32_t) * 2 * kSyncMaxStations))) return rc;
-    if ((rc = ensure(ctx, ctx->sync_part, sizeof(ClosureCand) * std::max<size_t>(n_sets * g.tiles, 1)))) return rc;
-    if ((rc = ensure(ctx, ctx->sync_out, sizeof(SyncOut) * n_sets))) return rc;
-    if ((rc = ensure(ctx, ctx->sync_clock, sizeof(int32_t) * n_sets * g.S))) return rc;
-    if ((rc = ensure(ctx, ctx->sync_lags, sizeof(int32_t) * n_sets * g.P))) return rc;
-    return ensure(ctx, ctx->sync_corr, sizeof(double) * n_sets * g.P);
+    SyncSearch s(gate, rounds, ref_delay, centre, SyncHost{sync_host, clock_host, lags_host, corr_host});
+    return process_search(ctx, windows_per_stack, s);
 }
 
-// the delays and the centres to the device, before the launch (asynchronous on ctx->stream; `in` lives until the caller has
-// synchronised).  Data, not part of a step graph's key: a call that changes only them replays the same graph.
-static int upload_sync_in(tdoa_ctx *ctx, const std::vector<int32_t> &in)
+int tdoa_group_process_sync(tdoa_group *g, int windows_per_stack, int gate, int rounds, const int32_t *ref_delay, const int32_t *centre,
+                            tdoa_sync *sync_host, int32_t *clock_host, int32_t *lags_host, double *corr_host)
 {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->sync_in.p, in.data(), sizeof(int32_t) * in.size(), hipMemcpyHostToDevice, ctx->stream));
-    return TDOA_OK;
+    SyncSearch s(gate, rounds, ref_delay, centre, SyncHost{sync_host, clock_host, lags_host, corr_host});
+    return group_process_search(g, windows_per_stack, s);
 }
 
-// Q [n_sets][P][n] -> the records in ctx->sync_out, the clocks, lags and correlations: the one place the search is launched.
-// Kernel launches only (the step graph captures them).
-static void launch_sync(tdoa_ctx *ctx, const long long *Q, const double *roots, int n_sets, const SyncGeom &g)
+int tdoa_debug_sync_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int gate, int rounds,
+                           const int32_t *ref_delay, const int32_t *centre, tdoa_sync *sync, int32_t *clock, int32_t *lags,
+                           double *corr)
 {
-    hipStream_t st = ctx->stream;
-    auto *in = ctx->sync_in.as<const int32_t>();
-    auto *part = ctx->sync_part.as<ClosureCand>();
-    if (g.tiles > 0)
-        hipLaunchKernelGGL(k_sync_start, dim3((unsigned)g.tiles, (unsigned)n_sets), dim3(kSyncThreads), 0, st, Q, g, in, part);
-    hipLaunchKernelGGL(k_sync_steps, dim3((unsigned)n_sets), dim3(kSyncThreads), 0, st, Q, g, in, roots,
-                       static_cast<const ClosureCand *>(part), ctx->sync_out.as<SyncOut>(), ctx->sync_clock.as<int32_t>(),
-                       ctx->sync_lags.as<int32_t>(), ctx->sync_corr.as<double>());
-}
-
-// the outputs to the host (all but sync may be NULL); asynchronous on ctx->stream
-static int download_sync(tdoa_ctx *ctx, size_t n_sets, const SyncGeom &g, tdoa_sync *sync, int32_t *clock, int32_t *lags, double *corr)
-{
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(sync, ctx->sync_out.p, sizeof(SyncOut) * n_sets, hipMemcpyDeviceToHost, st));
-    if (clock) HIPCHK(ctx, hipMemcpyAsync(clock, ctx->sync_clock.p, sizeof(int32_t) * n_sets * g.S, hipMemcpyDeviceToHost, st));
-    if (lags) HIPCHK(ctx, hipMemcpyAsync(lags, ctx->sync_lags.p, sizeof(int32_t) * n_sets * g.P, hipMemcpyDeviceToHost, st));
-    if (corr) HIPCHK(ctx, hipMemcpyAsync(corr, ctx->sync_corr.p, sizeof(double) * n_sets * g.P, hipMemcpyDeviceToHost, st));
-    return TDOA_OK;
-}
-
-// the clock search on a group's merged sum (finish_from_host, stacked_api.inc)
-static int sync_from_host(tdoa_ctx *ctx, const int64_t *q_sum, int windows_per_stack, int gate, int rounds, const int32_t *ref_delay,
-                          const int32_t *centre, tdoa_sync *sync, int32_t *clock, int32_t *lags, double *corr)
-{
-    const int S = (int)ctx->caps.size();
-    const SyncGeom g = sync_geom(S, ctx->prm.max_lag, gate, rounds);
-    const std::vector<int32_t> in = sync_inputs(ref_delay, centre, S);
-    return finish_from_host(
-        ctx, q_sum, windows_per_stack,
-        [&](int n_stacks, const double *roots) -> int {
-            int rc;
-            if ((rc = ensure_sync(ctx, n_stacks, g))) return rc;
-            if ((rc = upload_sync_in(ctx, in))) return rc;
-            launch_sync(ctx, ctx->stack_q.as<const long long>(), roots, n_stacks, g);
-            return TDOA_OK;
-        },
-        [&](int n_stacks) { return download_sync(ctx, n_stacks, g, sync, clock, lags, corr); });
-}
-
-// what tdoa_process_sync and the group's call refuse once the arguments are in range: the lag mode, the captures, the
-// station count, the overflow bound.  *what receives the message.
-static int check_sync_state(const tdoa_ctx *ctx, int windows_per_stack, const char **what)
-{
-    const auto refuse = [&](int status, const char *why) {
-        *what = why;
-        return status;
-    };
-    if (ctx->prm.lag_mode == TDOA_LAGS_GO) return refuse(TDOA_ERR_UNSUPPORTED, "the clock search with TDOA_LAGS_GO");
-    if (ctx->caps.empty()) return refuse(TDOA_ERR_STATE, "captures missing");
-    const int S = (int)ctx->caps.size();
-    if (S < 2 || S > kSyncMaxStations) return refuse(TDOA_ERR_UNSUPPORTED, "the clock search needs 2 .. 64 stations");
-    int wpb = 0;
-    if (tdoa_num_windows(ctx, &wpb, nullptr)) return refuse(TDOA_ERR_STATE, "captures missing or too small");
-    if (locate_overflows(S * (S - 1) / 2, stack_geom(wpb, windows_per_stack).mm))
-        return refuse(TDOA_ERR_UNSUPPORTED, "pairs x stack length > 2^17: the objective could overflow");
-    if (3ll * wpb > kLocateMaxSets) return refuse(TDOA_ERR_UNSUPPORTED, "more than 65535 stacks");
-    return TDOA_OK;
+    SyncSearch s(gate, rounds, ref_delay, centre, SyncHost{sync, clock, lags, corr});
+    return debug_search_from_q(ctx, q, n_sets, 0, n_stations, n_w, s);
 }
 
 }  // extern "C"

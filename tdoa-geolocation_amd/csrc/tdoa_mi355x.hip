@@ -200,7 +200,7 @@ struct tdoa_ctx {
     // [stack][pair]
     DevBuf sline_in, sline_tab, sline_roots, sline_cur, sline_k, sline_h, sline_part, sline_moved, sline_start, sline_out, sline_clock,
         sline_rate, sline_rows, sline_lags, sline_corr;
-    // tdoa_debug_closure_from_q, tdoa_debug_locate_from_q and tdoa_debug_sync_from_q: the caller's words and sqrt(n_w) per set
+    // the tdoa_debug_*_from_q entries (debug_search_from_q): the caller's words and sqrt(n_w) per set
     DevBuf debug_q, debug_roots;
     int locate_cells = 0, locate_cols = 0, locate_stations = 0;
     int clock_stacks = 0, clock_stations = 0;
@@ -408,11 +408,6 @@ int check_selection(tdoa_ctx *ctx, int k, int min_separation, const void *out)
 #include "fm_pair.inc"
 #include "step_graph.inc"
 #include "stacked_api.inc"
-#include "closure_api.inc"
-#include "map_stats_api.inc"
-#include "locate_api.inc"
-#include "locate_run.inc"
-#include "sync_api.inc"
 #include "step_products.inc"
 
 // ===========================================================================
@@ -1141,90 +1136,6 @@ int tdoa_process_track(tdoa_ctx *ctx, int windows_per_stack, int max_step, tdoa_
     return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
 }
 
-int tdoa_process_closure(tdoa_ctx *ctx, int windows_per_stack, int gate, int min_separation, const int32_t *centre,
-                         tdoa_closure *closure_host)
-{
-    if (int rc = refuse_stacked(ctx, windows_per_stack, check_closure_args(gate, min_separation, closure_host),
-                                "the closure search with TDOA_LAGS_GO", true))
-        return rc;
-    const int S = (int)ctx->caps.size();
-    if (S < 3 || S > kClosureMaxStations) return fail(ctx, TDOA_ERR_UNSUPPORTED, "the closure search needs 3 .. 64 stations");
-    ClosureProduct prod;
-    fill_stack(&prod, windows_per_stack);
-    prod.G = gate;
-    prod.sep = min_separation;
-    prod.centre = closure_centres(centre, S);
-    prod.out_host = closure_host;
-    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
-}
-
-// The four entries of the delay-table family (locate_run.inc): what they refuse -- the arguments, then the station count, the
-// table, the overflow bounds and the track's length, which the group's call shares -- and the product.
-static int process_locate_call(tdoa_ctx *ctx, int windows_per_stack, const LocateCall &call)
-{
-    if (int rc = refuse_stacked(ctx, windows_per_stack, check_locate_call(call), "the delay-table search with TDOA_LAGS_GO", true)) return rc;
-    const char *what = nullptr;
-    if (const int rc = check_locate_state(ctx, windows_per_stack, call.tracks, &what)) return fail(ctx, rc, what);
-    LocateProduct prod;
-    fill_stack(&prod, windows_per_stack);
-    prod.call = call;
-    prod.n_cells = ctx->locate_cells;
-    prod.n_cols = ctx->locate_cols;
-    prod.clocked = ctx->clock_stacks != 0;
-    prod.stats = map_stats_key(ctx);
-    prod.up = ctx->locate_up;
-    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
-}
-
-int tdoa_process_locate(tdoa_ctx *ctx, int windows_per_stack, int min_separation, tdoa_location *loc_host, int32_t *lags_host,
-                        double *corr_host, int64_t *map_host)
-{
-    return process_locate_call(ctx, windows_per_stack, locate_search_call(false, 1, 0, min_separation, loc_host, lags_host, corr_host, map_host));
-}
-
-int tdoa_process_locate_track(tdoa_ctx *ctx, int windows_per_stack, int max_step, int min_separation, tdoa_cell_track *track_host,
-                              int32_t *cells_host, int64_t *own_host, int32_t *lags_host, double *corr_host, int64_t *total_host)
-{
-    return process_locate_call(ctx, windows_per_stack, locate_track_call(false, max_step, 1, 0, min_separation, track_host, cells_host, own_host,
-                                                                         nullptr, lags_host, corr_host, total_host));
-}
-
-int tdoa_process_locate_multi(tdoa_ctx *ctx, int windows_per_stack, int n_emitters, int guard, int min_separation, tdoa_location *loc_host,
-                              int32_t *lags_host, double *corr_host, int64_t *map_host)
-{
-    return process_locate_call(ctx, windows_per_stack,
-                               locate_search_call(true, n_emitters, guard, min_separation, loc_host, lags_host, corr_host, map_host));
-}
-
-int tdoa_process_locate_track_multi(tdoa_ctx *ctx, int windows_per_stack, int max_step, int n_emitters, int guard, int min_separation,
-                                    tdoa_cell_track *track_host, int32_t *cells_host, int64_t *own_host, int32_t *pairs_host,
-                                    int32_t *lags_host, double *corr_host, int64_t *total_host)
-{
-    return process_locate_call(ctx, windows_per_stack, locate_track_call(true, max_step, n_emitters, guard, min_separation, track_host, cells_host,
-                                                                         own_host, pairs_host, lags_host, corr_host, total_host));
-}
-
-int tdoa_process_sync(tdoa_ctx *ctx, int windows_per_stack, int gate, int rounds, const int32_t *ref_delay, const int32_t *centre,
-                      tdoa_sync *sync_host, int32_t *clock_host, int32_t *lags_host, double *corr_host)
-{
-    if (int rc = refuse_stacked(ctx, windows_per_stack, check_sync_args(gate, rounds, ref_delay, sync_host),
-                                "the clock search with TDOA_LAGS_GO", true))
-        return rc;
-    const char *what = nullptr;              // (the station count, the overflow bound: shared with the group's call)
-    if (const int rc = check_sync_state(ctx, windows_per_stack, &what)) return fail(ctx, rc, what);
-    SyncProduct prod;
-    fill_stack(&prod, windows_per_stack);
-    prod.S = (int)ctx->caps.size();
-    prod.G = gate;
-    prod.R = rounds;
-    prod.in = sync_inputs(ref_delay, centre, prod.S);
-    prod.sync_host = sync_host;
-    prod.clock_host = clock_host;
-    prod.lags_host = lags_host;
-    prod.corr_host = corr_host;
-    return process_impl(ctx, 0, 1, nullptr, nullptr, nullptr, 0.0, &prod);
-}
-
 // fast_analyzer.go:139-155 and collector.go:224 from the exact integer sums, in the reference's expression order
 static void finalize_quality(const QualAcc &q, long long n_samples, tdoa_window_quality *out)
 {
@@ -1392,4 +1303,12 @@ int tdoa_solve_surface(const double *stations_lle, int n_stations, const double 
 #include "debug_api.inc"
 #include "exact_reference_api.inc"
 #include "group_api.inc"
+// The searches on the stacks' sums.  stack_search.inc's drivers call process_impl above and the group's helpers, which is why
+// it and the searches' files come last; a search's file needs nothing of another's but what its header names.
+#include "stack_search.inc"
+#include "closure_api.inc"
+#include "map_stats_api.inc"
+#include "locate_api.inc"
+#include "locate_run.inc"
+#include "sync_api.inc"
 #include "sync_drift_api.inc"
