@@ -448,6 +448,46 @@ func (g *gpuCorrelator) ProcessSync(windowsPerStack, gate, rounds int, refDelay,
 	return sync, clock, lags, corr, nil
 }
 
+// SyncFine is what ProcessSyncFine returns: the coarse stage's outputs exactly as ProcessSync's (Sync, Clock in samples, Lags,
+// Corr) and the refinement's: one more record per stack, Clock16 [stack][station] in units of 1/16 sample (what LocateSetClock
+// takes), FineLags [stack][pair] in units of 1/U sample and FineCorr, the signed value of the upsampled word there.
+type SyncFine struct {
+	Sync, Fine  []C.tdoa_sync
+	Clock, Lags []int32
+	Corr        []float64
+	Clock16     []int32
+	FineLags    []int32
+	FineCorr    []float64
+}
+
+func newSyncFine(total, stations, pairs int) *SyncFine {
+	return &SyncFine{Sync: make([]C.tdoa_sync, total), Fine: make([]C.tdoa_sync, total), Clock: make([]int32, total*stations),
+		Lags: make([]int32, total*pairs), Corr: make([]float64, total*pairs), Clock16: make([]int32, total*stations),
+		FineLags: make([]int32, total*pairs), FineCorr: make([]float64, total*pairs)}
+}
+
+// ProcessSyncFine is the fine clock search (the header's "fine clock search"): ProcessSync's whole-lag search, then fineRounds
+// sweeps that move every station's clock by up to u fine lags of 1/u sample (u one of 2, 4, 8, 16) on the words of the
+// surfaces upsampled as LocateSetUpsample defines them, evaluated from Q without materialising them.
+func (g *gpuCorrelator) ProcessSyncFine(windowsPerStack, gate, rounds, u, fineRounds int, refDelay, centre []int32) (*SyncFine, error) {
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs, stations := int(C.tdoa_num_pairs(g.ctx)), len(refDelay)
+	if int(total)*pairs == 0 || stations*(stations-1)/2 != pairs {
+		return nil, fmt.Errorf("tdoa_process_sync_fine: no stacks, fewer than two stations, or not one delay per station")
+	}
+	o := newSyncFine(int(total), stations, pairs)
+	if rc := C.tdoa_process_sync_fine(g.ctx, C.int(windowsPerStack), C.int(gate), C.int(rounds), C.int(u), C.int(fineRounds), tablePtr(refDelay),
+		centrePtr(centre), &o.Sync[0], (*C.int32_t)(unsafe.Pointer(&o.Clock[0])), (*C.int32_t)(unsafe.Pointer(&o.Lags[0])),
+		(*C.double)(unsafe.Pointer(&o.Corr[0])), &o.Fine[0], (*C.int32_t)(unsafe.Pointer(&o.Clock16[0])),
+		(*C.int32_t)(unsafe.Pointer(&o.FineLags[0])), (*C.double)(unsafe.Pointer(&o.FineCorr[0]))); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_process_sync_fine: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return o, nil
+}
+
 // SyncLines is what ProcessSyncDrift returns: one record, the clocks (samples) and the rates per block ([3][station]); per
 // stack the clock rows in units of 1/16 sample ([stack][station], what LocateSetClock takes for that block) and per stack and
 // pair the lag along the line and the signed correlation of that stack there.
@@ -774,6 +814,28 @@ func (g *Group) ProcessSync(windowsPerStack, gate, rounds int, refDelay, centre 
 		return nil, nil, nil, nil, fmt.Errorf("tdoa_group_process_sync: %s", C.GoString(C.tdoa_group_last_error(g.g)))
 	}
 	return sync, clock, lags, corr, nil
+}
+
+// ProcessSyncFine is gpuCorrelator.ProcessSyncFine over the group: the members' fixed-point partial sums are added on the host
+// and searched on member 0, coarse stage and refinement, the same bytes one context returns.
+func (g *Group) ProcessSyncFine(windowsPerStack, gate, rounds, u, fineRounds int, refDelay, centre []int32) (*SyncFine, error) {
+	m := C.tdoa_group_member(g.g, 0)
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(m, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs, stations := int(C.tdoa_num_pairs(m)), len(refDelay)
+	if int(total)*pairs == 0 || stations*(stations-1)/2 != pairs {
+		return nil, fmt.Errorf("tdoa_group_process_sync_fine: no stacks, fewer than two stations, or not one delay per station")
+	}
+	o := newSyncFine(int(total), stations, pairs)
+	if rc := C.tdoa_group_process_sync_fine(g.g, C.int(windowsPerStack), C.int(gate), C.int(rounds), C.int(u), C.int(fineRounds), tablePtr(refDelay),
+		centrePtr(centre), &o.Sync[0], (*C.int32_t)(unsafe.Pointer(&o.Clock[0])), (*C.int32_t)(unsafe.Pointer(&o.Lags[0])),
+		(*C.double)(unsafe.Pointer(&o.Corr[0])), &o.Fine[0], (*C.int32_t)(unsafe.Pointer(&o.Clock16[0])),
+		(*C.int32_t)(unsafe.Pointer(&o.FineLags[0])), (*C.double)(unsafe.Pointer(&o.FineCorr[0]))); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_group_process_sync_fine: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return o, nil
 }
 
 // ProcessSyncDrift is gpuCorrelator.ProcessSyncDrift over the group: the members' fixed-point partial sums are added on the

@@ -584,6 +584,53 @@ int tdoa_debug_sync_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_st
                            const int32_t *ref_delay, const int32_t *centre, tdoa_sync *sync, int32_t *clock, int32_t *lags,
                            double *corr);
 
+/* Fine clock search: the clock search's clocks refined to 1/U sample.  tdoa_process_sync works on whole lags: its clocks are up
+ * to half a sample off, and it rounds e_ij to whole lags before it searches.  tdoa_locate_set_upsample scores cells on surfaces
+ * of 1/U sample and tdoa_locate_set_clock takes clocks in 1/16 sample, so the refinement gives the locate clocks on its own grid.
+ * U is one of 2, 4, 8, 16.  Rf = fine_rounds, 0 <= Rf <= 16.
+ *   Coarse stage.  Exactly tdoa_process_sync(windows_per_stack, gate, rounds, ref_delay, centre, ...): sync_host, clock_host,
+ *     lags_host and corr_host receive that call's bytes, and k are its clocks.
+ *   The fine word.  n = 2 max_lag - 1.  A fine lag lam, in 1/U sample, is inside when |lam| <= (max_lag - 1) U.  Its word is
+ *     Q_U[lam + (max_lag - 1) U] of the pair's row, Q_U exactly as tdoa_locate_set_upsample defines it (the committed taps, Q
+ *     outside the row counting 0, phase 0 the word itself).  M_p(lam) is the word's magnitude.  An outside lag adds 0 and is not
+ *     counted.  No Q_U is materialised: the words that are needed are evaluated from Q.
+ *   The pair delays.  e^U_ij = sgn(d) * ((2|d| U + 16) div 32) with d = ref_delay[j] - ref_delay[i], taken in 64 bits: the
+ *     upsampled locate's lag rule, so clock and locate agree on the grid.
+ *   The search.  kappa_s = U k_s + y_s in 1/U sample, |y_s| <= U, y_0 = 0.  F_U(kappa) = sum over i < j of
+ *     M_ij(e^U_ij + kappa_j - kappa_i).  start_q = F_U(U k).  Rf Gauss-Seidel sweeps over stations 1 .. S-1: station s takes the y
+ *     of the largest sum over i != s of M with the others where they stand.  Candidates compete in the order
+ *     rank(y) = 2|y| - (y > 0); the first of equal maxima wins.  The window stays centred on U k_s in every sweep, so the
+ *     standing value is always a candidate and F_U never decreases.
+ *   Outputs per stack.  fine_host is a second tdoa_sync record: moved is that of the last fine sweep (0 with Rf = 0), pairs_in
+ *     the pairs inside at the final kappa, score_q = F_U(kappa), start_q, and score on the stack's scale.
+ *     clock16_host[s] = kappa_s * (16 / U): the row tdoa_locate_set_clock takes.  fine_lags_host[p] = e^U + kappa_j - kappa_i
+ *     in 1/U sample; fine_corr_host[p] the signed value of the word there; 0 and 0.0 for a pair outside.  If the coarse record
+ *     is the zero record, or the final F_U is 0, every fine output is zero.  With Rf = 0, clock16 = 16 * clock.
+ * The call does not read the context's tdoa_locate_set_upsample setting: its U is its own argument.  One more kernel behind
+ * the clock search's in the step graph, one workgroup per stack; (windows_per_stack, gate, rounds, U, fine_rounds) are part of
+ * the graph's key, ref_delay and centre stay data.  tdoa_group_process_sync_fine is the group form, same bytes.
+ * TDOA_ERR_INVALID: what tdoa_process_sync refuses, U not in {2, 4, 8, 16}, fine_rounds < 0 or > 16, a NULL fine_host (all
+ * checked before anything needs a device), |centre[s]| + gate + 1 >= 2^27 (the clock in 1/16 sample must fit int32).
+ * TDOA_ERR_UNSUPPORTED: what tdoa_process_sync refuses, and the upsampled locate's tightened overflow bound,
+ * 4 * P * (stack length in use) > 2^17. */
+int tdoa_process_sync_fine(tdoa_ctx *ctx, int windows_per_stack, int gate /* G */, int rounds /* R */, int U, int fine_rounds /* Rf */,
+                           const int32_t *ref_delay /* [n_stations] */, const int32_t *centre /* [n_stations] or NULL */,
+                           tdoa_sync *sync_host      /* [n_stacks_total], required: tdoa_process_sync's */,
+                           int32_t   *clock_host     /* [n_stacks_total][n_stations]: tdoa_process_sync's; may be NULL */,
+                           int32_t   *lags_host      /* [n_stacks_total][n_pairs]: tdoa_process_sync's; may be NULL */,
+                           double    *corr_host      /* same shape: tdoa_process_sync's; may be NULL */,
+                           tdoa_sync *fine_host      /* [n_stacks_total], required */,
+                           int32_t   *clock16_host   /* [n_stacks_total][n_stations]: kappa_s * (16 / U), 1/16 sample; may be NULL */,
+                           int32_t   *fine_lags_host /* [n_stacks_total][n_pairs]: 1/U sample, 0 where outside; may be NULL */,
+                           double    *fine_corr_host /* same shape: the signed word * 2^-32 / sqrt(n_w) there; may be NULL */);
+
+/* tests only: the same kernels on the caller's words, as tdoa_debug_sync_from_q.  Precondition: |q| <= 2^60 div P.
+ * TDOA_ERR_INVALID: what tdoa_process_sync_fine and tdoa_debug_sync_from_q refuse.  TDOA_ERR_UNSUPPORTED: 4 * P * n_w > 2^17. */
+int tdoa_debug_sync_fine_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int gate, int rounds, int U,
+                                int fine_rounds, const int32_t *ref_delay, const int32_t *centre, tdoa_sync *sync, int32_t *clock,
+                                int32_t *lags, double *corr, tdoa_sync *fine, int32_t *clock16, int32_t *fine_lags,
+                                double *fine_corr);
+
 /* Clock lines: the stations' clock offsets and rates from a reference block.  tdoa_process_sync finds one offset per station
  * per stack and assumes the clocks stand still inside that stack; free-running receivers drift by lags per second, so the
  * whole-block stack smears along the drift and a one-window stack is where the noise wins.  This search takes the S - 1 clock
@@ -1131,6 +1178,13 @@ int tdoa_group_locate_set_clock(tdoa_group *g, const int32_t *clock, int n_stack
 int tdoa_group_process_sync(tdoa_group *g, int windows_per_stack, int gate, int rounds, const int32_t *ref_delay,
                             const int32_t *centre, tdoa_sync *sync_host, int32_t *clock_host, int32_t *lags_host,
                             double *corr_host);
+
+/* tdoa_process_sync_fine over the members: the merged sum is searched on member 0, coarse stage and refinement, and the group
+ * returns a single context's bytes.  Errors as there and as tdoa_group_process_sync. */
+int tdoa_group_process_sync_fine(tdoa_group *g, int windows_per_stack, int gate, int rounds, int U, int fine_rounds,
+                                 const int32_t *ref_delay, const int32_t *centre, tdoa_sync *sync_host, int32_t *clock_host,
+                                 int32_t *lags_host, double *corr_host, tdoa_sync *fine_host, int32_t *clock16_host,
+                                 int32_t *fine_lags_host, double *fine_corr_host);
 
 /* tdoa_process_sync_drift over the members: they sum their windows as in tdoa_group_process_stacked, the host adds the
  * partials, and member 0 runs the search on the merged Q.  F is a function of the complete stacked Q only, so the members'

@@ -32,9 +32,12 @@ clocks, rates, rows, lags and correlations downloaded (the stack's accumulation,
 legs on S stations (default 3; 8 gives 56 triples).  Every `--locate-upsample U` adds a leg per `--locate` grid:
 tdoa_process_locate(M, 1) with tdoa_locate_set_upsample(U) (name ..._upU_ms): the two scalings and the upsampler come in front
 of the search's launches, which then gather from surfaces U times as long; every other leg runs with U = 1.  `--max-lag N`
-(default 20000) sets the context's search range: one-window stacks (`--stack 1`) at U = 16 want 512.
+(default 20000) sets the context's search range: one-window stacks (`--stack 1`) at U = 16 want 512.  Every
+`--sync-fine G/U[/R[/RF]]` adds a leg: tdoa_process_sync_fine(M, G, R, U, RF) (R and RF default to 2; M from `--stack`) against
+the same delays with all eight outputs downloaded -- the clock search's launches and one more kernel, one workgroup per stack --
+and, when M is not 0, the leg process_sync_G_R_stackM_ms: tdoa_process_sync(M, G, R), what the fine leg is compared with.
 usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--stack M] [--drift H/D]... [--track J]...
-[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]... [--locate-upsample U]... [--max-lag N]"""
+[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]... [--locate-upsample U]... [--sync-fine G/U[/R[/RF]]]... [--max-lag N]"""
 import json
 import os
 import sys
@@ -64,7 +67,7 @@ def timed(fn, steps):
 
 
 def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=(), locate_tracks=(), stack=0, emitters=(),
-         track_emitters=(), map_stats=None, sync_drifts=(), upsamples=(), max_lag=20000):
+         track_emitters=(), map_stats=None, sync_drifts=(), upsamples=(), max_lag=20000, sync_fines=()):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=max_lag)
     for s in range(stations):
         c.synth_capture(s, 66_666_666, ST[s % 3], TX, 0x5D0A0000 + s)
@@ -113,6 +116,10 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
         legs["process_sync_%d_%d_ms" % (G, R)] = lambda G=G, R=R: c.process_sync(ref, 0, G, R)
     for G, H, D, R in sync_drifts:
         legs["process_sync_drift_%d_%d_%d_%d_ms" % (G, H, D, R)] = lambda G=G, H=H, D=D, R=R: c.process_sync_drift(ref, stack, G, H, D, R)
+    for G, U, R, Rf in sync_fines:
+        if stack != 0:
+            legs["process_sync_%d_%d_stack%d_ms" % (G, R, stack)] = lambda G=G, R=R: c.process_sync(ref, stack, G, R)
+        legs["process_sync_fine_%d_%d_%d_%d_ms" % (G, U, R, Rf)] = lambda G=G, U=U, R=R, Rf=Rf: c.process_sync_fine(ref, stack, G, R, U, Rf)
     times = {name: [] for name in legs}
     for _ in range(rounds):
         for name, fn in legs.items():
@@ -189,6 +196,12 @@ if __name__ == "__main__":
         rows, _, cols = args[i + 1].partition("x")
         locates.append((int(rows), int(cols)))
         del args[i:i + 2]
+    sync_fines = []
+    while "--sync-fine" in args:
+        i = args.index("--sync-fine")
+        parts = args[i + 1].split("/")
+        sync_fines.append((int(parts[0]), int(parts[1]), int(parts[2]) if len(parts) > 2 else 2, int(parts[3]) if len(parts) > 3 else 2))
+        del args[i:i + 2]
     sync_drifts = []
     while "--sync-drift" in args:
         i = args.index("--sync-drift")
@@ -202,4 +215,4 @@ if __name__ == "__main__":
         syncs.append((int(g), int(r or 2)))
         del args[i:i + 2]
     main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs, locate_tracks, opt["--stack"], emitters,
-         track_emitters, map_stats, sync_drifts, upsamples, opt["--max-lag"])
+         track_emitters, map_stats, sync_drifts, upsamples, opt["--max-lag"], sync_fines)

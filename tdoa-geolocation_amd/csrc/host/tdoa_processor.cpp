@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--locate-upsample=U] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--sync-drift=H[/D]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--locate-upsample=U] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--sync-drift=H[/D]] [--sync-fine=U[/RF]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -162,6 +162,11 @@ int main(int argc, char **argv)
     // clocks, block 2 under block 1's line continued over its positions (tdoa_sync_line_clock)
     bool sync_drift = false;
     int sdrift_h = 0, sdrift_d = 1;
+    // --sync-fine=U[/RF] (with --sync, whole-block stacks), U in 2, 4, 8, 16: the clocks of --sync are refined to 1/U sample in RF
+    // sweeps on the upsampled surfaces' words (tdoa_process_sync_fine); blocks 1 and 3 are located under their own refined clocks,
+    // block 2 under the midpoint of the two rows rounded to 1/16 sample
+    bool sync_fine = false;
+    int sfine_u = 16, sfine_r = 2;
     double gate = 120.0;     // samples; PROJECT_NOTES.md:29-32 (max |TDOA| about 57 us = 114 samples at 2 Msps)
     tdoa_params prm;
     tdoa_default_params(&prm);
@@ -264,6 +269,14 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
+        else if (a.rfind("--sync-fine=", 0) == 0) {
+            sync_fine = true;
+            const int got = std::sscanf(a.c_str() + 12, "%d/%d", &sfine_u, &sfine_r);
+            if (got < 1 || (sfine_u != 2 && sfine_u != 4 && sfine_u != 8 && sfine_u != 16) || sfine_r < 0 || sfine_r > 16) {
+                std::fprintf(stderr, "--sync-fine=U[/RF] with U one of 2, 4, 8, 16 and RF in 0 .. 16, e.g. --sync-fine=16/2\n");
+                return 1;
+            }
+        }
         else if (a == "--gate" && i + 1 < argc) gate = std::atof(argv[++i]);
         else if (a == "--device" && i + 1 < argc) prm.device = std::atoi(argv[++i]);
         else if (a == "--window" && i + 1 < argc) prm.window_len = std::atoll(argv[++i]);
@@ -283,6 +296,7 @@ int main(int argc, char **argv)
     if (locate_up != 1 && !locate) { std::fprintf(stderr, "--locate-upsample needs --stack --locate\n"); return 1; }
     if (sync && !locate) { std::fprintf(stderr, "--sync needs --stack --locate\n"); return 1; }
     if (sync_drift && !sync) { std::fprintf(stderr, "--sync-drift needs --stack --locate --sync\n"); return 1; }
+    if (sync_fine && (!sync || sync_drift)) { std::fprintf(stderr, "--sync-fine needs --stack --locate --sync and no --sync-drift\n"); return 1; }
     if (sync && !sync_drift && stack_m != 0) { std::fprintf(stderr, "--sync needs whole-block stacks: --stack without =WINDOWS\n"); return 1; }
     if (pos.size() < 4) {                                     // processor.go:1048-1052
         usage(argv[0]);
@@ -462,6 +476,8 @@ int main(int argc, char **argv)
         std::vector<tdoa_map_stats> lstats, mstats, ltstats, mtstats;      // --map-stats: one record per record of the four above
         std::vector<tdoa_sync> syncs;            // --sync: one record and S clocks per block (tdoa_process_sync)
         std::vector<int32_t> clocks;
+        std::vector<tdoa_sync> sfines;           // --sync-fine: one more record and S clocks in 1/16 sample per block (tdoa_process_sync_fine)
+        std::vector<int32_t> clocks16;
         std::vector<tdoa_sync_line> lines;       // --sync-drift: one record, S clocks and S rates per block (tdoa_process_sync_drift)
         std::vector<int32_t> rates;
         double grid_lat0 = 0, grid_lon0 = 0, grid_dlat = 0, grid_dlon = 0;
@@ -526,6 +542,20 @@ int main(int argc, char **argv)
                             return die("tdoa_process_sync_drift", rc);
                         if ((rc = tdoa_sync_line_clock(clocks.data(), rates.data(), S, sdrift_d, spb, spb, table16.data() + (size_t)spb * S)))
                             return die("tdoa_sync_line_clock", rc);
+                    } else if (sync_fine) {
+                        syncs.resize((size_t)n_stacks);
+                        clocks.resize((size_t)n_stacks * S);
+                        sfines.resize((size_t)n_stacks);
+                        clocks16.resize((size_t)n_stacks * S);
+                        if ((rc = tdoa_process_sync_fine(ctx, stack_m, sync_g, sync_r, sfine_u, sfine_r, ref.data(), nullptr, syncs.data(), clocks.data(),
+                                                         nullptr, nullptr, sfines.data(), clocks16.data(), nullptr, nullptr)))
+                            return die("tdoa_process_sync_fine", rc);
+                        for (int s = 0; s < S; s++) {            // the midpoint: the nearest integer to (a + b) / 2, halves away from zero
+                            const long long before = clocks16[s], after = clocks16[2 * (size_t)S + s], t = before + after;
+                            table16[s] = (int32_t)before;
+                            table16[(size_t)S + s] = (int32_t)(t < 0 ? -((-t + 1) / 2) : (t + 1) / 2);
+                            table16[2 * (size_t)S + s] = (int32_t)after;
+                        }
                     } else {
                         syncs.resize((size_t)n_stacks);
                         clocks.resize((size_t)n_stacks * S);
@@ -660,6 +690,12 @@ int main(int argc, char **argv)
             std::printf("SYNC block %d: clock=", (int)sid + 1);
             for (int s = 0; s < S; s++) std::printf("%s%d", s ? "," : "", (int)clocks[sid * S + s]);
             std::printf(" moved=%d score=%.6f\n", (int)syncs[sid].moved, syncs[sid].score);
+        }
+        // --sync-fine: the refined clocks of the two reference blocks in 1/16 sample, a line each
+        for (size_t sid = 0; sid < sfines.size(); sid += 2) {
+            std::printf("SYNCFINE block %d: clock16=", (int)sid + 1);
+            for (int s = 0; s < S; s++) std::printf("%s%d", s ? "," : "", (int)clocks16[sid * S + s]);
+            std::printf(" moved=%d score=%.6f\n", (int)sfines[sid].moved, sfines[sid].score);
         }
         // --sync-drift: the lines of the two reference blocks, a line each
         for (size_t b = 0; b < lines.size(); b += 2) {

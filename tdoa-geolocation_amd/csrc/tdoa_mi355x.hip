@@ -47,6 +47,7 @@
 #include "stack_locate_track_multi.hpp"
 #include "stack_map_stats.hpp"
 #include "stack_upsample.hpp"
+#include "stack_sync_fine.hpp"
 
 using namespace tdoa;
 
@@ -194,6 +195,9 @@ struct tdoa_ctx {
     // the clock search: ref_delay and centre (kSyncMaxStations words each), the start's tiles' candidates [stack][tile], the
     // records [stack], the clocks [stack][station], the lags and correlations [stack][pair]
     DevBuf sync_in, sync_part, sync_out, sync_clock, sync_lags, sync_corr;
+    // the fine clock search, behind the clock search's: the fine records [stack], the clocks in 1/16 sample [stack][station],
+    // the lags in 1/U sample and the correlations [stack][pair]
+    DevBuf sfine_out, sfine_clock, sfine_lags, sfine_corr;
     // the clock-line search: ref_delay and centre, the shift table [rank(h)][position], sqrt(N_w) [line], the stations' clocks
     // [line][station][position], their k and h [line][station], the tiles' candidates [line][tile], `moved` and F after placing
     // [line], the records [line], the clocks and rates [line][station], the rows [stack][station], the lags and correlations
@@ -573,7 +577,8 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->mstat_ranks, &ctx->mstat_hist, &ctx->mstat_state, &ctx->mstat_out,
                       &ctx->sline_in, &ctx->sline_tab, &ctx->sline_roots, &ctx->sline_cur, &ctx->sline_k, &ctx->sline_h, &ctx->sline_part,
                       &ctx->sline_moved, &ctx->sline_start, &ctx->sline_out, &ctx->sline_clock, &ctx->sline_rate, &ctx->sline_rows,
-                      &ctx->sline_lags, &ctx->sline_corr, &ctx->locate_qu, &ctx->locate_table_up, &ctx->locate_clock_up};
+                      &ctx->sline_lags, &ctx->sline_corr, &ctx->locate_qu, &ctx->locate_table_up, &ctx->locate_clock_up,
+                      &ctx->sfine_out, &ctx->sfine_clock, &ctx->sfine_lags, &ctx->sfine_corr};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1311,4 +1316,5 @@ int tdoa_solve_surface(const double *stations_lle, int n_stations, const double 
 #include "locate_api.inc"
 #include "locate_run.inc"
 #include "sync_api.inc"
+#include "sync_fine_api.inc"
 #include "sync_drift_api.inc"

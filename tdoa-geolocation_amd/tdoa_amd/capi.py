@@ -125,6 +125,7 @@ SYMBOLS = [
     "tdoa_locate_set_stats", "tdoa_locate_last_stats", "tdoa_group_locate_set_stats", "tdoa_group_locate_last_stats",
     "tdoa_process_sync_drift", "tdoa_debug_sync_drift_from_q", "tdoa_group_process_sync_drift", "tdoa_sync_line_clock",
     "tdoa_locate_set_upsample", "tdoa_group_locate_set_upsample", "tdoa_locate_upsample_taps", "tdoa_debug_upsample_q",
+    "tdoa_process_sync_fine", "tdoa_group_process_sync_fine", "tdoa_debug_sync_fine_from_q",
 ]
 
 _lib = None
@@ -261,6 +262,9 @@ def load(build_if_missing=True):
     L.tdoa_group_process_locate_track_multi.argtypes = [vp] + [C.c_int] * 5 + [vp, i32p, i64p, i32p, i32p, dp, i64p]
     L.tdoa_debug_locate_track_multi_from_q.argtypes = [vp, i64p] + [C.c_int] * 8 + [vp, i32p, i64p, i32p, i32p, dp, i64p]
     L.tdoa_debug_sync_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, vp, i32p, i32p, dp]
+    L.tdoa_process_sync_fine.argtypes = [vp] + [C.c_int] * 5 + [i32p, i32p, vp, i32p, i32p, dp, vp, i32p, i32p, dp]
+    L.tdoa_group_process_sync_fine.argtypes = [vp] + [C.c_int] * 5 + [i32p, i32p, vp, i32p, i32p, dp, vp, i32p, i32p, dp]
+    L.tdoa_debug_sync_fine_from_q.argtypes = [vp, i64p] + [C.c_int] * 7 + [i32p, i32p, vp, i32p, i32p, dp, vp, i32p, i32p, dp]
     L.tdoa_process_sync_drift.argtypes = [vp] + [C.c_int] * 5 + [i32p, i32p, vp, i32p, i32p, i32p, i32p, dp]
     L.tdoa_group_process_sync_drift.argtypes = [vp] + [C.c_int] * 5 + [i32p, i32p, vp, i32p, i32p, i32p, i32p, dp]
     L.tdoa_debug_sync_drift_from_q.argtypes = [vp, i64p] + [C.c_int] * 8 + [i32p, i32p, vp, i32p, i32p, i32p, i32p, dp]
@@ -763,6 +767,33 @@ class Context:
                                                  *_sync_ptrs(out)))
         return out
 
+    def process_sync_fine(self, ref_delay, windows_per_stack=0, gate=0, rounds=0, U=16, fine_rounds=2, centre=None):
+        """tdoa_process_sync_fine -> process_sync's outputs (the coarse stage's bytes) and {"fine": [n_stacks] SYNC_DTYPE,
+        "clock16": [n_stacks][S] int32 (1/16 sample: tdoa_locate_set_clock's unit), "fine_lags": [n_stacks][P] int32 (1/U
+        sample), "fine_corr": [n_stacks][P] float64}: the coarse clocks moved by |y_s| <= U fine lags in `fine_rounds` sweeps
+        on the words of the surfaces upsampled to 1/U sample"""
+        _, n = self.num_stacks(windows_per_stack)
+        S = self.num_stations()
+        out = _sync_fine_outputs(n, S)
+        self._chk(self._L.tdoa_process_sync_fine(self._h, int(windows_per_stack), int(gate), int(rounds), int(U), int(fine_rounds),
+                                                 _ref_delay(ref_delay, S), _centre(centre, S), *_sync_fine_ptrs(out)))
+        return out
+
+    def sync_fine_from_q(self, q, ref_delay, n_w=1, gate=0, rounds=0, U=16, fine_rounds=2, centre=None):
+        """tdoa_debug_sync_fine_from_q: the clock search's and the refinement's kernels on the caller's words q
+        [n_sets][P][2 max_lag - 1] int64 (or one set [P][2 max_lag - 1]) -> what process_sync_fine returns, n_sets for n_stacks"""
+        q = np.ascontiguousarray(q, dtype=np.int64)
+        if q.ndim == 2:
+            q = q[None]
+        S = int(np.size(ref_delay))
+        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
+            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
+        out = _sync_fine_outputs(q.shape[0], S)
+        self._chk(self._L.tdoa_debug_sync_fine_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], S, int(n_w),
+                                                      int(gate), int(rounds), int(U), int(fine_rounds), _ref_delay(ref_delay, S),
+                                                      _centre(centre, S), *_sync_fine_ptrs(out)))
+        return out
+
     def process_sync_drift(self, ref_delay, windows_per_stack=0, gate=0, max_drift=0, drift_den=1, rounds=0, centre=None):
         """tdoa_process_sync_drift -> {"line": [3] SYNC_LINE_DTYPE, "clock": [3][S] int32 (samples), "rate": [3][S] int32,
         "rows": [n_stacks][S] int32 (1/16 sample: tdoa_locate_set_clock's unit), "lags": [n_stacks][P] int32, "corr":
@@ -1034,6 +1065,20 @@ def _sync_ptrs(out):
     i32p = C.POINTER(C.c_int32)
     return (out["sync"].ctypes.data_as(C.c_void_p), out["clock"].ctypes.data_as(i32p), out["lags"].ctypes.data_as(i32p),
             _d(out["corr"]))
+
+
+def _sync_fine_outputs(n_sets, n_stations):
+    p = n_stations * (n_stations - 1) // 2
+    out = _sync_outputs(n_sets, n_stations)
+    out.update({"fine": np.zeros(n_sets, dtype=SYNC_DTYPE), "clock16": np.zeros((n_sets, n_stations), dtype=np.int32),
+                "fine_lags": np.zeros((n_sets, p), dtype=np.int32), "fine_corr": np.zeros((n_sets, p), dtype=np.float64)})
+    return out
+
+
+def _sync_fine_ptrs(out):
+    i32p = C.POINTER(C.c_int32)
+    return _sync_ptrs(out) + (out["fine"].ctypes.data_as(C.c_void_p), out["clock16"].ctypes.data_as(i32p),
+                              out["fine_lags"].ctypes.data_as(i32p), _d(out["fine_corr"]))
 
 
 def _sync_line_outputs(n_lines, n_sets, n_stations):
@@ -1311,6 +1356,16 @@ class Group:
         out = _sync_outputs(n, S)
         self._chk(self._L.tdoa_group_process_sync(self._h, int(windows_per_stack), int(gate), int(rounds), _ref_delay(ref_delay, S),
                                                   _centre(centre, S), *_sync_ptrs(out)))
+        return out
+
+    def process_sync_fine(self, ref_delay, windows_per_stack=0, gate=0, rounds=0, U=16, fine_rounds=2, centre=None):
+        """tdoa_group_process_sync_fine -> Context.process_sync_fine's outputs, byte-identical to a single context's"""
+        m = self.member(0)
+        _, n = m.num_stacks(windows_per_stack)
+        S = m.num_stations()
+        out = _sync_fine_outputs(n, S)
+        self._chk(self._L.tdoa_group_process_sync_fine(self._h, int(windows_per_stack), int(gate), int(rounds), int(U), int(fine_rounds),
+                                                       _ref_delay(ref_delay, S), _centre(centre, S), *_sync_fine_ptrs(out)))
         return out
 
     def process_sync_drift(self, ref_delay, windows_per_stack=0, gate=0, max_drift=0, drift_den=1, rounds=0, centre=None):
