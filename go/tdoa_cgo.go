@@ -411,6 +411,52 @@ func (g *gpuCorrelator) LocateSetUpsample(u int) error {
 	return nil
 }
 
+// LocateSetFineTable hands the context the zoom locate's second table [nCells][nStations] (nil: forget it): the whole area at z
+// fine cells per cell of the table, in nCols columns.  It stays on the device until it is replaced.
+func (g *gpuCorrelator) LocateSetFineTable(delay []int32, nCells, nCols, nStations int) error {
+	if rc := C.tdoa_locate_set_fine_table(g.ctx, tablePtr(delay), C.int(nCells), C.int(nCols), C.int(nStations)); rc != C.TDOA_OK {
+		return fmt.Errorf("tdoa_locate_set_fine_table: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return nil
+}
+
+// LocateZoom is what ProcessLocateZoom returns: the coarse stage's outputs exactly as ProcessLocate's (Loc, Lags, Corr), and per
+// stack the zoom's record, its cell's lags (1/u sample with LocateSetUpsample) and signed correlations [stack][pair].
+type LocateZoom struct {
+	Loc   []C.tdoa_location
+	Lags  []int32
+	Corr  []float64
+	Zoom  []C.tdoa_zoom
+	ZLags []int32
+	ZCorr []float64
+}
+
+func newLocateZoom(stacks, pairs int) *LocateZoom {
+	return &LocateZoom{Loc: make([]C.tdoa_location, stacks), Lags: make([]int32, stacks*pairs), Corr: make([]float64, stacks*pairs),
+		Zoom: make([]C.tdoa_zoom, stacks), ZLags: make([]int32, stacks*pairs), ZCorr: make([]float64, stacks*pairs)}
+}
+
+// ProcessLocateZoom is the zoom locate (the header's "zoom locate"): ProcessLocate's search, then per stack the best of the
+// (2h+1)^2 cells of the fine table around z x the stack's best cell, in the same step.  A fine cell's position is the caller's:
+// row = Zoom[s].cell / nCols of the fine table, col = the remainder.
+func (g *gpuCorrelator) ProcessLocateZoom(windowsPerStack, minSeparation, z, h, fineSeparation int) (*LocateZoom, error) {
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs := int(C.tdoa_num_pairs(g.ctx))
+	if int(total)*pairs == 0 {
+		return nil, fmt.Errorf("tdoa_process_locate_zoom: no stacks or fewer than two stations")
+	}
+	o := newLocateZoom(int(total), pairs)
+	if rc := C.tdoa_process_locate_zoom(g.ctx, C.int(windowsPerStack), C.int(minSeparation), C.int(z), C.int(h), C.int(fineSeparation),
+		&o.Loc[0], (*C.int32_t)(unsafe.Pointer(&o.Lags[0])), (*C.double)(unsafe.Pointer(&o.Corr[0])), nil,
+		&o.Zoom[0], (*C.int32_t)(unsafe.Pointer(&o.ZLags[0])), (*C.double)(unsafe.Pointer(&o.ZCorr[0])), nil); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_process_locate_zoom: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return o, nil
+}
+
 // LocateUpsampleTaps returns the u phases' 16 taps at scale 2^15 (host only): the committed table the upsampler uses.
 func LocateUpsampleTaps(u int) ([]int32, error) {
 	if u < 1 || u > 16 {
@@ -660,6 +706,35 @@ func (g *Group) LocateSetTable(delay []int32, nCells, nCols, nStations int) erro
 		return fmt.Errorf("tdoa_group_locate_set_table: %s", C.GoString(C.tdoa_group_last_error(g.g)))
 	}
 	return nil
+}
+
+// LocateSetFineTable hands every member the zoom locate's fine table (gpuCorrelator.LocateSetFineTable).
+func (g *Group) LocateSetFineTable(delay []int32, nCells, nCols, nStations int) error {
+	if rc := C.tdoa_group_locate_set_fine_table(g.g, tablePtr(delay), C.int(nCells), C.int(nCols), C.int(nStations)); rc != C.TDOA_OK {
+		return fmt.Errorf("tdoa_group_locate_set_fine_table: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return nil
+}
+
+// ProcessLocateZoom is gpuCorrelator.ProcessLocateZoom over the group: the members' fixed-point partial sums are added on the
+// host and searched on member 0, coarse stage and window, the same bytes one context returns.
+func (g *Group) ProcessLocateZoom(windowsPerStack, minSeparation, z, h, fineSeparation int) (*LocateZoom, error) {
+	m := C.tdoa_group_member(g.g, 0)
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(m, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs := int(C.tdoa_num_pairs(m))
+	if int(total)*pairs == 0 {
+		return nil, fmt.Errorf("tdoa_group_process_locate_zoom: no stacks or fewer than two stations")
+	}
+	o := newLocateZoom(int(total), pairs)
+	if rc := C.tdoa_group_process_locate_zoom(g.g, C.int(windowsPerStack), C.int(minSeparation), C.int(z), C.int(h), C.int(fineSeparation),
+		&o.Loc[0], (*C.int32_t)(unsafe.Pointer(&o.Lags[0])), (*C.double)(unsafe.Pointer(&o.Corr[0])), nil,
+		&o.Zoom[0], (*C.int32_t)(unsafe.Pointer(&o.ZLags[0])), (*C.double)(unsafe.Pointer(&o.ZCorr[0])), nil); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_group_process_locate_zoom: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return o, nil
 }
 
 // ProcessLocate is gpuCorrelator.ProcessLocate over the group: the members' fixed-point partial sums are added on the host

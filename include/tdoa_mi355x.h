@@ -955,6 +955,72 @@ int tdoa_locate_upsample_taps(int U, int32_t *taps /* [U][16] */);
  * TDOA_ERR_INVALID: a NULL context, q or out NULL, n_rows < 1, a bad U. */
 int tdoa_debug_upsample_q(tdoa_ctx *ctx, const int64_t *q, int n_rows, int U, int64_t *out);
 
+/* Zoom locate: a fine table searched around each stack's best cell.  The family finds an emitter in two steps: the best cell
+ * of a coarse grid, then a finer grid around that cell, on whole lags or on the upsampled surfaces.  A context holds one table
+ * and every stack of a call has another best cell, so the second step used to be one table upload and one call per stack.
+ * Interpolating the coarse table on the device is no substitute: near a station range is a cone, and a bilinear table is
+ * wrong by more than a sample there.  The fine delays are data, like everything else the family is given.
+ *   The fine table: a second table of the context, delay[n_cells_f][n_stations] in n_cols_f columns, that covers the whole area
+ *     at Z cells per coarse cell: fine cell (Z r, Z c) is meant to be coarse cell (r, c).  The library does not check that; it
+ *     is the caller's table.  Units, limits, the station-major upload and the "forget" form are tdoa_locate_set_table's.  With
+ *     the setting U > 1 it gets its U-scaled copy wherever the table gets one.  Its shape (n_cells_f, n_cols_f) is part of a
+ *     step graph's key; its contents are data.  The last row may be short.
+ *   The coarse stage is tdoa_process_locate on the context's table, clocks, upsample setting and statistics setting: the first
+ *     four outputs are its bytes, and tdoa_locate_last_stats returns what it returns after that call.  The zoom's own map is
+ *     not judged.
+ *   The window: stack s has the location cell* = (r*, c*) in the coarse table's coordinates.  Its window is the positions
+ *     (wa, wb), 0 <= wa, wb <= 2H; a position's fine row is Z r* - H + wa and its fine column is Z c* - H + wb.  A position
+ *     competes when its row is >= 0, its column is in 0 .. n_cols_f - 1 and its fine cell index row * n_cols_f + col is
+ *     < n_cells_f.  The centre is read on the device, so one captured graph serves every block.
+ *   The score of a competing position is score_q of its fine cell exactly as the family defines it: the lag rule on the fine
+ *     table's differences, plus the stack's clock differences where a clock table is set; with U > 1 the rule
+ *     sgn(d) * ((2|d| U + 16) div 32) on Q_U.  A pair outside the searched range counts 0.  The words of Q are the same, and
+ *     so is the overflow bound.
+ *   The zoom's cell is the competing position with the largest score.  Among equal maxima the smaller fine cell index wins.
+ *   The zero record: a stack with no location (the zero coarse record) gets the zero tdoa_zoom, zero lags and correlations and
+ *     a zmap of -1 throughout.  A stack whose window's largest score is 0, or whose window has no competing position, also
+ *     gets the zero record and zero lags and correlations; its zmap still holds its scores.
+ * The record, 64 bytes, no padding: */
+typedef struct {
+    int32_t cell, runner_cell, pairs_in, n_best;     /* cell: the fine cell index; pairs_in there; n_best: the competing
+                                                        positions with exactly score_q */
+    int32_t row_lo, row_hi, col_lo, col_hi;          /* the smallest and largest fine row and column among those positions */
+    int64_t score_q, runner_q;
+    double  score, runner_up;                        /* (double)x_q * 2^-32 / sqrt(n_w) */
+} tdoa_zoom;
+/*   The runner-up is the largest score over competing positions with max(|row - row_z|, |col - col_z|) > fine_separation,
+ *     with the same tie rule; runner_q, runner_up and runner_cell are 0 where there is none.
+ *   With whole lags the best score is a plateau of many fine cells and the smaller index is a corner of it: n_best and the box
+ *     let a caller take the plateau's middle and see the fix's real resolution.
+ *   zlags and zcorr hold lag_p(cell) in 1/U sample and the signed correlation there, 0 and 0.0 for a pair outside the range:
+ *     what tdoa_solve_surface takes.  zmap[s][wa * (2H + 1) + wb] is the position's score, or -1 where it does not compete.
+ *   What follows: with the fine table equal to the table and Z = 1, the zoom's cell, score_q, lags and correlations are the
+ *     location's.  Whenever the brute-force best cell of the whole fine table (tdoa_process_locate with the fine table as the
+ *     table) lies inside a stack's window, it is the zoom's cell, with the same score, lags and correlations.
+ *   Scope: the rounds (tdoa_process_locate_multi) and the cell tracks are not zoomed.
+ * Two kernels behind the locate's launches, in the same step graph: nothing goes through the host.  The graph's key is the
+ * locate's words plus (Z, H, fine_separation, n_cells_f, n_cols_f).
+ * TDOA_ERR_INVALID (tdoa_locate_set_fine_table): what tdoa_locate_set_table refuses. */
+int tdoa_locate_set_fine_table(tdoa_ctx *ctx, const int32_t *delay /* [n_cells][n_stations] */, int n_cells, int n_cols, int n_stations);
+
+/* The refusals are the locate's, and: TDOA_ERR_INVALID: Z outside 1 .. 64, H outside 0 .. 64, fine_separation < 1, a NULL
+ * zoom_host.  TDOA_ERR_STATE: no fine table, or one of another n_stations.  TDOA_ERR_UNSUPPORTED: with U > 1, a fine table
+ * entry with |t| * U >= 2^31.  TDOA_ERR_NOMEM: the window maps [n_stacks_total][(2H+1)^2] do not fit; tdoa_last_error gives
+ * the sizes. */
+int tdoa_process_locate_zoom(tdoa_ctx *ctx, int windows_per_stack, int min_separation, int Z, int H, int fine_separation,
+                             tdoa_location *loc_host, int32_t *lags_host, double *corr_host, int64_t *map_host /* tdoa_process_locate's */,
+                             tdoa_zoom *zoom_host   /* [n_stacks_total], required */,
+                             int32_t *zlags_host    /* [n_stacks_total][n_pairs], may be NULL */,
+                             double  *zcorr_host    /* same shape, may be NULL */,
+                             int64_t *zmap_host     /* [n_stacks_total][(2H+1)^2], may be NULL */);
+
+/* tests only: the same kernels on the caller's words, as tdoa_debug_locate_from_q, with the context's table, fine table, clocks
+ * and settings; outputs as tdoa_process_locate_zoom's with n_sets for n_stacks_total.  Refuses what that call and
+ * tdoa_debug_locate_from_q refuse. */
+int tdoa_debug_locate_zoom_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int min_separation, int Z, int H,
+                                  int fine_separation, tdoa_location *loc, int32_t *lags, double *corr, int64_t *map, tdoa_zoom *zoom,
+                                  int32_t *zlags, double *zcorr, int64_t *zmap);
+
 /* Capture-quality statistics of every (window, station) in one streaming pass over the bytes
  * in HBM: the byte statistics of fastAnalyzeSamples
  * (fast_analyzer.go:117-155) and the block power of validateDataFile (collector.go:219-224).
@@ -1228,6 +1294,13 @@ int tdoa_group_locate_last_stats(tdoa_group *g, tdoa_map_stats *out, int max_pla
 /* tdoa_locate_set_upsample on every member.  A group of several upsamples the merged sum on member 0; the outputs are the
  * bytes a single context returns.  Errors as there. */
 int tdoa_group_locate_set_upsample(tdoa_group *g, int U);
+
+/* tdoa_locate_set_fine_table on every member, and tdoa_process_locate_zoom over them: the merged sum is searched on member 0,
+ * coarse stage and window, and the same bytes go through the merged sum as a single context returns.  Errors as there. */
+int tdoa_group_locate_set_fine_table(tdoa_group *g, const int32_t *delay, int n_cells, int n_cols, int n_stations);
+int tdoa_group_process_locate_zoom(tdoa_group *g, int windows_per_stack, int min_separation, int Z, int H, int fine_separation,
+                                   tdoa_location *loc_host, int32_t *lags_host, double *corr_host, int64_t *map_host, tdoa_zoom *zoom_host,
+                                   int32_t *zlags_host, double *zcorr_host, int64_t *zmap_host);
 
 /* the sample runs member `rank` of `world` uploads for a capture of total_samples (window grid from n_min, the shortest
  * capture of the job; block offsets from the capture's own thirds): adjacent owned windows form one run, and with fewer

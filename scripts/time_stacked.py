@@ -36,8 +36,14 @@ of the search's launches, which then gather from surfaces U times as long; every
 `--sync-fine G/U[/R[/RF]]` adds a leg: tdoa_process_sync_fine(M, G, R, U, RF) (R and RF default to 2; M from `--stack`) against
 the same delays with all eight outputs downloaded -- the clock search's launches and one more kernel, one workgroup per stack --
 and, when M is not 0, the leg process_sync_G_R_stackM_ms: tdoa_process_sync(M, G, R), what the fine leg is compared with.
+Every `--locate-zoom Z[/H]` (H defaults to 2 Z) adds, per `--locate` grid and for U = 1 and every `--locate-upsample U`, two legs:
+tdoa_process_locate_zoom(M, 1, Z, H, 1) with the same grid at Z cells per cell as the fine table (name
+process_locate_zoom_RxC_Z_H[_upU]_ms: the locate's launches and two more kernels; records, lags and correlations of both stages
+downloaded, the maps left on the device), and tdoa_process_locate(M, 1) with that fine grid as the table (name
+process_locate_fine_RxC_Z[_upU]_ms), the brute force the zoom replaces; the second is left out where the fine grid has more than
+2^22 cells.
 usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--stack M] [--drift H/D]... [--track J]...
-[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]... [--locate-upsample U]... [--sync-fine G/U[/R[/RF]]]... [--max-lag N]"""
+[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]... [--locate-upsample U]... [--sync-fine G/U[/R[/RF]]]... [--locate-zoom Z[/H]]... [--max-lag N]"""
 import json
 import os
 import sys
@@ -67,7 +73,7 @@ def timed(fn, steps):
 
 
 def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=(), locate_tracks=(), stack=0, emitters=(),
-         track_emitters=(), map_stats=None, sync_drifts=(), upsamples=(), max_lag=20000, sync_fines=()):
+         track_emitters=(), map_stats=None, sync_drifts=(), upsamples=(), max_lag=20000, sync_fines=(), zooms=()):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=max_lag)
     for s in range(stations):
         c.synth_capture(s, 66_666_666, ST[s % 3], TX, 0x5D0A0000 + s)
@@ -84,10 +90,12 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
         legs["process_closure_%d_ms" % G] = lambda G=G: c.process_closure(0, G, 1)
     setup = {}
 
-    def family(name, table, cols, fn, U=1):
+    def family(name, table, cols, fn, U=1, fine=None, fine_cols=None):
         """a leg of the delay-table family with the statistics off and, with --map-stats, the same leg with them on"""
         def base():
             c.locate_set_table(table, cols)
+            if fine is not None:
+                c.locate_set_fine_table(fine, fine_cols)
             if upsamples:
                 c.locate_set_upsample(U)
         setup[name] = lambda: (base(), c.locate_set_stats(None)) if map_stats else base()
@@ -103,6 +111,17 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
         family("process_locate_%dx%d_ms" % (rows, cols), table, cols, lambda: c.process_locate(stack, 1))
         for U in upsamples:
             family("process_locate_%dx%d_up%d_ms" % (rows, cols, U), table, cols, lambda: c.process_locate(stack, 1), U)
+        for Z, H in zooms:
+            rows_f, cols_f = (rows - 1) * Z + 1, (cols - 1) * Z + 1
+            if rows_f * cols_f > 2 ** 22:
+                raise SystemExit("--locate-zoom: the fine grid of %d x %d cells has more than 2^22 cells" % (rows_f, cols_f))
+            fine = tdoa_amd.capi.locate_grid_table([ST[s % 3] for s in range(stations)], 41.10, -96.20, 0.3 / max(rows - 1, 1) / Z,
+                                                   0.4 / max(cols - 1, 1) / Z, rows_f, cols_f, 350.0, 2e6)
+            for U in [1] + list(upsamples):
+                up = "_up%d" % U if U > 1 else ""
+                family("process_locate_zoom_%dx%d_%d_%d%s_ms" % (rows, cols, Z, H, up), table, cols,
+                       lambda Z=Z, H=H: c.process_locate_zoom(Z, H, stack, 1, 1, want_zmap=False), U, fine, cols_f)
+                family("process_locate_fine_%dx%d_%d%s_ms" % (rows, cols, Z, up), fine, cols_f, lambda: c.process_locate(stack, 1), U)
         for J in locate_tracks:
             family("process_locate_track_%dx%d_J%d_ms" % (rows, cols, J), table, cols, lambda J=J: c.process_locate_track(stack, J, 1))
             for K, guard in track_emitters:
@@ -196,6 +215,12 @@ if __name__ == "__main__":
         rows, _, cols = args[i + 1].partition("x")
         locates.append((int(rows), int(cols)))
         del args[i:i + 2]
+    zooms = []
+    while "--locate-zoom" in args:
+        i = args.index("--locate-zoom")
+        z, _, h = args[i + 1].partition("/")
+        zooms.append((int(z), int(h) if h else 2 * int(z)))
+        del args[i:i + 2]
     sync_fines = []
     while "--sync-fine" in args:
         i = args.index("--sync-fine")
@@ -215,4 +240,4 @@ if __name__ == "__main__":
         syncs.append((int(g), int(r or 2)))
         del args[i:i + 2]
     main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs, locate_tracks, opt["--stack"], emitters,
-         track_emitters, map_stats, sync_drifts, upsamples, opt["--max-lag"], sync_fines)
+         track_emitters, map_stats, sync_drifts, upsamples, opt["--max-lag"], sync_fines, zooms)

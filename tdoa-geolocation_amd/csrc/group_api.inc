@@ -324,6 +324,15 @@ int tdoa_group_locate_set_table(tdoa_group *g, const int32_t *delay, int n_cells
     return TDOA_OK;
 }
 
+// the zoom locate's fine table to every member
+int tdoa_group_locate_set_fine_table(tdoa_group *g, const int32_t *delay, int n_cells, int n_cols, int n_stations)
+{
+    if (!g) return TDOA_ERR_INVALID;
+    for (size_t m = 0; m < g->members.size(); m++)
+        if (const int rc = tdoa_locate_set_fine_table(g->members[m], delay, n_cells, n_cols, n_stations)) return member_fail(g, (int)m, rc);
+    return TDOA_OK;
+}
+
 // the clocks to every member: each keeps its own copy, member 0's is the one a group of several searches with
 int tdoa_group_locate_set_clock(tdoa_group *g, const int32_t *clock, int n_stacks, int n_stations)
 {

@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--locate-upsample=U] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--sync-drift=H[/D]] [--sync-fine=U[/RF]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--locate-upsample=U] [--locate-zoom=Z[/H[/SEP]]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--sync-drift=H[/D]] [--sync-fine=U[/RF]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -154,6 +154,11 @@ int main(int argc, char **argv)
     // --locate-upsample=U (with --stack --locate), U in 2, 4, 8, 16: the searches score their cells on the surfaces upsampled to
     // 1/U sample (tdoa_locate_set_upsample); a grid finer than one lag of range difference needs it
     int locate_up = 1;
+    // --locate-zoom=Z[/H[/SEP]] (with --stack --locate): every stack's best cell is searched again on the (2H+1)^2 cells around it of
+    // the same grid at Z cells per cell, ((ROWS-1) Z + 1) x ((COLS-1) Z + 1) cells, in the same call (tdoa_process_locate_zoom); a
+    // ZOOM line follows every LOCATE line.  H defaults to 2 Z, SEP to 1
+    bool locate_zoom = false;
+    int zoom_z = 1, zoom_h = -1, zoom_sep = 1;
     bool sync = false;
     double sync_lat = 0, sync_lon = 0, sync_h = 0;
     int sync_g = 128, sync_r = 2;
@@ -245,6 +250,15 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
+        else if (a.rfind("--locate-zoom=", 0) == 0) {
+            locate_zoom = true;
+            const int got = std::sscanf(a.c_str() + 14, "%d/%d/%d", &zoom_z, &zoom_h, &zoom_sep);
+            if (got < 2) zoom_h = zoom_z >= 1 && zoom_z <= 32 ? 2 * zoom_z : 64;
+            if (got < 1 || zoom_z < 1 || zoom_z > 64 || zoom_h < 0 || zoom_h > 64 || zoom_sep < 1) {
+                std::fprintf(stderr, "--locate-zoom=Z[/H[/SEP]] with Z in 1 .. 64, H in 0 .. 64 and SEP >= 1, e.g. --locate-zoom=8/16\n");
+                return 1;
+            }
+        }
         else if (a.rfind("--track-emitters=", 0) == 0) {
             track_emitters = true;
             const int got = std::sscanf(a.c_str() + 17, "%d/%d", &temitters_k, &temitters_guard);
@@ -294,6 +308,12 @@ int main(int argc, char **argv)
     if (track_emitters && !locate_track) { std::fprintf(stderr, "--track-emitters needs --stack --locate --locate-track\n"); return 1; }
     if (map_stats && !locate) { std::fprintf(stderr, "--map-stats needs --stack --locate\n"); return 1; }
     if (locate_up != 1 && !locate) { std::fprintf(stderr, "--locate-upsample needs --stack --locate\n"); return 1; }
+    if (locate_zoom && !locate) { std::fprintf(stderr, "--locate-zoom needs --stack --locate\n"); return 1; }
+    if (locate_zoom && ((long long)(locate_rows - 1) * zoom_z + 1) * ((long long)(locate_cols - 1) * zoom_z + 1) > (1ll << 22)) {
+        std::fprintf(stderr, "--locate-zoom: the fine grid of %lld x %lld cells has more than 2^22 cells\n", (long long)(locate_rows - 1) * zoom_z + 1,
+                     (long long)(locate_cols - 1) * zoom_z + 1);
+        return 1;
+    }
     if (sync && !locate) { std::fprintf(stderr, "--sync needs --stack --locate\n"); return 1; }
     if (sync_drift && !sync) { std::fprintf(stderr, "--sync-drift needs --stack --locate --sync\n"); return 1; }
     if (sync_fine && (!sync || sync_drift)) { std::fprintf(stderr, "--sync-fine needs --stack --locate --sync and no --sync-drift\n"); return 1; }
@@ -466,6 +486,8 @@ int main(int argc, char **argv)
         std::vector<int32_t> tlags;
         std::vector<tdoa_closure> clos;          // --closure: one record per stack and station triple (tdoa_process_closure)
         std::vector<tdoa_location> locs;         // --locate: one record per stack (tdoa_process_locate)
+        std::vector<tdoa_zoom> zooms;            // --locate-zoom: one more record per stack (tdoa_process_locate_zoom)
+        int zoom_cols = 1;                       // the fine grid's columns
         std::vector<tdoa_cell_track> ltracks;    // --locate-track: one record per block, a cell and its own score per stack
         std::vector<int32_t> lt_cells;           // (tdoa_process_locate_track)
         std::vector<int64_t> lt_own;
@@ -578,7 +600,21 @@ int main(int argc, char **argv)
                     return map_stats ? tdoa_locate_last_stats(ctx, out->data(), (int)n, nullptr) : TDOA_OK;
                 };
                 locs.resize((size_t)n_stacks);
-                if ((rc = tdoa_process_locate(ctx, stack_m, 1, locs.data(), nullptr, nullptr, nullptr))) return die("tdoa_process_locate", rc);
+                if (locate_zoom) {
+                    // the same grid at Z cells per cell: fine cell (Z r, Z c) lies where cell (r, c) does
+                    const int rows_f = (locate_rows - 1) * zoom_z + 1;
+                    zoom_cols = (locate_cols - 1) * zoom_z + 1;
+                    std::vector<int32_t> fine((size_t)rows_f * zoom_cols * S);
+                    if ((rc = tdoa_locate_grid_table(lle.data(), S, grid_lat0, grid_lon0, grid_dlat / zoom_z, grid_dlon / zoom_z, rows_f, zoom_cols, h_c,
+                                                     prm.sample_rate, fine.data())))
+                        return die("tdoa_locate_grid_table", rc);
+                    if ((rc = tdoa_locate_set_fine_table(ctx, fine.data(), rows_f * zoom_cols, zoom_cols, S))) return die("tdoa_locate_set_fine_table", rc);
+                    zooms.resize((size_t)n_stacks);
+                    if ((rc = tdoa_process_locate_zoom(ctx, stack_m, 1, zoom_z, zoom_h, zoom_sep, locs.data(), nullptr, nullptr, nullptr, zooms.data(),
+                                                       nullptr, nullptr, nullptr)))
+                        return die("tdoa_process_locate_zoom", rc);
+                } else if ((rc = tdoa_process_locate(ctx, stack_m, 1, locs.data(), nullptr, nullptr, nullptr)))
+                    return die("tdoa_process_locate", rc);
                 if ((rc = last_stats(&lstats, locs.size()))) return die("tdoa_locate_last_stats", rc);
                 if (emitters) {
                     mlocs.resize((size_t)emitters_k * n_stacks);
@@ -722,6 +758,14 @@ int main(int argc, char **argv)
                         (int)sid % spb, (int)l.cell, grid_lat0 + (l.cell / locate_cols) * grid_dlat, grid_lon0 + (l.cell % locate_cols) * grid_dlon,
                         (int)l.pairs_in, l.score, l.runner_up);
             print_stats(lstats, sid);
+            if (locate_zoom) {               // the fine cell, its plateau's box in fine rows and columns, the runner-up; cell=-1: none
+                const tdoa_zoom &z = zooms[sid];
+                const int cell = z.score_q > 0 ? (int)z.cell : -1;
+                std::printf("ZOOM block %d stack %d: cell=%d lat=%.6f lon=%.6f pairs=%d score=%.6f best=%d rows=%d..%d cols=%d..%d runner=%.6f runner_cell=%d\n",
+                            (int)sid / spb + 1, (int)sid % spb, cell, grid_lat0 + (z.cell / zoom_cols) * grid_dlat / zoom_z,
+                            grid_lon0 + (z.cell % zoom_cols) * grid_dlon / zoom_z, (int)z.pairs_in, z.score, (int)z.n_best, (int)z.row_lo, (int)z.row_hi,
+                            (int)z.col_lo, (int)z.col_hi, z.runner_up, (int)z.runner_cell);
+            }
         }
         // --emitters: a fix per round, the stack's rounds together; a round that found nothing prints cell=-1
         for (size_t sid = 0; sid < mlocs.size() / (size_t)emitters_k; sid++)

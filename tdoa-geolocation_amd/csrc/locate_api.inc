@@ -22,15 +22,22 @@ static LocateGeom locate_geom(const tdoa_ctx *ctx, int min_separation)
 // 2.04 n_w 2^45 + 1, and the bound is tightened by the factor 4
 static bool locate_overflows(int P, long long n_w, int U = 1) { return (U > 1 ? 4ll : 1ll) * P * n_w > (1ll << 17); }
 
-// U x the table and U x the clock differences beside the originals, for the searches on upsampled surfaces (stack_upsample.hpp):
-// remade whenever the table, the clocks or U change, so that they are data of a replayed graph like the originals.  Nothing to
-// do with U = 1.  (An entry with |t| U >= 2^31 wraps here; the calls refuse such a table: check_locate_upsample.)
+// U x the table, U x the zoom's fine table and U x the clock differences beside the originals, for the searches on upsampled
+// surfaces (stack_upsample.hpp): remade whenever one of them or U changes, so that they are data of a replayed graph like the
+// originals.  Nothing to do with U = 1.  (An entry with |t| U >= 2^31 wraps here; the calls refuse such a table:
+// check_locate_upsample, LocateZoomSearch::check_fine.)
 static int remake_locate_scaled(tdoa_ctx *ctx)
 {
     const int U = ctx->locate_up;
-    if (U == 1 || (ctx->locate_cells == 0 && ctx->clock_stacks == 0)) return TDOA_OK;
+    if (U == 1 || (ctx->locate_cells == 0 && ctx->clock_stacks == 0 && ctx->fine_cells == 0)) return TDOA_OK;
     int rc;
     if ((rc = check_ctx(ctx))) return rc;
+    if (ctx->fine_cells) {
+        const size_t n = (size_t)ctx->fine_stations * ctx->fine_cells;
+        if ((rc = ensure(ctx, ctx->locate_fine_up, sizeof(int32_t) * n))) return rc;
+        hipLaunchKernelGGL(k_locate_scale_i32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->locate_fine.as<const int32_t>(), U, n,
+                           ctx->locate_fine_up.as<int32_t>());
+    }
     if (ctx->locate_cells) {
         const size_t n = (size_t)ctx->locate_stations * ctx->locate_cells;
         if ((rc = ensure(ctx, ctx->locate_table_up, sizeof(int32_t) * n))) return rc;
@@ -48,11 +55,14 @@ static int remake_locate_scaled(tdoa_ctx *ctx)
     return TDOA_OK;
 }
 
-int tdoa_locate_set_table(tdoa_ctx *ctx, const int32_t *delay, int n_cells, int n_cols, int n_stations)
+// a delay table of the context, the table or the fine table: the caller's [cell][station] words station-major into buf, the
+// shape and the largest magnitude into the context's words, then the scaled copies
+static int set_delay_table(tdoa_ctx *ctx, const int32_t *delay, int n_cells, int n_cols, int n_stations, DevBuf &buf, int *cells, int *cols,
+                           int *stations, long long *largest)
 {
     if (!ctx) return TDOA_ERR_INVALID;
     if (!delay || n_cells == 0) {            // forget the table (the buffer stays: a cached step graph may still name it)
-        ctx->locate_cells = ctx->locate_cols = ctx->locate_stations = 0;
+        *cells = *cols = *stations = 0;
         return TDOA_OK;
     }
     if (n_cells < 1 || n_cells > kLocateMaxCells || n_cols < 1 || n_stations < 2 || n_stations > kLocateMaxStations)
@@ -67,17 +77,32 @@ int tdoa_locate_set_table(tdoa_ctx *ctx, const int32_t *delay, int n_cells, int 
             t[(size_t)s * n_cells + c] = d;
             t_max = std::max(t_max, std::llabs((long long)d));
         }
-    if ((rc = ensure(ctx, ctx->locate_table, sizeof(int32_t) * t.size()))) {
-        ctx->locate_cells = ctx->locate_cols = ctx->locate_stations = 0;
+    if ((rc = ensure(ctx, buf, sizeof(int32_t) * t.size()))) {
+        *cells = *cols = *stations = 0;
         return rc;
     }
-    ctx->locate_cells = n_cells;
-    ctx->locate_cols = n_cols;
-    ctx->locate_stations = n_stations;
-    ctx->locate_table_max = t_max;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->locate_table.p, t.data(), sizeof(int32_t) * t.size(), hipMemcpyHostToDevice, ctx->stream));
+    *cells = n_cells;
+    *cols = n_cols;
+    *stations = n_stations;
+    *largest = t_max;
+    HIPCHK(ctx, hipMemcpyAsync(buf.p, t.data(), sizeof(int32_t) * t.size(), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));            // t goes out of scope
     return remake_locate_scaled(ctx);
+}
+
+int tdoa_locate_set_table(tdoa_ctx *ctx, const int32_t *delay, int n_cells, int n_cols, int n_stations)
+{
+    if (!ctx) return TDOA_ERR_INVALID;
+    return set_delay_table(ctx, delay, n_cells, n_cols, n_stations, ctx->locate_table, &ctx->locate_cells, &ctx->locate_cols, &ctx->locate_stations,
+                           &ctx->locate_table_max);
+}
+
+// the zoom locate's second table (locate_zoom_api.inc): the same upload, beside the table
+int tdoa_locate_set_fine_table(tdoa_ctx *ctx, const int32_t *delay, int n_cells, int n_cols, int n_stations)
+{
+    if (!ctx) return TDOA_ERR_INVALID;
+    return set_delay_table(ctx, delay, n_cells, n_cols, n_stations, ctx->locate_fine, &ctx->fine_cells, &ctx->fine_cols, &ctx->fine_stations,
+                           &ctx->locate_fine_max);
 }
 
 int tdoa_locate_set_clock(tdoa_ctx *ctx, const int32_t *clock, int n_stacks, int n_stations)

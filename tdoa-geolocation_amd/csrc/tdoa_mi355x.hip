@@ -48,6 +48,7 @@
 #include "stack_map_stats.hpp"
 #include "stack_upsample.hpp"
 #include "stack_sync_fine.hpp"
+#include "stack_locate_zoom.hpp"
 
 using namespace tdoa;
 
@@ -214,6 +215,12 @@ struct tdoa_ctx {
     int locate_up = 1;
     long long locate_table_max = 0, locate_clock_max = 0;
     DevBuf locate_qu, locate_table_up, locate_clock_up;
+    // the zoom locate (tdoa_process_locate_zoom), behind the delay-table search: the fine table [station][fine cell] (state:
+    // tdoa_locate_set_fine_table; 0 cells: none), U x it, and a run's window maps [stack][(2H+1)^2], tiles' candidates
+    // [stack][tile], records [stack], lags and correlations [stack][pair]
+    int fine_cells = 0, fine_cols = 0, fine_stations = 0;
+    long long locate_fine_max = 0;
+    DevBuf locate_fine, locate_fine_up, zoom_map, zoom_part, zoom_out, zoom_lags, zoom_corr;
     size_t total_mem = 0;                   // of the device, 0: unknown
 };
 
@@ -224,6 +231,7 @@ static_assert(sizeof(FmStats) == sizeof(tdoa_fm_stats), "tdoa_fm_stats layout");
 static_assert(sizeof(ClosureOut) == sizeof(tdoa_closure) && sizeof(tdoa_closure) == 80, "tdoa_closure layout");
 static_assert(sizeof(LocateOut) == sizeof(tdoa_location) && sizeof(tdoa_location) == 48, "tdoa_location layout");
 static_assert(kLocateDelayUnit == TDOA_DELAY_UNIT, "the table's unit");
+static_assert(sizeof(LocateZoomOut) == sizeof(tdoa_zoom) && sizeof(tdoa_zoom) == 64, "tdoa_zoom layout");
 static_assert(kLocateMaxEmitters == TDOA_LOCATE_MAX_EMITTERS, "the rounds of tdoa_process_locate_multi");
 static_assert(sizeof(SyncOut) == sizeof(tdoa_sync) && sizeof(tdoa_sync) == 32, "tdoa_sync layout");
 static_assert(sizeof(CellTrackOut) == sizeof(tdoa_cell_track) && sizeof(tdoa_cell_track) == 48, "tdoa_cell_track layout");
@@ -578,7 +586,8 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->sline_in, &ctx->sline_tab, &ctx->sline_roots, &ctx->sline_cur, &ctx->sline_k, &ctx->sline_h, &ctx->sline_part,
                       &ctx->sline_moved, &ctx->sline_start, &ctx->sline_out, &ctx->sline_clock, &ctx->sline_rate, &ctx->sline_rows,
                       &ctx->sline_lags, &ctx->sline_corr, &ctx->locate_qu, &ctx->locate_table_up, &ctx->locate_clock_up,
-                      &ctx->sfine_out, &ctx->sfine_clock, &ctx->sfine_lags, &ctx->sfine_corr};
+                      &ctx->sfine_out, &ctx->sfine_clock, &ctx->sfine_lags, &ctx->sfine_corr,
+                      &ctx->locate_fine, &ctx->locate_fine_up, &ctx->zoom_map, &ctx->zoom_part, &ctx->zoom_out, &ctx->zoom_lags, &ctx->zoom_corr};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1315,6 +1324,7 @@ int tdoa_solve_surface(const double *stations_lle, int n_stations, const double 
 #include "map_stats_api.inc"
 #include "locate_api.inc"
 #include "locate_run.inc"
+#include "locate_zoom_api.inc"
 #include "sync_api.inc"
 #include "sync_fine_api.inc"
 #include "sync_drift_api.inc"

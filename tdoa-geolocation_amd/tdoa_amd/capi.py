@@ -52,6 +52,10 @@ CLOSURE_DTYPE = np.dtype([("lag_ij", np.int32), ("lag_ik", np.int32), ("lag_jk",
 LOCATION_DTYPE = np.dtype([("cell", np.int32), ("runner_cell", np.int32), ("pairs_in", np.int32), ("reserved", np.int32),
                            ("score_q", np.int64), ("runner_q", np.int64),
                            ("score", np.float64), ("runner_up", np.float64)])      # tdoa_location
+ZOOM_DTYPE = np.dtype([("cell", np.int32), ("runner_cell", np.int32), ("pairs_in", np.int32), ("n_best", np.int32),
+                       ("row_lo", np.int32), ("row_hi", np.int32), ("col_lo", np.int32), ("col_hi", np.int32),
+                       ("score_q", np.int64), ("runner_q", np.int64),
+                       ("score", np.float64), ("runner_up", np.float64)])      # tdoa_zoom
 SYNC_DTYPE = np.dtype([("moved", np.int32), ("pairs_in", np.int32), ("score_q", np.int64), ("start_q", np.int64),
                        ("score", np.float64)])      # tdoa_sync
 SYNC_LINE_DTYPE = np.dtype([("moved", np.int32), ("terms_in", np.int32), ("positions", np.int32), ("reserved", np.int32),
@@ -126,6 +130,8 @@ SYMBOLS = [
     "tdoa_process_sync_drift", "tdoa_debug_sync_drift_from_q", "tdoa_group_process_sync_drift", "tdoa_sync_line_clock",
     "tdoa_locate_set_upsample", "tdoa_group_locate_set_upsample", "tdoa_locate_upsample_taps", "tdoa_debug_upsample_q",
     "tdoa_process_sync_fine", "tdoa_group_process_sync_fine", "tdoa_debug_sync_fine_from_q",
+    "tdoa_locate_set_fine_table", "tdoa_group_locate_set_fine_table", "tdoa_process_locate_zoom", "tdoa_group_process_locate_zoom",
+    "tdoa_debug_locate_zoom_from_q",
 ]
 
 _lib = None
@@ -274,6 +280,11 @@ def load(build_if_missing=True):
     L.tdoa_locate_last_stats.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.tdoa_group_locate_last_stats.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.tdoa_locate_set_upsample.argtypes = [vp, C.c_int]
+    L.tdoa_locate_set_fine_table.argtypes = [vp, i32p, C.c_int, C.c_int, C.c_int]
+    L.tdoa_group_locate_set_fine_table.argtypes = [vp, i32p, C.c_int, C.c_int, C.c_int]
+    L.tdoa_process_locate_zoom.argtypes = [vp] + [C.c_int] * 5 + [vp, i32p, dp, i64p, vp, i32p, dp, i64p]
+    L.tdoa_group_process_locate_zoom.argtypes = [vp] + [C.c_int] * 5 + [vp, i32p, dp, i64p, vp, i32p, dp, i64p]
+    L.tdoa_debug_locate_zoom_from_q.argtypes = [vp, i64p] + [C.c_int] * 7 + [vp, i32p, dp, i64p, vp, i32p, dp, i64p]
     L.tdoa_group_locate_set_upsample.argtypes = [vp, C.c_int]
     L.tdoa_locate_upsample_taps.argtypes = [C.c_int, i32p]
     L.tdoa_debug_upsample_q.argtypes = [vp, i64p, C.c_int, C.c_int, i64p]
@@ -719,6 +730,38 @@ class Context:
         U = 1: off"""
         self._chk(self._L.tdoa_locate_set_upsample(self._h, int(U)))
 
+    def locate_set_fine_table(self, table, n_cols=None):
+        """tdoa_locate_set_fine_table: the zoom locate's second table [n_cells_f][n_stations] int32, in n_cols columns, Z fine
+        cells per cell of the table.  table None: forget it.  Kept on the device until replaced"""
+        ptr, n_cells, n_cols, S = _table(table, n_cols)
+        self._chk(self._L.tdoa_locate_set_fine_table(self._h, ptr, n_cells, n_cols, S))
+
+    def process_locate_zoom(self, Z, H, windows_per_stack=0, min_separation=1, fine_separation=1, want_map=False, want_zmap=True):
+        """tdoa_process_locate_zoom -> process_locate's dict (the coarse stage's bytes) and {"zoom": [n_stacks] ZOOM_DTYPE,
+        "zlags": [n_stacks][P] int32 (1/U sample), "zcorr": [n_stacks][P] float64, and with want_zmap "zmap":
+        [n_stacks][(2H+1)^2] int64}: per stack the best of the (2H+1)^2 cells of the fine table around Z x its best cell.  The
+        zoom's arrays are written over a poison pattern"""
+        _, n = self.num_stacks(windows_per_stack)
+        out = _zoom_outputs(n, self.num_pairs(), getattr(self, "_locate_cells", 0), H, want_map, want_zmap)
+        self._chk(self._L.tdoa_process_locate_zoom(self._h, int(windows_per_stack), int(min_separation), int(Z), int(H),
+                                                   int(fine_separation), *_zoom_ptrs(out)))
+        return self._with_stats(out, "loc")
+
+    def locate_zoom_from_q(self, q, n_stations, Z, H, n_w=1, min_separation=1, fine_separation=1, want_map=True, want_zmap=True):
+        """tdoa_debug_locate_zoom_from_q: the locate's and the zoom's kernels on the caller's words q [n_sets][P][2 max_lag - 1]
+        int64 (or one set) with the context's table, fine table and clocks -> what process_locate_zoom returns, n_sets for
+        n_stacks"""
+        q = np.ascontiguousarray(q, dtype=np.int64)
+        if q.ndim == 2:
+            q = q[None]
+        S = int(n_stations)
+        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
+            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
+        out = _zoom_outputs(q.shape[0], q.shape[1], getattr(self, "_locate_cells", 0), H, want_map, want_zmap)
+        self._chk(self._L.tdoa_debug_locate_zoom_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], S, int(n_w),
+                                                        int(min_separation), int(Z), int(H), int(fine_separation), *_zoom_ptrs(out)))
+        return self._with_stats(out, "loc")
+
     def upsample_q(self, q, U):
         """tdoa_debug_upsample_q: the upsampler on the caller's rows q [n_rows][2 max_lag - 1] int64 (or one row) ->
         [n_rows][(2 max_lag - 2) U + 1] int64, written over a poisoned array"""
@@ -1108,6 +1151,27 @@ def _locate_ptrs(out):
             out["map"].ctypes.data_as(C.POINTER(C.c_int64)) if "map" in out else None)
 
 
+def _poisoned(shape, dtype):
+    """an output array the library has to write every byte of"""
+    a = np.empty(shape, dtype=dtype)
+    a.view(np.uint8).reshape(-1)[:] = 0xA5
+    return a
+
+
+def _zoom_outputs(n_sets, p, n_cells, H, want_map, want_zmap):
+    side = 2 * min(max(int(H), 0), 64) + 1   # (an H out of range is refused by the library; the arrays only have to exist)
+    out = _locate_outputs(n_sets, p, n_cells, want_map)
+    out.update({"zoom": _poisoned(n_sets, ZOOM_DTYPE), "zlags": _poisoned((n_sets, p), np.int32), "zcorr": _poisoned((n_sets, p), np.float64)})
+    if want_zmap:
+        out["zmap"] = _poisoned((n_sets, side * side), np.int64)
+    return out
+
+
+def _zoom_ptrs(out):
+    return _locate_ptrs(out) + (out["zoom"].ctypes.data_as(C.c_void_p), out["zlags"].ctypes.data_as(C.POINTER(C.c_int32)), _d(out["zcorr"]),
+                                out["zmap"].ctypes.data_as(C.POINTER(C.c_int64)) if "zmap" in out else None)
+
+
 def _locate_multi_outputs(n_emitters, n_sets, p, n_cells, want_map):
     k = min(max(int(n_emitters), 1), 8)      # (a count out of range is refused by the library; the arrays only have to exist)
     out = {"loc": np.zeros((k, n_sets), dtype=LOCATION_DTYPE), "lags": np.zeros((k, n_sets, p), dtype=np.int32),
@@ -1317,6 +1381,20 @@ class Group:
     def locate_set_upsample(self, U):
         """tdoa_group_locate_set_upsample: Context.locate_set_upsample on every member"""
         self._chk(self._L.tdoa_group_locate_set_upsample(self._h, int(U)))
+
+    def locate_set_fine_table(self, table, n_cols=None):
+        """tdoa_group_locate_set_fine_table: the zoom locate's fine table to every member"""
+        ptr, n_cells, n_cols, S = _table(table, n_cols)
+        self._chk(self._L.tdoa_group_locate_set_fine_table(self._h, ptr, n_cells, n_cols, S))
+
+    def process_locate_zoom(self, Z, H, windows_per_stack=0, min_separation=1, fine_separation=1, want_map=False, want_zmap=True):
+        """tdoa_group_process_locate_zoom -> Context.process_locate_zoom's outputs, byte-identical to a single context's"""
+        m = self.member(0)
+        _, n = m.num_stacks(windows_per_stack)
+        out = _zoom_outputs(n, m.num_pairs(), getattr(self, "_locate_cells", 0), H, want_map, want_zmap)
+        self._chk(self._L.tdoa_group_process_locate_zoom(self._h, int(windows_per_stack), int(min_separation), int(Z), int(H),
+                                                         int(fine_separation), *_zoom_ptrs(out)))
+        return self._with_stats(out, "loc")
 
     _with_stats = Context._with_stats
 
