@@ -1,5 +1,6 @@
 """ctypes binding of include/tdoa_mi355x.h.  No CPU fallback: loading fails loudly if the
 HIP library is missing, and every compute call raises TdoaError on a non-zero status."""
+import collections
 import ctypes as C
 import os
 
@@ -134,6 +135,72 @@ SYMBOLS = [
     "tdoa_debug_locate_zoom_from_q",
 ]
 
+
+# ---- the stack searches (csrc/stack_search.inc), each stated once ---------------------------------------------------------
+# The header gives every search three entries of one shape: a handle; windows_per_stack (own, group) or q, n_sets, [track_len,]
+# n_stations, n_w (the caller's Q); the search's ints; ref_delay, centre; the outputs, <key>_host or <key>.  _run_search and
+# load() read the order from here, and tests/test_capi_bindings_cpu.py holds it to the header.
+_POINTER = {np.dtype(np.int32): C.POINTER(C.c_int32), np.dtype(np.float64): C.POINTER(C.c_double),
+            np.dtype(np.int64): C.POINTER(C.c_int64)}      # a record goes as void *
+_Output = collections.namedtuple("_Output", "key dtype shape want poison ctype")
+
+
+def _Out(key, dtype, shape, want=None, poison=False):
+    """an output: its key in the result, its dtype, its shape (names of _shape_numbers, or plain ints), the want_* flag that
+    selects it when it is optional, whether it starts as 0xA5 bytes and not as zeros; ctype is its pointer's argtype"""
+    return _Output(key, dtype, shape, want, poison, _POINTER.get(np.dtype(dtype), C.c_void_p))
+
+
+class _Search:
+    def __init__(self, name, ints, outputs, inputs=(), track_len=False, stats=None, bare=False):
+        self.name, self.ints, self.outputs, self.inputs = name, ints, outputs, inputs
+        self.entries = {"own": "tdoa_process_" + name, "group": "tdoa_group_process_" + name,
+                        "q": "tdoa_debug_%s_from_q" % name}
+        self.track_len = track_len           # the from-Q entry takes track_len
+        self.stats = stats                   # the key "stats" is shaped like, for the delay-table family
+        self.bare = bare                     # the result is the one array, not a dict
+
+
+def _rounds(outputs):
+    """the outputs with a leading axis of K rounds"""
+    return tuple(o._replace(shape=("K",) + o.shape) for o in outputs)
+
+
+_LOCATE_OUT = (_Out("loc", LOCATION_DTYPE, ("n_sets",)), _Out("lags", np.int32, ("n_sets", "P")),
+               _Out("corr", np.float64, ("n_sets", "P")), _Out("map", np.int64, ("n_sets", "n_cells"), "want_map"))
+_ZOOM_OUT = (_Out("zoom", ZOOM_DTYPE, ("n_sets",), poison=True), _Out("zlags", np.int32, ("n_sets", "P"), poison=True),
+             _Out("zcorr", np.float64, ("n_sets", "P"), poison=True),
+             _Out("zmap", np.int64, ("n_sets", "window"), "want_zmap", poison=True))
+_TRACK_OUT = (_Out("track", CELL_TRACK_DTYPE, ("n_tracks",)), _Out("cells", np.int32, ("n_tracks", "L")),
+              _Out("own", np.int64, ("n_tracks", "L")), _Out("lags", np.int32, ("n_sets", "P")),
+              _Out("corr", np.float64, ("n_sets", "P")), _Out("total", np.int64, ("n_tracks", "n_cells"), "want_total"))
+_SYNC_OUT = (_Out("sync", SYNC_DTYPE, ("n_sets",)), _Out("clock", np.int32, ("n_sets", "S")),
+             _Out("lags", np.int32, ("n_sets", "P")), _Out("corr", np.float64, ("n_sets", "P")))
+_CLOCKS = ("ref_delay", "centre")
+SEARCHES = {s.name: s for s in (
+    _Search("closure", ("gate", "min_separation"), (_Out("closure", CLOSURE_DTYPE, ("n_sets", "T")),), ("centre",), bare=True),
+    _Search("locate", ("min_separation",), _LOCATE_OUT, stats="loc"),
+    _Search("locate_multi", ("n_emitters", "guard", "min_separation"), _rounds(_LOCATE_OUT), stats="loc"),
+    _Search("locate_track", ("max_step", "min_separation"), _TRACK_OUT, track_len=True, stats="track"),
+    _Search("locate_track_multi", ("max_step", "n_emitters", "guard", "min_separation"),
+            _rounds(_TRACK_OUT[:3] + (_Out("pairs", np.int32, ("n_sets", 2)),) + _TRACK_OUT[3:]), track_len=True, stats="track"),
+    _Search("locate_zoom", ("min_separation", "Z", "H", "fine_separation"), _LOCATE_OUT + _ZOOM_OUT, stats="loc"),
+    _Search("sync", ("gate", "rounds"), _SYNC_OUT, _CLOCKS),
+    _Search("sync_fine", ("gate", "rounds", "U", "fine_rounds"),
+            _SYNC_OUT + (_Out("fine", SYNC_DTYPE, ("n_sets",)), _Out("clock16", np.int32, ("n_sets", "S")),
+                         _Out("fine_lags", np.int32, ("n_sets", "P")), _Out("fine_corr", np.float64, ("n_sets", "P"))), _CLOCKS),
+    _Search("sync_drift", ("gate", "max_drift", "drift_den", "rounds"),
+            (_Out("line", SYNC_LINE_DTYPE, ("n_tracks",)), _Out("clock", np.int32, ("n_tracks", "S")),
+             _Out("rate", np.int32, ("n_tracks", "S")), _Out("rows", np.int32, ("n_sets", "S")),
+             _Out("lags", np.int32, ("n_sets", "P")), _Out("corr", np.float64, ("n_sets", "P"))), _CLOCKS, track_len=True),
+)}
+def _search_argtypes(s, route):
+    """the argtypes of search s's entry `route`"""
+    i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    shape = [i64p] + [C.c_int] * (3 + s.track_len) if route == "q" else [C.c_int]
+    return [C.c_void_p] + shape + [C.c_int] * len(s.ints) + [i32p] * len(s.inputs) + [o.ctype for o in s.outputs]
+
+
 _lib = None
 
 
@@ -242,38 +309,13 @@ def load(build_if_missing=True):
                                              C.POINTER(C.c_int64), i32p, vp]
     L.tdoa_process_track.argtypes = [vp, C.c_int, C.c_int, vp, i32p, dp, fp, C.POINTER(C.c_int64)]
     L.tdoa_num_triples.argtypes = [vp]
-    L.tdoa_process_closure.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, vp]
-    L.tdoa_group_process_closure.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, vp]
-    L.tdoa_debug_closure_from_q.argtypes = [vp, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, vp]
     i64p = C.POINTER(C.c_int64)
     L.tdoa_locate_set_table.argtypes = [vp, i32p, C.c_int, C.c_int, C.c_int]
     L.tdoa_group_locate_set_table.argtypes = [vp, i32p, C.c_int, C.c_int, C.c_int]
-    L.tdoa_process_locate.argtypes = [vp, C.c_int, C.c_int, vp, i32p, dp, i64p]
-    L.tdoa_group_process_locate.argtypes = [vp, C.c_int, C.c_int, vp, i32p, dp, i64p]
-    L.tdoa_debug_locate_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p, dp, i64p]
     L.tdoa_locate_grid_table.argtypes = [dp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
                                          C.c_double, C.c_double, i32p]
     L.tdoa_locate_set_clock.argtypes = [vp, i32p, C.c_int, C.c_int]
     L.tdoa_group_locate_set_clock.argtypes = [vp, i32p, C.c_int, C.c_int]
-    L.tdoa_process_sync.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, vp, i32p, i32p, dp]
-    L.tdoa_group_process_sync.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, vp, i32p, i32p, dp]
-    L.tdoa_process_locate_track.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, i32p, i64p, i32p, dp, i64p]
-    L.tdoa_group_process_locate_track.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, i32p, i64p, i32p, dp, i64p]
-    L.tdoa_process_locate_multi.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p, dp, i64p]
-    L.tdoa_group_process_locate_multi.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p, dp, i64p]
-    L.tdoa_debug_locate_multi_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p, dp, i64p]
-    L.tdoa_debug_locate_track_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i32p, i64p, i32p,
-                                                 dp, i64p]
-    L.tdoa_process_locate_track_multi.argtypes = [vp] + [C.c_int] * 5 + [vp, i32p, i64p, i32p, i32p, dp, i64p]
-    L.tdoa_group_process_locate_track_multi.argtypes = [vp] + [C.c_int] * 5 + [vp, i32p, i64p, i32p, i32p, dp, i64p]
-    L.tdoa_debug_locate_track_multi_from_q.argtypes = [vp, i64p] + [C.c_int] * 8 + [vp, i32p, i64p, i32p, i32p, dp, i64p]
-    L.tdoa_debug_sync_from_q.argtypes = [vp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, vp, i32p, i32p, dp]
-    L.tdoa_process_sync_fine.argtypes = [vp] + [C.c_int] * 5 + [i32p, i32p, vp, i32p, i32p, dp, vp, i32p, i32p, dp]
-    L.tdoa_group_process_sync_fine.argtypes = [vp] + [C.c_int] * 5 + [i32p, i32p, vp, i32p, i32p, dp, vp, i32p, i32p, dp]
-    L.tdoa_debug_sync_fine_from_q.argtypes = [vp, i64p] + [C.c_int] * 7 + [i32p, i32p, vp, i32p, i32p, dp, vp, i32p, i32p, dp]
-    L.tdoa_process_sync_drift.argtypes = [vp] + [C.c_int] * 5 + [i32p, i32p, vp, i32p, i32p, i32p, i32p, dp]
-    L.tdoa_group_process_sync_drift.argtypes = [vp] + [C.c_int] * 5 + [i32p, i32p, vp, i32p, i32p, i32p, i32p, dp]
-    L.tdoa_debug_sync_drift_from_q.argtypes = [vp, i64p] + [C.c_int] * 8 + [i32p, i32p, vp, i32p, i32p, i32p, i32p, dp]
     L.tdoa_sync_line_clock.argtypes = [i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, i32p]
     L.tdoa_locate_set_stats.argtypes = [vp, C.POINTER(C.c_uint16), C.c_int, C.c_int]
     L.tdoa_group_locate_set_stats.argtypes = [vp, C.POINTER(C.c_uint16), C.c_int, C.c_int]
@@ -282,14 +324,14 @@ def load(build_if_missing=True):
     L.tdoa_locate_set_upsample.argtypes = [vp, C.c_int]
     L.tdoa_locate_set_fine_table.argtypes = [vp, i32p, C.c_int, C.c_int, C.c_int]
     L.tdoa_group_locate_set_fine_table.argtypes = [vp, i32p, C.c_int, C.c_int, C.c_int]
-    L.tdoa_process_locate_zoom.argtypes = [vp] + [C.c_int] * 5 + [vp, i32p, dp, i64p, vp, i32p, dp, i64p]
-    L.tdoa_group_process_locate_zoom.argtypes = [vp] + [C.c_int] * 5 + [vp, i32p, dp, i64p, vp, i32p, dp, i64p]
-    L.tdoa_debug_locate_zoom_from_q.argtypes = [vp, i64p] + [C.c_int] * 7 + [vp, i32p, dp, i64p, vp, i32p, dp, i64p]
     L.tdoa_group_locate_set_upsample.argtypes = [vp, C.c_int]
     L.tdoa_locate_upsample_taps.argtypes = [C.c_int, i32p]
     L.tdoa_debug_upsample_q.argtypes = [vp, i64p, C.c_int, C.c_int, i64p]
     L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
                                         C.POINTER(C.c_int)]
+    for s in SEARCHES.values():
+        for route, entry in s.entries.items():
+            getattr(L, entry).argtypes = _search_argtypes(s, route)
     _lib = L
     return L
 
@@ -655,26 +697,13 @@ class Context:
         close (lag_ij + lag_jk = lag_ik) with the largest summed magnitude within `gate` lags of the pairs' centres
         (centre: one int per station, None: all 0), next to what the three independent argmaxes give (own_q, residual)
         and the runner-up"""
-        _, n = self.num_stacks(windows_per_stack)
-        out = np.zeros((n, self.num_triples()), dtype=CLOSURE_DTYPE)
-        self._chk(self._L.tdoa_process_closure(self._h, int(windows_per_stack), int(gate), int(min_separation),
-                                               _centre(centre, self.num_stations()), out.ctypes.data_as(C.c_void_p)))
-        return out
+        return _process_search(self, self, "closure", dict(
+            windows_per_stack=windows_per_stack, gate=gate, min_separation=min_separation, centre=centre), T=self.num_triples())
 
     def closure_from_q(self, q, n_stations, n_w=1, gate=0, min_separation=1, centre=None):
         """tdoa_debug_closure_from_q: the closure kernels on the caller's words q [n_sets][P][2 max_lag - 1] int64 (or one
         set [P][2 max_lag - 1]) -> [n_sets][T] CLOSURE_DTYPE"""
-        q = np.ascontiguousarray(q, dtype=np.int64)
-        if q.ndim == 2:
-            q = q[None]
-        S = int(n_stations)
-        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
-            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
-        out = np.zeros((q.shape[0], max(S * (S - 1) * (S - 2) // 6, 1)), dtype=CLOSURE_DTYPE)
-        self._chk(self._L.tdoa_debug_closure_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], S, int(n_w),
-                                                    int(gate), int(min_separation), _centre(centre, S),
-                                                    out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._from_q("closure", q, n_stations, dict(n_w=n_w, gate=gate, min_separation=min_separation, centre=centre))
 
     def locate_set_table(self, table, n_cols=None):
         """tdoa_locate_set_table: table [n_cells][n_stations] int32 delays in units of 1/16 sample; n_cols gives cells their
@@ -687,24 +716,13 @@ class Context:
         """tdoa_process_locate -> {"loc": [n_stacks] LOCATION_DTYPE, "lags": [n_stacks][P] int32, "corr": [n_stacks][P]
         float64, and with want_map "map": [n_stacks][n_cells] int64}: per stack the table's cell with the largest summed
         magnitude of all pairs' stacks at the cell's lags, the runner-up, and the lags and signed correlations there"""
-        _, n = self.num_stacks(windows_per_stack)
-        out = _locate_outputs(n, self.num_pairs(), getattr(self, "_locate_cells", 0), want_map)
-        self._chk(self._L.tdoa_process_locate(self._h, int(windows_per_stack), int(min_separation), *_locate_ptrs(out)))
-        return self._with_stats(out, "loc")
+        return _process_search(self, self, "locate", dict(
+            windows_per_stack=windows_per_stack, min_separation=min_separation, want_map=want_map))
 
     def locate_from_q(self, q, n_stations, n_w=1, min_separation=1, want_map=True):
         """tdoa_debug_locate_from_q: the search's kernels on the caller's words q [n_sets][P][2 max_lag - 1] int64 (or one
         set [P][2 max_lag - 1]) with the context's table -> what process_locate returns, n_sets for n_stacks"""
-        q = np.ascontiguousarray(q, dtype=np.int64)
-        if q.ndim == 2:
-            q = q[None]
-        S = int(n_stations)
-        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
-            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
-        out = _locate_outputs(q.shape[0], q.shape[1], getattr(self, "_locate_cells", 0), want_map)
-        self._chk(self._L.tdoa_debug_locate_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], S, int(n_w),
-                                                   int(min_separation), *_locate_ptrs(out)))
-        return self._with_stats(out, "loc")
+        return self._from_q("locate", q, n_stations, dict(n_w=n_w, min_separation=min_separation, want_map=want_map))
 
     def locate_set_clock(self, clock):
         """tdoa_locate_set_clock: clock [n_stacks][n_stations] int32 station clocks in units of 1/16 sample, one row per stack
@@ -741,26 +759,17 @@ class Context:
         "zlags": [n_stacks][P] int32 (1/U sample), "zcorr": [n_stacks][P] float64, and with want_zmap "zmap":
         [n_stacks][(2H+1)^2] int64}: per stack the best of the (2H+1)^2 cells of the fine table around Z x its best cell.  The
         zoom's arrays are written over a poison pattern"""
-        _, n = self.num_stacks(windows_per_stack)
-        out = _zoom_outputs(n, self.num_pairs(), getattr(self, "_locate_cells", 0), H, want_map, want_zmap)
-        self._chk(self._L.tdoa_process_locate_zoom(self._h, int(windows_per_stack), int(min_separation), int(Z), int(H),
-                                                   int(fine_separation), *_zoom_ptrs(out)))
-        return self._with_stats(out, "loc")
+        return _process_search(self, self, "locate_zoom", dict(
+            windows_per_stack=windows_per_stack, min_separation=min_separation, Z=Z, H=H, fine_separation=fine_separation,
+            want_map=want_map, want_zmap=want_zmap))
 
     def locate_zoom_from_q(self, q, n_stations, Z, H, n_w=1, min_separation=1, fine_separation=1, want_map=True, want_zmap=True):
         """tdoa_debug_locate_zoom_from_q: the locate's and the zoom's kernels on the caller's words q [n_sets][P][2 max_lag - 1]
         int64 (or one set) with the context's table, fine table and clocks -> what process_locate_zoom returns, n_sets for
         n_stacks"""
-        q = np.ascontiguousarray(q, dtype=np.int64)
-        if q.ndim == 2:
-            q = q[None]
-        S = int(n_stations)
-        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
-            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
-        out = _zoom_outputs(q.shape[0], q.shape[1], getattr(self, "_locate_cells", 0), H, want_map, want_zmap)
-        self._chk(self._L.tdoa_debug_locate_zoom_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], S, int(n_w),
-                                                        int(min_separation), int(Z), int(H), int(fine_separation), *_zoom_ptrs(out)))
-        return self._with_stats(out, "loc")
+        return self._from_q("locate_zoom", q, n_stations, dict(
+            n_w=n_w, min_separation=min_separation, Z=Z, H=H, fine_separation=fine_separation, want_map=want_map,
+            want_zmap=want_zmap))
 
     def upsample_q(self, q, U):
         """tdoa_debug_upsample_q: the upsampler on the caller's rows q [n_rows][2 max_lag - 1] int64 (or one row) ->
@@ -777,6 +786,14 @@ class Context:
                                                 out.ctypes.data_as(C.POINTER(C.c_int64))))
         return out[0] if one else out
 
+    def _from_q(self, name, q, n_stations, values):
+        """search `name` on the caller's words q"""
+        s, S = SEARCHES[name], int(n_stations)
+        q = _q_sets(q, S, self.params.max_lag)
+        n = _shape_numbers(values, q.shape[0], S, getattr(self, "_locate_cells", 0), values.get("track_len", 1))
+        out = _run_search(s, "q", getattr(self._L, s.entries["q"]), self._h, self._chk, n, values, q)
+        return self._with_stats(out, s.stats) if s.stats else out
+
     def _with_stats(self, out, like):
         """out with "stats" shaped like out[like] while the setting is on"""
         if getattr(self, "_stats_on", False):
@@ -788,54 +805,29 @@ class Context:
         int32, "corr": [n_stacks][P] float64}: per stack the station clocks k_s = centre[s] + x_s, |x_s| <= gate, k_0 =
         centre[0], that make all pairs' stacks largest at the lags the known emitter's delays ref_delay [S] (units of 1/16
         sample) predict; a joint start, the placing and `rounds` sweeps"""
-        _, n = self.num_stacks(windows_per_stack)
-        S = self.num_stations()
-        out = _sync_outputs(n, S)
-        self._chk(self._L.tdoa_process_sync(self._h, int(windows_per_stack), int(gate), int(rounds), _ref_delay(ref_delay, S),
-                                            _centre(centre, S), *_sync_ptrs(out)))
-        return out
+        return _process_search(self, self, "sync", dict(
+            windows_per_stack=windows_per_stack, gate=gate, rounds=rounds, ref_delay=ref_delay, centre=centre))
 
     def sync_from_q(self, q, ref_delay, n_w=1, gate=0, rounds=0, centre=None):
         """tdoa_debug_sync_from_q: the clock search's kernels on the caller's words q [n_sets][P][2 max_lag - 1] int64 (or
         one set [P][2 max_lag - 1]) -> what process_sync returns, n_sets for n_stacks"""
-        q = np.ascontiguousarray(q, dtype=np.int64)
-        if q.ndim == 2:
-            q = q[None]
-        S = int(np.size(ref_delay))
-        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
-            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
-        out = _sync_outputs(q.shape[0], S)
-        self._chk(self._L.tdoa_debug_sync_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], S, int(n_w),
-                                                 int(gate), int(rounds), _ref_delay(ref_delay, S), _centre(centre, S),
-                                                 *_sync_ptrs(out)))
-        return out
+        return self._from_q("sync", q, np.size(ref_delay), dict(
+            n_w=n_w, gate=gate, rounds=rounds, ref_delay=ref_delay, centre=centre))
 
     def process_sync_fine(self, ref_delay, windows_per_stack=0, gate=0, rounds=0, U=16, fine_rounds=2, centre=None):
         """tdoa_process_sync_fine -> process_sync's outputs (the coarse stage's bytes) and {"fine": [n_stacks] SYNC_DTYPE,
         "clock16": [n_stacks][S] int32 (1/16 sample: tdoa_locate_set_clock's unit), "fine_lags": [n_stacks][P] int32 (1/U
         sample), "fine_corr": [n_stacks][P] float64}: the coarse clocks moved by |y_s| <= U fine lags in `fine_rounds` sweeps
         on the words of the surfaces upsampled to 1/U sample"""
-        _, n = self.num_stacks(windows_per_stack)
-        S = self.num_stations()
-        out = _sync_fine_outputs(n, S)
-        self._chk(self._L.tdoa_process_sync_fine(self._h, int(windows_per_stack), int(gate), int(rounds), int(U), int(fine_rounds),
-                                                 _ref_delay(ref_delay, S), _centre(centre, S), *_sync_fine_ptrs(out)))
-        return out
+        return _process_search(self, self, "sync_fine", dict(
+            windows_per_stack=windows_per_stack, gate=gate, rounds=rounds, U=U, fine_rounds=fine_rounds, ref_delay=ref_delay,
+            centre=centre))
 
     def sync_fine_from_q(self, q, ref_delay, n_w=1, gate=0, rounds=0, U=16, fine_rounds=2, centre=None):
         """tdoa_debug_sync_fine_from_q: the clock search's and the refinement's kernels on the caller's words q
         [n_sets][P][2 max_lag - 1] int64 (or one set [P][2 max_lag - 1]) -> what process_sync_fine returns, n_sets for n_stacks"""
-        q = np.ascontiguousarray(q, dtype=np.int64)
-        if q.ndim == 2:
-            q = q[None]
-        S = int(np.size(ref_delay))
-        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
-            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
-        out = _sync_fine_outputs(q.shape[0], S)
-        self._chk(self._L.tdoa_debug_sync_fine_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], S, int(n_w),
-                                                      int(gate), int(rounds), int(U), int(fine_rounds), _ref_delay(ref_delay, S),
-                                                      _centre(centre, S), *_sync_fine_ptrs(out)))
-        return out
+        return self._from_q("sync_fine", q, np.size(ref_delay), dict(
+            n_w=n_w, gate=gate, rounds=rounds, U=U, fine_rounds=fine_rounds, ref_delay=ref_delay, centre=centre))
 
     def process_sync_drift(self, ref_delay, windows_per_stack=0, gate=0, max_drift=0, drift_den=1, rounds=0, centre=None):
         """tdoa_process_sync_drift -> {"line": [3] SYNC_LINE_DTYPE, "clock": [3][S] int32 (samples), "rate": [3][S] int32,
@@ -843,28 +835,17 @@ class Context:
         [n_stacks][P] float64}: per block the station clocks k_s(j) = k_s + shift(h_s, j), |k_s - centre[s]| <= gate, |h_s| <=
         max_drift in units of 1 / drift_den lag per stack, that make all pairs' signed sums along the block's stacks largest
         at the lags the known emitter's delays ref_delay [S] predict; the placing and `rounds` sweeps"""
-        _, n = self.num_stacks(windows_per_stack)
-        S = self.num_stations()
-        out = _sync_line_outputs(3, n, S)
-        self._chk(self._L.tdoa_process_sync_drift(self._h, int(windows_per_stack), int(gate), int(max_drift), int(drift_den), int(rounds),
-                                                  _ref_delay(ref_delay, S), _centre(centre, S), *_sync_line_ptrs(out)))
-        return out
+        return _process_search(self, self, "sync_drift", dict(
+            windows_per_stack=windows_per_stack, gate=gate, max_drift=max_drift, drift_den=drift_den, rounds=rounds,
+            ref_delay=ref_delay, centre=centre), n_tracks=3)
 
     def sync_drift_from_q(self, q, ref_delay, track_len, n_w=1, gate=0, max_drift=0, drift_den=1, rounds=0, centre=None):
         """tdoa_debug_sync_drift_from_q: the clock-line search's kernels on the caller's words q [n_sets][P][2 max_lag - 1]
         int64, set t track_len + j position j of line t -> what process_sync_drift returns, n_sets / track_len lines and
         n_sets stacks"""
-        q = np.ascontiguousarray(q, dtype=np.int64)
-        if q.ndim == 2:
-            q = q[None]
-        S = int(np.size(ref_delay))
-        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
-            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
-        out = _sync_line_outputs(q.shape[0] // max(int(track_len), 1), q.shape[0], S)
-        self._chk(self._L.tdoa_debug_sync_drift_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], int(track_len), S,
-                                                       int(n_w), int(gate), int(max_drift), int(drift_den), int(rounds),
-                                                       _ref_delay(ref_delay, S), _centre(centre, S), *_sync_line_ptrs(out)))
-        return out
+        return self._from_q("sync_drift", q, np.size(ref_delay), dict(
+            track_len=track_len, n_w=n_w, gate=gate, max_drift=max_drift, drift_den=drift_den, rounds=rounds,
+            ref_delay=ref_delay, centre=centre))
 
     def process_locate_track(self, windows_per_stack=0, max_step=0, min_separation=1, want_total=False):
         """tdoa_process_locate_track -> {"track": [n_tracks] CELL_TRACK_DTYPE, "cells": [n_tracks][L] int32, "own":
@@ -872,79 +853,47 @@ class Context:
         [n_tracks][n_cells] int64}: per block the track of cells through its stacks' maps, consecutive cells at most max_step
         rows and columns apart, with the largest summed score; the runner-up; per stack the lags and signed correlations at
         the track's cell"""
-        per_block, n = self.num_stacks(windows_per_stack)
-        out = _locate_track_outputs(n, per_block, self.num_pairs(), getattr(self, "_locate_cells", 0), want_total)
-        self._chk(self._L.tdoa_process_locate_track(self._h, int(windows_per_stack), int(max_step), int(min_separation),
-                                                    *_locate_track_ptrs(out)))
-        return self._with_stats(out, "track")
+        return _process_search(self, self, "locate_track", dict(
+            windows_per_stack=windows_per_stack, max_step=max_step, min_separation=min_separation, want_total=want_total))
 
     def locate_track_from_q(self, q, n_stations, track_len, n_w=1, max_step=0, min_separation=1, want_total=True):
         """tdoa_debug_locate_track_from_q: the search's and the recurrence's kernels on the caller's words q
         [n_sets][P][2 max_lag - 1] int64, set t track_len + j position j of track t, with the context's table and clocks ->
         what process_locate_track returns, n_sets for n_stacks"""
-        q = np.ascontiguousarray(q, dtype=np.int64)
-        if q.ndim == 2:
-            q = q[None]
-        S = int(n_stations)
-        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
-            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
-        out = _locate_track_outputs(q.shape[0], max(int(track_len), 1), q.shape[1], getattr(self, "_locate_cells", 0), want_total)
-        self._chk(self._L.tdoa_debug_locate_track_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], int(track_len), S,
-                                                         int(n_w), int(max_step), int(min_separation), *_locate_track_ptrs(out)))
-        return self._with_stats(out, "track")
+        return self._from_q("locate_track", q, n_stations, dict(
+            track_len=track_len, n_w=n_w, max_step=max_step, min_separation=min_separation, want_total=want_total))
 
     def process_locate_multi(self, windows_per_stack=0, n_emitters=1, guard=0, min_separation=1, want_map=False):
         """tdoa_process_locate_multi -> process_locate's dict with a leading axis of n_emitters rounds: "loc" [K][n_stacks],
         "lags" and "corr" [K][n_stacks][P], with want_map "map" [K][n_stacks][n_cells].  Round r searches with the lags within
         `guard` of the earlier rounds' cells' lags counting 0 in every pair"""
-        _, n = self.num_stacks(windows_per_stack)
-        out = _locate_multi_outputs(n_emitters, n, self.num_pairs(), getattr(self, "_locate_cells", 0), want_map)
-        self._chk(self._L.tdoa_process_locate_multi(self._h, int(windows_per_stack), int(n_emitters), int(guard), int(min_separation),
-                                                    *_locate_ptrs(out)))
-        return self._with_stats(out, "loc")
+        return _process_search(self, self, "locate_multi", dict(
+            windows_per_stack=windows_per_stack, n_emitters=n_emitters, guard=guard, min_separation=min_separation,
+            want_map=want_map))
 
     def locate_multi_from_q(self, q, n_stations, n_w=1, n_emitters=1, guard=0, min_separation=1, want_map=True):
         """tdoa_debug_locate_multi_from_q: the rounds' kernels on the caller's words q [n_sets][P][2 max_lag - 1] int64 (or one
         set [P][2 max_lag - 1]) with the context's table and clocks -> what process_locate_multi returns, n_sets for n_stacks"""
-        q = np.ascontiguousarray(q, dtype=np.int64)
-        if q.ndim == 2:
-            q = q[None]
-        S = int(n_stations)
-        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
-            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
-        out = _locate_multi_outputs(n_emitters, q.shape[0], q.shape[1], getattr(self, "_locate_cells", 0), want_map)
-        self._chk(self._L.tdoa_debug_locate_multi_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], S, int(n_w),
-                                                         int(n_emitters), int(guard), int(min_separation), *_locate_ptrs(out)))
-        return self._with_stats(out, "loc")
+        return self._from_q("locate_multi", q, n_stations, dict(
+            n_w=n_w, n_emitters=n_emitters, guard=guard, min_separation=min_separation, want_map=want_map))
 
     def process_locate_track_multi(self, windows_per_stack=0, max_step=0, n_emitters=1, guard=0, min_separation=1, want_total=False):
         """tdoa_process_locate_track_multi -> process_locate_track's dict with a leading axis of n_emitters rounds: "track"
         [K][n_tracks], "cells" and "own" [K][n_tracks][L], "lags" and "corr" [K][n_stacks][P], "pairs" [K][n_stacks][2] int32
         (pairs_in, reserved), with want_total "total" [K][n_tracks][n_cells].  Round r tracks with the lags within `guard` of
         the earlier rounds' tracks' lags counting 0 in every stack's pairs"""
-        per_block, n = self.num_stacks(windows_per_stack)
-        out = _locate_track_multi_outputs(n_emitters, n, per_block, self.num_pairs(), getattr(self, "_locate_cells", 0), want_total)
-        self._chk(self._L.tdoa_process_locate_track_multi(self._h, int(windows_per_stack), int(max_step), int(n_emitters), int(guard),
-                                                          int(min_separation), *_locate_track_multi_ptrs(out)))
-        return self._with_stats(out, "track")
+        return _process_search(self, self, "locate_track_multi", dict(
+            windows_per_stack=windows_per_stack, max_step=max_step, n_emitters=n_emitters, guard=guard,
+            min_separation=min_separation, want_total=want_total))
 
     def locate_track_multi_from_q(self, q, n_stations, track_len, n_w=1, max_step=0, n_emitters=1, guard=0, min_separation=1,
                                   want_total=True):
         """tdoa_debug_locate_track_multi_from_q: the rounds' kernels on the caller's words q [n_sets][P][2 max_lag - 1] int64, set
         t track_len + j position j of track t, with the context's table and clocks -> what process_locate_track_multi returns,
         n_sets for n_stacks"""
-        q = np.ascontiguousarray(q, dtype=np.int64)
-        if q.ndim == 2:
-            q = q[None]
-        S = int(n_stations)
-        if q.ndim != 3 or q.shape[1:] != (S * (S - 1) // 2, 2 * self.params.max_lag - 1):
-            raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
-        out = _locate_track_multi_outputs(n_emitters, q.shape[0], max(int(track_len), 1), q.shape[1], getattr(self, "_locate_cells", 0),
-                                          want_total)
-        self._chk(self._L.tdoa_debug_locate_track_multi_from_q(self._h, q.ctypes.data_as(C.POINTER(C.c_int64)), q.shape[0], int(track_len),
-                                                               S, int(n_w), int(max_step), int(n_emitters), int(guard),
-                                                               int(min_separation), *_locate_track_multi_ptrs(out)))
-        return self._with_stats(out, "track")
+        return self._from_q("locate_track_multi", q, n_stations, dict(
+            track_len=track_len, n_w=n_w, max_step=max_step, n_emitters=n_emitters, guard=guard, min_separation=min_separation,
+            want_total=want_total))
 
     def fm_xcorr_peaks(self, iq1, iq2, max_lag, k, min_separation):
         """tdoa_fm_xcorr_peaks_u8 -> (peaks [k] PEAK_DTYPE, count) of one pair of windows"""
@@ -1098,57 +1047,14 @@ def _ref_delay(ref_delay, n_stations):
     return r.ctypes.data_as(C.POINTER(C.c_int32))
 
 
-def _sync_outputs(n_sets, n_stations):
-    p = n_stations * (n_stations - 1) // 2
-    return {"sync": np.zeros(n_sets, dtype=SYNC_DTYPE), "clock": np.zeros((n_sets, n_stations), dtype=np.int32),
-            "lags": np.zeros((n_sets, p), dtype=np.int32), "corr": np.zeros((n_sets, p), dtype=np.float64)}
-
-
-def _sync_ptrs(out):
-    i32p = C.POINTER(C.c_int32)
-    return (out["sync"].ctypes.data_as(C.c_void_p), out["clock"].ctypes.data_as(i32p), out["lags"].ctypes.data_as(i32p),
-            _d(out["corr"]))
-
-
-def _sync_fine_outputs(n_sets, n_stations):
-    p = n_stations * (n_stations - 1) // 2
-    out = _sync_outputs(n_sets, n_stations)
-    out.update({"fine": np.zeros(n_sets, dtype=SYNC_DTYPE), "clock16": np.zeros((n_sets, n_stations), dtype=np.int32),
-                "fine_lags": np.zeros((n_sets, p), dtype=np.int32), "fine_corr": np.zeros((n_sets, p), dtype=np.float64)})
-    return out
-
-
-def _sync_fine_ptrs(out):
-    i32p = C.POINTER(C.c_int32)
-    return _sync_ptrs(out) + (out["fine"].ctypes.data_as(C.c_void_p), out["clock16"].ctypes.data_as(i32p),
-                              out["fine_lags"].ctypes.data_as(i32p), _d(out["fine_corr"]))
-
-
-def _sync_line_outputs(n_lines, n_sets, n_stations):
-    p = n_stations * (n_stations - 1) // 2
-    n_lines = max(int(n_lines), 1)           # (the library refuses a call without a whole line)
-    return {"line": np.zeros(n_lines, dtype=SYNC_LINE_DTYPE), "clock": np.zeros((n_lines, n_stations), dtype=np.int32),
-            "rate": np.zeros((n_lines, n_stations), dtype=np.int32), "rows": np.zeros((n_sets, n_stations), dtype=np.int32),
-            "lags": np.zeros((n_sets, p), dtype=np.int32), "corr": np.zeros((n_sets, p), dtype=np.float64)}
-
-
-def _sync_line_ptrs(out):
-    i32p = C.POINTER(C.c_int32)
-    return (out["line"].ctypes.data_as(C.c_void_p), out["clock"].ctypes.data_as(i32p), out["rate"].ctypes.data_as(i32p),
-            out["rows"].ctypes.data_as(i32p), out["lags"].ctypes.data_as(i32p), _d(out["corr"]))
-
-
-def _locate_outputs(n_sets, p, n_cells, want_map):
-    out = {"loc": np.zeros(n_sets, dtype=LOCATION_DTYPE), "lags": np.zeros((n_sets, p), dtype=np.int32),
-           "corr": np.zeros((n_sets, p), dtype=np.float64)}
-    if want_map:
-        out["map"] = np.zeros((n_sets, n_cells), dtype=np.int64)
-    return out
-
-
-def _locate_ptrs(out):
-    return (out["loc"].ctypes.data_as(C.c_void_p), out["lags"].ctypes.data_as(C.POINTER(C.c_int32)), _d(out["corr"]),
-            out["map"].ctypes.data_as(C.POINTER(C.c_int64)) if "map" in out else None)
+def _q_sets(q, n_stations, max_lag):
+    """the caller's words as the from-Q entries take them: [n_sets][P][2 max_lag - 1] int64, one set promoted"""
+    q = np.ascontiguousarray(q, dtype=np.int64)
+    if q.ndim == 2:
+        q = q[None]
+    if q.ndim != 3 or q.shape[1:] != (n_stations * (n_stations - 1) // 2, 2 * max_lag - 1):
+        raise ValueError("q must be [n_sets][S (S-1) / 2][2 max_lag - 1]")
+    return q
 
 
 def _poisoned(shape, dtype):
@@ -1158,61 +1064,63 @@ def _poisoned(shape, dtype):
     return a
 
 
+def _shape_numbers(values, n_sets, S, n_cells=0, track_len=1, **given):
+    """the numbers the outputs' shapes name.  A count the library refuses is clamped: the arrays only have to exist.  `given`
+    states P, T or n_tracks where the caller knows them better"""
+    n = {"n_sets": n_sets, "S": S, "n_cells": n_cells, "P": S * (S - 1) // 2, "T": max(S * (S - 1) * (S - 2) // 6, 1),
+         "L": max(int(track_len), 1), "K": min(max(int(values.get("n_emitters", 1)), 1), 8),
+         "window": (2 * min(max(int(values.get("H", 0)), 0), 64) + 1) ** 2}
+    n["n_tracks"] = max(n_sets // n["L"], 1)             # (the library refuses a call without a whole track or line)
+    n.update(given)
+    return n
+
+
+def _search_outputs(s, n, values):
+    """{key: array} of search s's outputs; an optional one only where values[its flag] asks for it"""
+    return {o.key: (_poisoned if o.poison else np.zeros)([n.get(d, d) for d in o.shape], o.dtype)
+            for o in s.outputs if o.want is None or values[o.want]}
+
+
+def _search_ptrs(s, out):
+    """the outputs' pointers in the header's order, None for one that is absent"""
+    return [out[o.key].ctypes.data_as(o.ctype) if o.key in out else None for o in s.outputs]
+
+
+_INPUT = {"ref_delay": _ref_delay, "centre": _centre}
+
+
+def _run_search(s, route, fn, handle, chk, n, values, q=None):
+    """One call of search s (a SEARCHES record) through `route`: "own", "group", or "q" with the caller's words q (_q_sets').
+    fn is that entry's C function and chk raises on its status; n are the _shape_numbers; values holds what the caller gave,
+    by the header's parameter names: windows_per_stack or (track_len,) n_w, s.ints, s.inputs and the want_* flags"""
+    out = _search_outputs(s, n, values)
+    if route == "q":
+        shape = ([q.ctypes.data_as(C.POINTER(C.c_int64)), n["n_sets"]] + ([int(values["track_len"])] if s.track_len else []) +
+                 [n["S"], int(values["n_w"])])
+    else:
+        shape = [int(values["windows_per_stack"])]
+    chk(fn(handle, *shape, *[int(values[k]) for k in s.ints], *[_INPUT[k](values[k], n["S"]) for k in s.inputs],
+           *_search_ptrs(s, out)))
+    return out[s.outputs[0].key] if s.bare else out
+
+
+def _process_search(owner, counts, name, values, **given):
+    """search `name` on owner's own sum (a Context: counts is owner) or merged sum (a Group: counts is its member 0)"""
+    s = SEARCHES[name]
+    route = "own" if counts is owner else "group"
+    per_block, n_sets = counts.num_stacks(values["windows_per_stack"])
+    n = _shape_numbers(values, n_sets, counts.num_stations(), getattr(owner, "_locate_cells", 0), per_block, **given)
+    out = _run_search(s, route, getattr(owner._L, s.entries[route]), owner._h, owner._chk, n, values)
+    return owner._with_stats(out, s.stats) if s.stats else out
+
+
 def _zoom_outputs(n_sets, p, n_cells, H, want_map, want_zmap):
-    side = 2 * min(max(int(H), 0), 64) + 1   # (an H out of range is refused by the library; the arrays only have to exist)
-    out = _locate_outputs(n_sets, p, n_cells, want_map)
-    out.update({"zoom": _poisoned(n_sets, ZOOM_DTYPE), "zlags": _poisoned((n_sets, p), np.int32), "zcorr": _poisoned((n_sets, p), np.float64)})
-    if want_zmap:
-        out["zmap"] = _poisoned((n_sets, side * side), np.int64)
-    return out
+    return _search_outputs(SEARCHES["locate_zoom"], _shape_numbers({"H": H}, n_sets, 0, n_cells, P=p),
+                           {"want_map": want_map, "want_zmap": want_zmap})
 
 
 def _zoom_ptrs(out):
-    return _locate_ptrs(out) + (out["zoom"].ctypes.data_as(C.c_void_p), out["zlags"].ctypes.data_as(C.POINTER(C.c_int32)), _d(out["zcorr"]),
-                                out["zmap"].ctypes.data_as(C.POINTER(C.c_int64)) if "zmap" in out else None)
-
-
-def _locate_multi_outputs(n_emitters, n_sets, p, n_cells, want_map):
-    k = min(max(int(n_emitters), 1), 8)      # (a count out of range is refused by the library; the arrays only have to exist)
-    out = {"loc": np.zeros((k, n_sets), dtype=LOCATION_DTYPE), "lags": np.zeros((k, n_sets, p), dtype=np.int32),
-           "corr": np.zeros((k, n_sets, p), dtype=np.float64)}
-    if want_map:
-        out["map"] = np.zeros((k, n_sets, n_cells), dtype=np.int64)
-    return out
-
-
-def _locate_track_outputs(n_sets, track_len, p, n_cells, want_total):
-    n_tracks = max(n_sets // track_len, 1)
-    out = {"track": np.zeros(n_tracks, dtype=CELL_TRACK_DTYPE), "cells": np.zeros((n_tracks, track_len), dtype=np.int32),
-           "own": np.zeros((n_tracks, track_len), dtype=np.int64), "lags": np.zeros((n_sets, p), dtype=np.int32),
-           "corr": np.zeros((n_sets, p), dtype=np.float64)}
-    if want_total:
-        out["total"] = np.zeros((n_tracks, n_cells), dtype=np.int64)
-    return out
-
-
-def _locate_track_multi_outputs(n_emitters, n_sets, track_len, p, n_cells, want_total):
-    k = min(max(int(n_emitters), 1), 8)      # (a count out of range is refused by the library; the arrays only have to exist)
-    n_tracks = max(n_sets // track_len, 1)
-    out = {"track": np.zeros((k, n_tracks), dtype=CELL_TRACK_DTYPE), "cells": np.zeros((k, n_tracks, track_len), dtype=np.int32),
-           "own": np.zeros((k, n_tracks, track_len), dtype=np.int64), "pairs": np.zeros((k, n_sets, 2), dtype=np.int32),
-           "lags": np.zeros((k, n_sets, p), dtype=np.int32), "corr": np.zeros((k, n_sets, p), dtype=np.float64)}
-    if want_total:
-        out["total"] = np.zeros((k, n_tracks, n_cells), dtype=np.int64)
-    return out
-
-
-def _locate_track_multi_ptrs(out):
-    i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-    return (out["track"].ctypes.data_as(C.c_void_p), out["cells"].ctypes.data_as(i32p), out["own"].ctypes.data_as(i64p),
-            out["pairs"].ctypes.data_as(i32p), out["lags"].ctypes.data_as(i32p), _d(out["corr"]),
-            out["total"].ctypes.data_as(i64p) if "total" in out else None)
-
-
-def _locate_track_ptrs(out):
-    i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-    return (out["track"].ctypes.data_as(C.c_void_p), out["cells"].ctypes.data_as(i32p), out["own"].ctypes.data_as(i64p),
-            out["lags"].ctypes.data_as(i32p), _d(out["corr"]), out["total"].ctypes.data_as(i64p) if "total" in out else None)
+    return tuple(_search_ptrs(SEARCHES["locate_zoom"], out))
 
 
 def _stacked_outputs(n_stacks, p, n_lags, k, want_surface, want_partial):
@@ -1339,16 +1247,11 @@ class Group:
             _f(out["surface"]) if want_surface else None))
         return out
 
-
     def process_closure(self, windows_per_stack=0, gate=0, min_separation=1, centre=None):
         """tdoa_group_process_closure -> [n_stacks][T] CLOSURE_DTYPE, byte-identical to a single context's"""
         m = self.member(0)
-        _, n = m.num_stacks(windows_per_stack)
-        out = np.zeros((n, m.num_triples()), dtype=CLOSURE_DTYPE)
-        self._chk(self._L.tdoa_group_process_closure(self._h, int(windows_per_stack), int(gate), int(min_separation),
-                                                     _centre(centre, m.num_stations()), out.ctypes.data_as(C.c_void_p)))
-        return out
-
+        return _process_search(self, m, "closure", dict(
+            windows_per_stack=windows_per_stack, gate=gate, min_separation=min_separation, centre=centre), T=m.num_triples())
 
     def locate_set_table(self, table, n_cols=None):
         """tdoa_group_locate_set_table: the table to every member"""
@@ -1358,12 +1261,8 @@ class Group:
 
     def process_locate(self, windows_per_stack=0, min_separation=1, want_map=False):
         """tdoa_group_process_locate -> Context.process_locate's outputs, byte-identical to a single context's"""
-        m = self.member(0)
-        _, n = m.num_stacks(windows_per_stack)
-        out = _locate_outputs(n, m.num_pairs(), getattr(self, "_locate_cells", 0), want_map)
-        self._chk(self._L.tdoa_group_process_locate(self._h, int(windows_per_stack), int(min_separation), *_locate_ptrs(out)))
-        return self._with_stats(out, "loc")
-
+        return _process_search(self, self.member(0), "locate", dict(
+            windows_per_stack=windows_per_stack, min_separation=min_separation, want_map=want_map))
 
     def locate_set_clock(self, clock):
         """tdoa_group_locate_set_clock: the station clocks to every member"""
@@ -1389,72 +1288,46 @@ class Group:
 
     def process_locate_zoom(self, Z, H, windows_per_stack=0, min_separation=1, fine_separation=1, want_map=False, want_zmap=True):
         """tdoa_group_process_locate_zoom -> Context.process_locate_zoom's outputs, byte-identical to a single context's"""
-        m = self.member(0)
-        _, n = m.num_stacks(windows_per_stack)
-        out = _zoom_outputs(n, m.num_pairs(), getattr(self, "_locate_cells", 0), H, want_map, want_zmap)
-        self._chk(self._L.tdoa_group_process_locate_zoom(self._h, int(windows_per_stack), int(min_separation), int(Z), int(H),
-                                                         int(fine_separation), *_zoom_ptrs(out)))
-        return self._with_stats(out, "loc")
+        return _process_search(self, self.member(0), "locate_zoom", dict(
+            windows_per_stack=windows_per_stack, min_separation=min_separation, Z=Z, H=H, fine_separation=fine_separation,
+            want_map=want_map, want_zmap=want_zmap))
 
     _with_stats = Context._with_stats
 
     def process_locate_track(self, windows_per_stack=0, max_step=0, min_separation=1, want_total=False):
         """tdoa_group_process_locate_track -> Context.process_locate_track's outputs, byte-identical to a single context's"""
-        m = self.member(0)
-        per_block, n = m.num_stacks(windows_per_stack)
-        out = _locate_track_outputs(n, per_block, m.num_pairs(), getattr(self, "_locate_cells", 0), want_total)
-        self._chk(self._L.tdoa_group_process_locate_track(self._h, int(windows_per_stack), int(max_step), int(min_separation),
-                                                          *_locate_track_ptrs(out)))
-        return self._with_stats(out, "track")
+        return _process_search(self, self.member(0), "locate_track", dict(
+            windows_per_stack=windows_per_stack, max_step=max_step, min_separation=min_separation, want_total=want_total))
 
     def process_locate_multi(self, windows_per_stack=0, n_emitters=1, guard=0, min_separation=1, want_map=False):
         """tdoa_group_process_locate_multi -> Context.process_locate_multi's outputs, byte-identical to a single context's"""
-        m = self.member(0)
-        _, n = m.num_stacks(windows_per_stack)
-        out = _locate_multi_outputs(n_emitters, n, m.num_pairs(), getattr(self, "_locate_cells", 0), want_map)
-        self._chk(self._L.tdoa_group_process_locate_multi(self._h, int(windows_per_stack), int(n_emitters), int(guard),
-                                                          int(min_separation), *_locate_ptrs(out)))
-        return self._with_stats(out, "loc")
+        return _process_search(self, self.member(0), "locate_multi", dict(
+            windows_per_stack=windows_per_stack, n_emitters=n_emitters, guard=guard, min_separation=min_separation,
+            want_map=want_map))
 
     def process_locate_track_multi(self, windows_per_stack=0, max_step=0, n_emitters=1, guard=0, min_separation=1, want_total=False):
         """tdoa_group_process_locate_track_multi -> Context.process_locate_track_multi's outputs, byte-identical to a single
         context's"""
-        m = self.member(0)
-        per_block, n = m.num_stacks(windows_per_stack)
-        out = _locate_track_multi_outputs(n_emitters, n, per_block, m.num_pairs(), getattr(self, "_locate_cells", 0), want_total)
-        self._chk(self._L.tdoa_group_process_locate_track_multi(self._h, int(windows_per_stack), int(max_step), int(n_emitters),
-                                                                int(guard), int(min_separation), *_locate_track_multi_ptrs(out)))
-        return self._with_stats(out, "track")
+        return _process_search(self, self.member(0), "locate_track_multi", dict(
+            windows_per_stack=windows_per_stack, max_step=max_step, n_emitters=n_emitters, guard=guard,
+            min_separation=min_separation, want_total=want_total))
 
     def process_sync(self, ref_delay, windows_per_stack=0, gate=0, rounds=0, centre=None):
         """tdoa_group_process_sync -> Context.process_sync's outputs, byte-identical to a single context's"""
-        m = self.member(0)
-        _, n = m.num_stacks(windows_per_stack)
-        S = m.num_stations()
-        out = _sync_outputs(n, S)
-        self._chk(self._L.tdoa_group_process_sync(self._h, int(windows_per_stack), int(gate), int(rounds), _ref_delay(ref_delay, S),
-                                                  _centre(centre, S), *_sync_ptrs(out)))
-        return out
+        return _process_search(self, self.member(0), "sync", dict(
+            windows_per_stack=windows_per_stack, gate=gate, rounds=rounds, ref_delay=ref_delay, centre=centre))
 
     def process_sync_fine(self, ref_delay, windows_per_stack=0, gate=0, rounds=0, U=16, fine_rounds=2, centre=None):
         """tdoa_group_process_sync_fine -> Context.process_sync_fine's outputs, byte-identical to a single context's"""
-        m = self.member(0)
-        _, n = m.num_stacks(windows_per_stack)
-        S = m.num_stations()
-        out = _sync_fine_outputs(n, S)
-        self._chk(self._L.tdoa_group_process_sync_fine(self._h, int(windows_per_stack), int(gate), int(rounds), int(U), int(fine_rounds),
-                                                       _ref_delay(ref_delay, S), _centre(centre, S), *_sync_fine_ptrs(out)))
-        return out
+        return _process_search(self, self.member(0), "sync_fine", dict(
+            windows_per_stack=windows_per_stack, gate=gate, rounds=rounds, U=U, fine_rounds=fine_rounds, ref_delay=ref_delay,
+            centre=centre))
 
     def process_sync_drift(self, ref_delay, windows_per_stack=0, gate=0, max_drift=0, drift_den=1, rounds=0, centre=None):
         """tdoa_group_process_sync_drift -> Context.process_sync_drift's outputs, byte-identical to a single context's"""
-        m = self.member(0)
-        _, n = m.num_stacks(windows_per_stack)
-        S = m.num_stations()
-        out = _sync_line_outputs(3, n, S)
-        self._chk(self._L.tdoa_group_process_sync_drift(self._h, int(windows_per_stack), int(gate), int(max_drift), int(drift_den),
-                                                        int(rounds), _ref_delay(ref_delay, S), _centre(centre, S), *_sync_line_ptrs(out)))
-        return out
+        return _process_search(self, self.member(0), "sync_drift", dict(
+            windows_per_stack=windows_per_stack, gate=gate, max_drift=max_drift, drift_den=drift_den, rounds=rounds,
+            ref_delay=ref_delay, centre=centre), n_tracks=3)
 
 
 def sync_line_clock(clock, rate, drift_den, first_position, n_positions):
