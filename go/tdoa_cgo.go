@@ -586,6 +586,61 @@ func SyncLineClock(clock, rate []int32, driftDen, first, n int) ([]int32, error)
 	return out, nil
 }
 
+// SyncLinesFine is what ProcessSyncDriftFine returns: the coarse stage's outputs exactly as ProcessSyncDrift's, and the
+// refinement's: one more record per block, Clock16 [3][station] in units of 1/16 sample, FineRate [3][station] in units of
+// 1/(U driftDen) lag per stack, FineRows [stack][station] in units of 1/16 sample (what LocateSetClock takes for that block),
+// FineLags [stack][pair] in units of 1/U sample and FineCorr, the signed value of the upsampled word there.
+type SyncLinesFine struct {
+	SyncLines
+	Fine               []C.tdoa_sync_line
+	Clock16, FineRate  []int32
+	FineRows, FineLags []int32
+	FineCorr           []float64
+}
+
+func newSyncLinesFine(total, stations, pairs int) *SyncLinesFine {
+	return &SyncLinesFine{SyncLines: *newSyncLines(total, stations, pairs), Fine: make([]C.tdoa_sync_line, 3),
+		Clock16: make([]int32, 3*stations), FineRate: make([]int32, 3*stations), FineRows: make([]int32, total*stations),
+		FineLags: make([]int32, total*pairs), FineCorr: make([]float64, total*pairs)}
+}
+
+// ProcessSyncDriftFine is the fine clock lines (the header's "fine clock lines"): ProcessSyncDrift's search, then fineRounds
+// sweeps that move every station's offset by up to u fine lags of 1/u sample and its rate by up to u steps of 1/(u driftDen)
+// lag per stack (u one of 2, 4, 8, 16) on the words of the surfaces upsampled as LocateSetUpsample defines them, evaluated
+// from Q without materialising them.  SyncLineClock16 continues a fine line past its block.
+func (g *gpuCorrelator) ProcessSyncDriftFine(windowsPerStack, gate, maxDrift, driftDen, rounds, u, fineRounds int, refDelay, centre []int32) (*SyncLinesFine, error) {
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs, stations := int(C.tdoa_num_pairs(g.ctx)), len(refDelay)
+	if int(total)*pairs == 0 || stations*(stations-1)/2 != pairs {
+		return nil, fmt.Errorf("tdoa_process_sync_drift_fine: no stacks, fewer than two stations, or not one delay per station")
+	}
+	o := newSyncLinesFine(int(total), stations, pairs)
+	if rc := C.tdoa_process_sync_drift_fine(g.ctx, C.int(windowsPerStack), C.int(gate), C.int(maxDrift), C.int(driftDen), C.int(rounds),
+		C.int(u), C.int(fineRounds), tablePtr(refDelay), centrePtr(centre), &o.Line[0], i32Ptr(o.Clock), i32Ptr(o.Rate), i32Ptr(o.Rows),
+		i32Ptr(o.Lags), (*C.double)(unsafe.Pointer(&o.Corr[0])), &o.Fine[0], i32Ptr(o.Clock16), i32Ptr(o.FineRate), i32Ptr(o.FineRows),
+		i32Ptr(o.FineLags), (*C.double)(unsafe.Pointer(&o.FineCorr[0]))); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_process_sync_drift_fine: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return o, nil
+}
+
+// SyncLineClock16 continues one fine line (clock16 in units of 1/16 sample and the fine rate, one per station) over positions
+// first .. first + n - 1 in units of 1/16 sample: [position][station], what LocateSetClock takes.  Host only.
+func SyncLineClock16(clock16, fineRate []int32, u, driftDen, first, n int) ([]int32, error) {
+	if len(clock16) == 0 || len(clock16) != len(fineRate) || n < 1 {
+		return nil, fmt.Errorf("tdoa_sync_line_clock16: one clock and one rate per station, n >= 1")
+	}
+	out := make([]int32, n*len(clock16))
+	if rc := C.tdoa_sync_line_clock16(i32Ptr(clock16), i32Ptr(fineRate), C.int(len(clock16)), C.int(u), C.int(driftDen), C.int(first), C.int(n),
+		i32Ptr(out)); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_sync_line_clock16: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	return out, nil
+}
+
 // windowQuality is fastAnalyzeSamples' statistics (fast_analyzer.go:117-155) for every (window, station).
 func (g *gpuCorrelator) windowQuality(stations int) ([]C.tdoa_window_quality, error) {
 	var perBlock, total C.int
@@ -930,6 +985,28 @@ func (g *Group) ProcessSyncDrift(windowsPerStack, gate, maxDrift, driftDen, roun
 		tablePtr(refDelay), centrePtr(centre), &o.Line[0], i32Ptr(o.Clock), i32Ptr(o.Rate), i32Ptr(o.Rows), i32Ptr(o.Lags),
 		(*C.double)(unsafe.Pointer(&o.Corr[0]))); rc != C.TDOA_OK {
 		return nil, fmt.Errorf("tdoa_group_process_sync_drift: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return o, nil
+}
+
+// ProcessSyncDriftFine is gpuCorrelator.ProcessSyncDriftFine over the group: the members' fixed-point partial sums are added on
+// the host and searched on member 0, coarse stage and refinement, the same bytes one context returns.
+func (g *Group) ProcessSyncDriftFine(windowsPerStack, gate, maxDrift, driftDen, rounds, u, fineRounds int, refDelay, centre []int32) (*SyncLinesFine, error) {
+	m := C.tdoa_group_member(g.g, 0)
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(m, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs, stations := int(C.tdoa_num_pairs(m)), len(refDelay)
+	if int(total)*pairs == 0 || stations*(stations-1)/2 != pairs {
+		return nil, fmt.Errorf("tdoa_group_process_sync_drift_fine: no stacks, fewer than two stations, or not one delay per station")
+	}
+	o := newSyncLinesFine(int(total), stations, pairs)
+	if rc := C.tdoa_group_process_sync_drift_fine(g.g, C.int(windowsPerStack), C.int(gate), C.int(maxDrift), C.int(driftDen), C.int(rounds),
+		C.int(u), C.int(fineRounds), tablePtr(refDelay), centrePtr(centre), &o.Line[0], i32Ptr(o.Clock), i32Ptr(o.Rate), i32Ptr(o.Rows),
+		i32Ptr(o.Lags), (*C.double)(unsafe.Pointer(&o.Corr[0])), &o.Fine[0], i32Ptr(o.Clock16), i32Ptr(o.FineRate), i32Ptr(o.FineRows),
+		i32Ptr(o.FineLags), (*C.double)(unsafe.Pointer(&o.FineCorr[0]))); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_group_process_sync_drift_fine: %s", C.GoString(C.tdoa_group_last_error(g.g)))
 	}
 	return o, nil
 }

@@ -710,6 +710,80 @@ int tdoa_debug_sync_drift_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, in
 int tdoa_sync_line_clock(const int32_t *clock, const int32_t *rate, int n_stations, int drift_den, int first_position,
                          int n_positions, int32_t *out /* [n_positions][n_stations] */);
 
+/* Fine clock lines: the clock lines' offsets and rates refined to 1/U sample.  tdoa_process_sync_drift returns offsets in
+ * whole samples and slopes in steps of 1/D lag per position; after L positions a slope that is half a step off has put
+ * L/(2D) lags into every pair of the block the line is continued over, more than the upsampled locate gains.
+ * tdoa_process_sync_drift_fine runs that search unchanged and, behind it in the same step graph, refines every line's S - 1
+ * offsets and S - 1 rates on the 1/U-sample grid.
+ *   Arguments.  (windows_per_stack, gate G, max_drift H, drift_den D, rounds R, U, fine_rounds Rf, ref_delay, centre,
+ *     outputs).  U is one of 2, 4, 8, 16.  0 <= Rf <= 16.  The call does not read the context's tdoa_locate_set_upsample
+ *     setting.
+ *   Coarse stage.  Exactly tdoa_process_sync_drift(windows_per_stack, gate, max_drift, drift_den, rounds, ref_delay, centre,
+ *     ...).  The first six outputs are that call's bytes.  k_s and h_s are its clocks and rates.
+ *   The fine word.  It is as in tdoa_process_sync_fine.  A fine lag lam is inside when |lam| <= (max_lag - 1) U.  Its word is
+ *     Q_U[lam + (max_lag - 1) U] of that (position, pair) row, with Q_U exactly as tdoa_locate_set_upsample defines it.  An
+ *     outside term adds 0 and is not counted.  No Q_U is materialised.  e^U_ij = sgn(d) * ((2|d| U + 16) div 32) with
+ *     d = ref_delay[j] - ref_delay[i], taken in 64 bits.
+ *   Unknowns.  Per station s: kappa_s = U k_s + y_s in 1/U sample, |y_s| <= U, and eta_s = U h_s + g_s, |g_s| <= U, in units
+ *     of 1/(U D) lag per position.  Station 0 is the gauge: y_0 = g_0 = 0.
+ *   Clock at position x.  kappa_s(x) = kappa_s + shift(eta_s, x), in 1/U sample.  shift(h, x) = sgn(h) * ((2|h|x + D) div (2D))
+ *     is the slope search's rule with the same D.
+ *   Objective.  A^U_ij = sum over x of Q_U,x,ij[e^U_ij + kappa_j(x) - kappa_i(x)], the signed words summed along the line.
+ *     F_U = sum over i < j of |A^U_ij|.
+ *   Start.  start_q = F_U at y = g = 0.  Because of rounding (e^U and shift are rounded on the finer grid) this is not the
+ *     coarse line's F.
+ *   Search.  Rf Gauss-Seidel sweeps over stations 1 .. S-1.  There is no placing.  Station s takes the (g, y) of the largest
+ *     sum over i != s of |A^U_pair(i,s)|, with the others where they stand.  Candidates compete in the order
+ *     r = rank(g) * (2U + 1) + rank(y), with rank(x) = 2|x| - (x > 0).  The first of equal maxima wins.  The window stays
+ *     centred on (U k_s, U h_s) in every sweep.  The standing value is therefore always a candidate and F_U never decreases.
+ *   Outputs.  Per line: fine is a second tdoa_sync_line record: moved is that of the last fine sweep, 0 with Rf = 0; terms_in
+ *     counts the terms inside at the end; positions = L; score_q = F_U, and start_q is as defined above;
+ *     score = score_q * 2^-32 / sqrt(N_w).  Per line: clock16[S] = kappa_s * (16 / U).  Per line: fine_rate[S] = eta_s.  Per
+ *     stack: fine_rows[S] = kappa_s(x) * (16 / U), the row tdoa_locate_set_clock takes.  Per stack and pair: fine_lags in 1/U
+ *     sample and fine_corr, the signed word on that stack's scale.  Both are 0 and 0.0 for a term outside.  If the coarse
+ *     record is the zero record or the final F_U is 0, every fine output of that line is zero.  With Rf = 0:
+ *     clock16 = 16 * clock and fine_rate = U * rate.
+ * Behind the clock-line search's launches: one launch that sets the fine table, per step of a station one launch over groups
+ * of fine slopes and one that commits the groups' best, and two that write start_q and the outputs.  (windows_per_stack, gate,
+ * max_drift, drift_den, rounds, U, fine_rounds) are part of the graph's key; ref_delay and centre stay data, so a call that
+ * changes only them replays the graph.  tdoa_group_process_sync_drift_fine is the group form, same bytes.
+ * TDOA_ERR_INVALID: what tdoa_process_sync_drift refuses, U not in {2, 4, 8, 16}, fine_rounds < 0 or > 16, a NULL fine_host
+ * (all checked before anything needs a device), |centre[s]| + G + 2 + ((H + 1)(L - 1)) div D >= 2^27 (a fine row in 1/16
+ * sample must fit int32).  TDOA_ERR_STATE and TDOA_ERR_UNSUPPORTED: what tdoa_process_sync_drift refuses, and the tightened
+ * overflow bound 4 * P * N_w > 2^17, N_w the windows of a line. */
+int tdoa_process_sync_drift_fine(tdoa_ctx *ctx, int windows_per_stack, int gate /* G */, int max_drift /* H */, int drift_den /* D */,
+                                 int rounds /* R */, int U, int fine_rounds /* Rf */, const int32_t *ref_delay /* [n_stations] */,
+                                 const int32_t *centre /* [n_stations] or NULL */,
+                                 tdoa_sync_line *line_host /* [3], required: tdoa_process_sync_drift's */,
+                                 int32_t   *clock_host /* [3][n_stations]: tdoa_process_sync_drift's; may be NULL */,
+                                 int32_t   *rate_host  /* [3][n_stations]: tdoa_process_sync_drift's; may be NULL */,
+                                 int32_t   *rows_host  /* [n_stacks_total][n_stations]: tdoa_process_sync_drift's; may be NULL */,
+                                 int32_t   *lags_host  /* [n_stacks_total][n_pairs]: tdoa_process_sync_drift's; may be NULL */,
+                                 double    *corr_host  /* same shape: tdoa_process_sync_drift's; may be NULL */,
+                                 tdoa_sync_line *fine_host /* [3], required */,
+                                 int32_t   *clock16_host   /* [3][n_stations]: kappa_s * (16 / U), 1/16 sample; may be NULL */,
+                                 int32_t   *fine_rate_host /* [3][n_stations]: eta_s; may be NULL */,
+                                 int32_t   *fine_rows_host /* [n_stacks_total][n_stations]: kappa_s(x) * (16 / U); may be NULL */,
+                                 int32_t   *fine_lags_host /* [n_stacks_total][n_pairs]: 1/U sample, 0 where outside; may be NULL */,
+                                 double    *fine_corr_host /* same shape: the signed word * 2^-32 / sqrt(n_w) there; may be NULL */);
+
+/* tests only: the same kernels on the caller's words, as tdoa_debug_sync_drift_from_q.  Precondition: |q| <= 2^60 div (P * L).
+ * TDOA_ERR_INVALID: what tdoa_process_sync_drift_fine and tdoa_debug_sync_drift_from_q refuse.  TDOA_ERR_UNSUPPORTED:
+ * 4 * P * track_len * n_w > 2^17. */
+int tdoa_debug_sync_drift_fine_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, int gate,
+                                      int max_drift, int drift_den, int rounds, int U, int fine_rounds, const int32_t *ref_delay,
+                                      const int32_t *centre, tdoa_sync_line *line, int32_t *clock, int32_t *rate, int32_t *rows,
+                                      int32_t *lags, double *corr, tdoa_sync_line *fine, int32_t *clock16, int32_t *fine_rate,
+                                      int32_t *fine_rows, int32_t *fine_lags, double *fine_corr);
+
+/* Host helper, no device: writes out[x - first_position][s] = clock16[s] + r(16 * eta_s * x, U * D), eta_s = fine_rate[s], for
+ * x = first_position .. first_position + n_positions - 1.  Here r is the nearest integer, halves away from zero, in 64-bit
+ * integers only.  This is the fine line continued past its block, in the 1/16 sample tdoa_locate_set_clock takes; blocks that
+ * follow one another without a gap are assumed, as by tdoa_sync_line_clock.  TDOA_ERR_INVALID: a NULL pointer,
+ * n_stations < 1, U not a factor (2, 4, 8, 16), drift_den < 1, first_position < 0, n_positions < 1. */
+int tdoa_sync_line_clock16(const int32_t *clock16, const int32_t *fine_rate, int n_stations, int U, int drift_den,
+                           int first_position, int n_positions, int32_t *out /* [n_positions][n_stations] */);
+
 /* Cell tracks: follow an emitter from stack to stack through the delay-table search's maps.  tdoa_process_locate locates
  * every stack alone.  Stations with free-running clocks give every stack of a target block its own clock row, so the block's
  * windows cannot be summed lag by lag; their maps can be added cell by cell, because every map is in the emitter's
@@ -1260,6 +1334,14 @@ int tdoa_group_process_sync_drift(tdoa_group *g, int windows_per_stack, int gate
                                   const int32_t *ref_delay, const int32_t *centre, tdoa_sync_line *line_host,
                                   int32_t *clock_host, int32_t *rate_host, int32_t *rows_host, int32_t *lags_host,
                                   double *corr_host);
+
+/* tdoa_process_sync_drift_fine over the members: the merged sum is searched on member 0, coarse stage and refinement, and the
+ * group returns a single context's bytes.  Errors as there and as tdoa_group_process_sync_drift. */
+int tdoa_group_process_sync_drift_fine(tdoa_group *g, int windows_per_stack, int gate, int max_drift, int drift_den, int rounds, int U,
+                                       int fine_rounds, const int32_t *ref_delay, const int32_t *centre, tdoa_sync_line *line_host,
+                                       int32_t *clock_host, int32_t *rate_host, int32_t *rows_host, int32_t *lags_host,
+                                       double *corr_host, tdoa_sync_line *fine_host, int32_t *clock16_host, int32_t *fine_rate_host,
+                                       int32_t *fine_rows_host, int32_t *fine_lags_host, double *fine_corr_host);
 
 /* tdoa_process_locate_track over the members (the table and the clocks as set by tdoa_group_locate_set_table and
  * tdoa_group_locate_set_clock): they sum their windows as in tdoa_group_process_stacked, the host adds the partials, and

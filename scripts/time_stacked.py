@@ -41,9 +41,12 @@ tdoa_process_locate_zoom(M, 1, Z, H, 1) with the same grid at Z cells per cell a
 process_locate_zoom_RxC_Z_H[_upU]_ms: the locate's launches and two more kernels; records, lags and correlations of both stages
 downloaded, the maps left on the device), and tdoa_process_locate(M, 1) with that fine grid as the table (name
 process_locate_fine_RxC_Z[_upU]_ms), the brute force the zoom replaces; the second is left out where the fine grid has more than
-2^22 cells.
+2^22 cells.  Every `--sync-drift-fine G/H/D/R/U/RF` adds a leg: tdoa_process_sync_drift_fine(M, G, H, D, R, U, RF) against the same
+delays with all twelve outputs downloaded -- the clock-line search's launches, then the fine table, two launches per fine step
+((2U+1)^2 candidates in tiles of 256, and the commit) and two finishes; give the same G/H/D/R to `--sync-drift` to have the leg
+it is compared with in the same process.
 usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--stack M] [--drift H/D]... [--track J]...
-[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]... [--locate-upsample U]... [--sync-fine G/U[/R[/RF]]]... [--locate-zoom Z[/H]]... [--max-lag N]"""
+[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]... [--locate-upsample U]... [--sync-fine G/U[/R[/RF]]]... [--locate-zoom Z[/H]]... [--sync-drift-fine G/H/D/R/U/RF]... [--max-lag N]"""
 import json
 import os
 import sys
@@ -73,7 +76,7 @@ def timed(fn, steps):
 
 
 def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=(), locate_tracks=(), stack=0, emitters=(),
-         track_emitters=(), map_stats=None, sync_drifts=(), upsamples=(), max_lag=20000, sync_fines=(), zooms=()):
+         track_emitters=(), map_stats=None, sync_drifts=(), upsamples=(), max_lag=20000, sync_fines=(), zooms=(), sync_drift_fines=()):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=max_lag)
     for s in range(stations):
         c.synth_capture(s, 66_666_666, ST[s % 3], TX, 0x5D0A0000 + s)
@@ -139,6 +142,9 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
         if stack != 0:
             legs["process_sync_%d_%d_stack%d_ms" % (G, R, stack)] = lambda G=G, R=R: c.process_sync(ref, stack, G, R)
         legs["process_sync_fine_%d_%d_%d_%d_ms" % (G, U, R, Rf)] = lambda G=G, U=U, R=R, Rf=Rf: c.process_sync_fine(ref, stack, G, R, U, Rf)
+    for G, H, D, R, U, Rf in sync_drift_fines:
+        legs["process_sync_drift_fine_%d_%d_%d_%d_%d_%d_ms" % (G, H, D, R, U, Rf)] = \
+            lambda G=G, H=H, D=D, R=R, U=U, Rf=Rf: c.process_sync_drift_fine(ref, stack, G, H, D, R, U, Rf)
     times = {name: [] for name in legs}
     for _ in range(rounds):
         for name, fn in legs.items():
@@ -227,6 +233,14 @@ if __name__ == "__main__":
         parts = args[i + 1].split("/")
         sync_fines.append((int(parts[0]), int(parts[1]), int(parts[2]) if len(parts) > 2 else 2, int(parts[3]) if len(parts) > 3 else 2))
         del args[i:i + 2]
+    sync_drift_fines = []
+    while "--sync-drift-fine" in args:
+        i = args.index("--sync-drift-fine")
+        parts = args[i + 1].split("/")
+        if len(parts) != 6:
+            raise SystemExit("--sync-drift-fine G/H/D/R/U/RF")
+        sync_drift_fines.append(tuple(int(x) for x in parts))
+        del args[i:i + 2]
     sync_drifts = []
     while "--sync-drift" in args:
         i = args.index("--sync-drift")
@@ -240,4 +254,4 @@ if __name__ == "__main__":
         syncs.append((int(g), int(r or 2)))
         del args[i:i + 2]
     main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs, locate_tracks, opt["--stack"], emitters,
-         track_emitters, map_stats, sync_drifts, upsamples, opt["--max-lag"], sync_fines, zooms)
+         track_emitters, map_stats, sync_drifts, upsamples, opt["--max-lag"], sync_fines, zooms, sync_drift_fines)

@@ -133,12 +133,14 @@ int tdoa_debug_poison_workspace(tdoa_ctx *ctx)
     // which is state, is left alone; the clock-line search's clocks only enter lags that are checked against the range, and a
     // candidate's number taken from its tiles is clamped to the candidates there are; the upsampled surfaces are integers like
     // stack_q, every word written by the upsampler before a search reads it; the zoom locate's window maps, candidates and
-    // records are the delay-table search's again, and its fine table is state)
+    // records are the delay-table search's again, and its fine table is state; the fine clock lines' table and candidates are
+    // the clock-line search's again)
     for (DevBuf *b : {&ctx->v, &ctx->tz, &ctx->fine_raw, &ctx->once_edges, &ctx->surf, &ctx->surf_out, &ctx->stack_q, &ctx->stack_surf,
                       &ctx->track_t, &ctx->closure_part, &ctx->closure_best, &ctx->closure_out, &ctx->locate_map, &ctx->locate_part,
                       &ctx->locate_best, &ctx->locate_out, &ctx->locate_lags, &ctx->locate_corr, &ctx->sline_cur, &ctx->sline_part,
                       &ctx->sline_out, &ctx->sline_rows, &ctx->sline_lags, &ctx->sline_corr, &ctx->locate_qu, &ctx->zoom_map, &ctx->zoom_part,
-                      &ctx->zoom_out, &ctx->zoom_lags, &ctx->zoom_corr})
+                      &ctx->zoom_out, &ctx->zoom_lags, &ctx->zoom_corr, &ctx->slfine_cur, &ctx->slfine_part, &ctx->slfine_out,
+                      &ctx->slfine_rows, &ctx->slfine_lags, &ctx->slfine_corr})
         if (b->p && b->cap >= 4) HIPCHK(ctx, hipMemsetD32Async(static_cast<hipDeviceptr_t>(b->p), 0x7FC00000, b->cap / 4, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return TDOA_OK;

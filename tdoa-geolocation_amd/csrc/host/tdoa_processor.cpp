@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--locate-upsample=U] [--locate-zoom=Z[/H[/SEP]]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--sync-drift=H[/D]] [--sync-fine=U[/RF]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--locate-upsample=U] [--locate-zoom=Z[/H[/SEP]]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--sync-drift=H[/D]] [--sync-drift-fine=U[/RF]] [--sync-fine=U[/RF]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -172,6 +172,11 @@ int main(int argc, char **argv)
     // block 2 under the midpoint of the two rows rounded to 1/16 sample
     bool sync_fine = false;
     int sfine_u = 16, sfine_r = 2;
+    // --sync-drift-fine=U[/RF] (with --sync-drift), U in 2, 4, 8, 16: the lines' offsets and rates are refined to 1/U sample in RF
+    // sweeps (tdoa_process_sync_drift_fine); blocks 1 and 3 are located under their own fine rows, block 2 under block 1's fine
+    // line continued over its positions (tdoa_sync_line_clock16)
+    bool sync_drift_fine = false;
+    int sdfine_u = 16, sdfine_r = 2;
     double gate = 120.0;     // samples; PROJECT_NOTES.md:29-32 (max |TDOA| about 57 us = 114 samples at 2 Msps)
     tdoa_params prm;
     tdoa_default_params(&prm);
@@ -283,6 +288,14 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
+        else if (a.rfind("--sync-drift-fine=", 0) == 0) {
+            sync_drift_fine = true;
+            const int got = std::sscanf(a.c_str() + 18, "%d/%d", &sdfine_u, &sdfine_r);
+            if (got < 1 || (sdfine_u != 2 && sdfine_u != 4 && sdfine_u != 8 && sdfine_u != 16) || sdfine_r < 0 || sdfine_r > 16) {
+                std::fprintf(stderr, "--sync-drift-fine=U[/RF] with U one of 2, 4, 8, 16 and RF in 0 .. 16, e.g. --sync-drift-fine=16/2\n");
+                return 1;
+            }
+        }
         else if (a.rfind("--sync-fine=", 0) == 0) {
             sync_fine = true;
             const int got = std::sscanf(a.c_str() + 12, "%d/%d", &sfine_u, &sfine_r);
@@ -316,6 +329,7 @@ int main(int argc, char **argv)
     }
     if (sync && !locate) { std::fprintf(stderr, "--sync needs --stack --locate\n"); return 1; }
     if (sync_drift && !sync) { std::fprintf(stderr, "--sync-drift needs --stack --locate --sync\n"); return 1; }
+    if (sync_drift_fine && !sync_drift) { std::fprintf(stderr, "--sync-drift-fine needs --stack --locate --sync --sync-drift\n"); return 1; }
     if (sync_fine && (!sync || sync_drift)) { std::fprintf(stderr, "--sync-fine needs --stack --locate --sync and no --sync-drift\n"); return 1; }
     if (sync && !sync_drift && stack_m != 0) { std::fprintf(stderr, "--sync needs whole-block stacks: --stack without =WINDOWS\n"); return 1; }
     if (pos.size() < 4) {                                     // processor.go:1048-1052
@@ -502,6 +516,8 @@ int main(int argc, char **argv)
         std::vector<int32_t> clocks16;
         std::vector<tdoa_sync_line> lines;       // --sync-drift: one record, S clocks and S rates per block (tdoa_process_sync_drift)
         std::vector<int32_t> rates;
+        std::vector<tdoa_sync_line> flines;      // --sync-drift-fine: one more record, S clocks in 1/16 sample and S fine rates per block
+        std::vector<int32_t> fclocks16, frates;
         double grid_lat0 = 0, grid_lon0 = 0, grid_dlat = 0, grid_dlon = 0;
         if (stack) {
             if ((rc = tdoa_num_stacks(ctx, stack_m, &spb, &n_stacks))) return die("tdoa_num_stacks", rc);
@@ -559,11 +575,24 @@ int main(int argc, char **argv)
                         lines.resize(3);
                         clocks.resize(3 * (size_t)S);
                         rates.resize(3 * (size_t)S);
-                        if ((rc = tdoa_process_sync_drift(ctx, stack_m, sync_g, sdrift_h, sdrift_d, sync_r, ref.data(), nullptr, lines.data(),
-                                                          clocks.data(), rates.data(), table16.data(), nullptr, nullptr)))
-                            return die("tdoa_process_sync_drift", rc);
-                        if ((rc = tdoa_sync_line_clock(clocks.data(), rates.data(), S, sdrift_d, spb, spb, table16.data() + (size_t)spb * S)))
-                            return die("tdoa_sync_line_clock", rc);
+                        if (sync_drift_fine) {               // the fine rows; the target block's are block 1's fine line continued
+                            flines.resize(3);
+                            fclocks16.resize(3 * (size_t)S);
+                            frates.resize(3 * (size_t)S);
+                            if ((rc = tdoa_process_sync_drift_fine(ctx, stack_m, sync_g, sdrift_h, sdrift_d, sync_r, sdfine_u, sdfine_r, ref.data(),
+                                                                   nullptr, lines.data(), clocks.data(), rates.data(), nullptr, nullptr, nullptr,
+                                                                   flines.data(), fclocks16.data(), frates.data(), table16.data(), nullptr, nullptr)))
+                                return die("tdoa_process_sync_drift_fine", rc);
+                            if ((rc = tdoa_sync_line_clock16(fclocks16.data(), frates.data(), S, sdfine_u, sdrift_d, spb, spb,
+                                                             table16.data() + (size_t)spb * S)))
+                                return die("tdoa_sync_line_clock16", rc);
+                        } else {
+                            if ((rc = tdoa_process_sync_drift(ctx, stack_m, sync_g, sdrift_h, sdrift_d, sync_r, ref.data(), nullptr, lines.data(),
+                                                              clocks.data(), rates.data(), table16.data(), nullptr, nullptr)))
+                                return die("tdoa_process_sync_drift", rc);
+                            if ((rc = tdoa_sync_line_clock(clocks.data(), rates.data(), S, sdrift_d, spb, spb, table16.data() + (size_t)spb * S)))
+                                return die("tdoa_sync_line_clock", rc);
+                        }
                     } else if (sync_fine) {
                         syncs.resize((size_t)n_stacks);
                         clocks.resize((size_t)n_stacks * S);
@@ -740,6 +769,14 @@ int main(int argc, char **argv)
             std::printf(" rate=");
             for (int s = 0; s < S; s++) std::printf("%s%d", s ? "," : "", (int)rates[b * S + s]);
             std::printf("/%d moved=%d score=%.6f\n", sdrift_d, (int)lines[b].moved, lines[b].score);
+        }
+        // --sync-drift-fine: the fine lines of the two reference blocks, a line each
+        for (size_t b = 0; b < flines.size(); b += 2) {
+            std::printf("SYNCLINEFINE block %d: clock16=", (int)b + 1);
+            for (int s = 0; s < S; s++) std::printf("%s%d", s ? "," : "", (int)fclocks16[b * S + s]);
+            std::printf(" fine_rate=");
+            for (int s = 0; s < S; s++) std::printf("%s%d", s ? "," : "", (int)frates[b * S + s]);
+            std::printf("/%d moved=%d score=%.6f\n", sdfine_u * sdrift_d, (int)flines[b].moved, flines[b].score);
         }
         // --map-stats: the statistics of the plane the line before it judged, the words on the line's own scale
         const auto print_stats = [&](const std::vector<tdoa_map_stats> &all, size_t at) {

@@ -48,6 +48,7 @@
 #include "stack_map_stats.hpp"
 #include "stack_upsample.hpp"
 #include "stack_sync_fine.hpp"
+#include "stack_sync_drift_fine.hpp"
 #include "stack_locate_zoom.hpp"
 
 using namespace tdoa;
@@ -205,6 +206,12 @@ struct tdoa_ctx {
     // [stack][pair]
     DevBuf sline_in, sline_tab, sline_roots, sline_cur, sline_k, sline_h, sline_part, sline_moved, sline_start, sline_out, sline_clock,
         sline_rate, sline_rows, sline_lags, sline_corr;
+    // the fine clock lines, behind the clock-line search's: the fine clocks [line][station][position], kappa and eta
+    // [line][station], the tiles' candidates [line][tile], `moved` and F_U at the start [line], the fine records [line], the
+    // clocks in 1/16 sample and the fine rates [line][station], the rows [stack][station], the lags in 1/U sample and the
+    // correlations [stack][pair]
+    DevBuf slfine_cur, slfine_kappa, slfine_eta, slfine_part, slfine_moved, slfine_start, slfine_out, slfine_clock, slfine_rate,
+        slfine_rows, slfine_lags, slfine_corr;
     // the tdoa_debug_*_from_q entries (debug_search_from_q): the caller's words and sqrt(n_w) per set
     DevBuf debug_q, debug_roots;
     int locate_cells = 0, locate_cols = 0, locate_stations = 0;
@@ -587,6 +594,8 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->sline_moved, &ctx->sline_start, &ctx->sline_out, &ctx->sline_clock, &ctx->sline_rate, &ctx->sline_rows,
                       &ctx->sline_lags, &ctx->sline_corr, &ctx->locate_qu, &ctx->locate_table_up, &ctx->locate_clock_up,
                       &ctx->sfine_out, &ctx->sfine_clock, &ctx->sfine_lags, &ctx->sfine_corr,
+                      &ctx->slfine_cur, &ctx->slfine_kappa, &ctx->slfine_eta, &ctx->slfine_part, &ctx->slfine_moved, &ctx->slfine_start,
+                      &ctx->slfine_out, &ctx->slfine_clock, &ctx->slfine_rate, &ctx->slfine_rows, &ctx->slfine_lags, &ctx->slfine_corr,
                       &ctx->locate_fine, &ctx->locate_fine_up, &ctx->zoom_map, &ctx->zoom_part, &ctx->zoom_out, &ctx->zoom_lags, &ctx->zoom_corr};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1328,3 +1337,4 @@ int tdoa_solve_surface(const double *stations_lle, int n_stations, const double 
 #include "sync_api.inc"
 #include "sync_fine_api.inc"
 #include "sync_drift_api.inc"
+#include "sync_drift_fine_api.inc"

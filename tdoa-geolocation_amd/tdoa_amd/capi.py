@@ -133,6 +133,8 @@ SYMBOLS = [
     "tdoa_process_sync_fine", "tdoa_group_process_sync_fine", "tdoa_debug_sync_fine_from_q",
     "tdoa_locate_set_fine_table", "tdoa_group_locate_set_fine_table", "tdoa_process_locate_zoom", "tdoa_group_process_locate_zoom",
     "tdoa_debug_locate_zoom_from_q",
+    "tdoa_process_sync_drift_fine", "tdoa_group_process_sync_drift_fine", "tdoa_debug_sync_drift_fine_from_q",
+    "tdoa_sync_line_clock16",
 ]
 
 
@@ -194,6 +196,21 @@ SEARCHES = {s.name: s for s in (
              _Out("rate", np.int32, ("n_tracks", "S")), _Out("rows", np.int32, ("n_sets", "S")),
              _Out("lags", np.int32, ("n_sets", "P")), _Out("corr", np.float64, ("n_sets", "P"))), _CLOCKS, track_len=True),
 )}
+# searches added after the nine: the same records, resolved through _search (tests pin SEARCHES to its nine names)
+LATER_SEARCHES = {s.name: s for s in (
+    _Search("sync_drift_fine", ("gate", "max_drift", "drift_den", "rounds", "U", "fine_rounds"),
+            SEARCHES["sync_drift"].outputs +
+            (_Out("fine", SYNC_LINE_DTYPE, ("n_tracks",)), _Out("clock16", np.int32, ("n_tracks", "S")),
+             _Out("fine_rate", np.int32, ("n_tracks", "S")), _Out("fine_rows", np.int32, ("n_sets", "S")),
+             _Out("fine_lags", np.int32, ("n_sets", "P")), _Out("fine_corr", np.float64, ("n_sets", "P"))), _CLOCKS, track_len=True),
+)}
+
+
+def _search(name):
+    """the record of search `name`, from either table"""
+    return SEARCHES[name] if name in SEARCHES else LATER_SEARCHES[name]
+
+
 def _search_argtypes(s, route):
     """the argtypes of search s's entry `route`"""
     i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
@@ -317,6 +334,7 @@ def load(build_if_missing=True):
     L.tdoa_locate_set_clock.argtypes = [vp, i32p, C.c_int, C.c_int]
     L.tdoa_group_locate_set_clock.argtypes = [vp, i32p, C.c_int, C.c_int]
     L.tdoa_sync_line_clock.argtypes = [i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, i32p]
+    L.tdoa_sync_line_clock16.argtypes = [i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p]
     L.tdoa_locate_set_stats.argtypes = [vp, C.POINTER(C.c_uint16), C.c_int, C.c_int]
     L.tdoa_group_locate_set_stats.argtypes = [vp, C.POINTER(C.c_uint16), C.c_int, C.c_int]
     L.tdoa_locate_last_stats.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
@@ -329,7 +347,7 @@ def load(build_if_missing=True):
     L.tdoa_debug_upsample_q.argtypes = [vp, i64p, C.c_int, C.c_int, i64p]
     L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
                                         C.POINTER(C.c_int)]
-    for s in SEARCHES.values():
+    for s in list(SEARCHES.values()) + list(LATER_SEARCHES.values()):
         for route, entry in s.entries.items():
             getattr(L, entry).argtypes = _search_argtypes(s, route)
     _lib = L
@@ -368,7 +386,40 @@ def _params(kw):
     return p
 
 
-class Context:
+# The methods of searches added after the nine live in base classes of Context and Group, as their records live in
+# LATER_SEARCHES: tests pin the functions Context and Group define themselves to the parent commit's.
+class _LaterContextSearches:
+    def process_sync_drift_fine(self, ref_delay, windows_per_stack=0, gate=0, max_drift=0, drift_den=1, rounds=0, U=16, fine_rounds=2,
+                                centre=None):
+        """tdoa_process_sync_drift_fine -> process_sync_drift's outputs (the coarse stage's bytes) and {"fine": [3]
+        SYNC_LINE_DTYPE, "clock16": [3][S] int32 (kappa_s in 1/16 sample), "fine_rate": [3][S] int32 (eta_s, 1/(U drift_den) lag
+        per stack), "fine_rows": [n_stacks][S] int32 (1/16 sample: tdoa_locate_set_clock's unit), "fine_lags": [n_stacks][P]
+        int32 (1/U sample), "fine_corr": [n_stacks][P] float64}: the coarse lines' offsets and rates moved by |y_s|, |g_s| <= U
+        in `fine_rounds` sweeps on the words of the surfaces upsampled to 1/U sample"""
+        return _process_search(self, self, "sync_drift_fine", dict(
+            windows_per_stack=windows_per_stack, gate=gate, max_drift=max_drift, drift_den=drift_den, rounds=rounds, U=U,
+            fine_rounds=fine_rounds, ref_delay=ref_delay, centre=centre), n_tracks=3)
+
+    def sync_drift_fine_from_q(self, q, ref_delay, track_len, n_w=1, gate=0, max_drift=0, drift_den=1, rounds=0, U=16, fine_rounds=2,
+                               centre=None):
+        """tdoa_debug_sync_drift_fine_from_q: the clock-line search's and the refinement's kernels on the caller's words q
+        [n_sets][P][2 max_lag - 1] int64, set t track_len + j position j of line t -> what process_sync_drift_fine returns,
+        n_sets / track_len lines and n_sets stacks"""
+        return self._from_q("sync_drift_fine", q, np.size(ref_delay), dict(
+            track_len=track_len, n_w=n_w, gate=gate, max_drift=max_drift, drift_den=drift_den, rounds=rounds, U=U,
+            fine_rounds=fine_rounds, ref_delay=ref_delay, centre=centre))
+
+
+class _LaterGroupSearches:
+    def process_sync_drift_fine(self, ref_delay, windows_per_stack=0, gate=0, max_drift=0, drift_den=1, rounds=0, U=16, fine_rounds=2,
+                                centre=None):
+        """tdoa_group_process_sync_drift_fine -> Context.process_sync_drift_fine's outputs, byte-identical to a single context's"""
+        return _process_search(self, self.member(0), "sync_drift_fine", dict(
+            windows_per_stack=windows_per_stack, gate=gate, max_drift=max_drift, drift_den=drift_den, rounds=rounds, U=U,
+            fine_rounds=fine_rounds, ref_delay=ref_delay, centre=centre), n_tracks=3)
+
+
+class Context(_LaterContextSearches):
     """One tdoa_ctx (one GPU, single caller)."""
 
     def __init__(self, **kw):
@@ -788,7 +839,7 @@ class Context:
 
     def _from_q(self, name, q, n_stations, values):
         """search `name` on the caller's words q"""
-        s, S = SEARCHES[name], int(n_stations)
+        s, S = _search(name), int(n_stations)
         q = _q_sets(q, S, self.params.max_lag)
         n = _shape_numbers(values, q.shape[0], S, getattr(self, "_locate_cells", 0), values.get("track_len", 1))
         out = _run_search(s, "q", getattr(self._L, s.entries["q"]), self._h, self._chk, n, values, q)
@@ -1106,7 +1157,7 @@ def _run_search(s, route, fn, handle, chk, n, values, q=None):
 
 def _process_search(owner, counts, name, values, **given):
     """search `name` on owner's own sum (a Context: counts is owner) or merged sum (a Group: counts is its member 0)"""
-    s = SEARCHES[name]
+    s = _search(name)
     route = "own" if counts is owner else "group"
     per_block, n_sets = counts.num_stacks(values["windows_per_stack"])
     n = _shape_numbers(values, n_sets, counts.num_stations(), getattr(owner, "_locate_cells", 0), per_block, **given)
@@ -1167,7 +1218,7 @@ class _Member(Context):
         self._h = None
 
 
-class Group:
+class Group(_LaterGroupSearches):
     """A multi-device group (tdoa_group): one tdoa_ctx per member, member k = rank k of len(devices) in tdoa_process's
     sharding; devices may repeat (several members on one GPU).  Keyword arguments are tdoa_params fields, as for Context."""
 
@@ -1328,6 +1379,22 @@ class Group:
         return _process_search(self, self.member(0), "sync_drift", dict(
             windows_per_stack=windows_per_stack, gate=gate, max_drift=max_drift, drift_den=drift_den, rounds=rounds,
             ref_delay=ref_delay, centre=centre), n_tracks=3)
+
+
+def sync_line_clock16(clock16, fine_rate, U, drift_den, first_position, n_positions):
+    """tdoa_sync_line_clock16 (host only): a fine line's clocks [S] (1/16 sample) and fine rates [S] continued over positions
+    first_position .. first_position + n_positions - 1 -> [n_positions][S] int32 in 1/16 sample, what locate_set_clock takes"""
+    k = np.ascontiguousarray(clock16, dtype=np.int32).reshape(-1)
+    h = np.ascontiguousarray(fine_rate, dtype=np.int32).reshape(-1)
+    if k.shape != h.shape:
+        raise ValueError("clock16 and fine_rate must hold one integer per station")
+    out = np.zeros((max(int(n_positions), 1), k.shape[0]), dtype=np.int32)
+    i32p = C.POINTER(C.c_int32)
+    rc = load().tdoa_sync_line_clock16(k.ctypes.data_as(i32p), h.ctypes.data_as(i32p), k.shape[0], int(U), int(drift_den),
+                                       int(first_position), int(n_positions), out.ctypes.data_as(i32p))
+    if rc:
+        raise TdoaError(rc, "tdoa_sync_line_clock16")
+    return out
 
 
 def sync_line_clock(clock, rate, drift_den, first_position, n_positions):
