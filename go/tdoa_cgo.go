@@ -1010,3 +1010,73 @@ func (g *Group) ProcessSyncDriftFine(windowsPerStack, gate, maxDrift, driftDen, 
 	}
 	return o, nil
 }
+
+// LocateTrackZoom is what ProcessLocateTrackZoom returns: the coarse stage's outputs exactly as ProcessLocateTrack's (Track, Cells,
+// Own, Lags, Corr), and per block the track through the fine table's windows: its record (ZTrack: the cells are fine cells), its
+// fine cell in every stack and that stack's own score there (ZCells, ZOwn: [block][stacks per block]), and the fine cells' lags
+// (1/u sample with LocateSetUpsample) and signed correlations (ZLags, ZCorr: [stack][pair]).
+type LocateTrackZoom struct {
+	Track  []C.tdoa_cell_track
+	Cells  []int32
+	Own    []int64
+	Lags   []int32
+	Corr   []float64
+	ZTrack []C.tdoa_cell_track
+	ZCells []int32
+	ZOwn   []int64
+	ZLags  []int32
+	ZCorr  []float64
+}
+
+func newLocateTrackZoom(stacks, perBlock, pairs int) *LocateTrackZoom {
+	return &LocateTrackZoom{Track: make([]C.tdoa_cell_track, stacks/perBlock), Cells: make([]int32, stacks), Own: make([]int64, stacks),
+		Lags: make([]int32, stacks*pairs), Corr: make([]float64, stacks*pairs), ZTrack: make([]C.tdoa_cell_track, stacks/perBlock),
+		ZCells: make([]int32, stacks), ZOwn: make([]int64, stacks), ZLags: make([]int32, stacks*pairs), ZCorr: make([]float64, stacks*pairs)}
+}
+
+// ProcessLocateTrackZoom is the zoomed cell track (the header's "zoomed cell tracks"): ProcessLocateTrack's tracks, then per block
+// the track through the (2h+1)^2-cell windows of the fine table around z x the coarse track's cells, consecutive fine cells at
+// most fineStep rows and columns apart, in the same step.  A fine cell's position is the caller's: row = cell / nCols of the fine
+// table, col = the remainder.
+func (g *gpuCorrelator) ProcessLocateTrackZoom(windowsPerStack, maxStep, minSeparation, z, h, fineStep, fineSeparation int) (*LocateTrackZoom, error) {
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs := int(C.tdoa_num_pairs(g.ctx))
+	if int(total)*pairs == 0 {
+		return nil, fmt.Errorf("tdoa_process_locate_track_zoom: no stacks or fewer than two stations")
+	}
+	o := newLocateTrackZoom(int(total), int(perBlock), pairs)
+	if rc := C.tdoa_process_locate_track_zoom(g.ctx, C.int(windowsPerStack), C.int(maxStep), C.int(minSeparation), C.int(z), C.int(h),
+		C.int(fineStep), C.int(fineSeparation), &o.Track[0], (*C.int32_t)(unsafe.Pointer(&o.Cells[0])), (*C.int64_t)(unsafe.Pointer(&o.Own[0])),
+		(*C.int32_t)(unsafe.Pointer(&o.Lags[0])), (*C.double)(unsafe.Pointer(&o.Corr[0])), nil,
+		&o.ZTrack[0], (*C.int32_t)(unsafe.Pointer(&o.ZCells[0])), (*C.int64_t)(unsafe.Pointer(&o.ZOwn[0])),
+		(*C.int32_t)(unsafe.Pointer(&o.ZLags[0])), (*C.double)(unsafe.Pointer(&o.ZCorr[0])), nil, nil); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_process_locate_track_zoom: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return o, nil
+}
+
+// ProcessLocateTrackZoom is gpuCorrelator.ProcessLocateTrackZoom over the group: the members' fixed-point partial sums are added
+// on the host and tracked on member 0, coarse tracks and windows, the same bytes one context returns.
+func (g *Group) ProcessLocateTrackZoom(windowsPerStack, maxStep, minSeparation, z, h, fineStep, fineSeparation int) (*LocateTrackZoom, error) {
+	m := C.tdoa_group_member(g.g, 0)
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(m, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs := int(C.tdoa_num_pairs(m))
+	if int(total)*pairs == 0 {
+		return nil, fmt.Errorf("tdoa_group_process_locate_track_zoom: no stacks or fewer than two stations")
+	}
+	o := newLocateTrackZoom(int(total), int(perBlock), pairs)
+	if rc := C.tdoa_group_process_locate_track_zoom(g.g, C.int(windowsPerStack), C.int(maxStep), C.int(minSeparation), C.int(z), C.int(h),
+		C.int(fineStep), C.int(fineSeparation), &o.Track[0], (*C.int32_t)(unsafe.Pointer(&o.Cells[0])), (*C.int64_t)(unsafe.Pointer(&o.Own[0])),
+		(*C.int32_t)(unsafe.Pointer(&o.Lags[0])), (*C.double)(unsafe.Pointer(&o.Corr[0])), nil,
+		&o.ZTrack[0], (*C.int32_t)(unsafe.Pointer(&o.ZCells[0])), (*C.int64_t)(unsafe.Pointer(&o.ZOwn[0])),
+		(*C.int32_t)(unsafe.Pointer(&o.ZLags[0])), (*C.double)(unsafe.Pointer(&o.ZCorr[0])), nil, nil); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_group_process_locate_track_zoom: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return o, nil
+}

@@ -1071,7 +1071,8 @@ typedef struct {
  *   What follows: with the fine table equal to the table and Z = 1, the zoom's cell, score_q, lags and correlations are the
  *     location's.  Whenever the brute-force best cell of the whole fine table (tdoa_process_locate with the fine table as the
  *     table) lies inside a stack's window, it is the zoom's cell, with the same score, lags and correlations.
- *   Scope: the rounds (tdoa_process_locate_multi) and the cell tracks are not zoomed.
+ *   Scope: the rounds (tdoa_process_locate_multi) and the cell tracks are not zoomed by this call; the cell tracks have
+ *     tdoa_process_locate_track_zoom.
  * Two kernels behind the locate's launches, in the same step graph: nothing goes through the host.  The graph's key is the
  * locate's words plus (Z, H, fine_separation, n_cells_f, n_cols_f).
  * TDOA_ERR_INVALID (tdoa_locate_set_fine_table): what tdoa_locate_set_table refuses. */
@@ -1094,6 +1095,74 @@ int tdoa_process_locate_zoom(tdoa_ctx *ctx, int windows_per_stack, int min_separ
 int tdoa_debug_locate_zoom_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int min_separation, int Z, int H,
                                   int fine_separation, tdoa_location *loc, int32_t *lags, double *corr, int64_t *map, tdoa_zoom *zoom,
                                   int32_t *zlags, double *zcorr, int64_t *zmap);
+
+/* Zoomed cell tracks: a block's track refined on the fine table.  The cell track exists for free-running receivers: every
+ * stack of a block has its own clock row, so the block's windows can be summed map by map only, never lag by lag.  The zoom
+ * locate refines one stack; this call refines a whole track in the same step graph, with no table upload and no second call
+ * per block.
+ *   The coarse stage is tdoa_process_locate_track(windows_per_stack, max_step, min_separation) unchanged, on the context's
+ *     table, clocks, upsample setting and statistics setting.  The first six outputs are that call's bytes, and
+ *     tdoa_locate_last_stats returns what it returns after that call.  The fine planes are not judged.
+ *   The windows: position j of track t is stack sid = t L + j.  Its window is the zoom's window around the track's coarse cell
+ *     cells[t][j] = (r, c): position (wa, wb), 0 <= wa, wb <= 2H, has the fine row Z r - H + wa and the fine column
+ *     Z c - H + wb, and competes under the zoom's rule.  w_j[pos] is score_q of that fine cell under stack sid's clock row,
+ *     with the zoom's lag rule and the scaled fine table where U > 1, and -1 where the position does not compete.  w_j is zmap.
+ *   The recurrence runs in fine coordinates, from the last position back, with Jf = fine_step:
+ *     F_{L-1}[pos] = w_{L-1}[pos].  F_j[pos] = -1 where w_j[pos] = -1.  Otherwise let m be the largest F_{j+1}[pos'] over
+ *     |dr|, |dc| <= Jf, where pos' is the position of window j + 1 whose fine row and column are (row + dr, col + dc); it
+ *     must lie inside that window (0 <= wa', wb' <= 2H), and a -1 there does not count.  F_j[pos] = w_j[pos] + m.  If no such
+ *     position exists, F_j[pos] = -1: no continuation.  E_j[pos] is the (dr, dc) of the maximum; ties go to the smaller
+ *     rank(dr), then the smaller rank(dc), rank(x) = 2|x| - (x > 0), as in the coarse recurrence.
+ *     Consecutive windows are offset by Z (C_{j+1} - C_j).  With Z J > 2H + Jf they need not touch; that is the caller's
+ *     choice of H and is not refused.
+ *   The track: f_0 is the position with the largest F_0, equal maxima: the smaller fine cell.  f_{j+1} = f_j + E_j[f_j].
+ *     zcells holds the fine cells of f_j, zown holds w_j there.  zlags and zcorr hold the fine cell's lags (1/U sample) and
+ *     signed correlations under that stack's clocks, 0 and 0.0 outside the range: what tdoa_solve_surface takes.  ztotal is
+ *     F_0 in the coordinates of window 0.
+ *   The record is a tdoa_cell_track: cell = f_0's fine cell, positions = L, steps = the number of j with f_{j+1} != f_j,
+ *     score_q = max F_0; score and runner_up are on the coarse track's scale, 2^-32 / sqrt(N_w).  The runner-up is the largest
+ *     F_0 >= 0 over positions with max(|row - row_0|, |col - col_0|) > fine_separation from f_0, with the same tie rule;
+ *     runner_q, runner_up and runner_cell are 0 where there is none.
+ *   Zero records: a track with the zero coarse record gets the zero ztrack and zero zcells, zown, zlags and zcorr; its zmap
+ *     and ztotal are -1 throughout.  A track whose largest F_0 is <= 0 gets the same zeros; its zmap and ztotal keep their
+ *     words.
+ *   What follows:
+ *     1. L = 1: ztrack's cell, runner_cell, score_q, runner_q, score and runner_up are tdoa_process_locate_zoom's tdoa_zoom
+ *        fields; zlags, zcorr and zmap are its bytes; ztotal = zmap.
+ *     2. J = 0 and Jf = 0: all windows of a track coincide and ztotal = the sum over j of zmap_j word for word, -1 where a
+ *        position does not compete.
+ *     3. score_q = ztotal[pos(f_0)] = the sum over j of zown[j]; consecutive zcells are at most Jf fine rows and columns apart.
+ *     4. With the fine table equal to the table, Z = 1 and Jf = J, ztrack.score_q = track.score_q for any H: the coarse best
+ *        track runs through the windows' centres.
+ *     5. ztrack.score_q is at most the score of tdoa_process_locate_track with the fine table as the table and max_step = Jf,
+ *        and equals it whenever that brute-force track lies inside the windows.
+ *   Scope: the rounds (tdoa_process_locate_multi, tdoa_process_locate_track_multi) are not zoomed.
+ * Four kernels behind the tracks' launches, in the same step graph: nothing goes through the host, and the windows' centres
+ * are data.  The graph's key is the tracks' words plus (Z, H, fine_step, fine_separation, n_cells_f, n_cols_f).
+ * The refusals are tdoa_process_locate_track's, and: TDOA_ERR_INVALID: Z outside 1 .. 64, H outside 0 .. 64, fine_step outside
+ * 0 .. 16, fine_separation < 1, a NULL ztrack_host.  TDOA_ERR_STATE: no fine table, or one of another n_stations.
+ * TDOA_ERR_UNSUPPORTED: with U > 1, a fine table entry with |t| * U >= 2^31.  TDOA_ERR_NOMEM: the window maps
+ * [n_stacks_total][(2H+1)^2], the steps E (2 bytes per stack and position) or ztotal do not fit; tdoa_last_error gives the
+ * sizes.  All argument checks happen before anything needs a device. */
+int tdoa_process_locate_track_zoom(tdoa_ctx *ctx, int windows_per_stack, int max_step, int min_separation, int Z, int H, int fine_step,
+                                   int fine_separation,
+                                   tdoa_cell_track *track_host, int32_t *cells_host, int64_t *own_host, int32_t *lags_host,
+                                   double *corr_host, int64_t *total_host /* tdoa_process_locate_track's */,
+                                   tdoa_cell_track *ztrack_host /* [n_tracks], required; its cells are fine cell indices */,
+                                   int32_t *zcells_host   /* [n_tracks][L], may be NULL */,
+                                   int64_t *zown_host     /* [n_tracks][L], may be NULL */,
+                                   int32_t *zlags_host    /* [n_stacks_total][n_pairs], 1/U sample, may be NULL */,
+                                   double  *zcorr_host    /* same shape, may be NULL */,
+                                   int64_t *zmap_host     /* [n_stacks_total][(2H+1)^2], may be NULL */,
+                                   int64_t *ztotal_host   /* [n_tracks][(2H+1)^2], may be NULL */);
+
+/* tests only: the same kernels on the caller's words, as tdoa_debug_locate_track_from_q, with the context's table, fine table,
+ * clocks and settings; outputs as tdoa_process_locate_track_zoom's with n_sets for n_stacks_total and n_sets / track_len
+ * tracks.  Refuses what that call and tdoa_debug_locate_track_from_q refuse. */
+int tdoa_debug_locate_track_zoom_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, int max_step,
+                                        int min_separation, int Z, int H, int fine_step, int fine_separation, tdoa_cell_track *track,
+                                        int32_t *cells, int64_t *own, int32_t *lags, double *corr, int64_t *total, tdoa_cell_track *ztrack,
+                                        int32_t *zcells, int64_t *zown, int32_t *zlags, double *zcorr, int64_t *zmap, int64_t *ztotal);
 
 /* Capture-quality statistics of every (window, station) in one streaming pass over the bytes
  * in HBM: the byte statistics of fastAnalyzeSamples
@@ -1383,6 +1452,14 @@ int tdoa_group_locate_set_fine_table(tdoa_group *g, const int32_t *delay, int n_
 int tdoa_group_process_locate_zoom(tdoa_group *g, int windows_per_stack, int min_separation, int Z, int H, int fine_separation,
                                    tdoa_location *loc_host, int32_t *lags_host, double *corr_host, int64_t *map_host, tdoa_zoom *zoom_host,
                                    int32_t *zlags_host, double *zcorr_host, int64_t *zmap_host);
+
+/* tdoa_process_locate_track_zoom over the members: the merged sum is searched on member 0, coarse tracks and windows, and the
+ * same bytes go through the merged sum as a single context returns.  Errors as there. */
+int tdoa_group_process_locate_track_zoom(tdoa_group *g, int windows_per_stack, int max_step, int min_separation, int Z, int H, int fine_step,
+                                         int fine_separation, tdoa_cell_track *track_host, int32_t *cells_host, int64_t *own_host,
+                                         int32_t *lags_host, double *corr_host, int64_t *total_host, tdoa_cell_track *ztrack_host,
+                                         int32_t *zcells_host, int64_t *zown_host, int32_t *zlags_host, double *zcorr_host, int64_t *zmap_host,
+                                         int64_t *ztotal_host);
 
 /* the sample runs member `rank` of `world` uploads for a capture of total_samples (window grid from n_min, the shortest
  * capture of the job; block offsets from the capture's own thirds): adjacent owned windows form one run, and with fewer

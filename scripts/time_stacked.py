@@ -44,9 +44,16 @@ process_locate_fine_RxC_Z[_upU]_ms), the brute force the zoom replaces; the seco
 2^22 cells.  Every `--sync-drift-fine G/H/D/R/U/RF` adds a leg: tdoa_process_sync_drift_fine(M, G, H, D, R, U, RF) against the same
 delays with all twelve outputs downloaded -- the clock-line search's launches, then the fine table, two launches per fine step
 ((2U+1)^2 candidates in tiles of 256, and the commit) and two finishes; give the same G/H/D/R to `--sync-drift` to have the leg
-it is compared with in the same process.
+it is compared with in the same process.  Every `--locate-track-zoom Z[/H[/JF]]` (H defaults to 2 Z, JF to Z, at most 16) adds, per
+`--locate` grid, per `--locate-track J` and for U = 1 and every `--locate-upsample U`, three legs: tdoa_process_locate_track_zoom(M,
+J, 1, Z, H, JF, 1) with the same grid at Z cells per cell as the fine table (name process_locate_track_zoom_RxC_JJ_Z_H_JF[_upU]_ms:
+the tracks' launches and four more kernels; records, cells, own scores, lags and correlations of both stages downloaded, the planes
+left on the device), tdoa_process_locate_track(M, J, 1) on the coarse table (the `--locate-track` leg, with U > 1 the name
+process_locate_track_RxC_JJ_upU_ms) and tdoa_process_locate_track(M, JF, 1) with that fine grid as the table (name
+process_locate_track_fine_RxC_JJF_Z[_upU]_ms), the brute force the call replaces; the last is left out, with a message, where its
+maps, steps and sums do not fit the device.
 usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--stack M] [--drift H/D]... [--track J]...
-[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]... [--locate-upsample U]... [--sync-fine G/U[/R[/RF]]]... [--locate-zoom Z[/H]]... [--sync-drift-fine G/H/D/R/U/RF]... [--max-lag N]"""
+[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]... [--locate-upsample U]... [--sync-fine G/U[/R[/RF]]]... [--locate-zoom Z[/H]]... [--sync-drift-fine G/H/D/R/U/RF]... [--locate-track-zoom Z[/H[/JF]]]... [--max-lag N]"""
 import json
 import os
 import sys
@@ -76,7 +83,7 @@ def timed(fn, steps):
 
 
 def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=(), locate_tracks=(), stack=0, emitters=(),
-         track_emitters=(), map_stats=None, sync_drifts=(), upsamples=(), max_lag=20000, sync_fines=(), zooms=(), sync_drift_fines=()):
+         track_emitters=(), map_stats=None, sync_drifts=(), upsamples=(), max_lag=20000, sync_fines=(), zooms=(), sync_drift_fines=(), track_zooms=()):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=max_lag)
     for s in range(stations):
         c.synth_capture(s, 66_666_666, ST[s % 3], TX, 0x5D0A0000 + s)
@@ -127,6 +134,31 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
                 family("process_locate_fine_%dx%d_%d%s_ms" % (rows, cols, Z, up), fine, cols_f, lambda: c.process_locate(stack, 1), U)
         for J in locate_tracks:
             family("process_locate_track_%dx%d_J%d_ms" % (rows, cols, J), table, cols, lambda J=J: c.process_locate_track(stack, J, 1))
+            for Z, H, Jf in track_zooms:
+                rows_f, cols_f = (rows - 1) * Z + 1, (cols - 1) * Z + 1
+                if rows_f * cols_f > 2 ** 22:
+                    raise SystemExit("--locate-track-zoom: the fine grid of %d x %d cells has more than 2^22 cells" % (rows_f, cols_f))
+                fine = tdoa_amd.capi.locate_grid_table([ST[s % 3] for s in range(stations)], 41.10, -96.20, 0.3 / max(rows - 1, 1) / Z,
+                                                       0.4 / max(cols - 1, 1) / Z, rows_f, cols_f, 350.0, 2e6)
+                for U in [1] + list(upsamples):
+                    up = "_up%d" % U if U > 1 else ""
+                    family("process_locate_track_zoom_%dx%d_J%d_%d_%d_%d%s_ms" % (rows, cols, J, Z, H, Jf, up), table, cols,
+                           lambda J=J, Z=Z, H=H, Jf=Jf: c.process_locate_track_zoom(Z, H, stack, J, 1, Jf, 1, want_zmap=False, want_ztotal=False),
+                           U, fine, cols_f)
+                    if U > 1:
+                        family("process_locate_track_%dx%d_J%d%s_ms" % (rows, cols, J, up), table, cols,
+                               lambda J=J: c.process_locate_track(stack, J, 1), U)
+                    name = "process_locate_track_fine_%dx%d_J%d_%d%s_ms" % (rows, cols, Jf, Z, up)
+                    if name not in legs:
+                        c.locate_set_table(fine, cols_f)
+                        c.locate_set_upsample(U)
+                        try:                                             # its maps, steps and sums may not fit the device
+                            c.process_locate_track(stack, Jf, 1)
+                        except tdoa_amd.TdoaError as e:
+                            print("%s: left out: %s" % (name, e), file=sys.stderr)
+                        else:
+                            family(name, fine, cols_f, lambda Jf=Jf: c.process_locate_track(stack, Jf, 1), U)
+                        c.locate_set_upsample(1)
             for K, guard in track_emitters:
                 family("process_locate_track_multi_%dx%d_J%d_K%d_G%d_ms" % (rows, cols, J, K, guard), table, cols,
                        lambda J=J, K=K, guard=guard: c.process_locate_track_multi(stack, J, K, guard, 1))
@@ -241,6 +273,13 @@ if __name__ == "__main__":
             raise SystemExit("--sync-drift-fine G/H/D/R/U/RF")
         sync_drift_fines.append(tuple(int(x) for x in parts))
         del args[i:i + 2]
+    track_zooms = []
+    while "--locate-track-zoom" in args:
+        i = args.index("--locate-track-zoom")
+        parts = args[i + 1].split("/")
+        z = int(parts[0])
+        track_zooms.append((z, int(parts[1]) if len(parts) > 1 else min(2 * z, 64), int(parts[2]) if len(parts) > 2 else min(z, 16)))
+        del args[i:i + 2]
     sync_drifts = []
     while "--sync-drift" in args:
         i = args.index("--sync-drift")
@@ -254,4 +293,4 @@ if __name__ == "__main__":
         syncs.append((int(g), int(r or 2)))
         del args[i:i + 2]
     main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs, locate_tracks, opt["--stack"], emitters,
-         track_emitters, map_stats, sync_drifts, upsamples, opt["--max-lag"], sync_fines, zooms, sync_drift_fines)
+         track_emitters, map_stats, sync_drifts, upsamples, opt["--max-lag"], sync_fines, zooms, sync_drift_fines, track_zooms)

@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--locate-upsample=U] [--locate-zoom=Z[/H[/SEP]]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--sync-drift=H[/D]] [--sync-drift-fine=U[/RF]] [--sync-fine=U[/RF]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--locate-upsample=U] [--locate-zoom=Z[/H[/SEP]]] [--locate-track-zoom=Z[/H[/JF[/SEP]]]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--sync-drift=H[/D]] [--sync-drift-fine=U[/RF]] [--sync-fine=U[/RF]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -159,6 +159,12 @@ int main(int argc, char **argv)
     // ZOOM line follows every LOCATE line.  H defaults to 2 Z, SEP to 1
     bool locate_zoom = false;
     int zoom_z = 1, zoom_h = -1, zoom_sep = 1;
+    // --locate-track-zoom=Z[/H[/JF[/SEP]]] (with --stack --locate --locate-track): every block's track is followed again through the
+    // (2H+1)^2-cell windows around its cells on the same grid at Z cells per cell, consecutive fine cells at most JF rows and
+    // columns apart, in the same call (tdoa_process_locate_track_zoom); a TRACKZOOM line follows every block's LOCATE-TRACK lines.
+    // H defaults to 2 Z, JF to Z (at most 16), SEP to 1
+    bool track_zoom = false;
+    int tzoom_z = 1, tzoom_h = -1, tzoom_jf = -1, tzoom_sep = 1;
     bool sync = false;
     double sync_lat = 0, sync_lon = 0, sync_h = 0;
     int sync_g = 128, sync_r = 2;
@@ -264,6 +270,17 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
+        else if (a.rfind("--locate-track-zoom=", 0) == 0) {
+            track_zoom = true;
+            const int got = std::sscanf(a.c_str() + 20, "%d/%d/%d/%d", &tzoom_z, &tzoom_h, &tzoom_jf, &tzoom_sep);
+            if (got < 2) tzoom_h = tzoom_z >= 1 && tzoom_z <= 32 ? 2 * tzoom_z : 64;
+            if (got < 3) tzoom_jf = tzoom_z >= 1 && tzoom_z <= 16 ? tzoom_z : 16;
+            if (got < 1 || tzoom_z < 1 || tzoom_z > 64 || tzoom_h < 0 || tzoom_h > 64 || tzoom_jf < 0 || tzoom_jf > 16 || tzoom_sep < 1) {
+                std::fprintf(stderr, "--locate-track-zoom=Z[/H[/JF[/SEP]]] with Z in 1 .. 64, H in 0 .. 64, JF in 0 .. 16 and SEP >= 1, e.g. "
+                                     "--locate-track-zoom=8/16/8\n");
+                return 1;
+            }
+        }
         else if (a.rfind("--track-emitters=", 0) == 0) {
             track_emitters = true;
             const int got = std::sscanf(a.c_str() + 17, "%d/%d", &temitters_k, &temitters_guard);
@@ -325,6 +342,12 @@ int main(int argc, char **argv)
     if (locate_zoom && ((long long)(locate_rows - 1) * zoom_z + 1) * ((long long)(locate_cols - 1) * zoom_z + 1) > (1ll << 22)) {
         std::fprintf(stderr, "--locate-zoom: the fine grid of %lld x %lld cells has more than 2^22 cells\n", (long long)(locate_rows - 1) * zoom_z + 1,
                      (long long)(locate_cols - 1) * zoom_z + 1);
+        return 1;
+    }
+    if (track_zoom && !locate_track) { std::fprintf(stderr, "--locate-track-zoom needs --stack --locate --locate-track\n"); return 1; }
+    if (track_zoom && ((long long)(locate_rows - 1) * tzoom_z + 1) * ((long long)(locate_cols - 1) * tzoom_z + 1) > (1ll << 22)) {
+        std::fprintf(stderr, "--locate-track-zoom: the fine grid of %lld x %lld cells has more than 2^22 cells\n",
+                     (long long)(locate_rows - 1) * tzoom_z + 1, (long long)(locate_cols - 1) * tzoom_z + 1);
         return 1;
     }
     if (sync && !locate) { std::fprintf(stderr, "--sync needs --stack --locate\n"); return 1; }
@@ -505,6 +528,9 @@ int main(int argc, char **argv)
         std::vector<tdoa_cell_track> ltracks;    // --locate-track: one record per block, a cell and its own score per stack
         std::vector<int32_t> lt_cells;           // (tdoa_process_locate_track)
         std::vector<int64_t> lt_own;
+        std::vector<tdoa_cell_track> ztracks;    // --locate-track-zoom: one more record per block, a fine cell per stack
+        std::vector<int32_t> zt_cells;           // (tdoa_process_locate_track_zoom)
+        int tzoom_cols = 1;                      // its fine grid's columns
         std::vector<tdoa_location> mlocs;        // --emitters: one record per round and stack (tdoa_process_locate_multi)
         std::vector<tdoa_cell_track> mtracks;    // --track-emitters: one record per round and block, a cell, its own score and the
         std::vector<int32_t> mt_cells, mt_pairs; // pairs' counts per round and stack (tdoa_process_locate_track_multi)
@@ -655,8 +681,24 @@ int main(int argc, char **argv)
                     ltracks.resize((size_t)(n_stacks / spb));
                     lt_cells.resize((size_t)n_stacks);
                     lt_own.resize((size_t)n_stacks);
-                    if ((rc = tdoa_process_locate_track(ctx, stack_m, ltrack_j, ltrack_sep, ltracks.data(), lt_cells.data(), lt_own.data(), nullptr,
-                                                        nullptr, nullptr)))
+                    if (track_zoom) {
+                        // the same grid at Z cells per cell, as --locate-zoom builds it (this call's Z: the fine table is set anew)
+                        const int rows_f = (locate_rows - 1) * tzoom_z + 1;
+                        tzoom_cols = (locate_cols - 1) * tzoom_z + 1;
+                        std::vector<int32_t> fine((size_t)rows_f * tzoom_cols * S);
+                        if ((rc = tdoa_locate_grid_table(lle.data(), S, grid_lat0, grid_lon0, grid_dlat / tzoom_z, grid_dlon / tzoom_z, rows_f,
+                                                         tzoom_cols, h_c, prm.sample_rate, fine.data())))
+                            return die("tdoa_locate_grid_table", rc);
+                        if ((rc = tdoa_locate_set_fine_table(ctx, fine.data(), rows_f * tzoom_cols, tzoom_cols, S)))
+                            return die("tdoa_locate_set_fine_table", rc);
+                        ztracks.resize(ltracks.size());
+                        zt_cells.resize((size_t)n_stacks);
+                        if ((rc = tdoa_process_locate_track_zoom(ctx, stack_m, ltrack_j, ltrack_sep, tzoom_z, tzoom_h, tzoom_jf, tzoom_sep, ltracks.data(),
+                                                                 lt_cells.data(), lt_own.data(), nullptr, nullptr, nullptr, ztracks.data(),
+                                                                 zt_cells.data(), nullptr, nullptr, nullptr, nullptr, nullptr)))
+                            return die("tdoa_process_locate_track_zoom", rc);
+                    } else if ((rc = tdoa_process_locate_track(ctx, stack_m, ltrack_j, ltrack_sep, ltracks.data(), lt_cells.data(), lt_own.data(),
+                                                               nullptr, nullptr, nullptr)))
                         return die("tdoa_process_locate_track", rc);
                     if ((rc = last_stats(&ltstats, ltracks.size()))) return die("tdoa_locate_last_stats", rc);
                 }
@@ -826,6 +868,15 @@ int main(int argc, char **argv)
                 std::printf("LOCATE-TRACK block %d stack %d: cell=%d lat=%.6f lon=%.6f own=%.6f\n", (int)b + 1, j, cell,
                             grid_lat0 + (cell / locate_cols) * grid_dlat, grid_lon0 + (cell % locate_cols) * grid_dlon,
                             (double)lt_own[sid] / 4294967296.0 / std::sqrt((double)stacks.n_w((int)sid)));
+            }
+            if (track_zoom) {                // the fine track: its first fine cell and where that lies, then every stack's; cell=-1: none
+                const tdoa_cell_track &z = ztracks[b];
+                std::printf("TRACKZOOM block %d: cell=%d lat=%.6f lon=%.6f positions=%d steps=%d score=%.6f runner=%.6f runner_cell=%d cells=",
+                            (int)b + 1, z.score_q > 0 ? (int)z.cell : -1, grid_lat0 + (z.cell / tzoom_cols) * grid_dlat / tzoom_z,
+                            grid_lon0 + (z.cell % tzoom_cols) * grid_dlon / tzoom_z, (int)z.positions, (int)z.steps, z.score, z.runner_up,
+                            (int)z.runner_cell);
+                for (int j = 0; j < spb; j++) std::printf("%s%d", j ? "," : "", (int)zt_cells[b * spb + j]);
+                std::printf("\n");
             }
         }
         // --track-emitters: a track per block and round, the block's rounds together, each followed by its positions; a round

@@ -13,6 +13,17 @@ struct LocateZoomHost {
     int64_t *map = nullptr;                  // [set][(2H+1)^2]
 };
 
+// what a search on the context's fine table on S stations needs of it, after the locate's own checks (the zoom locate and the
+// zoomed cell tracks, locate_track_zoom_api.inc)
+int check_locate_fine(const tdoa_ctx *ctx, int S, const char **what)
+{
+    if (ctx->fine_cells == 0) return refuse_with(what, TDOA_ERR_STATE, "no fine delay table (tdoa_locate_set_fine_table)");
+    if (ctx->fine_stations != S) return refuse_with(what, TDOA_ERR_STATE, "the fine delay table's n_stations differs from the stations searched");
+    if (ctx->locate_up > 1 && ctx->locate_fine_max * ctx->locate_up >= (1ll << 31))
+        return refuse_with(what, TDOA_ERR_UNSUPPORTED, "a fine delay table entry times the upsampling factor does not fit 32 bits");
+    return TDOA_OK;
+}
+
 struct LocateZoomSearch : StackSearch {
     LocateSearch coarse;
     int Z, H, sep;                           // fine cells per cell, the window's half side, fine_separation
@@ -35,15 +46,7 @@ struct LocateZoomSearch : StackSearch {
         if (!o.zoom) return "zoom_host is NULL";
         return nullptr;
     }
-    // what the zoom needs of the context's fine table on S stations, after the locate's own checks
-    int check_fine(const tdoa_ctx *ctx, int S, const char **what) const
-    {
-        if (ctx->fine_cells == 0) return refuse_with(what, TDOA_ERR_STATE, "no fine delay table (tdoa_locate_set_fine_table)");
-        if (ctx->fine_stations != S) return refuse_with(what, TDOA_ERR_STATE, "the fine delay table's n_stations differs from the stations searched");
-        if (ctx->locate_up > 1 && ctx->locate_fine_max * ctx->locate_up >= (1ll << 31))
-            return refuse_with(what, TDOA_ERR_UNSUPPORTED, "a fine delay table entry times the upsampling factor does not fit 32 bits");
-        return TDOA_OK;
-    }
+    int check_fine(const tdoa_ctx *ctx, int S, const char **what) const { return check_locate_fine(ctx, S, what); }
     int check_state(const tdoa_ctx *ctx, int windows_per_stack, const char **what) const override
     {
         if (ctx->prm.lag_mode == TDOA_LAGS_GO) return refuse_with(what, TDOA_ERR_UNSUPPORTED, go_what);

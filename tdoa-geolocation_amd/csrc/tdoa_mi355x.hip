@@ -50,6 +50,7 @@
 #include "stack_sync_fine.hpp"
 #include "stack_sync_drift_fine.hpp"
 #include "stack_locate_zoom.hpp"
+#include "stack_locate_track_zoom.hpp"
 
 using namespace tdoa;
 
@@ -228,7 +229,11 @@ struct tdoa_ctx {
     int fine_cells = 0, fine_cols = 0, fine_stations = 0;
     long long locate_fine_max = 0;
     DevBuf locate_fine, locate_fine_up, zoom_map, zoom_part, zoom_out, zoom_lags, zoom_corr;
-    size_t total_mem = 0;                   // of the device, 0: unknown
+    // the zoomed cell tracks (tdoa_process_locate_track_zoom), behind the cell tracks: the windows' centres [stack], the steps E
+    // [stack][(2H+1)^2][2], the sums F_0 [track][(2H+1)^2], the records [track], the fine cells and own scores [stack]; the
+    // window maps, their tiles' candidates and the fine lags and correlations lie in the zoom locate's buffers
+    DevBuf tzoom_centre, tzoom_e, tzoom_total, tzoom_out, tzoom_cells, tzoom_own;
+    size_t total_mem = 0;                  // of the device, 0: unknown
 };
 
 namespace {
@@ -596,7 +601,8 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->sfine_out, &ctx->sfine_clock, &ctx->sfine_lags, &ctx->sfine_corr,
                       &ctx->slfine_cur, &ctx->slfine_kappa, &ctx->slfine_eta, &ctx->slfine_part, &ctx->slfine_moved, &ctx->slfine_start,
                       &ctx->slfine_out, &ctx->slfine_clock, &ctx->slfine_rate, &ctx->slfine_rows, &ctx->slfine_lags, &ctx->slfine_corr,
-                      &ctx->locate_fine, &ctx->locate_fine_up, &ctx->zoom_map, &ctx->zoom_part, &ctx->zoom_out, &ctx->zoom_lags, &ctx->zoom_corr};
+                      &ctx->locate_fine, &ctx->locate_fine_up, &ctx->zoom_map, &ctx->zoom_part, &ctx->zoom_out, &ctx->zoom_lags, &ctx->zoom_corr,
+                      &ctx->tzoom_centre, &ctx->tzoom_e, &ctx->tzoom_total, &ctx->tzoom_out, &ctx->tzoom_cells, &ctx->tzoom_own};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1334,6 +1340,7 @@ int tdoa_solve_surface(const double *stations_lle, int n_stations, const double 
 #include "locate_api.inc"
 #include "locate_run.inc"
 #include "locate_zoom_api.inc"
+#include "locate_track_zoom_api.inc"
 #include "sync_api.inc"
 #include "sync_fine_api.inc"
 #include "sync_drift_api.inc"

@@ -135,6 +135,7 @@ SYMBOLS = [
     "tdoa_debug_locate_zoom_from_q",
     "tdoa_process_sync_drift_fine", "tdoa_group_process_sync_drift_fine", "tdoa_debug_sync_drift_fine_from_q",
     "tdoa_sync_line_clock16",
+    "tdoa_process_locate_track_zoom", "tdoa_group_process_locate_track_zoom", "tdoa_debug_locate_track_zoom_from_q",
 ]
 
 
@@ -206,9 +207,25 @@ LATER_SEARCHES = {s.name: s for s in (
 )}
 
 
+# ... and after that one (tests pin LATER_SEARCHES to its one name as they pin SEARCHES): the zoomed cell tracks, whose z outputs
+# are written over a poison pattern like the zoom's
+_TRACK_ZOOM_OUT = (_Out("ztrack", CELL_TRACK_DTYPE, ("n_tracks",), poison=True), _Out("zcells", np.int32, ("n_tracks", "L"), poison=True),
+                   _Out("zown", np.int64, ("n_tracks", "L"), poison=True), _Out("zlags", np.int32, ("n_sets", "P"), poison=True),
+                   _Out("zcorr", np.float64, ("n_sets", "P"), poison=True),
+                   _Out("zmap", np.int64, ("n_sets", "window"), "want_zmap", poison=True),
+                   _Out("ztotal", np.int64, ("n_tracks", "window"), "want_ztotal", poison=True))
+TRACK_ZOOM_SEARCHES = {s.name: s for s in (
+    _Search("locate_track_zoom", ("max_step", "min_separation", "Z", "H", "fine_step", "fine_separation"),
+            _TRACK_OUT + _TRACK_ZOOM_OUT, track_len=True, stats="track"),
+)}
+
+
 def _search(name):
-    """the record of search `name`, from either table"""
-    return SEARCHES[name] if name in SEARCHES else LATER_SEARCHES[name]
+    """the record of search `name`, from any of the tables"""
+    for table in (SEARCHES, LATER_SEARCHES, TRACK_ZOOM_SEARCHES):
+        if name in table:
+            return table[name]
+    raise KeyError(name)
 
 
 def _search_argtypes(s, route):
@@ -347,7 +364,7 @@ def load(build_if_missing=True):
     L.tdoa_debug_upsample_q.argtypes = [vp, i64p, C.c_int, C.c_int, i64p]
     L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
                                         C.POINTER(C.c_int)]
-    for s in list(SEARCHES.values()) + list(LATER_SEARCHES.values()):
+    for s in list(SEARCHES.values()) + list(LATER_SEARCHES.values()) + list(TRACK_ZOOM_SEARCHES.values()):
         for route, entry in s.entries.items():
             getattr(L, entry).argtypes = _search_argtypes(s, route)
     _lib = L
@@ -409,6 +426,27 @@ class _LaterContextSearches:
             track_len=track_len, n_w=n_w, gate=gate, max_drift=max_drift, drift_den=drift_den, rounds=rounds, U=U,
             fine_rounds=fine_rounds, ref_delay=ref_delay, centre=centre))
 
+    def process_locate_track_zoom(self, Z, H, windows_per_stack=0, max_step=0, min_separation=1, fine_step=0, fine_separation=1,
+                                  want_total=False, want_zmap=True, want_ztotal=True):
+        """tdoa_process_locate_track_zoom -> process_locate_track's dict (the coarse stage's bytes) and {"ztrack": [n_tracks]
+        CELL_TRACK_DTYPE (its cells are fine cells), "zcells": [n_tracks][L] int32, "zown": [n_tracks][L] int64, "zlags":
+        [n_stacks][P] int32 (1/U sample), "zcorr": [n_stacks][P] float64, with want_zmap "zmap": [n_stacks][(2H+1)^2] int64 and
+        with want_ztotal "ztotal": [n_tracks][(2H+1)^2] int64}: per block the track through the (2H+1)^2-cell windows of the fine
+        table around Z x the coarse track's cells, consecutive fine cells at most fine_step rows and columns apart, with the
+        largest summed score.  The z arrays are written over a poison pattern"""
+        return _process_search(self, self, "locate_track_zoom", dict(
+            windows_per_stack=windows_per_stack, max_step=max_step, min_separation=min_separation, Z=Z, H=H, fine_step=fine_step,
+            fine_separation=fine_separation, want_total=want_total, want_zmap=want_zmap, want_ztotal=want_ztotal))
+
+    def locate_track_zoom_from_q(self, q, n_stations, track_len, Z, H, n_w=1, max_step=0, min_separation=1, fine_step=0,
+                                 fine_separation=1, want_total=True, want_zmap=True, want_ztotal=True):
+        """tdoa_debug_locate_track_zoom_from_q: the tracks' and the zoomed tracks' kernels on the caller's words q
+        [n_sets][P][2 max_lag - 1] int64, set t track_len + j position j of track t, with the context's table, fine table and
+        clocks -> what process_locate_track_zoom returns, n_sets for n_stacks"""
+        return self._from_q("locate_track_zoom", q, n_stations, dict(
+            track_len=track_len, n_w=n_w, max_step=max_step, min_separation=min_separation, Z=Z, H=H, fine_step=fine_step,
+            fine_separation=fine_separation, want_total=want_total, want_zmap=want_zmap, want_ztotal=want_ztotal))
+
 
 class _LaterGroupSearches:
     def process_sync_drift_fine(self, ref_delay, windows_per_stack=0, gate=0, max_drift=0, drift_den=1, rounds=0, U=16, fine_rounds=2,
@@ -417,6 +455,13 @@ class _LaterGroupSearches:
         return _process_search(self, self.member(0), "sync_drift_fine", dict(
             windows_per_stack=windows_per_stack, gate=gate, max_drift=max_drift, drift_den=drift_den, rounds=rounds, U=U,
             fine_rounds=fine_rounds, ref_delay=ref_delay, centre=centre), n_tracks=3)
+
+    def process_locate_track_zoom(self, Z, H, windows_per_stack=0, max_step=0, min_separation=1, fine_step=0, fine_separation=1,
+                                  want_total=False, want_zmap=True, want_ztotal=True):
+        """tdoa_group_process_locate_track_zoom -> Context.process_locate_track_zoom's outputs, byte-identical to a single context's"""
+        return _process_search(self, self.member(0), "locate_track_zoom", dict(
+            windows_per_stack=windows_per_stack, max_step=max_step, min_separation=min_separation, Z=Z, H=H, fine_step=fine_step,
+            fine_separation=fine_separation, want_total=want_total, want_zmap=want_zmap, want_ztotal=want_ztotal))
 
 
 class Context(_LaterContextSearches):
