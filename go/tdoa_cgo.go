@@ -641,6 +641,82 @@ func SyncLineClock16(clock16, fineRate []int32, u, driftDen, first, n int) ([]in
 	return out, nil
 }
 
+// ClockMix is one entry of a clock mix (the header's tdoa_clock_mix): the row of a stack is the nearest integer to
+// (Wa clock16[A] + Wb clock16[B]) / (Wa + Wb), halves away from zero.  {t, t, 1, 0} is stack t's own clock, {a, b, 1, 1} the
+// midpoint of two stacks' clocks.
+type ClockMix struct {
+	A, B, Wa, Wb int32
+}
+
+func mixPtr(mix []ClockMix) *C.tdoa_clock_mix {
+	if len(mix) == 0 {
+		return nil
+	}
+	return (*C.tdoa_clock_mix)(unsafe.Pointer(&mix[0]))
+}
+
+// MidpointMix is the mix for [reference | target | reference] blocks of stacksPerBlock stacks: blocks 1 and 3 keep their own
+// rows, stack j of block 2 gets the midpoint of stack j of blocks 1 and 3.
+func MidpointMix(stacksPerBlock int) []ClockMix {
+	l := int32(stacksPerBlock)
+	mix := make([]ClockMix, 3*stacksPerBlock)
+	for t := int32(0); t < 3*l; t++ {
+		mix[t] = ClockMix{t, t, 1, 0}
+		if t >= l && t < 2*l {
+			mix[t] = ClockMix{t - l, t + l, 1, 1}
+		}
+	}
+	return mix
+}
+
+// ClockMixRows is the mix in plain C (host only): clock16 [stack][station] in units of 1/16 sample and one entry per row ->
+// [row][station], what LocateSetClock takes and what ProcessSyncLocate locates under.
+func ClockMixRows(clock16 []int32, stations int, mix []ClockMix) ([]int32, error) {
+	if stations < 1 || len(clock16) == 0 || len(clock16)%stations != 0 || len(mix) == 0 {
+		return nil, fmt.Errorf("tdoa_clock_mix_rows: clock16 must be [stack][station] and the mix not empty")
+	}
+	out := make([]int32, len(mix)*stations)
+	if rc := C.tdoa_clock_mix_rows(i32Ptr(clock16), C.int(len(clock16)/stations), C.int(stations), mixPtr(mix), C.int(len(mix)),
+		i32Ptr(out)); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_clock_mix_rows: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	return out, nil
+}
+
+// SyncLocate is what ProcessSyncLocate returns: ProcessSyncFine's outputs, the stacks' clock rows [stack][station] in units of
+// 1/16 sample, and ProcessLocateZoom's outputs under those rows.
+type SyncLocate struct {
+	SyncFine
+	Rows []int32
+	LocateZoom
+}
+
+// ProcessSyncLocate is the header's "clocks to fix in one call": the fine clock search, a clock row per stack mixed on the device
+// from its clocks (mix: one entry per stack, nil: every stack its own clock; MidpointMix for the usual captures) and the zoom
+// locate under those rows, in one step.  The clock table of LocateSetClock is neither read nor changed.
+func (g *gpuCorrelator) ProcessSyncLocate(windowsPerStack, gate, rounds, u, fineRounds int, refDelay, centre []int32, mix []ClockMix,
+	minSeparation, z, h, fineSeparation int) (*SyncLocate, error) {
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs, stations := int(C.tdoa_num_pairs(g.ctx)), len(refDelay)
+	if int(total)*pairs == 0 || stations*(stations-1)/2 != pairs || (mix != nil && len(mix) != int(total)) {
+		return nil, fmt.Errorf("tdoa_process_sync_locate: no stacks, fewer than two stations, not one delay per station or not one mix entry per stack")
+	}
+	o := &SyncLocate{SyncFine: *newSyncFine(int(total), stations, pairs), Rows: make([]int32, int(total)*stations),
+		LocateZoom: *newLocateZoom(int(total), pairs)}
+	f, l := &o.SyncFine, &o.LocateZoom
+	if rc := C.tdoa_process_sync_locate(g.ctx, C.int(windowsPerStack), C.int(gate), C.int(rounds), C.int(u), C.int(fineRounds), tablePtr(refDelay),
+		centrePtr(centre), mixPtr(mix), C.int(minSeparation), C.int(z), C.int(h), C.int(fineSeparation), &f.Sync[0], i32Ptr(f.Clock),
+		i32Ptr(f.Lags), (*C.double)(unsafe.Pointer(&f.Corr[0])), &f.Fine[0], i32Ptr(f.Clock16), i32Ptr(f.FineLags),
+		(*C.double)(unsafe.Pointer(&f.FineCorr[0])), i32Ptr(o.Rows), &l.Loc[0], i32Ptr(l.Lags), (*C.double)(unsafe.Pointer(&l.Corr[0])), nil,
+		&l.Zoom[0], i32Ptr(l.ZLags), (*C.double)(unsafe.Pointer(&l.ZCorr[0])), nil); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_process_sync_locate: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return o, nil
+}
+
 // windowQuality is fastAnalyzeSamples' statistics (fast_analyzer.go:117-155) for every (window, station).
 func (g *gpuCorrelator) windowQuality(stations int) ([]C.tdoa_window_quality, error) {
 	var perBlock, total C.int
@@ -964,6 +1040,32 @@ func (g *Group) ProcessSyncFine(windowsPerStack, gate, rounds, u, fineRounds int
 		(*C.double)(unsafe.Pointer(&o.Corr[0])), &o.Fine[0], (*C.int32_t)(unsafe.Pointer(&o.Clock16[0])),
 		(*C.int32_t)(unsafe.Pointer(&o.FineLags[0])), (*C.double)(unsafe.Pointer(&o.FineCorr[0]))); rc != C.TDOA_OK {
 		return nil, fmt.Errorf("tdoa_group_process_sync_fine: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return o, nil
+}
+
+// ProcessSyncLocate is gpuCorrelator.ProcessSyncLocate over the group: the members' fixed-point partial sums are added on the
+// host and searched on member 0 with its table, fine table and settings, the same bytes one context returns.
+func (g *Group) ProcessSyncLocate(windowsPerStack, gate, rounds, u, fineRounds int, refDelay, centre []int32, mix []ClockMix,
+	minSeparation, z, h, fineSeparation int) (*SyncLocate, error) {
+	m := C.tdoa_group_member(g.g, 0)
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(m, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs, stations := int(C.tdoa_num_pairs(m)), len(refDelay)
+	if int(total)*pairs == 0 || stations*(stations-1)/2 != pairs || (mix != nil && len(mix) != int(total)) {
+		return nil, fmt.Errorf("tdoa_group_process_sync_locate: no stacks, fewer than two stations, not one delay per station or not one mix entry per stack")
+	}
+	o := &SyncLocate{SyncFine: *newSyncFine(int(total), stations, pairs), Rows: make([]int32, int(total)*stations),
+		LocateZoom: *newLocateZoom(int(total), pairs)}
+	f, l := &o.SyncFine, &o.LocateZoom
+	if rc := C.tdoa_group_process_sync_locate(g.g, C.int(windowsPerStack), C.int(gate), C.int(rounds), C.int(u), C.int(fineRounds),
+		tablePtr(refDelay), centrePtr(centre), mixPtr(mix), C.int(minSeparation), C.int(z), C.int(h), C.int(fineSeparation), &f.Sync[0],
+		i32Ptr(f.Clock), i32Ptr(f.Lags), (*C.double)(unsafe.Pointer(&f.Corr[0])), &f.Fine[0], i32Ptr(f.Clock16), i32Ptr(f.FineLags),
+		(*C.double)(unsafe.Pointer(&f.FineCorr[0])), i32Ptr(o.Rows), &l.Loc[0], i32Ptr(l.Lags), (*C.double)(unsafe.Pointer(&l.Corr[0])), nil,
+		&l.Zoom[0], i32Ptr(l.ZLags), (*C.double)(unsafe.Pointer(&l.ZCorr[0])), nil); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_group_process_sync_locate: %s", C.GoString(C.tdoa_group_last_error(g.g)))
 	}
 	return o, nil
 }

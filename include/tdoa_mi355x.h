@@ -1164,6 +1164,79 @@ int tdoa_debug_locate_track_zoom_from_q(tdoa_ctx *ctx, const int64_t *q, int n_s
                                         int32_t *cells, int64_t *own, int32_t *lags, double *corr, int64_t *total, tdoa_cell_track *ztrack,
                                         int32_t *zcells, int64_t *zown, int32_t *zlags, double *zcorr, int64_t *zmap, int64_t *ztotal);
 
+/* Clocks to fix in one call.  Every capture is [reference | target | reference]: the station clocks are found on the reference
+ * blocks, carried over to the target block and the target is located under them.  tdoa_process_sync_fine, a mix of its clock
+ * rows, tdoa_locate_set_clock and tdoa_process_locate_zoom do that in two steps with the clocks going through the host; this
+ * call does it in one step graph behind one accumulation of the stacks, and the clocks never leave the device.
+ *   1. The fine clock search: tdoa_process_sync_fine(windows_per_stack, gate, rounds, U, fine_rounds, ref_delay, centre)
+ *      unchanged, on every stack.  The first eight outputs are that call's bytes.
+ *   2. A clock row for every stack, from the fine clocks c16 = clock16 of step 1.  Which stacks' clocks make which stack's row
+ *      is data: mix[t] = (a, b, wa, wb), one entry per stack, and for station s, in 64 bits,
+ *        den = wa + wb,  T = wa c16[a][s] + wb c16[b][s],  row[t][s] = sgn(T) ((2 |T| + den) div (2 den)):
+ *      the nearest integer to T / den, halves away from zero.  Two identities:
+ *        (t, t, 1, 0) is the stack's own clock, row[t] = c16[t];
+ *        (a, b, 1, 1) is the midpoint of two rows, sgn(T) ((|T| + 1) div 2), the rule the target block of
+ *        tdoa_processor --sync-fine gets.
+ *      Unequal weights give a ramp between two reference stacks.  The sum is rounded, not an increment: a ramp that rounds
+ *      its step and adds it (as the coarse clocks' ramp does) differs from this on exact halves of opposite sign, and the two
+ *      are not claimed equal.  mix == NULL: every stack takes its own clock.  A stack whose fine record is the zero record
+ *      contributes its zero clocks like any other; the records tell.  rows_host receives the rows.
+ *   3. The zoom locate: tdoa_process_locate_zoom(windows_per_stack, min_separation, Z, H, fine_separation) unchanged, on every
+ *      stack, under those rows: the last eight outputs are that call's bytes after tdoa_locate_set_clock(rows).  It honours the
+ *      context's table, fine table, upsample setting and statistics setting as that call does, and tdoa_locate_last_stats
+ *      returns what it returns after that call.
+ * The context's own clock table (tdoa_locate_set_clock) is neither read nor changed, whatever its shape: the call after
+ * this one finds it as it was.
+ * One kernel between the two searches' launches; the mix, like ref_delay and centre, is data: a new mix, new delays, centres,
+ * table or fine table of the same shape replay the captured graph.  The graph's key is both searches' words, the locate's
+ * clock flag on.
+ * Scope: the chain for free-running receivers (tdoa_process_sync_drift_fine, the line continued, tdoa_process_locate_track_zoom)
+ * needs tdoa_sync_line_clock16's rule on the device, not a mix, and is not this call; nor are the rounds of
+ * tdoa_process_locate_multi.  fine_rounds = 0 gives clock16 = 16 clock, the coarse clock search alone; Z = 1, H = 0 with the
+ * fine table set to the table is the form without a zoom.
+ * The refusals are those of the two calls, and: TDOA_ERR_INVALID: a mix entry with a or b outside 0 .. n_stacks_total - 1, a
+ * negative weight, or wa + wb outside 1 .. 65536.  TDOA_ERR_UNSUPPORTED: with the upsample setting U_loc > 1, a station with
+ * 16 (|centre| + gate + 1) U_loc >= 2^31: a row times the factor might not fit 32 bits (the message is the clock table's).
+ * The weights form a convex combination, so |row| <= max |c16| <= 16 (|centre| + gate + 1), and no value on the device needs
+ * a check.  All checks happen before anything needs a device. */
+typedef struct {
+    int32_t a, b;         /* the two stacks whose fine clocks are mixed */
+    int32_t wa, wb;       /* their weights, >= 0, 1 <= wa + wb <= 65536 */
+} tdoa_clock_mix;
+
+int tdoa_process_sync_locate(tdoa_ctx *ctx, int windows_per_stack, int gate /* G */, int rounds /* R */, int U, int fine_rounds /* Rf */,
+                             const int32_t *ref_delay /* [n_stations] */, const int32_t *centre /* [n_stations], NULL: all 0 */,
+                             const tdoa_clock_mix *mix /* [n_stacks_total], NULL: every stack its own clock */,
+                             int min_separation, int Z, int H, int fine_separation,
+                             tdoa_sync *sync_host, int32_t *clock_host, int32_t *lags_host, double *corr_host,
+                             tdoa_sync *fine_host, int32_t *clock16_host, int32_t *fine_lags_host,
+                             double *fine_corr_host /* tdoa_process_sync_fine's eight; sync_host and fine_host required */,
+                             int32_t *rows_host /* [n_stacks_total][n_stations], 1/16 sample, may be NULL */,
+                             tdoa_location *loc_host, int32_t *loc_lags_host, double *loc_corr_host, int64_t *map_host,
+                             tdoa_zoom *zoom_host, int32_t *zlags_host, double *zcorr_host,
+                             int64_t *zmap_host /* tdoa_process_locate_zoom's eight; loc_host and zoom_host required */);
+
+/* tests only: the same kernels on the caller's words, as tdoa_debug_sync_fine_from_q and tdoa_debug_locate_zoom_from_q, with
+ * the context's table, fine table and settings; mix is [n_sets] and names sets.  Refuses what the call and those two refuse. */
+int tdoa_debug_sync_locate_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int gate, int rounds, int U,
+                                  int fine_rounds, const int32_t *ref_delay, const int32_t *centre, const tdoa_clock_mix *mix,
+                                  int min_separation, int Z, int H, int fine_separation, tdoa_sync *sync_host, int32_t *clock_host,
+                                  int32_t *lags_host, double *corr_host, tdoa_sync *fine_host, int32_t *clock16_host, int32_t *fine_lags_host,
+                                  double *fine_corr_host, int32_t *rows_host, tdoa_location *loc_host, int32_t *loc_lags_host,
+                                  double *loc_corr_host, int64_t *map_host, tdoa_zoom *zoom_host, int32_t *zlags_host, double *zcorr_host,
+                                  int64_t *zmap_host);
+
+/* Host only: step 2 in plain C.  clock16 [n_stacks][n_stations], mix [n_rows] -> rows [n_rows][n_stations].
+ * TDOA_ERR_INVALID: a NULL pointer, a count < 1, or a mix entry the call above refuses (a, b against n_stacks). */
+int tdoa_clock_mix_rows(const int32_t *clock16, int n_stacks, int n_stations, const tdoa_clock_mix *mix, int n_rows, int32_t *rows);
+
+/* tests only: the kernel of step 2 alone on the caller's clocks, with U_loc (1, 2, 4, 8 or 16) an argument; the context's
+ * setting is not read.  rows [n_rows][n_stations]; cdiff [n_rows][n_pairs] = row[j] - row[i] in tdoa_locate_set_clock's pair
+ * order (i < j, i first); cdiff_up = U_loc x cdiff: the two arrays the family's kernels take.  All outputs required.
+ * TDOA_ERR_INVALID as tdoa_clock_mix_rows, n_stacks or n_rows above 65535, n_stations outside 2 .. 64, another U_loc. */
+int tdoa_debug_clock_mix(tdoa_ctx *ctx, const int32_t *clock16, int n_stacks, int n_stations, const tdoa_clock_mix *mix, int n_rows,
+                         int U_loc, int32_t *rows, int64_t *cdiff, int64_t *cdiff_up);
+
 /* Capture-quality statistics of every (window, station) in one streaming pass over the bytes
  * in HBM: the byte statistics of fastAnalyzeSamples
  * (fast_analyzer.go:117-155) and the block power of validateDataFile (collector.go:219-224).
@@ -1460,6 +1533,15 @@ int tdoa_group_process_locate_track_zoom(tdoa_group *g, int windows_per_stack, i
                                          int32_t *lags_host, double *corr_host, int64_t *total_host, tdoa_cell_track *ztrack_host,
                                          int32_t *zcells_host, int64_t *zown_host, int32_t *zlags_host, double *zcorr_host, int64_t *zmap_host,
                                          int64_t *ztotal_host);
+
+/* tdoa_process_sync_locate over the members: the merged sum is searched on member 0 -- its table, fine table and settings,
+ * as for the zoom -- and the same bytes go through the merged sum as a single context returns.  Errors as there. */
+int tdoa_group_process_sync_locate(tdoa_group *g, int windows_per_stack, int gate, int rounds, int U, int fine_rounds,
+                                   const int32_t *ref_delay, const int32_t *centre, const tdoa_clock_mix *mix, int min_separation, int Z, int H,
+                                   int fine_separation, tdoa_sync *sync_host, int32_t *clock_host, int32_t *lags_host, double *corr_host,
+                                   tdoa_sync *fine_host, int32_t *clock16_host, int32_t *fine_lags_host, double *fine_corr_host,
+                                   int32_t *rows_host, tdoa_location *loc_host, int32_t *loc_lags_host, double *loc_corr_host,
+                                   int64_t *map_host, tdoa_zoom *zoom_host, int32_t *zlags_host, double *zcorr_host, int64_t *zmap_host);
 
 /* the sample runs member `rank` of `world` uploads for a capture of total_samples (window grid from n_min, the shortest
  * capture of the job; block offsets from the capture's own thirds): adjacent owned windows form one run, and with fewer

@@ -51,9 +51,15 @@ the tracks' launches and four more kernels; records, cells, own scores, lags and
 left on the device), tdoa_process_locate_track(M, J, 1) on the coarse table (the `--locate-track` leg, with U > 1 the name
 process_locate_track_RxC_JJ_upU_ms) and tdoa_process_locate_track(M, JF, 1) with that fine grid as the table (name
 process_locate_track_fine_RxC_JJF_Z[_upU]_ms), the brute force the call replaces; the last is left out, with a message, where its
-maps, steps and sums do not fit the device.
+maps, steps and sums do not fit the device.  `--sync-locate` adds, per `--locate` grid, `--locate-zoom Z[/H]`, `--sync-fine G/U[/R[/RF]]`
+and for U_loc = 1 and every `--locate-upsample U`, two legs: tdoa_process_sync_locate(M, G, R, U, RF, midpoint mix, 1, Z, H, 1) with
+the seventeen outputs but the maps downloaded (name process_sync_locate_RxC_Z_H_G_U_R_RF[_upU]_ms: the fine clock search's
+launches, one kernel for the rows and the zoom locate's launches in one step behind one accumulation), and the chain it
+replaces, timed as one unit (name sync_locate_chain_RxC_Z_H_G_U_R_RF[_upU]_ms): tdoa_process_sync_fine, tdoa_clock_mix_rows on
+the host, tdoa_locate_set_clock and tdoa_process_locate_zoom.  Give the same options their own legs (they are there already) to
+have process_sync_fine and process_locate_zoom in the same process.
 usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--stack M] [--drift H/D]... [--track J]...
-[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]... [--locate-upsample U]... [--sync-fine G/U[/R[/RF]]]... [--locate-zoom Z[/H]]... [--sync-drift-fine G/H/D/R/U/RF]... [--locate-track-zoom Z[/H[/JF]]]... [--max-lag N]"""
+[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]... [--locate-upsample U]... [--sync-fine G/U[/R[/RF]]]... [--locate-zoom Z[/H]]... [--sync-drift-fine G/H/D/R/U/RF]... [--locate-track-zoom Z[/H[/JF]]]... [--sync-locate] [--max-lag N]"""
 import json
 import os
 import sys
@@ -83,7 +89,8 @@ def timed(fn, steps):
 
 
 def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=(), locate_tracks=(), stack=0, emitters=(),
-         track_emitters=(), map_stats=None, sync_drifts=(), upsamples=(), max_lag=20000, sync_fines=(), zooms=(), sync_drift_fines=(), track_zooms=()):
+         track_emitters=(), map_stats=None, sync_drifts=(), upsamples=(), max_lag=20000, sync_fines=(), zooms=(), sync_drift_fines=(), track_zooms=(),
+         sync_locate=False):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=max_lag)
     for s in range(stations):
         c.synth_capture(s, 66_666_666, ST[s % 3], TX, 0x5D0A0000 + s)
@@ -99,10 +106,19 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
     for G in closures:
         legs["process_closure_%d_ms" % G] = lambda G=G: c.process_closure(0, G, 1)
     setup = {}
+    ref = tdoa_amd.capi.locate_grid_table([ST[s % 3] for s in range(stations)], TX[0], TX[1], 0.0, 0.0, 1, 1, TX[2], 2e6)[0]
+    mix = tdoa_amd.clock_mix.midpoint_mix(c.num_stacks(stack)[0])
+
+    def chain(G, R, U, Rf, Z, H):
+        """what a caller does without tdoa_process_sync_locate, as one unit"""
+        found = c.process_sync_fine(ref, stack, G, R, U, Rf)
+        c.locate_set_clock(tdoa_amd.capi.clock_mix_rows(found["clock16"], mix))
+        return c.process_locate_zoom(Z, H, stack, 1, 1, want_zmap=False)
 
     def family(name, table, cols, fn, U=1, fine=None, fine_cols=None):
         """a leg of the delay-table family with the statistics off and, with --map-stats, the same leg with them on"""
         def base():
+            c.locate_set_clock(None)                                         # (the chain leg of --sync-locate leaves its rows there)
             c.locate_set_table(table, cols)
             if fine is not None:
                 c.locate_set_fine_table(fine, fine_cols)
@@ -132,6 +148,13 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
                 family("process_locate_zoom_%dx%d_%d_%d%s_ms" % (rows, cols, Z, H, up), table, cols,
                        lambda Z=Z, H=H: c.process_locate_zoom(Z, H, stack, 1, 1, want_zmap=False), U, fine, cols_f)
                 family("process_locate_fine_%dx%d_%d%s_ms" % (rows, cols, Z, up), fine, cols_f, lambda: c.process_locate(stack, 1), U)
+                for G, Uf, R, Rf in sync_fines if sync_locate else ():
+                    tag = "%dx%d_%d_%d_%d_%d_%d_%d%s_ms" % (rows, cols, Z, H, G, Uf, R, Rf, up)
+                    family("process_sync_locate_" + tag, table, cols,
+                           lambda Z=Z, H=H, G=G, Uf=Uf, R=R, Rf=Rf: c.process_sync_locate(ref, Z, H, stack, G, R, Uf, Rf, None, mix, 1, 1,
+                                                                                          want_zmap=False), U, fine, cols_f)
+                    family("sync_locate_chain_" + tag, table, cols, lambda Z=Z, H=H, G=G, Uf=Uf, R=R, Rf=Rf: chain(G, R, Uf, Rf, Z, H), U, fine,
+                           cols_f)
         for J in locate_tracks:
             family("process_locate_track_%dx%d_J%d_ms" % (rows, cols, J), table, cols, lambda J=J: c.process_locate_track(stack, J, 1))
             for Z, H, Jf in track_zooms:
@@ -165,7 +188,6 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
         for K, guard in emitters:
             family("process_locate_multi_%dx%d_K%d_G%d_ms" % (rows, cols, K, guard), table, cols,
                    lambda K=K, guard=guard: c.process_locate_multi(stack, K, guard, 1))
-    ref = tdoa_amd.capi.locate_grid_table([ST[s % 3] for s in range(stations)], TX[0], TX[1], 0.0, 0.0, 1, 1, TX[2], 2e6)[0]
     for G, R in syncs:
         legs["process_sync_%d_%d_ms" % (G, R)] = lambda G=G, R=R: c.process_sync(ref, 0, G, R)
     for G, H, D, R in sync_drifts:
@@ -280,6 +302,9 @@ if __name__ == "__main__":
         z = int(parts[0])
         track_zooms.append((z, int(parts[1]) if len(parts) > 1 else min(2 * z, 64), int(parts[2]) if len(parts) > 2 else min(z, 16)))
         del args[i:i + 2]
+    sync_locate = "--sync-locate" in args
+    if sync_locate:
+        args.remove("--sync-locate")
     sync_drifts = []
     while "--sync-drift" in args:
         i = args.index("--sync-drift")
@@ -293,4 +318,4 @@ if __name__ == "__main__":
         syncs.append((int(g), int(r or 2)))
         del args[i:i + 2]
     main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs, locate_tracks, opt["--stack"], emitters,
-         track_emitters, map_stats, sync_drifts, upsamples, opt["--max-lag"], sync_fines, zooms, sync_drift_fines, track_zooms)
+         track_emitters, map_stats, sync_drifts, upsamples, opt["--max-lag"], sync_fines, zooms, sync_drift_fines, track_zooms, sync_locate)

@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--locate-upsample=U] [--locate-zoom=Z[/H[/SEP]]] [--locate-track-zoom=Z[/H[/JF[/SEP]]]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--sync-drift=H[/D]] [--sync-drift-fine=U[/RF]] [--sync-fine=U[/RF]] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--locate-upsample=U] [--locate-zoom=Z[/H[/SEP]]] [--locate-track-zoom=Z[/H[/JF[/SEP]]]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--sync-drift=H[/D]] [--sync-drift-fine=U[/RF]] [--sync-fine=U[/RF]] [--one-call] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -177,6 +177,10 @@ int main(int argc, char **argv)
     // sweeps on the upsampled surfaces' words (tdoa_process_sync_fine); blocks 1 and 3 are located under their own refined clocks,
     // block 2 under the midpoint of the two rows rounded to 1/16 sample
     bool sync_fine = false;
+    // --one-call (with --stack --locate --sync --sync-fine --locate-zoom): the clocks, the target block's midpoint row and the zoom
+    // locate in one call (tdoa_process_sync_locate): the clocks stay on the device and the stacks are accumulated once.  Prints
+    // what the run without the flag prints
+    bool one_call = false;
     int sfine_u = 16, sfine_r = 2;
     // --sync-drift-fine=U[/RF] (with --sync-drift), U in 2, 4, 8, 16: the lines' offsets and rates are refined to 1/U sample in RF
     // sweeps (tdoa_process_sync_drift_fine); blocks 1 and 3 are located under their own fine rows, block 2 under block 1's fine
@@ -321,6 +325,7 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
+        else if (a == "--one-call") one_call = true;
         else if (a == "--gate" && i + 1 < argc) gate = std::atof(argv[++i]);
         else if (a == "--device" && i + 1 < argc) prm.device = std::atoi(argv[++i]);
         else if (a == "--window" && i + 1 < argc) prm.window_len = std::atoll(argv[++i]);
@@ -354,6 +359,10 @@ int main(int argc, char **argv)
     if (sync_drift && !sync) { std::fprintf(stderr, "--sync-drift needs --stack --locate --sync\n"); return 1; }
     if (sync_drift_fine && !sync_drift) { std::fprintf(stderr, "--sync-drift-fine needs --stack --locate --sync --sync-drift\n"); return 1; }
     if (sync_fine && (!sync || sync_drift)) { std::fprintf(stderr, "--sync-fine needs --stack --locate --sync and no --sync-drift\n"); return 1; }
+    if (one_call && (!sync_fine || !locate_zoom)) {
+        std::fprintf(stderr, "--one-call needs --stack --locate --sync --sync-fine --locate-zoom\n");
+        return 1;
+    }
     if (sync && !sync_drift && stack_m != 0) { std::fprintf(stderr, "--sync needs whole-block stacks: --stack without =WINDOWS\n"); return 1; }
     if (pos.size() < 4) {                                     // processor.go:1048-1052
         usage(argv[0]);
@@ -538,6 +547,7 @@ int main(int argc, char **argv)
         std::vector<tdoa_map_stats> lstats, mstats, ltstats, mtstats;      // --map-stats: one record per record of the four above
         std::vector<tdoa_sync> syncs;            // --sync: one record and S clocks per block (tdoa_process_sync)
         std::vector<int32_t> clocks;
+        std::vector<int32_t> ref16;              // --one-call: the reference emitter's delays, kept for the one call
         std::vector<tdoa_sync> sfines;           // --sync-fine: one more record and S clocks in 1/16 sample per block (tdoa_process_sync_fine)
         std::vector<int32_t> clocks16;
         std::vector<tdoa_sync_line> lines;       // --sync-drift: one record, S clocks and S rates per block (tdoa_process_sync_drift)
@@ -619,6 +629,8 @@ int main(int argc, char **argv)
                             if ((rc = tdoa_sync_line_clock(clocks.data(), rates.data(), S, sdrift_d, spb, spb, table16.data() + (size_t)spb * S)))
                                 return die("tdoa_sync_line_clock", rc);
                         }
+                    } else if (one_call) {
+                        ref16 = ref;                         // the clocks are searched with the zoom locate, below
                     } else if (sync_fine) {
                         syncs.resize((size_t)n_stacks);
                         clocks.resize((size_t)n_stacks * S);
@@ -645,7 +657,7 @@ int main(int argc, char **argv)
                             table16[2 * (size_t)S + s] = TDOA_DELAY_UNIT * after;
                         }
                     }
-                    if ((rc = tdoa_locate_set_clock(ctx, table16.data(), n_stacks, S))) return die("tdoa_locate_set_clock", rc);
+                    if (!one_call && (rc = tdoa_locate_set_clock(ctx, table16.data(), n_stacks, S))) return die("tdoa_locate_set_clock", rc);
                 }
                 if ((rc = tdoa_locate_set_upsample(ctx, locate_up))) return die("tdoa_locate_set_upsample", rc);
                 if (map_stats && (rc = tdoa_locate_set_stats(ctx, stats_ranks.data(), (int)stats_ranks.size(), stats_foot)))
@@ -665,12 +677,30 @@ int main(int argc, char **argv)
                         return die("tdoa_locate_grid_table", rc);
                     if ((rc = tdoa_locate_set_fine_table(ctx, fine.data(), rows_f * zoom_cols, zoom_cols, S))) return die("tdoa_locate_set_fine_table", rc);
                     zooms.resize((size_t)n_stacks);
-                    if ((rc = tdoa_process_locate_zoom(ctx, stack_m, 1, zoom_z, zoom_h, zoom_sep, locs.data(), nullptr, nullptr, nullptr, zooms.data(),
-                                                       nullptr, nullptr, nullptr)))
+                    if (one_call) {
+                        // blocks 1 and 3 their own refined clocks, stack j of block 2 the midpoint of stack j of blocks 1 and 3; the
+                        // rows then go to the clock table for the searches further down, which this call itself never reads
+                        std::vector<tdoa_clock_mix> mix((size_t)n_stacks);
+                        for (int t = 0; t < n_stacks; t++)
+                            mix[t] = t / spb == 1 ? tdoa_clock_mix{t - spb, t + spb, 1, 1} : tdoa_clock_mix{t, t, 1, 0};
+                        std::vector<int32_t> rows16((size_t)n_stacks * S);
+                        syncs.resize((size_t)n_stacks);
+                        clocks.resize((size_t)n_stacks * S);
+                        sfines.resize((size_t)n_stacks);
+                        clocks16.resize((size_t)n_stacks * S);
+                        if ((rc = tdoa_process_sync_locate(ctx, stack_m, sync_g, sync_r, sfine_u, sfine_r, ref16.data(), nullptr, mix.data(), 1, zoom_z,
+                                                           zoom_h, zoom_sep, syncs.data(), clocks.data(), nullptr, nullptr, sfines.data(), clocks16.data(),
+                                                           nullptr, nullptr, rows16.data(), locs.data(), nullptr, nullptr, nullptr, zooms.data(), nullptr,
+                                                           nullptr, nullptr)))
+                            return die("tdoa_process_sync_locate", rc);
+                        if ((rc = last_stats(&lstats, locs.size()))) return die("tdoa_locate_last_stats", rc);
+                        if ((rc = tdoa_locate_set_clock(ctx, rows16.data(), n_stacks, S))) return die("tdoa_locate_set_clock", rc);
+                    } else if ((rc = tdoa_process_locate_zoom(ctx, stack_m, 1, zoom_z, zoom_h, zoom_sep, locs.data(), nullptr, nullptr, nullptr,
+                                                              zooms.data(), nullptr, nullptr, nullptr)))
                         return die("tdoa_process_locate_zoom", rc);
                 } else if ((rc = tdoa_process_locate(ctx, stack_m, 1, locs.data(), nullptr, nullptr, nullptr)))
                     return die("tdoa_process_locate", rc);
-                if ((rc = last_stats(&lstats, locs.size()))) return die("tdoa_locate_last_stats", rc);
+                if (!one_call && (rc = last_stats(&lstats, locs.size()))) return die("tdoa_locate_last_stats", rc);
                 if (emitters) {
                     mlocs.resize((size_t)emitters_k * n_stacks);
                     if ((rc = tdoa_process_locate_multi(ctx, stack_m, emitters_k, emitters_guard, 1, mlocs.data(), nullptr, nullptr, nullptr)))

@@ -83,7 +83,7 @@ LocateRun locate_run(const tdoa_ctx *ctx, const LocateCall &c, int n_sets, int L
 // nullptr, or the message and *status.  The fine lags of a row must fit 32 bits and U times every table and clock entry too
 // (TDOA_ERR_UNSUPPORTED); the upsampled surfaces must not be larger than the device's memory (TDOA_ERR_NOMEM, by arithmetic:
 // nothing is allocated here).
-const char *check_locate_upsample(const tdoa_ctx *ctx, size_t n_sets, int P, int *status)
+const char *check_locate_upsample(const tdoa_ctx *ctx, size_t n_sets, int P, int *status, bool ctx_clocks = true)
 {
     thread_local char buf[320];
     const int U = ctx->locate_up;
@@ -92,7 +92,7 @@ const char *check_locate_upsample(const tdoa_ctx *ctx, size_t n_sets, int P, int
     const long long n_u = upsample_len(2ll * ctx->prm.max_lag - 1, U);
     if (n_u > INT_MAX) return "the upsampled lag range does not fit 32 bits";
     if (ctx->locate_table_max * U >= (1ll << 31)) return "a delay table entry times the upsampling factor does not fit 32 bits";
-    if (ctx->clock_stacks && ctx->locate_clock_max * U >= (1ll << 31)) return "a clock table entry times the upsampling factor does not fit 32 bits";
+    if (ctx_clocks && ctx->clock_stacks && ctx->locate_clock_max * U >= (1ll << 31)) return "a clock table entry times the upsampling factor does not fit 32 bits";
     const double bytes = 8.0 * (double)n_sets * (double)P * (double)n_u;
     const size_t tiles = ((size_t)(2ll * ctx->prm.max_lag - 1) + kUpsampleThreads - 1) / kUpsampleThreads;
     if ((ctx->total_mem && bytes > (double)ctx->total_mem) || (double)n_sets * P * (double)tiles > (double)INT_MAX) {
@@ -134,8 +134,9 @@ const char *check_locate_clock(const tdoa_ctx *ctx, int n_sets, int S)
 
 // what a context's own call and the group's call refuse once the arguments are in range: the lag mode, the captures, the
 // station count, the table, the overflow bound, the clock table's shape; with tracks also a track's sum that could overflow
-// and too many positions.  *what receives the message.
-int check_locate_state(const tdoa_ctx *ctx, int windows_per_stack, bool tracks, const char **what)
+// and too many positions.  *what receives the message.  ctx_clocks: the run adds the context's clock table (LocateClocks);
+// a run under clocks of its own asks nothing of that table.
+int check_locate_state(const tdoa_ctx *ctx, int windows_per_stack, bool tracks, const char **what, bool ctx_clocks = true)
 {
     const auto refuse = [&](int status, const char *why) {
         *what = why;
@@ -154,9 +155,10 @@ int check_locate_state(const tdoa_ctx *ctx, int windows_per_stack, bool tracks, 
         return refuse(TDOA_ERR_UNSUPPORTED, U > 1 ? "4 x pairs x stack length > 2^17 on upsampled surfaces: a cell's score could overflow"
                                                   : "pairs x stack length > 2^17: a cell's score could overflow");
     if (3ll * wpb > kLocateMaxSets) return refuse(TDOA_ERR_UNSUPPORTED, "more than 65535 stacks");
-    if (const char *bad = check_locate_clock(ctx, sg.n_stacks, S)) return refuse(TDOA_ERR_STATE, bad);
+    if (ctx_clocks)
+        if (const char *bad = check_locate_clock(ctx, sg.n_stacks, S)) return refuse(TDOA_ERR_STATE, bad);
     int status = TDOA_OK;
-    if (const char *bad = check_locate_upsample(ctx, (size_t)sg.n_stacks, P, &status)) return refuse(status, bad);
+    if (const char *bad = check_locate_upsample(ctx, (size_t)sg.n_stacks, P, &status, ctx_clocks)) return refuse(status, bad);
     if (!tracks) return TDOA_OK;
     if (locate_overflows(P, wpb, U))
         return refuse(TDOA_ERR_UNSUPPORTED, U > 1 ? "4 x pairs x windows per block > 2^17 on upsampled surfaces: a track's sum could overflow"
@@ -166,13 +168,15 @@ int check_locate_state(const tdoa_ctx *ctx, int windows_per_stack, bool tracks, 
 }
 
 // what the debug entries refuse of the caller's sets: the table, the clock table's shape, the overflow bounds, the track's length
-int check_locate_sets(const tdoa_ctx *ctx, bool tracks, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, const char **what)
+int check_locate_sets(const tdoa_ctx *ctx, bool tracks, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, const char **what,
+                      bool ctx_clocks = true)
 {
     if (!q || n_sets < 1 || n_sets > kLocateMaxSets || n_w < 1 || n_stations < 2 || n_stations > kLocateMaxStations)
         return refuse_with(what, TDOA_ERR_INVALID, "q is NULL, n_sets outside 1 .. 65535, n_w < 1 or n_stations outside 2 .. 64");
     if (tracks && (track_len < 1 || n_sets % track_len != 0)) return refuse_with(what, TDOA_ERR_INVALID, "track_len < 1 or not a divisor of n_sets");
     if (const char *bad = check_locate_table(ctx, n_stations)) return refuse_with(what, TDOA_ERR_STATE, bad);
-    if (const char *bad = check_locate_clock(ctx, n_sets, n_stations)) return refuse_with(what, TDOA_ERR_STATE, bad);
+    if (ctx_clocks)
+        if (const char *bad = check_locate_clock(ctx, n_sets, n_stations)) return refuse_with(what, TDOA_ERR_STATE, bad);
     const int P = n_stations * (n_stations - 1) / 2, U = ctx->locate_up;
     if (!tracks && locate_overflows(P, n_w, U))
         return refuse_with(what, TDOA_ERR_UNSUPPORTED, U > 1 ? "4 x pairs x n_w > 2^17 on upsampled surfaces: a cell's score could overflow"
@@ -181,7 +185,7 @@ int check_locate_sets(const tdoa_ctx *ctx, bool tracks, const int64_t *q, int n_
         return refuse_with(what, TDOA_ERR_UNSUPPORTED, U > 1 ? "4 x pairs x track_len x n_w > 2^17 on upsampled surfaces: a track's sum could overflow"
                                                               : "pairs x track_len x n_w > 2^17: a track's sum could overflow");
     int status = TDOA_OK;
-    if (const char *bad = check_locate_upsample(ctx, (size_t)n_sets, P, &status)) return refuse_with(what, status, bad);
+    if (const char *bad = check_locate_upsample(ctx, (size_t)n_sets, P, &status, ctx_clocks)) return refuse_with(what, status, bad);
     if (tracks && track_len > kCellTrackMaxLen) return refuse_with(what, TDOA_ERR_UNSUPPORTED, "a track of more than 4096 stacks");
     return TDOA_OK;
 }
@@ -302,6 +306,20 @@ int ensure_locate_run(tdoa_ctx *ctx, const LocateRun &run)
 }
 
 // ---- the launches' pieces -----------------------------------------------------------------------------------------------------
+// The clock differences a run adds to its pairs' delays, [set][pair], and U x them for a run on upsampled surfaces; no buffers:
+// no clocks.  The family's one place that picks them: the context's clock table (tdoa_locate_set_clock) for every call but the
+// one that makes its stacks' clocks itself (sync_locate_api.inc).  Buffers, not pointers: a reserve between bind and launch
+// may move them.
+struct LocateClocks {
+    const DevBuf *diff = nullptr, *diff_up = nullptr;
+    bool any() const { return diff != nullptr; }
+    const long long *get(bool up) const { return diff ? (up ? diff_up : diff)->as<const long long>() : nullptr; }
+};
+LocateClocks locate_ctx_clocks(const tdoa_ctx *ctx)
+{
+    return ctx->clock_stacks ? LocateClocks{&ctx->locate_clock, &ctx->locate_clock_up} : LocateClocks{};
+}
+
 // what every launch of a run takes
 struct LocateDev {
     hipStream_t st;
@@ -443,15 +461,15 @@ CellTrackGeom cell_track_geom(const LocateGeom &lg, int L, int J)
 // tracks the recurrence and the tracks' end.  With a clock table (its shape checked by the caller: n_sets stacks of g.S
 // stations) the scores' clock instantiation runs and the finishes add the same differences.  With tracks their roots are in
 // ctx->ctrack_roots (LocateSearch::refresh).  With U > 1 the run starts with the upsampler, and every launch behind it takes
-// its output, the scaled table and the scaled clock differences: Q is [n_sets][P][n_in] then.  Kernel launches only (the step graph captures them).
-void launch_locate_run(tdoa_ctx *ctx, const long long *Q, const double *roots, const LocateRun &run)
+// its output, the scaled table and the scaled clock differences: Q is [n_sets][P][n_in] then.  clocks: the run's clock
+// differences (LocateSearch::bind).  Kernel launches only (the step graph captures them).
+void launch_locate_run(tdoa_ctx *ctx, const long long *Q, const double *roots, const LocateRun &run, const LocateClocks &clocks)
 {
     const LocateGeom &g = run.g;
     const int32_t *table = ctx->locate_table.as<const int32_t>();
-    const long long *cdiff = ctx->clock_stacks ? ctx->locate_clock.as<const long long>() : nullptr;
+    const long long *cdiff = clocks.get(run.U > 1);
     if (run.U > 1) {
         table = ctx->locate_table_up.as<const int32_t>();
-        if (cdiff) cdiff = ctx->locate_clock_up.as<const long long>();
         launch_stack_upsample(ctx->stream, Q, (size_t)run.n_sets * g.P, run.n_in, run.U, ctx->locate_qu.as<long long>());
         Q = ctx->locate_qu.as<const long long>();
     }
@@ -517,7 +535,9 @@ int download_locate_run(tdoa_ctx *ctx, const LocateRun &run, const LocateCall &o
 struct LocateSearch : StackSearch {
     LocateCall call;                         // the entry's arguments and outputs
     LocateRun run{};                         // bind: the call on the shape's sets; a context's own tracks span a block
-    bool clocked = false;                    // ... whether the context holds station clocks (another kernel; the clocks are data)
+    bool own_clocks = false;                 // the run's clocks are its holder's (set before the checks and bind), not the context's table
+    LocateClocks clocks;                     // bind: the context's clock table, if any; with own_clocks its holder's buffers
+    bool clocked = false;                    // ... whether the run has clocks (another kernel; the clocks are data)
     uint64_t stats = 0;                      // ... and the map statistics' word (map_stats_key: more kernels; the ranks are data), 0: off
     std::vector<double> track_roots;         // sqrt(N_w) per track
 
@@ -525,16 +545,17 @@ struct LocateSearch : StackSearch {
     const char *check_args() const override { return check_locate_call(call); }
     int check_state(const tdoa_ctx *ctx, int windows_per_stack, const char **what) const override
     {
-        return check_locate_state(ctx, windows_per_stack, call.tracks, what);
+        return check_locate_state(ctx, windows_per_stack, call.tracks, what, !own_clocks);
     }
     int check_sets(const tdoa_ctx *ctx, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, const char **what) const override
     {
-        return check_locate_sets(ctx, call.tracks, q, n_sets, track_len, n_stations, n_w, what);
+        return check_locate_sets(ctx, call.tracks, q, n_sets, track_len, n_stations, n_w, what, !own_clocks);
     }
     void bind(const tdoa_ctx *ctx, const SearchShape &sh) override
     {
         run = locate_run(ctx, call, sh.n_sets, sh.L);
-        clocked = ctx->clock_stacks != 0;
+        if (!own_clocks) clocks = locate_ctx_clocks(ctx);
+        clocked = clocks.any();
         stats = map_stats_key(ctx);
         track_roots.assign(run.n_tracks(), std::sqrt(sh.track_w));
     }
@@ -554,7 +575,7 @@ struct LocateSearch : StackSearch {
             HIPCHK(ctx, hipMemcpyAsync(ctx->ctrack_roots.p, track_roots.data(), sizeof(double) * track_roots.size(), hipMemcpyHostToDevice, ctx->stream));
         return TDOA_OK;
     }
-    void launch(tdoa_ctx *ctx, const long long *Q, const double *roots) const override { launch_locate_run(ctx, Q, roots, run); }
+    void launch(tdoa_ctx *ctx, const long long *Q, const double *roots) const override { launch_locate_run(ctx, Q, roots, run, clocks); }
     int download(tdoa_ctx *ctx) const override { return download_locate_run(ctx, run, call); }
 };
 

@@ -119,7 +119,7 @@ struct LocateTrackZoomSearch : StackSearch {
         coarse.launch(ctx, Q, roots);
         const bool up = coarse.run.U > 1;
         const int32_t *table = (up ? ctx->locate_fine_up : ctx->locate_fine).as<const int32_t>();
-        const long long *cdiff = !ctx->clock_stacks ? nullptr : (up ? ctx->locate_clock_up : ctx->locate_clock).as<const long long>();
+        const long long *cdiff = coarse.clocks.get(up);
         if (up) Q = ctx->locate_qu.as<const long long>();
         const unsigned n_sets = (unsigned)coarse.run.n_sets, n_tracks = (unsigned)coarse.run.n_tracks();
         const LocateRound p = locate_run_round(ctx, coarse.run, 0);

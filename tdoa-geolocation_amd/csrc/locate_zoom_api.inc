@@ -107,7 +107,7 @@ struct LocateZoomSearch : StackSearch {
         coarse.launch(ctx, Q, roots);
         const bool up = coarse.run.U > 1;
         const int32_t *table = (up ? ctx->locate_fine_up : ctx->locate_fine).as<const int32_t>();
-        const long long *cdiff = !ctx->clock_stacks ? nullptr : (up ? ctx->locate_clock_up : ctx->locate_clock).as<const long long>();
+        const long long *cdiff = coarse.clocks.get(up);
         if (up) Q = ctx->locate_qu.as<const long long>();
         const int32_t *best = ctx->locate_best.as<const int32_t>();
         long long *zmap = ctx->zoom_map.as<long long>();

@@ -51,6 +51,7 @@
 #include "stack_sync_drift_fine.hpp"
 #include "stack_locate_zoom.hpp"
 #include "stack_locate_track_zoom.hpp"
+#include "stack_clock_mix.hpp"
 
 using namespace tdoa;
 
@@ -233,6 +234,10 @@ struct tdoa_ctx {
     // [stack][(2H+1)^2][2], the sums F_0 [track][(2H+1)^2], the records [track], the fine cells and own scores [stack]; the
     // window maps, their tiles' candidates and the fine lags and correlations lie in the zoom locate's buffers
     DevBuf tzoom_centre, tzoom_e, tzoom_total, tzoom_out, tzoom_cells, tzoom_own;
+    // clocks to fix in one call (tdoa_process_sync_locate), between the fine clock search and the zoom locate: the mix [stack],
+    // the stacks' clock rows [stack][station] and their pairs' differences and U x them [stack][pair], which the zoom locate of
+    // that call takes where the others take locate_clock and locate_clock_up; tdoa_debug_clock_mix's clocks [stack][station]
+    DevBuf mix_in, mix_rows, mix_cdiff, mix_cdiff_up, mix_debug;
     size_t total_mem = 0;                  // of the device, 0: unknown
 };
 
@@ -602,7 +607,8 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->slfine_cur, &ctx->slfine_kappa, &ctx->slfine_eta, &ctx->slfine_part, &ctx->slfine_moved, &ctx->slfine_start,
                       &ctx->slfine_out, &ctx->slfine_clock, &ctx->slfine_rate, &ctx->slfine_rows, &ctx->slfine_lags, &ctx->slfine_corr,
                       &ctx->locate_fine, &ctx->locate_fine_up, &ctx->zoom_map, &ctx->zoom_part, &ctx->zoom_out, &ctx->zoom_lags, &ctx->zoom_corr,
-                      &ctx->tzoom_centre, &ctx->tzoom_e, &ctx->tzoom_total, &ctx->tzoom_out, &ctx->tzoom_cells, &ctx->tzoom_own};
+                      &ctx->tzoom_centre, &ctx->tzoom_e, &ctx->tzoom_total, &ctx->tzoom_out, &ctx->tzoom_cells, &ctx->tzoom_own,
+                      &ctx->mix_in, &ctx->mix_rows, &ctx->mix_cdiff, &ctx->mix_cdiff_up, &ctx->mix_debug};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1345,3 +1351,4 @@ int tdoa_solve_surface(const double *stations_lle, int n_stations, const double 
 #include "sync_fine_api.inc"
 #include "sync_drift_api.inc"
 #include "sync_drift_fine_api.inc"
+#include "sync_locate_api.inc"

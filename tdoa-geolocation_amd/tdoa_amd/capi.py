@@ -136,6 +136,8 @@ SYMBOLS = [
     "tdoa_process_sync_drift_fine", "tdoa_group_process_sync_drift_fine", "tdoa_debug_sync_drift_fine_from_q",
     "tdoa_sync_line_clock16",
     "tdoa_process_locate_track_zoom", "tdoa_group_process_locate_track_zoom", "tdoa_debug_locate_track_zoom_from_q",
+    "tdoa_process_sync_locate", "tdoa_group_process_sync_locate", "tdoa_debug_sync_locate_from_q", "tdoa_clock_mix_rows",
+    "tdoa_debug_clock_mix",
 ]
 
 
@@ -155,8 +157,9 @@ def _Out(key, dtype, shape, want=None, poison=False):
 
 
 class _Search:
-    def __init__(self, name, ints, outputs, inputs=(), track_len=False, stats=None, bare=False):
+    def __init__(self, name, ints, outputs, inputs=(), track_len=False, stats=None, bare=False, late_ints=()):
         self.name, self.ints, self.outputs, self.inputs = name, ints, outputs, inputs
+        self.late_ints = late_ints           # ints the header states behind the inputs
         self.entries = {"own": "tdoa_process_" + name, "group": "tdoa_group_process_" + name,
                         "q": "tdoa_debug_%s_from_q" % name}
         self.track_len = track_len           # the from-Q entry takes track_len
@@ -217,6 +220,12 @@ _TRACK_ZOOM_OUT = (_Out("ztrack", CELL_TRACK_DTYPE, ("n_tracks",), poison=True),
 TRACK_ZOOM_SEARCHES = {s.name: s for s in (
     _Search("locate_track_zoom", ("max_step", "min_separation", "Z", "H", "fine_step", "fine_separation"),
             _TRACK_OUT + _TRACK_ZOOM_OUT, track_len=True, stats="track"),
+    # clocks to fix in one call: the fine clock search's arguments, the mix, the zoom locate's ints, the sixteen outputs of the two
+    # with the rows between them (the locate's lags and corr under loc_ names: the clock search's have theirs)
+    _Search("sync_locate", SEARCHES["sync_fine"].ints,
+            SEARCHES["sync_fine"].outputs + (_Out("rows", np.int32, ("n_sets", "S")),) +
+            tuple(o._replace(key="loc_" + o.key) if o.key in ("lags", "corr") else o for o in SEARCHES["locate_zoom"].outputs),
+            _CLOCKS + ("mix",), stats="loc", late_ints=SEARCHES["locate_zoom"].ints),
 )}
 
 
@@ -232,7 +241,8 @@ def _search_argtypes(s, route):
     """the argtypes of search s's entry `route`"""
     i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
     shape = [i64p] + [C.c_int] * (3 + s.track_len) if route == "q" else [C.c_int]
-    return [C.c_void_p] + shape + [C.c_int] * len(s.ints) + [i32p] * len(s.inputs) + [o.ctype for o in s.outputs]
+    return ([C.c_void_p] + shape + [C.c_int] * len(s.ints) + [i32p] * len(s.inputs) + [C.c_int] * len(s.late_ints) +
+            [o.ctype for o in s.outputs])
 
 
 _lib = None
@@ -362,6 +372,8 @@ def load(build_if_missing=True):
     L.tdoa_group_locate_set_upsample.argtypes = [vp, C.c_int]
     L.tdoa_locate_upsample_taps.argtypes = [C.c_int, i32p]
     L.tdoa_debug_upsample_q.argtypes = [vp, i64p, C.c_int, C.c_int, i64p]
+    L.tdoa_clock_mix_rows.argtypes = [i32p, C.c_int, C.c_int, i32p, C.c_int, i32p]
+    L.tdoa_debug_clock_mix.argtypes = [vp, i32p, C.c_int, C.c_int, i32p, C.c_int, C.c_int, i32p, i64p, i64p]
     L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
                                         C.POINTER(C.c_int)]
     for s in list(SEARCHES.values()) + list(LATER_SEARCHES.values()) + list(TRACK_ZOOM_SEARCHES.values()):
@@ -448,6 +460,41 @@ class _LaterContextSearches:
             fine_separation=fine_separation, want_total=want_total, want_zmap=want_zmap, want_ztotal=want_ztotal))
 
 
+    def process_sync_locate(self, ref_delay, Z, H, windows_per_stack=0, gate=0, rounds=0, U=16, fine_rounds=2, centre=None, mix=None,
+                            min_separation=1, fine_separation=1, want_map=False, want_zmap=True):
+        """tdoa_process_sync_locate -> process_sync_fine's eight outputs (that call's bytes), "rows": [n_stacks][S] int32 (1/16
+        sample), and process_locate_zoom's eight as after locate_set_clock(rows), the locate's lags and corr under "loc_lags"
+        and "loc_corr": the fine clock search, a clock row per stack mixed on the device from its clock16 by mix [n_stacks][4]
+        (a, b, wa, wb; None: every stack its own clock; clock_mix.midpoint_mix for [reference | target | reference]), and the
+        zoom locate under those rows, in one step.  The context's clock table is neither read nor changed"""
+        return _process_search(self, self, "sync_locate", dict(
+            windows_per_stack=windows_per_stack, gate=gate, rounds=rounds, U=U, fine_rounds=fine_rounds, ref_delay=ref_delay,
+            centre=centre, mix=mix, min_separation=min_separation, Z=Z, H=H, fine_separation=fine_separation, want_map=want_map,
+            want_zmap=want_zmap))
+
+    def sync_locate_from_q(self, q, ref_delay, Z, H, n_w=1, gate=0, rounds=0, U=16, fine_rounds=2, centre=None, mix=None,
+                           min_separation=1, fine_separation=1, want_map=True, want_zmap=True):
+        """tdoa_debug_sync_locate_from_q: the same kernels on the caller's words q [n_sets][P][2 max_lag - 1] int64 with the
+        context's table, fine table and settings -> what process_sync_locate returns, n_sets for n_stacks; mix names sets"""
+        return self._from_q("sync_locate", q, np.size(ref_delay), dict(
+            n_w=n_w, gate=gate, rounds=rounds, U=U, fine_rounds=fine_rounds, ref_delay=ref_delay, centre=centre, mix=mix,
+            min_separation=min_separation, Z=Z, H=H, fine_separation=fine_separation, want_map=want_map, want_zmap=want_zmap))
+
+    def debug_clock_mix(self, clock16, mix, U_loc=1):
+        """tdoa_debug_clock_mix: the mix kernel alone on clock16 [n][S] int32 and mix [m][4] -> (rows [m][S] int32, cdiff [m][P]
+        int64 = row[j] - row[i] in locate_set_clock's pair order, cdiff_up = U_loc x cdiff), written over poisoned arrays"""
+        c = np.ascontiguousarray(clock16, dtype=np.int32)
+        if c.ndim != 2:
+            raise ValueError("clock16 must be [n][S]")
+        m, (n, S) = np.shape(mix)[0], c.shape
+        rows, cdiff, up = (_poisoned((m, S), np.int32), _poisoned((m, S * (S - 1) // 2), np.int64),
+                           _poisoned((m, S * (S - 1) // 2), np.int64))
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        self._chk(self._L.tdoa_debug_clock_mix(self._h, c.ctypes.data_as(i32p), n, S, _mix(mix), m, int(U_loc), rows.ctypes.data_as(i32p),
+                                               cdiff.ctypes.data_as(i64p), up.ctypes.data_as(i64p)))
+        return rows, cdiff, up
+
+
 class _LaterGroupSearches:
     def process_sync_drift_fine(self, ref_delay, windows_per_stack=0, gate=0, max_drift=0, drift_den=1, rounds=0, U=16, fine_rounds=2,
                                 centre=None):
@@ -462,6 +509,15 @@ class _LaterGroupSearches:
         return _process_search(self, self.member(0), "locate_track_zoom", dict(
             windows_per_stack=windows_per_stack, max_step=max_step, min_separation=min_separation, Z=Z, H=H, fine_step=fine_step,
             fine_separation=fine_separation, want_total=want_total, want_zmap=want_zmap, want_ztotal=want_ztotal))
+
+
+    def process_sync_locate(self, ref_delay, Z, H, windows_per_stack=0, gate=0, rounds=0, U=16, fine_rounds=2, centre=None, mix=None,
+                            min_separation=1, fine_separation=1, want_map=False, want_zmap=True):
+        """tdoa_group_process_sync_locate -> Context.process_sync_locate's outputs, byte-identical to a single context's"""
+        return _process_search(self, self.member(0), "sync_locate", dict(
+            windows_per_stack=windows_per_stack, gate=gate, rounds=rounds, U=U, fine_rounds=fine_rounds, ref_delay=ref_delay,
+            centre=centre, mix=mix, min_separation=min_separation, Z=Z, H=H, fine_separation=fine_separation, want_map=want_map,
+            want_zmap=want_zmap))
 
 
 class Context(_LaterContextSearches):
@@ -1182,7 +1238,20 @@ def _search_ptrs(s, out):
     return [out[o.key].ctypes.data_as(o.ctype) if o.key in out else None for o in s.outputs]
 
 
-_INPUT = {"ref_delay": _ref_delay, "centre": _centre}
+def _mix(mix, n_stations=None):
+    """a clock mix as the C ABI takes it: None, or [m][4] int32 (a, b, wa, wb; tdoa_clock_mix's layout)"""
+    if mix is None:
+        return None
+    m = np.asarray(mix)
+    if m.dtype.names:
+        m = np.stack([m[k] for k in ("a", "b", "wa", "wb")], axis=-1)
+    m = np.ascontiguousarray(m, dtype=np.int32)
+    if m.ndim != 2 or m.shape[1] != 4:
+        raise ValueError("mix must be [m][4]: a, b, wa, wb")
+    return m.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+_INPUT = {"ref_delay": _ref_delay, "centre": _centre, "mix": _mix}
 
 
 def _run_search(s, route, fn, handle, chk, n, values, q=None):
@@ -1195,8 +1264,10 @@ def _run_search(s, route, fn, handle, chk, n, values, q=None):
                  [n["S"], int(values["n_w"])])
     else:
         shape = [int(values["windows_per_stack"])]
+    if values.get("mix") is not None and np.shape(values["mix"])[0] != n["n_sets"]:
+        raise ValueError("mix must hold one entry per stack")
     chk(fn(handle, *shape, *[int(values[k]) for k in s.ints], *[_INPUT[k](values[k], n["S"]) for k in s.inputs],
-           *_search_ptrs(s, out)))
+           *[int(values[k]) for k in s.late_ints], *_search_ptrs(s, out)))
     return out[s.outputs[0].key] if s.bare else out
 
 
@@ -1424,6 +1495,21 @@ class Group(_LaterGroupSearches):
         return _process_search(self, self.member(0), "sync_drift", dict(
             windows_per_stack=windows_per_stack, gate=gate, max_drift=max_drift, drift_den=drift_den, rounds=rounds,
             ref_delay=ref_delay, centre=centre), n_tracks=3)
+
+
+def clock_mix_rows(clock16, mix):
+    """tdoa_clock_mix_rows (host only): clock16 [n][S] int32 and mix [m][4] (a, b, wa, wb) -> rows [m][S] int32, the nearest
+    integer to (wa clock16[a] + wb clock16[b]) / (wa + wb), halves away from zero: tdoa_process_sync_locate's clock rows"""
+    c = np.ascontiguousarray(clock16, dtype=np.int32)
+    if c.ndim != 2:
+        raise ValueError("clock16 must be [n][S]")
+    m = np.shape(mix)[0]
+    rows = _poisoned((m, c.shape[1]), np.int32)
+    i32p = C.POINTER(C.c_int32)
+    rc = load().tdoa_clock_mix_rows(c.ctypes.data_as(i32p), c.shape[0], c.shape[1], _mix(mix), m, rows.ctypes.data_as(i32p))
+    if rc != 0:
+        raise TdoaError(rc, "tdoa_clock_mix_rows")
+    return rows
 
 
 def sync_line_clock16(clock16, fine_rate, U, drift_den, first_position, n_positions):
