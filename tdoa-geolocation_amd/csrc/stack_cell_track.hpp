@@ -191,7 +191,7 @@ __global__ __launch_bounds__(kCellTrackThreads) void k_cell_track_finish(const l
     const int track = blockIdx.x, t = threadIdx.x;
     long long bs;
     uint32_t bk;
-    locate_best_candidate(partial + (size_t)track * lg.tiles, lg.tiles, red_s, red_k, bs, bk);
+    search_best_candidate(partial + (size_t)track * lg.tiles, lg.tiles, red_s, red_k, bs, bk);
     const double root = track_roots[track];
     const int cell = (int)~bk;
     if (pass == 1) {

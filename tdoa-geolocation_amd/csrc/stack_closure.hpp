@@ -10,7 +10,9 @@
 //                    after the second search: runner_q and runner_up
 //
 // Everything is integer arithmetic on the Q words of stack_surfaces.hpp; the only floating point is stack_value on the way
-// out.
+// out.  The candidate (ClosureCand), its order and the workgroup reductions (closure_block_best, search_best_candidate,
+// search_block_sum, search_wave_sum / _min / _max) serve the delay-table and the clock searches too: every search header
+// includes this one.
 #pragma once
 
 #include "stack_surfaces.hpp"
@@ -116,6 +118,69 @@ __device__ __forceinline__ void closure_block_best(long long &s, uint32_t &k, lo
     __syncthreads();
 }
 
+// The workgroup reductions of every stack search (closure, delay table, clocks), stated here once.  Each is for the
+// kClosureThreads threads the searches' kernels all have; a header whose kernels use another constant asserts that it is equal.
+
+// The start of a finishing kernel: the tiles' candidates of the workgroup's set, line or track, cand[tiles], -> the best of them
+// in every thread (equal scores: the larger key).  Ends with closure_block_best's barrier.
+__device__ __forceinline__ void search_best_candidate(const ClosureCand *cand, int tiles, long long *red_s, uint32_t *red_k, long long &bs,
+                                                      uint32_t &bk)
+{
+    bs = kClosureAbsent;
+    bk = 0;
+    for (int y = threadIdx.x; y < tiles; y += kClosureThreads) {
+        const ClosureCand c = cand[y];
+        if (closure_better(c.score, c.key, bs, bk)) {
+            bs = c.score;
+            bk = c.key;
+        }
+    }
+    closure_block_best(bs, bk, red_s, red_k);
+}
+
+// a wave's sum, smallest and largest word, in every lane
+__device__ __forceinline__ int search_wave_sum(int v)
+{
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+    return v;
+}
+__device__ __forceinline__ int search_wave_min(int v)
+{
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, kWave));
+    return v;
+}
+__device__ __forceinline__ int search_wave_max(int v)
+{
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, kWave));
+    return v;
+}
+
+// the workgroup's sums of f and n in every thread; red_s / red_n: one word per wave of LDS, free again on return
+__device__ __forceinline__ void search_block_sum(long long &f, int &n, long long *red_s, int *red_n)
+{
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+        f += __shfl_xor(f, off, kWave);
+        n += __shfl_xor(n, off, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        red_s[threadIdx.x / kWave] = f;
+        red_n[threadIdx.x / kWave] = n;
+    }
+    __syncthreads();
+    f = 0;
+    n = 0;
+#pragma unroll
+    for (int w = 0; w < kClosureThreads / kWave; w++) {
+        f += red_s[w];
+        n += red_n[w];
+    }
+    __syncthreads();
+}
+
 // LDS words of k_closure_search: the rows M_ik and M_jk over the whole gate, M_ij over the tile, the reduction's words
 __host__ __device__ constexpr size_t closure_lds_bytes(int G)
 {
@@ -192,16 +257,9 @@ __global__ __launch_bounds__(kClosureThreads) void k_closure_finish(const long l
     __shared__ long long red_s[kClosureThreads / kWave];
     __shared__ uint32_t red_k[kClosureThreads / kWave];
     const int st = blockIdx.x, set = st / g.T, t = threadIdx.x;
-    long long bs = kClosureAbsent;
-    uint32_t bk = 0;
-    for (int y = t; y < g.tiles; y += kClosureThreads) {
-        const ClosureCand c = partial[(size_t)st * g.tiles + y];
-        if (closure_better(c.score, c.key, bs, bk)) {
-            bs = c.score;
-            bk = c.key;
-        }
-    }
-    closure_block_best(bs, bk, red_s, red_k);
+    long long bs;
+    uint32_t bk;
+    search_best_candidate(partial + (size_t)st * g.tiles, g.tiles, red_s, red_k, bs, bk);
     const double root = roots[set];
     if (pass == 1) {
         if (t == 0 && out[st].score_q != 0) {

@@ -166,31 +166,6 @@ __device__ __forceinline__ bool locate_pair_value(const long long *q, const Loca
     return true;
 }
 
-// The start of every finishing kernel of the family: the tiles' candidates of the workgroup's set or track, cand[tiles], -> the
-// best of them in every thread (equal scores: the smaller cell).  kLocateThreads threads; ends with closure_block_best's barrier.
-__device__ __forceinline__ void locate_best_candidate(const ClosureCand *cand, int tiles, long long *red_s, uint32_t *red_k, long long &bs,
-                                                      uint32_t &bk)
-{
-    bs = kClosureAbsent;
-    bk = 0;
-    for (int y = threadIdx.x; y < tiles; y += kLocateThreads) {
-        const ClosureCand c = cand[y];
-        if (closure_better(c.score, c.key, bs, bk)) {
-            bs = c.score;
-            bk = c.key;
-        }
-    }
-    closure_block_best(bs, bk, red_s, red_k);
-}
-
-// the sum of a wave's counts, in every lane
-__device__ __forceinline__ int locate_wave_sum(int v)
-{
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
-
 // One workgroup per set.
 // pass 0: the tiles' candidates -> the location into best and the record (cell, pairs_in, score_q, score; the runner-up's
 // fields 0), and per pair lag_p(cell*) and the signed C there (0 and 0.0 for a pair outside the range).  A largest score of 0:
@@ -210,7 +185,7 @@ __global__ __launch_bounds__(kLocateThreads) void k_locate_finish(const long lon
     const int set = blockIdx.x, t = threadIdx.x;
     long long bs;
     uint32_t bk;
-    locate_best_candidate(partial + (size_t)set * g.tiles, g.tiles, red_s, red_k, bs, bk);
+    search_best_candidate(partial + (size_t)set * g.tiles, g.tiles, red_s, red_k, bs, bk);
     const double root = roots[set];
     const int cell = (int)~bk;
     if (pass == 1) {
@@ -231,7 +206,7 @@ __global__ __launch_bounds__(kLocateThreads) void k_locate_finish(const long lon
         lags[(size_t)set * g.P + p] = lag;
         corr[(size_t)set * g.P + p] = c;
     }
-    inside = locate_wave_sum(inside);
+    inside = search_wave_sum(inside);
     if ((t & (kWave - 1)) == 0) red_n[t / kWave] = inside;
     __syncthreads();
     if (t != 0) return;

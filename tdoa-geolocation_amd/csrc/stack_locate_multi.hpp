@@ -152,7 +152,7 @@ __global__ __launch_bounds__(kLocateThreads) void k_locate_finish_masked(const l
     const int set = blockIdx.x, t = threadIdx.x;
     long long bs;
     uint32_t bk;
-    locate_best_candidate(partial + (size_t)set * g.tiles, g.tiles, red_s, red_k, bs, bk);
+    search_best_candidate(partial + (size_t)set * g.tiles, g.tiles, red_s, red_k, bs, bk);
     const double root = roots[set];
     const int cell = (int)~bk;
     const bool found = bs > 0 && cell >= 0 && cell < g.n_cells;
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(kLocateThreads) void k_locate_finish_masked(const l
         corr[(size_t)set * g.P + p] = c;
         cen[p].c[mk.round] = centre;
     }
-    counts = locate_wave_sum(counts);
+    counts = search_wave_sum(counts);
     if ((t & (kWave - 1)) == 0) red_n[t / kWave] = counts;
     __syncthreads();
     if (t != 0) return;

@@ -41,7 +41,7 @@ __global__ __launch_bounds__(kLocateThreads) void k_track_centres(LocateGeom g, 
         for (int r = 1; r < kLocateMaxEmitters; r++) cc.c[r] = kLocateNoCentre;
         centres[(size_t)set * g.P + p] = cc;
     }
-    inside = locate_wave_sum(inside);
+    inside = search_wave_sum(inside);
     if ((t & (kWave - 1)) == 0) red_n[t / kWave] = inside;
     __syncthreads();
     if (t != 0) return;
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(kCellTrackThreads) void k_cell_track_finish_masked(
     const int track = blockIdx.x, t = threadIdx.x;
     long long bs;
     uint32_t bk;
-    locate_best_candidate(partial + (size_t)track * lg.tiles, lg.tiles, red_s, red_k, bs, bk);
+    search_best_candidate(partial + (size_t)track * lg.tiles, lg.tiles, red_s, red_k, bs, bk);
     const int cell = (int)~bk;
     const bool found = bs > 0 && cell >= 0 && cell < g.n_cells;
     const size_t set0 = (size_t)track * g.L;
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(kCellTrackThreads) void k_cell_track_finish_masked(
             corr[set * lg.P + p] = c;
             cen[p].c[mk.round] = centre;
         }
-        counts = locate_wave_sum(counts);
+        counts = search_wave_sum(counts);
         if (lane == 0) {
             pairs[2 * set] = counts & 0xffff;
             pairs[2 * set + 1] = counts >> 16;

@@ -109,20 +109,6 @@ __global__ __launch_bounds__(kLocateThreads) void k_locate_zoom_scores(const lon
     if (t == 0) partial[(size_t)set * z.tiles + blockIdx.x] = ClosureCand{bs, bk, 0};
 }
 
-// a wave's smallest and largest word, in every lane
-__device__ __forceinline__ int locate_wave_min(int v)
-{
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, kWave));
-    return v;
-}
-__device__ __forceinline__ int locate_wave_max(int v)
-{
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, kWave));
-    return v;
-}
-
 // One workgroup per set, kLocateThreads threads.  The tiles' candidates -> the zoom's cell (the largest score, equal scores: the
 // smaller fine cell).  A largest score of 0, no competing position or no location: the zero record, zero lags and correlations.
 // Otherwise one pass over the set's window on zmap: n_best and the box of the positions with exactly score_q, and the runner-up,
@@ -142,7 +128,7 @@ __global__ __launch_bounds__(kLocateThreads) void k_locate_zoom_finish(const lon
     const int set = blockIdx.x, t = threadIdx.x, b = locate_zoom_centre(z, best[set]);
     long long bs;
     uint32_t bk;
-    locate_best_candidate(partial + (size_t)set * z.tiles, z.tiles, red_s, red_k, bs, bk);
+    search_best_candidate(partial + (size_t)set * z.tiles, z.tiles, red_s, red_k, bs, bk);
     const double root = roots[set];
     const int cell = (int)~bk;
     const bool found = b >= 0 && bs > 0 && cell >= 0 && cell < gf.n_cells;      // (uniform over the workgroup)
@@ -182,12 +168,12 @@ __global__ __launch_bounds__(kLocateThreads) void k_locate_zoom_finish(const lon
         lags[(size_t)set * gf.P + p] = lag;
         corr[(size_t)set * gf.P + p] = c;
     }
-    n_best = locate_wave_sum(n_best);
-    inside = locate_wave_sum(inside);
-    row_lo = locate_wave_min(row_lo);
-    row_hi = locate_wave_max(row_hi);
-    col_lo = locate_wave_min(col_lo);
-    col_hi = locate_wave_max(col_hi);
+    n_best = search_wave_sum(n_best);
+    inside = search_wave_sum(inside);
+    row_lo = search_wave_min(row_lo);
+    row_hi = search_wave_max(row_hi);
+    col_lo = search_wave_min(col_lo);
+    col_hi = search_wave_max(col_hi);
     if ((t & (kWave - 1)) == 0) {
         const int w = t / kWave;
         red_n[w] = n_best;

@@ -13,8 +13,10 @@
 //                station, one gather per partner -- then F, the record, the clocks and the pairs' lags and correlations
 //
 // Everything is integer arithmetic on the Q words of stack_surfaces.hpp; the only floating point is stack_value on the way
-// out.  The candidate, its order and the workgroup reduction are the closure search's (stack_closure.hpp), the rule of e_ij
-// the delay-table search's (stack_locate.hpp).
+// out.  The candidate, its order and the workgroup reductions (a workgroup's best, the best of the tiles' candidates, the sum
+// of F with its count) are the ones all stack searches share (stack_closure.hpp); the rule of e_ij and the pair order are the
+// delay-table search's (stack_locate.hpp).  The clock family shares what is stated here: the lag grid (SyncGrid; the 1/U form is
+// SyncFineGrid in stack_sync_fine.hpp), the pair objective over it (sync_objective) and the per-set outputs (sync_finish_set).
 #pragma once
 
 #include "stack_locate.hpp"
@@ -49,6 +51,76 @@ __device__ __forceinline__ long long sync_m(const long long *q, long long lag, c
     if (idx < 0 || idx >= g.n) return 0;
     const long long v = q[idx];
     return v < 0 ? -v : v;
+}
+
+// A lag grid is what the clock family's kernels are written over: the lag of a pair from ref_delay, the word of a row at a lag
+// (false outside the searched range) and the factors that turn the grid's unit into 1/16 sample (unit16) and into the unit the
+// clocks go out in (clock_unit).  This is the whole-lag grid; SyncFineGrid (stack_sync_fine.hpp) is the 1/U one.
+struct SyncGrid {
+    int32_t n, lag_lo;         // lags per row of Q, the first one
+    __device__ __forceinline__ long long lag(int32_t ti, int32_t tj) const { return locate_lag(ti, tj); }
+    __device__ __forceinline__ bool word(const long long *row, long long lag, long long *v) const
+    {
+        const long long idx = lag - lag_lo;
+        if (idx < 0 || idx >= n) return false;
+        *v = row[idx];
+        return true;
+    }
+    __device__ __forceinline__ int unit16() const { return kLocateDelayUnit; }
+    __device__ __forceinline__ int clock_unit() const { return 1; }      // tdoa_sync's clocks are whole lags
+    __device__ __forceinline__ void stage() const {}                     // nothing to keep in LDS
+};
+
+// F at the clocks k [S] (in LDS, in the grid's unit) and the pairs inside the range, the same in every thread; with `write` the
+// pairs' lags and correlations.  q: the set's rows [P][n]; lags and corr: the set's [P].  kSyncThreads threads; ends with a barrier.
+template <class Grid>
+__device__ __forceinline__ long long sync_objective(const Grid &gr, const long long *q, int S, int P, const int32_t *ref, const long long *k,
+                                                    double root, bool write, int32_t *lags, double *corr, long long *red_s, int *red_n,
+                                                    int *pairs_in)
+{
+    long long f = 0;
+    int inside = 0;
+    for (int p = threadIdx.x; p < P; p += kSyncThreads) {
+        int i, j;
+        locate_pair(p, S, &i, &j);
+        const long long l = gr.lag(ref[i], ref[j]) + k[j] - k[i];
+        long long v;
+        int32_t lag = 0;
+        double c = 0.0;
+        if (gr.word(q + (size_t)p * gr.n, l, &v)) {
+            f += v < 0 ? -v : v;
+            inside++;
+            lag = (int32_t)l;
+            c = stack_value(v, root);
+        }
+        if (write) {
+            lags[p] = lag;
+            corr[p] = c;
+        }
+    }
+    search_block_sum(f, inside, red_s, red_n);
+    *pairs_in = inside;
+    return f;
+}
+
+// The end of a per-set kernel, behind sync_objective with `write`: the set's clocks k [S] in the grid's clock unit and its record.
+// rec.score_q == 0 (nothing found): all zero, every thread taking back the pairs it wrote (sync_objective's stride).
+template <class Grid>
+__device__ __forceinline__ void sync_finish_set(const Grid &gr, int S, int P, const long long *k, const SyncOut &rec, int32_t *lags,
+                                                double *corr, int32_t *clock, SyncOut *out)
+{
+    const int t = threadIdx.x;
+    if (rec.score_q == 0) {
+        for (int p = t; p < P; p += kSyncThreads) {
+            lags[p] = 0;
+            corr[p] = 0.0;
+        }
+        if (t < S) clock[t] = 0;
+        if (t == 0) *out = SyncOut{0, 0, 0, 0, 0.0};
+        return;
+    }
+    if (t < S) clock[t] = (int32_t)(k[t] * gr.clock_unit());
+    if (t == 0) *out = rec;
 }
 
 // grid (tiles, n_sets), kSyncThreads threads; S >= 3.  Q: [set][pair][n]; in: ref_delay [kSyncMaxStations], then centre
@@ -124,62 +196,19 @@ __global__ __launch_bounds__(kSyncThreads) void k_sync_steps(const long long *Q,
 
     // F(k) and the pairs inside the range, the same in every thread; with `write` the pairs' lags and correlations
     const double root = roots[set];
+    const SyncGrid gr{g.n, g.lag_lo};
+    int32_t *set_lags = lags + (size_t)set * g.P;
+    double *set_corr = corr + (size_t)set * g.P;
     const auto objective = [&](bool write, int *pairs_in) -> long long {
-        long long f = 0;
-        int inside = 0;
-        for (int p = t; p < g.P; p += kSyncThreads) {
-            int i, j;
-            locate_pair(p, g.S, &i, &j);
-            const long long l = locate_lag(ref[i], ref[j]) + k[j] - k[i], idx = l - g.lag_lo;
-            int32_t lag = 0;
-            double c = 0.0;
-            if (idx >= 0 && idx < g.n) {
-                const long long v = q[(size_t)p * g.n + idx];
-                f += v < 0 ? -v : v;
-                inside++;
-                lag = (int32_t)l;
-                c = stack_value(v, root);
-            }
-            if (write) {
-                lags[(size_t)set * g.P + p] = lag;
-                corr[(size_t)set * g.P + p] = c;
-            }
-        }
-#pragma unroll
-        for (int off = kWave / 2; off > 0; off >>= 1) {
-            f += __shfl_xor(f, off, kWave);
-            inside += __shfl_xor(inside, off, kWave);
-        }
-        if ((t & (kWave - 1)) == 0) {
-            red_s[t / kWave] = f;
-            red_n[t / kWave] = inside;
-        }
-        __syncthreads();
-        f = 0;
-        inside = 0;
-#pragma unroll
-        for (int w = 0; w < kSyncThreads / kWave; w++) {
-            f += red_s[w];
-            inside += red_n[w];
-        }
-        __syncthreads();
-        *pairs_in = inside;
-        return f;
+        return sync_objective(gr, q, g.S, g.P, ref, k, root, write, set_lags, set_corr, red_s, red_n, pairs_in);
     };
 
     if (g.S == 2) {
         step(1, 1);
     } else {
-        long long bs = kClosureAbsent;
-        uint32_t bk = 0;
-        for (int y = t; y < g.tiles; y += kSyncThreads) {
-            const ClosureCand c = partial[(size_t)set * g.tiles + y];
-            if (closure_better(c.score, c.key, bs, bk)) {
-                bs = c.score;
-                bk = c.key;
-            }
-        }
-        closure_block_best(bs, bk, red_s, red_k);
+        long long bs;
+        uint32_t bk;
+        search_best_candidate(partial + (size_t)set * g.tiles, g.tiles, red_s, red_k, bs, bk);
         const uint32_t cell = ~bk;                               // < W^2: every tile holds a cell
         if (t == 0) {
             k[1] = (long long)centre[1] + closure_unrank(cell / (uint32_t)g.W);
@@ -198,17 +227,8 @@ __global__ __launch_bounds__(kSyncThreads) void k_sync_steps(const long long *Q,
         }
     }
     const long long score_q = objective(true, &inside);
-    if (score_q == 0) {                                          // nothing found: every thread takes back the pairs it wrote
-        for (int p = t; p < g.P; p += kSyncThreads) {
-            lags[(size_t)set * g.P + p] = 0;
-            corr[(size_t)set * g.P + p] = 0.0;
-        }
-        if (t < g.S) clock[(size_t)set * g.S + t] = 0;
-        if (t == 0) out[set] = SyncOut{0, 0, 0, 0, 0.0};
-        return;
-    }
-    if (t < g.S) clock[(size_t)set * g.S + t] = (int32_t)k[t];
-    if (t == 0) out[set] = SyncOut{moved, inside, score_q, start_q, stack_value(score_q, root)};
+    sync_finish_set(gr, g.S, g.P, k, SyncOut{moved, inside, score_q, start_q, stack_value(score_q, root)}, set_lags, set_corr,
+                    clock + (size_t)set * g.S, out + set);
 }
 
 }  // namespace tdoa

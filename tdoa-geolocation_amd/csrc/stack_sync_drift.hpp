@@ -15,11 +15,13 @@
 //                    division in the loops.  The tile's best goes out as a two-word candidate, key = ~r
 // k_syncline_commit  one workgroup per line: the tiles' candidates -> the station's (k, h), its row of cur, and `moved`
 // k_syncline_finish  F and terms_in; pass 0 keeps F as start_q, pass 1 writes the record, the clocks, the rates, the rows,
-//                    the lags and the correlations, all zero where F = 0
+//                    the lags and the correlations, all zero where F = 0.  A template over the lag grid: on SyncFineGrid it is
+//                    the fine clock lines' finish as well
 //
 // Everything is integer arithmetic on the Q words of stack_surfaces.hpp; the only floating point is stack_value on the way
-// out.  The candidate, its order and the workgroup reduction are the closure search's (stack_closure.hpp), the rule of e_ij
-// the delay-table search's (stack_locate.hpp), shift the slope search's (stack_drift.hpp).
+// out.  The candidate, its order and the workgroup reductions are the ones all stack searches share (stack_closure.hpp), the
+// lag grid the clock search's (SyncGrid, stack_sync.hpp), the pair order the delay-table search's (stack_locate.hpp), shift
+// the slope search's (stack_drift.hpp).  syncline_best, the start of a commit kernel, serves the fine clock lines too.
 #pragma once
 
 #include "stack_sync.hpp"
@@ -56,13 +58,17 @@ struct SyncLineDev {
     long long *start_q;        // [line]
 };
 
-// the word of a (position, pair) row at a lag, 0 outside the searched range; *inside counts the words read
-__device__ __forceinline__ long long syncline_word(const long long *q, long long lag, const SyncLineGeom &g, int *inside)
+// The start of a commit kernel: the tiles' candidates of a line's step, part[tiles], -> the winner r = rank(slope) W + rank(offset)
+// as its two ranks, in every thread.  Every tile holds a candidate, so r < cands.
+__device__ __forceinline__ void syncline_best(const ClosureCand *part, int tiles, int cands, int W, long long *red_s, uint32_t *red_k,
+                                              uint32_t *rank_h, uint32_t *rank_x)
 {
-    const long long idx = lag - g.lag_lo;
-    if (idx < 0 || idx >= g.n) return 0;
-    ++*inside;
-    return q[idx];
+    long long bs;
+    uint32_t bk;
+    search_best_candidate(part, tiles, red_s, red_k, bs, bk);
+    const uint32_t r = min(~bk, (uint32_t)(cands - 1));
+    *rank_h = r / (uint32_t)W;
+    *rank_x = r - *rank_h * (uint32_t)W;
 }
 
 // One workgroup per line.
@@ -130,19 +136,9 @@ __global__ __launch_bounds__(kSyncLineThreads) void k_syncline_commit(SyncLineGe
     __shared__ long long red_s[kSyncLineThreads / kWave];
     __shared__ uint32_t red_k[kSyncLineThreads / kWave];
     const int line = blockIdx.x, t = threadIdx.x;
-    long long bs = kClosureAbsent;
-    uint32_t bk = 0;
-    for (int y = t; y < g.tiles; y += kSyncLineThreads) {
-        const ClosureCand c = d.part[(size_t)line * g.tiles + y];
-        if (closure_better(c.score, c.key, bs, bk)) {
-            bs = c.score;
-            bk = c.key;
-        }
-    }
-    closure_block_best(bs, bk, red_s, red_k);
-    const uint32_t r = min(~bk, (uint32_t)(g.cands - 1));           // < cands: every tile holds a candidate
-    const uint32_t rh = r / (uint32_t)g.W;
-    const long long ks = (long long)d.in[kSyncMaxStations + s] + closure_unrank(r - rh * (uint32_t)g.W);
+    uint32_t rh, rx;
+    syncline_best(d.part + (size_t)line * g.tiles, g.tiles, g.cands, g.W, red_s, red_k, &rh, &rx);
+    const long long ks = (long long)d.in[kSyncMaxStations + s] + closure_unrank(rx);
     const int32_t hs = closure_unrank(rh);
     for (int j = t; j < g.L; j += kSyncLineThreads) d.cur[((size_t)line * g.S + s) * g.L + j] = ks + d.tab[(size_t)rh * g.L + j];
     if (t == 0) {
@@ -154,10 +150,16 @@ __global__ __launch_bounds__(kSyncLineThreads) void k_syncline_commit(SyncLineGe
     }
 }
 
-// One workgroup per line.  roots [set]: sqrt(n_w) of a position's stack; line_roots [line]: sqrt(N_w).  rec [line]; clock and
-// rate [line][S]; rows [set][S]: 16 k_s(j); lags and corr [set][P]: the lag along the line and the signed C of that stack
-// there, 0 and 0.0 outside the range.
-__global__ __launch_bounds__(kSyncLineThreads) void k_syncline_finish(const long long *Q, SyncLineGeom g, SyncLineDev d, int pass,
+// One workgroup per line, for the clock lines (SyncGrid) and the fine clock lines (SyncFineGrid, stack_sync_drift_fine.hpp): g
+// and d are the search's own geometry (S, P, L) and buffers (in, cur, moved, start_q); k and h [line][S]: the stations' offsets
+// and slopes in the grid's unit; coarse [line]: the records a refinement stands on, nullptr: none.  roots [set]: sqrt(n_w) of a
+// position's stack; line_roots [line]: sqrt(N_w).
+// pass 0: F into start_q.  pass 1: rec [line]; clock [line][S] in the grid's clock unit and rate [line][S]; rows [set][S]: the
+// clock table in 1/16 sample; lags (in the grid's unit) and corr [set][P]: the lag along the line and the signed value of that
+// stack's word there, 0 and 0.0 outside the range.  F = 0 or a zero coarse record: all zero.
+template <class Grid, class Geom, class Dev, class Rate>
+__global__ __launch_bounds__(kSyncLineThreads) void k_syncline_finish(const long long *Q, Grid gr, Geom g, Dev d, const long long *k,
+                                                                      const Rate *h, const SyncLineOut *coarse, int pass,
                                                                       const double *roots, const double *line_roots, SyncLineOut *rec,
                                                                       int32_t *clock, int32_t *rate, int32_t *rows, int32_t *lags,
                                                                       double *corr)
@@ -165,55 +167,46 @@ __global__ __launch_bounds__(kSyncLineThreads) void k_syncline_finish(const long
     __shared__ long long red_s[kSyncLineThreads / kWave];
     __shared__ int red_n[kSyncLineThreads / kWave];
     const int line = blockIdx.x, t = threadIdx.x;
-    const long long *q_line = Q + (size_t)line * g.L * g.P * g.n;
+    const long long *q_line = Q + (size_t)line * g.L * g.P * gr.n;
     const long long *cur_line = d.cur + (size_t)line * g.S * g.L;
-    const size_t pos_stride = (size_t)g.P * g.n;
+    const size_t pos_stride = (size_t)g.P * gr.n;
+    gr.stage();
     long long f = 0;
     int inside = 0;
     for (int p = t; p < g.P; p += kSyncLineThreads) {
         int i, j;
         locate_pair(p, g.S, &i, &j);
-        const long long e = locate_lag(d.in[i], d.in[j]);
-        const long long *q = q_line + (size_t)p * g.n, *ki = cur_line + (size_t)i * g.L, *kj = cur_line + (size_t)j * g.L;
+        const long long e = gr.lag(d.in[i], d.in[j]);
+        const long long *q = q_line + (size_t)p * gr.n, *ki = cur_line + (size_t)i * g.L, *kj = cur_line + (size_t)j * g.L;
         long long acc = 0;
-        for (int x = 0; x < g.L; x++, q += pos_stride) acc += syncline_word(q, e + kj[x] - ki[x], g, &inside);
+        for (int x = 0; x < g.L; x++, q += pos_stride) {
+            long long v;
+            if (!gr.word(q, e + kj[x] - ki[x], &v)) continue;
+            acc += v;
+            inside++;
+        }
         f += acc < 0 ? -acc : acc;
     }
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-        f += __shfl_xor(f, off, kWave);
-        inside += __shfl_xor(inside, off, kWave);
-    }
-    if ((t & (kWave - 1)) == 0) {
-        red_s[t / kWave] = f;
-        red_n[t / kWave] = inside;
-    }
-    __syncthreads();
-    f = 0;
-    inside = 0;
-#pragma unroll
-    for (int w = 0; w < kSyncLineThreads / kWave; w++) {
-        f += red_s[w];
-        inside += red_n[w];
-    }
+    search_block_sum(f, inside, red_s, red_n);
     if (pass == 0) {
         if (t == 0) d.start_q[line] = f;
         return;
     }
-    const bool found = f != 0;
+    const bool found = f != 0 && (!coarse || coarse[line].score_q != 0);
     const size_t set0 = (size_t)line * g.L;
     for (int p = t; p < g.P; p += kSyncLineThreads) {
         int i, j;
         locate_pair(p, g.S, &i, &j);
-        const long long e = locate_lag(d.in[i], d.in[j]);
-        const long long *q = q_line + (size_t)p * g.n, *ki = cur_line + (size_t)i * g.L, *kj = cur_line + (size_t)j * g.L;
+        const long long e = gr.lag(d.in[i], d.in[j]);
+        const long long *q = q_line + (size_t)p * gr.n, *ki = cur_line + (size_t)i * g.L, *kj = cur_line + (size_t)j * g.L;
         for (int x = 0; x < g.L; x++, q += pos_stride) {
-            const long long l = e + kj[x] - ki[x], idx = l - g.lag_lo;
+            const long long l = e + kj[x] - ki[x];
+            long long v;
             int32_t lag = 0;
             double c = 0.0;
-            if (found && idx >= 0 && idx < g.n) {
+            if (found && gr.word(q, l, &v)) {
                 lag = (int32_t)l;
-                c = stack_value(q[idx], roots[set0 + x]);
+                c = stack_value(v, roots[set0 + x]);
             }
             lags[(set0 + x) * g.P + p] = lag;
             corr[(set0 + x) * g.P + p] = c;
@@ -221,11 +214,11 @@ __global__ __launch_bounds__(kSyncLineThreads) void k_syncline_finish(const long
     }
     for (int e = t; e < g.S * g.L; e += kSyncLineThreads) {
         const int s = e / g.L, x = e - s * g.L;
-        rows[(set0 + x) * g.S + s] = found ? (int32_t)(kLocateDelayUnit * cur_line[e]) : 0;
+        rows[(set0 + x) * g.S + s] = found ? (int32_t)(cur_line[e] * gr.unit16()) : 0;
     }
     if (t < g.S) {
-        clock[(size_t)line * g.S + t] = found ? (int32_t)d.k[(size_t)line * g.S + t] : 0;
-        rate[(size_t)line * g.S + t] = found ? d.h[(size_t)line * g.S + t] : 0;
+        clock[(size_t)line * g.S + t] = found ? (int32_t)(k[(size_t)line * g.S + t] * gr.clock_unit()) : 0;
+        rate[(size_t)line * g.S + t] = found ? (int32_t)h[(size_t)line * g.S + t] : 0;
     }
     if (t == 0)
         rec[line] = found ? SyncLineOut{d.moved[line], inside, g.L, 0, f, d.start_q[line], stack_value(f, line_roots[line])}

@@ -17,11 +17,13 @@
 //                        so the order of work cannot change a byte.  The partners' kappa_i(x) come from cur and are the same for
 //                        the whole workgroup.  The tile's best goes out as a two-word candidate, key = ~r
 // k_synclinefine_commit  one workgroup per line: the tiles' candidates -> the station's (kappa, eta), its row of cur, `moved`
-// k_synclinefine_finish  F_U and terms_in; pass 0 keeps F_U as start_q, pass 1 writes the record, clock16, the fine rates, rows,
-//                        lags and correlations, all zero where the coarse record is zero or F_U = 0
+// k_syncline_finish      (stack_sync_drift.hpp) on SyncFineGrid with kappa, eta and the coarse records: F_U and terms_in; pass 0
+//                        keeps F_U as start_q, pass 1 writes the record, clock16, the fine rates, rows, lags and correlations,
+//                        all zero where the coarse record is zero or F_U = 0
 //
-// Integer work only; stack_value on the way out.  The word, its split and e^U are stack_sync_fine.hpp's, the candidate, its
-// order and the workgroup reduction the closure search's, the pair order the delay-table search's.
+// Integer work only; stack_value on the way out.  The word, its split, e^U and the 1/U grid are stack_sync_fine.hpp's, the
+// commit's start (syncline_best) the clock lines', the candidate, its order and the workgroup reductions the ones all stack
+// searches share (stack_closure.hpp).
 #pragma once
 
 #include "stack_sync_drift.hpp"
@@ -149,20 +151,10 @@ __global__ __launch_bounds__(kSyncLineFineThreads) void k_synclinefine_commit(Sy
     __shared__ long long red_s[kSyncLineFineThreads / kWave];
     __shared__ uint32_t red_k[kSyncLineFineThreads / kWave];
     const int line = blockIdx.x, t = threadIdx.x;
-    long long bs = kClosureAbsent;
-    uint32_t bk = 0;
-    for (int y = t; y < g.tiles; y += kSyncLineFineThreads) {
-        const ClosureCand c = d.part[(size_t)line * g.tiles + y];
-        if (closure_better(c.score, c.key, bs, bk)) {
-            bs = c.score;
-            bk = c.key;
-        }
-    }
-    closure_block_best(bs, bk, red_s, red_k);
-    const uint32_t r = min(~bk, (uint32_t)(g.cands - 1));           // < cands: every tile holds a candidate
-    const uint32_t rg = r / (uint32_t)g.W;
+    uint32_t rg, ry;
+    syncline_best(d.part + (size_t)line * g.tiles, g.tiles, g.cands, g.W, red_s, red_k, &rg, &ry);
     const size_t at = (size_t)line * g.S + s;
-    const long long kap = d.k[at] * g.U + closure_unrank(r - rg * (uint32_t)g.W);
+    const long long kap = d.k[at] * g.U + closure_unrank(ry);
     const long long eta = (long long)d.h[at] * g.U + closure_unrank(rg);
     for (int x = t; x < g.L; x += kSyncLineFineThreads) d.cur[at * g.L + x] = kap + synclinefine_shift(eta, x, g.D);
     if (t == 0) {
@@ -171,94 +163,6 @@ __global__ __launch_bounds__(kSyncLineFineThreads) void k_synclinefine_commit(Sy
         d.eta[at] = eta;
         d.moved[line] = (first ? 0 : d.moved[line]) + changed;
     }
-}
-
-// One workgroup per line.  roots [set]: sqrt(n_w) of a position's stack; line_roots [line]: sqrt(N_w).  rec [line]; clock16 and
-// rate [line][S]; rows [set][S]: kappa_s(x) 16 / U; lags [set][P] in 1/U sample and corr [set][P]: the fine lag along the line and
-// the signed value of that stack's word there, 0 and 0.0 outside the range.
-__global__ __launch_bounds__(kSyncLineFineThreads) void k_synclinefine_finish(const long long *Q, SyncLineFineGeom g, SyncLineFineDev d, int pass,
-                                                                              const double *roots, const double *line_roots, SyncLineOut *rec,
-                                                                              int32_t *clock16, int32_t *rate, int32_t *rows, int32_t *lags,
-                                                                              double *corr)
-{
-    __shared__ long long red_s[kSyncLineFineThreads / kWave];
-    __shared__ int red_n[kSyncLineFineThreads / kWave];
-    __shared__ int32_t taps_s[kUpsamplePhases * kUpsampleTapCount];
-    const int line = blockIdx.x, t = threadIdx.x;
-    const long long *q_line = Q + (size_t)line * g.L * g.P * g.n;
-    const long long *cur_line = d.cur + (size_t)line * g.S * g.L;
-    const size_t pos_stride = (size_t)g.P * g.n;
-    const long long half = (long long)(g.n - 1) / 2 * g.U, top = (long long)(g.n - 1) * g.U;
-    taps_s[t] = kUpsampleTaps[t / kUpsampleTapCount][t % kUpsampleTapCount];
-    __syncthreads();
-    long long f = 0;
-    int inside = 0;
-    for (int p = t; p < g.P; p += kSyncLineFineThreads) {
-        int i, j;
-        locate_pair(p, g.S, &i, &j);
-        const long long e = sync_fine_lag(d.in[i], d.in[j], g.U);
-        const long long *q = q_line + (size_t)p * g.n, *ki = cur_line + (size_t)i * g.L, *kj = cur_line + (size_t)j * g.L;
-        long long acc = 0;
-        for (int x = 0; x < g.L; x++, q += pos_stride) {
-            const long long u = e + kj[x] - ki[x] + half;
-            if (u < 0 || u > top) continue;
-            acc += sync_fine_word(q, g.n, u, g.log_u, taps_s);
-            inside++;
-        }
-        f += acc < 0 ? -acc : acc;
-    }
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-        f += __shfl_xor(f, off, kWave);
-        inside += __shfl_xor(inside, off, kWave);
-    }
-    if ((t & (kWave - 1)) == 0) {
-        red_s[t / kWave] = f;
-        red_n[t / kWave] = inside;
-    }
-    __syncthreads();
-    f = 0;
-    inside = 0;
-#pragma unroll
-    for (int w = 0; w < kSyncLineFineThreads / kWave; w++) {
-        f += red_s[w];
-        inside += red_n[w];
-    }
-    if (pass == 0) {
-        if (t == 0) d.start_q[line] = f;
-        return;
-    }
-    const bool found = d.coarse[line].score_q != 0 && f != 0;
-    const size_t set0 = (size_t)line * g.L;
-    const int unit = kLocateDelayUnit / g.U;
-    for (int p = t; p < g.P; p += kSyncLineFineThreads) {
-        int i, j;
-        locate_pair(p, g.S, &i, &j);
-        const long long e = sync_fine_lag(d.in[i], d.in[j], g.U);
-        const long long *q = q_line + (size_t)p * g.n, *ki = cur_line + (size_t)i * g.L, *kj = cur_line + (size_t)j * g.L;
-        for (int x = 0; x < g.L; x++, q += pos_stride) {
-            const long long lam = e + kj[x] - ki[x], u = lam + half;
-            int32_t lag = 0;
-            double c = 0.0;
-            if (found && u >= 0 && u <= top) {
-                lag = (int32_t)lam;
-                c = stack_value(sync_fine_word(q, g.n, u, g.log_u, taps_s), roots[set0 + x]);
-            }
-            lags[(set0 + x) * g.P + p] = lag;
-            corr[(set0 + x) * g.P + p] = c;
-        }
-    }
-    for (int e = t; e < g.S * g.L; e += kSyncLineFineThreads) {
-        const int s = e / g.L, x = e - s * g.L;
-        rows[(set0 + x) * g.S + s] = found ? (int32_t)(cur_line[e] * unit) : 0;
-    }
-    if (t < g.S) {
-        clock16[(size_t)line * g.S + t] = found ? (int32_t)(d.kappa[(size_t)line * g.S + t] * unit) : 0;
-        rate[(size_t)line * g.S + t] = found ? (int32_t)d.eta[(size_t)line * g.S + t] : 0;
-    }
-    if (t == 0)
-        rec[line] = found ? SyncLineOut{d.moved[line], inside, g.L, 0, f, d.start_q[line], stack_value(f, line_roots[line])}
-                          : SyncLineOut{0, 0, 0, 0, 0, 0, 0.0};
 }
 
 }  // namespace tdoa

@@ -5,7 +5,7 @@
 // in Rf Gauss-Seidel sweeps over stations 1 .. S-1 against all the others.  Q_U is tdoa_locate_set_upsample's (stack_upsample.hpp)
 // and is never materialised: a sweep's step reads (2U + 1)(S - 1) of its words, the objective P, and each is evaluated from
 // the 16 words of Q under its taps.  e^U_ij = sgn(d) ((2 |d| U + 16) div 32) is the upsampled locate's lag rule; candidates
-// compete in the closure search's order rank(y), the first of equal maxima wins; a lag outside the range counts 0.
+// compete in the order rank(y) (closure_rank, stack_closure.hpp), the first of equal maxima wins; a lag outside the range counts 0.
 //
 // k_sync_refine  one workgroup per set, behind k_sync_steps on the same stream.  The taps go to LDS once (the phase differs per
 //                lane).  A step's 2U + 1 candidates of one partner are consecutive fine lags, inside three input lags: the
@@ -13,7 +13,8 @@
 //                every (partner, candidate) gets a lane -- (2U + 1)(S - 1) items, up to 33 x 63, strided over the 256 threads
 //                -- which reads its 16-word window and its phase's taps from LDS and adds the word's magnitude to the
 //                candidate's word in LDS as an integer, so the order cannot change a byte.  Lanes 0 .. 2U then compete on
-//                key = ~rank(y).  The objective strides the pairs, one word gathered from Q per pair.
+//                key = ~rank(y).  The objective and the outputs are the clock search's (sync_objective, sync_finish_set) on the
+//                1/U grid SyncFineGrid: the pairs strided, one word formed from Q per pair.
 //
 // The arithmetic is k_stack_upsample's: Q = hi 2^31 + lo, A = sum h hi and B = sum h lo + 2^14 as 32 x 32 -> 64 multiply-adds,
 // the word A 2^16 + (B >> 15); phase 0 is the delta and gives Q back.  It is stated here once more (upsample_word) so that
@@ -71,6 +72,33 @@ __device__ __forceinline__ long long sync_fine_lag(int32_t ti, int32_t tj, int U
     const long long a = (2 * (d < 0 ? -d : d) * U + kLocateDelayUnit) / (2 * kLocateDelayUnit);
     return d < 0 ? -a : a;
 }
+
+// The 1/U lag grid (SyncGrid, stack_sync.hpp, is the whole-lag one): lags in 1/U sample, a row's word formed from the 16 words
+// of Q under its taps, clocks out in 1/16 sample (clock16).  taps: the kUpsamplePhases phases' taps in LDS -- a kernel that reads
+// them elsewhere too stages them itself and builds the grid on them, any other calls stage().
+struct SyncFineGrid {
+    int32_t n, U, log_u;       // lags per row of Q, the factor, log2 U
+    const int32_t *taps;
+    __device__ __forceinline__ long long lag(int32_t ti, int32_t tj) const { return sync_fine_lag(ti, tj, U); }
+    __device__ __forceinline__ bool word(const long long *row, long long lam, long long *v) const
+    {
+        const long long u = lam + (long long)(n - 1) / 2 * U;        // lam = u - half, 0 <= u <= top
+        if (u < 0 || u > (long long)(n - 1) * U) return false;
+        *v = sync_fine_word(row, n, u, log_u, taps);
+        return true;
+    }
+    __device__ __forceinline__ int unit16() const { return kLocateDelayUnit / U; }
+    __device__ __forceinline__ int clock_unit() const { return kLocateDelayUnit / U; }
+    // kSyncThreads threads, one tap each; ends with the barrier that makes them readable
+    __device__ __forceinline__ void stage()
+    {
+        __shared__ int32_t taps_s[kUpsamplePhases * kUpsampleTapCount];
+        taps_s[threadIdx.x] = kUpsampleTaps[threadIdx.x / kUpsampleTapCount][threadIdx.x % kUpsampleTapCount];
+        __syncthreads();
+        taps = taps_s;
+    }
+};
+static_assert(kSyncThreads == kUpsamplePhases * kUpsampleTapCount, "one thread stages one tap");
 
 // One workgroup per set, kSyncThreads threads, after k_sync_steps.  coarse [set] and k [set][S]: that kernel's records and
 // clocks.  out [set]; clock16 [set][S]: kappa_s 16 / U; lags [set][P] in 1/U sample and corr [set][P]: e^U_ij + kappa_j - kappa_i
@@ -145,47 +173,11 @@ __global__ __launch_bounds__(kSyncThreads) void k_sync_refine(const long long *Q
 
     // F_U(kappa) and the pairs inside the range, the same in every thread; with `write` the pairs' lags and correlations
     const double root = roots[set];
+    const SyncFineGrid gr{g.n, U, log_u, taps_s};
+    int32_t *set_lags = lags + (size_t)set * g.P;
+    double *set_corr = corr + (size_t)set * g.P;
     const auto objective = [&](bool write, int *pairs_in) -> long long {
-        long long f = 0;
-        int inside = 0;
-        for (int p = t; p < g.P; p += kSyncThreads) {
-            int i, j;
-            locate_pair(p, g.S, &i, &j);
-            const long long lam = sync_fine_lag(ref[i], ref[j], U) + kap[j] - kap[i], u = lam + half;
-            int32_t lag = 0;
-            double c = 0.0;
-            if (u >= 0 && u <= top) {
-                const long long v = sync_fine_word(q + (size_t)p * g.n, g.n, u, log_u, taps_s);
-                f += v < 0 ? -v : v;
-                inside++;
-                lag = (int32_t)lam;
-                c = stack_value(v, root);
-            }
-            if (write) {
-                lags[(size_t)set * g.P + p] = lag;
-                corr[(size_t)set * g.P + p] = c;
-            }
-        }
-#pragma unroll
-        for (int off = kWave / 2; off > 0; off >>= 1) {
-            f += __shfl_xor(f, off, kWave);
-            inside += __shfl_xor(inside, off, kWave);
-        }
-        if ((t & (kWave - 1)) == 0) {
-            red_s[t / kWave] = f;
-            red_n[t / kWave] = inside;
-        }
-        __syncthreads();
-        f = 0;
-        inside = 0;
-#pragma unroll
-        for (int w = 0; w < kSyncThreads / kWave; w++) {
-            f += red_s[w];
-            inside += red_n[w];
-        }
-        __syncthreads();
-        *pairs_in = inside;
-        return f;
+        return sync_objective(gr, q, g.S, g.P, ref, kap, root, write, set_lags, set_corr, red_s, red_n, pairs_in);
     };
 
     int inside = 0, moved = 0;
@@ -201,17 +193,8 @@ __global__ __launch_bounds__(kSyncThreads) void k_sync_refine(const long long *Q
         }
         score_q = objective(true, &inside);
     }
-    if (score_q == 0) {                                          // nothing found: every thread writes the pairs it would have
-        for (int p = t; p < g.P; p += kSyncThreads) {
-            lags[(size_t)set * g.P + p] = 0;
-            corr[(size_t)set * g.P + p] = 0.0;
-        }
-        if (t < g.S) clock16[(size_t)set * g.S + t] = 0;
-        if (t == 0) out[set] = SyncOut{0, 0, 0, 0, 0.0};
-        return;
-    }
-    if (t < g.S) clock16[(size_t)set * g.S + t] = (int32_t)(kap[t] * (kLocateDelayUnit / U));
-    if (t == 0) out[set] = SyncOut{moved, inside, score_q, start_q, stack_value(score_q, root)};
+    sync_finish_set(gr, g.S, g.P, kap, SyncOut{moved, inside, score_q, start_q, stack_value(score_q, root)}, set_lags, set_corr,
+                    clock16 + (size_t)set * g.S, out + set);
 }
 
 }  // namespace tdoa

@@ -149,7 +149,8 @@ struct SyncLineSearch : StackSearch {
             hipLaunchKernelGGL(k_syncline_commit, lines, threads, 0, st, g, d, s, first, count);
         };
         const auto finish = [&](int pass) {
-            hipLaunchKernelGGL(k_syncline_finish, lines, threads, 0, st, Q, g, d, pass, roots, ctx->sline_roots.as<const double>(),
+            hipLaunchKernelGGL(k_syncline_finish, lines, threads, 0, st, Q, SyncGrid{g.n, g.lag_lo}, g, d, d.k, d.h, nullptr, pass, roots,
+                               ctx->sline_roots.as<const double>(),
                                ctx->sline_out.as<SyncLineOut>(), ctx->sline_clock.as<int32_t>(), ctx->sline_rate.as<int32_t>(),
                                ctx->sline_rows.as<int32_t>(), ctx->sline_lags.as<int32_t>(), ctx->sline_corr.as<double>());
         };

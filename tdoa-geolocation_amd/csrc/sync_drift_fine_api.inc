@@ -115,7 +115,8 @@ struct SyncLineFineSearch : StackSearch {
                                 ctx->slfine_start.as<long long>()};
         const dim3 lines((unsigned)coarse.n_lines), threads(kSyncLineFineThreads);
         const auto finish = [&](int pass) {
-            hipLaunchKernelGGL(k_synclinefine_finish, lines, threads, 0, st, Q, fg, d, pass, roots, ctx->sline_roots.as<const double>(),
+            hipLaunchKernelGGL(k_syncline_finish, lines, threads, 0, st, Q, SyncFineGrid{fg.n, fg.U, fg.log_u, nullptr}, fg, d,
+                               d.kappa, d.eta, d.coarse, pass, roots, ctx->sline_roots.as<const double>(),
                                ctx->slfine_out.as<SyncLineOut>(), ctx->slfine_clock.as<int32_t>(), ctx->slfine_rate.as<int32_t>(),
                                ctx->slfine_rows.as<int32_t>(), ctx->slfine_lags.as<int32_t>(), ctx->slfine_corr.as<double>());
         };
