@@ -1182,3 +1182,113 @@ func (g *Group) ProcessLocateTrackZoom(windowsPerStack, maxStep, minSeparation, 
 	}
 	return o, nil
 }
+
+// LineMix is one entry of a line mix (the header's tdoa_line_mix): the row of a stack is the nearest integer to
+// (Wa cont(A, Xa) + Wb cont(B, Xb)) / (Wa + Wb), halves away from zero, cont(l, x) being fine line l continued to position x by
+// SyncLineClock16's rule, x of either sign.  {l, x, l, x, 1, 0} is line l continued to x.
+type LineMix struct {
+	A, Xa, B, Xb, Wa, Wb int32
+}
+
+func lineMixPtr(mix []LineMix) *C.tdoa_line_mix {
+	if len(mix) == 0 {
+		return nil
+	}
+	return (*C.tdoa_line_mix)(unsafe.Pointer(&mix[0]))
+}
+
+// ForwardMix is the mix for [reference | target | reference] blocks of stacksPerBlock stacks: blocks 1 and 3 keep their own
+// lines at their own positions, stack j of block 2 gets block 1's line continued to stacksPerBlock + j.
+func ForwardMix(stacksPerBlock int) []LineMix {
+	l := int32(stacksPerBlock)
+	mix := make([]LineMix, 3*stacksPerBlock)
+	for t := int32(0); t < 3*l; t++ {
+		mix[t] = LineMix{t / l, t % l, t / l, t % l, 1, 0}
+		if t >= l && t < 2*l {
+			mix[t] = LineMix{0, t, 0, t, 1, 0}
+		}
+	}
+	return mix
+}
+
+// LineMixRows is the line mix in plain C (host only): clock16 and fineRate [line][station] (1/16 sample; 1/(u driftDen) lag per
+// position) and one entry per row -> [row][station], what LocateSetClock takes and what ProcessSyncDriftLocate tracks under.
+func LineMixRows(clock16, fineRate []int32, stations, u, driftDen int, mix []LineMix) ([]int32, error) {
+	if stations < 1 || len(clock16) == 0 || len(clock16)%stations != 0 || len(fineRate) != len(clock16) || len(mix) == 0 {
+		return nil, fmt.Errorf("tdoa_line_mix_rows: clock16 and fineRate must be [line][station] and the mix not empty")
+	}
+	out := make([]int32, len(mix)*stations)
+	if rc := C.tdoa_line_mix_rows(i32Ptr(clock16), i32Ptr(fineRate), C.int(len(clock16)/stations), C.int(stations), C.int(u), C.int(driftDen),
+		lineMixPtr(mix), C.int(len(mix)), i32Ptr(out)); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_line_mix_rows: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	return out, nil
+}
+
+// SyncDriftLocate is what ProcessSyncDriftLocate returns: ProcessSyncDriftFine's outputs, the stacks' clock rows [stack][station]
+// in units of 1/16 sample, and ProcessLocateTrackZoom's outputs under those rows.
+type SyncDriftLocate struct {
+	SyncLinesFine
+	MixRows []int32
+	LocateTrackZoom
+}
+
+func newSyncDriftLocate(total, perBlock, stations, pairs int) *SyncDriftLocate {
+	return &SyncDriftLocate{SyncLinesFine: *newSyncLinesFine(total, stations, pairs), MixRows: make([]int32, total*stations),
+		LocateTrackZoom: *newLocateTrackZoom(total, perBlock, pairs)}
+}
+
+// ProcessSyncDriftLocate is the header's "free-running clocks to fix in one call": the fine clock lines, a clock row per stack made
+// on the device from their clocks and rates (mix: one entry per stack, nil: every stack its own line at its own position;
+// ForwardMix for the usual captures) and the zoomed cell tracks under those rows, in one step.  The clock table of LocateSetClock
+// is neither read nor changed.
+func (g *gpuCorrelator) ProcessSyncDriftLocate(windowsPerStack, gate, maxDrift, driftDen, rounds, u, fineRounds int, refDelay, centre []int32,
+	mix []LineMix, maxStep, minSeparation, z, h, fineStep, fineSeparation int) (*SyncDriftLocate, error) {
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs, stations := int(C.tdoa_num_pairs(g.ctx)), len(refDelay)
+	if int(total)*pairs == 0 || stations*(stations-1)/2 != pairs || (mix != nil && len(mix) != int(total)) {
+		return nil, fmt.Errorf("tdoa_process_sync_drift_locate: no stacks, fewer than two stations, not one delay per station or not one mix entry per stack")
+	}
+	o := newSyncDriftLocate(int(total), int(perBlock), stations, pairs)
+	f, l := &o.SyncLinesFine, &o.LocateTrackZoom
+	if rc := C.tdoa_process_sync_drift_locate(g.ctx, C.int(windowsPerStack), C.int(gate), C.int(maxDrift), C.int(driftDen), C.int(rounds),
+		C.int(u), C.int(fineRounds), tablePtr(refDelay), centrePtr(centre), lineMixPtr(mix), C.int(maxStep), C.int(minSeparation), C.int(z),
+		C.int(h), C.int(fineStep), C.int(fineSeparation), &f.Line[0], i32Ptr(f.Clock), i32Ptr(f.Rate), i32Ptr(f.Rows), i32Ptr(f.Lags),
+		(*C.double)(unsafe.Pointer(&f.Corr[0])), &f.Fine[0], i32Ptr(f.Clock16), i32Ptr(f.FineRate), i32Ptr(f.FineRows), i32Ptr(f.FineLags),
+		(*C.double)(unsafe.Pointer(&f.FineCorr[0])), i32Ptr(o.MixRows), &l.Track[0], i32Ptr(l.Cells), (*C.int64_t)(unsafe.Pointer(&l.Own[0])),
+		i32Ptr(l.Lags), (*C.double)(unsafe.Pointer(&l.Corr[0])), nil, &l.ZTrack[0], i32Ptr(l.ZCells), (*C.int64_t)(unsafe.Pointer(&l.ZOwn[0])),
+		i32Ptr(l.ZLags), (*C.double)(unsafe.Pointer(&l.ZCorr[0])), nil, nil); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_process_sync_drift_locate: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return o, nil
+}
+
+// ProcessSyncDriftLocate is gpuCorrelator.ProcessSyncDriftLocate over the group: the members' fixed-point partial sums are added
+// on the host and searched on member 0 with its table, fine table and settings, the same bytes one context returns.
+func (g *Group) ProcessSyncDriftLocate(windowsPerStack, gate, maxDrift, driftDen, rounds, u, fineRounds int, refDelay, centre []int32,
+	mix []LineMix, maxStep, minSeparation, z, h, fineStep, fineSeparation int) (*SyncDriftLocate, error) {
+	m := C.tdoa_group_member(g.g, 0)
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(m, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs, stations := int(C.tdoa_num_pairs(m)), len(refDelay)
+	if int(total)*pairs == 0 || stations*(stations-1)/2 != pairs || (mix != nil && len(mix) != int(total)) {
+		return nil, fmt.Errorf("tdoa_group_process_sync_drift_locate: no stacks, fewer than two stations, not one delay per station or not one mix entry per stack")
+	}
+	o := newSyncDriftLocate(int(total), int(perBlock), stations, pairs)
+	f, l := &o.SyncLinesFine, &o.LocateTrackZoom
+	if rc := C.tdoa_group_process_sync_drift_locate(g.g, C.int(windowsPerStack), C.int(gate), C.int(maxDrift), C.int(driftDen), C.int(rounds),
+		C.int(u), C.int(fineRounds), tablePtr(refDelay), centrePtr(centre), lineMixPtr(mix), C.int(maxStep), C.int(minSeparation), C.int(z),
+		C.int(h), C.int(fineStep), C.int(fineSeparation), &f.Line[0], i32Ptr(f.Clock), i32Ptr(f.Rate), i32Ptr(f.Rows), i32Ptr(f.Lags),
+		(*C.double)(unsafe.Pointer(&f.Corr[0])), &f.Fine[0], i32Ptr(f.Clock16), i32Ptr(f.FineRate), i32Ptr(f.FineRows), i32Ptr(f.FineLags),
+		(*C.double)(unsafe.Pointer(&f.FineCorr[0])), i32Ptr(o.MixRows), &l.Track[0], i32Ptr(l.Cells), (*C.int64_t)(unsafe.Pointer(&l.Own[0])),
+		i32Ptr(l.Lags), (*C.double)(unsafe.Pointer(&l.Corr[0])), nil, &l.ZTrack[0], i32Ptr(l.ZCells), (*C.int64_t)(unsafe.Pointer(&l.ZOwn[0])),
+		i32Ptr(l.ZLags), (*C.double)(unsafe.Pointer(&l.ZCorr[0])), nil, nil); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_group_process_sync_drift_locate: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return o, nil
+}

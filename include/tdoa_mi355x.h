@@ -1191,8 +1191,8 @@ int tdoa_debug_locate_track_zoom_from_q(tdoa_ctx *ctx, const int64_t *q, int n_s
  * table or fine table of the same shape replay the captured graph.  The graph's key is both searches' words, the locate's
  * clock flag on.
  * Scope: the chain for free-running receivers (tdoa_process_sync_drift_fine, the line continued, tdoa_process_locate_track_zoom)
- * needs tdoa_sync_line_clock16's rule on the device, not a mix, and is not this call; nor are the rounds of
- * tdoa_process_locate_multi.  fine_rounds = 0 gives clock16 = 16 clock, the coarse clock search alone; Z = 1, H = 0 with the
+ * needs tdoa_sync_line_clock16's rule on the device, not a mix, and is not this call but tdoa_process_sync_drift_locate, below;
+ * the rounds of tdoa_process_locate_multi are in neither.  fine_rounds = 0 gives clock16 = 16 clock, the coarse clock search alone; Z = 1, H = 0 with the
  * fine table set to the table is the form without a zoom.
  * The refusals are those of the two calls, and: TDOA_ERR_INVALID: a mix entry with a or b outside 0 .. n_stacks_total - 1, a
  * negative weight, or wa + wb outside 1 .. 65536.  TDOA_ERR_UNSUPPORTED: with the upsample setting U_loc > 1, a station with
@@ -1236,6 +1236,99 @@ int tdoa_clock_mix_rows(const int32_t *clock16, int n_stacks, int n_stations, co
  * TDOA_ERR_INVALID as tdoa_clock_mix_rows, n_stacks or n_rows above 65535, n_stations outside 2 .. 64, another U_loc. */
 int tdoa_debug_clock_mix(tdoa_ctx *ctx, const int32_t *clock16, int n_stacks, int n_stations, const tdoa_clock_mix *mix, int n_rows,
                          int U_loc, int32_t *rows, int64_t *cdiff, int64_t *cdiff_up);
+
+/* Free-running clocks to fix in one call.  Receivers whose clocks run free have no stable offset to carry from the reference
+ * blocks to the target block: a line per station is found on a reference block (offset and rate), continued over the target
+ * block, and the target is tracked under those rows.  tdoa_process_sync_drift_fine, tdoa_sync_line_clock16 on the host,
+ * tdoa_locate_set_clock and tdoa_process_locate_track_zoom do that in two steps that accumulate the same windows twice, with
+ * the clocks going through the host; this call does it in one step graph behind one accumulation of the stacks, and the
+ * lines never leave the device.
+ *   1. The fine clock lines: tdoa_process_sync_drift_fine(windows_per_stack, gate, max_drift, drift_den, rounds, U,
+ *      fine_rounds, ref_delay, centre) unchanged, on every block.  The first twelve outputs are that call's bytes.
+ *   2. A clock row for every stack, from the lines' c16 = clock16 and eta = fine_rate of step 1.  Which lines, continued to
+ *      which positions, make which stack's row is data: mix[t] = (a, xa, b, xb, wa, wb), one entry per stack, and for station
+ *      s, in 64-bit integers,
+ *        cont(l, x)[s] = c16[l][s] + r(16 eta[l][s] x, U drift_den)
+ *        row[t][s] = sgn(T) ((2 |T| + den) div (2 den)),  T = wa cont(a, xa)[s] + wb cont(b, xb)[s],  den = wa + wb.
+ *      cont is tdoa_sync_line_clock16's rule: r the nearest integer, halves away from zero.  x is signed: a negative x
+ *      continues a line backwards, so the line of the reference block after the target serves as well as the one before.
+ *      The mean is tdoa_clock_mix's: the nearest integer to T / den, halves away from zero.  Two identities:
+ *        (l, x, l, x, 1, 0) is line l continued to x, tdoa_sync_line_clock16's word;
+ *        (0, L + j, 2, j - L, L - j, j + 1) on stack j of the middle one of three blocks of L stacks is the line before
+ *        continued forwards and the line after continued backwards, weighted by nearness.
+ *      mix == NULL: stack l L + x takes (l, x, l, x, 1, 0), its own line at its own position.  At U = 16 these rows are
+ *      fine_rows byte for byte.  At U < 16 they differ from fine_rows by less than 1/U sample: fine_rows rounds the
+ *      continuation in units of 1/U sample and scales by 16 / U, this rule rounds it in units of 1/16 sample.
+ *      mix_rows_host receives the rows.
+ *   3. The zoomed cell tracks: tdoa_process_locate_track_zoom(windows_per_stack, max_step, min_separation, Z, H, fine_step,
+ *      fine_separation) unchanged, on every block, under those rows: the last thirteen outputs are that call's bytes after
+ *      tdoa_locate_set_clock(rows), the coarse tracks' lags and corr under loc_lags_host and loc_corr_host.  It honours the
+ *      context's table, fine table, upsample setting and statistics setting as that call does, and tdoa_locate_last_stats
+ *      returns what it returns after that call.
+ * Both searches run on every block: a line on the target block and a track on a reference block are returned for what they
+ * are worth.  Lines and tracks are the same sets, a block's stacks.
+ * The context's own clock table (tdoa_locate_set_clock) is neither read nor changed, whatever its shape: the call after
+ * this one finds it as it was.
+ * One kernel between the two searches' launches; the mix, like ref_delay and centre, is data: a new mix, new delays, centres,
+ * table or fine table of the same shape replay the captured graph.  The graph's key is both searches' words, the tracks'
+ * clock flag on.
+ * Scope: the rounds of tdoa_process_locate_track_multi are not this call; Z = 1, H = 0 with the fine table set to the table is
+ * the form without a zoom.
+ * The refusals are those of the two calls, and: TDOA_ERR_INVALID: a mix entry with a or b outside 0 .. n_lines - 1 (n_lines = 3),
+ * |xa| or |xb| above 65535, a negative weight, or wa + wb outside 1 .. 65536; with X the larger of L - 1 and the mix's largest
+ * |x|, a station with |centre| + gate + 2 + ((max_drift + 1) X) div drift_den >= 2^27: a row in 1/16 sample would not fit int32.
+ * TDOA_ERR_UNSUPPORTED: with the upsample setting U_loc > 1, a station with 16 times that sum times U_loc >= 2^31 (the message is
+ * the clock table's); TDOA_LAGS_GO.  The bound follows from |clock16| <= 16 (|centre| + gate + 1) and |fine_rate| <=
+ * U (max_drift + 1); the mean is a convex combination, so no value on the device needs a check.  All checks happen before
+ * anything needs a device. */
+typedef struct {
+    int32_t a, xa;        /* a line and the position it is continued to, |xa| <= 65535 */
+    int32_t b, xb;        /* another (or the same), |xb| <= 65535 */
+    int32_t wa, wb;       /* their weights, >= 0, 1 <= wa + wb <= 65536 */
+} tdoa_line_mix;
+
+int tdoa_process_sync_drift_locate(tdoa_ctx *ctx, int windows_per_stack, int gate /* G */, int max_drift, int drift_den,
+                                   int rounds /* R */, int U, int fine_rounds /* Rf */, const int32_t *ref_delay /* [n_stations] */,
+                                   const int32_t *centre /* [n_stations], NULL: all 0 */,
+                                   const tdoa_line_mix *mix /* [n_stacks_total], NULL: every stack its own line at its own position */,
+                                   int max_step, int min_separation, int Z, int H, int fine_step, int fine_separation,
+                                   tdoa_sync_line *line_host, int32_t *clock_host, int32_t *rate_host, int32_t *rows_host,
+                                   int32_t *lags_host, double *corr_host, tdoa_sync_line *fine_host, int32_t *clock16_host,
+                                   int32_t *fine_rate_host, int32_t *fine_rows_host, int32_t *fine_lags_host,
+                                   double *fine_corr_host /* tdoa_process_sync_drift_fine's twelve; line_host and fine_host required */,
+                                   int32_t *mix_rows_host /* [n_stacks_total][n_stations], 1/16 sample, may be NULL */,
+                                   tdoa_cell_track *track_host, int32_t *cells_host, int64_t *own_host, int32_t *loc_lags_host,
+                                   double *loc_corr_host, int64_t *total_host, tdoa_cell_track *ztrack_host, int32_t *zcells_host,
+                                   int64_t *zown_host, int32_t *zlags_host, double *zcorr_host, int64_t *zmap_host,
+                                   int64_t *ztotal_host /* tdoa_process_locate_track_zoom's thirteen; track_host and ztrack_host required */);
+
+/* tests only: the same kernels on the caller's words, as tdoa_debug_sync_drift_fine_from_q and
+ * tdoa_debug_locate_track_zoom_from_q, with the context's table, fine table and settings: set t track_len + x is position x of
+ * line and track t, mix is [n_sets] and names the n_sets / track_len lines.  Refuses what the call and those two refuse. */
+int tdoa_debug_sync_drift_locate_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int track_len, int n_stations, int n_w, int gate,
+                                        int max_drift, int drift_den, int rounds, int U, int fine_rounds, const int32_t *ref_delay,
+                                        const int32_t *centre, const tdoa_line_mix *mix, int max_step, int min_separation, int Z, int H,
+                                        int fine_step, int fine_separation, tdoa_sync_line *line_host, int32_t *clock_host,
+                                        int32_t *rate_host, int32_t *rows_host, int32_t *lags_host, double *corr_host,
+                                        tdoa_sync_line *fine_host, int32_t *clock16_host, int32_t *fine_rate_host, int32_t *fine_rows_host,
+                                        int32_t *fine_lags_host, double *fine_corr_host, int32_t *mix_rows_host, tdoa_cell_track *track_host,
+                                        int32_t *cells_host, int64_t *own_host, int32_t *loc_lags_host, double *loc_corr_host,
+                                        int64_t *total_host, tdoa_cell_track *ztrack_host, int32_t *zcells_host, int64_t *zown_host,
+                                        int32_t *zlags_host, double *zcorr_host, int64_t *zmap_host, int64_t *ztotal_host);
+
+/* Host only: step 2 in plain C.  clock16, fine_rate [n_lines][n_stations], mix [n_rows] -> rows [n_rows][n_stations].
+ * TDOA_ERR_INVALID: a NULL pointer, a count < 1, U not a factor (2, 4, 8, 16), drift_den < 1, a mix entry the call above
+ * refuses (a, b against n_lines), or a continued clock that does not fit int32 (the words are the caller's, so they are
+ * looked at one by one). */
+int tdoa_line_mix_rows(const int32_t *clock16, const int32_t *fine_rate, int n_lines, int n_stations, int U, int drift_den,
+                       const tdoa_line_mix *mix, int n_rows, int32_t *rows);
+
+/* tests only: the kernel of step 2 alone on the caller's words, with U_loc (1, 2, 4, 8 or 16) an argument; the context's
+ * setting is not read.  rows [n_rows][n_stations]; cdiff [n_rows][n_pairs] = row[j] - row[i] in tdoa_locate_set_clock's pair
+ * order (i < j, i first); cdiff_up = U_loc x cdiff: the two arrays the family's kernels take.  All outputs required.
+ * TDOA_ERR_INVALID as tdoa_line_mix_rows, n_lines or n_rows above 65535, n_stations outside 2 .. 64, another U_loc. */
+int tdoa_debug_line_mix(tdoa_ctx *ctx, const int32_t *clock16, const int32_t *fine_rate, int n_lines, int n_stations, int U, int drift_den,
+                        const tdoa_line_mix *mix, int n_rows, int U_loc, int32_t *rows, int64_t *cdiff, int64_t *cdiff_up);
 
 /* Capture-quality statistics of every (window, station) in one streaming pass over the bytes
  * in HBM: the byte statistics of fastAnalyzeSamples
@@ -1542,6 +1635,20 @@ int tdoa_group_process_sync_locate(tdoa_group *g, int windows_per_stack, int gat
                                    tdoa_sync *fine_host, int32_t *clock16_host, int32_t *fine_lags_host, double *fine_corr_host,
                                    int32_t *rows_host, tdoa_location *loc_host, int32_t *loc_lags_host, double *loc_corr_host,
                                    int64_t *map_host, tdoa_zoom *zoom_host, int32_t *zlags_host, double *zcorr_host, int64_t *zmap_host);
+
+/* tdoa_process_sync_drift_locate over the members: the merged sum is searched on member 0 -- its table, fine table and
+ * settings, as for the zoomed tracks -- and the same bytes go through the merged sum as a single context returns.  Errors as
+ * there. */
+int tdoa_group_process_sync_drift_locate(tdoa_group *g, int windows_per_stack, int gate, int max_drift, int drift_den, int rounds, int U,
+                                         int fine_rounds, const int32_t *ref_delay, const int32_t *centre, const tdoa_line_mix *mix,
+                                         int max_step, int min_separation, int Z, int H, int fine_step, int fine_separation,
+                                         tdoa_sync_line *line_host, int32_t *clock_host, int32_t *rate_host, int32_t *rows_host,
+                                         int32_t *lags_host, double *corr_host, tdoa_sync_line *fine_host, int32_t *clock16_host,
+                                         int32_t *fine_rate_host, int32_t *fine_rows_host, int32_t *fine_lags_host, double *fine_corr_host,
+                                         int32_t *mix_rows_host, tdoa_cell_track *track_host, int32_t *cells_host, int64_t *own_host,
+                                         int32_t *loc_lags_host, double *loc_corr_host, int64_t *total_host, tdoa_cell_track *ztrack_host,
+                                         int32_t *zcells_host, int64_t *zown_host, int32_t *zlags_host, double *zcorr_host, int64_t *zmap_host,
+                                         int64_t *ztotal_host);
 
 /* the sample runs member `rank` of `world` uploads for a capture of total_samples (window grid from n_min, the shortest
  * capture of the job; block offsets from the capture's own thirds): adjacent owned windows form one run, and with fewer

@@ -57,9 +57,15 @@ the seventeen outputs but the maps downloaded (name process_sync_locate_RxC_Z_H_
 launches, one kernel for the rows and the zoom locate's launches in one step behind one accumulation), and the chain it
 replaces, timed as one unit (name sync_locate_chain_RxC_Z_H_G_U_R_RF[_upU]_ms): tdoa_process_sync_fine, tdoa_clock_mix_rows on
 the host, tdoa_locate_set_clock and tdoa_process_locate_zoom.  Give the same options their own legs (they are there already) to
-have process_sync_fine and process_locate_zoom in the same process.
+have process_sync_fine and process_locate_zoom in the same process.  `--sync-drift-locate` adds, per `--locate` grid, `--locate-track J`,
+`--locate-track-zoom Z[/H[/JF]]`, `--sync-drift-fine G/H/D/R/U/RF` and for U_loc = 1 and every `--locate-upsample U`, two legs:
+tdoa_process_sync_drift_locate(M, G, H, D, R, U, RF, forward mix, J, 1, Z, H, JF, 1) with the twenty-six outputs but the planes
+downloaded (name process_sync_drift_locate_RxC_JJ_Z_H_JF_G_H_D_R_U_RF[_upU]_ms: the fine lines' launches, one kernel for the rows
+and the zoomed tracks' launches in one step behind one accumulation), and the chain it replaces, timed as one unit (name
+sync_drift_locate_chain_...): tdoa_process_sync_drift_fine, tdoa_line_mix_rows on the host, tdoa_locate_set_clock and
+tdoa_process_locate_track_zoom.
 usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--stack M] [--drift H/D]... [--track J]...
-[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]... [--locate-upsample U]... [--sync-fine G/U[/R[/RF]]]... [--locate-zoom Z[/H]]... [--sync-drift-fine G/H/D/R/U/RF]... [--locate-track-zoom Z[/H[/JF]]]... [--sync-locate] [--max-lag N]"""
+[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]... [--locate-upsample U]... [--sync-fine G/U[/R[/RF]]]... [--locate-zoom Z[/H]]... [--sync-drift-fine G/H/D/R/U/RF]... [--locate-track-zoom Z[/H[/JF]]]... [--sync-locate] [--sync-drift-locate] [--max-lag N]"""
 import json
 import os
 import sys
@@ -90,7 +96,7 @@ def timed(fn, steps):
 
 def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=(), locate_tracks=(), stack=0, emitters=(),
          track_emitters=(), map_stats=None, sync_drifts=(), upsamples=(), max_lag=20000, sync_fines=(), zooms=(), sync_drift_fines=(), track_zooms=(),
-         sync_locate=False):
+         sync_locate=False, sync_drift_locate=False):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=max_lag)
     for s in range(stations):
         c.synth_capture(s, 66_666_666, ST[s % 3], TX, 0x5D0A0000 + s)
@@ -114,6 +120,14 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
         found = c.process_sync_fine(ref, stack, G, R, U, Rf)
         c.locate_set_clock(tdoa_amd.capi.clock_mix_rows(found["clock16"], mix))
         return c.process_locate_zoom(Z, H, stack, 1, 1, want_zmap=False)
+
+    forward = tdoa_amd.line_mix.forward_mix(c.num_stacks(stack)[0])
+
+    def drift_chain(G, Hd, D, R, U, Rf, J, Z, H, Jf):
+        """what a caller does without tdoa_process_sync_drift_locate, as one unit"""
+        found = c.process_sync_drift_fine(ref, stack, G, Hd, D, R, U, Rf)
+        c.locate_set_clock(tdoa_amd.capi.line_mix_rows(found["clock16"], found["fine_rate"], U, D, forward))
+        return c.process_locate_track_zoom(Z, H, stack, J, 1, Jf, 1, want_zmap=False, want_ztotal=False)
 
     def family(name, table, cols, fn, U=1, fine=None, fine_cols=None):
         """a leg of the delay-table family with the statistics off and, with --map-stats, the same leg with them on"""
@@ -168,6 +182,15 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
                     family("process_locate_track_zoom_%dx%d_J%d_%d_%d_%d%s_ms" % (rows, cols, J, Z, H, Jf, up), table, cols,
                            lambda J=J, Z=Z, H=H, Jf=Jf: c.process_locate_track_zoom(Z, H, stack, J, 1, Jf, 1, want_zmap=False, want_ztotal=False),
                            U, fine, cols_f)
+                    for G, Hd, D, R, Uf, Rf in sync_drift_fines if sync_drift_locate else ():
+                        tag = "%dx%d_J%d_%d_%d_%d_%d_%d_%d_%d_%d_%d%s_ms" % (rows, cols, J, Z, H, Jf, G, Hd, D, R, Uf, Rf, up)
+                        family("process_sync_drift_locate_" + tag, table, cols,
+                               lambda J=J, Z=Z, H=H, Jf=Jf, G=G, Hd=Hd, D=D, R=R, Uf=Uf, Rf=Rf: c.process_sync_drift_locate(
+                                   ref, Z, H, stack, G, Hd, D, R, Uf, Rf, None, forward, J, 1, Jf, 1, want_zmap=False, want_ztotal=False),
+                               U, fine, cols_f)
+                        family("sync_drift_locate_chain_" + tag, table, cols,
+                               lambda J=J, Z=Z, H=H, Jf=Jf, G=G, Hd=Hd, D=D, R=R, Uf=Uf, Rf=Rf: drift_chain(G, Hd, D, R, Uf, Rf, J, Z, H, Jf),
+                               U, fine, cols_f)
                     if U > 1:
                         family("process_locate_track_%dx%d_J%d%s_ms" % (rows, cols, J, up), table, cols,
                                lambda J=J: c.process_locate_track(stack, J, 1), U)
@@ -305,6 +328,9 @@ if __name__ == "__main__":
     sync_locate = "--sync-locate" in args
     if sync_locate:
         args.remove("--sync-locate")
+    sync_drift_locate = "--sync-drift-locate" in args
+    if sync_drift_locate:
+        args.remove("--sync-drift-locate")
     sync_drifts = []
     while "--sync-drift" in args:
         i = args.index("--sync-drift")
@@ -318,4 +344,5 @@ if __name__ == "__main__":
         syncs.append((int(g), int(r or 2)))
         del args[i:i + 2]
     main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs, locate_tracks, opt["--stack"], emitters,
-         track_emitters, map_stats, sync_drifts, upsamples, opt["--max-lag"], sync_fines, zooms, sync_drift_fines, track_zooms, sync_locate)
+         track_emitters, map_stats, sync_drifts, upsamples, opt["--max-lag"], sync_fines, zooms, sync_drift_fines, track_zooms, sync_locate,
+         sync_drift_locate)

@@ -179,7 +179,9 @@ int main(int argc, char **argv)
     bool sync_fine = false;
     // --one-call (with --stack --locate --sync --sync-fine --locate-zoom): the clocks, the target block's midpoint row and the zoom
     // locate in one call (tdoa_process_sync_locate): the clocks stay on the device and the stacks are accumulated once.  Prints
-    // what the run without the flag prints
+    // what the run without the flag prints.  Also with --stack=M --locate --sync --sync-drift --sync-drift-fine --locate-track
+    // --locate-track-zoom: the fine lines, the target block's rows (block 1's fine line continued) and the zoomed tracks in one call
+    // (tdoa_process_sync_drift_locate); the same stdout at --sync-drift-fine=16
     bool one_call = false;
     int sfine_u = 16, sfine_r = 2;
     // --sync-drift-fine=U[/RF] (with --sync-drift), U in 2, 4, 8, 16: the lines' offsets and rates are refined to 1/U sample in RF
@@ -359,7 +361,7 @@ int main(int argc, char **argv)
     if (sync_drift && !sync) { std::fprintf(stderr, "--sync-drift needs --stack --locate --sync\n"); return 1; }
     if (sync_drift_fine && !sync_drift) { std::fprintf(stderr, "--sync-drift-fine needs --stack --locate --sync --sync-drift\n"); return 1; }
     if (sync_fine && (!sync || sync_drift)) { std::fprintf(stderr, "--sync-fine needs --stack --locate --sync and no --sync-drift\n"); return 1; }
-    if (one_call && (!sync_fine || !locate_zoom)) {
+    if (one_call && (!sync_fine || !locate_zoom) && (!sync_drift_fine || !track_zoom)) {
         std::fprintf(stderr, "--one-call needs --stack --locate --sync --sync-fine --locate-zoom\n");
         return 1;
     }
@@ -611,7 +613,9 @@ int main(int argc, char **argv)
                         lines.resize(3);
                         clocks.resize(3 * (size_t)S);
                         rates.resize(3 * (size_t)S);
-                        if (sync_drift_fine) {               // the fine rows; the target block's are block 1's fine line continued
+                        if (one_call) {
+                            ref16 = ref;                     // the lines are searched with the zoomed tracks, below
+                        } else if (sync_drift_fine) {               // the fine rows; the target block's are block 1's fine line continued
                             flines.resize(3);
                             fclocks16.resize(3 * (size_t)S);
                             frates.resize(3 * (size_t)S);
@@ -666,6 +670,39 @@ int main(int argc, char **argv)
                     out->resize(map_stats ? n : 0);
                     return map_stats ? tdoa_locate_last_stats(ctx, out->data(), (int)n, nullptr) : TDOA_OK;
                 };
+                if (one_call && sync_drift_fine) {
+                    // The fine lines, the rows and the zoomed tracks in one call, on the fine grid --locate-track-zoom builds below:
+                    // blocks 1 and 3 their own lines at their own positions, stack j of block 2 block 1's fine line continued to
+                    // spb + j.  The rows then go to the clock table for the searches further down, which this call itself never reads
+                    const int rows_f = (locate_rows - 1) * tzoom_z + 1;
+                    tzoom_cols = (locate_cols - 1) * tzoom_z + 1;
+                    std::vector<int32_t> fine((size_t)rows_f * tzoom_cols * S);
+                    if ((rc = tdoa_locate_grid_table(lle.data(), S, grid_lat0, grid_lon0, grid_dlat / tzoom_z, grid_dlon / tzoom_z, rows_f, tzoom_cols,
+                                                     h_c, prm.sample_rate, fine.data())))
+                        return die("tdoa_locate_grid_table", rc);
+                    if ((rc = tdoa_locate_set_fine_table(ctx, fine.data(), rows_f * tzoom_cols, tzoom_cols, S))) return die("tdoa_locate_set_fine_table", rc);
+                    std::vector<tdoa_line_mix> mix((size_t)n_stacks);
+                    for (int t = 0; t < n_stacks; t++)
+                        mix[t] = t / spb == 1 ? tdoa_line_mix{0, t, 0, t, 1, 0} : tdoa_line_mix{t / spb, t % spb, t / spb, t % spb, 1, 0};
+                    std::vector<int32_t> rows16((size_t)n_stacks * S);
+                    flines.resize(3);
+                    fclocks16.resize(3 * (size_t)S);
+                    frates.resize(3 * (size_t)S);
+                    ltracks.resize((size_t)(n_stacks / spb));
+                    lt_cells.resize((size_t)n_stacks);
+                    lt_own.resize((size_t)n_stacks);
+                    ztracks.resize(ltracks.size());
+                    zt_cells.resize((size_t)n_stacks);
+                    if ((rc = tdoa_process_sync_drift_locate(ctx, stack_m, sync_g, sdrift_h, sdrift_d, sync_r, sdfine_u, sdfine_r, ref16.data(), nullptr,
+                                                             mix.data(), ltrack_j, ltrack_sep, tzoom_z, tzoom_h, tzoom_jf, tzoom_sep, lines.data(),
+                                                             clocks.data(), rates.data(), nullptr, nullptr, nullptr, flines.data(), fclocks16.data(),
+                                                             frates.data(), nullptr, nullptr, nullptr, rows16.data(), ltracks.data(), lt_cells.data(),
+                                                             lt_own.data(), nullptr, nullptr, nullptr, ztracks.data(), zt_cells.data(), nullptr, nullptr,
+                                                             nullptr, nullptr, nullptr)))
+                        return die("tdoa_process_sync_drift_locate", rc);
+                    if ((rc = last_stats(&ltstats, ltracks.size()))) return die("tdoa_locate_last_stats", rc);
+                    if ((rc = tdoa_locate_set_clock(ctx, rows16.data(), n_stacks, S))) return die("tdoa_locate_set_clock", rc);
+                }
                 locs.resize((size_t)n_stacks);
                 if (locate_zoom) {
                     // the same grid at Z cells per cell: fine cell (Z r, Z c) lies where cell (r, c) does
@@ -677,7 +714,7 @@ int main(int argc, char **argv)
                         return die("tdoa_locate_grid_table", rc);
                     if ((rc = tdoa_locate_set_fine_table(ctx, fine.data(), rows_f * zoom_cols, zoom_cols, S))) return die("tdoa_locate_set_fine_table", rc);
                     zooms.resize((size_t)n_stacks);
-                    if (one_call) {
+                    if (one_call && sync_fine) {
                         // blocks 1 and 3 their own refined clocks, stack j of block 2 the midpoint of stack j of blocks 1 and 3; the
                         // rows then go to the clock table for the searches further down, which this call itself never reads
                         std::vector<tdoa_clock_mix> mix((size_t)n_stacks);
@@ -700,14 +737,14 @@ int main(int argc, char **argv)
                         return die("tdoa_process_locate_zoom", rc);
                 } else if ((rc = tdoa_process_locate(ctx, stack_m, 1, locs.data(), nullptr, nullptr, nullptr)))
                     return die("tdoa_process_locate", rc);
-                if (!one_call && (rc = last_stats(&lstats, locs.size()))) return die("tdoa_locate_last_stats", rc);
+                if (!(one_call && sync_fine) && (rc = last_stats(&lstats, locs.size()))) return die("tdoa_locate_last_stats", rc);
                 if (emitters) {
                     mlocs.resize((size_t)emitters_k * n_stacks);
                     if ((rc = tdoa_process_locate_multi(ctx, stack_m, emitters_k, emitters_guard, 1, mlocs.data(), nullptr, nullptr, nullptr)))
                         return die("tdoa_process_locate_multi", rc);
                     if ((rc = last_stats(&mstats, mlocs.size()))) return die("tdoa_locate_last_stats", rc);
                 }
-                if (locate_track) {
+                if (locate_track && !(one_call && sync_drift_fine)) {       // (the one call above has tracked already)
                     ltracks.resize((size_t)(n_stacks / spb));
                     lt_cells.resize((size_t)n_stacks);
                     lt_own.resize((size_t)n_stacks);

@@ -193,11 +193,8 @@ int tdoa_sync_line_clock16(const int32_t *clock16, const int32_t *fine_rate, int
         return TDOA_ERR_INVALID;
     const long long den = (long long)U * drift_den;
     for (int x = 0; x < n_positions; x++)
-        for (int s = 0; s < n_stations; s++) {
-            const long long num = (long long)kLocateDelayUnit * fine_rate[s] * ((long long)first_position + x);
-            const long long a = (2 * (num < 0 ? -num : num) + den) / (2 * den);
-            out[(size_t)x * n_stations + s] = (int32_t)((long long)clock16[s] + (num < 0 ? -a : a));
-        }
+        for (int s = 0; s < n_stations; s++)
+            out[(size_t)x * n_stations + s] = (int32_t)line_cont(clock16[s], fine_rate[s], (long long)first_position + x, den);
     return TDOA_OK;
 }
 

@@ -52,6 +52,7 @@
 #include "stack_locate_zoom.hpp"
 #include "stack_locate_track_zoom.hpp"
 #include "stack_clock_mix.hpp"
+#include "stack_line_mix.hpp"
 
 using namespace tdoa;
 
@@ -238,6 +239,10 @@ struct tdoa_ctx {
     // the stacks' clock rows [stack][station] and their pairs' differences and U x them [stack][pair], which the zoom locate of
     // that call takes where the others take locate_clock and locate_clock_up; tdoa_debug_clock_mix's clocks [stack][station]
     DevBuf mix_in, mix_rows, mix_cdiff, mix_cdiff_up, mix_debug;
+    // free-running clocks to fix in one call (tdoa_process_sync_drift_locate), between the fine clock lines and the zoomed cell
+    // tracks: the line mix [stack]; its rows and differences go where the clock mix's go, and tdoa_debug_line_mix's clocks and
+    // rates [2][line][station] into mix_debug
+    DevBuf lmix_in;
     size_t total_mem = 0;                  // of the device, 0: unknown
 };
 
@@ -608,7 +613,7 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->slfine_out, &ctx->slfine_clock, &ctx->slfine_rate, &ctx->slfine_rows, &ctx->slfine_lags, &ctx->slfine_corr,
                       &ctx->locate_fine, &ctx->locate_fine_up, &ctx->zoom_map, &ctx->zoom_part, &ctx->zoom_out, &ctx->zoom_lags, &ctx->zoom_corr,
                       &ctx->tzoom_centre, &ctx->tzoom_e, &ctx->tzoom_total, &ctx->tzoom_out, &ctx->tzoom_cells, &ctx->tzoom_own,
-                      &ctx->mix_in, &ctx->mix_rows, &ctx->mix_cdiff, &ctx->mix_cdiff_up, &ctx->mix_debug};
+                      &ctx->mix_in, &ctx->mix_rows, &ctx->mix_cdiff, &ctx->mix_cdiff_up, &ctx->mix_debug, &ctx->lmix_in};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1352,3 +1357,4 @@ int tdoa_solve_surface(const double *stations_lle, int n_stations, const double 
 #include "sync_drift_api.inc"
 #include "sync_drift_fine_api.inc"
 #include "sync_locate_api.inc"
+#include "sync_drift_locate_api.inc"

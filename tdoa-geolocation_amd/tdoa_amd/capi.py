@@ -138,6 +138,8 @@ SYMBOLS = [
     "tdoa_process_locate_track_zoom", "tdoa_group_process_locate_track_zoom", "tdoa_debug_locate_track_zoom_from_q",
     "tdoa_process_sync_locate", "tdoa_group_process_sync_locate", "tdoa_debug_sync_locate_from_q", "tdoa_clock_mix_rows",
     "tdoa_debug_clock_mix",
+    "tdoa_process_sync_drift_locate", "tdoa_group_process_sync_drift_locate", "tdoa_debug_sync_drift_locate_from_q",
+    "tdoa_line_mix_rows", "tdoa_debug_line_mix",
 ]
 
 
@@ -157,9 +159,10 @@ def _Out(key, dtype, shape, want=None, poison=False):
 
 
 class _Search:
-    def __init__(self, name, ints, outputs, inputs=(), track_len=False, stats=None, bare=False, late_ints=()):
+    def __init__(self, name, ints, outputs, inputs=(), track_len=False, stats=None, bare=False, late_ints=(), mix_width=4):
         self.name, self.ints, self.outputs, self.inputs = name, ints, outputs, inputs
         self.late_ints = late_ints           # ints the header states behind the inputs
+        self.mix_width = mix_width           # the ints of an entry of the input "mix": 4 tdoa_clock_mix, 6 tdoa_line_mix
         self.entries = {"own": "tdoa_process_" + name, "group": "tdoa_group_process_" + name,
                         "q": "tdoa_debug_%s_from_q" % name}
         self.track_len = track_len           # the from-Q entry takes track_len
@@ -227,6 +230,14 @@ TRACK_ZOOM_SEARCHES = {s.name: s for s in (
             tuple(o._replace(key="loc_" + o.key) if o.key in ("lags", "corr") else o for o in SEARCHES["locate_zoom"].outputs),
             _CLOCKS + ("mix",), stats="loc", late_ints=SEARCHES["locate_zoom"].ints),
 )}
+# free-running clocks to fix in one call: the fine clock lines' arguments, the line mix, the zoomed tracks' ints, the twenty-six
+# outputs of the two with the mix's rows between them (the tracks' lags and corr under loc_ names: the lines have theirs)
+TRACK_ZOOM_SEARCHES["sync_drift_locate"] = _Search(
+    "sync_drift_locate", LATER_SEARCHES["sync_drift_fine"].ints,
+    LATER_SEARCHES["sync_drift_fine"].outputs + (_Out("mix_rows", np.int32, ("n_sets", "S")),) +
+    tuple(o._replace(key="loc_" + o.key) if o.key in ("lags", "corr") else o for o in TRACK_ZOOM_SEARCHES["locate_track_zoom"].outputs),
+    _CLOCKS + ("mix",), track_len=True, stats="track", late_ints=TRACK_ZOOM_SEARCHES["locate_track_zoom"].ints, mix_width=6)
+
 
 
 def _search(name):
@@ -374,6 +385,8 @@ def load(build_if_missing=True):
     L.tdoa_debug_upsample_q.argtypes = [vp, i64p, C.c_int, C.c_int, i64p]
     L.tdoa_clock_mix_rows.argtypes = [i32p, C.c_int, C.c_int, i32p, C.c_int, i32p]
     L.tdoa_debug_clock_mix.argtypes = [vp, i32p, C.c_int, C.c_int, i32p, C.c_int, C.c_int, i32p, i64p, i64p]
+    L.tdoa_line_mix_rows.argtypes = [i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, i32p, C.c_int, i32p]
+    L.tdoa_debug_line_mix.argtypes = [vp, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, i32p, C.c_int, C.c_int, i32p, i64p, i64p]
     L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
                                         C.POINTER(C.c_int)]
     for s in list(SEARCHES.values()) + list(LATER_SEARCHES.values()) + list(TRACK_ZOOM_SEARCHES.values()):
@@ -495,6 +508,48 @@ class _LaterContextSearches:
         return rows, cdiff, up
 
 
+    def process_sync_drift_locate(self, ref_delay, Z, H, windows_per_stack=0, gate=0, max_drift=0, drift_den=1, rounds=0, U=16,
+                                  fine_rounds=2, centre=None, mix=None, max_step=0, min_separation=1, fine_step=0, fine_separation=1,
+                                  want_total=False, want_zmap=True, want_ztotal=True):
+        """tdoa_process_sync_drift_locate -> process_sync_drift_fine's twelve outputs (that call's bytes), "mix_rows":
+        [n_stacks][S] int32 (1/16 sample), and process_locate_track_zoom's thirteen as after locate_set_clock(mix_rows), the
+        coarse tracks' lags and corr under "loc_lags" and "loc_corr": the fine clock lines, a clock row per stack made on the
+        device from their clock16 and fine_rate by mix [n_stacks][6] (a, xa, b, xb, wa, wb; None: every stack its own line at its
+        own position; line_mix.forward_mix or bridge_mix for [reference | target | reference]), and the zoomed cell tracks under
+        those rows, in one step.  The context's clock table is neither read nor changed"""
+        return _process_search(self, self, "sync_drift_locate", dict(
+            windows_per_stack=windows_per_stack, gate=gate, max_drift=max_drift, drift_den=drift_den, rounds=rounds, U=U,
+            fine_rounds=fine_rounds, ref_delay=ref_delay, centre=centre, mix=mix, max_step=max_step, min_separation=min_separation, Z=Z,
+            H=H, fine_step=fine_step, fine_separation=fine_separation, want_total=want_total, want_zmap=want_zmap,
+            want_ztotal=want_ztotal))
+
+    def sync_drift_locate_from_q(self, q, ref_delay, track_len, Z, H, n_w=1, gate=0, max_drift=0, drift_den=1, rounds=0, U=16,
+                                 fine_rounds=2, centre=None, mix=None, max_step=0, min_separation=1, fine_step=0, fine_separation=1,
+                                 want_total=True, want_zmap=True, want_ztotal=True):
+        """tdoa_debug_sync_drift_locate_from_q: the same kernels on the caller's words q [n_sets][P][2 max_lag - 1] int64, set
+        t track_len + j position j of line and track t, with the context's table, fine table and settings -> what
+        process_sync_drift_locate returns, n_sets for n_stacks; mix names the n_sets / track_len lines"""
+        return self._from_q("sync_drift_locate", q, np.size(ref_delay), dict(
+            track_len=track_len, n_w=n_w, gate=gate, max_drift=max_drift, drift_den=drift_den, rounds=rounds, U=U,
+            fine_rounds=fine_rounds, ref_delay=ref_delay, centre=centre, mix=mix, max_step=max_step, min_separation=min_separation, Z=Z,
+            H=H, fine_step=fine_step, fine_separation=fine_separation, want_total=want_total, want_zmap=want_zmap,
+            want_ztotal=want_ztotal))
+
+    def debug_line_mix(self, clock16, fine_rate, U, drift_den, mix, U_loc=1):
+        """tdoa_debug_line_mix: the line mix kernel alone on clock16, fine_rate [n_lines][S] int32 and mix [m][6] -> (rows [m][S]
+        int32, cdiff [m][P] int64 = row[j] - row[i] in locate_set_clock's pair order, cdiff_up = U_loc x cdiff), written over
+        poisoned arrays"""
+        c, h = _line_words(clock16, fine_rate)
+        m, (n, S) = np.shape(mix)[0], c.shape
+        rows, cdiff, up = (_poisoned((m, S), np.int32), _poisoned((m, S * (S - 1) // 2), np.int64),
+                           _poisoned((m, S * (S - 1) // 2), np.int64))
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        self._chk(self._L.tdoa_debug_line_mix(self._h, c.ctypes.data_as(i32p), h.ctypes.data_as(i32p), n, S, int(U), int(drift_den),
+                                              _mix(mix, width=6), m, int(U_loc), rows.ctypes.data_as(i32p), cdiff.ctypes.data_as(i64p),
+                                              up.ctypes.data_as(i64p)))
+        return rows, cdiff, up
+
+
 class _LaterGroupSearches:
     def process_sync_drift_fine(self, ref_delay, windows_per_stack=0, gate=0, max_drift=0, drift_den=1, rounds=0, U=16, fine_rounds=2,
                                 centre=None):
@@ -518,6 +573,18 @@ class _LaterGroupSearches:
             windows_per_stack=windows_per_stack, gate=gate, rounds=rounds, U=U, fine_rounds=fine_rounds, ref_delay=ref_delay,
             centre=centre, mix=mix, min_separation=min_separation, Z=Z, H=H, fine_separation=fine_separation, want_map=want_map,
             want_zmap=want_zmap))
+
+
+    def process_sync_drift_locate(self, ref_delay, Z, H, windows_per_stack=0, gate=0, max_drift=0, drift_den=1, rounds=0, U=16,
+                                  fine_rounds=2, centre=None, mix=None, max_step=0, min_separation=1, fine_step=0, fine_separation=1,
+                                  want_total=False, want_zmap=True, want_ztotal=True):
+        """tdoa_group_process_sync_drift_locate -> Context.process_sync_drift_locate's outputs, byte-identical to a single
+        context's"""
+        return _process_search(self, self.member(0), "sync_drift_locate", dict(
+            windows_per_stack=windows_per_stack, gate=gate, max_drift=max_drift, drift_den=drift_den, rounds=rounds, U=U,
+            fine_rounds=fine_rounds, ref_delay=ref_delay, centre=centre, mix=mix, max_step=max_step, min_separation=min_separation, Z=Z,
+            H=H, fine_step=fine_step, fine_separation=fine_separation, want_total=want_total, want_zmap=want_zmap,
+            want_ztotal=want_ztotal))
 
 
 class Context(_LaterContextSearches):
@@ -1238,17 +1305,27 @@ def _search_ptrs(s, out):
     return [out[o.key].ctypes.data_as(o.ctype) if o.key in out else None for o in s.outputs]
 
 
-def _mix(mix, n_stations=None):
-    """a clock mix as the C ABI takes it: None, or [m][4] int32 (a, b, wa, wb; tdoa_clock_mix's layout)"""
+def _mix(mix, n_stations=None, width=4):
+    """a mix as the C ABI takes it: None, or [m][width] int32: (a, b, wa, wb), tdoa_clock_mix's layout, or with width 6
+    (a, xa, b, xb, wa, wb), tdoa_line_mix's"""
     if mix is None:
         return None
+    names = ("a", "b", "wa", "wb") if width == 4 else ("a", "xa", "b", "xb", "wa", "wb")
     m = np.asarray(mix)
     if m.dtype.names:
-        m = np.stack([m[k] for k in ("a", "b", "wa", "wb")], axis=-1)
+        m = np.stack([m[k] for k in names], axis=-1)
     m = np.ascontiguousarray(m, dtype=np.int32)
-    if m.ndim != 2 or m.shape[1] != 4:
-        raise ValueError("mix must be [m][4]: a, b, wa, wb")
+    if m.ndim != 2 or m.shape[1] != width:
+        raise ValueError("mix must be [m][%d]: %s" % (width, ", ".join(names)))
     return m.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _line_words(clock16, fine_rate):
+    """the fine lines' clocks and rates as the C ABI takes them: two [n_lines][S] int32"""
+    c, h = np.ascontiguousarray(clock16, dtype=np.int32), np.ascontiguousarray(fine_rate, dtype=np.int32)
+    if c.ndim != 2 or c.shape != h.shape:
+        raise ValueError("clock16 and fine_rate must be [n_lines][S]")
+    return c, h
 
 
 _INPUT = {"ref_delay": _ref_delay, "centre": _centre, "mix": _mix}
@@ -1266,7 +1343,8 @@ def _run_search(s, route, fn, handle, chk, n, values, q=None):
         shape = [int(values["windows_per_stack"])]
     if values.get("mix") is not None and np.shape(values["mix"])[0] != n["n_sets"]:
         raise ValueError("mix must hold one entry per stack")
-    chk(fn(handle, *shape, *[int(values[k]) for k in s.ints], *[_INPUT[k](values[k], n["S"]) for k in s.inputs],
+    chk(fn(handle, *shape, *[int(values[k]) for k in s.ints],
+           *[_mix(values[k], width=s.mix_width) if k == "mix" else _INPUT[k](values[k], n["S"]) for k in s.inputs],
            *[int(values[k]) for k in s.late_ints], *_search_ptrs(s, out)))
     return out[s.outputs[0].key] if s.bare else out
 
@@ -1509,6 +1587,21 @@ def clock_mix_rows(clock16, mix):
     rc = load().tdoa_clock_mix_rows(c.ctypes.data_as(i32p), c.shape[0], c.shape[1], _mix(mix), m, rows.ctypes.data_as(i32p))
     if rc != 0:
         raise TdoaError(rc, "tdoa_clock_mix_rows")
+    return rows
+
+
+def line_mix_rows(clock16, fine_rate, U, drift_den, mix):
+    """tdoa_line_mix_rows (host only): clock16, fine_rate [n_lines][S] int32 and mix [m][6] (a, xa, b, xb, wa, wb) -> rows [m][S]
+    int32: line a continued to xa and line b to xb by tdoa_sync_line_clock16's rule (x of either sign), then tdoa_clock_mix_rows'
+    mean by wa, wb: tdoa_process_sync_drift_locate's clock rows"""
+    c, h = _line_words(clock16, fine_rate)
+    m = np.shape(mix)[0]
+    rows = _poisoned((m, c.shape[1]), np.int32)
+    i32p = C.POINTER(C.c_int32)
+    rc = load().tdoa_line_mix_rows(c.ctypes.data_as(i32p), h.ctypes.data_as(i32p), c.shape[0], c.shape[1], int(U), int(drift_den),
+                                   _mix(mix, width=6), m, rows.ctypes.data_as(i32p))
+    if rc != 0:
+        raise TdoaError(rc, "tdoa_line_mix_rows")
     return rows
 
 
