@@ -308,7 +308,7 @@ int ensure_locate_run(tdoa_ctx *ctx, const LocateRun &run)
 // ---- the launches' pieces -----------------------------------------------------------------------------------------------------
 // The clock differences a run adds to its pairs' delays, [set][pair], and U x them for a run on upsampled surfaces; no buffers:
 // no clocks.  The family's one place that picks them: the context's clock table (tdoa_locate_set_clock) for every call but the
-// one that makes its stacks' clocks itself (sync_locate_api.inc).  Buffers, not pointers: a reserve between bind and launch
+// ones that make their stacks' clocks themselves (sync_locate_api.inc).  Buffers, not pointers: a reserve between bind and launch
 // may move them.
 struct LocateClocks {
     const DevBuf *diff = nullptr, *diff_up = nullptr;

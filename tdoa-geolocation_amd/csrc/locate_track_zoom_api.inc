@@ -20,28 +20,23 @@ struct LocateTrackZoomHost {
 
 struct LocateTrackZoomSearch : StackSearch {
     LocateSearch coarse;
-    int Z, H, Jf, sep;                       // fine cells per cell, the window's half side, fine_step, fine_separation
+    LocateFineWindow w;                      // (locate_zoom_api.inc)
+    int Jf;                                  // fine_step
     LocateTrackZoomHost o;
-    LocateGeom gf{};                         // bind: the coarse run's geometry with the fine table's shape, fine_separation and the window's tiles
-    LocateZoomGeom z{};
     TrackZoomGeom tz{};
 
     LocateTrackZoomSearch(int max_step, int min_separation, int zoom, int half, int fine_step, int fine_separation, tdoa_cell_track *track,
                           int32_t *cells, int64_t *own, int32_t *lags, double *corr, int64_t *total, const LocateTrackZoomHost &host)
         : StackSearch("the zoomed cell tracks with TDOA_LAGS_GO", nullptr),
           coarse(locate_track_call(false, max_step, 1, 0, min_separation, track, cells, own, nullptr, lags, corr, total)),
-          Z(zoom), H(half), Jf(fine_step), sep(fine_separation), o(host)
+          w{zoom, half, fine_separation}, Jf(fine_step), o(host)
     {
     }
     const char *check_args() const override
     {
         if (const char *bad = coarse.check_args()) return bad;
-        if (Z < 1 || Z > kLocateZoomMaxZ) return "Z outside 1 .. 64";
-        if (H < 0 || H > kLocateZoomMaxH) return "H outside 0 .. 64";
-        if (Jf < 0 || Jf > kTrackZoomMaxStep) return "fine_step outside 0 .. 16";
-        if (sep < 1) return "fine_separation < 1";
-        if (!o.track) return "ztrack_host is NULL";
-        return nullptr;
+        if (const char *bad = w.check_args(Jf < 0 || Jf > kTrackZoomMaxStep ? "fine_step outside 0 .. 16" : nullptr)) return bad;
+        return o.track ? nullptr : "ztrack_host is NULL";
     }
     int check_state(const tdoa_ctx *ctx, int windows_per_stack, const char **what) const override
     {
@@ -57,19 +52,7 @@ struct LocateTrackZoomSearch : StackSearch {
     void bind(const tdoa_ctx *ctx, const SearchShape &sh) override
     {
         coarse.bind(ctx, sh);
-        const LocateGeom &g = coarse.run.g;
-        z.Z = Z;
-        z.H = H;
-        z.side = 2 * H + 1;
-        z.n_pos = z.side * z.side;
-        z.coarse_cells = g.n_cells;
-        z.coarse_cols = g.n_cols;
-        z.tiles = (z.n_pos + kLocateThreads - 1) / kLocateThreads;
-        gf = g;                              // S, P and the lags (with U > 1 the fine ones) are the coarse run's
-        gf.n_cells = ctx->fine_cells;
-        gf.n_cols = ctx->fine_cols;
-        gf.sep = sep;
-        gf.tiles = z.tiles;
+        w.bind(ctx, coarse.run.g);
         tz.L = coarse.run.L;
         tz.Jf = Jf;
         tz.n_sets = coarse.run.n_sets;
@@ -77,8 +60,7 @@ struct LocateTrackZoomSearch : StackSearch {
     // the window, the fine step and the fine table's shape (its contents are data), then the tracks' words
     void key(std::vector<uint64_t> *key, int m) const override
     {
-        key->insert(key->end(), {StepProduct::LocateTrackZoom, (uint64_t)Z | ((uint64_t)H << 32), (uint64_t)Jf | ((uint64_t)sep << 32),
-                                 (uint64_t)gf.n_cells | ((uint64_t)gf.n_cols << 32)});
+        w.key(key, StepProduct::LocateTrackZoom, (uint64_t)Jf | ((uint64_t)w.sep << 32));
         coarse.key(key, m);
     }
     // the tracks' buffers, then the window maps, the steps E and the sums F_0 (the three that can be large), the tiles'
@@ -86,19 +68,19 @@ struct LocateTrackZoomSearch : StackSearch {
     int reserve(tdoa_ctx *ctx) const override
     {
         int rc;
-        const size_t n_sets = coarse.run.n_sets, n_tracks = coarse.run.n_tracks(), sp = n_sets * gf.P;
+        const size_t n_sets = coarse.run.n_sets, n_tracks = coarse.run.n_tracks(), sp = n_sets * w.gf.P;
         if ((rc = coarse.reserve(ctx))) return rc;
-        if (ensure(ctx, ctx->zoom_map, sizeof(long long) * n_sets * z.n_pos) || ensure(ctx, ctx->tzoom_e, 2 * n_sets * z.n_pos) ||
-            ensure(ctx, ctx->tzoom_total, sizeof(long long) * n_tracks * z.n_pos)) {
+        if (ensure(ctx, ctx->zoom_map, sizeof(long long) * n_sets * w.z.n_pos) || ensure(ctx, ctx->tzoom_e, 2 * n_sets * w.z.n_pos) ||
+            ensure(ctx, ctx->tzoom_total, sizeof(long long) * n_tracks * w.z.n_pos)) {
             char buf[400];
             snprintf(buf, sizeof(buf),
                      "the zoomed cell tracks' window maps [%zu stacks][%d x %d positions] (%.1f MB), steps (%.1f MB) and sums [%zu tracks] (%.1f MB) "
                      "do not fit in device memory: %s",
-                     n_sets, (int)z.side, (int)z.side, 8.0 * (double)n_sets * (double)z.n_pos / 1e6, 2.0 * (double)n_sets * (double)z.n_pos / 1e6,
-                     n_tracks, 8.0 * (double)n_tracks * (double)z.n_pos / 1e6, ctx->last_error.c_str());
+                     n_sets, (int)w.z.side, (int)w.z.side, 8.0 * (double)n_sets * (double)w.z.n_pos / 1e6, 2.0 * (double)n_sets * (double)w.z.n_pos / 1e6,
+                     n_tracks, 8.0 * (double)n_tracks * (double)w.z.n_pos / 1e6, ctx->last_error.c_str());
             return fail(ctx, TDOA_ERR_NOMEM, buf);
         }
-        if ((rc = ensure(ctx, ctx->zoom_part, sizeof(ClosureCand) * n_sets * z.tiles))) return rc;
+        if ((rc = ensure(ctx, ctx->zoom_part, sizeof(ClosureCand) * n_sets * w.z.tiles))) return rc;
         if ((rc = ensure(ctx, ctx->tzoom_centre, sizeof(int32_t) * n_sets))) return rc;
         if ((rc = ensure(ctx, ctx->tzoom_out, sizeof(CellTrackOut) * n_tracks))) return rc;
         if ((rc = ensure(ctx, ctx->tzoom_cells, sizeof(int32_t) * n_sets))) return rc;
@@ -106,8 +88,8 @@ struct LocateTrackZoomSearch : StackSearch {
         if ((rc = ensure(ctx, ctx->zoom_lags, sizeof(int32_t) * sp))) return rc;
         if ((rc = ensure(ctx, ctx->zoom_corr, sizeof(double) * sp))) return rc;
         rc = TDOA_OK;
-        track_zoom_steps_dispatch(z.side, [&](auto rows, auto cols) {
-            rc = set_lds(ctx, k_track_zoom_steps<decltype(rows)::value, decltype(cols)::value>, track_zoom_lds_bytes(z.n_pos));
+        track_zoom_steps_dispatch(w.z.side, [&](auto rows, auto cols) {
+            rc = set_lds(ctx, k_track_zoom_steps<decltype(rows)::value, decltype(cols)::value>, track_zoom_lds_bytes(w.z.n_pos));
         });
         return rc;
     }
@@ -117,19 +99,18 @@ struct LocateTrackZoomSearch : StackSearch {
     void launch(tdoa_ctx *ctx, const long long *Q, const double *roots) const override
     {
         coarse.launch(ctx, Q, roots);
-        const bool up = coarse.run.U > 1;
-        const int32_t *table = (up ? ctx->locate_fine_up : ctx->locate_fine).as<const int32_t>();
-        const long long *cdiff = coarse.clocks.get(up);
-        if (up) Q = ctx->locate_qu.as<const long long>();
+        const int32_t *table;
+        const long long *cdiff;
+        w.select(ctx, coarse, &table, &cdiff, &Q);
         const unsigned n_sets = (unsigned)coarse.run.n_sets, n_tracks = (unsigned)coarse.run.n_tracks();
         const LocateRound p = locate_run_round(ctx, coarse.run, 0);
         int32_t *centre = ctx->tzoom_centre.as<int32_t>();
         long long *zmap = ctx->zoom_map.as<long long>(), *total = ctx->tzoom_total.as<long long>();
         signed char *E = ctx->tzoom_e.as<signed char>();
-        const dim3 grid((unsigned)z.tiles, n_sets), block(kLocateThreads);
+        const dim3 grid((unsigned)w.z.tiles, n_sets), block(kLocateThreads);
         hipStream_t st = ctx->stream;
-        const LocateGeom g = gf;
-        const LocateZoomGeom zg = z;
+        const LocateGeom g = w.gf;
+        const LocateZoomGeom zg = w.z;
         const TrackZoomGeom tg = tz;
         hipLaunchKernelGGL(k_track_zoom_centres, dim3((n_sets + kLocateThreads - 1) / kLocateThreads), block, 0, st, tg,
                            static_cast<const int32_t *>(p.cells), static_cast<const CellTrackOut *>(p.track), centre);
@@ -150,15 +131,15 @@ struct LocateTrackZoomSearch : StackSearch {
     int download(tdoa_ctx *ctx) const override
     {
         hipStream_t st = ctx->stream;
-        const size_t n_sets = coarse.run.n_sets, n_tracks = coarse.run.n_tracks(), sp = n_sets * gf.P;
+        const size_t n_sets = coarse.run.n_sets, n_tracks = coarse.run.n_tracks(), sp = n_sets * w.gf.P;
         if (int rc = coarse.download(ctx)) return rc;
         HIPCHK(ctx, hipMemcpyAsync(o.track, ctx->tzoom_out.p, sizeof(CellTrackOut) * n_tracks, hipMemcpyDeviceToHost, st));
         if (o.cells) HIPCHK(ctx, hipMemcpyAsync(o.cells, ctx->tzoom_cells.p, sizeof(int32_t) * n_sets, hipMemcpyDeviceToHost, st));
         if (o.own) HIPCHK(ctx, hipMemcpyAsync(o.own, ctx->tzoom_own.p, sizeof(int64_t) * n_sets, hipMemcpyDeviceToHost, st));
         if (o.lags) HIPCHK(ctx, hipMemcpyAsync(o.lags, ctx->zoom_lags.p, sizeof(int32_t) * sp, hipMemcpyDeviceToHost, st));
         if (o.corr) HIPCHK(ctx, hipMemcpyAsync(o.corr, ctx->zoom_corr.p, sizeof(double) * sp, hipMemcpyDeviceToHost, st));
-        if (o.map) HIPCHK(ctx, hipMemcpyAsync(o.map, ctx->zoom_map.p, sizeof(int64_t) * n_sets * z.n_pos, hipMemcpyDeviceToHost, st));
-        if (o.total) HIPCHK(ctx, hipMemcpyAsync(o.total, ctx->tzoom_total.p, sizeof(int64_t) * n_tracks * z.n_pos, hipMemcpyDeviceToHost, st));
+        if (o.map) HIPCHK(ctx, hipMemcpyAsync(o.map, ctx->zoom_map.p, sizeof(int64_t) * n_sets * w.z.n_pos, hipMemcpyDeviceToHost, st));
+        if (o.total) HIPCHK(ctx, hipMemcpyAsync(o.total, ctx->tzoom_total.p, sizeof(int64_t) * n_tracks * w.z.n_pos, hipMemcpyDeviceToHost, st));
         return TDOA_OK;
     }
 };

@@ -24,27 +24,67 @@ int check_locate_fine(const tdoa_ctx *ctx, int S, const char **what)
     return TDOA_OK;
 }
 
-struct LocateZoomSearch : StackSearch {
-    LocateSearch coarse;
+// The window on the context's fine table that such a search scores behind its coarse run: what the zoom locate and the zoomed
+// cell tracks share of their arguments, geometry, key words and launches
+struct LocateFineWindow {
     int Z, H, sep;                           // fine cells per cell, the window's half side, fine_separation
-    LocateZoomHost o;
     LocateGeom gf{};                         // bind: the coarse run's geometry with the fine table's shape, fine_separation and the window's tiles
     LocateZoomGeom z{};
+
+    // between: what the holder refuses of an argument of its own that the entries name between H and fine_separation
+    const char *check_args(const char *between = nullptr) const
+    {
+        if (Z < 1 || Z > kLocateZoomMaxZ) return "Z outside 1 .. 64";
+        if (H < 0 || H > kLocateZoomMaxH) return "H outside 0 .. 64";
+        if (between) return between;
+        return sep < 1 ? "fine_separation < 1" : nullptr;
+    }
+    void bind(const tdoa_ctx *ctx, const LocateGeom &g)
+    {
+        z.Z = Z;
+        z.H = H;
+        z.side = 2 * H + 1;
+        z.n_pos = z.side * z.side;
+        z.coarse_cells = g.n_cells;
+        z.coarse_cols = g.n_cols;
+        z.tiles = (z.n_pos + kLocateThreads - 1) / kLocateThreads;
+        gf = g;                              // S, P and the lags (with U > 1 the fine ones) are the coarse run's
+        gf.n_cells = ctx->fine_cells;
+        gf.n_cols = ctx->fine_cols;
+        gf.sep = sep;
+        gf.tiles = z.tiles;
+    }
+    // the holder's kind, the window, the holder's word, the fine table's shape (its contents are data)
+    void key(std::vector<uint64_t> *key, uint64_t kind, uint64_t word) const
+    {
+        key->insert(key->end(), {kind, (uint64_t)Z | ((uint64_t)H << 32), word, (uint64_t)gf.n_cells | ((uint64_t)gf.n_cols << 32)});
+    }
+    // the (fine) table scale, clock differences and words the coarse run ran on
+    void select(const tdoa_ctx *ctx, const LocateSearch &coarse, const int32_t **table, const long long **cdiff, const long long **Q) const
+    {
+        const bool up = coarse.run.U > 1;
+        *table = (up ? ctx->locate_fine_up : ctx->locate_fine).as<const int32_t>();
+        *cdiff = coarse.clocks.get(up);
+        if (up) *Q = ctx->locate_qu.as<const long long>();
+    }
+};
+
+struct LocateZoomSearch : StackSearch {
+    LocateSearch coarse;
+    LocateFineWindow w;
+    LocateZoomHost o;
 
     LocateZoomSearch(int min_separation, int zoom, int half, int fine_separation, tdoa_location *loc, int32_t *lags, double *corr, int64_t *map,
                      const LocateZoomHost &host)
         : StackSearch("the zoom locate with TDOA_LAGS_GO", nullptr), coarse(locate_search_call(false, 1, 0, min_separation, loc, lags, corr, map)),
-          Z(zoom), H(half), sep(fine_separation), o(host)
+          w{zoom, half, fine_separation}, o(host)
     {
     }
     const char *check_args() const override
     {
         if (const char *bad = coarse.check_args()) return bad;
-        if (Z < 1 || Z > kLocateZoomMaxZ) return "Z outside 1 .. 64";
-        if (H < 0 || H > kLocateZoomMaxH) return "H outside 0 .. 64";
-        if (sep < 1) return "fine_separation < 1";
-        if (!o.zoom) return "zoom_host is NULL";
-        return nullptr;
+        if (const char *bad = w.check_args()) return bad;
+        return o.zoom ? nullptr : "zoom_host is NULL";
     }
     int check_fine(const tdoa_ctx *ctx, int S, const char **what) const { return check_locate_fine(ctx, S, what); }
     int check_state(const tdoa_ctx *ctx, int windows_per_stack, const char **what) const override
@@ -61,40 +101,27 @@ struct LocateZoomSearch : StackSearch {
     void bind(const tdoa_ctx *ctx, const SearchShape &sh) override
     {
         coarse.bind(ctx, sh);
-        const LocateGeom &g = coarse.run.g;
-        z.Z = Z;
-        z.H = H;
-        z.side = 2 * H + 1;
-        z.n_pos = z.side * z.side;
-        z.coarse_cells = g.n_cells;
-        z.coarse_cols = g.n_cols;
-        z.tiles = (z.n_pos + kLocateThreads - 1) / kLocateThreads;
-        gf = g;                              // S, P and the lags (with U > 1 the fine ones) are the coarse run's
-        gf.n_cells = ctx->fine_cells;
-        gf.n_cols = ctx->fine_cols;
-        gf.sep = sep;
-        gf.tiles = z.tiles;
+        w.bind(ctx, coarse.run.g);
     }
     // the window and the fine table's shape (its contents are data), then the locate's words
     void key(std::vector<uint64_t> *key, int m) const override
     {
-        key->insert(key->end(), {StepProduct::LocateZoom, (uint64_t)Z | ((uint64_t)H << 32), (uint64_t)sep,
-                                 (uint64_t)gf.n_cells | ((uint64_t)gf.n_cols << 32)});
+        w.key(key, StepProduct::LocateZoom, (uint64_t)w.sep);
         coarse.key(key, m);
     }
     // the locate's buffers, then the window maps, the tiles' candidates, the records, lags and correlations
     int reserve(tdoa_ctx *ctx) const override
     {
         int rc;
-        const size_t n_sets = coarse.run.n_sets, sp = n_sets * gf.P;
+        const size_t n_sets = coarse.run.n_sets, sp = n_sets * w.gf.P;
         if ((rc = coarse.reserve(ctx))) return rc;
-        if (ensure(ctx, ctx->zoom_map, sizeof(long long) * n_sets * z.n_pos)) {
+        if (ensure(ctx, ctx->zoom_map, sizeof(long long) * n_sets * w.z.n_pos)) {
             char buf[320];
             snprintf(buf, sizeof(buf), "the zoom locate's window maps [%zu stacks][%d x %d positions] (%.1f MB) do not fit in device memory: %s", n_sets,
-                     (int)z.side, (int)z.side, 8.0 * (double)n_sets * (double)z.n_pos / 1e6, ctx->last_error.c_str());
+                     (int)w.z.side, (int)w.z.side, 8.0 * (double)n_sets * (double)w.z.n_pos / 1e6, ctx->last_error.c_str());
             return fail(ctx, TDOA_ERR_NOMEM, buf);
         }
-        if ((rc = ensure(ctx, ctx->zoom_part, sizeof(ClosureCand) * n_sets * z.tiles))) return rc;
+        if ((rc = ensure(ctx, ctx->zoom_part, sizeof(ClosureCand) * n_sets * w.z.tiles))) return rc;
         if ((rc = ensure(ctx, ctx->zoom_out, sizeof(LocateZoomOut) * n_sets))) return rc;
         if ((rc = ensure(ctx, ctx->zoom_lags, sizeof(int32_t) * sp))) return rc;
         return ensure(ctx, ctx->zoom_corr, sizeof(double) * sp);
@@ -105,17 +132,16 @@ struct LocateZoomSearch : StackSearch {
     void launch(tdoa_ctx *ctx, const long long *Q, const double *roots) const override
     {
         coarse.launch(ctx, Q, roots);
-        const bool up = coarse.run.U > 1;
-        const int32_t *table = (up ? ctx->locate_fine_up : ctx->locate_fine).as<const int32_t>();
-        const long long *cdiff = coarse.clocks.get(up);
-        if (up) Q = ctx->locate_qu.as<const long long>();
+        const int32_t *table;
+        const long long *cdiff;
+        w.select(ctx, coarse, &table, &cdiff, &Q);
         const int32_t *best = ctx->locate_best.as<const int32_t>();
         long long *zmap = ctx->zoom_map.as<long long>();
         ClosureCand *part = ctx->zoom_part.as<ClosureCand>();
-        const dim3 grid((unsigned)z.tiles, (unsigned)coarse.run.n_sets), one((unsigned)coarse.run.n_sets), block(kLocateThreads);
+        const dim3 grid((unsigned)w.z.tiles, (unsigned)coarse.run.n_sets), one((unsigned)coarse.run.n_sets), block(kLocateThreads);
         hipStream_t st = ctx->stream;
-        const LocateGeom g = gf;
-        const LocateZoomGeom zg = z;
+        const LocateGeom g = w.gf;
+        const LocateZoomGeom zg = w.z;
         locate_scores_dispatch(g.S, kLocateRegStations, cdiff != nullptr, [&](auto s, auto clk) {
             hipLaunchKernelGGL((k_locate_zoom_scores<decltype(s)::value, decltype(clk)::value>), grid, block, 0, st, Q, g, zg, table, cdiff, best, zmap, part);
         });
@@ -126,12 +152,12 @@ struct LocateZoomSearch : StackSearch {
     int download(tdoa_ctx *ctx) const override
     {
         hipStream_t st = ctx->stream;
-        const size_t n_sets = coarse.run.n_sets, sp = n_sets * gf.P;
+        const size_t n_sets = coarse.run.n_sets, sp = n_sets * w.gf.P;
         if (int rc = coarse.download(ctx)) return rc;
         HIPCHK(ctx, hipMemcpyAsync(o.zoom, ctx->zoom_out.p, sizeof(LocateZoomOut) * n_sets, hipMemcpyDeviceToHost, st));
         if (o.lags) HIPCHK(ctx, hipMemcpyAsync(o.lags, ctx->zoom_lags.p, sizeof(int32_t) * sp, hipMemcpyDeviceToHost, st));
         if (o.corr) HIPCHK(ctx, hipMemcpyAsync(o.corr, ctx->zoom_corr.p, sizeof(double) * sp, hipMemcpyDeviceToHost, st));
-        if (o.map) HIPCHK(ctx, hipMemcpyAsync(o.map, ctx->zoom_map.p, sizeof(int64_t) * n_sets * z.n_pos, hipMemcpyDeviceToHost, st));
+        if (o.map) HIPCHK(ctx, hipMemcpyAsync(o.map, ctx->zoom_map.p, sizeof(int64_t) * n_sets * w.z.n_pos, hipMemcpyDeviceToHost, st));
         return TDOA_OK;
     }
 };

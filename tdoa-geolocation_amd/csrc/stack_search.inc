@@ -5,7 +5,10 @@
 //   caller's Q   debug_search_from_q: the caller's words in ctx->debug_q, sqrt(n_w) per set in ctx->debug_roots
 // A search is a StackSearch: its checks, its geometry and host-side inputs for a shape (bind), its graph-key words, its
 // buffers, its uploads, its launches and its download.  closure_api.inc, sync_api.inc, sync_drift_api.inc and locate_run.inc
-// hold one each, with the extern "C" entries that build it from their arguments and call one of the drivers.
+// hold one each, with the extern "C" entries that build it from their arguments and call one of the drivers.  A search may
+// hold others and compose their members: a refinement (sync_fine_api.inc, sync_drift_fine_api.inc, locate_zoom_api.inc,
+// locate_track_zoom_api.inc) holds the search it refines and launches behind it; the one chain (SyncChain, sync_locate_api.inc)
+// holds a fine clock stage and a locate stage and puts the clock link between their launches.
 // Included by tdoa_mi355x.hip after group_api.inc (the drivers call process_impl and the group's helpers) and before the
 // searches' files.
 

@@ -26,14 +26,7 @@ struct SyncLineFineSearch : StackSearch {
           coarse(gate, max_drift, drift_den, rounds, ref_delay, centre, host), U(factor), Rf(fine_rounds), o(fine)
     {
     }
-    const char *check_args() const override
-    {
-        if (const char *bad = coarse.check_args()) return bad;
-        if (!sync_fine_factor_ok(U)) return "U is not 2, 4, 8 or 16";
-        if (Rf < 0 || Rf > kSyncFineMaxRounds) return "fine_rounds outside 0 .. 16";
-        if (!o.fine) return "fine_host is NULL";
-        return nullptr;
-    }
+    const char *check_args() const override { const char *bad = coarse.check_args(); return bad ? bad : SyncFineSearch::check_fine_args(U, Rf, o.fine); }
     // a fine row in 1/16 sample must fit int32: the offset's window, the slope's window over the line, the roundings
     bool row_too_large(int S, int L) const
     {

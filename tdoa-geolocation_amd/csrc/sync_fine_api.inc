@@ -23,14 +23,14 @@ struct SyncFineSearch : StackSearch {
           coarse(gate, rounds, ref_delay, centre, host), U(factor), Rf(fine_rounds), o(fine)
     {
     }
-    const char *check_args() const override
+    // what a refinement refuses of its own arguments; the fine clock lines' too (sync_drift_fine_api.inc)
+    static const char *check_fine_args(int U, int Rf, const void *fine_host)
     {
-        if (const char *bad = coarse.check_args()) return bad;
         if (!sync_fine_factor_ok(U)) return "U is not 2, 4, 8 or 16";
         if (Rf < 0 || Rf > kSyncFineMaxRounds) return "fine_rounds outside 0 .. 16";
-        if (!o.fine) return "fine_host is NULL";
-        return nullptr;
+        return fine_host ? nullptr : "fine_host is NULL";
     }
+    const char *check_args() const override { const char *bad = coarse.check_args(); return bad ? bad : check_fine_args(U, Rf, o.fine); }
     // the clock in 1/16 sample must fit int32
     bool centre_too_large(int S) const
     {

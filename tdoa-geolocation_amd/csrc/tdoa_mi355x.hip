@@ -51,7 +51,6 @@
 #include "stack_sync_drift_fine.hpp"
 #include "stack_locate_zoom.hpp"
 #include "stack_locate_track_zoom.hpp"
-#include "stack_clock_mix.hpp"
 #include "stack_line_mix.hpp"
 
 using namespace tdoa;
@@ -235,14 +234,11 @@ struct tdoa_ctx {
     // [stack][(2H+1)^2][2], the sums F_0 [track][(2H+1)^2], the records [track], the fine cells and own scores [stack]; the
     // window maps, their tiles' candidates and the fine lags and correlations lie in the zoom locate's buffers
     DevBuf tzoom_centre, tzoom_e, tzoom_total, tzoom_out, tzoom_cells, tzoom_own;
-    // clocks to fix in one call (tdoa_process_sync_locate), between the fine clock search and the zoom locate: the mix [stack],
-    // the stacks' clock rows [stack][station] and their pairs' differences and U x them [stack][pair], which the zoom locate of
-    // that call takes where the others take locate_clock and locate_clock_up; tdoa_debug_clock_mix's clocks [stack][station]
+    // from reference blocks to fix in one call (tdoa_process_sync_locate, tdoa_process_sync_drift_locate), between the fine clock
+    // stage and the locate stage: the mix [stack] as line-mix entries, the stacks' clock rows [stack][station] and their pairs'
+    // differences and U x them [stack][pair], which the locate stage of those calls takes where the others take locate_clock and
+    // locate_clock_up; tdoa_debug_clock_mix's clocks [stack][station] or tdoa_debug_line_mix's clocks and rates [2][line][station]
     DevBuf mix_in, mix_rows, mix_cdiff, mix_cdiff_up, mix_debug;
-    // free-running clocks to fix in one call (tdoa_process_sync_drift_locate), between the fine clock lines and the zoomed cell
-    // tracks: the line mix [stack]; its rows and differences go where the clock mix's go, and tdoa_debug_line_mix's clocks and
-    // rates [2][line][station] into mix_debug
-    DevBuf lmix_in;
     size_t total_mem = 0;                  // of the device, 0: unknown
 };
 
@@ -613,7 +609,7 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->slfine_out, &ctx->slfine_clock, &ctx->slfine_rate, &ctx->slfine_rows, &ctx->slfine_lags, &ctx->slfine_corr,
                       &ctx->locate_fine, &ctx->locate_fine_up, &ctx->zoom_map, &ctx->zoom_part, &ctx->zoom_out, &ctx->zoom_lags, &ctx->zoom_corr,
                       &ctx->tzoom_centre, &ctx->tzoom_e, &ctx->tzoom_total, &ctx->tzoom_out, &ctx->tzoom_cells, &ctx->tzoom_own,
-                      &ctx->mix_in, &ctx->mix_rows, &ctx->mix_cdiff, &ctx->mix_cdiff_up, &ctx->mix_debug, &ctx->lmix_in};
+                      &ctx->mix_in, &ctx->mix_rows, &ctx->mix_cdiff, &ctx->mix_cdiff_up, &ctx->mix_debug};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -1344,7 +1340,8 @@ int tdoa_solve_surface(const double *stations_lle, int n_stations, const double 
 #include "exact_reference_api.inc"
 #include "group_api.inc"
 // The searches on the stacks' sums.  stack_search.inc's drivers call process_impl above and the group's helpers, which is why
-// it and the searches' files come last; a search's file needs nothing of another's but what its header names.
+// it and the searches' files come last; a search's file needs nothing of another's but what its header names.  The last one
+// chains two of the others (a fine clock stage, k_line_mix, a locate stage) for the two calls that go from reference blocks to fix.
 #include "stack_search.inc"
 #include "closure_api.inc"
 #include "map_stats_api.inc"
@@ -1357,4 +1354,3 @@ int tdoa_solve_surface(const double *stations_lle, int n_stations, const double 
 #include "sync_drift_api.inc"
 #include "sync_drift_fine_api.inc"
 #include "sync_locate_api.inc"
-#include "sync_drift_locate_api.inc"

@@ -1,5 +1,5 @@
 """The clock mix of tdoa_process_sync_locate (include/tdoa_mi355x.h, "clocks to fix in one call") in int64 numpy: what the GPU
-kernel (csrc/stack_clock_mix.hpp) and tdoa_clock_mix_rows are held to, byte for byte.  Tests use it; the library does not.
+kernel (csrc/stack_line_mix.hpp) and tdoa_clock_mix_rows are held to, byte for byte.  Tests use it; the library does not.
 
 clock16 [n][S] are the fine clock search's clocks in 1/16 sample.  A mix is [m][4] int32, one (a, b, wa, wb) per row:
 

@@ -5,7 +5,8 @@ Every comparison is byte for byte.
 
 1. debug_line_mix, the kernel alone, against line_mix.mix_rows: the corner list of tests/test_line_mix_cpu.py, 2, 3, 5 and 64
    stations (2 016 pairs: several passes of the workgroup), 1 and 7 lines, 1 and 300 rows, U 2 and 16, U_loc 1 and 16; the
-   differences are row[j] - row[i] in tdoa_locate_set_clock's pair order and the scaled ones exactly U_loc x them;
+   differences are row[j] - row[i] in tdoa_locate_set_clock's pair order and the scaled ones exactly U_loc x them; the same
+   kernel without rates (debug_clock_mix) against itself with rates at position zero and against clock_mix.mix_rows;
 2. the chain identity: process_sync_drift_fine, line_mix_rows, locate_set_clock, process_locate_track_zoom on one context, then
    the clock table forgotten and process_sync_drift_locate: the same twenty-six outputs, for three mixes, three upsample
    settings, two fine searches, two pairs of steps, one-window, two-window and whole-block stacks, with and without map
@@ -140,6 +141,36 @@ def test_debug_line_mix_is_the_numpy_statement(ctx, U, U_loc):
             _check_mix(c, c16, eta, U, Dd, mx, U_loc)
     clock16, rate, mix = random_cases(7, 300, U, 4)
     _check_mix(c, clock16, rate, U, 4, mix, U_loc)
+
+
+@pytest.mark.parametrize("U_loc", [1, 16])
+def test_the_kernel_in_its_clock_role_is_its_line_role_at_position_zero(ctx, U_loc):
+    """one kernel serves both calls: without rates it takes the clocks as they are, and a clock-mix entry (a, b, wa, wb) is the
+    line-mix entry (a, 0, b, 0, wa, wb), whatever the rates and U D.  2 stations: one pair; 3: the fewest with several; 64: the
+    whole LDS row and 2 016 pairs, more than the workgroup's 256 threads.  Clocks up to +-(2^31 - 16), every other source small."""
+    from tdoa_amd import clock_mix
+    c, _ = ctx
+    rng = np.random.default_rng(37 + U_loc)
+    for n_st in (2, 3, 64):
+        for n in (1, 7):
+            for m in (1, 300):
+                c16 = rng.integers(-(2 ** 31 - 16), 2 ** 31 - 15, size=(n, n_st)).astype(np.int32)
+                c16[::2] = rng.integers(-9, 10, size=c16[::2].shape)
+                rate = (rng.integers(1, MAX_RATE + 1, size=(n, n_st)) * rng.choice([-1, 1], size=(n, n_st))).astype(np.int32)
+                den = rng.integers(1, 65537, size=m)
+                den[::3] = rng.integers(1, 9, size=len(den[::3]))
+                wa = rng.integers(0, den + 1)
+                a, b, zero = rng.integers(0, n, size=m), rng.integers(0, n, size=m), np.zeros(m, dtype=np.int64)
+                narrow = np.stack([a, b, wa, den - wa], axis=1).astype(np.int32)
+                wide = np.stack([a, zero, b, zero, wa, den - wa], axis=1).astype(np.int32)
+                want = clock_mix.mix_rows(c16, narrow)
+                d = clock_mix.pair_differences(want)
+                as_clocks = c.debug_clock_mix(c16, narrow, U_loc)
+                for U, Dd in ((2, 1), (16, 7)):
+                    as_lines = c.debug_line_mix(c16, rate, U, Dd, wide, U_loc)
+                    for got in (as_clocks, as_lines):
+                        assert _same_bytes(got[0], want) and _same_bytes(got[1], d) and _same_bytes(got[2], U_loc * d)
+                    assert all(_same_bytes(x, y) for x, y in zip(as_clocks, as_lines))
 
 
 # ---- 2. the chain identity ----------------------------------------------------------------------------------------------
