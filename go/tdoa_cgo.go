@@ -457,6 +457,47 @@ func (g *gpuCorrelator) ProcessLocateZoom(windowsPerStack, minSeparation, z, h, 
 	return o, nil
 }
 
+// LocateMultiZoom is what ProcessLocateMultiZoom returns, every slice [round][stack][...]: the rounds' outputs exactly as
+// ProcessLocateMulti's (Loc, Lags, Corr), and per round and stack the zoom's record, its counts (pairs inside the range and
+// not excluded at the fine cell, pairs excluded there), its cell's lags (1/u sample with LocateSetUpsample) and signed
+// correlations, 0.0 for an excluded pair.
+type LocateMultiZoom struct {
+	Loc    []C.tdoa_location
+	Lags   []int32
+	Corr   []float64
+	Zoom   []C.tdoa_zoom
+	ZPairs []int32
+	ZLags  []int32
+	ZCorr  []float64
+}
+
+func newLocateMultiZoom(rounds, stacks, pairs int) *LocateMultiZoom {
+	n := rounds * stacks
+	return &LocateMultiZoom{Loc: make([]C.tdoa_location, n), Lags: make([]int32, n*pairs), Corr: make([]float64, n*pairs),
+		Zoom: make([]C.tdoa_zoom, n), ZPairs: make([]int32, 2*n), ZLags: make([]int32, n*pairs), ZCorr: make([]float64, n*pairs)}
+}
+
+// ProcessLocateMultiZoom is the header's "zoomed rounds": ProcessLocateMulti's rounds, then per round and stack the best of the
+// (2h+1)^2 cells of the fine table around z x that round's coarse cell under the mask the round ran under, in the same step.
+func (g *gpuCorrelator) ProcessLocateMultiZoom(windowsPerStack, nEmitters, guard, minSeparation, z, h, fineSeparation int) (*LocateMultiZoom, error) {
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(g.ctx, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs := int(C.tdoa_num_pairs(g.ctx))
+	if int(total)*pairs == 0 || nEmitters < 1 || nEmitters > 8 {
+		return nil, fmt.Errorf("tdoa_process_locate_multi_zoom: no stacks, fewer than two stations or nEmitters outside 1 .. 8")
+	}
+	o := newLocateMultiZoom(nEmitters, int(total), pairs)
+	if rc := C.tdoa_process_locate_multi_zoom(g.ctx, C.int(windowsPerStack), C.int(nEmitters), C.int(guard), C.int(minSeparation), C.int(z),
+		C.int(h), C.int(fineSeparation), &o.Loc[0], (*C.int32_t)(unsafe.Pointer(&o.Lags[0])), (*C.double)(unsafe.Pointer(&o.Corr[0])), nil,
+		&o.Zoom[0], (*C.int32_t)(unsafe.Pointer(&o.ZPairs[0])), (*C.int32_t)(unsafe.Pointer(&o.ZLags[0])),
+		(*C.double)(unsafe.Pointer(&o.ZCorr[0])), nil); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_process_locate_multi_zoom: %s", C.GoString(C.tdoa_last_error(g.ctx)))
+	}
+	return o, nil
+}
+
 // LocateUpsampleTaps returns the u phases' 16 taps at scale 2^15 (host only): the committed table the upsampler uses.
 func LocateUpsampleTaps(u int) ([]int32, error) {
 	if u < 1 || u > 16 {
@@ -864,6 +905,28 @@ func (g *Group) ProcessLocateZoom(windowsPerStack, minSeparation, z, h, fineSepa
 		&o.Loc[0], (*C.int32_t)(unsafe.Pointer(&o.Lags[0])), (*C.double)(unsafe.Pointer(&o.Corr[0])), nil,
 		&o.Zoom[0], (*C.int32_t)(unsafe.Pointer(&o.ZLags[0])), (*C.double)(unsafe.Pointer(&o.ZCorr[0])), nil); rc != C.TDOA_OK {
 		return nil, fmt.Errorf("tdoa_group_process_locate_zoom: %s", C.GoString(C.tdoa_group_last_error(g.g)))
+	}
+	return o, nil
+}
+
+// ProcessLocateMultiZoom is gpuCorrelator.ProcessLocateMultiZoom over the group: the members' fixed-point partial sums are
+// added on the host and searched on member 0, rounds and windows, the same bytes one context returns.
+func (g *Group) ProcessLocateMultiZoom(windowsPerStack, nEmitters, guard, minSeparation, z, h, fineSeparation int) (*LocateMultiZoom, error) {
+	m := C.tdoa_group_member(g.g, 0)
+	var perBlock, total C.int
+	if rc := C.tdoa_num_stacks(m, C.int(windowsPerStack), &perBlock, &total); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_num_stacks: %s", C.GoString(C.tdoa_strerror(rc)))
+	}
+	pairs := int(C.tdoa_num_pairs(m))
+	if int(total)*pairs == 0 || nEmitters < 1 || nEmitters > 8 {
+		return nil, fmt.Errorf("tdoa_group_process_locate_multi_zoom: no stacks, fewer than two stations or nEmitters outside 1 .. 8")
+	}
+	o := newLocateMultiZoom(nEmitters, int(total), pairs)
+	if rc := C.tdoa_group_process_locate_multi_zoom(g.g, C.int(windowsPerStack), C.int(nEmitters), C.int(guard), C.int(minSeparation), C.int(z),
+		C.int(h), C.int(fineSeparation), &o.Loc[0], (*C.int32_t)(unsafe.Pointer(&o.Lags[0])), (*C.double)(unsafe.Pointer(&o.Corr[0])), nil,
+		&o.Zoom[0], (*C.int32_t)(unsafe.Pointer(&o.ZPairs[0])), (*C.int32_t)(unsafe.Pointer(&o.ZLags[0])),
+		(*C.double)(unsafe.Pointer(&o.ZCorr[0])), nil); rc != C.TDOA_OK {
+		return nil, fmt.Errorf("tdoa_group_process_locate_multi_zoom: %s", C.GoString(C.tdoa_group_last_error(g.g)))
 	}
 	return o, nil
 }

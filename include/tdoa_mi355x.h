@@ -1072,7 +1072,7 @@ typedef struct {
  *     location's.  Whenever the brute-force best cell of the whole fine table (tdoa_process_locate with the fine table as the
  *     table) lies inside a stack's window, it is the zoom's cell, with the same score, lags and correlations.
  *   Scope: the rounds (tdoa_process_locate_multi) and the cell tracks are not zoomed by this call; the cell tracks have
- *     tdoa_process_locate_track_zoom.
+ *     tdoa_process_locate_track_zoom.  The rounds have tdoa_process_locate_multi_zoom.
  * Two kernels behind the locate's launches, in the same step graph: nothing goes through the host.  The graph's key is the
  * locate's words plus (Z, H, fine_separation, n_cells_f, n_cols_f).
  * TDOA_ERR_INVALID (tdoa_locate_set_fine_table): what tdoa_locate_set_table refuses. */
@@ -1095,6 +1095,57 @@ int tdoa_process_locate_zoom(tdoa_ctx *ctx, int windows_per_stack, int min_separ
 int tdoa_debug_locate_zoom_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int min_separation, int Z, int H,
                                   int fine_separation, tdoa_location *loc, int32_t *lags, double *corr, int64_t *map, tdoa_zoom *zoom,
                                   int32_t *zlags, double *zcorr, int64_t *zmap);
+
+/* Zoomed rounds: every emitter round refined on the fine table.  tdoa_process_locate_multi finds a weaker second or third
+ * emitter of a stack, but only to a coarse cell; the zoom locate refines a stack's first emitter only.  This call runs the
+ * rounds and, behind them in the same step graph, searches every round's best cell again on the context's fine table, under
+ * the mask that round ran under.  No table upload, no second call, nothing through the host.
+ *   The coarse stage is tdoa_process_locate_multi(windows_per_stack, n_emitters, guard, min_separation) unchanged, on the
+ *     context's table, clocks, upsample setting and statistics setting: the first four outputs are its bytes, and
+ *     tdoa_locate_last_stats returns what it returns after that call.  The zoom's maps are not judged.
+ *   The window of round r of stack s is the zoom locate's window of (2H + 1)^2 positions around Z x that round's coarse cell,
+ *     with the zoom's geometry and competing rule.
+ *   The mask is M_p^r, the one round r's coarse scores ran under: the score of a competing position is the sum over the pairs
+ *     of M_p^r[lag_p(fine cell)], so a pair whose lag lies within guard of a centre left by rounds 0 .. r - 1 counts 0, and so
+ *     does a pair outside the searched range.  The centres stay the coarse cells' lags: a round's fine cell adds nothing to E.
+ *     With the setting U > 1 everything runs on Q_U, U x the fine table, U x the clocks and U x guard, as the rounds do.
+ *     Round 0 has no mask: its outputs are tdoa_process_locate_zoom's.
+ *   The outputs are [round][stack][...].  zoom: the round's tdoa_zoom; pairs_in counts the pairs inside the range and not
+ *     excluded at the fine cell; n_best, the box and the runner-up are taken on the round's masked window scores.  zpairs:
+ *     (pairs_in, reserved), reserved the pairs inside the range but excluded at the fine cell.  zlags and zcorr: the fine
+ *     cell's lags in 1/U sample and signed correlations; a pair outside the range reports 0 and 0.0, an excluded pair reports
+ *     its lag and 0.0 (all bytes zero), so tdoa_solve_surface gives it no weight.  zmap: the window's masked scores, -1 where
+ *     a position does not compete.
+ *   The zero record: a round with the zero coarse record gets the zero tdoa_zoom, zero zpairs, zero lags and correlations and
+ *     a zmap of -1 throughout.  A window with no competing position, or whose largest masked score is 0, also gets the zero
+ *     record, zero zpairs, lags and correlations; its zmap still holds its scores.
+ *   What follows: n_emitters = 1 returns tdoa_process_locate_zoom's eight outputs and zpairs = (pairs_in, 0); round 0 of every
+ *     n_emitters is that call's.  With the fine table equal to the table and Z = 1, every round's fine cell, score_q,
+ *     pairs_in, reserved, lags and correlations are that round's coarse record's.
+ *   Scope: the track rounds (tdoa_process_locate_track_multi) are not zoomed, nor are rounds part of the two one-call chains
+ *     (tdoa_process_sync_locate, tdoa_process_sync_drift_locate); the masks come from the coarse cells, never from the fine
+ *     ones; there is no stop rule: every call runs n_emitters rounds.
+ * Two kernels behind the rounds' launches for any n_emitters, the round a grid dimension.  The graph's key is the rounds'
+ * words plus (Z, H, fine_separation, n_cells_f, n_cols_f) under a kind of its own.
+ * The refusals are tdoa_process_locate_multi's and tdoa_process_locate_zoom's, with their messages, and a NULL zoom_host
+ * (TDOA_ERR_INVALID).  TDOA_ERR_NOMEM: the window maps [n_emitters][n_stacks_total][(2H+1)^2] do not fit (they can reach
+ * 70 GB); tdoa_last_error gives the sizes. */
+int tdoa_process_locate_multi_zoom(tdoa_ctx *ctx, int windows_per_stack, int n_emitters, int guard, int min_separation, int Z, int H,
+                                   int fine_separation, tdoa_location *loc_host, int32_t *lags_host, double *corr_host,
+                                   int64_t *map_host /* tdoa_process_locate_multi's */,
+                                   tdoa_zoom *zoom_host   /* [n_emitters][n_stacks_total], required */,
+                                   int32_t *zpairs_host   /* [n_emitters][n_stacks_total][2], may be NULL */,
+                                   int32_t *zlags_host    /* [n_emitters][n_stacks_total][n_pairs], may be NULL */,
+                                   double  *zcorr_host    /* same shape, may be NULL */,
+                                   int64_t *zmap_host     /* [n_emitters][n_stacks_total][(2H+1)^2], may be NULL */);
+
+/* tests only: the same kernels on the caller's words, as tdoa_debug_locate_multi_from_q, with the context's table, fine table,
+ * clocks and settings; outputs as tdoa_process_locate_multi_zoom's with n_sets for n_stacks_total.  Refuses what that call and
+ * tdoa_debug_locate_multi_from_q refuse. */
+int tdoa_debug_locate_multi_zoom_from_q(tdoa_ctx *ctx, const int64_t *q, int n_sets, int n_stations, int n_w, int n_emitters, int guard,
+                                        int min_separation, int Z, int H, int fine_separation, tdoa_location *loc, int32_t *lags,
+                                        double *corr, int64_t *map, tdoa_zoom *zoom, int32_t *zpairs, int32_t *zlags, double *zcorr,
+                                        int64_t *zmap);
 
 /* Zoomed cell tracks: a block's track refined on the fine table.  The cell track exists for free-running receivers: every
  * stack of a block has its own clock row, so the block's windows can be summed map by map only, never lag by lag.  The zoom
@@ -1618,6 +1669,13 @@ int tdoa_group_locate_set_fine_table(tdoa_group *g, const int32_t *delay, int n_
 int tdoa_group_process_locate_zoom(tdoa_group *g, int windows_per_stack, int min_separation, int Z, int H, int fine_separation,
                                    tdoa_location *loc_host, int32_t *lags_host, double *corr_host, int64_t *map_host, tdoa_zoom *zoom_host,
                                    int32_t *zlags_host, double *zcorr_host, int64_t *zmap_host);
+
+/* tdoa_process_locate_multi_zoom over the members: the merged sum is searched on member 0, rounds and windows, and the same
+ * bytes go through the merged sum as a single context returns.  Errors as there. */
+int tdoa_group_process_locate_multi_zoom(tdoa_group *g, int windows_per_stack, int n_emitters, int guard, int min_separation, int Z, int H,
+                                         int fine_separation, tdoa_location *loc_host, int32_t *lags_host, double *corr_host,
+                                         int64_t *map_host, tdoa_zoom *zoom_host, int32_t *zpairs_host, int32_t *zlags_host,
+                                         double *zcorr_host, int64_t *zmap_host);
 
 /* tdoa_process_locate_track_zoom over the members: the merged sum is searched on member 0, coarse tracks and windows, and the
  * same bytes go through the merged sum as a single context returns.  Errors as there. */

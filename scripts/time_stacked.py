@@ -63,9 +63,16 @@ tdoa_process_sync_drift_locate(M, G, H, D, R, U, RF, forward mix, J, 1, Z, H, JF
 downloaded (name process_sync_drift_locate_RxC_JJ_Z_H_JF_G_H_D_R_U_RF[_upU]_ms: the fine lines' launches, one kernel for the rows
 and the zoomed tracks' launches in one step behind one accumulation), and the chain it replaces, timed as one unit (name
 sync_drift_locate_chain_...): tdoa_process_sync_drift_fine, tdoa_line_mix_rows on the host, tdoa_locate_set_clock and
-tdoa_process_locate_track_zoom.
+tdoa_process_locate_track_zoom.  `--emitters-zoom` adds, per `--locate` grid, `--emitters K[/GUARD]`, `--locate-zoom Z[/H]` and for
+U = 1 and every `--locate-upsample U`, three legs: tdoa_process_locate_multi_zoom(M, K, GUARD, 1, Z, H, 1) with the same grid at Z
+cells per cell as the fine table (name process_locate_multi_zoom_RxC_KK_GG_Z_H[_upU]_ms: the rounds' launches and two more kernels
+for any K; records, counts, lags and correlations of both stages downloaded, the maps left on the device),
+tdoa_process_locate_multi(M, K, GUARD, 1) on the coarse table (the `--emitters` leg, with U > 1 the name
+process_locate_multi_RxC_KK_GG_upU_ms) and tdoa_process_locate_multi(M, K, GUARD, 1) with that fine grid as the table (name
+process_locate_multi_fine_RxC_KK_GG_Z[_upU]_ms), the nearest brute force; the last is left out, with a message, where its K
+planes of maps do not fit the device.
 usage: scripts/time_stacked.py [--steps N] [--rounds R] [--stations S] [--stack M] [--drift H/D]... [--track J]...
-[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]... [--locate-upsample U]... [--sync-fine G/U[/R[/RF]]]... [--locate-zoom Z[/H]]... [--sync-drift-fine G/H/D/R/U/RF]... [--locate-track-zoom Z[/H[/JF]]]... [--sync-locate] [--sync-drift-locate] [--max-lag N]"""
+[--closure G]... [--locate ROWSxCOLS]... [--locate-track J]... [--emitters K[/GUARD]]... [--track-emitters K[/GUARD]]... [--map-stats R1,R2[/FOOT]] [--sync G[/R]]... [--sync-drift G/H[/D[/R]]]... [--locate-upsample U]... [--sync-fine G/U[/R[/RF]]]... [--locate-zoom Z[/H]]... [--sync-drift-fine G/H/D/R/U/RF]... [--locate-track-zoom Z[/H[/JF]]]... [--sync-locate] [--sync-drift-locate] [--emitters-zoom] [--max-lag N]"""
 import json
 import os
 import sys
@@ -96,7 +103,7 @@ def timed(fn, steps):
 
 def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(), syncs=(), locate_tracks=(), stack=0, emitters=(),
          track_emitters=(), map_stats=None, sync_drifts=(), upsamples=(), max_lag=20000, sync_fines=(), zooms=(), sync_drift_fines=(), track_zooms=(),
-         sync_locate=False, sync_drift_locate=False):
+         sync_locate=False, sync_drift_locate=False, emitters_zoom=False):
     c = tdoa_amd.Context(sample_rate=2e6, window_len=2_000_000, max_lag=max_lag)
     for s in range(stations):
         c.synth_capture(s, 66_666_666, ST[s % 3], TX, 0x5D0A0000 + s)
@@ -211,6 +218,31 @@ def main(steps, rounds, drifts=(), tracks=(), closures=(), stations=3, locates=(
         for K, guard in emitters:
             family("process_locate_multi_%dx%d_K%d_G%d_ms" % (rows, cols, K, guard), table, cols,
                    lambda K=K, guard=guard: c.process_locate_multi(stack, K, guard, 1))
+            for Z, H in zooms if emitters_zoom else ():
+                rows_f, cols_f = (rows - 1) * Z + 1, (cols - 1) * Z + 1
+                if rows_f * cols_f > 2 ** 22:
+                    raise SystemExit("--emitters-zoom: the fine grid of %d x %d cells has more than 2^22 cells" % (rows_f, cols_f))
+                fine = tdoa_amd.capi.locate_grid_table([ST[s % 3] for s in range(stations)], 41.10, -96.20, 0.3 / max(rows - 1, 1) / Z,
+                                                       0.4 / max(cols - 1, 1) / Z, rows_f, cols_f, 350.0, 2e6)
+                for U in [1] + list(upsamples):
+                    up = "_up%d" % U if U > 1 else ""
+                    family("process_locate_multi_zoom_%dx%d_K%d_G%d_%d_%d%s_ms" % (rows, cols, K, guard, Z, H, up), table, cols,
+                           lambda K=K, guard=guard, Z=Z, H=H: c.process_locate_multi_zoom(Z, H, stack, K, guard, 1, 1, want_zmap=False),
+                           U, fine, cols_f)
+                    if U > 1:
+                        family("process_locate_multi_%dx%d_K%d_G%d%s_ms" % (rows, cols, K, guard, up), table, cols,
+                               lambda K=K, guard=guard: c.process_locate_multi(stack, K, guard, 1), U)
+                    name = "process_locate_multi_fine_%dx%d_K%d_G%d_%d%s_ms" % (rows, cols, K, guard, Z, up)
+                    c.locate_set_clock(None)
+                    c.locate_set_table(fine, cols_f)
+                    c.locate_set_upsample(U)
+                    try:                                                 # its K planes of maps may not fit the device
+                        c.process_locate_multi(stack, K, guard, 1)
+                    except tdoa_amd.TdoaError as e:
+                        print("%s: left out: %s" % (name, e), file=sys.stderr)
+                    else:
+                        family(name, fine, cols_f, lambda K=K, guard=guard: c.process_locate_multi(stack, K, guard, 1), U)
+                    c.locate_set_upsample(1)
     for G, R in syncs:
         legs["process_sync_%d_%d_ms" % (G, R)] = lambda G=G, R=R: c.process_sync(ref, 0, G, R)
     for G, H, D, R in sync_drifts:
@@ -331,6 +363,9 @@ if __name__ == "__main__":
     sync_drift_locate = "--sync-drift-locate" in args
     if sync_drift_locate:
         args.remove("--sync-drift-locate")
+    emitters_zoom = "--emitters-zoom" in args
+    if emitters_zoom:
+        args.remove("--emitters-zoom")
     sync_drifts = []
     while "--sync-drift" in args:
         i = args.index("--sync-drift")
@@ -345,4 +380,4 @@ if __name__ == "__main__":
         del args[i:i + 2]
     main(opt["--steps"], opt["--rounds"], drifts, tracks, closures, opt["--stations"], locates, syncs, locate_tracks, opt["--stack"], emitters,
          track_emitters, map_stats, sync_drifts, upsamples, opt["--max-lag"], sync_fines, zooms, sync_drift_fines, track_zooms, sync_locate,
-         sync_drift_locate)
+         sync_drift_locate, emitters_zoom)

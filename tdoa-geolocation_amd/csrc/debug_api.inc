@@ -136,12 +136,14 @@ int tdoa_debug_poison_workspace(tdoa_ctx *ctx)
     // records are the delay-table search's again, and its fine table is state; the fine clock lines' table and candidates are
     // the clock-line search's again; the zoomed cell tracks' sums, records, cells and own scores are compared and copied -- their
     // centres and steps E, which are added to window positions, stay as they are; the mixed clock rows and their differences
-    // only enter lags that are checked against the range, every word written by k_line_mix before the locate stage reads it)
+    // only enter lags that are checked against the range, every word written by k_line_mix before the locate stage reads it;
+    // the zoomed rounds' counts are copied, and the rounds' records they take their windows' centres from are written by the
+    // rounds before them, a cell checked against the table's size)
     for (DevBuf *b : {&ctx->mix_rows, &ctx->mix_cdiff, &ctx->mix_cdiff_up, &ctx->tzoom_total, &ctx->tzoom_out, &ctx->tzoom_cells, &ctx->tzoom_own, &ctx->v, &ctx->tz, &ctx->fine_raw, &ctx->once_edges, &ctx->surf, &ctx->surf_out, &ctx->stack_q, &ctx->stack_surf,
                       &ctx->track_t, &ctx->closure_part, &ctx->closure_best, &ctx->closure_out, &ctx->locate_map, &ctx->locate_part,
                       &ctx->locate_best, &ctx->locate_out, &ctx->locate_lags, &ctx->locate_corr, &ctx->sline_cur, &ctx->sline_part,
                       &ctx->sline_out, &ctx->sline_rows, &ctx->sline_lags, &ctx->sline_corr, &ctx->locate_qu, &ctx->zoom_map, &ctx->zoom_part,
-                      &ctx->zoom_out, &ctx->zoom_lags, &ctx->zoom_corr, &ctx->slfine_cur, &ctx->slfine_part, &ctx->slfine_out,
+                      &ctx->zoom_out, &ctx->zoom_lags, &ctx->zoom_corr, &ctx->mzoom_pairs, &ctx->slfine_cur, &ctx->slfine_part, &ctx->slfine_out,
                       &ctx->slfine_rows, &ctx->slfine_lags, &ctx->slfine_corr})
         if (b->p && b->cap >= 4) HIPCHK(ctx, hipMemsetD32Async(static_cast<hipDeviceptr_t>(b->p), 0x7FC00000, b->cap / 4, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));

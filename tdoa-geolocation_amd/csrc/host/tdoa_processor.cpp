@@ -92,7 +92,7 @@ bool read_file(const std::string &path, std::vector<uint8_t> *out, std::string *
 
 void usage(const char *argv0)
 {
-    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--locate-upsample=U] [--locate-zoom=Z[/H[/SEP]]] [--locate-track-zoom=Z[/H[/JF[/SEP]]]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--sync-drift=H[/D]] [--sync-drift-fine=U[/RF]] [--sync-fine=U[/RF]] [--one-call] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
+    std::printf("Usage: %s [--fm] [--fine] [--stack[=WINDOWS]] [--drift=H[/D]] [--track=J] [--closure=G[/SEP]] [--locate=ROWSxCOLS/SPAN_KM] [--locate-track=J[/SEP]] [--emitters=K[/GUARD]] [--zoom-emitters] [--track-emitters=K[/GUARD]] [--map-stats=R1[,R2...][/FOOT]] [--locate-upsample=U] [--locate-zoom=Z[/H[/SEP]]] [--locate-track-zoom=Z[/H[/JF[/SEP]]]] [--sync=LAT,LON,HEIGHT[/G[/R]]] [--sync-drift=H[/D]] [--sync-drift-fine=U[/RF]] [--sync-fine=U[/RF]] [--one-call] [--gate SAMPLES] [--device N] [--window SAMPLES] [--max-lag SAMPLES] [--k1-smooth SAMPLES] [--k1-gate] "
                 "<ref_freq_hz> <target_freq_hz> <csv_file> <dat_file1> [dat_file2] [dat_file3] ...\n", argv0);
     std::printf("Example: %s 162400000 101700000 lat-lon-table.csv kx0u-data.dat n3pay-data.dat kf0mtl-data.dat\n", argv0);
 }
@@ -141,6 +141,9 @@ int main(int argc, char **argv)
     // fixes' lags counting 0 in every pair (tdoa_process_locate_multi)
     bool emitters = false;
     int emitters_k = 1, emitters_guard = 2;
+    // --zoom-emitters (with --emitters and --locate-zoom): the rounds and every round's window of the fine grid in one call
+    // (tdoa_process_locate_multi_zoom); an EMITTER-ZOOM line per round behind the LOCATE-MULTI lines, which keep their bytes
+    bool zoom_emitters = false;
     // --track-emitters=K[/GUARD] (with --stack --locate --locate-track): per block K tracks, each tracked with the lags within
     // GUARD of the earlier tracks' lags counting 0 in every stack's pairs (tdoa_process_locate_track_multi)
     bool track_emitters = false;
@@ -287,6 +290,8 @@ int main(int argc, char **argv)
                 return 1;
             }
         }
+        else if (a == "--zoom-emitters")
+            zoom_emitters = true;
         else if (a.rfind("--track-emitters=", 0) == 0) {
             track_emitters = true;
             const int got = std::sscanf(a.c_str() + 17, "%d/%d", &temitters_k, &temitters_guard);
@@ -342,6 +347,10 @@ int main(int argc, char **argv)
     if (locate && !stack) { std::fprintf(stderr, "--locate needs --stack\n"); return 1; }
     if (locate_track && !locate) { std::fprintf(stderr, "--locate-track needs --stack --locate\n"); return 1; }
     if (emitters && !locate) { std::fprintf(stderr, "--emitters needs --stack --locate\n"); return 1; }
+    if (zoom_emitters && (!emitters || !locate_zoom)) {
+        std::fprintf(stderr, "usage: --zoom-emitters needs --stack --locate=... --emitters=K[/GUARD] --locate-zoom=Z[/H[/SEP]]\n");
+        return 1;
+    }
     if (track_emitters && !locate_track) { std::fprintf(stderr, "--track-emitters needs --stack --locate --locate-track\n"); return 1; }
     if (map_stats && !locate) { std::fprintf(stderr, "--map-stats needs --stack --locate\n"); return 1; }
     if (locate_up != 1 && !locate) { std::fprintf(stderr, "--locate-upsample needs --stack --locate\n"); return 1; }
@@ -543,6 +552,8 @@ int main(int argc, char **argv)
         std::vector<int32_t> zt_cells;           // (tdoa_process_locate_track_zoom)
         int tzoom_cols = 1;                      // its fine grid's columns
         std::vector<tdoa_location> mlocs;        // --emitters: one record per round and stack (tdoa_process_locate_multi)
+        std::vector<tdoa_zoom> mzooms;           // --zoom-emitters: one more record and its counts per round and stack
+        std::vector<int32_t> mzpairs;            // (tdoa_process_locate_multi_zoom)
         std::vector<tdoa_cell_track> mtracks;    // --track-emitters: one record per round and block, a cell, its own score and the
         std::vector<int32_t> mt_cells, mt_pairs; // pairs' counts per round and stack (tdoa_process_locate_track_multi)
         std::vector<int64_t> mt_own;
@@ -740,7 +751,13 @@ int main(int argc, char **argv)
                 if (!(one_call && sync_fine) && (rc = last_stats(&lstats, locs.size()))) return die("tdoa_locate_last_stats", rc);
                 if (emitters) {
                     mlocs.resize((size_t)emitters_k * n_stacks);
-                    if ((rc = tdoa_process_locate_multi(ctx, stack_m, emitters_k, emitters_guard, 1, mlocs.data(), nullptr, nullptr, nullptr)))
+                    if (zoom_emitters) {         // the rounds' records are tdoa_process_locate_multi's bytes
+                        mzooms.resize(mlocs.size());
+                        mzpairs.resize(2 * mlocs.size());
+                        if ((rc = tdoa_process_locate_multi_zoom(ctx, stack_m, emitters_k, emitters_guard, 1, zoom_z, zoom_h, zoom_sep, mlocs.data(),
+                                                                 nullptr, nullptr, nullptr, mzooms.data(), mzpairs.data(), nullptr, nullptr, nullptr)))
+                            return die("tdoa_process_locate_multi_zoom", rc);
+                    } else if ((rc = tdoa_process_locate_multi(ctx, stack_m, emitters_k, emitters_guard, 1, mlocs.data(), nullptr, nullptr, nullptr)))
                         return die("tdoa_process_locate_multi", rc);
                     if ((rc = last_stats(&mstats, mlocs.size()))) return die("tdoa_locate_last_stats", rc);
                 }
@@ -922,6 +939,18 @@ int main(int argc, char **argv)
                             (int)sid / spb + 1, (int)sid % spb, r, cell, grid_lat0 + (l.cell / locate_cols) * grid_dlat,
                             grid_lon0 + (l.cell % locate_cols) * grid_dlon, (int)l.pairs_in, (int)l.reserved, l.score, l.runner_up);
                 print_stats(mstats, (size_t)r * n_stacks + sid);
+            }
+        // --zoom-emitters: every round's fine cell, the ZOOM line's fields and the pairs excluded there; cell=-1: none
+        for (size_t sid = 0; sid < mzooms.size() / (size_t)emitters_k; sid++)
+            for (int r = 0; r < emitters_k; r++) {
+                const size_t at = (size_t)r * n_stacks + sid;
+                const tdoa_zoom &z = mzooms[at];
+                const int cell = z.score_q > 0 ? (int)z.cell : -1;
+                std::printf("EMITTER-ZOOM block %d stack %d round %d: cell=%d lat=%.6f lon=%.6f pairs=%d score=%.6f best=%d rows=%d..%d cols=%d..%d "
+                            "runner=%.6f runner_cell=%d reserved=%d\n",
+                            (int)sid / spb + 1, (int)sid % spb, r, cell, grid_lat0 + (z.cell / zoom_cols) * grid_dlat / zoom_z,
+                            grid_lon0 + (z.cell % zoom_cols) * grid_dlon / zoom_z, (int)z.pairs_in, z.score, (int)z.n_best, (int)z.row_lo, (int)z.row_hi,
+                            (int)z.col_lo, (int)z.col_hi, z.runner_up, (int)z.runner_cell, (int)mzpairs[2 * at + 1]);
             }
         // --locate-track: the block's track, then its cell in every stack with the stack's own score there (on the stack's scale)
         for (size_t b = 0; b < ltracks.size(); b++) {

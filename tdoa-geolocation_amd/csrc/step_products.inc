@@ -36,7 +36,7 @@ struct StepView {
 
 // the product of one step; the numbers are the first word a product appends to the graph key
 struct StepProduct {
-    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6, Locate = 7, Sync = 8, SyncDrift = 9, SyncFine = 10, LocateZoom = 11, SyncDriftFine = 12, LocateTrackZoom = 13, SyncLocate = 14, SyncDriftLocate = 15 };
+    enum Kind { None = 0, Lags = 1, Peaks = 2, Stack = 3, StackDrift = 4, StackTrack = 5, Closure = 6, Locate = 7, Sync = 8, SyncDrift = 9, SyncFine = 10, LocateZoom = 11, SyncDriftFine = 12, LocateTrackZoom = 13, SyncLocate = 14, SyncDriftLocate = 15, LocateMultiZoom = 16 };
     virtual int reserve(const StepView &v) = 0;
     virtual void key(std::vector<uint64_t> *key) const = 0;
     virtual int upload(const StepView &) { return TDOA_OK; }

@@ -51,6 +51,7 @@
 #include "stack_sync_drift_fine.hpp"
 #include "stack_locate_zoom.hpp"
 #include "stack_locate_track_zoom.hpp"
+#include "stack_locate_multi_zoom.hpp"
 #include "stack_line_mix.hpp"
 
 using namespace tdoa;
@@ -234,6 +235,9 @@ struct tdoa_ctx {
     // [stack][(2H+1)^2][2], the sums F_0 [track][(2H+1)^2], the records [track], the fine cells and own scores [stack]; the
     // window maps, their tiles' candidates and the fine lags and correlations lie in the zoom locate's buffers
     DevBuf tzoom_centre, tzoom_e, tzoom_total, tzoom_out, tzoom_cells, tzoom_own;
+    // the zoomed rounds (tdoa_process_locate_multi_zoom), behind the rounds: the counts [round][stack][2]; the K planes of the
+    // window maps, their tiles' candidates, the records, the fine lags and correlations lie in the zoom locate's buffers
+    DevBuf mzoom_pairs;
     // from reference blocks to fix in one call (tdoa_process_sync_locate, tdoa_process_sync_drift_locate), between the fine clock
     // stage and the locate stage: the mix [stack] as line-mix entries, the stacks' clock rows [stack][station] and their pairs'
     // differences and U x them [stack][pair], which the locate stage of those calls takes where the others take locate_clock and
@@ -608,7 +612,7 @@ void tdoa_destroy(tdoa_ctx *ctx)
                       &ctx->slfine_cur, &ctx->slfine_kappa, &ctx->slfine_eta, &ctx->slfine_part, &ctx->slfine_moved, &ctx->slfine_start,
                       &ctx->slfine_out, &ctx->slfine_clock, &ctx->slfine_rate, &ctx->slfine_rows, &ctx->slfine_lags, &ctx->slfine_corr,
                       &ctx->locate_fine, &ctx->locate_fine_up, &ctx->zoom_map, &ctx->zoom_part, &ctx->zoom_out, &ctx->zoom_lags, &ctx->zoom_corr,
-                      &ctx->tzoom_centre, &ctx->tzoom_e, &ctx->tzoom_total, &ctx->tzoom_out, &ctx->tzoom_cells, &ctx->tzoom_own,
+                      &ctx->tzoom_centre, &ctx->tzoom_e, &ctx->tzoom_total, &ctx->tzoom_out, &ctx->tzoom_cells, &ctx->tzoom_own, &ctx->mzoom_pairs,
                       &ctx->mix_in, &ctx->mix_rows, &ctx->mix_cdiff, &ctx->mix_cdiff_up, &ctx->mix_debug};
     for (DevBuf *b : bufs) release(*b);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1348,6 +1352,7 @@ int tdoa_solve_surface(const double *stations_lle, int n_stations, const double 
 #include "locate_api.inc"
 #include "locate_run.inc"
 #include "locate_zoom_api.inc"
+#include "locate_multi_zoom_api.inc"
 #include "locate_track_zoom_api.inc"
 #include "sync_api.inc"
 #include "sync_fine_api.inc"

@@ -140,6 +140,7 @@ SYMBOLS = [
     "tdoa_debug_clock_mix",
     "tdoa_process_sync_drift_locate", "tdoa_group_process_sync_drift_locate", "tdoa_debug_sync_drift_locate_from_q",
     "tdoa_line_mix_rows", "tdoa_debug_line_mix",
+    "tdoa_process_locate_multi_zoom", "tdoa_group_process_locate_multi_zoom", "tdoa_debug_locate_multi_zoom_from_q",
 ]
 
 
@@ -238,11 +239,17 @@ TRACK_ZOOM_SEARCHES["sync_drift_locate"] = _Search(
     tuple(o._replace(key="loc_" + o.key) if o.key in ("lags", "corr") else o for o in TRACK_ZOOM_SEARCHES["locate_track_zoom"].outputs),
     _CLOCKS + ("mix",), track_len=True, stats="track", late_ints=TRACK_ZOOM_SEARCHES["locate_track_zoom"].ints, mix_width=6)
 
+# the zoomed rounds (tests pin TRACK_ZOOM_SEARCHES to its three names too): the rounds' four outputs and, [round][stack][...], the
+# zoom's with the counts behind the records
+MULTI_ZOOM_SEARCHES = {s.name: s for s in (
+    _Search("locate_multi_zoom", ("n_emitters", "guard", "min_separation", "Z", "H", "fine_separation"),
+            _rounds(_LOCATE_OUT + _ZOOM_OUT[:1] + (_Out("zpairs", np.int32, ("n_sets", 2), poison=True),) + _ZOOM_OUT[1:]), stats="loc"),
+)}
 
 
 def _search(name):
     """the record of search `name`, from any of the tables"""
-    for table in (SEARCHES, LATER_SEARCHES, TRACK_ZOOM_SEARCHES):
+    for table in (SEARCHES, LATER_SEARCHES, TRACK_ZOOM_SEARCHES, MULTI_ZOOM_SEARCHES):
         if name in table:
             return table[name]
     raise KeyError(name)
@@ -389,7 +396,7 @@ def load(build_if_missing=True):
     L.tdoa_debug_line_mix.argtypes = [vp, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, i32p, C.c_int, C.c_int, i32p, i64p, i64p]
     L.tdoa_debug_owned_runs.argtypes = [sz, sz, C.c_int64, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz), C.c_int,
                                         C.POINTER(C.c_int)]
-    for s in list(SEARCHES.values()) + list(LATER_SEARCHES.values()) + list(TRACK_ZOOM_SEARCHES.values()):
+    for s in list(SEARCHES.values()) + list(LATER_SEARCHES.values()) + list(TRACK_ZOOM_SEARCHES.values()) + list(MULTI_ZOOM_SEARCHES.values()):
         for route, entry in s.entries.items():
             getattr(L, entry).argtypes = _search_argtypes(s, route)
     _lib = L
@@ -549,8 +556,34 @@ class _LaterContextSearches:
                                               up.ctypes.data_as(i64p)))
         return rows, cdiff, up
 
+    def process_locate_multi_zoom(self, Z, H, windows_per_stack=0, n_emitters=1, guard=0, min_separation=1, fine_separation=1,
+                                  want_map=False, want_zmap=True):
+        """tdoa_process_locate_multi_zoom -> process_locate_multi's dict (the rounds' bytes) and, all [n_emitters][n_stacks][...],
+        {"zoom": ZOOM_DTYPE, "zpairs": [2] int32 (pairs_in, reserved), "zlags": [P] int32 (1/U sample), "zcorr": [P] float64, with
+        want_zmap "zmap": [(2H+1)^2] int64}: every round's coarse cell searched again on the (2H+1)^2-cell window of the fine
+        table around Z x that cell, under the mask the round ran under.  The z arrays are written over a poison pattern"""
+        return _process_search(self, self, "locate_multi_zoom", dict(
+            windows_per_stack=windows_per_stack, n_emitters=n_emitters, guard=guard, min_separation=min_separation, Z=Z, H=H,
+            fine_separation=fine_separation, want_map=want_map, want_zmap=want_zmap))
+
+    def locate_multi_zoom_from_q(self, q, n_stations, Z, H, n_w=1, n_emitters=1, guard=0, min_separation=1, fine_separation=1,
+                                 want_map=True, want_zmap=True):
+        """tdoa_debug_locate_multi_zoom_from_q: the rounds' and the zoomed rounds' kernels on the caller's words q
+        [n_sets][P][2 max_lag - 1] int64 (or one set) with the context's table, fine table and clocks -> what
+        process_locate_multi_zoom returns, n_sets for n_stacks"""
+        return self._from_q("locate_multi_zoom", q, n_stations, dict(
+            n_w=n_w, n_emitters=n_emitters, guard=guard, min_separation=min_separation, Z=Z, H=H, fine_separation=fine_separation,
+            want_map=want_map, want_zmap=want_zmap))
+
 
 class _LaterGroupSearches:
+    def process_locate_multi_zoom(self, Z, H, windows_per_stack=0, n_emitters=1, guard=0, min_separation=1, fine_separation=1,
+                                  want_map=False, want_zmap=True):
+        """tdoa_group_process_locate_multi_zoom -> Context.process_locate_multi_zoom's outputs, byte-identical to a single context's"""
+        return _process_search(self, self.member(0), "locate_multi_zoom", dict(
+            windows_per_stack=windows_per_stack, n_emitters=n_emitters, guard=guard, min_separation=min_separation, Z=Z, H=H,
+            fine_separation=fine_separation, want_map=want_map, want_zmap=want_zmap))
+
     def process_sync_drift_fine(self, ref_delay, windows_per_stack=0, gate=0, max_drift=0, drift_den=1, rounds=0, U=16, fine_rounds=2,
                                 centre=None):
         """tdoa_group_process_sync_drift_fine -> Context.process_sync_drift_fine's outputs, byte-identical to a single context's"""
